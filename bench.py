@@ -8,9 +8,18 @@ with token id and position resident on the GPU (one hipGraph replay per step).  
 (tinygpt_amd.synth, seed 1234; no checkpoint exists offline) and prompt ids are uniform — timing is
 data-independent; parity is established by tests/.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]                       (N > 1: spawns its own N replica processes)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: spawns its own N replica processes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W                            (the launcher's N processes are the replicas)
+
+A plain run does only what the headline needs: set up, one untimed prefill, W warm-up steps, the K timed steps, the
+result line (`value` = tokens/s, `ms_per_step` = one timed step).  `--full` adds everything else the line used to carry
+(best-of-3 prefill timing, `roofline`, `cpu_baseline`); without it those fields are null.
+`--dump-outputs DIR` (rank 0) writes what the timed call returned after its K steps, from seeded, run-independent inputs:
+  DIR/tokens.npy  float64 [K, batch]   the greedy token ids of the K timed steps (what tgx_decode hands its caller)
+  DIR/logits.npy  float32 [batch, V]   the fp32 logits of the last timed step (tgx_read_logits, unrounded)
+so that two builds can be compared output for output.  To hand the ids back, the timed call then also copies them to the
+host (one small device-to-host copy after the K steps, inside the timed region).
 
 N > 1 runs N independent replicas (one process per GPU, distinct prompt seeds, no data-path collective —
 the streams never exchange data).  Both invocation shapes work: under a launcher torch.distributed
@@ -18,7 +27,7 @@ the streams never exchange data).  Both invocation shapes work: 
 environment) `spawn_replicas` starts the N processes itself and a directory of small files carries the same two
 things (`FileGroup`) — replicas need no rendezvous service.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+Extra objects on the line (--full only):
   roofline     the dominant kernel class (gate_up GEMV: 55 % of a layer's bytes): algorithmic bytes per launch
                (2*N*K) / its average duration measured with HIP events on the launch stream
                (tgx_profile_decode: the class launched back-to-back over all layers); HBM peak 8.0 TB/s.
@@ -78,10 +87,14 @@ def parse():
                     "its hyper-parameters and weights replace the synthetic ones; `data` then reads \"checkpoint\"")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"], help="storage dtype of parameters and KV cache (the headline is bf16)")
     ap.add_argument("--prompt", type=int, default=2048, help="prefill length before the timed decode")
-    ap.add_argument("--profile-reps", type=int, default=8)
+    ap.add_argument("--profile-reps", type=int, default=8, help="(--full) repetitions of the per-class kernel profile behind `roofline`")
     ap.add_argument("--no-graph", action="store_true", help="eager launches (needed under rocprofv3 kernel tracing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the cpu_baseline leg")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(--full) target CPU time of the cpu_baseline sample")
+    ap.add_argument("--full", action="store_true", help="also measure the prefill (best of 3), the roofline figures and the CPU baseline; "
+                    "a plain run times the decode steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/tokens.npy and DIR/logits.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -335,7 +348,7 @@ def main():
     need_ctx = args.prompt + args.warmup + args.steps + 8
     if need_ctx > desc.max_ctx:
         sys.exit(f"prompt+warmup+steps = {need_ctx} exceeds contextSize {desc.max_ctx}")
-    want_cpu = world == 1 and not args.no_cpu_baseline              # only then is the checkpoint needed twice (GPU upload, then the CPU leg)
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline   # only then is the checkpoint needed twice (GPU upload, then the CPU leg)
     tensors = iter_checkpoint(args.model_dir) if args.model_dir else synth.synth_checkpoint(desc, 1234, 0.02)
     if want_cpu:
         tensors = list(tensors)                                       # otherwise streamed: one tensor in host memory at a time (6.4 GB x 8 ranks for config #5)
@@ -349,13 +362,15 @@ def main():
     prompt = synth.synth_prompt(desc.vocab, args.prompt, 1234 + rank)[None, :]
     model.forward(prompt)                                           # untimed: allocates the prefill workspace, warms the code objects
     model.synchronize()
-    prefill_ms = float("inf")
-    for _ in range(3):                                              # best of three (the clocks are still ramping in the first timed pass); config info,
-        model.reset_cache()                                         # not part of the timed decode region
-        t0 = time.perf_counter()
-        model.forward(prompt)
-        model.synchronize()
-        prefill_ms = min(prefill_ms, (time.perf_counter() - t0) * 1e3)
+    prefill_ms = None
+    if args.full:
+        prefill_ms = float("inf")
+        for _ in range(3):                                          # best of three (the clocks are still ramping in the first timed pass); config info,
+            model.reset_cache()                                     # not part of the timed decode region
+            t0 = time.perf_counter()
+            model.forward(prompt)
+            model.synchronize()
+            prefill_ms = min(prefill_ms, (time.perf_counter() - t0) * 1e3)
     model.sample(GREEDY)
     # the library switches attention forms at a context limit and re-captures its graphs when a decode call crosses it: keep the warm-up and
     # the timed region on the same form (the one beyond the limit) when the timed region would cross
@@ -369,18 +384,52 @@ def main():
         if torch.cuda.is_available():
             torch.cuda.synchronize()
 
+    dump = bool(args.dump_outputs) and rank == 0
+    ids = []
     model.decode(args.warmup, GREEDY, fetch=False)                  # untimed warm-up (instantiates the graph)
-    elapsed, _mine = timed_region(lambda: model.decode(args.steps, GREEDY, fetch=False), sync, group)   # EXACTLY K steps per rank
+    elapsed, _mine = timed_region(lambda: ids.append(model.decode(args.steps, GREEDY, fetch=dump)), sync, group)   # EXACTLY K steps per rank
 
     if rank != 0:
         if group: group.close()
         return
 
-    T0 = args.prompt + 1 + args.warmup                              # tokens in the cache at the first timed step
-    T_mean = T0 + (args.steps - 1) / 2.0
-    tok_s = aggregate_tokens_per_s(world, args.steps, elapsed)
-    bytes_tok = model.bytes_per_token(int(round(T_mean)))
+    if dump:                                                        # before anything else launches: the logits are the last timed step's
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), ids[0].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), model.logits(rounded=False).astype(np.float32))
 
+    T0 = args.prompt + 1 + args.warmup                              # tokens in the cache at the first timed step
+    tok_s = aggregate_tokens_per_s(world, args.steps, elapsed)
+    line = {
+        # BASELINE.json's metric string for the headline configuration; other --model / --dtype runs name themselves
+        "metric": ("decode tokens/sec (and % HBM roofline), Llama-3.2-1B bf16 batch=1, 1 GPU" if (args.model == "llama-3.2-1b" and args.dtype == "bf16")
+                   else f"decode tokens/sec (and % HBM roofline), {desc.name} {args.dtype} batch=1, 1 GPU"),
+        "value": round(tok_s, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.dtype, "data": "checkpoint" if args.model_dir else "synthetic", "full": args.full,
+        "config": {"workload": f"{desc.name} {args.dtype}, batch 1 per GPU: {args.prompt}-token prefill then greedy decode "
+                               f"(one step = one token, context {T0}..{T0 + args.steps - 1})",
+                   "replicas": world, "prompt_tokens": args.prompt,
+                   **(full_prefill_figures(desc, args, prefill_ms) if args.full else {}),
+                   "params": desc.param_count(), "graph": not args.no_graph},
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+    if args.full:
+        line["roofline"] = full_roofline(model, desc, args, world, tok_s, T0)
+        if want_cpu:
+            try:
+                line["cpu_baseline"] = cpu_baseline(desc, tensors, args.cpu_seconds, args.prompt, 1234)
+            except Exception as e:     # the GPU number stands on its own; say why the baseline is absent
+                line["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+    print(json.dumps(line), flush=True)
+    if group: group.close()
+
+
+def full_roofline(model, desc, args, world, tok_s, T0):
+    """--full: the roofline object of the line (a per-class kernel profile launched right after the timed region)"""
+    T_mean = T0 + (args.steps - 1) / 2.0
+    bytes_tok = model.bytes_per_token(int(round(T_mean)))
     prof = model.profile_decode(args.profile_reps)
     n_gu, ms_gu = prof["gateup"]
     gu_bytes = (4 if args.dtype == "fp32" else 2) * ((1 if desc.family == "gpt2" else 2) * desc.inter) * desc.hidden   # GPT-2: c_fc alone
@@ -420,14 +469,11 @@ def main():
                 "kernel_classes_avg_us": classes,
                 "step_bytes_per_token": bytes_tok, "step_achieved": round(bytes_tok * tok_s / world / 1e9, 1),
                 "step_frac": round(bytes_tok * tok_s / world / 1e9 / HBM_PEAK_GBS, 4)}
+    return roofline
 
-    cpu = None
-    if want_cpu:
-        try:
-            cpu = cpu_baseline(desc, tensors, args.cpu_seconds, args.prompt, 1234)
-        except Exception as e:     # the GPU number stands on its own; say why the baseline is absent
-            cpu = {"value": None, "unit": "tokens/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
 
+def full_prefill_figures(desc, args, prefill_ms):
+    """--full: the batched prefill's best-of-3 time and its rates (config fields of the line)"""
     # batched prefill (MFMA): algorithmic flops of the S x H·W^T products (one bf16 pass; the kernel issues two, hi and lo)
     L, H, I = desc.layers, desc.hidden, desc.inter
     gemm_flops = 2.0 * args.prompt * L * ((desc.q_dim + 2 * desc.kv_dim) * H + H * desc.q_dim + (2 if desc.family == "gpt2" else 3) * I * H)
@@ -440,25 +486,9 @@ def main():
     if args.dtype == "fp32":
         executed_flops = gemm_flops + attn_flops          # f32-input MFMA: one pass
     prefill_exec_tflops = executed_flops / (prefill_ms * 1e-3) / 1e12
-
-    line = {
-        # BASELINE.json's metric string for the headline configuration; other --model / --dtype runs name themselves
-        "metric": ("decode tokens/sec (and % HBM roofline), Llama-3.2-1B bf16 batch=1, 1 GPU" if (args.model == "llama-3.2-1b" and args.dtype == "bf16")
-                   else f"decode tokens/sec (and % HBM roofline), {desc.name} {args.dtype} batch=1, 1 GPU"),
-        "value": round(tok_s, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": args.dtype, "data": "checkpoint" if args.model_dir else "synthetic",
-        "config": {"workload": f"{desc.name} {args.dtype}, batch 1 per GPU: {args.prompt}-token prefill then greedy decode "
-                               f"(one step = one token, context {T0}..{T0 + args.steps - 1})",
-                   "replicas": world, "prompt_tokens": args.prompt, "prefill_ms": round(prefill_ms, 2),
-                   "prefill_tflops": round(prefill_tflops, 1), "prefill_frac_of_2500_algorithmic": round(prefill_tflops / 2500.0, 4),
-                   "prefill_tflops_executed": round(prefill_exec_tflops, 1), "prefill_frac_of_2500_executed": round(prefill_exec_tflops / 2500.0, 4),
-                   "params": desc.param_count(), "graph": not args.no_graph},
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-    }
-    print(json.dumps(line), flush=True)
-    if group: group.close()
+    return {"prefill_ms": round(prefill_ms, 2),
+            "prefill_tflops": round(prefill_tflops, 1), "prefill_frac_of_2500_algorithmic": round(prefill_tflops / 2500.0, 4),
+            "prefill_tflops_executed": round(prefill_exec_tflops, 1), "prefill_frac_of_2500_executed": round(prefill_exec_tflops / 2500.0, 4)}
 
 
 if __name__ == "__main__":

@@ -90,7 +90,7 @@ def test_bench_runs_a_model_directory_on_the_gpu(tmp_path):
     cfg, g = load_golden("llama_tiny")
     write_model_dir(str(tmp_path), cfg, int(g["seed"]), float(g["std"]), shards=2)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model-dir", str(tmp_path), "--prompt", "9", "--steps", "8", "--warmup", "2", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--model-dir", str(tmp_path), "--prompt", "9", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_two_replicas_through_the_launcher_on_a_shared_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", TGX_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "32", "--warmup", "8", "--model", "qwen2.5-0.5b", "--prompt", "64"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "32", "--warmup", "8", "--model", "qwen2.5-0.5b", "--prompt", "64", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -35,7 +35,7 @@ def test_bench_two_replicas_self_spawned_on_a_shared_gpu():
     """the plain `python3 bench.py --gpus 2` shape (no launcher, no WORLD_SIZE): bench.py spawns its replicas and a file rendezvous carries barrier + MAX"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TGX_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "32", "--warmup", "8", "--model", "qwen2.5-0.5b", "--prompt", "64"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "32", "--warmup", "8", "--model", "qwen2.5-0.5b", "--prompt", "64", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

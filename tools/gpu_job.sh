@@ -11,7 +11,7 @@ cd $R
 
 job_suite()   { (time timeout 2700 python -m pytest tests -m gpu -x -q) > $O/pytest.log 2>&1; tail -5 $O/pytest.log; }
 job_smoke()   { python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -2 $O/smoke.log; }
-job_bench()   { python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench_line.json; cut -c1-600 $O/bench_line.json; }
+job_bench()   { python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench_line.json; cut -c1-600 $O/bench_line.json; }
 job_quick()   { python tools/quick_bench.py --prompt 2048 --steps 256 ${QB_ARGS:-} > $O/quick.log 2>&1; cat $O/quick.log; }
 # the attention pair at the bench's operating point: splits per kv head x o_proj form (K-sliced with the merge in its prologue / combine + row-sliced)
 job_attn_pair() {
@@ -23,7 +23,7 @@ job_kernarg_probe() { for b in kernarg_probe kernarg_probe_pre; do echo "== $b";
 # rocprofv3 kernel trace of the bench command (eager launches: rocprofv3 cannot trace hipGraphLaunch) + the per-class sequence table
 job_trace() {
   cd /tmp; rm -rf /tmp/tr
-  rocprofv3 --kernel-trace --stats -d /tmp/tr -o tr -- python $R/bench.py --no-graph --no-cpu-baseline > $O/trace_bench.log 2>&1
+  rocprofv3 --kernel-trace --stats -d /tmp/tr -o tr -- python $R/bench.py --full --no-graph --no-cpu-baseline > $O/trace_bench.log 2>&1
   db=$(find /tmp/tr -name "*.db" | head -1)
   python $R/tools/rocpd_stats.py $db > $O/kernel_stats.txt 2>&1; python $R/tools/rocpd_seq.py $db >> $O/kernel_stats.txt 2>&1
   tail -1 $O/trace_bench.log >> $O/kernel_stats.txt; head -24 $O/kernel_stats.txt | cut -c1-200; cd $R
