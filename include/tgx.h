@@ -27,6 +27,7 @@ extern "C" {
 
 /* 3 (round 5): per-row sequence lifecycle (tgx_reset_row / tgx_forward_row / tgx_sample_row / tgx_past_length_row); tgx_get_option added and
  * tgx_engine_read_stats + the options engine.*, pf.*, attn.fold_*, lmhead.fuse_finalize removed since 2. */
+/* (round 7, still 3: additive) per-row sampler settings and device-side stop — tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -191,6 +192,36 @@ TGX_API int tgx_reset_row(tgx_ctx* ctx, int row);
 TGX_API int tgx_forward_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
 TGX_API int tgx_sample_row(tgx_ctx* ctx, int row, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_id);
 TGX_API int64_t tgx_past_length_row(const tgx_ctx* ctx, int row);
+
+/* ---- per-row sampler settings and device-side stop (additive to ABI 3) --------------------------------------------------------------------------------
+ * The request half of continuous batching: the reference's worker reconfigures its engine per request (engine_->reconfigure(samplerConfig, maxNewTokens,
+ * stopIds), server/HttpServer.cpp:118-163 -> src/engine/GPTEngine.cpp:67-84) and checks EOS per token (GPTEngine.cpp:196-217).  Here every row of the batch
+ * carries its own settings and stop conditions on the device, and tgx_decode_rows steps them together.
+ *
+ *   Draw identity     a row's ids and logits under tgx_decode_rows are bit-identical to tgx_decode with that row's cfg and seed applied to the whole batch
+ *                     (the draw keeps its hash of (seed, position, row)); rows that share the call do not change each other's results.
+ *   Counting          the token that finishes a row (a stop id, or the max_new-th token) is reported in out_ids and counted in out_new; for every row
+ *                     tgx_past_length_row after the call == its value before + out_new[row].
+ *   Finished row      keeps its length (and its cache rows [0, past), never rewritten) until tgx_reset_row.  It rides along in later steps the way a retired
+ *                     row does — no advance, it counts for neither tgx_past_length nor the context check — and its out_ids are -1.  One that finished at
+ *                     the context size has no row left to ride on: tgx_decode_rows returns TGX_ERR_CONTEXT until it is reset.
+ *   Calls             tgx_forward_row into a finished row needs tgx_reset_row first (TGX_ERR_STATE); tgx_decode_rows with no unfinished live row returns
+ *                     TGX_ERR_STATE; tgx_decode, tgx_step_async and tgx_forward return TGX_ERR_STATE while any row is finished (they would advance it).
+ *   Retired rows      (tgx_reset_row) ride along as in tgx_decode; their out_ids are -1, out_new and out_finish 0.  tgx_forward_row starts the row's count afresh.
+ *   Paged KV          blocks are assigned up front for past + n_steps; after the call a finished row's blocks beyond ceil(past / 128) go back to the pool.
+ *   tgx_read_probs    after tgx_decode_rows: each row's vector under its own cfg (greedy rows read as zeros).
+ *   Existing calls    tgx_decode, tgx_sample*, tgx_step_async ignore the row settings. */
+#define TGX_MAX_STOP_IDS 8
+/* The sampler settings of ONE row, used by tgx_decode_rows.  Kept across calls until changed; tgx_reset_row / tgx_reset_cache restore the default (greedy,
+ * seed 0, no stop conditions).  Takes effect for steps enqueued after the call, stream-ordered: no host synchronisation. */
+TGX_API int tgx_set_row_sampler(tgx_ctx* ctx, int row, const tgx_sampler_cfg* cfg, uint64_t seed);
+/* The stop conditions of ONE row for tgx_decode_rows: finish after max_new more produced tokens (<= 0: no limit), or as soon as the row produces one of
+ * stop_ids (n_stop <= TGX_MAX_STOP_IDS; 0 = none; a stop id takes precedence when both hold).  Resets the row's produced-token count.  Stream-ordered. */
+TGX_API int tgx_set_row_stop(tgx_ctx* ctx, int row, int32_t max_new, const int32_t* stop_ids, int n_stop);
+/* n_steps decode steps in which every live row samples with ITS OWN settings and may finish on the device.
+ * out_ids [n_steps][batch] (may be NULL): the produced ids, -1 for a row after it finished.  out_new [batch] (may be NULL): tokens produced per row in this
+ * call.  out_finish [batch] (may be NULL): 0 running, 1 stopped on a stop id, 2 reached max_new (the reference's FinishReason Stop / Length). */
+TGX_API int tgx_decode_rows(tgx_ctx* ctx, int n_steps, int64_t* out_ids, int32_t* out_new, int32_t* out_finish);
 
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);

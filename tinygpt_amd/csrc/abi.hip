@@ -224,7 +224,8 @@ static void launch_decode_step(tgx_ctx* c, const tgx_sampler_cfg& cfg) {
     const int rem = c->batch - row0, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
     launch_layers(c, row0, R);
     launch_lm_head(c, row0, R);
-    launch_sample(c, row0, R, cfg, /*advance_pos=*/true, /*log_step=*/true);
+    if (c->row_union >= 0) launch_sample_rows(c, row0, R, c->row_union);      // tgx_decode_rows: every row with its own settings
+    else launch_sample(c, row0, R, cfg, /*advance_pos=*/true, /*log_step=*/true);
     row0 += R;
   }
 }
@@ -269,7 +270,8 @@ static int ensure_step_graph(tgx_ctx* c, const tgx_sampler_cfg& cfg, bool want_m
   int hit = -1, victim = 0;
   for (int i = 0; i < 6; i++) {
     const tgx_ctx::GraphSet& g = c->graph_cache[i];
-    if (g.step && g.batch == c->batch && same_cfg(g.cfg, cfg) && g.direct == c->attn_direct && g.mfma == c->attn_mfma && g.nw4 == c->attn_nw4) { hit = i; break; }
+    if (g.step && g.batch == c->batch && g.rows == c->row_union && (c->row_union >= 0 || same_cfg(g.cfg, cfg)) && g.direct == c->attn_direct && g.mfma == c->attn_mfma &&
+        g.nw4 == c->attn_nw4) { hit = i; break; }
     if (!g.step) victim = i;
     else if (c->graph_cache[victim].step && g.used < c->graph_cache[victim].used) victim = i;
   }
@@ -284,7 +286,7 @@ static int ensure_step_graph(tgx_ctx* c, const tgx_sampler_cfg& cfg, bool want_m
     }
     int rc = capture_steps(c, cfg, 1, &g.step);
     if (rc) { g = tgx_ctx::GraphSet{}; return rc; }
-    g.batch = c->batch; g.cfg = cfg; g.direct = c->attn_direct; g.mfma = c->attn_mfma; g.nw4 = c->attn_nw4;
+    g.batch = c->batch; g.cfg = cfg; g.rows = c->row_union; g.direct = c->attn_direct; g.mfma = c->attn_mfma; g.nw4 = c->attn_nw4;
     g.used = ++c->graph_clock;
     hit = victim;
   }
@@ -333,6 +335,60 @@ static void kv_release_row(tgx_ctx* c, int row) {       // the row's blocks back
   kv_tbl_push(c, ch);
 }
 
+// paged KV: a finished row keeps the blocks its length needs; the ones assigned up front for the steps it did not take go back to the pool
+static void kv_trim_row(tgx_ctx* c, int row, long long tokens) {
+  if (!c->kv_paged) return;
+  const int keep = (int)((tokens + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK);
+  int& have = c->kv_row_nblk[(size_t)row];
+  std::vector<std::pair<int, int>> ch;
+  for (int b = keep; b < have; b++) { const int i = row * c->kv_tbl_stride + b; c->kv_free.push_back(c->kv_tbl_host[(size_t)i]); ch.emplace_back(i, 0); }
+  if (keep < have) have = keep;
+  kv_tbl_push(c, ch);
+}
+
+// ---- per-row request state (tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows): host-side fields travel BY VALUE in a one-thread launch, stream-ordered
+// behind the steps that still read the old ones (no stream drain, no host buffer that has to outlive the call).  what: ROWQ_* bits
+enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4 };
+struct RowReqUpdate { int row, what; tgx::RowReq v; };
+static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u) {
+  if (threadIdx.x != 0) return;
+  tgx::RowReq& q = req[u.row];
+  if (u.what & ROWQ_SAMPLER) { q.temperature = u.v.temperature; q.top_k = u.v.top_k; q.top_p = u.v.top_p; q.min_p = u.v.min_p; q.seed = u.v.seed; }
+  if (u.what & ROWQ_STOP) {
+    q.max_new = u.v.max_new; q.n_stop = u.v.n_stop;
+    for (int k = 0; k < tgx::ROW_MAX_STOP; k++) q.stop[k] = u.v.stop[k];
+    q.produced = 0;
+  }
+  if (u.what & ROWQ_STATE) { q.produced = 0; q.finished = 0; }
+}
+static_assert(tgx::ROW_MAX_STOP == TGX_MAX_STOP_IDS, "kernels/common.h RowReq");
+
+static tgx::RowReq row_req_default() {   // greedy, seed 0, no stop conditions
+  tgx::RowReq q{};
+  q.temperature = 0.f; q.top_k = 0; q.top_p = 1.f; q.min_p = 0.f; q.seed = 0; q.max_new = 0; q.n_stop = 0;
+  return q;
+}
+static void row_req_push(tgx_ctx* c, int row, int what) {
+  RowReqUpdate u{};
+  u.row = row; u.what = what; u.v = c->row_req_host[(size_t)row];
+  hipLaunchKernelGGL(row_req_set_kernel, dim3(1), dim3(64), 0, c->stream, c->row_req, u);
+}
+static void row_req_reset(tgx_ctx* c, int row) {   // tgx_reset_row: the default settings and a fresh state
+  c->row_req_host[(size_t)row] = row_req_default();
+  c->row_fin[(size_t)row] = 0;
+  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE);
+}
+static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
+  const tgx::RowReq& q = c->row_req_host[(size_t)row];
+  tgx_sampler_cfg s{};
+  s.temperature = q.temperature; s.top_k = q.top_k; s.top_p = q.top_p; s.min_p = q.min_p;
+  return s;
+}
+static int finished_row(const tgx_ctx* c) {   // a live row of the batch that finished on the device, or -1
+  for (int b = 0; b < c->batch; b++) if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b]) return b;
+  return -1;
+}
+
 // tgx_read_probs evaluates a row's final probabilities on demand: remember what its last sampled step was configured with
 static void note_sampled(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg) {
   if (c->row_probs_cfg.size() < (size_t)c->d.max_batch) { c->row_probs_cfg.resize((size_t)c->d.max_batch); c->row_probs_ok.assign((size_t)c->d.max_batch, 0); }
@@ -342,11 +398,16 @@ static void note_sampled(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg
   for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_probs_ok[(size_t)b];
 }
 
+// rows mode (c->row_union >= 0, tgx_decode_rows): every row samples with its own settings, `cfg` and `seed` are unused, finished rows take no blocks and stay
+// where they are, and the caller updates row_past from the device afterwards (rows may finish on the device)
 static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t seed, int n) {
+  const bool rows = c->row_union >= 0;
   if (c->kv_paged)       // every live row's next n positions have a block before the steps that write them are enqueued
     for (int b = 0; b < c->batch; b++)
-      if (!c->row_idle[(size_t)b]) { int rc = kv_ensure_blocks(c, b, c->row_past[(size_t)b] + n); if (rc) return rc; }
-  if (!is_greedy(&cfg)) {
+      if (!c->row_idle[(size_t)b] && !c->row_fin[(size_t)b]) { int rc = kv_ensure_blocks(c, b, c->row_past[(size_t)b] + n); if (rc) return rc; }
+  if (rows) {
+    for (int b = 0; b < c->batch; b++) note_sampled(c, b, 1, row_cfg(c, b));
+  } else if (!is_greedy(&cfg)) {
     // the engine passes one seed for a whole generation (the draw mixes in position and row): only a CHANGED seed is copied — and that
     // copy must drain the stream, because steps already enqueued still read the old word.  With an unchanged seed tgx_step_async returns
     // without waiting for the previous step (the one-step lookahead of generateAsync, GPTEngine.cpp:196-217)
@@ -357,7 +418,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
       c->seed_on_dev = s; c->seed_valid = true;
     }
   }
-  note_sampled(c, 0, c->batch, cfg);
+  if (!rows) note_sampled(c, 0, c->batch, cfg);
   if (decode_mfma_ok(c)) {   // the batched step's workspace must exist before the step is captured
     int rc = ensure_skinny_ws(c, std::min(c->decode_step_rows, c->batch));
     if (rc) return rc;
@@ -369,6 +430,10 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
       HIP_OK(c, hipMemsetAsync(c->rows[(size_t)b].pos, 0, 4, c->stream));
       c->row_past[(size_t)b] = 0;
     }
+  // a finished row rides at its own length (it does not count for `past`): the attention form is chosen for it as well when it is the longest
+  if (rows)
+    for (int b = 0; b < c->batch; b++)
+      if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b]) c->past = std::max(c->past, c->row_past[(size_t)b]);
   // The attention form depends on the context (four-wave direct / sixteen-wave direct / split + combine / matrix cores): a call that crosses a limit is
   // issued in chunks, each on the form of its own contexts, from the cache of captured graphs
   int remaining = n;
@@ -394,7 +459,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
       LAUNCH_OK(c);
     }
     c->past += m;
-    for (int b = 0; b < c->batch; b++) c->row_past[(size_t)b] += m;
+    if (!rows) for (int b = 0; b < c->batch; b++) c->row_past[(size_t)b] += m;
     c->steps_issued += m;
     remaining -= m;
   }
@@ -696,6 +761,10 @@ int tgx_finalize(tgx_ctx* c) {
   // fixed-point accumulators of the K-sliced o_proj (kernels/oproj_sliced.h): zero between layers
   if ((rc = dev_alloc(c, &c->slab_acc, B * (size_t)H))) return rc;
   HIP_OK(c, hipMemset(c->slab_acc, 0, B * (size_t)H * 8));
+  c->row_req_host.assign(B, row_req_default());
+  c->row_fin.assign(B, 0);
+  if ((rc = dev_alloc(c, &c->row_req, B))) return rc;
+  HIP_OK(c, hipMemcpy(c->row_req, c->row_req_host.data(), B * sizeof(tgx::RowReq), hipMemcpyHostToDevice));
   c->past = 0;
   c->row_past.assign(B, 0);
   c->row_tok.assign(B, 0);
@@ -711,7 +780,7 @@ void tgx_destroy(tgx_ctx* c) {
   drop_step_graphs(c);
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(c->embed); fr(c->lm_head); fr(c->final_norm); fr(c->wpe); fr(c->final_norm_b); fr(c->rope_cos); fr(c->rope_sin); fr(c->step); fr(c->step_done); fr(c->tok_log); fr(c->scratch_x); fr(c->seed_dev); fr(c->samp_scratch); fr(c->samp_list_comp); fr(c->samp_list_v);
-  fr(c->slab_acc); fr(c->kv_tbl);
+  fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req);
   fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
   fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_part); fr(c->ws_ssq); fr(c->ws_pos);
   for (auto& w : c->L) { fr(w.in_norm); fr(w.post_norm); fr(w.wqkv); fr(w.bqkv); fr(w.wo); fr(w.q_norm); fr(w.k_norm); fr(w.wgu); fr(w.wdown); fr(w.in_norm_b); fr(w.post_norm_b); fr(w.bo); fr(w.bfc); fr(w.bdown); }
@@ -730,6 +799,7 @@ int tgx_forward(tgx_ctx* c, const int64_t* ids, int batch, int seq) {
   if (batch < 1 || batch > c->d.max_batch || seq < 1) return set_err(c, TGX_ERR_INVALID, "batch/seq out of range");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   if (seq > 1 && c->past > 0) return set_err(c, TGX_ERR_INVALID, "seq>1 with pastLength>0");
+  if (finished_row(c) >= 0) return set_err(c, TGX_ERR_STATE, "row %d finished in tgx_decode_rows: tgx_reset_row it (or tgx_reset_cache) first", finished_row(c));
   if (c->past + seq > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, seq, c->d.max_ctx);
   for (int b = 0; b < batch; b++)
     if (c->row_idle[(size_t)b] || c->row_past[(size_t)b] != c->past) return set_err(c, TGX_ERR_STATE, "tgx_forward on a batch whose rows differ in length (row %d: %lld, longest %lld): use tgx_decode / tgx_forward_row, or tgx_reset_cache", b, (long long)c->row_past[(size_t)b], (long long)c->past);
@@ -839,6 +909,7 @@ int tgx_decode(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int n_step
   if (!c || !cfg || n_steps < 0) return TGX_ERR_INVALID;
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   if (!c->have_token) return set_err(c, TGX_ERR_STATE, "decode needs a current token: call tgx_sample after tgx_forward");
+  if (finished_row(c) >= 0) return set_err(c, TGX_ERR_STATE, "row %d finished in tgx_decode_rows: tgx_reset_row it first (tgx_decode would advance it)", finished_row(c));
   if (c->past + n_steps > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, n_steps, c->d.max_ctx);
   if (n_steps > c->log_cap) return set_err(c, TGX_ERR_INVALID, "n_steps exceeds the token log capacity %d", c->log_cap);
   HIP_OK(c, hipSetDevice(c->device));
@@ -865,6 +936,7 @@ int tgx_step_async(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int64_
   if (!c || !cfg || !out_ticket) return TGX_ERR_INVALID;
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   if (!c->have_token) return set_err(c, TGX_ERR_STATE, "step needs a current token: call tgx_sample after tgx_forward");
+  if (finished_row(c) >= 0) return set_err(c, TGX_ERR_STATE, "row %d finished in tgx_decode_rows: tgx_reset_row it first (tgx_step_async would advance it)", finished_row(c));
   if (c->past + 1 > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded");
   HIP_OK(c, hipSetDevice(c->device));
   int rc = run_decode_steps(c, *cfg, seed, 1);
@@ -892,6 +964,9 @@ int tgx_reset_cache(tgx_ctx* c) {
   HIP_OK(c, hipSetDevice(c->device));
   for (auto& r : c->rows) HIP_OK(c, hipMemsetAsync(r.pos, 0, 4, c->stream));
   for (int b = 0; b < c->d.max_batch; b++) kv_release_row(c, b);
+  std::fill(c->row_req_host.begin(), c->row_req_host.end(), row_req_default());
+  std::fill(c->row_fin.begin(), c->row_fin.end(), 0);
+  HIP_OK(c, hipMemcpyAsync(c->row_req, c->row_req_host.data(), c->row_req_host.size() * sizeof(tgx::RowReq), hipMemcpyHostToDevice, c->stream));   // (synchronised below)
   if (c->slab_acc) HIP_OK(c, hipMemsetAsync(c->slab_acc, 0, (size_t)c->d.max_batch * c->d.hidden * 8, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->past = 0;
@@ -914,7 +989,7 @@ static void refresh_longest(tgx_ctx* c) {
   int live = 0;
   bool all = true;
   for (int b = 0; b < c->batch; b++) {
-    if (c->row_idle[(size_t)b]) continue;
+    if (c->row_idle[(size_t)b] || c->row_fin[(size_t)b]) continue;      // (a finished row counts for neither, include/tgx.h tgx_decode_rows)
     live++;
     m = std::max(m, c->row_past[(size_t)b]);
     all = all && c->row_tok[(size_t)b];
@@ -936,6 +1011,7 @@ int tgx_reset_row(tgx_ctx* c, int row) {
   HIP_OK(c, hipSetDevice(c->device));
   HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream));     // stream-ordered behind the steps already enqueued
   kv_release_row(c, row);                                                     // paged KV: its blocks go back to the pool (a retired row rides along on the scratch block)
+  row_req_reset(c, row);                                                      // tgx_decode_rows: default settings, not finished
   c->row_past[(size_t)row] = 0;
   c->row_tok[(size_t)row] = 0;
   c->row_idle[(size_t)row] = row < c->batch;                                  // a live slot becomes a retired one: the batch keeps stepping without it
@@ -949,7 +1025,8 @@ int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   if (row < 0 || row >= c->d.max_batch || row > c->batch) return set_err(c, TGX_ERR_INVALID, "row %d: a live row [0,%d) or the next free one (max_batch %d)", row, c->batch, c->d.max_batch);
   if (seq < 1 || seq > c->d.max_ctx) return set_err(c, seq < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "seq %d out of range (context size %d)", seq, c->d.max_ctx);
-  if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0) return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions: tgx_reset_row first", row, (long long)c->row_past[(size_t)row]);
+  if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
+    return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
   for (int i = 0; i < seq; i++)
     if (ids[i] < 0 || ids[i] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
   HIP_OK(c, hipSetDevice(c->device));
@@ -1001,6 +1078,8 @@ int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   LAUNCH_OK(c);
   HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` may be pageable and reused by the caller
   c->batch = std::max(batch_before, row + 1);
+  row_req_push(c, row, ROWQ_STATE);       // a new sequence: what the slot counted while it rode along retired is gone (its settings stay)
+  c->row_fin[(size_t)row] = 0;
   c->row_past[(size_t)row] = seq;
   c->row_tok[(size_t)row] = 0;
   c->row_idle[(size_t)row] = 0;
@@ -1035,6 +1114,89 @@ int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t see
   refresh_longest(c);
   return TGX_OK;
 }
+// ---- per-row sampler settings and device-side stop (include/tgx.h tgx_decode_rows) ----------------------------------------------------------------------
+int tgx_set_row_sampler(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t seed) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!cfg) return set_err(c, TGX_ERR_INVALID, "null sampler configuration");
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_sampler before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  HIP_OK(c, hipSetDevice(c->device));
+  tgx::RowReq& q = c->row_req_host[(size_t)row];
+  q.temperature = cfg->temperature; q.top_k = cfg->top_k; q.top_p = cfg->top_p; q.min_p = cfg->min_p; q.seed = seed;
+  row_req_push(c, row, ROWQ_SAMPLER);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+int tgx_set_row_stop(tgx_ctx* c, int row, int32_t max_new, const int32_t* stop_ids, int n_stop) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_stop before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (n_stop < 0 || n_stop > TGX_MAX_STOP_IDS) return set_err(c, TGX_ERR_INVALID, "n_stop %d out of range [0,%d]", n_stop, TGX_MAX_STOP_IDS);
+  if (n_stop > 0 && !stop_ids) return set_err(c, TGX_ERR_INVALID, "null stop_ids with n_stop %d", n_stop);
+  HIP_OK(c, hipSetDevice(c->device));
+  tgx::RowReq& q = c->row_req_host[(size_t)row];
+  q.max_new = max_new; q.n_stop = n_stop;
+  for (int k = 0; k < TGX_MAX_STOP_IDS; k++) q.stop[k] = k < n_stop ? stop_ids[k] : -1;
+  row_req_push(c, row, ROWQ_STOP);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new, int32_t* out_finish) {
+  if (!c) return TGX_ERR_INVALID;
+  if (n_steps < 0) return set_err(c, TGX_ERR_INVALID, "n_steps %d < 0", n_steps);
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "decode before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  int running = 0;
+  for (int b = 0; b < c->batch; b++) running += !c->row_idle[(size_t)b] && !c->row_fin[(size_t)b];
+  if (!running) return set_err(c, TGX_ERR_STATE, "tgx_decode_rows: no live row is unfinished (tgx_reset_row / tgx_forward_row a row first)");
+  if (!c->have_token) return set_err(c, TGX_ERR_STATE, "decode needs a current token: call tgx_sample / tgx_sample_row after the forward");
+  if (c->past + n_steps > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, n_steps, c->d.max_ctx);
+  for (int b = 0; b < c->batch; b++)      // a finished row rides at its own length: one that holds the whole context has no row left to ride on
+    if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b] && c->row_past[(size_t)b] >= c->d.max_ctx)
+      return set_err(c, TGX_ERR_CONTEXT, "row %d finished at the context size %d: tgx_reset_row it first", b, c->d.max_ctx);
+  if (n_steps > c->log_cap) return set_err(c, TGX_ERR_INVALID, "n_steps exceeds the token log capacity %d", c->log_cap);
+  HIP_OK(c, hipSetDevice(c->device));
+  const size_t B = (size_t)c->batch;
+  const std::vector<int64_t> before(c->row_past.begin(), c->row_past.begin() + (long)B);
+  const int64_t start = c->steps_issued;
+  int rc = TGX_OK;
+  if (n_steps > 0) {
+    c->row_union = row_union_of(c);
+    rc = run_decode_steps(c, tgx_sampler_cfg{0.f, 0, 1.f, 0.f}, 0, n_steps);
+    c->row_union = -1;
+  }
+  if (rc) { refresh_longest(c); return rc; }
+  c->have_logits = true;
+  // one readback behind the steps: the ids of the call, every row's position and request state
+  std::vector<int> ids((size_t)n_steps * B), pos(B);
+  std::vector<tgx::RowReq> req(B);
+  if (n_steps > 0) {
+    const int64_t s0 = start % c->log_cap;
+    const int64_t first = (s0 + n_steps <= c->log_cap) ? n_steps : c->log_cap - s0;
+    HIP_OK(c, hipMemcpyAsync(ids.data(), c->tok_log + (size_t)s0 * B, (size_t)first * B * 4, hipMemcpyDeviceToHost, c->stream));
+    if (first < n_steps)
+      HIP_OK(c, hipMemcpyAsync(ids.data() + (size_t)first * B, c->tok_log, (size_t)(n_steps - first) * B * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_OK(c, hipMemcpyAsync(pos.data(), c->slab_pos, B * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipMemcpyAsync(req.data(), c->row_req, B * sizeof(tgx::RowReq), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b < B; b++) {
+    const bool idle = c->row_idle[b];
+    c->row_past[b] = pos[b];                              // a row advanced once per token it produced (retired rows: wherever their ride took them)
+    c->row_fin[b] = idle ? 0 : (char)req[b].finished;
+    if (out_new) out_new[b] = idle ? 0 : (int32_t)(pos[b] - before[b]);
+    if (out_finish) out_finish[b] = idle ? 0 : req[b].finished;
+    if (c->row_fin[b]) kv_trim_row(c, (int)b, c->row_past[b]);
+  }
+  if (out_ids)
+    for (size_t i = 0; i < ids.size(); i++) out_ids[i] = c->row_idle[i % B] ? -1 : ids[i];
+  if (n_steps > 0) c->last_sampled0 = ids[(size_t)(n_steps - 1) * B];
+  refresh_longest(c);
+  return TGX_OK;
+}
+
 int64_t tgx_context_size(const tgx_ctx* c) { return c ? c->d.max_ctx : -1; }
 int32_t tgx_num_layers(const tgx_ctx* c) { return c ? c->d.layers : -1; }
 

@@ -106,6 +106,13 @@ struct tgx_ctx {
   std::vector<int64_t> row_past;   // host mirror of each row's own pos (tgx_reset_row / tgx_forward_row, include/tgx.h)
   std::vector<char> row_tok;       // the row has a current token (sampled after its last forward)
   std::vector<char> row_idle;      // the row was retired (tgx_reset_row) and not refilled: it rides in the steps, nothing waits for it, its output means nothing
+  // tgx_decode_rows (include/tgx.h): per-row sampler settings and stop conditions.  row_req [max_batch] on the device (kernels/common.h RowReq), pushed by value
+  // in stream order; row_req_host mirrors the pushed fields.  row_fin: the finish reason of the last readback (0 running, 1 stop id, 2 max_new) — a finished row
+  // keeps its length, rides along without advancing and counts for neither `past` nor the context check
+  tgx::RowReq* row_req = nullptr;
+  std::vector<tgx::RowReq> row_req_host;
+  std::vector<char> row_fin;
+  int row_union = -1;     // steps being issued / captured: -1 = the launch-wide cfg (tgx_decode), else the ROWU_* union of the rows' chains (tgx_decode_rows)
   int batch = 0;          // rows used by the last forward
   bool have_logits = false, have_token = false;
 
@@ -123,7 +130,8 @@ struct tgx_ctx {
   hipGraphExec_t multi_graph = nullptr;   // graph_steps consecutive decode steps (tgx_decode with many steps)
   // captured step graphs by (batch, sampler config, attention form): a generation that crosses an attention-form limit, or an engine that alternates between
   // sampler configurations / batch sizes, re-uses what it captured before instead of re-capturing (round 3; round 2 dropped the graphs at every change)
-  struct GraphSet { hipGraphExec_t step = nullptr, multi = nullptr; int batch = 0; tgx_sampler_cfg cfg{}; bool direct = false, mfma = false, nw4 = false; unsigned long long used = 0; };
+  // (per-row steps are keyed on the union of the rows' chains, not on cfg values: the kernels read every row's settings from row_req)
+  struct GraphSet { hipGraphExec_t step = nullptr, multi = nullptr; int batch = 0; tgx_sampler_cfg cfg{}; int rows = -1; bool direct = false, mfma = false, nw4 = false; unsigned long long used = 0; };
   GraphSet graph_cache[6];
   unsigned long long graph_clock = 0;
   int graph_cur = -1;
@@ -311,6 +319,9 @@ void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true)
 int attn_set_attrs(tgx_ctx* c);
 // ---- sampler.hip (kernels/sampler.h)
 void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step);
+enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick
+void launch_sample_rows(tgx_ctx* c, int row0, int R, int un);              // tgx_decode_rows: every row with its own settings (a decode step's sampler)
+int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg);
 int sampler_alloc(tgx_ctx* c);
 // ---- prefill.hip (kernels/prefill.h, gemm_dma.h)

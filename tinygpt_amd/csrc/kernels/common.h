@@ -155,6 +155,42 @@ constexpr int XACC_HIDDEN_MAX = 8192;
 __device__ __forceinline__ float fix_to_f32(long long a) { return (float)a * (1.0f / 4294967296.0f); }
 
 // ---- paged KV cache (round 6; option kv.budget_tokens) --------------------------------------------------------------------------------------------
+// ---- per-row request state of tgx_decode_rows (include/tgx.h): the sampler settings, seed and stop conditions of ONE row, read by the staged sampler's
+// launches (SampArgs.req) and by the publishing thread of a step (FinalizeArgs.req).  Host-pushed fields change by value in a stream-ordered launch
+// (abi.hip row_req_push); `produced` and `finished` move on the device only.
+constexpr int ROW_MAX_STOP = 8;     // == TGX_MAX_STOP_IDS
+struct RowReq {
+  float temperature, top_p, min_p;
+  int max_new;                      // <= 0: no limit
+  long long top_k;
+  unsigned long long seed;
+  int n_stop, produced;             // produced: tokens published since the last tgx_set_row_stop / tgx_reset_row / refill
+  int finished, pad;                // 0 running, 1 stop id, 2 max_new
+  int stop[ROW_MAX_STOP];
+};
+__device__ __forceinline__ bool row_req_greedy(const RowReq& q) {   // == is_greedy (Sampler.cpp:15-21)
+  return !(q.temperature > 0.f || q.top_k > 0 || q.top_p < 1.f || q.min_p > 0.f);
+}
+// the stop words a publishing thread needs: loaded at the top of its launch, beside the words it loads anyway
+struct RowStopWords { int finished, produced, max_new, n_stop, tok; int stop[ROW_MAX_STOP]; };
+__device__ __forceinline__ RowStopWords row_stop_words(const RowReq* q, const int* tok) {
+  RowStopWords w;
+  w.finished = q->finished; w.produced = q->produced; w.max_new = q->max_new; w.n_stop = q->n_stop; w.tok = *tok;
+#pragma unroll
+  for (int k = 0; k < ROW_MAX_STOP; k++) w.stop[k] = q->stop[k];
+  return w;
+}
+// the row produced `t` (an unfinished row): count it, then test the stop set and max_new (a stop id takes precedence)
+__device__ __forceinline__ void row_count_and_stop(RowReq* q, const RowStopWords& w, int t) {
+  const int n = w.produced + 1;
+  q->produced = n;
+  bool hit = false;
+#pragma unroll
+  for (int k = 0; k < ROW_MAX_STOP; k++) hit = hit || (k < w.n_stop && w.stop[k] == t);
+  const int reason = hit ? 1 : (w.max_new > 0 && n >= w.max_new ? 2 : 0);
+  if (reason) q->finished = reason;
+}
+
 // The reference's KVCacheManager grows a row's cache by concat (CacheManager.h:24-42); the unpaged layout here gives every row a max_ctx slab
 // [layer][kv_head][max_ctx][hd].  Paged: one pool per layer, [block][kv_head][KV_BLOCK tokens][hd], and a per-row block table on the device (entry b = the
 // physical block of tokens [b KV_BLOCK, (b + 1) KV_BLOCK); entry 0 of the pool is a scratch block that unassigned table entries point to, so a speculative or

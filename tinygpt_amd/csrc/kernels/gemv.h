@@ -77,6 +77,8 @@ struct FinalizeArgs {
   int advance_pos;       // 1: pos += 1 (the token just consumed is now in the cache)
   const void* wpe;       // GPT-2: [n_pos][H] learned positions (nullptr otherwise); the next token sits at the advanced pos
   int n_pos;
+  RowReq* req;           // tgx_decode_rows: this row's request state — the token is counted against its stop set / max_new, a finished row keeps its token and
+                         // position and logs -1 (it still counts itself in `done`).  nullptr: every other caller (no change)
 };
 
 // the body of the greedy finalize for one row, run by all 256 threads of a workgroup: finalize_greedy_kernel (tgx_sample after a
@@ -102,16 +104,22 @@ __device__ __forceinline__ void finalize_row(const FinalizeArgs& a) {
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const int t = (unsigned)si[0] < (unsigned)a.V ? si[0] : 0;   // all-NaN logits leave the sentinel index: never gather out of the table
+    int t = (unsigned)si[0] < (unsigned)a.V ? si[0] : 0;   // all-NaN logits leave the sentinel index: never gather out of the table
+    int adv = a.advance_pos, logged = t;
+    if (a.req) {                                   // (the loads leave together with pos / step below)
+      const RowStopWords w = row_stop_words(a.req, a.tok);
+      if (w.finished) { t = w.tok; adv = 0; logged = -1; }
+      else row_count_and_stop(a.req, w, t);
+    }
     s_tok = t;
     *a.tok = t;
-    const int np = *a.pos + (a.advance_pos ? 1 : 0);
-    if (a.advance_pos) *a.pos = np;
+    const int np = *a.pos + (adv ? 1 : 0);
+    if (adv) *a.pos = np;
     s_pos = np < a.n_pos ? np : a.n_pos - 1;    // a full context takes no further step: stay inside wpe
     if (a.log) {
       const int st = *a.step;
-      a.tok_log[(st % a.log_cap) * a.rows + a.row] = t;
-      if (a.host_ring) a.host_ring[(st % a.ring_cap) * a.rows + a.row] = t;
+      a.tok_log[(st % a.log_cap) * a.rows + a.row] = logged;
+      if (a.host_ring) a.host_ring[(st % a.ring_cap) * a.rows + a.row] = logged;
       if (a.done) { if (atomicAdd(a.done, 1) == a.done_total - 1) { *a.done = 0; *a.step = st + 1; } }
       else if (a.bump_step) *a.step = st + 1;
     }
@@ -598,10 +606,12 @@ struct FinalizeRowsArgs {
   FinalizeArgs f;          // row 0's view
   long long part_stride, x_stride;
 };
-template <int DT>
+// ROWS (tgx_decode_rows): f.req is row 0's request state; a row whose own settings are not greedy leaves at once (the staged sampler publishes it)
+template <int DT, bool ROWS = false>
 __global__ __launch_bounds__(256) void finalize_rows_kernel(const FinalizeRowsArgs a) {
   FinalizeArgs f = a.f;
   const int r = blockIdx.x;
+  if (ROWS) { f.req += r; if (!row_req_greedy(*f.req)) return; }
   f.part_val += (size_t)r * a.part_stride; f.part_idx += (size_t)r * a.part_stride;
   f.tok += r; f.pos += r; f.x += (size_t)r * a.x_stride; f.row = a.f.row + r;
   finalize_row<DT>(f);

@@ -84,7 +84,31 @@ struct SampArgs {
   int z_from_tail;                    // 1: the kept set's normaliser is sc->zk (the last filter's tail summed it); 0: the ordered sum of wg_z2
   unsigned long long* list_comp;      // [rows][V] compacted entries of the threshold's first-digit bin: composite keys ...
   float* list_v;                      // ... and logit / T
+  RowReq* req;                        // per-row mode (tgx_decode_rows, the ROWS instantiations): the launch's first row's request state; every row reads its own
+                                      // cfg (and seed) from it and the fields above are replaced by them.  nullptr: the launch-wide cfg above
 };
+
+// ---- per-row mode: the launch chain is the UNION of the rows' chains; every workgroup takes its row's settings and leaves at once when its row's chain has
+// no such stage.  A row sees exactly the launch sequence (and mx_ready / z_from_tail) of the uniform chain of its own cfg (sampler.hip launch_sample).
+enum { SST_K0 = 0, SST_KC, SST_KT, SST_P0, SST_PC, SST_PT, SST_S0, SST_S1, SST_PICK };
+// 0: the row skips this stage; 1: it takes part; 2: it takes part and draws here (the tail of its last filter)
+__device__ __forceinline__ int samp_row_apply(SampArgs& a, int row, int stage) {
+  const RowReq& q = a.req[row];
+  a.temperature = q.temperature; a.top_k = q.top_k; a.top_p = q.top_p; a.min_p = q.min_p;
+  const bool K = a.top_k > 0, P = a.top_p < 1.f, M = a.min_p > 0.f;
+  const bool sampled = K || P || M || a.temperature > 0.f;
+  a.z_from_tail = (K || P) && !M ? 1 : 0;
+  switch (stage) {
+    case SST_K0: case SST_KC: a.mx_ready = 0; return K;
+    case SST_KT: a.mx_ready = 1; return K ? (!P && !M ? 2 : 1) : 0;
+    case SST_P0: a.mx_ready = K; return P;
+    case SST_PC: a.mx_ready = 1; return P;
+    case SST_PT: a.mx_ready = 1; return P ? (!M ? 2 : 1) : 0;
+    case SST_S0: a.mx_ready = K || P; return M;
+    case SST_S1: a.mx_ready = K || P || M; return sampled && !a.z_from_tail;
+    default: a.mx_ready = 1; return sampled && !a.z_from_tail;
+  }
+}
 
 __device__ __forceinline__ unsigned int float_key(float f) {   // ascending order-preserving key
   const unsigned int u = __float_as_uint(f);
@@ -278,11 +302,13 @@ __device__ __forceinline__ void samp_thresholds(const SampArgs& a, const SampScr
 }
 
 // ---- first digit of a radix descent: the whole chip over the vocabulary.  MODE 0: top-k (counts), MODE 1: top-p (masses over the top-k survivors) ----
-template <int MODE>
-__global__ __launch_bounds__(SAMP_WG) void samp_level0_kernel(const SampArgs a) {
+template <int MODE, bool ROWS = false>
+__global__ __launch_bounds__(SAMP_WG) void samp_level0_kernel(const SampArgs a_in) {
   __shared__ float shf[4];
   __shared__ unsigned long long lds_hist[SAMP_BINS];       // counts use the low word
   const int row = blockIdx.y, tid = threadIdx.x;
+  SampArgs a = a_in;
+  if (ROWS && !samp_row_apply(a, row, MODE == 0 ? SST_K0 : SST_P0)) return;
   SampScratch* sc = a.sc + row;
   SAMP_STAMP(sc, 0);
   const unsigned long long thr_k = (MODE == 1 && a.top_k > 0) ? sc->thr_k : 0ull;       // the top-k tail ran before
@@ -317,12 +343,14 @@ __global__ __launch_bounds__(SAMP_WG) void samp_level0_kernel(const SampArgs a) 
 
 // ---- second pass of the chip: every workgroup derives the threshold's first-digit bin from the global histogram; entries above it are kept for sure
 // (their exp sums per workgroup: the normaliser's bulk), entries inside it go to the compacted list the tail finishes
-template <int MODE>
-__global__ __launch_bounds__(SAMP_WG) void samp_compact_kernel(const SampArgs a) {
+template <int MODE, bool ROWS = false>
+__global__ __launch_bounds__(SAMP_WG) void samp_compact_kernel(const SampArgs a_in) {
   __shared__ unsigned long long sh4[4], sh_res[2];
   __shared__ float shf[4];
   __shared__ double shd[4];
   const int row = blockIdx.y, tid = threadIdx.x;
+  SampArgs a = a_in;
+  if (ROWS && !samp_row_apply(a, row, MODE == 0 ? SST_KC : SST_PC)) return;
   SampScratch* sc = a.sc + row;
   SAMP_STAMP(sc, 2);
   const unsigned long long thr_k = (MODE == 1 && a.top_k > 0) ? sc->thr_k : 0ull;
@@ -378,19 +406,24 @@ struct SampPickArgs {
 __device__ __forceinline__ FinalizeArgs samp_row_fin(const SampPickArgs& pa, int r) {
   FinalizeArgs f = pa.fin;
   f.tok += r; f.pos += r; f.x += (size_t)r * pa.x_stride; f.row = pa.fin.row + r;
+  if (f.req) f.req += r;
   return f;
 }
 
 // the words every draw needs; their loads leave at the top of the launch (one workgroup on an idle chip: each dependent round trip costs ~1 us)
+// (per-row mode: the row's own seed and its stop words, from its request state)
 struct SampDrawWords {
   unsigned long long seed;
   int pos, step;
+  RowStopWords stop;
 };
+template <bool ROWS = false>
 __device__ __forceinline__ SampDrawWords samp_draw_words(const unsigned long long* seed, const FinalizeArgs& fin) {
   SampDrawWords w;
-  w.seed = *seed;
+  w.seed = ROWS ? fin.req->seed : *seed;
   w.pos = *fin.pos;
   w.step = fin.log ? *fin.step : 0;
+  if (ROWS) w.stop = row_stop_words(fin.req, fin.tok);
   return w;
 }
 
@@ -399,7 +432,7 @@ __device__ __forceinline__ SampDrawWords samp_draw_words(const unsigned long lon
 // looks at (unused without min-p).  The tile that holds the draw comes from a block-wide prefix sum over the tile masses (x 1 / z in double); INSIDE
 // the tile the probabilities are the oracle's floats (e * inv) accumulated in double on top of the tiles below.  The two agree to ~1e-7 of the total:
 // a draw that close to a tile boundary takes the boundary's neighbour (the fallbacks below), every other draw is the oracle's.
-template <int DT>
+template <int DT, bool ROWS = false>
 __device__ __forceinline__ void samp_draw_and_publish(const SampArgs& a, const FinalizeArgs& fin, int nwg, int row, double (&pw)[4], const SampDrawWords& dw, float mx,
                                                       float z, float z0, unsigned long long thr_k, unsigned long long thr_p, double* shd) {
   __shared__ int s_wg, s_pick, s_last, s_pos;
@@ -479,15 +512,20 @@ __device__ __forceinline__ void samp_draw_and_publish(const SampArgs& a, const F
   if (tid == 0) {
     int pick = s_pick != 0x7fffffff ? s_pick : s_last;   // no hit inside the selected tile: its last kept entry
     if ((unsigned)pick >= (unsigned)a.V) pick = 0;       // all-NaN logits: stay inside the embedding table
+    int adv = fin.advance_pos, logged = pick;
+    if (ROWS) {                                          // a finished row keeps its token and position; an unfinished one counts the token against its stops
+      if (dw.stop.finished) { pick = dw.stop.tok; adv = 0; logged = -1; }
+      else row_count_and_stop(fin.req, dw.stop, pick);
+    }
     s_pick = pick;
     *fin.tok = pick;
-    const int np = dw.pos + (fin.advance_pos ? 1 : 0);
-    if (fin.advance_pos) *fin.pos = np;
+    const int np = dw.pos + (adv ? 1 : 0);
+    if (adv) *fin.pos = np;
     s_pos = np < fin.n_pos ? np : fin.n_pos - 1;
     if (fin.log) {
       const int st = dw.step;
-      fin.tok_log[(st % fin.log_cap) * fin.rows + fin.row] = pick;
-      if (fin.host_ring) fin.host_ring[(st % fin.ring_cap) * fin.rows + fin.row] = pick;
+      fin.tok_log[(st % fin.log_cap) * fin.rows + fin.row] = logged;
+      if (fin.host_ring) fin.host_ring[(st % fin.ring_cap) * fin.rows + fin.row] = logged;
       if (fin.done) { if (atomicAdd(fin.done, 1) == fin.done_total - 1) { *fin.done = 0; *fin.step = st + 1; } }
       else if (fin.bump_step) *fin.step = st + 1;
     }
@@ -503,15 +541,19 @@ __device__ __forceinline__ void samp_draw_and_publish(const SampArgs& a, const F
 // ---- the tail: ONE workgroup per row takes the remaining four digits over the compacted list and derives the filter's threshold.  PICK (the last
 // filter of a chain without min-p): it also derives the kept set's normaliser and the kept mass of every
 // vocabulary tile (bulk sums of the compaction pass + the list's kept entries) and draws — the step's token leaves this launch
-template <int MODE, bool PICK, int DT>
+// ROWS: launched as the PICK instantiation; whether the row draws here is its own (samp_row_apply)
+template <int MODE, bool PICK, int DT, bool ROWS = false>
 __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs pa) {
   __shared__ unsigned long long sh4[4], sh_res[2];
   __shared__ float shf[4];
   __shared__ double shd[4];
   __shared__ unsigned long long lds_hist[SAMP_BINS];
   __shared__ unsigned int lds_cnt[SAMP_BINS];
-  const SampArgs& a = pa.s;
+  SampArgs a = pa.s;
   const int row = blockIdx.y, tid = threadIdx.x, nwg = pa.nwg;
+  const int role = ROWS ? samp_row_apply(a, row, MODE == 0 ? SST_KT : SST_PT) : (PICK ? 2 : 1);
+  if (ROWS && !role) return;
+  const bool pick = PICK && role == 2;
   const FinalizeArgs fin = samp_row_fin(pa, row);
   SampScratch* sc = a.sc + row;
   const unsigned long long* lc = a.list_comp + (size_t)row * a.V;
@@ -521,8 +563,8 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
   SampDrawWords dw{};
   double aw[4] = {0.0, 0.0, 0.0, 0.0};    // the compaction pass's bulk sums of this thread's four tiles (in flight beside the list)
   unsigned long long thr_k_prev = 0ull;
-  if (PICK) {
-    dw = samp_draw_words(pa.seed, fin);
+  if (pick) {
+    dw = samp_draw_words<ROWS>(pa.seed, fin);
 #pragma unroll
     for (int j = 0; j < 4; j++) { const int w = tid * 4 + j; const double t = sc->wg_above[min(w, nwg - 1)]; aw[j] = w < nwg ? t : 0.0; }
     if (MODE == 1 && a.top_k > 0) thr_k_prev = sc->thr_k;
@@ -544,7 +586,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
     ck[q] = in ? k : 0ull;                                 // key 0 matches no prefix below the first digit of a real entry
     cv[q] = in ? v : 0.f;
   }
-  if (MODE == 1 || PICK) {
+  if (MODE == 1 || pick) {
 #pragma unroll
     for (int q = 0; q < TAIL_CACHE; q++) cm[q] = samp_mass(cv[q], mx);
   }
@@ -596,7 +638,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
   SAMP_STAMP(sc, 5);
   __syncthreads();
   // the first-digit histogram and the list of this filter are spent (PICK: zeroed behind the draw — a barrier waits for the stores in flight)
-  if (!PICK) {
+  if (!pick) {
     for (int b = tid; b < SAMP_BINS; b += SAMP_WG) { if (MODE == 0) sc->cnt[0][b] = 0u; else sc->mass[0][b] = 0ull; }
     if (tid == 0) sc->list_n = 0u;
     return;
@@ -630,7 +672,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
 #pragma unroll
   for (int j = 0; j < 4; j++) pw[j] = aw[j] + (double)lds_hist[tid * 4 + j] * (1.0 / 1099511627776.0);
   __syncthreads();                        // shd is reused by the draw
-  samp_draw_and_publish<DT>(a, fin, nwg, row, pw, dw, mx, z, 0.f, MODE == 0 ? thr : thr_k_prev, MODE == 1 ? thr : 0ull, shd);
+  samp_draw_and_publish<DT, ROWS>(a, fin, nwg, row, pw, dw, mx, z, 0.f, MODE == 0 ? thr : thr_k_prev, MODE == 1 ? thr : 0ull, shd);
   for (int b = tid; b < SAMP_BINS; b += SAMP_WG) { if (MODE == 0) sc->cnt[0][b] = 0u; else sc->mass[0][b] = 0ull; }
   if (tid == 0) sc->list_n = 0u;
 }
@@ -644,11 +686,13 @@ __device__ __forceinline__ float samp_ordered_sum(const double* part, int n, dou
   return (float)samp_block_sum_d(s, shd);
 }
 
-template <int STAGE>
-__global__ __launch_bounds__(SAMP_WG) void samp_sum_kernel(const SampArgs a) {
+template <int STAGE, bool ROWS = false>
+__global__ __launch_bounds__(SAMP_WG) void samp_sum_kernel(const SampArgs a_in) {
   __shared__ float shf[4];
   __shared__ double shd[4];
   const int row = blockIdx.y, tid = threadIdx.x, nwg = gridDim.x;
+  SampArgs a = a_in;
+  if (ROWS && !samp_row_apply(a, row, STAGE == 0 ? SST_S0 : SST_S1)) return;
   SampScratch* sc = a.sc + row;
   SAMP_STAMP(sc, STAGE == 0 ? 0 : 2);
   SampElems e;
@@ -686,19 +730,20 @@ __global__ __launch_bounds__(SAMP_WG) void samp_sum_kernel(const SampArgs a) {
 }
 
 // the draw of a chain that ends in partial-sum stages (min-p, or no filter at all): the tile masses are stage 1's sums
-template <int DT>
+template <int DT, bool ROWS = false>
 __global__ __launch_bounds__(SAMP_WG) void samp_pick_kernel(const SampPickArgs pa) {
   __shared__ float shf[4];
   __shared__ double shd[4];
-  const SampArgs& a = pa.s;
+  SampArgs a = pa.s;
   const int row = blockIdx.y, tid = threadIdx.x, nwg = pa.nwg;
+  if (ROWS && !samp_row_apply(a, row, SST_PICK)) return;
   const FinalizeArgs fin = samp_row_fin(pa, row);
   SampScratch* sc = a.sc + row;
   SAMP_STAMP(sc, 4);
   double pw[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) { const int w = tid * 4 + j; pw[j] = sc->wg_z2[min(w, nwg - 1)]; }
-  const SampDrawWords dw = samp_draw_words(pa.seed, fin);
+  const SampDrawWords dw = samp_draw_words<ROWS>(pa.seed, fin);
   const unsigned long long thr_k = a.top_k > 0 ? sc->thr_k : 0ull, thr_p = a.top_p < 1.f ? sc->thr_p : 0ull;
   const float mx = samp_row_max(a, row, shf);
   const float z0 = a.min_p > 0.f ? samp_ordered_sum(sc->wg_z, nwg, shd) : 0.f;
@@ -706,7 +751,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_pick_kernel(const SampPickArgs p
   const float z = samp_ordered_sum(sc->wg_z2, nwg, shd);
   __syncthreads();
   SAMP_STAMP(sc, 5);
-  samp_draw_and_publish<DT>(a, fin, nwg, row, pw, dw, mx, z, z0, thr_k, thr_p, shd);
+  samp_draw_and_publish<DT, ROWS>(a, fin, nwg, row, pw, dw, mx, z, z0, thr_k, thr_p, shd);
 }
 
 }  // namespace tgx

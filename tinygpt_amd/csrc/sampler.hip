@@ -70,6 +70,62 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
   }
 }
 
+// tgx_decode_rows: every row samples with its own settings (tgx_set_row_sampler; kernels/sampler.h samp_row_apply).  `un` = the union of the rows' chains
+// (row_union_of): greedy rows publish from the argmax partials in one finalize launch, the sampled rows through the union of their filter stages — each
+// workgroup leaves at once when its row has no such stage, and every row publishes exactly once (the step counter moves on the batch's count).  The cfg
+// values are read on the device: a new request's settings need no recapture.
+void launch_sample_rows(tgx_ctx* c, int row0, int R, int un) {
+  tgx::RowReq* req = c->row_req + row0;
+  if (un & ROWU_GREEDY) {
+    tgx::FinalizeRowsArgs fa{};
+    fa.f = make_finalize_args(c, row0, /*advance_pos=*/true, /*log_step=*/true);
+    fa.f.req = req;
+    fa.part_stride = c->lm_grid; fa.x_stride = c->d.hidden;
+    TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::finalize_rows_kernel<DT, true>), dim3(R), dim3(256), 0, c->stream, fa))
+  }
+  if (!(un & (ROWU_K | ROWU_P | ROWU_M | ROWU_SUM))) return;
+  const tgx_sampler_cfg none{0.f, 0, 1.f, 0.f};
+  tgx::SampArgs a = samp_args(c, row0, none);     // cfg fields, mx_ready and z_from_tail: per row on the device
+  a.req = req;
+  const int nwg = (a.V + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE;
+  const dim3 grid(nwg, R), blk(tgx::SAMP_WG);
+  tgx::SampPickArgs pa{};
+  pa.s = a; pa.nwg = nwg; pa.seed = c->seed_dev;
+  pa.fin = make_finalize_args(c, row0, /*advance_pos=*/true, /*log_step=*/true);
+  pa.fin.req = req;
+  pa.x_stride = c->d.hidden;
+  if (un & ROWU_K) {
+    hipLaunchKernelGGL((tgx::samp_level0_kernel<0, true>), grid, blk, 0, c->stream, a);
+    hipLaunchKernelGGL((tgx::samp_compact_kernel<0, true>), grid, blk, 0, c->stream, a);
+    TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::samp_tail_kernel<0, true, DT, true>), dim3(1, R), blk, 0, c->stream, pa))
+  }
+  if (un & ROWU_P) {
+    hipLaunchKernelGGL((tgx::samp_level0_kernel<1, true>), grid, blk, 0, c->stream, a);
+    hipLaunchKernelGGL((tgx::samp_compact_kernel<1, true>), grid, blk, 0, c->stream, a);
+    TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::samp_tail_kernel<1, true, DT, true>), dim3(1, R), blk, 0, c->stream, pa))
+  }
+  if (un & ROWU_M) hipLaunchKernelGGL((tgx::samp_sum_kernel<0, true>), grid, blk, 0, c->stream, a);
+  if (un & ROWU_SUM) {
+    hipLaunchKernelGGL((tgx::samp_sum_kernel<1, true>), grid, blk, 0, c->stream, a);
+    TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::samp_pick_kernel<DT, true>), dim3(1, R), blk, 0, c->stream, pa))
+  }
+}
+
+// the union of the chains of rows [0, batch) under their own settings (host mirror of the request states)
+int row_union_of(const tgx_ctx* c) {
+  int un = 0;
+  for (int b = 0; b < c->batch; b++) {
+    const tgx::RowReq& q = c->row_req_host[(size_t)b];
+    const bool K = q.top_k > 0, P = q.top_p < 1.f, M = q.min_p > 0.f, sampled = K || P || M || q.temperature > 0.f;
+    if (!sampled) { un |= ROWU_GREEDY; continue; }
+    if (K) un |= ROWU_K;
+    if (P) un |= ROWU_P;
+    if (M) un |= ROWU_M;
+    if (!((K || P) && !M)) un |= ROWU_SUM;
+  }
+  return un;
+}
+
 // tgx_read_probs: the final probability vector of row `row`'s last sampled step, evaluated from what that step left on the device (its logits, the
 // filters' thresholds, the normalisers) — the step itself never needs the vector
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg) {

@@ -333,7 +333,9 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
   }
   hipLaunchKernelGGL(tgx::argmax_partials_rows_kernel, dim3(std::min(c->lm_grid, std::max(1, (V / 4 + 255) / 256)), M), dim3(256), 0, c->stream, (const float*)r.logits, (long long)V, V, r.part_val, r.part_idx,
                      (long long)c->lm_grid, c->lm_grid);
-  if (is_greedy(&cfg)) {
+  if (c->row_union >= 0) {           // tgx_decode_rows: every row with its own settings (the greedy ones from the partials above)
+    launch_sample_rows(c, row0, M, c->row_union);
+  } else if (is_greedy(&cfg)) {
     launch_finalize_rows(c, row0, M);
   } else {
     launch_sample(c, row0, M, cfg, /*advance_pos=*/true, /*log_step=*/true);

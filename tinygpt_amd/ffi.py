@@ -69,6 +69,9 @@ ABI = {
     "forward_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
+    "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
+    "set_row_stop": (c_int, [c_void_p, c_int, c_int32, POINTER(c_int32), c_int]),
+    "decode_rows": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "context_size": (c_int64, [c_void_p]),
     "num_layers": (c_int32, [c_void_p]),
     "last_error": (c_char_p, [c_void_p]),
@@ -253,6 +256,27 @@ class Model:
 
     def past_length_row(self, row: int) -> int:
         return self.be.past_length_row(self._ctx, row)
+
+    # -- per-row sampler settings and device-side stop (include/tgx.h tgx_decode_rows) ---------
+    def set_row_sampler(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0):
+        self._check(self.be.set_row_sampler(self._ctx, row, ctypes.byref(cfg) if cfg is not None else None, seed))
+        return self
+
+    def set_row_stop(self, row: int, max_new: int = 0, stop_ids=()):
+        ids = np.ascontiguousarray(np.asarray(list(stop_ids), dtype=np.int32).reshape(-1))
+        ptr = ids.ctypes.data_as(POINTER(c_int32)) if len(ids) else None
+        self._check(self.be.set_row_stop(self._ctx, row, max_new, ptr, len(ids)))
+        return self
+
+    def decode_rows(self, n_steps: int):
+        """n_steps steps, every row with its own settings -> (ids [n_steps][batch] (-1 after a row finished), produced [batch], finish [batch]:
+        0 running, 1 stop id, 2 max_new)"""
+        out = np.empty((n_steps, self.batch), dtype=np.int64)
+        new = np.empty(self.batch, dtype=np.int32)
+        fin = np.empty(self.batch, dtype=np.int32)
+        self._check(self.be.decode_rows(self._ctx, n_steps, out.ctypes.data_as(POINTER(c_int64)), new.ctypes.data_as(POINTER(c_int32)),
+                                        fin.ctypes.data_as(POINTER(c_int32))))
+        return out, new, fin
 
     @property
     def past_length(self) -> int:

@@ -7,7 +7,11 @@ serving loop would drive it, on the real kernels: a seeded stream of requests (p
   static       the reference worker's shape taken to a batch: B requests in, decode until the LONGEST is done (finished rows are retired, their slots stay empty),
                then the next B
 
-and reports generated tokens per second, the mean number of live rows per step and what the cache held.  The reference has neither (its server runs one request at
+With --mix every request draws its own sampler settings (greedy, T 0.8 / top-p 0.9, T 1.0 / top-k 50, T 0.7 / min-p 0.05) and seed, and the ticks run
+tgx_decode_rows (per-row settings, include/tgx.h); with --device-stop as well, each request's output length is its max_new (tgx_set_row_stop) and every tick
+is a full 16-step tgx_decode_rows call — the rows finish on the device, the host reads their counts back instead of limiting the call to the shortest output.
+
+The tool reports generated tokens per second, the mean number of live rows per step and what the cache held.  The reference has neither (its server runs one request at
 a time, HttpServer.cpp:118-163; continuous batching and paged attention are README.md:32-34 TODOs): this is the measurement of the kernel half only — no queue, no
 HTTP, synthetic weights; greedy unless --sampler.
 
@@ -31,6 +35,8 @@ ap.add_argument("--kv-budget", type=int, default=0, help="paged KV: tokens of ca
 ap.add_argument("--policy", default="both", choices=["continuous", "static", "both"])
 ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--sampler", default="", help="e.g. 'temperature=0.8,top_p=0.9' (default: greedy)")
+ap.add_argument("--mix", action="store_true", help="per-request sampler settings and seeds through tgx_decode_rows")
+ap.add_argument("--device-stop", action="store_true", help="(with --mix) output lengths as max_new on the device, full 16-step calls")
 args = ap.parse_args()
 B = args.rows
 CFG = GREEDY
@@ -50,6 +56,12 @@ blocks = (lambda n: (n + 127) // 128 * 128) if args.kv_budget else (lambda n: ar
 rng = np.random.default_rng(args.seed)
 reqs = [(int(rng.integers(plo, phi + 1)), int(rng.integers(nlo, nhi + 1))) for _ in range(args.requests)]
 prompts = [synth.synth_prompt(desc.vocab, L, 1000 + i) for i, (L, _) in enumerate(reqs)]
+if args.mix:
+    from tinygpt_amd.ffi import SamplerCfg
+    MIX = [GREEDY, SamplerCfg(0.8, 0, 0.9, 0.0), SamplerCfg(1.0, 50, 1.0, 0.0), SamplerCfg(0.7, 0, 1.0, 0.05)]
+    req_cfg = [(MIX[int(rng.integers(0, len(MIX)))], int(rng.integers(1, 1 << 30))) for _ in reqs]
+STOP = args.mix and args.device_stop
+SLACK = 16 if STOP else 0        # device stop: blocks are assigned up front for the whole 16-step call
 
 
 def born():
@@ -76,19 +88,39 @@ def serve(policy):
                     break
                 i = waiting[0]
                 L, new = reqs[i]
-                if reserved + blocks(L + new) > budget:
+                if reserved + blocks(L + new + SLACK) > budget:
                     break                                    # the head of the queue waits for room (FIFO)
                 waiting.pop(0)
-                m.forward_row(r, prompts[i]); m.sample_row(r, CFG, seed=3)
-                length[r], target[r] = L, L + new
-                reserved += blocks(L + new)
+                if args.mix:
+                    cfg, seed = req_cfg[i]
+                    m.forward_row(r, prompts[i]); m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
+                    if STOP:
+                        m.set_row_stop(r, max_new=new)
+                else:
+                    m.forward_row(r, prompts[i]); m.sample_row(r, CFG, seed=3)
+                length[r], target[r] = L, L + new + SLACK
+                reserved += blocks(L + new + SLACK)
                 produced += 1                                 # the first token came from the prefill's logits
         live = [r for r in range(B) if length[r]]
         if not live:
             raise SystemExit("the budget admits no request")
+        if STOP:                                               # full calls; the rows finish on the device
+            n = 16
+            _, cnt, fin = m.decode_rows(n)
+            calls += 1; steps += n
+            for r in live:
+                length[r] += int(cnt[r]); produced += int(cnt[r]); live_steps += int(cnt[r])
+            peak_tokens = max(peak_tokens, sum(length))
+            for r in live:
+                if fin[r]:
+                    m.reset_row(r); length[r] = target[r] = 0
+            continue
         remaining = [target[r] - length[r] for r in live]
         n = min(16, min(remaining))
-        m.decode(n, CFG, seed=3, fetch=False)
+        if args.mix:
+            m.decode_rows(n)
+        else:
+            m.decode(n, CFG, seed=3, fetch=False)
         calls += 1; steps += n
         for r in live:
             length[r] += n; produced += n; live_steps += n
@@ -103,6 +135,6 @@ def serve(policy):
 
 
 print(f"{desc.name}: {B} rows, max_ctx {args.max_ctx}, prompts {plo}..{phi}, outputs {nlo}..{nhi} tokens, "
-      f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}", flush=True)
+      f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}{', mixed settings' if args.mix else ''}{', device stop' if STOP else ''}", flush=True)
 for pol in (["continuous", "static"] if args.policy == "both" else [args.policy]):
     serve(pol)
