@@ -187,9 +187,25 @@ TGX_API int64_t tgx_past_length(const tgx_ctx* ctx);
  *                       logits in its slot of tgx_read_logits; the row is live again but has no current token until tgx_sample_row (or tgx_sample)
  *                       ran — tgx_decode refuses until then.
  * tgx_sample_row     == Sampler::sample on ONE row's logits; the id becomes that row's device-resident next token.
- * tgx_past_length_row   the row's own pastLength. */
+ * tgx_past_length_row   the row's own pastLength.
+ * tgx_forward_rows   == n tgx_forward_row calls (in array order) in ONE prefill pass, up to summation order: prompt i (lens[i] ids, the prompts back to back in
+ *                       `ids`) into row rows[i].  Each row follows tgx_forward_row's rules: a retired row < batch or a new row; the new rows of a call are exactly
+ *                       batch .. batch + k - 1 in any array order (the batch grows by k, up to max_batch); rows are distinct; lens[i] in [1, max_ctx]; every id in
+ *                       range; a live or finished row is TGX_ERR_STATE.  Afterwards each row holds lens[i] positions and its last-position logits / argmax in its
+ *                       own slot, exactly as tgx_forward_row leaves them (tgx_read_logits, tgx_sample_row, tgx_read_probs, tgx_decode / tgx_decode_rows work
+ *                       unchanged); rows not named keep their state bit for bit.  ALL OR NOTHING: a refused call changes no row, moves no KV block, leaves
+ *                       kv.free_tokens as it was and does not poison the context; on a paged cache the blocks of the whole call (the target rows' own blocks
+ *                       plus the free list) are counted before anything is assigned (TGX_ERR_CONTEXT), and a cache of more than 1024 blocks per row
+ *                       (max_ctx > 131072) is TGX_ERR_UNSUPPORTED.  n = 0 is TGX_ERR_INVALID.
+ *                       The prompts run in groups of whole prompts of at most max(8192, longest prompt) workspace rows, one matrix-core pass per group (skinny or
+ *                       tiled by tgx_forward's rule on the group's rows) with ONE RoPE / cache-append launch and ONE attention launch per layer for all its
+ *                       prompts, and lm_head four rows per pass over its weights.  Fall-back to tgx_forward_row's one-row passes (identical results): fp32
+ *                       storage, option prefill.mfma 0, layer shapes the matrix-core GEMM tile does not cover, groups of fewer than 4 rows. */
 TGX_API int tgx_reset_row(tgx_ctx* ctx, int row);
 TGX_API int tgx_forward_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
+/* n prompts into n rows of the live batch in ONE prefill pass: == n tgx_forward_row calls (in array order) up to summation order. */
+TGX_API int tgx_forward_rows(tgx_ctx* ctx, int n, const int32_t* rows, const int64_t* ids /* sum(lens) tokens, prompts back to back */,
+                             const int32_t* lens);
 TGX_API int tgx_sample_row(tgx_ctx* ctx, int row, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_id);
 TGX_API int64_t tgx_past_length_row(const tgx_ctx* ctx, int row);
 

@@ -6,6 +6,7 @@
 // There is NO CPU path in this library: every entry point either runs on the GPU or returns an error.
 #include <climits>
 #include "ctx.h"
+#include "kernels/prefill.h"       // tgx_forward_rows builds the ragged pass's tables (RgSeq, RgItem)
 
 static std::string g_create_err;
 
@@ -781,6 +782,7 @@ void tgx_destroy(tgx_ctx* c) {
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(c->embed); fr(c->lm_head); fr(c->final_norm); fr(c->wpe); fr(c->final_norm_b); fr(c->rope_cos); fr(c->rope_sin); fr(c->step); fr(c->step_done); fr(c->tok_log); fr(c->scratch_x); fr(c->seed_dev); fr(c->samp_scratch); fr(c->samp_list_comp); fr(c->samp_list_v);
   fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req);
+  fr(c->rg_buf); fr(c->rg_x); fr(c->rg_logits); fr(c->rg_part_val); fr(c->rg_part_idx);
   fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
   fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_part); fr(c->ws_ssq); fr(c->ws_pos);
   for (auto& w : c->L) { fr(w.in_norm); fr(w.post_norm); fr(w.wqkv); fr(w.bqkv); fr(w.wo); fr(w.q_norm); fr(w.k_norm); fr(w.wgu); fr(w.wdown); fr(w.in_norm_b); fr(w.post_norm_b); fr(w.bo); fr(w.bfc); fr(w.bdown); }
@@ -1019,24 +1021,11 @@ int tgx_reset_row(tgx_ctx* c, int row) {
   return TGX_OK;
 }
 
-int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
-  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
-  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
-  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
-  if (row < 0 || row >= c->d.max_batch || row > c->batch) return set_err(c, TGX_ERR_INVALID, "row %d: a live row [0,%d) or the next free one (max_batch %d)", row, c->batch, c->d.max_batch);
-  if (seq < 1 || seq > c->d.max_ctx) return set_err(c, seq < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "seq %d out of range (context size %d)", seq, c->d.max_ctx);
-  if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
-    return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
-  for (int i = 0; i < seq; i++)
-    if (ids[i] < 0 || ids[i] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
-  HIP_OK(c, hipSetDevice(c->device));
-  // the prompt runs as a one-row pass of the same prefill paths tgx_forward takes (they address rows by index and read the pass's past from c->past)
-  const int64_t longest = c->past;
-  const int batch_before = c->batch;
-  c->past = 0;
+// the launches of one tgx_forward_row pass: row `row` validated, its blocks assigned, c->past = 0 (the caller restores it).  The prompt runs as a one-row pass of
+// the same prefill paths tgx_forward takes (they address rows by index and read the pass's past from c->past)
+static int issue_row_pass(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   const bool f32_path = c->dt == tgx::DT_F32 && seq >= c->prefill_f32_min_rows && c->prefill_mfma;
   const bool mfma_path = (f32_path || (seq >= c->prefill_min_rows && seq >= 4 && c->prefill_mfma && c->dt != tgx::DT_F32 && prefill_shapes_ok(c->d)));
-  if (c->kv_paged) { kv_release_row(c, row); int rc0 = kv_ensure_blocks(c, row, seq); if (rc0) { c->past = longest; return rc0; } }
   RowState& r = c->rows[(size_t)row];
   int rc = TGX_OK;
   hipError_t e = hipMemcpyAsync(r.prompt, ids, (size_t)seq * 8, hipMemcpyHostToDevice, c->stream);
@@ -1070,24 +1059,228 @@ int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
       }
     }
   }
-  c->past = longest;
   if (rc) return rc;
   HIP_OK(c, e);
-  HIP_OK(c, hipGetLastError());
-  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }
-  LAUNCH_OK(c);
-  HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` may be pageable and reused by the caller
-  c->batch = std::max(batch_before, row + 1);
+  return TGX_OK;
+}
+
+// host state of a row after its prompt pass went through (the caller synchronised)
+static void row_admitted(tgx_ctx* c, int row, int seq) {
   row_req_push(c, row, ROWQ_STATE);       // a new sequence: what the slot counted while it rode along retired is gone (its settings stay)
   c->row_fin[(size_t)row] = 0;
   c->row_past[(size_t)row] = seq;
   c->row_tok[(size_t)row] = 0;
   c->row_idle[(size_t)row] = 0;
+  if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
+}
+
+int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
+  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  if (row < 0 || row >= c->d.max_batch || row > c->batch) return set_err(c, TGX_ERR_INVALID, "row %d: a live row [0,%d) or the next free one (max_batch %d)", row, c->batch, c->d.max_batch);
+  if (seq < 1 || seq > c->d.max_ctx) return set_err(c, seq < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "seq %d out of range (context size %d)", seq, c->d.max_ctx);
+  if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
+    return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
+  for (int i = 0; i < seq; i++)
+    if (ids[i] < 0 || ids[i] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
+  HIP_OK(c, hipSetDevice(c->device));
+  const int64_t longest = c->past;
+  const int batch_before = c->batch;
+  c->past = 0;
+  if (c->kv_paged) { kv_release_row(c, row); int rc0 = kv_ensure_blocks(c, row, seq); if (rc0) { c->past = longest; return rc0; } }
+  const int rc = issue_row_pass(c, row, ids, seq);
+  c->past = longest;
+  if (rc) return rc;
+  HIP_OK(c, hipGetLastError());
+  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }
+  LAUNCH_OK(c);
+  HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` may be pageable and reused by the caller
+  c->batch = std::max(batch_before, row + 1);
+  row_admitted(c, row, seq);
   refresh_longest(c);
   c->have_logits = true;
-  if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
   return TGX_OK;
 }
+
+// ---- tgx_forward_rows (include/tgx.h): n prompts into n rows in ONE prefill pass per group of whole prompts (<= max(8192, longest) workspace rows) -------------
+// Host tables of the call in one buffer, ONE upload: the ids back to back, then per group its RgSeq [n_g], its token -> prompt map [M_g] and its attention work list
+// (kernels/prefill.h), each 16-byte aligned.
+static size_t rg_align(size_t o) { return (o + 15) & ~(size_t)15; }
+
+int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens) {
+  if (!c || !rows || !ids || !lens) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
+  // ---- every check before anything changes
+  std::vector<char> named((size_t)d.max_batch, 0);
+  int n_new = 0;
+  for (int i = 0; i < n; i++) {
+    const int row = rows[i];
+    if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+    if (named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    named[(size_t)row] = 1;
+    n_new += row >= c->batch;
+  }
+  for (int row = c->batch; row < c->batch + n_new; row++)
+    if (row >= d.max_batch || !named[(size_t)row])
+      return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
+  long long total = 0;
+  int longest = 0;
+  for (int i = 0; i < n; i++) {
+    const int seq = lens[i];
+    if (seq < 1 || seq > d.max_ctx) return set_err(c, seq < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "prompt %d: seq %d out of range (context size %d)", i, seq, d.max_ctx);
+    const int row = rows[i];
+    if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
+      return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
+    total += seq;
+    longest = std::max(longest, seq);
+  }
+  for (long long i = 0; i < total; i++)
+    if (ids[i] < 0 || ids[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
+  if (c->kv_paged) {
+    // the prompt attention copies a row's block table into LDS (<= 1024 entries)
+    if (c->kv_tbl_stride > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_forward_rows on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
+    // all or nothing: the blocks of the whole call against the free list plus the blocks the target rows give back
+    long long need = 0, have = (long long)c->kv_free.size();
+    for (int i = 0; i < n; i++) { need += (lens[i] + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK; have += c->kv_row_nblk[(size_t)rows[i]]; }
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld blocks of %d tokens, %lld free or held by its rows of %d (option kv.budget_tokens = %d)", need,
+                     tgx::KV_BLOCK, have, c->kv_nblocks - 1, c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  const int64_t past_before = c->past;
+  c->past = 0;                       // every target row starts at position 0 (the skinny pass reads the pass's past from the context)
+  if (c->kv_paged) {
+    for (int i = 0; i < n; i++) kv_release_row(c, rows[i]);
+    for (int i = 0; i < n; i++) (void)kv_ensure_blocks(c, rows[i], lens[i]);     // cannot fail: counted above
+  }
+  // ---- groups of whole prompts; the ones the matrix-core pass cannot take run tgx_forward_row's one-row passes
+  const bool joint_ok = c->prefill_mfma && c->dt != tgx::DT_F32 && prefill_shapes_ok(d);
+  const int cap = std::max(8192, longest), min_rows = std::max(4, c->prefill_min_rows);
+  std::vector<int> first((size_t)n), g_begin;
+  std::vector<long long> off((size_t)n + 1, 0);           // prompt i's ids at ids + off[i]
+  for (int i = 0, M = 0; i < n; i++) {
+    if (i == 0 || M + lens[i] > cap) { g_begin.push_back(i); M = 0; }
+    first[(size_t)i] = M;
+    M += lens[i];
+    off[(size_t)i + 1] = off[(size_t)i] + lens[i];
+  }
+  g_begin.push_back(n);
+  const int n_groups = (int)g_begin.size() - 1;
+  std::vector<RaggedPass> passes((size_t)n_groups);
+  std::vector<size_t> o_seq((size_t)n_groups), o_tok((size_t)n_groups), o_item((size_t)n_groups);
+  size_t bytes = rg_align((size_t)total * 8);
+  for (int g = 0; g < n_groups; g++) {
+    RaggedPass& p = passes[(size_t)g];
+    const int i0 = g_begin[(size_t)g], i1 = g_begin[(size_t)g + 1];
+    p.n = i1 - i0; p.rows = rows + i0; p.lens = lens + i0; p.first = first.data() + i0;
+    for (int i = i0; i < i1; i++) { p.M += lens[i]; p.longest = std::max(p.longest, (int)lens[i]); p.n_items += ((lens[i] + 127) / 128) * d.heads; }
+    if (!joint_ok || p.M < min_rows) { p.n = 0; continue; }          // a group of one-row passes
+    o_seq[(size_t)g] = bytes; bytes = rg_align(bytes + (size_t)p.n * sizeof(tgx::RgSeq));
+    o_tok[(size_t)g] = bytes; bytes = rg_align(bytes + (size_t)p.M * 4);
+    o_item[(size_t)g] = bytes; bytes = rg_align(bytes + (size_t)p.n_items * sizeof(tgx::RgItem));
+  }
+  std::vector<unsigned char> host(bytes, 0);
+  std::memcpy(host.data(), ids, (size_t)total * 8);
+  for (int g = 0; g < n_groups; g++) {
+    RaggedPass& p = passes[(size_t)g];
+    if (!p.n) continue;
+    tgx::RgSeq* sq = reinterpret_cast<tgx::RgSeq*>(host.data() + o_seq[(size_t)g]);
+    int* tok = reinterpret_cast<int*>(host.data() + o_tok[(size_t)g]);
+    tgx::RgItem* it = reinterpret_cast<tgx::RgItem*>(host.data() + o_item[(size_t)g]);
+    std::vector<std::pair<int, int>> blocks;             // (prompt, query block), heaviest first: key tiles descending, ties in prompt order
+    for (int j = 0; j < p.n; j++) {
+      const RowState& r = c->rows[(size_t)p.rows[j]];
+      sq[j].row0 = p.first[j]; sq[j].S = p.lens[j];
+      sq[j].k = reinterpret_cast<bf16_t*>(r.kcache); sq[j].v = reinterpret_cast<bf16_t*>(r.vcache); sq[j].tbl = r.tbl; sq[j].pad = nullptr;
+      for (int s = 0; s < p.lens[j]; s++) tok[p.first[j] + s] = j;
+      for (int qb = 0; qb < (p.lens[j] + 127) / 128; qb++) blocks.emplace_back(j, qb);
+    }
+    auto tiles = [&](const std::pair<int, int>& b) { return std::min(b.second * 128 + 127, p.lens[b.first] - 1) / 64 + 1; };
+    std::stable_sort(blocks.begin(), blocks.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return tiles(x) > tiles(y); });
+    int k = 0;
+    for (const auto& b : blocks)
+      for (int h = 0; h < d.heads; h++) it[k++] = tgx::RgItem{b.first, b.second, h, 0};
+  }
+  int rc = TGX_OK;
+  if (bytes > c->rg_bytes) {
+    HIP_OK(c, hipStreamSynchronize(c->stream));
+    if (c->rg_buf) (void)hipFree(c->rg_buf);
+    c->rg_buf = nullptr; c->rg_bytes = 0;
+    if ((rc = dev_alloc(c, &c->rg_buf, bytes))) { c->past = past_before; return rc; }
+    c->rg_bytes = bytes;
+  }
+  if (!c->rg_x) {
+    const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
+    if ((rc = dev_alloc(c, &c->rg_x, 4 * H)) || (rc = dev_alloc(c, &c->rg_logits, 4 * V)) || (rc = dev_alloc(c, &c->rg_part_val, 4 * P)) || (rc = dev_alloc(c, &c->rg_part_idx, 4 * P))) {
+      c->past = past_before;
+      return rc;
+    }
+  }
+  hipError_t e = hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream);
+  for (int i = 0; e == hipSuccess && i < n; i++)      // retired rows that rode along since their reset: back to position 0
+    if (c->row_past[(size_t)rows[i]] != 0) { e = hipMemsetAsync(c->rows[(size_t)rows[i]].pos, 0, 4, c->stream); c->row_past[(size_t)rows[i]] = 0; }
+  std::vector<int> joint;             // prompts that went through a ragged pass: their lm_head comes below, four rows per pass over the weights
+  for (int g = 0; e == hipSuccess && !rc && g < n_groups; g++) {
+    RaggedPass& p = passes[(size_t)g];
+    const int i0 = g_begin[(size_t)g], i1 = g_begin[(size_t)g + 1];
+    if (!p.n) {
+      for (int i = i0; i < i1 && !rc; i++) rc = issue_row_pass(c, rows[i], ids + off[(size_t)i], lens[i]);
+      continue;
+    }
+    p.ids = reinterpret_cast<const long long*>(c->rg_buf + (size_t)off[(size_t)i0] * 8);
+    p.seq = reinterpret_cast<const tgx::RgSeq*>(c->rg_buf + o_seq[(size_t)g]);
+    p.tok_seq = reinterpret_cast<const int*>(c->rg_buf + o_tok[(size_t)g]);
+    p.items = reinterpret_cast<const tgx::RgItem*>(c->rg_buf + o_item[(size_t)g]);
+    const bool skinny = !c->gpt2 && c->prefill_skinny && d.vocab >= 128 &&       // tgx_forward's rule on the pass's rows
+                        (p.M <= 32 ? c->prefill_skinny_rows >= p.M : (p.M <= c->prefill_skinny_rows && d.hidden <= c->prefill_skinny_hidden_max && (p.M <= 64 || (c->skinny_dma && d.hidden <= c->prefill_skinny_hidden_max_wide))));
+    rc = skinny ? ensure_skinny_ws(c, p.M) : ensure_prefill_ws(c, p.M);
+    if (rc) break;
+    if (skinny) launch_prefill_skinny(c, 0, 0, 0, &p); else launch_prefill_ragged(c, p);
+    for (int i = i0; i < i1; i++) joint.push_back(i);
+  }
+  // lm_head: the call's rows four at a time (tgx_forward's grouping where they are consecutive rows; else gathered into staging rows and scattered back)
+  const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
+  for (size_t k = 0; e == hipSuccess && !rc && k < joint.size();) {
+    const size_t rem = joint.size() - k, real = std::min<size_t>(rem, 4);
+    const int R = rem >= 3 ? 4 : (int)rem;
+    bool consec = (int)real == R;
+    for (size_t j = 1; j < real; j++) consec = consec && rows[joint[k + j]] == rows[joint[k]] + (int)j;
+    if (consec) {
+      launch_lm_head(c, rows[joint[k]], R);
+    } else {
+      for (int j = 0; j < R; j++)
+        (void)hipMemcpyAsync(c->rg_x + j * H, c->rows[(size_t)rows[joint[k + std::min<size_t>(j, real - 1)]]].x, H * 4, hipMemcpyDeviceToDevice, c->stream);
+      launch_lm_head_at(c, c->rg_x, c->rg_logits, c->rg_part_val, c->rg_part_idx, R);
+      for (size_t j = 0; j < real; j++) {
+        RowState& r = c->rows[(size_t)rows[joint[k + j]]];
+        (void)hipMemcpyAsync(r.logits, c->rg_logits + j * V, V * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.part_val, c->rg_part_val + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.part_idx, c->rg_part_idx + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
+      }
+    }
+    k += real;
+  }
+  for (size_t k = 0; e == hipSuccess && !rc && k < joint.size(); k++) launch_add_pos(c, c->rows[(size_t)rows[joint[k]]].pos, lens[joint[k]]);
+  c->past = past_before;
+  if (rc) return rc;
+  HIP_OK(c, e);
+  HIP_OK(c, hipGetLastError());
+  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }
+  LAUNCH_OK(c);
+  HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` and the tables may be pageable
+  for (int i = 0; i < n; i++) {
+    c->batch = std::max(c->batch, rows[i] + 1);
+    row_admitted(c, rows[i], lens[i]);
+  }
+  refresh_longest(c);
+  c->have_logits = true;
+  return TGX_OK;
+}
+
 
 int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_id) {
   if (!c || !cfg) return TGX_ERR_INVALID;

@@ -73,6 +73,18 @@ struct Profiler {
 // where the QKV product of a one-sequence prefill may finish its rows (prefill.hip launch_prefill -> launch_gemm)
 struct QkvEpi { bf16_t *q_hi = nullptr, *q_lo = nullptr, *k = nullptr, *v = nullptr; int past = 0; const int* tbl = nullptr; };     // past: the position of the pass's first row (RoPE, cache append)
 
+namespace tgx { struct RgSeq; struct RgItem; }
+// one ragged prefill pass of tgx_forward_rows (abi.hip): prompt i at workspace rows [first[i], first[i] + lens[i]) into batch row rows[i], positions 0 .. lens[i] - 1
+struct RaggedPass {
+  int n = 0, M = 0, longest = 0;
+  const int *rows = nullptr, *lens = nullptr, *first = nullptr;   // host [n]
+  const long long* ids = nullptr;            // device [M]: the pass's ids, prompts back to back
+  const tgx::RgSeq* seq = nullptr;           // device [n] (kernels/prefill.h)
+  const int* tok_seq = nullptr;              // device [M]: the prompt of each workspace row
+  const tgx::RgItem* items = nullptr;        // device: the prompt-attention work list, heaviest first
+  int n_items = 0;
+};
+
 struct tgx_ctx {
   tgx_model_desc d{};
   int device = 0;
@@ -254,6 +266,9 @@ struct tgx_ctx {
   std::vector<int> kv_free;        // free physical blocks
   std::vector<int> kv_row_nblk;    // blocks assigned to each row
   long long* slab_acc = nullptr;   // [max_batch][hidden], resting at zero between layers
+  // tgx_forward_rows: the call's tables (ids, RaggedPass device arrays; one upload per call) and four staging rows for the lm_head of scattered target rows
+  unsigned char* rg_buf = nullptr; size_t rg_bytes = 0;
+  float *rg_x = nullptr, *rg_logits = nullptr, *rg_part_val = nullptr; int* rg_part_idx = nullptr;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -307,6 +322,7 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
 void launch_layers(tgx_ctx* c, RowState* rv, int R, long long kv_stride);
 void launch_layers(tgx_ctx* c, int row0, int R);
 void launch_lm_head(tgx_ctx* c, int row0, int R);
+void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_val, int* part_idx, int R);   // R rows at row strides from these pointers
 tgx::FinalizeArgs make_finalize_args(tgx_ctx* c, int row, bool advance_pos, bool log_step);
 void launch_finalize_greedy(tgx_ctx* c, int row0, int R, bool advance_pos, bool log_step);   // one finalize_greedy launch per row
 void launch_finalize_rows(tgx_ctx* c, int row0, int M);                                     // the batched step's greedy finalize (+ step counter)
@@ -328,6 +344,10 @@ int sampler_alloc(tgx_ctx* c);
 bool prefill_shapes_ok(const tgx_model_desc& d);
 int ensure_prefill_ws(tgx_ctx* c, int S);
 void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past);      // past: the rows' common pastLength (their positions are past .. past + S - 1) — explicit, not read from the context
+void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg);           // the same pass over the prompts of rg (every one from position 0)
+void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg);
+void launch_rope_kv_split_ragged(tgx_ctx* c, const tgx::RopeKvArgs& a, const RaggedPass& rg, long long layer_off);
+void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean);
 int prefill_set_attrs(tgx_ctx* c);
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean);
 void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S);
@@ -341,5 +361,5 @@ void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S);
 bool decode_mfma_ok(const tgx_ctx* c);
 int ensure_skinny_ws(tgx_ctx* c, int rows);
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg);
-void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S);
+void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, const RaggedPass* rg = nullptr);   // rg: a ragged pass of rg->M rows instead of rows [row0, row0 + NB)
 int skinny_set_attrs(tgx_ctx* c);

@@ -253,13 +253,17 @@ void launch_layers(tgx_ctx* c, int row0, int R) { launch_layers(c, &c->rows[(siz
 
 // model.norm -> lm_head on the current position + per-workgroup argmax partials   (GPTModel.h:56-57)
 void launch_lm_head(tgx_ctx* c, int row0, int R) {
-  const tgx_model_desc& d = c->d;
   RowState& r = c->rows[(size_t)row0];
+  launch_lm_head_at(c, r.x, r.logits, r.part_val, r.part_idx, R);
+}
+
+void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_val, int* part_idx, int R) {
+  const tgx_model_desc& d = c->d;
   tgx::GemvArgs a{};
   fill_strides(c, a);
-  a.W = d.tied ? c->embed : c->lm_head; a.x = r.x; a.x_stride = d.hidden; a.norm_w = c->final_norm; a.eps = d.norm_eps;
+  a.W = d.tied ? c->embed : c->lm_head; a.x = x; a.x_stride = d.hidden; a.norm_w = c->final_norm; a.eps = d.norm_eps;
   a.N = d.vocab; a.K = d.hidden; a.units = (d.vocab + 1) / 2; a.hd = 2;
-  a.logits = r.logits; a.part_val = r.part_val; a.part_idx = r.part_idx;
+  a.logits = logits; a.part_val = part_val; a.part_idx = part_idx;
   if (c->gpt2) {   // ln_f -> wte^T (tied head, ModelGPT2.h:170-176)
     a.norm_b = c->final_norm_b;
     launch_gemv<tgx::PRO_LAYERNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R);

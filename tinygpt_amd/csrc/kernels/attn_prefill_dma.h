@@ -23,8 +23,8 @@ namespace tgx {
 
 // PAGED (round 6): the workgroup's slice of the sequence's block table goes to LDS first; a DMA piece's source row then takes one LDS read (a tile of 64
 // keys lies inside one 128-token page, the clamped rows of the last tile in that page or an earlier one).
-template <int DT, bool PAGED = false>
-__global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(const AttnPrefillArgs a) {
+template <int DT, bool PAGED>
+__device__ __forceinline__ void attn_prefill_dma_wg(const AttnPrefillArgs& a, const int h, const int qblk) {      // query block qblk of head h
   constexpr int HD = 64, KS = HD / 16, NB = HD / 32, CH = HD / 8, NS = 3;
   constexpr int TILE = 64 * HD;                 // 16-bit elements of one K or V tile
   constexpr float LOG2E = 1.4426950408889634f;
@@ -34,10 +34,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(const AttnPref
   const unsigned lds_k = (unsigned)(size_t)smem, lds_v = lds_k + (unsigned)(NS * TILE * 2);
 
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5, ql = lane & 31;
-  const int h = a.heavy_first ? blockIdx.x : blockIdx.y, G = a.heads / a.kv_heads, kvh = h / G;
+  const int G = a.heads / a.kv_heads, kvh = h / G;
   const int qd = a.heads * HD;
-  const int qblk = a.heavy_first ? (int)gridDim.y - 1 - (int)blockIdx.y
-                                 : ((a.qblk_mirror && h >= a.heads / 2) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x);
   const int q0 = qblk * 128 + wv * 32;                 // first query of this wave
   const int qi = q0 + ql;                              // this lane's query
   const bool qvalid = qi < a.S;
@@ -279,6 +277,19 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(const AttnPref
         *reinterpret_cast<u32x4*>(dst + (size_t)(q0 + row) * qd + (size_t)h * HD + cc * 8) = u32x4{p0[0], p0[1], p1[0], p1[1]};
     }
   }
+}
+template <int DT, bool PAGED = false>
+__global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(const AttnPrefillArgs a) {
+  const int h = a.heavy_first ? blockIdx.x : blockIdx.y;
+  const int qblk = a.heavy_first ? (int)gridDim.y - 1 - (int)blockIdx.y
+                                 : ((a.qblk_mirror && h >= a.heads / 2) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x);
+  attn_prefill_dma_wg<DT, PAGED>(a, h, qblk);
+}
+// the ragged pass's form (kernels/prefill.h AttnRgArgs): one workgroup per work item
+template <int DT, bool PAGED>
+__global__ __launch_bounds__(256, 2) void attn_prefill_dma_rg_kernel(const AttnRgArgs r) {
+  const RgItem it = r.item[blockIdx.x];
+  attn_prefill_dma_wg<DT, PAGED>(attn_rg_args<64>(r, it), it.h, it.qblk);
 }
 
 }  // namespace tgx

@@ -182,10 +182,11 @@ struct RopeKvArgs {
   const float* part; int nsplit; long long slab; const bf16_t* bias;
   const int* blk_tbl;      // paged KV (common.h kv_paged_off): this sequence's block table, k_cache / v_cache = the layer's pools — or nullptr
 };
+// workspace row s (position pos of its sequence) into that sequence's cache k_cache / v_cache (blk_tbl: its block table, paged KV)
 template <int DT>
-__global__ __launch_bounds__(256) void rope_kv_split_kernel(const RopeKvArgs a) {
+__device__ __forceinline__ void rope_kv_split_row(const RopeKvArgs& a, const int s, const int pos, bf16_t* const k_cache, bf16_t* const v_cache, const int* const blk_tbl) {
   // one workgroup per position; a thread owns FOUR adjacent RoPE pairs (p..p+3, p+half..p+half+3) of one head: 16-byte loads, 8-byte stores
-  const int s = blockIdx.x, pos = a.past + s, half = a.hd >> 1, q4 = half >> 2;
+  const int half = a.hd >> 1, q4 = half >> 2;
   const int qd = a.heads * a.hd, kvd = a.kv_heads * a.hd;
   const float* row = (a.QKV ? a.QKV : a.part) + (size_t)s * (qd + 2 * kvd);
   const int units = (a.heads + 2 * a.kv_heads) * q4;
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(256) void rope_kv_split_kernel(const RopeKvArgs a) 
     } else {
       const bool is_k = hh < a.heads + a.kv_heads;
       const int kh = is_k ? hh - a.heads : hh - a.heads - a.kv_heads;
-      bf16_t* dst = (is_k ? a.k_cache : a.v_cache) + (a.blk_tbl ? kv_paged_off(a.blk_tbl, a.kv_heads, kh, pos, a.hd) : ((size_t)kh * a.max_ctx + pos) * a.hd);
+      bf16_t* dst = (is_k ? k_cache : v_cache) + (blk_tbl ? kv_paged_off(blk_tbl, a.kv_heads, kh, pos, a.hd) : ((size_t)kh * a.max_ctx + pos) * a.hd);
       bf16_t e0[4], e1[4];
 #pragma unroll
       for (int t = 0; t < 4; t++) { e0[t] = f32_to_elem<DT>(x0[t]); e1[t] = f32_to_elem<DT>(x1[t]); }
@@ -269,6 +270,28 @@ __global__ __launch_bounds__(256) void rope_kv_split_kernel(const RopeKvArgs a) 
       *reinterpret_cast<u32x2*>(dst + p + half) = pack4(e1);
     }
   }
+}
+template <int DT>
+__global__ __launch_bounds__(256) void rope_kv_split_kernel(const RopeKvArgs a) {
+  rope_kv_split_row<DT>(a, blockIdx.x, a.past + (int)blockIdx.x, a.k_cache, a.v_cache, a.blk_tbl);
+}
+
+// ---- ragged passes (tgx_forward_rows): prompts of different lengths stacked in one workspace, each into its own row's cache ------------------------------
+struct RgSeq {                 // one prompt of the pass
+  int row0, S;                 // its first workspace row, its length (positions 0 .. S-1: every prompt starts an empty row)
+  bf16_t *k, *v;               // layer 0 of its row's cache (slab KV) or of the pools (paged KV); layer l: + layer_off
+  const int* tbl;              // paged KV: its row's block table, else nullptr
+  const void* pad;
+};
+struct RgItem { int seq, qblk, h, pad; };      // one prompt-attention workgroup: (prompt, query block, head)
+// rope_kv_split_kernel over every workspace row of the pass in ONE launch: QKV / part / q_hi / q_lo address the whole pass (a.k_cache / v_cache / blk_tbl / past
+// unused); a row finds its prompt in tok_seq, its position = its row - the prompt's first row
+struct RopeRgArgs { RopeKvArgs a; const RgSeq* seq; const int* tok_seq; long long layer_off; };
+template <int DT>
+__global__ __launch_bounds__(256) void rope_kv_split_rg_kernel(const RopeRgArgs r) {
+  const int s = blockIdx.x;
+  const RgSeq q = r.seq[r.tok_seq[s]];
+  rope_kv_split_row<DT>(r.a, s, s - q.row0, q.k + r.layer_off, q.v + r.layer_off, q.tbl);
 }
 
 // ---- C[M][N] (+)= (Ahi + Alo)[M][K] · B[N][K]ᵀ on v_mfma_f32_32x32x16_bf16 ------------------------------------------
@@ -529,8 +552,9 @@ struct AttnPrefillArgs {
 // cycle, half the chain; blocks are dispatched heaviest first (AttnPrefillArgs.heavy_first) so that the second round fills the CUs as they free up.
 // PAGED (round 6): the workgroup copies the part of the sequence's block table it needs (<= 1024 entries) into LDS first; a K / V row's address then takes one LDS
 // read (it does not touch the counted vmcnt waits of the tile pipeline) — a 64-key tile never straddles a 128-token page.
-template <int DT, int HD, int LA = 2, int KP = 1, bool PAGED = false>
-__global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 2) : 1)) void attn_prefill_kernel(const AttnPrefillArgs a) {      // head_dim 128: LA = 1 fits two waves per SIMD (LA = 2 needs 292 registers: one)
+// one workgroup: query block qblk of head h (attn_prefill_kernel: from the grid; attn_prefill_rg_kernel: from its work item)
+template <int DT, int HD, int LA, int KP, bool PAGED>
+__device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const int h, const int qblk) {
   constexpr int DIS = TGX_ATTN_DIS;
   constexpr int LQ = HD + 8;                  // 16-bit row stride of the K tile (144 / 272 B: conflict-free 16-byte fragment reads)
   constexpr int LV = HD + 32;                 // 16-bit row stride of the V tile ([key][d], 64 B more than a row: the four key rows of a transposing read fall on four bank quarters)
@@ -545,12 +569,8 @@ __global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 
   bf16_t* const sK = smem + kp * REG;          // the tile this wave multiplies — and the one its thread group stages
   bf16_t* const sV = sK + 64 * LQ;
 
-  const int h = a.heavy_first ? blockIdx.x : blockIdx.y, G = a.heads / a.kv_heads, kvh = h / G;
+  const int G = a.heads / a.kv_heads, kvh = h / G;
   const int qd = a.heads * HD;
-  // causal work grows with the query block: the upper half of the heads walks the blocks in reverse, so that workgroups b and b + half
-  // the grid (which tend to share a CU) carry complementary amounts.  heavy_first: every head's last block first (linear workgroup order = dispatch order)
-  const int qblk = a.heavy_first ? (int)gridDim.y - 1 - (int)blockIdx.y
-                                 : ((a.qblk_mirror && h >= a.heads / 2) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x);
   const int q0 = qblk * 128 + wv * 32;                 // first query of this wave
   const int qi = q0 + ql;                              // this lane's query
   const bool qvalid = qi < a.S;
@@ -818,6 +838,35 @@ __global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 
         *reinterpret_cast<u32x4*>(dst + (size_t)(q0 + row) * qd + (size_t)h * HD + cc * 8) = u32x4{p0[0], p0[1], p1[0], p1[1]};
     }
   }
+}
+template <int DT, int HD, int LA = 2, int KP = 1, bool PAGED = false>
+__global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 2) : 1)) void attn_prefill_kernel(const AttnPrefillArgs a) {      // head_dim 128: LA = 1 fits two waves per SIMD (LA = 2 needs 292 registers: one)
+  // causal work grows with the query block: the upper half of the heads walks the blocks in reverse, so that workgroups b and b + half
+  // the grid (which tend to share a CU) carry complementary amounts.  heavy_first: every head's last block first (linear workgroup order = dispatch order)
+  const int h = a.heavy_first ? blockIdx.x : blockIdx.y;
+  const int qblk = a.heavy_first ? (int)gridDim.y - 1 - (int)blockIdx.y
+                                 : ((a.qblk_mirror && h >= a.heads / 2) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x);
+  attn_prefill_wg<DT, HD, LA, KP, PAGED>(a, h, qblk);
+}
+
+// ---- the prompt attention of a ragged pass (tgx_forward_rows): ONE launch for every prompt, one workgroup per work item (prompt, query block, head) of a device list
+// that the host orders heaviest first (key tiles descending, across prompts).  a = the pass's q / o terms from its first workspace row; the item sets the prompt's rows,
+// S, past 0 and its row's K / V (or pools + block table).  Per workgroup the same code as attn_prefill_kernel / attn_prefill_dma_kernel: bit for bit the per-row form.
+struct AttnRgArgs { AttnPrefillArgs a; const RgSeq* seq; const RgItem* item; long long layer_off; };
+template <int HD>
+__device__ __forceinline__ AttnPrefillArgs attn_rg_args(const AttnRgArgs& r, const RgItem& it) {
+  AttnPrefillArgs a = r.a;
+  const RgSeq q = r.seq[it.seq];
+  const size_t o = (size_t)q.row0 * a.heads * HD;
+  a.q_hi += o; a.q_lo += o; a.o_hi += o; a.o_lo += o;
+  a.S = q.S; a.past = 0;
+  a.k_cache = q.k + r.layer_off; a.v_cache = q.v + r.layer_off; a.blk_tbl = q.tbl;
+  return a;
+}
+template <int DT, int HD, int LA, int KP, bool PAGED>
+__global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 2) : 1)) void attn_prefill_rg_kernel(const AttnRgArgs r) {
+  const RgItem it = r.item[blockIdx.x];
+  attn_prefill_wg<DT, HD, LA, KP, PAGED>(attn_rg_args<HD>(r, it), it.h, it.qblk);
 }
 
 }  // namespace tgx

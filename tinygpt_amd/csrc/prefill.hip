@@ -334,9 +334,55 @@ void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_
   };
   if (a.blk_tbl) go(std::true_type{}); else go(std::false_type{});
 }
+// the prompt attention of a ragged pass: ONE launch over rg's work list (kernels/prefill.h attn_prefill_rg_kernel).  The form is launch_attn_prefill's rule with the
+// longest prompt in the place of the row: the key split (another fp32 summation order) as that rule gives it for the longest prompt's workgroups, so that equal-length
+// prompts take the form tgx_forward takes for each of their rows; among the one-group forms, which compute the same bits (tests/test_hip_prefill.py), the launch's
+// total workgroup count picks the occupancy form (LDS-DMA or the lean look-ahead from three workgroups per CU)
+void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean) {
+  tgx::AttnRgArgs r{};
+  r.a = a; r.seq = rg.seq; r.item = rg.items; r.layer_off = layer_off;
+  const int hd = c->d.head_dim;
+  const int nqb = (rg.longest + 127) / 128, nwg = nqb * a.heads, total = rg.n_items;
+  const size_t lds1 = (size_t)(64 * (hd + 8) + 64 * (hd + 32)) * 2;
+  const bool dma_row = hd == 64 && (c->attn_dma == 2 || (c->attn_dma == 1 && allow_lean && nwg >= 3 * c->num_cus));
+  const bool ksplit = !dma_row && nqb >= 2 && (c->attn_ksplit == 2 || (c->attn_ksplit == 1 && (hd == 128 || nwg < 3 * c->num_cus)));
+  const bool wide = !ksplit && allow_lean && hd == 64 && total >= 3 * c->num_cus;
+  const bool dma = dma_row || (wide && c->attn_dma == 1);
+  const bool lean = !dma && wide;
+  const dim3 grid(total), blk(256), blkk(512);
+  auto go = [&](auto paged) {
+    constexpr bool P = decltype(paged)::value;
+    TGX_DT16_SWITCH(c->dt,
+      if (dma) hipLaunchKernelGGL((tgx::attn_prefill_dma_rg_kernel<DT, P>), grid, blk, (size_t)2 * 3 * 64 * 64 * 2, c->stream, r);
+      else if (ksplit) {
+        if (hd == 64) hipLaunchKernelGGL((tgx::attn_prefill_rg_kernel<DT, 64, 2, 2, P>), grid, blkk, 2 * lds1, c->stream, r);
+        else hipLaunchKernelGGL((tgx::attn_prefill_rg_kernel<DT, 128, 1, 2, P>), grid, blkk, 2 * lds1, c->stream, r);
+      } else if (lean) hipLaunchKernelGGL((tgx::attn_prefill_rg_kernel<DT, 64, 1, 1, P>), grid, blk, lds1, c->stream, r);
+      else if (hd == 64) hipLaunchKernelGGL((tgx::attn_prefill_rg_kernel<DT, 64, 2, 1, P>), grid, blk, lds1, c->stream, r);
+      else hipLaunchKernelGGL((tgx::attn_prefill_rg_kernel<DT, 128, 1, 1, P>), grid, blk, lds1, c->stream, r))
+  };
+  if (c->kv_paged) go(std::true_type{}); else go(std::false_type{});
+}
 // RoPE + cache append + q split of S prompt rows of one batch row
 void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S) {
   TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::rope_kv_split_kernel<DT>, dim3(S), dim3(256), 0, c->stream, a))
+}
+// ... of every row of a ragged pass, each into its own prompt's row: ONE launch
+void launch_rope_kv_split_ragged(tgx_ctx* c, const tgx::RopeKvArgs& a, const RaggedPass& rg, long long layer_off) {
+  tgx::RopeRgArgs r{};
+  r.a = a; r.seq = rg.seq; r.tok_seq = rg.tok_seq; r.layer_off = layer_off;
+  TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::rope_kv_split_rg_kernel<DT>, dim3(rg.M), dim3(256), 0, c->stream, r))
+}
+// the ids of a ragged pass -> ws_x (GPT-2: + the learned position of each row within its prompt, one launch per prompt)
+void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg) {
+  const int H = c->d.hidden;
+  if (!c->gpt2) {
+    TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::embed_rows_any_kernel<DT>, dim3(rg.M), dim3(256), 0, c->stream, rg.ids, (const void*)c->embed, (const void*)nullptr, c->ws_x, H, rg.M, 0LL, 0))
+    return;
+  }
+  for (int i = 0; i < rg.n; i++)
+    TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::embed_rows_any_kernel<DT>, dim3(rg.lens[i]), dim3(256), 0, c->stream, rg.ids + rg.first[i], (const void*)c->embed, (const void*)c->wpe,
+                                              c->ws_x + (size_t)rg.first[i] * H, H, rg.lens[i], 0LL, 0))
 }
 // RMSNorm of the rows of x into 16-bit terms (ws_ah / ws_al), first adding a pending split-K residual (nsplit > 1: the slabs in ws_part)
 void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, int nsplit, bool third) {
@@ -358,15 +404,17 @@ void launch_embed_rows(tgx_ctx* c, const long long* ids, float* X, int M, int S)
 // == CausalLM::forward on [1,S] ids with an empty cache (GPTModel.h:51-56)
 // NB batch rows [row0, row0 + NB) are stacked into ONE [NB*S] row block for the row-wise kernels and the GEMMs (the weights stream
 // once for all of them); RoPE / cache append and attention run per batch row on its slice and its own cache.
-void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past) {
+// rg (tgx_forward_rows): a ragged pass of rg->M rows instead — RoPE / cache append and attention then run as ONE launch each for all its prompts
+static void prefill_pass(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd;
   const size_t kv_layer = c->kv_paged ? (size_t)c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
-  const int M = NB * S;
+  const int M = rg ? rg->M : NB * S;
   const size_t wout = (size_t)qd + 2 * kvd;
   // GPT-2 (ModelGPT2.h:23-208): wte + wpe rows, LayerNorm with bias ahead of both products, a bias on every Conv1D, c_fc -> gelu_new;
   // its rotation tables are the identity, so the RoPE / cache-append kernel and the attention are the Llama family's
-  TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::embed_rows_any_kernel<DT>, dim3(M), dim3(256), 0, c->stream, (const long long*)c->rows[(size_t)row0].prompt, (const void*)c->embed, (const void*)(c->gpt2 ? c->wpe : nullptr), c->ws_x, H, S, (long long)d.max_ctx, past))
+  if (rg) launch_embed_ragged(c, *rg);
+  else TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::embed_rows_any_kernel<DT>, dim3(M), dim3(256), 0, c->stream, (const long long*)c->rows[(size_t)row0].prompt, (const void*)c->embed, (const void*)(c->gpt2 ? c->wpe : nullptr), c->ws_x, H, S, (long long)d.max_ctx, past))
   int pend = 1;                     // slabs of the previous layer's down product still to be added to ws_x (1: none; -1: one whole-K slab, see launch_gemm)
   const bf16_t* pend_bias = nullptr;
   for (int l = 0; l < d.layers; l++) {
@@ -380,14 +428,27 @@ void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past) {
     pend = 1;
     int qsl = 1;
     c->qkv_epi = QkvEpi{};
-    if (NB == 1) {      // one sequence: the QKV product may finish its rows itself (launch_gemm: gemm_dma_qkv8_kernel<.., ROPE>)
+    if (NB == 1 && !rg) {      // one sequence: the QKV product may finish its rows itself (launch_gemm: gemm_dma_qkv8_kernel<.., ROPE>)
       RowState& r0 = c->rows[(size_t)row0];
       c->qkv_epi.q_hi = c->ws_qh; c->qkv_epi.q_lo = c->ws_ql; c->qkv_epi.past = past; c->qkv_epi.tbl = r0.tbl;
       c->qkv_epi.k = reinterpret_cast<bf16_t*>(r0.kcache) + (size_t)l * kv_layer; c->qkv_epi.v = reinterpret_cast<bf16_t*>(r0.vcache) + (size_t)l * kv_layer;
     }
     launch_gemm(c, tgx::GEMM_STORE, w.wqkv, w.bqkv, c->ws_out, M, qd + 2 * kvd, H, qd + 2 * kvd, /*three_terms=*/three, nullptr, nullptr, /*three_from=*/qd, &qsl);   // Q columns: two terms
     c->qkv_epi = QkvEpi{};
-    for (int b = 0; b < NB && qsl != 0; b++) {
+    if (rg) {
+      tgx::RopeKvArgs a{};
+      a.QKV = c->ws_out; a.q_hi = c->ws_qh; a.q_lo = c->ws_ql;
+      if (qsl > 1) { a.QKV = nullptr; a.part = c->ws_part; a.nsplit = qsl; a.slab = (long long)M * (long long)wout; a.bias = reinterpret_cast<const bf16_t*>(w.bqkv); }
+      a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+      a.heads = d.heads; a.kv_heads = d.kv_heads; a.hd = hd; a.max_ctx = d.max_ctx;
+      a.q_norm_w = d.qk_norm ? (const bf16_t*)w.q_norm : nullptr; a.k_norm_w = d.qk_norm ? (const bf16_t*)w.k_norm : nullptr; a.eps = d.norm_eps;
+      launch_rope_kv_split_ragged(c, a, *rg, (long long)((size_t)l * kv_layer));
+      tgx::AttnPrefillArgs at{};
+      at.q_hi = c->ws_qh; at.q_lo = c->ws_ql; at.o_hi = c->ws_ah; at.o_lo = c->ws_al;
+      at.heads = d.heads; at.kv_heads = d.kv_heads; at.max_ctx = d.max_ctx; at.scale = 1.0f / sqrtf((float)hd);
+      launch_attn_prefill_ragged(c, at, *rg, (long long)((size_t)l * kv_layer), /*allow_lean=*/true);
+    }
+    for (int b = 0; b < NB && qsl != 0 && !rg; b++) {
       RowState& r = c->rows[(size_t)(row0 + b)];
       bf16_t* kc = reinterpret_cast<bf16_t*>(r.kcache);
       bf16_t* vc = reinterpret_cast<bf16_t*>(r.vcache);
@@ -401,7 +462,7 @@ void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past) {
       a.q_norm_w = d.qk_norm ? (const bf16_t*)w.q_norm : nullptr; a.k_norm_w = d.qk_norm ? (const bf16_t*)w.k_norm : nullptr; a.eps = d.norm_eps;
       launch_rope_kv_split(c, a, S);
     }
-    for (int b = 0; b < NB; b++) {
+    for (int b = 0; b < NB && !rg; b++) {
       RowState& r = c->rows[(size_t)(row0 + b)];
       bf16_t* kc = reinterpret_cast<bf16_t*>(r.kcache);
       bf16_t* vc = reinterpret_cast<bf16_t*>(r.vcache);
@@ -430,9 +491,16 @@ void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past) {
     launch_gemm(c, tgx::GEMM_RESIDUAL, w.wdown, w.bdown, c->ws_x, M, H, I, H, false, c->ws_hh, c->ws_hl, 0, can_defer ? &pend : nullptr);
     pend_bias = reinterpret_cast<const bf16_t*>(w.bdown);
   }
+  if (rg) {
+    for (int i = 0; i < rg->n; i++)
+      (void)hipMemcpyAsync(c->rows[(size_t)rg->rows[i]].x, c->ws_x + ((size_t)rg->first[i] + rg->lens[i] - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, c->stream);
+    return;
+  }
   for (int b = 0; b < NB; b++)     // the last position of every batch row feeds lm_head
     (void)hipMemcpyAsync(c->rows[(size_t)(row0 + b)].x, c->ws_x + ((size_t)(b + 1) * S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, c->stream);
 }
+void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past) { prefill_pass(c, row0, NB, S, past, nullptr); }
+void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg) { prefill_pass(c, 0, 0, 0, 0, &rg); }
 
 // dynamic LDS sizes of the tiled GEMMs
 int prefill_set_attrs(tgx_ctx* c) {
@@ -458,6 +526,10 @@ int prefill_set_attrs(tgx_ctx* c) {
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_kernel<tgx::DT_BF16, 128, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_kernel<tgx::DT_F16, 128, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_kernel<tgx::DT_F16, 128, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_rg_kernel<tgx::DT_BF16, 128, 1, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_rg_kernel<tgx::DT_BF16, 128, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_rg_kernel<tgx::DT_F16, 128, 1, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefill_rg_kernel<tgx::DT_F16, 128, 1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (64 * 136 + 64 * 160) * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_dma8k_kernel<tgx::DT_BF16, tgx::GEMM_SILU>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 3 * 128 * 64 * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_dma8k_kernel<tgx::DT_F16, tgx::GEMM_SILU>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 3 * 128 * 64 * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_dma8k_kernel<tgx::DT_BF16, tgx::GEMM_RESIDUAL>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 3 * 128 * 64 * 2));

@@ -345,14 +345,15 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
 // Prompts of a few tokens (NB * S <= 32 workspace rows): the batched prefill with every product as a skinny MFMA GEMM (kernels/skinny.h) —
 // the 128-row tiles of gemm_x2_kernel would stream the weights for 4-25 % useful rows through a two-barrier K loop; here the weight stream
 // is the decode step's, RMSNorm rides in the activation staging and narrow products finish through the row-wise slab reducers.
-void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S) {
+void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, const RaggedPass* rg) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd;
   const size_t kv_layer = c->kv_paged ? (size_t)c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
-  const int M = NB * S, nq = qd + 2 * kvd;
+  const int M = rg ? rg->M : NB * S, nq = qd + 2 * kvd;
   const int nt_qkv = c->dt == tgx::DT_BF16 ? 3 : 2;
   float* ssq = c->ws_ssq;
-  launch_embed_rows(c, (const long long*)c->rows[(size_t)row0].prompt, c->ws_x, M, S);
+  if (rg) launch_embed_ragged(c, *rg);
+  else launch_embed_rows(c, (const long long*)c->rows[(size_t)row0].prompt, c->ws_x, M, S);
   // 33-64 rows (four activation blocks): RMSNorm + the 16-bit terms once per product in a row-wise launch (which also takes the pending split-K
   // residual), the panel kernel stages stored terms — its RMSNorm-on-the-way form runs out of registers at four blocks
   const bool terms = M > c->prefill_terms_rows || c->act16;      // (option prefill.terms_rows)
@@ -368,7 +369,20 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S) {
       q.asrc = 0; q.a_hi = c->ws_ah; q.a_lo = c->ws_al; q.a_lo2 = c->ws_al2; q.a_f32 = nullptr; q.norm_w = nullptr; q.ssq_in = nullptr;
     }
     const int qs = launch_skinny(c, q);
-    for (int b = 0; b < NB; b++) {
+    if (rg) {          // a ragged pass (tgx_forward_rows): RoPE / cache append and the attention in one launch each for all its prompts
+      tgx::RopeKvArgs a{};
+      a.QKV = c->ws_out; a.q_hi = c->ws_qh; a.q_lo = c->ws_ql;
+      if (qs > 1) { a.QKV = nullptr; a.part = c->ws_part; a.nsplit = qs; a.slab = (long long)M * nq; a.bias = reinterpret_cast<const bf16_t*>(w.bqkv); }
+      a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+      a.heads = d.heads; a.kv_heads = d.kv_heads; a.hd = hd; a.max_ctx = d.max_ctx;
+      a.q_norm_w = d.qk_norm ? (const bf16_t*)w.q_norm : nullptr; a.k_norm_w = d.qk_norm ? (const bf16_t*)w.k_norm : nullptr; a.eps = d.norm_eps;
+      launch_rope_kv_split_ragged(c, a, *rg, (long long)((size_t)l * kv_layer));
+      tgx::AttnPrefillArgs at{};
+      at.q_hi = c->ws_qh; at.q_lo = c->ws_ql; at.o_hi = c->ws_ah; at.o_lo = c->ws_al;
+      at.heads = d.heads; at.kv_heads = d.kv_heads; at.max_ctx = d.max_ctx; at.scale = 1.0f / sqrtf((float)hd);
+      launch_attn_prefill_ragged(c, at, *rg, (long long)((size_t)l * kv_layer), /*allow_lean=*/false);
+    }
+    for (int b = 0; b < NB && !rg; b++) {
       RowState& r = c->rows[(size_t)(row0 + b)];
       const size_t ro = (size_t)b * S;
       tgx::RopeKvArgs a{};
@@ -381,7 +395,7 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S) {
       a.q_norm_w = d.qk_norm ? (const bf16_t*)w.q_norm : nullptr; a.k_norm_w = d.qk_norm ? (const bf16_t*)w.k_norm : nullptr; a.eps = d.norm_eps;
       launch_rope_kv_split(c, a, S);
     }
-    for (int b = 0; b < NB; b++) {
+    for (int b = 0; b < NB && !rg; b++) {
       RowState& r = c->rows[(size_t)(row0 + b)];
       const size_t ro = (size_t)b * S;
       tgx::AttnPrefillArgs a{};
@@ -420,7 +434,9 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S) {
     else if (ds > 1) launch_reduce_rows(c, tgx::GEMM_RESIDUAL, ds, nullptr, c->ws_x, H, M, H, ssq);
     else if (!terms) hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)c->ws_x, (long long)H, H, ssq);
   }
-  for (int b = 0; b < NB; b++)     // the last position of every batch row feeds lm_head
+  for (int i = 0; rg && i < rg->n; i++)
+    (void)hipMemcpyAsync(c->rows[(size_t)rg->rows[i]].x, c->ws_x + ((size_t)rg->first[i] + rg->lens[i] - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, c->stream);
+  for (int b = 0; b < NB && !rg; b++)     // the last position of every batch row feeds lm_head
     (void)hipMemcpyAsync(c->rows[(size_t)(row0 + b)].x, c->ws_x + ((size_t)(b + 1) * S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, c->stream);
 }
 

@@ -67,6 +67,7 @@ ABI = {
     "past_length": (c_int64, [c_void_p]),
     "reset_row": (c_int, [c_void_p, c_int]),
     "forward_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
+    "forward_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -247,6 +248,19 @@ class Model:
         ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
         self._check(self.be.forward_row(self._ctx, row, ids.ctypes.data_as(POINTER(c_int64)), len(ids)))
         self.batch = max(self.batch, row + 1)
+        return self
+
+    def forward_rows(self, rows, prompts):
+        """prefill prompts[i] into rows[i] of the live batch, all in ONE pass (include/tgx.h tgx_forward_rows); the other rows keep their state"""
+        rows = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int32).reshape(-1))
+        ps = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
+        assert len(ps) == len(rows), "one prompt per row"
+        lens = np.ascontiguousarray(np.array([len(p) for p in ps], dtype=np.int32))
+        ids = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(1, dtype=np.int64))
+        self._check(self.be.forward_rows(self._ctx, len(rows), rows.ctypes.data_as(POINTER(c_int32)), ids.ctypes.data_as(POINTER(c_int64)),
+                                         lens.ctypes.data_as(POINTER(c_int32))))
+        if len(rows):
+            self.batch = max(self.batch, int(rows.max()) + 1)
         return self
 
     def sample_row(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0) -> int:

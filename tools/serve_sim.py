@@ -3,7 +3,8 @@
 serving loop would drive it, on the real kernels: a seeded stream of requests (prompt and output lengths uniform in given ranges) served on ONE context by
 
   continuous   every tick: retire the rows that reached their length (tgx_reset_row), admit waiting requests into idle rows while the token budget has room
-               (tgx_forward_row + tgx_sample_row), then ONE tgx_decode call of n <= 16 steps for all rows (n = the shortest remaining output)
+               (tgx_forward_row + tgx_sample_row; with --joint all of the tick's admissions in ONE tgx_forward_rows call), then ONE tgx_decode call of n <= 16
+               steps for all rows (n = the shortest remaining output)
   static       the reference worker's shape taken to a batch: B requests in, decode until the LONGEST is done (finished rows are retired, their slots stay empty),
                then the next B
 
@@ -37,6 +38,7 @@ ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--sampler", default="", help="e.g. 'temperature=0.8,top_p=0.9' (default: greedy)")
 ap.add_argument("--mix", action="store_true", help="per-request sampler settings and seeds through tgx_decode_rows")
 ap.add_argument("--device-stop", action="store_true", help="(with --mix) output lengths as max_new on the device, full 16-step calls")
+ap.add_argument("--joint", action="store_true", help="admit every request that fits in a tick with ONE tgx_forward_rows call, then tgx_sample_row per row")
 args = ap.parse_args()
 B = args.rows
 CFG = GREEDY
@@ -83,6 +85,7 @@ def serve(policy):
         idle = [r for r in range(B) if not length[r]]
         if policy == "continuous" or len(idle) == B:          # static: a new batch only when the whole previous one is done
             reserved = sum(blocks(t) for t in target if t)
+            admit = []
             for r in idle:
                 if not waiting:
                     break
@@ -91,7 +94,9 @@ def serve(policy):
                 if reserved + blocks(L + new + SLACK) > budget:
                     break                                    # the head of the queue waits for room (FIFO)
                 waiting.pop(0)
-                if args.mix:
+                if args.joint:                               # every admission of the tick in ONE tgx_forward_rows call below
+                    admit.append((r, i))
+                elif args.mix:
                     cfg, seed = req_cfg[i]
                     m.forward_row(r, prompts[i]); m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
                     if STOP:
@@ -101,6 +106,16 @@ def serve(policy):
                 length[r], target[r] = L, L + new + SLACK
                 reserved += blocks(L + new + SLACK)
                 produced += 1                                 # the first token came from the prefill's logits
+            if admit:
+                m.forward_rows([r for r, _ in admit], [prompts[i] for _, i in admit])
+                for r, i in admit:
+                    if args.mix:
+                        cfg, seed = req_cfg[i]
+                        m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
+                        if STOP:
+                            m.set_row_stop(r, max_new=reqs[i][1])
+                    else:
+                        m.sample_row(r, CFG, seed=3)
         live = [r for r in range(B) if length[r]]
         if not live:
             raise SystemExit("the budget admits no request")
@@ -135,6 +150,6 @@ def serve(policy):
 
 
 print(f"{desc.name}: {B} rows, max_ctx {args.max_ctx}, prompts {plo}..{phi}, outputs {nlo}..{nhi} tokens, "
-      f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}{', mixed settings' if args.mix else ''}{', device stop' if STOP else ''}", flush=True)
+      f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}{', mixed settings' if args.mix else ''}{', device stop' if STOP else ''}{', joint admission' if args.joint else ''}", flush=True)
 for pol in (["continuous", "static"] if args.policy == "both" else [args.policy]):
     serve(pol)
