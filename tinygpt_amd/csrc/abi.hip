@@ -6,7 +6,6 @@
 // There is NO CPU path in this library: every entry point either runs on the GPU or returns an error.
 #include <climits>
 #include "ctx.h"
-#include "kernels/prefill.h"       // tgx_forward_rows builds the ragged pass's tables (RgSeq, RgItem)
 
 static std::string g_create_err;
 
@@ -200,14 +199,14 @@ static long long nw4_limit(const tgx_ctx* c, int rpl, bool step) {
   if (step && rpl == 1 && c->batch == 1 && oproj_fused_capable(c)) return c->attn_fused_nw4;
   return c->attn_direct_nw4;
 }
-static void update_attn_modes(tgx_ctx* c, int n_positions, int rows_per_launch = -1, bool step = true) {   // rows_per_launch: batch rows that share an attention launch (-1: the batch); step: a decode step (not the chunk rows of a prefill-by-steps pass)
+static void update_attn_modes(tgx_ctx* c, long long past, int n_positions, int rows_per_launch = -1, bool step = true) {   // past: the context the launches start at (an argument: an admission pass starts at 0 whatever the batch's longest row); rows_per_launch: batch rows that share an attention launch (-1: the batch); step: a decode step (not the chunk rows of a prefill-by-steps pass)
   // batches (round 3): the rows themselves fill the chip, so the one-workgroup-per-(kv head, row) form stays ahead of the split form far beyond the
   // batch-1 crossover — Llama-3.2-1B at context 2k: B = 8 1.250 -> 1.105 ms/step, B = 32 2.360 -> 1.680; Mistral-7B at 600: B = 32 6.91 -> 5.47
   const int rpl = rows_per_launch < 0 ? c->batch : rows_per_launch;
   const long long direct_lim = direct_limit(c, rpl, step), nw4_lim = nw4_limit(c, rpl, step);
-  c->attn_direct = c->past + n_positions <= direct_lim;
-  c->attn_nw4 = c->attn_direct && nw4_lim > 0 && c->past + n_positions <= nw4_lim;
-  c->attn_mfma = !c->attn_direct && c->past >= attn_mfma_threshold(c) && c->dt != tgx::DT_F32 && !(c->d.qk_norm && c->d.head_dim == 128 && c->qk_fuse);
+  c->attn_direct = past + n_positions <= direct_lim;
+  c->attn_nw4 = c->attn_direct && nw4_lim > 0 && past + n_positions <= nw4_lim;
+  c->attn_mfma = !c->attn_direct && past >= attn_mfma_threshold(c) && c->dt != tgx::DT_F32 && !(c->d.qk_norm && c->d.head_dim == 128 && c->qk_fuse);
 }
 
 static void launch_decode_step(tgx_ctx* c, const tgx_sampler_cfg& cfg) {
@@ -327,16 +326,8 @@ int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens) {
   return TGX_OK;
 }
 
-static void kv_release_row(tgx_ctx* c, int row) {       // the row's blocks back to the free list; its table entries back to the scratch block
-  if (!c->kv_paged) return;
-  int& have = c->kv_row_nblk[(size_t)row];
-  std::vector<std::pair<int, int>> ch;
-  for (int b = 0; b < have; b++) { const int i = row * c->kv_tbl_stride + b; c->kv_free.push_back(c->kv_tbl_host[(size_t)i]); ch.emplace_back(i, 0); }
-  have = 0;
-  kv_tbl_push(c, ch);
-}
-
-// paged KV: a finished row keeps the blocks its length needs; the ones assigned up front for the steps it did not take go back to the pool
+// paged KV: a finished row keeps the blocks its length needs; the ones assigned up front for the steps it did not take go back to the free list, their table
+// entries back to the scratch block
 static void kv_trim_row(tgx_ctx* c, int row, long long tokens) {
   if (!c->kv_paged) return;
   const int keep = (int)((tokens + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK);
@@ -346,6 +337,7 @@ static void kv_trim_row(tgx_ctx* c, int row, long long tokens) {
   if (keep < have) have = keep;
   kv_tbl_push(c, ch);
 }
+static void kv_release_row(tgx_ctx* c, int row) { kv_trim_row(c, row, 0); }       // all of the row's blocks
 
 // ---- per-row request state (tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows): host-side fields travel BY VALUE in a one-thread launch, stream-ordered
 // behind the steps that still read the old ones (no stream drain, no host buffer that has to outlive the call).  what: ROWQ_* bits
@@ -399,6 +391,43 @@ static void note_sampled(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg
   for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_probs_ok[(size_t)b];
 }
 
+// the engine passes one seed for a whole generation (the draw mixes in position and row): only a CHANGED seed is copied — and that
+// copy must drain the stream, because steps already enqueued still read the old word.  With an unchanged seed tgx_step_async returns
+// without waiting for the previous step (the one-step lookahead of generateAsync, GPTEngine.cpp:196-217)
+static int ensure_seed(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t seed) {
+  const unsigned long long s = seed;
+  if (is_greedy(&cfg) || (c->seed_valid && c->seed_on_dev == s)) return TGX_OK;
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  HIP_OK(c, hipMemcpy(c->seed_dev, &s, 8, hipMemcpyHostToDevice));
+  c->seed_on_dev = s; c->seed_valid = true;
+  return TGX_OK;
+}
+
+// the end of a sequence of eager launches: a launcher that could not issue a kernel fails the call — the kernels issued before the fault advanced the device-side
+// state (position words, caches), so nothing of the failed pass stays in flight and the context is poisoned
+static int launches_ok(tgx_ctx* c) {
+  HIP_OK(c, hipGetLastError());
+  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }
+  LAUNCH_OK(c);
+  return TGX_OK;
+}
+// ... of a prompt pass: the caller's host buffers (ids, tables) may be pageable and reused once the entry point returns
+static int finish_pass(tgx_ctx* c) {
+  const int rc = launches_ok(c);
+  if (rc) return rc;
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  return TGX_OK;
+}
+
+// n steps of the token-log ring [log_cap][batch] from step `start` on (the ring wraps: two pieces), stream-ordered; the caller synchronises
+static int read_tok_log(tgx_ctx* c, int64_t start, int n, int* dst) {
+  const size_t B = (size_t)c->batch;
+  const int64_t s0 = start % c->log_cap, first = std::min<int64_t>(n, c->log_cap - s0);
+  HIP_OK(c, hipMemcpyAsync(dst, c->tok_log + (size_t)s0 * B, (size_t)first * B * 4, hipMemcpyDeviceToHost, c->stream));
+  if (first < n) HIP_OK(c, hipMemcpyAsync(dst + (size_t)first * B, c->tok_log, (size_t)(n - first) * B * 4, hipMemcpyDeviceToHost, c->stream));
+  return TGX_OK;
+}
+
 // rows mode (c->row_union >= 0, tgx_decode_rows): every row samples with its own settings, `cfg` and `seed` are unused, finished rows take no blocks and stay
 // where they are, and the caller updates row_past from the device afterwards (rows may finish on the device)
 static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t seed, int n) {
@@ -408,17 +437,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
       if (!c->row_idle[(size_t)b] && !c->row_fin[(size_t)b]) { int rc = kv_ensure_blocks(c, b, c->row_past[(size_t)b] + n); if (rc) return rc; }
   if (rows) {
     for (int b = 0; b < c->batch; b++) note_sampled(c, b, 1, row_cfg(c, b));
-  } else if (!is_greedy(&cfg)) {
-    // the engine passes one seed for a whole generation (the draw mixes in position and row): only a CHANGED seed is copied — and that
-    // copy must drain the stream, because steps already enqueued still read the old word.  With an unchanged seed tgx_step_async returns
-    // without waiting for the previous step (the one-step lookahead of generateAsync, GPTEngine.cpp:196-217)
-    if (!c->seed_valid || c->seed_on_dev != (unsigned long long)seed) {
-      HIP_OK(c, hipStreamSynchronize(c->stream));
-      const unsigned long long s = seed;
-      HIP_OK(c, hipMemcpy(c->seed_dev, &s, 8, hipMemcpyHostToDevice));
-      c->seed_on_dev = s; c->seed_valid = true;
-    }
-  }
+  } else if (int rc = ensure_seed(c, cfg, seed)) return rc;
   if (!rows) note_sampled(c, 0, c->batch, cfg);
   if (decode_mfma_ok(c)) {   // the batched step's workspace must exist before the step is captured
     int rc = ensure_skinny_ws(c, std::min(c->decode_step_rows, c->batch));
@@ -443,7 +462,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
     const long long lims[2] = {nw4_limit(c, c->batch, true), direct_limit(c, c->batch, true)};
     for (long long lim : lims)
       if (lim > 0 && c->past + 1 <= lim && c->past + m > lim) m = (int)(lim - c->past);
-    update_attn_modes(c, m);
+    update_attn_modes(c, c->past, m);
     if (c->use_graph) {
       const int K = c->graph_steps;
       // any multi-step call captures the K-step graph as well (a short warm-up call then leaves nothing to capture inside a later, longer
@@ -455,14 +474,78 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
       for (; i < m; i++) HIP_OK(c, hipGraphLaunch(c->step_graph, c->stream));
     } else {
       for (int i = 0; i < m; i++) launch_decode_step(c, cfg);
-      HIP_OK(c, hipGetLastError());
-      if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }      // the kernels issued before the fault advanced the device-side state
-      LAUNCH_OK(c);
+      if (int rc = launches_ok(c)) return rc;
     }
     c->past += m;
     if (!rows) for (int b = 0; b < c->batch; b++) c->row_past[(size_t)b] += m;
     c->steps_issued += m;
     remaining -= m;
+  }
+  return TGX_OK;
+}
+
+// ---- prompt passes (tgx_forward, tgx_forward_row, tgx_forward_rows) ------------------------------------------------------------------------------------------
+// The route of a prefill pass.  len: the prompt length the thresholds are tested against; rows: the workspace rows of the pass (tgx_forward: len = seq for a stack of
+// rows = nb * seq; a ragged pass of tgx_forward_rows: both its M).
+//   STEPS   through the decode kernels, up to 4 positions per pass: prompts shorter than 4 tokens / prefill_min_rows, fp32 storage below prefill_f32_min_rows, shapes the GEMM tile does not cover
+//   F32     fp32 storage through the f32-input MFMA (prefill_f32.hip)
+//   SKINNY  16-bit storage, a few rows: the weight stream of a decode step (skinny.hip; limits measured in ctx.h at prefill_skinny_rows)
+//   TILED   16-bit storage through the split-term GEMMs (prefill.hip; every family incl. GPT-2)
+enum PrefillRoute { ROUTE_STEPS, ROUTE_F32, ROUTE_SKINNY, ROUTE_TILED };
+static PrefillRoute prefill_route(const tgx_ctx* c, int len, int rows) {
+  if (!c->prefill_mfma) return ROUTE_STEPS;
+  if (c->dt == tgx::DT_F32) return len >= c->prefill_f32_min_rows ? ROUTE_F32 : ROUTE_STEPS;
+  if (len < std::max(4, c->prefill_min_rows) || !prefill_shapes_ok(c->d)) return ROUTE_STEPS;
+  const bool skinny = !c->gpt2 && c->prefill_skinny && c->d.vocab >= 128 &&
+                      (rows <= 32 ? c->prefill_skinny_rows >= rows : (rows <= c->prefill_skinny_rows && c->d.hidden <= c->prefill_skinny_hidden_max && (rows <= 64 || (c->skinny_dma && c->d.hidden <= c->prefill_skinny_hidden_max_wide))));
+  return skinny ? ROUTE_SKINNY : ROUTE_TILED;
+}
+
+// the workspace of a matrix-core route for M rows, then its launches: NB rows [row0, row0 + NB) of S positions from `past`, or the ragged pass rg
+static int launch_route(tgx_ctx* c, PrefillRoute rt, int M, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr) {
+  int rc = rt == ROUTE_SKINNY ? ensure_skinny_ws(c, M) : ensure_prefill_ws(c, M);
+  if (!rc && rt == ROUTE_F32) rc = ensure_f32_part(c, M);
+  if (rc) return rc;
+  if (rt == ROUTE_F32) launch_prefill_f32(c, row0, NB, S, past);
+  else if (rt == ROUTE_SKINNY) launch_prefill_skinny(c, row0, NB, S, past, rg);
+  else if (rg) launch_prefill_ragged(c, *rg);
+  else launch_prefill(c, row0, NB, S, past);
+  return TGX_OK;
+}
+
+// One pass of nb rows [row0, row0 + nb) over positions past .. past + seq - 1 of each (their ids are in rows[].prompt, their blocks assigned); leaves every row's
+// logits and advances its position word.  `past` is an argument: tgx_forward passes the batch's pastLength, an admission 0 whatever the other rows hold.
+static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past) {
+  const PrefillRoute rt = prefill_route(c, seq, nb * seq);
+  if (rt != ROUTE_STEPS) {
+    // batched prefill on the matrix cores; logits for the last position only (== forward + narrow, GPTEngine.cpp:96-97)
+    const int rc = launch_route(c, rt, nb * seq, row0, nb, seq, past);
+    if (rc) return rc;
+    for (int b = row0; b < row0 + nb;) {
+      const int rem = row0 + nb - b, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
+      launch_lm_head(c, b, R);
+      b += R;
+    }
+    for (int b = row0; b < row0 + nb; b++) launch_add_pos(c, c->rows[(size_t)b].pos, seq);
+    return TGX_OK;
+  }
+  for (int b = row0; b < row0 + nb; b++) {
+    RowState& r = c->rows[(size_t)b];
+    // prefill by steps: up to 4 consecutive positions per pass through the decode kernels — the chunk rows share this row's cache (kv_stride 0), each attends the
+    // keys up to its own position, so the result equals position-by-position passes at a quarter of the weight traffic
+    update_attn_modes(c, past, seq, 1, /*step=*/false);      // the chunk rows of a pass are positions of ONE sequence
+    for (int s0 = 0; s0 < seq;) {
+      const int rem = seq - s0, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
+      launch_embed_chunk(c, r.prompt + s0, R, past + s0);
+      for (int k = 0; k < R; k++) { c->chunk[k].kcache = r.kcache; c->chunk[k].vcache = r.vcache; c->chunk[k].tbl = r.tbl; }
+      launch_layers(c, c->chunk, R, 0);
+      s0 += R;
+      if (s0 == seq) {                                   // the last position's hidden state feeds lm_head; publish token and length
+        (void)hipMemcpyAsync(r.x, c->chunk[R - 1].x, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
+        launch_add_pos(c, r.pos, seq);
+        launch_lm_head(c, b, 1);
+      }
+    }
   }
   return TGX_OK;
 }
@@ -809,55 +892,13 @@ int tgx_forward(tgx_ctx* c, const int64_t* ids, int batch, int seq) {
     if (ids[i] < 0 || ids[i] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
   HIP_OK(c, hipSetDevice(c->device));
   c->batch = batch;
-  // matrix-core prefill: 16-bit storage through the split-term GEMMs (every family incl. GPT-2), fp32 storage through the f32-input MFMA
-  const bool f32_path = c->dt == tgx::DT_F32 && seq >= c->prefill_f32_min_rows && c->prefill_mfma;
-  const bool mfma_path = (f32_path || (seq >= c->prefill_min_rows && seq >= 4 && c->prefill_mfma && c->dt != tgx::DT_F32 && prefill_shapes_ok(c->d)));
   for (int b = 0; b < batch; b++) { int rc = kv_ensure_blocks(c, b, c->past + seq); if (rc) return rc; }
   for (int b = 0; b < batch; b++) HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)b].prompt, ids + (size_t)b * seq, (size_t)seq * 8, hipMemcpyHostToDevice, c->stream));
-  if (mfma_path) {
-    // batched prefill on the matrix cores; logits for the last position only (== forward + narrow, GPTEngine.cpp:96-97).  Batch rows are
-    // stacked into one row block while that stays within 8192 workspace rows (the CLI's 4 short prompts cost one pass over the weights)
-    const int per = std::max(1, std::min(batch, 8192 / seq));
-    for (int row0 = 0; row0 < batch; row0 += per) {
-      const int nb = std::min(per, batch - row0);
-      const bool skinny = !f32_path && !c->gpt2 && c->prefill_skinny && c->d.vocab >= 128 &&     // a few rows: the weight stream of a decode step
-                          (nb * seq <= 32 ? c->prefill_skinny_rows >= nb * seq : (nb * seq <= c->prefill_skinny_rows && c->d.hidden <= c->prefill_skinny_hidden_max && (nb * seq <= 64 || (c->skinny_dma && c->d.hidden <= c->prefill_skinny_hidden_max_wide))));
-      int rc = skinny ? ensure_skinny_ws(c, nb * seq) : ensure_prefill_ws(c, nb * seq);
-      if (rc) return rc;
-      if (f32_path && (rc = ensure_f32_part(c, nb * seq))) return rc;
-      if (f32_path) launch_prefill_f32(c, row0, nb, seq);
-      else if (skinny) launch_prefill_skinny(c, row0, nb, seq); else launch_prefill(c, row0, nb, seq, (int)c->past);   // tgx_forward: every row at the batch's pastLength
-      for (int b = row0; b < row0 + nb;) {
-        const int rem = row0 + nb - b, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
-        launch_lm_head(c, b, R);
-        b += R;
-      }
-      for (int b = row0; b < row0 + nb; b++) launch_add_pos(c, c->rows[(size_t)b].pos, seq);
-    }
-  }
-  for (int b = 0; b < batch && !mfma_path; b++) {
-    RowState& r = c->rows[(size_t)b];
-    // prefill by steps (fp32 storage, GPT-2, prompts shorter than 4 tokens, shapes the GEMM tile does not cover): up to 4 consecutive
-    // positions per pass through the decode kernels — the chunk rows share this row's cache (kv_stride 0), each attends the
-    // keys up to its own position, so the result equals position-by-position passes at a quarter of the weight traffic
-    update_attn_modes(c, seq, 1, /*step=*/false);      // the chunk rows of a pass are positions of ONE sequence
-    for (int s0 = 0; s0 < seq;) {
-      const int rem = seq - s0, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
-      launch_embed_chunk(c, r.prompt + s0, R, (int)c->past + s0);
-      for (int k = 0; k < R; k++) { c->chunk[k].kcache = r.kcache; c->chunk[k].vcache = r.vcache; c->chunk[k].tbl = r.tbl; }
-      launch_layers(c, c->chunk, R, 0);
-      s0 += R;
-      if (s0 == seq) {                                   // the last position's hidden state feeds lm_head; publish token and length
-        (void)hipMemcpyAsync(r.x, c->chunk[R - 1].x, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
-        launch_add_pos(c, r.pos, seq);
-        launch_lm_head(c, b, 1);
-      }
-    }
-  }
-  HIP_OK(c, hipGetLastError());
-  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }   // nothing of a failed pass stays in flight (the prompt copies read the caller's buffer); the caches hold a partial pass
-  LAUNCH_OK(c);
-  HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` may be pageable and reused by the caller
+  // batch rows are stacked into one row block while that stays within 8192 workspace rows (the CLI's 4 short prompts cost one pass over the weights)
+  const int per = std::max(1, std::min(batch, 8192 / seq));
+  for (int row0 = 0; row0 < batch; row0 += per)
+    if (int rc = issue_pass(c, row0, std::min(per, batch - row0), seq, (int)c->past)) return rc;      // every row at the batch's pastLength
+  if (int rc = finish_pass(c)) return rc;
   c->past += seq;
   for (int b = 0; b < batch; b++) { c->row_past[(size_t)b] = c->past; c->row_tok[(size_t)b] = 0; c->row_idle[(size_t)b] = 0; }
   c->have_logits = true;
@@ -884,14 +925,7 @@ int tgx_sample(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* o
   if (!c || !cfg) return TGX_ERR_INVALID;
   if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "no logits to sample from");
   HIP_OK(c, hipSetDevice(c->device));
-  if (!is_greedy(cfg)) {
-    if (!c->seed_valid || c->seed_on_dev != (unsigned long long)seed) {
-      HIP_OK(c, hipStreamSynchronize(c->stream));
-      const unsigned long long s = seed;
-      HIP_OK(c, hipMemcpy(c->seed_dev, &s, 8, hipMemcpyHostToDevice));
-      c->seed_on_dev = s; c->seed_valid = true;
-    }
-  }
+  if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, 0, c->batch, *cfg);
   launch_sample(c, 0, c->batch, *cfg, /*advance_pos=*/false, /*log_step=*/false);
   HIP_OK(c, hipGetLastError());
@@ -922,11 +956,7 @@ int tgx_decode(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int n_step
   if (out_ids && n_steps > 0) {
     const size_t B = (size_t)c->batch;
     std::vector<int> tmp((size_t)n_steps * B);
-    const int64_t s0 = start % c->log_cap;
-    const int64_t first = (s0 + n_steps <= c->log_cap) ? n_steps : c->log_cap - s0;
-    HIP_OK(c, hipMemcpyAsync(tmp.data(), c->tok_log + (size_t)s0 * B, (size_t)first * B * 4, hipMemcpyDeviceToHost, c->stream));
-    if (first < n_steps)
-      HIP_OK(c, hipMemcpyAsync(tmp.data() + (size_t)first * B, c->tok_log, (size_t)(n_steps - first) * B * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_tok_log(c, start, n_steps, tmp.data()))) return rc;
     HIP_OK(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < tmp.size(); i++) out_ids[i] = tmp[i];
     c->last_sampled0 = tmp[(size_t)(n_steps - 1) * B];
@@ -1021,49 +1051,6 @@ int tgx_reset_row(tgx_ctx* c, int row) {
   return TGX_OK;
 }
 
-// the launches of one tgx_forward_row pass: row `row` validated, its blocks assigned, c->past = 0 (the caller restores it).  The prompt runs as a one-row pass of
-// the same prefill paths tgx_forward takes (they address rows by index and read the pass's past from c->past)
-static int issue_row_pass(tgx_ctx* c, int row, const int64_t* ids, int seq) {
-  const bool f32_path = c->dt == tgx::DT_F32 && seq >= c->prefill_f32_min_rows && c->prefill_mfma;
-  const bool mfma_path = (f32_path || (seq >= c->prefill_min_rows && seq >= 4 && c->prefill_mfma && c->dt != tgx::DT_F32 && prefill_shapes_ok(c->d)));
-  RowState& r = c->rows[(size_t)row];
-  int rc = TGX_OK;
-  hipError_t e = hipMemcpyAsync(r.prompt, ids, (size_t)seq * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && c->row_past[(size_t)row] != 0) {                    // a retired row that rode along since its reset: back to position 0
-    e = hipMemsetAsync(r.pos, 0, 4, c->stream);
-    c->row_past[(size_t)row] = 0;
-  }
-  if (e == hipSuccess && mfma_path) {
-    const bool skinny = !f32_path && !c->gpt2 && c->prefill_skinny && c->d.vocab >= 128 &&
-                        (seq <= 32 ? c->prefill_skinny_rows >= seq : (seq <= c->prefill_skinny_rows && c->d.hidden <= c->prefill_skinny_hidden_max && (seq <= 64 || (c->skinny_dma && c->d.hidden <= c->prefill_skinny_hidden_max_wide))));
-    rc = skinny ? ensure_skinny_ws(c, seq) : ensure_prefill_ws(c, seq);
-    if (!rc && f32_path) rc = ensure_f32_part(c, seq);
-    if (!rc) {
-      if (f32_path) launch_prefill_f32(c, row, 1, seq);
-      else if (skinny) launch_prefill_skinny(c, row, 1, seq); else launch_prefill(c, row, 1, seq, /*past=*/0);
-      launch_lm_head(c, row, 1);
-      launch_add_pos(c, r.pos, seq);
-    }
-  } else if (e == hipSuccess) {
-    update_attn_modes(c, seq, 1, /*step=*/false);
-    for (int s0 = 0; s0 < seq;) {
-      const int rem = seq - s0, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
-      launch_embed_chunk(c, r.prompt + s0, R, s0);
-      for (int k = 0; k < R; k++) { c->chunk[k].kcache = r.kcache; c->chunk[k].vcache = r.vcache; c->chunk[k].tbl = r.tbl; }
-      launch_layers(c, c->chunk, R, 0);
-      s0 += R;
-      if (s0 == seq) {
-        (void)hipMemcpyAsync(r.x, c->chunk[R - 1].x, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
-        launch_add_pos(c, r.pos, seq);
-        launch_lm_head(c, row, 1);
-      }
-    }
-  }
-  if (rc) return rc;
-  HIP_OK(c, e);
-  return TGX_OK;
-}
-
 // host state of a row after its prompt pass went through (the caller synchronised)
 static void row_admitted(tgx_ctx* c, int row, int seq) {
   row_req_push(c, row, ROWQ_STATE);       // a new sequence: what the slot counted while it rode along retired is gone (its settings stay)
@@ -1074,42 +1061,12 @@ static void row_admitted(tgx_ctx* c, int row, int seq) {
   if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
 }
 
-int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
-  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
-  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
-  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
-  if (row < 0 || row >= c->d.max_batch || row > c->batch) return set_err(c, TGX_ERR_INVALID, "row %d: a live row [0,%d) or the next free one (max_batch %d)", row, c->batch, c->d.max_batch);
-  if (seq < 1 || seq > c->d.max_ctx) return set_err(c, seq < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "seq %d out of range (context size %d)", seq, c->d.max_ctx);
-  if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
-    return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
-  for (int i = 0; i < seq; i++)
-    if (ids[i] < 0 || ids[i] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
-  HIP_OK(c, hipSetDevice(c->device));
-  const int64_t longest = c->past;
-  const int batch_before = c->batch;
-  c->past = 0;
-  if (c->kv_paged) { kv_release_row(c, row); int rc0 = kv_ensure_blocks(c, row, seq); if (rc0) { c->past = longest; return rc0; } }
-  const int rc = issue_row_pass(c, row, ids, seq);
-  c->past = longest;
-  if (rc) return rc;
-  HIP_OK(c, hipGetLastError());
-  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }
-  LAUNCH_OK(c);
-  HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` may be pageable and reused by the caller
-  c->batch = std::max(batch_before, row + 1);
-  row_admitted(c, row, seq);
-  refresh_longest(c);
-  c->have_logits = true;
-  return TGX_OK;
-}
-
-// ---- tgx_forward_rows (include/tgx.h): n prompts into n rows in ONE prefill pass per group of whole prompts (<= max(8192, longest) workspace rows) -------------
-// Host tables of the call in one buffer, ONE upload: the ids back to back, then per group its RgSeq [n_g], its token -> prompt map [M_g] and its attention work list
-// (kernels/prefill.h), each 16-byte aligned.
-static size_t rg_align(size_t o) { return (o + 15) & ~(size_t)15; }
-
-int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens) {
-  if (!c || !rows || !ids || !lens) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+// ---- admission (include/tgx.h tgx_forward_row, tgx_forward_rows): n prompts, back to back in ids, into the empty rows rows[], each from position 0 whatever the other
+// rows of the batch hold — `past` of every pass is the argument 0, and c->past (the longest live row) moves only through refresh_longest after the passes went through.
+// may_join (tgx_forward_rows): consecutive whole prompts share ONE ragged prefill pass per group of <= max(8192, longest) workspace rows where a matrix-core route
+// takes the group's rows; every other prompt, and every prompt of tgx_forward_row, runs issue_pass's one-row pass.  Only a call with a ragged pass uploads tables
+// (one buffer, ONE upload: per group the tables of ragged_tables, then the call's ids) and holds the four lm_head staging rows.
+static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, bool may_join) {
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
@@ -1141,8 +1098,8 @@ int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids,
   for (long long i = 0; i < total; i++)
     if (ids[i] < 0 || ids[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
   if (c->kv_paged) {
-    // the prompt attention copies a row's block table into LDS (<= 1024 entries)
-    if (c->kv_tbl_stride > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_forward_rows on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
+    // the ragged prompt attention copies a row's block table into LDS (<= 1024 entries)
+    if (may_join && c->kv_tbl_stride > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_forward_rows on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
     // all or nothing: the blocks of the whole call against the free list plus the blocks the target rows give back
     long long need = 0, have = (long long)c->kv_free.size();
     for (int i = 0; i < n; i++) { need += (lens[i] + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK; have += c->kv_row_nblk[(size_t)rows[i]]; }
@@ -1151,15 +1108,12 @@ int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids,
                      tgx::KV_BLOCK, have, c->kv_nblocks - 1, c->kv_budget_tokens);
   }
   HIP_OK(c, hipSetDevice(c->device));
-  const int64_t past_before = c->past;
-  c->past = 0;                       // every target row starts at position 0 (the skinny pass reads the pass's past from the context)
   if (c->kv_paged) {
     for (int i = 0; i < n; i++) kv_release_row(c, rows[i]);
     for (int i = 0; i < n; i++) (void)kv_ensure_blocks(c, rows[i], lens[i]);     // cannot fail: counted above
   }
-  // ---- groups of whole prompts; the ones the matrix-core pass cannot take run tgx_forward_row's one-row passes
-  const bool joint_ok = c->prefill_mfma && c->dt != tgx::DT_F32 && prefill_shapes_ok(d);
-  const int cap = std::max(8192, longest), min_rows = std::max(4, c->prefill_min_rows);
+  // ---- groups of whole prompts: a ragged pass (p.n prompts) where a matrix-core route takes the group's rows, else (p.n = 0) one-row passes
+  const int cap = std::max(8192, longest);
   std::vector<int> first((size_t)n), g_begin;
   std::vector<long long> off((size_t)n + 1, 0);           // prompt i's ids at ids + off[i]
   for (int i = 0, M = 0; i < n; i++) {
@@ -1171,80 +1125,63 @@ int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids,
   g_begin.push_back(n);
   const int n_groups = (int)g_begin.size() - 1;
   std::vector<RaggedPass> passes((size_t)n_groups);
-  std::vector<size_t> o_seq((size_t)n_groups), o_tok((size_t)n_groups), o_item((size_t)n_groups);
-  size_t bytes = rg_align((size_t)total * 8);
+  std::vector<PrefillRoute> route((size_t)n_groups, ROUTE_STEPS);
+  std::vector<size_t> o_tab((size_t)n_groups);
+  std::vector<unsigned char> host;      // the call's buffer (lives until finish_pass has synchronised)
+  size_t bytes = 0;
   for (int g = 0; g < n_groups; g++) {
     RaggedPass& p = passes[(size_t)g];
     const int i0 = g_begin[(size_t)g], i1 = g_begin[(size_t)g + 1];
-    p.n = i1 - i0; p.rows = rows + i0; p.lens = lens + i0; p.first = first.data() + i0;
-    for (int i = i0; i < i1; i++) { p.M += lens[i]; p.longest = std::max(p.longest, (int)lens[i]); p.n_items += ((lens[i] + 127) / 128) * d.heads; }
-    if (!joint_ok || p.M < min_rows) { p.n = 0; continue; }          // a group of one-row passes
-    o_seq[(size_t)g] = bytes; bytes = rg_align(bytes + (size_t)p.n * sizeof(tgx::RgSeq));
-    o_tok[(size_t)g] = bytes; bytes = rg_align(bytes + (size_t)p.M * 4);
-    o_item[(size_t)g] = bytes; bytes = rg_align(bytes + (size_t)p.n_items * sizeof(tgx::RgItem));
+    p.rows = rows + i0; p.lens = lens + i0; p.first = first.data() + i0;
+    for (int i = i0; i < i1; i++) { p.M += lens[i]; p.longest = std::max(p.longest, (int)lens[i]); }
+    if (may_join) route[(size_t)g] = prefill_route(c, p.M, p.M);
+    if (route[(size_t)g] != ROUTE_SKINNY && route[(size_t)g] != ROUTE_TILED) continue;      // (fp32 storage has no ragged pass)
+    p.n = i1 - i0;
+    o_tab[(size_t)g] = bytes; bytes += ragged_tables(c, p, nullptr, nullptr);
   }
-  std::vector<unsigned char> host(bytes, 0);
-  std::memcpy(host.data(), ids, (size_t)total * 8);
-  for (int g = 0; g < n_groups; g++) {
-    RaggedPass& p = passes[(size_t)g];
-    if (!p.n) continue;
-    tgx::RgSeq* sq = reinterpret_cast<tgx::RgSeq*>(host.data() + o_seq[(size_t)g]);
-    int* tok = reinterpret_cast<int*>(host.data() + o_tok[(size_t)g]);
-    tgx::RgItem* it = reinterpret_cast<tgx::RgItem*>(host.data() + o_item[(size_t)g]);
-    std::vector<std::pair<int, int>> blocks;             // (prompt, query block), heaviest first: key tiles descending, ties in prompt order
-    for (int j = 0; j < p.n; j++) {
-      const RowState& r = c->rows[(size_t)p.rows[j]];
-      sq[j].row0 = p.first[j]; sq[j].S = p.lens[j];
-      sq[j].k = reinterpret_cast<bf16_t*>(r.kcache); sq[j].v = reinterpret_cast<bf16_t*>(r.vcache); sq[j].tbl = r.tbl; sq[j].pad = nullptr;
-      for (int s = 0; s < p.lens[j]; s++) tok[p.first[j] + s] = j;
-      for (int qb = 0; qb < (p.lens[j] + 127) / 128; qb++) blocks.emplace_back(j, qb);
+  if (bytes) {
+    const size_t o_ids = bytes;
+    bytes += (size_t)total * 8;
+    if (bytes > c->rg_bytes) {
+      HIP_OK(c, hipStreamSynchronize(c->stream));
+      if (c->rg_buf) (void)hipFree(c->rg_buf);
+      c->rg_buf = nullptr; c->rg_bytes = 0;
+      if (int rc = dev_alloc(c, &c->rg_buf, bytes)) return rc;
+      c->rg_bytes = bytes;
     }
-    auto tiles = [&](const std::pair<int, int>& b) { return std::min(b.second * 128 + 127, p.lens[b.first] - 1) / 64 + 1; };
-    std::stable_sort(blocks.begin(), blocks.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return tiles(x) > tiles(y); });
-    int k = 0;
-    for (const auto& b : blocks)
-      for (int h = 0; h < d.heads; h++) it[k++] = tgx::RgItem{b.first, b.second, h, 0};
-  }
-  int rc = TGX_OK;
-  if (bytes > c->rg_bytes) {
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    if (c->rg_buf) (void)hipFree(c->rg_buf);
-    c->rg_buf = nullptr; c->rg_bytes = 0;
-    if ((rc = dev_alloc(c, &c->rg_buf, bytes))) { c->past = past_before; return rc; }
-    c->rg_bytes = bytes;
-  }
-  if (!c->rg_x) {
-    const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
-    if ((rc = dev_alloc(c, &c->rg_x, 4 * H)) || (rc = dev_alloc(c, &c->rg_logits, 4 * V)) || (rc = dev_alloc(c, &c->rg_part_val, 4 * P)) || (rc = dev_alloc(c, &c->rg_part_idx, 4 * P))) {
-      c->past = past_before;
-      return rc;
+    if (!c->rg_x) {
+      const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
+      int rc;
+      if ((rc = dev_alloc(c, &c->rg_x, 4 * H)) || (rc = dev_alloc(c, &c->rg_logits, 4 * V)) || (rc = dev_alloc(c, &c->rg_part_val, 4 * P)) || (rc = dev_alloc(c, &c->rg_part_idx, 4 * P))) return rc;
     }
+    host.assign(bytes, 0);
+    std::memcpy(host.data() + o_ids, ids, (size_t)total * 8);
+    for (int g = 0; g < n_groups; g++) {
+      RaggedPass& p = passes[(size_t)g];
+      if (!p.n) continue;
+      ragged_tables(c, p, host.data() + o_tab[(size_t)g], c->rg_buf + o_tab[(size_t)g]);
+      p.ids = reinterpret_cast<const long long*>(c->rg_buf + o_ids) + off[(size_t)g_begin[(size_t)g]];
+    }
+    HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
   }
-  hipError_t e = hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream);
-  for (int i = 0; e == hipSuccess && i < n; i++)      // retired rows that rode along since their reset: back to position 0
-    if (c->row_past[(size_t)rows[i]] != 0) { e = hipMemsetAsync(c->rows[(size_t)rows[i]].pos, 0, 4, c->stream); c->row_past[(size_t)rows[i]] = 0; }
+  for (int i = 0; i < n; i++)      // retired rows that rode along since their reset: position word back to 0
+    if (c->row_past[(size_t)rows[i]] != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)rows[i]].pos, 0, 4, c->stream)); c->row_past[(size_t)rows[i]] = 0; }
   std::vector<int> joint;             // prompts that went through a ragged pass: their lm_head comes below, four rows per pass over the weights
-  for (int g = 0; e == hipSuccess && !rc && g < n_groups; g++) {
-    RaggedPass& p = passes[(size_t)g];
+  for (int g = 0; g < n_groups; g++) {
+    const RaggedPass& p = passes[(size_t)g];
     const int i0 = g_begin[(size_t)g], i1 = g_begin[(size_t)g + 1];
-    if (!p.n) {
-      for (int i = i0; i < i1 && !rc; i++) rc = issue_row_pass(c, rows[i], ids + off[(size_t)i], lens[i]);
-      continue;
-    }
-    p.ids = reinterpret_cast<const long long*>(c->rg_buf + (size_t)off[(size_t)i0] * 8);
-    p.seq = reinterpret_cast<const tgx::RgSeq*>(c->rg_buf + o_seq[(size_t)g]);
-    p.tok_seq = reinterpret_cast<const int*>(c->rg_buf + o_tok[(size_t)g]);
-    p.items = reinterpret_cast<const tgx::RgItem*>(c->rg_buf + o_item[(size_t)g]);
-    const bool skinny = !c->gpt2 && c->prefill_skinny && d.vocab >= 128 &&       // tgx_forward's rule on the pass's rows
-                        (p.M <= 32 ? c->prefill_skinny_rows >= p.M : (p.M <= c->prefill_skinny_rows && d.hidden <= c->prefill_skinny_hidden_max && (p.M <= 64 || (c->skinny_dma && d.hidden <= c->prefill_skinny_hidden_max_wide))));
-    rc = skinny ? ensure_skinny_ws(c, p.M) : ensure_prefill_ws(c, p.M);
-    if (rc) break;
-    if (skinny) launch_prefill_skinny(c, 0, 0, 0, &p); else launch_prefill_ragged(c, p);
-    for (int i = i0; i < i1; i++) joint.push_back(i);
+    if (p.n) {
+      if (int rc = launch_route(c, route[(size_t)g], p.M, 0, 0, 0, /*past=*/0, &p)) return rc;
+      for (int i = i0; i < i1; i++) joint.push_back(i);
+    } else
+      for (int i = i0; i < i1; i++) {
+        HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)rows[i]].prompt, ids + off[(size_t)i], (size_t)lens[i] * 8, hipMemcpyHostToDevice, c->stream));
+        if (int rc = issue_pass(c, rows[i], 1, lens[i], /*past=*/0)) return rc;
+      }
   }
-  // lm_head: the call's rows four at a time (tgx_forward's grouping where they are consecutive rows; else gathered into staging rows and scattered back)
+  // lm_head of the ragged passes: the call's rows four at a time (tgx_forward's grouping where they are consecutive rows; else gathered into staging rows and scattered back)
   const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
-  for (size_t k = 0; e == hipSuccess && !rc && k < joint.size();) {
+  for (size_t k = 0; k < joint.size();) {
     const size_t rem = joint.size() - k, real = std::min<size_t>(rem, 4);
     const int R = rem >= 3 ? 4 : (int)rem;
     bool consec = (int)real == R;
@@ -1264,14 +1201,8 @@ int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids,
     }
     k += real;
   }
-  for (size_t k = 0; e == hipSuccess && !rc && k < joint.size(); k++) launch_add_pos(c, c->rows[(size_t)rows[joint[k]]].pos, lens[joint[k]]);
-  c->past = past_before;
-  if (rc) return rc;
-  HIP_OK(c, e);
-  HIP_OK(c, hipGetLastError());
-  if (c->launch_fault) { (void)hipStreamSynchronize(c->stream); c->poisoned = true; }
-  LAUNCH_OK(c);
-  HIP_OK(c, hipStreamSynchronize(c->stream));   // host `ids` and the tables may be pageable
+  for (size_t k = 0; k < joint.size(); k++) launch_add_pos(c, c->rows[(size_t)rows[joint[k]]].pos, lens[joint[k]]);
+  if (int rc = finish_pass(c)) return rc;
   for (int i = 0; i < n; i++) {
     c->batch = std::max(c->batch, rows[i] + 1);
     row_admitted(c, rows[i], lens[i]);
@@ -1281,20 +1212,23 @@ int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids,
   return TGX_OK;
 }
 
+int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
+  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  const int32_t r = row, s = seq;
+  return admit_rows(c, 1, &r, ids, &s, /*may_join=*/false);
+}
+
+int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens) {
+  if (!c || !rows || !ids || !lens) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  return admit_rows(c, n, rows, ids, lens, /*may_join=*/true);
+}
 
 int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_id) {
   if (!c || !cfg) return TGX_ERR_INVALID;
   if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "no logits to sample from");
   if (row < 0 || row >= c->batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->batch);
   HIP_OK(c, hipSetDevice(c->device));
-  if (!is_greedy(cfg)) {
-    if (!c->seed_valid || c->seed_on_dev != (unsigned long long)seed) {
-      HIP_OK(c, hipStreamSynchronize(c->stream));
-      const unsigned long long s = seed;
-      HIP_OK(c, hipMemcpy(c->seed_dev, &s, 8, hipMemcpyHostToDevice));
-      c->seed_on_dev = s; c->seed_valid = true;
-    }
-  }
+  if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, row, 1, *cfg);
   launch_sample(c, row, 1, *cfg, /*advance_pos=*/false, /*log_step=*/false);
   HIP_OK(c, hipGetLastError());
@@ -1365,13 +1299,7 @@ int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new,
   // one readback behind the steps: the ids of the call, every row's position and request state
   std::vector<int> ids((size_t)n_steps * B), pos(B);
   std::vector<tgx::RowReq> req(B);
-  if (n_steps > 0) {
-    const int64_t s0 = start % c->log_cap;
-    const int64_t first = (s0 + n_steps <= c->log_cap) ? n_steps : c->log_cap - s0;
-    HIP_OK(c, hipMemcpyAsync(ids.data(), c->tok_log + (size_t)s0 * B, (size_t)first * B * 4, hipMemcpyDeviceToHost, c->stream));
-    if (first < n_steps)
-      HIP_OK(c, hipMemcpyAsync(ids.data() + (size_t)first * B, c->tok_log, (size_t)(n_steps - first) * B * 4, hipMemcpyDeviceToHost, c->stream));
-  }
+  if (n_steps > 0 && (rc = read_tok_log(c, start, n_steps, ids.data()))) return rc;
   HIP_OK(c, hipMemcpyAsync(pos.data(), c->slab_pos, B * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipMemcpyAsync(req.data(), c->row_req, B * sizeof(tgx::RowReq), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -1474,7 +1402,7 @@ int tgx_profile_decode(tgx_ctx* c, int n_reps, int64_t* launches, double* total_
   HIP_OK(c, hipSetDevice(c->device));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < TGX_KERNEL_COUNT; i++) { launches[i] = 0; total_ms[i] = 0.0; }
-  update_attn_modes(c, 1);
+  update_attn_modes(c, c->past, 1);
   // Each class is launched back-to-back over all layers (every launch streams a different layer's weights, so
   // nothing is served from the Infinity Cache) between two events on the launch stream.  The residual
   // epilogues write to a scratch vector: the model state (x, KV cache up to pastLength, token) is untouched.

@@ -1,9 +1,9 @@
 // ctx.h — the context of the MI355X shim (include/tgx.h) and the host-side launch interface shared by its translation units:
-//   abi.hip          C ABI entry points, weight upload, step graphs, decode loop
+//   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows)
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
-//   prefill.hip      batched MFMA prefill, 16-bit storage (kernels/prefill.h, gemm_dma.h)
+//   prefill.hip      batched MFMA prefill, 16-bit storage (kernels/prefill.h, gemm_dma.h); the device tables of a ragged pass
 //   prefill_f32.hip  batched prefill, fp32 storage (kernels/gemm_f32.h)
 //   skinny.hip       batched decode step / short prompts on the skinny MFMA GEMMs (kernels/skinny*.h)
 // One context = one GPU = one HIP stream; every call comes from one host thread.  There is NO CPU path in this library.
@@ -74,7 +74,8 @@ struct Profiler {
 struct QkvEpi { bf16_t *q_hi = nullptr, *q_lo = nullptr, *k = nullptr, *v = nullptr; int past = 0; const int* tbl = nullptr; };     // past: the position of the pass's first row (RoPE, cache append)
 
 namespace tgx { struct RgSeq; struct RgItem; }
-// one ragged prefill pass of tgx_forward_rows (abi.hip): prompt i at workspace rows [first[i], first[i] + lens[i]) into batch row rows[i], positions 0 .. lens[i] - 1
+// one ragged prefill pass of tgx_forward_rows: prompt i at workspace rows [first[i], first[i] + lens[i]) into batch row rows[i], positions 0 .. lens[i] - 1.
+// abi.hip groups the prompts (the host fields, M, longest) and uploads the call's buffer; ragged_tables (prefill.hip) lays out and fills the device tables
 struct RaggedPass {
   int n = 0, M = 0, longest = 0;
   const int *rows = nullptr, *lens = nullptr, *first = nullptr;   // host [n]
@@ -266,7 +267,7 @@ struct tgx_ctx {
   std::vector<int> kv_free;        // free physical blocks
   std::vector<int> kv_row_nblk;    // blocks assigned to each row
   long long* slab_acc = nullptr;   // [max_batch][hidden], resting at zero between layers
-  // tgx_forward_rows: the call's tables (ids, RaggedPass device arrays; one upload per call) and four staging rows for the lm_head of scattered target rows
+  // tgx_forward_rows: the call's buffer (the RaggedPass device tables, then the ids; one upload per call) and four staging rows for the lm_head of scattered target rows
   unsigned char* rg_buf = nullptr; size_t rg_bytes = 0;
   float *rg_x = nullptr, *rg_logits = nullptr, *rg_part_val = nullptr; int* rg_part_idx = nullptr;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
@@ -345,6 +346,9 @@ bool prefill_shapes_ok(const tgx_model_desc& d);
 int ensure_prefill_ws(tgx_ctx* c, int S);
 void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past);      // past: the rows' common pastLength (their positions are past .. past + S - 1) — explicit, not read from the context
 void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg);           // the same pass over the prompts of rg (every one from position 0)
+// the device tables of p (RgSeq [n], token -> prompt map [M], attention work list [n_items]; each 16-byte aligned) as one block: sets p.n_items and returns the block's
+// size; with `host` (16-byte aligned) it also fills the block there and points p.seq / tok_seq / items into its copy at `dev`
+size_t ragged_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const unsigned char* dev);
 void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg);
 void launch_rope_kv_split_ragged(tgx_ctx* c, const tgx::RopeKvArgs& a, const RaggedPass& rg, long long layer_off);
 void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean);
@@ -356,10 +360,10 @@ void launch_silu_slab_reduce(tgx_ctx* c, int M, int I, int nsplit);
 void launch_embed_rows(tgx_ctx* c, const long long* ids, float* X, int M, int S);
 // ---- prefill_f32.hip (kernels/gemm_f32.h)
 int ensure_f32_part(tgx_ctx* c, int rows);
-void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S);
+void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S, int past);   // past: as launch_prefill
 // ---- skinny.hip (kernels/skinny.h, skinny_ksplit.h, skinny_dma.h)
 bool decode_mfma_ok(const tgx_ctx* c);
 int ensure_skinny_ws(tgx_ctx* c, int rows);
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg);
-void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, const RaggedPass* rg = nullptr);   // rg: a ragged pass of rg->M rows instead of rows [row0, row0 + NB)
+void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB)
 int skinny_set_attrs(tgx_ctx* c);

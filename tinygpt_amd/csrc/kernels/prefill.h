@@ -284,6 +284,9 @@ struct RgSeq {                 // one prompt of the pass
   const void* pad;
 };
 struct RgItem { int seq, qblk, h, pad; };      // one prompt-attention workgroup: (prompt, query block, head)
+// the prompt attention's blocking (attn_prefill_wg below): a workgroup takes ATTN_QBLK queries of one head and walks the keys in tiles of ATTN_KTILE — the launch
+// geometry and the ragged work list (prefill.hip) are derived from the same two numbers
+constexpr int ATTN_QBLK = 128, ATTN_KTILE = 64;
 // rope_kv_split_kernel over every workspace row of the pass in ONE launch: QKV / part / q_hi / q_lo address the whole pass (a.k_cache / v_cache / blk_tbl / past
 // unused); a row finds its prompt in tok_seq, its position = its row - the prompt's first row
 struct RopeRgArgs { RopeKvArgs a; const RgSeq* seq; const int* tok_seq; long long layer_off; };

@@ -302,8 +302,8 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_lean) {
   tgx::AttnPrefillArgs a = a_;
   const int hd = c->d.head_dim;
-  const int nqb = (a.S + 127) / 128, nwg = nqb * a.heads;
-  const size_t lds1 = (size_t)(64 * (hd + 8) + 64 * (hd + 32)) * 2;      // one K tile | V tile pair (kernels/prefill.h)
+  const int nqb = (a.S + tgx::ATTN_QBLK - 1) / tgx::ATTN_QBLK, nwg = nqb * a.heads;
+  const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;      // one K tile | V tile pair (kernels/prefill.h)
   // head_dim 64, three or more workgroups per CU (prompts from ~3k tokens at 32 heads): K / V tiles by LDS-DMA, the next tile's scores under the current tile's
   // softmax (kernels/attn_prefill_dma.h; bit-identical to attn_prefill_kernel): S = 4096 203 -> 177 us per layer, 8192 730 -> 632; at S = 2048 (one round of 512
   // workgroups) the launch lasts as long as its heaviest workgroup's chain of tiles in either form (62-63 us).  Option prefill.attn_dma: 0 never, 1 auto, 2 always
@@ -342,8 +342,8 @@ void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const
   tgx::AttnRgArgs r{};
   r.a = a; r.seq = rg.seq; r.item = rg.items; r.layer_off = layer_off;
   const int hd = c->d.head_dim;
-  const int nqb = (rg.longest + 127) / 128, nwg = nqb * a.heads, total = rg.n_items;
-  const size_t lds1 = (size_t)(64 * (hd + 8) + 64 * (hd + 32)) * 2;
+  const int nqb = (rg.longest + tgx::ATTN_QBLK - 1) / tgx::ATTN_QBLK, nwg = nqb * a.heads, total = rg.n_items;
+  const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
   const bool dma_row = hd == 64 && (c->attn_dma == 2 || (c->attn_dma == 1 && allow_lean && nwg >= 3 * c->num_cus));
   const bool ksplit = !dma_row && nqb >= 2 && (c->attn_ksplit == 2 || (c->attn_ksplit == 1 && (hd == 128 || nwg < 3 * c->num_cus)));
   const bool wide = !ksplit && allow_lean && hd == 64 && total >= 3 * c->num_cus;
@@ -362,6 +362,35 @@ void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const
       else hipLaunchKernelGGL((tgx::attn_prefill_rg_kernel<DT, 128, 1, 1, P>), grid, blk, lds1, c->stream, r))
   };
   if (c->kv_paged) go(std::true_type{}); else go(std::false_type{});
+}
+// the device tables of a ragged pass (ctx.h): built here because the work list's blocking is attn_prefill_rg_kernel's
+size_t ragged_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const unsigned char* dev) {
+  constexpr int QB = tgx::ATTN_QBLK, KT = tgx::ATTN_KTILE;
+  auto align = [](size_t o) { return (o + 15) & ~(size_t)15; };
+  p.n_items = 0;
+  for (int j = 0; j < p.n; j++) p.n_items += ((p.lens[j] + QB - 1) / QB) * c->d.heads;
+  const size_t o_tok = align((size_t)p.n * sizeof(tgx::RgSeq)), o_item = align(o_tok + (size_t)p.M * 4), bytes = align(o_item + (size_t)p.n_items * sizeof(tgx::RgItem));
+  if (!host) return bytes;
+  tgx::RgSeq* sq = reinterpret_cast<tgx::RgSeq*>(host);
+  int* tok = reinterpret_cast<int*>(host + o_tok);
+  tgx::RgItem* it = reinterpret_cast<tgx::RgItem*>(host + o_item);
+  std::vector<std::pair<int, int>> blocks;             // (prompt, query block), heaviest first: key tiles descending, ties in prompt order
+  for (int j = 0; j < p.n; j++) {
+    const RowState& r = c->rows[(size_t)p.rows[j]];
+    sq[j].row0 = p.first[j]; sq[j].S = p.lens[j];
+    sq[j].k = reinterpret_cast<bf16_t*>(r.kcache); sq[j].v = reinterpret_cast<bf16_t*>(r.vcache); sq[j].tbl = r.tbl; sq[j].pad = nullptr;
+    for (int s = 0; s < p.lens[j]; s++) tok[p.first[j] + s] = j;
+    for (int qb = 0; qb < (p.lens[j] + QB - 1) / QB; qb++) blocks.emplace_back(j, qb);
+  }
+  auto tiles = [&](const std::pair<int, int>& b) { return std::min(b.second * QB + QB - 1, p.lens[b.first] - 1) / KT + 1; };
+  std::stable_sort(blocks.begin(), blocks.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return tiles(x) > tiles(y); });
+  int k = 0;
+  for (const auto& b : blocks)
+    for (int h = 0; h < c->d.heads; h++) it[k++] = tgx::RgItem{b.first, b.second, h, 0};
+  p.seq = reinterpret_cast<const tgx::RgSeq*>(dev);
+  p.tok_seq = reinterpret_cast<const int*>(dev + o_tok);
+  p.items = reinterpret_cast<const tgx::RgItem*>(dev + o_item);
+  return bytes;
 }
 // RoPE + cache append + q split of S prompt rows of one batch row
 void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S) {

@@ -61,7 +61,7 @@ int ensure_f32_part(tgx_ctx* c, int rows) {
   return TGX_OK;
 }
 
-void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S) {
+void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S, int past) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd, nq = qd + 2 * kvd;
   const size_t kv_layer = (size_t)d.kv_heads * d.max_ctx * hd * c->esz;
@@ -69,13 +69,13 @@ void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S) {
   float* xn = reinterpret_cast<float*>(c->ws_ah);      // [M][max(H, qd)]: normalised rows, later the attention output
   float* qrows = reinterpret_cast<float*>(c->ws_qh);   // [M][qd] rotated queries
   float* hrows = reinterpret_cast<float*>(c->ws_hh);   // [M][I]
-  hipLaunchKernelGGL((tgx::embed_rows_any_kernel<tgx::DT_F32>), dim3(M), dim3(256), 0, c->stream, (const long long*)c->rows[(size_t)row0].prompt, (const void*)c->embed, (const void*)(c->gpt2 ? c->wpe : nullptr), c->ws_x, H, S, (long long)d.max_ctx, (int)c->past);
-  hipLaunchKernelGGL(tgx::iota_pos_kernel, dim3((S + 255) / 256), dim3(256), 0, c->stream, c->ws_pos, (int)c->past, S);
+  hipLaunchKernelGGL((tgx::embed_rows_any_kernel<tgx::DT_F32>), dim3(M), dim3(256), 0, c->stream, (const long long*)c->rows[(size_t)row0].prompt, (const void*)c->embed, (const void*)(c->gpt2 ? c->wpe : nullptr), c->ws_x, H, S, (long long)d.max_ctx, past);
+  hipLaunchKernelGGL(tgx::iota_pos_kernel, dim3((S + 255) / 256), dim3(256), 0, c->stream, c->ws_pos, past, S);
   auto norm = [&](const ebyte* w, const ebyte* b) {
     if (c->gpt2) hipLaunchKernelGGL((tgx::norm_rows_kernel<tgx::DT_F32, 1, 0>), dim3(M), dim3(256), 0, c->stream, (const float*)c->ws_x, (const void*)w, (const void*)b, d.norm_eps, H, xn, (bf16_t*)nullptr, (bf16_t*)nullptr, (bf16_t*)nullptr);
     else hipLaunchKernelGGL((tgx::norm_rows_kernel<tgx::DT_F32, 0, 0>), dim3(M), dim3(256), 0, c->stream, (const float*)c->ws_x, (const void*)w, (const void*)nullptr, d.norm_eps, H, xn, (bf16_t*)nullptr, (bf16_t*)nullptr, (bf16_t*)nullptr);
   };
-  c->attn_direct = c->past + S <= c->attn_direct_max;
+  c->attn_direct = past + S <= c->attn_direct_max;
   for (int l = 0; l < d.layers; l++) {
     const LayerW& w = c->L[(size_t)l];
     norm(w.in_norm, w.in_norm_b);
@@ -97,7 +97,7 @@ void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S) {
       {                          // causal flash attention on the f32-input MFMA (K / V tiles shared by 128 queries)
         tgx::AttnPrefillF32Args a{};
         a.q = qrows + ro * qd; a.k_cache = reinterpret_cast<const float*>(r.kcache + (size_t)l * kv_layer); a.v_cache = reinterpret_cast<const float*>(r.vcache + (size_t)l * kv_layer);
-        a.out = xn + ro * qd; a.S = S; a.heads = d.heads; a.kv_heads = d.kv_heads; a.max_ctx = d.max_ctx; a.past = (int)c->past;
+        a.out = xn + ro * qd; a.S = S; a.heads = d.heads; a.kv_heads = d.kv_heads; a.max_ctx = d.max_ctx; a.past = past;
         a.scale = 1.0f / sqrtf((float)hd); a.qblk_mirror = 1;
         const dim3 grid((S + 127) / 128, d.heads), blk(256);
         if (hd == 64) hipLaunchKernelGGL((tgx::attn_prefill_f32_kernel<64>), grid, blk, 0, c->stream, a);
