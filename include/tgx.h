@@ -28,6 +28,7 @@ extern "C" {
 /* 3 (round 5): per-row sequence lifecycle (tgx_reset_row / tgx_forward_row / tgx_sample_row / tgx_past_length_row); tgx_get_option added and
  * tgx_engine_read_stats + the options engine.*, pf.*, attn.fold_*, lmhead.fuse_finalize removed since 2. */
 /* (round 7, still 3: additive) per-row sampler settings and device-side stop — tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows. */
+/* (still 3: additive) tgx_forward_rows; tgx_fork_row — a live row copied into other rows, its full paged KV blocks shared by reference. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -239,6 +240,31 @@ TGX_API int tgx_set_row_stop(tgx_ctx* ctx, int row, int32_t max_new, const int32
  * call.  out_finish [batch] (may be NULL): 0 running, 1 stopped on a stop id, 2 reached max_new (the reference's FinishReason Stop / Length). */
 TGX_API int tgx_decode_rows(tgx_ctx* ctx, int n_steps, int64_t* out_ids, int32_t* out_new, int32_t* out_finish);
 
+/* ---- forking a live row (additive to ABI 3) ------------------------------------------------------------------------------------------------------------
+ * n samples of one prompt (n-best / best_of) and a beam or branch taken mid-generation need the same sequence in several rows; the reference's engine rebuilds its
+ * batch per request (src/engine/GPTEngine.cpp:67-84) and would prefill the prompt once per sample.  tgx_fork_row makes dst_rows[i] (i < n) copies of the live
+ * row `src`: the same pastLength, the same cache rows [0, past) bit for bit, the same last logits / argmax partials / hidden row, and src's current token if it has one.
+ *
+ *   Source row        a live, unfinished row < batch.  A retired or finished src (or a row of the batch that holds no sequence) is TGX_ERR_STATE; src outside
+ *                     [0, max_batch) is TGX_ERR_INVALID.
+ *   Destination rows  follow tgx_forward_rows' rules: each a retired row < batch or a new row; the new rows of a call are exactly batch .. batch + k - 1 in any array
+ *                     order (the batch grows by k, up to max_batch); distinct and != src (a duplicate, or src itself, is TGX_ERR_INVALID); a live or finished
+ *                     destination is TGX_ERR_STATE.  n < 1 is TGX_ERR_INVALID.
+ *   Afterwards        a destination is in exactly the state src is in: if src has no current token (fresh from tgx_forward_row) the destination needs
+ *                     tgx_sample_row too; if src has one (mid-generation) the destination carries the same token and is ready for tgx_decode / tgx_decode_rows.
+ *                     Its sampler settings are untouched, its stop state and produced-token count start afresh (as for an admission), and tgx_read_probs has no
+ *                     vector for it until its next sampled step.  src and every row not named keep their state bit for bit.
+ *   Paged KV          the floor(past / 128) FULL blocks of src are shared by reference — a block returns to the pool when the last row that maps it lets go of
+ *                     it (tgx_reset_row / tgx_reset_cache / an admission into the row) — and each destination gets one fresh block for the partial tail when
+ *                     past % 128 != 0: the call needs n * (past % 128 ? 1 : 0) blocks, counted against the free list plus what the destination rows give back
+ *                     before anything is assigned (TGX_ERR_CONTEXT).  The cache is append-only and a shared block is full, so no later call writes into one;
+ *                     tgx_write_kv refuses a range that touches one (TGX_ERR_STATE).  Unpaged: the prefix [0, past) of every layer is copied into each
+ *                     destination's slab.
+ *   ALL OR NOTHING    a refused call changes no row, moves no KV block, leaves kv.free_tokens as it was and does not poison the context.
+ *   Cost              one copy launch per call (per 128 destinations) for all layers, both caches, all destinations and the per-row state, stream-ordered behind
+ *                     the steps already enqueued; the call returns when the copy has finished, like an admission. */
+TGX_API int tgx_fork_row(tgx_ctx* ctx, int src, int n, const int32_t* dst_rows);
+
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);
 TGX_API int32_t tgx_num_layers(const tgx_ctx* ctx);
@@ -258,7 +284,8 @@ TGX_API int tgx_read_kv(tgx_ctx* ctx, int row, int layer, float* k_out, float* v
 /* The inverse of tgx_read_kv: overwrites cache rows [0, n_rows) of (row, layer), n_rows <= pastLength, from fp32 k_in / v_in
  * [n_rows][kv_heads][head_dim] (either may be NULL), rounded once to the cache's storage dtype.  Test/diagnostic use: with the CPU path's
  * cache rows injected, a decode step is compared free of the bf16 KV-rounding floor (the reference's KVCacheManager holds the tensors
- * it was given, CacheManager.h:24-51 — there is nothing to overwrite there). */
+ * it was given, CacheManager.h:24-51 — there is nothing to overwrite there).  Paged KV: a range that touches a block shared with forked rows (tgx_fork_row)
+ * is TGX_ERR_STATE — writing through would change the siblings. */
 TGX_API int tgx_write_kv(tgx_ctx* ctx, int row, int layer, const float* k_in, const float* v_in, int64_t n_rows);
 
 /* Per-kernel-class timing with HIP events on the context's stream (bench.py's roofline leg).  For each

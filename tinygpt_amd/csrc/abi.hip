@@ -6,6 +6,7 @@
 // There is NO CPU path in this library: every entry point either runs on the GPU or returns an error.
 #include <climits>
 #include "ctx.h"
+#include "kernels/kv_fork.h"
 
 static std::string g_create_err;
 
@@ -302,13 +303,54 @@ static int ensure_step_graph(tgx_ctx* c, const tgx_sampler_cfg& cfg, bool want_m
 struct KvTblUpdate { int n; int idx[16]; int val[16]; };
 static __global__ void kv_tbl_set_kernel(int* tbl, KvTblUpdate u) { if ((int)threadIdx.x < u.n) tbl[u.idx[threadIdx.x]] = u.val[threadIdx.x]; }
 
+// (a fork writes whole rows of table entries: more than 16 changes travel 240 at a time)
+struct KvTblUpdateWide { int n; int idx[240]; int val[240]; };
+static __global__ void kv_tbl_set_wide_kernel(int* tbl, KvTblUpdateWide u) { if ((int)threadIdx.x < u.n) tbl[u.idx[threadIdx.x]] = u.val[threadIdx.x]; }
+
 static void kv_tbl_push(tgx_ctx* c, const std::vector<std::pair<int, int>>& changes) {      // (flat table index, value)
+  if (changes.size() > 16) {
+    for (size_t i = 0; i < changes.size(); i += 240) {
+      KvTblUpdateWide u{};
+      u.n = (int)std::min<size_t>(240, changes.size() - i);
+      for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first; u.val[k] = changes[i + (size_t)k].second; c->kv_tbl_host[(size_t)u.idx[k]] = u.val[k]; }
+      hipLaunchKernelGGL(kv_tbl_set_wide_kernel, dim3(1), dim3(256), 0, c->stream, c->kv_tbl, u);
+    }
+    return;
+  }
   for (size_t i = 0; i < changes.size(); i += 16) {
     KvTblUpdate u{};
     u.n = (int)std::min<size_t>(16, changes.size() - i);
     for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first; u.val[k] = changes[i + (size_t)k].second; c->kv_tbl_host[(size_t)u.idx[k]] = u.val[k]; }
     hipLaunchKernelGGL(kv_tbl_set_kernel, dim3(1), dim3(64), 0, c->stream, c->kv_tbl, u);
   }
+}
+
+// Shared blocks (tgx_fork_row): kv_ref[b] = the rows whose tables map physical block b.  A block leaves the free list at count 0 -> 1 and returns to it at 1 -> 0.
+// THE INVARIANT: a block mapped by more than one row is FULL — every position in it is < past of every row that maps it — so no launch
+// ever writes to it (every writer of the cache writes positions >= its row's past).  It is asserted where blocks are assigned: a block handed out for writing must
+// be mapped by nobody (kv_take_block), a block shared by reference must lie wholly below the source's past (kv_share_blocks).  A violation is a bug of this file
+// that would let one sequence write into another's cache: the process stops there (the library is built with NDEBUG, so the check is spelled out).
+#define KV_ASSERT(cond, what)                                                                                   \
+  do {                                                                                                          \
+    if (!(cond)) { fprintf(stderr, "tgx: paged KV invariant violated (%s) at %s:%d\n", what, __FILE__, __LINE__); abort(); } \
+  } while (0)
+static int kv_take_block(tgx_ctx* c) {
+  const int b = c->kv_free.back();
+  c->kv_free.pop_back();
+  KV_ASSERT(c->kv_ref[(size_t)b] == 0, "a block on the free list is still mapped by a row");
+  c->kv_ref[(size_t)b] = 1;
+  return b;
+}
+static void kv_drop_block(tgx_ctx* c, int b) {
+  if (--c->kv_ref[(size_t)b] == 0) c->kv_free.push_back(b);
+}
+// blocks that return to the free list when `row` releases its blocks: only those nobody else maps (a block a forked sibling still maps stays assigned).  Through the
+// entry points an admissible row (retired, or holding no position) holds no block at all — tgx_reset_row released them — so this reads 0 there; it is what keeps the
+// all-or-nothing sums of admit_rows / tgx_fork_row true whatever a row holds.  (A block shared ONLY among the rows of one call is not counted: the sum errs towards refusing.)
+static long long kv_blocks_given_back(const tgx_ctx* c, int row) {
+  long long n = 0;
+  for (int b = 0; b < c->kv_row_nblk[(size_t)row]; b++) n += c->kv_ref[(size_t)c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + b]] == 1;
+  return n;
 }
 
 int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens) {
@@ -321,23 +363,34 @@ int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens) {
     return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %d more blocks of %d tokens, %zu free of %d (option kv.budget_tokens = %d)", row, need - have,
                    tgx::KV_BLOCK, c->kv_free.size(), c->kv_nblocks - 1, c->kv_budget_tokens);
   std::vector<std::pair<int, int>> ch;
-  for (; have < need; have++) { ch.emplace_back(row * c->kv_tbl_stride + have, c->kv_free.back()); c->kv_free.pop_back(); }
+  for (; have < need; have++) ch.emplace_back(row * c->kv_tbl_stride + have, kv_take_block(c));
   kv_tbl_push(c, ch);
   return TGX_OK;
 }
 
 // paged KV: a finished row keeps the blocks its length needs; the ones assigned up front for the steps it did not take go back to the free list, their table
-// entries back to the scratch block
+// entries back to the scratch block.  (A block a forked sibling still maps only loses this row's reference.)
 static void kv_trim_row(tgx_ctx* c, int row, long long tokens) {
   if (!c->kv_paged) return;
   const int keep = (int)((tokens + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK);
   int& have = c->kv_row_nblk[(size_t)row];
   std::vector<std::pair<int, int>> ch;
-  for (int b = keep; b < have; b++) { const int i = row * c->kv_tbl_stride + b; c->kv_free.push_back(c->kv_tbl_host[(size_t)i]); ch.emplace_back(i, 0); }
+  for (int b = keep; b < have; b++) { const int i = row * c->kv_tbl_stride + b; kv_drop_block(c, c->kv_tbl_host[(size_t)i]); ch.emplace_back(i, 0); }
   if (keep < have) have = keep;
   kv_tbl_push(c, ch);
 }
 static void kv_release_row(tgx_ctx* c, int row) { kv_trim_row(c, row, 0); }       // all of the row's blocks
+
+// tgx_fork_row: row `dst` (holding no block) maps the first n_full blocks of `src` by reference
+static void kv_share_blocks(tgx_ctx* c, int src, int dst, int n_full, std::vector<std::pair<int, int>>& ch) {      // ch: the table changes, pushed by the caller
+  KV_ASSERT((long long)n_full * tgx::KV_BLOCK <= c->row_past[(size_t)src] && n_full <= c->kv_row_nblk[(size_t)src] && c->kv_row_nblk[(size_t)dst] == 0, "a block that is not full was about to be shared");
+  for (int b = 0; b < n_full; b++) {
+    const int blk = c->kv_tbl_host[(size_t)src * c->kv_tbl_stride + b];
+    c->kv_ref[(size_t)blk]++;
+    ch.emplace_back(dst * c->kv_tbl_stride + b, blk);
+  }
+  c->kv_row_nblk[(size_t)dst] = n_full;
+}
 
 // ---- per-row request state (tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows): host-side fields travel BY VALUE in a one-thread launch, stream-ordered
 // behind the steps that still read the old ones (no stream drain, no host buffer that has to outlive the call).  what: ROWQ_* bits
@@ -783,6 +836,7 @@ int tgx_finalize(tgx_ctx* c) {
     HIP_OK(c, hipMemset(c->kv_tbl, 0, B * (size_t)c->kv_tbl_stride * 4));
     c->kv_tbl_host.assign(B * (size_t)c->kv_tbl_stride, 0);
     c->kv_row_nblk.assign(B, 0);
+    c->kv_ref.assign((size_t)c->kv_nblocks, 0);
     c->kv_free.clear();
     for (int b = c->kv_nblocks - 1; b >= 1; b--) c->kv_free.push_back(b);
   }
@@ -1101,8 +1155,10 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
     // the ragged prompt attention copies a row's block table into LDS (<= 1024 entries)
     if (may_join && c->kv_tbl_stride > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_forward_rows on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
     // all or nothing: the blocks of the whole call against the free list plus the blocks the target rows give back
-    long long need = 0, have = (long long)c->kv_free.size();
-    for (int i = 0; i < n; i++) { need += (lens[i] + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK; have += c->kv_row_nblk[(size_t)rows[i]]; }
+    long long need = 0;
+    for (int i = 0; i < n; i++) need += (lens[i] + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK;
+    long long have = (long long)c->kv_free.size();
+    for (int i = 0; i < n; i++) have += kv_blocks_given_back(c, rows[i]);      // (a block a forked sibling still maps does not come back)
     if (need > have)
       return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld blocks of %d tokens, %lld free or held by its rows of %d (option kv.budget_tokens = %d)", need,
                      tgx::KV_BLOCK, have, c->kv_nblocks - 1, c->kv_budget_tokens);
@@ -1221,6 +1277,116 @@ int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
 int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens) {
   if (!c || !rows || !ids || !lens) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
   return admit_rows(c, n, rows, ids, lens, /*may_join=*/true);
+}
+
+// ---- tgx_fork_row (include/tgx.h): dst_rows become copies of the live row src.  Paged cache: src's full blocks by reference (kv_share_blocks), one fresh block per
+// destination for the partial tail; slab cache: the prefix [0, past) of every (layer, kv head).  ONE kv_fork_kernel launch carries what has to be copied for all layers,
+// both caches and all destinations, and the per-row state (hidden row, logits, argmax partials, position and token words) rides in the same launch.  Every check comes
+// before anything changes; the launch sequence ends in finish_pass like an admission.
+static void launch_kv_fork(tgx_ctx* c, int src, int n, const int32_t* dst_rows, const int* dst_blk, int src_blk) {
+  const tgx_model_desc& d = c->d;
+  const long long past = c->row_past[(size_t)src];
+  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz;
+  const bool v16 = tok_bytes % 16 == 0;
+  const long long n_tok = c->kv_paged ? past % tgx::KV_BLOCK : past;
+  for (int i0 = 0; i0 < n; i0 += tgx::KV_FORK_MAX_DST) {
+    tgx::KvForkArgs a{};
+    a.k = c->slab_k; a.v = c->slab_v;
+    a.kv_heads = d.kv_heads; a.n_spans = d.layers * d.kv_heads;
+    if (c->kv_paged) {
+      a.head_stride = tgx::KV_BLOCK * tok_bytes; a.id_stride = d.kv_heads * a.head_stride; a.layer_stride = c->kv_nblocks * a.id_stride;
+    } else {
+      a.head_stride = d.max_ctx * tok_bytes; a.layer_stride = d.kv_heads * a.head_stride; a.id_stride = (long long)c->kv_row_elems * (long long)c->esz;
+    }
+    a.span_vecs = n_tok * tok_bytes / (v16 ? 16 : 4);
+    a.n_dst = std::min(n - i0, (int)tgx::KV_FORK_MAX_DST);
+    a.src_row = src; a.src_id = c->kv_paged ? src_blk : src;
+    for (int k = 0; k < a.n_dst; k++) { a.dst_row[k] = dst_rows[i0 + k]; a.dst_id[k] = c->kv_paged ? dst_blk[i0 + k] : dst_rows[i0 + k]; }
+    // the grid from the bytes to move.  x: workgroups inside a span, one per KV_FORK_THREADS * KV_FORK_UNROLL vectors; y: grid rows that walk the 2 * n_spans spans, as
+    // many as keep the launch within eight workgroups per CU for a slab prefix (the chip filled, the rest in the rows' loops) and within 64 workgroups for a paged
+    // tail (at most 127 tokens per span: x = 1 at every released head_dim)
+    const long long per_wg = tgx::KV_FORK_THREADS * tgx::KV_FORK_UNROLL, cap = c->kv_paged ? 64 : 8ll * c->num_cus;
+    const int gx = (int)std::max<long long>(1, std::min<long long>((a.span_vecs + per_wg - 1) / per_wg, cap));
+    a.kv_rows = a.span_vecs ? (int)std::max<long long>(1, std::min<long long>(2ll * a.n_spans, cap / gx)) : 0;
+    const size_t H = (size_t)d.hidden, V = (size_t)d.vocab, P = (size_t)c->lm_grid;
+    a.seg[0] = {reinterpret_cast<unsigned char*>(c->slab_x), (long long)(H * 4), (int)H};
+    a.seg[1] = {reinterpret_cast<unsigned char*>(c->slab_logits), (long long)(V * 4), (int)V};
+    a.seg[2] = {reinterpret_cast<unsigned char*>(c->slab_part_val), (long long)(P * 4), (int)P};
+    a.seg[3] = {reinterpret_cast<unsigned char*>(c->slab_part_idx), (long long)(P * 4), (int)P};
+    a.seg[4] = {reinterpret_cast<unsigned char*>(c->slab_pos), 4, 1};
+    a.seg[5] = {reinterpret_cast<unsigned char*>(c->slab_tok), 4, 1};
+    const int st_rows = ((int)std::min<size_t>(64, (V + 1023) / 1024) + gx - 1) / gx;      // the state part: up to 64 workgroups, a dword per thread and round
+    const dim3 grid((unsigned)gx, (unsigned)(a.kv_rows + st_rows)), block(tgx::KV_FORK_THREADS);
+    if (v16) hipLaunchKernelGGL(tgx::kv_fork_kernel<tgx::u32x4>, grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL(tgx::kv_fork_kernel<unsigned int>, grid, block, 0, c->stream, a);
+  }
+}
+
+int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
+  if (!c || !dst_rows) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "fork before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  // ---- every check before anything changes
+  if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
+  if (src < 0 || src >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "source row %d out of range [0,%d)", src, d.max_batch);
+  std::vector<char> named((size_t)d.max_batch, 0);
+  int n_new = 0;
+  for (int i = 0; i < n; i++) {
+    const int row = dst_rows[i];
+    if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+    if (row == src) return set_err(c, TGX_ERR_INVALID, "row %d is the source of the fork", row);
+    if (named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    named[(size_t)row] = 1;
+    n_new += row >= c->batch;
+  }
+  if (src >= c->batch || c->row_idle[(size_t)src] || c->row_fin[(size_t)src] || c->row_past[(size_t)src] < 1)
+    return set_err(c, TGX_ERR_STATE, "source row %d is not a live, unfinished row of the batch", src);
+  for (int row = c->batch; row < c->batch + n_new; row++)
+    if (row >= d.max_batch || !named[(size_t)row])
+      return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
+  for (int i = 0; i < n; i++) {
+    const int row = dst_rows[i];
+    if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
+      return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
+  }
+  if (((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_fork_row: a cache row of %d bytes", (int)(d.head_dim * c->esz));
+  const long long past = c->row_past[(size_t)src];
+  const int n_full = (int)(past / tgx::KV_BLOCK), tail = (int)(past % tgx::KV_BLOCK);
+  if (c->kv_paged) {
+    // all or nothing: one fresh block per destination for the partial tail, against the free list plus what the destination rows give back
+    long long need = tail ? n : 0, have = (long long)c->kv_free.size();
+    for (int i = 0; i < n; i++) have += kv_blocks_given_back(c, dst_rows[i]);
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the fork needs %lld blocks of %d tokens for the rows' tails, %lld free or held by its rows of %d (option kv.budget_tokens = %d)",
+                     need, tgx::KV_BLOCK, have, c->kv_nblocks - 1, c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  std::vector<int> dst_blk((size_t)n, 0);
+  int src_blk = 0;
+  if (c->kv_paged) {
+    for (int i = 0; i < n; i++) kv_release_row(c, dst_rows[i]);
+    std::vector<std::pair<int, int>> ch;      // the table entries of all destinations in ONE push
+    for (int i = 0; i < n; i++) {
+      kv_share_blocks(c, src, dst_rows[i], n_full, ch);
+      if (!tail) continue;
+      dst_blk[(size_t)i] = kv_take_block(c);            // cannot run dry: counted above
+      ch.emplace_back(dst_rows[i] * c->kv_tbl_stride + n_full, dst_blk[(size_t)i]);
+      c->kv_row_nblk[(size_t)dst_rows[i]] = n_full + 1;
+    }
+    kv_tbl_push(c, ch);
+    if (tail) src_blk = c->kv_tbl_host[(size_t)src * c->kv_tbl_stride + n_full];
+  }
+  launch_kv_fork(c, src, n, dst_rows, dst_blk.data(), src_blk);
+  if (int rc = finish_pass(c)) return rc;
+  for (int i = 0; i < n; i++) {
+    c->batch = std::max(c->batch, dst_rows[i] + 1);
+    row_admitted(c, dst_rows[i], (int)past);
+    c->row_tok[(size_t)dst_rows[i]] = c->row_tok[(size_t)src];      // the token word travelled with the copy
+  }
+  refresh_longest(c);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
 }
 
 int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_id) {
@@ -1364,6 +1530,12 @@ int tgx_read_kv(tgx_ctx* c, int row, int layer, float* k_out, float* v_out) {
 
 int tgx_write_kv(tgx_ctx* c, int row, int layer, const float* k_in, const float* v_in, int64_t n_rows) {
   if (!c || !c->finalized || row < 0 || row >= c->d.max_batch || layer < 0 || layer >= c->d.layers || n_rows < 0 || n_rows > tgx_past_length_row(c, row)) return c ? set_err(c, TGX_ERR_INVALID, "write_kv: row / layer / n_rows out of range") : TGX_ERR_INVALID;
+  if (c->kv_paged)      // a block forked siblings map as well (tgx_fork_row) is not written through: the siblings would change with it
+    for (int64_t t0 = 0; t0 < n_rows; t0 += tgx::KV_BLOCK) {
+      const int blk = c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + (size_t)(t0 / tgx::KV_BLOCK)];
+      if (c->kv_ref[(size_t)blk] > 1)
+        return set_err(c, TGX_ERR_STATE, "write_kv: positions %lld.. of row %d lie in a block shared with %d forked row(s)", (long long)t0, row, c->kv_ref[(size_t)blk] - 1);
+    }
   HIP_OK(c, hipSetDevice(c->device));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   const tgx_model_desc& d = c->d;

@@ -1,5 +1,6 @@
 // ctx.h — the context of the MI355X shim (include/tgx.h) and the host-side launch interface shared by its translation units:
-//   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows)
+//   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows),
+//                    paged-KV block assignment and tgx_fork_row with its copy launch (kernels/kv_fork.h)
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
@@ -266,6 +267,7 @@ struct tgx_ctx {
   std::vector<int> kv_tbl_host;    // its host mirror
   std::vector<int> kv_free;        // free physical blocks
   std::vector<int> kv_row_nblk;    // blocks assigned to each row
+  std::vector<int> kv_ref;         // per physical block: the rows that map it (tgx_fork_row shares a row's FULL blocks by reference; free at 0)
   long long* slab_acc = nullptr;   // [max_batch][hidden], resting at zero between layers
   // tgx_forward_rows: the call's buffer (the RaggedPass device tables, then the ids; one upload per call) and four staging rows for the lm_head of scattered target rows
   unsigned char* rg_buf = nullptr; size_t rg_bytes = 0;

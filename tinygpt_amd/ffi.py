@@ -68,6 +68,7 @@ ABI = {
     "reset_row": (c_int, [c_void_p, c_int]),
     "forward_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "forward_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
+    "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -259,6 +260,16 @@ class Model:
         ids = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(1, dtype=np.int64))
         self._check(self.be.forward_rows(self._ctx, len(rows), rows.ctypes.data_as(POINTER(c_int32)), ids.ctypes.data_as(POINTER(c_int64)),
                                          lens.ctypes.data_as(POINTER(c_int32))))
+        if len(rows):
+            self.batch = max(self.batch, int(rows.max()) + 1)
+        return self
+
+    def fork_row(self, src: int, dst_rows):
+        """make every row of dst_rows (retired rows or the next free ones) a copy of the live row `src` (include/tgx.h tgx_fork_row): same length, cache, logits and
+        current token; on a paged cache the full blocks are shared, only the partial tail block is copied"""
+        rows = np.ascontiguousarray(np.asarray(list(dst_rows), dtype=np.int32).reshape(-1))
+        ptr = rows.ctypes.data_as(POINTER(c_int32)) if len(rows) else (c_int32 * 1)()
+        self._check(self.be.fork_row(self._ctx, src, len(rows), ptr))
         if len(rows):
             self.batch = max(self.batch, int(rows.max()) + 1)
         return self

@@ -4,6 +4,12 @@
 repetitions, each timed from a synchronised device to the call's own device synchronise (the row resets before each repetition are outside the window).
 
     python tools/admit_bench.py [--model llama-3.2-1b] [--dtype bf16] [--reps 10] [--sets 8x64,4x256,16x32,mixed]
+
+--fork N[,N..] measures n-best admission instead (include/tgx.h tgx_fork_row): ONE tgx_forward_row plus ONE tgx_fork_row into N - 1 rows against tgx_forward_rows with
+N copies of the prompt, for every prompt length of --fork-prompts; the fork call is also timed alone, and on slabs its copy rate (bytes read once + written N - 1 times
+over that time) is printed beside it.
+
+    python tools/admit_bench.py --fork 4,16 [--fork-prompts 256,2048]
 """
 import argparse, dataclasses, os, sys, time
 import numpy as np
@@ -19,7 +25,56 @@ ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--sets", default=",".join(SETS))
 ap.add_argument("--max-ctx", type=int, default=1024)
+ap.add_argument("--fork", default="", help="n-best admission: forward_row + fork_row into N - 1 rows against forward_rows of N copies (e.g. 4,16)")
+ap.add_argument("--fork-prompts", default="256,2048")
 args = ap.parse_args()
+
+
+def fork_bench():
+    ns, plens = [int(x) for x in args.fork.split(",")], [int(x) for x in args.fork_prompts.split(",")]
+    B, ctx = max(ns), max(args.max_ctx, max(plens) + 64)
+    for paged in (0, 1):
+        desc = dataclasses.replace(known_desc(args.model, args.dtype), max_batch=B, max_ctx=ctx)
+        m = Model(desc, product_backend())
+        if paged:
+            m.set_option("kv.budget_tokens", B * ((max(plens) + 127) // 128 + 1) * 128)      # room for N separate copies of the longest prompt
+        m.load_synthetic(1234, 0.02).finalize()
+        m.forward(np.zeros((B, 1), dtype=np.int64)); m.sample(GREEDY)
+        esz = 4 if args.dtype == "fp32" else 2
+        for P in plens:
+            p = synth.synth_prompt(desc.vocab, P, 900)
+            for N in ns:
+                def run(fork):
+                    for r in range(B):
+                        m.reset_row(r)
+                    m.synchronize()
+                    t0 = time.perf_counter()
+                    if fork:
+                        m.forward_row(0, p)
+                        t1 = time.perf_counter()
+                        m.fork_row(0, range(1, N))
+                    else:
+                        t1 = t0
+                        m.forward_rows(range(N), [p] * N)
+                    m.synchronize()
+                    t2 = time.perf_counter()
+                    return (t2 - t0) * 1e3, (t2 - t1) * 1e3
+                for _ in range(2):
+                    run(True); run(False)
+                whole, call, copies = [], [], []
+                for _ in range(args.reps):
+                    a, b = run(True); whole.append(a); call.append(b)
+                    copies.append(run(False)[0])
+                w, c, j = float(np.median(whole)), float(np.median(call)), float(np.median(copies))
+                moved = 2 * desc.layers * desc.kv_heads * (P % 128 if paged else P) * desc.head_dim * esz      # bytes read once, written N - 1 times
+                print(f"{desc.name} {args.dtype} {'paged' if paged else 'slabs'} prompt {P:5d} n {N:3d}: forward_row + fork_row {w:7.2f} ms (the fork call {c * 1e3:7.0f} us, "
+                      f"{moved * N / 1e6:7.1f} MB moved = {moved * N / max(c, 1e-9) / 1e6:6.1f} GB/s), forward_rows of {N} copies {j:7.2f} ms, ratio {w / j:.2f}", flush=True)
+        m.close()
+
+
+if args.fork:
+    fork_bench()
+    sys.exit(0)
 sets = [(name, SETS[name]) for name in args.sets.split(",")]
 B = max(len(lens) for _, lens in sets)
 

@@ -12,6 +12,10 @@ With --mix every request draws its own sampler settings (greedy, T 0.8 / top-p 0
 tgx_decode_rows (per-row settings, include/tgx.h); with --device-stop as well, each request's output length is its max_new (tgx_set_row_stop) and every tick
 is a full 16-step tgx_decode_rows call — the rows finish on the device, the host reads their counts back instead of limiting the call to the shortest output.
 
+With --n-best K every request wants K samples of its prompt (T 0.8 / top-p 0.9, seeds s .. s + K - 1, all of the request's output length): the request is admitted into
+K idle rows as ONE tgx_forward_row plus ONE tgx_fork_row (include/tgx.h; on a paged cache the prompt's full blocks are held once) — or, with --n-best-separate, as K
+prompts in one tgx_forward_rows call — and the ticks run tgx_decode_rows.  The mode reports tokens per second and the peak of budget - kv.free_tokens.
+
 The tool reports generated tokens per second, the mean number of live rows per step and what the cache held.  The reference has neither (its server runs one request at
 a time, HttpServer.cpp:118-163; continuous batching and paged attention are README.md:32-34 TODOs): this is the measurement of the kernel half only — no queue, no
 HTTP, synthetic weights; greedy unless --sampler.
@@ -39,6 +43,8 @@ ap.add_argument("--sampler", default="", help="e.g. 'temperature=0.8,top_p=0.9' 
 ap.add_argument("--mix", action="store_true", help="per-request sampler settings and seeds through tgx_decode_rows")
 ap.add_argument("--device-stop", action="store_true", help="(with --mix) output lengths as max_new on the device, full 16-step calls")
 ap.add_argument("--joint", action="store_true", help="admit every request that fits in a tick with ONE tgx_forward_rows call, then tgx_sample_row per row")
+ap.add_argument("--n-best", type=int, default=0, help="K samples per request: one prefill + tgx_fork_row into K - 1 rows (paged KV: --kv-budget)")
+ap.add_argument("--n-best-separate", action="store_true", help="(with --n-best) admit the K samples as K copies of the prompt in one tgx_forward_rows call instead")
 args = ap.parse_args()
 B = args.rows
 CFG = GREEDY
@@ -149,7 +155,68 @@ def serve(policy):
           f"{', paged' if args.kv_budget else ' as slabs'})", flush=True)
 
 
+def serve_nbest(K, fork):
+    """continuous policy over groups of K rows: a request takes K idle rows when the budget has room for its whole life (fork: the prompt's full blocks once)"""
+    from tinygpt_amd.ffi import SamplerCfg
+    warm = SamplerCfg(0.8, 0, 0.9, 0.0)
+    born()
+    nb = lambda n: (n + 127) // 128
+    waiting = list(range(len(reqs)))
+    groups = []                                   # [rows, length, target, reserved tokens]
+    idle = list(range(B))
+    produced = steps = calls = peak_held = 0
+    m.synchronize(); t0 = time.perf_counter()
+    while waiting or groups:
+        reserved = sum(g[3] for g in groups)
+        while waiting and len(idle) >= K:
+            i = waiting[0]
+            L, new = reqs[i]
+            if args.kv_budget:
+                cost = (nb(L + new) * K if not fork else L // 128 + K * (nb(L + new) - L // 128)) * 128
+            else:
+                cost = K * args.max_ctx
+            if reserved + cost > budget:
+                break
+            waiting.pop(0)
+            rows, idle = idle[:K], idle[K:]
+            if fork:
+                m.forward_row(rows[0], prompts[i])
+                if K > 1:
+                    m.fork_row(rows[0], rows[1:])
+            else:
+                m.forward_rows(rows, [prompts[i]] * K)
+            for k, r in enumerate(rows):
+                seed = 1000 * i + k
+                m.sample_row(r, warm, seed=seed); m.set_row_sampler(r, warm, seed)
+            groups.append([rows, L, L + new, cost])
+            reserved += cost
+            produced += K
+        if not groups:
+            raise SystemExit("the budget admits no request")
+        n = min(16, min(g[2] - g[1] for g in groups))
+        m.decode_rows(n)
+        calls += 1; steps += n
+        if args.kv_budget:
+            peak_held = max(peak_held, budget - m.get_option("kv.free_tokens"))
+        for g in groups:
+            g[1] += n; produced += n * K
+        for g in [g for g in groups if g[1] >= g[2]]:
+            for r in g[0]:
+                m.reset_row(r)
+            idle += g[0]
+            groups.remove(g)
+    m.synchronize(); dt = time.perf_counter() - t0
+    held = f"peak of budget - kv.free_tokens {peak_held} tokens = {peak_held // 128} blocks of {budget // 128}" if args.kv_budget else "unpaged"
+    print(f"n-best {K} {'prefill + fork' if fork else 'K separate prompts'}: {len(reqs)} requests, {produced} tokens generated in {dt:.2f} s = {produced / dt:8.0f} tokens/s; "
+          f"{steps} steps in {calls} decode calls; {held}", flush=True)
+
+
 print(f"{desc.name}: {B} rows, max_ctx {args.max_ctx}, prompts {plo}..{phi}, outputs {nlo}..{nhi} tokens, "
       f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}{', mixed settings' if args.mix else ''}{', device stop' if STOP else ''}{', joint admission' if args.joint else ''}", flush=True)
+if args.n_best:
+    if args.mix or args.joint or args.device_stop or args.sampler or args.policy != "both":
+        raise SystemExit("--n-best is a mode of its own (continuous policy, T 0.8 / top-p 0.9 per sample): it takes no --mix / --joint / --device-stop / --sampler / --policy")
+    serve_nbest(args.n_best, not args.n_best_separate)
+    sys.exit(0)
 for pol in (["continuous", "static"] if args.policy == "both" else [args.policy]):
     serve(pol)
