@@ -29,6 +29,7 @@ extern "C" {
  * tgx_engine_read_stats + the options engine.*, pf.*, attn.fold_*, lmhead.fuse_finalize removed since 2. */
 /* (round 7, still 3: additive) per-row sampler settings and device-side stop — tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows. */
 /* (still 3: additive) tgx_forward_rows; tgx_fork_row — a live row copied into other rows, its full paged KV blocks shared by reference. */
+/* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -265,6 +266,38 @@ TGX_API int tgx_decode_rows(tgx_ctx* ctx, int n_steps, int64_t* out_ids, int32_t
  *                     the steps already enqueued; the call returns when the copy has finished, like an admission. */
 TGX_API int tgx_fork_row(tgx_ctx* ctx, int src, int n, const int32_t* dst_rows);
 
+/* ---- extending and truncating a live row (additive to ABI 3) ------------------------------------------------------------------------------------------
+ * The next turn of a conversation, a request's own text after a shared (forked) prefix, a prompt admitted in pieces: "these tokens after that cached prefix" without
+ * tgx_reset_row and a second prefill of the whole sequence.  tgx_extend_row appends ids[0 .. seq) at positions past .. past + seq - 1 of `row`: the result is
+ * GPTModel::forward(inputIds[1, seq]) on a cache that already holds `past` positions, run CAUSALLY — new position i attends the cache and the new positions <= i.
+ * (The reference's attention would run such a call without a mask — isCausal only when qLen == kvLen, Attention.h:108 — and its engine never makes one: it resets
+ * its cache per request.)  So tgx_forward_row(r, A) + tgx_extend_row(r, B) equals tgx_forward_row(r, A + B) up to the order of the fp32 sums.
+ *
+ *   Accepted rows     a live row < batch that holds past >= 1 positions, with or without a current token, and a row that finished in tgx_decode_rows (the row stopped
+ *                     on EOS and the next turn arrives): its finished state is cleared.
+ *   The current token is NOT in the cache — it is the input of the next step.  tgx_extend_row DISCARDS it; a caller who wants it in the sequence passes it as ids[0].
+ *   Refused           a retired or empty row, or row >= batch: TGX_ERR_STATE (use tgx_forward_row).  row outside [0, max_batch), seq < 1, an id out of range, a null
+ *                     pointer: TGX_ERR_INVALID.  past + seq > max_ctx: TGX_ERR_CONTEXT.  A poisoned context: TGX_ERR_STATE.  Paged KV: the blocks for past + seq
+ *                     are counted against the free list before anything is assigned (TGX_ERR_CONTEXT); a cache of more than 1024 blocks per row is
+ *                     TGX_ERR_UNSUPPORTED on the matrix-core routes, as for tgx_forward_rows.
+ *   ALL OR NOTHING    a refused call changes no row, moves no KV block, leaves kv.free_tokens as it was and does not poison the context.
+ *   Afterwards        exactly as tgx_forward_row leaves a row: the last position's logits and argmax partials in the row's slot; no current token until
+ *                     tgx_sample_row (tgx_sample on a one-row batch) — tgx_decode* refuse until then; the sampler settings kept, the stop state and the
+ *                     produced-token count afresh; no tgx_read_probs vector; tgx_past_length = the longest live row.  Rows not named keep their state bit for bit.
+ *   Attention         a pass of <= 128 positions over a long context runs its attention split over the keys (option extend.attn_splits: -1 automatic from a measured
+ *                     context on, 0 never, N >= 1 N splits); the partials are merged in split order, so the result is the same bits from run to run. */
+TGX_API int tgx_extend_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
+/* Rolls a live or finished row back to 1 <= new_len <= past positions: an aborted generation, an edited last message, a prompt that shares only a prefix with what the
+ * row holds (truncate to min(common prefix, new prompt length - 1), then tgx_extend_row the rest).  Cache rows [0, new_len) are untouched; the position word and the
+ * host length move; a finished state is cleared.  The logits of position new_len - 1 no longer exist, so the row then has NO LOGITS AND NO CURRENT TOKEN:
+ * tgx_sample_row on it, tgx_fork_row from it, and tgx_decode / tgx_decode_rows / tgx_step_async / tgx_sample while it is in that state return TGX_ERR_STATE until
+ * tgx_extend_row has run on it (tgx_reset_row ends the state as well).  new_len == past on a row whose logits are in place is a no-op that returns TGX_OK.
+ * new_len < 1 (that is tgx_reset_row) and new_len > past: TGX_ERR_INVALID.  A retired or empty row: TGX_ERR_STATE.
+ * Paged KV: the blocks beyond ceil(new_len / 128) lose this row's reference.  If new_len % 128 != 0 and the block that now holds the tail is shared with forked
+ * siblings, the next append would write into a shared block: the row takes one fresh block, rows [0, new_len % 128) of every layer and both caches are copied into
+ * it in one launch, the table entry is swapped and the shared block loses this row's reference.  With no free block that is TGX_ERR_CONTEXT and nothing changes. */
+TGX_API int tgx_truncate_row(tgx_ctx* ctx, int row, int64_t new_len);
+
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);
 TGX_API int32_t tgx_num_layers(const tgx_ctx* ctx);
@@ -334,6 +367,9 @@ TGX_API int tgx_set_logits(tgx_ctx* ctx, const float* logits, int batch);
  *                  tgx_reset_row / tgx_reset_cache; max_ctx stays the per-row limit.  A call that would need a block when none is free returns TGX_ERR_CONTEXT and
  *                  changes nothing (retire a row, retry).  Results are those of the unpaged cache, bit for bit on the same kernels (tests/test_hip_paged.py);
  *                  tgx_get_option "kv.free_tokens" = the unassigned blocks' worth of tokens (-1 when unpaged)
+ *   "extend.attn_splits"  (default -1) the attention of a tgx_extend_row pass of <= 128 positions (16-bit storage): -1 = split over the keys (kernels/attn_extend.h) from
+ *                  the measured context on, min(32, CUs / heads) splits; 0 = never (the per-row prompt attention, which also serves longer passes, fp32 storage and
+ *                  passes by steps); N >= 1 = N splits (at most one per 64-key tile) wherever the split form applies.  tgx_get_option reads it back
  *   "debug.*"      experiment switches (tools/gemv_dissect.py, tools/attn_dissect.py; live only in a -DTGX_DISSECT=1 build) */
 TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
 

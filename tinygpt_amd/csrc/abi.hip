@@ -430,6 +430,14 @@ static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
   s.temperature = q.temperature; s.top_k = q.top_k; s.top_p = q.top_p; s.min_p = q.min_p;
   return s;
 }
+static int nologits_row(const tgx_ctx* c) {   // a live row of the batch that was truncated and not extended since (tgx_truncate_row), or -1
+  for (int b = 0; b < c->batch; b++) if (c->row_nologits[(size_t)b] && !c->row_idle[(size_t)b]) return b;
+  return -1;
+}
+#define REFUSE_NOLOGITS(c, what)                                                                                                                     \
+  do {                                                                                                                                               \
+    if (nologits_row(c) >= 0) return set_err((c), TGX_ERR_STATE, "%s: row %d was truncated and holds no logits: tgx_extend_row it first", what, nologits_row(c)); \
+  } while (0)
 static int finished_row(const tgx_ctx* c) {   // a live row of the batch that finished on the device, or -1
   for (int b = 0; b < c->batch; b++) if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b]) return b;
   return -1;
@@ -907,6 +915,7 @@ int tgx_finalize(tgx_ctx* c) {
   c->row_past.assign(B, 0);
   c->row_tok.assign(B, 0);
   c->row_idle.assign(B, 0);
+  c->row_nologits.assign(B, 0);
   c->finalized = true;
   return TGX_OK;
 }
@@ -918,7 +927,7 @@ void tgx_destroy(tgx_ctx* c) {
   drop_step_graphs(c);
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(c->embed); fr(c->lm_head); fr(c->final_norm); fr(c->wpe); fr(c->final_norm_b); fr(c->rope_cos); fr(c->rope_sin); fr(c->step); fr(c->step_done); fr(c->tok_log); fr(c->scratch_x); fr(c->seed_dev); fr(c->samp_scratch); fr(c->samp_list_comp); fr(c->samp_list_v);
-  fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req);
+  fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req); fr(c->ext_part);
   fr(c->rg_buf); fr(c->rg_x); fr(c->rg_logits); fr(c->rg_part_val); fr(c->rg_part_idx);
   fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
   fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_part); fr(c->ws_ssq); fr(c->ws_pos);
@@ -954,7 +963,7 @@ int tgx_forward(tgx_ctx* c, const int64_t* ids, int batch, int seq) {
     if (int rc = issue_pass(c, row0, std::min(per, batch - row0), seq, (int)c->past)) return rc;      // every row at the batch's pastLength
   if (int rc = finish_pass(c)) return rc;
   c->past += seq;
-  for (int b = 0; b < batch; b++) { c->row_past[(size_t)b] = c->past; c->row_tok[(size_t)b] = 0; c->row_idle[(size_t)b] = 0; }
+  for (int b = 0; b < batch; b++) { c->row_past[(size_t)b] = c->past; c->row_tok[(size_t)b] = 0; c->row_idle[(size_t)b] = 0; c->row_nologits[(size_t)b] = 0; }
   c->have_logits = true;
   c->have_token = false;
   c->have_probs = false;                          // the logits are new: no sampled step belongs to them yet
@@ -978,6 +987,7 @@ int tgx_read_logits(tgx_ctx* c, float* out, int rounded) {
 int tgx_sample(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_ids) {
   if (!c || !cfg) return TGX_ERR_INVALID;
   if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "no logits to sample from");
+  REFUSE_NOLOGITS(c, "tgx_sample");
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, 0, c->batch, *cfg);
@@ -998,6 +1008,7 @@ int tgx_sample(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* o
 int tgx_decode(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int n_steps, int64_t* out_ids) {
   if (!c || !cfg || n_steps < 0) return TGX_ERR_INVALID;
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  REFUSE_NOLOGITS(c, "tgx_decode");
   if (!c->have_token) return set_err(c, TGX_ERR_STATE, "decode needs a current token: call tgx_sample after tgx_forward");
   if (finished_row(c) >= 0) return set_err(c, TGX_ERR_STATE, "row %d finished in tgx_decode_rows: tgx_reset_row it first (tgx_decode would advance it)", finished_row(c));
   if (c->past + n_steps > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, n_steps, c->d.max_ctx);
@@ -1021,6 +1032,7 @@ int tgx_decode(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int n_step
 int tgx_step_async(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_ticket) {
   if (!c || !cfg || !out_ticket) return TGX_ERR_INVALID;
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  REFUSE_NOLOGITS(c, "tgx_step_async");
   if (!c->have_token) return set_err(c, TGX_ERR_STATE, "step needs a current token: call tgx_sample after tgx_forward");
   if (finished_row(c) >= 0) return set_err(c, TGX_ERR_STATE, "row %d finished in tgx_decode_rows: tgx_reset_row it first (tgx_step_async would advance it)", finished_row(c));
   if (c->past + 1 > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded");
@@ -1059,6 +1071,7 @@ int tgx_reset_cache(tgx_ctx* c) {
   std::fill(c->row_past.begin(), c->row_past.end(), 0);
   std::fill(c->row_tok.begin(), c->row_tok.end(), 0);
   std::fill(c->row_idle.begin(), c->row_idle.end(), 0);
+  std::fill(c->row_nologits.begin(), c->row_nologits.end(), 0);
   c->have_logits = c->have_token = false;
   c->poisoned = false;
   return TGX_OK;
@@ -1100,6 +1113,7 @@ int tgx_reset_row(tgx_ctx* c, int row) {
   row_req_reset(c, row);                                                      // tgx_decode_rows: default settings, not finished
   c->row_past[(size_t)row] = 0;
   c->row_tok[(size_t)row] = 0;
+  c->row_nologits[(size_t)row] = 0;
   c->row_idle[(size_t)row] = row < c->batch;                                  // a live slot becomes a retired one: the batch keeps stepping without it
   refresh_longest(c);
   return TGX_OK;
@@ -1112,6 +1126,7 @@ static void row_admitted(tgx_ctx* c, int row, int seq) {
   c->row_past[(size_t)row] = seq;
   c->row_tok[(size_t)row] = 0;
   c->row_idle[(size_t)row] = 0;
+  c->row_nologits[(size_t)row] = 0;
   if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
 }
 
@@ -1342,6 +1357,7 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
   }
   if (src >= c->batch || c->row_idle[(size_t)src] || c->row_fin[(size_t)src] || c->row_past[(size_t)src] < 1)
     return set_err(c, TGX_ERR_STATE, "source row %d is not a live, unfinished row of the batch", src);
+  if (c->row_nologits[(size_t)src]) return set_err(c, TGX_ERR_STATE, "source row %d was truncated and holds no logits: tgx_extend_row it first", src);
   for (int row = c->batch; row < c->batch + n_new; row++)
     if (row >= d.max_batch || !named[(size_t)row])
       return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
@@ -1389,10 +1405,110 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
   return TGX_OK;
 }
 
+// ---- tgx_extend_row / tgx_truncate_row (include/tgx.h): a live row grows by several positions in one pass, or is rolled back.  The pass is issue_pass's one-row pass
+// with the row's real length as `past` (every route takes it); the row then stands as tgx_forward_row leaves one.  Every check comes before anything changes.
+int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
+  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "extend before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+  if (seq < 1) return set_err(c, TGX_ERR_INVALID, "seq %d < 1", seq);
+  if (row >= c->batch || c->row_idle[(size_t)row] || c->row_past[(size_t)row] < 1)
+    return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to extend: use tgx_forward_row", row);
+  const long long past = c->row_past[(size_t)row];
+  if (past + seq > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, seq, d.max_ctx);
+  for (int i = 0; i < seq; i++)
+    if (ids[i] < 0 || ids[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
+  if (c->kv_paged) {
+    const PrefillRoute rt = prefill_route(c, seq, seq);
+    if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv_tbl_stride > 1024)      // the prompt attention copies the row's block table into LDS (<= 1024 entries)
+      return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_extend_row on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
+    const long long need = (past + seq + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK - c->kv_row_nblk[(size_t)row];
+    if (need > (long long)c->kv_free.size())
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %zu free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
+                     c->kv_free.size(), c->kv_nblocks - 1, c->kv_budget_tokens);
+    // (the block the first new position falls into is the row's own: a block forked siblings map as well is full, and tgx_truncate_row copies before it leaves a row inside one)
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = ensure_extend_ws(c, seq, (int)past)) return rc;
+  (void)kv_ensure_blocks(c, row, past + seq);      // cannot fail: counted above
+  HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)seq * 8, hipMemcpyHostToDevice, c->stream));
+  if (int rc = issue_pass(c, row, 1, seq, (int)past)) return rc;
+  if (int rc = finish_pass(c)) return rc;
+  row_admitted(c, row, (int)(past + seq));         // no current token, a fresh stop state (a finished row runs again), the sampler settings kept
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+// paged KV: rows [0, n_tok) of every (layer, kv head) of both caches from block src_blk into block dst_blk — the cache part of the fork's copy launch alone
+// (kernels/kv_fork.h: a grid without the state rows behind the cache part's)
+static void launch_kv_tail_copy(tgx_ctx* c, int src_blk, int dst_blk, int n_tok) {
+  const tgx_model_desc& d = c->d;
+  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz;
+  const bool v16 = tok_bytes % 16 == 0;
+  tgx::KvForkArgs a{};
+  a.k = c->slab_k; a.v = c->slab_v;
+  a.kv_heads = d.kv_heads; a.n_spans = d.layers * d.kv_heads;
+  a.head_stride = tgx::KV_BLOCK * tok_bytes; a.id_stride = d.kv_heads * a.head_stride; a.layer_stride = c->kv_nblocks * a.id_stride;
+  a.span_vecs = n_tok * tok_bytes / (v16 ? 16 : 4);
+  a.n_dst = 1; a.src_id = src_blk; a.dst_id[0] = dst_blk;
+  a.kv_rows = std::min(2 * a.n_spans, 64);
+  const dim3 grid(1, (unsigned)a.kv_rows), block(tgx::KV_FORK_THREADS);      // (at most 127 tokens per span: one workgroup covers it at every released head_dim)
+  if (v16) hipLaunchKernelGGL(tgx::kv_fork_kernel<tgx::u32x4>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(tgx::kv_fork_kernel<unsigned int>, grid, block, 0, c->stream, a);
+}
+
+int tgx_truncate_row(tgx_ctx* c, int row, int64_t new_len) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "truncate before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+  if (row >= c->batch || c->row_idle[(size_t)row] || c->row_past[(size_t)row] < 1) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to truncate", row);
+  const long long past = c->row_past[(size_t)row];
+  if (new_len < 1) return set_err(c, TGX_ERR_INVALID, "new_len %lld < 1: tgx_reset_row empties a row", (long long)new_len);
+  if (new_len > past) return set_err(c, TGX_ERR_INVALID, "new_len %lld beyond the %lld positions row %d holds", (long long)new_len, past, row);
+  // nothing to roll back and the logits in the slot are those of the last position held: the row stays as it is
+  if (new_len == past && !c->row_fin[(size_t)row] && !c->row_nologits[(size_t)row]) return TGX_OK;
+  const int keep = (int)((new_len + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK), tail = (int)(new_len % tgx::KV_BLOCK);
+  int shared_blk = 0;      // the block that holds the new tail, where forked siblings map it as well: the next append would write into it
+  if (c->kv_paged && tail) {
+    const int blk = c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + keep - 1];
+    if (c->kv_ref[(size_t)blk] > 1) shared_blk = blk;
+  }
+  if (shared_blk && c->kv_free.empty())
+    return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: truncating row %d to %lld leaves it inside a block shared with %d forked row(s) and no block is free for its copy (option kv.budget_tokens = %d)",
+                   row, (long long)new_len, c->kv_ref[(size_t)shared_blk] - 1, c->kv_budget_tokens);
+  if (shared_blk && ((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_truncate_row: a cache row of %d bytes", (int)(d.head_dim * c->esz));
+  // ---- nothing above changed anything: "a refused call changes nothing" is about those checks.  From here on the host bookkeeping (blocks, table) moves ahead of the
+  // launches; should one of them not issue, launches_ok poisons the context — the row's lengths then stay as they were, and only tgx_reset_cache follows
+  HIP_OK(c, hipSetDevice(c->device));
+  if (shared_blk) {        // copy on write, before any append can happen: rows [0, tail) into a fresh block, the table entry swapped, this row's reference dropped
+    const int fresh = kv_take_block(c);
+    launch_kv_tail_copy(c, shared_blk, fresh, tail);
+    kv_tbl_push(c, {{row * c->kv_tbl_stride + keep - 1, fresh}});
+    kv_drop_block(c, shared_blk);
+  }
+  kv_trim_row(c, row, new_len);                                         // the blocks beyond the new length (a shared one only loses this row's reference)
+  if (new_len != past) launch_add_pos(c, c->rows[(size_t)row].pos, (int)(new_len - past));      // stream-ordered behind the steps already enqueued
+  if (c->row_fin[(size_t)row]) { row_req_push(c, row, ROWQ_STATE); c->row_fin[(size_t)row] = 0; }
+  if (int rc = launches_ok(c)) return rc;
+  c->row_past[(size_t)row] = new_len;
+  c->row_tok[(size_t)row] = 0;
+  c->row_nologits[(size_t)row] = 1;                                     // the logits of position new_len - 1 no longer exist
+  if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
+  refresh_longest(c);
+  return TGX_OK;
+}
+
 int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* out_id) {
   if (!c || !cfg) return TGX_ERR_INVALID;
   if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "no logits to sample from");
   if (row < 0 || row >= c->batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->batch);
+  if (c->row_nologits[(size_t)row]) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, row, 1, *cfg);
@@ -1444,6 +1560,7 @@ int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new,
   int running = 0;
   for (int b = 0; b < c->batch; b++) running += !c->row_idle[(size_t)b] && !c->row_fin[(size_t)b];
   if (!running) return set_err(c, TGX_ERR_STATE, "tgx_decode_rows: no live row is unfinished (tgx_reset_row / tgx_forward_row a row first)");
+  REFUSE_NOLOGITS(c, "tgx_decode_rows");
   if (!c->have_token) return set_err(c, TGX_ERR_STATE, "decode needs a current token: call tgx_sample / tgx_sample_row after the forward");
   if (c->past + n_steps > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, n_steps, c->d.max_ctx);
   for (int b = 0; b < c->batch; b++)      // a finished row rides at its own length: one that holds the whole context has no row left to ride on
@@ -1642,6 +1759,7 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "graph.steps")) { *out_value = c->graph_steps; return TGX_OK; }
   if (!strcmp(key, "act.round16")) { *out_value = c->act16; return TGX_OK; }
   if (!strcmp(key, "kv.budget_tokens")) { *out_value = c->kv_budget_tokens; return TGX_OK; }
+  if (!strcmp(key, "extend.attn_splits")) { *out_value = c->extend_attn_splits; return TGX_OK; }
   if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv_free.size() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
   return TGX_ERR_INVALID;
 }
@@ -1708,6 +1826,7 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "skinny.cfg")) { if (value < -1 || value > 2) return set_err(c, TGX_ERR_INVALID, "skinny.cfg is -1..2"); c->skinny_cfg_force = value; return TGX_OK; }
   if (!strcmp(key, "decode.mfma_min_batch")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "decode.mfma_min_batch must be >= 1"); c->decode_mfma_min = value; return TGX_OK; }
   if (!strcmp(key, "debug.profile_same_layer")) { c->prof_same_layer = value; return TGX_OK; }
+  if (!strcmp(key, "extend.attn_splits")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "extend.attn_splits is -1 (automatic), 0 (never) or a split count"); c->extend_attn_splits = value; return TGX_OK; }
   if (!strcmp(key, "oproj.sliced")) { drop_step_graphs(c); c->oproj_sliced = value != 0; return TGX_OK; }
   if (!strcmp(key, "kv.budget_tokens")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "kv.budget_tokens is set before tgx_finalize (it sizes the caches)");

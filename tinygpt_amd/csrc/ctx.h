@@ -272,6 +272,20 @@ struct tgx_ctx {
   // tgx_forward_rows: the call's buffer (the RaggedPass device tables, then the ids; one upload per call) and four staging rows for the lm_head of scattered target rows
   unsigned char* rg_buf = nullptr; size_t rg_bytes = 0;
   float *rg_x = nullptr, *rg_logits = nullptr, *rg_part_val = nullptr; int* rg_part_idx = nullptr;
+  // ---- tgx_extend_row / tgx_truncate_row (include/tgx.h).  row_nologits: the row was truncated and not extended since — its slot's logits belong to a position it no
+  // longer holds, so nothing may sample, step or fork from it.
+  std::vector<char> row_nologits;
+  // option extend.attn_splits: the key-split attention of a continuation pass of <= 128 positions (kernels/attn_extend.h): -1 automatic, 0 never (the per-row prompt
+  // attention with `past`), N >= 1 N splits (clamped to the key tiles).  Automatic: min(32, CUs / heads) splits once past + S exceeds extend_attn_min{64,128} (head_dim)
+  // — the smallest measured context at which the split form wins by more than the spread of the measurement at every extension length (tools/admit_bench.py --extend,
+  // profiles/extend_row.txt; ms per tgx_extend_row, per-row kernel / 8 splits, S = 16 / 64 / 128 new tokens):
+  //   Llama-3.2-1B (head_dim 64, 16 layers)   past 256: 1.066 / 1.009, 1.345 / 1.332, 1.812 / 1.793 (the last two inside the spread)   past 512: 1.189 / 1.061, 1.441 / 1.369, 1.916 / 1.836
+  //                                           past 2048: 1.884 / 1.165, 1.939 / 1.433, 2.398 / 1.897     past 8192: 4.625 / 1.492, 3.968 / 1.713, 4.463 / 2.169
+  //   Mistral-7B shapes (head_dim 128, 2 layers)  past 512: 0.360 / 0.344, 0.482 / 0.475, 0.646 / 0.634 (about one spread: the same kernel read 0.360 and 0.374 in that run)
+  //                                           past 1024: 0.401 / 0.348, 0.510 / 0.476, 0.673 / 0.635     past 8192: 0.933 / 0.418, 0.945 / 0.541, 1.108 / 0.698
+  int extend_attn_splits = -1;
+  int extend_attn_min64 = 512, extend_attn_min128 = 1024;
+  float* ext_part = nullptr; size_t ext_part_bytes = 0;      // the splits' partials [ns][heads][attn_extend_part_vals][256] (kernels/attn_extend.h)
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -355,6 +369,8 @@ void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg);
 void launch_rope_kv_split_ragged(tgx_ctx* c, const tgx::RopeKvArgs& a, const RaggedPass& rg, long long layer_off);
 void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean);
 int prefill_set_attrs(tgx_ctx* c);
+int extend_attn_splits(const tgx_ctx* c, int S, int past);   // key splits of a continuation pass's attention (0: the per-row prompt attention)
+int ensure_extend_ws(tgx_ctx* c, int S, int past);           // ... and their partials' workspace, before the pass is issued
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean);
 void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S);
 void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, int nsplit, bool third = false);

@@ -533,6 +533,52 @@ struct AttnPrefillArgs {
   const int* blk_tbl;            // paged KV (kernel template PAGED): this sequence's block table, k_cache / v_cache = the layer's pools
 };
 
+// The end of a prompt-attention workgroup: normalise a wave's 32 queries and emit them as hi / lo 16-bit pairs (the o_proj GEMM's A operand).  A lane holds ONE
+// query's output dims (oacc[b][r]: dim 32 b + (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of query q0 + (lane & 31)), so direct stores would be 2-byte writes 4 KB apart
+// (64 cache lines per instruction: ~20 µs of the kernel at S = 2048); instead each wave transposes its 32 x HD block through LDS (wrow: 32 rows of 2 HD + 8 bytes,
+// conflict-free 4-byte column writes) and stores whole rows, 16 bytes per lane.
+template <int DT, int HD>
+__device__ __forceinline__ void attn_emit_rows(const AttnPrefillArgs& a, const int h, const int q0, const bool qvalid, const f32x16 (&oacc)[HD / 32], const float l_run,
+                                               bf16_t* const wrow, const int lane) {
+  constexpr int NB = HD / 32, CH = HD / 8;
+  constexpr int RS = HD + 4;                    // staged row stride in 16-bit elements
+  const int hh = lane >> 5, ql = lane & 31, qd = a.heads * HD;
+  const float inv_l = qvalid ? 1.0f / l_run : 0.f;
+  unsigned int whi[NB * 8], wlo[NB * 8];
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const float v0 = oacc[b][r] * inv_l, v1 = oacc[b][r + 1] * inv_l;
+      bf16_t h0, l0, h1, l1;
+      split16<DT>(v0, h0, l0);
+      split16<DT>(v1, h1, l1);
+      whi[b * 8 + (r >> 1)] = (unsigned int)h0 | ((unsigned int)h1 << 16);
+      wlo[b * 8 + (r >> 1)] = (unsigned int)l0 | ((unsigned int)l1 << 16);
+    }
+#pragma unroll
+  for (int term = 0; term < 2; term++) {
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const int d = 32 * b + (r & 3) + 8 * (r >> 2) + 4 * hh;                 // dims d, d + 1
+        *reinterpret_cast<unsigned int*>(wrow + ql * RS + d) = term ? wlo[b * 8 + (r >> 1)] : whi[b * 8 + (r >> 1)];
+      }
+    bf16_t* const dst = term ? a.o_lo : a.o_hi;
+#pragma unroll
+    for (int i = 0; i < HD / 16; i++) {          // 32 rows x HD / 8 chunks of 16 bytes over 64 lanes
+      const int c = lane + 64 * i, row = c / CH, cc = c - row * CH;
+      const u32x2 p0 = *reinterpret_cast<const u32x2*>(wrow + row * RS + cc * 8);
+      const u32x2 p1 = *reinterpret_cast<const u32x2*>(wrow + row * RS + cc * 8 + 4);
+      if (q0 + row < a.S)
+        *reinterpret_cast<u32x4*>(dst + (size_t)(q0 + row) * qd + (size_t)h * HD + cc * 8) = u32x4{p0[0], p0[1], p1[0], p1[1]};
+    }
+  }
+}
+template <int HD>
+constexpr int attn_extend_part_vals() { return HD / 32 * 16 + 2; }      // a SPLIT workgroup's record per lane: the O registers, then m, then l
+
 // Scores and probabilities never leave the registers (the first version of this round routed them through LDS with four
 // barriers per tile: 262 us per layer at S = 2048 against 165 us for this one).
 // One workgroup = 128 queries of one query head (4 waves x 32 queries); K / V tiles of 64 keys go global -> registers -> LDS
@@ -556,8 +602,11 @@ struct AttnPrefillArgs {
 // PAGED (round 6): the workgroup copies the part of the sequence's block table it needs (<= 1024 entries) into LDS first; a K / V row's address then takes one LDS
 // read (it does not touch the counted vmcnt waits of the tile pipeline) — a 64-key tile never straddles a 128-token page.
 // one workgroup: query block qblk of head h (attn_prefill_kernel: from the grid; attn_prefill_rg_kernel: from its work item)
-template <int DT, int HD, int LA, int KP, bool PAGED>
-__device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const int h, const int qblk) {
+// SPLIT (kernels/attn_extend.h): the workgroup walks the 64-key tiles [t0, t1) only and leaves its unnormalised (O, m, l) per query in `part` (the (split, head)
+// record, attn_extend_part_vals<HD>() values of 256 lanes each) instead of output rows.  Every difference is compile-time: the other instantiations are what they were.
+template <int DT, int HD, int LA, int KP, bool PAGED, bool SPLIT = false>
+__device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const int h, const int qblk, const int t0 = 0, const int t1 = 0, float* const part = nullptr) {
+  static_assert(!SPLIT || KP == 1, "a key range per workgroup has no key split inside it");
   constexpr int DIS = TGX_ATTN_DIS;
   constexpr int LQ = HD + 8;                  // 16-bit row stride of the K tile (144 / 272 B: conflict-free 16-byte fragment reads)
   constexpr int LV = HD + 32;                 // 16-bit row stride of the V tile ([key][d], 64 B more than a row: the four key rows of a transposing read fall on four bank quarters)
@@ -602,15 +651,17 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
   const bf16_t* vbase = a.v_cache + (PAGED ? (size_t)0 : (size_t)kvh * a.max_ctx * HD);
   const int wg_last_pos = a.past + min(qblk * 128 + 127, a.S - 1);   // keys beyond it are never attended by this workgroup
   __shared__ int stbl[PAGED ? 1024 : 1];
+  const int key_hi = SPLIT ? min(t1 * 64 + 63, wg_last_pos) : wg_last_pos;      // the last key a fetch may touch (SPLIT: its own tiles and the look-ahead tile behind them)
+  const int blk0 = SPLIT ? (t0 * 64) >> KV_BLOCK_SHIFT : 0;                       // first table entry held in stbl
   if constexpr (PAGED) {
-    for (int i = tid; i <= (wg_last_pos >> KV_BLOCK_SHIFT); i += 256 * KP) stbl[i] = a.blk_tbl[i];
+    for (int i = blk0 + tid; i <= (key_hi >> KV_BLOCK_SHIFT); i += 256 * KP) stbl[i - blk0] = a.blk_tbl[i];
     __syncthreads();
   }
   auto key_off = [&](int key) -> size_t {      // element offset of a key's row from kbase / vbase
-    if constexpr (PAGED) return (((size_t)stbl[key >> KV_BLOCK_SHIFT] * a.kv_heads + kvh) * KV_BLOCK + (key & (KV_BLOCK - 1))) * (size_t)HD;
+    if constexpr (PAGED) return (((size_t)stbl[(key >> KV_BLOCK_SHIFT) - blk0] * a.kv_heads + kvh) * KV_BLOCK + (key & (KV_BLOCK - 1))) * (size_t)HD;
     else return (size_t)key * HD;
   };
-  const int n_kt = (wg_last_pos / 64 + 1 + KP - 1) / KP;      // steps of KP tiles
+  const int n_kt = SPLIT ? t1 - t0 : (wg_last_pos / 64 + 1 + KP - 1) / KP;      // steps of KP tiles
   const int wave_last_pos = a.past + min(q0 + 31, a.S - 1);
   const bool wave_live = q0 < a.S;
   const float qs = a.scale * LOG2E;
@@ -624,7 +675,7 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
 #pragma unroll
     for (int i = 0; i < NCH; i++) {
       const int c = (tid & 255) + 256 * i, row = c / CH, kc = c - row * CH;
-      const int key = min((KP * kt + kp) * 64 + row, wg_last_pos);
+      const int key = min((SPLIT ? t0 + kt : KP * kt + kp) * 64 + row, key_hi);
       const size_t ko = key_off(key) + kc * 8;
       kr[i] = *reinterpret_cast<const u32x4*>(kbase + ko);
       __builtin_amdgcn_sched_barrier(0);       // the same issue order at every call site: the counted vmcnt waits rely on it
@@ -646,8 +697,9 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
   for (int r = 0; r < 16; r++) zero16[r] = 0.f;
 
   auto compute_tile = [&](int kt) {
-    const int key0 = (KP * kt + kp) * 64;
+    const int key0 = (SPLIT ? t0 + kt : KP * kt + kp) * 64;
     if (!wave_live || key0 > wave_last_pos) return;      // wave-uniform: nothing of this tile is visible to the wave's queries
+    if (SPLIT && kt >= n_kt) return;                     // (the pair loop's extra tile belongs to the next split)
 
     // S^T sub-tiles: sacc[sub][r] = raw score (q.k) of key key0 + 32 sub + (r&3) + 8 (r>>2) + 4 hh for this lane's query
     f32x16 sacc[2];
@@ -774,9 +826,16 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
   }
   }
 
-  // normalise and emit as hi / lo 16-bit pairs (the o_proj GEMM's A operand).  A lane holds ONE query's output dims, so direct stores would be
-  // 2-byte writes 4 KB apart (64 cache lines per instruction: ~20 µs of the kernel at S = 2048); instead each wave transposes its 32 x HD block
-  // through LDS (rows of 2 HD + 8 bytes: conflict-free 4-byte column writes) and stores whole rows, 16 bytes per lane.
+  if constexpr (SPLIT) {                         // the split's partial per query, lane-major (the merge kernel's threads hold the same queries in the same layout)
+    if (!wave_live) return;                      // (the merge leaves these waves out as well)
+    float* const po = part + wv * 64 + lane;
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) po[(b * 16 + r) * 256] = oacc[b][r];
+    po[(NB * 16) * 256] = m_run; po[(NB * 16 + 1) * 256] = l_run;
+    return;
+  }
   __syncthreads();                              // every wave is done with the last K / V tile
   if constexpr (KP == 2) {
     // the odd-tile stream of every query joins the even-tile one: lane-to-lane (the two waves hold the same queries in the same layout)
@@ -806,41 +865,8 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
     __syncthreads();                            // the merge buffer is read: the staging rows below reuse it
     if (kp == 1) return;
   }
-  constexpr int RS = HD + 4;                    // staged row stride in 16-bit elements
-  static_assert(4 * 32 * RS <= 64 * LQ + 64 * LV, "output staging exceeds the K / V tiles");
-  bf16_t* const wrow = smem + wv * 32 * RS;
-  const float inv_l = qvalid ? 1.0f / l_run : 0.f;
-  unsigned int whi[NB * 8], wlo[NB * 8];
-#pragma unroll
-  for (int b = 0; b < NB; b++)
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const float v0 = oacc[b][r] * inv_l, v1 = oacc[b][r + 1] * inv_l;
-      bf16_t h0, l0, h1, l1;
-      split16<DT>(v0, h0, l0);
-      split16<DT>(v1, h1, l1);
-      whi[b * 8 + (r >> 1)] = (unsigned int)h0 | ((unsigned int)h1 << 16);
-      wlo[b * 8 + (r >> 1)] = (unsigned int)l0 | ((unsigned int)l1 << 16);
-    }
-#pragma unroll
-  for (int term = 0; term < 2; term++) {
-#pragma unroll
-    for (int b = 0; b < NB; b++)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const int d = 32 * b + (r & 3) + 8 * (r >> 2) + 4 * hh;                 // dims d, d + 1
-        *reinterpret_cast<unsigned int*>(wrow + ql * RS + d) = term ? wlo[b * 8 + (r >> 1)] : whi[b * 8 + (r >> 1)];
-      }
-    bf16_t* const dst = term ? a.o_lo : a.o_hi;
-#pragma unroll
-    for (int i = 0; i < HD / 16; i++) {          // 32 rows x HD / 8 chunks of 16 bytes over 64 lanes
-      const int c = lane + 64 * i, row = c / CH, cc = c - row * CH;
-      const u32x2 p0 = *reinterpret_cast<const u32x2*>(wrow + row * RS + cc * 8);
-      const u32x2 p1 = *reinterpret_cast<const u32x2*>(wrow + row * RS + cc * 8 + 4);
-      if (q0 + row < a.S)
-        *reinterpret_cast<u32x4*>(dst + (size_t)(q0 + row) * qd + (size_t)h * HD + cc * 8) = u32x4{p0[0], p0[1], p1[0], p1[1]};
-    }
-  }
+  static_assert(4 * 32 * (HD + 4) <= 64 * LQ + 64 * LV, "output staging exceeds the K / V tiles");
+  attn_emit_rows<DT, HD>(a, h, q0, qvalid, oacc, l_run, smem + wv * 32 * (HD + 4), lane);
 }
 template <int DT, int HD, int LA = 2, int KP = 1, bool PAGED = false>
 __global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 2) : 1)) void attn_prefill_kernel(const AttnPrefillArgs a) {      // head_dim 128: LA = 1 fits two waves per SIMD (LA = 2 needs 292 registers: one)

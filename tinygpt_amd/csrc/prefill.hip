@@ -6,6 +6,7 @@
 #include "kernels/gemm_dma.h"
 #include "kernels/gemm_dma_qkv.h"
 #include "kernels/attn_prefill_dma.h"
+#include "kernels/attn_extend.h"
 #include "kernels/gemm_f32.h"
 
 bool prefill_shapes_ok(const tgx_model_desc& d) {
@@ -298,10 +299,57 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
     })
 }
 
+// ---- the key-split attention of a continuation (kernels/attn_extend.h; option extend.attn_splits).  Splits of a pass of S positions from `past`: 0 = the per-row
+// prompt attention (a pass from position 0, more than one query block, the option at 0, a context below the measured threshold)
+int extend_attn_splits(const tgx_ctx* c, int S, int past) {
+  if (c->extend_attn_splits == 0 || past <= 0 || S > tgx::ATTN_QBLK || c->dt == tgx::DT_F32) return 0;
+  const int tiles = (past + S - 1) / tgx::ATTN_KTILE + 1;
+  int ns = c->extend_attn_splits;
+  if (ns < 0) {      // automatic: heads x splits ~ the CUs, at most 32, from the context where the split form wins (ctx.h extend_attn_min)
+    if (past + S <= (c->d.head_dim == 64 ? c->extend_attn_min64 : c->extend_attn_min128)) return 0;
+    ns = std::min(32, c->num_cus / std::max(1, c->d.heads));
+    if (ns < 2) return 0;
+  }
+  return std::min(ns, tiles);
+}
+// bytes of the partials of ns splits: attn_extend_part_vals values of 256 lanes per (split, head) (kernels/attn_extend.h)
+static size_t extend_part_bytes(const tgx_ctx* c, int ns) {
+  const int vals = c->d.head_dim == 64 ? tgx::attn_extend_part_vals<64>() : tgx::attn_extend_part_vals<128>();
+  return (size_t)ns * c->d.heads * vals * 256 * sizeof(float);
+}
+int ensure_extend_ws(tgx_ctx* c, int S, int past) {
+  const int ns = extend_attn_splits(c, S, past);
+  if (!ns) return TGX_OK;
+  const size_t bytes = extend_part_bytes(c, ns);
+  if (bytes <= c->ext_part_bytes) return TGX_OK;
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  if (c->ext_part) (void)hipFree(c->ext_part);
+  c->ext_part = nullptr; c->ext_part_bytes = 0;
+  HIP_OK(c, hipMalloc((void**)&c->ext_part, bytes));
+  c->ext_part_bytes = bytes;
+  return TGX_OK;
+}
+static void launch_attn_extend(tgx_ctx* c, const tgx::AttnPrefillArgs& a, int ns) {
+  const int hd = c->d.head_dim;
+  tgx::AttnExtendArgs e{};
+  e.a = a; e.part = c->ext_part; e.ns = ns; e.n_tiles = (a.past + a.S - 1) / tgx::ATTN_KTILE + 1;
+  if (!c->ext_part || extend_part_bytes(c, ns) > c->ext_part_bytes) { c->launch_fault = "attn_extend: the partials' workspace was not sized for this pass"; return; }
+  const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
+  const dim3 grid(a.heads, ns), blk(256);
+  auto go = [&](auto paged) {
+    constexpr bool P = decltype(paged)::value;
+    TGX_DT16_SWITCH(c->dt,
+      if (hd == 64) { hipLaunchKernelGGL((tgx::attn_extend_kernel<DT, 64, P>), grid, blk, lds1, c->stream, e); hipLaunchKernelGGL((tgx::attn_extend_merge_kernel<DT, 64>), dim3(a.heads), blk, 0, c->stream, e); }
+      else { hipLaunchKernelGGL((tgx::attn_extend_kernel<DT, 128, P>), grid, blk, lds1, c->stream, e); hipLaunchKernelGGL((tgx::attn_extend_merge_kernel<DT, 128>), dim3(a.heads), blk, 0, c->stream, e); })
+  };
+  if (a.blk_tbl) go(std::true_type{}); else go(std::false_type{});
+}
+
 // causal GQA flash attention of S prompt positions of one batch row (grid = ceil(S / 128) query blocks x heads)
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_lean) {
   tgx::AttnPrefillArgs a = a_;
   const int hd = c->d.head_dim;
+  if (const int ns = extend_attn_splits(c, a.S, a.past)) { launch_attn_extend(c, a, ns); return; }
   const int nqb = (a.S + tgx::ATTN_QBLK - 1) / tgx::ATTN_QBLK, nwg = nqb * a.heads;
   const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;      // one K tile | V tile pair (kernels/prefill.h)
   // head_dim 64, three or more workgroups per CU (prompts from ~3k tokens at 32 heads): K / V tiles by LDS-DMA, the next tile's scores under the current tile's

@@ -69,6 +69,8 @@ ABI = {
     "forward_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "forward_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
     "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
+    "extend_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
+    "truncate_row": (c_int, [c_void_p, c_int, c_int64]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -272,6 +274,18 @@ class Model:
         self._check(self.be.fork_row(self._ctx, src, len(rows), ptr))
         if len(rows):
             self.batch = max(self.batch, int(rows.max()) + 1)
+        return self
+
+    def extend_row(self, row: int, ids):
+        """append ids at positions past .. past + len(ids) - 1 of the live (or finished) row `row` in one causal pass (include/tgx.h tgx_extend_row); the row's current
+        token, if any, is discarded"""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        self._check(self.be.extend_row(self._ctx, row, ids.ctypes.data_as(POINTER(c_int64)), len(ids)))
+        return self
+
+    def truncate_row(self, row: int, n: int):
+        """roll `row` back to its first n positions (include/tgx.h tgx_truncate_row); it then holds no logits until extend_row"""
+        self._check(self.be.truncate_row(self._ctx, row, int(n)))
         return self
 
     def sample_row(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0) -> int:

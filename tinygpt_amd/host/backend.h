@@ -38,6 +38,9 @@ struct Backend {
   int (*forward_row)(tgx_ctx*, int, const int64_t*, int) = nullptr;
   int (*sample_row)(tgx_ctx*, int, const tgx_sampler_cfg*, uint64_t, int64_t*) = nullptr;
   int64_t (*past_length_row)(const tgx_ctx*, int) = nullptr;
+  // prefix reuse (optional: GPTConfig::reusePrefix needs both)
+  int (*extend_row)(tgx_ctx*, int, const int64_t*, int) = nullptr;
+  int (*truncate_row)(tgx_ctx*, int, int64_t) = nullptr;
 
   bool open(const std::string& path, const std::string& prefix) {
     // RTLD_NODELETE: the shim's runtime owns threads (HIP's signal/event workers; libgomp's team under the CPU oracle) that
@@ -57,6 +60,7 @@ struct Backend {
     TGXH_BIND(step_async, false); TGXH_BIND(fetch_token, false);
     TGXH_BIND(reset_cache, true); TGXH_BIND(past_length, true); TGXH_BIND(context_size, true); TGXH_BIND(last_error, true);
     TGXH_BIND(reset_row, false); TGXH_BIND(forward_row, false); TGXH_BIND(sample_row, false); TGXH_BIND(past_length_row, false);
+    TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
 #undef TGXH_BIND
     return ok;
   }

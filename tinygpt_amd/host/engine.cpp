@@ -81,7 +81,21 @@ void GPTEngine::reconfigure(const SamplerConfig& samplerConfig, int64_t maxNewTo
   config_.maxNewTokens = maxNewTokens;
   eosTokenIds_ = baseEosTokenIds_;
   for (int32_t id : extraStopTokenIds) if (!isEosToken(id)) eosTokenIds_.push_back(id);
-  if (model_.ctx) be_.reset_cache(model_.ctx);           // context_.model->resetCache()  (:83)
+  if (model_.ctx && !reuseActive()) be_.reset_cache(model_.ctx);           // context_.model->resetCache()  (:83); reusePrefix: the generate calls decide
+}
+
+// reusePrefix: L = the common prefix of what row 0's cache holds and the new prompt, capped at prompt length - 1 (the last position's logits must be computed) and at
+// the cache's length; row 0 is rolled back to L and extended with the rest
+bool GPTEngine::prefillReusing(const std::vector<int64_t>& ids) {
+  const int64_t S = (int64_t)ids.size();
+  int64_t cap = std::min<int64_t>({(int64_t)cached_.size(), S - 1, be_.past_length(model_.ctx)});
+  int64_t L = 0;
+  while (L < cap && (int64_t)cached_[(size_t)L] == ids[(size_t)L]) L++;
+  if (L < 1) return false;
+  if (be_.truncate_row(model_.ctx, 0, L) != TGX_OK) return false;
+  if (be_.extend_row(model_.ctx, 0, ids.data() + L, (int)(S - L)) != TGX_OK) return false;
+  lastReused_ = L;
+  return true;
 }
 
 bool GPTEngine::isEosToken(int32_t id) const { return std::find(eosTokenIds_.begin(), eosTokenIds_.end(), id) != eosTokenIds_.end(); }
@@ -116,6 +130,8 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   if (S == 0) { fail("generateSync: every prompt is empty (nothing to prefill)"); return out; }
   const tgx_sampler_cfg sc = to_c(config_.samplerConfig);
   const int64_t n_new = std::max<int64_t>(1, config_.maxNewTokens);
+  lastReused_ = 0;
+  if (reuseActive()) { be_.reset_cache(model_.ctx); cached_.clear(); }      // (reconfigure left the cache in place)
 
   // prefill (mask ignored, like the reference: "TODO padding mask", GPTEngine.cpp:95)
   const auto t0 = std::chrono::steady_clock::now();
@@ -151,7 +167,13 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   if (S == 0) { fail("generateAsync: the prompt is empty (nothing to prefill)"); return out; }
   const tgx_sampler_cfg sc = to_c(config_.samplerConfig);
   const auto t0 = std::chrono::steady_clock::now();
-  if (be_.forward(model_.ctx, ids.data(), 1, (int)S) != TGX_OK) { fail(std::string("forward: ") + be_.last_error(model_.ctx)); return out; }
+  lastReused_ = 0;
+  const bool reuse = reuseActive();
+  if (!reuse || !prefillReusing(ids)) {
+    if (reuse) be_.reset_cache(model_.ctx);      // (reconfigure left the cache in place; a failed truncate / extend pair ends here as well)
+    if (be_.forward(model_.ctx, ids.data(), 1, (int)S) != TGX_OK) { cached_.clear(); fail(std::string("forward: ") + be_.last_error(model_.ctx)); return out; }
+  }
+  cached_.clear();      // (set again below, once the call knows what the cache holds)
   int64_t cur = 0;
   if (be_.sample(model_.ctx, &sc, config_.seed, &cur) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
   const auto t1 = std::chrono::steady_clock::now();
@@ -191,6 +213,11 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   }
   out.firstTokenMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
   out.decodeMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  if (reuse) {      // every step appended its input token: the cache holds the first past_length ids of prompt + generated tokens
+    const int64_t held = broke ? 0 : be_.past_length(model_.ctx);
+    if (held >= 1 && held <= (int64_t)tokens.size()) cached_.assign(tokens.begin(), tokens.begin() + held);
+    else cached_.clear();
+  }
   out.batch = 1;
   out.newTokens = (int64_t)tokens.size() - S;
   out.tokenIds = std::move(tokens);

@@ -35,6 +35,10 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   int maxBatch = 4;
   uint64_t seed = 0;
   std::string tokenizerDir;          // tokenizer.json + tokenizer_config.json; default: modelDir (lets --synthetic runs take text)
+  // Not in the reference (its engine resets the cache per request and prefills the whole conversation again): generateAsync keeps row 0's KV cache between calls
+  // and prefills only what follows the longest prefix the new prompt shares with it (tgx_truncate_row + tgx_extend_row).  Needs a backend with both symbols;
+  // generateSync and any failure of the two calls take the reset path.
+  bool reusePrefix = false;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -84,11 +88,19 @@ class GPTEngine {
   const std::string& lastError() const { return err_; }
   tgx_ctx* ctx() { return model_.ctx; }
   const Backend& backend() const { return be_; }
+  void setReusePrefix(bool on) {
+    if (!on && reuseActive() && model_.ctx) be_.reset_cache(model_.ctx);      // (as reconfigure would have left it)
+    config_.reusePrefix = on;
+    cached_.clear();
+  }
+  int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
 
  private:
   // == encodeTexts minus the tokenizer (GPTEngine.cpp:101-144): truncate to contextSize keeping the tail, left-pad
   std::vector<int64_t> alignPrompts(const std::vector<std::vector<int32_t>>& prompts, int32_t padToken, int64_t& maxLen) const;
   bool fail(const std::string& what);
+  bool reuseActive() const { return config_.reusePrefix && be_.extend_row && be_.truncate_row; }
+  bool prefillReusing(const std::vector<int64_t>& ids);      // the prompt after its cached prefix; false: nothing reusable (the caller resets and prefills)
 
   GPTConfig config_;
   Backend be_;
@@ -98,6 +110,8 @@ class GPTEngine {
   bool prepared_ = false;
   Tokenizer tokenizer_;
   bool tokenizerOk_ = false;
+  std::vector<int32_t> cached_;      // reusePrefix: the token ids row 0's cache holds, position by position (empty: unknown / nothing)
+  int64_t lastReused_ = 0;
 };
 
 // Deterministic synthetic checkpoint — bit-identical to tinygpt_amd/synth.py (same integer hash).

@@ -49,6 +49,9 @@ TGXE_API int tgxe_eos_ids(tgxe_engine* h, int32_t* out, int cap) {
   for (int i = 0; i < (int)v.size() && i < cap; i++) out[i] = v[(size_t)i];
   return (int)v.size();
 }
+// prefix reuse (GPTConfig::reusePrefix): generateAsync keeps row 0's KV cache between calls; tgxe_last_reused = the prompt tokens the last call served from it
+TGXE_API void tgxe_set_reuse_prefix(tgxe_engine* h, int on) { if (h) h->e->setReusePrefix(on != 0); }
+TGXE_API int64_t tgxe_last_reused(tgxe_engine* h) { return h ? h->e->lastReused() : -1; }
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
   tgxh::SamplerConfig s; s.temperature = temperature; s.topK = top_k; s.topP = top_p; s.minP = min_p;

@@ -10,6 +10,14 @@ N copies of the prompt, for every prompt length of --fork-prompts; the fork call
 over that time) is printed beside it.
 
     python tools/admit_bench.py --fork 4,16 [--fork-prompts 256,2048]
+
+--extend measures a continuation (include/tgx.h tgx_extend_row): S new tokens after P cached ones, with the attention of the pass on the per-row prompt kernel
+(extend.attn_splits 0), on the automatic choice (-1) and on 4 / 8 / 16 / 32 forced key splits (kernels/attn_extend.h) — and beside them tgx_reset_row +
+tgx_forward_row(P + S), what a caller without tgx_extend_row does.  The forms alternate inside every repetition; the row is rolled back (tgx_truncate_row) outside the
+timed window.  Each figure is the median of --reps repetitions with their min .. max beside it: the spread a difference has to exceed.
+
+    python tools/admit_bench.py --extend [--model llama-3.2-1b] [--layers 0] [--extend-pasts 512,2048,8192] [--extend-lens 16,64,128]
+    python tools/admit_bench.py --extend --model mistral-7b-v0.3 --dtype bf16 --layers 2        # head_dim 128 at two layers
 """
 import argparse, dataclasses, os, sys, time
 import numpy as np
@@ -27,7 +35,59 @@ ap.add_argument("--sets", default=",".join(SETS))
 ap.add_argument("--max-ctx", type=int, default=1024)
 ap.add_argument("--fork", default="", help="n-best admission: forward_row + fork_row into N - 1 rows against forward_rows of N copies (e.g. 4,16)")
 ap.add_argument("--fork-prompts", default="256,2048")
+ap.add_argument("--extend", action="store_true", help="a continuation of S tokens after P cached ones: tgx_extend_row per attention form against reset + forward_row(P + S)")
+ap.add_argument("--extend-pasts", default="512,2048,8192")
+ap.add_argument("--extend-lens", default="16,64,128")
+ap.add_argument("--extend-splits", default="0,-1,4,8,16,32")
+ap.add_argument("--layers", type=int, default=0, help="--extend: cut the model to this many layers (0 = all)")
 args = ap.parse_args()
+
+
+def extend_bench():
+    pasts, lens = [int(x) for x in args.extend_pasts.split(",")], [int(x) for x in args.extend_lens.split(",")]
+    forms = [int(x) for x in args.extend_splits.split(",")]
+    desc = dataclasses.replace(known_desc(args.model, args.dtype), max_batch=1, max_ctx=max(pasts) + max(lens) + 64)
+    if args.layers:
+        desc = dataclasses.replace(desc, layers=args.layers)
+    m = Model(desc, product_backend()).load_synthetic(1234, 0.02).finalize()
+    tag = f"{desc.name} {args.dtype} {desc.layers} layers head_dim {desc.head_dim}"
+    for P in pasts:
+        for S in lens:
+            seq = synth.synth_prompt(desc.vocab, P + S, 900)
+            m.reset_cache(); m.forward_row(0, seq[:P])
+
+            def ext(ns):
+                m.set_option("extend.attn_splits", ns)
+                m.synchronize()
+                t0 = time.perf_counter()
+                m.extend_row(0, seq[P:])
+                m.synchronize()
+                dt = (time.perf_counter() - t0) * 1e3
+                m.truncate_row(0, P)
+                return dt
+
+            for ns in forms:
+                ext(ns); ext(ns)
+            t = {ns: [] for ns in forms}
+            for _ in range(args.reps):
+                for ns in forms:
+                    t[ns].append(ext(ns))
+            full = []
+            for i in range(2 + max(3, args.reps // 3)):
+                m.reset_row(0); m.synchronize()
+                t0 = time.perf_counter()
+                m.forward_row(0, seq)
+                m.synchronize()
+                if i >= 2:
+                    full.append((time.perf_counter() - t0) * 1e3)
+            cells = "  ".join(f"{'auto' if ns < 0 else ns}: {np.median(v):6.3f} [{min(v):6.3f} .. {max(v):6.3f}]" for ns, v in t.items())
+            print(f"{tag} past {P:5d} S {S:3d} ms  {cells}  | reset + forward_row({P + S}): {np.median(full):7.3f}", flush=True)
+    m.close()
+
+
+if args.extend:
+    extend_bench()
+    sys.exit(0)
 
 
 def fork_bench():
