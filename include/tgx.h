@@ -381,7 +381,8 @@ TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
  *   "graph.steps"        decode steps per captured multi-step graph */
 TGX_API int tgx_get_option(const tgx_ctx* ctx, const char* key, int* out_value);
 
-/* Algorithmic HBM bytes one decoded token streams at context length T (SURVEY.md §8d formula). */
+/* Algorithmic HBM bytes one decoded token streams at context length T (SURVEY.md §8d formula).  Matrices stored exponent-packed (option "weights.packed",
+ * bf16 storage) count with the bytes the batch-1 step really streams: their packed planes and escape records instead of 2 bytes per weight. */
 TGX_API int64_t tgx_bytes_per_token(const tgx_ctx* ctx, int64_t T);
 
 TGX_API int tgx_abi_version(void);

@@ -669,6 +669,7 @@ int tgx_create(const tgx_model_desc* desc, int device_ordinal, tgx_ctx** out_ctx
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   HIP_OK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   if (const char* e = getenv("TGX_NO_GRAPH")) c->use_graph = !(e[0] == '1');
+  if (const char* e = getenv("TGX_PACKED_CLASSES")) c->packed_classes = atoi(e) & 7;      // experiments (A/B per class under an unchanged bench.py): option weights.packed_classes
   // measured crossover of the direct and the split attention (tools/sweep.py --grid attn.direct_max=0,100000): context ~850-1100 at
   // head_dim 64 (Qwen2.5-0.5B, Llama-3.2-1B), ~500 at 128 (Mistral-7B: half the tokens per wave-load)
   // round 4 (the split form lost its combine launch to the K-sliced o_proj, the 16-wave direct form its per-wave merge): Llama-3.2-1B 0.652 / 0.654 ms/token
@@ -911,6 +912,7 @@ int tgx_finalize(tgx_ctx* c) {
   c->row_fin.assign(B, 0);
   if ((rc = dev_alloc(c, &c->row_req, B))) return rc;
   HIP_OK(c, hipMemcpy(c->row_req, c->row_req_host.data(), B * sizeof(tgx::RowReq), hipMemcpyHostToDevice));
+  if ((rc = pack_weights(c))) return rc;
   c->past = 0;
   c->row_past.assign(B, 0);
   c->row_tok.assign(B, 0);
@@ -931,6 +933,8 @@ void tgx_destroy(tgx_ctx* c) {
   fr(c->rg_buf); fr(c->rg_x); fr(c->rg_logits); fr(c->rg_part_val); fr(c->rg_part_idx);
   fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
   fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_part); fr(c->ws_ssq); fr(c->ws_pos);
+  fr(c->plm.P); fr(c->plm.rec);
+  for (auto& w : c->L) { fr(w.pgu.P); fr(w.pgu.rec); fr(w.pdown.P); fr(w.pdown.rec); }
   for (auto& w : c->L) { fr(w.in_norm); fr(w.post_norm); fr(w.wqkv); fr(w.bqkv); fr(w.wo); fr(w.q_norm); fr(w.k_norm); fr(w.wgu); fr(w.wdown); fr(w.in_norm_b); fr(w.post_norm_b); fr(w.bo); fr(w.bfc); fr(w.bdown); }
   fr(c->slab_x); fr(c->slab_q); fr(c->slab_kraw); fr(c->slab_attn); fr(c->slab_h); fr(c->slab_logits); fr(c->slab_probs);
   fr(c->slab_part_val); fr(c->slab_part_idx); fr(c->slab_attn_part); fr(c->slab_tok); fr(c->slab_pos); fr(c->slab_prompt); fr(c->slab_k); fr(c->slab_v);
@@ -1760,6 +1764,11 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "act.round16")) { *out_value = c->act16; return TGX_OK; }
   if (!strcmp(key, "kv.budget_tokens")) { *out_value = c->kv_budget_tokens; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { *out_value = c->extend_attn_splits; return TGX_OK; }
+  if (!strcmp(key, "weights.packed")) { *out_value = c->weights_packed; return TGX_OK; }
+  if (!strcmp(key, "weights.packed_classes")) { *out_value = c->packed_classes; return TGX_OK; }
+  if (!strcmp(key, "weights.packed_matrices")) { *out_value = c->packed_matrices; return TGX_OK; }        // read-only, after tgx_finalize: matrices stored packed ...
+  if (!strcmp(key, "weights.packed_fallbacks")) { *out_value = c->packed_fallbacks; return TGX_OK; }      // ... matrices that stayed plain because a row's escape record overflowed ...
+  if (!strcmp(key, "weights.packed_max_row_esc")) { *out_value = c->packed_max_row_esc; return TGX_OK; }  // ... and the most escapes seen in one row
   if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv_free.size() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
   return TGX_ERR_INVALID;
 }
@@ -1828,6 +1837,12 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "debug.profile_same_layer")) { c->prof_same_layer = value; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "extend.attn_splits is -1 (automatic), 0 (never) or a split count"); c->extend_attn_splits = value; return TGX_OK; }
   if (!strcmp(key, "oproj.sliced")) { drop_step_graphs(c); c->oproj_sliced = value != 0; return TGX_OK; }
+  if (!strcmp(key, "weights.packed") || !strcmp(key, "weights.packed_classes")) {
+    if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the packed copies are made there)", key);
+    if (key[14] == '_') { if (value < 0 || value > 7) return set_err(c, TGX_ERR_INVALID, "weights.packed_classes is a mask of gate_up (1), down (2), lm_head (4)"); c->packed_classes = value; }
+    else c->weights_packed = value != 0;
+    return TGX_OK;
+  }
   if (!strcmp(key, "kv.budget_tokens")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "kv.budget_tokens is set before tgx_finalize (it sizes the caches)");
     if (value < 0) return set_err(c, TGX_ERR_INVALID, "kv.budget_tokens >= 0 (0 = one max_ctx slab per row)");
@@ -1867,7 +1882,12 @@ int64_t tgx_bytes_per_token(const tgx_ctx* c, int64_t T) {
     return b * (L * per_layer + 2 * H + H + V * H) + b * 2 * L * kv * T;
   }
   const int64_t per_layer = (q + 2 * kv) * H + (d.qkv_bias ? (q + 2 * kv) : 0) + H * q + 2 * I * H + H * I + 2 * H;
-  return b * (L * per_layer + H + V * H) + b * 2 * L * kv * T;
+  // exponent-packed matrices (option weights.packed) stream their planes and escape records instead of 2 bytes per weight
+  int64_t saved = 0;
+  auto packed_saving = [&](const PackedMat& m, int64_t rows, int64_t cols) { if (m.P) saved += b * rows * cols - rows * (m.row_bytes + 16); };
+  for (const LayerW& w : c->L) { packed_saving(w.pgu, 2 * I, H); packed_saving(w.pdown, H, I); }
+  packed_saving(c->plm, V, H);
+  return b * (L * per_layer + H + V * H) + b * 2 * L * kv * T - saved;
 }
 
 }  // extern "C"

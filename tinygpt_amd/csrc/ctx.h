@@ -31,9 +31,22 @@ namespace tgx { struct SampScratch; }
 constexpr int MAX_TICKET_EVENTS = 64;
 constexpr int HOST_RING = 256;
 
+// a bf16 matrix in the lossless 12-bit exponent-packed form (kernels/gemv_packed.h; option weights.packed): made once in tgx_finalize beside the bf16 original,
+// read by the batch-1 decode launches of its class.  P == nullptr: not packed (option off, class not adopted, other dtype / shape, or a row's escapes overflowed)
+struct PackedMat {
+  unsigned char* P = nullptr;     // planes, N * row_bytes
+  tgx::u32x4* rec = nullptr;      // [N] escape records
+  long long row_bytes = 0;
+  unsigned int base2 = 0;         // E0 << 7 | E0 << 23
+  int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
+  int max_row_esc = 0;            // most escapes in one row
+  long long n_esc = 0;            // escapes of the matrix
+};
+
 struct LayerW {
   ebyte *in_norm = nullptr, *post_norm = nullptr;
   ebyte *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
+  PackedMat pgu, pdown;         // wgu / wdown exponent-packed
   ebyte *q_norm = nullptr, *k_norm = nullptr;   // Qwen3 [head_dim]
   bool q_norm_ok = false, k_norm_ok = false;
   // one bit per checkpoint tensor that lands in a merged weight: q, k, v, gate, up (bits 0-4) and the q/k/v biases (bits 5-7) — a tensor
@@ -102,6 +115,12 @@ struct tgx_ctx {
   bool embed_ok = false, lm_head_ok = false, final_norm_ok = false, wpe_ok = false, final_norm_b_ok = false;
   bool gpt2 = false;
   std::vector<LayerW> L;
+  // option weights.packed (read at tgx_finalize; default 1): bf16 gate_up / down / lm_head weights also stored exponent-packed for the batch-1 decode stream.
+  // weights.packed_classes: which classes (bit 0 gate_up, 1 down, 2 lm_head).  Default: lm_head alone — on Llama-3.2-1B the packed lm_head launch is 13-16 us
+  // shorter, the packed gate_up (+0.9 us per layer) and down (+0.4) launches are bound by the decode arithmetic, not by the stream (profiles/packed_weights.txt).
+  // packed_matrices / packed_fallbacks: matrices packed / fallen back to plain
+  int weights_packed = 1, packed_classes = 4, packed_matrices = 0, packed_fallbacks = 0, packed_max_row_esc = 0;
+  PackedMat plm;                // the lm_head matrix (embed when tied) exponent-packed
   float *rope_cos = nullptr, *rope_sin = nullptr;
   std::vector<RowState> rows;   // views into the per-row slabs below (constant row stride: batched GEMV walks them)
   float *slab_x = nullptr, *slab_q = nullptr, *slab_kraw = nullptr, *slab_attn = nullptr, *slab_h = nullptr, *slab_logits = nullptr;
@@ -332,6 +351,7 @@ int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens);       // paged KV: 
 bool is_greedy(const tgx_sampler_cfg* s);   // Sampler.cpp:15-21
 // ---- decode.hip (kernels/gemv.h, kernels/oproj_sliced.h)
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc);
+int pack_weights(tgx_ctx* c);     // tgx_finalize: the exponent-packed copies of the bf16 gate_up / down / lm_head matrices (option weights.packed)
 bool oproj_sliced_ok(const tgx_ctx* c, int R, long long kv_stride);
 bool oproj_fused_capable(const tgx_ctx* c);                               // static conditions (geometry, dtype, option)
 bool oproj_fused_ok(const tgx_ctx* c, int R, long long kv_stride);       // ... and this launch is a batch-1 step on the direct form

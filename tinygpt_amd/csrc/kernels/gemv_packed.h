@@ -1,0 +1,397 @@
+// gemv_packed.h — the batch-1 weight stream of gate_up, down and lm_head over bf16 weights stored as a LOSSLESS 12-bit form: 25 % fewer bytes per
+// launch, every weight the kernel multiplies bit for bit the uploaded one (DESIGN.md §5 "Exponent-packed weights").
+//
+// Format of a bf16 matrix [N][K], K % 8 == 0 (option weights.packed, made once in tgx_finalize by pack_rows_kernel below; the bf16 original stays):
+//   exponent base   E0 = max(Emax - 15, 0), Emax = the largest exponent field below 255 in the matrix.  A weight whose exponent field is E0 + c with
+//                   c in 1..15 has CODE c; every other weight (zeros, subnormals, anything below the window, inf / NaN) has code 0 = ESCAPE.
+//   chunk           8 consecutive k of a row -> 12 bytes: two dwords S0, S1 of `sign << 7 | mantissa` bytes and one dword C of eight 4-bit codes
+//                     S0 = b(w0) | b(w2) << 8 | b(w1) << 16 | b(w3) << 24        S1 = the same of w4..w7
+//                     C  = sum over t = 0..3 of code(w[2t]) << 4t | code(w[2t+1]) << (4t + 16)
+//                   (the two weights of one bf16 pair sit 16 bits apart: one shift + mask moves both codes into the exponent fields of the pair's dword)
+//   escape record   16 bytes per row: up to PACKED_ESC entries `k << 16 | bits` (the weight's true 16 bits), unused entries 0xffffffff.  A matrix with a row
+//                   of more than PACKED_ESC escapes is NOT packed (per-matrix fallback to kernels/gemv.h, decided at finalize).
+//   physical layout follows the thread -> (row, k) map of gemv_kernel launched with `ks` waves per row pair, NX = ceil(K / 8 / (64 ks)) chunks per lane:
+//                   lane l of k-part p owns chunks c = p * per + l + 64 j (per = 64 NX), j = 0..NX-1.  Its chunks go in QUADS q = j / 4 of three 1 KiB planes
+//                     plane 0: lane l's 16 bytes = S0, S1 of chunk 4q, S0, S1 of chunk 4q + 1       plane 1: the same of chunks 4q + 2, 4q + 3
+//                     plane 2: lane l's 16 bytes = C of chunks 4q .. 4q + 3
+//                   row r, k-part p, quad q, plane i starts at byte r * row_bytes + ((p * NQ + q) * 3 + i) * 1024, NQ = ceil(NX / 4), row_bytes = ks * NQ * 3072.
+//                   Chunks past the row's end (j >= NX, c >= the k-part's end) are padding: S = 0, C = 0x11111111 (a finite value; its activation is zero).
+//                   At the 1B / 3B / 7B shapes NX is 4 or 8 and there is no padding: 1.5 bytes per weight.
+//
+// The kernel is gemv_kernel<DT_BF16, PRO, EPI, NX, 1, XACC> (kernels/gemv.h) with the weight loads and the slice unpack replaced: a lane rebuilds the four
+// dwords of a 16-byte bf16 slice in registers and hands them to the same dot8, so the per-lane order of multiply-adds, the wave reduction and the K-part sums
+// are those of the plain kernel and the results are bit-identical.  Every lane issues 16-byte non-temporal loads over whole 1 KiB planes; the rows' escape
+// records (one 16-byte load per row, the same address in every lane) leave with the unit's weight loads; the repair is a VALU-only branch taken when a chunk's code dword has a zero nibble.
+#pragma once
+#include "gemv.h"
+
+namespace tgx {
+
+constexpr int PACKED_ESC = 4;            // escape entries per row (one 16-byte record)
+constexpr int PACKED_K_MAX = 32768;      // k < 2^15: the empty entry 0xffffffff can never name a chunk of the row
+
+struct PackedQuad { u32x4 s01, s23, c; };
+
+struct GemvPackedArgs {
+  GemvArgs g;               // g.W is not read
+  const unsigned char* P;   // packed planes
+  const u32x4* rec;         // [N] escape records
+  long long row_bytes;
+  unsigned int base2;       // E0 << 7 | E0 << 23
+};
+
+__device__ __forceinline__ bool packed_has_escape(unsigned int C) { return ((C - 0x11111111u) & ~C & 0x88888888u) != 0; }   // some nibble of C is 0
+
+// chunk (S0, S1, C) -> the 16-byte bf16 slice it encodes.  `chunk` = the chunk's index in its row.
+__device__ __forceinline__ Slice8<DT_BF16> packed_decode(unsigned int S0, unsigned int S1, unsigned int C, unsigned int base2, const u32x4 rec, int chunk) {
+  Slice8<DT_BF16> o;
+  // sign << 7 | mantissa bytes -> sign << 15 | mantissa in both halves: bytes 0, 2 are pair (w0, w1), bytes 1, 3 pair (w2, w3)
+  o.v[0] = ((S0 & 0x007f007fu) | ((S0 << 8) & 0x80008000u)) + ((( C        & 0x000f000fu) << 7) + base2);
+  o.v[1] = (((S0 >> 8) & 0x007f007fu) | (S0 & 0x80008000u)) + ((((C >> 4)  & 0x000f000fu) << 7) + base2);
+  o.v[2] = ((S1 & 0x007f007fu) | ((S1 << 8) & 0x80008000u)) + ((((C >> 8)  & 0x000f000fu) << 7) + base2);
+  o.v[3] = (((S1 >> 8) & 0x007f007fu) | (S1 & 0x80008000u)) + ((((C >> 12) & 0x000f000fu) << 7) + base2);
+  if (packed_has_escape(C)) {        // rare (benchmark checkpoint: 3e-5 of the weights); no load in here
+#pragma unroll
+    for (int e = 0; e < PACKED_ESC; e++) {
+      const unsigned int en = rec[e];
+      const unsigned int t = (en >> 16) & 7u, sh = (t & 1u) << 4;
+      const unsigned int dsel = (en >> 19) == (unsigned int)chunk ? (t >> 1) : 4u;      // the dword of the slice this entry replaces half of (4: none)
+      const unsigned int m = 0xffffu << sh, val = (en & 0xffffu) << sh;
+#pragma unroll
+      for (int dd = 0; dd < 4; dd++) o.v[dd] = dsel == (unsigned int)dd ? ((o.v[dd] & ~m) | val) : o.v[dd];
+    }
+  }
+  return o;
+}
+
+// R = 1, bf16.  The three forms: (PRO_RMSNORM, EPI_SILU_MUL), (PRO_PLAIN, EPI_RESIDUAL), (PRO_RMSNORM, EPI_LOGITS).  Everything outside load_unit and the
+// decode in front of dot8 is gemv_kernel's text for R = 1.
+template <int PRO, int EPI, int NX, bool XACC = false>
+__global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const GemvPackedArgs pa) {
+  constexpr int DT = DT_BF16;
+  constexpr int NQ = (NX + 3) / 4;
+  typedef elem_t<DT> E;
+  static_assert(PRO == PRO_PLAIN || PRO == PRO_RMSNORM, "packed forms: plain or RMSNorm prologue");
+  static_assert(EPI == EPI_SILU_MUL || EPI == EPI_RESIDUAL || EPI == EPI_LOGITS, "packed forms: gate_up, down, lm_head");
+  const GemvArgs& a = pa.g;
+  const int n_wg = (int)gridDim.x;
+  __shared__ float ps[4][2];
+  __shared__ float sv[1][4];
+  __shared__ int si[1][4];
+
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int KS = a.ks, UPB = 4 / KS;
+  const int slot = wv / KS, kpart = wv - slot * KS;
+  const int nchunk = a.K >> 3;                                         // 16-byte weight slices per row
+  const int per = ((nchunk + KS * 64 - 1) / (KS * 64)) * 64;           // slices per k-part (multiple of 64)
+  const int c_begin = min(kpart * per, nchunk), c_end = min(c_begin + per, nchunk);
+  const int stride = n_wg * UPB;
+
+  int cidx[NX];
+  bool cok[NX];
+#pragma unroll
+  for (int j = 0; j < NX; j++) {
+    const int c = c_begin + lane + 64 * j;
+    cok[j] = c < c_end;
+    cidx[j] = cok[j] ? c : max(c_end - 1, 0);    // clamped: always a legal slice of the row
+  }
+
+  const size_t lane_off = (size_t)kpart * NQ * 3072 + (size_t)lane * 16;      // this lane's 16 bytes of its k-part's first plane
+  PackedQuad wa[NQ], wb[NQ], na[NQ], nb[NQ];
+  // the two rows' escape records: loaded ahead of the unit's planes (every lane the same 16 bytes), moved to scalar registers one unit ahead of their use
+  u32x4 ea, eb, nea = {}, neb = {};
+  auto load_unit = [&](int ub, PackedQuad* ta, PackedQuad* tb, u32x4& ra_rec, u32x4& rb_rec) {
+    const int u = min(ub + slot, a.units - 1);
+    int ra, rb; bool v;
+    unit_rows<EPI>(a, u, ra, rb, v);
+    ra_rec = pa.rec[ra]; rb_rec = pa.rec[rb];
+    const unsigned char* pra = pa.P + (size_t)ra * pa.row_bytes + lane_off;
+    const unsigned char* prb = pa.P + (size_t)rb * pa.row_bytes + lane_off;
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      const u32x4* qa = reinterpret_cast<const u32x4*>(pra + (size_t)q * 3072);
+      const u32x4* qb = reinterpret_cast<const u32x4*>(prb + (size_t)q * 3072);
+      ta[q].s01 = load_nt(qa); ta[q].s23 = load_nt(qa + 64); ta[q].c = load_nt(qa + 128);
+      tb[q].s01 = load_nt(qb); tb[q].s23 = load_nt(qb + 64); tb[q].c = load_nt(qb + 128);
+    }
+  };
+  auto rec_uniform = [](const u32x4 v) {
+    return u32x4{(unsigned int)__builtin_amdgcn_readfirstlane((int)v[0]), (unsigned int)__builtin_amdgcn_readfirstlane((int)v[1]),
+                 (unsigned int)__builtin_amdgcn_readfirstlane((int)v[2]), (unsigned int)__builtin_amdgcn_readfirstlane((int)v[3])};
+  };
+
+  float xr[NX][8];
+  auto load_x = [&]() {
+    const f32x4* xg = reinterpret_cast<const f32x4*>(a.x);
+#pragma unroll
+    for (int j = 0; j < NX; j++) {
+      f32x4 v0 = xg[2 * cidx[j]], v1 = xg[2 * cidx[j] + 1];
+      if (!cok[j]) { v0 = f32x4{0.f, 0.f, 0.f, 0.f}; v1 = v0; }
+#pragma unroll
+      for (int t = 0; t < 4; t++) { xr[j][t] = v0[t]; xr[j][4 + t] = v1[t]; }
+    }
+  };
+  // 0. XACC: this thread's eight accumulators of the residual stream leave first (gemv_kernel, step 0)
+  ulonglong2 xacc0[(XACC && PRO == PRO_RMSNORM) ? 4 : 1];
+  if constexpr (XACC && PRO == PRO_RMSNORM) {
+    const ulonglong2* ag = reinterpret_cast<const ulonglong2*>(a.x_acc + (size_t)min((int)threadIdx.x, nchunk - 1) * 8);
+#pragma unroll
+    for (int q = 0; q < 4; q++) xacc0[q] = ag[q];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // 1. the first unit's weights are in flight before anything else is touched
+  int ub = blockIdx.x * UPB;
+  if (ub < a.units) load_unit(ub, wa, wb, nea, neb);
+  Slice8<DT> nw_x[(XACC && PRO == PRO_RMSNORM) ? NX : 1];
+  if constexpr (XACC && PRO == PRO_RMSNORM) {
+#pragma unroll
+    for (int j = 0; j < NX; j++) nw_x[j] = load_slice<DT>(static_cast<const E*>(a.norm_w), cidx[j]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // 2. this wave's slice of the activation vector -> registers (zero outside the range)
+  if constexpr (XACC && PRO == PRO_RMSNORM) {
+    extern __shared__ __attribute__((aligned(16))) float xs[];
+    for (int cs = threadIdx.x; cs < nchunk; cs += 256) {
+      ulonglong2 t[4];
+      if (cs == (int)threadIdx.x) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) t[q] = xacc0[q];
+      } else {       // hidden sizes beyond 2048: the later chunks
+        const ulonglong2* ag = reinterpret_cast<const ulonglong2*>(a.x_acc + (size_t)cs * 8);
+#pragma unroll
+        for (int q = 0; q < 4; q++) t[q] = ag[q];
+      }
+      float f[8];
+#pragma unroll
+      for (int q = 0; q < 4; q++) { f[2 * q] = fix_to_f32((long long)t[q].x); f[2 * q + 1] = fix_to_f32((long long)t[q].y); }
+      f32x4* dst = reinterpret_cast<f32x4*>(xs + (size_t)cs * 8);
+      dst[0] = f32x4{f[0], f[1], f[2], f[3]}; dst[1] = f32x4{f[4], f[5], f[6], f[7]};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NX; j++) {
+      const f32x4* xl = reinterpret_cast<const f32x4*>(xs + (size_t)cidx[j] * 8);
+      f32x4 v0 = xl[0], v1 = xl[1];
+      if (!cok[j]) { v0 = f32x4{0.f, 0.f, 0.f, 0.f}; v1 = v0; }
+#pragma unroll
+      for (int t = 0; t < 4; t++) { xr[j][t] = v0[t]; xr[j][4 + t] = v1[t]; }
+    }
+  } else {
+    load_x();
+  }
+  // sum of one value over the KS waves that share a unit, in wave order (every wave of the workgroup takes part)
+  auto ks_sum = [&](float& v) {
+    if (lane == 0) ps[wv][0] = v;
+    __syncthreads();
+    float t = ps[slot * KS][0];
+    for (int k = 1; k < KS; k++) t += ps[slot * KS + k][0];
+    v = t;
+    __syncthreads();               // ps is reused (unit loop)
+  };
+  if (PRO == PRO_RMSNORM) {   // HF order: weight * (x * rsqrt(mean(x^2)+eps))
+    const E* wg = static_cast<const E*>(a.norm_w);
+    Slice8<DT> nw[NX];
+#pragma unroll
+    for (int j = 0; j < NX; j++) { if constexpr (XACC) nw[j] = nw_x[j]; else nw[j] = load_slice<DT>(wg, cidx[j]); }       // in flight together with x
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < NX; j++)
+#pragma unroll
+      for (int t = 0; t < 8; t++) ss = fmaf(xr[j][t], xr[j][t], ss);
+    float ssq = wave_sum(ss);
+    if (KS > 1) ks_sum(ssq);
+    const float inv = 1.0f / sqrtf(ssq / (float)a.K + a.eps);
+#pragma unroll
+    for (int j = 0; j < NX; j++) {
+      float w[8];
+      slice_unpack<DT>(nw[j], w);
+#pragma unroll
+      for (int t = 0; t < 8; t++) xr[j][t] = w[t] * (xr[j][t] * inv);
+    }
+  }
+
+  if constexpr (PRO != PRO_PLAIN) {     // option act.round16 (gemv_kernel)
+    if (a.act16) {          // (kernel-uniform)
+#pragma unroll
+      for (int j = 0; j < NX; j++)
+#pragma unroll
+        for (int t = 0; t < 8; t++) xr[j][t] = elem_to_f32<DT>(f32_to_elem<DT>(xr[j][t]));
+    }
+  }
+
+  float best_val = -INFINITY;
+  int best_idx = 0x7fffffff;
+  ea = rec_uniform(nea); eb = rec_uniform(neb);
+
+  for (; ub < a.units; ub += stride) {   // trip count uniform per workgroup
+    const bool has_next = ub + stride < a.units;
+    if (has_next) load_unit(ub + stride, na, nb, nea, neb);
+
+    // epilogue operands are fetched now so that their latency hides under the dot products
+    const int u = ub + slot;
+    const bool writer = u < a.units && kpart == 0 && lane == 0;
+    int ra = 0, rb = 0; bool rb_valid = false;
+    float e0 = 0.f, e1 = 0.f;                // RESIDUAL: x[ra], x[rb]
+    if (writer) {
+      unit_rows<EPI>(a, u, ra, rb, rb_valid);
+      if (EPI == EPI_RESIDUAL) {
+        if constexpr (XACC) { e0 = fix_to_f32(a.res_acc[ra]); e1 = fix_to_f32(a.res_acc[rb]); }
+        else { e0 = a.out[ra]; e1 = a.out[rb]; }
+      }
+    }
+
+    float acc_a0 = 0.f, acc_b0 = 0.f, acc_a1 = 0.f, acc_b1 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NX; j++) {
+      const f32x4 xa = f32x4{xr[j][0], xr[j][1], xr[j][2], xr[j][3]};
+      const f32x4 xb = f32x4{xr[j][4], xr[j][5], xr[j][6], xr[j][7]};
+      const int q = j >> 2, jj = j & 3;
+      const u32x4 sa4 = (jj & 2) ? wa[q].s23 : wa[q].s01, sb4 = (jj & 2) ? wb[q].s23 : wb[q].s01;
+      const int chunk = c_begin + lane + 64 * j;
+      const Slice8<DT> da = packed_decode(sa4[(jj & 1) * 2], sa4[(jj & 1) * 2 + 1], wa[q].c[jj], pa.base2, ea, chunk);
+      const Slice8<DT> db = packed_decode(sb4[(jj & 1) * 2], sb4[(jj & 1) * 2 + 1], wb[q].c[jj], pa.base2, eb, chunk);
+      if (j & 1) { acc_a1 = dot8<DT>(acc_a1, da, xa, xb); acc_b1 = dot8<DT>(acc_b1, db, xa, xb); }
+      else       { acc_a0 = dot8<DT>(acc_a0, da, xa, xb); acc_b0 = dot8<DT>(acc_b0, db, xa, xb); }
+    }
+    float sa = wave_sum(acc_a0 + acc_a1);
+    float sb = wave_sum(acc_b0 + acc_b1);
+
+    if (KS > 1) {   // fixed-order sum of the KS k-part partials through LDS
+      __syncthreads();             // previous iteration's readers are done
+      if (lane == 0) { ps[wv][0] = sa; ps[wv][1] = sb; }
+      __syncthreads();
+      if (kpart == 0) {
+        sa = ps[slot * KS][0]; sb = ps[slot * KS][1];
+        for (int k = 1; k < KS; k++) { sa += ps[slot * KS + k][0]; sb += ps[slot * KS + k][1]; }
+      }
+    }
+
+    if (writer) {
+      float va = sa, vb = sb;
+      if (EPI == EPI_LOGITS) {
+        a.logits[ra] = va;
+        if (va > best_val) { best_val = va; best_idx = ra; }     // rows ascend within a wave: '>' keeps the first
+        if (rb_valid) {
+          a.logits[rb] = vb;
+          if (vb > best_val) { best_val = vb; best_idx = rb; }
+        }
+      } else {
+        if (a.bias) { const E* bias = static_cast<const E*>(a.bias); va += elem_to_f32<DT>(bias[ra]); vb += elem_to_f32<DT>(bias[rb]); }
+        if (EPI == EPI_RESIDUAL) {
+          a.out[ra] = e0 + va;
+          if (rb_valid) a.out[rb] = e1 + vb;
+          if constexpr (XACC) { a.res_acc[ra] = 0; if (rb_valid) a.res_acc[rb] = 0; }     // this lane is the only reader / writer of its rows' accumulators
+        } else if (EPI == EPI_SILU_MUL) {
+          a.out[u] = round_storage_if<DT>((va / (1.0f + expf(-va))) * vb, a.act16);        // (the down product's input)
+        }
+      }
+    }
+
+#pragma unroll
+    for (int q = 0; q < NQ; q++) { wa[q] = na[q]; wb[q] = nb[q]; }
+    ea = rec_uniform(nea); eb = rec_uniform(neb);      // (the records left before the next unit's planes: this waits for nothing behind them)
+  }
+
+  if (EPI == EPI_LOGITS) {
+    // workgroup argmax, ties -> lowest index (== argmax(logits, -1), Sampler.cpp:28)
+    if (lane == 0) { sv[0][wv] = best_val; si[0][wv] = best_idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float bv = sv[0][0]; int bi = si[0][0];
+      for (int w = 1; w < 4; w++)
+        if (sv[0][w] > bv || (sv[0][w] == bv && si[0][w] < bi)) { bv = sv[0][w]; bi = si[0][w]; }
+      a.part_val[blockIdx.x] = bv;
+      a.part_idx[blockIdx.x] = bi;
+    }
+  }
+}
+
+// ---- the packer (tgx_finalize) ---------------------------------------------------------------------------------------------------------------------
+// stat[0] = Emax, stat[1] = rows whose record overflowed, stat[2] = escapes of the matrix, stat[3] = most escapes in one row
+__global__ __launch_bounds__(256) void packed_maxexp_kernel(const bf16_t* W, size_t n8, int* stat) {
+  int m = 0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
+    const u32x4 v = reinterpret_cast<const u32x4*>(W)[i];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int e0 = (v[t] >> 7) & 0xff, e1 = (v[t] >> 23) & 0xff;
+      if (e0 < 255) m = max(m, e0);
+      if (e1 < 255) m = max(m, e1);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) atomicMax(stat, m);
+}
+
+struct PackRowsArgs {
+  const bf16_t* W;          // [N][K]
+  int N, K, ks, nx;
+  unsigned char* P;
+  u32x4* rec;
+  long long row_bytes;
+  int* stat;
+};
+
+// one wave per row: the row's escape record, then its planes
+__global__ __launch_bounds__(64) void pack_rows_kernel(const PackRowsArgs a) {
+  __shared__ unsigned int ent[PACKED_ESC];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int E0 = max(a.stat[0] - 15, 0);
+  const bf16_t* w = a.W + (size_t)row * a.K;
+  if (lane < PACKED_ESC) ent[lane] = 0xffffffffu;
+  __syncthreads();
+  int cnt = 0;
+  for (int k0 = 0; k0 < a.K; k0 += 64) {
+    const int k = k0 + lane;
+    unsigned int bits = 0; bool esc = false;
+    if (k < a.K) { bits = w[k]; const int code = (int)((bits >> 7) & 0xff) - E0; esc = code < 1 || code > 15; }
+    const unsigned long long bal = __ballot(esc);
+    const int p = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+    if (esc && p < PACKED_ESC) ent[p] = ((unsigned int)k << 16) | bits;
+    cnt += __popcll(bal);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    a.rec[row] = u32x4{ent[0], ent[1], ent[2], ent[3]};
+    if (cnt > PACKED_ESC) atomicAdd(a.stat + 1, 1);
+    if (cnt) { atomicAdd(a.stat + 2, cnt); atomicMax(a.stat + 3, cnt); }
+  }
+  const int nchunk = a.K >> 3, nq = (a.nx + 3) / 4;
+  const int per = ((nchunk + a.ks * 64 - 1) / (a.ks * 64)) * 64;
+  for (int p = 0; p < a.ks; p++) {
+    const int c_begin = min(p * per, nchunk), c_end = min(c_begin + per, nchunk);
+    for (int q = 0; q < nq; q++) {
+      unsigned int S[8], C[4];
+#pragma unroll
+      for (int jj = 0; jj < 4; jj++) {
+        const int j = 4 * q + jj, c = c_begin + lane + 64 * j;
+        S[2 * jj] = 0; S[2 * jj + 1] = 0; C[jj] = 0x11111111u;
+        if (j < a.nx && c < c_end) {
+          const u32x4 v = reinterpret_cast<const u32x4*>(w)[c];
+          unsigned int b[8], cd[8];
+#pragma unroll
+          for (int t = 0; t < 8; t++) {
+            const unsigned int bits = (v[t >> 1] >> (16 * (t & 1))) & 0xffffu;
+            const int code = (int)((bits >> 7) & 0xff) - E0;
+            b[t] = ((bits >> 8) & 0x80u) | (bits & 0x7fu);
+            cd[t] = (code < 1 || code > 15) ? 0u : (unsigned int)code;
+          }
+          S[2 * jj] = b[0] | (b[2] << 8) | (b[1] << 16) | (b[3] << 24);
+          S[2 * jj + 1] = b[4] | (b[6] << 8) | (b[5] << 16) | (b[7] << 24);
+          unsigned int cc = 0;
+#pragma unroll
+          for (int t = 0; t < 4; t++) cc |= (cd[2 * t] << (4 * t)) | (cd[2 * t + 1] << (4 * t + 16));
+          C[jj] = cc;
+        }
+      }
+      u32x4* dst = reinterpret_cast<u32x4*>(a.P + (size_t)row * a.row_bytes + ((size_t)p * nq + q) * 3072) + lane;
+      dst[0] = u32x4{S[0], S[1], S[2], S[3]};
+      dst[64] = u32x4{S[4], S[5], S[6], S[7]};
+      dst[128] = u32x4{C[0], C[1], C[2], C[3]};
+    }
+  }
+}
+
+}  // namespace tgx
