@@ -27,7 +27,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 
 def _deps():
-    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h")]
+    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h")]
     kd = os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -77,6 +77,22 @@ CXX = shutil.which("g++") or "g++"
 CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-exceptions", "-Wall", "-Wextra", "-pthread"]
 
 
+def _stale(target, deps):
+    return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(d) for d in deps)
+
+
+def build_kv_pool_check(force: bool = False, verbose: bool = False):
+    """tests/kv_pool_check.cpp (the CPU audit of csrc/kv_pool.h, its own main) under the address and undefined-behaviour sanitizers: tests/_build/kv_pool_check."""
+    src, target = os.path.join(HERE, "..", "tests", "kv_pool_check.cpp"), os.path.join(TEST_BUILD, "kv_pool_check")
+    os.makedirs(TEST_BUILD, exist_ok=True)
+    if force or _stale(target, [src, os.path.join(CSRC, "kv_pool.h")]):
+        cmd = [CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-Wall", "-Wextra", src, "-o", target]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+    return target
+
+
 def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = False):
     """The C++ host engine (no HIP needed: it dlopen()s the device shim): libtgx_host.so + the tgx_cli binary.
 
@@ -89,7 +105,7 @@ def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = Fa
         lib, cli, flags = HOST_TEST_LIB, HOST_TEST_CLI, ["-DTGXH_TEST_HOOKS"]
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     for target, extra in ((lib, [os.path.join(HOST, "engine_c.cpp"), "-shared"]), (cli, [os.path.join(HOST, "main.cpp")])):
-        if not force and os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(d) for d in deps):
+        if not force and not _stale(target, deps):
             continue
         cmd = [CXX] + CXXFLAGS + flags + srcs + extra + ["-o", target, "-ldl"]
         if verbose:

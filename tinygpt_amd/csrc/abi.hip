@@ -302,94 +302,64 @@ static int ensure_step_graph(tgx_ctx* c, const tgx_sampler_cfg& cfg, bool want_m
 // new entries BY VALUE (stream-ordered behind the launches that still read the old ones; no host buffer has to outlive the call).
 struct KvTblUpdate { int n; int idx[16]; int val[16]; };
 static __global__ void kv_tbl_set_kernel(int* tbl, KvTblUpdate u) { if ((int)threadIdx.x < u.n) tbl[u.idx[threadIdx.x]] = u.val[threadIdx.x]; }
-
 // (a fork writes whole rows of table entries: more than 16 changes travel 240 at a time)
 struct KvTblUpdateWide { int n; int idx[240]; int val[240]; };
 static __global__ void kv_tbl_set_wide_kernel(int* tbl, KvTblUpdateWide u) { if ((int)threadIdx.x < u.n) tbl[u.idx[threadIdx.x]] = u.val[threadIdx.x]; }
 
-static void kv_tbl_push(tgx_ctx* c, const std::vector<std::pair<int, int>>& changes) {      // (flat table index, value)
-  if (changes.size() > 16) {
-    for (size_t i = 0; i < changes.size(); i += 240) {
-      KvTblUpdateWide u{};
-      u.n = (int)std::min<size_t>(240, changes.size() - i);
-      for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first; u.val[k] = changes[i + (size_t)k].second; c->kv_tbl_host[(size_t)u.idx[k]] = u.val[k]; }
-      hipLaunchKernelGGL(kv_tbl_set_wide_kernel, dim3(1), dim3(256), 0, c->stream, c->kv_tbl, u);
-    }
-    return;
-  }
-  for (size_t i = 0; i < changes.size(); i += 16) {
-    KvTblUpdate u{};
-    u.n = (int)std::min<size_t>(16, changes.size() - i);
-    for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first; u.val[k] = changes[i + (size_t)k].second; c->kv_tbl_host[(size_t)u.idx[k]] = u.val[k]; }
-    hipLaunchKernelGGL(kv_tbl_set_kernel, dim3(1), dim3(64), 0, c->stream, c->kv_tbl, u);
+template <typename U>
+static void kv_tbl_push_by(tgx_ctx* c, const KvPool::Changes& changes, void (*kernel)(int*, U), size_t per, int threads) {
+  for (size_t i = 0; i < changes.size(); i += per) {
+    U u{};
+    u.n = (int)std::min(per, changes.size() - i);
+    for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first; u.val[k] = changes[i + (size_t)k].second; }
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, c->stream, c->kv_tbl, u);
   }
 }
-
-// Shared blocks (tgx_fork_row): kv_ref[b] = the rows whose tables map physical block b.  A block leaves the free list at count 0 -> 1 and returns to it at 1 -> 0.
-// THE INVARIANT: a block mapped by more than one row is FULL — every position in it is < past of every row that maps it — so no launch
-// ever writes to it (every writer of the cache writes positions >= its row's past).  It is asserted where blocks are assigned: a block handed out for writing must
-// be mapped by nobody (kv_take_block), a block shared by reference must lie wholly below the source's past (kv_share_blocks).  A violation is a bug of this file
-// that would let one sequence write into another's cache: the process stops there (the library is built with NDEBUG, so the check is spelled out).
-#define KV_ASSERT(cond, what)                                                                                   \
-  do {                                                                                                          \
-    if (!(cond)) { fprintf(stderr, "tgx: paged KV invariant violated (%s) at %s:%d\n", what, __FILE__, __LINE__); abort(); } \
-  } while (0)
-static int kv_take_block(tgx_ctx* c) {
-  const int b = c->kv_free.back();
-  c->kv_free.pop_back();
-  KV_ASSERT(c->kv_ref[(size_t)b] == 0, "a block on the free list is still mapped by a row");
-  c->kv_ref[(size_t)b] = 1;
-  return b;
-}
-static void kv_drop_block(tgx_ctx* c, int b) {
-  if (--c->kv_ref[(size_t)b] == 0) c->kv_free.push_back(b);
-}
-// blocks that return to the free list when `row` releases its blocks: only those nobody else maps (a block a forked sibling still maps stays assigned).  Through the
-// entry points an admissible row (retired, or holding no position) holds no block at all — tgx_reset_row released them — so this reads 0 there; it is what keeps the
-// all-or-nothing sums of admit_rows / tgx_fork_row true whatever a row holds.  (A block shared ONLY among the rows of one call is not counted: the sum errs towards refusing.)
-static long long kv_blocks_given_back(const tgx_ctx* c, int row) {
-  long long n = 0;
-  for (int b = 0; b < c->kv_row_nblk[(size_t)row]; b++) n += c->kv_ref[(size_t)c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + b]] == 1;
-  return n;
+static void kv_tbl_push(tgx_ctx* c, const KvPool::Changes& changes) {      // the table entries a KvPool call wrote (kv_pool.h), into the device table
+  if (changes.size() > 16) kv_tbl_push_by(c, changes, kv_tbl_set_wide_kernel, 240, 256);
+  else kv_tbl_push_by(c, changes, kv_tbl_set_kernel, 16, 64);
 }
 
 int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens) {
   if (!c->kv_paged) return TGX_OK;
-  const int need = (int)((tokens + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK);
-  int& have = c->kv_row_nblk[(size_t)row];
-  if (need <= have) return TGX_OK;
-  if (need > c->kv_tbl_stride) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d wants %lld tokens (contextSize %d)", row, tokens, c->d.max_ctx);
-  if ((size_t)(need - have) > c->kv_free.size())
-    return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %d more blocks of %d tokens, %zu free of %d (option kv.budget_tokens = %d)", row, need - have,
-                   tgx::KV_BLOCK, c->kv_free.size(), c->kv_nblocks - 1, c->kv_budget_tokens);
-  std::vector<std::pair<int, int>> ch;
-  for (; have < need; have++) ch.emplace_back(row * c->kv_tbl_stride + have, kv_take_block(c));
-  kv_tbl_push(c, ch);
-  return TGX_OK;
+  KvPool::Changes ch;
+  const int more = c->kv.blocks_for(tokens) - c->kv.row_blocks(row);
+  switch (c->kv.grow(row, tokens, ch)) {
+    case KvPool::GROW_BEYOND_TABLE: return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d wants %lld tokens (contextSize %d)", row, tokens, c->d.max_ctx);
+    case KvPool::GROW_EXHAUSTED:
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %d more blocks of %d tokens, %zu free of %d (option kv.budget_tokens = %d)", row, more,
+                     tgx::KV_BLOCK, c->kv.free_blocks(), c->kv.n_blocks() - 1, c->kv_budget_tokens);
+    default: kv_tbl_push(c, ch); return TGX_OK;
+  }
 }
 
-// paged KV: a finished row keeps the blocks its length needs; the ones assigned up front for the steps it did not take go back to the free list, their table
-// entries back to the scratch block.  (A block a forked sibling still maps only loses this row's reference.)
+// paged KV: a finished row keeps the blocks its length needs; the ones assigned up front for the steps it did not take go back to the pool
 static void kv_trim_row(tgx_ctx* c, int row, long long tokens) {
   if (!c->kv_paged) return;
-  const int keep = (int)((tokens + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK);
-  int& have = c->kv_row_nblk[(size_t)row];
-  std::vector<std::pair<int, int>> ch;
-  for (int b = keep; b < have; b++) { const int i = row * c->kv_tbl_stride + b; kv_drop_block(c, c->kv_tbl_host[(size_t)i]); ch.emplace_back(i, 0); }
-  if (keep < have) have = keep;
+  KvPool::Changes ch;
+  c->kv.trim(row, tokens, ch);
   kv_tbl_push(c, ch);
 }
 static void kv_release_row(tgx_ctx* c, int row) { kv_trim_row(c, row, 0); }       // all of the row's blocks
 
-// tgx_fork_row: row `dst` (holding no block) maps the first n_full blocks of `src` by reference
-static void kv_share_blocks(tgx_ctx* c, int src, int dst, int n_full, std::vector<std::pair<int, int>>& ch) {      // ch: the table changes, pushed by the caller
-  KV_ASSERT((long long)n_full * tgx::KV_BLOCK <= c->row_past[(size_t)src] && n_full <= c->kv_row_nblk[(size_t)src] && c->kv_row_nblk[(size_t)dst] == 0, "a block that is not full was about to be shared");
-  for (int b = 0; b < n_full; b++) {
-    const int blk = c->kv_tbl_host[(size_t)src * c->kv_tbl_stride + b];
-    c->kv_ref[(size_t)blk]++;
-    ch.emplace_back(dst * c->kv_tbl_stride + b, blk);
+// one kv_fork_kernel launch: the cache geometry of the context and the span length of n_tok positions filled here, the rest (ids, kv_rows, the state segments) and
+// the grid by the caller's `rest`
+template <typename F>
+static void launch_kv_copy(tgx_ctx* c, long long n_tok, F&& rest) {
+  const tgx_model_desc& d = c->d;
+  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz;
+  const bool v16 = tok_bytes % 16 == 0;
+  tgx::KvForkArgs a{};
+  a.k = c->slab_k; a.v = c->slab_v; a.kv_heads = d.kv_heads; a.n_spans = d.layers * d.kv_heads;
+  if (c->kv_paged) {
+    a.head_stride = tgx::KV_BLOCK * tok_bytes; a.id_stride = d.kv_heads * a.head_stride; a.layer_stride = c->kv.n_blocks() * a.id_stride;
+  } else {
+    a.head_stride = d.max_ctx * tok_bytes; a.layer_stride = d.kv_heads * a.head_stride; a.id_stride = (long long)c->kv_row_elems * (long long)c->esz;
   }
-  c->kv_row_nblk[(size_t)dst] = n_full;
+  a.span_vecs = n_tok * tok_bytes / (v16 ? 16 : 4);
+  const dim3 grid = rest(a), block(tgx::KV_FORK_THREADS);
+  if (v16) hipLaunchKernelGGL(tgx::kv_fork_kernel<tgx::u32x4>, grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL(tgx::kv_fork_kernel<unsigned int>, grid, block, 0, c->stream, a);
 }
 
 // ---- per-row request state (tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows): host-side fields travel BY VALUE in a one-thread launch, stream-ordered
@@ -421,7 +391,6 @@ static void row_req_push(tgx_ctx* c, int row, int what) {
 }
 static void row_req_reset(tgx_ctx* c, int row) {   // tgx_reset_row: the default settings and a fresh state
   c->row_req_host[(size_t)row] = row_req_default();
-  c->row_fin[(size_t)row] = 0;
   row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE);
 }
 static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
@@ -431,7 +400,7 @@ static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
   return s;
 }
 static int nologits_row(const tgx_ctx* c) {   // a live row of the batch that was truncated and not extended since (tgx_truncate_row), or -1
-  for (int b = 0; b < c->batch; b++) if (c->row_nologits[(size_t)b] && !c->row_idle[(size_t)b]) return b;
+  for (int b = 0; b < c->batch; b++) if (c->row_host[(size_t)b].nologits && !c->row_host[(size_t)b].idle) return b;
   return -1;
 }
 #define REFUSE_NOLOGITS(c, what)                                                                                                                     \
@@ -439,17 +408,16 @@ static int nologits_row(const tgx_ctx* c) {   // a live row of the batch that wa
     if (nologits_row(c) >= 0) return set_err((c), TGX_ERR_STATE, "%s: row %d was truncated and holds no logits: tgx_extend_row it first", what, nologits_row(c)); \
   } while (0)
 static int finished_row(const tgx_ctx* c) {   // a live row of the batch that finished on the device, or -1
-  for (int b = 0; b < c->batch; b++) if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b]) return b;
+  for (int b = 0; b < c->batch; b++) if (c->row_host[(size_t)b].fin && !c->row_host[(size_t)b].idle) return b;
   return -1;
 }
 
 // tgx_read_probs evaluates a row's final probabilities on demand: remember what its last sampled step was configured with
 static void note_sampled(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg) {
-  if (c->row_probs_cfg.size() < (size_t)c->d.max_batch) { c->row_probs_cfg.resize((size_t)c->d.max_batch); c->row_probs_ok.assign((size_t)c->d.max_batch, 0); }
   const bool sampled = !is_greedy(&cfg);
-  for (int b = row0; b < row0 + R; b++) { c->row_probs_cfg[(size_t)b] = cfg; c->row_probs_ok[(size_t)b] = sampled ? 1 : 0; }
+  for (int b = row0; b < row0 + R; b++) { c->row_host[(size_t)b].probs_cfg = cfg; c->row_host[(size_t)b].probs_ok = sampled; }
   c->have_probs = false;
-  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_probs_ok[(size_t)b];
+  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
 }
 
 // the engine passes one seed for a whole generation (the draw mixes in position and row): only a CHANGED seed is copied — and that
@@ -490,12 +458,12 @@ static int read_tok_log(tgx_ctx* c, int64_t start, int n, int* dst) {
 }
 
 // rows mode (c->row_union >= 0, tgx_decode_rows): every row samples with its own settings, `cfg` and `seed` are unused, finished rows take no blocks and stay
-// where they are, and the caller updates row_past from the device afterwards (rows may finish on the device)
+// where they are, and the caller updates the rows' `past` from the device afterwards (rows may finish on the device)
 static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t seed, int n) {
   const bool rows = c->row_union >= 0;
   if (c->kv_paged)       // every live row's next n positions have a block before the steps that write them are enqueued
     for (int b = 0; b < c->batch; b++)
-      if (!c->row_idle[(size_t)b] && !c->row_fin[(size_t)b]) { int rc = kv_ensure_blocks(c, b, c->row_past[(size_t)b] + n); if (rc) return rc; }
+      if (!c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin) { int rc = kv_ensure_blocks(c, b, c->row_host[(size_t)b].past + n); if (rc) return rc; }
   if (rows) {
     for (int b = 0; b < c->batch; b++) note_sampled(c, b, 1, row_cfg(c, b));
   } else if (int rc = ensure_seed(c, cfg, seed)) return rc;
@@ -504,17 +472,17 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
     int rc = ensure_skinny_ws(c, std::min(c->decode_step_rows, c->batch));
     if (rc) return rc;
   }
-  // a retired row rides along from wherever its position word stands (row_past mirrors it); the attention form and the capacity check are chosen for the
+  // a retired row rides along from wherever its position word stands (RowHost::past mirrors it); the attention form and the capacity check are chosen for the
   // longest LIVE row, so an idle row that has outrun it (the longer rows were retired since) restarts from position 0
   for (int b = 0; b < c->batch; b++)
-    if (c->row_idle[(size_t)b] && c->row_past[(size_t)b] > c->past) {
+    if (c->row_host[(size_t)b].idle && c->row_host[(size_t)b].past > c->past) {
       HIP_OK(c, hipMemsetAsync(c->rows[(size_t)b].pos, 0, 4, c->stream));
-      c->row_past[(size_t)b] = 0;
+      c->row_host[(size_t)b].past = 0;
     }
   // a finished row rides at its own length (it does not count for `past`): the attention form is chosen for it as well when it is the longest
   if (rows)
     for (int b = 0; b < c->batch; b++)
-      if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b]) c->past = std::max(c->past, c->row_past[(size_t)b]);
+      if (c->row_host[(size_t)b].fin && !c->row_host[(size_t)b].idle) c->past = std::max(c->past, c->row_host[(size_t)b].past);
   // The attention form depends on the context (four-wave direct / sixteen-wave direct / split + combine / matrix cores): a call that crosses a limit is
   // issued in chunks, each on the form of its own contexts, from the cache of captured graphs
   int remaining = n;
@@ -538,7 +506,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
       if (int rc = launches_ok(c)) return rc;
     }
     c->past += m;
-    if (!rows) for (int b = 0; b < c->batch; b++) c->row_past[(size_t)b] += m;
+    if (!rows) for (int b = 0; b < c->batch; b++) c->row_host[(size_t)b].past += m;
     c->steps_issued += m;
     remaining -= m;
   }
@@ -837,17 +805,11 @@ int tgx_finalize(tgx_ctx* c) {
   if (c->kv_budget_tokens > 0) {                      // paged KV: pools of KV_BLOCK-token blocks shared by the rows (kernels/common.h)
     if (c->dt == tgx::DT_F32) return set_err(c, TGX_ERR_UNSUPPORTED, "kv.budget_tokens: paged KV serves the 16-bit storage dtypes");
     c->kv_paged = true;
-    c->kv_nblocks = (c->kv_budget_tokens + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK + 1;       // + the scratch block 0
-    c->kv_tbl_stride = (d.max_ctx + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK;
-    kv_total = (size_t)d.layers * c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd;
+    c->kv.init(d.max_batch, d.max_ctx, c->kv_budget_tokens, tgx::KV_BLOCK);
+    kv_total = (size_t)d.layers * c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * hd;
     c->kv_row_elems = 1;                              // "the rows are separate sequences" wherever a row stride is tested against 0; never used as a stride (decode.hip kvs)
-    if ((rc = dev_alloc(c, &c->kv_tbl, B * (size_t)c->kv_tbl_stride))) return rc;
-    HIP_OK(c, hipMemset(c->kv_tbl, 0, B * (size_t)c->kv_tbl_stride * 4));
-    c->kv_tbl_host.assign(B * (size_t)c->kv_tbl_stride, 0);
-    c->kv_row_nblk.assign(B, 0);
-    c->kv_ref.assign((size_t)c->kv_nblocks, 0);
-    c->kv_free.clear();
-    for (int b = c->kv_nblocks - 1; b >= 1; b--) c->kv_free.push_back(b);
+    if ((rc = dev_alloc(c, &c->kv_tbl, B * (size_t)c->kv.tbl_stride()))) return rc;
+    HIP_OK(c, hipMemset(c->kv_tbl, 0, B * (size_t)c->kv.tbl_stride() * 4));
   }
   c->attn_part_row = (size_t)d.heads * c->attn_nsplit * (hd + 4);
   if ((rc = dev_alloc(c, &c->slab_x, B * H))) return rc;
@@ -877,7 +839,7 @@ int tgx_finalize(tgx_ctx* c) {
     r.attn_part = c->slab_attn_part + b * c->attn_part_row;
     r.tok = c->slab_tok + b; r.pos = c->slab_pos + b; r.prompt = c->slab_prompt + b * d.max_ctx;
     r.kcache = c->slab_k + b * kv_elems * c->esz; r.vcache = c->slab_v + b * kv_elems * c->esz;
-    if (c->kv_paged) { r.kcache = c->slab_k; r.vcache = c->slab_v; r.tbl = c->kv_tbl + b * (size_t)c->kv_tbl_stride; }
+    if (c->kv_paged) { r.kcache = c->slab_k; r.vcache = c->slab_v; r.tbl = c->kv_tbl + b * (size_t)c->kv.tbl_stride(); }
   }
   if ((rc = dev_alloc(c, &c->ch_x, 4 * (size_t)H))) return rc;
   if ((rc = dev_alloc(c, &c->ch_q, 4 * (size_t)qd))) return rc;
@@ -909,15 +871,11 @@ int tgx_finalize(tgx_ctx* c) {
   if ((rc = dev_alloc(c, &c->slab_acc, B * (size_t)H))) return rc;
   HIP_OK(c, hipMemset(c->slab_acc, 0, B * (size_t)H * 8));
   c->row_req_host.assign(B, row_req_default());
-  c->row_fin.assign(B, 0);
   if ((rc = dev_alloc(c, &c->row_req, B))) return rc;
   HIP_OK(c, hipMemcpy(c->row_req, c->row_req_host.data(), B * sizeof(tgx::RowReq), hipMemcpyHostToDevice));
   if ((rc = pack_weights(c))) return rc;
   c->past = 0;
-  c->row_past.assign(B, 0);
-  c->row_tok.assign(B, 0);
-  c->row_idle.assign(B, 0);
-  c->row_nologits.assign(B, 0);
+  c->row_host.assign(B, RowHost{});
   c->finalized = true;
   return TGX_OK;
 }
@@ -954,7 +912,7 @@ int tgx_forward(tgx_ctx* c, const int64_t* ids, int batch, int seq) {
   if (finished_row(c) >= 0) return set_err(c, TGX_ERR_STATE, "row %d finished in tgx_decode_rows: tgx_reset_row it (or tgx_reset_cache) first", finished_row(c));
   if (c->past + seq > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, seq, c->d.max_ctx);
   for (int b = 0; b < batch; b++)
-    if (c->row_idle[(size_t)b] || c->row_past[(size_t)b] != c->past) return set_err(c, TGX_ERR_STATE, "tgx_forward on a batch whose rows differ in length (row %d: %lld, longest %lld): use tgx_decode / tgx_forward_row, or tgx_reset_cache", b, (long long)c->row_past[(size_t)b], (long long)c->past);
+    if (c->row_host[(size_t)b].idle || c->row_host[(size_t)b].past != c->past) return set_err(c, TGX_ERR_STATE, "tgx_forward on a batch whose rows differ in length (row %d: %lld, longest %lld): use tgx_decode / tgx_forward_row, or tgx_reset_cache", b, (long long)c->row_host[(size_t)b].past, (long long)c->past);
   for (int64_t i = 0; i < (int64_t)batch * seq; i++)
     if (ids[i] < 0 || ids[i] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
   HIP_OK(c, hipSetDevice(c->device));
@@ -967,11 +925,11 @@ int tgx_forward(tgx_ctx* c, const int64_t* ids, int batch, int seq) {
     if (int rc = issue_pass(c, row0, std::min(per, batch - row0), seq, (int)c->past)) return rc;      // every row at the batch's pastLength
   if (int rc = finish_pass(c)) return rc;
   c->past += seq;
-  for (int b = 0; b < batch; b++) { c->row_past[(size_t)b] = c->past; c->row_tok[(size_t)b] = 0; c->row_idle[(size_t)b] = 0; c->row_nologits[(size_t)b] = 0; }
+  for (int b = 0; b < batch; b++) c->row_host[(size_t)b].restart(c->past, /*idle=*/false, c->row_host[(size_t)b].fin);
   c->have_logits = true;
   c->have_token = false;
   c->have_probs = false;                          // the logits are new: no sampled step belongs to them yet
-  std::fill(c->row_probs_ok.begin(), c->row_probs_ok.end(), 0);
+  for (RowHost& r : c->row_host) r.probs_ok = false;
   return TGX_OK;
 }
 
@@ -1003,7 +961,7 @@ int tgx_sample(tgx_ctx* c, const tgx_sampler_cfg* cfg, uint64_t seed, int64_t* o
     HIP_OK(c, hipMemcpy(&t, c->rows[(size_t)b].tok, 4, hipMemcpyDeviceToHost));
     if (out_ids) out_ids[b] = t;
     if (b == 0) c->last_sampled0 = t;
-    c->row_tok[(size_t)b] = 1;
+    c->row_host[(size_t)b].tok = 1;
   }
   c->have_token = true;
   return TGX_OK;
@@ -1067,15 +1025,11 @@ int tgx_reset_cache(tgx_ctx* c) {
   for (auto& r : c->rows) HIP_OK(c, hipMemsetAsync(r.pos, 0, 4, c->stream));
   for (int b = 0; b < c->d.max_batch; b++) kv_release_row(c, b);
   std::fill(c->row_req_host.begin(), c->row_req_host.end(), row_req_default());
-  std::fill(c->row_fin.begin(), c->row_fin.end(), 0);
   HIP_OK(c, hipMemcpyAsync(c->row_req, c->row_req_host.data(), c->row_req_host.size() * sizeof(tgx::RowReq), hipMemcpyHostToDevice, c->stream));   // (synchronised below)
   if (c->slab_acc) HIP_OK(c, hipMemsetAsync(c->slab_acc, 0, (size_t)c->d.max_batch * c->d.hidden * 8, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->past = 0;
-  std::fill(c->row_past.begin(), c->row_past.end(), 0);
-  std::fill(c->row_tok.begin(), c->row_tok.end(), 0);
-  std::fill(c->row_idle.begin(), c->row_idle.end(), 0);
-  std::fill(c->row_nologits.begin(), c->row_nologits.end(), 0);
+  for (RowHost& r : c->row_host) r.restart(0, /*idle=*/false, /*fin=*/0);
   c->have_logits = c->have_token = false;
   c->poisoned = false;
   return TGX_OK;
@@ -1084,18 +1038,18 @@ int tgx_reset_cache(tgx_ctx* c) {
 int64_t tgx_past_length(const tgx_ctx* c) { return c ? c->past : -1; }
 
 // ---- per-row sequence lifecycle (include/tgx.h, ABI 3).  The step kernels read every row's position from its own device word; the host keeps the
-// mirror row_past[] and `past` = the longest row of the batch (capacity checks, attention-form limits: a form chosen for the longest row is valid for
+// mirror row_host[].past and `past` = the longest row of the batch (capacity checks, attention-form limits: a form chosen for the longest row is valid for
 // the shorter ones — the direct form's pass count and the split form's active splits are derived on the device from each row's position).
-// Retired rows (row_idle) are left out of both: nothing waits for them and they bound nothing (run_decode_steps keeps them below the longest live row).
+// Retired rows (RowHost::idle) are left out of both: nothing waits for them and they bound nothing (run_decode_steps keeps them below the longest live row).
 static void refresh_longest(tgx_ctx* c) {
   int64_t m = 0;
   int live = 0;
   bool all = true;
   for (int b = 0; b < c->batch; b++) {
-    if (c->row_idle[(size_t)b] || c->row_fin[(size_t)b]) continue;      // (a finished row counts for neither, include/tgx.h tgx_decode_rows)
+    if (c->row_host[(size_t)b].idle || c->row_host[(size_t)b].fin) continue;      // (a finished row counts for neither, include/tgx.h tgx_decode_rows)
     live++;
-    m = std::max(m, c->row_past[(size_t)b]);
-    all = all && c->row_tok[(size_t)b];
+    m = std::max(m, c->row_host[(size_t)b].past);
+    all = all && c->row_host[(size_t)b].tok;
   }
   c->past = m;
   c->have_token = live > 0 && all;
@@ -1103,7 +1057,7 @@ static void refresh_longest(tgx_ctx* c) {
 
 int64_t tgx_past_length_row(const tgx_ctx* c, int row) {
   if (!c || !c->finalized || row < 0 || row >= c->d.max_batch) return -1;
-  return c->row_idle[(size_t)row] ? 0 : c->row_past[(size_t)row];        // a retired row holds no sequence, wherever its position word stands
+  return c->row_host[(size_t)row].idle ? 0 : c->row_host[(size_t)row].past;        // a retired row holds no sequence, wherever its position word stands
 }
 
 int tgx_reset_row(tgx_ctx* c, int row) {
@@ -1114,11 +1068,8 @@ int tgx_reset_row(tgx_ctx* c, int row) {
   HIP_OK(c, hipSetDevice(c->device));
   HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream));     // stream-ordered behind the steps already enqueued
   kv_release_row(c, row);                                                     // paged KV: its blocks go back to the pool (a retired row rides along on the scratch block)
-  row_req_reset(c, row);                                                      // tgx_decode_rows: default settings, not finished
-  c->row_past[(size_t)row] = 0;
-  c->row_tok[(size_t)row] = 0;
-  c->row_nologits[(size_t)row] = 0;
-  c->row_idle[(size_t)row] = row < c->batch;                                  // a live slot becomes a retired one: the batch keeps stepping without it
+  row_req_reset(c, row);                                                      // tgx_decode_rows: default settings ...
+  c->row_host[(size_t)row].restart(0, /*idle=*/row < c->batch, /*fin=*/0);    // ... not finished; a live slot becomes a retired one: the batch keeps stepping without it
   refresh_longest(c);
   return TGX_OK;
 }
@@ -1126,12 +1077,39 @@ int tgx_reset_row(tgx_ctx* c, int row) {
 // host state of a row after its prompt pass went through (the caller synchronised)
 static void row_admitted(tgx_ctx* c, int row, int seq) {
   row_req_push(c, row, ROWQ_STATE);       // a new sequence: what the slot counted while it rode along retired is gone (its settings stay)
-  c->row_fin[(size_t)row] = 0;
-  c->row_past[(size_t)row] = seq;
-  c->row_tok[(size_t)row] = 0;
-  c->row_idle[(size_t)row] = 0;
-  c->row_nologits[(size_t)row] = 0;
-  if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
+  c->row_host[(size_t)row].restart(seq, /*idle=*/false, /*fin=*/0);
+  c->row_host[(size_t)row].probs_ok = false;
+}
+
+// the rows an admission (src -1, prompt lengths lens) or a fork of row src (lens nullptr) fills: each in range and named once, the new ones growing the batch in order,
+// every one empty (retired, or holding no position); a fork's source a live, unfinished row that holds logits
+static int check_target_rows(tgx_ctx* c, int n, const int32_t* rows, const int32_t* lens, int src) {
+  const tgx_model_desc& d = c->d;
+  std::vector<char> named((size_t)d.max_batch, 0);
+  int n_new = 0;
+  for (int i = 0; i < n; i++) {
+    const int row = rows[i];
+    if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+    if (row == src) return set_err(c, TGX_ERR_INVALID, "row %d is the source of the fork", row);
+    if (named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    named[(size_t)row] = 1;
+    n_new += row >= c->batch;
+  }
+  if (src >= 0) {
+    const RowHost& s = c->row_host[(size_t)src];
+    if (src >= c->batch || s.idle || s.fin || s.past < 1) return set_err(c, TGX_ERR_STATE, "source row %d is not a live, unfinished row of the batch", src);
+    if (s.nologits) return set_err(c, TGX_ERR_STATE, "source row %d was truncated and holds no logits: tgx_extend_row it first", src);
+  }
+  for (int row = c->batch; row < c->batch + n_new; row++)
+    if (row >= d.max_batch || !named[(size_t)row])
+      return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
+  for (int i = 0; i < n; i++) {
+    if (lens && (lens[i] < 1 || lens[i] > d.max_ctx))
+      return set_err(c, lens[i] < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "prompt %d: seq %d out of range (context size %d)", i, lens[i], d.max_ctx);
+    const RowHost& r = c->row_host[(size_t)rows[i]];
+    if (!r.idle && r.past != 0) return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", rows[i], (long long)r.past, r.fin ? " (finished)" : "");
+  }
+  return TGX_OK;
 }
 
 // ---- admission (include/tgx.h tgx_forward_row, tgx_forward_rows): n prompts, back to back in ids, into the empty rows rows[], each from position 0 whatever the other
@@ -1145,42 +1123,22 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
   const tgx_model_desc& d = c->d;
   if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
   // ---- every check before anything changes
-  std::vector<char> named((size_t)d.max_batch, 0);
-  int n_new = 0;
-  for (int i = 0; i < n; i++) {
-    const int row = rows[i];
-    if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
-    if (named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
-    named[(size_t)row] = 1;
-    n_new += row >= c->batch;
-  }
-  for (int row = c->batch; row < c->batch + n_new; row++)
-    if (row >= d.max_batch || !named[(size_t)row])
-      return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
+  if (int rc = check_target_rows(c, n, rows, lens, /*src=*/-1)) return rc;
   long long total = 0;
   int longest = 0;
-  for (int i = 0; i < n; i++) {
-    const int seq = lens[i];
-    if (seq < 1 || seq > d.max_ctx) return set_err(c, seq < 1 ? TGX_ERR_INVALID : TGX_ERR_CONTEXT, "prompt %d: seq %d out of range (context size %d)", i, seq, d.max_ctx);
-    const int row = rows[i];
-    if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
-      return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
-    total += seq;
-    longest = std::max(longest, seq);
-  }
+  for (int i = 0; i < n; i++) { total += lens[i]; longest = std::max(longest, (int)lens[i]); }
   for (long long i = 0; i < total; i++)
     if (ids[i] < 0 || ids[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
   if (c->kv_paged) {
     // the ragged prompt attention copies a row's block table into LDS (<= 1024 entries)
-    if (may_join && c->kv_tbl_stride > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_forward_rows on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
+    if (may_join && c->kv.tbl_stride() > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_forward_rows on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
     // all or nothing: the blocks of the whole call against the free list plus the blocks the target rows give back
     long long need = 0;
     for (int i = 0; i < n; i++) need += (lens[i] + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK;
-    long long have = (long long)c->kv_free.size();
-    for (int i = 0; i < n; i++) have += kv_blocks_given_back(c, rows[i]);      // (a block a forked sibling still maps does not come back)
+    const long long have = c->kv.available_for(rows, n);      // (a block a forked sibling still maps does not come back)
     if (need > have)
       return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld blocks of %d tokens, %lld free or held by its rows of %d (option kv.budget_tokens = %d)", need,
-                     tgx::KV_BLOCK, have, c->kv_nblocks - 1, c->kv_budget_tokens);
+                     tgx::KV_BLOCK, have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
   }
   HIP_OK(c, hipSetDevice(c->device));
   if (c->kv_paged) {
@@ -1240,7 +1198,7 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
     HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
   }
   for (int i = 0; i < n; i++)      // retired rows that rode along since their reset: position word back to 0
-    if (c->row_past[(size_t)rows[i]] != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)rows[i]].pos, 0, 4, c->stream)); c->row_past[(size_t)rows[i]] = 0; }
+    if (c->row_host[(size_t)rows[i]].past != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)rows[i]].pos, 0, 4, c->stream)); c->row_host[(size_t)rows[i]].past = 0; }
   std::vector<int> joint;             // prompts that went through a ragged pass: their lm_head comes below, four rows per pass over the weights
   for (int g = 0; g < n_groups; g++) {
     const RaggedPass& p = passes[(size_t)g];
@@ -1298,47 +1256,34 @@ int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids,
   return admit_rows(c, n, rows, ids, lens, /*may_join=*/true);
 }
 
-// ---- tgx_fork_row (include/tgx.h): dst_rows become copies of the live row src.  Paged cache: src's full blocks by reference (kv_share_blocks), one fresh block per
+// ---- tgx_fork_row (include/tgx.h): dst_rows become copies of the live row src.  Paged cache: src's full blocks by reference (KvPool::share), one fresh block per
 // destination for the partial tail; slab cache: the prefix [0, past) of every (layer, kv head).  ONE kv_fork_kernel launch carries what has to be copied for all layers,
 // both caches and all destinations, and the per-row state (hidden row, logits, argmax partials, position and token words) rides in the same launch.  Every check comes
 // before anything changes; the launch sequence ends in finish_pass like an admission.
 static void launch_kv_fork(tgx_ctx* c, int src, int n, const int32_t* dst_rows, const int* dst_blk, int src_blk) {
   const tgx_model_desc& d = c->d;
-  const long long past = c->row_past[(size_t)src];
-  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz;
-  const bool v16 = tok_bytes % 16 == 0;
-  const long long n_tok = c->kv_paged ? past % tgx::KV_BLOCK : past;
-  for (int i0 = 0; i0 < n; i0 += tgx::KV_FORK_MAX_DST) {
-    tgx::KvForkArgs a{};
-    a.k = c->slab_k; a.v = c->slab_v;
-    a.kv_heads = d.kv_heads; a.n_spans = d.layers * d.kv_heads;
-    if (c->kv_paged) {
-      a.head_stride = tgx::KV_BLOCK * tok_bytes; a.id_stride = d.kv_heads * a.head_stride; a.layer_stride = c->kv_nblocks * a.id_stride;
-    } else {
-      a.head_stride = d.max_ctx * tok_bytes; a.layer_stride = d.kv_heads * a.head_stride; a.id_stride = (long long)c->kv_row_elems * (long long)c->esz;
-    }
-    a.span_vecs = n_tok * tok_bytes / (v16 ? 16 : 4);
-    a.n_dst = std::min(n - i0, (int)tgx::KV_FORK_MAX_DST);
-    a.src_row = src; a.src_id = c->kv_paged ? src_blk : src;
-    for (int k = 0; k < a.n_dst; k++) { a.dst_row[k] = dst_rows[i0 + k]; a.dst_id[k] = c->kv_paged ? dst_blk[i0 + k] : dst_rows[i0 + k]; }
-    // the grid from the bytes to move.  x: workgroups inside a span, one per KV_FORK_THREADS * KV_FORK_UNROLL vectors; y: grid rows that walk the 2 * n_spans spans, as
-    // many as keep the launch within eight workgroups per CU for a slab prefix (the chip filled, the rest in the rows' loops) and within 64 workgroups for a paged
-    // tail (at most 127 tokens per span: x = 1 at every released head_dim)
-    const long long per_wg = tgx::KV_FORK_THREADS * tgx::KV_FORK_UNROLL, cap = c->kv_paged ? 64 : 8ll * c->num_cus;
-    const int gx = (int)std::max<long long>(1, std::min<long long>((a.span_vecs + per_wg - 1) / per_wg, cap));
-    a.kv_rows = a.span_vecs ? (int)std::max<long long>(1, std::min<long long>(2ll * a.n_spans, cap / gx)) : 0;
-    const size_t H = (size_t)d.hidden, V = (size_t)d.vocab, P = (size_t)c->lm_grid;
-    a.seg[0] = {reinterpret_cast<unsigned char*>(c->slab_x), (long long)(H * 4), (int)H};
-    a.seg[1] = {reinterpret_cast<unsigned char*>(c->slab_logits), (long long)(V * 4), (int)V};
-    a.seg[2] = {reinterpret_cast<unsigned char*>(c->slab_part_val), (long long)(P * 4), (int)P};
-    a.seg[3] = {reinterpret_cast<unsigned char*>(c->slab_part_idx), (long long)(P * 4), (int)P};
-    a.seg[4] = {reinterpret_cast<unsigned char*>(c->slab_pos), 4, 1};
-    a.seg[5] = {reinterpret_cast<unsigned char*>(c->slab_tok), 4, 1};
-    const int st_rows = ((int)std::min<size_t>(64, (V + 1023) / 1024) + gx - 1) / gx;      // the state part: up to 64 workgroups, a dword per thread and round
-    const dim3 grid((unsigned)gx, (unsigned)(a.kv_rows + st_rows)), block(tgx::KV_FORK_THREADS);
-    if (v16) hipLaunchKernelGGL(tgx::kv_fork_kernel<tgx::u32x4>, grid, block, 0, c->stream, a);
-    else hipLaunchKernelGGL(tgx::kv_fork_kernel<unsigned int>, grid, block, 0, c->stream, a);
-  }
+  const long long past = c->row_host[(size_t)src].past;
+  for (int i0 = 0; i0 < n; i0 += tgx::KV_FORK_MAX_DST)
+    launch_kv_copy(c, c->kv_paged ? past % tgx::KV_BLOCK : past, [&](tgx::KvForkArgs& a) {
+      a.n_dst = std::min(n - i0, (int)tgx::KV_FORK_MAX_DST);
+      a.src_row = src; a.src_id = c->kv_paged ? src_blk : src;
+      for (int k = 0; k < a.n_dst; k++) { a.dst_row[k] = dst_rows[i0 + k]; a.dst_id[k] = c->kv_paged ? dst_blk[i0 + k] : dst_rows[i0 + k]; }
+      // the grid from the bytes to move.  x: workgroups inside a span, one per KV_FORK_THREADS * KV_FORK_UNROLL vectors; y: grid rows that walk the 2 * n_spans spans, as
+      // many as keep the launch within eight workgroups per CU for a slab prefix (the chip filled, the rest in the rows' loops) and within 64 workgroups for a paged
+      // tail (at most 127 tokens per span: x = 1 at every released head_dim)
+      const long long per_wg = tgx::KV_FORK_THREADS * tgx::KV_FORK_UNROLL, cap = c->kv_paged ? 64 : 8ll * c->num_cus;
+      const int gx = (int)std::max<long long>(1, std::min<long long>((a.span_vecs + per_wg - 1) / per_wg, cap));
+      a.kv_rows = a.span_vecs ? (int)std::max<long long>(1, std::min<long long>(2ll * a.n_spans, cap / gx)) : 0;
+      const size_t H = (size_t)d.hidden, V = (size_t)d.vocab, P = (size_t)c->lm_grid;
+      a.seg[0] = {reinterpret_cast<unsigned char*>(c->slab_x), (long long)(H * 4), (int)H};
+      a.seg[1] = {reinterpret_cast<unsigned char*>(c->slab_logits), (long long)(V * 4), (int)V};
+      a.seg[2] = {reinterpret_cast<unsigned char*>(c->slab_part_val), (long long)(P * 4), (int)P};
+      a.seg[3] = {reinterpret_cast<unsigned char*>(c->slab_part_idx), (long long)(P * 4), (int)P};
+      a.seg[4] = {reinterpret_cast<unsigned char*>(c->slab_pos), 4, 1};
+      a.seg[5] = {reinterpret_cast<unsigned char*>(c->slab_tok), 4, 1};
+      const int st_rows = ((int)std::min<size_t>(64, (V + 1023) / 1024) + gx - 1) / gx;      // the state part: up to 64 workgroups, a dword per thread and round
+      return dim3((unsigned)gx, (unsigned)(a.kv_rows + st_rows));
+    });
 }
 
 int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
@@ -1349,60 +1294,36 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
   // ---- every check before anything changes
   if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
   if (src < 0 || src >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "source row %d out of range [0,%d)", src, d.max_batch);
-  std::vector<char> named((size_t)d.max_batch, 0);
-  int n_new = 0;
-  for (int i = 0; i < n; i++) {
-    const int row = dst_rows[i];
-    if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
-    if (row == src) return set_err(c, TGX_ERR_INVALID, "row %d is the source of the fork", row);
-    if (named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
-    named[(size_t)row] = 1;
-    n_new += row >= c->batch;
-  }
-  if (src >= c->batch || c->row_idle[(size_t)src] || c->row_fin[(size_t)src] || c->row_past[(size_t)src] < 1)
-    return set_err(c, TGX_ERR_STATE, "source row %d is not a live, unfinished row of the batch", src);
-  if (c->row_nologits[(size_t)src]) return set_err(c, TGX_ERR_STATE, "source row %d was truncated and holds no logits: tgx_extend_row it first", src);
-  for (int row = c->batch; row < c->batch + n_new; row++)
-    if (row >= d.max_batch || !named[(size_t)row])
-      return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
-  for (int i = 0; i < n; i++) {
-    const int row = dst_rows[i];
-    if (!c->row_idle[(size_t)row] && c->row_past[(size_t)row] != 0)
-      return set_err(c, TGX_ERR_STATE, "row %d holds %lld positions%s: tgx_reset_row first", row, (long long)c->row_past[(size_t)row], c->row_fin[(size_t)row] ? " (finished)" : "");
-  }
+  if (int rc = check_target_rows(c, n, dst_rows, /*lens=*/nullptr, src)) return rc;
   if (((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_fork_row: a cache row of %d bytes", (int)(d.head_dim * c->esz));
-  const long long past = c->row_past[(size_t)src];
+  const long long past = c->row_host[(size_t)src].past;
   const int n_full = (int)(past / tgx::KV_BLOCK), tail = (int)(past % tgx::KV_BLOCK);
   if (c->kv_paged) {
     // all or nothing: one fresh block per destination for the partial tail, against the free list plus what the destination rows give back
-    long long need = tail ? n : 0, have = (long long)c->kv_free.size();
-    for (int i = 0; i < n; i++) have += kv_blocks_given_back(c, dst_rows[i]);
+    const long long need = tail ? n : 0, have = c->kv.available_for(dst_rows, n);
     if (need > have)
       return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the fork needs %lld blocks of %d tokens for the rows' tails, %lld free or held by its rows of %d (option kv.budget_tokens = %d)",
-                     need, tgx::KV_BLOCK, have, c->kv_nblocks - 1, c->kv_budget_tokens);
+                     need, tgx::KV_BLOCK, have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
   }
   HIP_OK(c, hipSetDevice(c->device));
   std::vector<int> dst_blk((size_t)n, 0);
   int src_blk = 0;
   if (c->kv_paged) {
     for (int i = 0; i < n; i++) kv_release_row(c, dst_rows[i]);
-    std::vector<std::pair<int, int>> ch;      // the table entries of all destinations in ONE push
+    KvPool::Changes ch;      // the table entries of all destinations in ONE push
     for (int i = 0; i < n; i++) {
-      kv_share_blocks(c, src, dst_rows[i], n_full, ch);
-      if (!tail) continue;
-      dst_blk[(size_t)i] = kv_take_block(c);            // cannot run dry: counted above
-      ch.emplace_back(dst_rows[i] * c->kv_tbl_stride + n_full, dst_blk[(size_t)i]);
-      c->kv_row_nblk[(size_t)dst_rows[i]] = n_full + 1;
+      c->kv.share(src, dst_rows[i], n_full, past, ch);
+      if (tail) dst_blk[(size_t)i] = c->kv.fork_tail(dst_rows[i], ch);            // cannot run dry: counted above
     }
     kv_tbl_push(c, ch);
-    if (tail) src_blk = c->kv_tbl_host[(size_t)src * c->kv_tbl_stride + n_full];
+    if (tail) src_blk = c->kv.block_at(src, n_full);
   }
   launch_kv_fork(c, src, n, dst_rows, dst_blk.data(), src_blk);
   if (int rc = finish_pass(c)) return rc;
   for (int i = 0; i < n; i++) {
     c->batch = std::max(c->batch, dst_rows[i] + 1);
     row_admitted(c, dst_rows[i], (int)past);
-    c->row_tok[(size_t)dst_rows[i]] = c->row_tok[(size_t)src];      // the token word travelled with the copy
+    c->row_host[(size_t)dst_rows[i]].tok = c->row_host[(size_t)src].tok;      // the token word travelled with the copy
   }
   refresh_longest(c);
   HIP_OK(c, hipGetLastError());
@@ -1418,20 +1339,20 @@ int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   const tgx_model_desc& d = c->d;
   if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
   if (seq < 1) return set_err(c, TGX_ERR_INVALID, "seq %d < 1", seq);
-  if (row >= c->batch || c->row_idle[(size_t)row] || c->row_past[(size_t)row] < 1)
+  if (row >= c->batch || c->row_host[(size_t)row].idle || c->row_host[(size_t)row].past < 1)
     return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to extend: use tgx_forward_row", row);
-  const long long past = c->row_past[(size_t)row];
+  const long long past = c->row_host[(size_t)row].past;
   if (past + seq > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, seq, d.max_ctx);
   for (int i = 0; i < seq; i++)
     if (ids[i] < 0 || ids[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
   if (c->kv_paged) {
     const PrefillRoute rt = prefill_route(c, seq, seq);
-    if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv_tbl_stride > 1024)      // the prompt attention copies the row's block table into LDS (<= 1024 entries)
-      return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_extend_row on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv_tbl_stride, 1024 * tgx::KV_BLOCK);
-    const long long need = (past + seq + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK - c->kv_row_nblk[(size_t)row];
-    if (need > (long long)c->kv_free.size())
-      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %zu free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
-                     c->kv_free.size(), c->kv_nblocks - 1, c->kv_budget_tokens);
+    if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv.tbl_stride() > 1024)      // the prompt attention copies the row's block table into LDS (<= 1024 entries)
+      return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_extend_row on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+    const long long need = c->kv.blocks_for(past + seq) - c->kv.row_blocks(row), have = c->kv.available_for(nullptr, 0);
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
+                     have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
     // (the block the first new position falls into is the row's own: a block forked siblings map as well is full, and tgx_truncate_row copies before it leaves a row inside one)
   }
   HIP_OK(c, hipSetDevice(c->device));
@@ -1450,19 +1371,11 @@ int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
 // paged KV: rows [0, n_tok) of every (layer, kv head) of both caches from block src_blk into block dst_blk — the cache part of the fork's copy launch alone
 // (kernels/kv_fork.h: a grid without the state rows behind the cache part's)
 static void launch_kv_tail_copy(tgx_ctx* c, int src_blk, int dst_blk, int n_tok) {
-  const tgx_model_desc& d = c->d;
-  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz;
-  const bool v16 = tok_bytes % 16 == 0;
-  tgx::KvForkArgs a{};
-  a.k = c->slab_k; a.v = c->slab_v;
-  a.kv_heads = d.kv_heads; a.n_spans = d.layers * d.kv_heads;
-  a.head_stride = tgx::KV_BLOCK * tok_bytes; a.id_stride = d.kv_heads * a.head_stride; a.layer_stride = c->kv_nblocks * a.id_stride;
-  a.span_vecs = n_tok * tok_bytes / (v16 ? 16 : 4);
-  a.n_dst = 1; a.src_id = src_blk; a.dst_id[0] = dst_blk;
-  a.kv_rows = std::min(2 * a.n_spans, 64);
-  const dim3 grid(1, (unsigned)a.kv_rows), block(tgx::KV_FORK_THREADS);      // (at most 127 tokens per span: one workgroup covers it at every released head_dim)
-  if (v16) hipLaunchKernelGGL(tgx::kv_fork_kernel<tgx::u32x4>, grid, block, 0, c->stream, a);
-  else hipLaunchKernelGGL(tgx::kv_fork_kernel<unsigned int>, grid, block, 0, c->stream, a);
+  launch_kv_copy(c, n_tok, [&](tgx::KvForkArgs& a) {
+    a.n_dst = 1; a.src_id = src_blk; a.dst_id[0] = dst_blk;
+    a.kv_rows = std::min(2 * a.n_spans, 64);
+    return dim3(1, (unsigned)a.kv_rows);      // (at most 127 tokens per span: one workgroup covers it at every released head_dim)
+  });
 }
 
 int tgx_truncate_row(tgx_ctx* c, int row, int64_t new_len) {
@@ -1471,39 +1384,35 @@ int tgx_truncate_row(tgx_ctx* c, int row, int64_t new_len) {
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
   if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
-  if (row >= c->batch || c->row_idle[(size_t)row] || c->row_past[(size_t)row] < 1) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to truncate", row);
-  const long long past = c->row_past[(size_t)row];
+  if (row >= c->batch || c->row_host[(size_t)row].idle || c->row_host[(size_t)row].past < 1) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to truncate", row);
+  const long long past = c->row_host[(size_t)row].past;
   if (new_len < 1) return set_err(c, TGX_ERR_INVALID, "new_len %lld < 1: tgx_reset_row empties a row", (long long)new_len);
   if (new_len > past) return set_err(c, TGX_ERR_INVALID, "new_len %lld beyond the %lld positions row %d holds", (long long)new_len, past, row);
   // nothing to roll back and the logits in the slot are those of the last position held: the row stays as it is
-  if (new_len == past && !c->row_fin[(size_t)row] && !c->row_nologits[(size_t)row]) return TGX_OK;
+  if (new_len == past && !c->row_host[(size_t)row].fin && !c->row_host[(size_t)row].nologits) return TGX_OK;
   const int keep = (int)((new_len + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK), tail = (int)(new_len % tgx::KV_BLOCK);
-  int shared_blk = 0;      // the block that holds the new tail, where forked siblings map it as well: the next append would write into it
-  if (c->kv_paged && tail) {
-    const int blk = c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + keep - 1];
-    if (c->kv_ref[(size_t)blk] > 1) shared_blk = blk;
-  }
-  if (shared_blk && c->kv_free.empty())
+  // the block that holds the new tail, where forked siblings map it as well: the next append would write into it
+  const int shared_blk = c->kv_paged && tail && c->kv.shared(row, keep - 1) ? c->kv.block_at(row, keep - 1) : 0;
+  if (shared_blk && !c->kv.free_blocks())
     return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: truncating row %d to %lld leaves it inside a block shared with %d forked row(s) and no block is free for its copy (option kv.budget_tokens = %d)",
-                   row, (long long)new_len, c->kv_ref[(size_t)shared_blk] - 1, c->kv_budget_tokens);
+                   row, (long long)new_len, c->kv.sharers(shared_blk) - 1, c->kv_budget_tokens);
   if (shared_blk && ((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_truncate_row: a cache row of %d bytes", (int)(d.head_dim * c->esz));
   // ---- nothing above changed anything: "a refused call changes nothing" is about those checks.  From here on the host bookkeeping (blocks, table) moves ahead of the
   // launches; should one of them not issue, launches_ok poisons the context — the row's lengths then stay as they were, and only tgx_reset_cache follows
   HIP_OK(c, hipSetDevice(c->device));
   if (shared_blk) {        // copy on write, before any append can happen: rows [0, tail) into a fresh block, the table entry swapped, this row's reference dropped
-    const int fresh = kv_take_block(c);
+    KvPool::Changes ch;
+    const int fresh = c->kv.unshare_tail(row, keep - 1, ch).second;      // cannot run dry: checked above
     launch_kv_tail_copy(c, shared_blk, fresh, tail);
-    kv_tbl_push(c, {{row * c->kv_tbl_stride + keep - 1, fresh}});
-    kv_drop_block(c, shared_blk);
+    kv_tbl_push(c, ch);
   }
   kv_trim_row(c, row, new_len);                                         // the blocks beyond the new length (a shared one only loses this row's reference)
   if (new_len != past) launch_add_pos(c, c->rows[(size_t)row].pos, (int)(new_len - past));      // stream-ordered behind the steps already enqueued
-  if (c->row_fin[(size_t)row]) { row_req_push(c, row, ROWQ_STATE); c->row_fin[(size_t)row] = 0; }
+  if (c->row_host[(size_t)row].fin) { row_req_push(c, row, ROWQ_STATE); c->row_host[(size_t)row].fin = 0; }
   if (int rc = launches_ok(c)) return rc;
-  c->row_past[(size_t)row] = new_len;
-  c->row_tok[(size_t)row] = 0;
-  c->row_nologits[(size_t)row] = 1;                                     // the logits of position new_len - 1 no longer exist
-  if ((size_t)row < c->row_probs_ok.size()) c->row_probs_ok[(size_t)row] = 0;
+  RowHost& r = c->row_host[(size_t)row];
+  r.past = new_len;
+  r.tok = r.probs_ok = false; r.nologits = true;                        // the logits of position new_len - 1 no longer exist
   refresh_longest(c);
   return TGX_OK;
 }
@@ -1512,7 +1421,7 @@ int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t see
   if (!c || !cfg) return TGX_ERR_INVALID;
   if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "no logits to sample from");
   if (row < 0 || row >= c->batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->batch);
-  if (c->row_nologits[(size_t)row]) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
+  if (c->row_host[(size_t)row].nologits) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, row, 1, *cfg);
@@ -1523,7 +1432,7 @@ int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t see
   HIP_OK(c, hipMemcpy(&t, c->rows[(size_t)row].tok, 4, hipMemcpyDeviceToHost));
   if (out_id) *out_id = t;
   if (row == 0) c->last_sampled0 = t;
-  c->row_tok[(size_t)row] = 1;
+  c->row_host[(size_t)row].tok = 1;
   refresh_longest(c);
   return TGX_OK;
 }
@@ -1562,18 +1471,19 @@ int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new,
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "decode before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   int running = 0;
-  for (int b = 0; b < c->batch; b++) running += !c->row_idle[(size_t)b] && !c->row_fin[(size_t)b];
+  for (int b = 0; b < c->batch; b++) running += !c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin;
   if (!running) return set_err(c, TGX_ERR_STATE, "tgx_decode_rows: no live row is unfinished (tgx_reset_row / tgx_forward_row a row first)");
   REFUSE_NOLOGITS(c, "tgx_decode_rows");
   if (!c->have_token) return set_err(c, TGX_ERR_STATE, "decode needs a current token: call tgx_sample / tgx_sample_row after the forward");
   if (c->past + n_steps > c->d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: %lld + %d > %d", (long long)c->past, n_steps, c->d.max_ctx);
   for (int b = 0; b < c->batch; b++)      // a finished row rides at its own length: one that holds the whole context has no row left to ride on
-    if (c->row_fin[(size_t)b] && !c->row_idle[(size_t)b] && c->row_past[(size_t)b] >= c->d.max_ctx)
+    if (c->row_host[(size_t)b].fin && !c->row_host[(size_t)b].idle && c->row_host[(size_t)b].past >= c->d.max_ctx)
       return set_err(c, TGX_ERR_CONTEXT, "row %d finished at the context size %d: tgx_reset_row it first", b, c->d.max_ctx);
   if (n_steps > c->log_cap) return set_err(c, TGX_ERR_INVALID, "n_steps exceeds the token log capacity %d", c->log_cap);
   HIP_OK(c, hipSetDevice(c->device));
   const size_t B = (size_t)c->batch;
-  const std::vector<int64_t> before(c->row_past.begin(), c->row_past.begin() + (long)B);
+  std::vector<int64_t> before(B);
+  for (size_t b = 0; b < B; b++) before[b] = c->row_host[b].past;
   const int64_t start = c->steps_issued;
   int rc = TGX_OK;
   if (n_steps > 0) {
@@ -1591,15 +1501,15 @@ int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new,
   HIP_OK(c, hipMemcpyAsync(req.data(), c->row_req, B * sizeof(tgx::RowReq), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   for (size_t b = 0; b < B; b++) {
-    const bool idle = c->row_idle[b];
-    c->row_past[b] = pos[b];                              // a row advanced once per token it produced (retired rows: wherever their ride took them)
-    c->row_fin[b] = idle ? 0 : (char)req[b].finished;
+    const bool idle = c->row_host[b].idle;
+    c->row_host[b].past = pos[b];                              // a row advanced once per token it produced (retired rows: wherever their ride took them)
+    c->row_host[b].fin = idle ? 0 : (char)req[b].finished;
     if (out_new) out_new[b] = idle ? 0 : (int32_t)(pos[b] - before[b]);
     if (out_finish) out_finish[b] = idle ? 0 : req[b].finished;
-    if (c->row_fin[b]) kv_trim_row(c, (int)b, c->row_past[b]);
+    if (c->row_host[b].fin) kv_trim_row(c, (int)b, c->row_host[b].past);
   }
   if (out_ids)
-    for (size_t i = 0; i < ids.size(); i++) out_ids[i] = c->row_idle[i % B] ? -1 : ids[i];
+    for (size_t i = 0; i < ids.size(); i++) out_ids[i] = c->row_host[i % B].idle ? -1 : ids[i];
   if (n_steps > 0) c->last_sampled0 = ids[(size_t)(n_steps - 1) * B];
   refresh_longest(c);
   return TGX_OK;
@@ -1626,12 +1536,12 @@ int tgx_read_kv(tgx_ctx* c, int row, int layer, float* k_out, float* v_out) {
     float* out = which ? v_out : k_out;
     if (!out) continue;
     const ebyte* base = (which ? c->rows[(size_t)row].vcache : c->rows[(size_t)row].kcache) + (size_t)layer * d.kv_heads * per_head * c->esz;
-    if (c->kv_paged) base = (which ? c->slab_v : c->slab_k) + (size_t)layer * c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd * c->esz;
+    if (c->kv_paged) base = (which ? c->slab_v : c->slab_k) + (size_t)layer * c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * hd * c->esz;
     for (int h = 0; h < d.kv_heads; h++) {
       if (c->kv_paged) {      // the row's tokens block by block through its table
         for (size_t t0 = 0; t0 < T; t0 += tgx::KV_BLOCK) {
           const size_t n = std::min<size_t>(tgx::KV_BLOCK, T - t0);
-          const size_t blk = (size_t)c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + t0 / tgx::KV_BLOCK];
+          const size_t blk = (size_t)c->kv.block_at(row, (int)(t0 / tgx::KV_BLOCK));
           HIP_OK(c, hipMemcpy(tmp.data() + t0 * hd * c->esz, base + ((blk * d.kv_heads + h) * tgx::KV_BLOCK) * hd * c->esz, n * hd * c->esz, hipMemcpyDeviceToHost));
         }
       } else
@@ -1653,9 +1563,9 @@ int tgx_write_kv(tgx_ctx* c, int row, int layer, const float* k_in, const float*
   if (!c || !c->finalized || row < 0 || row >= c->d.max_batch || layer < 0 || layer >= c->d.layers || n_rows < 0 || n_rows > tgx_past_length_row(c, row)) return c ? set_err(c, TGX_ERR_INVALID, "write_kv: row / layer / n_rows out of range") : TGX_ERR_INVALID;
   if (c->kv_paged)      // a block forked siblings map as well (tgx_fork_row) is not written through: the siblings would change with it
     for (int64_t t0 = 0; t0 < n_rows; t0 += tgx::KV_BLOCK) {
-      const int blk = c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + (size_t)(t0 / tgx::KV_BLOCK)];
-      if (c->kv_ref[(size_t)blk] > 1)
-        return set_err(c, TGX_ERR_STATE, "write_kv: positions %lld.. of row %d lie in a block shared with %d forked row(s)", (long long)t0, row, c->kv_ref[(size_t)blk] - 1);
+      const int idx = (int)(t0 / tgx::KV_BLOCK);
+      if (c->kv.shared(row, idx))
+        return set_err(c, TGX_ERR_STATE, "write_kv: positions %lld.. of row %d lie in a block shared with %d forked row(s)", (long long)t0, row, c->kv.sharers(c->kv.block_at(row, idx)) - 1);
     }
   HIP_OK(c, hipSetDevice(c->device));
   HIP_OK(c, hipStreamSynchronize(c->stream));
@@ -1666,7 +1576,7 @@ int tgx_write_kv(tgx_ctx* c, int row, int layer, const float* k_in, const float*
     const float* in = which ? v_in : k_in;
     if (!in || !T) continue;
     ebyte* base = (which ? c->rows[(size_t)row].vcache : c->rows[(size_t)row].kcache) + (size_t)layer * d.kv_heads * per_head * c->esz;
-    if (c->kv_paged) base = (which ? c->slab_v : c->slab_k) + (size_t)layer * c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd * c->esz;
+    if (c->kv_paged) base = (which ? c->slab_v : c->slab_k) + (size_t)layer * c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * hd * c->esz;
     for (int h = 0; h < d.kv_heads; h++) {
       for (size_t t = 0; t < T; t++)
         for (size_t k = 0; k < hd; k++) {   // BSHD view in, head-major cache out; one round-to-nearest-even into the storage dtype
@@ -1678,7 +1588,7 @@ int tgx_write_kv(tgx_ctx* c, int row, int layer, const float* k_in, const float*
       if (c->kv_paged) {
         for (size_t t0 = 0; t0 < T; t0 += tgx::KV_BLOCK) {
           const size_t n = std::min<size_t>(tgx::KV_BLOCK, T - t0);
-          const size_t blk = (size_t)c->kv_tbl_host[(size_t)row * c->kv_tbl_stride + t0 / tgx::KV_BLOCK];
+          const size_t blk = (size_t)c->kv.block_at(row, (int)(t0 / tgx::KV_BLOCK));
           HIP_OK(c, hipMemcpy(base + ((blk * d.kv_heads + h) * tgx::KV_BLOCK) * hd * c->esz, tmp.data() + t0 * hd * c->esz, n * hd * c->esz, hipMemcpyHostToDevice));
         }
       } else
@@ -1725,7 +1635,7 @@ int tgx_read_probs(tgx_ctx* c, float* out) {
   // a sampled step leaves its logits, thresholds and normalisers on the device, not the vector: evaluate it now (rows whose last step was greedy read as zeros)
   const size_t V = (size_t)c->d.vocab;
   for (int b = 0; b < c->batch; b++) {
-    if (c->row_probs_ok[(size_t)b]) launch_probs(c, b, c->row_probs_cfg[(size_t)b]);
+    if (c->row_host[(size_t)b].probs_ok) launch_probs(c, b, c->row_host[(size_t)b].probs_cfg);
     else HIP_OK(c, hipMemsetAsync(c->rows[(size_t)b].probs, 0, V * 4, c->stream));
   }
   HIP_OK(c, hipGetLastError());
@@ -1751,7 +1661,7 @@ int tgx_set_logits(tgx_ctx* c, const float* logits, int batch) {
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->batch = batch;
   c->have_probs = false;
-  std::fill(c->row_probs_ok.begin(), c->row_probs_ok.end(), 0);
+  for (RowHost& r : c->row_host) r.probs_ok = false;
   c->have_logits = true;
   return TGX_OK;
 }
@@ -1769,7 +1679,7 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "weights.packed_matrices")) { *out_value = c->packed_matrices; return TGX_OK; }        // read-only, after tgx_finalize: matrices stored packed ...
   if (!strcmp(key, "weights.packed_fallbacks")) { *out_value = c->packed_fallbacks; return TGX_OK; }      // ... matrices that stayed plain because a row's escape record overflowed ...
   if (!strcmp(key, "weights.packed_max_row_esc")) { *out_value = c->packed_max_row_esc; return TGX_OK; }  // ... and the most escapes seen in one row
-  if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv_free.size() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
+  if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv.free_blocks() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
   return TGX_ERR_INVALID;
 }
 

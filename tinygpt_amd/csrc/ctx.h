@@ -1,6 +1,7 @@
 // ctx.h — the context of the MI355X shim (include/tgx.h) and the host-side launch interface shared by its translation units:
 //   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows),
-//                    paged-KV block assignment and tgx_fork_row with its copy launch (kernels/kv_fork.h)
+//                    the device side of paged-KV block assignment (table pushes) and tgx_fork_row with its copy launch (kernels/kv_fork.h)
+//   kv_pool.h        KvPool: the paged cache's block bookkeeping (free list, per-block row counts, the table's host mirror) — host-only, checked on a CPU
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
@@ -22,6 +23,7 @@
 
 #include "../../include/tgx.h"
 #include "kernels/common.h"
+#include "kv_pool.h"
 
 using tgx::bf16_t;
 typedef unsigned char ebyte;   // parameter / KV-cache storage in the compute dtype: offsets are elements * ctx.esz
@@ -70,6 +72,17 @@ struct RowState {       // independent KV/sequence state of one batch row
   long long* prompt = nullptr;
   ebyte *kcache = nullptr, *vcache = nullptr;   // [layers][kv_heads][max_ctx][hd] in the compute dtype; paged KV: the pools [layers][blocks][kv_heads][KV_BLOCK][hd], shared by the rows
   const int* tbl = nullptr;                     // paged KV: this row's block table on the device
+};
+
+struct RowHost {        // host state of one batch row
+  int64_t past = 0;     // mirror of the row's own device pos (tgx_reset_row / tgx_forward_row, include/tgx.h)
+  bool tok = false;     // the row has a current token (sampled after its last forward)
+  bool idle = false;    // the row was retired (tgx_reset_row) and not refilled: it rides in the steps, nothing waits for it, its output means nothing
+  bool nologits = false;   // the row was truncated (tgx_truncate_row) and not extended since: its slot's logits belong to a position it no longer holds, so nothing may sample, step or fork from it
+  char fin = 0;         // the finish reason of the last tgx_decode_rows readback (0 running, 1 stop id, 2 max_new) — a finished row keeps its length, rides along without advancing and counts for neither `past` nor the context check
+  bool probs_ok = false; tgx_sampler_cfg probs_cfg{};   // the row's last sampled step was a non-greedy one, and its sampler configuration (tgx_read_probs evaluates the vector on demand)
+  // the slot starts over at `len` positions: no current token, its logits its own; what its last sampled step left (probs_ok, probs_cfg) stays
+  void restart(int64_t len, bool idle_, char fin_) { past = len; tok = nologits = false; idle = idle_; fin = fin_; }
 };
 
 struct Tune {
@@ -136,15 +149,11 @@ struct tgx_ctx {
   int* ch_pos = nullptr;
 
   int64_t past = 0;       // host mirror of the device-resident pos: the LONGEST row of the batch (all rows, unless the per-row calls made them differ)
-  std::vector<int64_t> row_past;   // host mirror of each row's own pos (tgx_reset_row / tgx_forward_row, include/tgx.h)
-  std::vector<char> row_tok;       // the row has a current token (sampled after its last forward)
-  std::vector<char> row_idle;      // the row was retired (tgx_reset_row) and not refilled: it rides in the steps, nothing waits for it, its output means nothing
+  std::vector<RowHost> row_host;   // [max_batch]
   // tgx_decode_rows (include/tgx.h): per-row sampler settings and stop conditions.  row_req [max_batch] on the device (kernels/common.h RowReq), pushed by value
-  // in stream order; row_req_host mirrors the pushed fields.  row_fin: the finish reason of the last readback (0 running, 1 stop id, 2 max_new) — a finished row
-  // keeps its length, rides along without advancing and counts for neither `past` nor the context check
+  // in stream order; row_req_host mirrors the pushed fields
   tgx::RowReq* row_req = nullptr;
   std::vector<tgx::RowReq> row_req_host;
-  std::vector<char> row_fin;
   int row_union = -1;     // steps being issued / captured: -1 = the launch-wide cfg (tgx_decode), else the ROWU_* union of the rows' chains (tgx_decode_rows)
   int batch = 0;          // rows used by the last forward
   bool have_logits = false, have_token = false;
@@ -177,8 +186,6 @@ struct tgx_ctx {
   unsigned long long* samp_list_comp = nullptr;   // [max_batch][vocab] compacted threshold-bin entries of a filter (kernels/sampler.h): composite keys ...
   float* samp_list_v = nullptr;                   // ... and logit / T
   bool have_probs = false;
-  std::vector<tgx_sampler_cfg> row_probs_cfg;   // per row: the sampler configuration of its last sampled step (tgx_read_probs evaluates the vector on demand) ...
-  std::vector<char> row_probs_ok;               // ... and whether that step was a non-greedy one
   bool use_graph = true;
 
   Tune tune[TGX_KERNEL_COUNT];   // per kernel class: K-split and workgroups per CU
@@ -277,23 +284,16 @@ struct tgx_ctx {
   // template OPJ) — 4 launches per layer; the direct form then serves contexts up to attn_fused_max keys, with four wave-loads per softmax block up to attn_fused_nw4 keys and eight beyond (four waves per head either way); was: four / eight waves up to attn_fused_nw4
   int oproj_fused = 1, attn_fused_max = 640, attn_fused_nw4 = 384;
   // ---- paged KV (round 6; option kv.budget_tokens before tgx_finalize; include/tgx.h).  The caches become pools of KV_BLOCK-token blocks shared by the rows; a row's
-  // blocks are assigned on the host as its sequence grows (before the launch that writes them) and returned by tgx_reset_row / tgx_reset_cache.  Block 0 is scratch.
+  // blocks are assigned on the host as its sequence grows (before the launch that writes them) and returned by tgx_reset_row / tgx_reset_cache: `kv` (kv_pool.h)
   int kv_budget_tokens = 0;        // > 0: paged
   bool kv_paged = false;
-  int kv_nblocks = 0;              // physical blocks incl. the scratch block
-  int kv_tbl_stride = 0;           // table entries per row = ceil(max_ctx / KV_BLOCK)
-  int* kv_tbl = nullptr;           // device [max_batch][kv_tbl_stride]
-  std::vector<int> kv_tbl_host;    // its host mirror
-  std::vector<int> kv_free;        // free physical blocks
-  std::vector<int> kv_row_nblk;    // blocks assigned to each row
-  std::vector<int> kv_ref;         // per physical block: the rows that map it (tgx_fork_row shares a row's FULL blocks by reference; free at 0)
+  KvPool kv;                       // set up in tgx_finalize when paged: blocks, free list, the table's host mirror; kv.n_blocks() / kv.tbl_stride() size the pools and the table
+  int* kv_tbl = nullptr;           // device [max_batch][kv.tbl_stride()]
   long long* slab_acc = nullptr;   // [max_batch][hidden], resting at zero between layers
   // tgx_forward_rows: the call's buffer (the RaggedPass device tables, then the ids; one upload per call) and four staging rows for the lm_head of scattered target rows
   unsigned char* rg_buf = nullptr; size_t rg_bytes = 0;
   float *rg_x = nullptr, *rg_logits = nullptr, *rg_part_val = nullptr; int* rg_part_idx = nullptr;
-  // ---- tgx_extend_row / tgx_truncate_row (include/tgx.h).  row_nologits: the row was truncated and not extended since — its slot's logits belong to a position it no
-  // longer holds, so nothing may sample, step or fork from it.
-  std::vector<char> row_nologits;
+  // ---- tgx_extend_row / tgx_truncate_row (include/tgx.h)
   // option extend.attn_splits: the key-split attention of a continuation pass of <= 128 positions (kernels/attn_extend.h): -1 automatic, 0 never (the per-row prompt
   // attention with `past`), N >= 1 N splits (clamped to the key tiles).  Automatic: min(32, CUs / heads) splits once past + S exceeds extend_attn_min{64,128} (head_dim)
   // — the smallest measured context at which the split form wins by more than the spread of the measurement at every extension length (tools/admit_bench.py --extend,

@@ -214,9 +214,9 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
   RowState& r = rv[0];   // R consecutive row views with the slabs' row strides; kv_stride = 0 when the rows are positions of ONE sequence
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd;
   // bytes between a layer's caches (ebyte pointers): a row's slab [kv_heads][max_ctx][hd], or — paged KV — the layer's pool of KV_BLOCK-token blocks
-  const size_t kv_layer = (c->kv_paged ? (size_t)c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK : (size_t)d.kv_heads * d.max_ctx) * hd * c->esz;
+  const size_t kv_layer = (c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK : (size_t)d.kv_heads * d.max_ctx) * hd * c->esz;
   // paged: the rows share the pools (no row stride) and differ by their block tables; rows that are positions of ONE sequence (kv_stride 0) share one table
-  const long long kvs = c->kv_paged ? 0 : kv_stride, tbs = (c->kv_paged && kv_stride != 0) ? c->kv_tbl_stride : 0;
+  const long long kvs = c->kv_paged ? 0 : kv_stride, tbs = (c->kv_paged && kv_stride != 0) ? c->kv.tbl_stride() : 0;
   const LayerW& w = c->L[(size_t)l];
   switch (cls) {
     case TGX_KERNEL_QKV: {   // input_layernorm -> qkv_proj -> RoPE -> cache append   (DecoderLayer.h:40, Attention.h:94-106)

@@ -403,7 +403,7 @@ struct SampPickArgs {
 };
 
 // row r's view of the launch's finalize arguments
-__device__ __forceinline__ FinalizeArgs samp_row_fin(const SampPickArgs& pa, int r) {
+__device__ __forceinline__ FinalizeArgs samp_finalize_args(const SampPickArgs& pa, int r) {
   FinalizeArgs f = pa.fin;
   f.tok += r; f.pos += r; f.x += (size_t)r * pa.x_stride; f.row = pa.fin.row + r;
   if (f.req) f.req += r;
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
   const int role = ROWS ? samp_row_apply(a, row, MODE == 0 ? SST_KT : SST_PT) : (PICK ? 2 : 1);
   if (ROWS && !role) return;
   const bool pick = PICK && role == 2;
-  const FinalizeArgs fin = samp_row_fin(pa, row);
+  const FinalizeArgs fin = samp_finalize_args(pa, row);
   SampScratch* sc = a.sc + row;
   const unsigned long long* lc = a.list_comp + (size_t)row * a.V;
   const float* lv = a.list_v + (size_t)row * a.V;
@@ -737,7 +737,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_pick_kernel(const SampPickArgs p
   SampArgs a = pa.s;
   const int row = blockIdx.y, tid = threadIdx.x, nwg = pa.nwg;
   if (ROWS && !samp_row_apply(a, row, SST_PICK)) return;
-  const FinalizeArgs fin = samp_row_fin(pa, row);
+  const FinalizeArgs fin = samp_finalize_args(pa, row);
   SampScratch* sc = a.sc + row;
   SAMP_STAMP(sc, 4);
   double pw[4];

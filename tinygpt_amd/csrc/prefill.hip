@@ -485,7 +485,7 @@ void launch_embed_rows(tgx_ctx* c, const long long* ids, float* X, int M, int S)
 static void prefill_pass(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd;
-  const size_t kv_layer = c->kv_paged ? (size_t)c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
+  const size_t kv_layer = c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
   const int M = rg ? rg->M : NB * S;
   const size_t wout = (size_t)qd + 2 * kvd;
   // GPT-2 (ModelGPT2.h:23-208): wte + wpe rows, LayerNorm with bias ahead of both products, a bias on every Conv1D, c_fc -> gelu_new;

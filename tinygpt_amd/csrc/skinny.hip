@@ -233,8 +233,8 @@ static void launch_ksplit(tgx_ctx* c, int epi, const ebyte* W, float* C, int ldc
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd, V = d.vocab;
-  const size_t kv_layer = (c->kv_paged ? (size_t)c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK : (size_t)d.kv_heads * d.max_ctx) * hd * c->esz;      // paged KV: a layer's pool
-  const long long kvs = c->kv_paged ? 0 : (long long)c->kv_row_elems, tbs = c->kv_paged ? c->kv_tbl_stride : 0;
+  const size_t kv_layer = (c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK : (size_t)d.kv_heads * d.max_ctx) * hd * c->esz;      // paged KV: a layer's pool
+  const long long kvs = c->kv_paged ? 0 : (long long)c->kv_row_elems, tbs = c->kv_paged ? c->kv.tbl_stride() : 0;
   RowState& r = c->rows[(size_t)row0];
   const int nt_qkv = c->dt == tgx::DT_BF16 ? 3 : 2;
   float* ssq = c->ws_ssq;
@@ -348,7 +348,7 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
 void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd;
-  const size_t kv_layer = c->kv_paged ? (size_t)c->kv_nblocks * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
+  const size_t kv_layer = c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
   const int M = rg ? rg->M : NB * S, nq = qd + 2 * kvd;
   const int nt_qkv = c->dt == tgx::DT_BF16 ? 3 : 2;
   float* ssq = c->ws_ssq;
