@@ -30,6 +30,7 @@ extern "C" {
 /* (round 7, still 3: additive) per-row sampler settings and device-side stop — tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows. */
 /* (still 3: additive) tgx_forward_rows; tgx_fork_row — a live row copied into other rows, its full paged KV blocks shared by reference. */
 /* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
+/* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -297,6 +298,40 @@ TGX_API int tgx_extend_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
  * siblings, the next append would write into a shared block: the row takes one fresh block, rows [0, new_len % 128) of every layer and both caches are copied into
  * it in one launch, the table entry is swapped and the shared block loses this row's reference.  With no free block that is TGX_ERR_CONTEXT and nothing changes. */
 TGX_API int tgx_truncate_row(tgx_ctx* ctx, int row, int64_t new_len);
+
+/* ---- greedy speculative decoding: verifying a row's draft in one pass (additive to ABI 3) ---------------------------------------------------------------
+ * A decode step streams the weights once for one position; a pass over a few positions of ONE sequence streams them once as well (tgx_extend_row).  A caller that
+ * can guess the next tokens (a draft: prompt lookup, a small model) has the model check the guess in one pass.  `row` is a live, unfinished row that has a current
+ * token t0 (device resident; the host need not know it) and `past` positions in its cache.  The call runs ONE causal pass — tgx_extend_row's, with its routes and
+ * attention forms — over the inputs [t0, draft[0], .., draft[n_draft - 1]] at positions past .. past + n_draft, computes the logits of EVERY one of these
+ * n_draft + 1 positions and each position's greedy token g[i] (highest value, lowest index on a tie).  a = the number of leading i with g[i] == draft[i]; the
+ * row produces a + 1 tokens: draft[0 .. a - 1] followed by g[a].
+ *
+ *   Afterwards        the row stands exactly as after a + 1 greedy steps of tgx_decode_rows: length past + a + 1, current token g[a], the logits slot and argmax
+ *                     partials those of the position that produced g[a], the next embedding gathered (GPT-2: with wpe at the advanced position).  The result
+ *                     equals those steps up to the order of the fp32 sums — the contract between kernel paths.  Cache rows beyond the new length were written by
+ *                     the pass and are DEAD: nothing reads them, and the cache stays append-only from the new length.
+ *   Stop conditions   the row's own (tgx_set_row_stop): the produced tokens are counted against max_new and the stop set one by one, in order, on the device, and
+ *                     acceptance ends at the token that finishes the row.  out_finish is 0 / 1 / 2 as in tgx_decode_rows; out_n <= a + 1 tokens are returned in
+ *                     out_ids (the call's own read-back: the call returns when the pass has finished, like an admission); tgx_past_length_row grows by exactly
+ *                     out_n.  A finished row then behaves as after tgx_decode_rows.
+ *   Sampler           greedy only: a row whose settings (tgx_set_row_sampler) are not greedy is TGX_ERR_UNSUPPORTED.
+ *   Refused           null pointers, row outside [0, max_batch), n_draft outside [1, TGX_MAX_DRAFT], a draft id out of range: TGX_ERR_INVALID.  A retired, empty
+ *                     or finished row, a row without a current token (fresh from tgx_forward_row / tgx_extend_row), a truncated row that holds no logits, a
+ *                     poisoned context: TGX_ERR_STATE.  past + n_draft + 1 > max_ctx: TGX_ERR_CONTEXT.  Paged KV: the blocks for past + n_draft + 1 are counted
+ *                     against the free list before anything is assigned (TGX_ERR_CONTEXT); more than 1024 blocks per row: TGX_ERR_UNSUPPORTED as for tgx_extend_row.
+ *   ALL OR NOTHING    a refused call changes no row, moves no KV block, leaves kv.free_tokens as it was and does not poison the context.
+ *   Paged KV          blocks are assigned for the whole pass up front; afterwards the row's blocks beyond ceil(new length / 128) go back to the pool, so
+ *                     kv.free_tokens is what a row of the new length leaves.  The first new position falls into a block the row owns; shared (forked) blocks are
+ *                     never written.
+ *   Other rows        keep their state bit for bit and do not step.
+ *   Steps and tickets the call is no decode step: it is stream-ordered behind the steps already enqueued, writes neither the token log nor the host ring and moves
+ *                     no ticket, so tgx_step_async / tgx_fetch_token tickets and tgx_decode's ids stay exact; the produced ids come back in out_ids only.  On row 0
+ *                     the last produced token becomes ticket 0's token (as after tgx_sample).
+ *   tgx_read_probs    as after a greedy step: the row reads as zeros (and with no sampled row in the batch the call is TGX_ERR_STATE, as it always is).
+ *   Cost              one weight pass for the layers, and for lm_head one pass on the matrix-core route of 5-16 positions, ceil((n_draft + 1) / 4) otherwise. */
+#define TGX_MAX_DRAFT 15
+TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_draft, int64_t* out_ids /* [n_draft + 1] */, int32_t* out_n, int32_t* out_finish);
 
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);

@@ -93,6 +93,18 @@ def build_kv_pool_check(force: bool = False, verbose: bool = False):
     return target
 
 
+def build_spec_draft_check(force: bool = False, verbose: bool = False):
+    """tests/spec_draft_check.cpp (the CPU audit of host/spec_draft.h, its own main) under the address and undefined-behaviour sanitizers: tests/_build/spec_draft_check."""
+    src, target = os.path.join(HERE, "..", "tests", "spec_draft_check.cpp"), os.path.join(TEST_BUILD, "spec_draft_check")
+    os.makedirs(TEST_BUILD, exist_ok=True)
+    if force or _stale(target, [src, os.path.join(HOST, "spec_draft.h")]):
+        cmd = [CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-Wall", "-Wextra", src, "-o", target]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+    return target
+
+
 def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = False):
     """The C++ host engine (no HIP needed: it dlopen()s the device shim): libtgx_host.so + the tgx_cli binary.
 

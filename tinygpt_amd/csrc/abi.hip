@@ -542,14 +542,31 @@ static int launch_route(tgx_ctx* c, PrefillRoute rt, int M, int row0, int NB, in
   return TGX_OK;
 }
 
+// tgx_verify_row: the logits and argmax partials of ALL M positions of a one-row pass into the vf_* workspace.  The skinny route's final residual rows (ws_x) go
+// through the batched step's one-pass lm_head; every other route stages its hidden rows in vf_x (the matrix-core routes' ws_x here, prefill by steps chunk by chunk)
+// and runs the GEMV lm_head four rows per pass over the weights (a group of three rides as four: vf_x holds VERIFY_ROWS rows, the fourth's results are not read)
+static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M) {
+  const size_t H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
+  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, c->vf_logits, c->vf_part_val, c->vf_part_idx); return; }
+  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(c->vf_x, c->ws_x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, c->stream);
+  for (int m0 = 0; m0 < M;) {
+    const int rem = M - m0, R = rem >= 3 ? 4 : rem;
+    launch_lm_head_at(c, c->vf_x + m0 * H, c->vf_logits + m0 * V, c->vf_part_val + m0 * P, c->vf_part_idx + m0 * P, R);
+    m0 += R;
+  }
+}
+
 // One pass of nb rows [row0, row0 + nb) over positions past .. past + seq - 1 of each (their ids are in rows[].prompt, their blocks assigned); leaves every row's
 // logits and advances its position word.  `past` is an argument: tgx_forward passes the batch's pastLength, an admission 0 whatever the other rows hold.
-static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past) {
+// verify (tgx_verify_row, nb == 1): the same pass, but the logits of EVERY position land in the vf_* workspace (launch_lm_head_all) and neither the row's logits
+// slot nor its position word moves — the accept launch behind the pass writes both
+static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool verify = false) {
   const PrefillRoute rt = prefill_route(c, seq, nb * seq);
   if (rt != ROUTE_STEPS) {
     // batched prefill on the matrix cores; logits for the last position only (== forward + narrow, GPTEngine.cpp:96-97)
     const int rc = launch_route(c, rt, nb * seq, row0, nb, seq, past);
     if (rc) return rc;
+    if (verify) { launch_lm_head_all(c, rt, seq); return TGX_OK; }
     for (int b = row0; b < row0 + nb;) {
       const int rem = row0 + nb - b, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
       launch_lm_head(c, b, R);
@@ -569,6 +586,11 @@ static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past) {
       for (int k = 0; k < R; k++) { c->chunk[k].kcache = r.kcache; c->chunk[k].vcache = r.vcache; c->chunk[k].tbl = r.tbl; }
       launch_layers(c, c->chunk, R, 0);
       s0 += R;
+      if (verify) {                                      // every position's hidden state feeds lm_head
+        (void)hipMemcpyAsync(c->vf_x + (size_t)(s0 - R) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
+        if (s0 == seq) launch_lm_head_all(c, rt, seq);
+        continue;
+      }
       if (s0 == seq) {                                   // the last position's hidden state feeds lm_head; publish token and length
         (void)hipMemcpyAsync(r.x, c->chunk[R - 1].x, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
         launch_add_pos(c, r.pos, seq);
@@ -888,6 +910,7 @@ void tgx_destroy(tgx_ctx* c) {
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(c->embed); fr(c->lm_head); fr(c->final_norm); fr(c->wpe); fr(c->final_norm_b); fr(c->rope_cos); fr(c->rope_sin); fr(c->step); fr(c->step_done); fr(c->tok_log); fr(c->scratch_x); fr(c->seed_dev); fr(c->samp_scratch); fr(c->samp_list_comp); fr(c->samp_list_v);
   fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req); fr(c->ext_part);
+  fr(c->vf_x); fr(c->vf_logits); fr(c->vf_part_val); fr(c->vf_part_idx); fr(c->vf_rec);
   fr(c->rg_buf); fr(c->rg_x); fr(c->rg_logits); fr(c->rg_part_val); fr(c->rg_part_idx);
   fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
   fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_part); fr(c->ws_ssq); fr(c->ws_pos);
@@ -1362,6 +1385,78 @@ int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   if (int rc = issue_pass(c, row, 1, seq, (int)past)) return rc;
   if (int rc = finish_pass(c)) return rc;
   row_admitted(c, row, (int)(past + seq));         // no current token, a fresh stop state (a finished row runs again), the sampler settings kept
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+// ---- tgx_verify_row (include/tgx.h): greedy speculative decoding.  ONE causal pass — tgx_extend_row's, on whatever route it takes — over the row's current token
+// and the draft, with the logits of every position (issue_pass's verify form); ONE accept launch (kernels/verify.h) then takes the draft's matching prefix and
+// leaves the row as that many greedy decode steps would.  Every check comes before anything changes; the host follows the device's record afterwards.
+static int ensure_verify_ws(tgx_ctx* c) {
+  if (c->vf_rec) return TGX_OK;
+  const size_t R = tgx_ctx::VERIFY_ROWS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
+  int rc;
+  if ((rc = dev_alloc(c, &c->vf_x, R * H)) || (rc = dev_alloc(c, &c->vf_logits, R * V)) || (rc = dev_alloc(c, &c->vf_part_val, R * P)) || (rc = dev_alloc(c, &c->vf_part_idx, R * P))) return rc;
+  HIP_OK(c, hipMemset(c->vf_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
+  return dev_alloc(c, &c->vf_rec, sizeof(tgx::VerifyRecord) / 4);
+}
+
+int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  if (!c || !draft || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "verify before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  // ---- every check before anything changes
+  if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+  if (n_draft < 1 || n_draft > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [1,%d]", n_draft, TGX_MAX_DRAFT);
+  for (int i = 0; i < n_draft; i++)
+    if (draft[i] < 0 || draft[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "draft token id out of range");
+  const RowHost& rh = c->row_host[(size_t)row];
+  if (row >= c->batch || rh.idle || rh.past < 1) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to verify a draft on", row);
+  if (rh.fin) return set_err(c, TGX_ERR_STATE, "row %d finished: tgx_extend_row / tgx_reset_row it first", row);
+  if (rh.nologits) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
+  if (!rh.tok) return set_err(c, TGX_ERR_STATE, "row %d has no current token: tgx_sample_row it first", row);
+  const tgx_sampler_cfg cfg = row_cfg(c, row);
+  if (!is_greedy(&cfg)) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
+  const int M = n_draft + 1;
+  const long long past = rh.past;
+  if (past + M > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, M, d.max_ctx);
+  static_assert((int)tgx_ctx::VERIFY_ROWS == tgx::VERIFY_MAX_POS, "kernels/verify.h VerifyRecord");
+  if (c->kv_paged) {
+    const PrefillRoute rt = prefill_route(c, M, M);
+    if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
+      return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+    const long long need = c->kv.blocks_for(past + M) - c->kv.row_blocks(row), have = c->kv.available_for(nullptr, 0);
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
+                     have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
+    // (the first new position falls into a block the row owns: a block forked siblings map as well is full)
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = ensure_verify_ws(c)) return rc;
+  if (int rc = ensure_extend_ws(c, M, (int)past)) return rc;
+  (void)kv_ensure_blocks(c, row, past + M);        // the whole pass up front; cannot fail: counted above
+  long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the draft; input 0 is written on the device from the row's token word
+  for (int i = 0; i < n_draft; i++) ids[i + 1] = draft[i];
+  HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+  launch_verify_first_id(c, row);
+  if (int rc = issue_pass(c, row, 1, M, (int)past, /*verify=*/true)) return rc;
+  launch_verify_accept(c, row, M);
+  tgx::VerifyRecord rec{};
+  HIP_OK(c, hipMemcpyAsync(&rec, c->vf_rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
+  if (int rc = finish_pass(c)) return rc;
+  if (rec.n < 1 || rec.n > M) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "tgx_verify_row: the accept launch left no record"); }
+  // ---- the host follows the device: length, blocks, finished state
+  RowHost& r = c->row_host[(size_t)row];
+  r.past = past + rec.n;
+  r.fin = (char)rec.finish;
+  kv_trim_row(c, row, r.past);                     // the blocks assigned for the rejected tail go back to the pool
+  note_sampled(c, row, 1, cfg);                    // greedy: tgx_read_probs reads zeros for the row
+  for (int i = 0; i < rec.n; i++) out_ids[i] = rec.ids[i];
+  *out_n = rec.n; *out_finish = rec.finish;
+  if (row == 0) c->last_sampled0 = rec.ids[rec.n - 1];
   refresh_longest(c);
   c->have_logits = true;
   HIP_OK(c, hipGetLastError());

@@ -305,6 +305,10 @@ struct tgx_ctx {
   int extend_attn_splits = -1;
   int extend_attn_min64 = 512, extend_attn_min128 = 1024;
   float* ext_part = nullptr; size_t ext_part_bytes = 0;      // the splits' partials [ns][heads][attn_extend_part_vals][256] (kernels/attn_extend.h)
+  // ---- tgx_verify_row (include/tgx.h; kernels/verify.h): the M <= VERIFY_ROWS positions of a verify pass — their hidden rows (the routes without a one-pass
+  // lm_head stage them here, four to a pass over the weights), logits and argmax partials, and the record the accept launch leaves for the host.  Sized at first use
+  enum { VERIFY_ROWS = TGX_MAX_DRAFT + 1 };
+  float *vf_x = nullptr, *vf_logits = nullptr, *vf_part_val = nullptr; int *vf_part_idx = nullptr, *vf_rec = nullptr;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -366,6 +370,8 @@ void launch_finalize_rows(tgx_ctx* c, int row0, int M);                         
 void launch_embed_chunk(tgx_ctx* c, const long long* ids, int R, int pos0);
 void launch_add_pos(tgx_ctx* c, int* pos, int n);
 void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_val, int* part_idx);
+void launch_verify_first_id(tgx_ctx* c, int row);         // tgx_verify_row: prompt[0] of the row <- its current token
+void launch_verify_accept(tgx_ctx* c, int row, int M);    // ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h)
 // ---- attn.hip (kernels/attn_decode.h, attn_decode_mfma.h)
 bool attn_batch_on_mfma(const tgx_ctx* c, int R);
 void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true);   // combine = false: the caller's o_proj merges the split records
@@ -404,4 +410,5 @@ bool decode_mfma_ok(const tgx_ctx* c);
 int ensure_skinny_ws(tgx_ctx* c, int rows);
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg);
 void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB)
+void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
 int skinny_set_attrs(tgx_ctx* c);

@@ -6,6 +6,7 @@
 #include "kernels/gemv.h"
 #include "kernels/gemv_packed.h"
 #include "kernels/oproj_sliced.h"
+#include "kernels/verify.h"
 
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc) {
   const int upb = 4 / ks;
@@ -389,4 +390,21 @@ void launch_embed_chunk(tgx_ctx* c, const long long* ids, int R, int pos0) {
 void launch_add_pos(tgx_ctx* c, int* pos, int n) { hipLaunchKernelGGL(tgx::add_pos_kernel, dim3(1), dim3(64), 0, c->stream, pos, n); }
 void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_val, int* part_idx) {
   hipLaunchKernelGGL(tgx::argmax_partials_kernel, dim3(c->lm_grid), dim3(256), 0, c->stream, logits, V, part_val, part_idx);
+}
+
+// ---- tgx_verify_row (kernels/verify.h).  The pass's first input is the row's device-resident current token ...
+void launch_verify_first_id(tgx_ctx* c, int row) {
+  hipLaunchKernelGGL(tgx::verify_first_id_kernel, dim3(1), dim3(64), 0, c->stream, c->rows[(size_t)row].prompt, (const int*)c->rows[(size_t)row].tok);
+}
+// ... and behind the pass and the M positions' lm_head, ONE launch accepts the draft's matching prefix and leaves the row as that many greedy decode steps would
+void launch_verify_accept(tgx_ctx* c, int row, int M) {
+  RowState& r = c->rows[(size_t)row];
+  tgx::VerifyArgs a{};
+  a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
+  a.logits = c->vf_logits; a.draft = r.prompt + 1;
+  a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
+  a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
+  a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
+  a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vf_rec);
+  TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_kernel<DT>, dim3(1), dim3(256), 0, c->stream, a))
 }

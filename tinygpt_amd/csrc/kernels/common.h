@@ -191,6 +191,10 @@ __device__ __forceinline__ void row_count_and_stop(RowReq* q, const RowStopWords
   if (reason) q->finished = reason;
 }
 
+// tgx_verify_row (kernels/verify.h): what the accept launch leaves for the host — the tokens the row produced in the call and its finish reason
+constexpr int VERIFY_MAX_POS = 16;      // TGX_MAX_DRAFT + 1 positions of one pass
+struct VerifyRecord { int n, finish; int ids[VERIFY_MAX_POS]; };
+
 // The reference's KVCacheManager grows a row's cache by concat (CacheManager.h:24-42); the unpaged layout here gives every row a max_ctx slab
 // [layer][kv_head][max_ctx][hd].  Paged: one pool per layer, [block][kv_head][KV_BLOCK tokens][hd], and a per-row block table on the device (entry b = the
 // physical block of tokens [b KV_BLOCK, (b + 1) KV_BLOCK); entry 0 of the pool is a scratch block that unassigned table entries point to, so a speculative or

@@ -1,0 +1,88 @@
+// verify.h — the accept step of tgx_verify_row (include/tgx.h): greedy speculative decoding.  One causal pass ran the row's current token and its n_draft draft
+// tokens (M = n_draft + 1 positions) and left the logits and the per-workgroup argmax partials of EVERY position in the call's workspace; this launch decides on
+// the device how many of them the row takes and leaves the row as that many greedy decode steps would: nothing here depends on the host knowing the count.
+#pragma once
+#include "gemv.h"
+
+namespace tgx {
+
+struct VerifyArgs {
+  const float* part_val;     // [M][part_stride] argmax partials of the M positions (the lm_head epilogue's, or argmax_partials_rows_kernel's)
+  const int* part_idx;
+  long long part_stride;
+  int n_part, M;
+  const float* logits;       // [M][V]
+  const long long* draft;    // [M - 1] the draft ids on the device (the pass's inputs 1 .. M - 1)
+  int* tok;                  // the row's current token / position words
+  int* pos;                  // (the pass did NOT advance it: it still holds `past`)
+  RowReq* req;               // the row's request state: every produced token is counted against its stop set / max_new
+  float* row_logits;         // the row's slots: logits [V], argmax partials [n_part], residual stream [H]
+  float* row_part_val;
+  int* row_part_idx;
+  float* x;
+  const void* embed;         // [V][H] storage dtype
+  const void* wpe;           // GPT-2 learned positions or nullptr
+  int H, V, n_pos;
+  VerifyRecord* rec;
+};
+
+// the pass's first input is the row's device-resident current token: the host need not know it
+static __global__ void verify_first_id_kernel(long long* ids, const int* tok) { if (threadIdx.x == 0) ids[0] = *tok; }
+
+// One workgroup of 256 threads.  g[i] = the greedy token of position i (highest value, lowest index on a tie, the (unsigned)idx < V guard of finalize_row).
+// The row produces g[0], then g[1] if g[0] == draft[0], ... : draft[0 .. a - 1] followed by g[a]; a produced token that finishes the row (stop id, max_new)
+// ends the walk.  The position that produced the last token hands the row its logits row and partials; the next embedding is gathered at the advanced position.
+template <int DT>
+__global__ __launch_bounds__(256) void verify_accept_kernel(const VerifyArgs a) {
+  __shared__ int s_g[VERIFY_MAX_POS];
+  __shared__ int s_win, s_tok, s_pos;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int i = wv; i < a.M; i += 4) {      // a wave per position: merge its partials
+    const float* pv = a.part_val + (size_t)i * a.part_stride;
+    const int* pi = a.part_idx + (size_t)i * a.part_stride;
+    float bv = -INFINITY; int bi = 0x7fffffff;
+    for (int p = lane; p < a.n_part; p += 64) {
+      const float v = pv[p]; const int ix = pi[p];
+      if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v = __shfl_xor(bv, o, 64); const int ix = __shfl_xor(bi, o, 64);
+      if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
+    }
+    if (lane == 0) s_g[i] = (unsigned)bi < (unsigned)a.V ? bi : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    RowStopWords w = row_stop_words(a.req, a.tok);
+    int n = 0, win = 0;
+    for (int i = 0; i < a.M; i++) {
+      const int t = s_g[i];
+      row_count_and_stop(a.req, w, t);
+      w.produced++;
+      a.rec->ids[n++] = t; win = i;
+      if (a.req->finished || i + 1 == a.M || a.draft[i] != (long long)t) break;
+    }
+    a.rec->n = n; a.rec->finish = a.req->finished;
+    const int np = *a.pos + n;      // the n inputs that produced tokens are in the cache; the rows behind them are dead
+    *a.pos = np; *a.tok = s_g[win];
+    s_win = win; s_tok = s_g[win]; s_pos = np < a.n_pos ? np : a.n_pos - 1;
+    __threadfence();
+  }
+  __syncthreads();
+  const float* src = a.logits + (size_t)s_win * a.V;
+  if ((a.V & 3) == 0) {
+    const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
+    f32x4* d4 = reinterpret_cast<f32x4*>(a.row_logits);
+    for (int i = threadIdx.x; i < (a.V >> 2); i += 256) d4[i] = s4[i];
+  } else {
+    for (int i = threadIdx.x; i < a.V; i += 256) a.row_logits[i] = src[i];
+  }
+  for (int p = threadIdx.x; p < a.n_part; p += 256) {
+    a.row_part_val[p] = a.part_val[(size_t)s_win * a.part_stride + p];
+    a.row_part_idx[p] = a.part_idx[(size_t)s_win * a.part_stride + p];
+  }
+  gather_embedding<DT>(a.embed, s_tok, a.x, a.H, a.wpe, a.wpe ? s_pos : 0);
+}
+
+}  // namespace tgx

@@ -440,6 +440,24 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
     (void)hipMemcpyAsync(c->rows[(size_t)(row0 + b)].x, c->ws_x + ((size_t)(b + 1) * S - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, c->stream);
 }
 
+// tgx_verify_row: the logits of every position of a skinny pass.  ws_x holds the M final residual rows; model.norm's 16-bit terms come from the row-wise launch and
+// the product is the batched decode step's lm_head (terms form), ONE pass over the weights for all M rows, then the rows' argmax partials
+void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx) {
+  const tgx_model_desc& d = c->d;
+  const int H = d.hidden, V = d.vocab;
+  const ebyte* W = d.tied ? c->embed : c->lm_head;
+  launch_norm_terms(c, c->ws_x, c->final_norm, M, H, 0);
+  if (ksplit_ok(c, M, V, H)) {
+    launch_ksplit(c, tgx::GEMM_STORE, W, logits, V, M, V, H);
+  } else {
+    SkinnyCall lm;
+    lm.epi = tgx::GEMM_STORE; lm.W = W; lm.C = logits; lm.ldc = V; lm.M = M; lm.N = V; lm.K = H; lm.nt = 2; lm.asrc = 0; lm.a_hi = c->ws_ah; lm.a_lo = c->ws_al; lm.allow_split = false;
+    launch_skinny(c, lm);
+  }
+  hipLaunchKernelGGL(tgx::argmax_partials_rows_kernel, dim3(std::min(c->lm_grid, std::max(1, (V / 4 + 255) / 256)), M), dim3(256), 0, c->stream, (const float*)logits, (long long)V, V, part_val, part_idx,
+                     (long long)c->lm_grid, c->lm_grid);
+}
+
 // the skinny kernels' LDS images (weight tiles + activation panels / ring stages) exceed the 64 KB default
 int skinny_set_attrs(tgx_ctx* c) {
   int rc;

@@ -71,6 +71,7 @@ ABI = {
     "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
     "extend_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "truncate_row": (c_int, [c_void_p, c_int, c_int64]),
+    "verify_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -287,6 +288,16 @@ class Model:
         """roll `row` back to its first n positions (include/tgx.h tgx_truncate_row); it then holds no logits until extend_row"""
         self._check(self.be.truncate_row(self._ctx, row, int(n)))
         return self
+
+    def verify_row(self, row: int, draft):
+        """verify `draft` (1 .. 15 guessed next tokens) on the live row `row` in one pass (include/tgx.h tgx_verify_row): the row takes the draft's greedy-matching
+        prefix plus the model's own next token and stands as after that many greedy decode steps -> (produced ids, finish: 0 running, 1 stop id, 2 max_new)"""
+        draft = np.ascontiguousarray(np.asarray(draft, dtype=np.int64).reshape(-1))
+        out = np.empty(len(draft) + 1, dtype=np.int64)
+        n, fin = c_int32(0), c_int32(0)
+        ptr = draft.ctypes.data_as(POINTER(c_int64)) if len(draft) else (c_int64 * 1)()
+        self._check(self.be.verify_row(self._ctx, row, ptr, len(draft), out.ctypes.data_as(POINTER(c_int64)), ctypes.byref(n), ctypes.byref(fin)))
+        return out[:n.value].copy(), fin.value
 
     def sample_row(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0) -> int:
         out = c_int64()

@@ -41,6 +41,11 @@ struct Backend {
   // prefix reuse (optional: GPTConfig::reusePrefix needs both)
   int (*extend_row)(tgx_ctx*, int, const int64_t*, int) = nullptr;
   int (*truncate_row)(tgx_ctx*, int, int64_t) = nullptr;
+  // greedy speculative decoding (optional: GPTConfig::speculate needs all three — the draft is verified by verify_row, steps without a draft go through
+  // decode_rows so that every produced token is counted against the row's stop conditions on the device)
+  int (*verify_row)(tgx_ctx*, int, const int64_t*, int, int64_t*, int32_t*, int32_t*) = nullptr;
+  int (*set_row_stop)(tgx_ctx*, int, int32_t, const int32_t*, int) = nullptr;
+  int (*decode_rows)(tgx_ctx*, int, int64_t*, int32_t*, int32_t*) = nullptr;
 
   bool open(const std::string& path, const std::string& prefix) {
     // RTLD_NODELETE: the shim's runtime owns threads (HIP's signal/event workers; libgomp's team under the CPU oracle) that
@@ -61,6 +66,7 @@ struct Backend {
     TGXH_BIND(reset_cache, true); TGXH_BIND(past_length, true); TGXH_BIND(context_size, true); TGXH_BIND(last_error, true);
     TGXH_BIND(reset_row, false); TGXH_BIND(forward_row, false); TGXH_BIND(sample_row, false); TGXH_BIND(past_length_row, false);
     TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
+    TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
 #undef TGXH_BIND
     return ok;
   }

@@ -98,6 +98,34 @@ bool GPTEngine::prefillReusing(const std::vector<int64_t>& ids) {
   return true;
 }
 
+// ---- GPTConfig::speculate: prompt-lookup drafts verified in one pass (spec_draft.h, include/tgx.h tgx_verify_row)
+bool GPTEngine::speculateActive(int batch) const {
+  const SamplerConfig& s = config_.samplerConfig;
+  const bool greedy = !(s.temperature > 0.f || s.topK > 0 || s.topP < 1.f || s.minP > 0.f);      // Sampler.cpp:15-21
+  return config_.speculate > 0 && batch == 1 && greedy && be_.verify_row && be_.set_row_stop && be_.decode_rows && eosTokenIds_.size() <= (size_t)TGX_MAX_STOP_IDS;
+}
+
+bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
+  const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
+  // a pass over n draft tokens produces up to n + 1 tokens and fills positions past .. past + n
+  const int64_t cap = std::min<int64_t>({(int64_t)config_.speculate, (int64_t)TGX_MAX_DRAFT, room - 1, contextSize() - past - 1});
+  const std::vector<int32_t> draft = cap >= 1 ? ngram_draft(seq, (int)cap) : std::vector<int32_t>();
+  int32_t n = 0, fin = 0;
+  int64_t ids[TGX_MAX_DRAFT + 1] = {0};
+  if (!draft.empty()) {
+    int64_t d64[TGX_MAX_DRAFT];
+    for (size_t i = 0; i < draft.size(); i++) d64[i] = draft[i];
+    if (be_.verify_row(model_.ctx, 0, d64, (int)draft.size(), ids, &n, &fin) != TGX_OK) return fail(std::string("verify: ") + be_.last_error(model_.ctx));
+    spec_.verifyCalls++; spec_.draftTokens += (int64_t)draft.size(); spec_.acceptedDrafts += n - 1; spec_.producedHist[n]++;
+  } else {
+    if (be_.decode_rows(model_.ctx, 1, ids, &n, &fin) != TGX_OK) return fail(std::string("decode: ") + be_.last_error(model_.ctx));
+    spec_.plainSteps++;
+  }
+  for (int32_t i = 0; i < n; i++) seq.push_back((int32_t)ids[i]);
+  finished = fin != 0;
+  return n > 0 || finished ? true : fail("speculate: the row produced no token");
+}
+
 bool GPTEngine::isEosToken(int32_t id) const { return std::find(eosTokenIds_.begin(), eosTokenIds_.end(), id) != eosTokenIds_.end(); }
 
 int64_t GPTEngine::contextSize() const { return model_.ctx ? be_.context_size(model_.ctx) : 0; }
@@ -140,6 +168,17 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   if (be_.sample(model_.ctx, &sc, config_.seed, first.data()) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
   const auto t1 = std::chrono::steady_clock::now();
   // decode: maxNewTokens-1 iterations, no EOS check (:165-172)
+  if (n_new > 1 && speculateActive(B)) {      // ... of which a verified draft covers several at once: no stop ids (no EOS check here), the length on the device
+    std::vector<int32_t> seq;
+    for (int64_t i = 0; i < S; i++) seq.push_back((int32_t)ids[(size_t)i]);
+    seq.push_back((int32_t)first[0]);
+    if (be_.set_row_stop(model_.ctx, 0, (int32_t)(n_new - 1), nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+    bool finished = false;
+    while ((int64_t)seq.size() < S + n_new && !finished)
+      if (!speculateMore(seq, S + n_new, finished)) return out;
+    if ((int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
+    for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = seq[(size_t)(S + 1 + i)];
+  } else
   if (n_new > 1 && be_.decode(model_.ctx, &sc, config_.seed, (int)(n_new - 1), rest.data()) != TGX_OK) {
     fail(std::string("decode: ") + be_.last_error(model_.ctx));
     return out;
@@ -182,6 +221,45 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   tokens.push_back((int32_t)cur);
 
   bool hitEos = false, aborted = false, broke = false;
+  if (speculateActive(1) && config_.maxNewTokens > 1) {
+    // The same consumer as the loop below — token i is checked for EOS and reported in iteration i, the maxNewTokens-th is appended unreported — fed from `seq`,
+    // which grows by a verified draft or one step whenever the consumer runs dry.  EOS and the length stop the row on the device (tgx_set_row_stop), so a
+    // draft is never accepted past either.
+    std::vector<int32_t> seq = tokens;
+    const int64_t maxNew = config_.maxNewTokens;
+    bool finished = false;
+    if (be_.set_row_stop(model_.ctx, 0, (int32_t)(maxNew - 1), eosTokenIds_.empty() ? nullptr : eosTokenIds_.data(), (int)eosTokenIds_.size()) != TGX_OK) {
+      fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); broke = true;
+    }
+    auto have = [&](int64_t k) {      // token k (1-based) of the generation is in seq
+      while (!broke && (int64_t)seq.size() - S < k && !finished) broke = !speculateMore(seq, S + maxNew, finished);
+      return !broke && (int64_t)seq.size() - S >= k;
+    };
+    int64_t count = 1;
+    bool reported = false;
+    for (int64_t i = 1; i < maxNew && !broke; i++) {
+      if (!have(i)) { broke = true; break; }
+      const int32_t tokenId = seq[(size_t)(S + i - 1)];
+      count = i;
+      if (isEosToken(tokenId)) { hitEos = true; break; }
+      if (callback && !callback(tokenId)) { aborted = true; break; }
+      reported = true;
+    }
+    if (!hitEos && !aborted && !broke && reported && have(maxNew)) count = maxNew;
+    tokens.assign(seq.begin(), seq.begin() + (size_t)(S + count));
+    out.firstTokenMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    out.decodeMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    if (reuse) {      // the cache holds every input of a pass or step that produced a token: all of seq but its last token
+      const int64_t held = broke ? 0 : be_.past_length(model_.ctx);
+      if (held >= 1 && held <= (int64_t)seq.size()) cached_.assign(seq.begin(), seq.begin() + held);
+      else cached_.clear();
+    }
+    out.batch = 1;
+    out.newTokens = (int64_t)tokens.size() - S;
+    out.tokenIds = std::move(tokens);
+    out.finishReason = (hitEos || aborted) ? FinishReason::Stop : FinishReason::Length;
+    return out;
+  }
   const bool pipelined = be_.step_async && be_.fetch_token;
   // ticket 0 names the token the last tgx_sample produced (T1); ticket k the token of the k-th step issued since
   int64_t ticket_cur = 0, pending = cur;

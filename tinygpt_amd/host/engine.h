@@ -11,6 +11,7 @@
 
 #include "backend.h"
 #include "loader.h"
+#include "spec_draft.h"
 #include "tokenizer.h"
 
 namespace tgxh {
@@ -39,6 +40,11 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // and prefills only what follows the longest prefix the new prompt shares with it (tgx_truncate_row + tgx_extend_row).  Needs a backend with both symbols;
   // generateSync and any failure of the two calls take the reset path.
   bool reusePrefix = false;
+  // Not in the reference: greedy speculative decoding with prompt lookup (spec_draft.h).  0 = off: the loops below exactly as they were.  N > 0: up to N draft
+  // tokens (clamped to TGX_MAX_DRAFT) are proposed per iteration and verified in one pass (tgx_verify_row); without a match one ordinary step runs.  Active only
+  // for a greedy sampler configuration, ONE sequence, at most TGX_MAX_STOP_IDS EOS ids and a backend that has the calls — otherwise the existing loop runs.  The
+  // produced ids are those of the existing loop up to the summation order between kernel paths (include/tgx.h tgx_verify_row).
+  int speculate = 0;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -57,6 +63,13 @@ struct GPTOutput {       // src/engine/GPTEngine.h:34-40
   // not in the reference's struct: the generate call split at the first token (SURVEY.md §8 row H asks the harness for decode-only tok/s)
   double firstTokenMs = 0.0;         // encode-to-first-token: prefill + first sample
   double decodeMs = 0.0;             // the remaining newTokens-1 steps
+};
+
+// what GPTConfig::speculate did since prepare(): verify passes, the draft tokens they carried and how many of those were accepted, ordinary steps taken for want
+// of a draft, and the histogram of tokens produced per verify pass (1 = the draft's first token was wrong .. TGX_MAX_DRAFT + 1)
+struct SpecStats {
+  int64_t verifyCalls = 0, draftTokens = 0, acceptedDrafts = 0, plainSteps = 0;
+  int64_t producedHist[TGX_MAX_DRAFT + 2] = {};
 };
 
 using GenerateCallback = std::function<bool(int32_t tokenId)>;   // return false to abort (GPTEngine.cpp:208-213)
@@ -94,6 +107,8 @@ class GPTEngine {
     cached_.clear();
   }
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
+  void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
+  const SpecStats& specStats() const { return spec_; }
 
  private:
   // == encodeTexts minus the tokenizer (GPTEngine.cpp:101-144): truncate to contextSize keeping the tail, left-pad
@@ -101,6 +116,10 @@ class GPTEngine {
   bool fail(const std::string& what);
   bool reuseActive() const { return config_.reusePrefix && be_.extend_row && be_.truncate_row; }
   bool prefillReusing(const std::vector<int64_t>& ids);      // the prompt after its cached prefix; false: nothing reusable (the caller resets and prefills)
+  bool speculateActive(int batch) const;                      // GPTConfig::speculate applies to this call
+  // row 0 holds seq minus its last token, which is its current token; the row's stop conditions are set.  Drafts from seq, verifies (or takes one ordinary
+  // step), appends what the row produced — never more than maxTotal tokens in seq.  finished: the row finished on the device.  false: a call failed (err_ set)
+  bool speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished);
 
   GPTConfig config_;
   Backend be_;
@@ -112,6 +131,7 @@ class GPTEngine {
   bool tokenizerOk_ = false;
   std::vector<int32_t> cached_;      // reusePrefix: the token ids row 0's cache holds, position by position (empty: unknown / nothing)
   int64_t lastReused_ = 0;
+  SpecStats spec_;
 };
 
 // Deterministic synthetic checkpoint — bit-identical to tinygpt_amd/synth.py (same integer hash).

@@ -52,6 +52,22 @@ TGXE_API int tgxe_eos_ids(tgxe_engine* h, int32_t* out, int cap) {
 // prefix reuse (GPTConfig::reusePrefix): generateAsync keeps row 0's KV cache between calls; tgxe_last_reused = the prompt tokens the last call served from it
 TGXE_API void tgxe_set_reuse_prefix(tgxe_engine* h, int on) { if (h) h->e->setReusePrefix(on != 0); }
 TGXE_API int64_t tgxe_last_reused(tgxe_engine* h) { return h ? h->e->lastReused() : -1; }
+// greedy speculative decoding (GPTConfig::speculate): the maximum draft length (0 = off); tgxe_spec_stats writes {verify calls, draft tokens, accepted draft
+// tokens, ordinary steps, produced-per-verify histogram [0 .. TGX_MAX_DRAFT + 1]} (up to cap values) and returns how many there are
+TGXE_API void tgxe_set_speculate(tgxe_engine* h, int max_draft) { if (h) h->e->setSpeculate(max_draft); }
+TGXE_API int tgxe_spec_stats(tgxe_engine* h, int64_t* out, int cap) {
+  const tgxh::SpecStats& s = h->e->specStats();
+  const int n_hist = (int)(sizeof s.producedHist / sizeof s.producedHist[0]);
+  const int64_t head[4] = {s.verifyCalls, s.draftTokens, s.acceptedDrafts, s.plainSteps};
+  for (int i = 0; i < 4 + n_hist && i < cap; i++) out[i] = i < 4 ? head[i] : s.producedHist[i - 4];
+  return 4 + n_hist;
+}
+// the drafter alone (spec_draft.h): the proposal for the sequence ids[0 .. n), at most max_draft tokens into out; returns their number
+TGXE_API int tgxh_ngram_draft(const int32_t* ids, int n, int max_draft, int32_t* out) {
+  const std::vector<int32_t> d = tgxh::ngram_draft(std::vector<int32_t>(ids, ids + (ids && n > 0 ? n : 0)), max_draft);
+  for (size_t i = 0; i < d.size(); i++) out[i] = d[i];
+  return (int)d.size();
+}
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
   tgxh::SamplerConfig s; s.temperature = temperature; s.topK = top_k; s.topP = top_p; s.minP = min_p;

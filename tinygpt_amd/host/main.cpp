@@ -34,8 +34,17 @@ static void usage(const char* prog) {
           "  --stream                  batch-1 generateAsync: print UTF-8-safe chunks as they are produced\n"
           "  --prompt-ids <a,b,c;d,e>  prompts as token ids, ';' between batch rows (default without a tokenizer: the 4 prompts as gpt2 ids)\n"
           "  --pad-id <n>              left-pad id (default: eos_token_id of the model, else 0)\n"
-          "  --seed <n>                sampler seed (default: 0)\n",
+          "  --seed <n>                sampler seed (default: 0)\n"
+          "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n",
           prog);
+}
+
+// --speculate: what the drafts did (nothing is printed without the flag)
+static void print_spec(const tgxh::GPTConfig& cfg, const tgxh::GPTEngine& engine) {
+  if (cfg.speculate <= 0) return;
+  const tgxh::SpecStats& s = engine.specStats();
+  printf("speculate: %lld verify passes, %lld of %lld draft tokens accepted, %lld ordinary steps\n", (long long)s.verifyCalls, (long long)s.acceptedDrafts, (long long)s.draftTokens,
+         (long long)s.plainSteps);
 }
 
 int main(int argc, char** argv) {
@@ -66,6 +75,7 @@ int main(int argc, char** argv) {
     else if (a == "--stream") stream = true;
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
+    else if (a == "--speculate") cfg.speculate = atoi(next());
 #ifdef TGXH_TEST_HOOKS
     // tgx_cli_test only (tests/_build, -DTGXH_TEST_HOOKS): bind the host engine to a library of the test's choice that exports the tgx ABI
     // (the CPU oracle), to check host logic on a machine without a GPU.  The shipped tgx_cli has neither flag.
@@ -114,6 +124,7 @@ int main(int argc, char** argv) {
     printf("Time cost: %lld ms, speed: %.2f token/s\n", (long long)ms, out.tokenIds.size() * 1000.0 / ms);
     printf("new tokens: %lld, new-token rate: %.2f token/s\n", (long long)(out.batch * out.newTokens), out.batch * out.newTokens * 1000.0 / ms);
     if (out.newTokens > 1) printf("time to first token: %.1f ms, decode-only rate: %.2f token/s\n", out.firstTokenMs, out.batch * (out.newTokens - 1) * 1000.0 / out.decodeMs);
+    print_spec(cfg, engine);
     return 0;
   }
   int32_t pad = pad_id >= 0 ? (int32_t)pad_id : (!engine.eosTokenIds().empty() ? engine.eosTokenIds()[0] : 0);
@@ -136,5 +147,6 @@ int main(int argc, char** argv) {
   printf("Time cost: %lld ms, speed: %.2f token/s\n", (long long)ms, out.tokenIds.size() * 1000.0 / ms);
   printf("new tokens: %lld, new-token rate: %.2f token/s\n", (long long)(out.batch * out.newTokens), out.batch * out.newTokens * 1000.0 / ms);
   if (out.newTokens > 1) printf("time to first token: %.1f ms, decode-only rate: %.2f token/s\n", out.firstTokenMs, out.batch * (out.newTokens - 1) * 1000.0 / out.decodeMs);
+  print_spec(cfg, engine);
   return 0;
 }

@@ -1,0 +1,169 @@
+"""What tgx_verify_row costs and what it can return (profiles/verify_row.txt): Llama-3.2-1B bf16 synthetic at context ~2060 (the bench's region), unpaged and paged
+cache in ONE process.  Every timed call starts from the same state — the 2048-token prompt prefilled, its first greedy token sampled — rebuilt before the call, so
+the figures of one column differ only in the call; the cases are interleaved over the repeats and the medians are reported, with the spread (min .. max).
+
+  per n_draft in {1, 3, 7, 15}:
+    verify      tgx_verify_row of n_draft tokens (n_draft + 1 positions); drafts from a prior plain greedy run of the same prompt: all correct, the first wrong, the
+                middle one wrong — and, untimed, a wrong token at each position, to check the produced count against the plain run
+    extend      tgx_extend_row of the same n_draft + 1 positions: the pass alone (the parent commit's code) — the difference is the all-position lm_head + accept
+    step        one plain tgx_decode step, synchronised like the two calls above; and the streamed rate of tgx_decode(64) for the project's headline figure
+  derived: break-even accepted drafts = verify / step - 1; tokens/s at acceptance 0, half, full = (1, n_draft // 2 + 1, n_draft + 1) / verify
+  free-running: the host engine, speculate 0 against 7 with prompt lookup on a prompt made of a repeated span, with the histogram of tokens per verify pass
+
+usage: python tools/spec_bench.py [--reps 9] [--out profiles/verify_row.txt]"""
+import argparse
+import ctypes
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np
+
+from tinygpt_amd import known_desc, synth
+from tinygpt_amd.ffi import GREEDY, Model
+
+S = 2048
+NDRAFT = [1, 3, 7, 15]
+
+
+def fresh(m, prompt):
+    m.reset_cache()
+    m.forward(prompt[None, :])
+    return int(m.sample(GREEDY)[0])
+
+
+def timed(fn):
+    t = time.perf_counter()
+    r = fn()
+    return (time.perf_counter() - t) * 1e3, r
+
+
+def med(xs):
+    return "%.3f (%.3f .. %.3f)" % (statistics.median(xs), min(xs), max(xs))
+
+
+def measure(paged, reps, lines):
+    d = known_desc("llama-3.2-1b", "bf16")
+    d.max_batch = 1
+    m = Model(d)
+    if paged:
+        m.set_option("kv.budget_tokens", 4096)
+    m.load_synthetic(1234, 0.02).finalize()
+    V = d.vocab
+    prompt = synth.synth_prompt(V, S, 1234)
+    t0 = fresh(m, prompt)
+    ref = [int(t) for t in m.decode(40, GREEDY)[:, 0]]       # the plain greedy run: ref[i] follows t0, ref[0], ..
+    wrong = lambda ids, j: [t if i != j else (t + 1) % V for i, t in enumerate(ids)]
+    # ---- untimed: the produced count for a wrong token at each position (and none), against the plain run.  A count that differs is a step whose top-2 gap is
+    # inside the band between the two kernel paths: it is reported, not hidden
+    lines.append("cache: %s" % ("paged (kv.budget_tokens 4096)" if paged else "unpaged"))
+    for n in NDRAFT:
+        bad = []
+        for j in list(range(n)) + [None]:
+            assert fresh(m, prompt) == t0
+            ids, fin = m.verify_row(0, wrong(ref[:n], j))
+            want = n + 1 if j is None else j + 1
+            if len(ids) != want or list(ids[:want - 1]) != ref[:want - 1]:
+                bad.append((j, len(ids)))
+        lines.append("  n_draft %2d: produced count == index of the wrong token + 1 at every position and n_draft + 1 with none wrong: %s" % (n, "yes" if not bad else "NO %s" % bad))
+    # ---- timed
+    tv = {(n, k): [] for n in NDRAFT for k in ("all", "first", "mid")}
+    te = {n: [] for n in NDRAFT}
+    ts, tstream = [], []
+    for rep in range(reps + 2):                                # two warm-up rounds (workspaces, graphs), discarded
+        keep = rep >= 2
+        for n in NDRAFT:
+            for k, j in (("all", None), ("first", 0), ("mid", n // 2)):
+                fresh(m, prompt)
+                ms, _ = timed(lambda: m.verify_row(0, wrong(ref[:n], j)))
+                if keep:
+                    tv[(n, k)].append(ms)
+            fresh(m, prompt)
+            ms, _ = timed(lambda: m.extend_row(0, [t0] + ref[:n]))
+            if keep:
+                te[n].append(ms)
+        fresh(m, prompt)
+        ms, _ = timed(lambda: m.decode(1, GREEDY))
+        if keep:
+            ts.append(ms)
+        fresh(m, prompt)
+        ms, _ = timed(lambda: m.decode(64, GREEDY))
+        if keep:
+            tstream.append(ms / 64)
+    step = statistics.median(ts)
+    lines.append("  one plain step, synchronised        ms: %s" % med(ts))
+    lines.append("  plain steps, streamed (64 per call) ms/token: %s   -> %.0f tok/s" % (med(tstream), 1e3 / statistics.median(tstream)))
+    lines.append("  n_draft | verify ms: all correct / first wrong / middle wrong (medians) | extend ms | verify - extend | break-even accepted | tok/s at acceptance 0 / half / full | plain tok/s sync / streamed")
+    for n in NDRAFT:
+        v = statistics.median(tv[(n, "all")] + tv[(n, "first")] + tv[(n, "mid")])
+        e = statistics.median(te[n])
+        lines.append("  %7d | %.3f / %.3f / %.3f | %s | %+.3f | %.2f | %.0f / %.0f / %.0f | %.0f / %.0f" % (
+            n, statistics.median(tv[(n, "all")]), statistics.median(tv[(n, "first")]), statistics.median(tv[(n, "mid")]), med(te[n]), v - e, v / step - 1,
+            1e3 / v, 1e3 * (n // 2 + 1) / v, 1e3 * (n + 1) / v, 1e3 / step, 1e3 / statistics.median(tstream)))
+    out = {n: statistics.median(tv[(n, "all")]) for n in NDRAFT}
+    m.close()
+    return out, step, statistics.median(tstream)
+
+
+def free_running(lines):
+    from ctypes import POINTER, c_int, c_int64, c_void_p
+    from host_util import HostEngine, host_lib
+    lib = host_lib()
+    lib.tgxe_set_speculate.argtypes = [c_void_p, c_int]
+    lib.tgxe_spec_stats.restype = c_int
+    lib.tgxe_spec_stats.argtypes = [c_void_p, POINTER(c_int64), c_int]
+    e = HostEngine(lib, synthetic="llama-3.2-1b", device="mi355x", dtype=1, max_batch=1)
+    assert e.prepare(), e.error()
+    span = synth.synth_prompt(128256, 64, 99).astype(np.int32)
+    prompt = np.tile(span, S // 64)                            # 2048 tokens: one 64-token span, repeated
+    n_new = 256
+    res = {}
+    for rep in range(3):
+        for spec in (0, 7):
+            lib.tgxe_set_speculate(e.h, spec)
+            e.reconfigure(max_new=n_new)
+            t = time.perf_counter()
+            ids, new, fin = e.generate_sync([prompt])
+            res.setdefault(spec, []).append(((time.perf_counter() - t) * 1e3, ids[0, len(prompt):].tolist()))
+    buf = (c_int64 * 32)()
+    lib.tgxe_spec_stats(e.h, buf, 32)
+    st = list(buf[:21])
+    same = res[0][0][1] == res[7][0][1]
+    first_diff = next((i for i, (a, b) in enumerate(zip(res[0][0][1], res[7][0][1])) if a != b), None)
+    lines.append("free-running generateSync, %d new tokens after a %d-token prompt (a 64-token span repeated), unpaged, whole call incl. prefill, ms: speculate 0 %s | speculate 7 %s" % (
+        n_new, med([r[0] for r in res[0]]), med([r[0] for r in res[7]])))
+    lines.append("  ids equal: %s%s" % ("yes" if same else "no", "" if same else " (first difference at new token %d: a step whose top-2 gap is inside the band between the kernel paths)" % first_diff))
+    lines.append("  over the 3 speculate-7 runs: %d verify passes, %d of %d draft tokens accepted, %d ordinary steps; tokens produced per verify pass 1..16: %s" % (st[0], st[2], st[1], st[3], st[5:21]))
+    e.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    try:
+        commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip() or "working tree"
+    except OSError:
+        commit = "working tree"
+    import torch
+    lines = ["tools/spec_bench.py --reps %d   device: %s   commit: %s (+ this change)   Llama-3.2-1B bf16 synthetic, prompt %d tokens" % (a.reps, torch.cuda.get_device_name(0), commit, S)]
+    for paged in (0, 1):
+        measure(paged, a.reps, lines)
+    free_running(lines)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
