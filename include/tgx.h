@@ -31,6 +31,7 @@ extern "C" {
 /* (still 3: additive) tgx_forward_rows; tgx_fork_row — a live row copied into other rows, its full paged KV blocks shared by reference. */
 /* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
+/* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -332,6 +333,35 @@ TGX_API int tgx_truncate_row(tgx_ctx* ctx, int row, int64_t new_len);
  *   Cost              one weight pass for the layers, and for lm_head one pass on the matrix-core route of 5-16 positions, ceil((n_draft + 1) / 4) otherwise. */
 #define TGX_MAX_DRAFT 15
 TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_draft, int64_t* out_ids /* [n_draft + 1] */, int32_t* out_n, int32_t* out_finish);
+
+/* ---- per-token log-probabilities on the device (additive to ABI 3) --------------------------------------------------------------------------------------
+ * n-best ranking, beams and the completions protocol's `logprobs` / `top_logprobs` (the reference's server speaks it) need the model's opinion of the tokens it
+ * produces.  For a row that produced token t from the fp32 logits v[0 .. V) — what the argmax and the sampler look at, tgx_read_logits(rounded = 0) —
+ * lp(t) = v[t] - lse(v), lse(v) = max + log sum exp(v - max) with the sum taken in double in a fixed association and rounded once.  The distribution is the
+ * MODEL's: temperature 1, before top-k / top-p / min-p — the same for a greedy and a sampled row.  The top-N alternatives are the first N entries of v in the order
+ * (value descending, index ascending), as (id, lp) pairs in that order; the produced token need not be among them.  -inf logits rank last and have lp -inf.
+ *
+ *   Setting           per row: top_n = -1 off (the default), 0 the produced token's log-probability only, 1 .. TGX_MAX_LOGPROBS that many alternatives as well.
+ *                     Stream-ordered and kept across calls; tgx_reset_row / tgx_reset_cache restore "off", like tgx_set_row_sampler.  The first call that switches
+ *                     a row on allocates the rings (TGX_LOGPROB_RING records per row); a context that never asks allocates nothing and runs exactly the launches
+ *                     it ran before.  Out-of-range row or top_n: TGX_ERR_INVALID.
+ *   What records      every token a row PRODUCES while its setting is >= 0 appends one record to its ring: tgx_sample_row (the first token after an admission,
+ *                     tgx_extend_row or tgx_fork_row), tgx_decode_rows (one per step of an unfinished live row, the token that finishes it included),
+ *                     tgx_verify_row (out_n of them, each from the logits of the position that produced it).  A finished or retired row that rides along
+ *                     records nothing.  tgx_decode, tgx_sample and tgx_step_async ignore the setting, as they ignore the other row settings.
+ *   Record count      back to 0 on tgx_reset_row, tgx_reset_cache and an admission or fork INTO the row; tgx_extend_row and tgx_truncate_row keep it (truncation
+ *                     does not un-record).  A fork does not copy the source's records; the destination's setting is untouched.
+ *   Reading           tgx_read_row_logprobs returns the row's last n records, oldest first; 1 <= n <= min(records since the count was reset, TGX_LOGPROB_RING),
+ *                     otherwise TGX_ERR_INVALID and nothing is written (the caller knows the count from out_new / out_n and its own calls).  A row that has
+ *                     recorded nothing is TGX_ERR_STATE.  The call synchronises the stream, like the other readers.  out_top_* may be NULL; entries beyond a
+ *                     record's own top_n are id -1 / -INFINITY.
+ *   Cost              two launches behind a step's publish while some row of the batch records (one more bit of the union that keys the per-row step graphs);
+ *                     switching a row between top_n 0 .. TGX_MAX_LOGPROBS is read on the device and recaptures nothing.  Records are the same bits from run to run. */
+#define TGX_MAX_LOGPROBS 20
+#define TGX_LOGPROB_RING 256
+TGX_API int tgx_set_row_logprobs(tgx_ctx* ctx, int row, int top_n);
+TGX_API int tgx_read_row_logprobs(tgx_ctx* ctx, int row, int n, float* out_lp /* [n] */, int32_t* out_top_ids /* [n][TGX_MAX_LOGPROBS] */,
+                                  float* out_top_lp /* [n][TGX_MAX_LOGPROBS] */, int32_t* out_top_n /* [n] */);
 
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);

@@ -364,9 +364,11 @@ static void launch_kv_copy(tgx_ctx* c, long long n_tok, F&& rest) {
 
 // ---- per-row request state (tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows): host-side fields travel BY VALUE in a one-thread launch, stream-ordered
 // behind the steps that still read the old ones (no stream drain, no host buffer that has to outlive the call).  what: ROWQ_* bits
-enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4 };
+// (ROWQ_LP: the row's log-probability setting; ROWQ_LPCOUNT: its record count back to 0.  `lp`: the rows' logprob state once it exists (kernels/logprobs.h) — its
+// `seen` word follows `produced` wherever this launch moves that)
+enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4, ROWQ_LP = 8, ROWQ_LPCOUNT = 16 };
 struct RowReqUpdate { int row, what; tgx::RowReq v; };
-static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u) {
+static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u, tgx::LpRow* lp) {
   if (threadIdx.x != 0) return;
   tgx::RowReq& q = req[u.row];
   if (u.what & ROWQ_SAMPLER) { q.temperature = u.v.temperature; q.top_k = u.v.top_k; q.top_p = u.v.top_p; q.min_p = u.v.min_p; q.seed = u.v.seed; }
@@ -376,6 +378,11 @@ static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u) {
     q.produced = 0;
   }
   if (u.what & ROWQ_STATE) { q.produced = 0; q.finished = 0; }
+  if (u.what & ROWQ_LP) q.lp = u.v.lp;
+  if (lp) {
+    lp[u.row].seen = q.produced;
+    if (u.what & ROWQ_LPCOUNT) { lp[u.row].count = 0; lp[u.row].arrive = 0; }
+  }
 }
 static_assert(tgx::ROW_MAX_STOP == TGX_MAX_STOP_IDS, "kernels/common.h RowReq");
 
@@ -384,14 +391,18 @@ static tgx::RowReq row_req_default() {   // greedy, seed 0, no stop conditions
   q.temperature = 0.f; q.top_k = 0; q.top_p = 1.f; q.min_p = 0.f; q.seed = 0; q.max_new = 0; q.n_stop = 0;
   return q;
 }
+// does the row record log-probabilities in the steps: its setting, unless it is retired (the setting is kept on the host and travels with the admission)
+bool row_records(const tgx_ctx* c, int row) { return c->row_req_host[(size_t)row].lp > 0 && !c->row_host[(size_t)row].idle; }
 static void row_req_push(tgx_ctx* c, int row, int what) {
   RowReqUpdate u{};
   u.row = row; u.what = what; u.v = c->row_req_host[(size_t)row];
-  hipLaunchKernelGGL(row_req_set_kernel, dim3(1), dim3(64), 0, c->stream, c->row_req, u);
+  if (!row_records(c, row)) u.v.lp = 0;      // a retired row rides along in the steps and counts what it publishes: on the device its setting reads "off" until it is refilled
+  hipLaunchKernelGGL(row_req_set_kernel, dim3(1), dim3(64), 0, c->stream, c->row_req, u, c->lp_rows);
 }
 static void row_req_reset(tgx_ctx* c, int row) {   // tgx_reset_row: the default settings and a fresh state
   c->row_req_host[(size_t)row] = row_req_default();
-  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE);
+  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE | ROWQ_LP | ROWQ_LPCOUNT);
+  c->row_host[(size_t)row].lp_count = 0;
 }
 static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
   const tgx::RowReq& q = c->row_req_host[(size_t)row];
@@ -910,6 +921,7 @@ void tgx_destroy(tgx_ctx* c) {
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
   fr(c->embed); fr(c->lm_head); fr(c->final_norm); fr(c->wpe); fr(c->final_norm_b); fr(c->rope_cos); fr(c->rope_sin); fr(c->step); fr(c->step_done); fr(c->tok_log); fr(c->scratch_x); fr(c->seed_dev); fr(c->samp_scratch); fr(c->samp_list_comp); fr(c->samp_list_v);
   fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req); fr(c->ext_part);
+  fr(c->lp_ring); fr(c->lp_rows); fr(c->lp_tile_max); fr(c->lp_tile_sum); fr(c->lp_tile_keys);
   fr(c->vf_x); fr(c->vf_logits); fr(c->vf_part_val); fr(c->vf_part_idx); fr(c->vf_rec);
   fr(c->rg_buf); fr(c->rg_x); fr(c->rg_logits); fr(c->rg_part_val); fr(c->rg_part_idx);
   fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
@@ -1050,9 +1062,10 @@ int tgx_reset_cache(tgx_ctx* c) {
   std::fill(c->row_req_host.begin(), c->row_req_host.end(), row_req_default());
   HIP_OK(c, hipMemcpyAsync(c->row_req, c->row_req_host.data(), c->row_req_host.size() * sizeof(tgx::RowReq), hipMemcpyHostToDevice, c->stream));   // (synchronised below)
   if (c->slab_acc) HIP_OK(c, hipMemsetAsync(c->slab_acc, 0, (size_t)c->d.max_batch * c->d.hidden * 8, c->stream));
+  if (c->lp_rows) HIP_OK(c, hipMemsetAsync(c->lp_rows, 0, (size_t)c->d.max_batch * sizeof(tgx::LpRow), c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->past = 0;
-  for (RowHost& r : c->row_host) r.restart(0, /*idle=*/false, /*fin=*/0);
+  for (RowHost& r : c->row_host) { r.restart(0, /*idle=*/false, /*fin=*/0); r.lp_count = 0; }
   c->have_logits = c->have_token = false;
   c->poisoned = false;
   return TGX_OK;
@@ -1098,9 +1111,11 @@ int tgx_reset_row(tgx_ctx* c, int row) {
 }
 
 // host state of a row after its prompt pass went through (the caller synchronised)
-static void row_admitted(tgx_ctx* c, int row, int seq) {
-  row_req_push(c, row, ROWQ_STATE);       // a new sequence: what the slot counted while it rode along retired is gone (its settings stay)
+static void row_admitted(tgx_ctx* c, int row, int seq, bool keep_lp_count = false) {
   c->row_host[(size_t)row].restart(seq, /*idle=*/false, /*fin=*/0);
+  // a new sequence: what the slot counted while it rode along retired is gone (its settings stay; the log-probability setting, held back while the row was retired, goes to the device)
+  row_req_push(c, row, ROWQ_STATE | ROWQ_LP | (keep_lp_count ? 0 : ROWQ_LPCOUNT));
+  if (!keep_lp_count) c->row_host[(size_t)row].lp_count = 0;                   // ... its log-probability records as well; tgx_extend_row keeps them
   c->row_host[(size_t)row].probs_ok = false;
 }
 
@@ -1384,7 +1399,7 @@ int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)seq * 8, hipMemcpyHostToDevice, c->stream));
   if (int rc = issue_pass(c, row, 1, seq, (int)past)) return rc;
   if (int rc = finish_pass(c)) return rc;
-  row_admitted(c, row, (int)(past + seq));         // no current token, a fresh stop state (a finished row runs again), the sampler settings kept
+  row_admitted(c, row, (int)(past + seq), /*keep_lp_count=*/true);         // no current token, a fresh stop state (a finished row runs again), the sampler settings kept
   refresh_longest(c);
   c->have_logits = true;
   HIP_OK(c, hipGetLastError());
@@ -1444,6 +1459,8 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
   launch_verify_first_id(c, row);
   if (int rc = issue_pass(c, row, 1, M, (int)past, /*verify=*/true)) return rc;
   launch_verify_accept(c, row, M);
+  const bool records = row_records(c, row);
+  if (records) launch_logprobs_verify(c, row, M);      // one record per produced token, each from the logits of the position that produced it
   tgx::VerifyRecord rec{};
   HIP_OK(c, hipMemcpyAsync(&rec, c->vf_rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
   if (int rc = finish_pass(c)) return rc;
@@ -1452,6 +1469,7 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
   RowHost& r = c->row_host[(size_t)row];
   r.past = past + rec.n;
   r.fin = (char)rec.finish;
+  if (records) r.lp_count += rec.n;
   kv_trim_row(c, row, r.past);                     // the blocks assigned for the rejected tail go back to the pool
   note_sampled(c, row, 1, cfg);                    // greedy: tgx_read_probs reads zeros for the row
   for (int i = 0; i < rec.n; i++) out_ids[i] = rec.ids[i];
@@ -1521,8 +1539,12 @@ int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t see
   if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, row, 1, *cfg);
   launch_sample(c, row, 1, *cfg, /*advance_pos=*/false, /*log_step=*/false);
+  const bool records = row_records(c, row);
+  if (records) launch_logprobs(c, row, 1, /*force=*/true);      // the first token after an admission, tgx_extend_row or tgx_fork_row
   HIP_OK(c, hipGetLastError());
+  LAUNCH_OK(c);
   HIP_OK(c, hipStreamSynchronize(c->stream));
+  if (records) c->row_host[(size_t)row].lp_count++;
   int t = 0;
   HIP_OK(c, hipMemcpy(&t, c->rows[(size_t)row].tok, 4, hipMemcpyDeviceToHost));
   if (out_id) *out_id = t;
@@ -1560,6 +1582,49 @@ int tgx_set_row_stop(tgx_ctx* c, int row, int32_t max_new, const int32_t* stop_i
   return TGX_OK;
 }
 
+// ---- per-token log-probabilities (include/tgx.h; kernels/logprobs.h)
+int tgx_set_row_logprobs(tgx_ctx* c, int row, int top_n) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_logprobs before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (top_n < -1 || top_n > TGX_MAX_LOGPROBS) return set_err(c, TGX_ERR_INVALID, "top_n %d out of range [-1,%d]", top_n, TGX_MAX_LOGPROBS);
+  HIP_OK(c, hipSetDevice(c->device));
+  if (top_n >= 0) { if (int rc = logprobs_alloc(c)) return rc; }      // a context that never asks allocates nothing
+  c->row_req_host[(size_t)row].lp = top_n + 1;
+  row_req_push(c, row, ROWQ_LP);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+int tgx_read_row_logprobs(tgx_ctx* c, int row, int n, float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t* out_top_n) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "read_row_logprobs before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (!out_lp) return set_err(c, TGX_ERR_INVALID, "null out_lp");
+  // the host mirrors the row's record counter (RowHost::lp_count follows every call that records): a refused call touches neither the device nor the caller's buffers
+  const int64_t count = c->row_host[(size_t)row].lp_count;
+  if (count < 1) return set_err(c, TGX_ERR_STATE, "row %d has recorded no log-probabilities (tgx_set_row_logprobs; the count restarts with the row)", row);
+  const int have = (int)std::min<int64_t>(count, TGX_LOGPROB_RING);
+  if (n < 1 || n > have) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]: row %d holds %d record(s)", n, have, row, have);
+  HIP_OK(c, hipSetDevice(c->device));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  std::vector<tgx::LpRecord> recs((size_t)n);
+  const int s0 = (int)((count - n) % TGX_LOGPROB_RING), first = std::min(n, TGX_LOGPROB_RING - s0);
+  const tgx::LpRecord* ring = c->lp_ring + (size_t)row * TGX_LOGPROB_RING;
+  HIP_OK(c, hipMemcpy(recs.data(), ring + s0, (size_t)first * sizeof(tgx::LpRecord), hipMemcpyDeviceToHost));
+  if (first < n) HIP_OK(c, hipMemcpy(recs.data() + first, ring, (size_t)(n - first) * sizeof(tgx::LpRecord), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    const tgx::LpRecord& r = recs[(size_t)i];
+    out_lp[i] = r.lp;
+    if (out_top_n) out_top_n[i] = r.top_n;
+    for (int k = 0; k < TGX_MAX_LOGPROBS; k++) {
+      if (out_top_ids) out_top_ids[(size_t)i * TGX_MAX_LOGPROBS + k] = r.ids[k];
+      if (out_top_lp) out_top_lp[(size_t)i * TGX_MAX_LOGPROBS + k] = r.lps[k];
+    }
+  }
+  return TGX_OK;
+}
+
 int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new, int32_t* out_finish) {
   if (!c) return TGX_ERR_INVALID;
   if (n_steps < 0) return set_err(c, TGX_ERR_INVALID, "n_steps %d < 0", n_steps);
@@ -1594,9 +1659,14 @@ int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new,
   if (n_steps > 0 && (rc = read_tok_log(c, start, n_steps, ids.data()))) return rc;
   HIP_OK(c, hipMemcpyAsync(pos.data(), c->slab_pos, B * 4, hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipMemcpyAsync(req.data(), c->row_req, B * sizeof(tgx::RowReq), hipMemcpyDeviceToHost, c->stream));
+  bool records = false;      // the record counters travel with the readback only while some row of the batch records
+  for (size_t b = 0; b < B; b++) records = records || row_records(c, (int)b);
+  std::vector<tgx::LpRow> lp(records ? B : 0);
+  if (records) HIP_OK(c, hipMemcpyAsync(lp.data(), c->lp_rows, B * sizeof(tgx::LpRow), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   for (size_t b = 0; b < B; b++) {
     const bool idle = c->row_host[b].idle;
+    if (records) c->row_host[b].lp_count = lp[b].count;
     c->row_host[b].past = pos[b];                              // a row advanced once per token it produced (retired rows: wherever their ride took them)
     c->row_host[b].fin = idle ? 0 : (char)req[b].finished;
     if (out_new) out_new[b] = idle ? 0 : (int32_t)(pos[b] - before[b]);

@@ -28,7 +28,7 @@
 using tgx::bf16_t;
 typedef unsigned char ebyte;   // parameter / KV-cache storage in the compute dtype: offsets are elements * ctx.esz
 
-namespace tgx { struct SampScratch; }
+namespace tgx { struct SampScratch; struct LpRecord; struct LpRow; }
 
 constexpr int MAX_TICKET_EVENTS = 64;
 constexpr int HOST_RING = 256;
@@ -80,6 +80,7 @@ struct RowHost {        // host state of one batch row
   bool idle = false;    // the row was retired (tgx_reset_row) and not refilled: it rides in the steps, nothing waits for it, its output means nothing
   bool nologits = false;   // the row was truncated (tgx_truncate_row) and not extended since: its slot's logits belong to a position it no longer holds, so nothing may sample, step or fork from it
   char fin = 0;         // the finish reason of the last tgx_decode_rows readback (0 running, 1 stop id, 2 max_new) — a finished row keeps its length, rides along without advancing and counts for neither `past` nor the context check
+  int64_t lp_count = 0; // mirror of the row's device-side record counter (tgx_read_row_logprobs): records appended since the count was reset
   bool probs_ok = false; tgx_sampler_cfg probs_cfg{};   // the row's last sampled step was a non-greedy one, and its sampler configuration (tgx_read_probs evaluates the vector on demand)
   // the slot starts over at `len` positions: no current token, its logits its own; what its last sampled step left (probs_ok, probs_cfg) stays
   void restart(int64_t len, bool idle_, char fin_) { past = len; tok = nologits = false; idle = idle_; fin = fin_; }
@@ -309,6 +310,13 @@ struct tgx_ctx {
   // lm_head stage them here, four to a pass over the weights), logits and argmax partials, and the record the accept launch leaves for the host.  Sized at first use
   enum { VERIFY_ROWS = TGX_MAX_DRAFT + 1 };
   float *vf_x = nullptr, *vf_logits = nullptr, *vf_part_val = nullptr; int *vf_part_idx = nullptr, *vf_rec = nullptr;
+  // ---- per-token log-probabilities (include/tgx.h tgx_set_row_logprobs; kernels/logprobs.h).  Allocated by the first call that switches a row on: the rows' record
+  // rings and counters, and the tile launch's partials for max(max_batch, VERIFY_ROWS) rows (a verify pass puts its positions where a step puts its rows)
+  tgx::LpRecord* lp_ring = nullptr;          // [max_batch][TGX_LOGPROB_RING]
+  tgx::LpRow* lp_rows = nullptr;             // [max_batch]
+  float* lp_tile_max = nullptr;              // [rows][tiles]
+  double* lp_tile_sum = nullptr;             // [rows][tiles]
+  unsigned long long* lp_tile_keys = nullptr;   // [rows][tiles][TGX_MAX_LOGPROBS]
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -353,6 +361,7 @@ namespace tgx { struct AttnArgs; struct FinalizeArgs; struct AttnPrefillArgs; st
 void drop_step_graphs(tgx_ctx* c);
 int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens);       // paged KV: row `row` may hold `tokens` tokens after this (assigns blocks, updates the device table, stream-ordered)
 bool is_greedy(const tgx_sampler_cfg* s);   // Sampler.cpp:15-21
+bool row_records(const tgx_ctx* c, int row);   // the row records log-probabilities in the steps (tgx_set_row_logprobs; not while it is retired)
 // ---- decode.hip (kernels/gemv.h, kernels/oproj_sliced.h)
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc);
 int pack_weights(tgx_ctx* c);     // tgx_finalize: the exponent-packed copies of the bf16 gate_up / down / lm_head matrices (option weights.packed)
@@ -378,11 +387,14 @@ void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true)
 int attn_set_attrs(tgx_ctx* c);
 // ---- sampler.hip (kernels/sampler.h)
 void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step);
-enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick
+enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16, ROWU_LP = 32 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick; some row records log-probabilities
 void launch_sample_rows(tgx_ctx* c, int row0, int R, int un);              // tgx_decode_rows: every row with its own settings (a decode step's sampler)
 int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg);
 int sampler_alloc(tgx_ctx* c);
+int logprobs_alloc(tgx_ctx* c);                                              // the rings, counters and tile partials, at first use
+void launch_logprobs(tgx_ctx* c, int row0, int R, bool force);             // behind a step's publish: the rows that record and produced a token (force: tgx_sample_row)
+void launch_logprobs_verify(tgx_ctx* c, int row, int M);                   // behind tgx_verify_row's accept launch: one record per produced token
 // ---- prefill.hip (kernels/prefill.h, gemm_dma.h)
 bool prefill_shapes_ok(const tgx_model_desc& d);
 int ensure_prefill_ws(tgx_ctx* c, int S);

@@ -165,7 +165,8 @@ struct RowReq {
   long long top_k;
   unsigned long long seed;
   int n_stop, produced;             // produced: tokens published since the last tgx_set_row_stop / tgx_reset_row / refill
-  int finished, pad;                // 0 running, 1 stop id, 2 max_new
+  int finished;                     // 0 running, 1 stop id, 2 max_new
+  int lp;                           // per-token log-probabilities (kernels/logprobs.h; tgx_set_row_logprobs): 0 off — the zero-initialised state — else top_n + 1
   int stop[ROW_MAX_STOP];
 };
 __device__ __forceinline__ bool row_req_greedy(const RowReq& q) {   // == is_greedy (Sampler.cpp:15-21)
@@ -194,6 +195,22 @@ __device__ __forceinline__ void row_count_and_stop(RowReq* q, const RowStopWords
 // tgx_verify_row (kernels/verify.h): what the accept launch leaves for the host — the tokens the row produced in the call and its finish reason
 constexpr int VERIFY_MAX_POS = 16;      // TGX_MAX_DRAFT + 1 positions of one pass
 struct VerifyRecord { int n, finish; int ids[VERIFY_MAX_POS]; };
+
+// per-token log-probabilities (kernels/logprobs.h; include/tgx.h tgx_set_row_logprobs): a row's ring of records and its device-side counters
+constexpr int LP_MAX = 20;            // == TGX_MAX_LOGPROBS
+constexpr int LP_RING = 256;          // == TGX_LOGPROB_RING
+
+struct LpRecord {                     // one produced token
+  float lp;
+  int tok, top_n, pad;
+  int ids[LP_MAX];                    // the first top_n entries in (value descending, index ascending); -1 beyond
+  float lps[LP_MAX];
+};
+struct LpRow {                        // per-row device state
+  int count;                          // records appended since the count was reset (the ring slot of the next one is count % LP_RING)
+  int seen;                           // RowReq.produced as of the row's last record: a step in which `produced` moved produced a token
+  int arrive, pad;                    // verify form: positions that have written their record (the last one moves `count`)
+};
 
 // The reference's KVCacheManager grows a row's cache by concat (CacheManager.h:24-42); the unpaged layout here gives every row a max_ctx slab
 // [layer][kv_head][max_ctx][hd].  Paged: one pool per layer, [block][kv_head][KV_BLOCK tokens][hd], and a per-row block table on the device (entry b = the

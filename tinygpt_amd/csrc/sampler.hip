@@ -4,6 +4,7 @@
 // filter's tail — which also draws the token when the chain ends there.
 #include "ctx.h"
 #include "kernels/sampler.h"
+#include "kernels/logprobs.h"
 #include <type_traits>
 
 static tgx::SampArgs samp_args(tgx_ctx* c, int row0, const tgx_sampler_cfg& cfg) {
@@ -74,6 +75,7 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
 // (row_union_of): greedy rows publish from the argmax partials in one finalize launch, the sampled rows through the union of their filter stages — each
 // workgroup leaves at once when its row has no such stage, and every row publishes exactly once (the step counter moves on the batch's count).  The cfg
 // values are read on the device: a new request's settings need no recapture.
+static void launch_sample_rows_sampled(tgx_ctx* c, int row0, int R, int un);
 void launch_sample_rows(tgx_ctx* c, int row0, int R, int un) {
   tgx::RowReq* req = c->row_req + row0;
   if (un & ROWU_GREEDY) {
@@ -83,7 +85,12 @@ void launch_sample_rows(tgx_ctx* c, int row0, int R, int un) {
     fa.part_stride = c->lm_grid; fa.x_stride = c->d.hidden;
     TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::finalize_rows_kernel<DT, true>), dim3(R), dim3(256), 0, c->stream, fa))
   }
-  if (!(un & (ROWU_K | ROWU_P | ROWU_M | ROWU_SUM))) return;
+  if (un & (ROWU_K | ROWU_P | ROWU_M | ROWU_SUM)) launch_sample_rows_sampled(c, row0, R, un);
+  if (un & ROWU_LP) launch_logprobs(c, row0, R, /*force=*/false);      // behind the publish: the rows that record read their just-published token words
+}
+
+static void launch_sample_rows_sampled(tgx_ctx* c, int row0, int R, int un) {
+  tgx::RowReq* req = c->row_req + row0;
   const tgx_sampler_cfg none{0.f, 0, 1.f, 0.f};
   tgx::SampArgs a = samp_args(c, row0, none);     // cfg fields, mx_ready and z_from_tail: per row on the device
   a.req = req;
@@ -117,6 +124,7 @@ int row_union_of(const tgx_ctx* c) {
   for (int b = 0; b < c->batch; b++) {
     const tgx::RowReq& q = c->row_req_host[(size_t)b];
     const bool K = q.top_k > 0, P = q.top_p < 1.f, M = q.min_p > 0.f, sampled = K || P || M || q.temperature > 0.f;
+    if (row_records(c, b)) un |= ROWU_LP;
     if (!sampled) { un |= ROWU_GREEDY; continue; }
     if (K) un |= ROWU_K;
     if (P) un |= ROWU_P;
@@ -133,6 +141,53 @@ void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg) {
   a.mx_ready = 0;
   const int nwg = (a.V + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE;
   hipLaunchKernelGGL(tgx::samp_sum_kernel<2>, dim3(nwg, 1), dim3(tgx::SAMP_WG), 0, c->stream, a);
+}
+
+// ---- per-token log-probabilities (kernels/logprobs.h)
+static_assert(tgx::LP_MAX == TGX_MAX_LOGPROBS && tgx::LP_RING == TGX_LOGPROB_RING, "kernels/logprobs.h");
+static int lp_tiles(const tgx_ctx* c) { return (c->d.vocab + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE; }
+
+int logprobs_alloc(tgx_ctx* c) {
+  if (c->lp_rows) return TGX_OK;
+  const size_t B = (size_t)c->d.max_batch, rows = std::max<size_t>(B, tgx_ctx::VERIFY_ROWS), T = (size_t)lp_tiles(c);
+  int rc;
+  if ((rc = dev_alloc(c, &c->lp_ring, B * tgx::LP_RING)) || (rc = dev_alloc(c, &c->lp_tile_max, rows * T)) || (rc = dev_alloc(c, &c->lp_tile_sum, rows * T)) ||
+      (rc = dev_alloc(c, &c->lp_tile_keys, rows * T * tgx::LP_MAX)) || (rc = dev_alloc(c, &c->lp_rows, B))) return rc;
+  HIP_OK(c, hipMemsetAsync(c->lp_rows, 0, B * sizeof(tgx::LpRow), c->stream));
+  return TGX_OK;
+}
+
+static tgx::LpArgs lp_args(tgx_ctx* c) {
+  tgx::LpArgs a{};
+  a.V = c->d.vocab; a.nwg = lp_tiles(c); a.logits_stride = c->d.vocab;
+  return a;
+}
+static void lp_launch(tgx_ctx* c, const tgx::LpArgs& a, int R) {
+  hipLaunchKernelGGL(tgx::lp_tile_kernel, dim3(a.nwg, R), dim3(tgx::SAMP_WG), 0, c->stream, a);
+  hipLaunchKernelGGL(tgx::lp_record_kernel, dim3(1, R), dim3(tgx::SAMP_WG), 0, c->stream, a);
+}
+
+void launch_logprobs(tgx_ctx* c, int row0, int R, bool force) {
+  if (!c->lp_rows) { c->launch_fault = "log-probabilities requested before their buffers exist"; return; }
+  tgx::LpArgs a = lp_args(c);
+  const size_t T = (size_t)a.nwg;
+  a.logits = c->rows[(size_t)row0].logits;
+  a.req = c->row_req + row0; a.st = c->lp_rows + row0; a.tok = c->rows[(size_t)row0].tok;
+  a.force = force ? 1 : 0;
+  a.tile_max = c->lp_tile_max + row0 * T; a.tile_sum = c->lp_tile_sum + row0 * T; a.tile_keys = c->lp_tile_keys + row0 * T * tgx::LP_MAX;
+  a.ring = c->lp_ring + (size_t)row0 * tgx::LP_RING;
+  lp_launch(c, a, R);
+}
+
+void launch_logprobs_verify(tgx_ctx* c, int row, int M) {
+  if (!c->lp_rows) { c->launch_fault = "log-probabilities requested before their buffers exist"; return; }
+  tgx::LpArgs a = lp_args(c);
+  a.logits = c->vf_logits;
+  a.req = c->row_req + row; a.st = c->lp_rows + row;
+  a.rec = reinterpret_cast<const tgx::VerifyRecord*>(c->vf_rec);
+  a.tile_max = c->lp_tile_max; a.tile_sum = c->lp_tile_sum; a.tile_keys = c->lp_tile_keys;
+  a.ring = c->lp_ring + (size_t)row * tgx::LP_RING;
+  lp_launch(c, a, M);
 }
 
 int sampler_alloc(tgx_ctx* c) {

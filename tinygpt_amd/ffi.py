@@ -26,6 +26,7 @@ PRODUCT_LIB = os.path.join(HERE, "lib", "libtgx_mi355x.so")
 STATUS_NAMES = {0: "TGX_OK", 1: "TGX_ERR_INVALID", 2: "TGX_ERR_UNSUPPORTED", 3: "TGX_ERR_DEVICE", 4: "TGX_ERR_STATE",
                 5: "TGX_ERR_NOMEM", 6: "TGX_ERR_NAME", 7: "TGX_ERR_SHAPE", 8: "TGX_ERR_CONTEXT"}
 
+MAX_LOGPROBS, LOGPROB_RING = 20, 256      # TGX_MAX_LOGPROBS, TGX_LOGPROB_RING
 KERNEL_CLASSES = ["qkv", "attn", "oproj", "gateup", "down", "lmhead"]
 
 
@@ -77,6 +78,8 @@ ABI = {
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
     "set_row_stop": (c_int, [c_void_p, c_int, c_int32, POINTER(c_int32), c_int]),
     "decode_rows": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "set_row_logprobs": (c_int, [c_void_p, c_int, c_int]),
+    "read_row_logprobs": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
     "context_size": (c_int64, [c_void_p]),
     "num_layers": (c_int32, [c_void_p]),
     "last_error": (c_char_p, [c_void_p]),
@@ -327,6 +330,23 @@ class Model:
         self._check(self.be.decode_rows(self._ctx, n_steps, out.ctypes.data_as(POINTER(c_int64)), new.ctypes.data_as(POINTER(c_int32)),
                                         fin.ctypes.data_as(POINTER(c_int32))))
         return out, new, fin
+
+    # -- per-token log-probabilities (include/tgx.h tgx_set_row_logprobs) ------------------------
+    def set_row_logprobs(self, row: int, top_n: int = 0):
+        """-1 off, 0 the produced token's log-probability, 1 .. MAX_LOGPROBS that many alternatives as well"""
+        self._check(self.be.set_row_logprobs(self._ctx, row, top_n))
+        return self
+
+    def row_logprobs(self, row: int, n: int):
+        """the row's last n records, oldest first -> (lp [n], top ids [n][MAX_LOGPROBS] (-1 beyond top_n), top lp [n][MAX_LOGPROBS], top_n [n])"""
+        m = max(n, 1)
+        lp = np.empty(m, dtype=np.float32)
+        ids = np.empty((m, MAX_LOGPROBS), dtype=np.int32)
+        tlp = np.empty((m, MAX_LOGPROBS), dtype=np.float32)
+        tn = np.empty(m, dtype=np.int32)
+        self._check(self.be.read_row_logprobs(self._ctx, row, n, lp.ctypes.data_as(POINTER(c_float)), ids.ctypes.data_as(POINTER(c_int32)),
+                                              tlp.ctypes.data_as(POINTER(c_float)), tn.ctypes.data_as(POINTER(c_int32))))
+        return lp[:n], ids[:n], tlp[:n], tn[:n]
 
     @property
     def past_length(self) -> int:

@@ -46,6 +46,10 @@ struct Backend {
   int (*verify_row)(tgx_ctx*, int, const int64_t*, int, int64_t*, int32_t*, int32_t*) = nullptr;
   int (*set_row_stop)(tgx_ctx*, int, int32_t, const int32_t*, int) = nullptr;
   int (*decode_rows)(tgx_ctx*, int, int64_t*, int32_t*, int32_t*) = nullptr;
+  // per-token log-probabilities (optional: GPTConfig::logprobs needs these three, sample_row and decode_rows — the engine then steps through the per-row calls)
+  int (*set_row_sampler)(tgx_ctx*, int, const tgx_sampler_cfg*, uint64_t) = nullptr;
+  int (*set_row_logprobs)(tgx_ctx*, int, int) = nullptr;
+  int (*read_row_logprobs)(tgx_ctx*, int, int, float*, int32_t*, float*, int32_t*) = nullptr;
 
   bool open(const std::string& path, const std::string& prefix) {
     // RTLD_NODELETE: the shim's runtime owns threads (HIP's signal/event workers; libgomp's team under the CPU oracle) that
@@ -67,6 +71,7 @@ struct Backend {
     TGXH_BIND(reset_row, false); TGXH_BIND(forward_row, false); TGXH_BIND(sample_row, false); TGXH_BIND(past_length_row, false);
     TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
     TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
+    TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
 #undef TGXH_BIND
     return ok;
   }

@@ -108,7 +108,7 @@ bool GPTEngine::speculateActive(int batch) const {
 bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
   const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
   // a pass over n draft tokens produces up to n + 1 tokens and fills positions past .. past + n
-  const int64_t cap = std::min<int64_t>({(int64_t)config_.speculate, (int64_t)TGX_MAX_DRAFT, room - 1, contextSize() - past - 1});
+  const int64_t cap = !speculateActive(1) ? 0 : std::min<int64_t>({(int64_t)config_.speculate, (int64_t)TGX_MAX_DRAFT, room - 1, contextSize() - past - 1});      // (GPTConfig::logprobs alone feeds the consumer one step at a time)
   const std::vector<int32_t> draft = cap >= 1 ? ngram_draft(seq, (int)cap) : std::vector<int32_t>();
   int32_t n = 0, fin = 0;
   int64_t ids[TGX_MAX_DRAFT + 1] = {0};
@@ -119,11 +119,71 @@ bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool&
     spec_.verifyCalls++; spec_.draftTokens += (int64_t)draft.size(); spec_.acceptedDrafts += n - 1; spec_.producedHist[n]++;
   } else {
     if (be_.decode_rows(model_.ctx, 1, ids, &n, &fin) != TGX_OK) return fail(std::string("decode: ") + be_.last_error(model_.ctx));
-    spec_.plainSteps++;
+    if (speculateActive(1)) spec_.plainSteps++;      // (GPTConfig::logprobs alone also steps through here: no statistic of the drafts)
   }
   for (int32_t i = 0; i < n; i++) seq.push_back((int32_t)ids[i]);
   finished = fin != 0;
   return n > 0 || finished ? true : fail("speculate: the row produced no token");
+}
+
+// ---- GPTConfig::logprobs: the per-row calls record on the device (include/tgx.h tgx_set_row_logprobs); the engine drains each row's ring after every call,
+// and no call produces more than TGX_LOGPROB_RING tokens per row
+bool GPTEngine::logprobsActive() const {
+  return config_.logprobs >= 0 && config_.logprobs <= TGX_MAX_LOGPROBS && be_.set_row_logprobs && be_.read_row_logprobs && be_.set_row_sampler && be_.sample_row &&
+         be_.set_row_stop && be_.decode_rows;
+}
+
+// a request the engine cannot serve is an error, never plain generation with empty lists
+bool GPTEngine::logprobsRefused(bool async) {
+  if (config_.logprobs < 0) return false;
+  if (config_.logprobs > TGX_MAX_LOGPROBS) { fail("logprobs: at most " + std::to_string(TGX_MAX_LOGPROBS) + " alternatives per token"); return true; }
+  if (!logprobsActive()) { fail("logprobs: the device shim lacks tgx_set_row_logprobs / tgx_read_row_logprobs or the per-row calls they ride on"); return true; }
+  if (async && eosTokenIds_.size() > (size_t)TGX_MAX_STOP_IDS) { fail("logprobs: generateAsync stops the row on the device, which holds at most " + std::to_string(TGX_MAX_STOP_IDS) + " stop ids"); return true; }
+  return false;
+}
+
+bool GPTEngine::logprobsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first) {
+  first.assign((size_t)batch, 0);
+  for (int b = 0; b < batch; b++) {
+    if (be_.set_row_sampler(model_.ctx, b, &sc, config_.seed) != TGX_OK || be_.set_row_logprobs(model_.ctx, b, config_.logprobs) != TGX_OK ||
+        be_.sample_row(model_.ctx, b, &sc, config_.seed, &first[(size_t)b]) != TGX_OK)
+      return fail(std::string("logprobs: ") + be_.last_error(model_.ctx));
+  }
+  return true;
+}
+
+bool GPTEngine::logprobsDrain(int row, int64_t n, RowLogprobs& into) {
+  if (n < 1) return true;
+  std::vector<float> lp((size_t)n), tlp((size_t)n * TGX_MAX_LOGPROBS);
+  std::vector<int32_t> tid((size_t)n * TGX_MAX_LOGPROBS);
+  if (be_.read_row_logprobs(model_.ctx, row, (int)n, lp.data(), tid.data(), tlp.data(), nullptr) != TGX_OK) return fail(std::string("read_row_logprobs: ") + be_.last_error(model_.ctx));
+  for (int64_t i = 0; i < n; i++) {
+    into.lp.push_back(lp[(size_t)i]);
+    for (int k = 0; k < config_.logprobs; k++) {
+      into.topId.push_back(tid[(size_t)i * TGX_MAX_LOGPROBS + (size_t)k]);
+      into.topLp.push_back(tlp[(size_t)i * TGX_MAX_LOGPROBS + (size_t)k]);
+    }
+  }
+  return true;
+}
+
+// the rows' setting goes back to "off" however the call that switched it on ends: a failed drain or step must not leave a later call without logprobs
+// paying the record launches
+template <class F> struct AtExit { F f; ~AtExit() { f(); } };
+template <class F> AtExit<F> at_exit(F f) { return AtExit<F>{std::move(f)}; }
+
+void GPTEngine::logprobsEnd(int batch) {
+  for (int b = 0; b < batch; b++) be_.set_row_logprobs(model_.ctx, b, -1);
+}
+
+void GPTEngine::logprobsStore(GPTOutput& out, const std::vector<RowLogprobs>& rows, int64_t perRow) const {
+  out.topLogprobs = config_.logprobs;
+  for (const RowLogprobs& r : rows) {
+    out.logprobs.insert(out.logprobs.end(), r.lp.begin(), r.lp.begin() + std::min<int64_t>(perRow, (int64_t)r.lp.size()));
+    const int64_t k = std::min<int64_t>(perRow * config_.logprobs, (int64_t)r.topId.size());
+    out.topIds.insert(out.topIds.end(), r.topId.begin(), r.topId.begin() + k);
+    out.topLogprobValues.insert(out.topLogprobValues.end(), r.topLp.begin(), r.topLp.begin() + k);
+  }
 }
 
 bool GPTEngine::isEosToken(int32_t id) const { return std::find(eosTokenIds_.begin(), eosTokenIds_.end(), id) != eosTokenIds_.end(); }
@@ -152,6 +212,7 @@ std::vector<int64_t> GPTEngine::alignPrompts(const std::vector<std::vector<int32
 GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& prompts, int32_t padToken) {
   GPTOutput out;
   if (!prepared_ || prompts.empty()) { fail("generateSync: engine not prepared or empty batch"); return out; }
+  if (logprobsRefused(false)) return out;
   const int B = (int)prompts.size();
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts(prompts, padToken, S);
@@ -165,6 +226,13 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   const auto t0 = std::chrono::steady_clock::now();
   if (be_.forward(model_.ctx, ids.data(), B, (int)S) != TGX_OK) { fail(std::string("forward: ") + be_.last_error(model_.ctx)); return out; }
   std::vector<int64_t> first((size_t)B), rest((size_t)(B * (n_new - 1)));
+  const bool lpOn = logprobsActive();
+  std::vector<RowLogprobs> lpRows((size_t)(lpOn ? B : 0));
+  const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(B); });
+  if (lpOn) {
+    if (!logprobsBegin(B, sc, first)) return out;
+    for (int b = 0; b < B; b++) if (!logprobsDrain(b, 1, lpRows[(size_t)b])) return out;
+  } else
   if (be_.sample(model_.ctx, &sc, config_.seed, first.data()) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
   const auto t1 = std::chrono::steady_clock::now();
   // decode: maxNewTokens-1 iterations, no EOS check (:165-172)
@@ -174,15 +242,28 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
     seq.push_back((int32_t)first[0]);
     if (be_.set_row_stop(model_.ctx, 0, (int32_t)(n_new - 1), nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
     bool finished = false;
-    while ((int64_t)seq.size() < S + n_new && !finished)
+    while ((int64_t)seq.size() < S + n_new && !finished) {
+      const size_t before = seq.size();
       if (!speculateMore(seq, S + n_new, finished)) return out;
+      if (lpOn && !logprobsDrain(0, (int64_t)(seq.size() - before), lpRows[0])) return out;
+    }
     if ((int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
     for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = seq[(size_t)(S + 1 + i)];
+  } else if (lpOn) {      // every row with the call's settings through tgx_decode_rows (its ids are tgx_decode's), a ring's worth of steps at most per call
+    for (int b = 0; b < B; b++)
+      if (be_.set_row_stop(model_.ctx, b, 0, nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+    for (int64_t done = 0; done < n_new - 1;) {
+      const int m = (int)std::min<int64_t>(n_new - 1 - done, TGX_LOGPROB_RING / 2);
+      if (be_.decode_rows(model_.ctx, m, rest.data() + (size_t)(done * B), nullptr, nullptr) != TGX_OK) { fail(std::string("decode: ") + be_.last_error(model_.ctx)); return out; }
+      for (int b = 0; b < B; b++) if (!logprobsDrain(b, m, lpRows[(size_t)b])) return out;
+      done += m;
+    }
   } else
   if (n_new > 1 && be_.decode(model_.ctx, &sc, config_.seed, (int)(n_new - 1), rest.data()) != TGX_OK) {
     fail(std::string("decode: ") + be_.last_error(model_.ctx));
     return out;
   }
+  if (lpOn) logprobsStore(out, lpRows, n_new);
   out.firstTokenMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
   out.decodeMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
   out.batch = B;
@@ -201,6 +282,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
 GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const GenerateCallback& callback) {
   GPTOutput out;
   if (!prepared_) { fail("generateAsync: engine not prepared"); return out; }
+  if (logprobsRefused(true)) return out;
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts({prompt}, 0, S);
   if (S == 0) { fail("generateAsync: the prompt is empty (nothing to prefill)"); return out; }
@@ -214,6 +296,14 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   }
   cached_.clear();      // (set again below, once the call knows what the cache holds)
   int64_t cur = 0;
+  const bool lpOn = logprobsActive();
+  std::vector<RowLogprobs> lpRows((size_t)(lpOn ? 1 : 0));
+  const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(1); });
+  if (lpOn) {
+    std::vector<int64_t> first;
+    if (!logprobsBegin(1, sc, first) || !logprobsDrain(0, 1, lpRows[0])) return out;
+    cur = first[0];
+  } else
   if (be_.sample(model_.ctx, &sc, config_.seed, &cur) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
   const auto t1 = std::chrono::steady_clock::now();
   std::vector<int32_t> tokens;
@@ -221,7 +311,7 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   tokens.push_back((int32_t)cur);
 
   bool hitEos = false, aborted = false, broke = false;
-  if (speculateActive(1) && config_.maxNewTokens > 1) {
+  if ((speculateActive(1) || lpOn) && config_.maxNewTokens > 1) {      // (logprobs without speculate: the same consumer, fed one tgx_decode_rows step at a time)
     // The same consumer as the loop below — token i is checked for EOS and reported in iteration i, the maxNewTokens-th is appended unreported — fed from `seq`,
     // which grows by a verified draft or one step whenever the consumer runs dry.  EOS and the length stop the row on the device (tgx_set_row_stop), so a
     // draft is never accepted past either.
@@ -232,7 +322,11 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
       fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); broke = true;
     }
     auto have = [&](int64_t k) {      // token k (1-based) of the generation is in seq
-      while (!broke && (int64_t)seq.size() - S < k && !finished) broke = !speculateMore(seq, S + maxNew, finished);
+      while (!broke && (int64_t)seq.size() - S < k && !finished) {
+        const size_t before = seq.size();
+        broke = !speculateMore(seq, S + maxNew, finished);
+        if (!broke && lpOn) broke = !logprobsDrain(0, (int64_t)(seq.size() - before), lpRows[0]);
+      }
       return !broke && (int64_t)seq.size() - S >= k;
     };
     int64_t count = 1;
@@ -258,8 +352,10 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
     out.newTokens = (int64_t)tokens.size() - S;
     out.tokenIds = std::move(tokens);
     out.finishReason = (hitEos || aborted) ? FinishReason::Stop : FinishReason::Length;
+    if (lpOn) logprobsStore(out, lpRows, out.newTokens);
     return out;
   }
+  if (lpOn) logprobsStore(out, lpRows, 1);      // (one token asked for: the loop below takes no step, the first token's record is all there is)
   const bool pipelined = be_.step_async && be_.fetch_token;
   // ticket 0 names the token the last tgx_sample produced (T1); ticket k the token of the k-th step issued since
   int64_t ticket_cur = 0, pending = cur;

@@ -45,6 +45,15 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // for a greedy sampler configuration, ONE sequence, at most TGX_MAX_STOP_IDS EOS ids and a backend that has the calls — otherwise the existing loop runs.  The
   // produced ids are those of the existing loop up to the summation order between kernel paths (include/tgx.h tgx_verify_row).
   int speculate = 0;
+  // Not in the reference's engine (its server speaks the completions protocol's `logprobs`): -1 = off, the loops below exactly as they were.  N in
+  // [0, TGX_MAX_LOGPROBS]: every produced token comes with its log-probability under the model's distribution and the N most likely alternatives
+  // (include/tgx.h tgx_set_row_logprobs).  The engine then steps through tgx_sample_row / tgx_decode_rows (tgx_verify_row under `speculate`) and drains the rows'
+  // record rings before they can wrap; the ids are those of the existing loops (tgx_decode_rows' draw identity).  generateSync drains once per tgx_decode_rows call
+  // of up to 128 steps (or per verify pass).  generateAsync reports token by token, so it takes ONE tgx_decode_rows step and ONE ring read per token (each
+  // synchronises the stream; a verified draft under `speculate` covers several tokens per read): the one-step lookahead of the plain loop is given up.
+  // A request that cannot be served FAILS the generate call with a message (lastError): N > TGX_MAX_LOGPROBS, a backend without the calls, and in generateAsync
+  // more EOS / stop ids than TGX_MAX_STOP_IDS (the row stops on the device).
+  int logprobs = -1;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -63,6 +72,12 @@ struct GPTOutput {       // src/engine/GPTEngine.h:34-40
   // not in the reference's struct: the generate call split at the first token (SURVEY.md §8 row H asks the harness for decode-only tok/s)
   double firstTokenMs = 0.0;         // encode-to-first-token: prefill + first sample
   double decodeMs = 0.0;             // the remaining newTokens-1 steps
+  // GPTConfig::logprobs >= 0: the log-probability of every new token [batch][newTokens] and its topLogprobs alternatives [batch][newTokens][topLogprobs] as
+  // (id, logprob), most likely first; empty otherwise
+  int topLogprobs = 0;
+  std::vector<float> logprobs;
+  std::vector<int32_t> topIds;
+  std::vector<float> topLogprobValues;
 };
 
 // what GPTConfig::speculate did since prepare(): verify passes, the draft tokens they carried and how many of those were accepted, ordinary steps taken for want
@@ -108,6 +123,7 @@ class GPTEngine {
   }
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
   void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
+  void setLogprobs(int topN) { config_.logprobs = topN; }
   const SpecStats& specStats() const { return spec_; }
 
  private:
@@ -120,6 +136,14 @@ class GPTEngine {
   // row 0 holds seq minus its last token, which is its current token; the row's stop conditions are set.  Drafts from seq, verifies (or takes one ordinary
   // step), appends what the row produced — never more than maxTotal tokens in seq.  finished: the row finished on the device.  false: a call failed (err_ set)
   bool speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished);
+  // GPTConfig::logprobs
+  struct RowLogprobs { std::vector<float> lp, topLp; std::vector<int32_t> topId; };
+  bool logprobsActive() const;
+  bool logprobsRefused(bool async);                                                            // logprobs asked for and not servable: err_ set, the generate call fails
+  bool logprobsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first);      // the rows' settings, then the first token of every row through tgx_sample_row
+  bool logprobsDrain(int row, int64_t n, RowLogprobs& into);                                  // appends the row's last n records
+  void logprobsEnd(int batch);
+  void logprobsStore(GPTOutput& out, const std::vector<RowLogprobs>& rows, int64_t perRow) const;
 
   GPTConfig config_;
   Backend be_;

@@ -11,7 +11,13 @@ using tgxh::GPTEngine;
 struct tgxe_engine {
   GPTEngine* e = nullptr;
   std::string err;
+  tgxh::GPTOutput last;      // the log-probability lists of the last generate call (tgxe_last_logprobs)
 };
+static void keep_logprobs(tgxe_engine* h, tgxh::GPTOutput& r) {
+  h->last = tgxh::GPTOutput();
+  h->last.topLogprobs = r.topLogprobs;
+  h->last.logprobs = std::move(r.logprobs); h->last.topIds = std::move(r.topIds); h->last.topLogprobValues = std::move(r.topLogprobValues);
+}
 
 TGXE_API tgxe_engine* tgxe_create2(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
                                    const char* prefix, int device_ordinal, int dtype, int max_batch, const char* tokenizer_dir);
@@ -68,6 +74,23 @@ TGXE_API int tgxh_ngram_draft(const int32_t* ids, int n, int max_draft, int32_t*
   for (size_t i = 0; i < d.size(); i++) out[i] = d[i];
   return (int)d.size();
 }
+// per-token log-probabilities (GPTConfig::logprobs): top_n = -1 off, 0 .. TGX_MAX_LOGPROBS.  tgxe_last_logprobs copies what the last generate call recorded —
+// out_lp [batch * new tokens], out_top_ids / out_top_lp [batch * new tokens * top_n] (either may be NULL), up to cap tokens — and returns the number of tokens
+// recorded; *out_top_n = the top_n of that call
+TGXE_API void tgxe_set_logprobs(tgxe_engine* h, int top_n) { if (h) h->e->setLogprobs(top_n); }
+TGXE_API int64_t tgxe_last_logprobs(tgxe_engine* h, float* out_lp, int32_t* out_top_ids, float* out_top_lp, int64_t cap, int* out_top_n) {
+  const tgxh::GPTOutput& r = h->last;
+  const int64_t n = (int64_t)r.logprobs.size(), k = r.topLogprobs;
+  if (out_top_n) *out_top_n = r.topLogprobs;
+  for (int64_t i = 0; i < n && i < cap; i++) {
+    if (out_lp) out_lp[i] = r.logprobs[(size_t)i];
+    for (int64_t j = 0; j < k; j++) {
+      if (out_top_ids) out_top_ids[i * k + j] = r.topIds[(size_t)(i * k + j)];
+      if (out_top_lp) out_top_lp[i * k + j] = r.topLogprobValues[(size_t)(i * k + j)];
+    }
+  }
+  return n;
+}
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
   tgxh::SamplerConfig s; s.temperature = temperature; s.topK = top_k; s.topP = top_p; s.minP = min_p;
@@ -81,6 +104,7 @@ TGXE_API int tgxe_generate_sync(tgxe_engine* h, const int32_t* flat, const int32
   size_t o = 0;
   for (int b = 0; b < batch; b++) { p[(size_t)b].assign(flat + o, flat + o + lens[b]); o += (size_t)lens[b]; }
   tgxh::GPTOutput r = h->e->generateSync(p, pad);
+  keep_logprobs(h, r);
   if (r.batch == 0) return 1;
   if ((int64_t)r.tokenIds.size() > cap) return 2;
   memcpy(out_ids, r.tokenIds.data(), r.tokenIds.size() * 4);
@@ -92,6 +116,7 @@ TGXE_API int tgxe_generate_async(tgxe_engine* h, const int32_t* ids, int len, tg
                                  int32_t* out_ids, int64_t cap, int64_t* out_n, int64_t* out_new, int* out_finish) {
   std::vector<int32_t> p(ids, ids + len);
   tgxh::GPTOutput r = h->e->generateAsync(p, [&](int32_t t) { return cb ? cb(t, user) != 0 : true; });
+  keep_logprobs(h, r);
   if (r.batch == 0) return 1;
   if ((int64_t)r.tokenIds.size() > cap) return 2;
   memcpy(out_ids, r.tokenIds.data(), r.tokenIds.size() * 4);

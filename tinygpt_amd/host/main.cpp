@@ -35,6 +35,7 @@ static void usage(const char* prog) {
           "  --prompt-ids <a,b,c;d,e>  prompts as token ids, ';' between batch rows (default without a tokenizer: the 4 prompts as gpt2 ids)\n"
           "  --pad-id <n>              left-pad id (default: eos_token_id of the model, else 0)\n"
           "  --seed <n>                sampler seed (default: 0)\n"
+          "  --logprobs <n>            print every new token's log-probability and its n most likely alternatives (0 .. 20; default: off)\n"
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n",
           prog);
 }
@@ -45,6 +46,19 @@ static void print_spec(const tgxh::GPTConfig& cfg, const tgxh::GPTEngine& engine
   const tgxh::SpecStats& s = engine.specStats();
   printf("speculate: %lld verify passes, %lld of %lld draft tokens accepted, %lld ordinary steps\n", (long long)s.verifyCalls, (long long)s.acceptedDrafts, (long long)s.draftTokens,
          (long long)s.plainSteps);
+}
+
+// --logprobs: one line per new token — row, index, id, its log-probability and the alternatives as id:logprob, most likely first
+static void print_logprobs(const tgxh::GPTOutput& out) {
+  if (out.logprobs.empty()) return;
+  const int64_t per = (int64_t)out.logprobs.size() / out.batch, row = (int64_t)out.tokenIds.size() / out.batch, k = out.topLogprobs;
+  for (int64_t b = 0; b < out.batch; b++)
+    for (int64_t i = 0; i < per; i++) {
+      const size_t at = (size_t)(b * per + i);
+      printf("logprob row %lld token %lld id %d: %.6f |", (long long)b, (long long)i, out.tokenIds[(size_t)(b * row + row - out.newTokens + i)], out.logprobs[at]);
+      for (int64_t j = 0; j < k; j++) printf(" %d:%.6f", out.topIds[at * (size_t)k + (size_t)j], out.topLogprobValues[at * (size_t)k + (size_t)j]);
+      printf("\n");
+    }
 }
 
 int main(int argc, char** argv) {
@@ -76,6 +90,7 @@ int main(int argc, char** argv) {
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
+    else if (a == "--logprobs") cfg.logprobs = atoi(next());
 #ifdef TGXH_TEST_HOOKS
     // tgx_cli_test only (tests/_build, -DTGXH_TEST_HOOKS): bind the host engine to a library of the test's choice that exports the tgx ABI
     // (the CPU oracle), to check host logic on a machine without a GPU.  The shipped tgx_cli has neither flag.
@@ -124,6 +139,7 @@ int main(int argc, char** argv) {
     printf("Time cost: %lld ms, speed: %.2f token/s\n", (long long)ms, out.tokenIds.size() * 1000.0 / ms);
     printf("new tokens: %lld, new-token rate: %.2f token/s\n", (long long)(out.batch * out.newTokens), out.batch * out.newTokens * 1000.0 / ms);
     if (out.newTokens > 1) printf("time to first token: %.1f ms, decode-only rate: %.2f token/s\n", out.firstTokenMs, out.batch * (out.newTokens - 1) * 1000.0 / out.decodeMs);
+    print_logprobs(out);
     print_spec(cfg, engine);
     return 0;
   }
@@ -147,6 +163,7 @@ int main(int argc, char** argv) {
   printf("Time cost: %lld ms, speed: %.2f token/s\n", (long long)ms, out.tokenIds.size() * 1000.0 / ms);
   printf("new tokens: %lld, new-token rate: %.2f token/s\n", (long long)(out.batch * out.newTokens), out.batch * out.newTokens * 1000.0 / ms);
   if (out.newTokens > 1) printf("time to first token: %.1f ms, decode-only rate: %.2f token/s\n", out.firstTokenMs, out.batch * (out.newTokens - 1) * 1000.0 / out.decodeMs);
+  print_logprobs(out);
   print_spec(cfg, engine);
   return 0;
 }

@@ -28,7 +28,23 @@ for rep in range(4):            # the configurations alternate (the clock the po
         m.decode(16, cfg, seed=1, fetch=False); m.synchronize()
         t0 = time.perf_counter(); m.decode(128, cfg, seed=1, fetch=False); m.synchronize(); dt = (time.perf_counter() - t0) / 128
         best[label] = min(best.get(label, 1e9), dt)
+LP_LEGS = []
+# the log-probability records (tgx_set_row_logprobs) ride behind a step's publish: tgx_decode_rows greedy with logprobs off / top_n 0 / 5 / 20
+for rep in range(4):
+    for top_n in (-1, 0, 5, 20):
+        # (an untimed pass over the same contexts first, as above: the timed region captures no graph)
+        m.reset_cache(); m.forward(prompt); m.set_row_logprobs(0, top_n); m.sample_row(0); m.decode_rows(16 + 128); m.synchronize()
+        m.reset_cache(); m.forward(prompt); m.set_row_logprobs(0, top_n); m.sample_row(0)
+        m.decode_rows(16); m.synchronize()
+        t0 = time.perf_counter(); m.decode_rows(128); m.synchronize(); dt = (time.perf_counter() - t0) / 128
+        label = "decode_rows greedy, logprobs " + ("off" if top_n < 0 else f"top_n {top_n}")
+        best[label] = min(best.get(label, 1e9), dt)
+        if rep == 0: LP_LEGS.append(label)
 base = best["greedy"]
 for label, _ in CFGS:
     dt = best[label]
     print(f"{label:40s} {dt * 1e3:.4f} ms/step  {1 / dt:7.1f} tok/s  sampler adds {(dt - base) * 1e6:6.1f} us", flush=True)
+base = best[LP_LEGS[0]]          # the records' cost is read against the same per-row step with every row off
+for label in LP_LEGS:
+    dt = best[label]
+    print(f"{label:40s} {dt * 1e3:.4f} ms/step  {1 / dt:7.1f} tok/s  logprobs add {(dt - base) * 1e6:6.1f} us", flush=True)

@@ -162,7 +162,8 @@ def serve_nbest(K, fork):
     born()
     nb = lambda n: (n + 127) // 128
     waiting = list(range(len(reqs)))
-    groups = []                                   # [rows, length, target, reserved tokens]
+    groups = []                                   # [rows, length, target, reserved tokens, summed log-probability per sample]
+    spreads = []                                  # per finished request: best - worst summed log-probability of its K samples
     idle = list(range(B))
     produced = steps = calls = peak_held = 0
     m.synchronize(); t0 = time.perf_counter()
@@ -187,8 +188,9 @@ def serve_nbest(K, fork):
                 m.forward_rows(rows, [prompts[i]] * K)
             for k, r in enumerate(rows):
                 seed = 1000 * i + k
+                m.set_row_logprobs(r, 0)          # the samples are ranked by their summed log-probability (tgx_set_row_logprobs; tgx_reset_row switched it off)
                 m.sample_row(r, warm, seed=seed); m.set_row_sampler(r, warm, seed)
-            groups.append([rows, L, L + new, cost])
+            groups.append([rows, L, L + new, cost, [float(m.row_logprobs(r, 1)[0][0]) for r in rows]])
             reserved += cost
             produced += K
         if not groups:
@@ -200,7 +202,10 @@ def serve_nbest(K, fork):
             peak_held = max(peak_held, budget - m.get_option("kv.free_tokens"))
         for g in groups:
             g[1] += n; produced += n * K
+            for k, r in enumerate(g[0]):          # drained every call: the ring holds 256 records, a call produces at most 16
+                g[4][k] += float(m.row_logprobs(r, n)[0].sum())
         for g in [g for g in groups if g[1] >= g[2]]:
+            spreads.append(max(g[4]) - min(g[4]))
             for r in g[0]:
                 m.reset_row(r)
             idle += g[0]
@@ -208,7 +213,7 @@ def serve_nbest(K, fork):
     m.synchronize(); dt = time.perf_counter() - t0
     held = f"peak of budget - kv.free_tokens {peak_held} tokens = {peak_held // 128} blocks of {budget // 128}" if args.kv_budget else "unpaged"
     print(f"n-best {K} {'prefill + fork' if fork else 'K separate prompts'}: {len(reqs)} requests, {produced} tokens generated in {dt:.2f} s = {produced / dt:8.0f} tokens/s; "
-          f"{steps} steps in {calls} decode calls; {held}", flush=True)
+          f"{steps} steps in {calls} decode calls; {held}; samples ranked by summed log-probability, best - worst of a request: mean {sum(spreads) / max(len(spreads), 1):.2f} nats", flush=True)
 
 
 print(f"{desc.name}: {B} rows, max_ctx {args.max_ctx}, prompts {plo}..{phi}, outputs {nlo}..{nhi} tokens, "
