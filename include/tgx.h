@@ -443,7 +443,11 @@ TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
  *   "attn.direct_limit"  decode steps at contexts up to this many keys run the direct attention form (batch-1 steps at head_dim 64: with the
  *                        o_proj product in the same launch), beyond it the split form
  *   "attn.nw4_limit"     ... and up to this many keys its four-wave variant (0 = never)
- *   "graph.steps"        decode steps per captured multi-step graph */
+ *   "graph.steps"        decode steps per captured multi-step graph
+ * Read-only figures: "weights.packed_matrices" / "weights.packed_fallbacks" / "weights.packed_max_row_esc" (after tgx_finalize), "kv.free_tokens" (above), and
+ *   "mem.live_allocs"    device buffers the context holds now: weights, caches, and the workspaces that were sized at first use or grown since ...
+ *   "mem.live_kib"       ... and their bytes, rounded up to KiB.  A workspace that grows replaces its buffer: a context's figures depend on the largest shapes it has
+ *                        served (and on "act.round16" at the last growth), not on the way there — what a test can hold memory to on a device that others use */
 TGX_API int tgx_get_option(const tgx_ctx* ctx, const char* key, int* out_value);
 
 /* Algorithmic HBM bytes one decoded token streams at context length T (SURVEY.md §8d formula).  Matrices stored exponent-packed (option "weights.packed",

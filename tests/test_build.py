@@ -1,4 +1,5 @@
 """Build-time properties of the hand-written kernels that no numerics test sees (no GPU needed: hipcc cross-compiles gfx950 and reports its own resource usage)."""
+import glob
 import os
 import sys
 
@@ -27,4 +28,13 @@ def test_skinny_kernels_in_use_have_no_scratch():
     rows = check_spills.spills("skinny")
     bad = [r for r in rows if (r["spill"] > 8 or r["scratch"] > 32)
            and not ("skinny_gemm_kernel<1, " in r["name"] and ", 3, 0, 2>" in r["name"]) and not (", 4, 3, 0, 0>" in r["name"])]
+    assert not bad, bad
+
+
+def test_device_memory_goes_through_the_context_owner():
+    """Every device buffer of the library is handed out and freed by the context's DevMem (csrc/dev_mem.h, bound to the allocator in csrc/ctx.h): a translation unit that
+    called the allocator itself would bring back the hand-kept free list of tgx_destroy, which had already lost a buffer (ws_zero) once."""
+    units = sorted(glob.glob(os.path.join(ROOT, "tinygpt_amd", "csrc", "*.hip")))
+    assert len(units) >= 7
+    bad = [(os.path.basename(u), n + 1) for u in units for n, line in enumerate(open(u)) if "hipMalloc(" in line or "hipFree(" in line]
     assert not bad, bad

@@ -27,7 +27,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 
 def _deps():
-    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h")]
+    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h")]
     kd = os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -81,28 +81,31 @@ def _stale(target, deps):
     return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(d) for d in deps)
 
 
-def build_kv_pool_check(force: bool = False, verbose: bool = False):
-    """tests/kv_pool_check.cpp (the CPU audit of csrc/kv_pool.h, its own main) under the address and undefined-behaviour sanitizers: tests/_build/kv_pool_check."""
-    src, target = os.path.join(HERE, "..", "tests", "kv_pool_check.cpp"), os.path.join(TEST_BUILD, "kv_pool_check")
+def _build_cpu_check(name, header, force, verbose):
+    """tests/<name>.cpp (the CPU audit of `header`, its own main) under the address and undefined-behaviour sanitizers: tests/_build/<name>."""
+    src, target = os.path.join(HERE, "..", "tests", name + ".cpp"), os.path.join(TEST_BUILD, name)
     os.makedirs(TEST_BUILD, exist_ok=True)
-    if force or _stale(target, [src, os.path.join(CSRC, "kv_pool.h")]):
+    if force or _stale(target, [src, header]):
         cmd = [CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-Wall", "-Wextra", src, "-o", target]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
     return target
+
+
+def build_kv_pool_check(force: bool = False, verbose: bool = False):
+    """tests/kv_pool_check.cpp, the CPU audit of csrc/kv_pool.h."""
+    return _build_cpu_check("kv_pool_check", os.path.join(CSRC, "kv_pool.h"), force, verbose)
+
+
+def build_dev_mem_check(force: bool = False, verbose: bool = False):
+    """tests/dev_mem_check.cpp, the CPU audit of csrc/dev_mem.h."""
+    return _build_cpu_check("dev_mem_check", os.path.join(CSRC, "dev_mem.h"), force, verbose)
 
 
 def build_spec_draft_check(force: bool = False, verbose: bool = False):
-    """tests/spec_draft_check.cpp (the CPU audit of host/spec_draft.h, its own main) under the address and undefined-behaviour sanitizers: tests/_build/spec_draft_check."""
-    src, target = os.path.join(HERE, "..", "tests", "spec_draft_check.cpp"), os.path.join(TEST_BUILD, "spec_draft_check")
-    os.makedirs(TEST_BUILD, exist_ok=True)
-    if force or _stale(target, [src, os.path.join(HOST, "spec_draft.h")]):
-        cmd = [CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-Wall", "-Wextra", src, "-o", target]
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        subprocess.check_call(cmd)
-    return target
+    """tests/spec_draft_check.cpp, the CPU audit of host/spec_draft.h."""
+    return _build_cpu_check("spec_draft_check", os.path.join(HOST, "spec_draft.h"), force, verbose)
 
 
 def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = False):

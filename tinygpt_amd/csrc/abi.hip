@@ -918,19 +918,7 @@ void tgx_destroy(tgx_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   drop_step_graphs(c);
-  auto fr = [](void* p) { if (p) (void)hipFree(p); };
-  fr(c->embed); fr(c->lm_head); fr(c->final_norm); fr(c->wpe); fr(c->final_norm_b); fr(c->rope_cos); fr(c->rope_sin); fr(c->step); fr(c->step_done); fr(c->tok_log); fr(c->scratch_x); fr(c->seed_dev); fr(c->samp_scratch); fr(c->samp_list_comp); fr(c->samp_list_v);
-  fr(c->slab_acc); fr(c->kv_tbl); fr(c->row_req); fr(c->ext_part);
-  fr(c->lp_ring); fr(c->lp_rows); fr(c->lp_tile_max); fr(c->lp_tile_sum); fr(c->lp_tile_keys);
-  fr(c->vf_x); fr(c->vf_logits); fr(c->vf_part_val); fr(c->vf_part_idx); fr(c->vf_rec);
-  fr(c->rg_buf); fr(c->rg_x); fr(c->rg_logits); fr(c->rg_part_val); fr(c->rg_part_idx);
-  fr(c->ch_x); fr(c->ch_q); fr(c->ch_kraw); fr(c->ch_attn); fr(c->ch_h); fr(c->ch_part); fr(c->ch_pos);
-  fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_part); fr(c->ws_ssq); fr(c->ws_pos);
-  fr(c->plm.P); fr(c->plm.rec);
-  for (auto& w : c->L) { fr(w.pgu.P); fr(w.pgu.rec); fr(w.pdown.P); fr(w.pdown.rec); }
-  for (auto& w : c->L) { fr(w.in_norm); fr(w.post_norm); fr(w.wqkv); fr(w.bqkv); fr(w.wo); fr(w.q_norm); fr(w.k_norm); fr(w.wgu); fr(w.wdown); fr(w.in_norm_b); fr(w.post_norm_b); fr(w.bo); fr(w.bfc); fr(w.bdown); }
-  fr(c->slab_x); fr(c->slab_q); fr(c->slab_kraw); fr(c->slab_attn); fr(c->slab_h); fr(c->slab_logits); fr(c->slab_probs);
-  fr(c->slab_part_val); fr(c->slab_part_idx); fr(c->slab_attn_part); fr(c->slab_tok); fr(c->slab_pos); fr(c->slab_prompt); fr(c->slab_k); fr(c->slab_v);
+  c->mem.release_all();      // every device buffer of the context, by its record (dev_mem.h)
   if (c->host_ring) (void)hipHostFree(c->host_ring);
   for (auto& e : c->ticket_ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : c->prof.ev) if (e) (void)hipEventDestroy(e);
@@ -1213,13 +1201,7 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
   if (bytes) {
     const size_t o_ids = bytes;
     bytes += (size_t)total * 8;
-    if (bytes > c->rg_bytes) {
-      HIP_OK(c, hipStreamSynchronize(c->stream));
-      if (c->rg_buf) (void)hipFree(c->rg_buf);
-      c->rg_buf = nullptr; c->rg_bytes = 0;
-      if (int rc = dev_alloc(c, &c->rg_buf, bytes)) return rc;
-      c->rg_bytes = bytes;
-    }
+    if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
     if (!c->rg_x) {
       const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
       int rc;
@@ -1845,6 +1827,8 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "weights.packed_fallbacks")) { *out_value = c->packed_fallbacks; return TGX_OK; }      // ... matrices that stayed plain because a row's escape record overflowed ...
   if (!strcmp(key, "weights.packed_max_row_esc")) { *out_value = c->packed_max_row_esc; return TGX_OK; }  // ... and the most escapes seen in one row
   if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv.free_blocks() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
+  if (!strcmp(key, "mem.live_allocs")) { *out_value = (int)c->mem.live(); return TGX_OK; }                     // read-only: device buffers the context holds now ...
+  if (!strcmp(key, "mem.live_kib")) { *out_value = (int)((c->mem.live_bytes() + 1023) / 1024); return TGX_OK; }  // ... and their bytes, rounded up to KiB
   return TGX_ERR_INVALID;
 }
 

@@ -2,6 +2,7 @@
 //   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows),
 //                    the device side of paged-KV block assignment (table pushes) and tgx_fork_row with its copy launch (kernels/kv_fork.h)
 //   kv_pool.h        KvPool: the paged cache's block bookkeeping (free list, per-block row counts, the table's host mirror) — host-only, checked on a CPU
+//   dev_mem.h        DevMem: the owner of every device allocation of the context (dev_alloc / dev_free / dev_grow below) — host-only, checked on a CPU
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
@@ -24,6 +25,7 @@
 #include "../../include/tgx.h"
 #include "kernels/common.h"
 #include "kv_pool.h"
+#include "dev_mem.h"
 
 using tgx::bf16_t;
 typedef unsigned char ebyte;   // parameter / KV-cache storage in the compute dtype: offsets are elements * ctx.esz
@@ -114,8 +116,11 @@ struct RaggedPass {
   int n_items = 0;
 };
 
+inline void* hip_dev_alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }      // the library's two uses of the
+inline void hip_dev_free(void* p) { (void)hipFree(p); }                                                                         // device allocator: tgx_ctx::mem
 struct tgx_ctx {
   tgx_model_desc d{};
+  DevMem mem{hip_dev_alloc, hip_dev_free};      // owns every device buffer below: tgx_destroy frees by its record, not by a list of names
   int device = 0;
   int num_cus = 256;
   hipStream_t stream = nullptr;
@@ -280,7 +285,7 @@ struct tgx_ctx {
   int skinny_terms_above = 2;  // (round 4: 2 instead of 4 — Llama-3.2-1B B = 3 / 4 0.822 / 0.823 -> 0.794 / 0.798 ms per step) option skinny.terms_above: batched steps with more rows than this prepare stored terms for the norm-fused products (with skinny.dma_qkv 2)
   int qkv_nosplit = 1;       // option prefill.qkv_nosplit: the balanced QKV launch instead of K slabs when it alone covers 3/4 of the chip
   int splitk_8k = 1;         // option prefill.splitk_8k: N = hidden products of 129-1500-row prompts as 2-4 K slabs on the eight-wave LDS-DMA kernel
-  bf16_t* ws_zero = nullptr; size_t ws_zero_elems = 0;
+  bf16_t* ws_zero = nullptr;
   // batch-1 steps on the direct attention form (short contexts, head_dim 64): the o_proj product runs in the attention launch's epilogue (attn_decode_kernel
   // template OPJ) — 4 launches per layer; the direct form then serves contexts up to attn_fused_max keys, with four wave-loads per softmax block up to attn_fused_nw4 keys and eight beyond (four waves per head either way); was: four / eight waves up to attn_fused_nw4
   int oproj_fused = 1, attn_fused_max = 640, attn_fused_nw4 = 384;
@@ -349,10 +354,21 @@ int set_err(tgx_ctx* c, int code, const char* fmt, ...);
   if ((dt_) == tgx::DT_F16) { constexpr int DT = tgx::DT_F16; __VA_ARGS__; }             \
   else { constexpr int DT = tgx::DT_BF16; __VA_ARGS__; }
 
+// ---- device memory: every buffer of the context comes from c->mem (dev_mem.h) and is freed by tgx_destroy at the latest.  dev_grow: *p, of *bytes bytes, holds `need`
+// bytes after it — a growth loses the contents and first waits for the stream (launches in flight may read the old buffer; dropping captured graphs that point
+// into it is the caller's business); on failure *p == nullptr and *bytes == 0
 template <typename T>
 int dev_alloc(tgx_ctx* c, T** p, size_t n) {
-  HIP_OK(c, hipMalloc((void**)p, n * sizeof(T)));
-  return TGX_OK;
+  *p = static_cast<T*>(c->mem.alloc(n * sizeof(T)));
+  return *p ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "dev_alloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(hipPeekAtLastError()));
+}
+template <typename T> void dev_free(tgx_ctx* c, T** p) { c->mem.release(*p); *p = nullptr; }
+template <typename T>
+int dev_grow(tgx_ctx* c, T** p, size_t* bytes, size_t need) {
+  if (need <= *bytes) return TGX_OK;
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  void* q = *p; const bool ok = c->mem.grow(&q, bytes, need); *p = static_cast<T*>(q);
+  return ok ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "dev_grow to %zu bytes failed: %s", need, hipGetErrorString(hipPeekAtLastError()));
 }
 
 namespace tgx { struct AttnArgs; struct FinalizeArgs; struct AttnPrefillArgs; struct RopeKvArgs; }
@@ -398,6 +414,7 @@ void launch_logprobs_verify(tgx_ctx* c, int row, int M);                   // be
 // ---- prefill.hip (kernels/prefill.h, gemm_dma.h)
 bool prefill_shapes_ok(const tgx_model_desc& d);
 int ensure_prefill_ws(tgx_ctx* c, int S);
+int ensure_ws_part(tgx_ctx* c, size_t need);      // ws_part holds `need` bytes after this (a growth drops the step graphs: a captured batched step points into the old slabs)
 void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past);      // past: the rows' common pastLength (their positions are past .. past + S - 1) — explicit, not read from the context
 void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg);           // the same pass over the prompts of rg (every one from position 0)
 // the device tables of p (RgSeq [n], token -> prompt map [M], attention work list [n_items]; each 16-byte aligned) as one block: sets p.n_items and returns the block's

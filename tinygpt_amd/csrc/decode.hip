@@ -89,7 +89,7 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
   PackedMat m;
   m.ks = ks; m.row_bytes = (long long)ks * ((nx + 3) / 4) * 3072;
   int rc;
-  if ((rc = dev_alloc(c, &m.P, (size_t)N * (size_t)m.row_bytes)) || (rc = dev_alloc(c, &m.rec, (size_t)N))) { if (m.P) (void)hipFree(m.P); return rc; }
+  if ((rc = dev_alloc(c, &m.P, (size_t)N * (size_t)m.row_bytes)) || (rc = dev_alloc(c, &m.rec, (size_t)N))) { dev_free(c, &m.P); return rc; }
   HIP_OK(c, hipMemsetAsync(stat_dev, 0, 4 * sizeof(int), c->stream));
   const size_t n8 = (size_t)N * K / 8;
   hipLaunchKernelGGL(tgx::packed_maxexp_kernel, dim3((unsigned)std::min<size_t>((n8 + 255) / 256, 4096)), dim3(256), 0, c->stream, reinterpret_cast<const bf16_t*>(W), n8, stat_dev);
@@ -102,7 +102,7 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->packed_max_row_esc = std::max(c->packed_max_row_esc, stat[3]);
   if (stat[1] > 0) {       // a row's escapes do not fit its record: this matrix stays plain
-    (void)hipFree(m.P); (void)hipFree(m.rec);
+    dev_free(c, &m.P); dev_free(c, &m.rec);
     c->packed_fallbacks++;
     return TGX_OK;
   }
@@ -124,7 +124,7 @@ int pack_weights(tgx_ctx* c) {
     if (!rc && (c->packed_classes & 2) && d.inter <= 16384) rc = pack_matrix(c, w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, stat_dev, &w.pdown);
   }
   if (!rc && (c->packed_classes & 4)) rc = pack_matrix(c, d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, stat_dev, &c->plm);
-  if (stat_dev) (void)hipFree(stat_dev);
+  dev_free(c, &stat_dev);
   return rc;
 }
 

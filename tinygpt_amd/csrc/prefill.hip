@@ -21,34 +21,24 @@ int ensure_prefill_ws(tgx_ctx* c, int S) {
   const size_t wout = qd + 2 * kvd, wa = std::max(H, qd);   // the gate_up product leaves no fp32 intermediate (GEMM_SILU)
   drop_step_graphs(c);                                       // a captured batched decode step holds pointers into the old workspace
   HIP_OK(c, hipStreamSynchronize(c->stream));
-  auto fr = [](void* p) { if (p) (void)hipFree(p); };
-  fr(c->ws_x); fr(c->ws_out); fr(c->ws_ah); fr(c->ws_al); fr(c->ws_al2); fr(c->ws_qh); fr(c->ws_ql); fr(c->ws_hh); fr(c->ws_hl); fr(c->ws_zero);
-  c->ws_al2 = nullptr; c->ws_zero = nullptr; c->ws_zero_elems = 0;
-  c->ws_x = nullptr; c->ws_out = nullptr; c->ws_ah = c->ws_al = c->ws_qh = c->ws_ql = c->ws_hh = c->ws_hl = nullptr; c->ws_rows = 0;
-  const size_t rows = (size_t)S;
   // fp32 storage: ws_ah / ws_qh / ws_hh hold fp32 rows (the fp32 GEMM's A operands, the rotated queries); the lo terms are unused
-  const size_t te = c->dt == tgx::DT_F32 ? 4 : 2, lo = c->dt == tgx::DT_F32 ? 0 : 1;
-  HIP_OK(c, hipMalloc((void**)&c->ws_x, rows * H * 4));
-  HIP_OK(c, hipMalloc((void**)&c->ws_out, rows * wout * 4));
-  HIP_OK(c, hipMalloc((void**)&c->ws_ah, rows * wa * te));
-  HIP_OK(c, hipMalloc((void**)&c->ws_al, rows * wa * 2 * lo + 16));
-  HIP_OK(c, hipMalloc((void**)&c->ws_al2, rows * H * 2 * lo + 16));
-  HIP_OK(c, hipMalloc((void**)&c->ws_qh, rows * qd * te));
-  HIP_OK(c, hipMalloc((void**)&c->ws_ql, rows * qd * 2 * lo + 16));
-  HIP_OK(c, hipMalloc((void**)&c->ws_hh, rows * I * te));
-  HIP_OK(c, hipMalloc((void**)&c->ws_hl, rows * I * 2 * lo + 16));
-  if (c->act16 && lo) {      // option act.round16: the all-zero "lo term" of every stored-term product (any A operand fits: rows x max(H, qd, I))
-    c->ws_zero_elems = rows * std::max(wa, I) + 8;
-    HIP_OK(c, hipMalloc((void**)&c->ws_zero, c->ws_zero_elems * 2));
-    HIP_OK(c, hipMemset(c->ws_zero, 0, c->ws_zero_elems * 2));
-  }
-  if (c->dt == tgx::DT_F32) {
-    if (c->ws_pos) (void)hipFree(c->ws_pos);
-    c->ws_pos = nullptr;
-    HIP_OK(c, hipMalloc((void**)&c->ws_pos, rows * 4));
-  }
+  const size_t rows = (size_t)S, te = c->dt == tgx::DT_F32 ? 4 : 2, lo = c->dt == tgx::DT_F32 ? 0 : 1;
+  const size_t zero_bytes = c->act16 && lo ? (rows * std::max(wa, I) + 8) * 2 : 0;      // option act.round16: the all-zero "lo term" of every stored-term product (any A operand fits: rows x max(H, qd, I))
+  const struct { void* p; size_t bytes; } ws[] = {      // p: the context's pointer field.  0 bytes: released, not allocated (ws_pos: the fp32 prefill alone)
+    {&c->ws_x, rows * H * 4}, {&c->ws_out, rows * wout * 4}, {&c->ws_ah, rows * wa * te}, {&c->ws_al, rows * wa * 2 * lo + 16}, {&c->ws_al2, rows * H * 2 * lo + 16},
+    {&c->ws_qh, rows * qd * te}, {&c->ws_ql, rows * qd * 2 * lo + 16}, {&c->ws_hh, rows * I * te}, {&c->ws_hl, rows * I * 2 * lo + 16},
+    {&c->ws_zero, zero_bytes}, {&c->ws_pos, c->dt == tgx::DT_F32 ? rows * 4 : 0}};
+  for (const auto& w : ws) dev_free(c, (ebyte**)w.p);
+  c->ws_rows = 0;      // (a failure below leaves it so: the next call starts over)
+  for (const auto& w : ws) if (int rc = w.bytes ? dev_alloc(c, (ebyte**)w.p, w.bytes) : TGX_OK) return rc;
+  if (c->ws_zero) HIP_OK(c, hipMemset(c->ws_zero, 0, zero_bytes));
   c->ws_rows = S;
   return TGX_OK;
+}
+
+int ensure_ws_part(tgx_ctx* c, size_t need) {
+  if (need > c->ws_part_bytes) drop_step_graphs(c);
+  return dev_grow(c, &c->ws_part, &c->ws_part_bytes, need);
 }
 
 // defer (optional, RESIDUAL / STORE products): when the product is split over K, leave the slabs in ws_part for the consumer kernel to sum
@@ -124,15 +114,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
   // round (Llama-3.2-1B S = 2048: 256 workgroups) it ties with the one-slab 128 x 128 launch (141 vs 140-146 us) and costs a second slab; Mistral-7B S = 2048 56.1 -> 54.1 ms
   if (nsplit == 1 && defer && c->defer_reduce && epi == tgx::GEMM_RESIDUAL && (c->gemm_dma & 8) && !three_terms && !one && K >= 2 * N && K % 128 == 0 && N % 256 == 0 &&
       2 * (N / 256) * ((M + 127) / 128) >= c->wide_n_min * c->num_cus) {
-    const size_t need = (size_t)2 * M * N * 4;
-    if (need > c->ws_part_bytes) {
-      drop_step_graphs(c);
-      (void)hipStreamSynchronize(c->stream);
-      if (c->ws_part) (void)hipFree(c->ws_part);
-      c->ws_part = nullptr; c->ws_part_bytes = 0;
-      if (hipMalloc((void**)&c->ws_part, need) == hipSuccess) c->ws_part_bytes = need;
-    }
-    if (c->ws_part_bytes >= need) {
+    if (!ensure_ws_part(c, (size_t)2 * M * N * 4)) {      // (no slabs: the paths below)
       g.part = c->ws_part; g.nsplit = 2; g.interleave = 0; g.k_per = K / 2;
       const dim3 g8(N / 256, (M + 127) / 128, 2), b8(512);
       TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL((tgx::gemm_dma8n_kernel<DT>), g8, b8, (size_t)2 * (2 * 128 + 256) * 64 * 2, c->stream, g))
@@ -145,16 +127,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
   const bool store_slab = nsplit == 1 && defer && c->defer_reduce && epi == tgx::GEMM_RESIDUAL && (c->gemm_dma & 8) && K % 64 == 0 && !three_terms &&
                           2 * t128u >= c->num_cus && 2 * t128u <= 3 * c->num_cus &&
                           !((c->gemm_dma & 4) && ((N + 255) / 256) * ((M + 255) / 256) >= c->num_cus);
-  if (nsplit > 1 || store_slab) {
-    const size_t need = (size_t)nsplit * M * N * 4;
-    if (need > c->ws_part_bytes) {
-      drop_step_graphs(c);              // a captured batched decode step points into the old slab buffer
-      (void)hipStreamSynchronize(c->stream);
-      if (c->ws_part) (void)hipFree(c->ws_part);
-      c->ws_part = nullptr; c->ws_part_bytes = 0;
-      if (hipMalloc((void**)&c->ws_part, need) == hipSuccess) c->ws_part_bytes = need; else nsplit = 1;
-    }
-  }
+  if ((nsplit > 1 || store_slab) && ensure_ws_part(c, (size_t)nsplit * M * N * 4)) nsplit = 1;
   if (store_slab && c->ws_part_bytes >= (size_t)M * N * 4) {
     g.part = c->ws_part; g.nsplit = 1; g.interleave = 0; g.k_per = K;
     const dim3 g8((N + 127) / 128, (M + 127) / 128, 1), b8(512);
@@ -320,14 +293,7 @@ static size_t extend_part_bytes(const tgx_ctx* c, int ns) {
 int ensure_extend_ws(tgx_ctx* c, int S, int past) {
   const int ns = extend_attn_splits(c, S, past);
   if (!ns) return TGX_OK;
-  const size_t bytes = extend_part_bytes(c, ns);
-  if (bytes <= c->ext_part_bytes) return TGX_OK;
-  HIP_OK(c, hipStreamSynchronize(c->stream));
-  if (c->ext_part) (void)hipFree(c->ext_part);
-  c->ext_part = nullptr; c->ext_part_bytes = 0;
-  HIP_OK(c, hipMalloc((void**)&c->ext_part, bytes));
-  c->ext_part_bytes = bytes;
-  return TGX_OK;
+  return dev_grow(c, &c->ext_part, &c->ext_part_bytes, extend_part_bytes(c, ns));
 }
 static void launch_attn_extend(tgx_ctx* c, const tgx::AttnPrefillArgs& a, int ns) {
   const int hd = c->d.head_dim;

@@ -50,15 +50,7 @@ int ensure_f32_part(tgx_ctx* c, int rows) {
   const size_t widest = std::max<size_t>(std::max<size_t>((size_t)d.heads * d.head_dim + 2 * (size_t)d.kv_heads * d.head_dim, (size_t)(c->gpt2 ? 1 : 2) * d.inter), (size_t)d.hidden);
   // splits shrink as the tile count grows: nsplit * tiles stays near two per CU, so nsplit * rows * N is bounded by ~2 CUs x one 128 x 128 tile x 16
   const size_t need = std::min<size_t>((size_t)16 * rows * widest * 4, (size_t)64 << 20);
-  if (need > c->ws_part_bytes) {
-    drop_step_graphs(c);
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    if (c->ws_part) (void)hipFree(c->ws_part);
-    c->ws_part = nullptr; c->ws_part_bytes = 0;
-    HIP_OK(c, hipMalloc((void**)&c->ws_part, need));
-    c->ws_part_bytes = need;
-  }
-  return TGX_OK;
+  return ensure_ws_part(c, need);
 }
 
 void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S, int past) {

@@ -186,21 +186,12 @@ bool decode_mfma_ok(const tgx_ctx* c) {
 
 // workspace of the batched step, sized before the step is captured: qkv rows, siluMul terms, split-K slabs, sums of squares
 int ensure_skinny_ws(tgx_ctx* c, int rows) {
-  int rc = ensure_prefill_ws(c, rows);
-  if (rc) return rc;
+  if (int rc = ensure_prefill_ws(c, rows)) return rc;
   const tgx_model_desc& d = c->d;
   const size_t widest = std::max<size_t>((size_t)d.heads * d.head_dim + 2 * (size_t)d.kv_heads * d.head_dim, (size_t)2 * d.inter);
   const size_t need = (size_t)16 * rows * std::max<size_t>(widest, (size_t)d.hidden) * 4;       // up to 16 K splits
-  if (need > c->ws_part_bytes) {
-    drop_step_graphs(c);
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    if (c->ws_part) (void)hipFree(c->ws_part);
-    c->ws_part = nullptr; c->ws_part_bytes = 0;
-    HIP_OK(c, hipMalloc((void**)&c->ws_part, need));
-    c->ws_part_bytes = need;
-  }
-  if (!c->ws_ssq) HIP_OK(c, hipMalloc((void**)&c->ws_ssq, (size_t)128 * tgx::SK_NCB * 4));
-  return TGX_OK;
+  if (int rc = ensure_ws_part(c, need)) return rc;
+  return c->ws_ssq ? TGX_OK : dev_alloc(c, &c->ws_ssq, (size_t)128 * tgx::SK_NCB);
 }
 
 // The wide products of a batch of <= 32 rows on the barrier-free K-split kernel (kernels/skinny_ksplit.h); activations = the 16-bit terms
