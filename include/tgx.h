@@ -32,6 +32,7 @@ extern "C" {
 /* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
 /* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
+/* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -362,6 +363,35 @@ TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_dr
 TGX_API int tgx_set_row_logprobs(tgx_ctx* ctx, int row, int top_n);
 TGX_API int tgx_read_row_logprobs(tgx_ctx* ctx, int row, int n, float* out_lp /* [n] */, int32_t* out_top_ids /* [n][TGX_MAX_LOGPROBS] */,
                                   float* out_top_lp /* [n][TGX_MAX_LOGPROBS] */, int32_t* out_top_n /* [n] */);
+
+/* ---- scoring a sequence: every supplied token's log-probability in one prefill pass (additive to ABI 3) ------------------------------------------------
+ * The logprobs ring above holds the model's opinion of the tokens a row PRODUCES; the completions protocol's `echo` + `logprobs`, the perplexity of a checkpoint on
+ * a text and the ranking of candidate continuations behind a shared prefix (tgx_fork_row) need it for the tokens the caller SUPPLIES.  tgx_score_row is a prompt
+ * pass that also returns them, at the cost of one all-position lm_head instead of one pass per prefix.
+ *
+ *   The pass          on a retired row, an empty one or row == batch the call IS tgx_forward_row(row, ids, seq); on a live or finished row that holds >= 1
+ *                     positions it IS tgx_extend_row(row, ids, seq): the same route, the same refusals in the same order with the same status codes, all or
+ *                     nothing, the same block accounting on a paged cache, and the same row afterwards — the last position's logits in the row's slot, no current
+ *                     token, a fresh stop state, the sampler settings kept.  The logits slot, the KV rows and every id sampled afterwards are the plain call's bits.
+ *   Outputs           for i in [0, seq - 1): out_lp[i] = v_i[ids[i + 1]] - lse(v_i), v_i the fp32 logits of the pass's position i and lp as defined above
+ *                     (temperature 1, the model's distribution, whatever the row's sampler).  With top_n >= 1 also the first top_n entries of v_i in the order
+ *                     (value descending, index ascending) as (id, lp) pairs; entries beyond top_n are id -1 / -INFINITY.  out_top_* may be NULL.  The LAST position
+ *                     scores nothing: its logits are in the row's slot (tgx_sample_row, tgx_read_logits).  ids[0]'s own score is not produced either — on the
+ *                     extend form, to score the first new token as well, tgx_truncate_row(row, past - 1) and pass the dropped token as ids[0].
+ *                     seq == 1 is legal and writes nothing.
+ *   Refusals          top_n outside [0, TGX_MAX_LOGPROBS] and a null out_lp with seq > 1 are TGX_ERR_INVALID, checked ahead of the pass's own; nothing changes.
+ *   Side effects      nothing is recorded in the row's logprobs ring and its count does not move.  The call synchronises like an admission; the scores come back
+ *                     in one read-back.  A context that never calls it allocates nothing new and runs exactly the launches it ran before.
+ *   How               no [seq][V] buffer exists (2048 x 128256 fp32 would be 1 GiB).  16-bit storage on the matrix-core route: groups of at most `score.rows`
+ *                     positions (option; a multiple of 64, default 2048); per group the final norm, then per `score.vocab_chunk` columns (a multiple of 1024,
+ *                     default 16384) one product against that slice of the lm_head rows and one tile launch that keeps, per position and 1024-entry tile of V,
+ *                     (max, sum of exp, first top_n keys, the target's value); one record launch per group merges the tiles in a fixed association.  Each logit
+ *                     is one K-ordered sum on one pinned kernel form and the tile partition of V is global, so the scores are the same bits for every legal
+ *                     option value and from run to run.  The weights stream once per group.  Every other route (short prompts, fp32 storage, prefill by steps)
+ *                     scores in groups of TGX_MAX_DRAFT + 1 positions through tgx_verify_row's all-position lm_head.  Read-only option `score.last_form`, the form of the
+ *                     last call that scored a position: 0 none yet, 1 matrix cores, 2 by groups. */
+TGX_API int tgx_score_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq, int top_n, float* out_lp /* [seq - 1] */,
+                          int32_t* out_top_ids /* [seq - 1][TGX_MAX_LOGPROBS] */, float* out_top_lp /* [seq - 1][TGX_MAX_LOGPROBS] */);
 
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);

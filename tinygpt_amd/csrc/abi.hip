@@ -556,10 +556,11 @@ static int launch_route(tgx_ctx* c, PrefillRoute rt, int M, int row0, int NB, in
 // tgx_verify_row: the logits and argmax partials of ALL M positions of a one-row pass into the vf_* workspace.  The skinny route's final residual rows (ws_x) go
 // through the batched step's one-pass lm_head; every other route stages its hidden rows in vf_x (the matrix-core routes' ws_x here, prefill by steps chunk by chunk)
 // and runs the GEMV lm_head four rows per pass over the weights (a group of three rides as four: vf_x holds VERIFY_ROWS rows, the fourth's results are not read)
-static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M) {
+// (src: the M hidden rows of a matrix-core route, default the first M of ws_x — a scoring pass feeds it one group of positions at a time)
+static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M, float* src = nullptr) {
   const size_t H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
-  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, c->vf_logits, c->vf_part_val, c->vf_part_idx); return; }
-  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(c->vf_x, c->ws_x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, c->stream);
+  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, c->vf_logits, c->vf_part_val, c->vf_part_idx, src); return; }
+  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(c->vf_x, src ? src : c->ws_x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, c->stream);
   for (int m0 = 0; m0 < M;) {
     const int rem = M - m0, R = rem >= 3 ? 4 : rem;
     launch_lm_head_at(c, c->vf_x + m0 * H, c->vf_logits + m0 * V, c->vf_part_val + m0 * P, c->vf_part_idx + m0 * P, R);
@@ -567,11 +568,23 @@ static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M) {
   }
 }
 
+// tgx_score_row on the routes without the matrix-core form: the R <= VERIFY_ROWS positions from g0 through the verify form's lm_head into the vf_* workspace
+// (hidden: their rows of ws_x; nullptr: staged in vf_x already, prefill by steps), then the tile and record launches of kernels/score.h over it
+static void launch_score_group(tgx_ctx* c, PrefillRoute rt, const ScoreCall& sc, int g0, int R, float* hidden) {
+  launch_lm_head_all(c, rt, R, hidden);
+  launch_score_tiles(c, sc, c->vf_logits, c->d.vocab, 0, c->d.vocab, R, g0);
+  launch_score_record(c, sc, R, g0);
+}
+
 // One pass of nb rows [row0, row0 + nb) over positions past .. past + seq - 1 of each (their ids are in rows[].prompt, their blocks assigned); leaves every row's
 // logits and advances its position word.  `past` is an argument: tgx_forward passes the batch's pastLength, an admission 0 whatever the other rows hold.
 // verify (tgx_verify_row, nb == 1): the same pass, but the logits of EVERY position land in the vf_* workspace (launch_lm_head_all) and neither the row's logits
 // slot nor its position word moves — the accept launch behind the pass writes both
-static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool verify = false) {
+// sc (tgx_score_row, nb == 1): the plain pass, and behind it every position's score — the matrix-core form over ws_x on ROUTE_TILED (prefill.hip
+// launch_score_tiled), groups of VERIFY_ROWS positions on every other route (prefill by steps scores each group as its chunks complete)
+static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool verify = false, const ScoreCall* sc = nullptr) {
+  if (sc && sc->n_score < 1) sc = nullptr;      // (one position: nothing to score)
+  constexpr int SG = tgx_ctx::VERIFY_ROWS;
   const PrefillRoute rt = prefill_route(c, seq, nb * seq);
   if (rt != ROUTE_STEPS) {
     // batched prefill on the matrix cores; logits for the last position only (== forward + narrow, GPTEngine.cpp:96-97)
@@ -584,6 +597,9 @@ static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool veri
       b += R;
     }
     for (int b = row0; b < row0 + nb; b++) launch_add_pos(c, c->rows[(size_t)b].pos, seq);
+    if (sc && rt == ROUTE_TILED) launch_score_tiled(c, *sc);
+    else if (sc)
+      for (int g0 = 0; g0 < sc->n_score; g0 += SG) launch_score_group(c, rt, *sc, g0, std::min(SG, sc->n_score - g0), c->ws_x + (size_t)g0 * c->d.hidden);
     return TGX_OK;
   }
   for (int b = row0; b < row0 + nb; b++) {
@@ -601,6 +617,11 @@ static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool veri
         (void)hipMemcpyAsync(c->vf_x + (size_t)(s0 - R) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
         if (s0 == seq) launch_lm_head_all(c, rt, seq);
         continue;
+      }
+      if (sc) {                                          // the chunk's hidden rows into their group's slots; a complete group (chunks of four: its boundary is a chunk's) is scored at once
+        const int g0 = (s0 - R) / SG * SG;
+        (void)hipMemcpyAsync(c->vf_x + (size_t)(s0 - R - g0) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
+        if ((s0 % SG == 0 || s0 == seq) && g0 < sc->n_score) launch_score_group(c, rt, *sc, g0, std::min(s0, sc->n_score) - g0, nullptr);
       }
       if (s0 == seq) {                                   // the last position's hidden state feeds lm_head; publish token and length
         (void)hipMemcpyAsync(r.x, c->chunk[R - 1].x, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
@@ -1143,7 +1164,22 @@ static int check_target_rows(tgx_ctx* c, int n, const int32_t* rows, const int32
 // may_join (tgx_forward_rows): consecutive whole prompts share ONE ragged prefill pass per group of <= max(8192, longest) workspace rows where a matrix-core route
 // takes the group's rows; every other prompt, and every prompt of tgx_forward_row, runs issue_pass's one-row pass.  Only a call with a ragged pass uploads tables
 // (one buffer, ONE upload: per group the tables of ragged_tables, then the call's ids) and holds the four lm_head staging rows.
-static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, bool may_join) {
+static int ensure_verify_ws(tgx_ctx* c);
+// tgx_score_row: the workspace of a scoring pass of seq positions on route rt, before the pass is issued; the read-back of its scores, behind it
+static int score_prepare(tgx_ctx* c, ScoreCall* sc, PrefillRoute rt, int row) {
+  sc->ids = c->rows[(size_t)row].prompt;
+  if (sc->n_score < 1) return TGX_OK;
+  if (rt != ROUTE_TILED) if (int rc = ensure_verify_ws(c)) return rc;
+  return ensure_score_ws(c, sc->n_score + 1, rt == ROUTE_TILED);
+}
+static int score_read_back(tgx_ctx* c, const ScoreCall* sc) {
+  if (sc->n_score < 1) return TGX_OK;
+  HIP_OK(c, hipMemcpyAsync(sc->host, c->sc_out, sc->host_bytes, hipMemcpyDeviceToHost, c->stream));
+  return TGX_OK;
+}
+
+// sc (tgx_score_row; n == 1, may_join false): the pass also scores its positions (issue_pass)
+static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, bool may_join, ScoreCall* sc = nullptr) {
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
@@ -1167,6 +1203,8 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
                      tgx::KV_BLOCK, have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
   }
   HIP_OK(c, hipSetDevice(c->device));
+  const PrefillRoute sc_rt = prefill_route(c, lens[0], lens[0]);
+  if (sc) if (int rc = score_prepare(c, sc, sc_rt, rows[0])) return rc;
   if (c->kv_paged) {
     for (int i = 0; i < n; i++) kv_release_row(c, rows[i]);
     for (int i = 0; i < n; i++) (void)kv_ensure_blocks(c, rows[i], lens[i]);     // cannot fail: counted above
@@ -1229,7 +1267,7 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
     } else
       for (int i = i0; i < i1; i++) {
         HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)rows[i]].prompt, ids + off[(size_t)i], (size_t)lens[i] * 8, hipMemcpyHostToDevice, c->stream));
-        if (int rc = issue_pass(c, rows[i], 1, lens[i], /*past=*/0)) return rc;
+        if (int rc = issue_pass(c, rows[i], 1, lens[i], /*past=*/0, /*verify=*/false, sc)) return rc;
       }
   }
   // lm_head of the ragged passes: the call's rows four at a time (tgx_forward's grouping where they are consecutive rows; else gathered into staging rows and scattered back)
@@ -1255,7 +1293,9 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
     k += real;
   }
   for (size_t k = 0; k < joint.size(); k++) launch_add_pos(c, c->rows[(size_t)rows[joint[k]]].pos, lens[joint[k]]);
+  if (sc) if (int rc = score_read_back(c, sc)) return rc;
   if (int rc = finish_pass(c)) return rc;
+  if (sc && sc->n_score >= 1) c->score_last_form = sc_rt == ROUTE_TILED ? 1 : 2;      // (a call of one position scored nothing: the option keeps its value)
   for (int i = 0; i < n; i++) {
     c->batch = std::max(c->batch, rows[i] + 1);
     row_admitted(c, rows[i], lens[i]);
@@ -1352,8 +1392,7 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
 
 // ---- tgx_extend_row / tgx_truncate_row (include/tgx.h): a live row grows by several positions in one pass, or is rolled back.  The pass is issue_pass's one-row pass
 // with the row's real length as `past` (every route takes it); the row then stands as tgx_forward_row leaves one.  Every check comes before anything changes.
-int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
-  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+static int extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq, ScoreCall* sc) {      // sc (tgx_score_row): the pass also scores its positions
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "extend before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
@@ -1377,10 +1416,14 @@ int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   }
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_extend_ws(c, seq, (int)past)) return rc;
+  const PrefillRoute sc_rt = prefill_route(c, seq, seq);
+  if (sc) if (int rc = score_prepare(c, sc, sc_rt, row)) return rc;
   (void)kv_ensure_blocks(c, row, past + seq);      // cannot fail: counted above
   HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)seq * 8, hipMemcpyHostToDevice, c->stream));
-  if (int rc = issue_pass(c, row, 1, seq, (int)past)) return rc;
+  if (int rc = issue_pass(c, row, 1, seq, (int)past, /*verify=*/false, sc)) return rc;
+  if (sc) if (int rc = score_read_back(c, sc)) return rc;
   if (int rc = finish_pass(c)) return rc;
+  if (sc && sc->n_score >= 1) c->score_last_form = sc_rt == ROUTE_TILED ? 1 : 2;      // (a call of one position scored nothing: the option keeps its value)
   row_admitted(c, row, (int)(past + seq), /*keep_lp_count=*/true);         // no current token, a fresh stop state (a finished row runs again), the sampler settings kept
   refresh_longest(c);
   c->have_logits = true;
@@ -1388,10 +1431,41 @@ int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
   return TGX_OK;
 }
 
+int tgx_extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
+  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  return extend_row(c, row, ids, seq, nullptr);
+}
+
+// ---- tgx_score_row (include/tgx.h): tgx_forward_row (an empty row) or tgx_extend_row (a row that holds a sequence) — the same checks in the same order, the same pass,
+// the same row state afterwards — plus the log-probability of every supplied token, computed behind the pass (issue_pass) and read back once.  The call's own
+// argument checks come first; nothing is recorded in the row's logprobs ring
+int tgx_score_row(tgx_ctx* c, int row, const int64_t* ids, int seq, int top_n, float* out_lp, int32_t* out_top_ids, float* out_top_lp) {
+  if (!c || !ids) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (top_n < 0 || top_n > TGX_MAX_LOGPROBS) return set_err(c, TGX_ERR_INVALID, "top_n %d out of range [0,%d]", top_n, TGX_MAX_LOGPROBS);
+  if (seq > 1 && !out_lp) return set_err(c, TGX_ERR_INVALID, "null out_lp for %d scored positions", seq - 1);
+  ScoreCall sc;
+  sc.top_n = top_n; sc.n_score = std::max(0, seq - 1);
+  const size_t n = (size_t)sc.n_score, L = TGX_MAX_LOGPROBS;
+  const bool tops = out_top_ids || out_top_lp;
+  std::vector<uint32_t> host;
+  if (c->finalized && seq <= c->d.max_ctx) {
+    host.resize(tops ? n * (1 + 2 * L) : n);
+    sc.host = host.data(); sc.host_bytes = host.size() * 4;
+  } else sc.n_score = 0;      // (the pass is refused below)
+  const bool holds = c->finalized && row >= 0 && row < c->batch && !c->row_host[(size_t)row].idle && c->row_host[(size_t)row].past >= 1;
+  const int32_t r = row, s = seq;
+  const int rc = holds ? extend_row(c, row, ids, seq, &sc) : admit_rows(c, 1, &r, ids, &s, /*may_join=*/false, &sc);
+  if (rc || !n) return rc;
+  std::memcpy(out_lp, host.data(), n * 4);
+  if (out_top_ids) std::memcpy(out_top_ids, host.data() + n, n * L * 4);
+  if (out_top_lp) std::memcpy(out_top_lp, host.data() + n + n * L, n * L * 4);
+  return TGX_OK;
+}
+
 // ---- tgx_verify_row (include/tgx.h): greedy speculative decoding.  ONE causal pass — tgx_extend_row's, on whatever route it takes — over the row's current token
 // and the draft, with the logits of every position (issue_pass's verify form); ONE accept launch (kernels/verify.h) then takes the draft's matching prefix and
 // leaves the row as that many greedy decode steps would.  Every check comes before anything changes; the host follows the device's record afterwards.
-static int ensure_verify_ws(tgx_ctx* c) {
+static int ensure_verify_ws(tgx_ctx* c) {      // (tgx_score_row's group form holds it as well)
   if (c->vf_rec) return TGX_OK;
   const size_t R = tgx_ctx::VERIFY_ROWS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
   int rc;
@@ -1821,6 +1895,9 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "act.round16")) { *out_value = c->act16; return TGX_OK; }
   if (!strcmp(key, "kv.budget_tokens")) { *out_value = c->kv_budget_tokens; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { *out_value = c->extend_attn_splits; return TGX_OK; }
+  if (!strcmp(key, "score.rows")) { *out_value = c->score_rows; return TGX_OK; }
+  if (!strcmp(key, "score.vocab_chunk")) { *out_value = c->score_vocab_chunk; return TGX_OK; }
+  if (!strcmp(key, "score.last_form")) { *out_value = c->score_last_form; return TGX_OK; }      // read-only: the form of the last tgx_score_row that scored a position (0 none yet, 1 matrix cores, 2 by groups)
   if (!strcmp(key, "weights.packed")) { *out_value = c->weights_packed; return TGX_OK; }
   if (!strcmp(key, "weights.packed_classes")) { *out_value = c->packed_classes; return TGX_OK; }
   if (!strcmp(key, "weights.packed_matrices")) { *out_value = c->packed_matrices; return TGX_OK; }        // read-only, after tgx_finalize: matrices stored packed ...
@@ -1895,6 +1972,8 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "decode.mfma_min_batch")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "decode.mfma_min_batch must be >= 1"); c->decode_mfma_min = value; return TGX_OK; }
   if (!strcmp(key, "debug.profile_same_layer")) { c->prof_same_layer = value; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "extend.attn_splits is -1 (automatic), 0 (never) or a split count"); c->extend_attn_splits = value; return TGX_OK; }
+  if (!strcmp(key, "score.rows")) { if (value < 64 || value % 64) return set_err(c, TGX_ERR_INVALID, "score.rows is a positive multiple of 64"); c->score_rows = value; return TGX_OK; }
+  if (!strcmp(key, "score.vocab_chunk")) { if (value < 1024 || value % 1024) return set_err(c, TGX_ERR_INVALID, "score.vocab_chunk is a positive multiple of 1024"); c->score_vocab_chunk = value; return TGX_OK; }
   if (!strcmp(key, "oproj.sliced")) { drop_step_graphs(c); c->oproj_sliced = value != 0; return TGX_OK; }
   if (!strcmp(key, "weights.packed") || !strcmp(key, "weights.packed_classes")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the packed copies are made there)", key);

@@ -103,6 +103,13 @@ struct Profiler {
 // where the QKV product of a one-sequence prefill may finish its rows (prefill.hip launch_prefill -> launch_gemm)
 struct QkvEpi { bf16_t *q_hi = nullptr, *q_lo = nullptr, *k = nullptr, *v = nullptr; int past = 0; const int* tbl = nullptr; };     // past: the position of the pass's first row (RoPE, cache append)
 
+// a scoring pass (tgx_score_row): positions [0, n_score) of the pass each score the id at the next position
+struct ScoreCall {
+  int top_n = 0, n_score = 0;
+  const long long* ids = nullptr;                     // the pass's ids on the device (the row's prompt buffer)
+  void* host = nullptr; size_t host_bytes = 0;        // where the call's read-back lands: lp [n] (| top ids | top lps)
+};
+
 namespace tgx { struct RgSeq; struct RgItem; }
 // one ragged prefill pass of tgx_forward_rows: prompt i at workspace rows [first[i], first[i] + lens[i]) into batch row rows[i], positions 0 .. lens[i] - 1.
 // abi.hip groups the prompts (the host fields, M, longest) and uploads the call's buffer; ragged_tables (prefill.hip) lays out and fills the device tables
@@ -322,6 +329,17 @@ struct tgx_ctx {
   float* lp_tile_max = nullptr;              // [rows][tiles]
   double* lp_tile_sum = nullptr;             // [rows][tiles]
   unsigned long long* lp_tile_keys = nullptr;   // [rows][tiles][TGX_MAX_LOGPROBS]
+  // ---- tgx_score_row (include/tgx.h; kernels/score.h).  Allocated by the first call that scores (a context that never does holds none of it).
+  // Options score.rows / score.vocab_chunk: the positions per group and the vocabulary columns per product of the matrix-core form (multiples of 64 / of the
+  // 1024-entry tile).  Measured (profiles/score_row.txt, Llama-3.2-1B seq 2048 top_n 20, ms per call, rows x chunk): 512 x 16384 17.05, 1024 x 8192 16.83,
+  // 1024 x 16384 16.68, 1024 x 32768 16.33, 2048 x 8192 16.47, 2048 x 16384 16.21, 2048 x 32768 16.25 (spread of a figure ~0.3) -> 2048 x 16384: a 128 MiB product
+  // beside a 64 MiB weight slice at hidden 2048 (whether the tile launch then reads the product from the Infinity Cache was not measured: no counter run).
+  // score.last_form (read-only): the last call that scored a position: 0 none yet, 1 matrix cores, 2 by groups of VERIFY_ROWS
+  int score_rows = 2048, score_vocab_chunk = 16384, score_last_form = 0;
+  float* sc_logits = nullptr; size_t sc_logits_bytes = 0;            // [group rows][chunk] the product of one vocabulary chunk
+  unsigned char* sc_part = nullptr; size_t sc_part_bytes = 0;        // one group's tile sums | keys | maxima | target values, laid out for sc_part_rows rows
+  int sc_part_rows = 0;
+  unsigned char* sc_out = nullptr; size_t sc_out_bytes = 0;          // the call's lp [n] | top ids [n][TGX_MAX_LOGPROBS] | top lps: one read-back
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -424,6 +442,10 @@ void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg);
 void launch_rope_kv_split_ragged(tgx_ctx* c, const tgx::RopeKvArgs& a, const RaggedPass& rg, long long layer_off);
 void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean);
 int prefill_set_attrs(tgx_ctx* c);
+int ensure_score_ws(tgx_ctx* c, int seq, bool tiled);          // tgx_score_row: the workspace of a pass of seq positions (tiled: the matrix-core form's product buffer as well)
+void launch_score_tiles(tgx_ctx* c, const ScoreCall& sc, const float* logits, long long stride, int col0, int width, int R, int pos0);   // the tile launch over [R][width] logits = entries [col0, col0 + width) of positions pos0 ..
+void launch_score_record(tgx_ctx* c, const ScoreCall& sc, int R, int pos0);                                                           // ... the group's records, behind the tile launches of the whole vocabulary
+void launch_score_tiled(tgx_ctx* c, const ScoreCall& sc);      // the matrix-core form over ws_x behind launch_prefill
 int extend_attn_splits(const tgx_ctx* c, int S, int past);   // key splits of a continuation pass's attention (0: the per-row prompt attention)
 int ensure_extend_ws(tgx_ctx* c, int S, int past);           // ... and their partials' workspace, before the pass is issued
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean);
@@ -439,5 +461,5 @@ bool decode_mfma_ok(const tgx_ctx* c);
 int ensure_skinny_ws(tgx_ctx* c, int rows);
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg);
 void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB)
-void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
+void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x = nullptr);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
 int skinny_set_attrs(tgx_ctx* c);

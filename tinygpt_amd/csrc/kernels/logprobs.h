@@ -55,28 +55,27 @@ __device__ __forceinline__ bool lp_active(const LpArgs& a, int y, int& top_n, in
   return true;
 }
 
-static __global__ __launch_bounds__(SAMP_WG) void lp_tile_kernel(const LpArgs a) {
+// one tile of one row of logits: lg[i] is entry i of the row, `wg` the tile (entries [SAMP_TILE wg, SAMP_TILE wg + SAMP_TILE) of V), the results into the tile's slots.
+// Shared by lp_tile_kernel and the scoring pass (score.h score_tile_kernel, where the row is a slice of a [rows][chunk] product)
+__device__ __forceinline__ void lp_tile_body(const float* lg, const int V, const int wg, const int top_n, float* out_max, double* out_sum, unsigned long long* out_keys) {
   __shared__ float shf[4];
   __shared__ double shd[4];
   __shared__ unsigned long long s_keys[4 * LP_MAX], s_out[LP_MAX];
-  const int y = blockIdx.y, wg = blockIdx.x, tid = threadIdx.x;
-  int top_n, tok;
-  if (!lp_active(a, y, top_n, tok)) return;
-  const float* lg = a.logits + (size_t)y * a.logits_stride;
+  const int tid = threadIdx.x;
   const int base = (wg * SAMP_WG + tid) * SAMP_EPT;
   float v[SAMP_EPT];
-  if (base + SAMP_EPT <= a.V && ((reinterpret_cast<size_t>(lg + base) & 15) == 0)) {
+  if (base + SAMP_EPT <= V && ((reinterpret_cast<size_t>(lg + base) & 15) == 0)) {
     const f32x4 q = *reinterpret_cast<const f32x4*>(lg + base);
     v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
   } else {
 #pragma unroll
-    for (int j = 0; j < SAMP_EPT; j++) v[j] = base + j < a.V ? lg[base + j] : -INFINITY;
+    for (int j = 0; j < SAMP_EPT; j++) v[j] = base + j < V ? lg[base + j] : -INFINITY;
   }
   unsigned long long key[SAMP_EPT];
   float m = -INFINITY;
 #pragma unroll
   for (int j = 0; j < SAMP_EPT; j++) {
-    const bool in = base + j < a.V;
+    const bool in = base + j < V;
     key[j] = in ? lp_key(v[j], base + j) : 0ull;
     if (in) m = fmaxf(m, v[j]);
   }
@@ -84,11 +83,10 @@ static __global__ __launch_bounds__(SAMP_WG) void lp_tile_kernel(const LpArgs a)
   double s = 0.0;
   if (tmax > -INFINITY) {                 // (a tile of -inf alone contributes nothing)
 #pragma unroll
-    for (int j = 0; j < SAMP_EPT; j++) s += base + j < a.V ? (double)expf(v[j] - tmax) : 0.0;
+    for (int j = 0; j < SAMP_EPT; j++) s += base + j < V ? (double)expf(v[j] - tmax) : 0.0;
   }
   s = samp_block_sum_d(s, shd);
-  const size_t t = (size_t)y * a.nwg + wg;
-  if (tid == 0) { a.tile_max[t] = tmax; a.tile_sum[t] = s; }
+  if (tid == 0) { *out_max = tmax; *out_sum = s; }
   if (top_n == 0) return;                 // (block-uniform)
   // the tile's first top_n entries: every wave takes the first top_n of its 256 by repeated maxima over the lanes (no barrier), the four lists are merged
   // by rank (the keys are distinct: they carry the index)
@@ -115,24 +113,25 @@ static __global__ __launch_bounds__(SAMP_WG) void lp_tile_kernel(const LpArgs a)
     }
   }
   __syncthreads();
-  if (tid < top_n) a.tile_keys[t * LP_MAX + tid] = s_out[tid];
+  if (tid < top_n) out_keys[tid] = s_out[tid];
 }
 
-static __global__ __launch_bounds__(SAMP_WG) void lp_record_kernel(const LpArgs a) {
+static __global__ __launch_bounds__(SAMP_WG) void lp_tile_kernel(const LpArgs a) {
+  const int y = blockIdx.y, wg = blockIdx.x;
+  int top_n, tok;
+  if (!lp_active(a, y, top_n, tok)) return;
+  const size_t t = (size_t)y * a.nwg + wg;
+  lp_tile_body(a.logits + (size_t)y * a.logits_stride, a.V, wg, top_n, a.tile_max + t, a.tile_sum + t, a.tile_keys + t * LP_MAX);
+}
+
+// the tiles of one row merged: lse = max + log sum exp(v - max), and (top_n > 0) the row's first top_n composite keys, returned in shared memory (entries
+// [0, top_n); 0 = none).  Shared by lp_record_kernel and the scoring pass (score.h score_record_kernel)
+__device__ __forceinline__ const unsigned long long* lp_merge(const float* tmaxs, const double* tsums, const unsigned long long* tkeys, const int nwg, const int top_n, double& lse) {
   __shared__ float shf[4];
   __shared__ double shd[4];
   __shared__ unsigned long long s_head[SAMP_MAX_WG], s_cand[LP_MAX * LP_MAX], s_out[LP_MAX];
   __shared__ int s_tile[LP_MAX];
-  const int y = blockIdx.y, tid = threadIdx.x, nwg = a.nwg;
-  int top_n, tok;
-  if (!lp_active(a, y, top_n, tok)) return;
-  LpRow* st = a.rec ? a.st : a.st + y;
-  const int count0 = __atomic_load_n(&st->count, __ATOMIC_RELAXED);       // (verify form: the last position to arrive moves it, behind every read)
-  const float* tmaxs = a.tile_max + (size_t)y * nwg;
-  const double* tsums = a.tile_sum + (size_t)y * nwg;
-  const unsigned long long* tkeys = a.tile_keys + (size_t)y * nwg * LP_MAX;
-  const float* lg = a.logits + (size_t)y * a.logits_stride;
-  const float vt = (unsigned)tok < (unsigned)a.V ? lg[tok] : -INFINITY;
+  const int tid = threadIdx.x;
   // the row maximum: the maximum of the tile maxima (the same value the lm_head's argmax partials hold)
   float m = -INFINITY;
   for (int t = tid; t < nwg; t += SAMP_WG) m = fmaxf(m, tmaxs[t]);
@@ -144,7 +143,7 @@ static __global__ __launch_bounds__(SAMP_WG) void lp_record_kernel(const LpArgs 
     if (tm > -INFINITY) s += tsums[t] * exp((double)tm - (double)mx);
   }
   s = samp_block_sum_d(s, shd);
-  const double lse = (double)mx + log(s);
+  lse = (double)mx + log(s);
   // the first top_n entries of the row lie in the top_n tiles with the largest heads, among those tiles' own first top_n: rank the heads, gather the
   // candidates of these tiles (<= top_n^2), rank them
   if (top_n > 0) {
@@ -170,6 +169,19 @@ static __global__ __launch_bounds__(SAMP_WG) void lp_record_kernel(const LpArgs 
     }
     __syncthreads();
   }
+  return s_out;
+}
+
+static __global__ __launch_bounds__(SAMP_WG) void lp_record_kernel(const LpArgs a) {
+  const int y = blockIdx.y, tid = threadIdx.x, nwg = a.nwg;
+  int top_n, tok;
+  if (!lp_active(a, y, top_n, tok)) return;
+  LpRow* st = a.rec ? a.st : a.st + y;
+  const int count0 = __atomic_load_n(&st->count, __ATOMIC_RELAXED);       // (verify form: the last position to arrive moves it, behind every read)
+  const float* lg = a.logits + (size_t)y * a.logits_stride;
+  const float vt = (unsigned)tok < (unsigned)a.V ? lg[tok] : -INFINITY;
+  double lse;
+  const unsigned long long* s_out = lp_merge(a.tile_max + (size_t)y * nwg, a.tile_sum + (size_t)y * nwg, a.tile_keys + (size_t)y * nwg * LP_MAX, nwg, top_n, lse);
   LpRecord* out = a.ring + (a.rec ? (size_t)0 : (size_t)y * LP_RING) + (size_t)((unsigned)(count0 + (a.rec ? y : 0)) % (unsigned)LP_RING);
   if (tid < LP_MAX) {
     const unsigned long long k = tid < top_n ? s_out[tid] : 0ull;

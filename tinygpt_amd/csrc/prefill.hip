@@ -8,6 +8,7 @@
 #include "kernels/attn_prefill_dma.h"
 #include "kernels/attn_extend.h"
 #include "kernels/gemm_f32.h"
+#include "kernels/score.h"
 
 bool prefill_shapes_ok(const tgx_model_desc& d) {
   return d.hidden % 64 == 0 && (d.heads * d.head_dim) % 64 == 0 && d.inter % 64 == 0;
@@ -544,6 +545,77 @@ static void prefill_pass(tgx_ctx* c, int row0, int NB, int S, int past, const Ra
 }
 void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past) { prefill_pass(c, row0, NB, S, past, nullptr); }
 void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg) { prefill_pass(c, 0, 0, 0, 0, &rg); }
+
+// ---- tgx_score_row (include/tgx.h; kernels/score.h): every position's log-probability behind a prompt pass.
+// Workspace, all of it through dev_grow and none of it seq x V: the tile partials and target values of one group of positions, the call's output arrays
+// (lp | top ids | top lps: ONE read-back) and, for the matrix-core form, the [group rows][vocabulary chunk] fp32 product
+static int score_tiles(const tgx_ctx* c) { return (c->d.vocab + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE; }
+static int score_chunk(const tgx_ctx* c) { return std::min(c->score_vocab_chunk, score_tiles(c) * tgx::SAMP_TILE); }
+int ensure_score_ws(tgx_ctx* c, int seq, bool tiled) {
+  const size_t n = (size_t)std::max(0, seq - 1), T = (size_t)score_tiles(c);
+  if (!n) return TGX_OK;
+  if (T > (size_t)tgx::SAMP_MAX_WG) return set_err(c, TGX_ERR_UNSUPPORTED, "vocabulary %d exceeds the sampler's %d entries", c->d.vocab, tgx::SAMP_MAX_WG * tgx::SAMP_TILE);
+  const size_t rows = tiled ? std::min<size_t>((size_t)c->score_rows, n) : (size_t)tgx_ctx::VERIFY_ROWS;
+  int rc;
+  if ((rc = dev_grow(c, &c->sc_part, &c->sc_part_bytes, rows * T * (8 + 8 * tgx::LP_MAX + 4) + rows * 4))) return rc;
+  if ((rc = dev_grow(c, &c->sc_out, &c->sc_out_bytes, n * (1 + 2 * (size_t)tgx::LP_MAX) * 4))) return rc;
+  if (tiled && (rc = dev_grow(c, &c->sc_logits, &c->sc_logits_bytes, rows * (size_t)score_chunk(c) * 4))) return rc;
+  c->sc_part_rows = (int)rows;
+  return TGX_OK;
+}
+static tgx::ScoreArgs score_args(tgx_ctx* c, const ScoreCall& sc, int pos0) {
+  const size_t R = (size_t)c->sc_part_rows, T = (size_t)score_tiles(c), n = (size_t)sc.n_score;
+  tgx::ScoreArgs a{};
+  a.V = c->d.vocab; a.nwg = (int)T; a.top_n = sc.top_n; a.ids = sc.ids; a.pos0 = pos0; a.n_score = sc.n_score;
+  a.tile_sum = reinterpret_cast<double*>(c->sc_part);
+  a.tile_keys = reinterpret_cast<unsigned long long*>(c->sc_part + R * T * 8);
+  a.tile_max = reinterpret_cast<float*>(c->sc_part + R * T * (8 + 8 * tgx::LP_MAX));
+  a.tgt = a.tile_max + R * T;
+  a.out_lp = reinterpret_cast<float*>(c->sc_out); a.out_ids = reinterpret_cast<int*>(a.out_lp + n); a.out_top_lp = a.out_lp + n + n * tgx::LP_MAX;
+  return a;
+}
+// the tile launch over a block of R positions from pos0: `width` vocabulary entries from col0 (a multiple of the tile) per position, `stride` floats apart
+void launch_score_tiles(tgx_ctx* c, const ScoreCall& sc, const float* logits, long long stride, int col0, int width, int R, int pos0) {
+  if (R > c->sc_part_rows || col0 % tgx::SAMP_TILE) { c->launch_fault = "score: a block the workspace was not sized for"; return; }
+  tgx::ScoreArgs a = score_args(c, sc, pos0);
+  a.logits = logits; a.stride = stride; a.col0 = col0;
+  hipLaunchKernelGGL(tgx::score_tile_kernel, dim3((width + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE, R), dim3(tgx::SAMP_WG), 0, c->stream, a);
+}
+// ... and, behind the tile launches of all the vocabulary, the group's records
+void launch_score_record(tgx_ctx* c, const ScoreCall& sc, int R, int pos0) {
+  if (R > c->sc_part_rows) { c->launch_fault = "score: a block the workspace was not sized for"; return; }
+  const tgx::ScoreArgs a = score_args(c, sc, pos0);
+  hipLaunchKernelGGL(tgx::score_record_kernel, dim3(1, R), dim3(tgx::SAMP_WG), 0, c->stream, a);
+}
+// The matrix-core form, behind prefill_pass over ws_x (one sequence): groups of <= score.rows positions; per group the final norm into 16-bit terms, then per
+// vocabulary chunk ONE product against that slice of the lm_head rows (the plain matrix; `embed` when tied) and the tile launch over it.  The product is pinned to
+// ONE kernel form — gemm_dma_kernel, 128-row tiles, unsplit K — called directly, not through launch_gemm's tile-count heuristics: a logit is the same K-ordered
+// sum (per k16 step the lo term, then the hi term) whatever the group and chunk sizes, so the scores are the same bits for every legal option value.
+// The weights stream once per group.
+void launch_score_tiled(tgx_ctx* c, const ScoreCall& sc) {
+  const tgx_model_desc& d = c->d;
+  const int H = d.hidden, V = d.vocab, chunk = score_chunk(c);
+  const bf16_t* W = reinterpret_cast<const bf16_t*>(d.tied ? c->embed : c->lm_head);
+  if (H % 64 != 0 || !c->sc_logits) { c->launch_fault = "score: the matrix-core form needs hidden % 64 == 0 and its workspace"; return; }
+  const bool one = c->act16 && c->ws_zero;
+  const size_t lds = tgx::gemm_dma_lds_bytes(2, false, 32, 2);
+  for (int g0 = 0; g0 < sc.n_score; g0 += c->sc_part_rows) {
+    const int R = std::min(c->sc_part_rows, sc.n_score - g0);
+    float* x = c->ws_x + (size_t)g0 * H;
+    if (c->gpt2) { TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL((tgx::norm_rows_kernel<DT, 1, 1>), dim3(R), dim3(256), 0, c->stream, (const float*)x, (const void*)c->final_norm, (const void*)c->final_norm_b, d.norm_eps, H, (float*)nullptr, c->ws_ah, c->ws_al, (bf16_t*)nullptr)) }
+    else { TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::rmsnorm_split_kernel<DT>, dim3(R), dim3(256), 0, c->stream, x, (const bf16_t*)c->final_norm, d.norm_eps, H, c->ws_ah, c->ws_al, (bf16_t*)nullptr, (const float*)nullptr, 0, 0LL, (const bf16_t*)nullptr, 0)) }
+    for (int n0 = 0; n0 < V; n0 += chunk) {
+      const int N = std::min(chunk, V - n0);
+      tgx::GemmArgs g{};
+      g.A_hi = c->ws_ah; g.A_lo = one ? c->ws_zero : c->ws_al; g.A_lo2 = nullptr;
+      g.B = W + (size_t)n0 * H; g.bias = nullptr; g.C = c->sc_logits; g.M = R; g.N = N; g.K = H; g.ldc = chunk; g.three_from = 0;
+      const dim3 grid((N + tgx::GBN - 1) / tgx::GBN, (R + 127) / 128), blk(256);
+      TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL((tgx::gemm_dma_kernel<DT, tgx::GEMM_STORE, 2, 32, 2>), grid, blk, lds, c->stream, g))
+      launch_score_tiles(c, sc, c->sc_logits, chunk, n0, N, R, g0);
+    }
+    launch_score_record(c, sc, R, g0);
+  }
+}
 
 // dynamic LDS sizes of the tiled GEMMs
 int prefill_set_attrs(tgx_ctx* c) {

@@ -433,11 +433,11 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
 
 // tgx_verify_row: the logits of every position of a skinny pass.  ws_x holds the M final residual rows; model.norm's 16-bit terms come from the row-wise launch and
 // the product is the batched decode step's lm_head (terms form), ONE pass over the weights for all M rows, then the rows' argmax partials
-void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx) {
+void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x) {      // x: the M hidden rows (default: the first M of ws_x)
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, V = d.vocab;
   const ebyte* W = d.tied ? c->embed : c->lm_head;
-  launch_norm_terms(c, c->ws_x, c->final_norm, M, H, 0);
+  launch_norm_terms(c, x ? x : c->ws_x, c->final_norm, M, H, 0);
   if (ksplit_ok(c, M, V, H)) {
     launch_ksplit(c, tgx::GEMM_STORE, W, logits, V, M, V, H);
   } else {

@@ -80,6 +80,7 @@ ABI = {
     "decode_rows": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "set_row_logprobs": (c_int, [c_void_p, c_int, c_int]),
     "read_row_logprobs": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
+    "score_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, c_int, POINTER(c_float), POINTER(c_int32), POINTER(c_float)]),
     "context_size": (c_int64, [c_void_p]),
     "num_layers": (c_int32, [c_void_p]),
     "last_error": (c_char_p, [c_void_p]),
@@ -347,6 +348,19 @@ class Model:
         self._check(self.be.read_row_logprobs(self._ctx, row, n, lp.ctypes.data_as(POINTER(c_float)), ids.ctypes.data_as(POINTER(c_int32)),
                                               tlp.ctypes.data_as(POINTER(c_float)), tn.ctypes.data_as(POINTER(c_int32))))
         return lp[:n], ids[:n], tlp[:n], tn[:n]
+
+    def score_row(self, row: int, ids, top_n: int = 0):
+        """tgx_forward_row (an empty row) or tgx_extend_row (a row that holds a sequence) of `ids`, plus the log-probability of every supplied token (include/tgx.h
+        tgx_score_row): (lp [n], top_ids [n][TGX_MAX_LOGPROBS], top_lp likewise), n = len(ids) - 1; lp[i] is ids[i + 1]'s under position i's distribution"""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        n = max(len(ids) - 1, 0)
+        lp = np.empty(n, np.float32)
+        top_ids = np.empty((n, MAX_LOGPROBS), np.int32)
+        top_lp = np.empty((n, MAX_LOGPROBS), np.float32)
+        self._check(self.be.score_row(self._ctx, row, ids.ctypes.data_as(POINTER(c_int64)), len(ids), top_n, lp.ctypes.data_as(POINTER(c_float)),
+                                      top_ids.ctypes.data_as(POINTER(c_int32)), top_lp.ctypes.data_as(POINTER(c_float))))
+        self.batch = max(self.batch, row + 1)
+        return lp, top_ids, top_lp
 
     @property
     def past_length(self) -> int:

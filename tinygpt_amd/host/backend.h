@@ -50,6 +50,8 @@ struct Backend {
   int (*set_row_sampler)(tgx_ctx*, int, const tgx_sampler_cfg*, uint64_t) = nullptr;
   int (*set_row_logprobs)(tgx_ctx*, int, int) = nullptr;
   int (*read_row_logprobs)(tgx_ctx*, int, int, float*, int32_t*, float*, int32_t*) = nullptr;
+  // scoring a supplied sequence (optional: GPTEngine::score needs it)
+  int (*score_row)(tgx_ctx*, int, const int64_t*, int, int, float*, int32_t*, float*) = nullptr;
 
   bool open(const std::string& path, const std::string& prefix) {
     // RTLD_NODELETE: the shim's runtime owns threads (HIP's signal/event workers; libgomp's team under the CPU oracle) that
@@ -72,6 +74,7 @@ struct Backend {
     TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
     TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
+    TGXH_BIND(score_row, false);
 #undef TGXH_BIND
     return ok;
   }

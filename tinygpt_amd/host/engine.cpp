@@ -98,6 +98,45 @@ bool GPTEngine::prefillReusing(const std::vector<int64_t>& ids) {
   return true;
 }
 
+// ---- GPTEngine::score (include/tgx.h tgx_score_row): one prefill pass over the sequence on row 0 of a reset cache
+double ScoreOutput::perplexity() const {
+  if (logprobs.empty()) return 0.0;
+  double s = 0.0;
+  for (float v : logprobs) s += (double)v;
+  return std::exp(-s / (double)logprobs.size());
+}
+
+ScoreOutput GPTEngine::score(const std::vector<int32_t>& ids, int topN) {
+  ScoreOutput out;
+  if (!prepared_ || ids.empty()) { fail("score: engine not prepared or empty sequence"); return out; }
+  if (!be_.score_row) { fail("score: the device shim lacks tgx_score_row"); return out; }
+  if (topN < 0 || topN > TGX_MAX_LOGPROBS) { fail("score: at most " + std::to_string(TGX_MAX_LOGPROBS) + " alternatives per token"); return out; }
+  const size_t keep = (size_t)std::min<int64_t>((int64_t)ids.size(), contextSize());      // beyond the context: the tail, like a prompt
+  out.tokenIds.assign(ids.end() - (std::ptrdiff_t)keep, ids.end());
+  out.dropped = (int64_t)(ids.size() - keep);
+  const std::vector<int64_t> ids64(out.tokenIds.begin(), out.tokenIds.end());
+  const size_t n = keep - 1, L = TGX_MAX_LOGPROBS;
+  std::vector<float> lp(n), tlp(n * L);
+  std::vector<int32_t> tid(n * L);
+  be_.reset_cache(model_.ctx);
+  cached_.clear(); lastReused_ = 0;
+  const int rc = be_.score_row(model_.ctx, 0, ids64.data(), (int)keep, topN, lp.data(), tid.data(), tlp.data());
+  if (rc != TGX_OK) fail(std::string("score_row: ") + be_.last_error(model_.ctx));
+  be_.reset_cache(model_.ctx);      // as reconfigure leaves it: the next generate call prefills from an empty cache
+  if (rc != TGX_OK) return out;
+  out.topLogprobs = topN;
+  out.logprobs = std::move(lp);
+  for (size_t i = 0; i < n; i++)
+    for (int k = 0; k < topN; k++) { out.topIds.push_back(tid[i * L + (size_t)k]); out.topLogprobValues.push_back(tlp[i * L + (size_t)k]); }
+  out.ok = true;
+  return out;
+}
+
+ScoreOutput GPTEngine::score(const std::string& text, int topN) {
+  if (!tokenizerOk_) { fail("score: no tokenizer loaded (tokenizerDir / modelDir must hold tokenizer.json)"); return ScoreOutput{}; }
+  return score(tokenizer_.encode(text, true), topN);
+}
+
 // ---- GPTConfig::speculate: prompt-lookup drafts verified in one pass (spec_draft.h, include/tgx.h tgx_verify_row)
 bool GPTEngine::speculateActive(int batch) const {
   const SamplerConfig& s = config_.samplerConfig;

@@ -87,6 +87,19 @@ struct SpecStats {
   int64_t producedHist[TGX_MAX_DRAFT + 2] = {};
 };
 
+// GPTEngine::score: the log-probability of tokenIds[i + 1] under the model's distribution after tokenIds[0 .. i], for i in [0, n - 1) — n - 1 values, one per
+// supplied token but the first — and, with topN >= 1, each position's topN most likely tokens as (id, logprob), most likely first (include/tgx.h tgx_score_row)
+struct ScoreOutput {
+  bool ok = false;
+  std::vector<int32_t> tokenIds;     // what was scored (a text after the tokenizer; a sequence beyond contextSize keeps its tail, like a prompt)
+  int64_t dropped = 0;               // tokens of the supplied sequence ahead of that tail: logprobs[i] belongs to the supplied token dropped + i + 1
+  int topLogprobs = 0;
+  std::vector<float> logprobs;       // [n - 1]
+  std::vector<int32_t> topIds;       // [n - 1][topLogprobs]
+  std::vector<float> topLogprobValues;
+  double perplexity() const;         // exp(-mean logprob); 0 with nothing scored
+};
+
 using GenerateCallback = std::function<bool(int32_t tokenId)>;   // return false to abort (GPTEngine.cpp:208-213)
 using TextCallback = std::function<bool(const std::string& chunk)>;   // the reference's GenerateCallback: complete UTF-8 only
 
@@ -105,6 +118,10 @@ class GPTEngine {
   // text entry points (need a tokenizer: tokenizerDir / modelDir must hold tokenizer.json + tokenizer_config.json)
   GPTOutput generateSync(const std::vector<std::string>& texts);                                   // :154-174 incl. encodeTexts :101-144
   GPTOutput generateAsync(const std::string& text, const TextCallback& callback);                  // :180-232 incl. decodeStream
+  // Not in the reference: score a supplied sequence in ONE prefill pass on row 0 of a reset cache, which it leaves empty again; generates nothing.  ok == false (lastError set): a backend
+  // without tgx_score_row, topN outside [0, TGX_MAX_LOGPROBS], an empty sequence, no tokenizer for the text form, or a failed call
+  ScoreOutput score(const std::vector<int32_t>& ids, int topN = 0);
+  ScoreOutput score(const std::string& text, int topN = 0);
   bool hasTokenizer() const { return tokenizerOk_; }
   Tokenizer& tokenizer() { return tokenizer_; }
   int32_t padTokenId() const;                                                                       // pad -> eos -> 0 (:108-114)

@@ -91,6 +91,27 @@ TGXE_API int64_t tgxe_last_logprobs(tgxe_engine* h, float* out_lp, int32_t* out_
   }
   return n;
 }
+// scoring a supplied sequence (GPTEngine::score; include/tgx.h tgx_score_row): out_lp [n - 1], out_top_ids / out_top_lp [n - 1][top_n] (either may be NULL).
+// Returns 0, or 1 when the call failed (tgxe_last_error); the text form also reports the ids it scored (up to cap) and their number
+TGXE_API int tgxe_score(tgxe_engine* h, const int32_t* ids, int n, int top_n, float* out_lp, int32_t* out_top_ids, float* out_top_lp) {
+  const tgxh::ScoreOutput r = h->e->score(std::vector<int32_t>(ids, ids + (ids && n > 0 ? n : 0)), top_n);
+  if (!r.ok) return 1;
+  if (out_lp) memcpy(out_lp, r.logprobs.data(), r.logprobs.size() * 4);
+  if (out_top_ids) memcpy(out_top_ids, r.topIds.data(), r.topIds.size() * 4);
+  if (out_top_lp) memcpy(out_top_lp, r.topLogprobValues.data(), r.topLogprobValues.size() * 4);
+  return 0;
+}
+TGXE_API int tgxe_score_text(tgxe_engine* h, const char* text, int top_n, int32_t* out_ids, int64_t cap, int64_t* out_n, float* out_lp, int32_t* out_top_ids, float* out_top_lp) {
+  const tgxh::ScoreOutput r = h->e->score(std::string(text ? text : ""), top_n);
+  if (!r.ok) return 1;
+  if (out_n) *out_n = (int64_t)r.tokenIds.size();
+  if ((int64_t)r.tokenIds.size() > cap) return 2;
+  if (out_ids) memcpy(out_ids, r.tokenIds.data(), r.tokenIds.size() * 4);
+  if (out_lp) memcpy(out_lp, r.logprobs.data(), r.logprobs.size() * 4);
+  if (out_top_ids) memcpy(out_top_ids, r.topIds.data(), r.topIds.size() * 4);
+  if (out_top_lp) memcpy(out_top_lp, r.topLogprobValues.data(), r.topLogprobValues.size() * 4);
+  return 0;
+}
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
   tgxh::SamplerConfig s; s.temperature = temperature; s.topK = top_k; s.topP = top_p; s.minP = min_p;

@@ -36,6 +36,9 @@ static void usage(const char* prog) {
           "  --pad-id <n>              left-pad id (default: eos_token_id of the model, else 0)\n"
           "  --seed <n>                sampler seed (default: 0)\n"
           "  --logprobs <n>            print every new token's log-probability and its n most likely alternatives (0 .. 20; default: off)\n"
+          "  --score                   generate nothing: print the log-probability of every prompt token but the first (position id lp, %%.9g; with --logprobs n the n most\n"
+          "                            likely alternatives as id:lp) and the prompt's perplexity, one prefill pass per prompt; of a prompt\n"
+          "                            longer than the context the last contextSize tokens are scored (positions count from the prompt's start)\n"
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n",
           prog);
 }
@@ -61,6 +64,19 @@ static void print_logprobs(const tgxh::GPTOutput& out) {
     }
 }
 
+// --score: per prompt one line per scored token — its position in the prompt, its id, its log-probability, then the alternatives — and `ppl exp(-mean lp)`
+static bool print_score(const tgxh::ScoreOutput& r) {
+  if (!r.ok) return false;
+  const size_t k = (size_t)r.topLogprobs;
+  for (size_t i = 0; i < r.logprobs.size(); i++) {
+    printf("%lld %d %.9g", (long long)(r.dropped + (int64_t)i + 1), r.tokenIds[i + 1], (double)r.logprobs[i]);      // the position in the prompt as supplied
+    for (size_t j = 0; j < k; j++) printf(" %d:%.9g", r.topIds[i * k + j], (double)r.topLogprobValues[i * k + j]);
+    printf("\n");
+  }
+  printf("ppl %.9g\n", r.perplexity());
+  return true;
+}
+
 int main(int argc, char** argv) {
   tgxh::GPTConfig cfg;
   cfg.maxNewTokens = 32;
@@ -69,7 +85,7 @@ int main(int argc, char** argv) {
   std::string dtype = "bf16", prompt_ids;
   long pad_id = -1;
   std::vector<std::string> text_prompts;
-  bool stream = false;
+  bool stream = false, score = false;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -87,6 +103,7 @@ int main(int argc, char** argv) {
     else if (a == "--prompt") text_prompts.push_back(next());
     else if (a == "--tokenizer") cfg.tokenizerDir = next();
     else if (a == "--stream") stream = true;
+    else if (a == "--score") score = true;
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
@@ -117,9 +134,21 @@ int main(int argc, char** argv) {
   }
   cfg.maxBatch = (int)std::max(std::max(prompts.size(), text_prompts.size()), kInputStrs.size());
 
+  const int score_top = std::max(0, cfg.logprobs);
+  if (score) cfg.logprobs = -1;      // (--logprobs n names the alternatives of --score: nothing is generated, nothing recorded)
   tgxh::GPTEngine engine(cfg);
   if (!engine.prepare()) { fprintf(stderr, "Prepare engine failed\n"); return 1; }
 
+  if (score) {
+    const bool texts = engine.hasTokenizer() && prompt_ids.empty();
+    if (texts && text_prompts.empty()) text_prompts = kInputStrs;
+    const size_t n = texts ? text_prompts.size() : prompts.size();
+    for (size_t b = 0; b < n; b++) {
+      if (!texts) for (auto& t : prompts[b]) if (t >= engine.desc().vocab) t = t % engine.desc().vocab;
+      if (!print_score(texts ? engine.score(text_prompts[b], score_top) : engine.score(prompts[b], score_top))) { fprintf(stderr, "score failed: %s\n", engine.lastError().c_str()); return 1; }
+    }
+    return 0;
+  }
   if (engine.hasTokenizer() && prompt_ids.empty()) {       // the reference's flow: texts in, texts out (main.cpp:97-114)
     if (text_prompts.empty()) text_prompts = kInputStrs;
     const auto t0 = std::chrono::steady_clock::now();

@@ -3,6 +3,7 @@
 
     python tools/verify_checkpoint.py --model-dir D --tokens N [--prompt-len S | --prompt-ids a,b,c] [--dtype bf16]
     python tools/verify_checkpoint.py --synthetic-peaked [--find-seed K] [--prompt-len 2048 --tokens 256]
+    python tools/verify_checkpoint.py --model-dir D --ppl --prompt-file ids.txt
 
 Both sides load the same tensors (a real HF directory: config.json + model.safetensors[.index.json], ModelLoader.cpp:25-89; or the peaked synthetic
 Llama-3.2-1B checkpoint of tinygpt_amd.synth), prefill the same prompt, then generate N tokens greedily, each from its OWN previous token
@@ -11,6 +12,9 @@ CPU path's top-2 gap; it exits 0 iff every id is equal and every distance is und
 that step was inside the tie band (4 x the distance) — a tie, not a defect — and stops (the contexts differ from there on).
 
 A checker, like tools/quick_parity.py: it is the only kind of code outside tests/ that touches oracle/ (the product never does, tests/test_abi.py).
+--ppl (HIP only): scores the prompt — --prompt-file (ids separated by commas or white space), --prompt-ids or the seeded one — in ONE prefill pass (include/tgx.h
+tgx_score_row), prints `tokens N  mean logprob M  ppl P` (P = exp(-mean log-probability of every token but the first)) and exits; sequences beyond the context are
+scored in windows of contextSize tokens that overlap by one, each window from an empty cache.
 --find-seed K (CPU only, no GPU needed): tries prompt seeds 1..K on the peaked synthetic checkpoint and reports those whose every top-2 gap clears --gap
 (tests/test_hip_parity_bar.py uses the first good one)."""
 import argparse
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=2048)
     ap.add_argument("--prompt-seed", type=int, default=8)
     ap.add_argument("--prompt-ids", default=None, help="comma-separated ids instead of the seeded uniform prompt")
+    ap.add_argument("--prompt-file", default=None, help="a file of token ids (commas or white space) instead of --prompt-ids")
+    ap.add_argument("--ppl", action="store_true", help="print the perplexity of the prompt on the HIP path (one scoring pass) and exit")
     ap.add_argument("--tol", type=float, default=1e-3)
     ap.add_argument("--gap", type=float, default=4e-3, help="--find-seed: the top-2 gap every step must clear")
     ap.add_argument("--find-seed", type=int, default=0)
@@ -57,12 +63,31 @@ def main():
         d.tied = False
         tensors = lambda: synth.synth_checkpoint(d, 1234, 0.02, peaked=True)
         strict = True
-    if args.prompt_ids:
+    if args.prompt_file:
+        prompt0 = np.array([int(t) for t in open(args.prompt_file).read().replace(",", " ").split()], dtype=np.int64)
+    elif args.prompt_ids:
         prompt0 = np.array([int(t) for t in args.prompt_ids.split(",")], dtype=np.int64)
     else:
         prompt0 = None
     S = len(prompt0) if prompt0 is not None else args.prompt_len
     d.max_batch = 1
+    if args.ppl:
+        from tinygpt_amd.ffi import Model, product_backend
+        d.max_ctx = min(d.max_ctx, max(S, 2)) if d.max_ctx else max(S, 2)
+        gpu = Model(d, product_backend())
+        for name, bits in tensors():
+            gpu.upload(name, bits, strict=strict)
+        gpu.finalize()
+        prompt = prompt0 if prompt0 is not None else synth.synth_prompt(d.vocab, S, args.prompt_seed)
+        lps = []
+        for at in range(0, max(len(prompt) - 1, 1), d.max_ctx - 1):
+            gpu.reset_cache()
+            lps.append(gpu.score_row(0, prompt[at:at + d.max_ctx])[0].astype(np.float64))
+        lp = np.concatenate(lps)
+        if not len(lp):
+            sys.exit("--ppl needs at least two tokens")
+        print(f"tokens {len(prompt)}  mean logprob {lp.mean():.9g}  ppl {np.exp(-lp.mean()):.9g}")
+        return 0
     d.max_ctx = min(d.max_ctx, S + args.tokens + 8) if d.max_ctx else S + args.tokens + 8
     if S + args.tokens > d.max_ctx:
         sys.exit(f"prompt + tokens = {S + args.tokens} exceeds contextSize {d.max_ctx}")
