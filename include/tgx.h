@@ -393,6 +393,42 @@ TGX_API int tgx_read_row_logprobs(tgx_ctx* ctx, int row, int n, float* out_lp /*
 TGX_API int tgx_score_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq, int top_n, float* out_lp /* [seq - 1] */,
                           int32_t* out_top_ids /* [seq - 1][TGX_MAX_LOGPROBS] */, float* out_top_lp /* [seq - 1][TGX_MAX_LOGPROBS] */);
 
+/* ---- per-row logit processors on the device: penalties and logit bias (additive to ABI 3) -------------------------------------------------------------------
+ * The completions protocol's `presence_penalty`, `frequency_penalty` and `logit_bias`, `repetition_penalty` of a checkpoint's generation_config.json, and "never
+ * emit this id" (a bias of -INFINITY: EOS suppressed for a minimum length, bad-word ids) — per row, read on the device, stepped in the same graphs as the sampler
+ * settings.  The raw logits are never modified: tgx_read_logits and the logprobs ring keep reading the MODEL's; tgx_read_probs returns the vector the draw used.
+ *
+ *   History           one 32-bit word per (row, token id): bit 31 "occurs in the prompt", bits 0 .. 30 n = the number of times the row produced the id (saturating).
+ *                     tgx_set_row_history REPLACES the row's words: clear, then set from the two lists (either may be empty with a null pointer).  The library never
+ *                     looks at prompt ids by itself.
+ *   Counting          in a tgx_decode_rows step an unfinished live row whose processors are on (any non-neutral penalty, or a non-empty bias list) first counts its
+ *                     current token — the one the step consumes.  Finished and retired rows neither count nor process (settings and a history stated for a retired
+ *                     row are kept and take effect with its admission, like the log-probability setting); tokens produced while a row's processors were
+ *                     off are not counted (a caller who switches penalties on mid-generation supplies the history).  tgx_extend_row and tgx_truncate_row keep the
+ *                     words; tgx_fork_row copies the source's words into each destination (its settings are untouched, like its sampler settings).
+ *   Formula           every operation rounded once to fp32, no fused multiply-add.  Per entry i with raw fp32 logit v:
+ *                       1. if prompt-bit or n > 0:  v = v > 0 ? v / repetition : v * repetition
+ *                       2. v = v - frequency * (float)n;  v = v - (n > 0 ? presence : 0)
+ *                       3. if i is in the row's bias list:  v = v + bias
+ *                     Temperature and the filters follow unchanged.
+ *   Where             tgx_decode_rows; tgx_sample_row (the row's settings, no counting step: the row has no current token then).  tgx_decode, tgx_sample and
+ *                     tgx_step_async ignore the processors, as they ignore every row setting.  tgx_verify_row on a row with a processor on is TGX_ERR_UNSUPPORTED
+ *                     (its accept rule compares raw argmaxes).
+ *   Settings          per row, kept across calls until changed, stream-ordered; the caller's arrays may be freed on return.  tgx_reset_row / tgx_reset_cache restore
+ *                     the neutral settings (repetition 1, presence 0, frequency 0), empty the bias list and clear the row's history.
+ *   Refusals          TGX_ERR_INVALID, nothing changes: a null cfg, a row outside [0, max_batch), repetition <= 0 or non-finite, a non-finite presence or frequency,
+ *                     n outside [0, TGX_MAX_LOGIT_BIAS], a bias id out of range or named twice, a bias that is NaN or +INFINITY (-INFINITY is legal, on fewer than
+ *                     vocab entries), a history id out of range.  Before tgx_finalize: TGX_ERR_STATE.
+ *   Cost              the first non-neutral setting or non-empty history of a context allocates the buffers (the words, a processed-logits slab [max_batch][vocab]);
+ *                     a context that never asks allocates nothing and runs exactly the launches it ran before, and neutral values on such a context are a no-op.
+ *                     One launch ahead of a step's publish while some row of the batch has a processor on (one more bit of the union that keys the per-row step
+ *                     graphs); the values are read on the device and changing them recaptures nothing. */
+#define TGX_MAX_LOGIT_BIAS 320
+typedef struct tgx_penalty_cfg { float repetition, presence, frequency; } tgx_penalty_cfg;  /* neutral: 1, 0, 0 */
+TGX_API int tgx_set_row_penalties(tgx_ctx* ctx, int row, const tgx_penalty_cfg* cfg);
+TGX_API int tgx_set_row_logit_bias(tgx_ctx* ctx, int row, int n, const int32_t* ids, const float* bias);  /* n = 0 clears */
+TGX_API int tgx_set_row_history(tgx_ctx* ctx, int row, const int64_t* prompt_ids, int n_prompt, const int64_t* produced_ids, int n_produced);
+
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);
 TGX_API int32_t tgx_num_layers(const tgx_ctx* ctx);

@@ -366,7 +366,7 @@ static void launch_kv_copy(tgx_ctx* c, long long n_tok, F&& rest) {
 // behind the steps that still read the old ones (no stream drain, no host buffer that has to outlive the call).  what: ROWQ_* bits
 // (ROWQ_LP: the row's log-probability setting; ROWQ_LPCOUNT: its record count back to 0.  `lp`: the rows' logprob state once it exists (kernels/logprobs.h) — its
 // `seen` word follows `produced` wherever this launch moves that)
-enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4, ROWQ_LP = 8, ROWQ_LPCOUNT = 16 };
+enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4, ROWQ_LP = 8, ROWQ_LPCOUNT = 16, ROWQ_PROC = 32 };      // (ROWQ_PROC: the logit processors' settings)
 struct RowReqUpdate { int row, what; tgx::RowReq v; };
 static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u, tgx::LpRow* lp) {
   if (threadIdx.x != 0) return;
@@ -379,6 +379,7 @@ static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u, tgx:
   }
   if (u.what & ROWQ_STATE) { q.produced = 0; q.finished = 0; }
   if (u.what & ROWQ_LP) q.lp = u.v.lp;
+  if (u.what & ROWQ_PROC) { q.proc = u.v.proc; q.n_bias = u.v.n_bias; q.repetition = u.v.repetition; q.presence = u.v.presence; q.frequency = u.v.frequency; }
   if (lp) {
     lp[u.row].seen = q.produced;
     if (u.what & ROWQ_LPCOUNT) { lp[u.row].count = 0; lp[u.row].arrive = 0; }
@@ -389,6 +390,7 @@ static_assert(tgx::ROW_MAX_STOP == TGX_MAX_STOP_IDS, "kernels/common.h RowReq");
 static tgx::RowReq row_req_default() {   // greedy, seed 0, no stop conditions
   tgx::RowReq q{};
   q.temperature = 0.f; q.top_k = 0; q.top_p = 1.f; q.min_p = 0.f; q.seed = 0; q.max_new = 0; q.n_stop = 0;
+  q.proc = 0; q.n_bias = 0; q.repetition = 1.f; q.presence = 0.f; q.frequency = 0.f;      // logit processors off
   return q;
 }
 // does the row record log-probabilities in the steps: its setting, unless it is retired (the setting is kept on the host and travels with the admission)
@@ -397,11 +399,12 @@ static void row_req_push(tgx_ctx* c, int row, int what) {
   RowReqUpdate u{};
   u.row = row; u.what = what; u.v = c->row_req_host[(size_t)row];
   if (!row_records(c, row)) u.v.lp = 0;      // a retired row rides along in the steps and counts what it publishes: on the device its setting reads "off" until it is refilled
+  if (!row_processed(c, row)) u.v.proc = 0;  // ... and so do its logit processors: a retired row neither counts into the history the caller stated for its next sequence nor processes
   hipLaunchKernelGGL(row_req_set_kernel, dim3(1), dim3(64), 0, c->stream, c->row_req, u, c->lp_rows);
 }
 static void row_req_reset(tgx_ctx* c, int row) {   // tgx_reset_row: the default settings and a fresh state
   c->row_req_host[(size_t)row] = row_req_default();
-  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE | ROWQ_LP | ROWQ_LPCOUNT);
+  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE | ROWQ_LP | ROWQ_LPCOUNT | ROWQ_PROC);
   c->row_host[(size_t)row].lp_count = 0;
 }
 static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
@@ -426,7 +429,7 @@ static int finished_row(const tgx_ctx* c) {   // a live row of the batch that fi
 // tgx_read_probs evaluates a row's final probabilities on demand: remember what its last sampled step was configured with
 static void note_sampled(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg) {
   const bool sampled = !is_greedy(&cfg);
-  for (int b = row0; b < row0 + R; b++) { c->row_host[(size_t)b].probs_cfg = cfg; c->row_host[(size_t)b].probs_ok = sampled; }
+  for (int b = row0; b < row0 + R; b++) { c->row_host[(size_t)b].probs_cfg = cfg; c->row_host[(size_t)b].probs_ok = sampled; c->row_host[(size_t)b].probs_proc = false; }
   c->have_probs = false;
   for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
 }
@@ -476,7 +479,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
     for (int b = 0; b < c->batch; b++)
       if (!c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin) { int rc = kv_ensure_blocks(c, b, c->row_host[(size_t)b].past + n); if (rc) return rc; }
   if (rows) {
-    for (int b = 0; b < c->batch; b++) note_sampled(c, b, 1, row_cfg(c, b));
+    for (int b = 0; b < c->batch; b++) { note_sampled(c, b, 1, row_cfg(c, b)); c->row_host[(size_t)b].probs_proc = (c->row_union & ROWU_PROC) != 0; }      // (a processed step passes every row through the processed slab)
   } else if (int rc = ensure_seed(c, cfg, seed)) return rc;
   if (!rows) note_sampled(c, 0, c->batch, cfg);
   if (decode_mfma_ok(c)) {   // the batched step's workspace must exist before the step is captured
@@ -1072,6 +1075,7 @@ int tgx_reset_cache(tgx_ctx* c) {
   HIP_OK(c, hipMemcpyAsync(c->row_req, c->row_req_host.data(), c->row_req_host.size() * sizeof(tgx::RowReq), hipMemcpyHostToDevice, c->stream));   // (synchronised below)
   if (c->slab_acc) HIP_OK(c, hipMemsetAsync(c->slab_acc, 0, (size_t)c->d.max_batch * c->d.hidden * 8, c->stream));
   if (c->lp_rows) HIP_OK(c, hipMemsetAsync(c->lp_rows, 0, (size_t)c->d.max_batch * sizeof(tgx::LpRow), c->stream));
+  if (c->proc_hist) HIP_OK(c, hipMemsetAsync(c->proc_hist, 0, (size_t)c->d.max_batch * c->d.vocab * sizeof(unsigned int), c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->past = 0;
   for (RowHost& r : c->row_host) { r.restart(0, /*idle=*/false, /*fin=*/0); r.lp_count = 0; }
@@ -1114,6 +1118,7 @@ int tgx_reset_row(tgx_ctx* c, int row) {
   HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream));     // stream-ordered behind the steps already enqueued
   kv_release_row(c, row);                                                     // paged KV: its blocks go back to the pool (a retired row rides along on the scratch block)
   row_req_reset(c, row);                                                      // tgx_decode_rows: default settings ...
+  if (c->proc_hist) HIP_OK(c, hipMemsetAsync(c->proc_hist + (size_t)row * c->d.vocab, 0, (size_t)c->d.vocab * sizeof(unsigned int), c->stream));      // ... and an empty history
   c->row_host[(size_t)row].restart(0, /*idle=*/row < c->batch, /*fin=*/0);    // ... not finished; a live slot becomes a retired one: the batch keeps stepping without it
   refresh_longest(c);
   return TGX_OK;
@@ -1123,7 +1128,7 @@ int tgx_reset_row(tgx_ctx* c, int row) {
 static void row_admitted(tgx_ctx* c, int row, int seq, bool keep_lp_count = false) {
   c->row_host[(size_t)row].restart(seq, /*idle=*/false, /*fin=*/0);
   // a new sequence: what the slot counted while it rode along retired is gone (its settings stay; the log-probability setting, held back while the row was retired, goes to the device)
-  row_req_push(c, row, ROWQ_STATE | ROWQ_LP | (keep_lp_count ? 0 : ROWQ_LPCOUNT));
+  row_req_push(c, row, ROWQ_STATE | ROWQ_LP | ROWQ_PROC | (keep_lp_count ? 0 : ROWQ_LPCOUNT));      // (the processors' settings likewise)
   if (!keep_lp_count) c->row_host[(size_t)row].lp_count = 0;                   // ... its log-probability records as well; tgx_extend_row keeps them
   c->row_host[(size_t)row].probs_ok = false;
 }
@@ -1379,6 +1384,9 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
     if (tail) src_blk = c->kv.block_at(src, n_full);
   }
   launch_kv_fork(c, src, n, dst_rows, dst_blk.data(), src_blk);
+  if (c->proc_hist)        // the same sequence, the same history: the source's words into every destination (the destinations' settings are untouched)
+    for (int i = 0; i < n; i++)
+      HIP_OK(c, hipMemcpyAsync(c->proc_hist + (size_t)dst_rows[i] * d.vocab, c->proc_hist + (size_t)src * d.vocab, (size_t)d.vocab * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
   if (int rc = finish_pass(c)) return rc;
   for (int i = 0; i < n; i++) {
     c->batch = std::max(c->batch, dst_rows[i] + 1);
@@ -1491,6 +1499,7 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
   if (!rh.tok) return set_err(c, TGX_ERR_STATE, "row %d has no current token: tgx_sample_row it first", row);
   const tgx_sampler_cfg cfg = row_cfg(c, row);
   if (!is_greedy(&cfg)) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
+  if (row_processed(c, row)) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d has a logit processor on (the accept rule compares raw argmaxes)", row);
   const int M = n_draft + 1;
   const long long past = rh.past;
   if (past + M > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, M, d.max_ctx);
@@ -1594,7 +1603,10 @@ int tgx_sample_row(tgx_ctx* c, int row, const tgx_sampler_cfg* cfg, uint64_t see
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_seed(c, *cfg, seed)) return rc;
   note_sampled(c, row, 1, *cfg);
-  launch_sample(c, row, 1, *cfg, /*advance_pos=*/false, /*log_step=*/false);
+  const bool processed = row_processed(c, row);      // the row's own processors, without the counting step: it has no current token yet
+  if (processed) launch_logit_proc(c, row, 1, /*step=*/false);
+  c->row_host[(size_t)row].probs_proc = processed;
+  launch_sample(c, row, 1, *cfg, /*advance_pos=*/false, /*log_step=*/false, processed);
   const bool records = row_records(c, row);
   if (records) launch_logprobs(c, row, 1, /*force=*/true);      // the first token after an admission, tgx_extend_row or tgx_fork_row
   HIP_OK(c, hipGetLastError());
@@ -1649,6 +1661,98 @@ int tgx_set_row_logprobs(tgx_ctx* c, int row, int top_n) {
   c->row_req_host[(size_t)row].lp = top_n + 1;
   row_req_push(c, row, ROWQ_LP);
   HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+// ---- per-row logit processors (include/tgx.h; kernels/logit_proc.h).  Every check comes before anything changes; the settings travel by value in stream-ordered
+// launches, like the sampler settings
+static void row_proc_refresh(tgx::RowReq& q) {      // proc: which processors are on (0: none — the row is copied through)
+  const bool pen = q.repetition != 1.f || q.presence != 0.f || q.frequency != 0.f;
+  q.proc = (pen ? tgx::PROC_PENALTY : 0) | (q.n_bias > 0 ? tgx::PROC_BIAS : 0);
+}
+
+int tgx_set_row_penalties(tgx_ctx* c, int row, const tgx_penalty_cfg* cfg) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!cfg) return set_err(c, TGX_ERR_INVALID, "null penalty configuration");
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_penalties before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (!std::isfinite(cfg->repetition) || !(cfg->repetition > 0.f)) return set_err(c, TGX_ERR_INVALID, "repetition penalty %g: a finite value > 0", (double)cfg->repetition);
+  if (!std::isfinite(cfg->presence) || !std::isfinite(cfg->frequency)) return set_err(c, TGX_ERR_INVALID, "presence / frequency penalty not finite");
+  const bool neutral = cfg->repetition == 1.f && cfg->presence == 0.f && cfg->frequency == 0.f;
+  if (neutral && !c->proc_part_idx) return TGX_OK;      // a context that never asked: nothing to switch off, nothing allocated
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = proc_alloc(c)) return rc;
+  tgx::RowReq& q = c->row_req_host[(size_t)row];
+  q.repetition = cfg->repetition; q.presence = cfg->presence; q.frequency = cfg->frequency;
+  row_proc_refresh(q);
+  row_req_push(c, row, ROWQ_PROC);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+struct RowBiasUpdate { int row, n; int ids[TGX_MAX_LOGIT_BIAS]; float val[TGX_MAX_LOGIT_BIAS]; };
+static __global__ void row_bias_set_kernel(int* ids, float* val, RowBiasUpdate u) {
+  for (int k = threadIdx.x; k < u.n; k += blockDim.x) { ids[(size_t)u.row * TGX_MAX_LOGIT_BIAS + k] = u.ids[k]; val[(size_t)u.row * TGX_MAX_LOGIT_BIAS + k] = u.val[k]; }
+}
+
+int tgx_set_row_logit_bias(tgx_ctx* c, int row, int n, const int32_t* ids, const float* bias) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_logit_bias before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (n < 0 || n > TGX_MAX_LOGIT_BIAS) return set_err(c, TGX_ERR_INVALID, "n %d out of range [0,%d]", n, TGX_MAX_LOGIT_BIAS);
+  if (n > 0 && (!ids || !bias)) return set_err(c, TGX_ERR_INVALID, "null ids / bias with n %d", n);
+  RowBiasUpdate u{};
+  u.row = row; u.n = n;
+  int banned = 0;
+  for (int k = 0; k < n; k++) {
+    if (ids[k] < 0 || ids[k] >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "bias id %d out of range [0,%d)", (int)ids[k], c->d.vocab);
+    if (std::isnan(bias[k]) || bias[k] == INFINITY) return set_err(c, TGX_ERR_INVALID, "bias of id %d is NaN or +inf", (int)ids[k]);
+    banned += bias[k] == -INFINITY;
+    u.ids[k] = ids[k]; u.val[k] = bias[k];
+  }
+  if (n > 1) {
+    std::vector<int32_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int k = 1; k < n; k++) if (sorted[(size_t)k] == sorted[(size_t)k - 1]) return set_err(c, TGX_ERR_INVALID, "bias id %d named twice", (int)sorted[(size_t)k]);
+  }
+  if (banned >= c->d.vocab) return set_err(c, TGX_ERR_INVALID, "a bias of -inf on all %d ids", c->d.vocab);
+  if (n == 0 && !c->proc_part_idx) return TGX_OK;       // a context that never asked: nothing to clear, nothing allocated
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = proc_alloc(c)) return rc;
+  if (n > 0) hipLaunchKernelGGL(row_bias_set_kernel, dim3(1), dim3(64), 0, c->stream, c->proc_bias_ids, c->proc_bias_val, u);
+  tgx::RowReq& q = c->row_req_host[(size_t)row];
+  q.n_bias = n;
+  row_proc_refresh(q);
+  row_req_push(c, row, ROWQ_PROC);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+int tgx_set_row_history(tgx_ctx* c, int row, const int64_t* prompt_ids, int n_prompt, const int64_t* produced_ids, int n_produced) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_history before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (n_prompt < 0 || n_produced < 0) return set_err(c, TGX_ERR_INVALID, "negative list length");
+  if ((n_prompt > 0 && !prompt_ids) || (n_produced > 0 && !produced_ids)) return set_err(c, TGX_ERR_INVALID, "null id list with a length > 0");
+  const int64_t V = c->d.vocab;
+  for (int i = 0; i < n_prompt; i++) if (prompt_ids[i] < 0 || prompt_ids[i] >= V) return set_err(c, TGX_ERR_INVALID, "history id out of range");
+  for (int i = 0; i < n_produced; i++) if (produced_ids[i] < 0 || produced_ids[i] >= V) return set_err(c, TGX_ERR_INVALID, "history id out of range");
+  if (n_prompt + n_produced == 0 && !c->proc_part_idx) return TGX_OK;      // a context that never asked: its rows' histories are empty
+  HIP_OK(c, hipSetDevice(c->device));
+  if (n_prompt + n_produced == 0) {         // clearing: a stream-ordered fill, no host buffer and nothing to wait for (as tgx_reset_row)
+    HIP_OK(c, hipMemsetAsync(c->proc_hist + (size_t)row * V, 0, (size_t)V * sizeof(unsigned int), c->stream));
+    return TGX_OK;
+  }
+  if (int rc = proc_alloc(c)) return rc;
+  // REPLACE: the row's words built here and copied in stream order behind the steps that still count into the old ones (the copy is waited for: the vector is this call's)
+  std::vector<unsigned int> words((size_t)V, 0u);
+  for (int i = 0; i < n_prompt; i++) words[(size_t)prompt_ids[i]] |= tgx::PROC_PROMPT_BIT;
+  for (int i = 0; i < n_produced; i++) {
+    unsigned int& w = words[(size_t)produced_ids[i]];
+    if ((w & tgx::PROC_COUNT_MASK) < tgx::PROC_COUNT_MASK) w++;
+  }
+  HIP_OK(c, hipMemcpyAsync(c->proc_hist + (size_t)row * V, words.data(), (size_t)V * sizeof(unsigned int), hipMemcpyHostToDevice, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
   return TGX_OK;
 }
 
@@ -1856,7 +1960,7 @@ int tgx_read_probs(tgx_ctx* c, float* out) {
   // a sampled step leaves its logits, thresholds and normalisers on the device, not the vector: evaluate it now (rows whose last step was greedy read as zeros)
   const size_t V = (size_t)c->d.vocab;
   for (int b = 0; b < c->batch; b++) {
-    if (c->row_host[(size_t)b].probs_ok) launch_probs(c, b, c->row_host[(size_t)b].probs_cfg);
+    if (c->row_host[(size_t)b].probs_ok) launch_probs(c, b, c->row_host[(size_t)b].probs_cfg, c->row_host[(size_t)b].probs_proc);
     else HIP_OK(c, hipMemsetAsync(c->rows[(size_t)b].probs, 0, V * 4, c->stream));
   }
   HIP_OK(c, hipGetLastError());

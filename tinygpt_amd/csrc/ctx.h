@@ -84,6 +84,7 @@ struct RowHost {        // host state of one batch row
   char fin = 0;         // the finish reason of the last tgx_decode_rows readback (0 running, 1 stop id, 2 max_new) — a finished row keeps its length, rides along without advancing and counts for neither `past` nor the context check
   int64_t lp_count = 0; // mirror of the row's device-side record counter (tgx_read_row_logprobs): records appended since the count was reset
   bool probs_ok = false; tgx_sampler_cfg probs_cfg{};   // the row's last sampled step was a non-greedy one, and its sampler configuration (tgx_read_probs evaluates the vector on demand)
+  bool probs_proc = false;   // ... and it drew from the processed logits (kernels/logit_proc.h): tgx_read_probs evaluates the vector from that slab
   // the slot starts over at `len` positions: no current token, its logits its own; what its last sampled step left (probs_ok, probs_cfg) stays
   void restart(int64_t len, bool idle_, char fin_) { past = len; tok = nologits = false; idle = idle_; fin = fin_; }
 };
@@ -340,6 +341,14 @@ struct tgx_ctx {
   unsigned char* sc_part = nullptr; size_t sc_part_bytes = 0;        // one group's tile sums | keys | maxima | target values, laid out for sc_part_rows rows
   int sc_part_rows = 0;
   unsigned char* sc_out = nullptr; size_t sc_out_bytes = 0;          // the call's lp [n] | top ids [n][TGX_MAX_LOGPROBS] | top lps: one read-back
+  // ---- per-row logit processors (include/tgx.h tgx_set_row_penalties / tgx_set_row_logit_bias / tgx_set_row_history; kernels/logit_proc.h).  Allocated by the first
+  // non-neutral setting or non-empty history (proc_alloc): a context that never asks holds none of it and runs the launches it ran before
+  unsigned int* proc_hist = nullptr;         // [max_batch][vocab] history words: bit 31 "in the prompt", bits 0 .. 30 times produced
+  int* proc_bias_ids = nullptr;              // [max_batch][TGX_MAX_LOGIT_BIAS]
+  float* proc_bias_val = nullptr;
+  float* proc_logits = nullptr;              // [max_batch][vocab] the processed logits of the rows' last processed step
+  float* proc_part_val = nullptr;            // [max_batch][ceil(vocab / 1024)] their per-tile (max, lowest index)
+  int* proc_part_idx = nullptr;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -420,11 +429,14 @@ bool attn_batch_on_mfma(const tgx_ctx* c, int R);
 void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true);   // combine = false: the caller's o_proj merges the split records
 int attn_set_attrs(tgx_ctx* c);
 // ---- sampler.hip (kernels/sampler.h)
-void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step);
-enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16, ROWU_LP = 32 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick; some row records log-probabilities
+void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step, bool processed = false);   // processed: from the processed logits (launch_logit_proc ran for these rows)
+enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16, ROWU_LP = 32, ROWU_PROC = 64 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick; some row records log-probabilities; some row has a logit processor on
 void launch_sample_rows(tgx_ctx* c, int row0, int R, int un);              // tgx_decode_rows: every row with its own settings (a decode step's sampler)
 int row_union_of(const tgx_ctx* c);
-void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg);
+void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);
+int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
+bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
+void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)
 int sampler_alloc(tgx_ctx* c);
 int logprobs_alloc(tgx_ctx* c);                                              // the rings, counters and tile partials, at first use
 void launch_logprobs(tgx_ctx* c, int row0, int R, bool force);             // behind a step's publish: the rows that record and produced a token (force: tgx_sample_row)

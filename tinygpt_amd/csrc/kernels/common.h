@@ -168,7 +168,14 @@ struct RowReq {
   int finished;                     // 0 running, 1 stop id, 2 max_new
   int lp;                           // per-token log-probabilities (kernels/logprobs.h; tgx_set_row_logprobs): 0 off — the zero-initialised state — else top_n + 1
   int stop[ROW_MAX_STOP];
+  // logit processors (kernels/logit_proc.h; tgx_set_row_penalties / tgx_set_row_logit_bias): proc 0 off — the zero-initialised state, the values below are then
+  // not looked at — else PROC_PENALTY | PROC_BIAS; n_bias: entries of the row's bias list
+  int proc, n_bias;
+  float repetition, presence, frequency;
+  int proc_pad;
 };
+enum { PROC_PENALTY = 1, PROC_BIAS = 2 };
+constexpr unsigned int PROC_PROMPT_BIT = 0x80000000u, PROC_COUNT_MASK = 0x7fffffffu;   // a history word (kernels/logit_proc.h): "occurs in the prompt" | times produced
 __device__ __forceinline__ bool row_req_greedy(const RowReq& q) {   // == is_greedy (Sampler.cpp:15-21)
   return !(q.temperature > 0.f || q.top_k > 0 || q.top_p < 1.f || q.min_p > 0.f);
 }

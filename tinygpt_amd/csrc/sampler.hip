@@ -5,14 +5,22 @@
 #include "ctx.h"
 #include "kernels/sampler.h"
 #include "kernels/logprobs.h"
+#include "kernels/logit_proc.h"
 #include <type_traits>
 
-static tgx::SampArgs samp_args(tgx_ctx* c, int row0, const tgx_sampler_cfg& cfg) {
+static int proc_tiles(const tgx_ctx* c) { return (c->d.vocab + tgx::PROC_TILE - 1) / tgx::PROC_TILE; }
+// processed: the rows' logits and maxima come from the processed slab and its partials (kernels/logit_proc.h; launch_logit_proc ran ahead)
+static tgx::SampArgs samp_args(tgx_ctx* c, int row0, const tgx_sampler_cfg& cfg, bool processed = false) {
   const int V = c->d.vocab;
   RowState& r = c->rows[(size_t)row0];
   tgx::SampArgs a{};
   a.logits = r.logits; a.logits_stride = V;
   a.part_val = r.part_val; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
+  if (processed) {
+    const int T = proc_tiles(c);
+    a.logits = c->proc_logits + (size_t)row0 * V;
+    a.part_val = c->proc_part_val + (size_t)row0 * T; a.part_stride = T; a.n_part = T;
+  }
   a.sc = c->samp_scratch + row0;
   a.probs_out = r.probs; a.probs_stride = V;
   a.V = V; a.idx_bits = 1;
@@ -24,9 +32,23 @@ static tgx::SampArgs samp_args(tgx_ctx* c, int row0, const tgx_sampler_cfg& cfg)
   return a;
 }
 
-void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step) {
-  if (is_greedy(&cfg)) { launch_finalize_greedy(c, row0, R, advance_pos, log_step); return; }
-  tgx::SampArgs a = samp_args(c, row0, cfg);
+// the finalize arguments of row `row` reading the processed partials instead of the lm_head's
+static void finalize_from_processed(tgx_ctx* c, tgx::FinalizeArgs& f, int row) {
+  const int T = proc_tiles(c);
+  f.part_val = c->proc_part_val + (size_t)row * T; f.part_idx = c->proc_part_idx + (size_t)row * T; f.n_part = T;
+}
+
+void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step, bool processed) {
+  if (is_greedy(&cfg)) {
+    if (!processed) { launch_finalize_greedy(c, row0, R, advance_pos, log_step); return; }
+    for (int b = row0; b < row0 + R; b++) {
+      tgx::FinalizeArgs f = make_finalize_args(c, b, advance_pos, log_step);
+      finalize_from_processed(c, f, b);
+      TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::finalize_greedy_kernel<DT>, dim3(1), dim3(256), 0, c->stream, f))
+    }
+    return;
+  }
+  tgx::SampArgs a = samp_args(c, row0, cfg, processed);
   const bool setK = cfg.top_k > 0, setP = cfg.top_p < 1.f, setM = cfg.min_p > 0.f;
   const int nwg = (a.V + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE;
   const dim3 grid(nwg, R), blk(tgx::SAMP_WG);
@@ -35,7 +57,7 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
     tgx::SampPickArgs pa{};
     pa.s = now;
     pa.nwg = nwg; pa.seed = c->seed_dev;
-    pa.fin = make_finalize_args(c, row0, advance_pos, log_step);
+    pa.fin = make_finalize_args(c, row0, advance_pos, log_step);      // (the pick publishes the token it drew: the argmax partials are not read)
     pa.x_stride = c->d.hidden;
     return pa;
   };
@@ -78,11 +100,15 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
 static void launch_sample_rows_sampled(tgx_ctx* c, int row0, int R, int un);
 void launch_sample_rows(tgx_ctx* c, int row0, int R, int un) {
   tgx::RowReq* req = c->row_req + row0;
+  // some row of the batch has a logit processor on: every row's logits pass through the processed slab (unprocessed rows are copied), and every consumer below but
+  // the log-probabilities — the MODEL's distribution — reads that slab and its partials
+  if (un & ROWU_PROC) launch_logit_proc(c, row0, R, /*step=*/true);
   if (un & ROWU_GREEDY) {
     tgx::FinalizeRowsArgs fa{};
     fa.f = make_finalize_args(c, row0, /*advance_pos=*/true, /*log_step=*/true);
     fa.f.req = req;
     fa.part_stride = c->lm_grid; fa.x_stride = c->d.hidden;
+    if (un & ROWU_PROC) { finalize_from_processed(c, fa.f, row0); fa.part_stride = proc_tiles(c); }
     TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::finalize_rows_kernel<DT, true>), dim3(R), dim3(256), 0, c->stream, fa))
   }
   if (un & (ROWU_K | ROWU_P | ROWU_M | ROWU_SUM)) launch_sample_rows_sampled(c, row0, R, un);
@@ -92,7 +118,7 @@ void launch_sample_rows(tgx_ctx* c, int row0, int R, int un) {
 static void launch_sample_rows_sampled(tgx_ctx* c, int row0, int R, int un) {
   tgx::RowReq* req = c->row_req + row0;
   const tgx_sampler_cfg none{0.f, 0, 1.f, 0.f};
-  tgx::SampArgs a = samp_args(c, row0, none);     // cfg fields, mx_ready and z_from_tail: per row on the device
+  tgx::SampArgs a = samp_args(c, row0, none, (un & ROWU_PROC) != 0);     // cfg fields, mx_ready and z_from_tail: per row on the device
   a.req = req;
   const int nwg = (a.V + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE;
   const dim3 grid(nwg, R), blk(tgx::SAMP_WG);
@@ -125,6 +151,7 @@ int row_union_of(const tgx_ctx* c) {
     const tgx::RowReq& q = c->row_req_host[(size_t)b];
     const bool K = q.top_k > 0, P = q.top_p < 1.f, M = q.min_p > 0.f, sampled = K || P || M || q.temperature > 0.f;
     if (row_records(c, b)) un |= ROWU_LP;
+    if (row_processed(c, b)) un |= ROWU_PROC;
     if (!sampled) { un |= ROWU_GREEDY; continue; }
     if (K) un |= ROWU_K;
     if (P) un |= ROWU_P;
@@ -136,11 +163,43 @@ int row_union_of(const tgx_ctx* c) {
 
 // tgx_read_probs: the final probability vector of row `row`'s last sampled step, evaluated from what that step left on the device (its logits, the
 // filters' thresholds, the normalisers) — the step itself never needs the vector
-void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg) {
-  tgx::SampArgs a = samp_args(c, row, cfg);
+void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed) {
+  tgx::SampArgs a = samp_args(c, row, cfg, processed);
   a.mx_ready = 0;
   const int nwg = (a.V + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE;
   hipLaunchKernelGGL(tgx::samp_sum_kernel<2>, dim3(nwg, 1), dim3(tgx::SAMP_WG), 0, c->stream, a);
+}
+
+// ---- per-row logit processors (kernels/logit_proc.h)
+static_assert(tgx::PROC_MAX_BIAS == TGX_MAX_LOGIT_BIAS && tgx::PROC_TILE == tgx::SAMP_TILE, "kernels/logit_proc.h");
+// does the row process its logits in the steps: its settings, unless it is retired (like the log-probability setting, they are kept on the host and travel with the admission)
+bool row_processed(const tgx_ctx* c, int row) { return c->row_req_host[(size_t)row].proc != 0 && !c->row_host[(size_t)row].idle; }
+
+int proc_alloc(tgx_ctx* c) {
+  if (c->proc_part_idx) return TGX_OK;       // the last of the six: set only when all of them exist
+  const size_t B = (size_t)c->d.max_batch, V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
+  int rc;
+  if ((rc = dev_alloc(c, &c->proc_hist, B * V)) || (rc = dev_alloc(c, &c->proc_bias_ids, B * tgx::PROC_MAX_BIAS)) || (rc = dev_alloc(c, &c->proc_bias_val, B * tgx::PROC_MAX_BIAS)) ||
+      (rc = dev_alloc(c, &c->proc_logits, B * V)) || (rc = dev_alloc(c, &c->proc_part_val, B * T)) || (rc = dev_alloc(c, &c->proc_part_idx, B * T))) {
+    // all or nothing: a later attempt starts over instead of allocating over live pointers (dev_free of a null pointer is a no-op)
+    dev_free(c, &c->proc_hist); dev_free(c, &c->proc_bias_ids); dev_free(c, &c->proc_bias_val); dev_free(c, &c->proc_logits); dev_free(c, &c->proc_part_val); dev_free(c, &c->proc_part_idx);
+    return rc;
+  }
+  HIP_OK(c, hipMemsetAsync(c->proc_hist, 0, B * V * sizeof(unsigned int), c->stream));
+  return TGX_OK;
+}
+
+void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step) {
+  if (!c->proc_part_idx) { c->launch_fault = "logit processors requested before their buffers exist"; return; }
+  const size_t V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
+  tgx::LogitProcArgs a{};
+  a.logits = c->rows[(size_t)row0].logits; a.logits_stride = (long long)V;
+  a.req = c->row_req + row0; a.tok = c->rows[(size_t)row0].tok;
+  a.hist = c->proc_hist + row0 * V;
+  a.bias_ids = c->proc_bias_ids + (size_t)row0 * tgx::PROC_MAX_BIAS; a.bias_val = c->proc_bias_val + (size_t)row0 * tgx::PROC_MAX_BIAS;
+  a.out = c->proc_logits + row0 * V; a.part_val = c->proc_part_val + row0 * T; a.part_idx = c->proc_part_idx + row0 * T;
+  a.V = (int)V; a.n_tile = (int)T; a.step = step ? 1 : 0;
+  hipLaunchKernelGGL(tgx::logit_proc_kernel, dim3((unsigned)T, (unsigned)R), dim3(tgx::PROC_WG), 0, c->stream, a);
 }
 
 // ---- per-token log-probabilities (kernels/logprobs.h)

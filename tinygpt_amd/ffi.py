@@ -45,6 +45,17 @@ class SamplerCfg(ctypes.Structure):
 GREEDY = SamplerCfg()
 
 
+class PenaltyCfg(ctypes.Structure):
+    """tgx_penalty_cfg; neutral: repetition 1, presence 0, frequency 0"""
+    _fields_ = [("repetition", c_float), ("presence", c_float), ("frequency", c_float)]
+
+    def __init__(self, repetition=1.0, presence=0.0, frequency=0.0):
+        super().__init__(repetition, presence, frequency)
+
+
+MAX_LOGIT_BIAS = 320     # TGX_MAX_LOGIT_BIAS
+
+
 class TgxError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {msg}")
@@ -81,6 +92,9 @@ ABI = {
     "set_row_logprobs": (c_int, [c_void_p, c_int, c_int]),
     "read_row_logprobs": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_int32), POINTER(c_float), POINTER(c_int32)]),
     "score_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, c_int, POINTER(c_float), POINTER(c_int32), POINTER(c_float)]),
+    "set_row_penalties": (c_int, [c_void_p, c_int, POINTER(PenaltyCfg)]),
+    "set_row_logit_bias": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
+    "set_row_history": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), c_int]),
     "context_size": (c_int64, [c_void_p]),
     "num_layers": (c_int32, [c_void_p]),
     "last_error": (c_char_p, [c_void_p]),
@@ -348,6 +362,29 @@ class Model:
         self._check(self.be.read_row_logprobs(self._ctx, row, n, lp.ctypes.data_as(POINTER(c_float)), ids.ctypes.data_as(POINTER(c_int32)),
                                               tlp.ctypes.data_as(POINTER(c_float)), tn.ctypes.data_as(POINTER(c_int32))))
         return lp[:n], ids[:n], tlp[:n], tn[:n]
+
+    # -- per-row logit processors (include/tgx.h tgx_set_row_penalties) --------------------------
+    def set_row_penalties(self, row: int, repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0):
+        cfg = PenaltyCfg(repetition, presence, frequency)
+        self._check(self.be.set_row_penalties(self._ctx, row, ctypes.byref(cfg)))
+        return self
+
+    def set_row_logit_bias(self, row: int, bias=None):
+        """bias: {id: value} or a sequence of (id, value) pairs; empty / None clears.  -inf bans an id"""
+        pairs = list(bias.items()) if isinstance(bias, dict) else list(bias or ())
+        ids = np.ascontiguousarray(np.asarray([p[0] for p in pairs], dtype=np.int32).reshape(-1))
+        val = np.ascontiguousarray(np.asarray([p[1] for p in pairs], dtype=np.float32).reshape(-1))
+        self._check(self.be.set_row_logit_bias(self._ctx, row, len(ids), ids.ctypes.data_as(POINTER(c_int32)) if len(ids) else None,
+                                               val.ctypes.data_as(POINTER(c_float)) if len(ids) else None))
+        return self
+
+    def set_row_history(self, row: int, prompt_ids=(), produced_ids=()):
+        """REPLACES the row's history words: the prompt bit of every id in prompt_ids, the produced count of every id in produced_ids"""
+        p = np.ascontiguousarray(np.asarray(list(prompt_ids), dtype=np.int64).reshape(-1))
+        g = np.ascontiguousarray(np.asarray(list(produced_ids), dtype=np.int64).reshape(-1))
+        self._check(self.be.set_row_history(self._ctx, row, p.ctypes.data_as(POINTER(c_int64)) if len(p) else None, len(p),
+                                            g.ctypes.data_as(POINTER(c_int64)) if len(g) else None, len(g)))
+        return self
 
     def score_row(self, row: int, ids, top_n: int = 0):
         """tgx_forward_row (an empty row) or tgx_extend_row (a row that holds a sequence) of `ids`, plus the log-probability of every supplied token (include/tgx.h

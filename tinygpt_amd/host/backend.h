@@ -50,6 +50,10 @@ struct Backend {
   int (*set_row_sampler)(tgx_ctx*, int, const tgx_sampler_cfg*, uint64_t) = nullptr;
   int (*set_row_logprobs)(tgx_ctx*, int, int) = nullptr;
   int (*read_row_logprobs)(tgx_ctx*, int, int, float*, int32_t*, float*, int32_t*) = nullptr;
+  // per-row logit processors (optional: a non-neutral SamplerConfig penalty or logit bias needs these three, and the per-row calls the logprobs path steps through)
+  int (*set_row_penalties)(tgx_ctx*, int, const tgx_penalty_cfg*) = nullptr;
+  int (*set_row_logit_bias)(tgx_ctx*, int, int, const int32_t*, const float*) = nullptr;
+  int (*set_row_history)(tgx_ctx*, int, const int64_t*, int, const int64_t*, int) = nullptr;
   // scoring a supplied sequence (optional: GPTEngine::score needs it)
   int (*score_row)(tgx_ctx*, int, const int64_t*, int, int, float*, int32_t*, float*) = nullptr;
 
@@ -74,6 +78,7 @@ struct Backend {
     TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
     TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
+    TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);
     TGXH_BIND(score_row, false);
 #undef TGXH_BIND
     return ok;

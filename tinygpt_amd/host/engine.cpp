@@ -141,7 +141,7 @@ ScoreOutput GPTEngine::score(const std::string& text, int topN) {
 bool GPTEngine::speculateActive(int batch) const {
   const SamplerConfig& s = config_.samplerConfig;
   const bool greedy = !(s.temperature > 0.f || s.topK > 0 || s.topP < 1.f || s.minP > 0.f);      // Sampler.cpp:15-21
-  return config_.speculate > 0 && batch == 1 && greedy && be_.verify_row && be_.set_row_stop && be_.decode_rows && eosTokenIds_.size() <= (size_t)TGX_MAX_STOP_IDS;
+  return config_.speculate > 0 && batch == 1 && greedy && !processorsOn() && be_.verify_row && be_.set_row_stop && be_.decode_rows && eosTokenIds_.size() <= (size_t)TGX_MAX_STOP_IDS;
 }
 
 bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
@@ -181,14 +181,48 @@ bool GPTEngine::logprobsRefused(bool async) {
   return false;
 }
 
-bool GPTEngine::logprobsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first) {
+bool GPTEngine::rowsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first) {
   first.assign((size_t)batch, 0);
+  const bool lp = logprobsActive();
   for (int b = 0; b < batch; b++) {
-    if (be_.set_row_sampler(model_.ctx, b, &sc, config_.seed) != TGX_OK || be_.set_row_logprobs(model_.ctx, b, config_.logprobs) != TGX_OK ||
+    if (be_.set_row_sampler(model_.ctx, b, &sc, config_.seed) != TGX_OK || (lp && be_.set_row_logprobs(model_.ctx, b, config_.logprobs) != TGX_OK) ||
         be_.sample_row(model_.ctx, b, &sc, config_.seed, &first[(size_t)b]) != TGX_OK)
-      return fail(std::string("logprobs: ") + be_.last_error(model_.ctx));
+      return fail(std::string(lp ? "logprobs: " : "sample_row: ") + be_.last_error(model_.ctx));
   }
   return true;
+}
+
+// ---- SamplerConfig's penalties and logit bias: per row on the device (include/tgx.h tgx_set_row_penalties); the engine supplies each row's history from the prompt
+// it admitted and steps through the per-row calls, which count what the rows produce
+bool GPTEngine::processorsRefused(bool async) {
+  if (!processorsOn()) return false;
+  if (!(be_.set_row_penalties && be_.set_row_logit_bias && be_.set_row_history && be_.set_row_sampler && be_.sample_row && be_.set_row_stop && be_.decode_rows)) {
+    fail("penalties / logit bias: the device shim lacks tgx_set_row_penalties / tgx_set_row_logit_bias / tgx_set_row_history or the per-row calls they ride on");
+    return true;
+  }
+  if (config_.samplerConfig.logitBias.size() > (size_t)TGX_MAX_LOGIT_BIAS) { fail("logit bias: at most " + std::to_string(TGX_MAX_LOGIT_BIAS) + " ids"); return true; }
+  if (async && eosTokenIds_.size() > (size_t)TGX_MAX_STOP_IDS) { fail("penalties / logit bias: generateAsync stops the row on the device, which holds at most " + std::to_string(TGX_MAX_STOP_IDS) + " stop ids"); return true; }
+  return false;
+}
+
+bool GPTEngine::processorsBegin(int row, const int64_t* prompt, int64_t n) {
+  const SamplerConfig& s = config_.samplerConfig;
+  const tgx_penalty_cfg pc{s.repetitionPenalty, s.presencePenalty, s.frequencyPenalty};
+  std::vector<int32_t> ids; std::vector<float> val;
+  for (const auto& kv : s.logitBias) { ids.push_back(kv.first); val.push_back(kv.second); }
+  if (be_.set_row_penalties(model_.ctx, row, &pc) != TGX_OK || be_.set_row_logit_bias(model_.ctx, row, (int)ids.size(), ids.data(), val.data()) != TGX_OK ||
+      be_.set_row_history(model_.ctx, row, prompt, (int)n, nullptr, 0) != TGX_OK)
+    return fail(std::string("penalties / logit bias: ") + be_.last_error(model_.ctx));
+  return true;
+}
+
+void GPTEngine::processorsEnd(int batch) {
+  const tgx_penalty_cfg neutral{1.f, 0.f, 0.f};
+  for (int b = 0; b < batch; b++) {
+    be_.set_row_penalties(model_.ctx, b, &neutral);
+    be_.set_row_logit_bias(model_.ctx, b, 0, nullptr, nullptr);
+    be_.set_row_history(model_.ctx, b, nullptr, 0, nullptr, 0);
+  }
 }
 
 bool GPTEngine::logprobsDrain(int row, int64_t n, RowLogprobs& into) {
@@ -251,7 +285,7 @@ std::vector<int64_t> GPTEngine::alignPrompts(const std::vector<std::vector<int32
 GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& prompts, int32_t padToken) {
   GPTOutput out;
   if (!prepared_ || prompts.empty()) { fail("generateSync: engine not prepared or empty batch"); return out; }
-  if (logprobsRefused(false)) return out;
+  if (logprobsRefused(false) || processorsRefused(false)) return out;
   const int B = (int)prompts.size();
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts(prompts, padToken, S);
@@ -268,9 +302,16 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   const bool lpOn = logprobsActive();
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? B : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(B); });
-  if (lpOn) {
-    if (!logprobsBegin(B, sc, first)) return out;
-    for (int b = 0; b < B; b++) if (!logprobsDrain(b, 1, lpRows[(size_t)b])) return out;
+  const bool procOn = processorsOn(), perRow = lpOn || procOn;
+  const auto procOff = at_exit([&] { if (procOn) processorsEnd(B); });
+  if (procOn)      // every row's history: the prompt it admitted, without the left padding
+    for (int b = 0; b < B; b++) {
+      const int64_t n = std::min<int64_t>((int64_t)prompts[(size_t)b].size(), S);
+      if (!processorsBegin(b, ids.data() + (size_t)(b * S + (S - n)), n)) return out;
+    }
+  if (perRow) {
+    if (!rowsBegin(B, sc, first)) return out;
+    for (int b = 0; lpOn && b < B; b++) if (!logprobsDrain(b, 1, lpRows[(size_t)b])) return out;
   } else
   if (be_.sample(model_.ctx, &sc, config_.seed, first.data()) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
   const auto t1 = std::chrono::steady_clock::now();
@@ -288,13 +329,13 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
     }
     if ((int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
     for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = seq[(size_t)(S + 1 + i)];
-  } else if (lpOn) {      // every row with the call's settings through tgx_decode_rows (its ids are tgx_decode's), a ring's worth of steps at most per call
+  } else if (perRow) {      // every row with the call's settings through tgx_decode_rows (its ids are tgx_decode's), a ring's worth of steps at most per call
     for (int b = 0; b < B; b++)
       if (be_.set_row_stop(model_.ctx, b, 0, nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
     for (int64_t done = 0; done < n_new - 1;) {
       const int m = (int)std::min<int64_t>(n_new - 1 - done, TGX_LOGPROB_RING / 2);
       if (be_.decode_rows(model_.ctx, m, rest.data() + (size_t)(done * B), nullptr, nullptr) != TGX_OK) { fail(std::string("decode: ") + be_.last_error(model_.ctx)); return out; }
-      for (int b = 0; b < B; b++) if (!logprobsDrain(b, m, lpRows[(size_t)b])) return out;
+      for (int b = 0; lpOn && b < B; b++) if (!logprobsDrain(b, m, lpRows[(size_t)b])) return out;
       done += m;
     }
   } else
@@ -321,7 +362,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
 GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const GenerateCallback& callback) {
   GPTOutput out;
   if (!prepared_) { fail("generateAsync: engine not prepared"); return out; }
-  if (logprobsRefused(true)) return out;
+  if (logprobsRefused(true) || processorsRefused(true)) return out;
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts({prompt}, 0, S);
   if (S == 0) { fail("generateAsync: the prompt is empty (nothing to prefill)"); return out; }
@@ -338,9 +379,12 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   const bool lpOn = logprobsActive();
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? 1 : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(1); });
-  if (lpOn) {
+  const bool procOn = processorsOn(), perRow = lpOn || procOn;
+  const auto procOff = at_exit([&] { if (procOn) processorsEnd(1); });
+  if (procOn && !processorsBegin(0, ids.data(), S)) return out;
+  if (perRow) {
     std::vector<int64_t> first;
-    if (!logprobsBegin(1, sc, first) || !logprobsDrain(0, 1, lpRows[0])) return out;
+    if (!rowsBegin(1, sc, first) || (lpOn && !logprobsDrain(0, 1, lpRows[0]))) return out;
     cur = first[0];
   } else
   if (be_.sample(model_.ctx, &sc, config_.seed, &cur) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
@@ -350,7 +394,7 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   tokens.push_back((int32_t)cur);
 
   bool hitEos = false, aborted = false, broke = false;
-  if ((speculateActive(1) || lpOn) && config_.maxNewTokens > 1) {      // (logprobs without speculate: the same consumer, fed one tgx_decode_rows step at a time)
+  if ((speculateActive(1) || perRow) && config_.maxNewTokens > 1) {      // (logprobs without speculate: the same consumer, fed one tgx_decode_rows step at a time)
     // The same consumer as the loop below — token i is checked for EOS and reported in iteration i, the maxNewTokens-th is appended unreported — fed from `seq`,
     // which grows by a verified draft or one step whenever the consumer runs dry.  EOS and the length stop the row on the device (tgx_set_row_stop), so a
     // draft is never accepted past either.

@@ -6,6 +6,7 @@
 #pragma once
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -21,6 +22,16 @@ struct SamplerConfig {   // src/engine/Sampler.h:13-22
   int64_t topK = 0;
   float topP = 1.f;
   float minP = 0.f;
+  // Not in the reference (the completions protocol's presence_penalty / frequency_penalty / logit_bias and HF's repetition_penalty; include/tgx.h
+  // tgx_set_row_penalties).  The neutral defaults leave the generate loops exactly as they were.  Any non-neutral value: the engine steps through tgx_sample_row /
+  // tgx_decode_rows (the shape the `logprobs` path has), sets every row's history from the prompt it admitted (pad tokens are not counted) and switches the rows
+  // back to neutral when the call ends; `speculate` falls back to plain steps.  A backend without the calls FAILS the generate call with a message (lastError).
+  // generation_config.json's repetition_penalty is NOT applied by default: the reference ignores it.
+  float repetitionPenalty = 1.f;
+  float presencePenalty = 0.f;
+  float frequencyPenalty = 0.f;
+  std::map<int32_t, float> logitBias;      // id -> value added to the id's logit; -INFINITY bans the id
+  bool processorsNeutral() const { return repetitionPenalty == 1.f && presencePenalty == 0.f && frequencyPenalty == 0.f && logitBias.empty(); }
 };
 
 enum class FinishReason { Stop, Length };
@@ -141,6 +152,11 @@ class GPTEngine {
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
   void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
   void setLogprobs(int topN) { config_.logprobs = topN; }
+  const SamplerConfig& samplerConfig() const { return config_.samplerConfig; }
+  void setProcessors(float repetition, float presence, float frequency, std::map<int32_t, float> bias) {      // kept by the C view across tgxe_reconfigure
+    config_.samplerConfig.repetitionPenalty = repetition; config_.samplerConfig.presencePenalty = presence; config_.samplerConfig.frequencyPenalty = frequency;
+    config_.samplerConfig.logitBias = std::move(bias);
+  }
   const SpecStats& specStats() const { return spec_; }
 
  private:
@@ -157,10 +173,15 @@ class GPTEngine {
   struct RowLogprobs { std::vector<float> lp, topLp; std::vector<int32_t> topId; };
   bool logprobsActive() const;
   bool logprobsRefused(bool async);                                                            // logprobs asked for and not servable: err_ set, the generate call fails
-  bool logprobsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first);      // the rows' settings, then the first token of every row through tgx_sample_row
   bool logprobsDrain(int row, int64_t n, RowLogprobs& into);                                  // appends the row's last n records
   void logprobsEnd(int batch);
   void logprobsStore(GPTOutput& out, const std::vector<RowLogprobs>& rows, int64_t perRow) const;
+  // SamplerConfig's penalties / logit bias
+  bool processorsOn() const { return !config_.samplerConfig.processorsNeutral(); }
+  bool processorsRefused(bool async);                                                          // asked for and not servable: err_ set, the generate call fails
+  bool processorsBegin(int row, const int64_t* prompt, int64_t n);                            // the row's settings, and its history from the prompt it admitted
+  void processorsEnd(int batch);                                                               // neutral again, histories cleared
+  bool rowsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first);          // the rows' sampler (and logprobs) settings, then every row's first token through tgx_sample_row
 
   GPTConfig config_;
   Backend be_;

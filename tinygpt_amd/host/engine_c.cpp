@@ -112,9 +112,17 @@ TGXE_API int tgxe_score_text(tgxe_engine* h, const char* text, int top_n, int32_
   if (out_top_lp) memcpy(out_top_lp, r.topLogprobValues.data(), r.topLogprobValues.size() * 4);
   return 0;
 }
+// SamplerConfig's penalties and logit bias (neutral: 1, 0, 0 and n = 0); kept across tgxe_reconfigure until set again
+TGXE_API void tgxe_set_processors(tgxe_engine* h, float repetition, float presence, float frequency, const int32_t* bias_ids, const float* bias, int n) {
+  if (!h) return;
+  std::map<int32_t, float> m;
+  for (int i = 0; bias_ids && bias && i < n; i++) m[bias_ids[i]] = bias[i];
+  h->e->setProcessors(repetition, presence, frequency, std::move(m));
+}
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
-  tgxh::SamplerConfig s; s.temperature = temperature; s.topK = top_k; s.topP = top_p; s.minP = min_p;
+  tgxh::SamplerConfig s = h->e->samplerConfig();      // (the penalties / logit bias of tgxe_set_processors stay)
+  s.temperature = temperature; s.topK = top_k; s.topP = top_p; s.minP = min_p;
   std::vector<int32_t> ex(extra_stop, extra_stop + (extra_stop ? n_extra : 0));
   h->e->reconfigure(s, max_new, ex);
 }

@@ -39,6 +39,9 @@ static void usage(const char* prog) {
           "  --score                   generate nothing: print the log-probability of every prompt token but the first (position id lp, %%.9g; with --logprobs n the n most\n"
           "                            likely alternatives as id:lp) and the prompt's perplexity, one prefill pass per prompt; of a prompt\n"
           "                            longer than the context the last contextSize tokens are scored (positions count from the prompt's start)\n"
+          "  --repetition-penalty <r> --presence-penalty <p> --frequency-penalty <f>\n"
+          "                            penalties over each row's prompt and produced tokens, applied to the logits on the device (default: 1 0 0 = off)\n"
+          "  --logit-bias <id:val,...> added to those ids' logits; -inf bans an id (at most 320 ids; default: none)\n"
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n",
           prog);
 }
@@ -108,6 +111,23 @@ int main(int argc, char** argv) {
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
     else if (a == "--logprobs") cfg.logprobs = atoi(next());
+    else if (a == "--repetition-penalty") cfg.samplerConfig.repetitionPenalty = strtof(next(), nullptr);
+    else if (a == "--presence-penalty") cfg.samplerConfig.presencePenalty = strtof(next(), nullptr);
+    else if (a == "--frequency-penalty") cfg.samplerConfig.frequencyPenalty = strtof(next(), nullptr);
+    else if (a == "--logit-bias") {
+      std::stringstream ss(next());
+      std::string item;
+      while (std::getline(ss, item, ',')) {
+        const size_t colon = item.find(':');
+        if (colon == std::string::npos || colon == 0 || colon + 1 >= item.size()) { fprintf(stderr, "--logit-bias: expected id:val[,id:val...], got '%s'\n", item.c_str()); return 1; }
+        const std::string id_s = item.substr(0, colon), val_s = item.substr(colon + 1);
+        char *id_end = nullptr, *val_end = nullptr;
+        const long id = strtol(id_s.c_str(), &id_end, 10);
+        const float val = strtof(val_s.c_str(), &val_end);      // (strtof reads "-inf")
+        if (*id_end != '\0' || *val_end != '\0' || id < 0 || id > 0x7fffffffL) { fprintf(stderr, "--logit-bias: '%s' is not id:val (a token id and a number)\n", item.c_str()); return 1; }
+        cfg.samplerConfig.logitBias[(int32_t)id] = val;
+      }
+    }
 #ifdef TGXH_TEST_HOOKS
     // tgx_cli_test only (tests/_build, -DTGXH_TEST_HOOKS): bind the host engine to a library of the test's choice that exports the tgx ABI
     // (the CPU oracle), to check host logic on a machine without a GPU.  The shipped tgx_cli has neither flag.
