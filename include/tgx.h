@@ -33,6 +33,7 @@ extern "C" {
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
 /* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
 /* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
+/* (still 3: additive) tgx_row_snapshot_bytes / tgx_save_row / tgx_restore_row — a live row saved to host memory and restored into any row of any context of the same geometry. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -300,6 +301,62 @@ TGX_API int tgx_extend_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
  * siblings, the next append would write into a shared block: the row takes one fresh block, rows [0, new_len % 128) of every layer and both caches are copied into
  * it in one launch, the table entry is swapped and the shared block loses this row's reference.  With no free block that is TGX_ERR_CONTEXT and nothing changes. */
 TGX_API int tgx_truncate_row(tgx_ctx* ctx, int row, int64_t new_len);
+
+/* ---- row snapshots: a live row saved to host memory and restored anywhere (additive to ABI 3) ---------------------------------------------------------------
+ * Everything above keeps a sequence in device memory from admission to retirement.  A snapshot moves one off the device and back: swap-out when a paged cache has no
+ * block left (TGX_ERR_CONTEXT: save a row, tgx_reset_row it, restore it later instead of a second prefill of prompt + generated tokens), a conversation or a shared
+ * system prompt kept across processes (a snapshot is plain bytes: write it to a file), a sequence moved to another context — another GPU's replica, or between a
+ * paged and an unpaged context.  tgx_restore_row is a tgx_fork_row whose source lives in host memory.
+ *
+ *   Source of a save  a live, unfinished row < batch that holds past >= 1 positions, in any of its three states: logits and a current token (mid-generation), logits
+ *                     and no token (fresh from tgx_forward_row / tgx_extend_row), no logits (after tgx_truncate_row: the "prefix only" snapshot).  A retired, empty or
+ *                     finished row, row >= batch, a poisoned context, a call before tgx_finalize: TGX_ERR_STATE.  A row outside [0, max_batch), a null pointer,
+ *                     cap < the snapshot's size: TGX_ERR_INVALID; nothing is written then and *out_bytes is not touched.  tgx_row_snapshot_bytes applies the same
+ *                     checks and returns the size tgx_save_row would write now (it changes with every step the row takes).
+ *   A save            changes nothing on the device but the library's own staging buffer: the row, kv.free_tokens and every other row stay as they were — the caller
+ *                     calls tgx_reset_row itself if it wants the blocks back.  Stream-ordered behind the steps already enqueued; returns when the bytes are in buf.
+ *   What it holds     what tgx_fork_row's copy launch carries: cache positions [0, past) of every layer and both caches in the storage dtype, bit for bit; the
+ *                     position word and the token word; iff the row holds logits, its fp32 hidden row [hidden] and its fp32 logits [vocab].  NOT held: the argmax
+ *                     partials (restore recomputes them from the logits), the row's sampler / stop / logprobs / processor settings, its processor history words,
+ *                     its logprob records.  Settings are the caller's, as for tgx_fork_row and tgx_forward_row; a history is restated with tgx_set_row_history.
+ *                     Whether the weights behind the snapshot are the weights of the context that restores it is the caller's business, and so is the integrity
+ *                     of the bytes in transit: there is no checksum.
+ *   Format            version TGX_SNAPSHOT_VERSION, little-endian, independent of whether the cache it came from is paged:
+ *                       [0, 128) header   0 magic "TGXSNAP\0" (8 bytes) | 8 u32 version | 12 u32 header bytes = 128 | 16 u64 total bytes |
+ *                                         24 nine i32 that must match the restoring context: family, hidden, layers, heads, kv_heads, head_dim, vocab, compute_dtype,
+ *                                         qk_norm | 60 u32 flags: bit 0 "holds logits", bit 1 "has a current token" (only with bit 0) | 64 i64 past |
+ *                                         72 u64 state offset | 80 u64 state bytes | 88 u64 KV offset | 96 u64 KV bytes | 104 .. 127 zeros
+ *                       state section     at 128: u32 position word (== past) | u32 token word (0 without bit 1) | iff bit 0: f32 hidden [hidden] | f32 logits [vocab]
+ *                       KV section        at the next multiple of 16 (zeros between): [layer][K, then V][kv_head][past][head_dim] in the storage dtype; a layer's
+ *                                         bytes are contiguous
+ *   Restore target    tgx_forward_row's rule: a retired or empty row < batch, or row == batch (the batch grows by one, up to max_batch).  A live or finished target is
+ *                     TGX_ERR_STATE; a new row other than batch, or a row outside [0, max_batch), TGX_ERR_INVALID.
+ *   Restore checks    the blob is validated on the host before anything changes.  TGX_ERR_INVALID: bytes smaller than the header or not the header's total; a wrong
+ *                     magic or version; section offsets or sizes that do not follow from the geometry and past; a geometry word that differs from the context's; a
+ *                     position word != past; a token word outside [0, vocab) with bit 1 set; bit 1 without bit 0.  past > max_ctx: TGX_ERR_CONTEXT.  A head_dim *
+ *                     element size that is no multiple of 4: TGX_ERR_UNSUPPORTED, as for tgx_fork_row.
+ *   Paged KV          ceil(past / 128) fresh blocks, counted against the free list plus what the target row gives back before anything is assigned (TGX_ERR_CONTEXT);
+ *                     more than 1024 blocks per row is TGX_ERR_UNSUPPORTED.  The restored row owns all its blocks: nothing is shared, no shared block is written.
+ *   ALL OR NOTHING    a refused call changes no row, moves no KV block, leaves kv.free_tokens as it was and does not poison the context.
+ *   Afterwards        the row is in exactly the state the source was in when it was saved: with a token it is ready for tgx_decode / tgx_decode_rows; with logits only
+ *                     it needs tgx_sample_row; without logits tgx_sample_row, the decode calls and tgx_fork_row return TGX_ERR_STATE until tgx_extend_row has run on
+ *                     it.  A restore is an admission: the row's settings are untouched, its stop state and produced-token count start afresh, its logprob record
+ *                     count goes back to 0, tgx_read_probs has no vector for it.  tgx_past_length is refreshed; rows not named keep their state bit for bit; on row 0
+ *                     the token becomes ticket 0's token, as after tgx_sample.  The call returns when the copy has finished.
+ *   Reproducibility   a greedy continuation is the same bits in any row of any context.  A sampled draw hashes (seed, position, ROW): a sampled sequence continues
+ *                     as it would have only when it is restored into the row index it was saved from, with its seed set again.
+ *   Staging           the snapshot moves through one device buffer in groups of whole layers: per group one pack launch (kernels/kv_pack.h) and one copy for a save,
+ *                     one copy and one unpack launch for a restore; the state section rides in the first group's launch.  Option snapshot.stage_kib (default 65536)
+ *                     caps the buffer; one layer is always staged.  The buffer is allocated by the first save or restore: a context that never calls these
+ *                     functions allocates nothing new and runs the launches it ran before.  buf may be pageable.
+ *   Cost              measured (profiles/row_snapshot.txt; Llama-3.2-1B bf16, 32 KiB of cache per token, pageable host buffer, wall time of the call): save / reset +
+ *                     restore 0.19 / 0.21 ms at 256 tokens (8.5 MiB), 1.28 / 1.28 ms at 2048 (64.5 MiB), 5.07 / 4.97 ms at 8192 (256.5 MiB) — 52 - 54 GB/s from 2048
+ *                     tokens on, paged and unpaged alike — against 2.43 / 9.09 / 44.9 ms for tgx_reset_row + tgx_forward_row of the same length: restore wins at
+ *                     every length measured (0.09 - 0.14 of the prefill). */
+#define TGX_SNAPSHOT_VERSION 1
+TGX_API int tgx_row_snapshot_bytes(const tgx_ctx* ctx, int row, int64_t* out_bytes);
+TGX_API int tgx_save_row(tgx_ctx* ctx, int row, void* buf, int64_t cap, int64_t* out_bytes);
+TGX_API int tgx_restore_row(tgx_ctx* ctx, int row, const void* buf, int64_t bytes);
 
 /* ---- greedy speculative decoding: verifying a row's draft in one pass (additive to ABI 3) ---------------------------------------------------------------
  * A decode step streams the weights once for one position; a pass over a few positions of ONE sequence streams them once as well (tgx_extend_row).  A caller that

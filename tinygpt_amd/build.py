@@ -27,7 +27,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 
 def _deps():
-    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h")]
+    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h")]
     kd = os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -103,6 +103,11 @@ def build_dev_mem_check(force: bool = False, verbose: bool = False):
     return _build_cpu_check("dev_mem_check", os.path.join(CSRC, "dev_mem.h"), force, verbose)
 
 
+def build_row_snapshot_check(force: bool = False, verbose: bool = False):
+    """tests/row_snapshot_check.cpp, the CPU audit of csrc/row_snapshot.h."""
+    return _build_cpu_check("row_snapshot_check", os.path.join(CSRC, "row_snapshot.h"), force, verbose)
+
+
 def build_spec_draft_check(force: bool = False, verbose: bool = False):
     """tests/spec_draft_check.cpp, the CPU audit of host/spec_draft.h."""
     return _build_cpu_check("spec_draft_check", os.path.join(HOST, "spec_draft.h"), force, verbose)
@@ -114,7 +119,7 @@ def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = Fa
     test_hooks=True builds the TEST variants instead (tests/_build/libtgx_host_test.so, tgx_cli_test, -DTGXH_TEST_HOOKS): the only
     builds that can bind a library other than libtgx_mi355x.so (the CPU oracle, for host-logic tests without a GPU)."""
     srcs = [os.path.join(HOST, f) for f in ("loader.cpp", "engine.cpp", "regex.cpp", "tokenizer.cpp")]
-    deps = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(HERE, "..", "include", "tgx.h")]
+    deps = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "row_snapshot.h")]
     lib, cli, flags = HOST_LIB, HOST_CLI, []
     if test_hooks:
         lib, cli, flags = HOST_TEST_LIB, HOST_TEST_CLI, ["-DTGXH_TEST_HOOKS"]

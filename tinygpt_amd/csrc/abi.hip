@@ -7,6 +7,8 @@
 #include <climits>
 #include "ctx.h"
 #include "kernels/kv_fork.h"
+#include "kernels/kv_pack.h"
+#include "row_snapshot.h"
 
 static std::string g_create_err;
 
@@ -1398,6 +1400,169 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
   return TGX_OK;
 }
 
+// ---- row snapshots (include/tgx.h tgx_save_row / tgx_restore_row; csrc/row_snapshot.h holds the format, kernels/kv_pack.h the copy launches).  The snapshot moves
+// through ONE device staging buffer in groups of whole layers: a save runs one pack launch and one copy to the host per group, a restore one copy and one unpack
+// launch.  The state section (position and token words, hidden row, logits) travels with the first group, in front of its KV bytes — the bytes [128, KV offset +
+// the group's layers) of the blob are one copy.  Option snapshot.stage_kib caps the buffer (one layer is always staged); it is allocated by the first call that
+// moves a snapshot: a context that never does holds none of it.
+static row_snapshot::Geometry snap_geometry(const tgx_ctx* c) {
+  const tgx_model_desc& d = c->d;
+  return {d.family, d.hidden, d.layers, d.heads, d.kv_heads, d.head_dim, d.vocab, d.compute_dtype, d.qk_norm};
+}
+// the checks of a save's source, and the layout of its snapshot
+static int snap_source(tgx_ctx* c, int row, row_snapshot::Layout* out) {
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "snapshot before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  const RowHost& r = c->row_host[(size_t)row];
+  if (row >= c->batch || r.idle || r.fin || r.past < 1) return set_err(c, TGX_ERR_STATE, "row %d is not a live, unfinished row of the batch", row);
+  const bool logits = c->have_logits && !r.nologits;
+  *out = row_snapshot::layout(snap_geometry(c), r.past, (logits ? row_snapshot::FLAG_LOGITS : 0u) | (logits && r.tok ? row_snapshot::FLAG_TOKEN : 0u));
+  return TGX_OK;
+}
+struct SnapGroups { long long layer_bytes; size_t state_area; int per_group; };
+// the groups of whole layers a snapshot laid out as l moves in, and the staging buffer that holds one of them behind the state area
+static int snap_stage_for(tgx_ctx* c, const row_snapshot::Layout& l, SnapGroups* g) {
+  g->layer_bytes = (long long)row_snapshot::layer_bytes(snap_geometry(c), l.past);
+  g->state_area = (size_t)(l.kv_off - l.state_off);
+  const long long room = (long long)c->snapshot_stage_kib * 1024 - (long long)g->state_area;
+  g->per_group = (int)std::max<long long>(1, std::min<long long>(c->d.layers, room / g->layer_bytes));
+  return dev_grow(c, &c->snap_stage, &c->snap_stage_bytes, g->state_area + (size_t)g->per_group * (size_t)g->layer_bytes);
+}
+// one kv_pack_kernel launch: layers [l0, l0 + nl) of `row`, past positions each, between the cache and staging + state_area; with_state: the state section as well
+static void launch_kv_pack(tgx_ctx* c, int row, long long past, int l0, int nl, size_t state_area, bool with_state, bool logits, bool unpack) {
+  const tgx_model_desc& d = c->d;
+  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz;
+  const bool v16 = tok_bytes % 16 == 0;
+  const int vec = v16 ? 16 : 4;
+  tgx::KvPackArgs a{};
+  a.stage = c->snap_stage + state_area;
+  if (c->kv_paged) {
+    a.k = c->slab_k; a.v = c->slab_v; a.tbl = c->kv_tbl + (size_t)row * c->kv.tbl_stride();
+    a.head_stride = tgx::KV_BLOCK * tok_bytes; a.piece_stride = d.kv_heads * a.head_stride; a.layer_stride = c->kv.n_blocks() * a.piece_stride;
+  } else {
+    a.k = c->rows[(size_t)row].kcache; a.v = c->rows[(size_t)row].vcache; a.tbl = nullptr;
+    a.piece_stride = tgx::KV_BLOCK * tok_bytes; a.head_stride = d.max_ctx * tok_bytes; a.layer_stride = d.kv_heads * a.head_stride;
+  }
+  a.span_vecs = past * tok_bytes / vec; a.piece_vecs = (int)(tgx::KV_BLOCK * tok_bytes / vec);
+  a.n_pieces = (int)((past + tgx::KV_BLOCK - 1) / tgx::KV_BLOCK);
+  a.layer0 = l0; a.kv_heads = d.kv_heads; a.n_spans = nl * 2 * d.kv_heads;
+  // the grid from the pieces to move, within eight workgroups per CU as launch_kv_fork's (the rest in the kernel's loops).  x: the pieces of a span; y: the spans
+  const long long cap = 8ll * c->num_cus;
+  const int gx = (int)std::max<long long>(1, std::min<long long>(a.n_pieces, cap));
+  a.kv_rows = (int)std::max<long long>(1, std::min<long long>(a.n_spans, cap / gx));
+  int st_rows = 0;
+  if (with_state) {
+    const size_t H = (size_t)d.hidden, V = (size_t)d.vocab;
+    unsigned char* const st = c->snap_stage;
+    a.seg[0] = {reinterpret_cast<unsigned char*>(c->slab_pos + row), st, 1};
+    a.seg[1] = {reinterpret_cast<unsigned char*>(c->slab_tok + row), st + 4, 1};
+    a.n_seg = 2;
+    if (logits) {
+      a.seg[2] = {reinterpret_cast<unsigned char*>(c->slab_x + (size_t)row * H), st + 8, (int)H};
+      a.seg[3] = {reinterpret_cast<unsigned char*>(c->slab_logits + (size_t)row * V), st + 8 + 4 * H, (int)V};
+      a.n_seg = 4;
+    }
+    st_rows = ((int)std::min<size_t>(64, logits ? (V + 1023) / 1024 : 1) + gx - 1) / gx;      // the state part: up to 64 workgroups, a dword per thread and round
+  }
+  const dim3 grid((unsigned)gx, (unsigned)(a.kv_rows + st_rows)), block(tgx::KV_PACK_THREADS);
+  if (v16) {
+    if (unpack) hipLaunchKernelGGL((tgx::kv_pack_kernel<tgx::u32x4, true>), grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((tgx::kv_pack_kernel<tgx::u32x4, false>), grid, block, 0, c->stream, a);
+  } else {
+    if (unpack) hipLaunchKernelGGL((tgx::kv_pack_kernel<unsigned int, true>), grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((tgx::kv_pack_kernel<unsigned int, false>), grid, block, 0, c->stream, a);
+  }
+}
+
+int tgx_row_snapshot_bytes(const tgx_ctx* cc, int row, int64_t* out_bytes) {
+  tgx_ctx* c = const_cast<tgx_ctx*>(cc);      // (the error text alone is written)
+  if (!c || !out_bytes) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  row_snapshot::Layout l;
+  if (int rc = snap_source(c, row, &l)) return rc;
+  *out_bytes = (int64_t)l.total;
+  return TGX_OK;
+}
+
+int tgx_save_row(tgx_ctx* c, int row, void* buf, int64_t cap, int64_t* out_bytes) {
+  if (!c || !buf || !out_bytes) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  row_snapshot::Layout l;
+  if (int rc = snap_source(c, row, &l)) return rc;
+  if (cap < (int64_t)l.total) return set_err(c, TGX_ERR_INVALID, "tgx_save_row: the snapshot of row %d takes %llu bytes, the buffer holds %lld", row, (unsigned long long)l.total, (long long)cap);
+  const tgx_model_desc& d = c->d;
+  if (((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_save_row: a cache row of %d bytes", (int)(d.head_dim * c->esz));
+  HIP_OK(c, hipSetDevice(c->device));
+  SnapGroups g;
+  if (int rc = snap_stage_for(c, l, &g)) return rc;
+  unsigned char* const out = static_cast<unsigned char*>(buf);
+  const bool logits = (l.flags & row_snapshot::FLAG_LOGITS) != 0;
+  for (int l0 = 0; l0 < d.layers; l0 += g.per_group) {
+    const int nl = std::min(g.per_group, d.layers - l0);
+    launch_kv_pack(c, row, l.past, l0, nl, g.state_area, /*with_state=*/l0 == 0, logits, /*unpack=*/false);
+    const size_t kv_at = (size_t)l.kv_off + (size_t)l0 * (size_t)g.layer_bytes, kv_n = (size_t)nl * (size_t)g.layer_bytes;
+    if (l0 == 0) HIP_OK(c, hipMemcpyAsync(out + l.state_off, c->snap_stage, g.state_area + kv_n, hipMemcpyDeviceToHost, c->stream));      // state | padding | the first group
+    else HIP_OK(c, hipMemcpyAsync(out + kv_at, c->snap_stage + g.state_area, kv_n, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (int rc = finish_pass(c)) return rc;
+  row_snapshot::write_header(out, snap_geometry(c), l);
+  if (!(l.flags & row_snapshot::FLAG_TOKEN)) row_snapshot::put32(out + l.state_off + 4, 0);      // no current token: the word reads 0, whatever the slot held
+  memset(out + l.state_off + l.state_bytes, 0, (size_t)(l.kv_off - l.state_off - l.state_bytes));      // the padding in front of the KV section
+  *out_bytes = (int64_t)l.total;
+  return TGX_OK;
+}
+
+int tgx_restore_row(tgx_ctx* c, int row, const void* buf, int64_t bytes) {
+  if (!c || !buf) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "restore before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  // ---- every check before anything changes
+  const int32_t r32 = row;
+  if (int rc = check_target_rows(c, 1, &r32, /*lens=*/nullptr, /*src=*/-1)) return rc;
+  row_snapshot::Layout l;
+  int32_t tok = 0;
+  const char* why = "";
+  if (const int v = row_snapshot::validate(buf, bytes, snap_geometry(c), d.max_ctx, &l, &tok, &why)) return set_err(c, v, "tgx_restore_row: not a snapshot this context can restore: %s", why);
+  if (((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_restore_row: a cache row of %d bytes", (int)(d.head_dim * c->esz));
+  if (c->kv_paged) {
+    const long long need = c->kv.blocks_for(l.past), have = c->kv.available_for(&row, 1);
+    if (need > 1024) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_restore_row of %lld blocks into a paged cache (at most 1024 per row)", need);
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the snapshot needs %lld blocks of %d tokens, %lld free or held by row %d of %d (option kv.budget_tokens = %d)", need,
+                     tgx::KV_BLOCK, have, row, c->kv.n_blocks() - 1, c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  SnapGroups g;
+  if (int rc = snap_stage_for(c, l, &g)) return rc;
+  if (c->kv_paged) {       // blocks of its own for every position: nothing is shared, no shared block is written
+    kv_release_row(c, row);
+    (void)kv_ensure_blocks(c, row, l.past);      // cannot fail: counted above
+  }
+  const unsigned char* const in = static_cast<const unsigned char*>(buf);
+  const bool logits = (l.flags & row_snapshot::FLAG_LOGITS) != 0, has_tok = (l.flags & row_snapshot::FLAG_TOKEN) != 0;
+  for (int l0 = 0; l0 < d.layers; l0 += g.per_group) {
+    const int nl = std::min(g.per_group, d.layers - l0);
+    const size_t kv_at = (size_t)l.kv_off + (size_t)l0 * (size_t)g.layer_bytes, kv_n = (size_t)nl * (size_t)g.layer_bytes;
+    if (l0 == 0) HIP_OK(c, hipMemcpyAsync(c->snap_stage, in + l.state_off, g.state_area + kv_n, hipMemcpyHostToDevice, c->stream));
+    else HIP_OK(c, hipMemcpyAsync(c->snap_stage + g.state_area, in + kv_at, kv_n, hipMemcpyHostToDevice, c->stream));
+    launch_kv_pack(c, row, l.past, l0, nl, g.state_area, /*with_state=*/l0 == 0, logits, /*unpack=*/true);
+  }
+  if (logits) {            // the argmax partials depend on lm_grid and are not held: from the logits, as tgx_set_logits does
+    RowState& r = c->rows[(size_t)row];
+    launch_argmax_partials(c, r.logits, d.vocab, r.part_val, r.part_idx);
+  }
+  if (int rc = finish_pass(c)) return rc;
+  c->batch = std::max(c->batch, row + 1);
+  row_admitted(c, row, (int)l.past);
+  c->row_host[(size_t)row].tok = has_tok;
+  c->row_host[(size_t)row].nologits = !logits;
+  if (logits) c->have_logits = true;
+  if (row == 0 && has_tok) c->last_sampled0 = tok;      // ticket 0's token, as after tgx_sample
+  refresh_longest(c);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
 // ---- tgx_extend_row / tgx_truncate_row (include/tgx.h): a live row grows by several positions in one pass, or is rolled back.  The pass is issue_pass's one-row pass
 // with the row's real length as `past` (every route takes it); the row then stands as tgx_forward_row leaves one.  Every check comes before anything changes.
 static int extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq, ScoreCall* sc) {      // sc (tgx_score_row): the pass also scores its positions
@@ -2001,6 +2166,7 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "extend.attn_splits")) { *out_value = c->extend_attn_splits; return TGX_OK; }
   if (!strcmp(key, "score.rows")) { *out_value = c->score_rows; return TGX_OK; }
   if (!strcmp(key, "score.vocab_chunk")) { *out_value = c->score_vocab_chunk; return TGX_OK; }
+  if (!strcmp(key, "snapshot.stage_kib")) { *out_value = c->snapshot_stage_kib; return TGX_OK; }
   if (!strcmp(key, "score.last_form")) { *out_value = c->score_last_form; return TGX_OK; }      // read-only: the form of the last tgx_score_row that scored a position (0 none yet, 1 matrix cores, 2 by groups)
   if (!strcmp(key, "weights.packed")) { *out_value = c->weights_packed; return TGX_OK; }
   if (!strcmp(key, "weights.packed_classes")) { *out_value = c->packed_classes; return TGX_OK; }
@@ -2078,6 +2244,7 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "extend.attn_splits")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "extend.attn_splits is -1 (automatic), 0 (never) or a split count"); c->extend_attn_splits = value; return TGX_OK; }
   if (!strcmp(key, "score.rows")) { if (value < 64 || value % 64) return set_err(c, TGX_ERR_INVALID, "score.rows is a positive multiple of 64"); c->score_rows = value; return TGX_OK; }
   if (!strcmp(key, "score.vocab_chunk")) { if (value < 1024 || value % 1024) return set_err(c, TGX_ERR_INVALID, "score.vocab_chunk is a positive multiple of 1024"); c->score_vocab_chunk = value; return TGX_OK; }
+  if (!strcmp(key, "snapshot.stage_kib")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "snapshot.stage_kib is a size in KiB (one layer of a row is always staged)"); c->snapshot_stage_kib = value; return TGX_OK; }
   if (!strcmp(key, "oproj.sliced")) { drop_step_graphs(c); c->oproj_sliced = value != 0; return TGX_OK; }
   if (!strcmp(key, "weights.packed") || !strcmp(key, "weights.packed_classes")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the packed copies are made there)", key);

@@ -2,6 +2,7 @@
 //   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows),
 //                    the device side of paged-KV block assignment (table pushes) and tgx_fork_row with its copy launch (kernels/kv_fork.h)
 //   kv_pool.h        KvPool: the paged cache's block bookkeeping (free list, per-block row counts, the table's host mirror) — host-only, checked on a CPU
+//   row_snapshot.h   the byte format of a row snapshot (tgx_save_row / tgx_restore_row): header, size formula, validation — host-only, checked on a CPU
 //   dev_mem.h        DevMem: the owner of every device allocation of the context (dev_alloc / dev_free / dev_grow below) — host-only, checked on a CPU
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
@@ -349,6 +350,11 @@ struct tgx_ctx {
   float* proc_logits = nullptr;              // [max_batch][vocab] the processed logits of the rows' last processed step
   float* proc_part_val = nullptr;            // [max_batch][ceil(vocab / 1024)] their per-tile (max, lowest index)
   int* proc_part_idx = nullptr;
+  // ---- row snapshots (include/tgx.h tgx_save_row / tgx_restore_row; row_snapshot.h, kernels/kv_pack.h): the staging buffer a snapshot moves through in groups of
+  // whole layers (the state section in front of the first group's).  Allocated by the first save or restore, grown to the largest group seen; option
+  // snapshot.stage_kib caps it (one layer is always staged)
+  unsigned char* snap_stage = nullptr; size_t snap_stage_bytes = 0;
+  int snapshot_stage_kib = 65536;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };

@@ -83,6 +83,9 @@ ABI = {
     "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
     "extend_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "truncate_row": (c_int, [c_void_p, c_int, c_int64]),
+    "row_snapshot_bytes": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "save_row": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
+    "restore_row": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "verify_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
@@ -305,6 +308,28 @@ class Model:
     def truncate_row(self, row: int, n: int):
         """roll `row` back to its first n positions (include/tgx.h tgx_truncate_row); it then holds no logits until extend_row"""
         self._check(self.be.truncate_row(self._ctx, row, int(n)))
+        return self
+
+    # -- row snapshots (include/tgx.h tgx_save_row / tgx_restore_row) -----------------------------
+    def row_snapshot_bytes(self, row: int) -> int:
+        n = c_int64(0)
+        self._check(self.be.row_snapshot_bytes(self._ctx, row, ctypes.byref(n)))
+        return n.value
+
+    def save_row(self, row: int) -> bytes:
+        """the live row `row` as a snapshot (include/tgx.h tgx_save_row): its cache positions, position and token words and, if it holds them, hidden row and logits;
+        the row stays as it is"""
+        buf = np.empty(self.row_snapshot_bytes(row), dtype=np.uint8)
+        n = c_int64(0)
+        self._check(self.be.save_row(self._ctx, row, buf.ctypes.data_as(c_void_p), buf.size, ctypes.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def restore_row(self, row: int, blob):
+        """`row` (a retired or empty row, or the next free one) becomes the row `blob` was saved from (include/tgx.h tgx_restore_row); settings are the caller's"""
+        a = np.frombuffer(blob, dtype=np.uint8)
+        ptr = a.ctypes.data_as(c_void_p) if a.size else ctypes.cast((ctypes.c_ubyte * 1)(), c_void_p)
+        self._check(self.be.restore_row(self._ctx, row, ptr, a.size))
+        self.batch = max(self.batch, row + 1)
         return self
 
     def verify_row(self, row: int, draft):

@@ -56,6 +56,10 @@ struct Backend {
   int (*set_row_history)(tgx_ctx*, int, const int64_t*, int, const int64_t*, int) = nullptr;
   // scoring a supplied sequence (optional: GPTEngine::score needs it)
   int (*score_row)(tgx_ctx*, int, const int64_t*, int, int, float*, int32_t*, float*) = nullptr;
+  // row snapshots (optional: GPTEngine::saveSession / loadSession need all three, and prefix reuse)
+  int (*row_snapshot_bytes)(const tgx_ctx*, int, int64_t*) = nullptr;
+  int (*save_row)(tgx_ctx*, int, void*, int64_t, int64_t*) = nullptr;
+  int (*restore_row)(tgx_ctx*, int, const void*, int64_t) = nullptr;
 
   bool open(const std::string& path, const std::string& prefix) {
     // RTLD_NODELETE: the shim's runtime owns threads (HIP's signal/event workers; libgomp's team under the CPU oracle) that
@@ -80,6 +84,7 @@ struct Backend {
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
     TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);
     TGXH_BIND(score_row, false);
+    TGXH_BIND(row_snapshot_bytes, false); TGXH_BIND(save_row, false); TGXH_BIND(restore_row, false);
 #undef TGXH_BIND
     return ok;
   }

@@ -1,4 +1,5 @@
 #include "engine.h"
+#include "../csrc/row_snapshot.h"
 
 #include <chrono>
 
@@ -95,6 +96,85 @@ bool GPTEngine::prefillReusing(const std::vector<int64_t>& ids) {
   if (be_.truncate_row(model_.ctx, 0, L) != TGX_OK) return false;
   if (be_.extend_row(model_.ctx, 0, ids.data() + L, (int)(S - L)) != TGX_OK) return false;
   lastReused_ = L;
+  return true;
+}
+
+// ---- GPTEngine::saveSession / loadSession (include/tgx.h tgx_save_row / tgx_restore_row): [magic 8][u32 version][u32 count][i32 ids x count][u64 snapshot bytes][snapshot]
+static const unsigned char kSessionMagic[8] = {'T', 'G', 'X', 'S', 'E', 'S', 'S', 0};
+enum : uint32_t { kSessionVersion = 1 };
+
+static row_snapshot::Geometry session_geometry(const tgx_model_desc& d) {
+  return {d.family, d.hidden, d.layers, d.heads, d.kv_heads, d.head_dim, d.vocab, d.compute_dtype, d.qk_norm};
+}
+
+bool GPTEngine::sessionCapable(const char* what) {
+  if (!prepared_) return fail(std::string(what) + ": engine not prepared");
+  if (!reuseActive()) return fail(std::string(what) + ": prefix reuse is not active (GPTConfig::reusePrefix and a backend with tgx_extend_row / tgx_truncate_row)");
+  if (!be_.row_snapshot_bytes || !be_.save_row || !be_.restore_row) return fail(std::string(what) + ": the device shim lacks tgx_save_row / tgx_restore_row");
+  return true;
+}
+
+bool GPTEngine::saveSession(const std::string& path) {
+  if (!sessionCapable("saveSession")) return false;
+  const int64_t held = be_.past_length(model_.ctx);
+  if (cached_.empty() || held < 1 || held != (int64_t)cached_.size()) return fail("saveSession: row 0 holds no conversation (run generateAsync first)");
+  const tgx_model_desc& d = desc();
+  int64_t bytes = 0;
+  if (be_.row_snapshot_bytes(model_.ctx, 0, &bytes) != TGX_OK) return fail(std::string("row_snapshot_bytes: ") + be_.last_error(model_.ctx));
+  std::vector<unsigned char> file(16 + 4 * (size_t)held + 8 + (size_t)bytes);
+  memcpy(file.data(), kSessionMagic, 8);
+  row_snapshot::put32(file.data() + 8, kSessionVersion); row_snapshot::put32(file.data() + 12, (uint32_t)held);
+  for (int64_t i = 0; i < held; i++) row_snapshot::put32(file.data() + 16 + 4 * (size_t)i, (uint32_t)cached_[(size_t)i]);
+  unsigned char* const snap = file.data() + 16 + 4 * (size_t)held + 8;
+  int64_t wrote = 0;
+  if (be_.save_row(model_.ctx, 0, snap, bytes, &wrote) != TGX_OK) return fail(std::string("save_row: ") + be_.last_error(model_.ctx));
+  // the next turn extends the row and computes its own logits: the file keeps the positions alone (the row on the device stays as it is)
+  row_snapshot::Layout l;
+  const char* why = "";
+  if (row_snapshot::validate(snap, wrote, session_geometry(d), contextSize(), &l, nullptr, &why) != row_snapshot::OK || l.past != held)
+    return fail(std::string("saveSession: the snapshot of row 0 is not what this engine expects: ") + why);
+  wrote = (int64_t)row_snapshot::drop_logits(snap, session_geometry(d), l).total;
+  row_snapshot::put64(snap - 8, (uint64_t)wrote);
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return fail("saveSession: cannot open " + path);
+  const size_t n = (size_t)(snap - file.data()) + (size_t)wrote;
+  const bool ok = fwrite(file.data(), 1, n, f) == n;
+  if (fclose(f) != 0 || !ok) { remove(path.c_str()); return fail("saveSession: writing " + path + " failed"); }
+  return true;
+}
+
+bool GPTEngine::loadSession(const std::string& path) {
+  if (!sessionCapable("loadSession")) return false;
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return fail("loadSession: cannot open " + path);
+  std::vector<unsigned char> file;
+  unsigned char chunk[1 << 16];
+  for (size_t n; (n = fread(chunk, 1, sizeof chunk, f)) > 0;) file.insert(file.end(), chunk, chunk + n);
+  fclose(f);
+  // ---- the whole file against this engine's model, before anything changes
+  if (file.size() < 16 || memcmp(file.data(), kSessionMagic, 8) != 0) return fail("loadSession: " + path + " is not a session file");
+  if (row_snapshot::get32(file.data() + 8) != kSessionVersion) return fail("loadSession: " + path + " has an unknown version");
+  const uint64_t count = row_snapshot::get32(file.data() + 12), ids_end = 16 + 4 * count;
+  if (count < 1 || file.size() < ids_end + 8) return fail("loadSession: " + path + " is truncated");
+  const uint64_t bytes = row_snapshot::get64(file.data() + ids_end);
+  if (bytes != file.size() - (ids_end + 8)) return fail("loadSession: " + path + " is truncated (the snapshot's size differs from what the file holds)");
+  const tgx_model_desc& d = desc();
+  std::vector<int32_t> ids((size_t)count);
+  for (uint64_t i = 0; i < count; i++) {
+    ids[(size_t)i] = (int32_t)row_snapshot::get32(file.data() + 16 + 4 * i);
+    if (ids[(size_t)i] < 0 || ids[(size_t)i] >= d.vocab) return fail("loadSession: " + path + " holds a token id outside the vocabulary");
+  }
+  const unsigned char* const snap = file.data() + ids_end + 8;
+  row_snapshot::Layout l;
+  const char* why = "";
+  if (row_snapshot::validate(snap, (int64_t)bytes, session_geometry(d), contextSize(), &l, nullptr, &why) != row_snapshot::OK)
+    return fail("loadSession: " + path + " does not fit this model: " + why);
+  if ((uint64_t)l.past != count) return fail("loadSession: " + path + " names " + std::to_string(count) + " token ids for a cache of " + std::to_string(l.past) + " positions");
+  // ---- row 0 of a reset cache
+  be_.reset_cache(model_.ctx);
+  cached_.clear(); lastReused_ = 0;
+  if (be_.restore_row(model_.ctx, 0, snap, (int64_t)bytes) != TGX_OK) return fail(std::string("restore_row: ") + be_.last_error(model_.ctx));
+  cached_ = std::move(ids);
   return true;
 }
 

@@ -133,6 +133,20 @@ class GPTEngine {
   // without tgx_score_row, topN outside [0, TGX_MAX_LOGPROBS], an empty sequence, no tokenizer for the text form, or a failed call
   ScoreOutput score(const std::vector<int32_t>& ids, int topN = 0);
   ScoreOutput score(const std::string& text, int topN = 0);
+  // Not in the reference: the conversation row 0's cache holds (GPTConfig::reusePrefix), kept across processes.  saveSession writes a small header (magic "TGXSESS\0",
+  // u32 version 1, u32 count, the count cached token ids as i32, u64 snapshot bytes) followed by row 0's snapshot (include/tgx.h tgx_save_row) WITHOUT its hidden row,
+  // logits and token (csrc/row_snapshot.h drop_logits, on the host): the next turn extends the row and computes its own, and 4 * (hidden + vocab) bytes stay out of the
+  // file.  (A deviation from rolling the row back by one position before the save: that would leave the reloaded engine one reusable position short of the engine
+  // that never stopped, and it would change the live row; the price is a second producer of the snapshot format, checked by tests/row_snapshot_check.cpp.)
+  // loadSession validates the whole file against this engine's model before anything changes, then restores row 0 of a reset cache and takes over the ids: the
+  // next generateAsync prefills only what follows the shared prefix (lastReused()).  Both need prefix reuse active and a backend with the snapshot calls; false
+  // with lastError set otherwise.  A missing, truncated or mismatching file is rejected by that validation and leaves the engine as it was; should tgx_restore_row
+  // itself fail behind it (a device allocation), the engine is left with an EMPTY cache and serves the next call from scratch.
+  // saveSession needs the conversation generateAsync left in row 0: a call that ran the per-row path to its end (GPTConfig::speculate, logprobs, or a non-neutral
+  // penalty / logit bias — the row then finishes on the device by its stop conditions and its cache is not kept for reuse) leaves nothing to save, and saveSession
+  // returns false with a message.  Little-endian, like the snapshot.
+  bool saveSession(const std::string& path);
+  bool loadSession(const std::string& path);
   bool hasTokenizer() const { return tokenizerOk_; }
   Tokenizer& tokenizer() { return tokenizer_; }
   int32_t padTokenId() const;                                                                       // pad -> eos -> 0 (:108-114)
@@ -164,6 +178,7 @@ class GPTEngine {
   std::vector<int64_t> alignPrompts(const std::vector<std::vector<int32_t>>& prompts, int32_t padToken, int64_t& maxLen) const;
   bool fail(const std::string& what);
   bool reuseActive() const { return config_.reusePrefix && be_.extend_row && be_.truncate_row; }
+  bool sessionCapable(const char* what);                       // prefix reuse active and the backend has the snapshot calls; else err_ set
   bool prefillReusing(const std::vector<int64_t>& ids);      // the prompt after its cached prefix; false: nothing reusable (the caller resets and prefills)
   bool speculateActive(int batch) const;                      // GPTConfig::speculate applies to this call
   // row 0 holds seq minus its last token, which is its current token; the row's stop conditions are set.  Drafts from seq, verifies (or takes one ordinary

@@ -58,6 +58,9 @@ TGXE_API int tgxe_eos_ids(tgxe_engine* h, int32_t* out, int cap) {
 // prefix reuse (GPTConfig::reusePrefix): generateAsync keeps row 0's KV cache between calls; tgxe_last_reused = the prompt tokens the last call served from it
 TGXE_API void tgxe_set_reuse_prefix(tgxe_engine* h, int on) { if (h) h->e->setReusePrefix(on != 0); }
 TGXE_API int64_t tgxe_last_reused(tgxe_engine* h) { return h ? h->e->lastReused() : -1; }
+// session files (GPTEngine::saveSession / loadSession): row 0's conversation kept across processes; 0 = done, 1 = refused (tgxe_last_error says why)
+TGXE_API int tgxe_save_session(tgxe_engine* h, const char* path) { return h && path && h->e->saveSession(path) ? 0 : 1; }
+TGXE_API int tgxe_load_session(tgxe_engine* h, const char* path) { return h && path && h->e->loadSession(path) ? 0 : 1; }
 // greedy speculative decoding (GPTConfig::speculate): the maximum draft length (0 = off); tgxe_spec_stats writes {verify calls, draft tokens, accepted draft
 // tokens, ordinary steps, produced-per-verify histogram [0 .. TGX_MAX_DRAFT + 1]} (up to cap values) and returns how many there are
 TGXE_API void tgxe_set_speculate(tgxe_engine* h, int max_draft) { if (h) h->e->setSpeculate(max_draft); }

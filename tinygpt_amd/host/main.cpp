@@ -42,6 +42,11 @@ static void usage(const char* prog) {
           "  --repetition-penalty <r> --presence-penalty <p> --frequency-penalty <f>\n"
           "                            penalties over each row's prompt and produced tokens, applied to the logits on the device (default: 1 0 0 = off)\n"
           "  --logit-bias <id:val,...> added to those ids' logits; -inf bans an id (at most 320 ids; default: none)\n"
+          "  --session-load <file>     with --stream and one text prompt: start from the conversation cache a --session-save run left (only what follows the shared\n"
+          "                            prefix is prefilled; the file must come from the same model and dtype)\n"
+          "  --session-save <file>     with --stream and one text prompt: keep the conversation's KV cache (prompt + generated tokens) in a file when the run ends\n"
+          "                            (neither flag combines with --speculate, --logprobs, the penalties or --logit-bias: those runs end with the row finished on the\n"
+          "                            device, which keeps no cache to save)\n"
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n",
           prog);
 }
@@ -85,7 +90,7 @@ int main(int argc, char** argv) {
   cfg.maxNewTokens = 32;
   cfg.samplerConfig.temperature = 0.8f;
   cfg.samplerConfig.topP = 0.9f;
-  std::string dtype = "bf16", prompt_ids;
+  std::string dtype = "bf16", prompt_ids, session_load, session_save;
   long pad_id = -1;
   std::vector<std::string> text_prompts;
   bool stream = false, score = false;
@@ -110,6 +115,8 @@ int main(int argc, char** argv) {
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
+    else if (a == "--session-load") session_load = next();
+    else if (a == "--session-save") session_save = next();
     else if (a == "--logprobs") cfg.logprobs = atoi(next());
     else if (a == "--repetition-penalty") cfg.samplerConfig.repetitionPenalty = strtof(next(), nullptr);
     else if (a == "--presence-penalty") cfg.samplerConfig.presencePenalty = strtof(next(), nullptr);
@@ -156,8 +163,20 @@ int main(int argc, char** argv) {
 
   const int score_top = std::max(0, cfg.logprobs);
   if (score) cfg.logprobs = -1;      // (--logprobs n names the alternatives of --score: nothing is generated, nothing recorded)
+  const bool session = !session_load.empty() || !session_save.empty();
+  if (session && (!stream || score || !prompt_ids.empty() || text_prompts.size() != 1)) {
+    fprintf(stderr, "Error: --session-load / --session-save need --stream and exactly one --prompt (the single-prompt streaming path keeps row 0's cache)\n");
+    return 1;
+  }
+  if (session && (cfg.speculate > 0 || cfg.logprobs >= 0 || !cfg.samplerConfig.processorsNeutral())) {
+    fprintf(stderr, "Error: --session-load / --session-save do not combine with --speculate, --logprobs, the penalties or --logit-bias (the row finishes on the device and keeps no cache)\n");
+    return 1;
+  }
+  if (session) cfg.reusePrefix = true;
   tgxh::GPTEngine engine(cfg);
   if (!engine.prepare()) { fprintf(stderr, "Prepare engine failed\n"); return 1; }
+  if (session && !engine.hasTokenizer()) { fprintf(stderr, "Error: --session-load / --session-save need a tokenizer (--model or --tokenizer)\n"); return 1; }
+  if (!session_load.empty() && !engine.loadSession(session_load)) fprintf(stderr, "session not loaded, starting from an empty cache: %s\n", engine.lastError().c_str());
 
   if (score) {
     const bool texts = engine.hasTokenizer() && prompt_ids.empty();
@@ -177,6 +196,8 @@ int main(int argc, char** argv) {
       printf("%s", text_prompts[0].c_str());
       out = engine.generateAsync(text_prompts[0], [](const std::string& chunk) { fputs(chunk.c_str(), stdout); fflush(stdout); return true; });
       printf("\n");
+      if (session && out.batch) fprintf(stderr, "session: %lld prompt tokens served from the cache\n", (long long)engine.lastReused());
+      if (!session_save.empty() && out.batch && !engine.saveSession(session_save)) { fprintf(stderr, "session not saved: %s\n", engine.lastError().c_str()); return 1; }
     } else out = engine.generateSync(text_prompts);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (out.batch == 0) { fprintf(stderr, "generate failed: %s\n", engine.lastError().c_str()); return 1; }

@@ -18,6 +18,12 @@ timed window.  Each figure is the median of --reps repetitions with their min ..
 
     python tools/admit_bench.py --extend [--model llama-3.2-1b] [--layers 0] [--extend-pasts 512,2048,8192] [--extend-lens 16,64,128]
     python tools/admit_bench.py --extend --model mistral-7b-v0.3 --dtype bf16 --layers 2        # head_dim 128 at two layers
+
+--snapshot measures moving a row off the device and back (include/tgx.h tgx_save_row / tgx_restore_row): for a prompt of P tokens (--fork-prompts plus 8192), on
+slabs and paged, tgx_save_row into a pageable host buffer, tgx_reset_row + tgx_restore_row from it, and tgx_reset_row + tgx_forward_row(P) — what a caller without
+snapshots does to bring the sequence back.  The three alternate inside every repetition; median [min .. max] of --reps, and the GB/s each copy direction reached.
+
+    python tools/admit_bench.py --snapshot [--fork-prompts 256,2048]
 """
 import argparse, dataclasses, os, sys, time
 import numpy as np
@@ -40,7 +46,55 @@ ap.add_argument("--extend-pasts", default="512,2048,8192")
 ap.add_argument("--extend-lens", default="16,64,128")
 ap.add_argument("--extend-splits", default="0,-1,4,8,16,32")
 ap.add_argument("--layers", type=int, default=0, help="--extend: cut the model to this many layers (0 = all)")
+ap.add_argument("--snapshot", action="store_true", help="tgx_save_row, reset + tgx_restore_row and reset + forward_row(P) for the P of --fork-prompts plus 8192")
 args = ap.parse_args()
+
+
+def snapshot_bench():
+    import ctypes
+    plens = sorted(set([int(x) for x in args.fork_prompts.split(",")] + [8192]))
+    ctx = max(plens) + 64
+    for paged in (0, 1):
+        desc = dataclasses.replace(known_desc(args.model, args.dtype), max_batch=1, max_ctx=ctx)
+        m = Model(desc, product_backend())
+        if paged:
+            m.set_option("kv.budget_tokens", ((max(plens) + 127) // 128 + 1) * 128)
+        m.load_synthetic(1234, 0.02).finalize()
+        for P in plens:
+            p = synth.synth_prompt(desc.vocab, P, 900)
+            m.reset_row(0); m.forward_row(0, p)
+            n = m.row_snapshot_bytes(0)
+            buf = np.zeros(n, dtype=np.uint8)              # pageable, touched
+            ptr, wrote = buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(0)
+
+            def timed(call, reset):
+                if reset:
+                    m.reset_row(0)
+                m.synchronize()
+                t0 = time.perf_counter()
+                call()
+                m.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            forms = {"save": (lambda: m._check(m.be.save_row(m._ctx, 0, ptr, n, ctypes.byref(wrote))), False),
+                     "restore": (lambda: m._check(m.be.restore_row(m._ctx, 0, ptr, n)), True),
+                     "forward": (lambda: m.forward_row(0, p), True)}
+            t = {k: [] for k in forms}
+            for rep in range(2 + args.reps):
+                for k, (call, reset) in forms.items():      # save (the row is live), reset + restore, reset + forward_row: each leaves the row live for the next
+                    dt = timed(call, reset)
+                    if rep >= 2:
+                        t[k].append(dt)
+            cell = lambda v: f"{np.median(v):8.3f} [{min(v):8.3f} .. {max(v):8.3f}]"
+            sv, rs, fw = (float(np.median(t[k])) for k in ("save", "restore", "forward"))
+            print(f"{desc.name} {args.dtype} {'paged' if paged else 'slabs'} prompt {P:5d} ({n / 2**20:7.1f} MiB) ms  save_row {cell(t['save'])} = {n / sv / 1e6:5.1f} GB/s   "
+                  f"reset + restore_row {cell(t['restore'])} = {n / rs / 1e6:5.1f} GB/s   reset + forward_row({P}) {cell(t['forward'])}   restore / forward {rs / fw:.2f}", flush=True)
+        m.close()
+
+
+if args.snapshot:
+    snapshot_bench()
+    sys.exit(0)
 
 
 def extend_bench():
