@@ -230,7 +230,10 @@ TGX_API int64_t tgx_past_length_row(const tgx_ctx* ctx, int row);
  *   Calls             tgx_forward_row into a finished row needs tgx_reset_row first (TGX_ERR_STATE); tgx_decode_rows with no unfinished live row returns
  *                     TGX_ERR_STATE; tgx_decode, tgx_step_async and tgx_forward return TGX_ERR_STATE while any row is finished (they would advance it).
  *   Retired rows      (tgx_reset_row) ride along as in tgx_decode; their out_ids are -1, out_new and out_finish 0.  tgx_forward_row starts the row's count afresh.
- *   Paged KV          blocks are assigned up front for past + n_steps; after the call a finished row's blocks beyond ceil(past / 128) go back to the pool.
+ *   Paged KV          blocks are assigned up front for past + n_steps; after the call a finished row's blocks beyond ceil(past / 128) go back to the pool.  The blocks
+ *                     of ALL the unfinished live rows are counted against the free list before any is assigned (tgx_decode and tgx_step_async likewise): a call
+ *                     refused for want of a block (TGX_ERR_CONTEXT) assigns none, steps no row and leaves kv.free_tokens as it was.
+ *   out_finish        of a row that had finished BEFORE the call repeats its reason (1 or 2); its out_new is 0 and its out_ids are -1.
  *   tgx_read_probs    after tgx_decode_rows: each row's vector under its own cfg (greedy rows read as zeros).
  *   Existing calls    tgx_decode, tgx_sample*, tgx_step_async ignore the row settings. */
 #define TGX_MAX_STOP_IDS 8

@@ -159,6 +159,31 @@ def test_the_budget_is_enforced_and_retired_rows_return_their_blocks(hip):
     np.testing.assert_array_equal(solo.decode(4, GREEDY)[:, 0], tail[:, 1])
 
 
+def test_steps_refused_for_want_of_blocks_assign_none(hip):
+    """three rows that each need one more block for the next 10 steps, ONE block free: tgx_decode_rows and tgx_decode return TGX_ERR_CONTEXT and leave kv.free_tokens
+    and every length as they were — the first row must not keep a block for steps that never ran (found by tests/test_hip_row_fuzz.py: the blocks used to be assigned
+    row by row, so a call refused at its second row left the pool one block short until the first row was reset)"""
+    paged, g = make("llama_tiny", hip, max_batch=3, max_ctx=512, budget=5 * 128)
+    V = paged.desc.vocab
+    p = np.resize(g["prompt"][0], 250).astype(np.int64) % V
+    paged.forward_rows([0, 1, 2], [p[:120], p[5:125], p])            # 1 + 1 + 2 blocks
+    for r in range(3):
+        paged.sample_row(r, GREEDY)
+    assert paged.get_option("kv.free_tokens") == 128
+    for call in (lambda: paged.decode_rows(10), lambda: paged.decode(10, GREEDY)):
+        with pytest.raises(TgxError) as ei:
+            call()
+        assert ei.value.status == 8 and "budget" in str(ei.value)
+        assert paged.get_option("kv.free_tokens") == 128
+        assert [paged.past_length_row(r) for r in range(3)] == [120, 120, 250]
+    paged.decode_rows(8)                                             # 128, 128, 258: one block, for row 2
+    assert paged.get_option("kv.free_tokens") == 0
+    paged.reset_row(2)
+    assert paged.get_option("kv.free_tokens") == 3 * 128
+    paged.decode_rows(10)
+    assert paged.get_option("kv.free_tokens") == 128 and [paged.past_length_row(r) for r in range(3)] == [138, 138, 0]
+
+
 def test_paged_needs_16_bit_storage_and_is_set_before_finalize(hip):
     cfg, g = load_golden("llama_tiny")
     d = desc_from_hf_config(cfg, "fp32")

@@ -477,9 +477,18 @@ static int read_tok_log(tgx_ctx* c, int64_t start, int n, int* dst) {
 // where they are, and the caller updates the rows' `past` from the device afterwards (rows may finish on the device)
 static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t seed, int n) {
   const bool rows = c->row_union >= 0;
-  if (c->kv_paged)       // every live row's next n positions have a block before the steps that write them are enqueued
+  if (c->kv_paged) {     // every live row's next n positions have a block before the steps that write them are enqueued
+    // all or nothing: the blocks of ALL the rows against the free list before any is assigned — a call refused at its third row must not leave the first two
+    // holding blocks for steps that never ran (kv.free_tokens would read low until those rows are reset)
+    long long need = 0;
+    for (int b = 0; b < c->batch; b++)
+      if (!c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin) need += std::max(0, c->kv.blocks_for(c->row_host[(size_t)b].past + n) - c->kv.row_blocks(b));
+    if (need > (long long)c->kv.free_blocks())
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: %d more steps need %lld more blocks of %d tokens, %zu free of %d (option kv.budget_tokens = %d)", n, need, tgx::KV_BLOCK,
+                     c->kv.free_blocks(), c->kv.n_blocks() - 1, c->kv_budget_tokens);
     for (int b = 0; b < c->batch; b++)
       if (!c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin) { int rc = kv_ensure_blocks(c, b, c->row_host[(size_t)b].past + n); if (rc) return rc; }
+  }
   if (rows) {
     for (int b = 0; b < c->batch; b++) { note_sampled(c, b, 1, row_cfg(c, b)); c->row_host[(size_t)b].probs_proc = (c->row_union & ROWU_PROC) != 0; }      // (a processed step passes every row through the processed slab)
   } else if (int rc = ensure_seed(c, cfg, seed)) return rc;
