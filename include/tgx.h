@@ -31,6 +31,7 @@ extern "C" {
 /* (still 3: additive) tgx_forward_rows; tgx_fork_row — a live row copied into other rows, its full paged KV blocks shared by reference. */
 /* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
+/* (still 3: additive) tgx_verify_row_sampled — the same under the row's own sampler: exact by the draw identity; tgx_read_pass_logits — the pass's logits (diagnostic). */
 /* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
 /* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
 /* (still 3: additive) tgx_row_snapshot_bytes / tgx_save_row / tgx_restore_row — a live row saved to host memory and restored into any row of any context of the same geometry. */
@@ -394,6 +395,40 @@ TGX_API int tgx_restore_row(tgx_ctx* ctx, int row, const void* buf, int64_t byte
  *   Cost              one weight pass for the layers, and for lm_head one pass on the matrix-core route of 5-16 positions, ceil((n_draft + 1) / 4) otherwise. */
 #define TGX_MAX_DRAFT 15
 TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_draft, int64_t* out_ids /* [n_draft + 1] */, int32_t* out_n, int32_t* out_finish);
+
+/* ---- speculative decoding under sampling: verifying a draft with the row's own sampler (additive to ABI 3) ----------------------------------------------
+ * tgx_verify_row for a row that SAMPLES.  A sampled token here is a pure function of its position's fp32 logits, the row's sampler settings and the draw key
+ * (row seed, index of the produced token, row) — tgx_decode_rows draws with nothing else.  The token s[i] the row would draw at position i of the pass is
+ * therefore known from that position's logits alone, and "accept while the draft equals the draw" produces precisely the ids tgx_decode_rows would have
+ * produced: the output distribution is untouched by construction, with no rejection-sampling arithmetic.  For a point-mass draft (prompt lookup) a draft token
+ * is accepted with its probability under the filtered distribution, as in textbook speculative sampling.
+ *
+ *   The pass          tgx_verify_row's: the inputs [t0, draft[0], .., draft[n_draft - 1]] at positions past .. past + n_draft, the logits v_i of every position.
+ *                     s[i] = the token the row's OWN settings (tgx_set_row_sampler: cfg and seed) draw from v_i with the key (row seed, past + i + 1, row), the
+ *                     key tgx_decode_rows would use for the token at that index.  a = the number of leading i with s[i] == draft[i]; the row produces a + 1
+ *                     tokens: draft[0 .. a - 1] followed by s[a].
+ *   Greedy row        the call IS tgx_verify_row: the same launches, the same bits.
+ *   Afterwards        the row stands as after out_n steps of tgx_decode_rows, up to the order of the fp32 sums: length past + out_n, current token the last
+ *                     produced id, the logits slot and argmax partials those of the position that produced it, the next embedding gathered (GPT-2: with wpe).
+ *                     tgx_sample_row with the row's cfg and seed right after the call returns the last produced id again (same logits, same key).
+ *   Everything else   the refusals and their order, ALL OR NOTHING, the stop-condition walk (on the device, token by token), the paged-KV block accounting, "other
+ *                     rows keep their state bit for bit", steps and tickets: as for tgx_verify_row, word for word.  A logit processor on: TGX_ERR_UNSUPPORTED
+ *                     (penalty counting is sequential).  tgx_verify_row itself still refuses a sampled row.
+ *   Log-probabilities recorded as by tgx_verify_row, one record per produced token: the MODEL's distribution, which the sampler does not touch.
+ *   tgx_read_probs    the row has no vector until its next sampled step (the rule of tgx_fork_row): the pass's scratch is not the row's.
+ *   Memory            the first call on a sampled row allocates the positions' sampler workspace: 16 x vocab x 12 bytes of compacted lists and 16 scratch
+ *                     records.  A context that never makes such a call allocates nothing new and runs exactly the launches it ran before; greedy calls
+ *                     through this entry allocate only what tgx_verify_row allocates.
+ *   Cost              tgx_verify_row's, plus ONE sampler chain of the row's cfg whose launches carry the n_draft + 1 positions on blockIdx.y (3 launches for
+ *                     T / top-p, the CLI default).  Measured (profiles/verify_sampled.txt; Llama-3.2-1B bf16, context 2048, T 0.8 / top-p 0.9, ms per call):
+ *                     1.313 / 1.250 / 1.312 at 4 / 8 / 16 positions against 1.297 / 1.239 / 1.303 for the greedy verify of the same build: +0.010 .. +0.016,
+ *                     less than the +0.037 one row's chain adds to a decode step (0.788 against 0.750). */
+TGX_API int tgx_verify_row_sampled(tgx_ctx* ctx, int row, const int64_t* draft, int n_draft, int64_t* out_ids /* [n_draft + 1] */, int32_t* out_n, int32_t* out_finish);
+
+/* Test / diagnostic use, like tgx_read_kv: the fp32 logits [M][vocab] of the M = n_draft + 1 positions of the last tgx_verify_row / tgx_verify_row_sampled pass,
+ * *out_rows = M.  TGX_ERR_STATE when the workspace holds no such pass: no call yet, tgx_score_row's group form or another verify call that failed has used it
+ * since, or after tgx_reset_cache.  cap_rows < M: TGX_ERR_INVALID, nothing is written.  Synchronises the stream. */
+TGX_API int tgx_read_pass_logits(tgx_ctx* ctx, float* out /* [cap_rows][vocab] */, int cap_rows, int32_t* out_rows);
 
 /* ---- per-token log-probabilities on the device (additive to ABI 3) --------------------------------------------------------------------------------------
  * n-best ranking, beams and the completions protocol's `logprobs` / `top_logprobs` (the reference's server speaks it) need the model's opinion of the tokens it

@@ -113,6 +113,11 @@ def build_spec_draft_check(force: bool = False, verbose: bool = False):
     return _build_cpu_check("spec_draft_check", os.path.join(HOST, "spec_draft.h"), force, verbose)
 
 
+def build_spec_mode_check(force: bool = False, verbose: bool = False):
+    """tests/spec_mode_check.cpp, the CPU audit of host/spec_mode.h."""
+    return _build_cpu_check("spec_mode_check", os.path.join(HOST, "spec_mode.h"), force, verbose)
+
+
 def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = False):
     """The C++ host engine (no HIP needed: it dlopen()s the device shim): libtgx_host.so + the tgx_cli binary.
 

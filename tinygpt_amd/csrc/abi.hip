@@ -585,6 +585,7 @@ static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M, float* src = 
 // tgx_score_row on the routes without the matrix-core form: the R <= VERIFY_ROWS positions from g0 through the verify form's lm_head into the vf_* workspace
 // (hidden: their rows of ws_x; nullptr: staged in vf_x already, prefill by steps), then the tile and record launches of kernels/score.h over it
 static void launch_score_group(tgx_ctx* c, PrefillRoute rt, const ScoreCall& sc, int g0, int R, float* hidden) {
+  c->vf_pass_rows = 0;                     // the workspace no longer holds a verify pass (tgx_read_pass_logits)
   launch_lm_head_all(c, rt, R, hidden);
   launch_score_tiles(c, sc, c->vf_logits, c->d.vocab, 0, c->d.vocab, R, g0);
   launch_score_record(c, sc, R, g0);
@@ -1087,7 +1088,9 @@ int tgx_reset_cache(tgx_ctx* c) {
   if (c->slab_acc) HIP_OK(c, hipMemsetAsync(c->slab_acc, 0, (size_t)c->d.max_batch * c->d.hidden * 8, c->stream));
   if (c->lp_rows) HIP_OK(c, hipMemsetAsync(c->lp_rows, 0, (size_t)c->d.max_batch * sizeof(tgx::LpRow), c->stream));
   if (c->proc_hist) HIP_OK(c, hipMemsetAsync(c->proc_hist, 0, (size_t)c->d.max_batch * c->d.vocab * sizeof(unsigned int), c->stream));
+  if (int rc = vs_rezero(c)) return rc;      // (a sampled verify pass that failed half-way may have left its histograms)
   HIP_OK(c, hipStreamSynchronize(c->stream));
+  c->vf_pass_rows = 0;
   c->past = 0;
   for (RowHost& r : c->row_host) { r.restart(0, /*idle=*/false, /*fin=*/0); r.lp_count = 0; }
   c->have_logits = c->have_token = false;
@@ -1656,7 +1659,10 @@ static int ensure_verify_ws(tgx_ctx* c) {      // (tgx_score_row's group form ho
   return dev_alloc(c, &c->vf_rec, sizeof(tgx::VerifyRecord) / 4);
 }
 
-int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+// both entry points: tgx_verify_row (`sampled_entry` false: a row that does not sample greedily is refused) and tgx_verify_row_sampled (such a row's positions are
+// drawn by its own sampler between the pass and the accept launch; a greedy row takes exactly tgx_verify_row's launches)
+static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, bool sampled_entry) {
+  const char* const fn = sampled_entry ? "tgx_verify_row_sampled" : "tgx_verify_row";
   if (!c || !draft || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "verify before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
@@ -1672,8 +1678,9 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
   if (rh.nologits) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
   if (!rh.tok) return set_err(c, TGX_ERR_STATE, "row %d has no current token: tgx_sample_row it first", row);
   const tgx_sampler_cfg cfg = row_cfg(c, row);
-  if (!is_greedy(&cfg)) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
-  if (row_processed(c, row)) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d has a logit processor on (the accept rule compares raw argmaxes)", row);
+  const bool sampled = !is_greedy(&cfg);
+  if (sampled && !sampled_entry) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
+  if (row_processed(c, row)) return set_err(c, TGX_ERR_UNSUPPORTED, "%s: row %d has a logit processor on (the accept rule compares raw argmaxes)", fn, row);
   const int M = n_draft + 1;
   const long long past = rh.past;
   if (past + M > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, M, d.max_ctx);
@@ -1681,7 +1688,7 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
   if (c->kv_paged) {
     const PrefillRoute rt = prefill_route(c, M, M);
     if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
-      return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+      return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
     const long long need = c->kv.blocks_for(past + M) - c->kv.row_blocks(row), have = c->kv.available_for(nullptr, 0);
     if (need > have)
       return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
@@ -1690,33 +1697,62 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
   }
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_verify_ws(c)) return rc;
+  if (sampled) if (int rc = vs_alloc(c)) return rc;      // the positions' sampler workspace: only a sampled row's call ever holds it
   if (int rc = ensure_extend_ws(c, M, (int)past)) return rc;
+  c->vf_pass_rows = 0;                             // the workspace changes hands
   (void)kv_ensure_blocks(c, row, past + M);        // the whole pass up front; cannot fail: counted above
   long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the draft; input 0 is written on the device from the row's token word
   for (int i = 0; i < n_draft; i++) ids[i + 1] = draft[i];
   HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
   launch_verify_first_id(c, row);
   if (int rc = issue_pass(c, row, 1, M, (int)past, /*verify=*/true)) return rc;
-  launch_verify_accept(c, row, M);
+  if (sampled) launch_sample_positions(c, row, M, cfg);      // every position's draw under the row's settings, with the key its step would use
+  launch_verify_accept(c, row, M, sampled ? c->vs_draws : nullptr);
   const bool records = row_records(c, row);
   if (records) launch_logprobs_verify(c, row, M);      // one record per produced token, each from the logits of the position that produced it
   tgx::VerifyRecord rec{};
   HIP_OK(c, hipMemcpyAsync(&rec, c->vf_rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
   if (int rc = finish_pass(c)) return rc;
-  if (rec.n < 1 || rec.n > M) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "tgx_verify_row: the accept launch left no record"); }
+  if (rec.n < 1 || rec.n > M) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record", fn); }
+  c->vf_pass_rows = M;
   // ---- the host follows the device: length, blocks, finished state
   RowHost& r = c->row_host[(size_t)row];
   r.past = past + rec.n;
   r.fin = (char)rec.finish;
   if (records) r.lp_count += rec.n;
   kv_trim_row(c, row, r.past);                     // the blocks assigned for the rejected tail go back to the pool
-  note_sampled(c, row, 1, cfg);                    // greedy: tgx_read_probs reads zeros for the row
+  if (!sampled) note_sampled(c, row, 1, cfg);      // greedy: tgx_read_probs reads zeros for the row
+  else {                                           // the pass's scratch is not the row's: no vector until its next sampled step (the rule of tgx_fork_row)
+    r.probs_ok = false;
+    c->have_probs = false;
+    for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
+  }
   for (int i = 0; i < rec.n; i++) out_ids[i] = rec.ids[i];
   *out_n = rec.n; *out_finish = rec.finish;
   if (row == 0) c->last_sampled0 = rec.ids[rec.n - 1];
   refresh_longest(c);
   c->have_logits = true;
   HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  return verify_row_impl(c, row, draft, n_draft, out_ids, out_n, out_finish, /*sampled_entry=*/false);
+}
+int tgx_verify_row_sampled(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  return verify_row_impl(c, row, draft, n_draft, out_ids, out_n, out_finish, /*sampled_entry=*/true);
+}
+
+// test / diagnostic use: the fp32 logits [M][V] of the last verify pass, while the workspace still holds them
+int tgx_read_pass_logits(tgx_ctx* c, float* out, int cap_rows, int32_t* out_rows) {
+  if (!c || !out || !out_rows) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  const int M = c->vf_pass_rows;
+  if (M < 1 || !c->vf_logits) return set_err(c, TGX_ERR_STATE, "no verify pass to read: the workspace holds none (no call yet, or another call has used it since)");
+  if (cap_rows < M) return set_err(c, TGX_ERR_INVALID, "cap_rows %d below the pass's %d positions", cap_rows, M);
+  HIP_OK(c, hipSetDevice(c->device));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  HIP_OK(c, hipMemcpy(out, c->vf_logits, (size_t)M * c->d.vocab * 4, hipMemcpyDeviceToHost));
+  *out_rows = M;
   return TGX_OK;
 }
 

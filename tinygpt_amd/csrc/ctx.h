@@ -324,6 +324,13 @@ struct tgx_ctx {
   // lm_head stage them here, four to a pass over the weights), logits and argmax partials, and the record the accept launch leaves for the host.  Sized at first use
   enum { VERIFY_ROWS = TGX_MAX_DRAFT + 1 };
   float *vf_x = nullptr, *vf_logits = nullptr, *vf_part_val = nullptr; int *vf_part_idx = nullptr, *vf_rec = nullptr;
+  int vf_pass_rows = 0;      // the positions of the verify pass whose logits vf_logits holds (tgx_read_pass_logits); 0: none, or another call has used the workspace since
+  // ... and tgx_verify_row_sampled on a sampled row: the staged sampler's scratch and compacted lists for the VERIFY_ROWS positions (the pass's, not the row's) and
+  // their draws.  Allocated by the first such call (vs_alloc): a context that never makes one holds none of it
+  tgx::SampScratch* vs_scratch = nullptr;
+  unsigned long long* vs_list_comp = nullptr;    // [VERIFY_ROWS][vocab]
+  float* vs_list_v = nullptr;
+  int* vs_draws = nullptr;                       // [VERIFY_ROWS]
   // ---- per-token log-probabilities (include/tgx.h tgx_set_row_logprobs; kernels/logprobs.h).  Allocated by the first call that switches a row on: the rows' record
   // rings and counters, and the tile launch's partials for max(max_batch, VERIFY_ROWS) rows (a verify pass puts its positions where a step puts its rows)
   tgx::LpRecord* lp_ring = nullptr;          // [max_batch][TGX_LOGPROB_RING]
@@ -429,7 +436,7 @@ void launch_embed_chunk(tgx_ctx* c, const long long* ids, int R, int pos0);
 void launch_add_pos(tgx_ctx* c, int* pos, int n);
 void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_val, int* part_idx);
 void launch_verify_first_id(tgx_ctx* c, int row);         // tgx_verify_row: prompt[0] of the row <- its current token
-void launch_verify_accept(tgx_ctx* c, int row, int M);    // ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h)
+void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws = nullptr);    // ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h); draws: the positions' sampled ids
 // ---- attn.hip (kernels/attn_decode.h, attn_decode_mfma.h)
 bool attn_batch_on_mfma(const tgx_ctx* c, int R);
 void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true);   // combine = false: the caller's o_proj merges the split records
@@ -440,6 +447,9 @@ enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16, ROWU_
 void launch_sample_rows(tgx_ctx* c, int row0, int R, int un);              // tgx_decode_rows: every row with its own settings (a decode step's sampler)
 int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);
+int vs_alloc(tgx_ctx* c);                                                    // tgx_verify_row_sampled: the positions' sampler workspace, at first use
+int vs_rezero(tgx_ctx* c);                                                   // ... its scratch back to the zero state the chain expects (tgx_reset_cache; stream-ordered; a no-op without the workspace)
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes)
 int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
 bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)

@@ -396,12 +396,13 @@ void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_
 void launch_verify_first_id(tgx_ctx* c, int row) {
   hipLaunchKernelGGL(tgx::verify_first_id_kernel, dim3(1), dim3(64), 0, c->stream, c->rows[(size_t)row].prompt, (const int*)c->rows[(size_t)row].tok);
 }
-// ... and behind the pass and the M positions' lm_head, ONE launch accepts the draft's matching prefix and leaves the row as that many greedy decode steps would
-void launch_verify_accept(tgx_ctx* c, int row, int M) {
+// ... and behind the pass and the M positions' lm_head, ONE launch accepts the draft's matching prefix and leaves the row as that many decode steps would
+// (draws: the positions' sampled ids, launch_sample_positions; nullptr: greedy)
+void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws) {
   RowState& r = c->rows[(size_t)row];
   tgx::VerifyArgs a{};
   a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
-  a.logits = c->vf_logits; a.draft = r.prompt + 1;
+  a.logits = c->vf_logits; a.draft = r.prompt + 1; a.draws = draws;
   a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
   a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
   a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;

@@ -199,6 +199,18 @@ __device__ __forceinline__ void row_count_and_stop(RowReq* q, const RowStopWords
   if (reason) q->finished = reason;
 }
 
+// ---- the draw key of a sampled token (kernels/sampler.h samp_draw): the uniform variate of a draw is splitmix64 of
+//   seed * 0x9E3779B97F4A7C15 + index * 0xD1342543DE82EF95 + row      (mod 2^64)
+// and of nothing else.  seed: the call's (tgx_sample / tgx_decode / tgx_sample_row) or the row's own (tgx_set_row_sampler: tgx_decode_rows,
+// tgx_verify_row_sampled); index: the index of the PRODUCED token in the row's sequence — the row's length when the draw follows an admission (tgx_sample,
+// tgx_sample_row: the position word as it stands), the length after the step for a decode step (position word + 1), and past + i + 1 for position i of a
+// sampled verify pass over a row that holds `past` positions (the pass leaves the position word alone until the accept launch); row: the batch row.
+// A draw is therefore a pure function of (logits, sampler settings, key): a verify pass that draws every position with the key the steps would use produces
+// the steps' ids, which is what makes "accept while the draft equals the draw" exact.
+__device__ __forceinline__ unsigned long long draw_key(unsigned long long seed, int index, int row) {
+  return seed * 0x9E3779B97F4A7C15ull + (unsigned long long)index * 0xD1342543DE82EF95ull + (unsigned long long)row;
+}
+
 // tgx_verify_row (kernels/verify.h): what the accept launch leaves for the host — the tokens the row produced in the call and its finish reason
 constexpr int VERIFY_MAX_POS = 16;      // TGX_MAX_DRAFT + 1 positions of one pass
 struct VerifyRecord { int n, finish; int ids[VERIFY_MAX_POS]; };

@@ -27,6 +27,9 @@
 // filters; T = 0.8 / top-p 0.9 (the CLI defaults): 3 launches (rounds 1-5: 8, +48 us per decode step at V = 128 256; the
 // one-workgroup version of round 1 added 600 us; profiles/r06_sampler_cost.txt).  The final probability vector
 // (tgx_read_probs) is not part of a step: it is evaluated on demand from the thresholds and normalisers the step left.
+// Positions mode (tgx_verify_row_sampled): the same chain over the [M][V] logits of ONE row's verify pass, position on blockIdx.y, with a scratch of its own; its
+// last launch (the POS instantiations of the tail and the pick) draws every position with the key that position's token would have in a step (common.h draw_key)
+// into a vector of ids and publishes nothing.  The draw is samp_draw in every mode: the same logits and key give the same id everywhere.
 #pragma once
 #include "common.h"
 #include "gemv.h"
@@ -400,6 +403,9 @@ struct SampPickArgs {
   const unsigned long long* seed;   // device word
   FinalizeArgs fin;                 // token publish / rings / embedding of the launch's first row (part_* unused); row r of the launch = blockIdx.y:
   long long x_stride;               // tok + r, pos + r, x + r * x_stride (the rows' state lives in slabs)
+  int* draws;                       // positions mode (POS instantiations; tgx_verify_row_sampled): blockIdx.y = position i of ONE row's verify pass, `s` the pass's
+                                    // workspace and `fin` that row's own words (nothing is offset by i).  The launch draws with the row's seed for the token
+                                    // index *fin.pos + 1 + i (common.h draw_key) into draws[i] and publishes nothing; nullptr otherwise
 };
 
 // row r's view of the launch's finalize arguments
@@ -415,6 +421,7 @@ __device__ __forceinline__ FinalizeArgs samp_finalize_args(const SampPickArgs& p
 struct SampDrawWords {
   unsigned long long seed;
   int pos, step;
+  int index;                        // the index of the token this draw produces: the position word of the draw key
   RowStopWords stop;
 };
 template <bool ROWS = false>
@@ -422,27 +429,36 @@ __device__ __forceinline__ SampDrawWords samp_draw_words(const unsigned long lon
   SampDrawWords w;
   w.seed = ROWS ? fin.req->seed : *seed;
   w.pos = *fin.pos;
+  w.index = w.pos + fin.advance_pos;
   w.step = fin.log ? *fin.step : 0;
   if (ROWS) w.stop = row_stop_words(fin.req, fin.tok);
   return w;
 }
+// positions mode: position i of the row's verify pass draws what the row's step would draw for the token at index past + i + 1 (the pass has not moved *fin.pos)
+__device__ __forceinline__ SampDrawWords samp_position_words(const FinalizeArgs& fin, int i) {
+  SampDrawWords w{};
+  w.seed = fin.req->seed;
+  w.pos = *fin.pos;
+  w.index = w.pos + 1 + i;
+  return w;
+}
 
-// Inverse CDF in index order + the duties of finalize_greedy_kernel, run by the 256 threads of one workgroup.  pw[j] = the UNNORMALISED kept mass
+// Inverse CDF in index order, run by the 256 threads of one workgroup: THE draw of every sampled token — the steps', tgx_sample's and the positions of a
+// sampled verify pass alike, so that the same logits and the same key (common.h draw_key) give the same id everywhere.  pw[j] = the UNNORMALISED kept mass
 // (sum of exp(v - max) over the final kept set) of vocabulary tile 4 * tid + j; z = the kept set's normaliser; z0 = the normaliser of the set min-p
 // looks at (unused without min-p).  The tile that holds the draw comes from a block-wide prefix sum over the tile masses (x 1 / z in double); INSIDE
 // the tile the probabilities are the oracle's floats (e * inv) accumulated in double on top of the tiles below.  The two agree to ~1e-7 of the total:
 // a draw that close to a tile boundary takes the boundary's neighbour (the fallbacks below), every other draw is the oracle's.
-template <int DT, bool ROWS = false>
-__device__ __forceinline__ void samp_draw_and_publish(const SampArgs& a, const FinalizeArgs& fin, int nwg, int row, double (&pw)[4], const SampDrawWords& dw, float mx,
-                                                      float z, float z0, unsigned long long thr_k, unsigned long long thr_p, double* shd) {
-  __shared__ int s_wg, s_pick, s_last, s_pos;
+// `row`: where the launch's row (or position) sits in a's slabs; key_row: the batch row of the key.  Returns the drawn id in thread 0 (0 elsewhere).
+__device__ __forceinline__ int samp_draw(const SampArgs& a, int nwg, int row, double (&pw)[4], const SampDrawWords& dw, int key_row, float mx,
+                                         float z, float z0, unsigned long long thr_k, unsigned long long thr_p, double* shd) {
+  __shared__ int s_wg, s_pick, s_last;
   __shared__ double s_run, s_u;
   const int tid = threadIdx.x;
   const float inv = 1.0f / z;
   const double invd = (double)inv;
   if (tid == 0) {
-    unsigned long long s = dw.seed * 0x9E3779B97F4A7C15ull + (unsigned long long)(dw.pos + fin.advance_pos) * 0xD1342543DE82EF95ull +
-                           (unsigned long long)fin.row;
+    unsigned long long s = draw_key(dw.seed, dw.index, key_row);
     s_u = (double)(splitmix64(s) >> 11) * (1.0 / 9007199254740992.0);
     s_wg = 0x7fffffff; s_pick = 0x7fffffff; s_last = -1;
   }
@@ -509,15 +525,25 @@ __device__ __forceinline__ void samp_draw_and_publish(const SampArgs& a, const F
   if (hit != 0x7fffffff) atomicMin(&s_pick, hit);
   if (last >= 0) atomicMax(&s_last, last);
   __syncthreads();
+  int pick = 0;
   if (tid == 0) {
-    int pick = s_pick != 0x7fffffff ? s_pick : s_last;   // no hit inside the selected tile: its last kept entry
+    pick = s_pick != 0x7fffffff ? s_pick : s_last;       // no hit inside the selected tile: its last kept entry
     if ((unsigned)pick >= (unsigned)a.V) pick = 0;       // all-NaN logits: stay inside the embedding table
+  }
+  return pick;
+}
+
+// ... and the duties of finalize_greedy_kernel for the id thread 0 drew: token word, position, rings, step counter, the next embedding
+template <int DT, bool ROWS = false>
+__device__ __forceinline__ void samp_publish(const SampArgs& a, const FinalizeArgs& fin, int row, const SampDrawWords& dw, int pick) {
+  __shared__ int s_tok, s_pos;
+  if (threadIdx.x == 0) {
     int adv = fin.advance_pos, logged = pick;
     if (ROWS) {                                          // a finished row keeps its token and position; an unfinished one counts the token against its stops
       if (dw.stop.finished) { pick = dw.stop.tok; adv = 0; logged = -1; }
       else row_count_and_stop(fin.req, dw.stop, pick);
     }
-    s_pick = pick;
+    s_tok = pick;
     *fin.tok = pick;
     const int np = dw.pos + (adv ? 1 : 0);
     if (adv) *fin.pos = np;
@@ -532,17 +558,26 @@ __device__ __forceinline__ void samp_draw_and_publish(const SampArgs& a, const F
   }
   SAMP_STAMP(a.sc + row, 7);
   __syncthreads();
-  gather_embedding<DT>(fin.embed, s_pick, fin.x, fin.H, fin.wpe, fin.wpe ? s_pos : 0);
+  gather_embedding<DT>(fin.embed, s_tok, fin.x, fin.H, fin.wpe, fin.wpe ? s_pos : 0);
   __syncthreads();
   SAMP_STAMP(a.sc + row, 8);
   SAMP_STAMP_NEXT(a.sc + row);
 }
 
+// the end of a chain: draw, then publish — or, in positions mode, leave the id in draws[position] (a plain vector store) and touch nothing of the row
+template <int DT, bool ROWS, bool POS>
+__device__ __forceinline__ void samp_draw_finish(const SampPickArgs& pa, const SampArgs& a, const FinalizeArgs& fin, int row, double (&pw)[4], const SampDrawWords& dw,
+                                                 float mx, float z, float z0, unsigned long long thr_k, unsigned long long thr_p, double* shd) {
+  const int pick = samp_draw(a, pa.nwg, row, pw, dw, fin.row, mx, z, z0, thr_k, thr_p, shd);
+  if constexpr (POS) { if (threadIdx.x == 0) pa.draws[row] = pick; }
+  else samp_publish<DT, ROWS>(a, fin, row, dw, pick);
+}
+
 // ---- the tail: ONE workgroup per row takes the remaining four digits over the compacted list and derives the filter's threshold.  PICK (the last
 // filter of a chain without min-p): it also derives the kept set's normaliser and the kept mass of every
 // vocabulary tile (bulk sums of the compaction pass + the list's kept entries) and draws — the step's token leaves this launch
-// ROWS: launched as the PICK instantiation; whether the row draws here is its own (samp_row_apply)
-template <int MODE, bool PICK, int DT, bool ROWS = false>
+// ROWS: launched as the PICK instantiation; whether the row draws here is its own (samp_row_apply).  POS: the positions mode (SampPickArgs.draws)
+template <int MODE, bool PICK, int DT, bool ROWS = false, bool POS = false>
 __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs pa) {
   __shared__ unsigned long long sh4[4], sh_res[2];
   __shared__ float shf[4];
@@ -554,7 +589,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
   const int role = ROWS ? samp_row_apply(a, row, MODE == 0 ? SST_KT : SST_PT) : (PICK ? 2 : 1);
   if (ROWS && !role) return;
   const bool pick = PICK && role == 2;
-  const FinalizeArgs fin = samp_finalize_args(pa, row);
+  const FinalizeArgs fin = POS ? pa.fin : samp_finalize_args(pa, row);
   SampScratch* sc = a.sc + row;
   const unsigned long long* lc = a.list_comp + (size_t)row * a.V;
   const float* lv = a.list_v + (size_t)row * a.V;
@@ -564,7 +599,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
   double aw[4] = {0.0, 0.0, 0.0, 0.0};    // the compaction pass's bulk sums of this thread's four tiles (in flight beside the list)
   unsigned long long thr_k_prev = 0ull;
   if (pick) {
-    dw = samp_draw_words<ROWS>(pa.seed, fin);
+    dw = POS ? samp_position_words(fin, row) : samp_draw_words<ROWS>(pa.seed, fin);
 #pragma unroll
     for (int j = 0; j < 4; j++) { const int w = tid * 4 + j; const double t = sc->wg_above[min(w, nwg - 1)]; aw[j] = w < nwg ? t : 0.0; }
     if (MODE == 1 && a.top_k > 0) thr_k_prev = sc->thr_k;
@@ -672,7 +707,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
 #pragma unroll
   for (int j = 0; j < 4; j++) pw[j] = aw[j] + (double)lds_hist[tid * 4 + j] * (1.0 / 1099511627776.0);
   __syncthreads();                        // shd is reused by the draw
-  samp_draw_and_publish<DT, ROWS>(a, fin, nwg, row, pw, dw, mx, z, 0.f, MODE == 0 ? thr : thr_k_prev, MODE == 1 ? thr : 0ull, shd);
+  samp_draw_finish<DT, ROWS, POS>(pa, a, fin, row, pw, dw, mx, z, 0.f, MODE == 0 ? thr : thr_k_prev, MODE == 1 ? thr : 0ull, shd);
   for (int b = tid; b < SAMP_BINS; b += SAMP_WG) { if (MODE == 0) sc->cnt[0][b] = 0u; else sc->mass[0][b] = 0ull; }
   if (tid == 0) sc->list_n = 0u;
 }
@@ -730,20 +765,20 @@ __global__ __launch_bounds__(SAMP_WG) void samp_sum_kernel(const SampArgs a_in) 
 }
 
 // the draw of a chain that ends in partial-sum stages (min-p, or no filter at all): the tile masses are stage 1's sums
-template <int DT, bool ROWS = false>
+template <int DT, bool ROWS = false, bool POS = false>
 __global__ __launch_bounds__(SAMP_WG) void samp_pick_kernel(const SampPickArgs pa) {
   __shared__ float shf[4];
   __shared__ double shd[4];
   SampArgs a = pa.s;
   const int row = blockIdx.y, tid = threadIdx.x, nwg = pa.nwg;
   if (ROWS && !samp_row_apply(a, row, SST_PICK)) return;
-  const FinalizeArgs fin = samp_finalize_args(pa, row);
+  const FinalizeArgs fin = POS ? pa.fin : samp_finalize_args(pa, row);
   SampScratch* sc = a.sc + row;
   SAMP_STAMP(sc, 4);
   double pw[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) { const int w = tid * 4 + j; pw[j] = sc->wg_z2[min(w, nwg - 1)]; }
-  const SampDrawWords dw = samp_draw_words<ROWS>(pa.seed, fin);
+  const SampDrawWords dw = POS ? samp_position_words(fin, row) : samp_draw_words<ROWS>(pa.seed, fin);
   const unsigned long long thr_k = a.top_k > 0 ? sc->thr_k : 0ull, thr_p = a.top_p < 1.f ? sc->thr_p : 0ull;
   const float mx = samp_row_max(a, row, shf);
   const float z0 = a.min_p > 0.f ? samp_ordered_sum(sc->wg_z, nwg, shd) : 0.f;
@@ -751,7 +786,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_pick_kernel(const SampPickArgs p
   const float z = samp_ordered_sum(sc->wg_z2, nwg, shd);
   __syncthreads();
   SAMP_STAMP(sc, 5);
-  samp_draw_and_publish<DT, ROWS>(a, fin, nwg, row, pw, dw, mx, z, z0, thr_k, thr_p, shd);
+  samp_draw_finish<DT, ROWS, POS>(pa, a, fin, row, pw, dw, mx, z, z0, thr_k, thr_p, shd);
 }
 
 }  // namespace tgx

@@ -1,6 +1,7 @@
-// verify.h — the accept step of tgx_verify_row (include/tgx.h): greedy speculative decoding.  One causal pass ran the row's current token and its n_draft draft
+// verify.h — the accept step of tgx_verify_row / tgx_verify_row_sampled (include/tgx.h): speculative decoding.  One causal pass ran the row's current token and its n_draft draft
 // tokens (M = n_draft + 1 positions) and left the logits and the per-workgroup argmax partials of EVERY position in the call's workspace; this launch decides on
-// the device how many of them the row takes and leaves the row as that many greedy decode steps would: nothing here depends on the host knowing the count.
+// the device how many of them the row takes and leaves the row as that many decode steps would: nothing here depends on the host knowing the count.  Under
+// sampling the staged sampler's positions mode (kernels/sampler.h) ran in between and left every position's draw; the walk is the same.
 #pragma once
 #include "gemv.h"
 
@@ -12,6 +13,7 @@ struct VerifyArgs {
   long long part_stride;
   int n_part, M;
   const float* logits;       // [M][V]
+  const int* draws;          // [M] the row's sampler's draw of every position (tgx_verify_row_sampled on a sampled row), or nullptr: the merged argmax partials
   const long long* draft;    // [M - 1] the draft ids on the device (the pass's inputs 1 .. M - 1)
   int* tok;                  // the row's current token / position words
   int* pos;                  // (the pass did NOT advance it: it still holds `past`)
@@ -29,7 +31,8 @@ struct VerifyArgs {
 // the pass's first input is the row's device-resident current token: the host need not know it
 static __global__ void verify_first_id_kernel(long long* ids, const int* tok) { if (threadIdx.x == 0) ids[0] = *tok; }
 
-// One workgroup of 256 threads.  g[i] = the greedy token of position i (highest value, lowest index on a tie, the (unsigned)idx < V guard of finalize_row).
+// One workgroup of 256 threads.  g[i] = the token the row's settings choose at position i: the greedy token (highest value, lowest index on a tie, the
+// (unsigned)idx < V guard of finalize_row), or the sampler's draw a.draws[i].
 // The row produces g[0], then g[1] if g[0] == draft[0], ... : draft[0 .. a - 1] followed by g[a]; a produced token that finishes the row (stop id, max_new)
 // ends the walk.  The position that produced the last token hands the row its logits row and partials; the next embedding is gathered at the advanced position.
 template <int DT>
@@ -37,7 +40,11 @@ __global__ __launch_bounds__(256) void verify_accept_kernel(const VerifyArgs a) 
   __shared__ int s_g[VERIFY_MAX_POS];
   __shared__ int s_win, s_tok, s_pos;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int i = wv; i < a.M; i += 4) {      // a wave per position: merge its partials
+  for (int i = wv; i < a.M; i += 4) {      // a wave per position: its draw, or the merge of its partials
+    if (a.draws) {                         // (kernel-uniform)
+      if (lane == 0) { const int t = a.draws[i]; s_g[i] = (unsigned)t < (unsigned)a.V ? t : 0; }
+      continue;
+    }
     const float* pv = a.part_val + (size_t)i * a.part_stride;
     const int* pi = a.part_idx + (size_t)i * a.part_stride;
     float bv = -INFINITY; int bi = 0x7fffffff;

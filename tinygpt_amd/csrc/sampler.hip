@@ -38,29 +38,14 @@ static void finalize_from_processed(tgx_ctx* c, tgx::FinalizeArgs& f, int row) {
   f.part_val = c->proc_part_val + (size_t)row * T; f.part_idx = c->proc_part_idx + (size_t)row * T; f.n_part = T;
 }
 
-void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step, bool processed) {
-  if (is_greedy(&cfg)) {
-    if (!processed) { launch_finalize_greedy(c, row0, R, advance_pos, log_step); return; }
-    for (int b = row0; b < row0 + R; b++) {
-      tgx::FinalizeArgs f = make_finalize_args(c, b, advance_pos, log_step);
-      finalize_from_processed(c, f, b);
-      TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::finalize_greedy_kernel<DT>, dim3(1), dim3(256), 0, c->stream, f))
-    }
-    return;
-  }
-  tgx::SampArgs a = samp_args(c, row0, cfg, processed);
+// the uniform chain of `cfg` over R rows (blockIdx.y) of `a`: the stages every row of the launch takes, ending in the draw.  pa0: the draw's arguments (its `s` is
+// the chain's state at the draw).  positions: the draw-only mode of the tail and the pick (SampPickArgs.draws), else they publish for storage dtype c->dt
+static void launch_chain(tgx_ctx* c, tgx::SampArgs a, const tgx_sampler_cfg& cfg, int R, tgx::SampPickArgs pa0, bool positions) {
   const bool setK = cfg.top_k > 0, setP = cfg.top_p < 1.f, setM = cfg.min_p > 0.f;
   const int nwg = (a.V + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE;
   const dim3 grid(nwg, R), blk(tgx::SAMP_WG);
-  // the draw's arguments — the last launch of the chain, one workgroup per row (blockIdx.y; the row that completes the batch's count moves the step counter)
-  auto pick_args = [&](const tgx::SampArgs& now) {
-    tgx::SampPickArgs pa{};
-    pa.s = now;
-    pa.nwg = nwg; pa.seed = c->seed_dev;
-    pa.fin = make_finalize_args(c, row0, advance_pos, log_step);      // (the pick publishes the token it drew: the argmax partials are not read)
-    pa.x_stride = c->d.hidden;
-    return pa;
-  };
+  pa0.nwg = nwg;
+  auto pick_args = [&](const tgx::SampArgs& now) { tgx::SampPickArgs pa = pa0; pa.s = now; return pa; };
   // a filter = first digit over the vocabulary, compaction of the threshold's bin, the tail (four digits, threshold) in one workgroup; the tail of the
   // chain's LAST filter also draws when no min-p follows
   a.mx_ready = 0;                 // the first launch that needs max(logits / T) reduces the lm_head partials and leaves it in sc->mx for the others
@@ -68,6 +53,7 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
     constexpr int MODE = decltype(mode)::value;
     const tgx::SampPickArgs pa = pick_args(a);
     if (!draws) { hipLaunchKernelGGL((tgx::samp_tail_kernel<MODE, false, 0>), dim3(1, R), blk, 0, c->stream, pa); return; }
+    if (positions) { hipLaunchKernelGGL((tgx::samp_tail_kernel<MODE, true, 0, false, true>), dim3(1, R), blk, 0, c->stream, pa); return; }
     TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::samp_tail_kernel<MODE, true, DT>), dim3(1, R), blk, 0, c->stream, pa))
   };
   if (setK) {
@@ -89,8 +75,63 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
   a.mx_ready = 1;
   {
     const tgx::SampPickArgs pa = pick_args(a);
+    if (positions) { hipLaunchKernelGGL((tgx::samp_pick_kernel<0, false, true>), dim3(1, R), blk, 0, c->stream, pa); return; }
     TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::samp_pick_kernel<DT>, dim3(1, R), blk, 0, c->stream, pa))
   }
+}
+
+void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step, bool processed) {
+  if (is_greedy(&cfg)) {
+    if (!processed) { launch_finalize_greedy(c, row0, R, advance_pos, log_step); return; }
+    for (int b = row0; b < row0 + R; b++) {
+      tgx::FinalizeArgs f = make_finalize_args(c, b, advance_pos, log_step);
+      finalize_from_processed(c, f, b);
+      TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::finalize_greedy_kernel<DT>, dim3(1), dim3(256), 0, c->stream, f))
+    }
+    return;
+  }
+  // the draw's arguments — the last launch of the chain, one workgroup per row (blockIdx.y; the row that completes the batch's count moves the step counter)
+  tgx::SampPickArgs pa{};
+  pa.seed = c->seed_dev;
+  pa.fin = make_finalize_args(c, row0, advance_pos, log_step);      // (the pick publishes the token it drew: the argmax partials are not read)
+  pa.x_stride = c->d.hidden;
+  launch_chain(c, samp_args(c, row0, cfg, processed), cfg, R, pa, /*positions=*/false);
+}
+
+// tgx_verify_row_sampled: the M positions of row `row`'s verify pass ride on blockIdx.y of the uniform chain of the row's cfg, over the pass's logits and argmax
+// partials (vf_*) with a scratch and lists of their own (vs_*).  The end of the chain draws every position with the row's seed and the key of the token that
+// position produces (kernels/common.h draw_key) into vs_draws and publishes nothing: the accept launch decides what the row takes
+int vs_alloc(tgx_ctx* c) {
+  if (c->vs_draws) return TGX_OK;            // the last of the four: set only when all of them exist
+  const size_t R = tgx_ctx::VERIFY_ROWS, V = (size_t)c->d.vocab;
+  int rc;
+  if ((rc = dev_alloc(c, &c->vs_scratch, R)) || (rc = dev_alloc(c, &c->vs_list_comp, R * V)) || (rc = dev_alloc(c, &c->vs_list_v, R * V)) || (rc = dev_alloc(c, &c->vs_draws, R))) {
+    dev_free(c, &c->vs_scratch); dev_free(c, &c->vs_list_comp); dev_free(c, &c->vs_list_v); dev_free(c, &c->vs_draws);      // all or nothing, as proc_alloc
+    return rc;
+  }
+  return vs_rezero(c);      // (the chain's launches leave it zero again)
+}
+int vs_rezero(tgx_ctx* c) {
+  if (c->vs_scratch) HIP_OK(c, hipMemsetAsync(c->vs_scratch, 0, sizeof(tgx::SampScratch) * (size_t)tgx_ctx::VERIFY_ROWS, c->stream));
+  return TGX_OK;
+}
+
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg) {
+  if (!c->vs_draws || !c->vf_rec) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
+  const int V = c->d.vocab;
+  tgx::SampArgs a{};
+  a.logits = c->vf_logits; a.logits_stride = V;
+  a.part_val = c->vf_part_val; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
+  a.sc = c->vs_scratch;
+  a.V = V; a.idx_bits = 1;
+  while ((1 << a.idx_bits) < V) a.idx_bits++;
+  a.temperature = cfg.temperature; a.top_k = cfg.top_k; a.top_p = cfg.top_p; a.min_p = cfg.min_p;
+  a.list_comp = c->vs_list_comp; a.list_v = c->vs_list_v;
+  a.z_from_tail = ((cfg.top_k > 0 || cfg.top_p < 1.f) && !(cfg.min_p > 0.f)) ? 1 : 0;
+  tgx::SampPickArgs pa{};
+  pa.fin.pos = c->rows[(size_t)row].pos; pa.fin.req = c->row_req + row; pa.fin.row = row;      // the key's words: read, never written
+  pa.draws = c->vs_draws;
+  launch_chain(c, a, cfg, M, pa, /*positions=*/true);
 }
 
 // tgx_decode_rows: every row samples with its own settings (tgx_set_row_sampler; kernels/sampler.h samp_row_apply).  `un` = the union of the rows' chains

@@ -87,6 +87,8 @@ ABI = {
     "save_row": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
     "restore_row": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "verify_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "verify_row_sampled": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "read_pass_logits": (c_int, [c_void_p, POINTER(c_float), c_int, POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -341,6 +343,23 @@ class Model:
         ptr = draft.ctypes.data_as(POINTER(c_int64)) if len(draft) else (c_int64 * 1)()
         self._check(self.be.verify_row(self._ctx, row, ptr, len(draft), out.ctypes.data_as(POINTER(c_int64)), ctypes.byref(n), ctypes.byref(fin)))
         return out[:n.value].copy(), fin.value
+
+    def verify_row_sampled(self, row: int, draft):
+        """verify_row under the row's OWN sampler (include/tgx.h tgx_verify_row_sampled; set_row_sampler: cfg and seed): the row takes the draft's prefix that equals
+        its draws plus its own draw at the first mismatch, the ids decode_rows would have produced -> (produced ids, finish).  A greedy row: verify_row itself"""
+        draft = np.ascontiguousarray(np.asarray(draft, dtype=np.int64).reshape(-1))
+        out = np.empty(len(draft) + 1, dtype=np.int64)
+        n, fin = c_int32(0), c_int32(0)
+        ptr = draft.ctypes.data_as(POINTER(c_int64)) if len(draft) else (c_int64 * 1)()
+        self._check(self.be.verify_row_sampled(self._ctx, row, ptr, len(draft), out.ctypes.data_as(POINTER(c_int64)), ctypes.byref(n), ctypes.byref(fin)))
+        return out[:n.value].copy(), fin.value
+
+    def pass_logits(self) -> np.ndarray:
+        """the fp32 logits [M][vocab] of the last verify pass's M positions (include/tgx.h tgx_read_pass_logits; test / diagnostic use)"""
+        out = np.empty((16, self.desc.vocab), dtype=np.float32)      # TGX_MAX_DRAFT + 1 positions at the most
+        m = c_int32(0)
+        self._check(self.be.read_pass_logits(self._ctx, out.ctypes.data_as(POINTER(c_float)), 16, ctypes.byref(m)))
+        return out[:m.value].copy()
 
     def sample_row(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0) -> int:
         out = c_int64()

@@ -1,5 +1,6 @@
 #include "engine.h"
 #include "../csrc/row_snapshot.h"
+#include "spec_mode.h"
 
 #include <chrono>
 
@@ -218,11 +219,20 @@ ScoreOutput GPTEngine::score(const std::string& text, int topN) {
 }
 
 // ---- GPTConfig::speculate: prompt-lookup drafts verified in one pass (spec_draft.h, include/tgx.h tgx_verify_row)
-bool GPTEngine::speculateActive(int batch) const {
-  const SamplerConfig& s = config_.samplerConfig;
-  const bool greedy = !(s.temperature > 0.f || s.topK > 0 || s.topP < 1.f || s.minP > 0.f);      // Sampler.cpp:15-21
-  return config_.speculate > 0 && batch == 1 && greedy && !processorsOn() && be_.verify_row && be_.set_row_stop && be_.decode_rows && eosTokenIds_.size() <= (size_t)TGX_MAX_STOP_IDS;
+// (which of the two, or neither: spec_mode.h)
+static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int batch, bool processors, size_t stopIds) {
+  const SamplerConfig& s = cfg.samplerConfig;
+  tgxh::SpecInputs in;
+  in.speculate = cfg.speculate; in.speculateSampled = cfg.speculateSampled; in.batch = batch;
+  in.greedy = !(s.temperature > 0.f || s.topK > 0 || s.topP < 1.f || s.minP > 0.f);      // Sampler.cpp:15-21
+  in.processors = processors; in.stopIds = stopIds; in.maxStopIds = (size_t)TGX_MAX_STOP_IDS;
+  in.rowStopCalls = be.set_row_stop && be.decode_rows;
+  in.verifyRow = be.verify_row != nullptr;
+  in.verifyRowSampled = be.verify_row_sampled && be.set_row_sampler && be.sample_row;
+  return tgxh::spec_mode(in);
 }
+bool GPTEngine::speculateActive(int batch) const { return spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) != tgxh::SpecMode::Off; }
+bool GPTEngine::speculateSampledActive(int batch) const { return spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) == tgxh::SpecMode::Sampled; }
 
 bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
   const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
@@ -234,7 +244,8 @@ bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool&
   if (!draft.empty()) {
     int64_t d64[TGX_MAX_DRAFT];
     for (size_t i = 0; i < draft.size(); i++) d64[i] = draft[i];
-    if (be_.verify_row(model_.ctx, 0, d64, (int)draft.size(), ids, &n, &fin) != TGX_OK) return fail(std::string("verify: ") + be_.last_error(model_.ctx));
+    const auto verify = speculateSampledActive(1) ? be_.verify_row_sampled : be_.verify_row;      // (the row's sampler is the call's: rowsBegin)
+    if (verify(model_.ctx, 0, d64, (int)draft.size(), ids, &n, &fin) != TGX_OK) return fail(std::string("verify: ") + be_.last_error(model_.ctx));
     spec_.verifyCalls++; spec_.draftTokens += (int64_t)draft.size(); spec_.acceptedDrafts += n - 1; spec_.producedHist[n]++;
   } else {
     if (be_.decode_rows(model_.ctx, 1, ids, &n, &fin) != TGX_OK) return fail(std::string("decode: ") + be_.last_error(model_.ctx));
@@ -325,6 +336,12 @@ bool GPTEngine::logprobsDrain(int row, int64_t n, RowLogprobs& into) {
 template <class F> struct AtExit { F f; ~AtExit() { f(); } };
 template <class F> AtExit<F> at_exit(F f) { return AtExit<F>{std::move(f)}; }
 
+// GPTConfig::speculateSampled made row 0's sampler the call's: back to the default, so that a later greedy call's per-row steps are greedy whatever ran before
+void GPTEngine::rowSamplerEnd() {
+  const tgx_sampler_cfg greedy{0.f, 0, 1.f, 0.f};
+  be_.set_row_sampler(model_.ctx, 0, &greedy, 0);
+}
+
 void GPTEngine::logprobsEnd(int batch) {
   for (int b = 0; b < batch; b++) be_.set_row_logprobs(model_.ctx, b, -1);
 }
@@ -382,8 +399,9 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   const bool lpOn = logprobsActive();
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? B : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(B); });
-  const bool procOn = processorsOn(), perRow = lpOn || procOn;
+  const bool procOn = processorsOn(), specSampled = speculateSampledActive(B), perRow = lpOn || procOn || specSampled;
   const auto procOff = at_exit([&] { if (procOn) processorsEnd(B); });
+  const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(); });
   if (procOn)      // every row's history: the prompt it admitted, without the left padding
     for (int b = 0; b < B; b++) {
       const int64_t n = std::min<int64_t>((int64_t)prompts[(size_t)b].size(), S);
@@ -459,8 +477,9 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   const bool lpOn = logprobsActive();
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? 1 : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(1); });
-  const bool procOn = processorsOn(), perRow = lpOn || procOn;
+  const bool procOn = processorsOn(), specSampled = speculateSampledActive(1), perRow = lpOn || procOn || specSampled;
   const auto procOff = at_exit([&] { if (procOn) processorsEnd(1); });
+  const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(); });
   if (procOn && !processorsBegin(0, ids.data(), S)) return out;
   if (perRow) {
     std::vector<int64_t> first;

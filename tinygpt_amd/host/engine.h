@@ -56,6 +56,12 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // for a greedy sampler configuration, ONE sequence, at most TGX_MAX_STOP_IDS EOS ids and a backend that has the calls — otherwise the existing loop runs.  The
   // produced ids are those of the existing loop up to the summation order between kernel paths (include/tgx.h tgx_verify_row).
   int speculate = 0;
+  // ... and under a SAMPLING configuration (default false: every existing run is unchanged).  With it set, speculate > 0, one sequence, a non-greedy sampler,
+  // neutral processors and a backend that exports tgx_verify_row_sampled, the generate loops take the per-row path: the row's sampler is the call's
+  // (tgx_set_row_sampler), the first token comes from tgx_sample_row, prompt-lookup drafts go through tgx_verify_row_sampled and steps without a draft through
+  // tgx_decode_rows.  A sampled token is a pure function of its logits and the draw key (seed, token index, row), so the ids are those of the plain loop up to
+  // the summation order between kernel paths.  A backend without the call keeps the old loop.
+  bool speculateSampled = false;
   // Not in the reference's engine (its server speaks the completions protocol's `logprobs`): -1 = off, the loops below exactly as they were.  N in
   // [0, TGX_MAX_LOGPROBS]: every produced token comes with its log-probability under the model's distribution and the N most likely alternatives
   // (include/tgx.h tgx_set_row_logprobs).  The engine then steps through tgx_sample_row / tgx_decode_rows (tgx_verify_row under `speculate`) and drains the rows'
@@ -165,6 +171,7 @@ class GPTEngine {
   }
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
   void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
+  void setSpeculateSampled(bool on) { config_.speculateSampled = on; }
   void setLogprobs(int topN) { config_.logprobs = topN; }
   const SamplerConfig& samplerConfig() const { return config_.samplerConfig; }
   void setProcessors(float repetition, float presence, float frequency, std::map<int32_t, float> bias) {      // kept by the C view across tgxe_reconfigure
@@ -181,6 +188,7 @@ class GPTEngine {
   bool sessionCapable(const char* what);                       // prefix reuse active and the backend has the snapshot calls; else err_ set
   bool prefillReusing(const std::vector<int64_t>& ids);      // the prompt after its cached prefix; false: nothing reusable (the caller resets and prefills)
   bool speculateActive(int batch) const;                      // GPTConfig::speculate applies to this call
+  bool speculateSampledActive(int batch) const;               // ... through tgx_verify_row_sampled (GPTConfig::speculateSampled; spec_mode.h)
   // row 0 holds seq minus its last token, which is its current token; the row's stop conditions are set.  Drafts from seq, verifies (or takes one ordinary
   // step), appends what the row produced — never more than maxTotal tokens in seq.  finished: the row finished on the device.  false: a call failed (err_ set)
   bool speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished);
@@ -190,6 +198,7 @@ class GPTEngine {
   bool logprobsRefused(bool async);                                                            // logprobs asked for and not servable: err_ set, the generate call fails
   bool logprobsDrain(int row, int64_t n, RowLogprobs& into);                                  // appends the row's last n records
   void logprobsEnd(int batch);
+  void rowSamplerEnd();                                       // GPTConfig::speculateSampled: row 0's sampler back to the default when the call ends
   void logprobsStore(GPTOutput& out, const std::vector<RowLogprobs>& rows, int64_t perRow) const;
   // SamplerConfig's penalties / logit bias
   bool processorsOn() const { return !config_.samplerConfig.processorsNeutral(); }

@@ -64,6 +64,10 @@ TGXE_API int tgxe_load_session(tgxe_engine* h, const char* path) { return h && p
 // greedy speculative decoding (GPTConfig::speculate): the maximum draft length (0 = off); tgxe_spec_stats writes {verify calls, draft tokens, accepted draft
 // tokens, ordinary steps, produced-per-verify histogram [0 .. TGX_MAX_DRAFT + 1]} (up to cap values) and returns how many there are
 TGXE_API void tgxe_set_speculate(tgxe_engine* h, int max_draft) { if (h) h->e->setSpeculate(max_draft); }
+// ... under a sampling configuration as well (GPTConfig::speculateSampled; 0 = off, the default)
+TGXE_API void tgxe_set_speculate_sampled(tgxe_engine* h, int on) { if (h) h->e->setSpeculateSampled(on != 0); }
+// the engine's device context (GPTEngine::ctx): for the diagnostic calls of include/tgx.h (tgx_read_pass_logits, tgx_read_kv) on what the engine just ran
+TGXE_API void* tgxe_ctx(tgxe_engine* h) { return h ? (void*)h->e->ctx() : nullptr; }
 TGXE_API int tgxe_spec_stats(tgxe_engine* h, int64_t* out, int cap) {
   const tgxh::SpecStats& s = h->e->specStats();
   const int n_hist = (int)(sizeof s.producedHist / sizeof s.producedHist[0]);

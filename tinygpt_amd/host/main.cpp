@@ -47,7 +47,8 @@ static void usage(const char* prog) {
           "  --session-save <file>     with --stream and one text prompt: keep the conversation's KV cache (prompt + generated tokens) in a file when the run ends\n"
           "                            (neither flag combines with --speculate, --logprobs, the penalties or --logit-bias: those runs end with the row finished on the\n"
           "                            device, which keeps no cache to save)\n"
-          "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n",
+          "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n"
+          "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n",
           prog);
 }
 
@@ -115,6 +116,7 @@ int main(int argc, char** argv) {
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
+    else if (a == "--speculate-sampled") cfg.speculateSampled = true;
     else if (a == "--session-load") session_load = next();
     else if (a == "--session-save") session_save = next();
     else if (a == "--logprobs") cfg.logprobs = atoi(next());

@@ -10,7 +10,13 @@ the figures of one column differ only in the call; the cases are interleaved ove
   derived: break-even accepted drafts = verify / step - 1; tokens/s at acceptance 0, half, full = (1, n_draft // 2 + 1, n_draft + 1) / verify
   free-running: the host engine, speculate 0 against 7 with prompt lookup on a prompt made of a repeated span, with the histogram of tokens per verify pass
 
-usage: python tools/spec_bench.py [--reps 9] [--out profiles/verify_row.txt]"""
+usage: python tools/spec_bench.py [--reps 9] [--out profiles/verify_row.txt]
+
+--sampler T,K,P,M (profiles/verify_sampled.txt): tgx_verify_row_sampled under that sampler instead.  Per pass at 4 / 8 / 16 positions, interleaved over the repeats:
+the sampled verify (drafts from the row's own sampled run: all accepted, as far as the two paths agree), the greedy verify of the same build, one sampled and one
+greedy tgx_decode_rows step of this build and — with --parent-lib, a libtgx_mi355x.so built from the parent commit, loaded beside this one — one sampled step of the
+parent.  Then the host engine free-running with speculateSampled on the repetitive prompt: tokens per pass and acceptance.
+usage: python tools/spec_bench.py --sampler 0.8,0,0.9,0 [--parent-lib PATH] [--reps 9] [--out profiles/verify_sampled.txt]"""
 import argparse
 import ctypes
 import os
@@ -143,11 +149,126 @@ def free_running(lines):
     e.close()
 
 
+def measure_sampled(cfg, reps, lines, parent_lib):
+    from tinygpt_amd.ffi import ABI, Backend, SamplerCfg
+    d = known_desc("llama-3.2-1b", "bf16")
+    d.max_batch = 1
+    seed = 7
+    m = Model(d).load_synthetic(1234, 0.02).finalize()
+    old = None
+    if parent_lib:      # the parent commit's library beside this one: every symbol it has (it lacks the new ones)
+        old = Model(d, backend=Backend(parent_lib, "tgx_", required=[n for n in ABI if n not in ("verify_row_sampled", "read_pass_logits")])).load_synthetic(1234, 0.02).finalize()
+    V = d.vocab
+    prompt = synth.synth_prompt(V, S, 1234)
+
+    def fresh_row(mm, c):
+        mm.reset_cache()
+        mm.forward_row(0, prompt)
+        mm.set_row_sampler(0, c, seed)
+        return int(mm.sample_row(0, c, seed))
+
+    fresh_row(m, cfg)
+    ref_s = [int(t) for t in m.decode_rows(16)[0][:, 0]]       # the row's own sampled run
+    fresh_row(m, GREEDY)
+    ref_g = [int(t) for t in m.decode_rows(16)[0][:, 0]]
+    lines.append("sampler: T %g top-k %d top-p %g min-p %g, row seed %d; unpaged; ms per call, synchronised: median (min .. max) over %d interleaved repeats" % (
+        cfg.temperature, cfg.top_k, cfg.top_p, cfg.min_p, seed, reps))
+    ND = [3, 7, 15]
+    tv = {(n, k): [] for n in ND for k in ("sampled", "greedy")}
+    acc = {n: [] for n in ND}
+    ts = {k: [] for k in ("step sampled", "step greedy", "parent step sampled")}
+    for rep in range(reps + 2):                                # two warm-up rounds, discarded
+        keep = rep >= 2
+        for n in ND:
+            fresh_row(m, cfg)
+            ms, r = timed(lambda: m.verify_row_sampled(0, ref_s[:n]))
+            if keep:
+                tv[(n, "sampled")].append(ms); acc[n].append(len(r[0]))
+            fresh_row(m, GREEDY)
+            ms, _ = timed(lambda: m.verify_row(0, ref_g[:n]))
+            if keep:
+                tv[(n, "greedy")].append(ms)
+        for k, mm, c in (("step sampled", m, cfg), ("parent step sampled", old, cfg), ("step greedy", m, GREEDY)):      # A / B side by side
+            if mm is None:
+                continue
+            fresh_row(mm, c)
+            ms, _ = timed(lambda: mm.decode_rows(1))
+            if keep:
+                ts[k].append(ms)
+    for k in ts:
+        if ts[k]:
+            lines.append("  one tgx_decode_rows step, %-20s %s" % (k + ":", med(ts[k])))
+    chain = statistics.median(ts["step sampled"]) - statistics.median(ts["step greedy"])
+    lines.append("  one row's sampler chain (sampled step - greedy step, this build): %+.3f ms" % chain)
+    lines.append("  positions | sampled verify | greedy verify | surcharge | surcharge / one row's chain | sampled verify / parent's sampled step | tokens produced by the all-right draft (median)")
+    base = statistics.median(ts["parent step sampled"] or ts["step sampled"])
+    for n in ND:
+        a_, g_ = statistics.median(tv[(n, "sampled")]), statistics.median(tv[(n, "greedy")])
+        lines.append("  %9d | %s | %s | %+.3f | %.2f | %.2f | %d of %d" % (n + 1, med(tv[(n, "sampled")]), med(tv[(n, "greedy")]), a_ - g_, (a_ - g_) / chain if chain > 0 else float("nan"),
+                                                                  a_ / base, statistics.median(acc[n]), n + 1))
+    m.close()
+    if old is not None:
+        old.close()
+
+
+def free_running_sampled(cfg, lines):
+    from ctypes import POINTER, c_int, c_int64, c_void_p
+    from host_util import HostEngine, host_lib
+    lib = host_lib()
+    lib.tgxe_set_speculate.argtypes = [c_void_p, c_int]
+    lib.tgxe_set_speculate_sampled.argtypes = [c_void_p, c_int]
+    lib.tgxe_spec_stats.restype = c_int
+    lib.tgxe_spec_stats.argtypes = [c_void_p, POINTER(c_int64), c_int]
+    e = HostEngine(lib, synthetic="llama-3.2-1b", device="mi355x", dtype=1, max_batch=1)
+    assert e.prepare(), e.error()
+    span = synth.synth_prompt(128256, 64, 99).astype(np.int32)
+    prompt = np.tile(span, S // 64)
+    n_new = 256
+    res = {}
+    for rep in range(3):
+        for on in (0, 1):
+            lib.tgxe_set_speculate(e.h, 7)
+            lib.tgxe_set_speculate_sampled(e.h, on)
+            e.reconfigure(temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p, min_p=cfg.min_p, max_new=n_new)
+            t = time.perf_counter()
+            ids, new, fin = e.generate_sync([prompt])
+            res.setdefault(on, []).append(((time.perf_counter() - t) * 1e3, ids[0, len(prompt):].tolist()))
+    buf = (c_int64 * 32)()
+    lib.tgxe_spec_stats(e.h, buf, 32)
+    st = list(buf[:21])
+    first_diff = next((i for i, (a, b) in enumerate(zip(res[0][0][1], res[1][0][1])) if a != b), None)
+    lines.append("free-running generateSync under that sampler, speculate 7, %d new tokens after a %d-token prompt (a 64-token span repeated), whole call incl. prefill, ms: speculateSampled off %s | on %s" % (
+        n_new, len(prompt), med([r[0] for r in res[0]]), med([r[0] for r in res[1]])))
+    lines.append("  ids equal: %s" % ("yes" if first_diff is None else "up to new token %d (a draw inside the band between the kernel paths)" % first_diff))
+    passes = max(st[0], 1)
+    lines.append("  over the 3 runs with it on: %d verify passes, %d of %d draft tokens accepted (%.0f %%), %d ordinary steps; %.2f tokens per pass; tokens produced per verify pass 1..16: %s" % (
+        st[0], st[2], st[1], 100.0 * st[2] / max(st[1], 1), st[3], (st[2] + st[0]) / passes, st[5:21]))
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default="")
+    ap.add_argument("--sampler", default="", help="T,K,P,M: measure tgx_verify_row_sampled under this sampler instead")
+    ap.add_argument("--parent-lib", default="", help="with --sampler: a libtgx_mi355x.so of the parent commit, for the A/B step")
     a = ap.parse_args()
+    if a.sampler:
+        import torch
+        from tinygpt_amd.ffi import SamplerCfg
+        T, K, P, M = a.sampler.split(",")
+        cfg = SamplerCfg(float(T), int(K), float(P), float(M))
+        lines = ["tools/spec_bench.py --sampler %s --reps %d%s   device: %s   Llama-3.2-1B bf16 synthetic, prompt %d tokens" % (
+            a.sampler, a.reps, " --parent-lib <parent build>" if a.parent_lib else "", torch.cuda.get_device_name(0), S)]
+        measure_sampled(cfg, a.reps, lines, a.parent_lib)
+        free_running_sampled(cfg, lines)
+        text = "\n".join(lines) + "\n"
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     try:
         commit = subprocess.run(["git", "rev-parse", "--short", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip() or "working tree"
     except OSError:
