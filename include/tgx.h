@@ -32,6 +32,7 @@ extern "C" {
 /* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
 /* (still 3: additive) tgx_verify_row_sampled — the same under the row's own sampler: exact by the draw identity; tgx_read_pass_logits — the pass's logits (diagnostic). */
+/* (still 3: additive) tgx_verify_rows — the drafts of several rows verified in ONE joint pass and ONE accept launch; n_draft 0 rows step along. */
 /* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
 /* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
 /* (still 3: additive) tgx_row_snapshot_bytes / tgx_save_row / tgx_restore_row — a live row saved to host memory and restored into any row of any context of the same geometry. */
@@ -429,6 +430,52 @@ TGX_API int tgx_verify_row_sampled(tgx_ctx* ctx, int row, const int64_t* draft, 
  * *out_rows = M.  TGX_ERR_STATE when the workspace holds no such pass: no call yet, tgx_score_row's group form or another verify call that failed has used it
  * since, or after tgx_reset_cache.  cap_rows < M: TGX_ERR_INVALID, nothing is written.  Synchronises the stream. */
 TGX_API int tgx_read_pass_logits(tgx_ctx* ctx, float* out /* [cap_rows][vocab] */, int cap_rows, int32_t* out_rows);
+
+/* ---- batched speculative decoding: the drafts of several rows verified in one pass (additive to ABI 3) --------------------------------------------------
+ * tgx_verify_row_sampled for n rows at once.  A scheduler that holds a draft for some rows of its batch otherwise pays one pass over all the weights and one
+ * read-back PER ROW; here the current tokens and drafts of all named rows go through ONE causal pass (the ragged pass of tgx_forward_rows, each sequence from its
+ * own length), ONE lm_head over all positions and ONE accept launch, and the host reads n records back once.
+ *
+ *   Equivalence       the call equals n calls tgx_verify_row_sampled(rows[i], draft_i, n_draft[i], ..) in array order, up to the order of the fp32 sums (the
+ *                     contract between kernel paths).  Rows are independent, so the order is immaterial.  draft_i = the n_draft[i] ids behind those of the rows
+ *                     before it in `drafts`; row i's results are out_ids[i * (TGX_MAX_DRAFT + 1) ..], out_n[i], out_finish[i].
+ *   Settings, keys    every row uses its OWN settings: a greedy row applies tgx_verify_row's rule, a sampled row draws position j with the key (row seed,
+ *                     past_i + j + 1, row) — nothing another row does enters it.
+ *   n_draft[i] == 0   legal here (unlike the one-row calls): the row takes part with its current token alone and produces exactly one token, as one
+ *                     tgx_decode_rows step would.  A scheduler can advance every unfinished live row in one call, with or without a draft.
+ *   Limits            M = sum(n_draft[i] + 1) <= TGX_MAX_VERIFY_POSITIONS; n in [1, max_batch]; rows distinct.
+ *   Refused           per row in array order, each row's checks in tgx_verify_row_sampled's order with its codes: null pointers, a row out of range, n_draft
+ *                     outside [0, TGX_MAX_DRAFT], a draft id out of range, a row named twice, n < 1, M too large: TGX_ERR_INVALID.  A retired, empty or finished
+ *                     row, a row with no current token or no logits, a poisoned context: TGX_ERR_STATE.  A logit processor on any named row: TGX_ERR_UNSUPPORTED.
+ *                     past_i + n_draft[i] + 1 > max_ctx for any row: TGX_ERR_CONTEXT.  More than 1024 blocks per row on a matrix-core route: TGX_ERR_UNSUPPORTED.
+ *   Paged KV          the blocks of ALL named rows are counted together against the free list before any is assigned; if they do not all fit: TGX_ERR_CONTEXT.
+ *   ALL OR NOTHING    a refused call changes no row, moves no block, leaves kv.free_tokens as it was and does not poison the context.
+ *   Afterwards        per row, tgx_verify_row_sampled's statement word for word: length past_i + out_n[i] and the current token; the logits slot and argmax
+ *                     partials of the producing position; the next embedding gathered (GPT-2: with wpe at the advanced position); the stop-condition walk on the
+ *                     device, token by token; one log-probability record per produced token; no tgx_read_probs vector for a sampled row; paged blocks beyond
+ *                     ceil(new length / 128) back in the pool; on row 0 the last produced id becomes ticket 0's token.  Rows not named keep their state bit for
+ *                     bit and do not step; no ticket, token log or host ring moves.
+ *   tgx_read_pass_logits   after this call: all M positions in call order, *out_rows = M (cap_rows up to TGX_MAX_VERIFY_POSITIONS); otherwise unchanged.
+ *   Forms             read-only option `verify.last_form`: 0 no call yet, 1 the joint pass, 2 row by row.  Row by row — fp32 storage, `prefill.mfma` 0, layer
+ *                     shapes the matrix-core tile does not cover, M below the matrix-core routes' minimum — runs each row's own pass, draws and accept launch
+ *                     behind the joint checks and block count: the results are those of the one-row calls bit for bit.
+ *   Attention         option `extend.attn_splits` as for tgx_extend_row: 0 the per-sequence prompt attention from each past_i; N >= 1 the ragged key-split form
+ *                     (grid heads x N x rows; a row uses min(N, its key tiles) splits, merged in split order: the same bits from run to run); -1 splits when
+ *                     the longest past_i + n_draft[i] + 1 exceeds tgx_extend_row's threshold, with min(32, 2 * CUs / (n * heads)) splits (two workgroups per
+ *                     CU: measured, profiles/verify_rows.txt), unsplit below 2.  The threshold itself is the one measured for ONE row.  Read-only option
+ *                     `verify.last_splits`: the splits of the last joint pass (0: unsplit).
+ *   Memory            the first call sizes the joint workspace: 64 hidden rows, logits [64][vocab], argmax partials, n records, 64 draws.  A context that never
+ *                     makes the call allocates nothing new and runs exactly the launches it ran before.
+ *   Cost              measured (tools/spec_bench.py --rows, profiles/verify_rows.txt; Llama-3.2-1B bf16, context 2048, synchronised ms per call; baselines
+ *                     from the parent commit's library).  4 positions per row, 2 / 4 / 8 rows: the joint call takes 1.29 / 1.44 / 1.92 with greedy rows and
+ *                     1.35 / 1.60 / 2.14 with rows at T 0.8 / top-p 0.9, against 2.5 / 5.1 / 10.0 for as many one-row calls and 0.97 / 1.05 / 1.09 for one
+ *                     plain step of those rows.  8 positions per row: 1.35 / 1.63 / 2.12 and 1.42 / 1.80 / 2.40, against 2.4 / 4.8 / 9.4.  The joint pass
+ *                     beats plain stepping from a mean of 0.34 (2 rows, 4 positions, greedy) to 1.17 (8 rows, 8 positions, sampled) accepted draft tokens
+ *                     per row on.  Every sampled row adds its own sampler chain, about 0.03 ms per row. */
+#define TGX_MAX_VERIFY_POSITIONS 64
+TGX_API int tgx_verify_rows(tgx_ctx* ctx, int n, const int32_t* rows, const int64_t* drafts /* sum(n_draft) ids, back to back */,
+                            const int32_t* n_draft /* [n], each in [0, TGX_MAX_DRAFT] */, int64_t* out_ids /* [n][TGX_MAX_DRAFT + 1] */, int32_t* out_n /* [n] */,
+                            int32_t* out_finish /* [n] */);
 
 /* ---- per-token log-probabilities on the device (additive to ABI 3) --------------------------------------------------------------------------------------
  * n-best ranking, beams and the completions protocol's `logprobs` / `top_logprobs` (the reference's server speaks it) need the model's opinion of the tokens it

@@ -118,6 +118,11 @@ def build_spec_mode_check(force: bool = False, verbose: bool = False):
     return _build_cpu_check("spec_mode_check", os.path.join(HOST, "spec_mode.h"), force, verbose)
 
 
+def build_spec_rows_check(force: bool = False, verbose: bool = False):
+    """tests/spec_rows_check.cpp, the CPU audit of SpecInputs::verifyRows in host/spec_mode.h."""
+    return _build_cpu_check("spec_rows_check", os.path.join(HOST, "spec_mode.h"), force, verbose)
+
+
 def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = False):
     """The C++ host engine (no HIP needed: it dlopen()s the device shim): libtgx_host.so + the tgx_cli binary.
 

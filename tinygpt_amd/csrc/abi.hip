@@ -571,13 +571,18 @@ static int launch_route(tgx_ctx* c, PrefillRoute rt, int M, int row0, int NB, in
 // through the batched step's one-pass lm_head; every other route stages its hidden rows in vf_x (the matrix-core routes' ws_x here, prefill by steps chunk by chunk)
 // and runs the GEMV lm_head four rows per pass over the weights (a group of three rides as four: vf_x holds VERIFY_ROWS rows, the fourth's results are not read)
 // (src: the M hidden rows of a matrix-core route, default the first M of ws_x — a scoring pass feeds it one group of positions at a time)
-static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M, float* src = nullptr) {
+// (joint: tgx_verify_rows' joint pass — the M <= VERIFY_POSITIONS positions of all its rows into the vj_* workspace, the same two forms)
+static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M, float* src = nullptr, bool joint = false) {
   const size_t H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
-  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, c->vf_logits, c->vf_part_val, c->vf_part_idx, src); return; }
-  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(c->vf_x, src ? src : c->ws_x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, c->stream);
+  float* const x = joint ? c->vj_x : c->vf_x;
+  float* const logits = joint ? c->vj_logits : c->vf_logits;
+  float* const part_val = joint ? c->vj_part_val : c->vf_part_val;
+  int* const part_idx = joint ? c->vj_part_idx : c->vf_part_idx;
+  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, logits, part_val, part_idx, src); return; }
+  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(x, src ? src : c->ws_x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, c->stream);
   for (int m0 = 0; m0 < M;) {
     const int rem = M - m0, R = rem >= 3 ? 4 : rem;
-    launch_lm_head_at(c, c->vf_x + m0 * H, c->vf_logits + m0 * V, c->vf_part_val + m0 * P, c->vf_part_idx + m0 * P, R);
+    launch_lm_head_at(c, x + m0 * H, logits + m0 * V, part_val + m0 * P, part_idx + m0 * P, R);
     m0 += R;
   }
 }
@@ -1661,15 +1666,11 @@ static int ensure_verify_ws(tgx_ctx* c) {      // (tgx_score_row's group form ho
 
 // both entry points: tgx_verify_row (`sampled_entry` false: a row that does not sample greedily is refused) and tgx_verify_row_sampled (such a row's positions are
 // drawn by its own sampler between the pass and the accept launch; a greedy row takes exactly tgx_verify_row's launches)
-static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, bool sampled_entry) {
-  const char* const fn = sampled_entry ? "tgx_verify_row_sampled" : "tgx_verify_row";
-  if (!c || !draft || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
-  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "verify before finalize");
-  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+// one row's checks, the same for the one-row calls (min_draft 1) and for every row of tgx_verify_rows (min_draft 0), in this order; nothing changes
+static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int min_draft, bool sampled_entry, const char* fn) {
   const tgx_model_desc& d = c->d;
-  // ---- every check before anything changes
   if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
-  if (n_draft < 1 || n_draft > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [1,%d]", n_draft, TGX_MAX_DRAFT);
+  if (n_draft < min_draft || n_draft > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [%d,%d]", n_draft, min_draft, TGX_MAX_DRAFT);
   for (int i = 0; i < n_draft; i++)
     if (draft[i] < 0 || draft[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "draft token id out of range");
   const RowHost& rh = c->row_host[(size_t)row];
@@ -1678,12 +1679,22 @@ static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draf
   if (rh.nologits) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
   if (!rh.tok) return set_err(c, TGX_ERR_STATE, "row %d has no current token: tgx_sample_row it first", row);
   const tgx_sampler_cfg cfg = row_cfg(c, row);
-  const bool sampled = !is_greedy(&cfg);
-  if (sampled && !sampled_entry) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
+  if (!is_greedy(&cfg) && !sampled_entry) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
   if (row_processed(c, row)) return set_err(c, TGX_ERR_UNSUPPORTED, "%s: row %d has a logit processor on (the accept rule compares raw argmaxes)", fn, row);
+  if (rh.past + n_draft + 1 > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, (long long)rh.past, n_draft + 1, d.max_ctx);
+  return TGX_OK;
+}
+static int verify_row_run(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, const char* fn);
+
+static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, bool sampled_entry) {
+  const char* const fn = sampled_entry ? "tgx_verify_row_sampled" : "tgx_verify_row";
+  if (!c || !draft || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "verify before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  // ---- every check before anything changes
+  if (int rc = verify_row_check(c, row, draft, n_draft, /*min_draft=*/1, sampled_entry, fn)) return rc;
   const int M = n_draft + 1;
-  const long long past = rh.past;
-  if (past + M > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, M, d.max_ctx);
+  const long long past = c->row_host[(size_t)row].past;
   static_assert((int)tgx_ctx::VERIFY_ROWS == tgx::VERIFY_MAX_POS, "kernels/verify.h VerifyRecord");
   if (c->kv_paged) {
     const PrefillRoute rt = prefill_route(c, M, M);
@@ -1695,6 +1706,15 @@ static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draf
                      have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
     // (the first new position falls into a block the row owns: a block forked siblings map as well is full)
   }
+  return verify_row_run(c, row, draft, n_draft, out_ids, out_n, out_finish, fn);
+}
+// ... and behind the checks: the pass, the draws of a sampled row, the accept launch, the host's bookkeeping (tgx_verify_rows' row-by-row form runs it per row
+// after ITS checks: n_draft 0 is then a pass of the current token alone)
+static int verify_row_run(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, const char* fn) {
+  const tgx_sampler_cfg cfg = row_cfg(c, row);
+  const bool sampled = !is_greedy(&cfg);
+  const int M = n_draft + 1;
+  const long long past = c->row_host[(size_t)row].past;
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_verify_ws(c)) return rc;
   if (sampled) if (int rc = vs_alloc(c)) return rc;      // the positions' sampler workspace: only a sampled row's call ever holds it
@@ -1714,7 +1734,7 @@ static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draf
   HIP_OK(c, hipMemcpyAsync(&rec, c->vf_rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
   if (int rc = finish_pass(c)) return rc;
   if (rec.n < 1 || rec.n > M) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record", fn); }
-  c->vf_pass_rows = M;
+  c->vf_pass_rows = M; c->vf_pass_joint = false;
   // ---- the host follows the device: length, blocks, finished state
   RowHost& r = c->row_host[(size_t)row];
   r.past = past + rec.n;
@@ -1743,15 +1763,142 @@ int tgx_verify_row_sampled(tgx_ctx* c, int row, const int64_t* draft, int n_draf
   return verify_row_impl(c, row, draft, n_draft, out_ids, out_n, out_finish, /*sampled_entry=*/true);
 }
 
+// ---- tgx_verify_rows (include/tgx.h): the drafts of n rows in ONE causal pass and ONE accept launch.  The pass is tgx_forward_rows' ragged pass with each
+// sequence's real length as its `past` (RaggedPass.past): row i's current token and draft at workspace rows [first_i, first_i + n_draft[i] + 1) into its cache from
+// past_i, on prefill_route(M, M)'s skinny or tiled route; lm_head of all M positions into the vj_* workspace; one sampler chain per sampled row over its slice; the
+// accept launch with one workgroup per row (kernels/verify.h); ONE read-back of the n records.  Where no matrix-core route takes the M positions (fp32 storage,
+// prefill.mfma 0, shapes the tile does not cover, M below the routes' minimum) the rows run verify_row_run one by one behind the same checks: verify.last_form 2.
+static int ensure_verify_rows_ws(tgx_ctx* c) {
+  if (c->vj_args) return TGX_OK;      // the last of them
+  const size_t R = tgx_ctx::VERIFY_POSITIONS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid, B = (size_t)c->d.max_batch;
+  int rc;
+  if ((rc = dev_alloc(c, &c->vj_x, R * H)) || (rc = dev_alloc(c, &c->vj_logits, R * V)) || (rc = dev_alloc(c, &c->vj_part_val, R * P)) || (rc = dev_alloc(c, &c->vj_part_idx, R * P)) ||
+      (rc = dev_alloc(c, &c->vj_draws, R)) || (rc = dev_alloc(c, &c->vj_rec, B * (sizeof(tgx::VerifyRecord) / 4)))) return rc;
+  HIP_OK(c, hipMemset(c->vj_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
+  return dev_alloc(c, &c->vj_args, B * verify_args_bytes());
+}
+
+int tgx_verify_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* drafts, const int32_t* n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  const char* const fn = "tgx_verify_rows";
+  if (!c || !rows || !drafts || !n_draft || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "verify before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
+  // ---- every check before anything changes: per row in array order, each row's in the one-row call's order
+  std::vector<int> first((size_t)n), lens((size_t)n), past((size_t)n), rws((size_t)n), nd((size_t)n);
+  std::vector<char> named((size_t)d.max_batch, 0);
+  long long M = 0, off = 0;
+  for (int i = 0; i < n; i++) {
+    const int row = rows[i];
+    if (row >= 0 && row < d.max_batch && named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    if (n_draft[i] < 0 || n_draft[i] > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [0,%d]", (int)n_draft[i], TGX_MAX_DRAFT);      // (ahead of the read of its ids)
+    if (int rc = verify_row_check(c, row, drafts + off, n_draft[i], /*min_draft=*/0, /*sampled_entry=*/true, fn)) return rc;
+    named[(size_t)row] = 1;
+    rws[(size_t)i] = row; nd[(size_t)i] = n_draft[i]; lens[(size_t)i] = n_draft[i] + 1; first[(size_t)i] = (int)M; past[(size_t)i] = (int)c->row_host[(size_t)row].past;
+    M += n_draft[i] + 1; off += n_draft[i];
+  }
+  if (M > TGX_MAX_VERIFY_POSITIONS) return set_err(c, TGX_ERR_INVALID, "%s: %lld positions in one call (at most %d)", fn, M, TGX_MAX_VERIFY_POSITIONS);
+  static_assert(TGX_MAX_VERIFY_POSITIONS <= tgx::VERIFY_MAX_ROWS, "kernels/verify.h VerifyFirstIds");
+  const PrefillRoute rt = prefill_route(c, (int)M, (int)M);
+  const bool joint = rt == ROUTE_SKINNY || rt == ROUTE_TILED;
+  if (c->kv_paged) {
+    bool mfma_row = joint;      // row by row: does some row's own pass take a matrix-core route?
+    for (int i = 0; i < n && !mfma_row; i++) { const PrefillRoute r1 = prefill_route(c, lens[(size_t)i], lens[(size_t)i]); mfma_row = r1 == ROUTE_SKINNY || r1 == ROUTE_TILED; }
+    if (mfma_row && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
+      return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+    // all or nothing: the blocks of all named rows together against the free list
+    long long need = 0;
+    for (int i = 0; i < n; i++) need += c->kv.blocks_for((long long)past[(size_t)i] + lens[(size_t)i]) - c->kv.row_blocks(rws[(size_t)i]);
+    const long long have = c->kv.available_for(nullptr, 0);
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", need, tgx::KV_BLOCK, have,
+                     c->kv.n_blocks() - 1, c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = ensure_verify_rows_ws(c)) return rc;
+  const size_t V = (size_t)d.vocab;
+  if (!joint) {      // ---- row by row: each row's own pass -> draws -> accept, bit for bit the one-row call; its positions' logits then join the call's in vj_logits
+    for (int i = 0; i < n; i++) {
+      if (int rc = verify_row_run(c, rws[(size_t)i], drafts + (first[(size_t)i] - i), nd[(size_t)i], out_ids + (size_t)i * (TGX_MAX_DRAFT + 1), out_n + i, out_finish + i, fn)) return rc;
+      HIP_OK(c, hipMemcpyAsync(c->vj_logits + (size_t)first[(size_t)i] * V, c->vf_logits, (size_t)lens[(size_t)i] * V * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (int rc = finish_pass(c)) return rc;
+    c->vf_pass_rows = (int)M; c->vf_pass_joint = true;
+    c->verify_last_form = 2;
+    return TGX_OK;
+  }
+  // ---- the joint pass
+  std::vector<tgx_sampler_cfg> cfg((size_t)n);
+  std::vector<char> smp((size_t)n, 0);
+  bool any_sampled = false;
+  for (int i = 0; i < n; i++) { cfg[(size_t)i] = row_cfg(c, rws[(size_t)i]); smp[(size_t)i] = !is_greedy(&cfg[(size_t)i]); any_sampled = any_sampled || smp[(size_t)i]; }
+  if (any_sampled) if (int rc = vs_alloc(c)) return rc;
+  RaggedPass p;
+  p.n = n; p.M = (int)M; p.rows = rws.data(); p.lens = lens.data(); p.first = first.data(); p.past = past.data();
+  for (int i = 0; i < n; i++) p.longest = std::max(p.longest, lens[(size_t)i]);
+  if (int rc = ensure_extend_rg_ws(c, p)) return rc;
+  // the call's buffer: the pass's tables, then its ids (ONE upload; input 0 of every sequence is written on the device from the row's token word)
+  const size_t o_ids = ragged_tables(c, p, nullptr, nullptr), bytes = o_ids + (size_t)M * 8;
+  if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
+  std::vector<unsigned char> host(bytes, 0);      // (lives until finish_pass has synchronised)
+  ragged_tables(c, p, host.data(), c->rg_buf);
+  long long* const h_ids = reinterpret_cast<long long*>(host.data() + o_ids);
+  for (int i = 0; i < n; i++)
+    for (int k = 0; k < nd[(size_t)i]; k++) h_ids[first[(size_t)i] + 1 + k] = drafts[first[(size_t)i] - i + k];
+  long long* const d_ids = reinterpret_cast<long long*>(c->rg_buf + o_ids);
+  p.ids = d_ids;
+  c->vf_pass_rows = 0;                             // the workspace changes hands
+  for (int i = 0; i < n; i++) (void)kv_ensure_blocks(c, rws[(size_t)i], (long long)past[(size_t)i] + lens[(size_t)i]);      // cannot fail: counted above
+  HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  launch_verify_first_ids(c, d_ids, n, rws.data(), first.data());
+  if (int rc = launch_route(c, rt, (int)M, 0, 0, 0, /*past=*/0, &p)) return rc;
+  launch_lm_head_all(c, rt, (int)M, nullptr, /*joint=*/true);
+  for (int i = 0; i < n; i++)      // a sampled row's positions under its own settings, each with the key its step would use; the chains share one scratch: stream order
+    if (smp[(size_t)i]) launch_sample_positions(c, rws[(size_t)i], lens[(size_t)i], cfg[(size_t)i], first[(size_t)i]);
+  launch_verify_accept_rows(c, d_ids, n, rws.data(), first.data(), nd.data(), smp.data());
+  for (int i = 0; i < n; i++)
+    if (row_records(c, rws[(size_t)i])) launch_logprobs_verify(c, rws[(size_t)i], lens[(size_t)i], first[(size_t)i], i);
+  std::vector<tgx::VerifyRecord> rec((size_t)n);
+  HIP_OK(c, hipMemcpyAsync(rec.data(), c->vj_rec, (size_t)n * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = finish_pass(c)) return rc;
+  for (int i = 0; i < n; i++)
+    if (rec[(size_t)i].n < 1 || rec[(size_t)i].n > lens[(size_t)i]) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record for row %d", fn, rws[(size_t)i]); }
+  c->vf_pass_rows = (int)M; c->vf_pass_joint = true;
+  c->verify_last_form = 1; c->verify_last_splits = p.ext_ns;
+  // ---- the host follows the device, row by row as the one-row call does
+  for (int i = 0; i < n; i++) {
+    const int row = rws[(size_t)i];
+    const tgx::VerifyRecord& rc1 = rec[(size_t)i];
+    RowHost& r = c->row_host[(size_t)row];
+    r.past = past[(size_t)i] + rc1.n;
+    r.fin = (char)rc1.finish;
+    if (row_records(c, row)) r.lp_count += rc1.n;
+    kv_trim_row(c, row, r.past);
+    if (!smp[(size_t)i]) note_sampled(c, row, 1, cfg[(size_t)i]);
+    else r.probs_ok = false;
+    for (int k = 0; k < rc1.n; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = rc1.ids[k];
+    out_n[i] = rc1.n; out_finish[i] = rc1.finish;
+    if (row == 0) c->last_sampled0 = rc1.ids[rc1.n - 1];
+  }
+  c->have_probs = false;
+  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
 // test / diagnostic use: the fp32 logits [M][V] of the last verify pass, while the workspace still holds them
 int tgx_read_pass_logits(tgx_ctx* c, float* out, int cap_rows, int32_t* out_rows) {
   if (!c || !out || !out_rows) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
   const int M = c->vf_pass_rows;
-  if (M < 1 || !c->vf_logits) return set_err(c, TGX_ERR_STATE, "no verify pass to read: the workspace holds none (no call yet, or another call has used it since)");
+  const float* const src = c->vf_pass_joint ? c->vj_logits : c->vf_logits;      // (a tgx_verify_rows joint pass: all its positions in call order)
+  if (M < 1 || !src) return set_err(c, TGX_ERR_STATE, "no verify pass to read: the workspace holds none (no call yet, or another call has used it since)");
   if (cap_rows < M) return set_err(c, TGX_ERR_INVALID, "cap_rows %d below the pass's %d positions", cap_rows, M);
   HIP_OK(c, hipSetDevice(c->device));
   HIP_OK(c, hipStreamSynchronize(c->stream));
-  HIP_OK(c, hipMemcpy(out, c->vf_logits, (size_t)M * c->d.vocab * 4, hipMemcpyDeviceToHost));
+  HIP_OK(c, hipMemcpy(out, src, (size_t)M * c->d.vocab * 4, hipMemcpyDeviceToHost));
   *out_rows = M;
   return TGX_OK;
 }
@@ -2212,6 +2359,8 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "score.rows")) { *out_value = c->score_rows; return TGX_OK; }
   if (!strcmp(key, "score.vocab_chunk")) { *out_value = c->score_vocab_chunk; return TGX_OK; }
   if (!strcmp(key, "snapshot.stage_kib")) { *out_value = c->snapshot_stage_kib; return TGX_OK; }
+  if (!strcmp(key, "verify.last_splits")) { *out_value = c->verify_last_splits; return TGX_OK; }  // read-only: the key splits of the last tgx_verify_rows joint pass's attention (0: unsplit)
+  if (!strcmp(key, "verify.last_form")) { *out_value = c->verify_last_form; return TGX_OK; }      // read-only: the form of the last tgx_verify_rows (0 none yet, 1 the joint pass, 2 row by row)
   if (!strcmp(key, "score.last_form")) { *out_value = c->score_last_form; return TGX_OK; }      // read-only: the form of the last tgx_score_row that scored a position (0 none yet, 1 matrix cores, 2 by groups)
   if (!strcmp(key, "weights.packed")) { *out_value = c->weights_packed; return TGX_OK; }
   if (!strcmp(key, "weights.packed_classes")) { *out_value = c->packed_classes; return TGX_OK; }

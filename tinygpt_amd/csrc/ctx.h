@@ -123,6 +123,10 @@ struct RaggedPass {
   const int* tok_seq = nullptr;              // device [M]: the prompt of each workspace row
   const tgx::RgItem* items = nullptr;        // device: the prompt-attention work list, heaviest first
   int n_items = 0;
+  // tgx_verify_rows: sequence i continues its row from position past[i] (host [n]; nullptr: an admission, every one from 0).  ext_ns > 0: the attention is the ragged
+  // key-split form (kernels/attn_extend.h attn_extend_rg_kernel) with that many splits, its partials sized by ensure_extend_rg_ws; 0: the work-list form
+  const int* past = nullptr;
+  int ext_ns = 0;
 };
 
 inline void* hip_dev_alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }      // the library's two uses of the
@@ -331,6 +335,15 @@ struct tgx_ctx {
   unsigned long long* vs_list_comp = nullptr;    // [VERIFY_ROWS][vocab]
   float* vs_list_v = nullptr;
   int* vs_draws = nullptr;                       // [VERIFY_ROWS]
+  // ---- tgx_verify_rows (include/tgx.h): the joint pass over M <= VERIFY_POSITIONS positions of several rows — the hidden rows, logits and argmax partials of every
+  // position, one record per named row, the sampled rows' draws, and the accept launch's per-row argument table.  Sized by the first call (ensure_verify_rows_ws):
+  // a context that never makes it holds none of it.  Option verify.last_form (read-only): 0 no call yet, 1 the joint pass, 2 row by row
+  enum { VERIFY_POSITIONS = TGX_MAX_VERIFY_POSITIONS };
+  float *vj_x = nullptr, *vj_logits = nullptr, *vj_part_val = nullptr; int *vj_part_idx = nullptr, *vj_rec = nullptr, *vj_draws = nullptr;
+  unsigned char* vj_args = nullptr;              // [max_batch] tgx::VerifyArgs
+  std::vector<unsigned char> vj_args_host;       // ... and the host copy the upload reads
+  bool vf_pass_joint = false;                    // vf_pass_rows counts positions of vj_logits (a tgx_verify_rows joint pass), not of vf_logits
+  int verify_last_form = 0, verify_last_splits = 0;      // ... and `verify.last_splits` (read-only): the key splits of the last joint pass's attention (0: unsplit)
   // ---- per-token log-probabilities (include/tgx.h tgx_set_row_logprobs; kernels/logprobs.h).  Allocated by the first call that switches a row on: the rows' record
   // rings and counters, and the tile launch's partials for max(max_batch, VERIFY_ROWS) rows (a verify pass puts its positions where a step puts its rows)
   tgx::LpRecord* lp_ring = nullptr;          // [max_batch][TGX_LOGPROB_RING]
@@ -437,6 +450,10 @@ void launch_add_pos(tgx_ctx* c, int* pos, int n);
 void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_val, int* part_idx);
 void launch_verify_first_id(tgx_ctx* c, int row);         // tgx_verify_row: prompt[0] of the row <- its current token
 void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws = nullptr);    // ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h); draws: the positions' sampled ids
+// tgx_verify_rows, the joint pass: sequence i = row rows[i], M_i = n_draft[i] + 1 positions at slice first[i] of the vj_* workspace and of the pass's ids
+void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows, const int* first);          // ids[first[i]] <- row rows[i]'s current token, one launch
+void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled);   // one workgroup per row -> vj_rec[i]
+size_t verify_args_bytes();                                // one entry of the accept launch's table (vj_args)
 // ---- attn.hip (kernels/attn_decode.h, attn_decode_mfma.h)
 bool attn_batch_on_mfma(const tgx_ctx* c, int R);
 void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true);   // combine = false: the caller's o_proj merges the split records
@@ -449,20 +466,20 @@ int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);
 int vs_alloc(tgx_ctx* c);                                                    // tgx_verify_row_sampled: the positions' sampler workspace, at first use
 int vs_rezero(tgx_ctx* c);                                                   // ... its scratch back to the zero state the chain expects (tgx_reset_cache; stream-ordered; a no-op without the workspace)
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes)
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first = -1);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes); joint_first >= 0: over the row's slice of the vj_* workspace -> its slice of vj_draws
 int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
 bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)
 int sampler_alloc(tgx_ctx* c);
 int logprobs_alloc(tgx_ctx* c);                                              // the rings, counters and tile partials, at first use
 void launch_logprobs(tgx_ctx* c, int row0, int R, bool force);             // behind a step's publish: the rows that record and produced a token (force: tgx_sample_row)
-void launch_logprobs_verify(tgx_ctx* c, int row, int M);                   // behind tgx_verify_row's accept launch: one record per produced token
+void launch_logprobs_verify(tgx_ctx* c, int row, int M, int joint_first = -1, int joint_i = 0);   // behind tgx_verify_row's accept launch: one record per produced token (joint_first >= 0: the row's slice of the vj_* workspace, its record vj_rec[joint_i])
 // ---- prefill.hip (kernels/prefill.h, gemm_dma.h)
 bool prefill_shapes_ok(const tgx_model_desc& d);
 int ensure_prefill_ws(tgx_ctx* c, int S);
 int ensure_ws_part(tgx_ctx* c, size_t need);      // ws_part holds `need` bytes after this (a growth drops the step graphs: a captured batched step points into the old slabs)
 void launch_prefill(tgx_ctx* c, int row0, int NB, int S, int past);      // past: the rows' common pastLength (their positions are past .. past + S - 1) — explicit, not read from the context
-void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg);           // the same pass over the prompts of rg (every one from position 0)
+void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg);           // the same pass over the sequences of rg (each from its rg.past, default 0)
 // the device tables of p (RgSeq [n], token -> prompt map [M], attention work list [n_items]; each 16-byte aligned) as one block: sets p.n_items and returns the block's
 // size; with `host` (16-byte aligned) it also fills the block there and points p.seq / tok_seq / items into its copy at `dev`
 size_t ragged_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const unsigned char* dev);
@@ -476,6 +493,8 @@ void launch_score_record(tgx_ctx* c, const ScoreCall& sc, int R, int pos0);     
 void launch_score_tiled(tgx_ctx* c, const ScoreCall& sc);      // the matrix-core form over ws_x behind launch_prefill
 int extend_attn_splits(const tgx_ctx* c, int S, int past);   // key splits of a continuation pass's attention (0: the per-row prompt attention)
 int ensure_extend_ws(tgx_ctx* c, int S, int past);           // ... and their partials' workspace, before the pass is issued
+// tgx_verify_rows: the key splits of a ragged continuation pass (p.n sequences, p.past set) by option extend.attn_splits -> p.ext_ns, and the partials' workspace
+int ensure_extend_rg_ws(tgx_ctx* c, RaggedPass& p);
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean);
 void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S);
 void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, int nsplit, bool third = false);

@@ -409,3 +409,32 @@ void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws) {
   a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vf_rec);
   TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_kernel<DT>, dim3(1), dim3(256), 0, c->stream, a))
 }
+// ---- tgx_verify_rows: both launches for the n rows of a joint pass (ids: the pass's ids on the device, row i's M_i = n_draft[i] + 1 inputs from first[i])
+void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows, const int* first) {
+  tgx::VerifyFirstIds f{};
+  for (int i = 0; i < n; i++) { f.tok[i] = c->rows[(size_t)rows[i]].tok; f.first[i] = first[i]; }
+  hipLaunchKernelGGL(tgx::verify_first_ids_kernel, dim3(1), dim3(tgx::VERIFY_MAX_ROWS), 0, c->stream, ids, f, n);
+}
+void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled) {
+  static_assert(sizeof(tgx::VerifyArgs) % 8 == 0, "the table's entries hold pointers");
+  if (!c->vj_args || !c->vj_rec || n > tgx::VERIFY_MAX_ROWS) { c->launch_fault = "joint verification requested before its buffers exist"; return; }
+  const size_t V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
+  c->vj_args_host.resize((size_t)n * sizeof(tgx::VerifyArgs));      // (the context's: it outlives the upload)
+  tgx::VerifyArgs* tab = reinterpret_cast<tgx::VerifyArgs*>(c->vj_args_host.data());
+  for (int i = 0; i < n; i++) {
+    RowState& r = c->rows[(size_t)rows[i]];
+    const size_t f = (size_t)first[i];
+    tgx::VerifyArgs a{};
+    a.part_val = c->vj_part_val + f * P; a.part_idx = c->vj_part_idx + f * P; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = n_draft[i] + 1;
+    a.logits = c->vj_logits + f * V; a.draft = ids + f + 1; a.draws = sampled[i] ? c->vj_draws + f : nullptr;
+    a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + rows[i];
+    a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
+    a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
+    a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vj_rec) + i;
+    tab[i] = a;
+  }
+  if (hipMemcpyAsync(c->vj_args, tab, (size_t)n * sizeof(tgx::VerifyArgs), hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->launch_fault = "joint verification: the argument table's upload failed"; return; }
+  TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_rows_kernel<DT>, dim3(n), dim3(256), 0, c->stream, reinterpret_cast<const tgx::VerifyArgs*>(c->vj_args)))
+}
+// the size of one entry of the accept launch's table, for the workspace (abi.hip ensure_verify_rows_ws)
+size_t verify_args_bytes() { return sizeof(tgx::VerifyArgs); }

@@ -67,4 +67,69 @@ __global__ __launch_bounds__(256) void attn_extend_merge_kernel(const AttnExtend
   attn_emit_rows<DT, HD>(e.a, h, q0, qvalid, oacc, l_run, stage + wv * 32 * (HD + 4), lane);
 }
 
+// ---- the ragged form (tgx_verify_rows): the continuations of SEVERAL sequences (each one query block, S_i <= 128, from its own past_i) in one launch pair.
+// Grid (heads, NS, sequences).  Sequence i has n_tiles_i = (past_i + S_i - 1) / 64 + 1 key tiles and uses ns_i = min(NS, n_tiles_i) splits with attn_extend_kernel's
+// contiguous partition; a workgroup whose split >= ns_i leaves before any barrier.  Partials: part[seq][split][head][value][256].  The merge walks the ns_i partials
+// of its sequence in split order (the same bits from run to run) and emits at the sequence's workspace rows.
+struct AttnExtendRgArgs {
+  AttnRgArgs r;          // the pass's q / o terms from its first workspace row; the sequences' table (item unused)
+  float* part;
+  int ns;                // NS >= 1
+};
+// the sequence's arguments, its split count and (split kernel) this split's tiles
+template <int HD>
+__device__ __forceinline__ AttnPrefillArgs attn_extend_rg_seq(const AttnExtendRgArgs& e, const int j, const int h, int& ns_j, int& n_tiles) {
+  const RgItem it{j, 0, h, 0};
+  const AttnPrefillArgs a = attn_rg_args<HD>(e.r, it);
+  n_tiles = (a.past + a.S - 1) / ATTN_KTILE + 1;
+  ns_j = min(e.ns, n_tiles);
+  return a;
+}
+template <int DT, int HD, bool PAGED>
+__global__ __launch_bounds__(256, HD == 64 ? 1 : 2) void attn_extend_rg_kernel(const AttnExtendRgArgs e) {
+  constexpr int LA = HD == 64 ? 2 : 1;
+  const int h = blockIdx.x, s = blockIdx.y, j = blockIdx.z;
+  int ns_j, n_tiles;
+  const AttnPrefillArgs a = attn_extend_rg_seq<HD>(e, j, h, ns_j, n_tiles);
+  if (s >= ns_j) return;                     // workgroup-uniform; no barrier above
+  const int base = n_tiles / ns_j, rem = n_tiles - base * ns_j;
+  const int t0 = s * base + min(s, rem), t1 = t0 + base + (s < rem ? 1 : 0);
+  float* const part = e.part + (((size_t)j * e.ns + s) * a.heads + h) * (size_t)(attn_extend_part_vals<HD>() * 256);
+  attn_prefill_wg<DT, HD, LA, 1, PAGED, true>(a, h, 0, t0, t1, part);
+}
+
+template <int DT, int HD>
+__global__ __launch_bounds__(256) void attn_extend_rg_merge_kernel(const AttnExtendRgArgs e) {
+  constexpr int NB = HD / 32, NV = attn_extend_part_vals<HD>();
+  __shared__ __attribute__((aligned(16))) bf16_t stage[4 * 32 * (HD + 4)];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, h = blockIdx.x, j = blockIdx.y;
+  int ns_j, n_tiles;
+  const AttnPrefillArgs a = attn_extend_rg_seq<HD>(e, j, h, ns_j, n_tiles);
+  const int q0 = wv * 32;
+  if (q0 >= a.S) return;                     // wave-uniform; no barrier below
+  const bool qvalid = q0 + (lane & 31) < a.S;
+  const size_t split_stride = (size_t)a.heads * (NV * 256);
+  const float* pi = e.part + (size_t)j * e.ns * split_stride + (size_t)h * (NV * 256) + tid;
+  f32x16 oacc[NB];
+#pragma unroll
+  for (int b = 0; b < NB; b++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) oacc[b][r] = pi[(b * 16 + r) * 256];
+  float m_run = pi[(NB * 16) * 256], l_run = pi[(NB * 16 + 1) * 256];
+  for (int s = 1; s < ns_j; s++) {
+    pi += split_stride;
+    const float m_b = pi[(NB * 16) * 256], l_b = pi[(NB * 16 + 1) * 256];
+    const float m_new = fmaxf(m_run, m_b);
+    const bool dead = m_new == -INFINITY;      // nothing attended in either part (a padded query)
+    const float fa = dead ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new), fb = dead ? 1.f : __builtin_amdgcn_exp2f(m_b - m_new);
+    l_run = l_run * fa + l_b * fb;
+    m_run = m_new;
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) oacc[b][r] = oacc[b][r] * fa + pi[(b * 16 + r) * 256] * fb;
+  }
+  attn_emit_rows<DT, HD>(a, h, q0, qvalid, oacc, l_run, stage + wv * 32 * (HD + 4), lane);
+}
+
 }  // namespace tgx

@@ -276,25 +276,25 @@ __global__ __launch_bounds__(256) void rope_kv_split_kernel(const RopeKvArgs a) 
   rope_kv_split_row<DT>(a, blockIdx.x, a.past + (int)blockIdx.x, a.k_cache, a.v_cache, a.blk_tbl);
 }
 
-// ---- ragged passes (tgx_forward_rows): prompts of different lengths stacked in one workspace, each into its own row's cache ------------------------------
-struct RgSeq {                 // one prompt of the pass
-  int row0, S;                 // its first workspace row, its length (positions 0 .. S-1: every prompt starts an empty row)
+// ---- ragged passes (tgx_forward_rows, tgx_verify_rows): sequences of different lengths stacked in one workspace, each into its own row's cache -------------
+struct RgSeq {                 // one sequence of the pass
+  int row0, S;                 // its first workspace row, its length
   bf16_t *k, *v;               // layer 0 of its row's cache (slab KV) or of the pools (paged KV); layer l: + layer_off
   const int* tbl;              // paged KV: its row's block table, else nullptr
-  const void* pad;
+  int past, pad;               // the positions its row already holds: the pass covers past .. past + S - 1 (an admission: 0, every prompt starts an empty row)
 };
 struct RgItem { int seq, qblk, h, pad; };      // one prompt-attention workgroup: (prompt, query block, head)
 // the prompt attention's blocking (attn_prefill_wg below): a workgroup takes ATTN_QBLK queries of one head and walks the keys in tiles of ATTN_KTILE — the launch
 // geometry and the ragged work list (prefill.hip) are derived from the same two numbers
 constexpr int ATTN_QBLK = 128, ATTN_KTILE = 64;
 // rope_kv_split_kernel over every workspace row of the pass in ONE launch: QKV / part / q_hi / q_lo address the whole pass (a.k_cache / v_cache / blk_tbl / past
-// unused); a row finds its prompt in tok_seq, its position = its row - the prompt's first row
+// unused); a row finds its sequence in tok_seq, its position = the sequence's past + its row - the sequence's first row
 struct RopeRgArgs { RopeKvArgs a; const RgSeq* seq; const int* tok_seq; long long layer_off; };
 template <int DT>
 __global__ __launch_bounds__(256) void rope_kv_split_rg_kernel(const RopeRgArgs r) {
   const int s = blockIdx.x;
   const RgSeq q = r.seq[r.tok_seq[s]];
-  rope_kv_split_row<DT>(r.a, s, s - q.row0, q.k + r.layer_off, q.v + r.layer_off, q.tbl);
+  rope_kv_split_row<DT>(r.a, s, q.past + s - q.row0, q.k + r.layer_off, q.v + r.layer_off, q.tbl);
 }
 
 // ---- C[M][N] (+)= (Ahi + Alo)[M][K] · B[N][K]ᵀ on v_mfma_f32_32x32x16_bf16 ------------------------------------------
@@ -880,7 +880,7 @@ __global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 
 
 // ---- the prompt attention of a ragged pass (tgx_forward_rows): ONE launch for every prompt, one workgroup per work item (prompt, query block, head) of a device list
 // that the host orders heaviest first (key tiles descending, across prompts).  a = the pass's q / o terms from its first workspace row; the item sets the prompt's rows,
-// S, past 0 and its row's K / V (or pools + block table).  Per workgroup the same code as attn_prefill_kernel / attn_prefill_dma_kernel: bit for bit the per-row form.
+// S, its past (0 for an admission) and its row's K / V (or pools + block table).  Per workgroup the same code as attn_prefill_kernel / attn_prefill_dma_kernel: bit for bit the per-row form.
 struct AttnRgArgs { AttnPrefillArgs a; const RgSeq* seq; const RgItem* item; long long layer_off; };
 template <int HD>
 __device__ __forceinline__ AttnPrefillArgs attn_rg_args(const AttnRgArgs& r, const RgItem& it) {
@@ -888,7 +888,7 @@ __device__ __forceinline__ AttnPrefillArgs attn_rg_args(const AttnRgArgs& r, con
   const RgSeq q = r.seq[it.seq];
   const size_t o = (size_t)q.row0 * a.heads * HD;
   a.q_hi += o; a.q_lo += o; a.o_hi += o; a.o_lo += o;
-  a.S = q.S; a.past = 0;
+  a.S = q.S; a.past = q.past;
   a.k_cache = q.k + r.layer_off; a.v_cache = q.v + r.layer_off; a.blk_tbl = q.tbl;
   return a;
 }

@@ -36,12 +36,12 @@ static __global__ void verify_first_id_kernel(long long* ids, const int* tok) { 
 // The row produces g[0], then g[1] if g[0] == draft[0], ... : draft[0 .. a - 1] followed by g[a]; a produced token that finishes the row (stop id, max_new)
 // ends the walk.  The position that produced the last token hands the row its logits row and partials; the next embedding is gathered at the advanced position.
 template <int DT>
-__global__ __launch_bounds__(256) void verify_accept_kernel(const VerifyArgs a) {
+__device__ __forceinline__ void verify_accept_body(const VerifyArgs& a) {
   __shared__ int s_g[VERIFY_MAX_POS];
   __shared__ int s_win, s_tok, s_pos;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int i = wv; i < a.M; i += 4) {      // a wave per position: its draw, or the merge of its partials
-    if (a.draws) {                         // (kernel-uniform)
+    if (a.draws) {                         // (workgroup-uniform)
       if (lane == 0) { const int t = a.draws[i]; s_g[i] = (unsigned)t < (unsigned)a.V ? t : 0; }
       continue;
     }
@@ -91,5 +91,17 @@ __global__ __launch_bounds__(256) void verify_accept_kernel(const VerifyArgs a) 
   }
   gather_embedding<DT>(a.embed, s_tok, a.x, a.H, a.wpe, a.wpe ? s_pos : 0);
 }
+template <int DT>
+__global__ __launch_bounds__(256) void verify_accept_kernel(const VerifyArgs a) { verify_accept_body<DT>(a); }
+
+// ---- tgx_verify_rows: the same two launches for the n rows of a joint pass.  tab[i] = row i's arguments over ITS slice of the pass's workspace (logits, partials,
+// draws or nullptr, the draft ids behind its first input) and its own record; one workgroup per row runs the walk above, so a row ends as its own one-row call leaves it
+struct VerifyFirstIds { int* tok[VERIFY_MAX_ROWS]; int first[VERIFY_MAX_ROWS]; };
+static __global__ void verify_first_ids_kernel(long long* ids, const VerifyFirstIds f, int n) {
+  const int i = threadIdx.x;
+  if (i < n) ids[f.first[i]] = *f.tok[i];
+}
+template <int DT>
+__global__ __launch_bounds__(256) void verify_accept_rows_kernel(const VerifyArgs* tab) { verify_accept_body<DT>(tab[blockIdx.x]); }
 
 }  // namespace tgx

@@ -311,6 +311,43 @@ static void launch_attn_extend(tgx_ctx* c, const tgx::AttnPrefillArgs& a, int ns
   };
   if (a.blk_tbl) go(std::true_type{}); else go(std::false_type{});
 }
+// ---- the ragged key-split form (tgx_verify_rows; kernels/attn_extend.h attn_extend_rg_kernel).  Option extend.attn_splits: 0 never, N >= 1 N splits, -1 automatic:
+// split when the longest past_i + S_i of the pass exceeds extend_attn_min{64,128}, with min(32, 2 * CUs / (n * heads)) splits, unsplit when that is below 2.
+// The split count is measured (tools/spec_bench.py --rows, profiles/verify_rows.txt; Llama-3.2-1B bf16, 32 heads, context 2048, ms per tgx_verify_rows call of
+// 4 positions per row, greedy; spread of a figure ~0.05): two workgroups per CU win at every batch size tried —
+//   n = 2: unsplit 1.95, 2 splits 1.53, 4 1.34, 8 1.30      n = 4: unsplit 2.05, 2 1.63, 4 1.47, 8 1.55      n = 8: unsplit 2.23, 2 1.88, 4 1.95, 8 2.04
+// (one workgroup per CU, the one-row call's rule taken to n rows, gave 1.34 / 1.63 / unsplit 2.23).  The THRESHOLD is still the one measured for ONE row (ctx.h
+// extend_attn_min); for n > 1 sequences, for contexts other than 2048 and for head_dim 128 it is unmeasured.
+static size_t extend_rg_part_bytes(const tgx_ctx* c, int n, int ns) { return (size_t)n * extend_part_bytes(c, ns); }
+int ensure_extend_rg_ws(tgx_ctx* c, RaggedPass& p) {
+  p.ext_ns = 0;
+  if (c->extend_attn_splits == 0 || !p.past || p.longest > tgx::ATTN_QBLK || c->dt == tgx::DT_F32) return TGX_OK;
+  int reach = 0;       // the longest past_i + S_i
+  for (int i = 0; i < p.n; i++) reach = std::max(reach, p.past[i] + p.lens[i]);
+  int ns = c->extend_attn_splits;
+  if (ns < 0) {
+    if (reach <= (c->d.head_dim == 64 ? c->extend_attn_min64 : c->extend_attn_min128)) return TGX_OK;
+    ns = std::min(32, 2 * c->num_cus / std::max(1, p.n * c->d.heads));
+    if (ns < 2) return TGX_OK;
+  }
+  p.ext_ns = std::min(ns, (reach - 1) / tgx::ATTN_KTILE + 1);
+  return dev_grow(c, &c->ext_part, &c->ext_part_bytes, extend_rg_part_bytes(c, p.n, p.ext_ns));
+}
+static void launch_attn_extend_rg(tgx_ctx* c, const tgx::AttnRgArgs& r, const RaggedPass& rg) {
+  const int hd = c->d.head_dim;
+  tgx::AttnExtendRgArgs e{};
+  e.r = r; e.part = c->ext_part; e.ns = rg.ext_ns;
+  if (!c->ext_part || extend_rg_part_bytes(c, rg.n, rg.ext_ns) > c->ext_part_bytes) { c->launch_fault = "attn_extend_rg: the partials' workspace was not sized for this pass"; return; }
+  const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
+  const dim3 grid(r.a.heads, rg.ext_ns, rg.n), mgrid(r.a.heads, rg.n), blk(256);
+  auto go = [&](auto paged) {
+    constexpr bool P = decltype(paged)::value;
+    TGX_DT16_SWITCH(c->dt,
+      if (hd == 64) { hipLaunchKernelGGL((tgx::attn_extend_rg_kernel<DT, 64, P>), grid, blk, lds1, c->stream, e); hipLaunchKernelGGL((tgx::attn_extend_rg_merge_kernel<DT, 64>), mgrid, blk, 0, c->stream, e); }
+      else { hipLaunchKernelGGL((tgx::attn_extend_rg_kernel<DT, 128, P>), grid, blk, lds1, c->stream, e); hipLaunchKernelGGL((tgx::attn_extend_rg_merge_kernel<DT, 128>), mgrid, blk, 0, c->stream, e); })
+  };
+  if (c->kv_paged) go(std::true_type{}); else go(std::false_type{});
+}
 
 // causal GQA flash attention of S prompt positions of one batch row (grid = ceil(S / 128) query blocks x heads)
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_lean) {
@@ -356,6 +393,7 @@ void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_
 void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean) {
   tgx::AttnRgArgs r{};
   r.a = a; r.seq = rg.seq; r.item = rg.items; r.layer_off = layer_off;
+  if (rg.ext_ns > 0) { launch_attn_extend_rg(c, r, rg); return; }      // continuations (tgx_verify_rows): the key-split form
   const int hd = c->d.head_dim;
   const int nqb = (rg.longest + tgx::ATTN_QBLK - 1) / tgx::ATTN_QBLK, nwg = nqb * a.heads, total = rg.n_items;
   const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
@@ -393,11 +431,11 @@ size_t ragged_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const
   for (int j = 0; j < p.n; j++) {
     const RowState& r = c->rows[(size_t)p.rows[j]];
     sq[j].row0 = p.first[j]; sq[j].S = p.lens[j];
-    sq[j].k = reinterpret_cast<bf16_t*>(r.kcache); sq[j].v = reinterpret_cast<bf16_t*>(r.vcache); sq[j].tbl = r.tbl; sq[j].pad = nullptr;
+    sq[j].k = reinterpret_cast<bf16_t*>(r.kcache); sq[j].v = reinterpret_cast<bf16_t*>(r.vcache); sq[j].tbl = r.tbl; sq[j].past = p.past ? p.past[j] : 0; sq[j].pad = 0;
     for (int s = 0; s < p.lens[j]; s++) tok[p.first[j] + s] = j;
     for (int qb = 0; qb < (p.lens[j] + QB - 1) / QB; qb++) blocks.emplace_back(j, qb);
   }
-  auto tiles = [&](const std::pair<int, int>& b) { return std::min(b.second * QB + QB - 1, p.lens[b.first] - 1) / KT + 1; };
+  auto tiles = [&](const std::pair<int, int>& b) { return ((p.past ? p.past[b.first] : 0) + std::min(b.second * QB + QB - 1, p.lens[b.first] - 1)) / KT + 1; };      // its real key tiles
   std::stable_sort(blocks.begin(), blocks.end(), [&](const std::pair<int, int>& x, const std::pair<int, int>& y) { return tiles(x) > tiles(y); });
   int k = 0;
   for (const auto& b : blocks)
@@ -426,7 +464,7 @@ void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg) {
   }
   for (int i = 0; i < rg.n; i++)
     TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::embed_rows_any_kernel<DT>, dim3(rg.lens[i]), dim3(256), 0, c->stream, rg.ids + rg.first[i], (const void*)c->embed, (const void*)c->wpe,
-                                              c->ws_x + (size_t)rg.first[i] * H, H, rg.lens[i], 0LL, 0))
+                                              c->ws_x + (size_t)rg.first[i] * H, H, rg.lens[i], 0LL, rg.past ? rg.past[i] : 0))
 }
 // RMSNorm of the rows of x into 16-bit terms (ws_ah / ws_al), first adding a pending split-K residual (nsplit > 1: the slabs in ws_part)
 void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, int nsplit, bool third) {

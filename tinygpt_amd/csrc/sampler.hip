@@ -116,12 +116,13 @@ int vs_rezero(tgx_ctx* c) {
   return TGX_OK;
 }
 
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg) {
-  if (!c->vs_draws || !c->vf_rec) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first) {
+  const bool joint = joint_first >= 0;      // tgx_verify_rows: the row's slice of the joint pass's workspace; the scratch and lists are the one-row call's (chains are stream-ordered)
+  if (!c->vs_draws || !(joint ? c->vj_draws : c->vf_rec) || M > (int)tgx_ctx::VERIFY_ROWS) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
   const int V = c->d.vocab;
   tgx::SampArgs a{};
-  a.logits = c->vf_logits; a.logits_stride = V;
-  a.part_val = c->vf_part_val; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
+  a.logits = joint ? c->vj_logits + (size_t)joint_first * V : c->vf_logits; a.logits_stride = V;
+  a.part_val = joint ? c->vj_part_val + (size_t)joint_first * c->lm_grid : c->vf_part_val; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
   a.sc = c->vs_scratch;
   a.V = V; a.idx_bits = 1;
   while ((1 << a.idx_bits) < V) a.idx_bits++;
@@ -130,7 +131,7 @@ void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& 
   a.z_from_tail = ((cfg.top_k > 0 || cfg.top_p < 1.f) && !(cfg.min_p > 0.f)) ? 1 : 0;
   tgx::SampPickArgs pa{};
   pa.fin.pos = c->rows[(size_t)row].pos; pa.fin.req = c->row_req + row; pa.fin.row = row;      // the key's words: read, never written
-  pa.draws = c->vs_draws;
+  pa.draws = joint ? c->vj_draws + joint_first : c->vs_draws;
   launch_chain(c, a, cfg, M, pa, /*positions=*/true);
 }
 
@@ -279,12 +280,13 @@ void launch_logprobs(tgx_ctx* c, int row0, int R, bool force) {
   lp_launch(c, a, R);
 }
 
-void launch_logprobs_verify(tgx_ctx* c, int row, int M) {
+void launch_logprobs_verify(tgx_ctx* c, int row, int M, int joint_first, int joint_i) {
   if (!c->lp_rows) { c->launch_fault = "log-probabilities requested before their buffers exist"; return; }
+  const bool joint = joint_first >= 0;
   tgx::LpArgs a = lp_args(c);
-  a.logits = c->vf_logits;
+  a.logits = joint ? c->vj_logits + (size_t)joint_first * c->d.vocab : c->vf_logits;
   a.req = c->row_req + row; a.st = c->lp_rows + row;
-  a.rec = reinterpret_cast<const tgx::VerifyRecord*>(c->vf_rec);
+  a.rec = joint ? reinterpret_cast<const tgx::VerifyRecord*>(c->vj_rec) + joint_i : reinterpret_cast<const tgx::VerifyRecord*>(c->vf_rec);
   a.tile_max = c->lp_tile_max; a.tile_sum = c->lp_tile_sum; a.tile_keys = c->lp_tile_keys;
   a.ring = c->lp_ring + (size_t)row * tgx::LP_RING;
   lp_launch(c, a, M);

@@ -89,6 +89,7 @@ ABI = {
     "verify_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "verify_row_sampled": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "read_pass_logits": (c_int, [c_void_p, POINTER(c_float), c_int, POINTER(c_int32)]),
+    "verify_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -356,10 +357,25 @@ class Model:
 
     def pass_logits(self) -> np.ndarray:
         """the fp32 logits [M][vocab] of the last verify pass's M positions (include/tgx.h tgx_read_pass_logits; test / diagnostic use)"""
-        out = np.empty((16, self.desc.vocab), dtype=np.float32)      # TGX_MAX_DRAFT + 1 positions at the most
+        out = np.empty((64, self.desc.vocab), dtype=np.float32)      # TGX_MAX_VERIFY_POSITIONS at the most (a one-row pass: TGX_MAX_DRAFT + 1)
         m = c_int32(0)
-        self._check(self.be.read_pass_logits(self._ctx, out.ctypes.data_as(POINTER(c_float)), 16, ctypes.byref(m)))
+        self._check(self.be.read_pass_logits(self._ctx, out.ctypes.data_as(POINTER(c_float)), 64, ctypes.byref(m)))
         return out[:m.value].copy()
+
+    def verify_rows(self, rows, drafts):
+        """verify_row_sampled for several rows in ONE joint pass (include/tgx.h tgx_verify_rows): drafts[i] = row rows[i]'s draft ids, possibly empty (the row then
+        produces one token, as a decode_rows step would) -> a list of (produced ids, finish), one per row in call order"""
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        ds = [np.asarray(d, dtype=np.int64).reshape(-1) for d in drafts]
+        assert len(ds) == len(rows), (len(ds), len(rows))
+        n_draft = np.ascontiguousarray(np.array([len(d) for d in ds], dtype=np.int32))
+        flat = np.ascontiguousarray(np.concatenate(ds + [np.zeros(1, dtype=np.int64)]))      # (never empty: the pointer stays valid)
+        n = len(rows)
+        out = np.zeros((max(n, 1), 16), dtype=np.int64)      # [n][TGX_MAX_DRAFT + 1]
+        out_n, fin = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.be.verify_rows(self._ctx, n, rows.ctypes.data_as(POINTER(c_int32)), flat.ctypes.data_as(POINTER(c_int64)), n_draft.ctypes.data_as(POINTER(c_int32)),
+                                        out.ctypes.data_as(POINTER(c_int64)), out_n.ctypes.data_as(POINTER(c_int32)), fin.ctypes.data_as(POINTER(c_int32))))
+        return [(out[i, :out_n[i]].copy(), int(fin[i])) for i in range(n)]
 
     def sample_row(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0) -> int:
         out = c_int64()

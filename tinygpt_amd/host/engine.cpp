@@ -229,6 +229,7 @@ static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int 
   in.rowStopCalls = be.set_row_stop && be.decode_rows;
   in.verifyRow = be.verify_row != nullptr;
   in.verifyRowSampled = be.verify_row_sampled && be.set_row_sampler && be.sample_row;
+  in.verifyRows = be.verify_rows != nullptr;
   return tgxh::spec_mode(in);
 }
 bool GPTEngine::speculateActive(int batch) const { return spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) != tgxh::SpecMode::Off; }
@@ -254,6 +255,47 @@ bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool&
   for (int32_t i = 0; i < n; i++) seq.push_back((int32_t)ids[i]);
   finished = fin != 0;
   return n > 0 || finished ? true : fail("speculate: the row produced no token");
+}
+
+bool GPTEngine::speculateMoreRows(std::vector<std::vector<int32_t>>& seqs, int64_t maxTotal, std::vector<char>& finished, std::vector<int64_t>& produced) {
+  const int B = (int)seqs.size();
+  produced.assign((size_t)B, 0);
+  std::vector<int32_t> rows, nDraft, outN, outFin;
+  std::vector<int64_t> drafts, outIds;
+  auto flush = [&]() -> bool {      // one tgx_verify_rows call over the rows gathered so far
+    if (rows.empty()) return true;
+    const size_t n = rows.size();
+    outIds.assign(n * (TGX_MAX_DRAFT + 1), 0); outN.assign(n, 0); outFin.assign(n, 0);
+    if (drafts.empty()) drafts.push_back(0);      // (a valid pointer for a call without any draft)
+    if (be_.verify_rows(model_.ctx, (int)n, rows.data(), drafts.data(), nDraft.data(), outIds.data(), outN.data(), outFin.data()) != TGX_OK)
+      return fail(std::string("verify_rows: ") + be_.last_error(model_.ctx));
+    bool drafted = false;
+    for (size_t i = 0; i < n; i++) {
+      const int b = rows[i];
+      if (outN[i] < 1 && !outFin[i]) return fail("speculate: a row produced no token");
+      for (int32_t k = 0; k < outN[i]; k++) seqs[(size_t)b].push_back((int32_t)outIds[i * (TGX_MAX_DRAFT + 1) + (size_t)k]);
+      produced[(size_t)b] = outN[i];
+      finished[(size_t)b] = outFin[i] != 0;
+      if (nDraft[i] > 0) { drafted = true; spec_.draftTokens += nDraft[i]; spec_.acceptedDrafts += outN[i] - 1; spec_.producedHist[outN[i]]++; }
+      else spec_.plainSteps++;
+    }
+    if (drafted) spec_.verifyCalls++;
+    rows.clear(); nDraft.clear(); drafts.clear();
+    return true;
+  };
+  int64_t M = 0;
+  for (int b = 0; b < B; b++) {
+    std::vector<int32_t>& seq = seqs[(size_t)b];
+    if (finished[(size_t)b] || (int64_t)seq.size() >= maxTotal) continue;
+    const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();
+    const int64_t cap = std::min<int64_t>({(int64_t)config_.speculate, (int64_t)TGX_MAX_DRAFT, room - 1, contextSize() - past - 1});
+    const std::vector<int32_t> draft = cap >= 1 ? ngram_draft(seq, (int)cap) : std::vector<int32_t>();
+    if (M + (int64_t)draft.size() + 1 > TGX_MAX_VERIFY_POSITIONS) { if (!flush()) return false; M = 0; }
+    rows.push_back(b); nDraft.push_back((int32_t)draft.size());
+    for (int32_t t : draft) drafts.push_back(t);
+    M += (int64_t)draft.size() + 1;
+  }
+  return flush();
 }
 
 // ---- GPTConfig::logprobs: the per-row calls record on the device (include/tgx.h tgx_set_row_logprobs); the engine drains each row's ring after every call,
@@ -337,9 +379,9 @@ template <class F> struct AtExit { F f; ~AtExit() { f(); } };
 template <class F> AtExit<F> at_exit(F f) { return AtExit<F>{std::move(f)}; }
 
 // GPTConfig::speculateSampled made row 0's sampler the call's: back to the default, so that a later greedy call's per-row steps are greedy whatever ran before
-void GPTEngine::rowSamplerEnd() {
+void GPTEngine::rowSamplerEnd(int batch) {
   const tgx_sampler_cfg greedy{0.f, 0, 1.f, 0.f};
-  be_.set_row_sampler(model_.ctx, 0, &greedy, 0);
+  for (int b = 0; b < batch; b++) be_.set_row_sampler(model_.ctx, b, &greedy, 0);
 }
 
 void GPTEngine::logprobsEnd(int batch) {
@@ -401,7 +443,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(B); });
   const bool procOn = processorsOn(), specSampled = speculateSampledActive(B), perRow = lpOn || procOn || specSampled;
   const auto procOff = at_exit([&] { if (procOn) processorsEnd(B); });
-  const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(); });
+  const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(B); });
   if (procOn)      // every row's history: the prompt it admitted, without the left padding
     for (int b = 0; b < B; b++) {
       const int64_t n = std::min<int64_t>((int64_t)prompts[(size_t)b].size(), S);
@@ -414,7 +456,25 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   if (be_.sample(model_.ctx, &sc, config_.seed, first.data()) != TGX_OK) { fail(std::string("sample: ") + be_.last_error(model_.ctx)); return out; }
   const auto t1 = std::chrono::steady_clock::now();
   // decode: maxNewTokens-1 iterations, no EOS check (:165-172)
-  if (n_new > 1 && speculateActive(B)) {      // ... of which a verified draft covers several at once: no stop ids (no EOS check here), the length on the device
+  if (n_new > 1 && B > 1 && speculateActive(B)) {      // a batch: every unfinished row advances through tgx_verify_rows, with its own draft or none
+    std::vector<std::vector<int32_t>> seqs((size_t)B);
+    for (int b = 0; b < B; b++) {
+      for (int64_t i = 0; i < S; i++) seqs[(size_t)b].push_back((int32_t)ids[(size_t)(b * S + i)]);
+      seqs[(size_t)b].push_back((int32_t)first[(size_t)b]);
+      if (be_.set_row_stop(model_.ctx, b, (int32_t)(n_new - 1), nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+    }
+    std::vector<char> finished((size_t)B, 0);
+    std::vector<int64_t> produced;
+    auto open = [&] { for (int b = 0; b < B; b++) if (!finished[(size_t)b] && (int64_t)seqs[(size_t)b].size() < S + n_new) return true; return false; };
+    while (open()) {
+      if (!speculateMoreRows(seqs, S + n_new, finished, produced)) return out;
+      for (int b = 0; lpOn && b < B; b++) if (!logprobsDrain(b, produced[(size_t)b], lpRows[(size_t)b])) return out;
+    }
+    for (int b = 0; b < B; b++) {
+      if ((int64_t)seqs[(size_t)b].size() != S + n_new) { fail("speculate: a row finished before maxNewTokens"); return out; }
+      for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)(i * B + b)] = seqs[(size_t)b][(size_t)(S + 1 + i)];
+    }
+  } else if (n_new > 1 && speculateActive(B)) {      // ... of which a verified draft covers several at once: no stop ids (no EOS check here), the length on the device
     std::vector<int32_t> seq;
     for (int64_t i = 0; i < S; i++) seq.push_back((int32_t)ids[(size_t)i]);
     seq.push_back((int32_t)first[0]);

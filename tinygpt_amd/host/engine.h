@@ -54,7 +54,8 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // Not in the reference: greedy speculative decoding with prompt lookup (spec_draft.h).  0 = off: the loops below exactly as they were.  N > 0: up to N draft
   // tokens (clamped to TGX_MAX_DRAFT) are proposed per iteration and verified in one pass (tgx_verify_row); without a match one ordinary step runs.  Active only
   // for a greedy sampler configuration, ONE sequence, at most TGX_MAX_STOP_IDS EOS ids and a backend that has the calls — otherwise the existing loop runs.  The
-  // produced ids are those of the existing loop up to the summation order between kernel paths (include/tgx.h tgx_verify_row).
+  // produced ids are those of the existing loop up to the summation order between kernel paths (include/tgx.h tgx_verify_row).  A backend that exports
+  // tgx_verify_rows lifts "one sequence" in generateSync: every row of the batch drafts on its own sequence and all rows advance through one joint call.
   int speculate = 0;
   // ... and under a SAMPLING configuration (default false: every existing run is unchanged).  With it set, speculate > 0, one sequence, a non-greedy sampler,
   // neutral processors and a backend that exports tgx_verify_row_sampled, the generate loops take the per-row path: the row's sampler is the call's
@@ -192,13 +193,16 @@ class GPTEngine {
   // row 0 holds seq minus its last token, which is its current token; the row's stop conditions are set.  Drafts from seq, verifies (or takes one ordinary
   // step), appends what the row produced — never more than maxTotal tokens in seq.  finished: the row finished on the device.  false: a call failed (err_ set)
   bool speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished);
+  // the same for a batch (the backend exports tgx_verify_rows): seqs[b] as seq above for row b, every unfinished row advanced by ONE tgx_verify_rows call per chunk
+  // of TGX_MAX_VERIFY_POSITIONS positions — its prompt-lookup draft, or no draft at all (the row then takes one token).  produced[b]: tokens appended to row b
+  bool speculateMoreRows(std::vector<std::vector<int32_t>>& seqs, int64_t maxTotal, std::vector<char>& finished, std::vector<int64_t>& produced);
   // GPTConfig::logprobs
   struct RowLogprobs { std::vector<float> lp, topLp; std::vector<int32_t> topId; };
   bool logprobsActive() const;
   bool logprobsRefused(bool async);                                                            // logprobs asked for and not servable: err_ set, the generate call fails
   bool logprobsDrain(int row, int64_t n, RowLogprobs& into);                                  // appends the row's last n records
   void logprobsEnd(int batch);
-  void rowSamplerEnd();                                       // GPTConfig::speculateSampled: row 0's sampler back to the default when the call ends
+  void rowSamplerEnd(int batch = 1);                          // GPTConfig::speculateSampled: the rows' sampler back to the default when the call ends
   void logprobsStore(GPTOutput& out, const std::vector<RowLogprobs>& rows, int64_t perRow) const;
   // SamplerConfig's penalties / logit bias
   bool processorsOn() const { return !config_.samplerConfig.processorsNeutral(); }

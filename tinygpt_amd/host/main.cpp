@@ -47,7 +47,8 @@ static void usage(const char* prog) {
           "  --session-save <file>     with --stream and one text prompt: keep the conversation's KV cache (prompt + generated tokens) in a file when the run ends\n"
           "                            (neither flag combines with --speculate, --logprobs, the penalties or --logit-bias: those runs end with the row finished on the\n"
           "                            device, which keeps no cache to save)\n"
-          "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (one prompt, --temperature 0 --top-p 1; default: 0 = off)\n"
+          "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (--temperature 0 --top-p 1; several prompts: every row's\n"
+          "                            draft in one joint pass; default: 0 = off)\n"
           "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n",
           prog);
 }

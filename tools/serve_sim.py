@@ -10,7 +10,8 @@ serving loop would drive it, on the real kernels: a seeded stream of requests (p
 
 With --mix every request draws its own sampler settings (greedy, T 0.8 / top-p 0.9, T 1.0 / top-k 50, T 0.7 / min-p 0.05) and seed, and the ticks run
 tgx_decode_rows (per-row settings, include/tgx.h); with --device-stop as well, each request's output length is its max_new (tgx_set_row_stop) and every tick
-is a full 16-step tgx_decode_rows call — the rows finish on the device, the host reads their counts back instead of limiting the call to the shortest output.
+is a full 16-step tgx_decode_rows call — the rows finish on the device, the host reads their counts back instead of limiting the call to the shortest output.  With --speculate N on top of the two, every tick is ONE
+tgx_verify_rows call instead (per 64 positions): each live row with a prompt-lookup draft of up to N tokens from its own history, or with none.
 
 With --n-best K every request wants K samples of its prompt (T 0.8 / top-p 0.9, seeds s .. s + K - 1, all of the request's output length): the request is admitted into
 K idle rows as ONE tgx_forward_row plus ONE tgx_fork_row (include/tgx.h; on a paged cache the prompt's full blocks are held once) — or, with --n-best-separate, as K
@@ -42,6 +43,7 @@ ap.add_argument("--seed", type=int, default=7)
 ap.add_argument("--sampler", default="", help="e.g. 'temperature=0.8,top_p=0.9' (default: greedy)")
 ap.add_argument("--mix", action="store_true", help="per-request sampler settings and seeds through tgx_decode_rows")
 ap.add_argument("--device-stop", action="store_true", help="(with --mix) output lengths as max_new on the device, full 16-step calls")
+ap.add_argument("--speculate", type=int, default=0, help="(with --mix --device-stop) prompt-lookup drafts of up to N tokens per row, one tgx_verify_rows call per tick in place of tgx_decode_rows")
 ap.add_argument("--joint", action="store_true", help="admit every request that fits in a tick with ONE tgx_forward_rows call, then tgx_sample_row per row")
 ap.add_argument("--n-best", type=int, default=0, help="K samples per request: one prefill + tgx_fork_row into K - 1 rows (paged KV: --kv-budget)")
 ap.add_argument("--n-best-separate", action="store_true", help="(with --n-best) admit the K samples as K copies of the prompt in one tgx_forward_rows call instead")
@@ -80,12 +82,26 @@ def born():
         m.reset_row(r)
 
 
+def lookup(seq, cap):
+    """prompt lookup: the tokens that followed the latest earlier occurrence of the sequence's last 3 / 2 / 1 tokens, at most cap of them"""
+    for k in (3, 2, 1):
+        if len(seq) <= k or cap < 1:
+            continue
+        tail = seq[-k:]
+        for s0 in range(len(seq) - k - 1, -1, -1):
+            if seq[s0:s0 + k] == tail:
+                return seq[s0 + k:s0 + k + cap]
+    return []
+
+
 def serve(policy):
     born()
     waiting = list(range(len(reqs)))
     length, target = [0] * B, [0] * B
     produced = steps = live_steps = calls = 0
     peak_tokens = 0
+    hist = [[] for _ in range(B)]      # --speculate: every row's tokens so far (prompt + produced), the drafter's input
+    drafted = [0, 0]                   # draft tokens offered / accepted
     m.synchronize(); t0 = time.perf_counter()
     while waiting or any(length):
         idle = [r for r in range(B) if not length[r]]
@@ -104,7 +120,8 @@ def serve(policy):
                     admit.append((r, i))
                 elif args.mix:
                     cfg, seed = req_cfg[i]
-                    m.forward_row(r, prompts[i]); m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
+                    m.forward_row(r, prompts[i]); t = m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
+                    hist[r] = [int(x) for x in prompts[i]] + [int(t)]
                     if STOP:
                         m.set_row_stop(r, max_new=new)
                 else:
@@ -117,7 +134,8 @@ def serve(policy):
                 for r, i in admit:
                     if args.mix:
                         cfg, seed = req_cfg[i]
-                        m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
+                        t = m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed)
+                        hist[r] = [int(x) for x in prompts[i]] + [int(t)]
                         if STOP:
                             m.set_row_stop(r, max_new=reqs[i][1])
                     else:
@@ -125,6 +143,26 @@ def serve(policy):
         live = [r for r in range(B) if length[r]]
         if not live:
             raise SystemExit("the budget admits no request")
+        if STOP and args.speculate > 0:                        # one tgx_verify_rows per tick (per 64 positions): every live row with its prompt-lookup draft, or none
+            group, pos = [], 0
+            todo = []
+            for r in live:
+                d = lookup(hist[r], min(args.speculate, 15, args.max_ctx - length[r] - 1))
+                if pos + len(d) + 1 > 64:
+                    todo.append(group); group, pos = [], 0
+                group.append((r, d)); pos += len(d) + 1
+            todo.append(group)
+            for group in todo:
+                res = m.verify_rows([r for r, _ in group], [d for _, d in group])
+                calls += 1; steps += 1
+                for (r, d), (ids, fin) in zip(group, res):
+                    hist[r].extend(int(t) for t in ids)
+                    length[r] += len(ids); produced += len(ids); live_steps += len(ids)
+                    peak_tokens = max(peak_tokens, sum(length))
+                    drafted[0] += len(d); drafted[1] += len(ids) - 1 if d else 0
+                    if fin:
+                        m.reset_row(r); length[r] = target[r] = 0
+            continue
         if STOP:                                               # full calls; the rows finish on the device
             n = 16
             _, cnt, fin = m.decode_rows(n)
@@ -153,6 +191,8 @@ def serve(policy):
     print(f"{policy:10s} {len(reqs)} requests, {produced} tokens generated in {dt:.2f} s = {produced / dt:8.0f} tokens/s; {steps} steps in {calls} decode calls, "
           f"{live_steps / max(steps, 1):.1f} live rows per step of {B}; most tokens held at once {peak_tokens} (cache: {budget} tokens"
           f"{', paged' if args.kv_budget else ' as slabs'})", flush=True)
+    if STOP and args.speculate > 0:
+        print(f"           --speculate {args.speculate}: {drafted[1]} of {drafted[0]} draft tokens accepted, one tgx_verify_rows call per tick and 64 positions", flush=True)
 
 
 def serve_nbest(K, fork):

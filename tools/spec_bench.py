@@ -16,7 +16,12 @@ usage: python tools/spec_bench.py [--reps 9] [--out profiles/verify_row.txt]
 the sampled verify (drafts from the row's own sampled run: all accepted, as far as the two paths agree), the greedy verify of the same build, one sampled and one
 greedy tgx_decode_rows step of this build and — with --parent-lib, a libtgx_mi355x.so built from the parent commit, loaded beside this one — one sampled step of the
 parent.  Then the host engine free-running with speculateSampled on the repetitive prompt: tokens per pass and acceptance.
-usage: python tools/spec_bench.py --sampler 0.8,0,0.9,0 [--parent-lib PATH] [--reps 9] [--out profiles/verify_sampled.txt]"""
+usage: python tools/spec_bench.py --sampler 0.8,0,0.9,0 [--parent-lib PATH] [--reps 9] [--out profiles/verify_sampled.txt]
+
+--rows B[,B..] (profiles/verify_rows.txt): tgx_verify_rows over B rows at context 2048 — 4 and 8 positions per row, greedy and T 0.8 / top-p 0.9, extend.attn_splits
+0, -1, the split count min(32, 2 * 256 CUs / (B * heads)) of the automatic rule and 2 / 4 / 8 — against B sequential tgx_verify_row_sampled calls and one B-row tgx_decode_rows step
+of the parent commit's library (--parent-lib; without it, of this build), and the accepted drafts per row from which the joint call beats plain stepping.
+usage: python tools/spec_bench.py --rows 2,4,8 [--parent-lib PATH] [--reps 9] [--out profiles/verify_rows.txt]"""
 import argparse
 import ctypes
 import os
@@ -246,13 +251,93 @@ def free_running_sampled(cfg, lines):
     e.close()
 
 
+def measure_rows(B_list, reps, lines, parent_lib):
+    """--rows (profiles/verify_rows.txt): ms per tgx_verify_rows call over B rows at context 2048, 4 and 8 positions per row, greedy and T 0.8 / top-p 0.9, with
+    extend.attn_splits 0, -1 and the split counts the automatic rule would pick; against B sequential tgx_verify_row_sampled calls and one B-row tgx_decode_rows
+    step — both of the parent commit's library with --parent-lib, else of this build.  Derived: the mean number of accepted draft tokens per row from which the
+    joint call beats plain stepping = joint / step - 1."""
+    from tinygpt_amd.ffi import ABI, Backend, SamplerCfg
+    Bmax = max(B_list)
+    d = known_desc("llama-3.2-1b", "bf16")
+    d.max_batch, d.max_ctx = Bmax, S + 64
+    new = ("verify_rows",)
+    m = Model(d).load_synthetic(1234, 0.02).finalize()
+    old = Model(d, backend=Backend(parent_lib, "tgx_", required=[n for n in ABI if n not in new])).load_synthetic(1234, 0.02).finalize() if parent_lib else m
+    V = d.vocab
+    prompts = [synth.synth_prompt(V, S, 1234 + r) for r in range(Bmax)]
+    samplers = {"greedy": GREEDY, "T 0.8 / top-p 0.9": SamplerCfg(0.8, 0, 0.9, 0.0)}
+    cus = 256
+
+    def fresh_rows(mm, B, c):
+        mm.reset_cache()
+        mm.forward_rows(range(B), prompts[:B])
+        for r in range(B):
+            mm.set_row_sampler(r, c, 7 + r)
+        return [int(mm.sample_row(r, c, 7 + r)) for r in range(B)]
+
+    lines.append("baselines from: %s; ms per call, synchronised: median (min .. max) over %d interleaved repeats" % ("the parent commit's library" if parent_lib else "this build (no --parent-lib)", reps))
+    lines.append("  B | positions/row | sampler | one B-row step | B one-row verify calls | joint, splits 0 | joint, splits -1 (what the rule picks) | joint at explicit split counts | joint(-1) / sequential | break-even accepted drafts per row (joint(-1) / step - 1) | form")
+    for B in B_list:
+        ns_rule = min(32, 2 * cus // (B * d.heads))
+        for P in (4, 8):
+            n = P - 1
+            for sname, c in samplers.items():
+                fresh_rows(m, B, c)
+                ref = m.decode_rows(n)[0]                       # every row's own continuation: all accepted, as far as the paths agree
+                drafts = [[int(t) for t in ref[:, r]] for r in range(B)]
+                variants = [("0", 0), ("-1", -1)] + [(str(k), k) for k in sorted({2, 4, 8} | ({ns_rule} if ns_rule >= 2 else set()))]
+                t = {k: [] for k in ["step", "seq"] + [v[0] for v in variants]}
+                form = picked = 0
+                for rep in range(reps + 2):                     # two warm-up rounds, discarded
+                    keep = rep >= 2
+                    fresh_rows(old, B, c)
+                    ms, _ = timed(lambda: old.decode_rows(1))
+                    if keep:
+                        t["step"].append(ms)
+                    fresh_rows(old, B, c)
+                    ms, _ = timed(lambda: [old.verify_row_sampled(r, drafts[r]) for r in range(B)])
+                    if keep:
+                        t["seq"].append(ms)
+                    for k, ns in variants:
+                        m.set_option("extend.attn_splits", ns)
+                        fresh_rows(m, B, c)
+                        ms, _ = timed(lambda: m.verify_rows(range(B), drafts))
+                        form = m.get_option("verify.last_form")
+                        if k == "-1":
+                            picked = m.get_option("verify.last_splits")
+                        if keep:
+                            t[k].append(ms)
+                    m.set_option("extend.attn_splits", -1)
+                step, seq, auto = statistics.median(t["step"]), statistics.median(t["seq"]), statistics.median(t["-1"])
+                lines.append("  %d | %d | %s | %s | %s | %s | %s | %s | %.2f | %.2f | %d" % (
+                    B, P, sname, med(t["step"]), med(t["seq"]), med(t["0"]), "%s (%s)" % (med(t["-1"]), picked or "unsplit"),
+                    "; ".join("%s: %.3f" % (k, statistics.median(t[k])) for k, _ in variants[2:]),
+                    auto / seq, auto / step - 1, form))
+    m.close()
+    if old is not m:
+        old.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default="")
+    ap.add_argument("--rows", default="", help="B[,B..]: measure tgx_verify_rows over B rows instead (profiles/verify_rows.txt), e.g. --rows 2,4,8")
     ap.add_argument("--sampler", default="", help="T,K,P,M: measure tgx_verify_row_sampled under this sampler instead")
-    ap.add_argument("--parent-lib", default="", help="with --sampler: a libtgx_mi355x.so of the parent commit, for the A/B step")
+    ap.add_argument("--parent-lib", default="", help="with --sampler / --rows: a libtgx_mi355x.so of the parent commit, for the A/B baselines")
     a = ap.parse_args()
+    if a.rows:
+        import torch
+        lines = ["tools/spec_bench.py --rows %s --reps %d%s   device: %s   Llama-3.2-1B bf16 synthetic, %d-token prompts, unpaged" % (
+            a.rows, a.reps, " --parent-lib <parent build>" if a.parent_lib else "", torch.cuda.get_device_name(0), S)]
+        measure_rows([int(b) for b in a.rows.split(",")], a.reps, lines, a.parent_lib)
+        text = "\n".join(lines) + "\n"
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     if a.sampler:
         import torch
         from tinygpt_amd.ffi import SamplerCfg
