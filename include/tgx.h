@@ -477,6 +477,69 @@ TGX_API int tgx_verify_rows(tgx_ctx* ctx, int n, const int32_t* rows, const int6
                             const int32_t* n_draft /* [n], each in [0, TGX_MAX_DRAFT] */, int64_t* out_ids /* [n][TGX_MAX_DRAFT + 1] */, int32_t* out_n /* [n] */,
                             int32_t* out_finish /* [n] */);
 
+/* ---- chunked prefill: prompt chunks and live rows' steps in one ragged pass (additive to ABI 3) -----------------------------------------------------------
+ * While a prompt is prefilled every live row stands still, and the weights are streamed again for the live rows' next step.  tgx_advance_rows puts both into
+ * ONE causal pass over the weights: each named row either STEPs (tgx_verify_rows' "current token + draft", 0 drafts = one plain step) or is FED the next piece
+ * of its prompt.  A scheduler that admits a waiting request in pieces of <= N tokens, one piece per call, bounds the stall of its live rows by one such call.
+ *
+ *   Kinds             kinds[i] = TGX_ADV_STEP: a live row with a current token; lens[i] in [0, TGX_MAX_DRAFT] draft ids.  TGX_ADV_FEED: lens[i] >= 1 supplied ids;
+ *                     the last position's logits land in the row's slot.  TGX_ADV_FEED_MORE: lens[i] >= 1 supplied ids, more of the prompt follows: no lm_head
+ *                     for this row.  `ids` holds sum(lens) ids back to back in array order (it may be NULL when that sum is 0).
+ *   Equivalence       the call equals, up to the order of the fp32 sums (the contract between kernel paths): tgx_verify_rows over the STEP rows in array order;
+ *                     for each FEED / FEED_MORE row on a retired or empty row < batch or a new row, tgx_forward_row(row, its ids, lens[i]); for each FEED /
+ *                     FEED_MORE row on a live or finished row that holds >= 1 positions — a row in the no-logits state included — tgx_extend_row(row, its ids,
+ *                     lens[i]): the current token is discarded and a finished state is cleared.  The new rows of a call are exactly batch .. batch + k - 1, as
+ *                     for tgx_forward_rows.  A prompt fed in pieces leaves the row as tgx_forward_row of the whole prompt does, up to the order of the sums.
+ *   FEED_MORE         afterwards the row holds past + lens[i] positions and is in tgx_truncate_row's state "no logits and no current token": tgx_sample_row,
+ *                     the decode calls, tgx_fork_row and a STEP on it are TGX_ERR_STATE until a FEED, tgx_extend_row or tgx_score_row has run on it;
+ *                     tgx_save_row works (the prefix-only snapshot).  An admission by FEED_MORE counts as an admission: stop state and token count afresh,
+ *                     log-probability record count 0, settings kept.
+ *   Outputs           STEP rows: out_ids[i * (TGX_MAX_DRAFT + 1) ..], out_n[i], out_finish[i] as tgx_verify_rows.  FEED and FEED_MORE rows: out_n[i] = 0,
+ *                     out_finish[i] = 0.  Named rows otherwise end as the equivalent calls leave them; rows not named keep their state bit for bit and do not
+ *                     step.  No ticket, token log or host ring moves.  tgx_read_pass_logits returns the STEP positions in call order (TGX_ERR_STATE after a call
+ *                     without a STEP row).
+ *   Limits            the STEP positions together (sum of lens[i] + 1) <= TGX_MAX_VERIFY_POSITIONS; all positions together <= TGX_MAX_ADVANCE_POSITIONS; n in
+ *                     [1, max_batch]; rows distinct.  A call with no STEP row, or with no FEED row, is legal.
+ *   Refused           first the call's own: null pointers, n out of range, a kinds[i] outside 0 .. 2, a lens[i] < 0, either position limit: TGX_ERR_INVALID.  Then
+ *                     per row in array order, each row's checks in the order and with the codes of its equivalent call (tgx_verify_rows' per-row checks, a
+ *                     logit processor on a STEP row -> TGX_ERR_UNSUPPORTED included; tgx_extend_row's; tgx_forward_row's), a row named twice TGX_ERR_INVALID;
+ *                     then "the new rows are batch .. batch + k - 1" (TGX_ERR_INVALID) and, on a paged cache, more than 1024 blocks per row on a matrix-core
+ *                     route (TGX_ERR_UNSUPPORTED).
+ *   Paged KV          the blocks of ALL named rows are counted together against the free list plus what the target rows of admissions give back, before any
+ *                     is assigned; if they do not all fit: TGX_ERR_CONTEXT.  STEP rows give the blocks of their rejected tail back, as after tgx_verify_rows.
+ *   ALL OR NOTHING    a refused call changes no row, moves no block, leaves kv.free_tokens as it was and does not poison the context.
+ *   Forms             read-only option `advance.last_form`: 0 no call yet, 1 the joint pass, 2 piecewise.  Piecewise — fp32 storage, `prefill.mfma` 0, layer
+ *                     shapes the matrix-core tile does not cover, all positions together below the matrix-core routes' minimum — runs the equivalent calls one
+ *                     after another behind the joint checks and block count (tgx_verify_rows, then the continuations in array order, then the admissions in
+ *                     row order): the results are those calls' results bit for bit.
+ *   The joint pass    the ragged pass of tgx_forward_rows with every sequence from its own length, the STEP sequences first in the workspace: one all-position
+ *                     lm_head pass and one accept launch for the STEP rows (tgx_verify_rows' own; where the STEP positions alone would not take the short-prompt
+ *                     route, one pass per four positions), ceil(F / 4) lm_head passes for F FEED rows (tgx_forward_rows' own), none for FEED_MORE rows; one
+ *                     upload of tables + ids, one sampler chain per sampled STEP row, one read-back.
+ *   Attention         option `advance.attn_tiles` (kernels/attn_mixed.h): one work list whose items carry a key range.  0: never split — the pass's list is
+ *                     exactly tgx_forward_rows' list and order, one workgroup per (sequence, query block, head) walking every 64-key tile of its causal range.
+ *                     N >= 1: a query block whose range exceeds N tiles is cut at tile boundaries into ranges of <= N tiles (at most 32 ranges; N is doubled
+ *                     while the partials would exceed 512 MiB), each leaving an unnormalised partial; a merge launch walks a block's partials in split
+ *                     order: the same bits from run to run.  At most three launches per layer (whole blocks, ranges, merge).  -1: the largest N that gives
+ *                     those launches two workgroups per CU, the rule measured for tgx_verify_rows' key-split form.  The default is 16: it won or tied the
+ *                     sweep of profiles/advance_rows.txt (head_dim 64, contexts up to 2048; head_dim 128 unmeasured), where -1 did not.  Read-only option
+ *                     `advance.last_tiles`: the N of the last joint pass.
+ *   Memory            a context that never makes the call allocates nothing new and runs exactly the launches it ran before.  The first call with a STEP row
+ *                     sizes tgx_verify_rows' workspace, the first joint pass that splits a block the partials' (grown on demand).
+ *   Cost              measured (tools/admit_bench.py --mixed, profiles/advance_rows.txt; Llama-3.2-1B bf16, ms per call, the baseline tgx_decode_rows(1) +
+ *                     tgx_extend_row(chunk) on the parent commit's library, spread of a figure ~0.05): 8 step rows at context ~300 plus a chunk of 128 / 256 /
+ *                     512 at past 256: 2.77 / 3.50 / 4.52 against 2.93 / 3.54 / 4.46 — below the two calls by more than the spread at 128, inside it at 256 and
+ *                     512.  32 step rows: 3.56 / 4.14 / 5.19 against 3.32 / 3.91 / 4.83 — ABOVE the two calls, and at context 2048 6.10 against 4.20: a STEP
+ *                     row's one query rides a 128-query block of the prompt attention (one of four waves works), which the batched step's own attention
+ *                     kernel does not pay.  What the call buys at those shapes is the bound on the stall (one call per tick, no live row waits for a whole
+ *                     prompt), not time. */
+#define TGX_ADV_STEP      0
+#define TGX_ADV_FEED      1
+#define TGX_ADV_FEED_MORE 2
+#define TGX_MAX_ADVANCE_POSITIONS 8192
+TGX_API int tgx_advance_rows(tgx_ctx* ctx, int n, const int32_t* rows, const int32_t* kinds, const int64_t* ids /* sum(lens) ids back to back, in array order */,
+                             const int32_t* lens /* [n] */, int64_t* out_ids /* [n][TGX_MAX_DRAFT + 1] */, int32_t* out_n /* [n] */, int32_t* out_finish /* [n] */);
+
 /* ---- per-token log-probabilities on the device (additive to ABI 3) --------------------------------------------------------------------------------------
  * n-best ranking, beams and the completions protocol's `logprobs` / `top_logprobs` (the reference's server speaks it) need the model's opinion of the tokens it
  * produces.  For a row that produced token t from the fp32 logits v[0 .. V) — what the argmax and the sampler look at, tgx_read_logits(rounded = 0) —
@@ -643,6 +706,9 @@ TGX_API int tgx_set_logits(tgx_ctx* ctx, const float* logits, int batch);
  *   "extend.attn_splits"  (default -1) the attention of a tgx_extend_row pass of <= 128 positions (16-bit storage): -1 = split over the keys (kernels/attn_extend.h) from
  *                  the measured context on, min(32, CUs / heads) splits; 0 = never (the per-row prompt attention, which also serves longer passes, fp32 storage and
  *                  passes by steps); N >= 1 = N splits (at most one per 64-key tile) wherever the split form applies.  tgx_get_option reads it back
+ *   "advance.attn_tiles"  (default 16) the attention of a tgx_advance_rows joint pass: a query block whose causal key range exceeds this many 64-key tiles is cut into
+ *                  ranges of at most that many (kernels/attn_mixed.h); 0 = never split, -1 = the largest target that gives the launches two workgroups per CU.
+ *                  tgx_get_option reads it back, and the read-only "advance.last_form" / "advance.last_tiles" (tgx_advance_rows above)
  *   "debug.*"      experiment switches (tools/gemv_dissect.py, tools/attn_dissect.py; live only in a -DTGX_DISSECT=1 build) */
 TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
 

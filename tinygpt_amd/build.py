@@ -27,8 +27,9 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 
 def _deps():
-    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h")]
-    kd = os.path.join(CSRC, "kernels")
+    deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
+            os.path.join(CSRC, "attn_worklist.h")]
+    kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
 
@@ -106,6 +107,11 @@ def build_dev_mem_check(force: bool = False, verbose: bool = False):
 def build_row_snapshot_check(force: bool = False, verbose: bool = False):
     """tests/row_snapshot_check.cpp, the CPU audit of csrc/row_snapshot.h."""
     return _build_cpu_check("row_snapshot_check", os.path.join(CSRC, "row_snapshot.h"), force, verbose)
+
+
+def build_attn_worklist_check(force: bool = False, verbose: bool = False):
+    """tests/attn_worklist_check.cpp, the CPU audit of csrc/attn_worklist.h."""
+    return _build_cpu_check("attn_worklist_check", os.path.join(CSRC, "attn_worklist.h"), force, verbose)
 
 
 def build_spec_draft_check(force: bool = False, verbose: bool = False):

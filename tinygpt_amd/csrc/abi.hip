@@ -1202,6 +1202,40 @@ static int score_read_back(tgx_ctx* c, const ScoreCall* sc) {
   return TGX_OK;
 }
 
+// the four lm_head staging rows of a ragged pass, at first use
+static int ensure_rg_lm_ws(tgx_ctx* c) {
+  if (c->rg_x) return TGX_OK;
+  const size_t V = (size_t)c->d.vocab, H = (size_t)c->d.hidden, P = (size_t)c->lm_grid;
+  int rc;
+  if ((rc = dev_alloc(c, &c->rg_x, 4 * H)) || (rc = dev_alloc(c, &c->rg_logits, 4 * V)) || (rc = dev_alloc(c, &c->rg_part_val, 4 * P)) || (rc = dev_alloc(c, &c->rg_part_idx, 4 * P))) return rc;
+  return TGX_OK;
+}
+// lm_head of the batch rows rws[] whose hidden rows a ragged pass left (tgx_forward_rows, tgx_advance_rows' FEED rows): four at a time (tgx_forward's grouping where
+// they are consecutive rows; else gathered into staging rows and scattered back)
+static void launch_lm_head_rows(tgx_ctx* c, const std::vector<int>& rws) {
+  const size_t V = (size_t)c->d.vocab, H = (size_t)c->d.hidden, P = (size_t)c->lm_grid;
+  for (size_t k = 0; k < rws.size();) {
+    const size_t rem = rws.size() - k, real = std::min<size_t>(rem, 4);
+    const int R = rem >= 3 ? 4 : (int)rem;
+    bool consec = (int)real == R;
+    for (size_t j = 1; j < real; j++) consec = consec && rws[k + j] == rws[k] + (int)j;
+    if (consec) {
+      launch_lm_head(c, rws[k], R);
+    } else {
+      for (int j = 0; j < R; j++)
+        (void)hipMemcpyAsync(c->rg_x + j * H, c->rows[(size_t)rws[k + std::min<size_t>(j, real - 1)]].x, H * 4, hipMemcpyDeviceToDevice, c->stream);
+      launch_lm_head_at(c, c->rg_x, c->rg_logits, c->rg_part_val, c->rg_part_idx, R);
+      for (size_t j = 0; j < real; j++) {
+        RowState& r = c->rows[(size_t)rws[k + j]];
+        (void)hipMemcpyAsync(r.logits, c->rg_logits + j * V, V * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.part_val, c->rg_part_val + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.part_idx, c->rg_part_idx + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
+      }
+    }
+    k += real;
+  }
+}
+
 // sc (tgx_score_row; n == 1, may_join false): the pass also scores its positions (issue_pass)
 static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, bool may_join, ScoreCall* sc = nullptr) {
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
@@ -1264,11 +1298,7 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
     const size_t o_ids = bytes;
     bytes += (size_t)total * 8;
     if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
-    if (!c->rg_x) {
-      const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
-      int rc;
-      if ((rc = dev_alloc(c, &c->rg_x, 4 * H)) || (rc = dev_alloc(c, &c->rg_logits, 4 * V)) || (rc = dev_alloc(c, &c->rg_part_val, 4 * P)) || (rc = dev_alloc(c, &c->rg_part_idx, 4 * P))) return rc;
-    }
+    if (int rc = ensure_rg_lm_ws(c)) return rc;
     host.assign(bytes, 0);
     std::memcpy(host.data() + o_ids, ids, (size_t)total * 8);
     for (int g = 0; g < n_groups; g++) {
@@ -1294,28 +1324,9 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
         if (int rc = issue_pass(c, rows[i], 1, lens[i], /*past=*/0, /*verify=*/false, sc)) return rc;
       }
   }
-  // lm_head of the ragged passes: the call's rows four at a time (tgx_forward's grouping where they are consecutive rows; else gathered into staging rows and scattered back)
-  const size_t V = (size_t)d.vocab, H = (size_t)d.hidden, P = (size_t)c->lm_grid;
-  for (size_t k = 0; k < joint.size();) {
-    const size_t rem = joint.size() - k, real = std::min<size_t>(rem, 4);
-    const int R = rem >= 3 ? 4 : (int)rem;
-    bool consec = (int)real == R;
-    for (size_t j = 1; j < real; j++) consec = consec && rows[joint[k + j]] == rows[joint[k]] + (int)j;
-    if (consec) {
-      launch_lm_head(c, rows[joint[k]], R);
-    } else {
-      for (int j = 0; j < R; j++)
-        (void)hipMemcpyAsync(c->rg_x + j * H, c->rows[(size_t)rows[joint[k + std::min<size_t>(j, real - 1)]]].x, H * 4, hipMemcpyDeviceToDevice, c->stream);
-      launch_lm_head_at(c, c->rg_x, c->rg_logits, c->rg_part_val, c->rg_part_idx, R);
-      for (size_t j = 0; j < real; j++) {
-        RowState& r = c->rows[(size_t)rows[joint[k + j]]];
-        (void)hipMemcpyAsync(r.logits, c->rg_logits + j * V, V * 4, hipMemcpyDeviceToDevice, c->stream);
-        (void)hipMemcpyAsync(r.part_val, c->rg_part_val + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
-        (void)hipMemcpyAsync(r.part_idx, c->rg_part_idx + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
-      }
-    }
-    k += real;
-  }
+  std::vector<int> joint_rows(joint.size());
+  for (size_t k = 0; k < joint.size(); k++) joint_rows[k] = rows[joint[k]];
+  launch_lm_head_rows(c, joint_rows);
   for (size_t k = 0; k < joint.size(); k++) launch_add_pos(c, c->rows[(size_t)rows[joint[k]]].pos, lens[joint[k]]);
   if (sc) if (int rc = score_read_back(c, sc)) return rc;
   if (int rc = finish_pass(c)) return rc;
@@ -1889,6 +1900,207 @@ int tgx_verify_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* draft
   return TGX_OK;
 }
 
+// ---- tgx_advance_rows (include/tgx.h): STEP rows (tgx_verify_rows' sequences) and FEED / FEED_MORE rows (continuations from their row's length, admissions from 0)
+// in ONE ragged pass.  The STEP sequences come first in the workspace, so launch_lm_head_all(.., joint) and launch_verify_accept_rows serve them as they serve
+// tgx_verify_rows; the FEED rows take tgx_forward_rows' lm_head (launch_lm_head_rows), FEED_MORE rows none.  The attention is the mixed work list (prefill.hip
+// advance_tables; kernels/attn_mixed.h).  Where no matrix-core route takes the M positions the equivalent calls run one after another behind the joint checks:
+// advance.last_form 2.
+int tgx_advance_rows(tgx_ctx* c, int n, const int32_t* rows, const int32_t* kinds, const int64_t* ids, const int32_t* lens, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  const char* const fn = "tgx_advance_rows";
+  if (!c || !rows || !kinds || !lens || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "advance before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
+  // ---- every check before anything changes.  The call's own first: kinds, lens, the two position limits
+  long long M = 0, Ms = 0, n_ids = 0;
+  for (int i = 0; i < n; i++) {
+    if (kinds[i] < TGX_ADV_STEP || kinds[i] > TGX_ADV_FEED_MORE) return set_err(c, TGX_ERR_INVALID, "%s: kinds[%d] = %d (0 step, 1 feed, 2 feed, more follows)", fn, i, (int)kinds[i]);
+    if (lens[i] < 0) return set_err(c, TGX_ERR_INVALID, "%s: lens[%d] = %d < 0", fn, i, (int)lens[i]);
+    if (kinds[i] == TGX_ADV_STEP) Ms += (long long)lens[i] + 1;
+    M += (long long)lens[i] + (kinds[i] == TGX_ADV_STEP ? 1 : 0);
+    n_ids += lens[i];
+  }
+  if (Ms > TGX_MAX_VERIFY_POSITIONS) return set_err(c, TGX_ERR_INVALID, "%s: %lld step positions in one call (at most %d)", fn, Ms, TGX_MAX_VERIFY_POSITIONS);
+  if (M > TGX_MAX_ADVANCE_POSITIONS) return set_err(c, TGX_ERR_INVALID, "%s: %lld positions in one call (at most %d)", fn, M, TGX_MAX_ADVANCE_POSITIONS);
+  if (n_ids > 0 && !ids) return set_err(c, TGX_ERR_INVALID, "null argument");
+  // ... then per row in array order, each row's in its equivalent call's order
+  std::vector<long long> off((size_t)n + 1, 0);      // row i's ids at ids + off[i]
+  std::vector<char> named((size_t)d.max_batch, 0), holds((size_t)n, 0);
+  int n_new = 0;
+  for (int i = 0; i < n; i++) {
+    const int row = rows[i], len = lens[i];
+    off[(size_t)i + 1] = off[(size_t)i] + len;
+    const int64_t* const my = ids ? ids + off[(size_t)i] : nullptr;
+    if (row >= 0 && row < d.max_batch && named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    if (kinds[i] == TGX_ADV_STEP) {
+      if (len > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [0,%d]", len, TGX_MAX_DRAFT);      // (ahead of the read of its ids)
+      if (int rc = verify_row_check(c, row, my, len, /*min_draft=*/0, /*sampled_entry=*/true, fn)) return rc;
+    } else {
+      if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+      if (len < 1) return set_err(c, TGX_ERR_INVALID, "seq %d < 1", len);
+      const RowHost& rh = c->row_host[(size_t)row];
+      holds[(size_t)i] = row < c->batch && !rh.idle && rh.past >= 1;
+      if (holds[(size_t)i] && rh.past + len > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, (long long)rh.past, len, d.max_ctx);
+      if (!holds[(size_t)i] && len > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "prompt %d: seq %d out of range (context size %d)", i, len, d.max_ctx);
+      for (int k = 0; k < len; k++)
+        if (my[k] < 0 || my[k] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
+      n_new += row >= c->batch;
+    }
+    named[(size_t)row] = 1;
+  }
+  for (int row = c->batch; row < c->batch + n_new; row++)
+    if (row >= d.max_batch || !named[(size_t)row])
+      return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
+  // the pass's sequences: the STEP rows first (array order), then the FEED / FEED_MORE rows (array order); src[j] = the array index of sequence j
+  std::vector<int> src;
+  for (int i = 0; i < n; i++) if (kinds[i] == TGX_ADV_STEP) src.push_back(i);
+  const int ns = (int)src.size();
+  for (int i = 0; i < n; i++) if (kinds[i] != TGX_ADV_STEP) src.push_back(i);
+  std::vector<int> first((size_t)n), sl((size_t)n), past((size_t)n), rws((size_t)n), nd((size_t)n, 0), adm;
+  for (int j = 0, m = 0; j < n; j++) {
+    const int i = src[(size_t)j], row = rows[i];
+    rws[(size_t)j] = row; first[(size_t)j] = m;
+    sl[(size_t)j] = lens[i] + (j < ns ? 1 : 0);
+    if (j < ns) nd[(size_t)j] = lens[i];
+    past[(size_t)j] = (j < ns || holds[(size_t)i]) ? (int)c->row_host[(size_t)row].past : 0;
+    if (j >= ns && !holds[(size_t)i]) adm.push_back(row);
+    m += sl[(size_t)j];
+  }
+  const PrefillRoute rt = prefill_route(c, (int)M, (int)M);
+  const bool joint = rt == ROUTE_SKINNY || rt == ROUTE_TILED;
+  if (c->kv_paged) {
+    bool mfma_row = joint;      // piecewise: does some piece's own pass take a matrix-core route?
+    for (int j = 0; j < n && !mfma_row; j++) { const PrefillRoute r1 = prefill_route(c, sl[(size_t)j], sl[(size_t)j]); mfma_row = r1 == ROUTE_SKINNY || r1 == ROUTE_TILED; }
+    if (mfma_row && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
+      return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+    // all or nothing: the blocks of all named rows together against the free list plus what the admissions' target rows give back
+    long long need = 0;
+    for (int j = 0; j < n; j++) {
+      const bool admission = j >= ns && !holds[(size_t)src[(size_t)j]];
+      need += c->kv.blocks_for((long long)past[(size_t)j] + sl[(size_t)j]) - (admission ? 0 : c->kv.row_blocks(rws[(size_t)j]));
+    }
+    const long long have = c->kv.available_for(adm.data(), (int)adm.size());
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld more blocks of %d tokens, %lld free or held by its admissions' rows of %d (option kv.budget_tokens = %d)", need,
+                     tgx::KV_BLOCK, have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  for (int i = 0; i < n; i++) { out_n[i] = 0; out_finish[i] = 0; }
+  if (!joint) {      // ---- piecewise: the equivalent calls behind the joint checks; the admissions' rows give their blocks back first, so that every piece's own count fits
+    if (c->kv_paged) for (int row : adm) kv_release_row(c, row);
+    if (ns) {
+      std::vector<int32_t> r32((size_t)ns), nd32((size_t)ns), on((size_t)ns), of((size_t)ns);
+      std::vector<int64_t> dr, oi((size_t)ns * (TGX_MAX_DRAFT + 1));
+      for (int j = 0; j < ns; j++) {
+        r32[(size_t)j] = rws[(size_t)j]; nd32[(size_t)j] = nd[(size_t)j];
+        for (int k = 0; k < nd[(size_t)j]; k++) dr.push_back(ids[off[(size_t)src[(size_t)j]] + k]);
+      }
+      dr.push_back(0);      // (never read: a non-null pointer for a call without drafts)
+      if (int rc = tgx_verify_rows(c, ns, r32.data(), dr.data(), nd32.data(), oi.data(), on.data(), of.data())) return rc;
+      for (int j = 0; j < ns; j++) {
+        const int i = src[(size_t)j];
+        for (int k = 0; k < on[(size_t)j]; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = oi[(size_t)j * (TGX_MAX_DRAFT + 1) + k];
+        out_n[i] = on[(size_t)j]; out_finish[i] = of[(size_t)j];
+      }
+    }
+    std::vector<int> feeds(src.begin() + ns, src.end());      // the continuations in array order, then the admissions in row order (the batch grows in order)
+    std::stable_sort(feeds.begin(), feeds.end(), [&](int x, int y) { return holds[(size_t)x] != holds[(size_t)y] ? holds[(size_t)x] > holds[(size_t)y] : (!holds[(size_t)x] && rows[x] < rows[y]); });
+    for (int i : feeds) {
+      const int32_t r1 = rows[i], s1 = lens[i];
+      if (int rc = holds[(size_t)i] ? extend_row(c, r1, ids + off[(size_t)i], s1, nullptr) : admit_rows(c, 1, &r1, ids + off[(size_t)i], &s1, /*may_join=*/false)) return rc;
+      if (kinds[i] == TGX_ADV_FEED_MORE) c->row_host[(size_t)r1].nologits = true;      // its logits slot is not the caller's to read: more of the prompt follows
+    }
+    refresh_longest(c);
+    c->advance_last_form = 2;
+    return TGX_OK;
+  }
+  // ---- the joint pass
+  std::vector<tgx_sampler_cfg> cfg((size_t)std::max(ns, 1));
+  std::vector<char> smp((size_t)std::max(ns, 1), 0);
+  bool any_sampled = false;
+  for (int j = 0; j < ns; j++) { cfg[(size_t)j] = row_cfg(c, rws[(size_t)j]); smp[(size_t)j] = !is_greedy(&cfg[(size_t)j]); any_sampled = any_sampled || smp[(size_t)j]; }
+  if (ns) if (int rc = ensure_verify_rows_ws(c)) return rc;
+  if (any_sampled) if (int rc = vs_alloc(c)) return rc;
+  // the STEP positions' lm_head: on the tiled route the GEMV form would stream the lm_head weights once per FOUR positions (32 step rows: eight passes, measured
+  // +0.8 ms on Llama-3.2-1B, profiles/advance_rows.txt); where the skinny route would take Ms rows by themselves, its one-pass form serves them from ws_x
+  PrefillRoute lm_rt = rt;
+  if (ns && rt == ROUTE_TILED && prefill_route(c, (int)Ms, (int)Ms) == ROUTE_SKINNY) {
+    if (int rc = ensure_skinny_ws(c, (int)Ms)) return rc;
+    lm_rt = ROUTE_SKINNY;
+  }
+  std::vector<int> head_rows;     // the FEED rows: their last position's logits
+  for (int j = ns; j < n; j++) if (kinds[src[(size_t)j]] == TGX_ADV_FEED) head_rows.push_back(rws[(size_t)j]);
+  if (!head_rows.empty()) if (int rc = ensure_rg_lm_ws(c)) return rc;
+  RaggedPass p;
+  p.n = n; p.M = (int)M; p.rows = rws.data(); p.lens = sl.data(); p.first = first.data(); p.past = past.data();
+  for (int j = 0; j < n; j++) p.longest = std::max(p.longest, sl[(size_t)j]);
+  const int target = advance_attn_target(c, p);
+  // the call's buffer: the pass's tables, then its ids (ONE upload; input 0 of every STEP sequence is written on the device from the row's token word)
+  const size_t o_ids = advance_tables(c, p, nullptr, nullptr, target), bytes = o_ids + (size_t)M * 8;
+  if (int rc = ensure_mix_ws(c, p)) return rc;
+  if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
+  std::vector<unsigned char> host(bytes, 0);      // (lives until finish_pass has synchronised)
+  advance_tables(c, p, host.data(), c->rg_buf, target);
+  long long* const h_ids = reinterpret_cast<long long*>(host.data() + o_ids);
+  for (int j = 0; j < n; j++)
+    for (int k = 0; k < lens[src[(size_t)j]]; k++) h_ids[first[(size_t)j] + (j < ns ? 1 : 0) + k] = ids[off[(size_t)src[(size_t)j]] + k];
+  long long* const d_ids = reinterpret_cast<long long*>(c->rg_buf + o_ids);
+  p.ids = d_ids;
+  c->vf_pass_rows = 0;                             // the workspace changes hands
+  if (c->kv_paged) for (int row : adm) kv_release_row(c, row);
+  for (int j = 0; j < n; j++) (void)kv_ensure_blocks(c, rws[(size_t)j], (long long)past[(size_t)j] + sl[(size_t)j]);      // cannot fail: counted above
+  for (int row : adm)      // retired rows that rode along since their reset: position word back to 0
+    if (c->row_host[(size_t)row].past != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream)); c->row_host[(size_t)row].past = 0; }
+  HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  if (ns) launch_verify_first_ids(c, d_ids, ns, rws.data(), first.data());
+  if (int rc = launch_route(c, rt, (int)M, 0, 0, 0, /*past=*/0, &p)) return rc;
+  std::vector<tgx::VerifyRecord> rec((size_t)std::max(ns, 1));
+  if (ns) {
+    launch_lm_head_all(c, lm_rt, (int)Ms, nullptr, /*joint=*/true);
+    for (int j = 0; j < ns; j++)
+      if (smp[(size_t)j]) launch_sample_positions(c, rws[(size_t)j], sl[(size_t)j], cfg[(size_t)j], first[(size_t)j]);
+    launch_verify_accept_rows(c, d_ids, ns, rws.data(), first.data(), nd.data(), smp.data());
+    for (int j = 0; j < ns; j++)
+      if (row_records(c, rws[(size_t)j])) launch_logprobs_verify(c, rws[(size_t)j], sl[(size_t)j], first[(size_t)j], j);
+    HIP_OK(c, hipMemcpyAsync(rec.data(), c->vj_rec, (size_t)ns * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  }
+  launch_lm_head_rows(c, head_rows);
+  for (int j = ns; j < n; j++) launch_add_pos(c, c->rows[(size_t)rws[(size_t)j]].pos, sl[(size_t)j]);
+  if (int rc = finish_pass(c)) return rc;
+  for (int j = 0; j < ns; j++)
+    if (rec[(size_t)j].n < 1 || rec[(size_t)j].n > sl[(size_t)j]) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record for row %d", fn, rws[(size_t)j]); }
+  c->vf_pass_rows = (int)Ms; c->vf_pass_joint = true;
+  c->advance_last_form = 1; c->advance_last_tiles = target;
+  // ---- the host follows the device: the STEP rows as tgx_verify_rows does, the FEED rows as an admission / tgx_extend_row does
+  for (int j = 0; j < ns; j++) {
+    const int row = rws[(size_t)j], i = src[(size_t)j];
+    const tgx::VerifyRecord& rc1 = rec[(size_t)j];
+    RowHost& r = c->row_host[(size_t)row];
+    r.past = past[(size_t)j] + rc1.n;
+    r.fin = (char)rc1.finish;
+    if (row_records(c, row)) r.lp_count += rc1.n;
+    kv_trim_row(c, row, r.past);
+    if (!smp[(size_t)j]) note_sampled(c, row, 1, cfg[(size_t)j]);
+    else r.probs_ok = false;
+    for (int k = 0; k < rc1.n; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = rc1.ids[k];
+    out_n[i] = rc1.n; out_finish[i] = rc1.finish;
+    if (row == 0) c->last_sampled0 = rc1.ids[rc1.n - 1];
+  }
+  for (int j = ns; j < n; j++) {
+    const int row = rws[(size_t)j], i = src[(size_t)j];
+    c->batch = std::max(c->batch, row + 1);
+    row_admitted(c, row, past[(size_t)j] + sl[(size_t)j], /*keep_lp_count=*/(bool)holds[(size_t)i]);
+    if (kinds[i] == TGX_ADV_FEED_MORE) c->row_host[(size_t)row].nologits = true;
+  }
+  c->have_probs = false;
+  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
 // test / diagnostic use: the fp32 logits [M][V] of the last verify pass, while the workspace still holds them
 int tgx_read_pass_logits(tgx_ctx* c, float* out, int cap_rows, int32_t* out_rows) {
   if (!c || !out || !out_rows) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
@@ -2361,7 +2573,10 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "snapshot.stage_kib")) { *out_value = c->snapshot_stage_kib; return TGX_OK; }
   if (!strcmp(key, "verify.last_splits")) { *out_value = c->verify_last_splits; return TGX_OK; }  // read-only: the key splits of the last tgx_verify_rows joint pass's attention (0: unsplit)
   if (!strcmp(key, "verify.last_form")) { *out_value = c->verify_last_form; return TGX_OK; }      // read-only: the form of the last tgx_verify_rows (0 none yet, 1 the joint pass, 2 row by row)
-  if (!strcmp(key, "score.last_form")) { *out_value = c->score_last_form; return TGX_OK; }      // read-only: the form of the last tgx_score_row that scored a position (0 none yet, 1 matrix cores, 2 by groups)
+  if (!strcmp(key, "advance.attn_tiles")) { *out_value = c->advance_attn_tiles; return TGX_OK; }
+  if (!strcmp(key, "advance.last_form")) { *out_value = c->advance_last_form; return TGX_OK; }    // read-only: the form of the last tgx_advance_rows (0 none yet, 1 the joint pass, 2 piecewise)
+  if (!strcmp(key, "advance.last_tiles")) { *out_value = c->advance_last_tiles; return TGX_OK; }  // read-only: the tile target of the last joint pass's attention (0: nothing split)
+  if (!strcmp(key, "score.last_form")) { *out_value = c->score_last_form; return TGX_OK; }     // read-only: the form of the last tgx_score_row that scored a position (0 none yet, 1 matrix cores, 2 by groups)
   if (!strcmp(key, "weights.packed")) { *out_value = c->weights_packed; return TGX_OK; }
   if (!strcmp(key, "weights.packed_classes")) { *out_value = c->packed_classes; return TGX_OK; }
   if (!strcmp(key, "weights.packed_matrices")) { *out_value = c->packed_matrices; return TGX_OK; }        // read-only, after tgx_finalize: matrices stored packed ...
@@ -2436,6 +2651,7 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "decode.mfma_min_batch")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "decode.mfma_min_batch must be >= 1"); c->decode_mfma_min = value; return TGX_OK; }
   if (!strcmp(key, "debug.profile_same_layer")) { c->prof_same_layer = value; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "extend.attn_splits is -1 (automatic), 0 (never) or a split count"); c->extend_attn_splits = value; return TGX_OK; }
+  if (!strcmp(key, "advance.attn_tiles")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "advance.attn_tiles is -1 (automatic), 0 (never split) or a tile count"); c->advance_attn_tiles = value; return TGX_OK; }
   if (!strcmp(key, "score.rows")) { if (value < 64 || value % 64) return set_err(c, TGX_ERR_INVALID, "score.rows is a positive multiple of 64"); c->score_rows = value; return TGX_OK; }
   if (!strcmp(key, "score.vocab_chunk")) { if (value < 1024 || value % 1024) return set_err(c, TGX_ERR_INVALID, "score.vocab_chunk is a positive multiple of 1024"); c->score_vocab_chunk = value; return TGX_OK; }
   if (!strcmp(key, "snapshot.stage_kib")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "snapshot.stage_kib is a size in KiB (one layer of a row is always staged)"); c->snapshot_stage_kib = value; return TGX_OK; }

@@ -112,7 +112,7 @@ struct ScoreCall {
   void* host = nullptr; size_t host_bytes = 0;        // where the call's read-back lands: lp [n] (| top ids | top lps)
 };
 
-namespace tgx { struct RgSeq; struct RgItem; }
+namespace tgx { struct RgSeq; struct RgItem; struct MixItem; }
 // one ragged prefill pass of tgx_forward_rows: prompt i at workspace rows [first[i], first[i] + lens[i]) into batch row rows[i], positions 0 .. lens[i] - 1.
 // abi.hip groups the prompts (the host fields, M, longest) and uploads the call's buffer; ragged_tables (prefill.hip) lays out and fills the device tables
 struct RaggedPass {
@@ -127,6 +127,10 @@ struct RaggedPass {
   // key-split form (kernels/attn_extend.h attn_extend_rg_kernel) with that many splits, its partials sized by ensure_extend_rg_ws; 0: the work-list form
   const int* past = nullptr;
   int ext_ns = 0;
+  // tgx_advance_rows (advance_tables): `items` holds the whole query blocks only; the blocks cut into key ranges are the two lists of the mixed attention
+  // (kernels/attn_mixed.h), their partials mix_slots records of ctx.mix_part.  n_mix_split == 0: the work-list form alone
+  const tgx::MixItem *mix_split = nullptr, *mix_merge = nullptr;
+  int n_mix_split = 0, n_mix_merge = 0, mix_slots = 0;
 };
 
 inline void* hip_dev_alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }      // the library's two uses of the
@@ -344,6 +348,17 @@ struct tgx_ctx {
   std::vector<unsigned char> vj_args_host;       // ... and the host copy the upload reads
   bool vf_pass_joint = false;                    // vf_pass_rows counts positions of vj_logits (a tgx_verify_rows joint pass), not of vf_logits
   int verify_last_form = 0, verify_last_splits = 0;      // ... and `verify.last_splits` (read-only): the key splits of the last joint pass's attention (0: unsplit)
+  // ---- tgx_advance_rows (include/tgx.h): prompt chunks and live rows' steps in one ragged pass.  Option advance.attn_tiles: the tile target of the mixed attention
+  // (kernels/attn_mixed.h; csrc/attn_worklist.h): 0 never split (the work-list form alone), N >= 1 query blocks of more than N key tiles are cut into ranges of <= N
+  // tiles (<= 32 ranges), -1 automatic: the largest target that gives the attention's launches two workgroups per CU (attn_worklist.h auto_target) — the rule
+  // profiles/verify_rows.txt measured for attn_extend_rg_kernel.  Default 16, by the sweep of profiles/advance_rows.txt (tools/admit_bench.py --mixed; Llama-3.2-1B
+  // bf16, head_dim 64, ms per call, 0 / 4 / 8 / 16 / -1; spread of a figure ~0.1): 32 step rows at context 2048 + a chunk of 256: 6.49 / 6.43 / 6.26 / 6.10 / 6.47
+  // (-1 chose 0: the whole blocks alone are four workgroups per CU); 8 step rows at 300 + a chunk of 512 at past 512: 4.48 / 4.58 / 4.66 / 4.48 / 4.66 (-1 chose 9).
+  // 16 wins or ties at both; the two-per-CU rule does not carry over to this kernel.  UNMEASURED: head_dim 128, contexts beyond 2048, targets above 16.
+  // Read-only: advance.last_form (0 no call yet, 1 the joint pass, 2 piecewise), advance.last_tiles (the target the last joint pass ran with).
+  // mix_part: the ranges' partials, grown by the first joint pass that splits
+  int advance_attn_tiles = 16, advance_last_form = 0, advance_last_tiles = 0;
+  float* mix_part = nullptr; size_t mix_part_bytes = 0;
   // ---- per-token log-probabilities (include/tgx.h tgx_set_row_logprobs; kernels/logprobs.h).  Allocated by the first call that switches a row on: the rows' record
   // rings and counters, and the tile launch's partials for max(max_batch, VERIFY_ROWS) rows (a verify pass puts its positions where a step puts its rows)
   tgx::LpRecord* lp_ring = nullptr;          // [max_batch][TGX_LOGPROB_RING]
@@ -483,6 +498,12 @@ void launch_prefill_ragged(tgx_ctx* c, const RaggedPass& rg);           // the s
 // the device tables of p (RgSeq [n], token -> prompt map [M], attention work list [n_items]; each 16-byte aligned) as one block: sets p.n_items and returns the block's
 // size; with `host` (16-byte aligned) it also fills the block there and points p.seq / tok_seq / items into its copy at `dev`
 size_t ragged_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const unsigned char* dev);
+// tgx_advance_rows: the same block with the attention lists of csrc/attn_worklist.h at tile target `target` (>= 0) behind it — the whole blocks as p.items, the
+// ranges and merge items as p.mix_split / p.mix_merge (at target 0 exactly ragged_tables' block); advance_attn_target: option advance.attn_tiles resolved for p
+// (raised while the partials would exceed 512 MiB); ensure_mix_ws: the partials' workspace for p.mix_slots records, before the pass is issued
+size_t advance_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const unsigned char* dev, int target);
+int advance_attn_target(const tgx_ctx* c, const RaggedPass& p);
+int ensure_mix_ws(tgx_ctx* c, const RaggedPass& p);
 void launch_embed_ragged(tgx_ctx* c, const RaggedPass& rg);
 void launch_rope_kv_split_ragged(tgx_ctx* c, const tgx::RopeKvArgs& a, const RaggedPass& rg, long long layer_off);
 void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const RaggedPass& rg, long long layer_off, bool allow_lean);

@@ -7,6 +7,8 @@
 #include "kernels/gemm_dma_qkv.h"
 #include "kernels/attn_prefill_dma.h"
 #include "kernels/attn_extend.h"
+#include "kernels/attn_mixed.h"
+#include "attn_worklist.h"
 #include "kernels/gemm_f32.h"
 #include "kernels/score.h"
 
@@ -349,6 +351,49 @@ static void launch_attn_extend_rg(tgx_ctx* c, const tgx::AttnRgArgs& r, const Ra
   if (c->kv_paged) go(std::true_type{}); else go(std::false_type{});
 }
 
+// ---- the mixed attention of tgx_advance_rows (kernels/attn_mixed.h; the lists: attn_worklist.h through advance_tables below).  Option advance.attn_tiles -> the
+// tile target of a pass; -1 is attn_worklist.h's auto_target at two workgroups per CU; the default is a fixed 16 (ctx.h advance_attn_tiles: the sweep, and what it left unmeasured).
+// A target whose partials would exceed MIX_PART_MAX is doubled until they fit (a pass of 8192 positions at target 1 would ask for gigabytes)
+static_assert(attn_worklist::QBLK == tgx::ATTN_QBLK && attn_worklist::KTILE == tgx::ATTN_KTILE, "attn_worklist.h restates the prompt attention's blocking");
+static_assert(sizeof(attn_worklist::Item) == sizeof(tgx::MixItem), "kernels/attn_mixed.h MixItem is attn_worklist.h Item");
+constexpr size_t MIX_PART_MAX = (size_t)512 << 20;
+static size_t mix_slot_bytes(const tgx_ctx* c) {
+  return (size_t)(c->d.head_dim == 64 ? tgx::attn_extend_part_vals<64>() : tgx::attn_extend_part_vals<128>()) * 256 * sizeof(float);
+}
+static std::vector<attn_worklist::Seq> mix_seqs(const RaggedPass& p) {
+  std::vector<attn_worklist::Seq> s((size_t)p.n);
+  for (int j = 0; j < p.n; j++) s[(size_t)j] = attn_worklist::Seq{p.lens[j], p.past ? p.past[j] : 0};
+  return s;
+}
+int advance_attn_target(const tgx_ctx* c, const RaggedPass& p) {
+  if (c->dt == tgx::DT_F32 || c->advance_attn_tiles == 0) return 0;
+  const std::vector<attn_worklist::Seq> s = mix_seqs(p);
+  int t = c->advance_attn_tiles > 0 ? c->advance_attn_tiles : attn_worklist::auto_target(s.data(), p.n, c->d.heads, 2 * c->num_cus);
+  while (t > 0 && (size_t)attn_worklist::count(s.data(), p.n, c->d.heads, t).slots * mix_slot_bytes(c) > MIX_PART_MAX) t *= 2;
+  return t;
+}
+int ensure_mix_ws(tgx_ctx* c, const RaggedPass& p) {
+  if (!p.mix_slots) return TGX_OK;
+  return dev_grow(c, &c->mix_part, &c->mix_part_bytes, (size_t)p.mix_slots * mix_slot_bytes(c));
+}
+static void launch_attn_mixed(tgx_ctx* c, const tgx::AttnRgArgs& r, const RaggedPass& rg) {
+  const int hd = c->d.head_dim;
+  if (!c->mix_part || (size_t)rg.mix_slots * mix_slot_bytes(c) > c->mix_part_bytes) { c->launch_fault = "attn_mixed: the partials' workspace was not sized for this pass"; return; }
+  tgx::AttnMixArgs e{};
+  e.r = r; e.part = c->mix_part; e.items = rg.mix_split;
+  tgx::AttnMixArgs m = e;
+  m.items = rg.mix_merge;
+  const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
+  const dim3 grid(rg.n_mix_split), mgrid(rg.n_mix_merge), blk(256);
+  auto go = [&](auto paged) {
+    constexpr bool P = decltype(paged)::value;
+    TGX_DT16_SWITCH(c->dt,
+      if (hd == 64) { hipLaunchKernelGGL((tgx::attn_mixed_split_kernel<DT, 64, P>), grid, blk, lds1, c->stream, e); hipLaunchKernelGGL((tgx::attn_mixed_merge_kernel<DT, 64>), mgrid, blk, 0, c->stream, m); }
+      else { hipLaunchKernelGGL((tgx::attn_mixed_split_kernel<DT, 128, P>), grid, blk, lds1, c->stream, e); hipLaunchKernelGGL((tgx::attn_mixed_merge_kernel<DT, 128>), mgrid, blk, 0, c->stream, m); })
+  };
+  if (c->kv_paged) go(std::true_type{}); else go(std::false_type{});
+}
+
 // causal GQA flash attention of S prompt positions of one batch row (grid = ceil(S / 128) query blocks x heads)
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_lean) {
   tgx::AttnPrefillArgs a = a_;
@@ -394,6 +439,8 @@ void launch_attn_prefill_ragged(tgx_ctx* c, const tgx::AttnPrefillArgs& a, const
   tgx::AttnRgArgs r{};
   r.a = a; r.seq = rg.seq; r.item = rg.items; r.layer_off = layer_off;
   if (rg.ext_ns > 0) { launch_attn_extend_rg(c, r, rg); return; }      // continuations (tgx_verify_rows): the key-split form
+  if (rg.n_mix_split > 0) launch_attn_mixed(c, r, rg);                  // tgx_advance_rows: the query blocks cut into key ranges, and their merge (two launches) ...
+  if (rg.n_items == 0) return;                                          // ... beside the whole blocks below (an empty list launches nothing)
   const int hd = c->d.head_dim;
   const int nqb = (rg.longest + tgx::ATTN_QBLK - 1) / tgx::ATTN_QBLK, nwg = nqb * a.heads, total = rg.n_items;
   const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
@@ -443,6 +490,36 @@ size_t ragged_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const
   p.seq = reinterpret_cast<const tgx::RgSeq*>(dev);
   p.tok_seq = reinterpret_cast<const int*>(dev + o_tok);
   p.items = reinterpret_cast<const tgx::RgItem*>(dev + o_item);
+  return bytes;
+}
+// ... of tgx_advance_rows: ragged_tables' block (the sequences, the token map, the whole query blocks as its work list) with the mixed attention's two lists behind
+// it.  The lists, their order and the partial slots are attn_worklist.h's (checked on a CPU: tests/attn_worklist_check.cpp); at target 0 both lists are empty
+size_t advance_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, const unsigned char* dev, int target) {
+  auto align = [](size_t o) { return (o + 15) & ~(size_t)15; };
+  const std::vector<attn_worklist::Seq> s = mix_seqs(p);
+  const attn_worklist::Counts n = attn_worklist::count(s.data(), p.n, c->d.heads, target);
+  p.n_items = n.unsplit; p.n_mix_split = n.split; p.n_mix_merge = n.merge; p.mix_slots = n.slots;
+  const size_t o_tok = align((size_t)p.n * sizeof(tgx::RgSeq)), o_item = align(o_tok + (size_t)p.M * 4), o_split = align(o_item + (size_t)n.unsplit * sizeof(tgx::RgItem)),
+               o_merge = align(o_split + (size_t)n.split * sizeof(tgx::MixItem)), bytes = align(o_merge + (size_t)n.merge * sizeof(tgx::MixItem));
+  if (!host) return bytes;
+  tgx::RgSeq* sq = reinterpret_cast<tgx::RgSeq*>(host);
+  int* tok = reinterpret_cast<int*>(host + o_tok);
+  for (int j = 0; j < p.n; j++) {
+    const RowState& r = c->rows[(size_t)p.rows[j]];
+    sq[j].row0 = p.first[j]; sq[j].S = p.lens[j];
+    sq[j].k = reinterpret_cast<bf16_t*>(r.kcache); sq[j].v = reinterpret_cast<bf16_t*>(r.vcache); sq[j].tbl = r.tbl; sq[j].past = p.past ? p.past[j] : 0; sq[j].pad = 0;
+    for (int k = 0; k < p.lens[j]; k++) tok[p.first[j] + k] = j;
+  }
+  const attn_worklist::Lists L = attn_worklist::build(s.data(), p.n, c->d.heads, target);
+  tgx::RgItem* it = reinterpret_cast<tgx::RgItem*>(host + o_item);
+  for (size_t k = 0; k < L.unsplit.size(); k++) it[k] = tgx::RgItem{L.unsplit[k].seq, L.unsplit[k].qblk, L.unsplit[k].h, 0};
+  if (!L.split.empty()) std::memcpy(host + o_split, L.split.data(), L.split.size() * sizeof(tgx::MixItem));
+  if (!L.merge.empty()) std::memcpy(host + o_merge, L.merge.data(), L.merge.size() * sizeof(tgx::MixItem));
+  p.seq = reinterpret_cast<const tgx::RgSeq*>(dev);
+  p.tok_seq = reinterpret_cast<const int*>(dev + o_tok);
+  p.items = reinterpret_cast<const tgx::RgItem*>(dev + o_item);
+  p.mix_split = reinterpret_cast<const tgx::MixItem*>(dev + o_split);
+  p.mix_merge = reinterpret_cast<const tgx::MixItem*>(dev + o_merge);
   return bytes;
 }
 // RoPE + cache append + q split of S prompt rows of one batch row

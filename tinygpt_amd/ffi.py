@@ -54,6 +54,8 @@ class PenaltyCfg(ctypes.Structure):
 
 
 MAX_LOGIT_BIAS = 320     # TGX_MAX_LOGIT_BIAS
+ADV_STEP, ADV_FEED, ADV_FEED_MORE = 0, 1, 2      # TGX_ADV_*: the kinds of tgx_advance_rows
+MAX_ADVANCE_POSITIONS = 8192                     # TGX_MAX_ADVANCE_POSITIONS
 
 
 class TgxError(RuntimeError):
@@ -90,6 +92,7 @@ ABI = {
     "verify_row_sampled": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "read_pass_logits": (c_int, [c_void_p, POINTER(c_float), c_int, POINTER(c_int32)]),
     "verify_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "advance_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "sample_row": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64, POINTER(c_int64)]),
     "past_length_row": (c_int64, [c_void_p, c_int]),
     "set_row_sampler": (c_int, [c_void_p, c_int, POINTER(SamplerCfg), c_uint64]),
@@ -376,6 +379,41 @@ class Model:
         self._check(self.be.verify_rows(self._ctx, n, rows.ctypes.data_as(POINTER(c_int32)), flat.ctypes.data_as(POINTER(c_int64)), n_draft.ctypes.data_as(POINTER(c_int32)),
                                         out.ctypes.data_as(POINTER(c_int64)), out_n.ctypes.data_as(POINTER(c_int32)), fin.ctypes.data_as(POINTER(c_int32))))
         return [(out[i, :out_n[i]].copy(), int(fin[i])) for i in range(n)]
+
+    def advance_rows(self, rows, kinds, ids_per_row):
+        """prompt chunks and live rows' steps in ONE ragged pass (include/tgx.h tgx_advance_rows).  kinds[i]: ADV_STEP — rows[i] is a live row with a current token,
+        ids_per_row[i] its draft (possibly empty: one plain step); ADV_FEED — ids_per_row[i] is appended to (or admitted into) rows[i] and the last position's logits
+        land in its slot; ADV_FEED_MORE — the same without logits, more of the prompt follows -> a list of (produced ids, finish), one per row in call order (FEED
+        rows: no ids, 0)"""
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        kinds = np.ascontiguousarray(np.asarray(kinds, dtype=np.int32).reshape(-1))
+        ps = [np.asarray(p, dtype=np.int64).reshape(-1) for p in ids_per_row]
+        assert len(ps) == len(rows) == len(kinds), (len(ps), len(rows), len(kinds))
+        lens = np.ascontiguousarray(np.array([len(p) for p in ps], dtype=np.int32))
+        flat = np.ascontiguousarray(np.concatenate(ps + [np.zeros(1, dtype=np.int64)]))      # (never empty: the pointer stays valid)
+        n = len(rows)
+        out = np.zeros((max(n, 1), 16), dtype=np.int64)      # [n][TGX_MAX_DRAFT + 1]
+        out_n, fin = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.be.advance_rows(self._ctx, n, rows.ctypes.data_as(POINTER(c_int32)), kinds.ctypes.data_as(POINTER(c_int32)), flat.ctypes.data_as(POINTER(c_int64)),
+                                         lens.ctypes.data_as(POINTER(c_int32)), out.ctypes.data_as(POINTER(c_int64)), out_n.ctypes.data_as(POINTER(c_int32)),
+                                         fin.ctypes.data_as(POINTER(c_int32))))
+        if n:
+            self.batch = max(self.batch, int(rows.max()) + 1)
+        return [(out[i, :out_n[i]].copy(), int(fin[i])) for i in range(n)]
+
+    @property
+    def advance_attn_tiles(self) -> int:
+        """option advance.attn_tiles: the tile target of tgx_advance_rows' attention (-1 automatic, 0 never split, N tiles per work item)"""
+        return self.get_option("advance.attn_tiles")
+
+    @advance_attn_tiles.setter
+    def advance_attn_tiles(self, value: int):
+        self.set_option("advance.attn_tiles", value)
+
+    @property
+    def advance_last_form(self) -> int:
+        """read-only option advance.last_form: 0 no advance_rows call yet, 1 the joint pass, 2 piecewise"""
+        return self.get_option("advance.last_form")
 
     def sample_row(self, row: int, cfg: SamplerCfg = GREEDY, seed: int = 0) -> int:
         out = c_int64()

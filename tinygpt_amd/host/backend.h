@@ -51,6 +51,8 @@ struct Backend {
   int (*read_pass_logits)(tgx_ctx*, float*, int, int32_t*) = nullptr;
   // ... of a batch of several sequences (optional: all rows' drafts in one joint pass; without it a batch keeps the plain loop)
   int (*verify_rows)(tgx_ctx*, int, const int32_t*, const int64_t*, const int32_t*, int64_t*, int32_t*, int32_t*) = nullptr;
+  // chunked prefill (optional; bound for a batch engine to come — nothing in this host engine calls it yet): prompt chunks and live rows' steps in one ragged pass
+  int (*advance_rows)(tgx_ctx*, int, const int32_t*, const int32_t*, const int64_t*, const int32_t*, int64_t*, int32_t*, int32_t*) = nullptr;
   // per-token log-probabilities (optional: GPTConfig::logprobs needs these three, sample_row and decode_rows — the engine then steps through the per-row calls)
   int (*set_row_sampler)(tgx_ctx*, int, const tgx_sampler_cfg*, uint64_t) = nullptr;
   int (*set_row_logprobs)(tgx_ctx*, int, int) = nullptr;
@@ -87,6 +89,7 @@ struct Backend {
     TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
     TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
     TGXH_BIND(verify_row_sampled, false); TGXH_BIND(read_pass_logits, false); TGXH_BIND(verify_rows, false);
+    TGXH_BIND(advance_rows, false);
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
     TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);
     TGXH_BIND(score_row, false);

@@ -24,6 +24,14 @@ slabs and paged, tgx_save_row into a pageable host buffer, tgx_reset_row + tgx_r
 snapshots does to bring the sequence back.  The three alternate inside every repetition; median [min .. max] of --reps, and the GB/s each copy direction reached.
 
     python tools/admit_bench.py --snapshot [--fork-prompts 256,2048]
+
+--mixed measures chunked prefill (include/tgx.h tgx_advance_rows): B live rows at a context of ~--mixed-ctx tokens take one step while one more row, which holds
+--mixed-past positions, is fed a chunk of S tokens — as ONE tgx_advance_rows call on this build, per value of --mixed-tiles (option advance.attn_tiles), against
+tgx_decode_rows(1) + tgx_extend_row(chunk) on --parent-lib (a library without the call; default: this build's).  The baseline's chunk row has to hold a token for
+tgx_decode_rows, so it steps too: B + 1 rows.  The forms alternate inside every repetition on two contexts of one process; the chunk's row is rebuilt outside the timed
+window; the step rows grow by one position per call.  Median [min .. max] of --reps.
+
+    python tools/admit_bench.py --mixed [--mixed-rows 8,32] [--mixed-chunks 128,256,512] [--mixed-tiles 0,4,8,16,-1] [--parent-lib PATH]
 """
 import argparse, dataclasses, os, sys, time
 import numpy as np
@@ -47,6 +55,13 @@ ap.add_argument("--extend-lens", default="16,64,128")
 ap.add_argument("--extend-splits", default="0,-1,4,8,16,32")
 ap.add_argument("--layers", type=int, default=0, help="--extend: cut the model to this many layers (0 = all)")
 ap.add_argument("--snapshot", action="store_true", help="tgx_save_row, reset + tgx_restore_row and reset + forward_row(P) for the P of --fork-prompts plus 8192")
+ap.add_argument("--mixed", action="store_true", help="B step rows + one prompt chunk: ONE tgx_advance_rows call against tgx_decode_rows(1) + tgx_extend_row(chunk)")
+ap.add_argument("--mixed-rows", default="8,32")
+ap.add_argument("--mixed-chunks", default="128,256,512")
+ap.add_argument("--mixed-ctx", type=int, default=300, help="--mixed: the step rows' context")
+ap.add_argument("--mixed-past", type=int, default=256, help="--mixed: the positions the chunk's row already holds")
+ap.add_argument("--mixed-tiles", default="-1", help="--mixed: the advance.attn_tiles values to time the joint call with (e.g. 0,4,8,16,-1)")
+ap.add_argument("--parent-lib", default="", help="--mixed: the library the two-call baseline runs on (default: this build's)")
 args = ap.parse_args()
 
 
@@ -94,6 +109,73 @@ def snapshot_bench():
 
 if args.snapshot:
     snapshot_bench()
+    sys.exit(0)
+
+
+def mixed_bench():
+    from tinygpt_amd.ffi import ABI, ADV_FEED, ADV_STEP, Backend
+    new_syms = ("advance_rows",)
+    rows_l, chunks = [int(x) for x in args.mixed_rows.split(",")], [int(x) for x in args.mixed_chunks.split(",")]
+    tiles_l = [int(x) for x in args.mixed_tiles.split(",")]
+    C0, P = args.mixed_ctx, args.mixed_past
+    old_be = Backend(args.parent_lib, "tgx_", required=[n for n in ABI if n not in new_syms]) if args.parent_lib else product_backend()
+    for paged in (0, 1):
+        for B in rows_l:
+            ctx = max(C0 + 8 * (4 + args.reps), P + max(chunks) + 8) + 64
+            desc = dataclasses.replace(known_desc(args.model, args.dtype), max_batch=B + 1, max_ctx=ctx)
+            ms = []
+            for be in (product_backend(), old_be):
+                m = Model(desc, be)
+                if paged:
+                    m.set_option("kv.budget_tokens", (B + 1) * ((ctx + 127) // 128) * 128)
+                m.load_synthetic(1234, 0.02).finalize()
+                for r in range(B):
+                    m.forward_row(r, synth.synth_prompt(desc.vocab, C0 - (r % 7), 900 + r))
+                    m.set_row_sampler(r, GREEDY, 0); m.sample_row(r, GREEDY)
+                ms.append(m)
+            new, old = ms
+            prefix = synth.synth_prompt(desc.vocab, P, 77)
+            for S in chunks:
+                chunk = [int(t) for t in synth.synth_prompt(desc.vocab, S, 78)]
+
+                def joint(tiles):
+                    new.reset_row(B); new.forward_row(B, prefix)
+                    new.set_option("advance.attn_tiles", tiles)
+                    new.synchronize()
+                    t0 = time.perf_counter()
+                    new.advance_rows(list(range(B + 1)), [ADV_STEP] * B + [ADV_FEED], [[]] * B + [chunk])
+                    new.synchronize()
+                    return (time.perf_counter() - t0) * 1e3
+
+                def apart():
+                    old.reset_row(B); old.forward_row(B, prefix); old.sample_row(B, GREEDY)
+                    old.synchronize()
+                    t0 = time.perf_counter()
+                    old.decode_rows(1)
+                    old.extend_row(B, chunk)
+                    old.synchronize()
+                    return (time.perf_counter() - t0) * 1e3
+
+                for _ in range(2):
+                    apart()
+                    for tl in tiles_l:
+                        joint(tl)
+                t = {tl: [] for tl in tiles_l}
+                base = []
+                for _ in range(args.reps):
+                    base.append(apart())
+                    for tl in tiles_l:
+                        t[tl].append(joint(tl))
+                cell = lambda v: f"{np.median(v):6.3f} [{min(v):6.3f} .. {max(v):6.3f}]"
+                cells = "  ".join(f"tiles {'auto' if tl < 0 else tl}: {cell(v)}" for tl, v in t.items())
+                print(f"{desc.name} {args.dtype} {'paged' if paged else 'slabs'} {B:2d} step rows at ~{C0} + a chunk of {S:3d} at past {P} ms  "
+                      f"decode_rows(1) + extend_row ({'parent' if args.parent_lib else 'this'} library) {cell(base)}  |  one tgx_advance_rows  {cells}"
+                      f"  (advance.last_tiles {new.get_option('advance.last_tiles')})", flush=True)
+            new.close(); old.close()
+
+
+if args.mixed:
+    mixed_bench()
     sys.exit(0)
 
 

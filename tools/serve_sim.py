@@ -13,6 +13,14 @@ tgx_decode_rows (per-row settings, include/tgx.h); with --device-stop as well, e
 is a full 16-step tgx_decode_rows call — the rows finish on the device, the host reads their counts back instead of limiting the call to the shortest output.  With --speculate N on top of the two, every tick is ONE
 tgx_verify_rows call instead (per 64 positions): each live row with a prompt-lookup draft of up to N tokens from its own history, or with none.
 
+With --chunk N (on --mix --device-stop) a waiting request is admitted in pieces of <= N prompt tokens, one piece per tick (chunked prefill, include/tgx.h
+tgx_advance_rows): ONE call carries the tick's pieces (FEED_MORE, the last one FEED; at most --chunk-tick prompt tokens per tick, default N, in admission order) and
+one step of every live row, so no live row waits for a whole prompt; ticks without a pending prompt stay full 16-step tgx_decode_rows calls.
+
+Every mode also prints the median and the longest wall time between two consecutive tokens of a live row: a call that starts at t0, ends at t1 and gives a row k
+tokens counts k gaps — the first from the row's previous token (the end of the call that produced it) to t0 + (t1 - t0) / k, the others (t1 - t0) / k each — so
+the time the batch stood still for an admission shows up in the first gap.  --lib runs the tool on another build of the library (a baseline).
+
 With --n-best K every request wants K samples of its prompt (T 0.8 / top-p 0.9, seeds s .. s + K - 1, all of the request's output length): the request is admitted into
 K idle rows as ONE tgx_forward_row plus ONE tgx_fork_row (include/tgx.h; on a paged cache the prompt's full blocks are held once) — or, with --n-best-separate, as K
 prompts in one tgx_forward_rows call — and the ticks run tgx_decode_rows.  The mode reports tokens per second and the peak of budget - kv.free_tokens.
@@ -44,6 +52,9 @@ ap.add_argument("--sampler", default="", help="e.g. 'temperature=0.8,top_p=0.9' 
 ap.add_argument("--mix", action="store_true", help="per-request sampler settings and seeds through tgx_decode_rows")
 ap.add_argument("--device-stop", action="store_true", help="(with --mix) output lengths as max_new on the device, full 16-step calls")
 ap.add_argument("--speculate", type=int, default=0, help="(with --mix --device-stop) prompt-lookup drafts of up to N tokens per row, one tgx_verify_rows call per tick in place of tgx_decode_rows")
+ap.add_argument("--chunk", type=int, default=0, help="(with --mix --device-stop) admit prompts in pieces of <= N tokens through tgx_advance_rows, one piece per tick beside one step of every live row")
+ap.add_argument("--chunk-tick", type=int, default=0, help="(with --chunk) prompt tokens per tick over all pending prompts (default: N)")
+ap.add_argument("--lib", default="", help="the library to run on (default: this build's)")
 ap.add_argument("--joint", action="store_true", help="admit every request that fits in a tick with ONE tgx_forward_rows call, then tgx_sample_row per row")
 ap.add_argument("--n-best", type=int, default=0, help="K samples per request: one prefill + tgx_fork_row into K - 1 rows (paged KV: --kv-budget)")
 ap.add_argument("--n-best-separate", action="store_true", help="(with --n-best) admit the K samples as K copies of the prompt in one tgx_forward_rows call instead")
@@ -57,7 +68,14 @@ plo, phi = (int(x) for x in args.prompt.split(","))
 nlo, nhi = (int(x) for x in args.new.split(","))
 assert phi + nhi <= args.max_ctx
 desc = dataclasses.replace(known_desc(args.model), max_batch=B, max_ctx=args.max_ctx)
-m = Model(desc, product_backend())
+if args.lib:      # another build: bind what it exports
+    import ctypes
+    from tinygpt_amd.ffi import ABI, Backend
+    probe = ctypes.CDLL(args.lib)
+    backend = Backend(args.lib, "tgx_", required=[n for n in ABI if hasattr(probe, "tgx_" + n)])
+else:
+    backend = product_backend()
+m = Model(desc, backend)
 if args.kv_budget:
     m.set_option("kv.budget_tokens", args.kv_budget)
 m.load_synthetic(1234, 0.02).finalize()
@@ -71,6 +89,9 @@ if args.mix:
     MIX = [GREEDY, SamplerCfg(0.8, 0, 0.9, 0.0), SamplerCfg(1.0, 50, 1.0, 0.0), SamplerCfg(0.7, 0, 1.0, 0.05)]
     req_cfg = [(MIX[int(rng.integers(0, len(MIX)))], int(rng.integers(1, 1 << 30))) for _ in reqs]
 STOP = args.mix and args.device_stop
+CHUNK = args.chunk if STOP else 0
+if args.chunk and not STOP:
+    raise SystemExit("--chunk needs --mix --device-stop")
 SLACK = 16 if STOP else 0        # device stop: blocks are assigned up front for the whole 16-step call
 
 
@@ -101,10 +122,18 @@ def serve(policy):
     produced = steps = live_steps = calls = 0
     peak_tokens = 0
     hist = [[] for _ in range(B)]      # --speculate: every row's tokens so far (prompt + produced), the drafter's input
+    feeding = {}                       # --chunk: row -> [request, prompt tokens fed so far], in admission order
+    last_tok, gaps = [0.0] * B, []     # the wall time of every live row's latest token; the gaps between consecutive tokens of a row (module docstring)
+
+    def note(r, k, t_start, t_end):
+        if k > 0:
+            per = (t_end - t_start) / k
+            gaps.append(t_start + per - last_tok[r]); gaps.extend([per] * (k - 1))
+            last_tok[r] = t_end
     drafted = [0, 0]                   # draft tokens offered / accepted
     m.synchronize(); t0 = time.perf_counter()
-    while waiting or any(length):
-        idle = [r for r in range(B) if not length[r]]
+    while waiting or any(length) or feeding:
+        idle = [r for r in range(B) if not length[r] and r not in feeding]
         if policy == "continuous" or len(idle) == B:          # static: a new batch only when the whole previous one is done
             reserved = sum(blocks(t) for t in target if t)
             admit = []
@@ -116,6 +145,11 @@ def serve(policy):
                 if reserved + blocks(L + new + SLACK) > budget:
                     break                                    # the head of the queue waits for room (FIFO)
                 waiting.pop(0)
+                if CHUNK:                                    # the prompt goes in piece by piece with the ticks below
+                    feeding[r] = [i, 0]
+                    target[r] = L + new + SLACK
+                    reserved += blocks(L + new + SLACK)
+                    continue
                 if args.joint:                               # every admission of the tick in ONE tgx_forward_rows call below
                     admit.append((r, i))
                 elif args.mix:
@@ -126,6 +160,7 @@ def serve(policy):
                         m.set_row_stop(r, max_new=new)
                 else:
                     m.forward_row(r, prompts[i]); m.sample_row(r, CFG, seed=3)
+                last_tok[r] = time.perf_counter()
                 length[r], target[r] = L, L + new + SLACK
                 reserved += blocks(L + new + SLACK)
                 produced += 1                                 # the first token came from the prefill's logits
@@ -140,9 +175,41 @@ def serve(policy):
                             m.set_row_stop(r, max_new=reqs[i][1])
                     else:
                         m.sample_row(r, CFG, seed=3)
+                    last_tok[r] = time.perf_counter()
         live = [r for r in range(B) if length[r]]
-        if not live:
+        if not live and not feeding:
             raise SystemExit("the budget admits no request")
+        if feeding:                                            # one tgx_advance_rows: the tick's pieces and one step of every live row
+            from tinygpt_amd.ffi import ADV_FEED, ADV_FEED_MORE, ADV_STEP
+            assert len(live) <= 64, "one call steps at most 64 rows"
+            rows_, kinds, ids_, room = list(live), [ADV_STEP] * len(live), [[] for _ in live], args.chunk_tick or CHUNK
+            done = []
+            for r, (i, off) in feeding.items():
+                n_piece = min(CHUNK, len(prompts[i]) - off, room)
+                if n_piece < 1:
+                    break
+                last = off + n_piece == len(prompts[i])
+                rows_.append(r); kinds.append(ADV_FEED if last else ADV_FEED_MORE); ids_.append(prompts[i][off:off + n_piece])
+                feeding[r][1] += n_piece; room -= n_piece
+                if last:
+                    done.append(r)
+            ts = time.perf_counter()
+            res = m.advance_rows(rows_, kinds, ids_)
+            te = time.perf_counter()
+            calls += 1; steps += 1
+            for r, (ids, fin) in zip(live, res):
+                length[r] += len(ids); produced += len(ids); live_steps += len(ids)
+                note(r, len(ids), ts, te)
+                if fin:
+                    m.reset_row(r); length[r] = target[r] = 0
+            for r in done:                                     # the prompt is in: the row's first token, its settings, its stop condition
+                i = feeding.pop(r)[0]
+                cfg, seed = req_cfg[i]
+                m.sample_row(r, cfg, seed=seed); m.set_row_sampler(r, cfg, seed); m.set_row_stop(r, max_new=reqs[i][1])
+                length[r] = reqs[i][0]; produced += 1
+                last_tok[r] = time.perf_counter()
+            peak_tokens = max(peak_tokens, sum(length))
+            continue
         if STOP and args.speculate > 0:                        # one tgx_verify_rows per tick (per 64 positions): every live row with its prompt-lookup draft, or none
             group, pos = [], 0
             todo = []
@@ -153,9 +220,12 @@ def serve(policy):
                 group.append((r, d)); pos += len(d) + 1
             todo.append(group)
             for group in todo:
+                ts = time.perf_counter()
                 res = m.verify_rows([r for r, _ in group], [d for _, d in group])
+                te = time.perf_counter()
                 calls += 1; steps += 1
                 for (r, d), (ids, fin) in zip(group, res):
+                    note(r, len(ids), ts, te)
                     hist[r].extend(int(t) for t in ids)
                     length[r] += len(ids); produced += len(ids); live_steps += len(ids)
                     peak_tokens = max(peak_tokens, sum(length))
@@ -165,9 +235,12 @@ def serve(policy):
             continue
         if STOP:                                               # full calls; the rows finish on the device
             n = 16
+            ts = time.perf_counter()
             _, cnt, fin = m.decode_rows(n)
+            te = time.perf_counter()
             calls += 1; steps += n
             for r in live:
+                note(r, int(cnt[r]), ts, te)
                 length[r] += int(cnt[r]); produced += int(cnt[r]); live_steps += int(cnt[r])
             peak_tokens = max(peak_tokens, sum(length))
             for r in live:
@@ -176,12 +249,15 @@ def serve(policy):
             continue
         remaining = [target[r] - length[r] for r in live]
         n = min(16, min(remaining))
+        ts = time.perf_counter()
         if args.mix:
             m.decode_rows(n)
         else:
-            m.decode(n, CFG, seed=3, fetch=False)
+            m.decode(n, CFG, seed=3, fetch=False)             # (not synchronised: this mode's gaps are those of the host's enqueue times)
+        te = time.perf_counter()
         calls += 1; steps += n
         for r in live:
+            note(r, n, ts, te)
             length[r] += n; produced += n; live_steps += n
         peak_tokens = max(peak_tokens, sum(length))
         for r in live:                                         # a finished row is retired at once under both policies (static: its slot stays empty until the batch is done)
@@ -191,6 +267,8 @@ def serve(policy):
     print(f"{policy:10s} {len(reqs)} requests, {produced} tokens generated in {dt:.2f} s = {produced / dt:8.0f} tokens/s; {steps} steps in {calls} decode calls, "
           f"{live_steps / max(steps, 1):.1f} live rows per step of {B}; most tokens held at once {peak_tokens} (cache: {budget} tokens"
           f"{', paged' if args.kv_budget else ' as slabs'})", flush=True)
+    if gaps:
+        print(f"           between two consecutive tokens of a live row: median {np.median(gaps) * 1e3:.2f} ms, longest {max(gaps) * 1e3:.2f} ms ({len(gaps)} gaps)", flush=True)
     if STOP and args.speculate > 0:
         print(f"           --speculate {args.speculate}: {drafted[1]} of {drafted[0]} draft tokens accepted, one tgx_verify_rows call per tick and 64 positions", flush=True)
 
@@ -257,7 +335,7 @@ def serve_nbest(K, fork):
 
 
 print(f"{desc.name}: {B} rows, max_ctx {args.max_ctx}, prompts {plo}..{phi}, outputs {nlo}..{nhi} tokens, "
-      f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}{', mixed settings' if args.mix else ''}{', device stop' if STOP else ''}{', joint admission' if args.joint else ''}", flush=True)
+      f"{'kv.budget_tokens ' + str(args.kv_budget) if args.kv_budget else 'unpaged'}{', mixed settings' if args.mix else ''}{', device stop' if STOP else ''}{', joint admission' if args.joint else ''}{', chunked prefill of ' + str(CHUNK) if CHUNK else ''}", flush=True)
 if args.n_best:
     if args.mix or args.joint or args.device_stop or args.sampler or args.policy != "both":
         raise SystemExit("--n-best is a mode of its own (continuous policy, T 0.8 / top-p 0.9 per sample): it takes no --mix / --joint / --device-stop / --sampler / --policy")
