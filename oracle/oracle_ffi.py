@@ -26,6 +26,9 @@ ORACLE_EXTRA = {
     "set_act16": (c_int, [c_void_p, c_int]),
     "set_one_row_dots": (c_int, [c_int]),
     "set_torch_rounding": (c_int, [c_void_p, c_int]),
+    "write_kv": (c_int, [c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float), c_int64]),
+    "set_past": (c_int, [c_void_p, c_int64]),
+    "set_ablate_key": (c_int, [c_void_p, c_int]),
 }
 
 
@@ -70,6 +73,16 @@ class OracleModel(Model):
     def set_torch_rounding(self, on: bool = True):
         """every op output rounded to bf16 (a torch-bf16 module's contract); before finalize()"""
         self._check(self.be.set_torch_rounding(self._ctx, 1 if on else 0))
+        return self
+
+    def set_past(self, n: int):
+        """the context holds n positions (its cache rows written with write_kv): no prefill runs"""
+        self._check(self.be.set_past(self._ctx, int(n)))
+        return self
+
+    def set_ablate_key(self, pos: int = -1):
+        """attention loses key `pos` (score -inf) for every query, head and layer whose key range holds it; -1 = off"""
+        self._check(self.be.set_ablate_key(self._ctx, int(pos)))
         return self
 
     def rope_tables(self, n_pos: int):

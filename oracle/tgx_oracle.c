@@ -38,6 +38,10 @@
  * with different fp32 summation order agree either bit-for-bit or only to the bf16 noise floor (a 1-ulp flip
  * re-amplifies at every later rounding; measured 3-6e-3 on logits), so north_star's "1e-3 relative" is only
  * a meaningful bar for an fp32 activation path.  TGXO_TORCH_ROUNDING=1 restores per-op rounding for study.
+ *
+ * Test hooks beyond the ABI (oracle_ffi.ORACLE_EXTRA): set_reorder, set_act16, set_torch_rounding, set_one_row_dots, set_logits, set_next_token, and for
+ * the key-range tests tgxo_write_kv (cache rows from the host, rounded once to the storage dtype), tgxo_set_past (a written cache holds n positions, no
+ * prefill) and tgxo_set_ablate_key (attend() loses one key position: the yardstick of tests/test_oracle_plant.py's sensitivity sweep).
  */
 #define _GNU_SOURCE
 #include <math.h>
@@ -86,6 +90,7 @@ typedef struct tgxo_ctx {
   int round_act;
   int act16;                     /* tgxo_set_act16: the input of every Linear is rounded to the storage dtype first (the reference's bf16 modules see bf16 tensors, ModelLlama.h:62) */
   int reorder;                   /* tgxo_set_reorder: every reduction runs in the REVERSE element order (a second, equally valid fp32 schedule) */
+  int ablate_key;                /* tgxo_set_ablate_key: attend() gives this key position the score -inf (-1 = off) */
   mat_t embed, wpe, lm_head;
   vec_t final_norm;
   layer_t* L;
@@ -216,6 +221,7 @@ TGXO_EXPORT int tgxo_create(const desc_t* d, int device_ordinal, tgxo_ctx** out)
   if (c->d.max_batch < 1) c->d.max_batch = 1;
   c->bf16 = d->compute_dtype == DT_BF16;
   c->f16 = d->compute_dtype == DT_F16;
+  c->ablate_key = -1;
   { const char* e = getenv("TGXO_TORCH_ROUNDING"); c->round_act = c->bf16 && e && e[0] == '1'; }
   int H = d->hidden, I = d->inter, V = d->vocab;
   int qd = d->heads * d->head_dim, kvd = d->kv_heads * d->head_dim;
@@ -546,6 +552,7 @@ static void attend(const tgxo_ctx* c, const float* q, const float* K, const floa
     if (ro) for (int t = hd - 1; t >= 0; t--) a += q[t] * k[t];
     else for (int t = 0; t < hd; t++) a += q[t] * k[t];
     sc[j] = a * scale;
+    if (j == c->ablate_key) sc[j] = -INFINITY;   /* tgxo_set_ablate_key: the key is lost (weight exactly 0); a query whose ONLY key it is yields NaN */
     if (sc[j] > mx) mx = sc[j];
   }
   float sum = 0.f;
@@ -841,6 +848,28 @@ TGXO_EXPORT int tgxo_read_kv(tgxo_ctx* c, int row, int layer, float* k_out, floa
   if (v_out) memcpy(v_out, c->vcache + off, (size_t)c->past * kvd * 4);
   return 0;
 }
+
+/* Test hooks of the key-range tests (tests/kv_plant.py, tests/test_oracle_plant.py, tests/test_hip_attn_keyrange.py).
+ * tgxo_write_kv: the inverse of tgxo_read_kv — cache rows [0, n_rows) of (row, layer) from fp32 [n_rows][kv_heads][head_dim], rounded ONCE to the storage
+ * dtype (what the cache append does); n_rows may reach max_ctx whatever pastLength is.  tgxo_set_past: the context then holds n positions without a prefill.
+ * tgxo_set_ablate_key: attend() scores key `pos` -inf for every query, head and layer whose key range holds it (pos < nkeys); -1 = off.  The distance the
+ * logits move is the yardstick the planted caches are chosen by: how far the reference itself moves when exactly that key is lost. */
+TGXO_EXPORT int tgxo_write_kv(tgxo_ctx* c, int row, int layer, const float* k_in, const float* v_in, int64_t n_rows) {
+  if (!c || row < 0 || row >= c->d.max_batch || layer < 0 || layer >= c->d.layers || n_rows < 0 || n_rows > c->d.max_ctx) return c ? fail(c, 1, "%s", "write_kv: row / layer / n_rows out of range") : 1;
+  size_t kvd = (size_t)c->d.kv_heads * c->d.head_dim;
+  size_t off = (((size_t)row * c->d.layers + layer) * c->d.max_ctx) * kvd, n = (size_t)n_rows * kvd;
+  if (k_in) for (size_t i = 0; i < n; i++) c->kcache[off + i] = RKV(c, k_in[i]);
+  if (v_in) for (size_t i = 0; i < n; i++) c->vcache[off + i] = RKV(c, v_in[i]);
+  return 0;
+}
+TGXO_EXPORT int tgxo_set_past(tgxo_ctx* c, int64_t n) {
+  if (!c) return 1;
+  if (!c->finalized) return fail(c, 4, "%s", "set_past before finalize");
+  if (n < 0 || n > c->d.max_ctx) return fail(c, 1, "%s", "set_past: n out of range");
+  c->past = n;
+  return 0;
+}
+TGXO_EXPORT int tgxo_set_ablate_key(tgxo_ctx* c, int pos) { if (!c) return 1; c->ablate_key = pos < 0 ? -1 : pos; return 0; }
 
 /* RoPE table read-back for the golden-table test: out[2][n_pos][head_dim/2] */
 TGXO_EXPORT int tgxo_read_rope(tgxo_ctx* c, int n_pos, float* out) {
