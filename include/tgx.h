@@ -634,6 +634,56 @@ TGX_API int tgx_set_row_penalties(tgx_ctx* ctx, int row, const tgx_penalty_cfg* 
 TGX_API int tgx_set_row_logit_bias(tgx_ctx* ctx, int row, int n, const int32_t* ids, const float* bias);  /* n = 0 clears */
 TGX_API int tgx_set_row_history(tgx_ctx* ctx, int row, const int64_t* prompt_ids, int n_prompt, const int64_t* produced_ids, int n_produced);
 
+/* ---- constrained decoding: per-row token automata stepped on the device (additive to ABI 3) ------------------------------------------------------------------
+ * "Answer yes / no / maybe", "a date", "this JSON template": an allowed set that covers the whole vocabulary and changes with every token, which a bias list
+ * cannot state.  The constraint is a token-level automaton resident on the device: a row carries an automaton id and a state word, the logit-processor launch
+ * masks the row's logits with the allowed set of its state, and the state moves on the device as the row consumes tokens — no host round trip per token, in
+ * the same multi-step graphs as every other row setting.  The host compiles a pattern into a table once per request (host/constraint.h).
+ *
+ *   Table             next[n_states][vocab], 16-bit words: next[s][t] = the state after token t in state s, or TGX_AUTOMATON_NONE (t is not allowed in s).  The
+ *                     library knows nothing about EOS: a caller that wants a row to be able to end in state s gives its stop ids a valid target there.  Stored on
+ *                     the device as it is, n_states * vocab * 2 bytes, by the one owner of device memory ("mem.live_allocs" / "mem.live_kib" count it);
+ *                     tgx_automaton_destroy frees it.  The caller's array is the caller's again on return.  At most TGX_MAX_AUTOMATA live tables per context.
+ *   Validation        on the host (csrc/automaton.h), before anything is allocated or copied.  TGX_ERR_INVALID: n_states outside [1, TGX_MAX_AUTOMATON_STATES],
+ *                     start outside [0, n_states), an entry that is neither a state of the table nor NONE, a state with no allowed token (a dead end is the
+ *                     compiler's bug, not the kernel's problem), a null pointer, a 17th live table.  Before tgx_finalize: TGX_ERR_STATE.
+ *   State word        follows the history words' convention: the state after every token the row has CONSUMED while the automaton was on.  A tgx_decode_rows
+ *                     step of an unfinished live row first advances the state by the row's current token (state = next[state][token]) and then masks with the
+ *                     new state's allowed set.  tgx_sample_row masks with the state as it stands and advances nothing: the row has no current token then.  A
+ *                     consumed token that the state does not allow leaves the state where it is — only a caller that switched the automaton on mid-stream, or
+ *                     set a state that does not belong to the row's text, can feed one.  Finished and retired rows neither advance nor mask.
+ *                     tgx_read_row_automaton returns the word as it stands (id -1 and state -1 for a row without one); a caller that wants the state including
+ *                     the current token looks up its own table.
+ *   Formula           step 4 of the processors' formula above, after the bias: an entry i with next[state][i] == NONE becomes -INFINITY.  Penalties and bias
+ *                     compose with it unchanged.  The raw logits, tgx_read_logits and the logprobs ring stay the model's; tgx_read_probs returns the vector the
+ *                     draw used (a disallowed id has probability exactly 0).
+ *   Lifecycle         settings are stream-ordered and kept across calls.  tgx_set_row_automaton(row, id, state): id -1 switches the row off, state -1 is the table's
+ *                     start.  tgx_reset_row / tgx_reset_cache switch the row off; the table lives on.  A setting made on a retired row takes effect with its
+ *                     admission, like the other processors.  tgx_extend_row and tgx_truncate_row keep id and state.  tgx_fork_row copies the source's id and
+ *                     state into each destination, as it copies the history words.  Snapshots do not hold the setting: settings are the caller's, and
+ *                     tgx_read_row_automaton lets the caller keep it.  tgx_automaton_destroy of a table that any row, live or retired, still names is
+ *                     TGX_ERR_STATE (it waits for the stream before it frees).
+ *   Refusals          tgx_set_row_automaton, TGX_ERR_INVALID and nothing changes: a row outside [0, max_batch), an unknown id, a state outside [-1, n_states).
+ *                     Before tgx_finalize: TGX_ERR_STATE.
+ *   A processor       the automaton is a logit processor: every rule about "a processor on" applies unchanged.  tgx_verify_row, tgx_verify_row_sampled,
+ *                     tgx_verify_rows and a STEP row of tgx_advance_rows refuse such a row with TGX_ERR_UNSUPPORTED; tgx_decode, tgx_sample and tgx_step_async
+ *                     ignore it, as they ignore every row setting.
+ *   Cost              a context that never creates an automaton allocates nothing new and runs exactly the launches it ran before; so does a context that has
+ *                     tables but no row using one.  The first row that names one allocates the processors' buffers (above).  While some row of the batch has one
+ *                     on: the processor launch (2 * vocab more bytes read per constrained row) and, ahead of it, one one-workgroup launch that moves the state
+ *                     words (one more bit of the union that keys the per-row step graphs).  Id and state are read on the device: changing them recaptures
+ *                     nothing.  Measured (profiles/automaton.txt; Llama-3.2-1B bf16, ms per tgx_decode_rows step, no processor / a bias list on every row / an
+ *                     automaton on every row): 1 row 0.6032 / 0.6086 / 0.6101, 8 rows 0.8082 / 0.8131 / 0.8149, 32 rows 1.1157 / 1.1358 / 1.1399 (spread of a
+ *                     figure 0.5 us); the unconstrained step issues the parent build's launches, kernel for kernel.  tgx_automaton_create of a 64-state table at
+ *                     V = 128256 (15.7 MiB): 25.5 ms.  Pattern compile time over a 128k vocabulary: unmeasured (no such tokenizer at hand). */
+#define TGX_AUTOMATON_NONE 0xFFFFu        /* next[s][t]: token t is not allowed in state s */
+#define TGX_MAX_AUTOMATON_STATES 65535    /* state ids 0 .. 65534 */
+#define TGX_MAX_AUTOMATA 16               /* live tables per context */
+TGX_API int tgx_automaton_create(tgx_ctx* ctx, int32_t n_states, int32_t start, const uint16_t* next /* [n_states][vocab] */, int32_t* out_id);
+TGX_API int tgx_automaton_destroy(tgx_ctx* ctx, int32_t id);
+TGX_API int tgx_set_row_automaton(tgx_ctx* ctx, int row, int32_t id /* -1: off */, int32_t state /* -1: the table's start */);
+TGX_API int tgx_read_row_automaton(tgx_ctx* ctx, int row, int32_t* out_id, int32_t* out_state);   /* synchronises, like the other readers */
+
 /* == GPTModel::contextSize() / numLayers() (src/model/GPTModel.h:97-98). */
 TGX_API int64_t tgx_context_size(const tgx_ctx* ctx);
 TGX_API int32_t tgx_num_layers(const tgx_ctx* ctx);

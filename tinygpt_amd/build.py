@@ -28,7 +28,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "attn_worklist.h")]
+            os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -129,13 +129,20 @@ def build_spec_rows_check(force: bool = False, verbose: bool = False):
     return _build_cpu_check("spec_rows_check", os.path.join(HOST, "spec_mode.h"), force, verbose)
 
 
+def build_constraint_check(force: bool = False, verbose: bool = False):
+    """tests/constraint_check.cpp, the CPU audit of csrc/automaton.h and host/constraint.cpp."""
+    if _stale(os.path.join(TEST_BUILD, "constraint_check"), [os.path.join(CSRC, "automaton.h"), os.path.join(HOST, "constraint.h")]):
+        force = True
+    return _build_cpu_check("constraint_check", os.path.join(HOST, "constraint.cpp"), force, verbose)
+
+
 def build_host(force: bool = False, verbose: bool = False, test_hooks: bool = False):
     """The C++ host engine (no HIP needed: it dlopen()s the device shim): libtgx_host.so + the tgx_cli binary.
 
     test_hooks=True builds the TEST variants instead (tests/_build/libtgx_host_test.so, tgx_cli_test, -DTGXH_TEST_HOOKS): the only
     builds that can bind a library other than libtgx_mi355x.so (the CPU oracle, for host-logic tests without a GPU)."""
-    srcs = [os.path.join(HOST, f) for f in ("loader.cpp", "engine.cpp", "regex.cpp", "tokenizer.cpp")]
-    deps = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "row_snapshot.h")]
+    srcs = [os.path.join(HOST, f) for f in ("loader.cpp", "engine.cpp", "regex.cpp", "tokenizer.cpp", "constraint.cpp")]
+    deps = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "row_snapshot.h"), os.path.join(CSRC, "automaton.h")]
     lib, cli, flags = HOST_LIB, HOST_CLI, []
     if test_hooks:
         lib, cli, flags = HOST_TEST_LIB, HOST_TEST_CLI, ["-DTGXH_TEST_HOOKS"]

@@ -9,6 +9,7 @@
 #include "kernels/kv_fork.h"
 #include "kernels/kv_pack.h"
 #include "row_snapshot.h"
+#include "automaton.h"
 
 static std::string g_create_err;
 
@@ -368,7 +369,7 @@ static void launch_kv_copy(tgx_ctx* c, long long n_tok, F&& rest) {
 // behind the steps that still read the old ones (no stream drain, no host buffer that has to outlive the call).  what: ROWQ_* bits
 // (ROWQ_LP: the row's log-probability setting; ROWQ_LPCOUNT: its record count back to 0.  `lp`: the rows' logprob state once it exists (kernels/logprobs.h) — its
 // `seen` word follows `produced` wherever this launch moves that)
-enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4, ROWQ_LP = 8, ROWQ_LPCOUNT = 16, ROWQ_PROC = 32 };      // (ROWQ_PROC: the logit processors' settings)
+enum { ROWQ_SAMPLER = 1, ROWQ_STOP = 2, ROWQ_STATE = 4, ROWQ_LP = 8, ROWQ_LPCOUNT = 16, ROWQ_PROC = 32, ROWQ_AUTO = 64 };      // (ROWQ_PROC: the logit processors' settings; ROWQ_AUTO: the row's automaton table and state word)
 struct RowReqUpdate { int row, what; tgx::RowReq v; };
 static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u, tgx::LpRow* lp) {
   if (threadIdx.x != 0) return;
@@ -382,6 +383,7 @@ static __global__ void row_req_set_kernel(tgx::RowReq* req, RowReqUpdate u, tgx:
   if (u.what & ROWQ_STATE) { q.produced = 0; q.finished = 0; }
   if (u.what & ROWQ_LP) q.lp = u.v.lp;
   if (u.what & ROWQ_PROC) { q.proc = u.v.proc; q.n_bias = u.v.n_bias; q.repetition = u.v.repetition; q.presence = u.v.presence; q.frequency = u.v.frequency; }
+  if (u.what & ROWQ_AUTO) { q.auto_next = u.v.auto_next; q.auto_state = u.v.auto_state; }
   if (lp) {
     lp[u.row].seen = q.produced;
     if (u.what & ROWQ_LPCOUNT) { lp[u.row].count = 0; lp[u.row].arrive = 0; }
@@ -393,7 +395,12 @@ static tgx::RowReq row_req_default() {   // greedy, seed 0, no stop conditions
   tgx::RowReq q{};
   q.temperature = 0.f; q.top_k = 0; q.top_p = 1.f; q.min_p = 0.f; q.seed = 0; q.max_new = 0; q.n_stop = 0;
   q.proc = 0; q.n_bias = 0; q.repetition = 1.f; q.presence = 0.f; q.frequency = 0.f;      // logit processors off
+  q.auto_next = nullptr; q.auto_state = 0;                                                   // ... no automaton
   return q;
+}
+static void row_proc_refresh(tgx::RowReq& q) {      // proc: which processors are on (0: none — the row is copied through)
+  const bool pen = q.repetition != 1.f || q.presence != 0.f || q.frequency != 0.f;
+  q.proc = (pen ? tgx::PROC_PENALTY : 0) | (q.n_bias > 0 ? tgx::PROC_BIAS : 0) | (q.auto_next ? tgx::PROC_AUTOMATON : 0);
 }
 // does the row record log-probabilities in the steps: its setting, unless it is retired (the setting is kept on the host and travels with the admission)
 bool row_records(const tgx_ctx* c, int row) { return c->row_req_host[(size_t)row].lp > 0 && !c->row_host[(size_t)row].idle; }
@@ -406,8 +413,9 @@ static void row_req_push(tgx_ctx* c, int row, int what) {
 }
 static void row_req_reset(tgx_ctx* c, int row) {   // tgx_reset_row: the default settings and a fresh state
   c->row_req_host[(size_t)row] = row_req_default();
-  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE | ROWQ_LP | ROWQ_LPCOUNT | ROWQ_PROC);
+  row_req_push(c, row, ROWQ_SAMPLER | ROWQ_STOP | ROWQ_STATE | ROWQ_LP | ROWQ_LPCOUNT | ROWQ_PROC | ROWQ_AUTO);
   c->row_host[(size_t)row].lp_count = 0;
+  c->row_host[(size_t)row].auto_id = -1;      // (the table lives on: tgx_automaton_destroy)
 }
 static tgx_sampler_cfg row_cfg(const tgx_ctx* c, int row) {
   const tgx::RowReq& q = c->row_req_host[(size_t)row];
@@ -1097,7 +1105,7 @@ int tgx_reset_cache(tgx_ctx* c) {
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->vf_pass_rows = 0;
   c->past = 0;
-  for (RowHost& r : c->row_host) { r.restart(0, /*idle=*/false, /*fin=*/0); r.lp_count = 0; }
+  for (RowHost& r : c->row_host) { r.restart(0, /*idle=*/false, /*fin=*/0); r.lp_count = 0; r.auto_id = -1; }
   c->have_logits = c->have_token = false;
   c->poisoned = false;
   return TGX_OK;
@@ -1420,6 +1428,16 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
   if (int rc = finish_pass(c)) return rc;
   for (int i = 0; i < n; i++) {
     c->batch = std::max(c->batch, dst_rows[i] + 1);
+    {      // the same sequence, the same automaton and state: like the history words (the mirror of the source's state word is exact: it moves in tgx_decode_rows alone)
+      const tgx::RowReq& qs = c->row_req_host[(size_t)src];
+      tgx::RowReq& qd = c->row_req_host[(size_t)dst_rows[i]];
+      if (qs.auto_next || qd.auto_next) {
+        qd.auto_next = qs.auto_next; qd.auto_state = qs.auto_state;
+        c->row_host[(size_t)dst_rows[i]].auto_id = c->row_host[(size_t)src].auto_id;
+        row_proc_refresh(qd);
+        row_req_push(c, dst_rows[i], ROWQ_AUTO);
+      }
+    }
     row_admitted(c, dst_rows[i], (int)past);
     c->row_host[(size_t)dst_rows[i]].tok = c->row_host[(size_t)src].tok;      // the token word travelled with the copy
   }
@@ -2235,11 +2253,6 @@ int tgx_set_row_logprobs(tgx_ctx* c, int row, int top_n) {
 
 // ---- per-row logit processors (include/tgx.h; kernels/logit_proc.h).  Every check comes before anything changes; the settings travel by value in stream-ordered
 // launches, like the sampler settings
-static void row_proc_refresh(tgx::RowReq& q) {      // proc: which processors are on (0: none — the row is copied through)
-  const bool pen = q.repetition != 1.f || q.presence != 0.f || q.frequency != 0.f;
-  q.proc = (pen ? tgx::PROC_PENALTY : 0) | (q.n_bias > 0 ? tgx::PROC_BIAS : 0);
-}
-
 int tgx_set_row_penalties(tgx_ctx* c, int row, const tgx_penalty_cfg* cfg) {
   if (!c) return TGX_ERR_INVALID;
   if (!cfg) return set_err(c, TGX_ERR_INVALID, "null penalty configuration");
@@ -2325,6 +2338,75 @@ int tgx_set_row_history(tgx_ctx* c, int row, const int64_t* prompt_ids, int n_pr
   return TGX_OK;
 }
 
+// ---- token automata (include/tgx.h; automaton.h holds the checks, kernels/logit_proc.h the mask stage and the advance launch)
+static_assert(automaton::NONE == TGX_AUTOMATON_NONE && automaton::MAX_STATES == TGX_MAX_AUTOMATON_STATES && automaton::MAX_TABLES == TGX_MAX_AUTOMATA && tgx::AUTO_NONE == TGX_AUTOMATON_NONE, "automaton.h");
+int tgx_automaton_create(tgx_ctx* c, int32_t n_states, int32_t start, const uint16_t* next, int32_t* out_id) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "automaton_create before finalize");
+  if (!next || !out_id) return set_err(c, TGX_ERR_INVALID, "null argument");
+  char why[160];
+  if (automaton::validate(n_states, start, next, c->d.vocab, why, sizeof(why))) return set_err(c, TGX_ERR_INVALID, "tgx_automaton_create: %s", why);
+  int id = -1;
+  for (int i = 0; i < TGX_MAX_AUTOMATA && id < 0; i++) if (!c->automata[i].next) id = i;
+  if (id < 0) return set_err(c, TGX_ERR_INVALID, "tgx_automaton_create: %d tables are live (tgx_automaton_destroy one first)", TGX_MAX_AUTOMATA);
+  HIP_OK(c, hipSetDevice(c->device));
+  const size_t words = (size_t)n_states * (size_t)c->d.vocab;
+  unsigned short* dev = nullptr;
+  if (int rc = dev_alloc(c, &dev, words)) return rc;
+  // the caller's array may be pageable and is the caller's again on return: the copy is waited for
+  const hipError_t e = hipMemcpy(dev, next, words * sizeof(uint16_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { dev_free(c, &dev); return set_err(c, TGX_ERR_DEVICE, "tgx_automaton_create: copying the table failed: %s", hipGetErrorString(e)); }
+  c->automata[id].next = dev; c->automata[id].n_states = n_states; c->automata[id].start = start;
+  *out_id = id;
+  return TGX_OK;
+}
+
+int tgx_automaton_destroy(tgx_ctx* c, int32_t id) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "automaton_destroy before finalize");
+  if (id < 0 || id >= TGX_MAX_AUTOMATA || !c->automata[id].next) return set_err(c, TGX_ERR_INVALID, "tgx_automaton_destroy: no automaton %d", (int)id);
+  for (int b = 0; b < c->d.max_batch; b++)
+    if (c->row_host[(size_t)b].auto_id == id) return set_err(c, TGX_ERR_STATE, "tgx_automaton_destroy: row %d still names automaton %d (tgx_set_row_automaton(row, -1, -1) or reset it first)", b, (int)id);
+  HIP_OK(c, hipSetDevice(c->device));
+  HIP_OK(c, hipStreamSynchronize(c->stream));      // steps in flight may still read the table of a row that was switched off behind them
+  dev_free(c, &c->automata[id].next);
+  c->automata[id] = tgx_ctx::AutoTable{};
+  return TGX_OK;
+}
+
+int tgx_set_row_automaton(tgx_ctx* c, int row, int32_t id, int32_t state) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "set_row_automaton before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  if (id < -1 || id >= TGX_MAX_AUTOMATA || (id >= 0 && !c->automata[id].next)) return set_err(c, TGX_ERR_INVALID, "tgx_set_row_automaton: no automaton %d", (int)id);
+  if (id >= 0 && !automaton::state_ok(c->automata[id].n_states, state)) return set_err(c, TGX_ERR_INVALID, "tgx_set_row_automaton: state %d out of range [-1,%d)", (int)state, c->automata[id].n_states);
+  tgx::RowReq& q = c->row_req_host[(size_t)row];
+  if (id < 0 && !q.auto_next) return TGX_OK;      // nothing to switch off
+  HIP_OK(c, hipSetDevice(c->device));
+  if (id >= 0) { if (int rc = proc_alloc(c)) return rc; }      // the mask is a stage of the processor launch: its slab and partials
+  q.auto_next = id >= 0 ? c->automata[id].next : nullptr;
+  q.auto_state = id >= 0 ? (state < 0 ? c->automata[id].start : state) : 0;
+  c->row_host[(size_t)row].auto_id = id;
+  row_proc_refresh(q);
+  row_req_push(c, row, ROWQ_PROC | ROWQ_AUTO);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+int tgx_read_row_automaton(tgx_ctx* c, int row, int32_t* out_id, int32_t* out_state) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "read_row_automaton before finalize");
+  if (row < 0 || row >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, c->d.max_batch);
+  HIP_OK(c, hipSetDevice(c->device));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  const int id = c->row_host[(size_t)row].auto_id;
+  int state = -1;
+  if (id >= 0) HIP_OK(c, hipMemcpy(&state, &c->row_req[row].auto_state, 4, hipMemcpyDeviceToHost));
+  if (out_id) *out_id = id;
+  if (out_state) *out_state = state;
+  return TGX_OK;
+}
+
 int tgx_read_row_logprobs(tgx_ctx* c, int row, int n, float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t* out_top_n) {
   if (!c) return TGX_ERR_INVALID;
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "read_row_logprobs before finalize");
@@ -2398,6 +2480,7 @@ int tgx_decode_rows(tgx_ctx* c, int n_steps, int64_t* out_ids, int32_t* out_new,
     if (records) c->row_host[b].lp_count = lp[b].count;
     c->row_host[b].past = pos[b];                              // a row advanced once per token it produced (retired rows: wherever their ride took them)
     c->row_host[b].fin = idle ? 0 : (char)req[b].finished;
+    c->row_req_host[b].auto_state = req[b].auto_state;         // the automaton's state word moves on the device only: the mirror follows the readback
     if (out_new) out_new[b] = idle ? 0 : (int32_t)(pos[b] - before[b]);
     if (out_finish) out_finish[b] = idle ? 0 : req[b].finished;
     if (c->row_host[b].fin) kv_trim_row(c, (int)b, c->row_host[b].past);

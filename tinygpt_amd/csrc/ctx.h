@@ -86,6 +86,7 @@ struct RowHost {        // host state of one batch row
   int64_t lp_count = 0; // mirror of the row's device-side record counter (tgx_read_row_logprobs): records appended since the count was reset
   bool probs_ok = false; tgx_sampler_cfg probs_cfg{};   // the row's last sampled step was a non-greedy one, and its sampler configuration (tgx_read_probs evaluates the vector on demand)
   bool probs_proc = false;   // ... and it drew from the processed logits (kernels/logit_proc.h): tgx_read_probs evaluates the vector from that slab
+  int auto_id = -1;          // the automaton the row names (tgx_set_row_automaton; -1: none) — a setting: restart() keeps it, tgx_reset_row / tgx_reset_cache clear it
   // the slot starts over at `len` positions: no current token, its logits its own; what its last sampled step left (probs_ok, probs_cfg) stays
   void restart(int64_t len, bool idle_, char fin_) { past = len; tok = nologits = false; idle = idle_; fin = fin_; }
 };
@@ -385,6 +386,10 @@ struct tgx_ctx {
   float* proc_logits = nullptr;              // [max_batch][vocab] the processed logits of the rows' last processed step
   float* proc_part_val = nullptr;            // [max_batch][ceil(vocab / 1024)] their per-tile (max, lowest index)
   int* proc_part_idx = nullptr;
+  // ---- token automata (include/tgx.h tgx_automaton_create; automaton.h holds the checks): the live tables, each [n_states][vocab] 16-bit words from c->mem.  A row
+  // names one by RowHost::auto_id; its table pointer and state word live in its RowReq.  A context that never creates one holds none of it
+  struct AutoTable { unsigned short* next = nullptr; int n_states = 0, start = 0; };
+  AutoTable automata[TGX_MAX_AUTOMATA];
   // ---- row snapshots (include/tgx.h tgx_save_row / tgx_restore_row; row_snapshot.h, kernels/kv_pack.h): the staging buffer a snapshot moves through in groups of
   // whole layers (the state section in front of the first group's).  Allocated by the first save or restore, grown to the largest group seen; option
   // snapshot.stage_kib caps it (one layer is always staged)
@@ -475,7 +480,7 @@ void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true)
 int attn_set_attrs(tgx_ctx* c);
 // ---- sampler.hip (kernels/sampler.h)
 void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step, bool processed = false);   // processed: from the processed logits (launch_logit_proc ran for these rows)
-enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16, ROWU_LP = 32, ROWU_PROC = 64 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick; some row records log-probabilities; some row has a logit processor on
+enum { ROWU_GREEDY = 1, ROWU_K = 2, ROWU_P = 4, ROWU_M = 8, ROWU_SUM = 16, ROWU_LP = 32, ROWU_PROC = 64, ROWU_AUTO = 128 };   // stages of a per-row step: greedy finalize, top-k, top-p, min-p, partial sums + pick; some row records log-probabilities; some row has a logit processor on; ... an automaton among them (its state advances ahead of the processor launch)
 void launch_sample_rows(tgx_ctx* c, int row0, int R, int un);              // tgx_decode_rows: every row with its own settings (a decode step's sampler)
 int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);

@@ -169,12 +169,16 @@ struct RowReq {
   int lp;                           // per-token log-probabilities (kernels/logprobs.h; tgx_set_row_logprobs): 0 off — the zero-initialised state — else top_n + 1
   int stop[ROW_MAX_STOP];
   // logit processors (kernels/logit_proc.h; tgx_set_row_penalties / tgx_set_row_logit_bias): proc 0 off — the zero-initialised state, the values below are then
-  // not looked at — else PROC_PENALTY | PROC_BIAS; n_bias: entries of the row's bias list
+  // not looked at — else PROC_PENALTY | PROC_BIAS | PROC_AUTOMATON; n_bias: entries of the row's bias list
   int proc, n_bias;
   float repetition, presence, frequency;
-  int proc_pad;
+  // the row's token automaton (tgx_set_row_automaton; PROC_AUTOMATON): its table [n_states][vocab] of 16-bit words on the device and the state after every
+  // token the row CONSUMED while the automaton was on — moved on the device only (automaton_advance_kernel), like `produced`
+  int auto_state;
+  const unsigned short* auto_next;
 };
-enum { PROC_PENALTY = 1, PROC_BIAS = 2 };
+enum { PROC_PENALTY = 1, PROC_BIAS = 2, PROC_AUTOMATON = 4 };
+constexpr unsigned short AUTO_NONE = 0xFFFFu;       // == TGX_AUTOMATON_NONE: next[s][t] of a token that state s does not allow
 constexpr unsigned int PROC_PROMPT_BIT = 0x80000000u, PROC_COUNT_MASK = 0x7fffffffu;   // a history word (kernels/logit_proc.h): "occurs in the prompt" | times produced
 __device__ __forceinline__ bool row_req_greedy(const RowReq& q) {   // == is_greedy (Sampler.cpp:15-21)
   return !(q.temperature > 0.f || q.top_k > 0 || q.top_p < 1.f || q.min_p > 0.f);

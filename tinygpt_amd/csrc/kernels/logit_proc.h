@@ -1,5 +1,6 @@
 // logit_proc.h — per-row logit processors (include/tgx.h tgx_set_row_penalties / tgx_set_row_logit_bias / tgx_set_row_history): repetition, presence and
-// frequency penalties over a row's token history and an additive logit bias, applied on the device ahead of a step's publish.
+// frequency penalties over a row's token history, an additive logit bias and the mask of a token automaton (tgx_set_row_automaton), applied on the device ahead of
+// a step's publish.
 // One launch per launch_sample_rows call (sampler.hip) while some row of the batch has a processor on: grid (ceil(V / 1024), rows), 256 threads; workgroup t of
 // row y owns entries [1024 t, 1024 t + 1024), four consecutive ones per thread.  It reads the raw logits and the row's history words (16-byte loads when
 // V % 4 == 0: every row of both slabs then starts on a 16-byte boundary; entry by entry otherwise), counts the row's current token (the owner of that entry reads,
@@ -13,6 +14,15 @@
 //   1. w != 0:  v = v > 0 ? v / repetition : v * repetition
 //   2. v = v - frequency * (float)n;  v = v - (n > 0 ? presence : 0)
 //   3. the entry is in the bias list:  v = v + bias
+//   4. the row has an automaton on and next[state][entry] == NONE:  v = -INFINITY
+//
+// The automaton (include/tgx.h tgx_set_row_automaton).  Stage 4 reads the row's table pointer and state word once per workgroup and the four 16-bit entries of
+// the thread's four logits (one 8-byte load when V % 4 == 0: the table comes from the device allocator and a table row is then a multiple of 8 bytes; entry by
+// entry otherwise), after the bias stage and before the tile is written, so the tile's (max, lowest index) partial sees the mask: 2 V more bytes read per
+// constrained row and step.  The STATE moves in a launch of its own ahead of this one (automaton_advance_kernel: one workgroup, one thread per row of the step,
+// state = next[state][current token] for rows that are on and unfinished), issued only under the union bit ROWU_AUTO: every tile of a row needs the NEW state, and
+// a fold into this kernel would have the tile that owns the current token move a word the other tiles of the row read in no defined order.  A consumed token that
+// the state does not allow (only a caller that switched the automaton on mid-stream can feed one) leaves the state where it is.
 #pragma once
 #include "common.h"
 
@@ -55,6 +65,19 @@ __device__ __forceinline__ float proc_penalise(float v, unsigned int w, float re
   v = proc_sub(v, proc_mul(freq, (float)n));
   v = proc_sub(v, n > 0 ? pres : 0.f);
   return v;
+}
+
+// rows [0, rows) of a tgx_decode_rows step: an unfinished row whose automaton is on consumes its current token.  One workgroup; the only writer of the state words
+struct AutoAdvanceArgs { RowReq* req; const int* tok; int rows, V; };
+__global__ __launch_bounds__(WAVE) void automaton_advance_kernel(const AutoAdvanceArgs a) {
+  for (int y = threadIdx.x; y < a.rows; y += WAVE) {
+    RowReq& q = a.req[y];
+    if (!(q.proc & PROC_AUTOMATON) || q.finished) continue;
+    const int t = a.tok[y];
+    if (t < 0 || t >= a.V) continue;
+    const unsigned short n = q.auto_next[(size_t)q.auto_state * a.V + t];
+    if (n != AUTO_NONE) q.auto_state = n;
+  }
 }
 
 __global__ __launch_bounds__(PROC_WG) void logit_proc_kernel(const LogitProcArgs a) {
@@ -113,6 +136,19 @@ __global__ __launch_bounds__(PROC_WG) void logit_proc_kernel(const LogitProcArgs
       const f32x4 r = *reinterpret_cast<const f32x4*>(tile + tid * PROC_EPT);
 #pragma unroll
       for (int j = 0; j < PROC_EPT; j++) v[j] = r[j];
+    }
+    if (proc & PROC_AUTOMATON) {      // stage 4: the entries the row's state does not allow
+      const unsigned short* nx = q.auto_next + (size_t)q.auto_state * V;
+      unsigned int e[PROC_EPT];
+      if (vec && base < V) {
+        const u32x2 r = *reinterpret_cast<const u32x2*>(nx + base);
+        e[0] = r[0] & 0xffffu; e[1] = r[0] >> 16; e[2] = r[1] & 0xffffu; e[3] = r[1] >> 16;
+      } else {
+#pragma unroll
+        for (int j = 0; j < PROC_EPT; j++) e[j] = !vec && base + j < V ? nx[base + j] : 0u;
+      }
+#pragma unroll
+      for (int j = 0; j < PROC_EPT; j++) if (e[j] == AUTO_NONE) v[j] = -INFINITY;
     }
   }
   float* out = a.out + (size_t)y * V;

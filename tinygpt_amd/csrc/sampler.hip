@@ -144,6 +144,10 @@ void launch_sample_rows(tgx_ctx* c, int row0, int R, int un) {
   tgx::RowReq* req = c->row_req + row0;
   // some row of the batch has a logit processor on: every row's logits pass through the processed slab (unprocessed rows are copied), and every consumer below but
   // the log-probabilities — the MODEL's distribution — reads that slab and its partials
+  if (un & ROWU_AUTO) {       // some row has an automaton on: the rows' state words consume the current tokens ahead of the launch that masks with them
+    tgx::AutoAdvanceArgs aa{req, c->rows[(size_t)row0].tok, R, c->d.vocab};
+    hipLaunchKernelGGL(tgx::automaton_advance_kernel, dim3(1), dim3(tgx::WAVE), 0, c->stream, aa);
+  }
   if (un & ROWU_PROC) launch_logit_proc(c, row0, R, /*step=*/true);
   if (un & ROWU_GREEDY) {
     tgx::FinalizeRowsArgs fa{};
@@ -193,7 +197,7 @@ int row_union_of(const tgx_ctx* c) {
     const tgx::RowReq& q = c->row_req_host[(size_t)b];
     const bool K = q.top_k > 0, P = q.top_p < 1.f, M = q.min_p > 0.f, sampled = K || P || M || q.temperature > 0.f;
     if (row_records(c, b)) un |= ROWU_LP;
-    if (row_processed(c, b)) un |= ROWU_PROC;
+    if (row_processed(c, b)) un |= ROWU_PROC | ((q.proc & tgx::PROC_AUTOMATON) ? ROWU_AUTO : 0);
     if (!sampled) { un |= ROWU_GREEDY; continue; }
     if (K) un |= ROWU_K;
     if (P) un |= ROWU_P;

@@ -104,6 +104,10 @@ ABI = {
     "set_row_penalties": (c_int, [c_void_p, c_int, POINTER(PenaltyCfg)]),
     "set_row_logit_bias": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_float)]),
     "set_row_history": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), c_int]),
+    "automaton_create": (c_int, [c_void_p, c_int32, c_int32, POINTER(ctypes.c_uint16), POINTER(c_int32)]),
+    "automaton_destroy": (c_int, [c_void_p, c_int32]),
+    "set_row_automaton": (c_int, [c_void_p, c_int, c_int32, c_int32]),
+    "read_row_automaton": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32)]),
     "context_size": (c_int64, [c_void_p]),
     "num_layers": (c_int32, [c_void_p]),
     "last_error": (c_char_p, [c_void_p]),
@@ -475,6 +479,31 @@ class Model:
         self._check(self.be.set_row_logit_bias(self._ctx, row, len(ids), ids.ctypes.data_as(POINTER(c_int32)) if len(ids) else None,
                                                val.ctypes.data_as(POINTER(c_float)) if len(ids) else None))
         return self
+
+    # -- token automata (include/tgx.h tgx_automaton_create) ------------------------------------
+    def automaton_create(self, next, start: int = 0) -> int:
+        """next: uint16 [n_states][vocab], 0xFFFF = not allowed; returns the table's id"""
+        t = np.ascontiguousarray(next)
+        if t.dtype != np.uint16 or t.ndim != 2 or t.shape[1] != self.desc.vocab:
+            raise ValueError(f"automaton table: uint16 [n_states][{self.desc.vocab}] expected, got {t.dtype} {t.shape}")
+        out = c_int32(-1)
+        self._check(self.be.automaton_create(self._ctx, t.shape[0], start, t.ctypes.data_as(POINTER(ctypes.c_uint16)), ctypes.byref(out)))
+        return out.value
+
+    def automaton_destroy(self, aid: int):
+        self._check(self.be.automaton_destroy(self._ctx, aid))
+        return self
+
+    def set_row_automaton(self, row: int, aid: int = -1, state: int = -1):
+        """aid -1 switches the row off; state -1 is the table's start"""
+        self._check(self.be.set_row_automaton(self._ctx, row, aid, state))
+        return self
+
+    def read_row_automaton(self, row: int):
+        """(id, state) of the row as it stands (-1, -1: none); synchronises"""
+        i, s = c_int32(-1), c_int32(-1)
+        self._check(self.be.read_row_automaton(self._ctx, row, ctypes.byref(i), ctypes.byref(s)))
+        return i.value, s.value
 
     def set_row_history(self, row: int, prompt_ids=(), produced_ids=()):
         """REPLACES the row's history words: the prompt bit of every id in prompt_ids, the produced count of every id in produced_ids"""

@@ -61,6 +61,11 @@ struct Backend {
   int (*set_row_penalties)(tgx_ctx*, int, const tgx_penalty_cfg*) = nullptr;
   int (*set_row_logit_bias)(tgx_ctx*, int, int, const int32_t*, const float*) = nullptr;
   int (*set_row_history)(tgx_ctx*, int, const int64_t*, int, const int64_t*, int) = nullptr;
+  // token automata (optional: SamplerConfig::regex needs create, destroy and set_row_automaton, and the per-row calls the processors step through)
+  int (*automaton_create)(tgx_ctx*, int32_t, int32_t, const uint16_t*, int32_t*) = nullptr;
+  int (*automaton_destroy)(tgx_ctx*, int32_t) = nullptr;
+  int (*set_row_automaton)(tgx_ctx*, int, int32_t, int32_t) = nullptr;
+  int (*read_row_automaton)(tgx_ctx*, int, int32_t*, int32_t*) = nullptr;
   // scoring a supplied sequence (optional: GPTEngine::score needs it)
   int (*score_row)(tgx_ctx*, int, const int64_t*, int, int, float*, int32_t*, float*) = nullptr;
   // row snapshots (optional: GPTEngine::saveSession / loadSession need all three, and prefix reuse)
@@ -92,6 +97,7 @@ struct Backend {
     TGXH_BIND(advance_rows, false);
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
     TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);
+    TGXH_BIND(automaton_create, false); TGXH_BIND(automaton_destroy, false); TGXH_BIND(set_row_automaton, false); TGXH_BIND(read_row_automaton, false);
     TGXH_BIND(score_row, false);
     TGXH_BIND(row_snapshot_bytes, false); TGXH_BIND(save_row, false); TGXH_BIND(restore_row, false);
 #undef TGXH_BIND

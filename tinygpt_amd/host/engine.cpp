@@ -84,6 +84,25 @@ void GPTEngine::reconfigure(const SamplerConfig& samplerConfig, int64_t maxNewTo
   eosTokenIds_ = baseEosTokenIds_;
   for (int32_t id : extraStopTokenIds) if (!isEosToken(id)) eosTokenIds_.push_back(id);
   if (model_.ctx && !reuseActive()) be_.reset_cache(model_.ctx);           // context_.model->resetCache()  (:83); reusePrefix: the generate calls decide
+  if (prepared_ && constraintOn()) constraintEnsure();                     // (a failure is reported by the generate call, which asks again)
+}
+
+// ---- SamplerConfig::regex: the pattern compiled over the tokenizer (constraint.h) and its table on the device (include/tgx.h tgx_automaton_create)
+bool GPTEngine::constraintEnsure() {
+  if (!(be_.automaton_create && be_.automaton_destroy && be_.set_row_automaton && be_.set_row_sampler && be_.sample_row && be_.set_row_stop && be_.decode_rows))
+    return fail("regex: the device shim lacks tgx_automaton_create / tgx_set_row_automaton or the per-row calls they ride on");
+  if (!tokenizerOk_) return fail("regex: no tokenizer loaded (tokenizerDir / modelDir must hold tokenizer.json)");
+  if (eosTokenIds_.size() > (size_t)TGX_MAX_STOP_IDS) return fail("regex: the rows stop on the device, which holds at most " + std::to_string(TGX_MAX_STOP_IDS) + " stop ids");
+  const std::string& pattern = config_.samplerConfig.regex;
+  if (constraintId_ >= 0 && pattern == constraintPattern_ && eosTokenIds_ == constraintStops_) return true;
+  TokenAutomaton a;
+  std::string why;
+  if (!compileConstraint(pattern, tokenizer_, desc().vocab, eosTokenIds_, a, why)) return fail("regex: " + why);
+  if (constraintId_ >= 0) { be_.automaton_destroy(model_.ctx, constraintId_); constraintId_ = -1; }      // (every call switched its rows off when it ended)
+  int32_t id = -1;
+  if (be_.automaton_create(model_.ctx, a.nStates, a.start, a.next.data(), &id) != TGX_OK) return fail(std::string("regex: ") + be_.last_error(model_.ctx));
+  constraintId_ = id; constraintPattern_ = pattern; constraintStops_ = eosTokenIds_;
+  return true;
 }
 
 // reusePrefix: L = the common prefix of what row 0's cache holds and the new prompt, capped at prompt length - 1 (the last position's logits must be computed) and at
@@ -329,6 +348,7 @@ bool GPTEngine::rowsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int6
 // it admitted and steps through the per-row calls, which count what the rows produce
 bool GPTEngine::processorsRefused(bool async) {
   if (!processorsOn()) return false;
+  if (constraintOn() && !constraintEnsure()) return true;
   if (!(be_.set_row_penalties && be_.set_row_logit_bias && be_.set_row_history && be_.set_row_sampler && be_.sample_row && be_.set_row_stop && be_.decode_rows)) {
     fail("penalties / logit bias: the device shim lacks tgx_set_row_penalties / tgx_set_row_logit_bias / tgx_set_row_history or the per-row calls they ride on");
     return true;
@@ -346,6 +366,7 @@ bool GPTEngine::processorsBegin(int row, const int64_t* prompt, int64_t n) {
   if (be_.set_row_penalties(model_.ctx, row, &pc) != TGX_OK || be_.set_row_logit_bias(model_.ctx, row, (int)ids.size(), ids.data(), val.data()) != TGX_OK ||
       be_.set_row_history(model_.ctx, row, prompt, (int)n, nullptr, 0) != TGX_OK)
     return fail(std::string("penalties / logit bias: ") + be_.last_error(model_.ctx));
+  if (constraintOn() && be_.set_row_automaton(model_.ctx, row, constraintId_, -1) != TGX_OK) return fail(std::string("regex: ") + be_.last_error(model_.ctx));
   return true;
 }
 
@@ -355,6 +376,7 @@ void GPTEngine::processorsEnd(int batch) {
     be_.set_row_penalties(model_.ctx, b, &neutral);
     be_.set_row_logit_bias(model_.ctx, b, 0, nullptr, nullptr);
     be_.set_row_history(model_.ctx, b, nullptr, 0, nullptr, 0);
+    if (be_.set_row_automaton) be_.set_row_automaton(model_.ctx, b, -1, -1);
   }
 }
 
@@ -442,6 +464,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? B : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(B); });
   const bool procOn = processorsOn(), specSampled = speculateSampledActive(B), perRow = lpOn || procOn || specSampled;
+  bool allStopped = false;      // SamplerConfig::regex: every row ended at a stop id
   const auto procOff = at_exit([&] { if (procOn) processorsEnd(B); });
   const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(B); });
   if (procOn)      // every row's history: the prompt it admitted, without the left padding
@@ -488,13 +511,31 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
     if ((int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
     for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = seq[(size_t)(S + 1 + i)];
   } else if (perRow) {      // every row with the call's settings through tgx_decode_rows (its ids are tgx_decode's), a ring's worth of steps at most per call
+    // under a regex the rows end on the device at an EOS / stop id, which the automaton allows only where a match may end; otherwise no EOS check, as below
+    const bool constrained = constraintOn();
     for (int b = 0; b < B; b++)
-      if (be_.set_row_stop(model_.ctx, b, 0, nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
-    for (int64_t done = 0; done < n_new - 1;) {
+      if (be_.set_row_stop(model_.ctx, b, 0, constrained && !eosTokenIds_.empty() ? eosTokenIds_.data() : nullptr, constrained ? (int)eosTokenIds_.size() : 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+    std::vector<int32_t> fin((size_t)B, 0), made((size_t)B, 0);
+    if (constrained) for (int b = 0; b < B; b++) fin[(size_t)b] = isEosToken((int32_t)first[(size_t)b]) ? 1 : 0;      // (a pattern that matches the empty string: tgx_sample_row does not test the stop set)
+    auto running = [&] { for (int32_t f : fin) if (!f) return true; return false; };
+    int64_t done = 0;
+    while (done < n_new - 1 && running()) {
       const int m = (int)std::min<int64_t>(n_new - 1 - done, TGX_LOGPROB_RING / 2);
-      if (be_.decode_rows(model_.ctx, m, rest.data() + (size_t)(done * B), nullptr, nullptr) != TGX_OK) { fail(std::string("decode: ") + be_.last_error(model_.ctx)); return out; }
-      for (int b = 0; lpOn && b < B; b++) if (!logprobsDrain(b, m, lpRows[(size_t)b])) return out;
+      if (be_.decode_rows(model_.ctx, m, rest.data() + (size_t)(done * B), constrained ? made.data() : nullptr, constrained ? fin.data() : nullptr) != TGX_OK) { fail(std::string("decode: ") + be_.last_error(model_.ctx)); return out; }
+      for (int b = 0; lpOn && b < B; b++) if (!logprobsDrain(b, constrained ? made[(size_t)b] : m, lpRows[(size_t)b])) return out;
       done += m;
+    }
+    if (constrained) {      // behind a row's stop: the pad token
+      const int32_t pad = padTokenId();
+      for (int b = 0; b < B; b++) {
+        bool stopped = isEosToken((int32_t)first[(size_t)b]);
+        for (int64_t i = 0; i + 1 < n_new; i++) {
+          int64_t& t = rest[(size_t)(i * B + b)];
+          if (stopped || i >= done || t < 0) t = pad;
+          else if (isEosToken((int32_t)t)) stopped = true;
+        }
+      }
+      allStopped = !running();
     }
   } else
   if (n_new > 1 && be_.decode(model_.ctx, &sc, config_.seed, (int)(n_new - 1), rest.data()) != TGX_OK) {
@@ -513,7 +554,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
     row[S] = (int32_t)first[(size_t)b];
     for (int64_t i = 0; i + 1 < n_new; i++) row[S + 1 + i] = (int32_t)rest[(size_t)(i * B + b)];
   }
-  out.finishReason = FinishReason::Length;
+  out.finishReason = allStopped ? FinishReason::Stop : FinishReason::Length;
   return out;
 }
 
@@ -652,6 +693,14 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::string>& texts) {
   if (!tokenizerOk_) { fail("generateSync(texts): no tokenizer loaded"); return GPTOutput(); }
   const std::vector<std::vector<int32_t>> prompts = tokenizer_.encodeBatch(texts);
   GPTOutput out = generateSync(prompts, padTokenId());
+  if (out.batch > 0 && constraintOn()) {      // a row's text ends where the row stopped: the stop id and the pad tokens behind it are not part of the match
+    const size_t row = out.tokenIds.size() / (size_t)out.batch, S = row - (size_t)out.newTokens;
+    for (int64_t b = 0; b < out.batch; b++) {
+      std::vector<int32_t> ids;
+      for (size_t i = S; i < row && !isEosToken(out.tokenIds[(size_t)b * row + i]); i++) ids.push_back(out.tokenIds[(size_t)b * row + i]);
+      out.texts.push_back(tokenizer_.decode(ids));
+    }
+  } else
   if (out.batch > 0) out.texts = tokenizer_.decodeBatch(out.tokenIds, (uint32_t)out.batch, (uint32_t)(out.tokenIds.size() / (size_t)out.batch - (size_t)out.newTokens));
   return out;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "backend.h"
+#include "constraint.h"
 #include "loader.h"
 #include "spec_draft.h"
 #include "tokenizer.h"
@@ -31,7 +32,15 @@ struct SamplerConfig {   // src/engine/Sampler.h:13-22
   float presencePenalty = 0.f;
   float frequencyPenalty = 0.f;
   std::map<int32_t, float> logitBias;      // id -> value added to the id's logit; -INFINITY bans the id
-  bool processorsNeutral() const { return repetitionPenalty == 1.f && presencePenalty == 0.f && frequencyPenalty == 0.f && logitBias.empty(); }
+  // Constrained decoding (constraint.h states the supported subset; include/tgx.h tgx_automaton_create): empty = off.  Otherwise every row's output must match the
+  // pattern as a whole.  The engine compiles it over its tokenizer into a token automaton (on reconfigure / prepare, and the same pattern twice compiles once), with
+  // its EOS ids and extra stop ids allowed exactly where a match may end; it sets every row's automaton at its admission, steps through the per-row path the
+  // penalties take, stops every row on the device at such an id and switches the rows off when the call ends.  `speculate` falls back to plain steps.  A row that
+  // stops has produced a full match (finish reason Stop; generateSync: when every row stopped; positions of a row behind its stop hold the pad token); a row that
+  // maxNewTokens ends first has produced a PREFIX of a match, finish reason Length.  A backend without the calls, no tokenizer, a tokenizer that is not ByteLevel,
+  // more stop ids than TGX_MAX_STOP_IDS or a failed compile FAILS the generate call with a message (lastError).
+  std::string regex;
+  bool processorsNeutral() const { return repetitionPenalty == 1.f && presencePenalty == 0.f && frequencyPenalty == 0.f && logitBias.empty() && regex.empty(); }
 };
 
 enum class FinishReason { Stop, Length };
@@ -179,6 +188,7 @@ class GPTEngine {
     config_.samplerConfig.repetitionPenalty = repetition; config_.samplerConfig.presencePenalty = presence; config_.samplerConfig.frequencyPenalty = frequency;
     config_.samplerConfig.logitBias = std::move(bias);
   }
+  void setRegex(std::string pattern) { config_.samplerConfig.regex = std::move(pattern); }      // kept by the C view across tgxe_reconfigure, like setProcessors
   const SpecStats& specStats() const { return spec_; }
 
  private:
@@ -209,6 +219,8 @@ class GPTEngine {
   bool processorsRefused(bool async);                                                          // asked for and not servable: err_ set, the generate call fails
   bool processorsBegin(int row, const int64_t* prompt, int64_t n);                            // the row's settings, and its history from the prompt it admitted
   void processorsEnd(int batch);                                                               // neutral again, histories cleared
+  bool constraintOn() const { return !config_.samplerConfig.regex.empty(); }
+  bool constraintEnsure();                                                                     // SamplerConfig::regex compiled and its table on the device (kept while pattern and stop ids stay); false: err_ set
   bool rowsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first);          // the rows' sampler (and logprobs) settings, then every row's first token through tgx_sample_row
 
   GPTConfig config_;
@@ -222,6 +234,9 @@ class GPTEngine {
   std::vector<int32_t> cached_;      // reusePrefix: the token ids row 0's cache holds, position by position (empty: unknown / nothing)
   int64_t lastReused_ = 0;
   SpecStats spec_;
+  std::string constraintPattern_;            // the pattern and stop ids of the table the device holds (constraintId_ >= 0)
+  std::vector<int32_t> constraintStops_;
+  int32_t constraintId_ = -1;
 };
 
 // Deterministic synthetic checkpoint — bit-identical to tinygpt_amd/synth.py (same integer hash).

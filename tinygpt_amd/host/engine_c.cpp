@@ -1,6 +1,8 @@
 // engine_c.cpp — a C view of the host engine so that tests (ctypes) and other hosts can drive it.
 #include <cstring>
 
+#include "../csrc/automaton.h"
+#include "constraint.h"
 #include "engine.h"
 #include "tokenizer.h"
 
@@ -126,6 +128,8 @@ TGXE_API void tgxe_set_processors(tgxe_engine* h, float repetition, float presen
   for (int i = 0; bias_ids && bias && i < n; i++) m[bias_ids[i]] = bias[i];
   h->e->setProcessors(repetition, presence, frequency, std::move(m));
 }
+// SamplerConfig::regex (constrained decoding; empty or NULL: off); kept across tgxe_reconfigure until set again
+TGXE_API void tgxe_set_regex(tgxe_engine* h, const char* pattern) { if (h) h->e->setRegex(pattern ? pattern : ""); }
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
   tgxh::SamplerConfig s = h->e->samplerConfig();      // (the penalties / logit bias of tgxe_set_processors stay)
@@ -234,6 +238,51 @@ TGXE_API int64_t tgxe_regex_match_all(const char* pattern, const char* text, int
   re.matchAll(std::string(text, (size_t)len), m);
   for (int64_t i = 0; i < (int64_t)m.size() && i < cap_pairs; i++) { out[2 * i] = (int64_t)m[(size_t)i].first; out[2 * i + 1] = (int64_t)m[(size_t)i].second; }
   return (int64_t)m.size();
+}
+
+// ---- the pattern compiler (constraint.h) for its tests
+// the byte DFA of `pattern` over the string: 1 accepted, 0 not, -1 the pattern did not compile (err says why)
+TGXE_API int tgxe_regex_dfa_match(const char* pattern, const char* text, int64_t len, char* err, int err_cap) {
+  tgxh::ByteDfa d;
+  std::string why;
+  if (!tgxh::compileByteDfa(pattern ? pattern : "", d, why)) {
+    if (err && err_cap > 0) { strncpy(err, why.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+    return -1;
+  }
+  return d.matches(std::string(text ? text : "", (size_t)(text ? len : 0))) ? 1 : 0;
+}
+// `pattern` compiled over the tokenizer in `tokenizer_dir` into a table `vocab` ids wide (0: the tokenizer's own size), the stop ids allowed in accepting states.
+// Returns a handle (tgxe_constraint_info / _copy / _destroy) or NULL with err
+struct tgxe_constraint { tgxh::TokenAutomaton a; };
+TGXE_API tgxe_constraint* tgxe_constraint_compile(const char* tokenizer_dir, const char* pattern, const int32_t* stop_ids, int n_stop, int32_t vocab, int max_states, char* err, int err_cap) {
+  auto refuse = [&](const std::string& why) -> tgxe_constraint* {
+    if (err && err_cap > 0) { strncpy(err, why.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+    return nullptr;
+  };
+  tgxh::Tokenizer tok;
+  const std::string dir = tokenizer_dir ? tokenizer_dir : "";
+  if (!tok.initWithConfig(dir + "/tokenizer.json", dir + "/tokenizer_config.json")) return refuse("tokenizer: " + tok.lastError());
+  tgxh::ConstraintLimits lim;
+  if (max_states > 0) lim.maxStates = max_states;
+  auto* h = new tgxe_constraint();
+  std::string why;
+  const std::vector<int32_t> stops(stop_ids, stop_ids + (stop_ids && n_stop > 0 ? n_stop : 0));
+  if (tgxh::compileConstraint(pattern ? pattern : "", tok, vocab > 0 ? vocab : (int32_t)tok.vocabSize(), stops, h->a, why, lim)) return h;
+  delete h;
+  return refuse(why);
+}
+TGXE_API void tgxe_constraint_info(const tgxe_constraint* h, int32_t* n_states, int32_t* start, int32_t* vocab) { *n_states = h->a.nStates; *start = h->a.start; *vocab = h->a.vocab; }
+TGXE_API void tgxe_constraint_copy(const tgxe_constraint* h, uint16_t* next /* [n_states][vocab] */, uint8_t* accept /* [n_states] */) {
+  if (next) memcpy(next, h->a.next.data(), h->a.next.size() * sizeof(uint16_t));
+  for (size_t i = 0; accept && i < h->a.accept.size(); i++) accept[i] = h->a.accept[i] ? 1 : 0;
+}
+TGXE_API void tgxe_constraint_destroy(tgxe_constraint* h) { delete h; }
+// the table validation of tgx_automaton_create (csrc/automaton.h): 0 accepted, 1 refused (err says why)
+TGXE_API int tgxe_automaton_validate(int32_t n_states, int32_t start, const uint16_t* next, int32_t vocab, char* err, int err_cap) {
+  char why[160];
+  const bool bad = automaton::validate(n_states, start, next, vocab, why, sizeof(why)) != nullptr;
+  if (bad && err && err_cap > 0) { strncpy(err, why, (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+  return bad ? 1 : 0;
 }
 
 // Unicode normalisation for the normalizer tests: form 0 NFC, 1 NFD, 2 NFKC, 3 NFKD; returns the byte length, copies up to cap

@@ -42,6 +42,9 @@ static void usage(const char* prog) {
           "  --repetition-penalty <r> --presence-penalty <p> --frequency-penalty <f>\n"
           "                            penalties over each row's prompt and produced tokens, applied to the logits on the device (default: 1 0 0 = off)\n"
           "  --logit-bias <id:val,...> added to those ids' logits; -inf bans an id (at most 320 ids; default: none)\n"
+          "  --regex <pattern>         constrained decoding: the output must match the pattern as a whole (needs a ByteLevel tokenizer; host/constraint.h\n"
+          "                            lists the supported subset; a run that --max-tokens ends first prints a prefix of a match)\n"
+          "  --stop-ids <id,...>       stop token ids beside the model's EOS ids (--stream ends there; --regex allows them where a match may end)\n"
           "  --session-load <file>     with --stream and one text prompt: start from the conversation cache a --session-save run left (only what follows the shared\n"
           "                            prefix is prefilled; the file must come from the same model and dtype)\n"
           "  --session-save <file>     with --stream and one text prompt: keep the conversation's KV cache (prompt + generated tokens) in a file when the run ends\n"
@@ -93,6 +96,7 @@ int main(int argc, char** argv) {
   cfg.samplerConfig.temperature = 0.8f;
   cfg.samplerConfig.topP = 0.9f;
   std::string dtype = "bf16", prompt_ids, session_load, session_save;
+  std::vector<int32_t> stop_ids;
   long pad_id = -1;
   std::vector<std::string> text_prompts;
   bool stream = false, score = false;
@@ -124,6 +128,12 @@ int main(int argc, char** argv) {
     else if (a == "--repetition-penalty") cfg.samplerConfig.repetitionPenalty = strtof(next(), nullptr);
     else if (a == "--presence-penalty") cfg.samplerConfig.presencePenalty = strtof(next(), nullptr);
     else if (a == "--frequency-penalty") cfg.samplerConfig.frequencyPenalty = strtof(next(), nullptr);
+    else if (a == "--regex") cfg.samplerConfig.regex = next();
+    else if (a == "--stop-ids") {
+      std::stringstream list(next());
+      std::string item;
+      while (std::getline(list, item, ',')) if (!item.empty()) stop_ids.push_back((int32_t)atol(item.c_str()));
+    }
     else if (a == "--logit-bias") {
       std::stringstream ss(next());
       std::string item;
@@ -178,6 +188,7 @@ int main(int argc, char** argv) {
   if (session) cfg.reusePrefix = true;
   tgxh::GPTEngine engine(cfg);
   if (!engine.prepare()) { fprintf(stderr, "Prepare engine failed\n"); return 1; }
+  if (!stop_ids.empty()) engine.reconfigure(cfg.samplerConfig, cfg.maxNewTokens, stop_ids);
   if (session && !engine.hasTokenizer()) { fprintf(stderr, "Error: --session-load / --session-save need a tokenizer (--model or --tokenizer)\n"); return 1; }
   if (!session_load.empty() && !engine.loadSession(session_load)) fprintf(stderr, "session not loaded, starting from an empty cache: %s\n", engine.lastError().c_str());
 

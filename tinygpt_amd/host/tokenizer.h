@@ -56,6 +56,9 @@ class Tokenizer {
   std::string eosTokenStr() const { return eosTokenId_ < 0 ? std::string() : id2Token(eosTokenId_); }
   std::string padTokenStr() const { return padTokenId_ < 0 ? std::string() : id2Token(padTokenId_); }
   size_t vocabSize() const { return idToToken_.size(); }
+  // what the pattern compiler (constraint.h) asks: is `id` an added / special token, and is decode() the concatenation of the tokens' bytes (a ByteLevel decoder)
+  bool isAddedToken(int32_t id) const { return id >= 0 && (size_t)id < isAdded_.size() && isAdded_[(size_t)id]; }
+  bool byteLevelDecoder() const { return byteLevelDecode_; }
 
  private:
   struct Step;                                   // one normalizer / pre-tokenizer / decoder stage
