@@ -36,6 +36,7 @@ extern "C" {
 /* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
 /* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
 /* (still 3: additive) tgx_row_snapshot_bytes / tgx_save_row / tgx_restore_row — a live row saved to host memory and restored into any row of any context of the same geometry. */
+/* (still 3: additive) tgx_embed_rows — the pooled final hidden state (last / mean / first) of several texts in one ragged pass, without lm_head. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -597,6 +598,36 @@ TGX_API int tgx_read_row_logprobs(tgx_ctx* ctx, int row, int n, float* out_lp /*
  *                     last call that scored a position: 0 none yet, 1 matrix cores, 2 by groups. */
 TGX_API int tgx_score_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq, int top_n, float* out_lp /* [seq - 1] */,
                           int32_t* out_top_ids /* [seq - 1][TGX_MAX_LOGPROBS] */, float* out_top_lp /* [seq - 1][TGX_MAX_LOGPROBS] */);
+
+/* ---- embeddings: the pooled final hidden state of several texts in one ragged pass (additive to ABI 3) --------------------------------------------------------
+ * Retrieval, reranking and classification read the model's final hidden state, not its logits (Qwen3-Embedding is a plain Qwen3 checkpoint pooled at the last
+ * token).  tgx_embed_rows is tgx_forward_rows without lm_head plus one pooling pass: no [V][H] head is streamed and no logits exist afterwards.
+ *
+ *   Admission         exactly tgx_forward_rows' rules, checks, status codes and order: each row a retired row < batch or one of the next new rows, rows distinct, every
+ *                     length in [1, max_ctx], every id in range, the 1024-block limit of a paged cache; ALL OR NOTHING — the blocks of the whole call are counted
+ *                     before any is assigned; a refused call changes no row, moves no block and does not poison the context.  The call's own checks come first:
+ *                     a null pointer, a pool that is none of the three, dims outside [0, hidden] are TGX_ERR_INVALID.
+ *   The pass          the groups, routes and launches of tgx_forward_rows (one-row passes where no ragged route applies: fp32 storage, prefill.mfma 0, unsupported
+ *                     shapes, short groups) with NO lm_head launch and no lm_head staging.
+ *   The vector        per pooled position the model's final norm (model.norm; GPT-2: ln_f with bias) of the fp32 final residual — the row lm_head would be
+ *                     multiplied with, rounded to the storage dtype under act.round16 as that input is.  Pooled in fp32: TGX_POOL_LAST / TGX_POOL_FIRST take one
+ *                     position, TGX_POOL_MEAN is sum / len.  dims: 0 = hidden, else the first dims components are kept (Matryoshka truncation) BEFORE
+ *                     normalisation; normalize != 0 divides by the L2 norm (a zero vector stays zero).  out[i] is text i's vector, [n][dims ? dims : hidden].
+ *   Reproducibility   the MEAN sum is taken in an order that depends on the text's length alone: slices of 32 consecutive positions summed in position order, the
+ *                     slices merged in slice order; no atomics.  The same call returns the same bits from run to run.
+ *   Afterwards        release == 0: row i holds its lens[i] positions in tgx_truncate_row's no-logits state (as TGX_ADV_FEED_MORE leaves a row): tgx_extend_row,
+ *                     tgx_truncate_row, tgx_reset_row and tgx_save_row work on it; the decode and sample calls are TGX_ERR_STATE until it has logits.  Its per-row
+ *                     settings start afresh as for an admission.  release != 0: every named row is retired as by tgx_reset_row before the call returns and its
+ *                     blocks are back in the pool (the batch size may still have grown to cover new rows).  The call synchronises: out is valid on return.  Rows
+ *                     not named keep their state bit for bit.
+ *   Memory            a context that never calls it allocates nothing new.  The partial sums are one hidden row per 32 pooled positions, never [M][hidden].
+ *                     Read-only option `embed.last_pool_launches`: pooling launches (partials + finish) of the last call. */
+#define TGX_POOL_LAST  0   /* the last position (Qwen3-Embedding, causal LMs) */
+#define TGX_POOL_MEAN  1   /* the mean over all positions of the text */
+#define TGX_POOL_FIRST 2   /* the first position */
+typedef struct { int32_t pool; int32_t normalize; int32_t dims; int32_t release; } tgx_embed_cfg;
+TGX_API int tgx_embed_rows(tgx_ctx* ctx, int n, const int32_t* rows, const int64_t* ids /* sum(lens), back to back */,
+                           const int32_t* lens, const tgx_embed_cfg* cfg, float* out /* [n][dims ? dims : hidden] */);
 
 /* ---- per-row logit processors on the device: penalties and logit bias (additive to ABI 3) -------------------------------------------------------------------
  * The completions protocol's `presence_penalty`, `frequency_penalty` and `logit_bias`, `repetition_penalty` of a checkpoint's generation_config.json, and "never

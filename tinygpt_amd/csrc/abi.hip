@@ -610,7 +610,10 @@ static void launch_score_group(tgx_ctx* c, PrefillRoute rt, const ScoreCall& sc,
 // slot nor its position word moves — the accept launch behind the pass writes both
 // sc (tgx_score_row, nb == 1): the plain pass, and behind it every position's score — the matrix-core form over ws_x on ROUTE_TILED (prefill.hip
 // launch_score_tiled), groups of VERIFY_ROWS positions on every other route (prefill by steps scores each group as its chunks complete)
-static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool verify = false, const ScoreCall* sc = nullptr) {
+// em (tgx_embed_rows, nb == 1, past == 0): the pass WITHOUT its lm_head — the row's logits slot is not written — and behind it the pooled partials of text em->cur
+// (kernels/embed_pool.h): one launch over ws_x on the matrix-core routes; prefill by steps copies its chunks' pooled rows into the staging slice and launches
+// the same kernel per completed slice, so the slices hold the sums of the same positions in the same order on every route
+static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool verify = false, const ScoreCall* sc = nullptr, const EmbedCall* em = nullptr) {
   if (sc && sc->n_score < 1) sc = nullptr;      // (one position: nothing to score)
   constexpr int SG = tgx_ctx::VERIFY_ROWS;
   const PrefillRoute rt = prefill_route(c, seq, nb * seq);
@@ -619,12 +622,13 @@ static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool veri
     const int rc = launch_route(c, rt, nb * seq, row0, nb, seq, past);
     if (rc) return rc;
     if (verify) { launch_lm_head_all(c, rt, seq); return TGX_OK; }
-    for (int b = row0; b < row0 + nb;) {
+    for (int b = row0; b < row0 + nb && !em;) {
       const int rem = row0 + nb - b, R = rem >= 4 ? 4 : (rem >= 2 ? 2 : 1);
       launch_lm_head(c, b, R);
       b += R;
     }
     for (int b = row0; b < row0 + nb; b++) launch_add_pos(c, c->rows[(size_t)b].pos, seq);
+    if (em) launch_embed_pool(c, *em, em->cur, 1);
     if (sc && rt == ROUTE_TILED) launch_score_tiled(c, *sc);
     else if (sc)
       for (int g0 = 0; g0 < sc->n_score; g0 += SG) launch_score_group(c, rt, *sc, g0, std::min(SG, sc->n_score - g0), c->ws_x + (size_t)g0 * c->d.hidden);
@@ -651,10 +655,19 @@ static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool veri
         (void)hipMemcpyAsync(c->vf_x + (size_t)(s0 - R - g0) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
         if ((s0 % SG == 0 || s0 == seq) && g0 < sc->n_score) launch_score_group(c, rt, *sc, g0, std::min(s0, sc->n_score) - g0, nullptr);
       }
+      if (em) {                                          // the chunk's pooled positions into the staging slice; a slice that is complete, or the text's last, is summed
+        const int p_first = em->pool == TGX_POOL_MEAN || em->pool == TGX_POOL_FIRST ? 0 : seq - 1, np = em->np(em->cur);
+        for (int p = s0 - R; p < s0; p++) {
+          const int q = p - p_first;                     // index among the pooled positions
+          if (q < 0 || q >= np) continue;
+          (void)hipMemcpyAsync(c->em_stage + (size_t)(q % EmbedCall::SLICE) * c->d.hidden, c->ch_x + (size_t)(p - (s0 - R)) * c->d.hidden, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
+          if ((q + 1) % EmbedCall::SLICE == 0 || q == np - 1) launch_embed_pool_stage(c, *em, em->cur, q / EmbedCall::SLICE, q % EmbedCall::SLICE + 1);
+        }
+      }
       if (s0 == seq) {                                   // the last position's hidden state feeds lm_head; publish token and length
         (void)hipMemcpyAsync(r.x, c->chunk[R - 1].x, (size_t)c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
         launch_add_pos(c, r.pos, seq);
-        launch_lm_head(c, b, 1);
+        if (!em) launch_lm_head(c, b, 1);
       }
     }
   }
@@ -1245,7 +1258,9 @@ static void launch_lm_head_rows(tgx_ctx* c, const std::vector<int>& rws) {
 }
 
 // sc (tgx_score_row; n == 1, may_join false): the pass also scores its positions (issue_pass)
-static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, bool may_join, ScoreCall* sc = nullptr) {
+// em (tgx_embed_rows; may_join true): the same groups, routes and passes WITHOUT any lm_head launch or lm_head staging; behind each pass the pooled partials of its texts,
+// behind the last the finish launch and the read-back (kernels/embed_pool.h).  The rows end in tgx_truncate_row's no-logits state
+static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, bool may_join, ScoreCall* sc = nullptr, EmbedCall* em = nullptr) {
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "forward before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
@@ -1271,6 +1286,16 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
   HIP_OK(c, hipSetDevice(c->device));
   const PrefillRoute sc_rt = prefill_route(c, lens[0], lens[0]);
   if (sc) if (int rc = score_prepare(c, sc, sc_rt, rows[0])) return rc;
+  if (em) {      // the pooled positions of every text and its rows of the partials (the workspace rows follow with the groups below)
+    em->n = n; em->slices = 0;
+    em->tab.assign((size_t)n * 4, 0);
+    for (int i = 0; i < n; i++) {
+      const int np = em->pool == TGX_POOL_MEAN ? lens[i] : 1;
+      em->tab[(size_t)i * 4 + 1] = np; em->tab[(size_t)i * 4 + 2] = em->slices;
+      em->slices += (np + EmbedCall::SLICE - 1) / EmbedCall::SLICE;
+    }
+    if (int rc = ensure_embed_ws(c, *em)) return rc;
+  }
   if (c->kv_paged) {
     for (int i = 0; i < n; i++) kv_release_row(c, rows[i]);
     for (int i = 0; i < n; i++) (void)kv_ensure_blocks(c, rows[i], lens[i]);     // cannot fail: counted above
@@ -1306,7 +1331,7 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
     const size_t o_ids = bytes;
     bytes += (size_t)total * 8;
     if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
-    if (int rc = ensure_rg_lm_ws(c)) return rc;
+    if (!em) if (int rc = ensure_rg_lm_ws(c)) return rc;
     host.assign(bytes, 0);
     std::memcpy(host.data() + o_ids, ids, (size_t)total * 8);
     for (int g = 0; g < n_groups; g++) {
@@ -1319,32 +1344,42 @@ static int admit_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids
   }
   for (int i = 0; i < n; i++)      // retired rows that rode along since their reset: position word back to 0
     if (c->row_host[(size_t)rows[i]].past != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)rows[i]].pos, 0, 4, c->stream)); c->row_host[(size_t)rows[i]].past = 0; }
+  if (em) {      // the workspace row of every text's first pooled position: behind its group's first row in a ragged pass, from row 0 in a one-row pass
+    for (int g = 0; g < n_groups; g++)
+      for (int i = g_begin[(size_t)g]; i < g_begin[(size_t)g + 1]; i++)
+        em->tab[(size_t)i * 4] = (passes[(size_t)g].n ? first[(size_t)i] : 0) + (em->pool == TGX_POOL_LAST ? lens[i] - 1 : 0);
+    if (int rc = embed_upload_table(c, *em)) return rc;
+  }
   std::vector<int> joint;             // prompts that went through a ragged pass: their lm_head comes below, four rows per pass over the weights
   for (int g = 0; g < n_groups; g++) {
     const RaggedPass& p = passes[(size_t)g];
     const int i0 = g_begin[(size_t)g], i1 = g_begin[(size_t)g + 1];
     if (p.n) {
       if (int rc = launch_route(c, route[(size_t)g], p.M, 0, 0, 0, /*past=*/0, &p)) return rc;
+      if (em) launch_embed_pool(c, *em, i0, i1 - i0);      // (the next group's pass overwrites ws_x)
       for (int i = i0; i < i1; i++) joint.push_back(i);
     } else
       for (int i = i0; i < i1; i++) {
         HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)rows[i]].prompt, ids + off[(size_t)i], (size_t)lens[i] * 8, hipMemcpyHostToDevice, c->stream));
-        if (int rc = issue_pass(c, rows[i], 1, lens[i], /*past=*/0, /*verify=*/false, sc)) return rc;
+        if (em) em->cur = i;
+        if (int rc = issue_pass(c, rows[i], 1, lens[i], /*past=*/0, /*verify=*/false, sc, em)) return rc;
       }
   }
   std::vector<int> joint_rows(joint.size());
   for (size_t k = 0; k < joint.size(); k++) joint_rows[k] = rows[joint[k]];
-  launch_lm_head_rows(c, joint_rows);
+  if (!em) launch_lm_head_rows(c, joint_rows);
   for (size_t k = 0; k < joint.size(); k++) launch_add_pos(c, c->rows[(size_t)rows[joint[k]]].pos, lens[joint[k]]);
   if (sc) if (int rc = score_read_back(c, sc)) return rc;
+  if (em) if (int rc = launch_embed_finish(c, *em)) return rc;
   if (int rc = finish_pass(c)) return rc;
   if (sc && sc->n_score >= 1) c->score_last_form = sc_rt == ROUTE_TILED ? 1 : 2;      // (a call of one position scored nothing: the option keeps its value)
   for (int i = 0; i < n; i++) {
     c->batch = std::max(c->batch, rows[i] + 1);
     row_admitted(c, rows[i], lens[i]);
+    if (em) c->row_host[(size_t)rows[i]].nologits = true;      // no lm_head ran: the slot's logits are not this sequence's (tgx_truncate_row's state)
   }
   refresh_longest(c);
-  c->have_logits = true;
+  if (!em) c->have_logits = true;
   return TGX_OK;
 }
 
@@ -1357,6 +1392,20 @@ int tgx_forward_row(tgx_ctx* c, int row, const int64_t* ids, int seq) {
 int tgx_forward_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens) {
   if (!c || !rows || !ids || !lens) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
   return admit_rows(c, n, rows, ids, lens, /*may_join=*/true);
+}
+
+// ---- tgx_embed_rows (include/tgx.h): tgx_forward_rows' admission and passes without lm_head, the pooled final-norm hidden state of every text behind them
+// (admit_rows' em form).  The call's own argument checks come first; release retires the rows as tgx_reset_row does, behind the pass in stream order
+int tgx_embed_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* ids, const int32_t* lens, const tgx_embed_cfg* cfg, float* out) {
+  if (!c || !rows || !ids || !lens || !cfg || !out) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (cfg->pool != TGX_POOL_LAST && cfg->pool != TGX_POOL_MEAN && cfg->pool != TGX_POOL_FIRST) return set_err(c, TGX_ERR_INVALID, "pool %d is none of TGX_POOL_LAST / MEAN / FIRST", cfg->pool);
+  if (cfg->dims < 0 || cfg->dims > c->d.hidden) return set_err(c, TGX_ERR_INVALID, "dims %d out of range [0,%d] (0: the hidden size)", cfg->dims, c->d.hidden);
+  EmbedCall em;
+  em.pool = cfg->pool; em.normalize = cfg->normalize != 0; em.dims = cfg->dims ? cfg->dims : c->d.hidden; em.host_out = out;
+  if (int rc = admit_rows(c, n, rows, ids, lens, /*may_join=*/true, nullptr, &em)) return rc;
+  if (cfg->release)
+    for (int i = 0; i < n; i++) if (int rc = tgx_reset_row(c, rows[i])) return rc;
+  return TGX_OK;
 }
 
 // ---- tgx_fork_row (include/tgx.h): dst_rows become copies of the live row src.  Paged cache: src's full blocks by reference (KvPool::share), one fresh block per
@@ -2659,6 +2708,7 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "advance.attn_tiles")) { *out_value = c->advance_attn_tiles; return TGX_OK; }
   if (!strcmp(key, "advance.last_form")) { *out_value = c->advance_last_form; return TGX_OK; }    // read-only: the form of the last tgx_advance_rows (0 none yet, 1 the joint pass, 2 piecewise)
   if (!strcmp(key, "advance.last_tiles")) { *out_value = c->advance_last_tiles; return TGX_OK; }  // read-only: the tile target of the last joint pass's attention (0: nothing split)
+  if (!strcmp(key, "embed.last_pool_launches")) { *out_value = c->embed_last_launches; return TGX_OK; }     // read-only: pooling launches (partials + finish) of the last tgx_embed_rows
   if (!strcmp(key, "score.last_form")) { *out_value = c->score_last_form; return TGX_OK; }     // read-only: the form of the last tgx_score_row that scored a position (0 none yet, 1 matrix cores, 2 by groups)
   if (!strcmp(key, "weights.packed")) { *out_value = c->weights_packed; return TGX_OK; }
   if (!strcmp(key, "weights.packed_classes")) { *out_value = c->packed_classes; return TGX_OK; }

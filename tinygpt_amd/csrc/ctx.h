@@ -7,7 +7,8 @@
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
-//   prefill.hip      batched MFMA prefill, 16-bit storage (kernels/prefill.h, gemm_dma.h); the device tables of a ragged pass
+//   prefill.hip      batched MFMA prefill, 16-bit storage (kernels/prefill.h, gemm_dma.h); the device tables of a ragged pass; the launches of tgx_score_row (kernels/score.h)
+//                    and tgx_embed_rows (kernels/embed_pool.h) behind a pass
 //   prefill_f32.hip  batched prefill, fp32 storage (kernels/gemm_f32.h)
 //   skinny.hip       batched decode step / short prompts on the skinny MFMA GEMMs (kernels/skinny*.h)
 // One context = one GPU = one HIP stream; every call comes from one host thread.  There is NO CPU path in this library.
@@ -111,6 +112,18 @@ struct ScoreCall {
   int top_n = 0, n_score = 0;
   const long long* ids = nullptr;                     // the pass's ids on the device (the row's prompt buffer)
   void* host = nullptr; size_t host_bytes = 0;        // where the call's read-back lands: lp [n] (| top ids | top lps)
+};
+
+// an embedding pass (tgx_embed_rows): the pass issues no lm_head; behind it the pooled final-norm hidden state of every text (kernels/embed_pool.h)
+struct EmbedCall {
+  static constexpr int SLICE = 32;                    // == tgx::EMB_SLICE: pooled positions per row of the partials
+  int pool = 0, normalize = 0, dims = 0;              // dims: resolved (hidden when the caller passed 0)
+  int n = 0;                                          // texts of the call
+  int cur = 0;                                        // the text a one-row pass carries (issue_pass)
+  std::vector<int> tab;                               // host image of the device table, [n] x tgx::EmbedText {row0, np, slice0, pad}: ONE upload ahead of the passes
+  int slices = 0;                                     // rows of the partials of the whole call
+  float* host_out = nullptr;                          // where the read-back lands: [n][dims]
+  int np(int t) const { return tab[(size_t)t * 4 + 1]; }
 };
 
 namespace tgx { struct RgSeq; struct RgItem; struct MixItem; }
@@ -378,6 +391,13 @@ struct tgx_ctx {
   unsigned char* sc_part = nullptr; size_t sc_part_bytes = 0;        // one group's tile sums | keys | maxima | target values, laid out for sc_part_rows rows
   int sc_part_rows = 0;
   unsigned char* sc_out = nullptr; size_t sc_out_bytes = 0;          // the call's lp [n] | top ids [n][TGX_MAX_LOGPROBS] | top lps: one read-back
+  // ---- tgx_embed_rows (include/tgx.h; kernels/embed_pool.h).  Allocated by the first call (a context that never embeds holds none of it), grown to the largest call:
+  // em_buf = the call's text table | out [n][dims] | partials [slices][H] (one row per EMB_SLICE pooled positions: never [M][H]); em_stage = the [EMB_SLICE][H] staging
+  // slice of prefill by steps.  embed.last_pool_launches (read-only option): pooling launches of the last call (partials + finish)
+  unsigned char* em_buf = nullptr; size_t em_bytes = 0;
+  float* em_stage = nullptr; size_t em_stage_bytes = 0;
+  size_t em_off_out = 0, em_off_part = 0;             // byte offsets of the last call's sections in em_buf
+  int embed_last_launches = 0;
   // ---- per-row logit processors (include/tgx.h tgx_set_row_penalties / tgx_set_row_logit_bias / tgx_set_row_history; kernels/logit_proc.h).  Allocated by the first
   // non-neutral setting or non-empty history (proc_alloc): a context that never asks holds none of it and runs the launches it ran before
   unsigned int* proc_hist = nullptr;         // [max_batch][vocab] history words: bit 31 "in the prompt", bits 0 .. 30 times produced
@@ -517,6 +537,13 @@ int ensure_score_ws(tgx_ctx* c, int seq, bool tiled);          // tgx_score_row:
 void launch_score_tiles(tgx_ctx* c, const ScoreCall& sc, const float* logits, long long stride, int col0, int width, int R, int pos0);   // the tile launch over [R][width] logits = entries [col0, col0 + width) of positions pos0 ..
 void launch_score_record(tgx_ctx* c, const ScoreCall& sc, int R, int pos0);                                                           // ... the group's records, behind the tile launches of the whole vocabulary
 void launch_score_tiled(tgx_ctx* c, const ScoreCall& sc);      // the matrix-core form over ws_x behind launch_prefill
+// tgx_embed_rows (kernels/embed_pool.h): the call's workspace before anything changes; the table upload ahead of the passes; the partials of texts [t0, t0 + nt) of
+// a pass over ws_x (ONE launch); one slice of text t from the staging slice (prefill by steps); the finish launch over all texts and the read-back, behind the passes
+int ensure_embed_ws(tgx_ctx* c, EmbedCall& em);
+int embed_upload_table(tgx_ctx* c, const EmbedCall& em);
+void launch_embed_pool(tgx_ctx* c, const EmbedCall& em, int t0, int nt);
+void launch_embed_pool_stage(tgx_ctx* c, const EmbedCall& em, int t, int slice, int cnt);
+int launch_embed_finish(tgx_ctx* c, const EmbedCall& em);
 int extend_attn_splits(const tgx_ctx* c, int S, int past);   // key splits of a continuation pass's attention (0: the per-row prompt attention)
 int ensure_extend_ws(tgx_ctx* c, int S, int past);           // ... and their partials' workspace, before the pass is issued
 // tgx_verify_rows: the key splits of a ragged continuation pass (p.n sequences, p.past set) by option extend.attn_splits -> p.ext_ns, and the partials' workspace

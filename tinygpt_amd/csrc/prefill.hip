@@ -11,6 +11,7 @@
 #include "attn_worklist.h"
 #include "kernels/gemm_f32.h"
 #include "kernels/score.h"
+#include "kernels/embed_pool.h"
 
 bool prefill_shapes_ok(const tgx_model_desc& d) {
   return d.hidden % 64 == 0 && (d.heads * d.head_dim) % 64 == 0 && d.inter % 64 == 0;
@@ -798,5 +799,59 @@ int prefill_set_attrs(tgx_ctx* c) {
 #undef TGX_DMA_ATTR_D
 #undef TGX_DMA_ATTR
 #undef TGX_DMA_ATTR1
+  return TGX_OK;
+}
+
+// ---- tgx_embed_rows (include/tgx.h; kernels/embed_pool.h): the pooled final-norm hidden state of every text behind its prompt pass.
+// Workspace, all of it through dev_grow: em_buf = the text table | out [n][dims] | partials [slices][H]; em_stage = one slice of rows for prefill by steps
+int ensure_embed_ws(tgx_ctx* c, EmbedCall& em) {
+  const size_t H = (size_t)c->d.hidden, al = 32;
+  const size_t tab = ((size_t)em.n * sizeof(tgx::EmbedText) + al - 1) / al * al, out = ((size_t)em.n * (size_t)em.dims * 4 + al - 1) / al * al;
+  if (int rc = dev_grow(c, &c->em_buf, &c->em_bytes, tab + out + (size_t)em.slices * H * 4)) return rc;
+  if (int rc = dev_grow(c, &c->em_stage, &c->em_stage_bytes, (size_t)tgx::EMB_SLICE * H * 4)) return rc;
+  c->em_off_out = tab; c->em_off_part = tab + out;
+  c->embed_last_launches = 0;
+  return TGX_OK;
+}
+int embed_upload_table(tgx_ctx* c, const EmbedCall& em) {
+  static_assert(sizeof(tgx::EmbedText) == 16, "EmbedCall::tab holds four ints per text");
+  static_assert(EmbedCall::SLICE == tgx::EMB_SLICE, "the host lays the partials out by the kernel's slice");
+  HIP_OK(c, hipMemcpyAsync(c->em_buf, em.tab.data(), (size_t)em.n * sizeof(tgx::EmbedText), hipMemcpyHostToDevice, c->stream));
+  return TGX_OK;
+}
+static tgx::EmbedPoolArgs embed_pool_args(tgx_ctx* c, int t0) {
+  tgx::EmbedPoolArgs a{};
+  a.x = c->ws_x; a.tab = reinterpret_cast<const tgx::EmbedText*>(c->em_buf); a.part = reinterpret_cast<float*>(c->em_buf + c->em_off_part);
+  a.norm_w = c->final_norm; a.norm_b = c->gpt2 ? c->final_norm_b : nullptr; a.eps = c->d.norm_eps; a.H = c->d.hidden;
+  a.act16 = c->act16 && c->dt != tgx::DT_F32 ? 1 : 0;
+  a.t0 = t0; a.stage_slice = -1; a.stage_cnt = 0;
+  return a;
+}
+static void launch_embed_pool_grid(tgx_ctx* c, const tgx::EmbedPoolArgs& a, dim3 grid) {
+  if (c->gpt2) { TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::embed_pool_kernel<DT, 1>), grid, dim3(tgx::EMB_WG), 0, c->stream, a)) }
+  else { TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL((tgx::embed_pool_kernel<DT, 0>), grid, dim3(tgx::EMB_WG), 0, c->stream, a)) }
+  c->embed_last_launches++;
+}
+void launch_embed_pool(tgx_ctx* c, const EmbedCall& em, int t0, int nt) {
+  if (!c->em_buf || !c->ws_x || t0 < 0 || nt < 1 || t0 + nt > em.n) { c->launch_fault = "embed: a pass the workspace was not sized for"; return; }
+  int most = 1;
+  for (int t = t0; t < t0 + nt; t++) most = std::max(most, em.np(t));
+  launch_embed_pool_grid(c, embed_pool_args(c, t0), dim3((unsigned)((most + tgx::EMB_SLICE - 1) / tgx::EMB_SLICE), (unsigned)nt));
+}
+void launch_embed_pool_stage(tgx_ctx* c, const EmbedCall& em, int t, int slice, int cnt) {
+  if (!c->em_buf || !c->em_stage || t < 0 || t >= em.n || cnt < 1 || cnt > tgx::EMB_SLICE || slice < 0 || slice * tgx::EMB_SLICE + cnt > em.np(t)) {
+    c->launch_fault = "embed: a slice the workspace was not sized for"; return;
+  }
+  tgx::EmbedPoolArgs a = embed_pool_args(c, t);
+  a.x = c->em_stage; a.stage_slice = slice; a.stage_cnt = cnt;
+  launch_embed_pool_grid(c, a, dim3(1, 1));
+}
+int launch_embed_finish(tgx_ctx* c, const EmbedCall& em) {
+  tgx::EmbedFinishArgs a{};
+  a.tab = reinterpret_cast<const tgx::EmbedText*>(c->em_buf); a.part = reinterpret_cast<const float*>(c->em_buf + c->em_off_part);
+  a.out = reinterpret_cast<float*>(c->em_buf + c->em_off_out); a.H = c->d.hidden; a.dims = em.dims; a.normalize = em.normalize;
+  hipLaunchKernelGGL(tgx::embed_finish_kernel, dim3((unsigned)em.n), dim3(tgx::EMB_WG), 0, c->stream, a);
+  c->embed_last_launches++;
+  HIP_OK(c, hipMemcpyAsync(em.host_out, a.out, (size_t)em.n * (size_t)em.dims * 4, hipMemcpyDeviceToHost, c->stream));
   return TGX_OK;
 }

@@ -58,6 +58,14 @@ ADV_STEP, ADV_FEED, ADV_FEED_MORE = 0, 1, 2      # TGX_ADV_*: the kinds of tgx_a
 MAX_ADVANCE_POSITIONS = 8192                     # TGX_MAX_ADVANCE_POSITIONS
 
 
+POOL_MODES = {"last": 0, "mean": 1, "first": 2}      # TGX_POOL_*
+
+
+class EmbedCfg(ctypes.Structure):
+    """tgx_embed_cfg"""
+    _fields_ = [("pool", c_int32), ("normalize", c_int32), ("dims", c_int32), ("release", c_int32)]
+
+
 class TgxError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {msg}")
@@ -82,6 +90,7 @@ ABI = {
     "reset_row": (c_int, [c_void_p, c_int]),
     "forward_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "forward_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
+    "embed_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(EmbedCfg), POINTER(c_float)]),
     "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
     "extend_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "truncate_row": (c_int, [c_void_p, c_int, c_int64]),
@@ -297,6 +306,23 @@ class Model:
         if len(rows):
             self.batch = max(self.batch, int(rows.max()) + 1)
         return self
+
+    def embed_rows(self, rows, prompts, pool="last", normalize=True, dims=0, release=False) -> np.ndarray:
+        """the pooled final-norm hidden state of prompts[i], prefilled into rows[i] in ONE pass without lm_head (include/tgx.h tgx_embed_rows): float32
+        [n][dims or hidden].  release=False leaves the rows holding their positions without logits; release=True retires them"""
+        rows = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int32).reshape(-1))
+        ps = [np.asarray(p, dtype=np.int64).reshape(-1) for p in prompts]
+        assert len(ps) == len(rows), "one prompt per row"
+        lens = np.ascontiguousarray(np.array([len(p) for p in ps], dtype=np.int32))
+        ids = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(1, dtype=np.int64))
+        cfg = EmbedCfg(POOL_MODES[pool] if isinstance(pool, str) else int(pool), int(bool(normalize)), int(dims), int(bool(release)))
+        width = int(dims) if 0 < int(dims) else self.desc.hidden
+        out = np.zeros((max(len(rows), 1), max(width, 1)), dtype=np.float32)
+        self._check(self.be.embed_rows(self._ctx, len(rows), rows.ctypes.data_as(POINTER(c_int32)), ids.ctypes.data_as(POINTER(c_int64)),
+                                       lens.ctypes.data_as(POINTER(c_int32)), ctypes.byref(cfg), out.ctypes.data_as(POINTER(c_float))))
+        if len(rows):
+            self.batch = max(self.batch, int(rows.max()) + 1)
+        return out[:len(rows), :width]
 
     def fork_row(self, src: int, dst_rows):
         """make every row of dst_rows (retired rows or the next free ones) a copy of the live row `src` (include/tgx.h tgx_fork_row): same length, cache, logits and

@@ -237,6 +237,53 @@ ScoreOutput GPTEngine::score(const std::string& text, int topN) {
   return score(tokenizer_.encode(text, true), topN);
 }
 
+// ---- GPTEngine::embed (include/tgx.h tgx_embed_rows): the texts in calls of at most max_batch rows of an empty cache, every call releasing its rows
+EmbedOutput GPTEngine::embed(const std::vector<std::vector<int32_t>>& ids, const EmbedConfig& cfg) {
+  EmbedOutput out;
+  // ---- every check before anything changes
+  if (!prepared_ || ids.empty()) { fail("embed: engine not prepared or no text"); return out; }
+  if (!be_.embed_rows) { fail("embed: the device shim lacks tgx_embed_rows"); return out; }
+  const tgx_model_desc& d = desc();
+  if (cfg.pool != TGX_POOL_LAST && cfg.pool != TGX_POOL_MEAN && cfg.pool != TGX_POOL_FIRST) { fail("embed: pool is none of last / mean / first"); return out; }
+  if (cfg.dims < 0 || cfg.dims > d.hidden) { fail("embed: dims outside [0, " + std::to_string(d.hidden) + "]"); return out; }
+  for (const auto& t : ids) if (t.empty()) { fail("embed: an empty text"); return out; }
+  if (!cached_.empty()) { fail("embed: the engine holds a conversation in row 0 (prefix reuse) that the call's rows would collide with"); return out; }
+  const int dims = cfg.dims ? cfg.dims : d.hidden, B = std::max(1, (int)d.max_batch);
+  const tgx_embed_cfg ec{cfg.pool, cfg.normalize ? 1 : 0, cfg.dims, /*release=*/1};
+  out.dims = dims;
+  out.vectors.assign(ids.size() * (size_t)dims, 0.f);
+  out.dropped.assign(ids.size(), 0);
+  be_.reset_cache(model_.ctx);
+  lastReused_ = 0;
+  bool ok = true;
+  for (size_t t0 = 0; t0 < ids.size() && ok; t0 += (size_t)B) {
+    const int n = (int)std::min<size_t>((size_t)B, ids.size() - t0);
+    std::vector<int32_t> rows((size_t)n), lens((size_t)n);
+    std::vector<int64_t> flat;
+    for (int i = 0; i < n; i++) {
+      const std::vector<int32_t>& t = ids[t0 + (size_t)i];
+      const size_t keep = (size_t)std::min<int64_t>((int64_t)t.size(), contextSize());      // beyond the context: the tail, like a prompt
+      out.dropped[t0 + (size_t)i] = (int64_t)(t.size() - keep);
+      rows[(size_t)i] = i; lens[(size_t)i] = (int32_t)keep;
+      flat.insert(flat.end(), t.end() - (std::ptrdiff_t)keep, t.end());
+    }
+    const int rc = be_.embed_rows(model_.ctx, n, rows.data(), flat.data(), lens.data(), &ec, out.vectors.data() + t0 * (size_t)dims);
+    if (rc != TGX_OK) { fail(std::string("embed_rows: ") + be_.last_error(model_.ctx)); ok = false; }
+    else out.calls++;
+  }
+  be_.reset_cache(model_.ctx);      // as reconfigure leaves it: the next generate call prefills from an empty cache
+  if (!ok) { out.vectors.clear(); out.dropped.clear(); out.calls = 0; return out; }
+  out.ok = true;
+  return out;
+}
+
+EmbedOutput GPTEngine::embed(const std::vector<std::string>& texts, const EmbedConfig& cfg) {
+  if (!tokenizerOk_) { fail("embed: no tokenizer loaded (tokenizerDir / modelDir must hold tokenizer.json)"); return EmbedOutput{}; }
+  std::vector<std::vector<int32_t>> ids;
+  for (const std::string& t : texts) ids.push_back(tokenizer_.encode(t, true));
+  return embed(ids, cfg);
+}
+
 // ---- GPTConfig::speculate: prompt-lookup drafts verified in one pass (spec_draft.h, include/tgx.h tgx_verify_row)
 // (which of the two, or neither: spec_mode.h)
 static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int batch, bool processors, size_t stopIds) {

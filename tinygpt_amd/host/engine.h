@@ -127,6 +127,20 @@ struct ScoreOutput {
   double perplexity() const;         // exp(-mean logprob); 0 with nothing scored
 };
 
+// GPTEngine::embed: how the final hidden states of a text become one vector (include/tgx.h tgx_embed_rows) and what comes back
+struct EmbedConfig {
+  int pool = TGX_POOL_LAST;          // TGX_POOL_LAST / TGX_POOL_MEAN / TGX_POOL_FIRST
+  bool normalize = true;             // divide by the L2 norm
+  int dims = 0;                      // 0: the hidden size; else keep the first dims components (before normalisation)
+};
+struct EmbedOutput {
+  bool ok = false;
+  int dims = 0;                      // components per vector
+  int64_t calls = 0;                 // tgx_embed_rows calls the texts were batched into
+  std::vector<float> vectors;        // [texts][dims]
+  std::vector<int64_t> dropped;      // per text: tokens ahead of the tail that was embedded (a text beyond contextSize keeps its tail, like a prompt)
+};
+
 using GenerateCallback = std::function<bool(int32_t tokenId)>;   // return false to abort (GPTEngine.cpp:208-213)
 using TextCallback = std::function<bool(const std::string& chunk)>;   // the reference's GenerateCallback: complete UTF-8 only
 
@@ -149,6 +163,12 @@ class GPTEngine {
   // without tgx_score_row, topN outside [0, TGX_MAX_LOGPROBS], an empty sequence, no tokenizer for the text form, or a failed call
   ScoreOutput score(const std::vector<int32_t>& ids, int topN = 0);
   ScoreOutput score(const std::string& text, int topN = 0);
+  // Not in the reference: one vector per text — the pooled final-norm hidden state (include/tgx.h tgx_embed_rows), no lm_head.  The texts go through calls of at most
+  // max_batch rows of an empty cache, each releasing its rows, and the cache is left empty; generates nothing.  ok == false (lastError set), NOTHING changed: a backend
+  // without tgx_embed_rows, no text or an empty one, a bad pool or dims, no tokenizer for the text form, or an engine that holds a conversation in row 0 (prefix reuse:
+  // the rows of the call would collide with it — setReusePrefix(false) or a generate call without reuse first).  A failed device call leaves the cache empty
+  EmbedOutput embed(const std::vector<std::vector<int32_t>>& ids, const EmbedConfig& cfg = {});
+  EmbedOutput embed(const std::vector<std::string>& texts, const EmbedConfig& cfg = {});
   // Not in the reference: the conversation row 0's cache holds (GPTConfig::reusePrefix), kept across processes.  saveSession writes a small header (magic "TGXSESS\0",
   // u32 version 1, u32 count, the count cached token ids as i32, u64 snapshot bytes) followed by row 0's snapshot (include/tgx.h tgx_save_row) WITHOUT its hidden row,
   // logits and token (csrc/row_snapshot.h drop_logits, on the host): the next turn extends the row and computes its own, and 4 * (hidden + vocab) bytes stay out of the

@@ -121,6 +121,24 @@ TGXE_API int tgxe_score_text(tgxe_engine* h, const char* text, int top_n, int32_
   if (out_top_lp) memcpy(out_top_lp, r.topLogprobValues.data(), r.topLogprobValues.size() * 4);
   return 0;
 }
+// embeddings (GPTEngine::embed; include/tgx.h tgx_embed_rows): n texts, their ids back to back with lens[i] each; out [n][dims ? dims : hidden].  pool: TGX_POOL_*.
+// Returns 0, or 1 when the call failed (tgxe_last_error); out_calls (may be NULL): the tgx_embed_rows calls the texts were batched into
+TGXE_API int tgxe_embed(tgxe_engine* h, int n, const int32_t* ids, const int32_t* lens, int pool, int normalize, int dims, float* out, int64_t* out_calls) {
+  if (!h || !ids || !lens || !out || n < 1) return 1;
+  std::vector<std::vector<int32_t>> texts;
+  for (int i = 0; i < n; i++) {
+    const int len = lens[i] > 0 ? lens[i] : 0;
+    texts.emplace_back(ids, ids + len);
+    ids += len;
+  }
+  tgxh::EmbedConfig cfg;
+  cfg.pool = pool; cfg.normalize = normalize != 0; cfg.dims = dims;
+  const tgxh::EmbedOutput r = h->e->embed(texts, cfg);
+  if (!r.ok) return 1;
+  memcpy(out, r.vectors.data(), r.vectors.size() * 4);
+  if (out_calls) *out_calls = r.calls;
+  return 0;
+}
 // SamplerConfig's penalties and logit bias (neutral: 1, 0, 0 and n = 0); kept across tgxe_reconfigure until set again
 TGXE_API void tgxe_set_processors(tgxe_engine* h, float repetition, float presence, float frequency, const int32_t* bias_ids, const float* bias, int n) {
   if (!h) return;

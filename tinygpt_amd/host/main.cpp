@@ -39,6 +39,12 @@ static void usage(const char* prog) {
           "  --score                   generate nothing: print the log-probability of every prompt token but the first (position id lp, %%.9g; with --logprobs n the n most\n"
           "                            likely alternatives as id:lp) and the prompt's perplexity, one prefill pass per prompt; of a prompt\n"
           "                            longer than the context the last contextSize tokens are scored (positions count from the prompt's start)\n"
+          "  --embed                   generate nothing: print one JSON array per prompt, its embedding (the pooled final hidden state, no lm_head; %%.9g); the prompts\n"
+          "                            share ragged passes of up to four rows (or as many as there are prompts); of a prompt longer than the context the last\n"
+          "                            contextSize tokens are embedded\n"
+          "  --pool <last|mean|first>  with --embed: the position(s) pooled (default: last)\n"
+          "  --embed-dims <n>          with --embed: keep the first n components before normalisation (default: 0 = the hidden size)\n"
+          "  --no-normalize            with --embed: do not divide by the L2 norm\n"
           "  --repetition-penalty <r> --presence-penalty <p> --frequency-penalty <f>\n"
           "                            penalties over each row's prompt and produced tokens, applied to the logits on the device (default: 1 0 0 = off)\n"
           "  --logit-bias <id:val,...> added to those ids' logits; -inf bans an id (at most 320 ids; default: none)\n"
@@ -99,7 +105,8 @@ int main(int argc, char** argv) {
   std::vector<int32_t> stop_ids;
   long pad_id = -1;
   std::vector<std::string> text_prompts;
-  bool stream = false, score = false;
+  bool stream = false, score = false, embed = false;
+  tgxh::EmbedConfig embed_cfg;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -118,6 +125,22 @@ int main(int argc, char** argv) {
     else if (a == "--tokenizer") cfg.tokenizerDir = next();
     else if (a == "--stream") stream = true;
     else if (a == "--score") score = true;
+    else if (a == "--embed") embed = true;
+    else if (a == "--pool") {
+      const std::string v = next();
+      if (v == "last") embed_cfg.pool = TGX_POOL_LAST;
+      else if (v == "mean") embed_cfg.pool = TGX_POOL_MEAN;
+      else if (v == "first") embed_cfg.pool = TGX_POOL_FIRST;
+      else { fprintf(stderr, "--pool: expected last, mean or first, got '%s'\n", v.c_str()); return 1; }
+    }
+    else if (a == "--embed-dims") {
+      const std::string v = next();
+      char* end = nullptr;
+      const long n = strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end != '\0' || n < 0 || n > 0x7fffffffL) { fprintf(stderr, "--embed-dims: expected a component count, got '%s'\n", v.c_str()); return 1; }
+      embed_cfg.dims = (int)n;
+    }
+    else if (a == "--no-normalize") embed_cfg.normalize = false;
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
@@ -176,8 +199,10 @@ int main(int argc, char** argv) {
 
   const int score_top = std::max(0, cfg.logprobs);
   if (score) cfg.logprobs = -1;      // (--logprobs n names the alternatives of --score: nothing is generated, nothing recorded)
+  if (embed && (score || stream)) { fprintf(stderr, "Error: --embed does not combine with --score or --stream (nothing is generated)\n"); return 1; }
+  if (embed) cfg.logprobs = -1;
   const bool session = !session_load.empty() || !session_save.empty();
-  if (session && (!stream || score || !prompt_ids.empty() || text_prompts.size() != 1)) {
+  if (session && (!stream || score || embed || !prompt_ids.empty() || text_prompts.size() != 1)) {
     fprintf(stderr, "Error: --session-load / --session-save need --stream and exactly one --prompt (the single-prompt streaming path keeps row 0's cache)\n");
     return 1;
   }
@@ -192,6 +217,20 @@ int main(int argc, char** argv) {
   if (session && !engine.hasTokenizer()) { fprintf(stderr, "Error: --session-load / --session-save need a tokenizer (--model or --tokenizer)\n"); return 1; }
   if (!session_load.empty() && !engine.loadSession(session_load)) fprintf(stderr, "session not loaded, starting from an empty cache: %s\n", engine.lastError().c_str());
 
+  if (embed) {      // one JSON array per prompt, in prompt order
+    const bool texts = engine.hasTokenizer() && prompt_ids.empty();
+    if (texts && text_prompts.empty()) text_prompts = kInputStrs;
+    if (!texts) for (auto& p : prompts) for (auto& t : p) if (t >= engine.desc().vocab) t = t % engine.desc().vocab;
+    const tgxh::EmbedOutput r = texts ? engine.embed(text_prompts, embed_cfg) : engine.embed(prompts, embed_cfg);
+    if (!r.ok) { fprintf(stderr, "embed failed: %s\n", engine.lastError().c_str()); return 1; }
+    const size_t n = r.vectors.size() / (size_t)r.dims;
+    for (size_t b = 0; b < n; b++) {
+      printf("[");
+      for (int k = 0; k < r.dims; k++) printf(k ? ", %.9g" : "%.9g", (double)r.vectors[b * (size_t)r.dims + (size_t)k]);
+      printf("]\n");
+    }
+    return 0;
+  }
   if (score) {
     const bool texts = engine.hasTokenizer() && prompt_ids.empty();
     if (texts && text_prompts.empty()) text_prompts = kInputStrs;
