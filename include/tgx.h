@@ -30,6 +30,7 @@ extern "C" {
 /* (round 7, still 3: additive) per-row sampler settings and device-side stop — tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows. */
 /* (still 3: additive) tgx_forward_rows; tgx_fork_row — a live row copied into other rows, its full paged KV blocks shared by reference. */
 /* (still 3: additive) tgx_extend_row / tgx_truncate_row — a live row grows by several positions in one pass, or is rolled back: prefix reuse without a second prefill. */
+/* (still 3: additive) tgx_splice_row — ranges cut out of the middle of a live row's cache, the keys behind them re-rotated: context shift without a second prefill. */
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
 /* (still 3: additive) tgx_verify_row_sampled — the same under the row's own sampler: exact by the draw identity; tgx_read_pass_logits — the pass's logits (diagnostic). */
 /* (still 3: additive) tgx_verify_rows — the drafts of several rows verified in ONE joint pass and ONE accept launch; n_draft 0 rows step along. */
@@ -307,6 +308,58 @@ TGX_API int tgx_extend_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
  * siblings, the next append would write into a shared block: the row takes one fresh block, rows [0, new_len % 128) of every layer and both caches are copied into
  * it in one launch, the table entry is swapped and the shared block loses this row's reference.  With no free block that is TGX_ERR_CONTEXT and nothing changes. */
 TGX_API int tgx_truncate_row(tgx_ctx* ctx, int row, int64_t new_len);
+
+/* ---- cutting ranges out of a live row (additive to ABI 3) ----------------------------------------------------------------------------------------------
+ * Generation past the context ("context shift": keep the first positions, drop half of the rest, slide the tail down), a tool result or a retrieved document
+ * dropped from the middle of a long chat, "sinks + a recent window" of a stream, blocks of a paged cache freed from a long row: positions taken out of the MIDDLE of
+ * a row's cache without tgx_reset_row and a second prefill of what remains.  The row's new sequence is the concatenation of the kept ranges
+ * [starts[i], starts[i] + lens[i]), i < n_keep: sorted, non-empty, inside [0, past), disjoint (they may touch).  A kept position s of range i ends at
+ * d = s - delta_i, delta_i = starts[i] - sum(lens[0 .. i)); new_len = sum(lens) >= 1 is written to *out_len (may be NULL).
+ *
+ *   What moves        for every layer and kv head: V'[d] = V[s] bit for bit; K'[d] = K[s] bit for bit where delta == 0.  Otherwise — every key is stored post-RoPE
+ *                     at the position it was appended at — the pair (K[s][p], K[s][p + hd/2]) is rotated by the angle table(d) - table(s): with
+ *                     (c_o, s_o) = rope_cos / rope_sin[s][p] and (c_n, s_n) = rope_cos / rope_sin[d][p],
+ *                       c = fmaf(c_n, c_o, __fmul_rn(s_n, s_o)),  s = fmaf(s_n, c_o, -__fmul_rn(c_n, s_o)),
+ *                     then the rotation every append site uses (x0' = fmaf(x0, c, -__fmul_rn(x1, s)), x1' = fmaf(x1, c, __fmul_rn(x0, s))) on the stored values
+ *                     converted to fp32, rounded once to the storage dtype.  Both table rows are used, not the row of delta: the tables hold
+ *                     cosf(fl32(inv * pos)), whose angles are not additive at large positions.  The key is then what the append kernels would have written at d,
+ *                     up to one more storage rounding.
+ *   Accepted rows     tgx_truncate_row's: a live or finished row < batch that holds past >= 1 positions, in any of its three states (logits and a current token,
+ *                     logits only, no logits).  A finished state is cleared.
+ *   Refused           a null pointer, row outside [0, max_batch), n_keep outside [1, TGX_MAX_SPLICE_RANGES], a range that is empty, unsorted, overlapping or outside
+ *                     [0, past): TGX_ERR_INVALID.  A retired or empty row, row >= batch, a poisoned context, a call before tgx_finalize: TGX_ERR_STATE.  GPT-2:
+ *                     TGX_ERR_UNSUPPORTED (its positions are learned and added to the hidden state: there is nothing to re-rotate).  A cache row of head_dim *
+ *                     element size bytes that is no multiple of 4 (or whose half is none): TGX_ERR_UNSUPPORTED, as for tgx_fork_row.
+ *   ALL OR NOTHING    a refused call changes no row, moves no KV block, leaves kv.free_tokens as it was and does not poison the context.
+ *   No-op             one range [0, past) on a row whose logits are in place returns TGX_OK and changes nothing; one range [0, L), L < past, IS
+ *                     tgx_truncate_row(row, L): the same bits, the same block accounting.
+ *   Afterwards        the row holds new_len positions and is in tgx_truncate_row's state "no logits, no current token": tgx_sample_row, the decode calls and
+ *                     tgx_fork_row return TGX_ERR_STATE until tgx_extend_row has run on it.  The current token is NOT in the cache and is discarded, as
+ *                     tgx_extend_row discards it: a caller that goes on generating passes it as ids[0] of the next tgx_extend_row (which starts the
+ *                     produced-token count afresh: restate the stop with the remaining max_new).  Settings, history words, automaton id / state and the logprob
+ *                     count are kept, as tgx_truncate_row keeps them.  tgx_past_length is refreshed.  Rows not named keep their state bit for bit.  The call
+ *                     is stream-ordered behind the steps already enqueued and does not synchronise (a first call that allocates or grows the staging buffer
+ *                     does).
+ *   Sampling          a sampled row's draw key hashes the POSITION of the produced token (seed, position, row): after a splice positions repeat, so a row that
+ *                     is shifted and sampled with the same seed draws position p's variate again the second time it reaches p.
+ *   Paged KV          f = the first position whose content changes: the end of the leading delta == 0 range (0 without one; new_len for a truncation).  Blocks
+ *                     with index < f / 128 are untouched and may stay shared with forked rows; every block from f / 128 to ceil(new_len / 128) - 1 is written.
+ *                     A written block that forked siblings map as well is swapped for a fresh block before anything writes to it (copy on write); if
+ *                     f % 128 != 0, rows [0, f % 128) of the first one are carried over, as tgx_truncate_row carries them.  The fresh blocks are counted against
+ *                     the FREE LIST ALONE before anything is assigned — the blocks the row gives back are not counted, the sum errs towards refusing — and a
+ *                     shortfall is TGX_ERR_CONTEXT.  Blocks beyond ceil(new_len / 128) lose this row's reference.  Afterwards kv.free_tokens is what a row of
+ *                     new_len leaves, minus the fresh blocks taken; a shared block is still full for every row that maps it.
+ *   Staging           the move overlaps itself (one position's destination is another's source), so it runs through the snapshot staging buffer (option
+ *                     snapshot.stage_kib caps it; one layer is always staged) in groups of whole layers: per group one gather launch (reads through the old
+ *                     block table, rotates K, copies V) and one scatter launch (writes through the new one); kernels/kv_splice.h.  The buffer is allocated by the
+ *                     first call that needs it: a context that never splices allocates nothing new and runs the launches it ran before.
+ *   Cost              measured (profiles/splice_row.txt, tools/admit_bench.py --splice; Llama-3.2-1B bf16, one synchronised call, median of 10): 2048 -> 4 + 1024
+ *                     positions (32 MiB moved) 0.07 ms on slabs / 0.08 ms paged, 8192 -> 4 + 4096 (128 MiB) 0.17 / 0.17 ms, against 6.4 and 22.5 ms for
+ *                     tgx_reset_row + tgx_forward_row of the kept tokens: about 0.01 of the re-prefill at both shapes.  With the one-token tgx_extend_row that
+ *                     re-feeds the current token (0.75 - 0.77 ms, the larger part of a shift) 0.13 and 0.04 of it.  Two launches per group of layers, plus,
+ *                     paged, three small table launches and the tail copy of a copy on write. */
+#define TGX_MAX_SPLICE_RANGES 16
+TGX_API int tgx_splice_row(tgx_ctx* ctx, int row, int n_keep, const int64_t* starts, const int64_t* lens, int64_t* out_len);
 
 /* ---- row snapshots: a live row saved to host memory and restored anywhere (additive to ABI 3) ---------------------------------------------------------------
  * Everything above keeps a sequence in device memory from admission to retirement.  A snapshot moves one off the device and back: swap-out when a paged cache has no

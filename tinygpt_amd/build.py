@@ -28,7 +28,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h")]
+            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -97,6 +97,13 @@ def _build_cpu_check(name, header, force, verbose):
 def build_kv_pool_check(force: bool = False, verbose: bool = False):
     """tests/kv_pool_check.cpp, the CPU audit of csrc/kv_pool.h."""
     return _build_cpu_check("kv_pool_check", os.path.join(CSRC, "kv_pool.h"), force, verbose)
+
+
+def build_splice_plan_check(force: bool = False, verbose: bool = False):
+    """tests/splice_plan_check.cpp, the CPU audit of csrc/splice_plan.h (and of the KvPool calls tgx_splice_row makes)."""
+    if _stale(os.path.join(TEST_BUILD, "splice_plan_check"), [os.path.join(CSRC, "kv_pool.h")]):
+        force = True
+    return _build_cpu_check("splice_plan_check", os.path.join(CSRC, "splice_plan.h"), force, verbose)
 
 
 def build_dev_mem_check(force: bool = False, verbose: bool = False):

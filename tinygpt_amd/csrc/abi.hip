@@ -8,7 +8,9 @@
 #include "ctx.h"
 #include "kernels/kv_fork.h"
 #include "kernels/kv_pack.h"
+#include "kernels/kv_splice.h"
 #include "row_snapshot.h"
+#include "splice_plan.h"
 #include "automaton.h"
 
 static std::string g_create_err;
@@ -310,17 +312,20 @@ struct KvTblUpdateWide { int n; int idx[240]; int val[240]; };
 static __global__ void kv_tbl_set_wide_kernel(int* tbl, KvTblUpdateWide u) { if ((int)threadIdx.x < u.n) tbl[u.idx[threadIdx.x]] = u.val[threadIdx.x]; }
 
 template <typename U>
-static void kv_tbl_push_by(tgx_ctx* c, const KvPool::Changes& changes, void (*kernel)(int*, U), size_t per, int threads) {
+static void kv_tbl_push_by(tgx_ctx* c, int* tbl, int idx0, const KvPool::Changes& changes, void (*kernel)(int*, U), size_t per, int threads) {
   for (size_t i = 0; i < changes.size(); i += per) {
     U u{};
     u.n = (int)std::min(per, changes.size() - i);
-    for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first; u.val[k] = changes[i + (size_t)k].second; }
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, c->stream, c->kv_tbl, u);
+    for (int k = 0; k < u.n; k++) { u.idx[k] = changes[i + (size_t)k].first - idx0; u.val[k] = changes[i + (size_t)k].second; }
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, c->stream, tbl, u);
   }
 }
-static void kv_tbl_push(tgx_ctx* c, const KvPool::Changes& changes) {      // the table entries a KvPool call wrote (kv_pool.h), into the device table
-  if (changes.size() > 16) kv_tbl_push_by(c, changes, kv_tbl_set_wide_kernel, 240, 256);
-  else kv_tbl_push_by(c, changes, kv_tbl_set_kernel, 16, 64);
+// the table entries a KvPool call wrote (kv_pool.h), into the device table — or into a copy of ONE row of it at `row_copy`, whose entry 0 is flat index idx0
+// (tgx_splice_row: every change of the call lies in that row)
+static void kv_tbl_push(tgx_ctx* c, const KvPool::Changes& changes, int* row_copy = nullptr, int idx0 = 0) {
+  int* const tbl = row_copy ? row_copy : c->kv_tbl;
+  if (changes.size() > 16) kv_tbl_push_by(c, tbl, idx0, changes, kv_tbl_set_wide_kernel, 240, 256);
+  else kv_tbl_push_by(c, tbl, idx0, changes, kv_tbl_set_kernel, 16, 64);
 }
 
 int kv_ensure_blocks(tgx_ctx* c, int row, long long tokens) {
@@ -363,6 +368,25 @@ static void launch_kv_copy(tgx_ctx* c, long long n_tok, F&& rest) {
   const dim3 grid = rest(a), block(tgx::KV_FORK_THREADS);
   if (v16) hipLaunchKernelGGL(tgx::kv_fork_kernel<tgx::u32x4>, grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL(tgx::kv_fork_kernel<unsigned int>, grid, block, 0, c->stream, a);
+}
+
+// the launches of tgx_splice_row (kernels/kv_splice.h): the row's table copied into the staging buffer, and one gather or scatter of a group of layers
+static __global__ void kv_tbl_copy_kernel(int* dst, const int* src, int n) {
+  for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) dst[i] = src[i];
+}
+template <int DT, int W>
+static void launch_kv_splice_dt(tgx_ctx* c, const tgx::KvSpliceArgs& a, dim3 grid, bool scatter) {
+  const dim3 block(tgx::KV_SPLICE_THREADS);
+  if (scatter) hipLaunchKernelGGL((tgx::kv_splice_kernel<DT, W, true>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((tgx::kv_splice_kernel<DT, W, false>), grid, block, 0, c->stream, a);
+}
+static void launch_kv_splice(tgx_ctx* c, const tgx::KvSpliceArgs& a, bool wide, bool scatter) {
+  // the grid from the bytes to move, within eight workgroups per CU as launch_kv_fork's.  x: (moved token, chunk) items; y: rows that walk the group's spans
+  const long long items = (long long)a.moved * a.chunks, cap = 8ll * c->num_cus;
+  const long long gx = (items + tgx::KV_SPLICE_THREADS - 1) / tgx::KV_SPLICE_THREADS;
+  const long long gy = std::max<long long>(1, std::min<long long>((long long)a.n_layers * a.kv_heads, cap / gx));
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  TGX_DT_SWITCH(c->dt, if (wide) launch_kv_splice_dt<DT, 4>(c, a, grid, scatter); else launch_kv_splice_dt<DT, 1>(c, a, grid, scatter));
 }
 
 // ---- per-row request state (tgx_set_row_sampler / tgx_set_row_stop / tgx_decode_rows): host-side fields travel BY VALUE in a one-thread launch, stream-ordered
@@ -2228,6 +2252,90 @@ int tgx_truncate_row(tgx_ctx* c, int row, int64_t new_len) {
   r.past = new_len;
   r.tok = r.probs_ok = false; r.nologits = true;                        // the logits of position new_len - 1 no longer exist
   refresh_longest(c);
+  return TGX_OK;
+}
+
+// ---- tgx_splice_row (include/tgx.h): ranges cut out of the middle of a live row.  checks -> plan (splice_plan.h) -> launches (kernels/kv_splice.h) -> bookkeeping.
+// The move runs in groups of whole layers through the snapshot staging buffer (option snapshot.stage_kib caps it; one layer is always staged), allocated at first use.
+// Paged cache: the scatter launches write through the row's NEW table while later groups' gathers still read through the old one, so the new table row is first
+// built in the head of the staging buffer (a copy of the device row plus the pool's changes) and the device table itself is pushed behind the last scatter.
+int tgx_splice_row(tgx_ctx* c, int row, int n_keep, const int64_t* starts, const int64_t* lens, int64_t* out_len) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!starts || !lens) return set_err(c, TGX_ERR_INVALID, "null argument");
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "splice before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
+  if (n_keep < 1 || n_keep > TGX_MAX_SPLICE_RANGES) return set_err(c, TGX_ERR_INVALID, "n_keep %d out of range [1,%d]", n_keep, TGX_MAX_SPLICE_RANGES);
+  if (row >= c->batch || c->row_host[(size_t)row].idle || c->row_host[(size_t)row].past < 1) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to splice", row);
+  if (d.family == TGX_FAMILY_GPT2) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_splice_row: GPT-2's positions are learned and added to the hidden state: there is nothing to re-rotate");
+  const long long past = c->row_host[(size_t)row].past;
+  splice_plan::Plan plan;
+  if (const char* why = splice_plan::make(past, n_keep, starts, lens, &plan)) return set_err(c, TGX_ERR_INVALID, "tgx_splice_row: %s (row %d holds %lld positions)", why, row, past);
+  const long long tok_bytes = (long long)d.head_dim * (long long)c->esz, half_bytes = tok_bytes / 2;
+  if (tok_bytes % 4 != 0 || (d.head_dim & 1) || half_bytes % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_splice_row: a cache row of %d bytes", (int)tok_bytes);
+  if (plan.truncation()) {      // one range [0, L): tgx_truncate_row's bits and block accounting (L == past with the logits in place: its no-op)
+    if (int rc = tgx_truncate_row(c, row, plan.new_len)) return rc;
+    if (out_len) *out_len = plan.new_len;
+    return TGX_OK;
+  }
+  splice_plan::Blocks blk;
+  if (c->kv_paged) {
+    // all or nothing: the fresh blocks of the copy on write against the FREE LIST ALONE (the blocks the row gives back are not counted: the sum errs towards refusing)
+    blk = splice_plan::blocks(c->kv, row, plan);
+    if (blk.fresh.size() > c->kv.free_blocks())
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: splicing row %d writes %zu block(s) shared with forked rows and %zu block(s) are free for their copies (option kv.budget_tokens = %d)",
+                     row, blk.fresh.size(), c->kv.free_blocks(), c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  // the staging buffer: [the new table row | groups of whole layers].  (A failed growth fails the call before the row or the pool moved.)
+  const int moved = (int)plan.moved(), stride = c->kv_paged ? c->kv.tbl_stride() : 0;
+  const size_t head = ((size_t)stride * 4 + 255) / 256 * 256;
+  const long long layer_bytes = 2ll * d.kv_heads * moved * tok_bytes;
+  const long long room = (long long)c->snapshot_stage_kib * 1024 - (long long)head;
+  const int per_group = (int)std::max<long long>(1, std::min<long long>(d.layers, room / layer_bytes));
+  if (int rc = dev_grow(c, &c->snap_stage, &c->snap_stage_bytes, head + (size_t)per_group * (size_t)layer_bytes)) return rc;
+  // ---- nothing above changed anything: "a refused call changes nothing" is about those checks.  From here on the host bookkeeping (blocks, table) moves ahead of the
+  // launches; should one of them not issue, launches_ok poisons the context — the row's lengths then stay as they were, and only tgx_reset_cache follows
+  int* const new_tbl = reinterpret_cast<int*>(c->snap_stage);
+  KvPool::Changes ch;
+  if (c->kv_paged) {
+    hipLaunchKernelGGL(kv_tbl_copy_kernel, dim3(1), dim3(256), 0, c->stream, new_tbl, c->kv_tbl + (size_t)row * stride, stride);
+    for (size_t i = 0; i < blk.fresh.size(); i++) {      // copy on write, before anything writes: cannot run dry, counted above
+      const std::pair<int, int> of = c->kv.unshare(row, blk.fresh[i], ch);
+      if (i == 0 && blk.carry) launch_kv_tail_copy(c, of.first, of.second, blk.carry);      // the identity rows in front of f
+    }
+    c->kv.trim(row, plan.new_len, ch);      // the blocks beyond the new length (a shared one only loses this row's reference)
+    kv_tbl_push(c, ch, new_tbl, row * stride);
+  }
+  tgx::KvSpliceArgs a{};
+  a.k = c->rows[(size_t)row].kcache; a.v = c->rows[(size_t)row].vcache;
+  a.stage = c->snap_stage + head;
+  a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+  a.layer_stride = c->kv_paged ? (long long)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * d.head_dim : (long long)d.kv_heads * d.max_ctx * d.head_dim;
+  a.kv_heads = d.kv_heads; a.hd = d.head_dim; a.max_ctx = d.max_ctx; a.moved = moved;
+  const bool wide = half_bytes % 16 == 0;
+  a.chunks = (int)(half_bytes / (wide ? 16 : 4));
+  for (int i = plan.first_moved, m0 = 0; i < plan.n_seg; i++) {
+    a.seg[a.n_seg++] = {(int)plan.seg[i].src, (int)plan.seg[i].dst, m0, (int)plan.seg[i].len};
+    m0 += (int)plan.seg[i].len;
+  }
+  for (int l0 = 0; l0 < d.layers; l0 += per_group) {
+    a.layer0 = l0; a.n_layers = std::min(per_group, d.layers - l0);
+    a.tbl = c->kv_paged ? c->kv_tbl + (size_t)row * stride : nullptr;
+    launch_kv_splice(c, a, wide, /*scatter=*/false);
+    a.tbl = c->kv_paged ? new_tbl : nullptr;
+    launch_kv_splice(c, a, wide, /*scatter=*/true);
+  }
+  if (c->kv_paged) kv_tbl_push(c, ch);
+  launch_add_pos(c, c->rows[(size_t)row].pos, (int)(plan.new_len - past));      // stream-ordered behind the steps already enqueued
+  if (c->row_host[(size_t)row].fin) { row_req_push(c, row, ROWQ_STATE); c->row_host[(size_t)row].fin = 0; }
+  if (int rc = launches_ok(c)) return rc;
+  RowHost& r = c->row_host[(size_t)row];
+  r.past = plan.new_len;
+  r.tok = r.probs_ok = false; r.nologits = true;      // the logits belong to a sequence the row no longer holds
+  refresh_longest(c);
+  if (out_len) *out_len = plan.new_len;
   return TGX_OK;
 }
 

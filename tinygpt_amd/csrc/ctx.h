@@ -412,7 +412,8 @@ struct tgx_ctx {
   AutoTable automata[TGX_MAX_AUTOMATA];
   // ---- row snapshots (include/tgx.h tgx_save_row / tgx_restore_row; row_snapshot.h, kernels/kv_pack.h): the staging buffer a snapshot moves through in groups of
   // whole layers (the state section in front of the first group's).  Allocated by the first save or restore, grown to the largest group seen; option
-  // snapshot.stage_kib caps it (one layer is always staged)
+  // snapshot.stage_kib caps it (one layer is always staged).  tgx_splice_row (kernels/kv_splice.h) moves its groups of layers through the same buffer, the row's
+  // new block table in front of them
   unsigned char* snap_stage = nullptr; size_t snap_stage_bytes = 0;
   int snapshot_stage_kib = 65536;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode

@@ -28,6 +28,7 @@ class KvPool {
   }
   int n_blocks() const { return nblocks; }        // physical blocks incl. the scratch block
   int tbl_stride() const { return stride; }       // table entries per row = ceil(max_ctx / block_tokens)
+  int block_tokens() const { return block; }
   int blocks_for(long long tokens) const { return (int)((tokens + block - 1) / block); }
   size_t free_blocks() const { return free_list.size(); }
   int row_blocks(int row) const { return row_nblk[(size_t)row]; }
@@ -64,13 +65,17 @@ class KvPool {
   }
   // ... and one fresh block behind them for the copy of the source's partial tail (the caller counted: available_for)
   int fork_tail(int dst, Changes& ch) { const int b = take(); set(dst, row_nblk[(size_t)dst]++, b, ch); return b; }
-  // tgx_truncate_row, copy on write: block idx of `row`, which other rows map as well, is swapped for a fresh one and loses this row's reference.  Returns
-  // (old, fresh) for the copy launch — fresh 0, and nothing changed, when no block is free
-  std::pair<int, int> unshare_tail(int row, int idx, Changes& ch) {
-    const int old = block_at(row, idx);
-    if (free_list.empty()) return {old, 0};
-    const int fresh = take(); set(row, idx, fresh, ch); drop(old);
+  // copy on write for one block of a row (tgx_truncate_row: its new tail block; tgx_splice_row: every block it writes, splice_plan.h): block idx of `row`, which
+  // other rows map as well, is swapped for a fresh one and loses this row's reference.  Returns (old, fresh) for the copy launch.  unshare: the caller counted the
+  // fresh blocks against the free list; unshare_tail: fresh 0, and nothing changed, when no block is free
+  std::pair<int, int> unshare(int row, int idx, Changes& ch) {
+    const int old = block_at(row, idx), fresh = take();
+    set(row, idx, fresh, ch); drop(old);
     return {old, fresh};
+  }
+  std::pair<int, int> unshare_tail(int row, int idx, Changes& ch) {
+    if (free_list.empty()) return {block_at(row, idx), 0};
+    return unshare(row, idx, ch);
   }
   bool operator==(const KvPool& o) const { return block == o.block && nblocks == o.nblocks && stride == o.stride && tbl == o.tbl && free_list == o.free_list && row_nblk == o.row_nblk && ref == o.ref; }
   // the full audit, given every row's length: nullptr, or what is wrong

@@ -94,6 +94,7 @@ ABI = {
     "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
     "extend_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "truncate_row": (c_int, [c_void_p, c_int, c_int64]),
+    "splice_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "row_snapshot_bytes": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
     "save_row": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
     "restore_row": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
@@ -345,6 +346,15 @@ class Model:
         """roll `row` back to its first n positions (include/tgx.h tgx_truncate_row); it then holds no logits until extend_row"""
         self._check(self.be.truncate_row(self._ctx, row, int(n)))
         return self
+
+    def splice_row(self, row: int, ranges) -> int:
+        """keep the positions in `ranges` — (start, length) pairs, sorted and disjoint — of `row` and slide them together, the keys re-rotated to where they land
+        (include/tgx.h tgx_splice_row); returns the new length.  The row then holds no logits until extend_row"""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+        starts, lens = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+        n = c_int64(0)
+        self._check(self.be.splice_row(self._ctx, row, len(r), starts.ctypes.data_as(POINTER(c_int64)), lens.ctypes.data_as(POINTER(c_int64)), ctypes.byref(n)))
+        return n.value
 
     # -- row snapshots (include/tgx.h tgx_save_row / tgx_restore_row) -----------------------------
     def row_snapshot_bytes(self, row: int) -> int:

@@ -41,6 +41,8 @@ struct Backend {
   // prefix reuse (optional: GPTConfig::reusePrefix needs both)
   int (*extend_row)(tgx_ctx*, int, const int64_t*, int) = nullptr;
   int (*truncate_row)(tgx_ctx*, int, int64_t) = nullptr;
+  // context shift (optional: GPTConfig::contextShift needs it with extend_row, sample_row, set_row_sampler, set_row_stop, decode_rows and past_length_row)
+  int (*splice_row)(tgx_ctx*, int, int, const int64_t*, const int64_t*, int64_t*) = nullptr;
   // greedy speculative decoding (optional: GPTConfig::speculate needs all three — the draft is verified by verify_row, steps without a draft go through
   // decode_rows so that every produced token is counted against the row's stop conditions on the device)
   int (*verify_row)(tgx_ctx*, int, const int64_t*, int, int64_t*, int32_t*, int32_t*) = nullptr;
@@ -93,7 +95,7 @@ struct Backend {
     TGXH_BIND(step_async, false); TGXH_BIND(fetch_token, false);
     TGXH_BIND(reset_cache, true); TGXH_BIND(past_length, true); TGXH_BIND(context_size, true); TGXH_BIND(last_error, true);
     TGXH_BIND(reset_row, false); TGXH_BIND(forward_row, false); TGXH_BIND(sample_row, false); TGXH_BIND(past_length_row, false);
-    TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false);
+    TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false); TGXH_BIND(splice_row, false);
     TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
     TGXH_BIND(verify_row_sampled, false); TGXH_BIND(read_pass_logits, false); TGXH_BIND(verify_rows, false);
     TGXH_BIND(advance_rows, false);

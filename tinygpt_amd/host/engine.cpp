@@ -298,8 +298,9 @@ static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int 
   in.verifyRows = be.verify_rows != nullptr;
   return tgxh::spec_mode(in);
 }
-bool GPTEngine::speculateActive(int batch) const { return spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) != tgxh::SpecMode::Off; }
-bool GPTEngine::speculateSampledActive(int batch) const { return spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) == tgxh::SpecMode::Sampled; }
+// (GPTConfig::contextShift: the shifting loops take plain steps — a draft's positions are counted from the sequence, which a shifted row no longer holds in full)
+bool GPTEngine::speculateActive(int batch) const { return !shiftActive() && spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) != tgxh::SpecMode::Off; }
+bool GPTEngine::speculateSampledActive(int batch) const { return !shiftActive() && spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) == tgxh::SpecMode::Sampled; }
 
 bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
   const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
@@ -378,6 +379,84 @@ bool GPTEngine::logprobsRefused(bool async) {
   if (!logprobsActive()) { fail("logprobs: the device shim lacks tgx_set_row_logprobs / tgx_read_row_logprobs or the per-row calls they ride on"); return true; }
   if (async && eosTokenIds_.size() > (size_t)TGX_MAX_STOP_IDS) { fail("logprobs: generateAsync stops the row on the device, which holds at most " + std::to_string(TGX_MAX_STOP_IDS) + " stop ids"); return true; }
   return false;
+}
+
+// ---- GPTConfig::contextShift (engine.h; include/tgx.h tgx_splice_row)
+bool GPTEngine::shiftRow(int row, int32_t cur, const tgx_sampler_cfg& sc, int64_t* next, std::vector<int32_t>* held) {
+  const int64_t past = be_.past_length_row(model_.ctx, row);
+  if (past < 2) return fail("context shift: the row holds fewer than two positions");
+  const int64_t n_keep = std::min<int64_t>(std::max(0, config_.shiftKeep), past - 1), n_discard = (past - n_keep) / 2;
+  int64_t starts[2] = {0, n_keep + n_discard}, lens[2] = {n_keep, past - n_keep - n_discard}, new_len = 0;
+  if (n_discard < 1)
+    return fail("context shift: shiftKeep " + std::to_string(config_.shiftKeep) + " keeps all but one of the row's " + std::to_string(past) + " positions: nothing is left to discard");
+  const int first = n_keep > 0 ? 0 : 1;
+  if (be_.splice_row(model_.ctx, row, 2 - first, starts + first, lens + first, &new_len) != TGX_OK) return fail(std::string("splice_row: ") + be_.last_error(model_.ctx));
+  const int64_t t = cur;
+  if (be_.extend_row(model_.ctx, row, &t, 1) != TGX_OK) return fail(std::string("extend_row: ") + be_.last_error(model_.ctx));
+  if (be_.sample_row(model_.ctx, row, &sc, config_.seed, next) != TGX_OK) return fail(std::string("sample_row: ") + be_.last_error(model_.ctx));
+  if (held) {
+    if ((int64_t)held->size() == past) { held->erase(held->begin() + n_keep, held->begin() + n_keep + n_discard); held->push_back(cur); }
+    else held->clear();      // (unknown: the caller's record did not match the row)
+  }
+  lastShifts_++;
+  return true;
+}
+
+// generateSync's decode under contextShift: every row through tgx_decode_rows with its length on the device (max_new = what it may still produce), never more steps
+// per call than the fullest unfinished row has room for; a full row is shifted, which produces its next token.  got[b]: the tokens of row b after its first
+bool GPTEngine::decodeRowsShifting(int B, const tgx_sampler_cfg& sc, int64_t n_more, bool constrained, std::vector<std::vector<int64_t>>& got, std::vector<RowLogprobs>* lp) {
+  const int64_t ctxSize = contextSize();
+  const int32_t* stops = constrained && !eosTokenIds_.empty() ? eosTokenIds_.data() : nullptr;
+  const int n_stops = constrained ? (int)eosTokenIds_.size() : 0;
+  std::vector<char> over((size_t)B, 0);
+  for (int b = 0; b < B; b++) {
+    if (constrained && !got[(size_t)b].empty() && isEosToken((int32_t)got[(size_t)b].back())) over[(size_t)b] = 1;
+  }
+  std::vector<int64_t> cur((size_t)B);
+  for (int b = 0; b < B; b++) { cur[(size_t)b] = got[(size_t)b].back(); got[(size_t)b].clear(); }      // (in: the row's first token)
+  auto restate = [&](int b) {
+    const int64_t rem = n_more - (int64_t)got[(size_t)b].size();
+    if (rem <= 0) {      // the row is done: retired, so that the other rows' steps leave it alone
+      over[(size_t)b] = 1;
+      return be_.reset_row(model_.ctx, b) == TGX_OK || fail(std::string("reset_row: ") + be_.last_error(model_.ctx));
+    }
+    return be_.set_row_stop(model_.ctx, b, (int32_t)rem, stops, n_stops) == TGX_OK || fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx));
+  };
+  for (int b = 0; b < B; b++) {
+    if (over[(size_t)b]) { if (be_.reset_row(model_.ctx, b) != TGX_OK) return fail(std::string("reset_row: ") + be_.last_error(model_.ctx)); }
+    else if (!restate(b)) return false;
+  }
+  std::vector<int64_t> ids;
+  std::vector<int32_t> made((size_t)B), fin((size_t)B);
+  auto open = [&] { for (char o : over) if (!o) return true; return false; };
+  while (open()) {
+    int64_t room = TGX_LOGPROB_RING / 2;
+    for (int b = 0; b < B; b++) {
+      if (over[(size_t)b]) continue;
+      if (be_.past_length_row(model_.ctx, b) >= ctxSize) {
+        int64_t next = 0;
+        if (!shiftRow(b, (int32_t)cur[(size_t)b], sc, &next, nullptr)) return false;
+        got[(size_t)b].push_back(next); cur[(size_t)b] = next;
+        if (lp && !logprobsDrain(b, 1, (*lp)[(size_t)b])) return false;
+        if (constrained && isEosToken((int32_t)next)) { over[(size_t)b] = 1; if (be_.reset_row(model_.ctx, b) != TGX_OK) return fail(std::string("reset_row: ") + be_.last_error(model_.ctx)); continue; }
+        if (!restate(b) || over[(size_t)b]) { if (!over[(size_t)b]) return false; continue; }
+      }
+      room = std::min<int64_t>({room, ctxSize - be_.past_length_row(model_.ctx, b), n_more - (int64_t)got[(size_t)b].size()});
+    }
+    if (!open()) break;
+    const int m = (int)std::max<int64_t>(1, room);
+    ids.assign((size_t)m * (size_t)B, -1);
+    if (be_.decode_rows(model_.ctx, m, ids.data(), made.data(), fin.data()) != TGX_OK) return fail(std::string("decode: ") + be_.last_error(model_.ctx));
+    for (int b = 0; b < B; b++) {
+      if (over[(size_t)b]) continue;
+      if (made[(size_t)b] < 1 && !fin[(size_t)b]) return fail("context shift: a row produced no token");
+      for (int32_t i = 0; i < made[(size_t)b]; i++) got[(size_t)b].push_back(ids[(size_t)i * (size_t)B + (size_t)b]);
+      if (made[(size_t)b] > 0) cur[(size_t)b] = got[(size_t)b].back();
+      if (lp && !logprobsDrain(b, made[(size_t)b], (*lp)[(size_t)b])) return false;
+      if (fin[(size_t)b]) over[(size_t)b] = 1;
+    }
+  }
+  return true;
 }
 
 bool GPTEngine::rowsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first) {
@@ -510,7 +589,9 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   const bool lpOn = logprobsActive();
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? B : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(B); });
-  const bool procOn = processorsOn(), specSampled = speculateSampledActive(B), perRow = lpOn || procOn || specSampled;
+  const bool shift = shiftActive() && be_.reset_row;
+  const bool procOn = processorsOn(), specSampled = speculateSampledActive(B), perRow = lpOn || procOn || specSampled || shift;
+  lastShifts_ = 0;
   bool allStopped = false;      // SamplerConfig::regex: every row ended at a stop id
   const auto procOff = at_exit([&] { if (procOn) processorsEnd(B); });
   const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(B); });
@@ -557,6 +638,24 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
     }
     if ((int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
     for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = seq[(size_t)(S + 1 + i)];
+  } else if (shift && n_new > 1) {      // GPTConfig::contextShift: the rows may pass the context (decodeRowsShifting)
+    const bool constrained = constraintOn();
+    std::vector<std::vector<int64_t>> got((size_t)B);
+    for (int b = 0; b < B; b++) got[(size_t)b].push_back(first[(size_t)b]);
+    if (!decodeRowsShifting(B, sc, n_new - 1, constrained, got, lpOn ? &lpRows : nullptr)) return out;
+    const int32_t pad = padTokenId();
+    allStopped = constrained;
+    for (int b = 0; b < B; b++) {
+      bool stopped = constrained && isEosToken((int32_t)first[(size_t)b]);
+      if (!constrained && (int64_t)got[(size_t)b].size() != n_new - 1) { fail("context shift: a row finished before maxNewTokens"); return out; }
+      for (int64_t i = 0; i + 1 < n_new; i++) {
+        int64_t& t = rest[(size_t)(i * B + b)];
+        if (stopped || i >= (int64_t)got[(size_t)b].size()) { t = pad; continue; }
+        t = got[(size_t)b][(size_t)i];
+        if (constrained && isEosToken((int32_t)t)) stopped = true;
+      }
+      allStopped = allStopped && stopped;
+    }
   } else if (perRow) {      // every row with the call's settings through tgx_decode_rows (its ids are tgx_decode's), a ring's worth of steps at most per call
     // under a regex the rows end on the device at an EOS / stop id, which the automaton allows only where a match may end; otherwise no EOS check, as below
     const bool constrained = constraintOn();
@@ -625,7 +724,9 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   const bool lpOn = logprobsActive();
   std::vector<RowLogprobs> lpRows((size_t)(lpOn ? 1 : 0));
   const auto lpOff = at_exit([&] { if (lpOn) logprobsEnd(1); });
-  const bool procOn = processorsOn(), specSampled = speculateSampledActive(1), perRow = lpOn || procOn || specSampled;
+  const bool shift = shiftActive();
+  const bool procOn = processorsOn(), specSampled = speculateSampledActive(1), perRow = lpOn || procOn || specSampled || shift;
+  lastShifts_ = 0;
   const auto procOff = at_exit([&] { if (procOn) processorsEnd(1); });
   const auto samplerOff = at_exit([&] { if (specSampled) rowSamplerEnd(); });
   if (procOn && !processorsBegin(0, ids.data(), S)) return out;
@@ -651,9 +752,35 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
     if (be_.set_row_stop(model_.ctx, 0, (int32_t)(maxNew - 1), eosTokenIds_.empty() ? nullptr : eosTokenIds_.data(), (int)eosTokenIds_.size()) != TGX_OK) {
       fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); broke = true;
     }
+    // GPTConfig::contextShift: the ids the cache holds, once the row has been shifted — `held` as of the last shift, then seq from `mark` on
+    std::vector<int32_t> held;
+    bool shifted = false;
+    size_t mark = 0;
+    auto heldNow = [&](int64_t past) {
+      if (!shifted) return past <= (int64_t)seq.size() ? std::vector<int32_t>(seq.begin(), seq.begin() + past) : std::vector<int32_t>();
+      std::vector<int32_t> h = held;
+      const int64_t more = past - (int64_t)h.size();
+      if (h.empty() || more < 0 || mark + (size_t)more > seq.size()) return std::vector<int32_t>();
+      h.insert(h.end(), seq.begin() + (int64_t)mark, seq.begin() + (int64_t)mark + more);
+      return h;
+    };
     auto have = [&](int64_t k) {      // token k (1-based) of the generation is in seq
       while (!broke && (int64_t)seq.size() - S < k && !finished) {
         const size_t before = seq.size();
+        if (shift && be_.past_length_row(model_.ctx, 0) >= contextSize()) {      // the next step would exceed the context: shift, which produces the next token
+          int64_t next = 0;
+          std::vector<int32_t> h = heldNow(be_.past_length_row(model_.ctx, 0));
+          broke = !shiftRow(0, seq.back(), sc, &next, &h);
+          if (!broke) {
+            held = std::move(h); shifted = true; mark = seq.size();
+            seq.push_back((int32_t)next);
+            const int64_t rem = S + maxNew - (int64_t)seq.size();      // tgx_extend_row started the produced-token count afresh: the stop with what remains
+            if (rem <= 0) finished = true;
+            else if (be_.set_row_stop(model_.ctx, 0, (int32_t)rem, eosTokenIds_.empty() ? nullptr : eosTokenIds_.data(), (int)eosTokenIds_.size()) != TGX_OK) {
+              fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); broke = true;
+            }
+          }
+        } else
         broke = !speculateMore(seq, S + maxNew, finished);
         if (!broke && lpOn) broke = !logprobsDrain(0, (int64_t)(seq.size() - before), lpRows[0]);
       }
@@ -674,8 +801,8 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
     out.firstTokenMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
     out.decodeMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     if (reuse) {      // the cache holds every input of a pass or step that produced a token: all of seq but its last token
-      const int64_t held = broke ? 0 : be_.past_length(model_.ctx);
-      if (held >= 1 && held <= (int64_t)seq.size()) cached_.assign(seq.begin(), seq.begin() + held);
+      const int64_t n_held = broke ? 0 : be_.past_length(model_.ctx);
+      if (n_held >= 1 && (shifted || n_held <= (int64_t)seq.size())) cached_ = heldNow(n_held);
       else cached_.clear();
     }
     out.batch = 1;

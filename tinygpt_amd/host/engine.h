@@ -60,6 +60,18 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // and prefills only what follows the longest prefix the new prompt shares with it (tgx_truncate_row + tgx_extend_row).  Needs a backend with both symbols;
   // generateSync and any failure of the two calls take the reset path.
   bool reusePrefix = false;
+  // Not in the reference (its generation ends at contextSize()): generation past the context.  Off by default: every run as it was.  With it set and a backend that
+  // exports tgx_splice_row (and the per-row calls), the generate loops step through tgx_sample_row / tgx_decode_rows, never more steps per call than the row that
+  // holds the most positions has room for, and a row whose next step would exceed contextSize() is SHIFTED (include/tgx.h tgx_splice_row): with
+  // n_keep = min(shiftKeep, past - 1) and n_discard = (past - n_keep) / 2 it keeps [0, n_keep) + [n_keep + n_discard, past), its current token is fed again
+  // (tgx_extend_row of one token), the next token is sampled from that (tgx_sample_row) and the row's stop is restated with what remains of maxNewTokens
+  // (tgx_extend_row starts the produced-token count afresh).  reusePrefix's record of what row 0 holds is spliced the same way.  A sampled row's draw key hashes
+  // the position, and positions repeat after a shift: a sampled run draws position p's variate again the second time it reaches p.
+  // A shiftKeep that keeps all but one of a full row's positions leaves nothing to discard: the generate call then ends there with a message that names it.
+  // While it is on no drafts are proposed (speculate), and a prompt is still cut to contextSize() before its prefill, keeping the tail.  generateSync's rows are
+  // aligned to one length, so they fill up — and shift — at the same step unless a regex ends one early.
+  bool contextShift = false;
+  int shiftKeep = 0;
   // Not in the reference: greedy speculative decoding with prompt lookup (spec_draft.h).  0 = off: the loops below exactly as they were.  N > 0: up to N draft
   // tokens (clamped to TGX_MAX_DRAFT) are proposed per iteration and verified in one pass (tgx_verify_row); without a match one ordinary step runs.  Active only
   // for a greedy sampler configuration, ONE sequence, at most TGX_MAX_STOP_IDS EOS ids and a backend that has the calls — otherwise the existing loop runs.  The
@@ -199,6 +211,8 @@ class GPTEngine {
     config_.reusePrefix = on;
     cached_.clear();
   }
+  void setContextShift(bool on, int keep) { config_.contextShift = on; config_.shiftKeep = keep < 0 ? 0 : keep; }
+  int64_t lastShifts() const { return lastShifts_; }      // context shifts the last generate call made, over all its rows
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
   void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
   void setSpeculateSampled(bool on) { config_.speculateSampled = on; }
@@ -218,6 +232,12 @@ class GPTEngine {
   bool reuseActive() const { return config_.reusePrefix && be_.extend_row && be_.truncate_row; }
   bool sessionCapable(const char* what);                       // prefix reuse active and the backend has the snapshot calls; else err_ set
   bool prefillReusing(const std::vector<int64_t>& ids);      // the prompt after its cached prefix; false: nothing reusable (the caller resets and prefills)
+  bool shiftActive() const {
+    return config_.contextShift && be_.splice_row && be_.extend_row && be_.sample_row && be_.set_row_sampler && be_.set_row_stop && be_.decode_rows && be_.past_length_row;
+  }
+  // the shift of `row`, whose current token is cur and whose cache is full: splice, feed cur again, sample the next token into *next.  held (may be null): the ids
+  // the row's cache holds, kept in step.  false: a call failed (err_ set)
+  bool shiftRow(int row, int32_t cur, const tgx_sampler_cfg& sc, int64_t* next, std::vector<int32_t>* held);
   bool speculateActive(int batch) const;                      // GPTConfig::speculate applies to this call
   bool speculateSampledActive(int batch) const;               // ... through tgx_verify_row_sampled (GPTConfig::speculateSampled; spec_mode.h)
   // row 0 holds seq minus its last token, which is its current token; the row's stop conditions are set.  Drafts from seq, verifies (or takes one ordinary
@@ -234,6 +254,8 @@ class GPTEngine {
   void logprobsEnd(int batch);
   void rowSamplerEnd(int batch = 1);                          // GPTConfig::speculateSampled: the rows' sampler back to the default when the call ends
   void logprobsStore(GPTOutput& out, const std::vector<RowLogprobs>& rows, int64_t perRow) const;
+  // GPTConfig::contextShift, generateSync: got[b] holds row b's first token on entry and its tokens after the first on return
+  bool decodeRowsShifting(int batch, const tgx_sampler_cfg& sc, int64_t n_more, bool constrained, std::vector<std::vector<int64_t>>& got, std::vector<RowLogprobs>* lp);
   // SamplerConfig's penalties / logit bias
   bool processorsOn() const { return !config_.samplerConfig.processorsNeutral(); }
   bool processorsRefused(bool async);                                                          // asked for and not servable: err_ set, the generate call fails
@@ -252,7 +274,7 @@ class GPTEngine {
   Tokenizer tokenizer_;
   bool tokenizerOk_ = false;
   std::vector<int32_t> cached_;      // reusePrefix: the token ids row 0's cache holds, position by position (empty: unknown / nothing)
-  int64_t lastReused_ = 0;
+  int64_t lastReused_ = 0, lastShifts_ = 0;
   SpecStats spec_;
   std::string constraintPattern_;            // the pattern and stop ids of the table the device holds (constraintId_ >= 0)
   std::vector<int32_t> constraintStops_;

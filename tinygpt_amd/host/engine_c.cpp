@@ -63,6 +63,9 @@ TGXE_API int64_t tgxe_last_reused(tgxe_engine* h) { return h ? h->e->lastReused(
 // session files (GPTEngine::saveSession / loadSession): row 0's conversation kept across processes; 0 = done, 1 = refused (tgxe_last_error says why)
 TGXE_API int tgxe_save_session(tgxe_engine* h, const char* path) { return h && path && h->e->saveSession(path) ? 0 : 1; }
 TGXE_API int tgxe_load_session(tgxe_engine* h, const char* path) { return h && path && h->e->loadSession(path) ? 0 : 1; }
+// generation past the context (GPTConfig::contextShift / shiftKeep; off by default); tgxe_last_shifts = the shifts the last generate call made, over all its rows
+TGXE_API void tgxe_set_context_shift(tgxe_engine* h, int on, int keep) { if (h) h->e->setContextShift(on != 0, keep); }
+TGXE_API int64_t tgxe_last_shifts(tgxe_engine* h) { return h ? h->e->lastShifts() : 0; }
 // greedy speculative decoding (GPTConfig::speculate): the maximum draft length (0 = off); tgxe_spec_stats writes {verify calls, draft tokens, accepted draft
 // tokens, ordinary steps, produced-per-verify histogram [0 .. TGX_MAX_DRAFT + 1]} (up to cap values) and returns how many there are
 TGXE_API void tgxe_set_speculate(tgxe_engine* h, int max_draft) { if (h) h->e->setSpeculate(max_draft); }

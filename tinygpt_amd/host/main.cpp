@@ -58,7 +58,10 @@ static void usage(const char* prog) {
           "                            device, which keeps no cache to save)\n"
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (--temperature 0 --top-p 1; several prompts: every row's\n"
           "                            draft in one joint pass; default: 0 = off)\n"
-          "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n",
+          "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n"
+          "  --context-shift           generate past the context: a full row keeps its first --keep positions, drops half of the rest and slides the tail down, its keys\n"
+          "                            re-rotated (no drafts are proposed while it is on; default: off, the run ends at the context)\n"
+          "  --keep <n>                with --context-shift: positions kept at the front of a shifted row (default: 0)\n",
           prog);
 }
 
@@ -145,6 +148,8 @@ int main(int argc, char** argv) {
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
     else if (a == "--speculate") cfg.speculate = atoi(next());
     else if (a == "--speculate-sampled") cfg.speculateSampled = true;
+    else if (a == "--context-shift") cfg.contextShift = true;
+    else if (a == "--keep") cfg.shiftKeep = std::max(0, atoi(next()));
     else if (a == "--session-load") session_load = next();
     else if (a == "--session-save") session_save = next();
     else if (a == "--logprobs") cfg.logprobs = atoi(next());

@@ -32,6 +32,13 @@ tgx_decode_rows, so it steps too: B + 1 rows.  The forms alternate inside every 
 window; the step rows grow by one position per call.  Median [min .. max] of --reps.
 
     python tools/admit_bench.py --mixed [--mixed-rows 8,32] [--mixed-chunks 128,256,512] [--mixed-tiles 0,4,8,16,-1] [--parent-lib PATH]
+
+--splice measures cutting the middle out of a row (include/tgx.h tgx_splice_row), the context shift "keep 4, drop the first half of the rest": 2048 -> 4 + 1024 and
+8192 -> 4 + 4096 positions, on slabs and paged.  Per repetition, each from a synchronised device to the call's own synchronise: ONE tgx_splice_row; the one-token
+tgx_extend_row that re-feeds the current token behind it; and tgx_reset_row + tgx_forward_row of the kept tokens, what a caller without the call does.  The row is
+prefilled again outside the timed window.  Median [min .. max] of --reps; the lines are also written to --splice-out (default profiles/splice_row.txt).
+
+    python tools/admit_bench.py --splice [--splice-out FILE]
 """
 import argparse, dataclasses, os, sys, time
 import numpy as np
@@ -62,7 +69,56 @@ ap.add_argument("--mixed-ctx", type=int, default=300, help="--mixed: the step ro
 ap.add_argument("--mixed-past", type=int, default=256, help="--mixed: the positions the chunk's row already holds")
 ap.add_argument("--mixed-tiles", default="-1", help="--mixed: the advance.attn_tiles values to time the joint call with (e.g. 0,4,8,16,-1)")
 ap.add_argument("--parent-lib", default="", help="--mixed: the library the two-call baseline runs on (default: this build's)")
+ap.add_argument("--splice", action="store_true", help="tgx_splice_row (2048 -> 4 + 1024, 8192 -> 4 + 4096) and the one-token extend_row behind it against reset + forward_row of the kept tokens")
+ap.add_argument("--splice-out", default=os.path.join(ROOT, "profiles", "splice_row.txt"))
 args = ap.parse_args()
+
+
+def splice_bench():
+    shapes = [(2048, 4, 1024), (8192, 4, 4096)]      # (past, kept at the front, kept at the end)
+    ctx = max(s[0] for s in shapes) + 64
+    lines = [f"# tools/admit_bench.py --splice --model {args.model} --dtype {args.dtype} --reps {args.reps}: one synchronised call each, ms, median [min .. max]"]
+    for paged in (0, 1):
+        desc = dataclasses.replace(known_desc(args.model, args.dtype), max_batch=1, max_ctx=ctx)
+        m = Model(desc, product_backend())
+        if paged:
+            m.set_option("kv.budget_tokens", ((ctx + 127) // 128 + 1) * 128)
+        m.load_synthetic(1234, 0.02).finalize()
+        for P, head, tail in shapes:
+            p = synth.synth_prompt(desc.vocab, P, 900)
+            ranges = [(0, head), (P - tail, tail)]
+            kept = np.concatenate([p[:head], p[P - tail:]])
+
+            def timed(call):
+                m.synchronize()
+                t0 = time.perf_counter()
+                call()
+                m.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            t = {"splice": [], "extend": [], "forward": []}
+            for rep in range(2 + args.reps):
+                m.reset_row(0); m.forward_row(0, p)
+                tok = int(m.sample_row(0, GREEDY))
+                a = timed(lambda: m.splice_row(0, ranges))
+                b = timed(lambda: m.extend_row(0, [tok]))
+                c = timed(lambda: (m.reset_row(0), m.forward_row(0, kept)))
+                if rep >= 2:
+                    t["splice"].append(a); t["extend"].append(b); t["forward"].append(c)
+            cell = lambda v: f"{np.median(v):8.3f} [{min(v):8.3f} .. {max(v):8.3f}]"
+            sp, ex, fw = (float(np.median(t[k])) for k in ("splice", "extend", "forward"))
+            mib = 2 * desc.layers * desc.kv_heads * desc.head_dim * (4 if args.dtype == 'fp32' else 2) * tail / 2**20
+            lines.append(f"{desc.name} {args.dtype} {'paged' if paged else 'slabs'} {P:5d} -> {head} + {tail:4d} ({mib:6.1f} MiB moved)  splice_row {cell(t['splice'])}   "
+                         f"extend_row(1) {cell(t['extend'])}   reset + forward_row({head + tail}) {cell(t['forward'])}   splice / forward {sp / fw:.3f}   (splice + extend) / forward {(sp + ex) / fw:.3f}")
+            print(lines[-1], flush=True)
+        m.close()
+    with open(args.splice_out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if args.splice:
+    splice_bench()
+    sys.exit(0)
 
 
 def snapshot_bench():
