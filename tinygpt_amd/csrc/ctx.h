@@ -43,7 +43,7 @@ struct PackedMat {
   unsigned char* P = nullptr;     // planes, N * row_bytes
   tgx::u32x4* rec = nullptr;      // [N] escape records
   long long row_bytes = 0;
-  unsigned int base2 = 0;         // E0 << 7 | E0 << 23
+  unsigned int e0h4 = 0;          // E0h * 0x01010101: the window's base in every byte
   int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
   int max_row_esc = 0;            // most escapes in one row
   long long n_esc = 0;            // escapes of the matrix
@@ -166,10 +166,11 @@ struct tgx_ctx {
   bool gpt2 = false;
   std::vector<LayerW> L;
   // option weights.packed (read at tgx_finalize; default 1): bf16 gate_up / down / lm_head weights also stored exponent-packed for the batch-1 decode stream.
-  // weights.packed_classes: which classes (bit 0 gate_up, 1 down, 2 lm_head).  Default: lm_head alone — on Llama-3.2-1B the packed lm_head launch is 13-16 us
-  // shorter, the packed gate_up (+0.9 us per layer) and down (+0.4) launches are bound by the decode arithmetic, not by the stream (profiles/packed_weights.txt).
+  // weights.packed_classes: which classes (bit 0 gate_up, 1 down, 2 lm_head).  Default: gate_up and lm_head — on Llama-3.2-1B the packed lm_head launch is
+  // 14 us shorter and the packed gate_up launch 0.6 us per layer; the packed down launch (one unit per workgroup, a third of its rows with a record, 5 of 16
+  // matrices beyond the record) is 0.2 us LONGER and stays off (profiles/packed_weights_hl.txt).
   // packed_matrices / packed_fallbacks: matrices packed / fallen back to plain
-  int weights_packed = 1, packed_classes = 4, packed_matrices = 0, packed_fallbacks = 0, packed_max_row_esc = 0;
+  int weights_packed = 1, packed_classes = 5, packed_matrices = 0, packed_fallbacks = 0, packed_max_row_esc = 0;
   PackedMat plm;                // the lm_head matrix (embed when tied) exponent-packed
   float *rope_cos = nullptr, *rope_sin = nullptr;
   std::vector<RowState> rows;   // views into the per-row slabs below (constant row stride: batched GEMV walks them)

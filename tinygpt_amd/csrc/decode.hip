@@ -68,7 +68,7 @@ static void launch_gemv_packed_nx(tgx_ctx* c, const tgx::GemvPackedArgs& p, int 
 template <int PRO, int EPI>
 static void launch_gemv_packed(tgx_ctx* c, const tgx::GemvArgs& a, const PackedMat& pk, int grid, int nx) {
   tgx::GemvPackedArgs p{};
-  p.g = a; p.P = pk.P; p.rec = pk.rec; p.row_bytes = pk.row_bytes; p.base2 = pk.base2;
+  p.g = a; p.P = pk.P; p.rec = pk.rec; p.row_bytes = pk.row_bytes; p.e0h4 = pk.e0h4;
   switch (nx) {
     case 1: launch_gemv_packed_nx<PRO, EPI, 1>(c, p, grid); break;
     case 2: launch_gemv_packed_nx<PRO, EPI, 2>(c, p, grid); break;
@@ -106,8 +106,8 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
     c->packed_fallbacks++;
     return TGX_OK;
   }
-  const unsigned int E0 = (unsigned int)std::max(stat[0] - 15, 0);
-  m.base2 = (E0 << 7) | (E0 << 23); m.n_esc = stat[2]; m.max_row_esc = stat[3];
+  const unsigned int E0h = (unsigned int)std::max((stat[0] >> 1) - 7, 0);
+  m.e0h4 = E0h * 0x01010101u; m.n_esc = stat[2]; m.max_row_esc = stat[3];
   *out = m;
   c->packed_matrices++;
   return TGX_OK;

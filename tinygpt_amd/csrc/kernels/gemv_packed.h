@@ -1,27 +1,35 @@
 // gemv_packed.h — the batch-1 weight stream of gate_up, down and lm_head over bf16 weights stored as a LOSSLESS 12-bit form: 25 % fewer bytes per
 // launch, every weight the kernel multiplies bit for bit the uploaded one (DESIGN.md §5 "Exponent-packed weights").
 //
-// Format of a bf16 matrix [N][K], K % 8 == 0 (option weights.packed, made once in tgx_finalize by pack_rows_kernel below; the bf16 original stays):
-//   exponent base   E0 = max(Emax - 15, 0), Emax = the largest exponent field below 255 in the matrix.  A weight whose exponent field is E0 + c with
-//                   c in 1..15 has CODE c; every other weight (zeros, subnormals, anything below the window, inf / NaN) has code 0 = ESCAPE.
-//   chunk           8 consecutive k of a row -> 12 bytes: two dwords S0, S1 of `sign << 7 | mantissa` bytes and one dword C of eight 4-bit codes
-//                     S0 = b(w0) | b(w2) << 8 | b(w1) << 16 | b(w3) << 24        S1 = the same of w4..w7
-//                     C  = sum over t = 0..3 of code(w[2t]) << 4t | code(w[2t+1]) << (4t + 16)
-//                   (the two weights of one bf16 pair sit 16 bits apart: one shift + mask moves both codes into the exponent fields of the pair's dword)
-//   escape record   16 bytes per row: up to PACKED_ESC entries `k << 16 | bits` (the weight's true 16 bits), unused entries 0xffffffff.  A matrix with a row
-//                   of more than PACKED_ESC escapes is NOT packed (per-matrix fallback to kernels/gemv.h, decided at finalize).
+// Format "HL" of a bf16 matrix [N][K], K % 8 == 0 (option weights.packed, made once in tgx_finalize by pack_rows_kernel below; the bf16 original stays).
+// A bf16 pattern is split into its LOW byte L = e0 << 7 | mantissa (e0 = the lowest bit of the exponent field) and its HIGH byte sign << 7 | exponent_field >> 1;
+// the low byte is stored as it is, the high byte as a nibble:
+//   window          E0h = max((Emax >> 1) - 7, 0), Emax = the largest exponent field below 255 in the matrix.  IN BAND are the weights whose exponent field
+//                   lies in [2 E0h, 2 E0h + 15] without 0 and 255: 16 binades when Emax is odd, 15 when it is even.  Their nibble is n = sign << 3 | d,
+//                   d = (exponent_field >> 1) - E0h in 0..7.  Every other weight (zeros, subnormals, anything below the window, inf / NaN) is an ESCAPE: it is
+//                   written in band as n = 0, L = 0 (there is NO in-band flag) and listed in its row's record.
+//   chunk           8 consecutive k of a row -> 12 bytes: two dwords L0, L1 of the low bytes in k order (w0..w3, w4..w7) and one dword of eight nibbles
+//                     Nb = sum over t = 0..3 of n(w[t]) << 8t | n(w[4 + t]) << (8t + 4)
+//   decode          four weights at once: t = Nb & 0x0f0f0f0f (or (Nb >> 4) & 0x0f0f0f0f for w4..w7), H4 = (((t << 4) + t) & 0x87878787) + E0h * 0x01010101
+//                   (no carry crosses a byte: d + E0h <= 127); weight t as fp32 bits is H4.byte[t] << 24 | L.byte[t] << 16 — ONE byte permute with a constant
+//                   selector, no bf16 intermediate.
+//   escape record   16 bytes per row: up to PACKED_ESC entries `k << 16 | bits` (the weight's true 16 bits), unused entries 0xffffffff, filled from entry 0.
+//                   A matrix with a row of more than PACKED_ESC escapes is NOT packed (per-matrix fallback to kernels/gemv.h, decided at finalize).
 //   physical layout follows the thread -> (row, k) map of gemv_kernel launched with `ks` waves per row pair, NX = ceil(K / 8 / (64 ks)) chunks per lane:
 //                   lane l of k-part p owns chunks c = p * per + l + 64 j (per = 64 NX), j = 0..NX-1.  Its chunks go in QUADS q = j / 4 of three 1 KiB planes
-//                     plane 0: lane l's 16 bytes = S0, S1 of chunk 4q, S0, S1 of chunk 4q + 1       plane 1: the same of chunks 4q + 2, 4q + 3
-//                     plane 2: lane l's 16 bytes = C of chunks 4q .. 4q + 3
+//                     plane 0: lane l's 16 bytes = L0, L1 of chunk 4q, L0, L1 of chunk 4q + 1       plane 1: the same of chunks 4q + 2, 4q + 3
+//                     plane 2: lane l's 16 bytes = Nb of chunks 4q .. 4q + 3
 //                   row r, k-part p, quad q, plane i starts at byte r * row_bytes + ((p * NQ + q) * 3 + i) * 1024, NQ = ceil(NX / 4), row_bytes = ks * NQ * 3072.
-//                   Chunks past the row's end (j >= NX, c >= the k-part's end) are padding: S = 0, C = 0x11111111 (a finite value; its activation is zero).
+//                   Chunks past the row's end (j >= NX, c >= the k-part's end) are padding: all zero (a finite value; its activation is zero).
 //                   At the 1B / 3B / 7B shapes NX is 4 or 8 and there is no padding: 1.5 bytes per weight.
 //
-// The kernel is gemv_kernel<DT_BF16, PRO, EPI, NX, 1, XACC> (kernels/gemv.h) with the weight loads and the slice unpack replaced: a lane rebuilds the four
-// dwords of a 16-byte bf16 slice in registers and hands them to the same dot8, so the per-lane order of multiply-adds, the wave reduction and the K-part sums
-// are those of the plain kernel and the results are bit-identical.  Every lane issues 16-byte non-temporal loads over whole 1 KiB planes; the rows' escape
-// records (one 16-byte load per row, the same address in every lane) leave with the unit's weight loads; the repair is a VALU-only branch taken when a chunk's code dword has a zero nibble.
+// The kernel is gemv_kernel<DT_BF16, PRO, EPI, NX, 1, XACC> (kernels/gemv.h) with the weight loads and the dot product replaced: a lane decodes a chunk of
+// each of its unit's two rows straight into fp32 and runs the two rows' FMA chains as ONE chain of 2-vectors (v_pk_fma_f32: both halves multiply the same
+// activation).  FMA is exact per element, the element order 0..7, the even / odd-j accumulators, the wave reduction and the K-part sums are those of the
+// plain kernel: the results are bit-identical.  Every lane issues 16-byte non-temporal loads over whole 1 KiB planes; the rows' escape records (one 16-byte
+// load per row, the same address in every lane) leave with the unit's weight loads and are moved to scalar registers one unit ahead; the repair makes the
+// escape's fp32 value bits << 16 (its two bytes inserted ahead of the permute) and runs only for a row whose record is non-empty — a wave-uniform branch
+// with VALU work only, no load under it.
 #pragma once
 #include "gemv.h"
 
@@ -30,42 +38,66 @@ namespace tgx {
 constexpr int PACKED_ESC = 4;            // escape entries per row (one 16-byte record)
 constexpr int PACKED_K_MAX = 32768;      // k < 2^15: the empty entry 0xffffffff can never name a chunk of the row
 
-struct PackedQuad { u32x4 s01, s23, c; };
+struct PackedQuad { u32x4 l01, l23, nb; };      // one lane's 16 bytes of a quad's three planes
 
 struct GemvPackedArgs {
   GemvArgs g;               // g.W is not read
   const unsigned char* P;   // packed planes
   const u32x4* rec;         // [N] escape records
   long long row_bytes;
-  unsigned int base2;       // E0 << 7 | E0 << 23
+  unsigned int e0h4;        // E0h * 0x01010101
 };
 
-__device__ __forceinline__ bool packed_has_escape(unsigned int C) { return ((C - 0x11111111u) & ~C & 0x88888888u) != 0; }   // some nibble of C is 0
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// chunk (S0, S1, C) -> the 16-byte bf16 slice it encodes.  `chunk` = the chunk's index in its row.
-__device__ __forceinline__ Slice8<DT_BF16> packed_decode(unsigned int S0, unsigned int S1, unsigned int C, unsigned int base2, const u32x4 rec, int chunk) {
-  Slice8<DT_BF16> o;
-  // sign << 7 | mantissa bytes -> sign << 15 | mantissa in both halves: bytes 0, 2 are pair (w0, w1), bytes 1, 3 pair (w2, w3)
-  o.v[0] = ((S0 & 0x007f007fu) | ((S0 << 8) & 0x80008000u)) + ((( C        & 0x000f000fu) << 7) + base2);
-  o.v[1] = (((S0 >> 8) & 0x007f007fu) | (S0 & 0x80008000u)) + ((((C >> 4)  & 0x000f000fu) << 7) + base2);
-  o.v[2] = ((S1 & 0x007f007fu) | ((S1 << 8) & 0x80008000u)) + ((((C >> 8)  & 0x000f000fu) << 7) + base2);
-  o.v[3] = (((S1 >> 8) & 0x007f007fu) | (S1 & 0x80008000u)) + ((((C >> 12) & 0x000f000fu) << 7) + base2);
-  if (packed_has_escape(C)) {        // rare (benchmark checkpoint: 3e-5 of the weights); no load in here
+// acc += w * x[0] (pk_fma_x0) or w * x[1] (pk_fma_x1) in both halves: v_pk_fma_f32 with the activation's half chosen by op_sel.  Written out because
+// __builtin_elementwise_fma over a splat keeps every activation twice in registers (64 instead of 32 VGPRs at NX = 4, which spills); the instruction and its
+// per-element result are the same.
+__device__ __forceinline__ f32x2 pk_fma_x0(f32x2 w, f32x2 x, f32x2 acc) {
+  asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(w), "v"(x));
+  return acc;
+}
+__device__ __forceinline__ f32x2 pk_fma_x1(f32x2 w, f32x2 x, f32x2 acc) {
+  asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w), "v"(x));
+  return acc;
+}
+
+// four nibbles, one per byte of t -> the four high bytes sign << 7 | exponent_field >> 1
+__device__ __forceinline__ unsigned int packed_high4(unsigned int t, unsigned int e0h4) { return (((t << 4) + t) & 0x87878787u) + e0h4; }
+// weight T of a half chunk as fp32: H.byte[T] << 24 | L.byte[T] << 16 (v_perm_b32: selector bytes 4..7 name H's bytes, 0..3 L's, 0x0c a zero byte)
+template <int T> __device__ __forceinline__ float packed_weight(unsigned int H, unsigned int L) {
+  return __uint_as_float(__builtin_amdgcn_perm(H, L, ((4u + T) << 24) | ((unsigned int)T << 16) | 0x0c0cu));
+}
+// a chunk's bytes ahead of the permutes: the high bytes H0 (w0..w3), H1 (w4..w7) expanded from the nibbles, and the low bytes as loaded
+struct PackedBytes { unsigned int H0, H1, L0, L1; };
+__device__ __forceinline__ PackedBytes packed_expand(unsigned int L0, unsigned int L1, unsigned int Nb, unsigned int e0h4) {
+  return PackedBytes{packed_high4(Nb & 0x0f0f0f0fu, e0h4), packed_high4((Nb >> 4) & 0x0f0f0f0fu, e0h4), L0, L1};
+}
+__device__ __forceinline__ void packed_weights(const PackedBytes& b, float f[8]) {
+  f[0] = packed_weight<0>(b.H0, b.L0); f[1] = packed_weight<1>(b.H0, b.L0); f[2] = packed_weight<2>(b.H0, b.L0); f[3] = packed_weight<3>(b.H0, b.L0);
+  f[4] = packed_weight<0>(b.H1, b.L1); f[5] = packed_weight<1>(b.H1, b.L1); f[6] = packed_weight<2>(b.H1, b.L1); f[7] = packed_weight<3>(b.H1, b.L1);
+}
+// The repair: the row's record (in scalar registers) over the chunks c0 .. c0 + 63 that the wave's lanes hold now (c0 wave-uniform).  An escape's fp32 value
+// is bits << 16, i.e. its two bytes in the places the permute reads: the entry's bytes are inserted into the expanded H and the L dword of the lane that
+// holds its chunk (the expanded high byte is a whole byte, so every 16-bit pattern fits).  An entry of another chunk range — the empty entry names chunk
+// 8191 — costs scalar work only.
+__device__ __forceinline__ void packed_repair(PackedBytes& b, const u32x4 rec, int c0, int lane) {
 #pragma unroll
-    for (int e = 0; e < PACKED_ESC; e++) {
-      const unsigned int en = rec[e];
-      const unsigned int t = (en >> 16) & 7u, sh = (t & 1u) << 4;
-      const unsigned int dsel = (en >> 19) == (unsigned int)chunk ? (t >> 1) : 4u;      // the dword of the slice this entry replaces half of (4: none)
-      const unsigned int m = 0xffffu << sh, val = (en & 0xffffu) << sh;
-#pragma unroll
-      for (int dd = 0; dd < 4; dd++) o.v[dd] = dsel == (unsigned int)dd ? ((o.v[dd] & ~m) | val) : o.v[dd];
+  for (int e = 0; e < PACKED_ESC; e++) {
+    const unsigned int en = rec[e], l = (en >> 19) - (unsigned int)c0;
+    if (l < 64u) {
+      const unsigned int sh = (en >> 13) & 0x18u;                                   // 8 * (t & 3), t = k & 7
+      const unsigned int vh = ((en >> 8) & 0xffu) << sh, vl = (en & 0xffu) << sh;
+      const unsigned int m = (unsigned int)lane == l ? 0xffu << sh : 0u;
+      const unsigned int m0 = (en & 0x40000u) ? 0u : m, m1 = (en & 0x40000u) ? m : 0u;      // t < 4: the first half chunk
+      b.H0 = (b.H0 & ~m0) | (vh & m0); b.L0 = (b.L0 & ~m0) | (vl & m0);
+      b.H1 = (b.H1 & ~m1) | (vh & m1); b.L1 = (b.L1 & ~m1) | (vl & m1);
     }
   }
-  return o;
 }
 
 // R = 1, bf16.  The three forms: (PRO_RMSNORM, EPI_SILU_MUL), (PRO_PLAIN, EPI_RESIDUAL), (PRO_RMSNORM, EPI_LOGITS).  Everything outside load_unit and the
-// decode in front of dot8 is gemv_kernel's text for R = 1.
+// decode + dot block is gemv_kernel's text for R = 1.
 template <int PRO, int EPI, int NX, bool XACC = false>
 __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const GemvPackedArgs pa) {
   constexpr int DT = DT_BF16;
@@ -86,6 +118,7 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
   const int per = ((nchunk + KS * 64 - 1) / (KS * 64)) * 64;           // slices per k-part (multiple of 64)
   const int c_begin = min(kpart * per, nchunk), c_end = min(c_begin + per, nchunk);
   const int stride = n_wg * UPB;
+  const int c0_u = __builtin_amdgcn_readfirstlane(c_begin);            // the chunk of lane 0 at j = 0, in a scalar register (the repair's range test)
 
   int cidx[NX];
   bool cok[NX];
@@ -111,8 +144,8 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
     for (int q = 0; q < NQ; q++) {
       const u32x4* qa = reinterpret_cast<const u32x4*>(pra + (size_t)q * 3072);
       const u32x4* qb = reinterpret_cast<const u32x4*>(prb + (size_t)q * 3072);
-      ta[q].s01 = load_nt(qa); ta[q].s23 = load_nt(qa + 64); ta[q].c = load_nt(qa + 128);
-      tb[q].s01 = load_nt(qb); tb[q].s23 = load_nt(qb + 64); tb[q].c = load_nt(qb + 128);
+      ta[q].l01 = load_nt(qa); ta[q].l23 = load_nt(qa + 64); ta[q].nb = load_nt(qa + 128);
+      tb[q].l01 = load_nt(qb); tb[q].l23 = load_nt(qb + 64); tb[q].nb = load_nt(qb + 128);
     }
   };
   auto rec_uniform = [](const u32x4 v) {
@@ -141,6 +174,7 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
   }
   // 1. the first unit's weights are in flight before anything else is touched
   int ub = blockIdx.x * UPB;
+  // (only the first: a second unit sent ahead of the prologue fits the registers, and made the gate_up launch 1.8 us LONGER — profiles/packed_weights_hl.txt)
   if (ub < a.units) load_unit(ub, wa, wb, nea, neb);
   Slice8<DT> nw_x[(XACC && PRO == PRO_RMSNORM) ? NX : 1];
   if constexpr (XACC && PRO == PRO_RMSNORM) {
@@ -241,21 +275,30 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
       }
     }
 
-    float acc_a0 = 0.f, acc_b0 = 0.f, acc_a1 = 0.f, acc_b1 = 0.f;
+    // (acc_a, acc_b) of the unit's two rows as one 2-vector: the even-j and the odd-j chain, elements 0..7 in order (gemv_kernel's dot8 per row)
+    f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
+    const bool rep_a = ea[0] != 0xffffffffu, rep_b = eb[0] != 0xffffffffu;      // (wave-uniform: records fill from entry 0)
 #pragma unroll
     for (int j = 0; j < NX; j++) {
-      const f32x4 xa = f32x4{xr[j][0], xr[j][1], xr[j][2], xr[j][3]};
-      const f32x4 xb = f32x4{xr[j][4], xr[j][5], xr[j][6], xr[j][7]};
       const int q = j >> 2, jj = j & 3;
-      const u32x4 sa4 = (jj & 2) ? wa[q].s23 : wa[q].s01, sb4 = (jj & 2) ? wb[q].s23 : wb[q].s01;
-      const int chunk = c_begin + lane + 64 * j;
-      const Slice8<DT> da = packed_decode(sa4[(jj & 1) * 2], sa4[(jj & 1) * 2 + 1], wa[q].c[jj], pa.base2, ea, chunk);
-      const Slice8<DT> db = packed_decode(sb4[(jj & 1) * 2], sb4[(jj & 1) * 2 + 1], wb[q].c[jj], pa.base2, eb, chunk);
-      if (j & 1) { acc_a1 = dot8<DT>(acc_a1, da, xa, xb); acc_b1 = dot8<DT>(acc_b1, db, xa, xb); }
-      else       { acc_a0 = dot8<DT>(acc_a0, da, xa, xb); acc_b0 = dot8<DT>(acc_b0, db, xa, xb); }
+      const u32x4 la4 = (jj & 2) ? wa[q].l23 : wa[q].l01, lb4 = (jj & 2) ? wb[q].l23 : wb[q].l01;
+      PackedBytes ba = packed_expand(la4[(jj & 1) * 2], la4[(jj & 1) * 2 + 1], wa[q].nb[jj], pa.e0h4);
+      PackedBytes bb = packed_expand(lb4[(jj & 1) * 2], lb4[(jj & 1) * 2 + 1], wb[q].nb[jj], pa.e0h4);
+      if (rep_a) packed_repair(ba, ea, c0_u + 64 * j, lane);
+      if (rep_b) packed_repair(bb, eb, c0_u + 64 * j, lane);
+      float fa[8], fb[8];
+      packed_weights(ba, fa); packed_weights(bb, fb);
+      f32x2 acc = (j & 1) ? acc1 : acc0;
+#pragma unroll
+      for (int t = 0; t < 8; t += 2) {
+        const f32x2 x2 = f32x2{xr[j][t], xr[j][t + 1]};
+        acc = pk_fma_x0(f32x2{fa[t], fb[t]}, x2, acc);
+        acc = pk_fma_x1(f32x2{fa[t + 1], fb[t + 1]}, x2, acc);
+      }
+      if (j & 1) acc1 = acc; else acc0 = acc;
     }
-    float sa = wave_sum(acc_a0 + acc_a1);
-    float sb = wave_sum(acc_b0 + acc_b1);
+    float sa = wave_sum(acc0[0] + acc1[0]);
+    float sb = wave_sum(acc0[1] + acc1[1]);
 
     if (KS > 1) {   // fixed-order sum of the KS k-part partials through LDS
       __syncthreads();             // previous iteration's readers are done
@@ -325,6 +368,12 @@ __global__ __launch_bounds__(256) void packed_maxexp_kernel(const bf16_t* W, siz
   if ((threadIdx.x & 63) == 0) atomicMax(stat, m);
 }
 
+// out of the window [2 E0h, 2 E0h + 15], or a zero / subnormal / inf / NaN at its edges
+__device__ __forceinline__ bool packed_is_escape(unsigned int bits, int E0h) {
+  const int e = (int)((bits >> 7) & 0xff), d = (e >> 1) - E0h;
+  return d < 0 || d > 7 || e == 0 || e == 255;
+}
+
 struct PackRowsArgs {
   const bf16_t* W;          // [N][K]
   int N, K, ks, nx;
@@ -338,7 +387,7 @@ struct PackRowsArgs {
 __global__ __launch_bounds__(64) void pack_rows_kernel(const PackRowsArgs a) {
   __shared__ unsigned int ent[PACKED_ESC];
   const int row = blockIdx.x, lane = threadIdx.x;
-  const int E0 = max(a.stat[0] - 15, 0);
+  const int E0h = max((a.stat[0] >> 1) - 7, 0);
   const bf16_t* w = a.W + (size_t)row * a.K;
   if (lane < PACKED_ESC) ent[lane] = 0xffffffffu;
   __syncthreads();
@@ -346,7 +395,7 @@ __global__ __launch_bounds__(64) void pack_rows_kernel(const PackRowsArgs a) {
   for (int k0 = 0; k0 < a.K; k0 += 64) {
     const int k = k0 + lane;
     unsigned int bits = 0; bool esc = false;
-    if (k < a.K) { bits = w[k]; const int code = (int)((bits >> 7) & 0xff) - E0; esc = code < 1 || code > 15; }
+    if (k < a.K) { bits = w[k]; esc = packed_is_escape(bits, E0h); }
     const unsigned long long bal = __ballot(esc);
     const int p = cnt + __popcll(bal & ((1ull << lane) - 1ull));
     if (esc && p < PACKED_ESC) ent[p] = ((unsigned int)k << 16) | bits;
@@ -363,33 +412,33 @@ __global__ __launch_bounds__(64) void pack_rows_kernel(const PackRowsArgs a) {
   for (int p = 0; p < a.ks; p++) {
     const int c_begin = min(p * per, nchunk), c_end = min(c_begin + per, nchunk);
     for (int q = 0; q < nq; q++) {
-      unsigned int S[8], C[4];
+      unsigned int L[8], Nb[4];
 #pragma unroll
       for (int jj = 0; jj < 4; jj++) {
         const int j = 4 * q + jj, c = c_begin + lane + 64 * j;
-        S[2 * jj] = 0; S[2 * jj + 1] = 0; C[jj] = 0x11111111u;
+        L[2 * jj] = 0; L[2 * jj + 1] = 0; Nb[jj] = 0;
         if (j < a.nx && c < c_end) {
           const u32x4 v = reinterpret_cast<const u32x4*>(w)[c];
-          unsigned int b[8], cd[8];
+          unsigned int lo[8], n[8];
 #pragma unroll
           for (int t = 0; t < 8; t++) {
             const unsigned int bits = (v[t >> 1] >> (16 * (t & 1))) & 0xffffu;
-            const int code = (int)((bits >> 7) & 0xff) - E0;
-            b[t] = ((bits >> 8) & 0x80u) | (bits & 0x7fu);
-            cd[t] = (code < 1 || code > 15) ? 0u : (unsigned int)code;
+            const bool esc = packed_is_escape(bits, E0h);
+            lo[t] = esc ? 0u : (bits & 0xffu);
+            n[t] = esc ? 0u : (((bits >> 12) & 8u) | (((bits >> 8) & 0x7fu) - (unsigned int)E0h));
           }
-          S[2 * jj] = b[0] | (b[2] << 8) | (b[1] << 16) | (b[3] << 24);
-          S[2 * jj + 1] = b[4] | (b[6] << 8) | (b[5] << 16) | (b[7] << 24);
-          unsigned int cc = 0;
+          L[2 * jj] = lo[0] | (lo[1] << 8) | (lo[2] << 16) | (lo[3] << 24);
+          L[2 * jj + 1] = lo[4] | (lo[5] << 8) | (lo[6] << 16) | (lo[7] << 24);
+          unsigned int nn = 0;
 #pragma unroll
-          for (int t = 0; t < 4; t++) cc |= (cd[2 * t] << (4 * t)) | (cd[2 * t + 1] << (4 * t + 16));
-          C[jj] = cc;
+          for (int t = 0; t < 4; t++) nn |= (n[t] << (8 * t)) | (n[4 + t] << (8 * t + 4));
+          Nb[jj] = nn;
         }
       }
       u32x4* dst = reinterpret_cast<u32x4*>(a.P + (size_t)row * a.row_bytes + ((size_t)p * nq + q) * 3072) + lane;
-      dst[0] = u32x4{S[0], S[1], S[2], S[3]};
-      dst[64] = u32x4{S[4], S[5], S[6], S[7]};
-      dst[128] = u32x4{C[0], C[1], C[2], C[3]};
+      dst[0] = u32x4{L[0], L[1], L[2], L[3]};
+      dst[64] = u32x4{L[4], L[5], L[6], L[7]};
+      dst[128] = u32x4{Nb[0], Nb[1], Nb[2], Nb[3]};
     }
   }
 }

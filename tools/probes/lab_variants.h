@@ -426,7 +426,105 @@ static void lab_qkv_attn(Lab& b) {
   CK(hipFree(f.gq)); CK(hipFree(f.gkv)); CK(hipFree(f.epoch)); CK(hipFree(f.part2)); CK(hipFree(acc));
 }
 
+
+// ---- LAB_PACKED=1: gate_up and down over the exponent-packed "HL" form (kernels/gemv_packed.h) beside the plain kernels, on the same weights ----
+// value check = bit equality of the outputs with the plain kernels (layers whose matrix has a row beyond the escape record are left out of it and counted);
+// axes: workgroups per CU (bpc: fewer workgroups = more units per wave, which is where the one-unit-ahead prefetch and the early second unit matter).
+#include "kernels/gemv_packed.h"
+struct LabPacked { unsigned char* P; u32x4* rec; long long row_bytes; unsigned int e0h4; int overflow_rows, escapes, most; };
+static LabPacked lab_pack(Lab& b, const unsigned short* W, int N, int K, int ks, int* stat_dev) {
+  LabPacked m{};
+  const int nx = b.nx_of(K, ks);
+  m.row_bytes = (long long)ks * ((nx + 3) / 4) * 3072;
+  CK(hipMalloc(&m.P, (size_t)N * (size_t)m.row_bytes)); CK(hipMalloc(&m.rec, (size_t)N * 16));
+  CK(hipMemsetAsync(stat_dev, 0, 16, b.st));
+  const size_t n8 = (size_t)N * K / 8;
+  hipLaunchKernelGGL(packed_maxexp_kernel, dim3(4096), dim3(256), 0, b.st, W, n8, stat_dev);
+  PackRowsArgs a{};
+  a.W = W; a.N = N; a.K = K; a.ks = ks; a.nx = nx; a.P = m.P; a.rec = m.rec; a.row_bytes = m.row_bytes; a.stat = stat_dev;
+  hipLaunchKernelGGL(pack_rows_kernel, dim3(N), dim3(64), 0, b.st, a);
+  int stat[4];
+  CK(hipMemcpyAsync(stat, stat_dev, 16, hipMemcpyDeviceToHost, b.st)); CK(hipStreamSynchronize(b.st));
+  m.e0h4 = (unsigned int)std::max((stat[0] >> 1) - 7, 0) * 0x01010101u; m.overflow_rows = stat[1]; m.escapes = stat[2]; m.most = stat[3];
+  return m;
+}
+template <int PRO, int EPI>
+static void launch_packed(Lab& b, const GemvArgs& g, const LabPacked& pk, int ks, int bpc) {
+  GemvPackedArgs p{};
+  p.g = g; p.P = pk.P; p.rec = pk.rec; p.row_bytes = pk.row_bytes; p.e0h4 = pk.e0h4;
+  const int nx = b.nx_of(g.K, ks), gr = b.grid_of(g.units, ks, bpc);
+  switch (nx) {
+    case 1: hipLaunchKernelGGL((gemv_packed_kernel<PRO, EPI, 1>), dim3(gr), dim3(256), 0, b.st, p); break;
+    case 2: hipLaunchKernelGGL((gemv_packed_kernel<PRO, EPI, 2>), dim3(gr), dim3(256), 0, b.st, p); break;
+    case 3: hipLaunchKernelGGL((gemv_packed_kernel<PRO, EPI, 3>), dim3(gr), dim3(256), 0, b.st, p); break;
+    case 4: hipLaunchKernelGGL((gemv_packed_kernel<PRO, EPI, 4>), dim3(gr), dim3(256), 0, b.st, p); break;
+    default: printf("lab: packed forms are instantiated for NX <= 4 here (NX = %d)\n", nx); exit(1);
+  }
+}
+static GemvArgs gateup_args(Lab& b, int l, float* out) {
+  const LayerBuf& w = b.lb[(size_t)l];
+  GemvArgs u{};
+  u.W = w.wgu; u.x = b.x; u.norm_w = w.post_norm; u.eps = b.eps; u.N = 2 * b.I; u.K = b.H; u.ldw = b.H; u.units = b.I; u.ks = 1; u.out = out; u.hd = 2;
+  return u;
+}
+static GemvArgs down_args(Lab& b, int l, float* resid) {
+  const LayerBuf& w = b.lb[(size_t)l];
+  GemvArgs d{};
+  d.W = w.wdown; d.x = b.h; d.N = b.H; d.K = b.I; d.ldw = b.I; d.units = b.H / 2; d.ks = 4; d.out = resid; d.hd = 2;
+  return d;
+}
+static void lab_packed(Lab& b) {
+  int* stat_dev; CK(hipMalloc(&stat_dev, 16));
+  std::vector<LabPacked> pgu((size_t)b.L), pdn((size_t)b.L);
+  int over_gu = 0, over_dn = 0, most_gu = 0, most_dn = 0; long long esc_gu = 0, esc_dn = 0;
+  for (int l = 0; l < b.L; l++) {
+    pgu[(size_t)l] = lab_pack(b, b.lb[(size_t)l].wgu, 2 * b.I, b.H, 1, stat_dev);
+    pdn[(size_t)l] = lab_pack(b, b.lb[(size_t)l].wdown, b.H, b.I, 4, stat_dev);
+    over_gu += pgu[(size_t)l].overflow_rows > 0; over_dn += pdn[(size_t)l].overflow_rows > 0;
+    esc_gu += pgu[(size_t)l].escapes; esc_dn += pdn[(size_t)l].escapes;
+    most_gu = std::max(most_gu, pgu[(size_t)l].most); most_dn = std::max(most_dn, pdn[(size_t)l].most);
+  }
+  printf("packed: gate_up escapes %lld (most in a row %d, %d of %d matrices beyond the record), down %lld (%d, %d of %d)\n", esc_gu, most_gu, over_gu, b.L, esc_dn, most_dn, over_dn, b.L);
+  // value check: every layer within the record, outputs as uint32
+  float *h2, *r1, *r2; CK(hipMalloc(&h2, (size_t)b.I * 4)); CK(hipMalloc(&r1, (size_t)b.H * 4)); CK(hipMalloc(&r2, (size_t)b.H * 4));
+  std::vector<unsigned int> va((size_t)b.I), vb((size_t)b.I);
+  long long bad_gu = 0, bad_dn = 0; int checked_gu = 0, checked_dn = 0;
+  for (int l = 0; l < b.L; l++) {
+    if (!pgu[(size_t)l].overflow_rows) {
+      p_gateup(b, l, nullptr);
+      launch_packed<PRO_RMSNORM, EPI_SILU_MUL>(b, gateup_args(b, l, h2), pgu[(size_t)l], 1, 4);
+      CK(hipMemcpyAsync(va.data(), b.h, (size_t)b.I * 4, hipMemcpyDeviceToHost, b.st)); CK(hipMemcpyAsync(vb.data(), h2, (size_t)b.I * 4, hipMemcpyDeviceToHost, b.st));
+      CK(hipStreamSynchronize(b.st));
+      for (int i = 0; i < b.I; i++) bad_gu += va[(size_t)i] != vb[(size_t)i];
+      checked_gu++;
+    }
+  }
+  hipLaunchKernelGGL(fill_f32, dim3(32), dim3(256), 0, b.st, b.h, (size_t)b.I, 81u, 1.0f, 0.f);      // (the down input as main() made it)
+  for (int l = 0; l < b.L; l++) {
+    if (!pdn[(size_t)l].overflow_rows) {
+      CK(hipMemcpyAsync(r1, b.x, (size_t)b.H * 4, hipMemcpyDeviceToDevice, b.st)); CK(hipMemcpyAsync(r2, b.x, (size_t)b.H * 4, hipMemcpyDeviceToDevice, b.st));
+      p_down(b, l, r1);
+      launch_packed<PRO_PLAIN, EPI_RESIDUAL>(b, down_args(b, l, r2), pdn[(size_t)l], 4, 4);
+      CK(hipMemcpyAsync(va.data(), r1, (size_t)b.H * 4, hipMemcpyDeviceToHost, b.st)); CK(hipMemcpyAsync(vb.data(), r2, (size_t)b.H * 4, hipMemcpyDeviceToHost, b.st));
+      CK(hipStreamSynchronize(b.st));
+      for (int i = 0; i < b.H; i++) bad_dn += va[(size_t)i] != vb[(size_t)i];
+      checked_dn++;
+    }
+  }
+  printf("packed vs plain, outputs as uint32: gate_up %lld differing of %d x %d, down %lld differing of %d x %d\n", bad_gu, checked_gu, b.I, bad_dn, checked_dn, b.H);
+  if (bad_gu || bad_dn) { printf("packed: VALUE CHECK FAILED\n"); exit(1); }
+  const float tg = time_graph(b, [&] { for (int l = 0; l < b.L; l++) p_gateup(b, l, nullptr); }, b.L);
+  const float td = time_graph(b, [&] { for (int l = 0; l < b.L; l++) p_down(b, l, b.scratch_x); }, b.L);
+  printf("plain (bpc 4):   gate_up %6.2f us   down %6.2f us\n", tg, td);
+  for (int bpc : {4, 3, 2, 1}) {
+    const float pg = time_graph(b, [&] { for (int l = 0; l < b.L; l++) launch_packed<PRO_RMSNORM, EPI_SILU_MUL>(b, gateup_args(b, l, h2), pgu[(size_t)l], 1, bpc); }, b.L);
+    const float pd = time_graph(b, [&] { for (int l = 0; l < b.L; l++) launch_packed<PRO_PLAIN, EPI_RESIDUAL>(b, down_args(b, l, b.scratch_x), pdn[(size_t)l], 4, bpc); }, b.L);
+    printf("packed (bpc %d):  gate_up %6.2f us   down %6.2f us\n", bpc, pg, pd);
+  }
+}
+
 static void lab_variants_main(Lab& b) {
+  if (getenv("LAB_PACKED")) { lab_packed(b); return; }
   if (getenv("LAB_FUSE")) { lab_qkv_attn(b); return; }
   if (getenv("LAB_MLP")) { lab_mlp_fused(b); return; }
   if (getenv("LAB_OPROJ")) { lab_oproj_shapes(b); return; }

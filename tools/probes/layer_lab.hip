@@ -4,6 +4,7 @@
 // against the product kernels on identical data before they enter csrc/decode.hip.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form -DLAB_VARIANTS -DLAB_EPOCH -I../../tinygpt_amd/csrc layer_lab.hip -o build/layer_lab
 // Run:   layer_lab [geom=1b|0.5b|3b|7b] [pos=2064] [layers=16] [nsplit=CUs / kv heads, <= 32]
+//        LAB_PACKED=1 layer_lab 1b: gate_up and down over the exponent-packed form (kernels/gemv_packed.h) beside the plain kernels (lab_variants.h lab_packed)
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
