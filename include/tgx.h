@@ -820,6 +820,7 @@ TGX_API int tgx_set_logits(tgx_ctx* ctx, const float* logits, int batch);
 /* Launch-geometry knobs for tuning sweeps (results stay within the parity tolerances; summation order may change):
  *   "<class>.ks"   waves sharing a row pair's K range (1/2/4), class in {qkv,oproj,gateup,down,lmhead}
  *   "<class>.bpc"  grid cap in workgroups per CU ("lmhead.bpc" only before tgx_finalize)
+ *   "<class>.packed_bpc"  the same for the class's exponent-packed batch-1 launch, class in {gateup,down,lmhead} (default 3 / 4 / 4; "lmhead.packed_bpc" only before tgx_finalize)
  *   "attn.nsplit"  KV splits per kv head (<= 32, before tgx_finalize); "attn.gmax" query heads per attention workgroup
  *   "attn.direct_max"  contexts up to this many keys run attention as one workgroup per head group, without the combine launch (default 768 at head_dim 64, 384 at 128; 0 = never)
  *   "graph" 0/1    hipGraph replay vs eager launches; "graph.steps" decode steps per graph for long tgx_decode calls

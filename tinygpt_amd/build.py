@@ -28,7 +28,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h")]
+            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -119,6 +119,11 @@ def build_row_snapshot_check(force: bool = False, verbose: bool = False):
 def build_attn_worklist_check(force: bool = False, verbose: bool = False):
     """tests/attn_worklist_check.cpp, the CPU audit of csrc/attn_worklist.h."""
     return _build_cpu_check("attn_worklist_check", os.path.join(CSRC, "attn_worklist.h"), force, verbose)
+
+
+def build_gemv_grid_check(force: bool = False, verbose: bool = False):
+    """tests/gemv_grid_check.cpp, the CPU audit of csrc/gemv_grid.h."""
+    return _build_cpu_check("gemv_grid_check", os.path.join(CSRC, "gemv_grid.h"), force, verbose)
 
 
 def build_spec_draft_check(force: bool = False, verbose: bool = False):

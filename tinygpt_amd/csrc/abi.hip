@@ -767,7 +767,10 @@ int tgx_create(const tgx_model_desc* desc, int device_ordinal, tgx_ctx** out_ctx
   // very short prompts: ONE pass through the batched decode kernels (4 positions) still beats the skinny MFMA prefill on small models
   // (Llama-3.2-1B: S = 4 1.00 vs 1.07 ms, S = 5 1.55 vs 1.07; Mistral-7B S = 4 4.65 vs 4.09) — tools/prefill_crossover.py, profiles/r02_prefill_short.txt
   c->prefill_min_rows = d.hidden > 2048 ? 4 : 5;
-  c->tune[TGX_KERNEL_DOWN].ks = d.inter >= 8192 ? 4 : 2;   // K = intermediate_size: 4 waves split each row pair (2 below 8192 columns: Qwen2.5-0.5B 0.549 -> 0.542 ms/token, tools/sweep.py round 4)
+  // the packed gate_up launch at 3 workgroups per CU (768 on 256 CUs: its waves take 3, 3, 2 units instead of 2 each): Llama-3.2-1B 0.6295 -> 0.6162 ms per token,
+  // -13 us over 16 launches; packed down and lm_head are best at 4 (profiles/packed_kpart_geometry.txt section 4)
+  c->tune[TGX_KERNEL_GATEUP].packed_bpc = 3;
+  c->tune[TGX_KERNEL_DOWN].ks = d.inter >= 8192 ? 4 : 2;  // K = intermediate_size: 4 waves split each row pair (2 below 8192 columns: Qwen2.5-0.5B 0.549 -> 0.542 ms/token, tools/sweep.py round 4)
   // qkv is the most latency-bound launch (few rows): 4 waves per row pair shorten every wave's load -> reduce chain; measured
   // ks 1 -> 4: Llama-3.2-1B 1395 -> 1411 tok/s, 3B 628 -> 637, Mistral-7B 341 -> 347; hidden 896 (Qwen2.5-0.5B) loses 2 %
   c->tune[TGX_KERNEL_QKV].ks = d.hidden >= 2048 ? 4 : 1;
@@ -911,7 +914,10 @@ int tgx_finalize(tgx_ctx* c) {
   HIP_OK(c, hipMemcpy(c->rope_cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
   HIP_OK(c, hipMemcpy(c->rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
 
-  c->lm_grid = gemv_grid(c, (V + 1) / 2, 1, c->tune[TGX_KERNEL_LMHEAD].bpc);
+  // one grid for every lm_head launch (it sizes the argmax partials): the packed launch's workgroups per CU where the options ask for a packed lm_head
+  // (pack_weights runs below; a lm_head that then falls back, and the batched steps, run their plain kernels on this grid too)
+  const bool lm_packed = c->weights_packed && (c->packed_classes & 4) && c->dt == tgx::DT_BF16 && !c->gpt2;
+  c->lm_grid = gemv_grid(c, (V + 1) / 2, 1, lm_packed ? c->tune[TGX_KERNEL_LMHEAD].packed_bpc : c->tune[TGX_KERNEL_LMHEAD].bpc);
   int ns = c->num_cus / d.kv_heads;
   c->attn_nsplit = ns < 1 ? 1 : (ns > 32 ? 32 : ns);
   if (c->attn_nsplit_opt > 0) c->attn_nsplit = c->attn_nsplit_opt;
@@ -2928,6 +2934,12 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
       c->tune[i].bpc = value;
       return TGX_OK;
     }
+    if (!strcmp(key + n + 1, "packed_bpc") && (i == TGX_KERNEL_GATEUP || i == TGX_KERNEL_DOWN || i == TGX_KERNEL_LMHEAD)) {      // the classes with a packed form
+      if (value < 1 || value > 16) return set_err(c, TGX_ERR_INVALID, "packed_bpc out of range");
+      if (i == TGX_KERNEL_LMHEAD && c->finalized) return set_err(c, TGX_ERR_STATE, "lmhead.packed_bpc must be set before tgx_finalize");
+      c->tune[i].packed_bpc = value;
+      return TGX_OK;
+    }
   }
   return set_err(c, TGX_ERR_INVALID, "unknown option %s", key);
 }
@@ -2944,7 +2956,7 @@ int64_t tgx_bytes_per_token(const tgx_ctx* c, int64_t T) {
   const int64_t per_layer = (q + 2 * kv) * H + (d.qkv_bias ? (q + 2 * kv) : 0) + H * q + 2 * I * H + H * I + 2 * H;
   // exponent-packed matrices (option weights.packed) stream their planes and escape records instead of 2 bytes per weight
   int64_t saved = 0;
-  auto packed_saving = [&](const PackedMat& m, int64_t rows, int64_t cols) { if (m.P) saved += b * rows * cols - rows * (m.row_bytes + 16); };
+  auto packed_saving = [&](const PackedMat& m, int64_t rows, int64_t cols) { if (m.P) saved += b * rows * cols - rows * (m.row_bytes + 16 * m.ks); };      // (one 16-byte record per row and K-part)
   for (const LayerW& w : c->L) { packed_saving(w.pgu, 2 * I, H); packed_saving(w.pdown, H, I); }
   packed_saving(c->plm, V, H);
   return b * (L * per_layer + H + V * H) + b * 2 * L * kv * T - saved;

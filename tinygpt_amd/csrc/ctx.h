@@ -41,7 +41,7 @@ constexpr int HOST_RING = 256;
 // read by the batch-1 decode launches of its class.  P == nullptr: not packed (option off, class not adopted, other dtype / shape, or a row's escapes overflowed)
 struct PackedMat {
   unsigned char* P = nullptr;     // planes, N * row_bytes
-  tgx::u32x4* rec = nullptr;      // [N] escape records
+  tgx::u32x4* rec = nullptr;      // [N][ks] escape records, one per (row, K-part)
   long long row_bytes = 0;
   unsigned int e0h4 = 0;          // E0h * 0x01010101: the window's base in every byte
   int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
@@ -95,6 +95,10 @@ struct RowHost {        // host state of one batch row
 struct Tune {
   int ks = 1;    // waves sharing one unit's K range (1, 2, 4)
   int bpc = 4;   // grid cap in workgroups per CU
+  // the same for the class's exponent-packed batch-1 launch (gate_up, down, lm_head; option <class>.packed_bpc) — the plain kernel of the class (fallen-back
+  // matrices, other dtypes, batched steps) keeps bpc.  gate_up: 3 (tgx_create; -13 us per token on Llama-3.2-1B, also ahead on the 3B and Qwen2.5-0.5B shapes);
+  // down and lm_head measured best at 4.  The lm_head's value is read at tgx_finalize, where lm_grid is fixed (profiles/packed_kpart_geometry.txt).
+  int packed_bpc = 4;
 };
 
 struct Profiler {
@@ -167,8 +171,9 @@ struct tgx_ctx {
   std::vector<LayerW> L;
   // option weights.packed (read at tgx_finalize; default 1): bf16 gate_up / down / lm_head weights also stored exponent-packed for the batch-1 decode stream.
   // weights.packed_classes: which classes (bit 0 gate_up, 1 down, 2 lm_head).  Default: gate_up and lm_head — on Llama-3.2-1B the packed lm_head launch is
-  // 14 us shorter and the packed gate_up launch 0.6 us per layer; the packed down launch (one unit per workgroup, a third of its rows with a record, 5 of 16
-  // matrices beyond the record) is 0.2 us LONGER and stays off (profiles/packed_weights_hl.txt).
+  // 14 us shorter and the packed gate_up launch 0.6 us per layer (1.5 us at its own 3 workgroups per CU, Tune::packed_bpc).  The packed down launch stays off:
+  // with the escape records kept per (row, K-part) — 15 of its 16 matrices packed, a tenth of its waves with a record instead of a third — the step with it
+  // measures the same as without it (0.6286 against 0.6288 ms, inside the run-to-run spread; profiles/packed_kpart_geometry.txt, profiles/packed_weights_hl.txt).
   // packed_matrices / packed_fallbacks: matrices packed / fallen back to plain
   int weights_packed = 1, packed_classes = 5, packed_matrices = 0, packed_fallbacks = 0, packed_max_row_esc = 0;
   PackedMat plm;                // the lm_head matrix (embed when tied) exponent-packed

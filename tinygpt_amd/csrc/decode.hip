@@ -2,18 +2,14 @@
 // split-form attention (kernels/oproj_sliced.h), lm_head + per-workgroup argmax, the greedy finalize.
 // == for (auto& layer : layers_) x = layer->forward(x); norm; lm_head  (GPTModel.h:51-58, DecoderLayer.h:38-43, Attention.h:71-91, GatedMLP.h:37-41)
 #include "ctx.h"
+#include "gemv_grid.h"
 #include "kernels/attn_decode.h"
 #include "kernels/gemv.h"
 #include "kernels/gemv_packed.h"
 #include "kernels/oproj_sliced.h"
 #include "kernels/verify.h"
 
-int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc) {
-  const int upb = 4 / ks;
-  const int want = (units + upb - 1) / upb;
-  const int cap = c->num_cus * bpc;
-  return want < cap ? want : cap;
-}
+int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc) { return tgx::gemv_grid_plan(units, 4 / ks, c->num_cus * bpc).grid; }
 
 // 16-byte slices per lane per row for a K range split over ks waves (the kernel's NX template parameter)
 static int gemv_nx(int K, int ks) { return ((K / 8) + ks * 64 - 1) / (ks * 64); }
@@ -89,7 +85,7 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
   PackedMat m;
   m.ks = ks; m.row_bytes = (long long)ks * ((nx + 3) / 4) * 3072;
   int rc;
-  if ((rc = dev_alloc(c, &m.P, (size_t)N * (size_t)m.row_bytes)) || (rc = dev_alloc(c, &m.rec, (size_t)N))) { dev_free(c, &m.P); return rc; }
+  if ((rc = dev_alloc(c, &m.P, (size_t)N * (size_t)m.row_bytes)) || (rc = dev_alloc(c, &m.rec, (size_t)N * (size_t)ks))) { dev_free(c, &m.P); return rc; }
   HIP_OK(c, hipMemsetAsync(stat_dev, 0, 4 * sizeof(int), c->stream));
   const size_t n8 = (size_t)N * K / 8;
   hipLaunchKernelGGL(tgx::packed_maxexp_kernel, dim3((unsigned)std::min<size_t>((n8 + 255) / 256, 4096)), dim3(256), 0, c->stream, reinterpret_cast<const bf16_t*>(W), n8, stat_dev);
@@ -101,7 +97,7 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
   HIP_OK(c, hipMemcpyAsync(stat, stat_dev, sizeof(stat), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->packed_max_row_esc = std::max(c->packed_max_row_esc, stat[3]);
-  if (stat[1] > 0) {       // a row's escapes do not fit its record: this matrix stays plain
+  if (stat[1] > 0) {       // a (row, K-part)'s escapes do not fit its record: this matrix stays plain
     dev_free(c, &m.P); dev_free(c, &m.rec);
     c->packed_fallbacks++;
     return TGX_OK;
@@ -142,7 +138,11 @@ static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const Packe
   const int nx = gemv_nx(a.K, a.ks);
   if constexpr ((PRO == tgx::PRO_RMSNORM && (EPI == tgx::EPI_SILU_MUL || EPI == tgx::EPI_LOGITS)) || (PRO == tgx::PRO_PLAIN && EPI == tgx::EPI_RESIDUAL)) {
     // batch 1 over an exponent-packed matrix laid out for this K split: 25 % fewer bytes, bit-identical results
-    if (pk && pk->P && R == 1 && pk->ks == a.ks && a.ldw == a.K && !a.dbg) { launch_gemv_packed<PRO, EPI>(c, a, *pk, grid, nx); return; }
+    // (its own workgroups per CU, Tune::packed_bpc; the lm_head's grid is lm_grid in both forms: it sizes the argmax partials)
+    if (pk && pk->P && R == 1 && pk->ks == a.ks && a.ldw == a.K && !a.dbg) {
+      launch_gemv_packed<PRO, EPI>(c, a, *pk, (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc), nx);
+      return;
+    }
   }
   if constexpr (PRO == tgx::PRO_LAYERNORM || EPI == tgx::EPI_GELU) {   // GPT-2 (hidden <= 2048, checked in tgx_create): at most 4 slices per lane
     TGX_DT_SWITCH(c->dt, switch (nx) {

@@ -13,8 +13,11 @@
 //   decode          four weights at once: t = Nb & 0x0f0f0f0f (or (Nb >> 4) & 0x0f0f0f0f for w4..w7), H4 = (((t << 4) + t) & 0x87878787) + E0h * 0x01010101
 //                   (no carry crosses a byte: d + E0h <= 127); weight t as fp32 bits is H4.byte[t] << 24 | L.byte[t] << 16 — ONE byte permute with a constant
 //                   selector, no bf16 intermediate.
-//   escape record   16 bytes per row: up to PACKED_ESC entries `k << 16 | bits` (the weight's true 16 bits), unused entries 0xffffffff, filled from entry 0.
-//                   A matrix with a row of more than PACKED_ESC escapes is NOT packed (per-matrix fallback to kernels/gemv.h, decided at finalize).
+//   escape record   16 bytes per (row, k-part), rec[row * ks + p]: up to PACKED_ESC entries `k << 16 | bits` (k the ROW's k, bits the weight's true 16 bits) of
+//                   the escapes whose chunk k / 8 lies in k-part p's range [c_begin(p), c_end(p)) (below), in k order from entry 0, unused entries 0xffffffff.
+//                   A wave of a K-split launch reads the record of its own k-part only: it never walks the escapes of the other waves' ranges.  At ks = 1
+//                   this is one record per row.  A matrix with more than PACKED_ESC escapes in one (row, k-part) is NOT packed (per-matrix fallback to
+//                   kernels/gemv.h, decided at finalize).
 //   physical layout follows the thread -> (row, k) map of gemv_kernel launched with `ks` waves per row pair, NX = ceil(K / 8 / (64 ks)) chunks per lane:
 //                   lane l of k-part p owns chunks c = p * per + l + 64 j (per = 64 NX), j = 0..NX-1.  Its chunks go in QUADS q = j / 4 of three 1 KiB planes
 //                     plane 0: lane l's 16 bytes = L0, L1 of chunk 4q, L0, L1 of chunk 4q + 1       plane 1: the same of chunks 4q + 2, 4q + 3
@@ -26,16 +29,16 @@
 // The kernel is gemv_kernel<DT_BF16, PRO, EPI, NX, 1, XACC> (kernels/gemv.h) with the weight loads and the dot product replaced: a lane decodes a chunk of
 // each of its unit's two rows straight into fp32 and runs the two rows' FMA chains as ONE chain of 2-vectors (v_pk_fma_f32: both halves multiply the same
 // activation).  FMA is exact per element, the element order 0..7, the even / odd-j accumulators, the wave reduction and the K-part sums are those of the
-// plain kernel: the results are bit-identical.  Every lane issues 16-byte non-temporal loads over whole 1 KiB planes; the rows' escape records (one 16-byte
-// load per row, the same address in every lane) leave with the unit's weight loads and are moved to scalar registers one unit ahead; the repair makes the
-// escape's fp32 value bits << 16 (its two bytes inserted ahead of the permute) and runs only for a row whose record is non-empty — a wave-uniform branch
-// with VALU work only, no load under it.
+// plain kernel: the results are bit-identical.  Every lane issues 16-byte non-temporal loads over whole 1 KiB planes; the escape records of the wave's k-part
+// of its two rows (one 16-byte load per row, the same address in every lane) leave with the unit's weight loads and are moved to scalar registers one unit
+// ahead; the repair makes the escape's fp32 value bits << 16 (its two bytes inserted ahead of the permute) and runs only in a wave whose own record is
+// non-empty — a wave-uniform branch with VALU work only, no load under it.
 #pragma once
 #include "gemv.h"
 
 namespace tgx {
 
-constexpr int PACKED_ESC = 4;            // escape entries per row (one 16-byte record)
+constexpr int PACKED_ESC = 4;            // escape entries per (row, K-part) (one 16-byte record)
 constexpr int PACKED_K_MAX = 32768;      // k < 2^15: the empty entry 0xffffffff can never name a chunk of the row
 
 struct PackedQuad { u32x4 l01, l23, nb; };      // one lane's 16 bytes of a quad's three planes
@@ -43,7 +46,7 @@ struct PackedQuad { u32x4 l01, l23, nb; };      // one lane's 16 bytes of a quad
 struct GemvPackedArgs {
   GemvArgs g;               // g.W is not read
   const unsigned char* P;   // packed planes
-  const u32x4* rec;         // [N] escape records
+  const u32x4* rec;         // [N][ks] escape records
   long long row_bytes;
   unsigned int e0h4;        // E0h * 0x01010101
 };
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
     const int u = min(ub + slot, a.units - 1);
     int ra, rb; bool v;
     unit_rows<EPI>(a, u, ra, rb, v);
-    ra_rec = pa.rec[ra]; rb_rec = pa.rec[rb];
+    ra_rec = pa.rec[(size_t)ra * KS + kpart]; rb_rec = pa.rec[(size_t)rb * KS + kpart];      // this wave's K-part of either row
     const unsigned char* pra = pa.P + (size_t)ra * pa.row_bytes + lane_off;
     const unsigned char* prb = pa.P + (size_t)rb * pa.row_bytes + lane_off;
 #pragma unroll
@@ -277,7 +280,7 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
 
     // (acc_a, acc_b) of the unit's two rows as one 2-vector: the even-j and the odd-j chain, elements 0..7 in order (gemv_kernel's dot8 per row)
     f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
-    const bool rep_a = ea[0] != 0xffffffffu, rep_b = eb[0] != 0xffffffffu;      // (wave-uniform: records fill from entry 0)
+    const bool rep_a = ea[0] != 0xffffffffu, rep_b = eb[0] != 0xffffffffu;      // (wave-uniform: records fill from entry 0; true only where this wave's own K-part holds an escape)
 #pragma unroll
     for (int j = 0; j < NX; j++) {
       const int q = j >> 2, jj = j & 3;
@@ -351,7 +354,7 @@ __global__ __launch_bounds__(256, NX <= 4 ? 4 : 1) void gemv_packed_kernel(const
 }
 
 // ---- the packer (tgx_finalize) ---------------------------------------------------------------------------------------------------------------------
-// stat[0] = Emax, stat[1] = rows whose record overflowed, stat[2] = escapes of the matrix, stat[3] = most escapes in one row
+// stat[0] = Emax, stat[1] = rows with a K-part whose record overflowed, stat[2] = escapes of the matrix, stat[3] = most escapes in one ROW (all its K-parts)
 __global__ __launch_bounds__(256) void packed_maxexp_kernel(const bf16_t* W, size_t n8, int* stat) {
   int m = 0;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
@@ -383,32 +386,36 @@ struct PackRowsArgs {
   int* stat;
 };
 
-// one wave per row: the row's escape record, then its planes
+// one wave per row: the records of the row's K-parts (ks <= 4), then its planes
 __global__ __launch_bounds__(64) void pack_rows_kernel(const PackRowsArgs a) {
-  __shared__ unsigned int ent[PACKED_ESC];
+  __shared__ unsigned int ent[4][PACKED_ESC];
   const int row = blockIdx.x, lane = threadIdx.x;
   const int E0h = max((a.stat[0] >> 1) - 7, 0);
   const bf16_t* w = a.W + (size_t)row * a.K;
-  if (lane < PACKED_ESC) ent[lane] = 0xffffffffu;
+  const int nchunk = a.K >> 3, nq = (a.nx + 3) / 4;
+  const int per = ((nchunk + a.ks * 64 - 1) / (a.ks * 64)) * 64;
+  if (lane < 4 * PACKED_ESC) ent[lane / PACKED_ESC][lane % PACKED_ESC] = 0xffffffffu;
   __syncthreads();
-  int cnt = 0;
+  int cnt = 0, part = 0, pcnt = 0, pmax = 0;      // escapes of the row; the K-part of the 64 k at hand and its escapes so far; the most in one K-part
   for (int k0 = 0; k0 < a.K; k0 += 64) {
+    // the 8 chunks k0 / 8 .. k0 / 8 + 7 lie in one K-part (`per` is a multiple of 64 chunks), the one whose [c_begin, c_end) holds them; k ascends, so do the parts
+    const int kp = (k0 >> 3) / per;
+    if (kp != part) { part = kp; pcnt = 0; }
     const int k = k0 + lane;
     unsigned int bits = 0; bool esc = false;
     if (k < a.K) { bits = w[k]; esc = packed_is_escape(bits, E0h); }
     const unsigned long long bal = __ballot(esc);
-    const int p = cnt + __popcll(bal & ((1ull << lane) - 1ull));
-    if (esc && p < PACKED_ESC) ent[p] = ((unsigned int)k << 16) | bits;
-    cnt += __popcll(bal);
+    const int p = pcnt + __popcll(bal & ((1ull << lane) - 1ull));
+    if (esc && p < PACKED_ESC) ent[part][p] = ((unsigned int)k << 16) | bits;
+    const int n = __popcll(bal);
+    cnt += n; pcnt += n; pmax = max(pmax, pcnt);
   }
   __syncthreads();
+  if (lane < a.ks) a.rec[(size_t)row * a.ks + lane] = u32x4{ent[lane][0], ent[lane][1], ent[lane][2], ent[lane][3]};
   if (lane == 0) {
-    a.rec[row] = u32x4{ent[0], ent[1], ent[2], ent[3]};
-    if (cnt > PACKED_ESC) atomicAdd(a.stat + 1, 1);
+    if (pmax > PACKED_ESC) atomicAdd(a.stat + 1, 1);
     if (cnt) { atomicAdd(a.stat + 2, cnt); atomicMax(a.stat + 3, cnt); }
   }
-  const int nchunk = a.K >> 3, nq = (a.nx + 3) / 4;
-  const int per = ((nchunk + a.ks * 64 - 1) / (a.ks * 64)) * 64;
   for (int p = 0; p < a.ks; p++) {
     const int c_begin = min(p * per, nchunk), c_end = min(c_begin + per, nchunk);
     for (int q = 0; q < nq; q++) {
