@@ -38,6 +38,7 @@ extern "C" {
 /* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
 /* (still 3: additive) tgx_row_snapshot_bytes / tgx_save_row / tgx_restore_row — a live row saved to host memory and restored into any row of any context of the same geometry. */
 /* (still 3: additive) tgx_embed_rows — the pooled final hidden state (last / mean / first) of several texts in one ragged pass, without lm_head. */
+/* (still 3: additive) tgx_beam_select / tgx_beam_advance — beam search: the joint ranking of several rows' distributions on the device, a group of rows re-seated in place. */
 #define TGX_ABI_VERSION 3
 
 #if defined(__GNUC__)
@@ -276,6 +277,61 @@ TGX_API int tgx_decode_rows(tgx_ctx* ctx, int n_steps, int64_t* out_ids, int32_t
  *   Cost              one copy launch per call (per 128 destinations) for all layers, both caches, all destinations and the per-row state, stream-ordered behind
  *                     the steps already enqueued; the call returns when the copy has finished, like an admission. */
 TGX_API int tgx_fork_row(tgx_ctx* ctx, int src, int n, const int32_t* dst_rows);
+
+/* ---- beam search (additive to ABI 3) --------------------------------------------------------------------------------------------------------------------
+ * K hypotheses of one prompt advance together: each step ranks every (hypothesis, next token) pair by the hypothesis' running score plus the token's log-probability
+ * and keeps the best K.  Emulated with the calls above a step costs K read-backs of [vocab] logits, a ranking on the host, K tgx_fork_row into freshly retired rows and
+ * K one-token tgx_extend_row passes over all the weights, in 2K rows.  The two calls below do it in K rows with one small read-back and ONE batched step:
+ *   tgx_beam_select(rows, scores, k)  ->  the caller picks k candidates  ->  tgx_beam_advance(rows, parent, tokens)  ->  tgx_decode_rows(1)  ->  tgx_beam_select ...
+ *
+ * tgx_beam_select — the joint ranking (kernels/beam.h)
+ *   Inputs            rows[0 .. n): distinct live, unfinished rows that hold logits (after tgx_forward_row / tgx_extend_row, or after a step); a current token is not
+ *                     needed and not looked at.  scores[i]: the finite running score of the hypothesis in rows[i].
+ *   What is ranked    v_i = the row's fp32 logits (tgx_read_logits, rounded = 0) — with a logit processor or an automaton on, the processed vector tgx_sample_row would
+ *                     draw from (no counting step, no state move).  lse_i is tgx_set_row_logprobs' quantity (tile sums in double, a fixed association),
+ *                     lp_i(t) = (double)v_i[t] - lse_i, key(i, t) = (double)scores[i] + lp_i(t).  The joint order: key descending, then array index i ascending,
+ *                     then the rank within the row (value descending, index ascending) ascending; an entry of key -inf is no candidate.
+ *   Output            the prefix of the joint order that ends at the k-th candidate whose token is none of end_ids — an end-id candidate ahead of it is a hypothesis
+ *                     that ends here — cut at TGX_MAX_BEAM_CAND entries or where the candidates run out; *out_n entries, each {beam = i, token,
+ *                     score = (float)key, lp = (float)lp_i(token)}.  The same call returns the same bits from run to run.
+ *   Refusals          TGX_ERR_INVALID: a null pointer, n or k outside [1, TGX_MAX_BEAMS], n_end outside [0, TGX_MAX_STOP_IDS], a non-finite score, a row named
+ *                     twice or out of range.  TGX_ERR_STATE: a retired, empty, finished or no-logits row, a poisoned context, a call before tgx_finalize.  A refused
+ *                     call changes nothing.
+ *   Cost              three small launches (a tile launch over the n rows' vocabularies, a merge per row, one ranking workgroup), one synchronisation and a
+ *                     528-byte read-back; the workspace is sized by the first call (a context that never selects holds none of it).
+ *
+ * tgx_beam_advance — the group re-seated (csrc/beam_plan.h, kernels/beam.h)
+ *   Rows              rows[0 .. n_rows) distinct, n_rows <= TGX_MAX_BEAMS, each a SOURCE (a live, unfinished row that holds logits) or a SPARE (a retired or
+ *                     empty row < batch, or a new row by tgx_forward_rows' rule: the new rows that RECEIVE a hypothesis must be exactly batch .. batch + m - 1).
+ *                     1 <= n_next <= n_rows; parent[j] indexes rows and names a source; tokens[j] in [0, vocab).
+ *   Afterwards        new hypothesis j is the sequence of rows[parent[j]] with current token tokens[j], in out_rows[j], ready for tgx_decode_rows (or
+ *                     tgx_verify_rows with n_draft 0).  On row 0 the token becomes ticket 0's token.
+ *   Placement         PINNED: for each source in array order that has children, its lowest-j child stays IN PLACE (no copy, no block moves); the sources without
+ *                     a child are retired first, as by tgx_reset_row; the remaining children, in ascending j, take the rows that are empty now (retired
+ *                     sources and spares) in ascending array index.  A group lives in K rows, and a step copies exactly n_next - (distinct parents) rows.
+ *   Copied children   tgx_fork_row's destination, word for word: the full paged blocks shared by reference, one fresh tail block when past % 128 != 0, the prefix
+ *                     copied on slabs; hidden row, logits, partials, position word, history words and automaton id / state travel with the copy; settings are the
+ *                     caller's (a retired source's are back at their defaults, as after tgx_reset_row).  One copy launch per parent that has a copied child, then
+ *                     ONE publish launch for all placed rows: the token word and the next embedding at the row's position (GPT-2: with wpe) — the row ends as a
+ *                     step that produced that token would leave it.
+ *   Not done here     no log-probability record is written (the candidate carries lp).  Stop conditions are the caller's: a row that finished on the device is no
+ *                     legal source (TGX_ERR_STATE), so beam rows carry no stop ids and no max_new.
+ *   Paged KV          ALL OR NOTHING: the fresh tail blocks are counted against the free list plus what the childless sources give back before anything is released
+ *                     or assigned (TGX_ERR_CONTEXT); one table push.  Rows not named keep their state bit for bit.
+ *   Refusals          TGX_ERR_INVALID: a null pointer, n_rows outside [1, TGX_MAX_BEAMS], n_next outside [1, n_rows], a row out of range or named twice, a parent
+ *                     outside [0, n_rows), a token out of range, new rows that leave a gap.  TGX_ERR_STATE: a named row that finished or holds no logits, a parent
+ *                     that is a spare, a poisoned context, a call before tgx_finalize.  TGX_ERR_CONTEXT: the paged budget.  A refused call changes nothing.
+ *   Equivalence       tgx_beam_advance followed by one step equals, up to the order of the fp32 sums, tgx_fork_row of each parent followed by
+ *                     tgx_extend_row(row, &token, 1); cache rows [0, past) are equal bit for bit.
+ *   Cost              NOT YET MEASURED on the device in this tree: tools/beam_bench.py writes profiles/beam_search.txt (the step against tgx_decode_rows alone and
+ *                     against the emulation above); no figure is quoted until that file exists.  On slabs a copied child costs a copy of its whole prefix. */
+#define TGX_MAX_BEAMS 8
+#define TGX_MAX_BEAM_CAND 32
+typedef struct tgx_beam_cand { int32_t beam; int32_t token; float score; float lp; } tgx_beam_cand;
+TGX_API int tgx_beam_select(tgx_ctx* ctx, int n, const int32_t* rows, const float* scores /* [n] */, int k, const int32_t* end_ids, int n_end,
+                            tgx_beam_cand* out /* [TGX_MAX_BEAM_CAND] */, int32_t* out_n);
+TGX_API int tgx_beam_advance(tgx_ctx* ctx, int n_rows, const int32_t* rows, int n_next, const int32_t* parent /* [n_next], index into rows */,
+                             const int32_t* tokens /* [n_next] */, int32_t* out_rows /* [n_next] */);
 
 /* ---- extending and truncating a live row (additive to ABI 3) ------------------------------------------------------------------------------------------
  * The next turn of a conversation, a request's own text after a shared (forked) prefix, a prompt admitted in pieces: "these tokens after that cached prefix" without

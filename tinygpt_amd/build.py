@@ -28,7 +28,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h")]
+            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -104,6 +104,18 @@ def build_splice_plan_check(force: bool = False, verbose: bool = False):
     if _stale(os.path.join(TEST_BUILD, "splice_plan_check"), [os.path.join(CSRC, "kv_pool.h")]):
         force = True
     return _build_cpu_check("splice_plan_check", os.path.join(CSRC, "splice_plan.h"), force, verbose)
+
+
+def build_beam_plan_check(force: bool = False, verbose: bool = False):
+    """tests/beam_plan_check.cpp, the CPU audit of csrc/beam_plan.h (and of the KvPool calls tgx_beam_advance makes)."""
+    if _stale(os.path.join(TEST_BUILD, "beam_plan_check"), [os.path.join(CSRC, "kv_pool.h")]):
+        force = True
+    return _build_cpu_check("beam_plan_check", os.path.join(CSRC, "beam_plan.h"), force, verbose)
+
+
+def build_beam_check(force: bool = False, verbose: bool = False):
+    """tests/beam_check.cpp, the CPU audit of host/beam.h."""
+    return _build_cpu_check("beam_check", os.path.join(HOST, "beam.h"), force, verbose)
 
 
 def build_dev_mem_check(force: bool = False, verbose: bool = False):

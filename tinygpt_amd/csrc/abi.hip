@@ -11,6 +11,7 @@
 #include "kernels/kv_splice.h"
 #include "row_snapshot.h"
 #include "splice_plan.h"
+#include "beam_plan.h"
 #include "automaton.h"
 
 static std::string g_create_err;
@@ -1519,6 +1520,110 @@ int tgx_fork_row(tgx_ctx* c, int src, int n, const int32_t* dst_rows) {
     }
     row_admitted(c, dst_rows[i], (int)past);
     c->row_host[(size_t)dst_rows[i]].tok = c->row_host[(size_t)src].tok;      // the token word travelled with the copy
+  }
+  refresh_longest(c);
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
+
+// ---- beam search (include/tgx.h tgx_beam_select / tgx_beam_advance; kernels/beam.h, beam_plan.h).  tgx_beam_select: every check here, the launches and the
+// read-back in sampler.hip (beam_select_run).  A refused call changes nothing
+static_assert(beam_plan::MAX_BEAMS == TGX_MAX_BEAMS && (int)beam_plan::INVALID == (int)TGX_ERR_INVALID && (int)beam_plan::STATE == (int)TGX_ERR_STATE, "beam_plan.h");
+int tgx_beam_select(tgx_ctx* c, int n, const int32_t* rows, const float* scores, int k, const int32_t* end_ids, int n_end, tgx_beam_cand* out, int32_t* out_n) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!rows || !scores || !out || !out_n) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: null argument");
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "beam_select before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  if (n < 1 || n > TGX_MAX_BEAMS) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: n %d out of range [1,%d]", n, TGX_MAX_BEAMS);
+  if (k < 1 || k > TGX_MAX_BEAMS) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: k %d out of range [1,%d]", k, TGX_MAX_BEAMS);
+  if (n_end < 0 || n_end > TGX_MAX_STOP_IDS) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: n_end %d out of range [0,%d]", n_end, TGX_MAX_STOP_IDS);
+  if (n_end > 0 && !end_ids) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: null end_ids with n_end %d", n_end);
+  for (int i = 0; i < n; i++) {
+    if (rows[i] < 0 || rows[i] >= c->d.max_batch) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: row %d out of range [0,%d)", rows[i], c->d.max_batch);
+    for (int j = 0; j < i; j++)
+      if (rows[j] == rows[i]) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: row %d named twice", rows[i]);
+    if (!std::isfinite(scores[i])) return set_err(c, TGX_ERR_INVALID, "tgx_beam_select: scores[%d] is not finite", i);
+  }
+  if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "tgx_beam_select: no logits to select from");
+  for (int i = 0; i < n; i++) {
+    const RowHost& r = c->row_host[(size_t)rows[i]];
+    if (rows[i] >= c->batch || r.idle || r.past < 1) return set_err(c, TGX_ERR_STATE, "tgx_beam_select: row %d is not a live row of the batch", rows[i]);
+    if (r.fin) return set_err(c, TGX_ERR_STATE, "tgx_beam_select: row %d finished on the device", rows[i]);
+    if (r.nologits) return set_err(c, TGX_ERR_STATE, "tgx_beam_select: row %d was truncated and holds no logits: tgx_extend_row it first", rows[i]);
+  }
+  HIP_OK(c, hipSetDevice(c->device));      // (tgx_finalize refused a vocabulary of more tiles than lp_merge ranks: sampler_alloc)
+  return beam_select_run(c, n, rows, scores, k, end_ids, n_end, out, out_n);
+}
+
+// tgx_beam_advance: beam_plan.h decides (validation, placement, block count) before anything changes; then the childless sources retire as by tgx_reset_row, every
+// pool change of the call goes to the device table in ONE push, each parent with copied children takes ONE kv_fork_kernel launch (tgx_fork_row's, unchanged), and
+// ONE publish launch gives every placed row its token and next embedding.  The launch sequence ends in finish_pass like a fork
+int tgx_beam_advance(tgx_ctx* c, int n_rows, const int32_t* rows, int n_next, const int32_t* parent, const int32_t* tokens, int32_t* out_rows) {
+  if (!c) return TGX_ERR_INVALID;
+  if (!rows || !parent || !tokens || !out_rows) return set_err(c, TGX_ERR_INVALID, "tgx_beam_advance: null argument");
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "beam_advance before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  const tgx_model_desc& d = c->d;
+  // ---- every check before anything changes
+  std::vector<beam_plan::RowState> st((size_t)d.max_batch);
+  for (int r = 0; r < d.max_batch; r++) { const RowHost& h = c->row_host[(size_t)r]; st[(size_t)r].past = h.past; st[(size_t)r].idle = h.idle; st[(size_t)r].fin = h.fin != 0; st[(size_t)r].nologits = h.nologits; }
+  beam_plan::Plan plan;
+  const char* why = "";
+  if (const int rc = beam_plan::make(d.max_batch, c->batch, d.vocab, st.data(), n_rows, rows, n_next, parent, tokens, &plan, &why)) return set_err(c, rc, "tgx_beam_advance: %s", why);
+  if (!c->have_logits) return set_err(c, TGX_ERR_STATE, "tgx_beam_advance: no logits");
+  if (plan.n_copies && ((long long)d.head_dim * (long long)c->esz) % 4 != 0) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_beam_advance: a cache row of %d bytes", (int)(d.head_dim * c->esz));
+  if (c->kv_paged) {
+    const long long need = beam_plan::fresh_blocks(plan, tgx::KV_BLOCK), have = beam_plan::available(c->kv, plan);
+    if (need > have)
+      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the beam step needs %lld blocks of %d tokens for the copied rows' tails, %lld free or held by its childless rows of %d (option kv.budget_tokens = %d)",
+                     need, tgx::KV_BLOCK, have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
+  }
+  HIP_OK(c, hipSetDevice(c->device));
+  // ---- the sources without a child retire (tgx_reset_row; their blocks go back with the call's one table push below)
+  for (int i = 0; i < plan.n_retire; i++) {
+    const int row = plan.retire[i];
+    HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream));
+    row_req_reset(c, row);
+    if (c->proc_hist) HIP_OK(c, hipMemsetAsync(c->proc_hist + (size_t)row * d.vocab, 0, (size_t)d.vocab * sizeof(unsigned int), c->stream));
+    c->row_host[(size_t)row].restart(0, /*idle=*/true, /*fin=*/0);
+  }
+  beam_plan::Blocks blk;
+  if (c->kv_paged) {
+    KvPool::Changes ch;
+    blk = beam_plan::apply(c->kv, plan, ch);      // cannot run dry: counted above
+    kv_tbl_push(c, ch);
+  }
+  // ---- the copied children: tgx_fork_row's destination, word for word
+  for (int g = 0; g < plan.n_groups; g++) {
+    const beam_plan::Group& gr = plan.group[g];
+    launch_kv_fork(c, gr.src, gr.n_dst, gr.dst, blk.tail_blk[g], blk.src_blk[g]);
+    if (c->proc_hist)
+      for (int k = 0; k < gr.n_dst; k++)
+        HIP_OK(c, hipMemcpyAsync(c->proc_hist + (size_t)gr.dst[k] * d.vocab, c->proc_hist + (size_t)gr.src * d.vocab, (size_t)d.vocab * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+  }
+  // ---- every placed row: its token and the next embedding at its position
+  launch_beam_publish(c, n_next, plan.out_rows, tokens);
+  if (int rc = finish_pass(c)) return rc;
+  c->batch = std::max(c->batch, plan.new_batch);
+  for (int g = 0; g < plan.n_groups; g++) {
+    const beam_plan::Group& gr = plan.group[g];
+    for (int k = 0; k < gr.n_dst; k++) {
+      const int dst = gr.dst[k];
+      const tgx::RowReq& qs = c->row_req_host[(size_t)gr.src];
+      tgx::RowReq& qd = c->row_req_host[(size_t)dst];
+      if (qs.auto_next || qd.auto_next) {      // the same sequence, the same automaton and state (tgx_fork_row)
+        qd.auto_next = qs.auto_next; qd.auto_state = qs.auto_state;
+        c->row_host[(size_t)dst].auto_id = c->row_host[(size_t)gr.src].auto_id;
+        row_proc_refresh(qd);
+        row_req_push(c, dst, ROWQ_AUTO);
+      }
+      row_admitted(c, dst, (int)gr.past);
+    }
+  }
+  for (int j = 0; j < n_next; j++) {
+    c->row_host[(size_t)plan.out_rows[j]].tok = true;
+    if (plan.out_rows[j] == 0) c->last_sampled0 = tokens[j];      // ticket 0's token, as after tgx_sample
+    out_rows[j] = plan.out_rows[j];
   }
   refresh_longest(c);
   HIP_OK(c, hipGetLastError());

@@ -422,6 +422,9 @@ struct tgx_ctx {
   // new block table in front of them
   unsigned char* snap_stage = nullptr; size_t snap_stage_bytes = 0;
   int snapshot_stage_kib = 65536;
+  // ---- beam search (include/tgx.h tgx_beam_select; kernels/beam.h): the tile maxima, sums and keys of TGX_MAX_BEAMS rows, the rows' lse and first keys, and the
+  // call's record, in ONE buffer sized by the first tgx_beam_select: a context that never selects holds none of it (tgx_beam_advance needs no workspace)
+  unsigned char* beam_ws = nullptr;
   float* scratch_x = nullptr;   // [hidden] residual sink for tgx_profile_decode
   Profiler prof;
 };
@@ -517,6 +520,10 @@ void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& 
 int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
 bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)
+// beam search (kernels/beam.h): the three launches of tgx_beam_select over rows[0 .. n) and the read-back of its record (the caller checked every argument); the
+// publish launch of tgx_beam_advance: row rows[j] takes tokens[j] as its current token and the next embedding at its position
+int beam_select_run(tgx_ctx* c, int n, const int32_t* rows, const float* scores, int k, const int32_t* end_ids, int n_end, tgx_beam_cand* out, int32_t* out_n);
+void launch_beam_publish(tgx_ctx* c, int n, const int* rows, const int32_t* tokens);
 int sampler_alloc(tgx_ctx* c);
 int logprobs_alloc(tgx_ctx* c);                                              // the rings, counters and tile partials, at first use
 void launch_logprobs(tgx_ctx* c, int row0, int R, bool force);             // behind a step's publish: the rows that record and produced a token (force: tgx_sample_row)

@@ -6,6 +6,8 @@
 #include "kernels/sampler.h"
 #include "kernels/logprobs.h"
 #include "kernels/logit_proc.h"
+#include "kernels/beam.h"
+#include <cstddef>
 #include <type_traits>
 
 static int proc_tiles(const tgx_ctx* c) { return (c->d.vocab + tgx::PROC_TILE - 1) / tgx::PROC_TILE; }
@@ -305,6 +307,54 @@ int sampler_alloc(tgx_ctx* c) {
   if ((rc = dev_alloc(c, &c->samp_list_comp, (size_t)d.max_batch * d.vocab)) || (rc = dev_alloc(c, &c->samp_list_v, (size_t)d.max_batch * d.vocab))) return rc;
   if ((d.vocab + tgx::SAMP_TILE - 1) / tgx::SAMP_TILE > tgx::SAMP_MAX_WG) return set_err(c, TGX_ERR_UNSUPPORTED, "vocabulary %d exceeds the sampler's %d entries", d.vocab, tgx::SAMP_MAX_WG * tgx::SAMP_TILE);
   return TGX_OK;
+}
+
+// ---- beam search (kernels/beam.h; include/tgx.h tgx_beam_select / tgx_beam_advance)
+static_assert(tgx::BEAM_MAX_ROWS == TGX_MAX_BEAMS && tgx::BEAM_MAX_CAND == TGX_MAX_BEAM_CAND && tgx::BEAM_ROW_CAND == TGX_MAX_BEAMS + TGX_MAX_STOP_IDS, "kernels/beam.h");
+static_assert(sizeof(tgx::BeamCand) == sizeof(tgx_beam_cand) && offsetof(tgx::BeamCand, score) == offsetof(tgx_beam_cand, score), "kernels/beam.h BeamCand");
+
+int beam_select_run(tgx_ctx* c, int n, const int32_t* rows, const float* scores, int k, const int32_t* end_ids, int n_end, tgx_beam_cand* out, int32_t* out_n) {
+  const size_t V = (size_t)c->d.vocab, T = (size_t)lp_tiles(c), R = (size_t)tgx::BEAM_MAX_ROWS;
+  // the workspace, widest elements first: tile sums | tile keys | row lse | row keys | record | tile maxima
+  const size_t o_sum = 0, o_keys = o_sum + R * T * 8, o_lse = o_keys + R * T * tgx::LP_MAX * 8, o_rkeys = o_lse + R * 8, o_rec = o_rkeys + R * tgx::BEAM_ROW_CAND * 8,
+               o_max = o_rec + sizeof(tgx::BeamRecord), total = o_max + R * T * 4;
+  if (!c->beam_ws) { if (int rc = dev_alloc(c, &c->beam_ws, total)) return rc; }      // sized by the first call: the vocabulary is the context's
+  tgx::BeamSelArgs a{};
+  for (int i = 0; i < n; i++) {
+    const int row = rows[i];
+    const bool processed = row_processed(c, row);      // what tgx_sample_row would draw from: the row's processors without the counting step, no state moves
+    if (processed) launch_logit_proc(c, row, 1, /*step=*/false);
+    a.lg[i] = processed ? c->proc_logits + (size_t)row * V : c->rows[(size_t)row].logits;
+    a.score[i] = scores[i];
+  }
+  for (int e = 0; e < n_end; e++) a.end_id[e] = end_ids[e];
+  a.n = n; a.k = k; a.n_end = n_end; a.top_n = k + n_end;
+  a.V = (int)V; a.nwg = (int)T;
+  a.tile_sum = reinterpret_cast<double*>(c->beam_ws + o_sum); a.tile_keys = reinterpret_cast<unsigned long long*>(c->beam_ws + o_keys);
+  a.row_lse = reinterpret_cast<double*>(c->beam_ws + o_lse); a.row_keys = reinterpret_cast<unsigned long long*>(c->beam_ws + o_rkeys);
+  a.rec = reinterpret_cast<tgx::BeamRecord*>(c->beam_ws + o_rec); a.tile_max = reinterpret_cast<float*>(c->beam_ws + o_max);
+  hipLaunchKernelGGL(tgx::beam_tile_kernel, dim3((unsigned)T, (unsigned)n), dim3(tgx::SAMP_WG), 0, c->stream, a);
+  hipLaunchKernelGGL(tgx::beam_row_kernel, dim3((unsigned)n), dim3(tgx::SAMP_WG), 0, c->stream, a);
+  hipLaunchKernelGGL(tgx::beam_rank_kernel, dim3(1), dim3(tgx::BEAM_MAX_ROWS * tgx::BEAM_ROW_CAND), 0, c->stream, a);
+  HIP_OK(c, hipGetLastError());
+  LAUNCH_OK(c);
+  tgx::BeamRecord rec;
+  HIP_OK(c, hipMemcpyAsync(&rec, a.rec, sizeof(rec), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  const int m = std::max(0, std::min(rec.n, (int)tgx::BEAM_MAX_CAND));
+  for (int i = 0; i < m; i++) { out[i].beam = rec.cand[i].beam; out[i].token = rec.cand[i].token; out[i].score = rec.cand[i].score; out[i].lp = rec.cand[i].lp; }
+  *out_n = m;
+  return TGX_OK;
+}
+
+void launch_beam_publish(tgx_ctx* c, int n, const int* rows, const int32_t* tokens) {
+  tgx::BeamPublishArgs a{};
+  for (int j = 0; j < n; j++) {
+    RowState& r = c->rows[(size_t)rows[j]];
+    a.tok[j] = r.tok; a.pos[j] = r.pos; a.x[j] = r.x; a.token[j] = tokens[j];
+  }
+  a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
+  TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::beam_publish_kernel<DT>, dim3((unsigned)n), dim3(256), 0, c->stream, a))
 }
 
 #ifdef TGX_SAMP_TIMELINE

@@ -58,6 +58,14 @@ ADV_STEP, ADV_FEED, ADV_FEED_MORE = 0, 1, 2      # TGX_ADV_*: the kinds of tgx_a
 MAX_ADVANCE_POSITIONS = 8192                     # TGX_MAX_ADVANCE_POSITIONS
 
 
+MAX_BEAMS, MAX_BEAM_CAND, MAX_STOP_IDS = 8, 32, 8    # TGX_MAX_BEAMS, TGX_MAX_BEAM_CAND, TGX_MAX_STOP_IDS
+
+
+class BeamCand(ctypes.Structure):
+    """tgx_beam_cand"""
+    _fields_ = [("beam", c_int32), ("token", c_int32), ("score", c_float), ("lp", c_float)]
+
+
 POOL_MODES = {"last": 0, "mean": 1, "first": 2}      # TGX_POOL_*
 
 
@@ -92,6 +100,8 @@ ABI = {
     "forward_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32)]),
     "embed_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(EmbedCfg), POINTER(c_float)]),
     "fork_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32)]),
+    "beam_select": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_float), c_int, POINTER(c_int32), c_int, POINTER(BeamCand), POINTER(c_int32)]),
+    "beam_advance": (c_int, [c_void_p, c_int, POINTER(c_int32), c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "extend_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int]),
     "truncate_row": (c_int, [c_void_p, c_int, c_int64]),
     "splice_row": (c_int, [c_void_p, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
@@ -334,6 +344,37 @@ class Model:
         if len(rows):
             self.batch = max(self.batch, int(rows.max()) + 1)
         return self
+
+    # -- beam search (include/tgx.h tgx_beam_select / tgx_beam_advance) ---------------------------
+    def beam_select(self, rows, scores, k: int, end_ids=()):
+        """the joint ranking of rows' next-token distributions plus their running scores (include/tgx.h tgx_beam_select): the prefix of the joint order that ends at
+        the k-th candidate whose token is no end id -> (beam [m] int32 — an index into rows —, token [m] int32, score [m] float32, lp [m] float32)"""
+        rows = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int32).reshape(-1))
+        sc = np.ascontiguousarray(np.asarray(list(scores), dtype=np.float32).reshape(-1))
+        assert len(sc) == len(rows), "one score per row"
+        ends = np.ascontiguousarray(np.asarray(list(end_ids), dtype=np.int32).reshape(-1))
+        out = (BeamCand * MAX_BEAM_CAND)()
+        n = c_int32(0)
+        self._check(self.be.beam_select(self._ctx, len(rows), rows.ctypes.data_as(POINTER(c_int32)) if len(rows) else None, sc.ctypes.data_as(POINTER(c_float)) if len(sc) else None,
+                                        int(k), ends.ctypes.data_as(POINTER(c_int32)) if len(ends) else None, len(ends), out, ctypes.byref(n)))
+        a = np.frombuffer(out, dtype=np.dtype([("beam", np.int32), ("token", np.int32), ("score", np.float32), ("lp", np.float32)]), count=MAX_BEAM_CAND)[:n.value]
+        return a["beam"].copy(), a["token"].copy(), a["score"].copy(), a["lp"].copy()
+
+    def beam_advance(self, rows, parent, tokens):
+        """re-seat the group `rows` (sources and spares) on its next hypotheses (include/tgx.h tgx_beam_advance): hypothesis j continues rows[parent[j]] with current
+        token tokens[j] -> the rows the hypotheses live in, by the header's pinned placement"""
+        rows = np.ascontiguousarray(np.asarray(list(rows), dtype=np.int32).reshape(-1))
+        par = np.ascontiguousarray(np.asarray(list(parent), dtype=np.int32).reshape(-1))
+        tok = np.ascontiguousarray(np.asarray(list(tokens), dtype=np.int32).reshape(-1))
+        assert len(par) == len(tok), "one token per parent"
+        out = np.full(max(len(par), 1), -1, dtype=np.int32)
+        self._check(self.be.beam_advance(self._ctx, len(rows), rows.ctypes.data_as(POINTER(c_int32)) if len(rows) else None, len(par),
+                                         par.ctypes.data_as(POINTER(c_int32)) if len(par) else None, tok.ctypes.data_as(POINTER(c_int32)) if len(tok) else None,
+                                         out.ctypes.data_as(POINTER(c_int32))))
+        out = out[:len(par)]
+        if len(out):
+            self.batch = max(self.batch, int(out.max()) + 1)
+        return out
 
     def extend_row(self, row: int, ids):
         """append ids at positions past .. past + len(ids) - 1 of the live (or finished) row `row` in one causal pass (include/tgx.h tgx_extend_row); the row's current

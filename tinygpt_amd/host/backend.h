@@ -72,6 +72,9 @@ struct Backend {
   int (*score_row)(tgx_ctx*, int, const int64_t*, int, int, float*, int32_t*, float*) = nullptr;
   // embeddings (optional: GPTEngine::embed needs it)
   int (*embed_rows)(tgx_ctx*, int, const int32_t*, const int64_t*, const int32_t*, const tgx_embed_cfg*, float*) = nullptr;
+  // beam search (optional: GPTConfig::numBeams > 1 needs both, forward_row, decode_rows and reset_row)
+  int (*beam_select)(tgx_ctx*, int, const int32_t*, const float*, int, const int32_t*, int, tgx_beam_cand*, int32_t*) = nullptr;
+  int (*beam_advance)(tgx_ctx*, int, const int32_t*, int, const int32_t*, const int32_t*, int32_t*) = nullptr;
   // row snapshots (optional: GPTEngine::saveSession / loadSession need all three, and prefix reuse)
   int (*row_snapshot_bytes)(const tgx_ctx*, int, int64_t*) = nullptr;
   int (*save_row)(tgx_ctx*, int, void*, int64_t, int64_t*) = nullptr;
@@ -103,6 +106,7 @@ struct Backend {
     TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);
     TGXH_BIND(automaton_create, false); TGXH_BIND(automaton_destroy, false); TGXH_BIND(set_row_automaton, false); TGXH_BIND(read_row_automaton, false);
     TGXH_BIND(score_row, false); TGXH_BIND(embed_rows, false);
+    TGXH_BIND(beam_select, false); TGXH_BIND(beam_advance, false);
     TGXH_BIND(row_snapshot_bytes, false); TGXH_BIND(save_row, false); TGXH_BIND(restore_row, false);
 #undef TGXH_BIND
     return ok;

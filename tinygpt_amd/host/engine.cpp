@@ -1,6 +1,7 @@
 #include "engine.h"
 #include "../csrc/row_snapshot.h"
 #include "spec_mode.h"
+#include "beam.h"
 
 #include <chrono>
 
@@ -572,6 +573,7 @@ std::vector<int64_t> GPTEngine::alignPrompts(const std::vector<std::vector<int32
 GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& prompts, int32_t padToken) {
   GPTOutput out;
   if (!prepared_ || prompts.empty()) { fail("generateSync: engine not prepared or empty batch"); return out; }
+  if (config_.numBeams > 1) return beamsRefused(prompts.size()) ? out : generateBeams(prompts[0], padToken);
   if (logprobsRefused(false) || processorsRefused(false)) return out;
   const int B = (int)prompts.size();
   int64_t S = 0;
@@ -704,9 +706,84 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   return out;
 }
 
+// ---- GPTConfig::numBeams > 1 (beam.h holds the rules; include/tgx.h tgx_beam_select / tgx_beam_advance the device side)
+static_assert(sizeof(BeamCand) == sizeof(tgx_beam_cand), "beam.h BeamCand == tgx_beam_cand");
+bool GPTEngine::beamsRefused(size_t prompts) {
+  const int K = config_.numBeams;
+  const SamplerConfig& s = config_.samplerConfig;
+  if (K > TGX_MAX_BEAMS) { fail("beam search: numBeams " + std::to_string(K) + " exceeds TGX_MAX_BEAMS " + std::to_string(TGX_MAX_BEAMS)); return true; }
+  if (config_.numReturn < 1 || config_.numReturn > K) { fail("beam search: numReturn " + std::to_string(config_.numReturn) + " outside [1, numBeams]"); return true; }
+  if (s.temperature > 0.f || s.topK > 0 || s.topP < 1.f || s.minP > 0.f) { fail("beam search: needs a greedy sampler configuration (temperature 0, no top-k / top-p / min-p)"); return true; }
+  if (prompts != 1) { fail("beam search: one prompt per generateSync call, got " + std::to_string(prompts)); return true; }
+  if (config_.speculate > 0 || config_.logprobs >= 0 || config_.contextShift) { fail("beam search does not combine with speculate, logprobs or contextShift"); return true; }
+  if (config_.maxBatch < K) { fail("beam search: maxBatch " + std::to_string(config_.maxBatch) + " < numBeams " + std::to_string(K)); return true; }
+  if (eosTokenIds_.size() > (size_t)TGX_MAX_STOP_IDS) { fail("beam search: at most " + std::to_string(TGX_MAX_STOP_IDS) + " EOS / stop ids"); return true; }
+  if (!(be_.beam_select && be_.beam_advance && be_.forward_row && be_.decode_rows)) { fail("beam search: the device shim lacks tgx_beam_select / tgx_beam_advance or the per-row calls they ride on"); return true; }
+  return processorsRefused(false);
+}
+
+GPTOutput GPTEngine::generateBeams(const std::vector<int32_t>& prompt, int32_t padToken) {
+  GPTOutput out;
+  const int K = config_.numBeams;
+  int64_t S = 0;
+  const std::vector<int64_t> ids = alignPrompts({prompt}, padToken, S);
+  if (S == 0) { fail("generateSync: every prompt is empty (nothing to prefill)"); return out; }
+  const int64_t n_new = std::max<int64_t>(1, config_.maxNewTokens);
+  lastReused_ = 0; lastShifts_ = 0;
+  cached_.clear();
+  const auto t0 = std::chrono::steady_clock::now();
+  auto dev = [&](int rc, const char* what) { if (rc != TGX_OK) fail(std::string("beam search: ") + what + ": " + be_.last_error(model_.ctx)); return rc == TGX_OK; };
+  if (!dev(be_.reset_cache(model_.ctx), "reset_cache") || !dev(be_.forward_row(model_.ctx, 0, ids.data(), (int)S), "forward_row")) return out;
+  const bool procOn = processorsOn();
+  const auto procOff = at_exit([&] { if (procOn) processorsEnd(K); be_.reset_cache(model_.ctx); });
+  if (procOn && !processorsBegin(0, ids.data(), S)) return out;
+  // a copied child carries its parent's history words and automaton state; penalties and bias are settings, and a retired row's are back at their defaults
+  auto settings = [&](int row) {
+    if (!procOn) return true;
+    const SamplerConfig& s = config_.samplerConfig;
+    const tgx_penalty_cfg pc{s.repetitionPenalty, s.presencePenalty, s.frequencyPenalty};
+    std::vector<int32_t> bi; std::vector<float> bv;
+    for (const auto& kv : s.logitBias) { bi.push_back(kv.first); bv.push_back(kv.second); }
+    return dev(be_.set_row_penalties(model_.ctx, row, &pc), "set_row_penalties") && dev(be_.set_row_logit_bias(model_.ctx, row, (int)bi.size(), bi.data(), bv.data()), "set_row_logit_bias");
+  };
+  BeamScorer scorer(K, config_.lengthPenalty, config_.earlyStopping, n_new, eosTokenIds_);
+  std::vector<int32_t> rows(1, 0), group((size_t)K), placed((size_t)K);
+  for (int b = 0; b < K; b++) group[(size_t)b] = b;
+  std::vector<tgx_beam_cand> cands(TGX_MAX_BEAM_CAND);
+  auto t1 = t0;
+  for (int64_t step = 0;; step++) {
+    int32_t n = 0;
+    if (!dev(be_.beam_select(model_.ctx, (int)rows.size(), rows.data(), scorer.scores().data(), K, eosTokenIds_.empty() ? nullptr : eosTokenIds_.data(), (int)eosTokenIds_.size(), cands.data(), &n), "beam_select")) return out;
+    if (step == 0) t1 = std::chrono::steady_clock::now();
+    if (scorer.step(reinterpret_cast<const BeamCand*>(cands.data()), n)) break;
+    const int m = (int)scorer.parents().size();
+    const std::vector<int32_t>& from = step ? rows : group;      // the first step seats the group: row 0 and numBeams - 1 spares
+    if (!dev(be_.beam_advance(model_.ctx, (int)from.size(), from.data(), m, scorer.parents().data(), scorer.tokens().data(), placed.data()), "beam_advance")) return out;
+    rows.assign(placed.begin(), placed.begin() + m);
+    for (int32_t r : rows) if (!settings(r)) return out;
+    if (!dev(be_.decode_rows(model_.ctx, 1, nullptr, nullptr, nullptr), "decode_rows")) return out;
+  }
+  const std::vector<BeamHyp> hyps = scorer.finish();
+  const int R = (int)std::min<size_t>((size_t)config_.numReturn, hyps.size());
+  if (R < 1) { fail("beam search: no hypothesis (every candidate was masked)"); return out; }
+  out.firstTokenMs = std::chrono::duration<double, std::milli>(t1 - t0).count();
+  out.decodeMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+  out.batch = R; out.newTokens = n_new;
+  out.tokenIds.assign((size_t)(R * (S + n_new)), padToken);
+  for (int b = 0; b < R; b++) {
+    int32_t* row = out.tokenIds.data() + (size_t)b * (size_t)(S + n_new);
+    for (int64_t i = 0; i < S; i++) row[i] = (int32_t)ids[(size_t)i];
+    for (size_t i = 0; i < hyps[(size_t)b].tokens.size() && (int64_t)i < n_new; i++) row[S + (int64_t)i] = hyps[(size_t)b].tokens[i];
+    out.beamScores.push_back(hyps[(size_t)b].score);
+  }
+  out.finishReason = hyps[0].length ? FinishReason::Length : FinishReason::Stop;
+  return out;
+}
+
 GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const GenerateCallback& callback) {
   GPTOutput out;
   if (!prepared_) { fail("generateAsync: engine not prepared"); return out; }
+  if (config_.numBeams > 1) { fail("beam search: generateAsync streams one sequence; use generateSync (numBeams " + std::to_string(config_.numBeams) + ")"); return out; }
   if (logprobsRefused(true) || processorsRefused(true)) return out;
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts({prompt}, 0, S);
@@ -867,7 +944,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::string>& texts) {
   if (!tokenizerOk_) { fail("generateSync(texts): no tokenizer loaded"); return GPTOutput(); }
   const std::vector<std::vector<int32_t>> prompts = tokenizer_.encodeBatch(texts);
   GPTOutput out = generateSync(prompts, padTokenId());
-  if (out.batch > 0 && constraintOn()) {      // a row's text ends where the row stopped: the stop id and the pad tokens behind it are not part of the match
+  if (out.batch > 0 && (constraintOn() || config_.numBeams > 1)) {      // a row's text ends where the row stopped: the stop id and the pad tokens behind it are not part of the match
     const size_t row = out.tokenIds.size() / (size_t)out.batch, S = row - (size_t)out.newTokens;
     for (int64_t b = 0; b < out.batch; b++) {
       std::vector<int32_t> ids;

@@ -93,6 +93,17 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // A request that cannot be served FAILS the generate call with a message (lastError): N > TGX_MAX_LOGPROBS, a backend without the calls, and in generateAsync
   // more EOS / stop ids than TGX_MAX_STOP_IDS (the row stops on the device).
   int logprobs = -1;
+  // Not in the reference: beam search (include/tgx.h tgx_beam_select / tgx_beam_advance; beam.h holds the rules).  numBeams 1 = off: every loop as it was.  With
+  // numBeams > 1, generateSync of ONE prompt prefills it into row 0, selects with n = 1, advances 1 -> numBeams, and then per step runs tgx_decode_rows(1) + select +
+  // advance on numBeams rows; it returns numReturn rows, best first (a row's tokens behind its end are the pad token), and GPTOutput::beamScores.  A finished
+  // hypothesis scores sum_lp / L^lengthPenalty; earlyStopping ends the search once numBeams hypotheses are finished.  SamplerConfig::regex and the penalties compose
+  // (the select reads the processed vector).  The generate call FAILS with a message (lastError): a non-greedy sampler, several prompts, generateAsync, speculate /
+  // logprobs / contextShift together with beams, maxBatch < numBeams, numBeams > TGX_MAX_BEAMS, numReturn outside [1, numBeams], more EOS ids than
+  // TGX_MAX_STOP_IDS, a backend without the two calls.
+  int numBeams = 1;
+  float lengthPenalty = 1.f;
+  bool earlyStopping = false;
+  int numReturn = 1;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -113,6 +124,7 @@ struct GPTOutput {       // src/engine/GPTEngine.h:34-40
   double decodeMs = 0.0;             // the remaining newTokens-1 steps
   // GPTConfig::logprobs >= 0: the log-probability of every new token [batch][newTokens] and its topLogprobs alternatives [batch][newTokens][topLogprobs] as
   // (id, logprob), most likely first; empty otherwise
+  std::vector<double> beamScores;    // GPTConfig::numBeams > 1: the score of every returned row (sum_lp / L^lengthPenalty), best first; empty otherwise
   int topLogprobs = 0;
   std::vector<float> logprobs;
   std::vector<int32_t> topIds;
@@ -222,6 +234,9 @@ class GPTEngine {
     config_.samplerConfig.repetitionPenalty = repetition; config_.samplerConfig.presencePenalty = presence; config_.samplerConfig.frequencyPenalty = frequency;
     config_.samplerConfig.logitBias = std::move(bias);
   }
+  void setBeams(int numBeams, float lengthPenalty, bool earlyStopping, int numReturn) {      // kept by the C view across tgxe_reconfigure
+    config_.numBeams = numBeams; config_.lengthPenalty = lengthPenalty; config_.earlyStopping = earlyStopping; config_.numReturn = numReturn;
+  }
   void setRegex(std::string pattern) { config_.samplerConfig.regex = std::move(pattern); }      // kept by the C view across tgxe_reconfigure, like setProcessors
   const SpecStats& specStats() const { return spec_; }
 
@@ -264,6 +279,10 @@ class GPTEngine {
   bool constraintOn() const { return !config_.samplerConfig.regex.empty(); }
   bool constraintEnsure();                                                                     // SamplerConfig::regex compiled and its table on the device (kept while pattern and stop ids stay); false: err_ set
   bool rowsBegin(int batch, const tgx_sampler_cfg& sc, std::vector<int64_t>& first);          // the rows' sampler (and logprobs) settings, then every row's first token through tgx_sample_row
+
+  // GPTConfig::numBeams > 1
+  bool beamsRefused(size_t prompts);                                                           // not servable: err_ set, the generate call fails
+  GPTOutput generateBeams(const std::vector<int32_t>& prompt, int32_t padToken);
 
   GPTConfig config_;
   Backend be_;

@@ -19,6 +19,7 @@ static void keep_logprobs(tgxe_engine* h, tgxh::GPTOutput& r) {
   h->last = tgxh::GPTOutput();
   h->last.topLogprobs = r.topLogprobs;
   h->last.logprobs = std::move(r.logprobs); h->last.topIds = std::move(r.topIds); h->last.topLogprobValues = std::move(r.topLogprobValues);
+  h->last.beamScores = r.beamScores;
 }
 
 TGXE_API tgxe_engine* tgxe_create2(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
@@ -151,6 +152,17 @@ TGXE_API void tgxe_set_processors(tgxe_engine* h, float repetition, float presen
 }
 // SamplerConfig::regex (constrained decoding; empty or NULL: off); kept across tgxe_reconfigure until set again
 TGXE_API void tgxe_set_regex(tgxe_engine* h, const char* pattern) { if (h) h->e->setRegex(pattern ? pattern : ""); }
+// beam search (GPTConfig::numBeams / lengthPenalty / earlyStopping / numReturn; num_beams 1 = off); kept across tgxe_reconfigure until set again.  A beam call of
+// tgxe_generate_sync takes ONE prompt and writes num_return rows: out_ids needs num_return * (prompt + max_new) entries.  tgxe_last_beam_scores copies the rows'
+// scores of the last tgxe_generate_sync call, best first (up to cap), and returns how many there are
+TGXE_API void tgxe_set_beams(tgxe_engine* h, int num_beams, float length_penalty, int early_stopping, int num_return) {
+  if (h) h->e->setBeams(num_beams, length_penalty, early_stopping != 0, num_return);
+}
+TGXE_API int tgxe_last_beam_scores(tgxe_engine* h, double* out, int cap) {
+  if (!h) return 0;
+  for (int i = 0; out && i < (int)h->last.beamScores.size() && i < cap; i++) out[i] = h->last.beamScores[(size_t)i];
+  return (int)h->last.beamScores.size();
+}
 TGXE_API void tgxe_reconfigure(tgxe_engine* h, float temperature, int64_t top_k, float top_p, float min_p, int64_t max_new,
                                const int32_t* extra_stop, int n_extra) {
   tgxh::SamplerConfig s = h->e->samplerConfig();      // (the penalties / logit bias of tgxe_set_processors stay)
@@ -191,6 +203,7 @@ TGXE_API int tgxe_generate_sync_text(tgxe_engine* h, const char* const* texts, i
   std::vector<std::string> t;
   for (int b = 0; b < batch; b++) t.emplace_back(texts[b]);
   tgxh::GPTOutput r = h->e->generateSync(t);
+  h->last.beamScores = r.beamScores;      // (tgxe_last_beam_scores; the log-probability lists of an earlier call stay as they were)
   if (r.batch == 0) return 1;
   if ((int64_t)r.tokenIds.size() > cap) return 2;
   memcpy(out_ids, r.tokenIds.data(), r.tokenIds.size() * 4);

@@ -56,6 +56,10 @@ static void usage(const char* prog) {
           "  --session-save <file>     with --stream and one text prompt: keep the conversation's KV cache (prompt + generated tokens) in a file when the run ends\n"
           "                            (neither flag combines with --speculate, --logprobs, the penalties or --logit-bias: those runs end with the row finished on the\n"
           "                            device, which keeps no cache to save)\n"
+          "  --num-beams <n>           beam search over n hypotheses of ONE prompt (2 .. 8; needs --temperature 0 --top-p 1; not with --stream, --speculate, --logprobs)\n"
+          "  --length-penalty <f>      ... a finished hypothesis scores sum of log-probabilities / length^f (default 1)\n"
+          "  --early-stopping          ... stop once n hypotheses are finished\n"
+          "  --num-return <n>          ... print the n best hypotheses, best first, each with its score (default 1)\n"
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (--temperature 0 --top-p 1; several prompts: every row's\n"
           "                            draft in one joint pass; default: 0 = off)\n"
           "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n"
@@ -71,6 +75,11 @@ static void print_spec(const tgxh::GPTConfig& cfg, const tgxh::GPTEngine& engine
   const tgxh::SpecStats& s = engine.specStats();
   printf("speculate: %lld verify passes, %lld of %lld draft tokens accepted, %lld ordinary steps\n", (long long)s.verifyCalls, (long long)s.acceptedDrafts, (long long)s.draftTokens,
          (long long)s.plainSteps);
+}
+
+// --num-beams: one line per returned hypothesis, best first (nothing is printed without the flag)
+static void print_beams(const tgxh::GPTOutput& out) {
+  for (size_t b = 0; b < out.beamScores.size(); b++) printf("beam %zu score %.6f\n", b, out.beamScores[b]);
 }
 
 // --logprobs: one line per new token — row, index, id, its log-probability and the alternatives as id:logprob, most likely first
@@ -146,6 +155,10 @@ int main(int argc, char** argv) {
     else if (a == "--no-normalize") embed_cfg.normalize = false;
     else if (a == "--pad-id") pad_id = atol(next());
     else if (a == "--seed") cfg.seed = strtoull(next(), nullptr, 10);
+    else if (a == "--num-beams") cfg.numBeams = atoi(next());
+    else if (a == "--length-penalty") cfg.lengthPenalty = strtof(next(), nullptr);
+    else if (a == "--early-stopping") cfg.earlyStopping = true;
+    else if (a == "--num-return") cfg.numReturn = atoi(next());
     else if (a == "--speculate") cfg.speculate = atoi(next());
     else if (a == "--speculate-sampled") cfg.speculateSampled = true;
     else if (a == "--context-shift") cfg.contextShift = true;
@@ -262,12 +275,13 @@ int main(int argc, char** argv) {
     if (!stream) {
       printf("Generated Outputs:\n------------------------------------------------------------\n");
       for (int64_t b = 0; b < out.batch; b++)
-        printf("Prompt:    '%s'\nOutput:    '%s'\n------------------------------------------------------------\n", text_prompts[(size_t)b].c_str(), out.texts[(size_t)b].c_str());
+        printf("Prompt:    '%s'\nOutput:    '%s'\n------------------------------------------------------------\n", text_prompts[out.beamScores.empty() ? (size_t)b : 0].c_str(), out.texts[(size_t)b].c_str());
     }
     printf("Time cost: %lld ms, speed: %.2f token/s\n", (long long)ms, out.tokenIds.size() * 1000.0 / ms);
     printf("new tokens: %lld, new-token rate: %.2f token/s\n", (long long)(out.batch * out.newTokens), out.batch * out.newTokens * 1000.0 / ms);
     if (out.newTokens > 1) printf("time to first token: %.1f ms, decode-only rate: %.2f token/s\n", out.firstTokenMs, out.batch * (out.newTokens - 1) * 1000.0 / out.decodeMs);
     print_logprobs(out);
+    print_beams(out);
     print_spec(cfg, engine);
     return 0;
   }
@@ -292,6 +306,7 @@ int main(int argc, char** argv) {
   printf("new tokens: %lld, new-token rate: %.2f token/s\n", (long long)(out.batch * out.newTokens), out.batch * out.newTokens * 1000.0 / ms);
   if (out.newTokens > 1) printf("time to first token: %.1f ms, decode-only rate: %.2f token/s\n", out.firstTokenMs, out.batch * (out.newTokens - 1) * 1000.0 / out.decodeMs);
   print_logprobs(out);
+  print_beams(out);
   print_spec(cfg, engine);
   return 0;
 }
