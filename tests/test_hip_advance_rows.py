@@ -3,7 +3,7 @@ the STEP rows, tgx_extend_row for a FEED on a row that holds positions, tgx_forw
 the project's numbers: GPU against GPU logits rel_err < 1e-3, live cache rows by tests/test_hip_verify_row.py's check_kv, greedy ids equal where the CPU oracle's
 top-2 gap clears that file's BAND (asserted, so no id comparison is skipped), sampled ids restated from the call's OWN pass logits with the row's key
 (tests/verify_sampled_util.py: expected_draw, walk; the cap on compared draws inside the top-p band is 0).  Every context is a 2-layer cut of
-tests/verify_sampled_util.py (vocabulary 4096, max_batch 4 - 6, max_ctx 512).
+tests/verify_sampled_util.py (vocabulary 4096, max_batch 2 - 7, max_ctx 512).
 
 The prompt seeds were picked with the CPU oracle alone, the way tests/test_hip_verify_rows.py describes: per model the first seed (1, 2, ..) whose compared greedy
 steps all clear BAND — test 1: past 63 (7 steps: the row's token, the two calls, four steps), the 329-token prompt of row 2 (129 held + 200 fed; 5 steps) and the
@@ -353,6 +353,37 @@ def test_refusals_change_nothing():
     assert 1 <= len(ids) <= 2 and p.get_option("kv.free_tokens") == BLK
     p.advance_rows([1], [ADV_FEED], [[4, 5, 6]])
     assert p.past_length_row(1) == 129 and p.get_option("kv.free_tokens") == 0
+    p.close()
+
+
+def test_which_refusal_wins():
+    """calls that break two rules: the status and the message of the refusal that comes first, and lengths and kv.free_tokens as they were"""
+    m = llama(7, 24 * BLK)
+    prompts = [synth.synth_prompt(V, p, 11 + r) for r, p in enumerate((30, 31, 32, 33, 34))]
+    setup(m, prompts, [(GREEDY, 0)] * 5)
+    m.extend_row(4, [5, 6])                                               # row 4: no current token; rows 5 and 6 are new
+
+    def no(x, status, text, rows, kinds, ids):
+        s0 = ([x.past_length_row(r) for r in range(x.desc.max_batch)], x.get_option("kv.free_tokens"))
+        with pytest.raises(TgxError) as ei:
+            x.advance_rows(rows, kinds, ids)
+        assert ei.value.status == status and text in str(ei.value), (status, text, str(ei.value))
+        assert s0 == ([x.past_length_row(r) for r in range(x.desc.max_batch)], x.get_option("kv.free_tokens")), (rows, kinds)
+
+    no(m, 1, "kinds[1] = 3", [4, 0], [ADV_STEP, 3], [[1], [2]])             # the call's own checks come before any row's
+    no(m, 1, "65 step positions", [0, 1, 2, 3, 4], [ADV_STEP] * 5, [[1] * 12] * 5)
+    no(m, 4, "row 4 has no current token", [4, 0], [ADV_STEP, ADV_FEED], [[1], [1, V]])      # the rows in array order
+    no(m, 1, "token id out of range", [0, 4], [ADV_FEED, ADV_STEP], [[1, V], [1]])
+    no(m, 8, "context size exceeded: row 1", [1, 6], [ADV_FEED, ADV_FEED], [[1] * (CTX - 30), [1, 2]])      # the rows' checks come before the new rows' order
+    no(m, 1, "the new rows of a call must be 5..5", [6], [ADV_FEED], [[1, 2]])
+    m.close()
+    prompts = [synth.synth_prompt(V, 126, 3), synth.synth_prompt(V, 126, 4)]
+    p = llama(2, 3 * BLK)                                                 # paged: one block free, each row would take one
+    setup(p, prompts, [(GREEDY, 0)] * 2)
+    p.set_row_penalties(1, repetition=1.3)
+    no(p, 2, "row 1 has a logit processor on", [0, 1], [ADV_STEP, ADV_STEP], [[1, 2, 3], [4, 5, 6]])      # the budget is checked last
+    p.set_row_penalties(1)
+    no(p, 8, "1 free or held by its admissions' rows of", [0, 1], [ADV_STEP, ADV_STEP], [[1, 2, 3], [4, 5, 6]])
     p.close()
 
 

@@ -456,6 +456,31 @@ def test_every_refusal_changes_nothing():
     m.close()
 
 
+def test_which_refusal_wins():
+    """calls that break two rules: the status and the message of the refusal that comes first, and lengths and kv.free_tokens as they were"""
+    m = gpu_model("llama-3.2-1b", "bf16", 2, 10 * BLK)
+    m.forward_row(0, synth.synth_prompt(V, CTX - 5, 5)); m.forward_row(1, synth.synth_prompt(V, 31, 12))
+    for r in (0, 1):
+        m.sample_row(r, GREEDY)
+
+    def no(call, status, text, row, draft):
+        s0 = ([m.past_length_row(r) for r in range(2)], m.get_option("kv.free_tokens"))
+        with pytest.raises(TgxError) as ei:
+            call(row, draft)
+        assert ei.value.status == status and text in str(ei.value), (status, text, str(ei.value))
+        assert s0 == ([m.past_length_row(r) for r in range(2)], m.get_option("kv.free_tokens")), (row, draft)
+
+    m.set_row_stop(0, 1, [])
+    fin = m.decode_rows(1)[2]
+    assert fin[0] == 2 and m.past_length_row(0) == CTX - 4
+    no(m.verify_row, 4, "row 0 finished", 0, [1, 2, 3, 4])                # past + 5 > max_ctx as well: the row's state before the context size
+    m.set_row_sampler(1, SamplerCfg(temperature=0.7), 3)
+    m.set_row_penalties(1, repetition=1.3)
+    no(m.verify_row, 2, "row 1 does not sample greedily", 1, [1, 2])      # the row's sampler before its processors
+    no(m.verify_row_sampled, 2, "tgx_verify_row_sampled: row 1 has a logit processor on", 1, [1, 2])
+    m.close()
+
+
 def spec_engine(tmp_path):
     from host_util import HostEngine, host_lib, write_model_dir
     from ctypes import POINTER, c_int, c_int64, c_void_p

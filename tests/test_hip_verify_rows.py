@@ -250,6 +250,27 @@ def test_every_refusal_changes_nothing():
     p.close()
 
 
+def test_which_refusal_wins():
+    """calls that break two rules: the status and the message of the refusal that comes first, and lengths and kv.free_tokens as they were"""
+    m = llama(6, 24 * BLK)
+    prompts = [synth.synth_prompt(V, p, 11 + r) for r, p in enumerate((30, 31, 32, 33, 34))]
+    setup(m, prompts, [(GREEDY, 0)] * 5)
+    m.extend_row(4, [5, 6])                                               # row 4: no current token
+
+    def no(status, text, rows, drafts):
+        s0 = ([m.past_length_row(r) for r in range(6)], m.get_option("kv.free_tokens"))
+        with pytest.raises(TgxError) as ei:
+            m.verify_rows(rows, drafts)
+        assert ei.value.status == status and text in str(ei.value), (status, text, str(ei.value))
+        assert s0 == ([m.past_length_row(r) for r in range(6)], m.get_option("kv.free_tokens")), rows
+
+    no(4, "row 4 has no current token", [0, 1, 2, 3, 4], [[1] * 12] * 5)      # 65 positions: every row's checks come before the call's limit
+    no(4, "row 4 has no current token", [4, 0], [[1], [1] * 16])          # the rows in array order
+    no(1, "n_draft 16 out of range", [0, 4], [[1] * 16, [1]])
+    no(1, "row 0 named twice", [0, 1, 0], [[1], [2], [V]])                # ahead of the second naming's own checks
+    m.close()
+
+
 def test_the_same_call_twice_gives_the_same_bits():
     outs = []
     prompts = [synth.synth_prompt(V, p, 90 + r) for r, p in enumerate((63, 200, 129))]

@@ -5,6 +5,7 @@
 // entered by one thread only: examples/inference/main.cpp, server/HttpServer.cpp:118-163).
 // There is NO CPU path in this library: every entry point either runs on the GPU or returns an error.
 #include <climits>
+#include <functional>
 #include "ctx.h"
 #include "kernels/kv_fork.h"
 #include "kernels/kv_pack.h"
@@ -461,12 +462,16 @@ static int finished_row(const tgx_ctx* c) {   // a live row of the batch that fi
   return -1;
 }
 
-// tgx_read_probs evaluates a row's final probabilities on demand: remember what its last sampled step was configured with
+// tgx_read_probs evaluates a row's final probabilities on demand: does any row of the batch hold the vector of a sampled step? ...
+static void refresh_have_probs(tgx_ctx* c) {
+  c->have_probs = false;
+  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
+}
+// ... and remember what a row's last sampled step was configured with
 static void note_sampled(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg) {
   const bool sampled = !is_greedy(&cfg);
   for (int b = row0; b < row0 + R; b++) { c->row_host[(size_t)b].probs_cfg = cfg; c->row_host[(size_t)b].probs_ok = sampled; c->row_host[(size_t)b].probs_proc = false; }
-  c->have_probs = false;
-  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
+  refresh_have_probs(c);
 }
 
 // the engine passes one seed for a whole generation (the draw mixes in position and row): only a CHANGED seed is copied — and that
@@ -1240,7 +1245,15 @@ static int check_target_rows(tgx_ctx* c, int n, const int32_t* rows, const int32
 // may_join (tgx_forward_rows): consecutive whole prompts share ONE ragged prefill pass per group of <= max(8192, longest) workspace rows where a matrix-core route
 // takes the group's rows; every other prompt, and every prompt of tgx_forward_row, runs issue_pass's one-row pass.  Only a call with a ragged pass uploads tables
 // (one buffer, ONE upload: per group the tables of ragged_tables, then the call's ids) and holds the four lm_head staging rows.
-static int ensure_verify_ws(tgx_ctx* c);
+// the vf_* workspace: every position's logits of a one-row verify pass (tgx_verify_row), at first use; the group form of tgx_score_row holds it as well
+static int ensure_verify_ws(tgx_ctx* c) {
+  if (c->vf_rec) return TGX_OK;
+  const size_t R = tgx_ctx::VERIFY_ROWS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
+  int rc;
+  if ((rc = dev_alloc(c, &c->vf_x, R * H)) || (rc = dev_alloc(c, &c->vf_logits, R * V)) || (rc = dev_alloc(c, &c->vf_part_val, R * P)) || (rc = dev_alloc(c, &c->vf_part_idx, R * P))) return rc;
+  HIP_OK(c, hipMemset(c->vf_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
+  return dev_alloc(c, &c->vf_rec, sizeof(tgx::VerifyRecord) / 4);
+}
 // tgx_score_row: the workspace of a scoring pass of seq positions on route rt, before the pass is issued; the read-back of its scores, behind it
 static int score_prepare(tgx_ctx* c, ScoreCall* sc, PrefillRoute rt, int row) {
   sc->ids = c->rows[(size_t)row].prompt;
@@ -1793,30 +1806,130 @@ int tgx_restore_row(tgx_ctx* c, int row, const void* buf, int64_t bytes) {
   return TGX_OK;
 }
 
-// ---- tgx_extend_row / tgx_truncate_row (include/tgx.h): a live row grows by several positions in one pass, or is rolled back.  The pass is issue_pass's one-row pass
-// with the row's real length as `past` (every route takes it); the row then stands as tgx_forward_row leaves one.  Every check comes before anything changes.
+// ---- the continuation calls (include/tgx.h): live rows grow by several positions in one pass.  tgx_extend_row / tgx_score_row on a held row (a FEED of one row),
+// tgx_verify_row / tgx_verify_row_sampled (a STEP of one row: its current token and a draft, accepted on the device), tgx_verify_rows (n STEPs), tgx_advance_rows
+// (STEPs, FEEDs and admissions together).  Every call runs its own argument checks, in its own order and words, before anything changes; behind them ONE
+// description of the pass (ContPass) serves the blocks the calls share: the paged cache's room (check_paged_room), the STEP launches behind a joint pass (step_tail),
+// the host's bookkeeping from the device's records (follow_step_rows), the call's buffer (call_buffer), and the joint pass itself (joint_pass).
+static bool row_holds(const tgx_ctx* c, int row) { return row < c->batch && !c->row_host[(size_t)row].idle && c->row_host[(size_t)row].past >= 1; }      // (row >= 0) a sequence to continue
+
+// One continuation pass: its sequences in workspace order — the STEP sequences first, then the FEED / FEED_MORE ones, both in the caller's array order, so that the
+// STEP sequences alone are the pass's first ns sequences and first Ms workspace rows.  Built once per call, behind the call's checks
+struct ContPass {
+  int n = 0, ns = 0, M = 0, Ms = 0;                         // sequences and workspace rows; the STEP ones among them
+  // per sequence: batch row, index in the caller's arrays, TGX_ADV_*, first workspace row, positions in the pass (a STEP: n_draft + 1), the position it starts
+  // at (an admission: 0), n_draft (a FEED: 0)
+  std::vector<int> rows, idx, kind, first, lens, past, nd;
+  std::vector<const int64_t*> ids;                          // its ids in the caller's array (a STEP: the draft)
+  std::vector<char> holds, smp;                             // the row holds a sequence (0: an admission); a STEP row that does not sample greedily
+  std::vector<tgx_sampler_cfg> cfg;                         // a STEP row's sampler settings
+  std::vector<tgx::VerifyRecord> rec;                       // the STEP rows' records, read back behind the pass
+  std::vector<int> adm;                                     // the admissions' rows
+  bool any_sampled = false;
+  void add(const tgx_ctx* c, int row, int i, int k, const int64_t* src, int len) {      // (every STEP before the first FEED)
+    const bool step = k == TGX_ADV_STEP, held = step || row_holds(c, row);
+    const int sl = len + (step ? 1 : 0);
+    rows.push_back(row); idx.push_back(i); kind.push_back(k); ids.push_back(src); first.push_back(M); lens.push_back(sl); nd.push_back(step ? len : 0);
+    past.push_back(held ? (int)c->row_host[(size_t)row].past : 0); holds.push_back(held);
+    cfg.push_back(step ? row_cfg(c, row) : tgx_sampler_cfg{}); smp.push_back(step && !is_greedy(&cfg.back()));
+    any_sampled = any_sampled || smp.back();
+    if (!held) adm.push_back(row);
+    n++; M += sl;
+    if (step) { ns++; Ms += sl; rec.emplace_back(); }
+  }
+  // the ragged pass over all sequences, or over the STEP sequences alone
+  RaggedPass view(bool steps_only) const {
+    RaggedPass p;
+    p.n = steps_only ? ns : n; p.M = steps_only ? Ms : M;
+    p.rows = rows.data(); p.lens = lens.data(); p.first = first.data(); p.past = past.data();
+    for (int j = 0; j < p.n; j++) p.longest = std::max(p.longest, lens[(size_t)j]);
+    return p;
+  }
+};
+// the pass of an n-row call: row rows[i] takes lens[i] ids, the rows' ids back to back; kinds nullptr (tgx_verify_rows): every sequence a STEP
+static ContPass cont_pass(const tgx_ctx* c, int n, const int32_t* rows, const int32_t* kinds, const int64_t* ids, const int32_t* lens) {
+  ContPass cp;
+  for (int steps = 1; steps >= 0; steps--) {
+    long long off = 0;
+    for (int i = 0; i < n; off += lens[i], i++) {
+      const int k = kinds ? kinds[i] : TGX_ADV_STEP;
+      if ((k == TGX_ADV_STEP) == (bool)steps) cp.add(c, rows[i], i, k, ids ? ids + off : nullptr, lens[i]);
+    }
+  }
+  return cp;
+}
+
+// A row named by an n-row call: refused the second time (a row out of range is left to the row's own checks)
+static int name_row(tgx_ctx* c, std::vector<char>& named, int row) {
+  if (row < 0 || row >= c->d.max_batch) return TGX_OK;
+  if (named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+  named[(size_t)row] = 1;
+  return TGX_OK;
+}
+
+// The paged cache's room for a pass, all or nothing: the blocks of all its sequences together against the free list plus what the admissions' rows give back.
+// Ahead of it the refusal of more than 1024 blocks per row where the joint pass, or some sequence's own pass (the piecewise forms), takes a matrix-core route: the
+// prompt attention copies the row's block table into LDS (<= 1024 entries).  The budget message keeps each call's words.
+// (The block a continuation's first new position falls into is the row's own: a block forked siblings map as well is full, and tgx_truncate_row copies before it
+// leaves a row inside one.)
+enum RoomWords { ROOM_ROW, ROOM_CALL, ROOM_CALL_ADM };
+static int check_paged_room(tgx_ctx* c, const ContPass& cp, const char* fn, RoomWords words) {
+  if (!c->kv_paged) return TGX_OK;
+  auto matrix_core = [&](int len) { const PrefillRoute rt = prefill_route(c, len, len); return rt == ROUTE_SKINNY || rt == ROUTE_TILED; };
+  bool mfma = matrix_core(cp.M);
+  for (int j = 0; j < cp.n && !mfma; j++) mfma = matrix_core(cp.lens[(size_t)j]);
+  if (mfma && c->kv.tbl_stride() > 1024)
+    return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+  long long need = 0;
+  for (int j = 0; j < cp.n; j++)
+    need += c->kv.blocks_for((long long)cp.past[(size_t)j] + cp.lens[(size_t)j]) - (cp.holds[(size_t)j] ? c->kv.row_blocks(cp.rows[(size_t)j]) : 0);
+  const long long have = c->kv.available_for(cp.adm.data(), (int)cp.adm.size());
+  if (need <= have) return TGX_OK;
+  const std::string who = words == ROOM_ROW ? "row " + std::to_string(cp.rows[0]) : std::string("the call");
+  return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: %s needs %lld more blocks of %d tokens, %lld %s of %d (option kv.budget_tokens = %d)", who.c_str(), need, tgx::KV_BLOCK,
+                 have, words == ROOM_CALL_ADM ? "free or held by its admissions' rows" : "free", c->kv.n_blocks() - 1, c->kv_budget_tokens);
+}
+
+// The host follows the device: the STEP sequences [j0, j1) of a pass that has gone through, from their records — a record outside [1, positions] poisons the
+// context; else length, blocks (those assigned for the rejected tail go back to the pool), finished state, the log-probability count, the probabilities' state
+// (greedy: tgx_read_probs reads zeros for the row; sampled: the pass's scratch is not the row's, no vector until its next sampled step — the rule of tgx_fork_row)
+// and the caller's results.  The caller refreshes have_probs once its other rows are settled
+static int follow_step_rows(tgx_ctx* c, const ContPass& cp, int j0, int j1, const char* fn, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  for (int j = j0; j < j1; j++)
+    if (cp.rec[(size_t)j].n < 1 || cp.rec[(size_t)j].n > cp.lens[(size_t)j]) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record for row %d", fn, cp.rows[(size_t)j]); }
+  for (int j = j0; j < j1; j++) {
+    const int row = cp.rows[(size_t)j], i = cp.idx[(size_t)j];
+    const tgx::VerifyRecord& rec = cp.rec[(size_t)j];
+    RowHost& r = c->row_host[(size_t)row];
+    r.past = cp.past[(size_t)j] + rec.n;
+    r.fin = (char)rec.finish;
+    if (row_records(c, row)) r.lp_count += rec.n;
+    kv_trim_row(c, row, r.past);
+    if (!cp.smp[(size_t)j]) note_sampled(c, row, 1, cp.cfg[(size_t)j]);
+    else r.probs_ok = false;
+    for (int k = 0; k < rec.n; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = rec.ids[k];
+    out_n[i] = rec.n; out_finish[i] = rec.finish;
+    if (row == 0) c->last_sampled0 = rec.ids[rec.n - 1];
+  }
+  return TGX_OK;
+}
+
+// ---- tgx_extend_row (include/tgx.h): a live row grows by several positions in one pass.  The pass is issue_pass's one-row pass with the row's real length as
+// `past` (every route takes it); the row then stands as tgx_forward_row leaves one.
 static int extend_row(tgx_ctx* c, int row, const int64_t* ids, int seq, ScoreCall* sc) {      // sc (tgx_score_row): the pass also scores its positions
   if (!c->finalized) return set_err(c, TGX_ERR_STATE, "extend before finalize");
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
   if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
   if (seq < 1) return set_err(c, TGX_ERR_INVALID, "seq %d < 1", seq);
-  if (row >= c->batch || c->row_host[(size_t)row].idle || c->row_host[(size_t)row].past < 1)
-    return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to extend: use tgx_forward_row", row);
+  if (!row_holds(c, row)) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to extend: use tgx_forward_row", row);
   const long long past = c->row_host[(size_t)row].past;
   if (past + seq > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, seq, d.max_ctx);
   for (int i = 0; i < seq; i++)
     if (ids[i] < 0 || ids[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
-  if (c->kv_paged) {
-    const PrefillRoute rt = prefill_route(c, seq, seq);
-    if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv.tbl_stride() > 1024)      // the prompt attention copies the row's block table into LDS (<= 1024 entries)
-      return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_extend_row on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
-    const long long need = c->kv.blocks_for(past + seq) - c->kv.row_blocks(row), have = c->kv.available_for(nullptr, 0);
-    if (need > have)
-      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
-                     have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
-    // (the block the first new position falls into is the row's own: a block forked siblings map as well is full, and tgx_truncate_row copies before it leaves a row inside one)
-  }
+  ContPass cp;
+  cp.add(c, row, 0, TGX_ADV_FEED, ids, seq);
+  if (int rc = check_paged_room(c, cp, "tgx_extend_row", ROOM_ROW)) return rc;
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_extend_ws(c, seq, (int)past)) return rc;
   const PrefillRoute sc_rt = prefill_route(c, seq, seq);
@@ -1855,7 +1968,7 @@ int tgx_score_row(tgx_ctx* c, int row, const int64_t* ids, int seq, int top_n, f
     host.resize(tops ? n * (1 + 2 * L) : n);
     sc.host = host.data(); sc.host_bytes = host.size() * 4;
   } else sc.n_score = 0;      // (the pass is refused below)
-  const bool holds = c->finalized && row >= 0 && row < c->batch && !c->row_host[(size_t)row].idle && c->row_host[(size_t)row].past >= 1;
+  const bool holds = c->finalized && row >= 0 && row_holds(c, row);
   const int32_t r = row, s = seq;
   const int rc = holds ? extend_row(c, row, ids, seq, &sc) : admit_rows(c, 1, &r, ids, &s, /*may_join=*/false, &sc);
   if (rc || !n) return rc;
@@ -1865,21 +1978,11 @@ int tgx_score_row(tgx_ctx* c, int row, const int64_t* ids, int seq, int top_n, f
   return TGX_OK;
 }
 
-// ---- tgx_verify_row (include/tgx.h): greedy speculative decoding.  ONE causal pass — tgx_extend_row's, on whatever route it takes — over the row's current token
-// and the draft, with the logits of every position (issue_pass's verify form); ONE accept launch (kernels/verify.h) then takes the draft's matching prefix and
-// leaves the row as that many greedy decode steps would.  Every check comes before anything changes; the host follows the device's record afterwards.
-static int ensure_verify_ws(tgx_ctx* c) {      // (tgx_score_row's group form holds it as well)
-  if (c->vf_rec) return TGX_OK;
-  const size_t R = tgx_ctx::VERIFY_ROWS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
-  int rc;
-  if ((rc = dev_alloc(c, &c->vf_x, R * H)) || (rc = dev_alloc(c, &c->vf_logits, R * V)) || (rc = dev_alloc(c, &c->vf_part_val, R * P)) || (rc = dev_alloc(c, &c->vf_part_idx, R * P))) return rc;
-  HIP_OK(c, hipMemset(c->vf_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
-  return dev_alloc(c, &c->vf_rec, sizeof(tgx::VerifyRecord) / 4);
-}
-
-// both entry points: tgx_verify_row (`sampled_entry` false: a row that does not sample greedily is refused) and tgx_verify_row_sampled (such a row's positions are
-// drawn by its own sampler between the pass and the accept launch; a greedy row takes exactly tgx_verify_row's launches)
-// one row's checks, the same for the one-row calls (min_draft 1) and for every row of tgx_verify_rows (min_draft 0), in this order; nothing changes
+// ---- tgx_verify_row / tgx_verify_row_sampled (include/tgx.h): speculative decoding on one row.  ONE causal pass — tgx_extend_row's, on whatever route it takes —
+// over the row's current token and the draft, with the logits of every position (issue_pass's verify form); a row that does not sample greedily then draws every
+// position with its own sampler; ONE accept launch (kernels/verify.h) takes the draft's matching prefix and leaves the row as that many decode steps would.
+// One STEP row's checks, the same for the one-row calls (min_draft 1) and for every STEP row of tgx_verify_rows / tgx_advance_rows (min_draft 0), in this order;
+// sampled_entry false (tgx_verify_row): a row that does not sample greedily is refused.  Nothing changes
 static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int min_draft, bool sampled_entry, const char* fn) {
   const tgx_model_desc& d = c->d;
   if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
@@ -1887,7 +1990,7 @@ static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_dra
   for (int i = 0; i < n_draft; i++)
     if (draft[i] < 0 || draft[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "draft token id out of range");
   const RowHost& rh = c->row_host[(size_t)row];
-  if (row >= c->batch || rh.idle || rh.past < 1) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to verify a draft on", row);
+  if (!row_holds(c, row)) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to verify a draft on", row);
   if (rh.fin) return set_err(c, TGX_ERR_STATE, "row %d finished: tgx_extend_row / tgx_reset_row it first", row);
   if (rh.nologits) return set_err(c, TGX_ERR_STATE, "row %d was truncated and holds no logits: tgx_extend_row it first", row);
   if (!rh.tok) return set_err(c, TGX_ERR_STATE, "row %d has no current token: tgx_sample_row it first", row);
@@ -1897,7 +2000,36 @@ static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_dra
   if (rh.past + n_draft + 1 > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, (long long)rh.past, n_draft + 1, d.max_ctx);
   return TGX_OK;
 }
-static int verify_row_run(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, const char* fn);
+// ... and behind the checks, STEP sequence j of a pass by itself: the one-row pass, the draws of a sampled row, the accept launch, the host's bookkeeping (the
+// row-by-row form of verify_steps runs it per row: n_draft 0 is then a pass of the current token alone)
+static int verify_row_run(tgx_ctx* c, ContPass& cp, int j, const char* fn, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  const int row = cp.rows[(size_t)j], M = cp.lens[(size_t)j], past = cp.past[(size_t)j];
+  const bool sampled = cp.smp[(size_t)j];
+  static_assert((int)tgx_ctx::VERIFY_ROWS == tgx::VERIFY_MAX_POS, "kernels/verify.h VerifyRecord");
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = ensure_verify_ws(c)) return rc;
+  if (sampled) if (int rc = vs_alloc(c)) return rc;      // the positions' sampler workspace: only a sampled row's call ever holds it
+  if (int rc = ensure_extend_ws(c, M, past)) return rc;
+  c->vf_pass_rows = 0;                             // the workspace changes hands
+  (void)kv_ensure_blocks(c, row, (long long)past + M);      // the whole pass up front; cannot fail: counted above
+  long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the draft; input 0 is written on the device from the row's token word
+  for (int i = 0; i + 1 < M; i++) ids[i + 1] = cp.ids[(size_t)j][i];
+  HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+  launch_verify_first_id(c, row);
+  if (int rc = issue_pass(c, row, 1, M, past, /*verify=*/true)) return rc;
+  if (sampled) launch_sample_positions(c, row, M, cp.cfg[(size_t)j]);      // every position's draw under the row's settings, with the key its step would use
+  launch_verify_accept(c, row, M, sampled ? c->vs_draws : nullptr);
+  if (row_records(c, row)) launch_logprobs_verify(c, row, M);      // one record per produced token, each from the logits of the position that produced it
+  HIP_OK(c, hipMemcpyAsync(&cp.rec[(size_t)j], c->vf_rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = finish_pass(c)) return rc;
+  if (int rc = follow_step_rows(c, cp, j, j + 1, fn, out_ids, out_n, out_finish)) return rc;
+  c->vf_pass_rows = M; c->vf_pass_joint = false;
+  refresh_have_probs(c);
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
 
 static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, bool sampled_entry) {
   const char* const fn = sampled_entry ? "tgx_verify_row_sampled" : "tgx_verify_row";
@@ -1906,69 +2038,11 @@ static int verify_row_impl(tgx_ctx* c, int row, const int64_t* draft, int n_draf
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   // ---- every check before anything changes
   if (int rc = verify_row_check(c, row, draft, n_draft, /*min_draft=*/1, sampled_entry, fn)) return rc;
-  const int M = n_draft + 1;
-  const long long past = c->row_host[(size_t)row].past;
-  static_assert((int)tgx_ctx::VERIFY_ROWS == tgx::VERIFY_MAX_POS, "kernels/verify.h VerifyRecord");
-  if (c->kv_paged) {
-    const PrefillRoute rt = prefill_route(c, M, M);
-    if ((rt == ROUTE_SKINNY || rt == ROUTE_TILED) && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
-      return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
-    const long long need = c->kv.blocks_for(past + M) - c->kv.row_blocks(row), have = c->kv.available_for(nullptr, 0);
-    if (need > have)
-      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: row %d needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", row, need, tgx::KV_BLOCK,
-                     have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
-    // (the first new position falls into a block the row owns: a block forked siblings map as well is full)
-  }
-  return verify_row_run(c, row, draft, n_draft, out_ids, out_n, out_finish, fn);
+  ContPass cp;
+  cp.add(c, row, 0, TGX_ADV_STEP, draft, n_draft);
+  if (int rc = check_paged_room(c, cp, fn, ROOM_ROW)) return rc;
+  return verify_row_run(c, cp, 0, fn, out_ids, out_n, out_finish);
 }
-// ... and behind the checks: the pass, the draws of a sampled row, the accept launch, the host's bookkeeping (tgx_verify_rows' row-by-row form runs it per row
-// after ITS checks: n_draft 0 is then a pass of the current token alone)
-static int verify_row_run(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish, const char* fn) {
-  const tgx_sampler_cfg cfg = row_cfg(c, row);
-  const bool sampled = !is_greedy(&cfg);
-  const int M = n_draft + 1;
-  const long long past = c->row_host[(size_t)row].past;
-  HIP_OK(c, hipSetDevice(c->device));
-  if (int rc = ensure_verify_ws(c)) return rc;
-  if (sampled) if (int rc = vs_alloc(c)) return rc;      // the positions' sampler workspace: only a sampled row's call ever holds it
-  if (int rc = ensure_extend_ws(c, M, (int)past)) return rc;
-  c->vf_pass_rows = 0;                             // the workspace changes hands
-  (void)kv_ensure_blocks(c, row, past + M);        // the whole pass up front; cannot fail: counted above
-  long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the draft; input 0 is written on the device from the row's token word
-  for (int i = 0; i < n_draft; i++) ids[i + 1] = draft[i];
-  HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
-  launch_verify_first_id(c, row);
-  if (int rc = issue_pass(c, row, 1, M, (int)past, /*verify=*/true)) return rc;
-  if (sampled) launch_sample_positions(c, row, M, cfg);      // every position's draw under the row's settings, with the key its step would use
-  launch_verify_accept(c, row, M, sampled ? c->vs_draws : nullptr);
-  const bool records = row_records(c, row);
-  if (records) launch_logprobs_verify(c, row, M);      // one record per produced token, each from the logits of the position that produced it
-  tgx::VerifyRecord rec{};
-  HIP_OK(c, hipMemcpyAsync(&rec, c->vf_rec, sizeof rec, hipMemcpyDeviceToHost, c->stream));
-  if (int rc = finish_pass(c)) return rc;
-  if (rec.n < 1 || rec.n > M) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record", fn); }
-  c->vf_pass_rows = M; c->vf_pass_joint = false;
-  // ---- the host follows the device: length, blocks, finished state
-  RowHost& r = c->row_host[(size_t)row];
-  r.past = past + rec.n;
-  r.fin = (char)rec.finish;
-  if (records) r.lp_count += rec.n;
-  kv_trim_row(c, row, r.past);                     // the blocks assigned for the rejected tail go back to the pool
-  if (!sampled) note_sampled(c, row, 1, cfg);      // greedy: tgx_read_probs reads zeros for the row
-  else {                                           // the pass's scratch is not the row's: no vector until its next sampled step (the rule of tgx_fork_row)
-    r.probs_ok = false;
-    c->have_probs = false;
-    for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
-  }
-  for (int i = 0; i < rec.n; i++) out_ids[i] = rec.ids[i];
-  *out_n = rec.n; *out_finish = rec.finish;
-  if (row == 0) c->last_sampled0 = rec.ids[rec.n - 1];
-  refresh_longest(c);
-  c->have_logits = true;
-  HIP_OK(c, hipGetLastError());
-  return TGX_OK;
-}
-
 int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
   return verify_row_impl(c, row, draft, n_draft, out_ids, out_n, out_finish, /*sampled_entry=*/false);
 }
@@ -1976,11 +2050,12 @@ int tgx_verify_row_sampled(tgx_ctx* c, int row, const int64_t* draft, int n_draf
   return verify_row_impl(c, row, draft, n_draft, out_ids, out_n, out_finish, /*sampled_entry=*/true);
 }
 
-// ---- tgx_verify_rows (include/tgx.h): the drafts of n rows in ONE causal pass and ONE accept launch.  The pass is tgx_forward_rows' ragged pass with each
-// sequence's real length as its `past` (RaggedPass.past): row i's current token and draft at workspace rows [first_i, first_i + n_draft[i] + 1) into its cache from
-// past_i, on prefill_route(M, M)'s skinny or tiled route; lm_head of all M positions into the vj_* workspace; one sampler chain per sampled row over its slice; the
-// accept launch with one workgroup per row (kernels/verify.h); ONE read-back of the n records.  Where no matrix-core route takes the M positions (fp32 storage,
-// prefill.mfma 0, shapes the tile does not cover, M below the routes' minimum) the rows run verify_row_run one by one behind the same checks: verify.last_form 2.
+// ---- the joint pass of tgx_verify_rows and tgx_advance_rows: the pass's sequences in ONE ragged causal pass — tgx_forward_rows' with each sequence's real length as
+// its `past` (RaggedPass.past) — on the skinny or tiled route rt.  Sequence j's ids stand at workspace rows [first_j, first_j + lens_j) and go into its row's cache
+// from past_j; a STEP sequence's row 0 is the row's current token, written on the device.  Behind the pass: the STEP sequences' tail (step_tail), tgx_forward_rows'
+// lm_head for the FEED rows' last positions (launch_lm_head_rows; FEED_MORE rows: none), ONE read-back of the records.
+// The vj_* workspace of the STEP positions: hidden rows, logits and argmax partials per position, the sampled rows' draws, one record per row and the accept
+// launch's argument table; sized by the first call that has a STEP
 static int ensure_verify_rows_ws(tgx_ctx* c) {
   if (c->vj_args) return TGX_OK;      // the last of them
   const size_t R = tgx_ctx::VERIFY_POSITIONS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid, B = (size_t)c->d.max_batch;
@@ -1990,7 +2065,120 @@ static int ensure_verify_rows_ws(tgx_ctx* c) {
   HIP_OK(c, hipMemset(c->vj_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
   return dev_alloc(c, &c->vj_args, B * verify_args_bytes());
 }
+// The call's buffer: the pass's tables, then its ids — ONE upload.  tables(host, dev): ragged_tables, or advance_tables with its target; (nullptr, nullptr) sizes
+// them.  Grows rg_buf, fills `host` (it lives until finish_pass has synchronised) and scatters the caller's ids behind each sequence's first slot (input 0 of a STEP
+// sequence is written on the device from the row's token word); *o_ids: where the ids stand in the buffer
+typedef std::function<size_t(unsigned char* host, const unsigned char* dev)> PassTables;
+static int call_buffer(tgx_ctx* c, const ContPass& cp, const RaggedPass& p, const PassTables& tables, std::vector<unsigned char>& host, size_t* o_ids) {
+  *o_ids = tables(nullptr, nullptr);
+  if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, *o_ids + (size_t)p.M * 8)) return rc;
+  host.assign(*o_ids + (size_t)p.M * 8, 0);
+  tables(host.data(), c->rg_buf);
+  long long* const h_ids = reinterpret_cast<long long*>(host.data() + *o_ids);
+  for (int j = 0; j < p.n; j++) {
+    const int step = j < cp.ns ? 1 : 0;
+    for (int k = 0; k < cp.lens[(size_t)j] - step; k++) h_ids[cp.first[(size_t)j] + step + k] = cp.ids[(size_t)j][k];
+  }
+  return TGX_OK;
+}
+// The STEP tail behind a joint pass: lm_head of the Ms STEP positions into the vj_* workspace; a sampled row's positions under its own settings, each with the key its
+// step would use (the chains share one scratch: stream order); the accept launch with one workgroup per row (kernels/verify.h); one log-probability record per
+// produced token of a recording row; the records' read-back, queued
+static int step_tail(tgx_ctx* c, ContPass& cp, PrefillRoute lm_rt, const long long* d_ids) {
+  launch_lm_head_all(c, lm_rt, cp.Ms, nullptr, /*joint=*/true);
+  for (int j = 0; j < cp.ns; j++)
+    if (cp.smp[(size_t)j]) launch_sample_positions(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.cfg[(size_t)j], cp.first[(size_t)j]);
+  launch_verify_accept_rows(c, d_ids, cp.ns, cp.rows.data(), cp.first.data(), cp.nd.data(), cp.smp.data());
+  for (int j = 0; j < cp.ns; j++)
+    if (row_records(c, cp.rows[(size_t)j])) launch_logprobs_verify(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.first[(size_t)j], j);
+  HIP_OK(c, hipMemcpyAsync(cp.rec.data(), c->vj_rec, (size_t)cp.ns * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  return TGX_OK;
+}
+// The attention form is the routine's one switch.  ATTN_KEY_SPLIT (tgx_verify_rows): the STEP sequences alone — the pass's first ns — with the key-split attention
+// (ragged_tables, ensure_extend_rg_ws; kernels/attn_extend.h), recorded in verify.last_form / last_splits.  ATTN_MIXED (tgx_advance_rows): every sequence with
+// the mixed work list (advance_tables at advance_attn_target, ensure_mix_ws; kernels/attn_mixed.h), recorded in advance.last_form / last_tiles.  The two forms
+// agree only up to the order of the fp32 sums: neither call takes the other's
+enum ContAttn { ATTN_KEY_SPLIT, ATTN_MIXED };
+static int joint_pass(tgx_ctx* c, ContPass& cp, ContAttn attn, PrefillRoute rt, const char* fn, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  static_assert(TGX_MAX_VERIFY_POSITIONS <= tgx::VERIFY_MAX_ROWS, "kernels/verify.h VerifyFirstIds");
+  const bool mixed = attn == ATTN_MIXED;
+  RaggedPass p = cp.view(/*steps_only=*/!mixed);
+  const int n = p.n, ns = cp.ns;
+  if (ns) if (int rc = ensure_verify_rows_ws(c)) return rc;
+  if (cp.any_sampled) if (int rc = vs_alloc(c)) return rc;
+  // the STEP positions' lm_head: on the tiled route the GEMV form would stream the lm_head weights once per FOUR positions (32 step rows: eight passes, measured
+  // +0.8 ms on Llama-3.2-1B, profiles/advance_rows.txt); where the skinny route would take Ms rows by themselves, its one-pass form serves them from ws_x
+  // (a pass of STEP sequences alone: rt is that route already)
+  PrefillRoute lm_rt = rt;
+  if (ns && rt == ROUTE_TILED && prefill_route(c, cp.Ms, cp.Ms) == ROUTE_SKINNY) {
+    if (int rc = ensure_skinny_ws(c, cp.Ms)) return rc;
+    lm_rt = ROUTE_SKINNY;
+  }
+  std::vector<int> head_rows;     // the FEED rows: their last position's logits
+  for (int j = ns; j < n; j++) if (cp.kind[(size_t)j] == TGX_ADV_FEED) head_rows.push_back(cp.rows[(size_t)j]);
+  if (!head_rows.empty()) if (int rc = ensure_rg_lm_ws(c)) return rc;
+  int target = 0;
+  if (mixed) target = advance_attn_target(c, p);
+  else if (int rc = ensure_extend_rg_ws(c, p)) return rc;
+  std::vector<unsigned char> host;
+  size_t o_ids = 0;
+  if (int rc = call_buffer(c, cp, p, [&](unsigned char* h, const unsigned char* dev) { return mixed ? advance_tables(c, p, h, dev, target) : ragged_tables(c, p, h, dev); }, host, &o_ids)) return rc;
+  if (mixed) if (int rc = ensure_mix_ws(c, p)) return rc;
+  long long* const d_ids = reinterpret_cast<long long*>(c->rg_buf + o_ids);
+  p.ids = d_ids;
+  c->vf_pass_rows = 0;                             // the workspace changes hands
+  if (c->kv_paged)                                 // the admissions' rows give their blocks back first
+    for (int j = ns; j < n; j++) if (!cp.holds[(size_t)j]) kv_release_row(c, cp.rows[(size_t)j]);
+  for (int j = 0; j < n; j++) (void)kv_ensure_blocks(c, cp.rows[(size_t)j], (long long)cp.past[(size_t)j] + cp.lens[(size_t)j]);      // cannot fail: counted (check_paged_room)
+  for (int j = ns; j < n; j++) {                   // retired rows that rode along since their reset: position word back to 0
+    const int row = cp.rows[(size_t)j];
+    if (!cp.holds[(size_t)j] && c->row_host[(size_t)row].past != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream)); c->row_host[(size_t)row].past = 0; }
+  }
+  HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+  if (ns) launch_verify_first_ids(c, d_ids, ns, cp.rows.data(), cp.first.data());
+  if (int rc = launch_route(c, rt, p.M, 0, 0, 0, /*past=*/0, &p)) return rc;
+  if (ns) if (int rc = step_tail(c, cp, lm_rt, d_ids)) return rc;
+  launch_lm_head_rows(c, head_rows);
+  for (int j = ns; j < n; j++) launch_add_pos(c, c->rows[(size_t)cp.rows[(size_t)j]].pos, cp.lens[(size_t)j]);
+  if (int rc = finish_pass(c)) return rc;
+  // ---- the host follows the device: the STEP rows from their records, the FEED rows as an admission / tgx_extend_row does
+  if (int rc = follow_step_rows(c, cp, 0, ns, fn, out_ids, out_n, out_finish)) return rc;
+  c->vf_pass_rows = cp.Ms; c->vf_pass_joint = true;
+  if (mixed) { c->advance_last_form = 1; c->advance_last_tiles = target; }
+  else { c->verify_last_form = 1; c->verify_last_splits = p.ext_ns; }
+  for (int j = ns; j < n; j++) {
+    const int row = cp.rows[(size_t)j];
+    c->batch = std::max(c->batch, row + 1);
+    row_admitted(c, row, cp.past[(size_t)j] + cp.lens[(size_t)j], /*keep_lp_count=*/(bool)cp.holds[(size_t)j]);
+    if (cp.kind[(size_t)j] == TGX_ADV_FEED_MORE) c->row_host[(size_t)row].nologits = true;      // its logits slot is not the caller's to read: more of the prompt follows
+  }
+  refresh_have_probs(c);
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
+}
 
+// The STEP sequences of a pass behind their checks — all of tgx_verify_rows, and the STEP part of tgx_advance_rows' piecewise form.  Where a matrix-core route
+// takes the Ms positions: the joint pass with the key-split attention.  Else (fp32 storage, prefill.mfma 0, shapes the tile does not cover, Ms below the routes'
+// minimum) row by row: each row's own pass -> draws -> accept, bit for bit the one-row call; its positions' logits then join the call's in vj_logits:
+// verify.last_form 2
+static int verify_steps(tgx_ctx* c, ContPass& cp, const char* fn, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  const PrefillRoute rt = prefill_route(c, cp.Ms, cp.Ms);
+  if (rt == ROUTE_SKINNY || rt == ROUTE_TILED) return joint_pass(c, cp, ATTN_KEY_SPLIT, rt, fn, out_ids, out_n, out_finish);
+  if (int rc = ensure_verify_rows_ws(c)) return rc;
+  const size_t V = (size_t)c->d.vocab;
+  for (int j = 0; j < cp.ns; j++) {
+    if (int rc = verify_row_run(c, cp, j, fn, out_ids, out_n, out_finish)) return rc;
+    HIP_OK(c, hipMemcpyAsync(c->vj_logits + (size_t)cp.first[(size_t)j] * V, c->vf_logits, (size_t)cp.lens[(size_t)j] * V * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (int rc = finish_pass(c)) return rc;
+  c->vf_pass_rows = cp.Ms; c->vf_pass_joint = true;
+  c->verify_last_form = 2;
+  return TGX_OK;
+}
+
+// ---- tgx_verify_rows (include/tgx.h): the drafts of n rows in ONE causal pass and ONE accept launch (verify_steps)
 int tgx_verify_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* drafts, const int32_t* n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
   const char* const fn = "tgx_verify_rows";
   if (!c || !rows || !drafts || !n_draft || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
@@ -1998,115 +2186,25 @@ int tgx_verify_rows(tgx_ctx* c, int n, const int32_t* rows, const int64_t* draft
   if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
   const tgx_model_desc& d = c->d;
   if (n < 1 || n > d.max_batch) return set_err(c, TGX_ERR_INVALID, "n %d out of range [1,%d]", n, d.max_batch);
-  // ---- every check before anything changes: per row in array order, each row's in the one-row call's order
-  std::vector<int> first((size_t)n), lens((size_t)n), past((size_t)n), rws((size_t)n), nd((size_t)n);
+  // ---- every check before anything changes: per row in array order, each row's in the one-row call's order; the call's position limit behind them
   std::vector<char> named((size_t)d.max_batch, 0);
   long long M = 0, off = 0;
   for (int i = 0; i < n; i++) {
-    const int row = rows[i];
-    if (row >= 0 && row < d.max_batch && named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    if (int rc = name_row(c, named, rows[i])) return rc;
     if (n_draft[i] < 0 || n_draft[i] > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [0,%d]", (int)n_draft[i], TGX_MAX_DRAFT);      // (ahead of the read of its ids)
-    if (int rc = verify_row_check(c, row, drafts + off, n_draft[i], /*min_draft=*/0, /*sampled_entry=*/true, fn)) return rc;
-    named[(size_t)row] = 1;
-    rws[(size_t)i] = row; nd[(size_t)i] = n_draft[i]; lens[(size_t)i] = n_draft[i] + 1; first[(size_t)i] = (int)M; past[(size_t)i] = (int)c->row_host[(size_t)row].past;
+    if (int rc = verify_row_check(c, rows[i], drafts + off, n_draft[i], /*min_draft=*/0, /*sampled_entry=*/true, fn)) return rc;
     M += n_draft[i] + 1; off += n_draft[i];
   }
   if (M > TGX_MAX_VERIFY_POSITIONS) return set_err(c, TGX_ERR_INVALID, "%s: %lld positions in one call (at most %d)", fn, M, TGX_MAX_VERIFY_POSITIONS);
-  static_assert(TGX_MAX_VERIFY_POSITIONS <= tgx::VERIFY_MAX_ROWS, "kernels/verify.h VerifyFirstIds");
-  const PrefillRoute rt = prefill_route(c, (int)M, (int)M);
-  const bool joint = rt == ROUTE_SKINNY || rt == ROUTE_TILED;
-  if (c->kv_paged) {
-    bool mfma_row = joint;      // row by row: does some row's own pass take a matrix-core route?
-    for (int i = 0; i < n && !mfma_row; i++) { const PrefillRoute r1 = prefill_route(c, lens[(size_t)i], lens[(size_t)i]); mfma_row = r1 == ROUTE_SKINNY || r1 == ROUTE_TILED; }
-    if (mfma_row && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
-      return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
-    // all or nothing: the blocks of all named rows together against the free list
-    long long need = 0;
-    for (int i = 0; i < n; i++) need += c->kv.blocks_for((long long)past[(size_t)i] + lens[(size_t)i]) - c->kv.row_blocks(rws[(size_t)i]);
-    const long long have = c->kv.available_for(nullptr, 0);
-    if (need > have)
-      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld more blocks of %d tokens, %lld free of %d (option kv.budget_tokens = %d)", need, tgx::KV_BLOCK, have,
-                     c->kv.n_blocks() - 1, c->kv_budget_tokens);
-  }
+  ContPass cp = cont_pass(c, n, rows, /*kinds=*/nullptr, drafts, n_draft);
+  if (int rc = check_paged_room(c, cp, fn, ROOM_CALL)) return rc;
   HIP_OK(c, hipSetDevice(c->device));
-  if (int rc = ensure_verify_rows_ws(c)) return rc;
-  const size_t V = (size_t)d.vocab;
-  if (!joint) {      // ---- row by row: each row's own pass -> draws -> accept, bit for bit the one-row call; its positions' logits then join the call's in vj_logits
-    for (int i = 0; i < n; i++) {
-      if (int rc = verify_row_run(c, rws[(size_t)i], drafts + (first[(size_t)i] - i), nd[(size_t)i], out_ids + (size_t)i * (TGX_MAX_DRAFT + 1), out_n + i, out_finish + i, fn)) return rc;
-      HIP_OK(c, hipMemcpyAsync(c->vj_logits + (size_t)first[(size_t)i] * V, c->vf_logits, (size_t)lens[(size_t)i] * V * 4, hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (int rc = finish_pass(c)) return rc;
-    c->vf_pass_rows = (int)M; c->vf_pass_joint = true;
-    c->verify_last_form = 2;
-    return TGX_OK;
-  }
-  // ---- the joint pass
-  std::vector<tgx_sampler_cfg> cfg((size_t)n);
-  std::vector<char> smp((size_t)n, 0);
-  bool any_sampled = false;
-  for (int i = 0; i < n; i++) { cfg[(size_t)i] = row_cfg(c, rws[(size_t)i]); smp[(size_t)i] = !is_greedy(&cfg[(size_t)i]); any_sampled = any_sampled || smp[(size_t)i]; }
-  if (any_sampled) if (int rc = vs_alloc(c)) return rc;
-  RaggedPass p;
-  p.n = n; p.M = (int)M; p.rows = rws.data(); p.lens = lens.data(); p.first = first.data(); p.past = past.data();
-  for (int i = 0; i < n; i++) p.longest = std::max(p.longest, lens[(size_t)i]);
-  if (int rc = ensure_extend_rg_ws(c, p)) return rc;
-  // the call's buffer: the pass's tables, then its ids (ONE upload; input 0 of every sequence is written on the device from the row's token word)
-  const size_t o_ids = ragged_tables(c, p, nullptr, nullptr), bytes = o_ids + (size_t)M * 8;
-  if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
-  std::vector<unsigned char> host(bytes, 0);      // (lives until finish_pass has synchronised)
-  ragged_tables(c, p, host.data(), c->rg_buf);
-  long long* const h_ids = reinterpret_cast<long long*>(host.data() + o_ids);
-  for (int i = 0; i < n; i++)
-    for (int k = 0; k < nd[(size_t)i]; k++) h_ids[first[(size_t)i] + 1 + k] = drafts[first[(size_t)i] - i + k];
-  long long* const d_ids = reinterpret_cast<long long*>(c->rg_buf + o_ids);
-  p.ids = d_ids;
-  c->vf_pass_rows = 0;                             // the workspace changes hands
-  for (int i = 0; i < n; i++) (void)kv_ensure_blocks(c, rws[(size_t)i], (long long)past[(size_t)i] + lens[(size_t)i]);      // cannot fail: counted above
-  HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
-  launch_verify_first_ids(c, d_ids, n, rws.data(), first.data());
-  if (int rc = launch_route(c, rt, (int)M, 0, 0, 0, /*past=*/0, &p)) return rc;
-  launch_lm_head_all(c, rt, (int)M, nullptr, /*joint=*/true);
-  for (int i = 0; i < n; i++)      // a sampled row's positions under its own settings, each with the key its step would use; the chains share one scratch: stream order
-    if (smp[(size_t)i]) launch_sample_positions(c, rws[(size_t)i], lens[(size_t)i], cfg[(size_t)i], first[(size_t)i]);
-  launch_verify_accept_rows(c, d_ids, n, rws.data(), first.data(), nd.data(), smp.data());
-  for (int i = 0; i < n; i++)
-    if (row_records(c, rws[(size_t)i])) launch_logprobs_verify(c, rws[(size_t)i], lens[(size_t)i], first[(size_t)i], i);
-  std::vector<tgx::VerifyRecord> rec((size_t)n);
-  HIP_OK(c, hipMemcpyAsync(rec.data(), c->vj_rec, (size_t)n * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
-  if (int rc = finish_pass(c)) return rc;
-  for (int i = 0; i < n; i++)
-    if (rec[(size_t)i].n < 1 || rec[(size_t)i].n > lens[(size_t)i]) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record for row %d", fn, rws[(size_t)i]); }
-  c->vf_pass_rows = (int)M; c->vf_pass_joint = true;
-  c->verify_last_form = 1; c->verify_last_splits = p.ext_ns;
-  // ---- the host follows the device, row by row as the one-row call does
-  for (int i = 0; i < n; i++) {
-    const int row = rws[(size_t)i];
-    const tgx::VerifyRecord& rc1 = rec[(size_t)i];
-    RowHost& r = c->row_host[(size_t)row];
-    r.past = past[(size_t)i] + rc1.n;
-    r.fin = (char)rc1.finish;
-    if (row_records(c, row)) r.lp_count += rc1.n;
-    kv_trim_row(c, row, r.past);
-    if (!smp[(size_t)i]) note_sampled(c, row, 1, cfg[(size_t)i]);
-    else r.probs_ok = false;
-    for (int k = 0; k < rc1.n; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = rc1.ids[k];
-    out_n[i] = rc1.n; out_finish[i] = rc1.finish;
-    if (row == 0) c->last_sampled0 = rc1.ids[rc1.n - 1];
-  }
-  c->have_probs = false;
-  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
-  refresh_longest(c);
-  c->have_logits = true;
-  HIP_OK(c, hipGetLastError());
-  return TGX_OK;
+  return verify_steps(c, cp, fn, out_ids, out_n, out_finish);
 }
 
 // ---- tgx_advance_rows (include/tgx.h): STEP rows (tgx_verify_rows' sequences) and FEED / FEED_MORE rows (continuations from their row's length, admissions from 0)
-// in ONE ragged pass.  The STEP sequences come first in the workspace, so launch_lm_head_all(.., joint) and launch_verify_accept_rows serve them as they serve
-// tgx_verify_rows; the FEED rows take tgx_forward_rows' lm_head (launch_lm_head_rows), FEED_MORE rows none.  The attention is the mixed work list (prefill.hip
-// advance_tables; kernels/attn_mixed.h).  Where no matrix-core route takes the M positions the equivalent calls run one after another behind the joint checks:
-// advance.last_form 2.
+// in ONE ragged pass: the joint pass with the mixed attention.  Where no matrix-core route takes the M positions the equivalent calls run one after another
+// behind the joint checks — the STEP rows through verify_steps, a FEED through extend_row or admit_rows: advance.last_form 2.
 int tgx_advance_rows(tgx_ctx* c, int n, const int32_t* rows, const int32_t* kinds, const int64_t* ids, const int32_t* lens, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
   const char* const fn = "tgx_advance_rows";
   if (!c || !rows || !kinds || !lens || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
@@ -2126,180 +2224,50 @@ int tgx_advance_rows(tgx_ctx* c, int n, const int32_t* rows, const int32_t* kind
   if (Ms > TGX_MAX_VERIFY_POSITIONS) return set_err(c, TGX_ERR_INVALID, "%s: %lld step positions in one call (at most %d)", fn, Ms, TGX_MAX_VERIFY_POSITIONS);
   if (M > TGX_MAX_ADVANCE_POSITIONS) return set_err(c, TGX_ERR_INVALID, "%s: %lld positions in one call (at most %d)", fn, M, TGX_MAX_ADVANCE_POSITIONS);
   if (n_ids > 0 && !ids) return set_err(c, TGX_ERR_INVALID, "null argument");
-  // ... then per row in array order, each row's in its equivalent call's order
-  std::vector<long long> off((size_t)n + 1, 0);      // row i's ids at ids + off[i]
-  std::vector<char> named((size_t)d.max_batch, 0), holds((size_t)n, 0);
+  // ... then per row in array order, each row's in its equivalent call's order; the new rows' order behind them
+  std::vector<char> named((size_t)d.max_batch, 0);
   int n_new = 0;
-  for (int i = 0; i < n; i++) {
+  long long off = 0;
+  for (int i = 0; i < n; off += lens[i], i++) {
     const int row = rows[i], len = lens[i];
-    off[(size_t)i + 1] = off[(size_t)i] + len;
-    const int64_t* const my = ids ? ids + off[(size_t)i] : nullptr;
-    if (row >= 0 && row < d.max_batch && named[(size_t)row]) return set_err(c, TGX_ERR_INVALID, "row %d named twice", row);
+    const int64_t* const my = ids ? ids + off : nullptr;
+    if (int rc = name_row(c, named, row)) return rc;
     if (kinds[i] == TGX_ADV_STEP) {
       if (len > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [0,%d]", len, TGX_MAX_DRAFT);      // (ahead of the read of its ids)
       if (int rc = verify_row_check(c, row, my, len, /*min_draft=*/0, /*sampled_entry=*/true, fn)) return rc;
     } else {
       if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
       if (len < 1) return set_err(c, TGX_ERR_INVALID, "seq %d < 1", len);
-      const RowHost& rh = c->row_host[(size_t)row];
-      holds[(size_t)i] = row < c->batch && !rh.idle && rh.past >= 1;
-      if (holds[(size_t)i] && rh.past + len > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, (long long)rh.past, len, d.max_ctx);
-      if (!holds[(size_t)i] && len > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "prompt %d: seq %d out of range (context size %d)", i, len, d.max_ctx);
+      const long long past = c->row_host[(size_t)row].past;
+      if (row_holds(c, row) && past + len > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, past, len, d.max_ctx);
+      if (!row_holds(c, row) && len > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "prompt %d: seq %d out of range (context size %d)", i, len, d.max_ctx);
       for (int k = 0; k < len; k++)
         if (my[k] < 0 || my[k] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "token id out of range");
       n_new += row >= c->batch;
     }
-    named[(size_t)row] = 1;
   }
   for (int row = c->batch; row < c->batch + n_new; row++)
     if (row >= d.max_batch || !named[(size_t)row])
       return set_err(c, TGX_ERR_INVALID, "the new rows of a call must be %d..%d (the batch grows in order, max_batch %d)", c->batch, c->batch + n_new - 1, d.max_batch);
-  // the pass's sequences: the STEP rows first (array order), then the FEED / FEED_MORE rows (array order); src[j] = the array index of sequence j
-  std::vector<int> src;
-  for (int i = 0; i < n; i++) if (kinds[i] == TGX_ADV_STEP) src.push_back(i);
-  const int ns = (int)src.size();
-  for (int i = 0; i < n; i++) if (kinds[i] != TGX_ADV_STEP) src.push_back(i);
-  std::vector<int> first((size_t)n), sl((size_t)n), past((size_t)n), rws((size_t)n), nd((size_t)n, 0), adm;
-  for (int j = 0, m = 0; j < n; j++) {
-    const int i = src[(size_t)j], row = rows[i];
-    rws[(size_t)j] = row; first[(size_t)j] = m;
-    sl[(size_t)j] = lens[i] + (j < ns ? 1 : 0);
-    if (j < ns) nd[(size_t)j] = lens[i];
-    past[(size_t)j] = (j < ns || holds[(size_t)i]) ? (int)c->row_host[(size_t)row].past : 0;
-    if (j >= ns && !holds[(size_t)i]) adm.push_back(row);
-    m += sl[(size_t)j];
-  }
-  const PrefillRoute rt = prefill_route(c, (int)M, (int)M);
-  const bool joint = rt == ROUTE_SKINNY || rt == ROUTE_TILED;
-  if (c->kv_paged) {
-    bool mfma_row = joint;      // piecewise: does some piece's own pass take a matrix-core route?
-    for (int j = 0; j < n && !mfma_row; j++) { const PrefillRoute r1 = prefill_route(c, sl[(size_t)j], sl[(size_t)j]); mfma_row = r1 == ROUTE_SKINNY || r1 == ROUTE_TILED; }
-    if (mfma_row && c->kv.tbl_stride() > 1024)      // as tgx_extend_row
-      return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
-    // all or nothing: the blocks of all named rows together against the free list plus what the admissions' target rows give back
-    long long need = 0;
-    for (int j = 0; j < n; j++) {
-      const bool admission = j >= ns && !holds[(size_t)src[(size_t)j]];
-      need += c->kv.blocks_for((long long)past[(size_t)j] + sl[(size_t)j]) - (admission ? 0 : c->kv.row_blocks(rws[(size_t)j]));
-    }
-    const long long have = c->kv.available_for(adm.data(), (int)adm.size());
-    if (need > have)
-      return set_err(c, TGX_ERR_CONTEXT, "KV budget exhausted: the call needs %lld more blocks of %d tokens, %lld free or held by its admissions' rows of %d (option kv.budget_tokens = %d)", need,
-                     tgx::KV_BLOCK, have, c->kv.n_blocks() - 1, c->kv_budget_tokens);
-  }
+  ContPass cp = cont_pass(c, n, rows, kinds, ids, lens);
+  if (int rc = check_paged_room(c, cp, fn, ROOM_CALL_ADM)) return rc;
   HIP_OK(c, hipSetDevice(c->device));
   for (int i = 0; i < n; i++) { out_n[i] = 0; out_finish[i] = 0; }
-  if (!joint) {      // ---- piecewise: the equivalent calls behind the joint checks; the admissions' rows give their blocks back first, so that every piece's own count fits
-    if (c->kv_paged) for (int row : adm) kv_release_row(c, row);
-    if (ns) {
-      std::vector<int32_t> r32((size_t)ns), nd32((size_t)ns), on((size_t)ns), of((size_t)ns);
-      std::vector<int64_t> dr, oi((size_t)ns * (TGX_MAX_DRAFT + 1));
-      for (int j = 0; j < ns; j++) {
-        r32[(size_t)j] = rws[(size_t)j]; nd32[(size_t)j] = nd[(size_t)j];
-        for (int k = 0; k < nd[(size_t)j]; k++) dr.push_back(ids[off[(size_t)src[(size_t)j]] + k]);
-      }
-      dr.push_back(0);      // (never read: a non-null pointer for a call without drafts)
-      if (int rc = tgx_verify_rows(c, ns, r32.data(), dr.data(), nd32.data(), oi.data(), on.data(), of.data())) return rc;
-      for (int j = 0; j < ns; j++) {
-        const int i = src[(size_t)j];
-        for (int k = 0; k < on[(size_t)j]; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = oi[(size_t)j * (TGX_MAX_DRAFT + 1) + k];
-        out_n[i] = on[(size_t)j]; out_finish[i] = of[(size_t)j];
-      }
-    }
-    std::vector<int> feeds(src.begin() + ns, src.end());      // the continuations in array order, then the admissions in row order (the batch grows in order)
-    std::stable_sort(feeds.begin(), feeds.end(), [&](int x, int y) { return holds[(size_t)x] != holds[(size_t)y] ? holds[(size_t)x] > holds[(size_t)y] : (!holds[(size_t)x] && rows[x] < rows[y]); });
-    for (int i : feeds) {
-      const int32_t r1 = rows[i], s1 = lens[i];
-      if (int rc = holds[(size_t)i] ? extend_row(c, r1, ids + off[(size_t)i], s1, nullptr) : admit_rows(c, 1, &r1, ids + off[(size_t)i], &s1, /*may_join=*/false)) return rc;
-      if (kinds[i] == TGX_ADV_FEED_MORE) c->row_host[(size_t)r1].nologits = true;      // its logits slot is not the caller's to read: more of the prompt follows
-    }
-    refresh_longest(c);
-    c->advance_last_form = 2;
-    return TGX_OK;
+  const PrefillRoute rt = prefill_route(c, cp.M, cp.M);
+  if (rt == ROUTE_SKINNY || rt == ROUTE_TILED) return joint_pass(c, cp, ATTN_MIXED, rt, fn, out_ids, out_n, out_finish);
+  // ---- piecewise: the equivalent calls behind the joint checks; the admissions' rows give their blocks back first, so that every piece's own count fits
+  if (c->kv_paged) for (int row : cp.adm) kv_release_row(c, row);
+  if (cp.ns) if (int rc = verify_steps(c, cp, "tgx_verify_rows", out_ids, out_n, out_finish)) return rc;      // (the call it stands for, named in a device failure's message)
+  std::vector<int> feeds;      // the continuations in array order, then the admissions in row order (the batch grows in order)
+  for (int j = cp.ns; j < cp.n; j++) feeds.push_back(j);
+  std::stable_sort(feeds.begin(), feeds.end(), [&](int x, int y) { return cp.holds[(size_t)x] != cp.holds[(size_t)y] ? cp.holds[(size_t)x] > cp.holds[(size_t)y] : (!cp.holds[(size_t)x] && cp.rows[(size_t)x] < cp.rows[(size_t)y]); });
+  for (int j : feeds) {
+    const int32_t r1 = cp.rows[(size_t)j], s1 = cp.lens[(size_t)j];
+    if (int rc = cp.holds[(size_t)j] ? extend_row(c, r1, cp.ids[(size_t)j], s1, nullptr) : admit_rows(c, 1, &r1, cp.ids[(size_t)j], &s1, /*may_join=*/false)) return rc;
+    if (cp.kind[(size_t)j] == TGX_ADV_FEED_MORE) c->row_host[(size_t)r1].nologits = true;      // its logits slot is not the caller's to read: more of the prompt follows
   }
-  // ---- the joint pass
-  std::vector<tgx_sampler_cfg> cfg((size_t)std::max(ns, 1));
-  std::vector<char> smp((size_t)std::max(ns, 1), 0);
-  bool any_sampled = false;
-  for (int j = 0; j < ns; j++) { cfg[(size_t)j] = row_cfg(c, rws[(size_t)j]); smp[(size_t)j] = !is_greedy(&cfg[(size_t)j]); any_sampled = any_sampled || smp[(size_t)j]; }
-  if (ns) if (int rc = ensure_verify_rows_ws(c)) return rc;
-  if (any_sampled) if (int rc = vs_alloc(c)) return rc;
-  // the STEP positions' lm_head: on the tiled route the GEMV form would stream the lm_head weights once per FOUR positions (32 step rows: eight passes, measured
-  // +0.8 ms on Llama-3.2-1B, profiles/advance_rows.txt); where the skinny route would take Ms rows by themselves, its one-pass form serves them from ws_x
-  PrefillRoute lm_rt = rt;
-  if (ns && rt == ROUTE_TILED && prefill_route(c, (int)Ms, (int)Ms) == ROUTE_SKINNY) {
-    if (int rc = ensure_skinny_ws(c, (int)Ms)) return rc;
-    lm_rt = ROUTE_SKINNY;
-  }
-  std::vector<int> head_rows;     // the FEED rows: their last position's logits
-  for (int j = ns; j < n; j++) if (kinds[src[(size_t)j]] == TGX_ADV_FEED) head_rows.push_back(rws[(size_t)j]);
-  if (!head_rows.empty()) if (int rc = ensure_rg_lm_ws(c)) return rc;
-  RaggedPass p;
-  p.n = n; p.M = (int)M; p.rows = rws.data(); p.lens = sl.data(); p.first = first.data(); p.past = past.data();
-  for (int j = 0; j < n; j++) p.longest = std::max(p.longest, sl[(size_t)j]);
-  const int target = advance_attn_target(c, p);
-  // the call's buffer: the pass's tables, then its ids (ONE upload; input 0 of every STEP sequence is written on the device from the row's token word)
-  const size_t o_ids = advance_tables(c, p, nullptr, nullptr, target), bytes = o_ids + (size_t)M * 8;
-  if (int rc = ensure_mix_ws(c, p)) return rc;
-  if (int rc = dev_grow(c, &c->rg_buf, &c->rg_bytes, bytes)) return rc;
-  std::vector<unsigned char> host(bytes, 0);      // (lives until finish_pass has synchronised)
-  advance_tables(c, p, host.data(), c->rg_buf, target);
-  long long* const h_ids = reinterpret_cast<long long*>(host.data() + o_ids);
-  for (int j = 0; j < n; j++)
-    for (int k = 0; k < lens[src[(size_t)j]]; k++) h_ids[first[(size_t)j] + (j < ns ? 1 : 0) + k] = ids[off[(size_t)src[(size_t)j]] + k];
-  long long* const d_ids = reinterpret_cast<long long*>(c->rg_buf + o_ids);
-  p.ids = d_ids;
-  c->vf_pass_rows = 0;                             // the workspace changes hands
-  if (c->kv_paged) for (int row : adm) kv_release_row(c, row);
-  for (int j = 0; j < n; j++) (void)kv_ensure_blocks(c, rws[(size_t)j], (long long)past[(size_t)j] + sl[(size_t)j]);      // cannot fail: counted above
-  for (int row : adm)      // retired rows that rode along since their reset: position word back to 0
-    if (c->row_host[(size_t)row].past != 0) { HIP_OK(c, hipMemsetAsync(c->rows[(size_t)row].pos, 0, 4, c->stream)); c->row_host[(size_t)row].past = 0; }
-  HIP_OK(c, hipMemcpyAsync(c->rg_buf, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
-  if (ns) launch_verify_first_ids(c, d_ids, ns, rws.data(), first.data());
-  if (int rc = launch_route(c, rt, (int)M, 0, 0, 0, /*past=*/0, &p)) return rc;
-  std::vector<tgx::VerifyRecord> rec((size_t)std::max(ns, 1));
-  if (ns) {
-    launch_lm_head_all(c, lm_rt, (int)Ms, nullptr, /*joint=*/true);
-    for (int j = 0; j < ns; j++)
-      if (smp[(size_t)j]) launch_sample_positions(c, rws[(size_t)j], sl[(size_t)j], cfg[(size_t)j], first[(size_t)j]);
-    launch_verify_accept_rows(c, d_ids, ns, rws.data(), first.data(), nd.data(), smp.data());
-    for (int j = 0; j < ns; j++)
-      if (row_records(c, rws[(size_t)j])) launch_logprobs_verify(c, rws[(size_t)j], sl[(size_t)j], first[(size_t)j], j);
-    HIP_OK(c, hipMemcpyAsync(rec.data(), c->vj_rec, (size_t)ns * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
-  }
-  launch_lm_head_rows(c, head_rows);
-  for (int j = ns; j < n; j++) launch_add_pos(c, c->rows[(size_t)rws[(size_t)j]].pos, sl[(size_t)j]);
-  if (int rc = finish_pass(c)) return rc;
-  for (int j = 0; j < ns; j++)
-    if (rec[(size_t)j].n < 1 || rec[(size_t)j].n > sl[(size_t)j]) { c->poisoned = true; return set_err(c, TGX_ERR_DEVICE, "%s: the accept launch left no record for row %d", fn, rws[(size_t)j]); }
-  c->vf_pass_rows = (int)Ms; c->vf_pass_joint = true;
-  c->advance_last_form = 1; c->advance_last_tiles = target;
-  // ---- the host follows the device: the STEP rows as tgx_verify_rows does, the FEED rows as an admission / tgx_extend_row does
-  for (int j = 0; j < ns; j++) {
-    const int row = rws[(size_t)j], i = src[(size_t)j];
-    const tgx::VerifyRecord& rc1 = rec[(size_t)j];
-    RowHost& r = c->row_host[(size_t)row];
-    r.past = past[(size_t)j] + rc1.n;
-    r.fin = (char)rc1.finish;
-    if (row_records(c, row)) r.lp_count += rc1.n;
-    kv_trim_row(c, row, r.past);
-    if (!smp[(size_t)j]) note_sampled(c, row, 1, cfg[(size_t)j]);
-    else r.probs_ok = false;
-    for (int k = 0; k < rc1.n; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = rc1.ids[k];
-    out_n[i] = rc1.n; out_finish[i] = rc1.finish;
-    if (row == 0) c->last_sampled0 = rc1.ids[rc1.n - 1];
-  }
-  for (int j = ns; j < n; j++) {
-    const int row = rws[(size_t)j], i = src[(size_t)j];
-    c->batch = std::max(c->batch, row + 1);
-    row_admitted(c, row, past[(size_t)j] + sl[(size_t)j], /*keep_lp_count=*/(bool)holds[(size_t)i]);
-    if (kinds[i] == TGX_ADV_FEED_MORE) c->row_host[(size_t)row].nologits = true;
-  }
-  c->have_probs = false;
-  for (int b = 0; b < c->batch; b++) c->have_probs = c->have_probs || c->row_host[(size_t)b].probs_ok;
   refresh_longest(c);
-  c->have_logits = true;
-  HIP_OK(c, hipGetLastError());
+  c->advance_last_form = 2;
   return TGX_OK;
 }
 
