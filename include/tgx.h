@@ -33,6 +33,7 @@ extern "C" {
 /* (still 3: additive) tgx_splice_row — ranges cut out of the middle of a live row's cache, the keys behind them re-rotated: context shift without a second prefill. */
 /* (still 3: additive) tgx_verify_row — greedy speculative decoding: a row's draft tokens verified in ONE pass, the row left as after the accepted decode steps. */
 /* (still 3: additive) tgx_verify_row_sampled — the same under the row's own sampler: exact by the draw identity; tgx_read_pass_logits — the pass's logits (diagnostic). */
+/* (still 3: additive) tgx_verify_tree — a token TREE of guesses verified in one pass: each position attends its own branch, the accepted branch is compacted in place. */
 /* (still 3: additive) tgx_verify_rows — the drafts of several rows verified in ONE joint pass and ONE accept launch; n_draft 0 rows step along. */
 /* (still 3: additive) tgx_set_row_logprobs / tgx_read_row_logprobs — per-token log-probabilities (chosen token and top-N) recorded on the device into a per-row ring. */
 /* (still 3: additive) tgx_score_row — a prompt pass that also returns the log-probability of every token the caller SUPPLIED (echo, perplexity, ranking). */
@@ -536,8 +537,47 @@ TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_dr
  *                     less than the +0.037 one row's chain adds to a decode step (0.788 against 0.750). */
 TGX_API int tgx_verify_row_sampled(tgx_ctx* ctx, int row, const int64_t* draft, int n_draft, int64_t* out_ids /* [n_draft + 1] */, int32_t* out_n, int32_t* out_finish);
 
+/* ---- tree speculative decoding: verifying a token TREE in one pass (additive to ABI 3) -------------------------------------------------------------------
+ * A chain of guesses stops paying at its first wrong token.  A token tree spends the same <= 16 positions of one pass on alternatives: several candidates for the
+ * next token, each with its own continuation.  The draw identity of tgx_verify_row_sampled makes it exact for free: the row's draw at a given depth is ONE token,
+ * so at most one child of a node matches it, and the walk follows that child.
+ *
+ *   The tree          tokens[i] / parent[i], i < n_nodes, in topological order: parent[i] = -1 (a child of the row's current token t0) or an index < i.  Two
+ *                     children of one parent never carry the same token.
+ *   The pass          t0 is pass position 0 at depth 0; node i is pass position i + 1 at depth depth(parent) + 1.  ONE pass runs all M = n_nodes + 1 positions:
+ *                     position p is written to cache slot past + p, rotated (RoPE) for sequence position past + depth(p), and attends to the history [0, past)
+ *                     and to exactly its ancestors and itself among the new slots.
+ *   The walk          on the device, from cur = position 0: the row's settings choose g from cur's logits — greedy: highest value, lowest index on a tie;
+ *                     sampled: the draw with the key (row seed, past + depth(cur) + 1, row), the key tgx_decode_rows would use for that token.  g is produced
+ *                     and counted against the row's stop set / max_new.  If the row has not finished and a child of cur carries g, cur becomes that child;
+ *                     otherwise the walk ends.  out_n <= max depth + 1.
+ *   Afterwards        the row stands as after out_n steps of tgx_decode_rows, up to the order of the fp32 sums: length past + out_n, the current token, the
+ *                     logits slot and argmax partials, the next embedding, the cache rows [0, past + out_n).  The accepted inputs' K / V rows are moved from
+ *                     slot past + path[j] to slot past + j bit for bit (K was rotated for its depth, which is j: no second rotation).  Rows beyond are DEAD.
+ *   A chain           parent[i] == i - 1 for every i: the call IS tgx_verify_row_sampled — the same launches, the same bits, on every route, with everything
+ *                     that call supports (log-probability records included).
+ *   Everything else   as for tgx_verify_row_sampled, word for word: ALL OR NOTHING, the paged-KV block accounting for past + M up front and the trim afterwards,
+ *                     shared blocks never written, other rows bit for bit, steps and tickets, tgx_read_probs.  tgx_read_pass_logits returns the M positions'
+ *                     logits in pass order.
+ *   Refused           in this order.  Null pointers, row outside [0, max_batch), n_nodes outside [1, TGX_MAX_TREE_NODES], a token id out of range:
+ *                     TGX_ERR_INVALID.  Then the row's state, as tgx_verify_row_sampled checks it and in its order: a retired, empty or finished row, no
+ *                     logits, no current token: TGX_ERR_STATE; a logit processor or an automaton on: TGX_ERR_UNSUPPORTED; past + n_nodes + 1 > max_ctx:
+ *                     TGX_ERR_CONTEXT.  Then the tree's shape: parent[i] outside [-1, i), two children of one parent with the same token: TGX_ERR_INVALID.
+ *                     Then, for a tree that is NO chain, TGX_ERR_UNSUPPORTED when the row records log-probabilities, when the pass cannot take the skinny
+ *                     matrix-core route (fp32 storage, GPT-2, option prefill.mfma or prefill.skinny at 0, shapes the skinny kernels do not cover, a head_dim
+ *                     other than 64 / 128) or when a paged cache has more than 1024 blocks per row.  Last the paged cache's room: TGX_ERR_CONTEXT.
+ *                     Option prefill.min_rows is a speed threshold for chains and does not bind a tree: every M in [3, 16] runs the skinny route.
+ *   Not built         trees in tgx_verify_rows / tgx_advance_rows; log-probability records, logit processors and automata on a tree that is no chain.
+ *   Cost              tgx_verify_row_sampled's for the same number of positions, plus ONE compaction launch of layers x kv_heads x 2 workgroups
+ *                     (profiles/verify_tree.txt; Llama-3.2-1B bf16, context 2048, greedy, ms per call: 1.263 / 1.281 / 1.354 at 4 / 8 / 16 positions against
+ *                     1.296 / 1.231 / 1.309 for the parent build's chain pass, whose repeated medians spread by 0.011). */
+#define TGX_MAX_TREE_NODES 15   /* = TGX_MAX_DRAFT: root + nodes <= 16 positions of one pass */
+TGX_API int tgx_verify_tree(tgx_ctx* ctx, int row, const int64_t* tokens /* [n_nodes] */,
+                            const int32_t* parent /* [n_nodes]: -1 = child of the row's current token, else an index < i */, int n_nodes,
+                            int64_t* out_ids /* [n_nodes + 1] */, int32_t* out_n, int32_t* out_finish);
+
 /* Test / diagnostic use, like tgx_read_kv: the fp32 logits [M][vocab] of the M = n_draft + 1 positions of the last tgx_verify_row / tgx_verify_row_sampled pass,
- * *out_rows = M.  TGX_ERR_STATE when the workspace holds no such pass: no call yet, tgx_score_row's group form or another verify call that failed has used it
+ * or of the M = n_nodes + 1 positions of the last tgx_verify_tree pass in pass order (the row's current token, then the nodes by index); *out_rows = M.  TGX_ERR_STATE when the workspace holds no such pass: no call yet, tgx_score_row's group form or another verify call that failed has used it
  * since, or after tgx_reset_cache.  cap_rows < M: TGX_ERR_INVALID, nothing is written.  Synchronises the stream. */
 TGX_API int tgx_read_pass_logits(tgx_ctx* ctx, float* out /* [cap_rows][vocab] */, int cap_rows, int32_t* out_rows);
 

@@ -28,7 +28,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h")]
+            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "verify_tree_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -111,6 +111,16 @@ def build_beam_plan_check(force: bool = False, verbose: bool = False):
     if _stale(os.path.join(TEST_BUILD, "beam_plan_check"), [os.path.join(CSRC, "kv_pool.h")]):
         force = True
     return _build_cpu_check("beam_plan_check", os.path.join(CSRC, "beam_plan.h"), force, verbose)
+
+
+def build_verify_tree_plan_check(force: bool = False, verbose: bool = False):
+    """tests/verify_tree_plan_check.cpp, the CPU audit of csrc/verify_tree_plan.h."""
+    return _build_cpu_check("verify_tree_plan_check", os.path.join(CSRC, "verify_tree_plan.h"), force, verbose)
+
+
+def build_spec_tree_check(force: bool = False, verbose: bool = False):
+    """tests/spec_tree_check.cpp, the CPU audit of ngram_tree in host/spec_draft.h."""
+    return _build_cpu_check("spec_tree_check", os.path.join(HOST, "spec_draft.h"), force, verbose)
 
 
 def build_beam_check(force: bool = False, verbose: bool = False):

@@ -13,6 +13,7 @@
 #include "row_snapshot.h"
 #include "splice_plan.h"
 #include "beam_plan.h"
+#include "verify_tree_plan.h"
 #include "automaton.h"
 
 static std::string g_create_err;
@@ -1983,12 +1984,14 @@ int tgx_score_row(tgx_ctx* c, int row, const int64_t* ids, int seq, int top_n, f
 // position with its own sampler; ONE accept launch (kernels/verify.h) takes the draft's matching prefix and leaves the row as that many decode steps would.
 // One STEP row's checks, the same for the one-row calls (min_draft 1) and for every STEP row of tgx_verify_rows / tgx_advance_rows (min_draft 0), in this order;
 // sampled_entry false (tgx_verify_row): a row that does not sample greedily is refused.  Nothing changes
-static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int min_draft, bool sampled_entry, const char* fn) {
+// (count_name / id_name: what the call names the two arguments — tgx_verify_tree's are n_nodes and tokens)
+static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int min_draft, bool sampled_entry, const char* fn, const char* count_name = "n_draft",
+                            const char* id_name = "draft token id") {
   const tgx_model_desc& d = c->d;
   if (row < 0 || row >= d.max_batch) return set_err(c, TGX_ERR_INVALID, "row %d out of range [0,%d)", row, d.max_batch);
-  if (n_draft < min_draft || n_draft > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "n_draft %d out of range [%d,%d]", n_draft, min_draft, TGX_MAX_DRAFT);
+  if (n_draft < min_draft || n_draft > TGX_MAX_DRAFT) return set_err(c, TGX_ERR_INVALID, "%s %d out of range [%d,%d]", count_name, n_draft, min_draft, TGX_MAX_DRAFT);
   for (int i = 0; i < n_draft; i++)
-    if (draft[i] < 0 || draft[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "draft token id out of range");
+    if (draft[i] < 0 || draft[i] >= d.vocab) return set_err(c, TGX_ERR_INVALID, "%s out of range", id_name);
   const RowHost& rh = c->row_host[(size_t)row];
   if (!row_holds(c, row)) return set_err(c, TGX_ERR_STATE, "row %d holds no sequence to verify a draft on", row);
   if (rh.fin) return set_err(c, TGX_ERR_STATE, "row %d finished: tgx_extend_row / tgx_reset_row it first", row);
@@ -2048,6 +2051,84 @@ int tgx_verify_row(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64
 }
 int tgx_verify_row_sampled(tgx_ctx* c, int row, const int64_t* draft, int n_draft, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
   return verify_row_impl(c, row, draft, n_draft, out_ids, out_n, out_finish, /*sampled_entry=*/true);
+}
+
+// ---- tgx_verify_tree (include/tgx.h): one more one-sequence member of the family — a STEP of one row whose n_nodes guesses form a token tree (csrc/verify_tree_plan.h)
+// instead of a chain.  ONE pass on the skinny route runs the M = n_nodes + 1 positions: position p into cache slot past + p, rotated for past + depth(p), attending
+// the history and its own branch (TreePass); the all-position lm_head and a sampled row's chain as for a chain (the draws keyed by depth); the accept launch walks
+// the tree on the device and leaves the path; the compaction launch behind it moves the accepted K / V rows into place.  A chain-shaped tree IS
+// tgx_verify_row_sampled: it takes that call's launches.
+// The skinny route whatever prefill.min_rows says (a speed threshold for chains): prefill_route's conditions without the length test, for M <= 16 rows
+static bool tree_route_ok(const tgx_ctx* c, int M) {
+  return c->prefill_mfma && c->dt != tgx::DT_F32 && prefill_shapes_ok(c->d) && !c->gpt2 && c->prefill_skinny && c->d.vocab >= 128 && c->prefill_skinny_rows >= M &&
+         (c->d.head_dim == 64 || c->d.head_dim == 128);
+}
+int tgx_verify_tree(tgx_ctx* c, int row, const int64_t* tokens, const int32_t* parent, int n_nodes, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
+  const char* const fn = "tgx_verify_tree";
+  if (!c || !tokens || !parent || !out_ids || !out_n || !out_finish) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
+  if (!c->finalized) return set_err(c, TGX_ERR_STATE, "verify before finalize");
+  if (c->poisoned) return set_err(c, TGX_ERR_STATE, "an earlier pass failed half-way: call tgx_reset_cache first");
+  static_assert(TGX_MAX_TREE_NODES == TGX_MAX_DRAFT && TGX_MAX_TREE_NODES == verify_tree_plan::MAX_NODES && verify_tree_plan::MAX_POS == tgx::VERIFY_MAX_POS, "root + nodes <= VERIFY_MAX_POS");
+  // ---- every check before anything changes.  The argument checks and the row's state, in verify_row_check's order and words ...
+  if (int rc = verify_row_check(c, row, tokens, n_nodes, /*min_draft=*/1, /*sampled_entry=*/true, fn, "n_nodes", "token id")) return rc;
+  // ... then the tree's shape ...
+  verify_tree_plan::Plan tp;
+  switch (verify_tree_plan::plan(tokens, parent, n_nodes, tp)) {
+    case verify_tree_plan::OK: break;
+    case verify_tree_plan::BAD_PARENT: return set_err(c, TGX_ERR_INVALID, "parent[%d] = %d outside [-1,%d): a node's parent stands before it", tp.bad, (int)parent[tp.bad], tp.bad);
+    case verify_tree_plan::DUP_SIBLING: return set_err(c, TGX_ERR_INVALID, "node %d carries the token of an earlier child of the same parent", tp.bad);
+    case verify_tree_plan::BAD_COUNT: return set_err(c, TGX_ERR_INVALID, "n_nodes %d out of range [1,%d]", n_nodes, TGX_MAX_TREE_NODES);      // (the planner's own check: refused above already)
+  }
+  ContPass cp;
+  cp.add(c, row, 0, TGX_ADV_STEP, tokens, n_nodes);
+  if (tp.chain) {      // tgx_verify_row_sampled's pass, launches and bits
+    if (int rc = check_paged_room(c, cp, fn, ROOM_ROW)) return rc;
+    return verify_row_run(c, cp, 0, fn, out_ids, out_n, out_finish);
+  }
+  // ... what a tree that is no chain cannot have, the route and the room
+  const int M = tp.M, past = cp.past[0];
+  if (row_records(c, row)) return set_err(c, TGX_ERR_UNSUPPORTED, "%s: row %d records log-probabilities (not built for a tree that is no chain)", fn, row);
+  if (!tree_route_ok(c, M))
+    return set_err(c, TGX_ERR_UNSUPPORTED, "%s: a tree that is no chain needs the skinny matrix-core pass (16-bit storage, no GPT-2, prefill.mfma and prefill.skinny on, head_dim 64 or 128)", fn);
+  if (c->kv_paged && c->kv.tbl_stride() > 1024)
+    return set_err(c, TGX_ERR_UNSUPPORTED, "%s on a paged cache of %d blocks per row (at most 1024: max_ctx <= %d)", fn, c->kv.tbl_stride(), 1024 * tgx::KV_BLOCK);
+  if (int rc = check_paged_room(c, cp, fn, ROOM_ROW)) return rc;
+  // ---- the pass
+  const bool sampled = cp.smp[0];
+  HIP_OK(c, hipSetDevice(c->device));
+  if (int rc = ensure_verify_ws(c)) return rc;
+  if (!c->vt_tab) if (int rc = dev_alloc(c, &c->vt_tab, (size_t)tgx_ctx::VT_INTS)) return rc;
+  if (sampled) if (int rc = vs_alloc(c)) return rc;
+  if (int rc = ensure_extend_ws(c, M, past)) return rc;
+  if (int rc = ensure_skinny_ws(c, M)) return rc;
+  c->vf_pass_rows = 0;                             // the workspace changes hands
+  (void)kv_ensure_blocks(c, row, (long long)past + M);      // the whole pass up front; cannot fail: counted above
+  long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the nodes; input 0 is written on the device from the row's token word
+  int tab[tgx_ctx::VT_INTS] = {0};                 // (both live until finish_pass has synchronised)
+  for (int p = 0; p < M; p++) {
+    if (p) ids[p] = tokens[p - 1];
+    tab[tgx_ctx::VT_DEPTH + p] = tp.depth[p]; tab[tgx_ctx::VT_PAR + p] = tp.par[p];
+  }
+  static_assert(sizeof(tp.anc) == 2 * verify_tree_plan::MAX_POS && sizeof(tp.anc) <= 4 * (tgx_ctx::VT_INTS - tgx_ctx::VT_ANC), "the masks' slot");
+  std::memcpy(tab + tgx_ctx::VT_ANC, tp.anc, sizeof(tp.anc));      // 16-bit words (positions >= M: zero)
+  HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_OK(c, hipMemcpyAsync(c->vt_tab, tab, sizeof(tab), hipMemcpyHostToDevice, c->stream));
+  launch_verify_first_id(c, row);
+  TreePass tree{c->vt_tab + tgx_ctx::VT_DEPTH, reinterpret_cast<const unsigned short*>(c->vt_tab + tgx_ctx::VT_ANC)};
+  launch_prefill_skinny(c, row, 1, M, past, nullptr, &tree);
+  launch_lm_head_all(c, ROUTE_SKINNY, M);
+  if (sampled) launch_sample_positions(c, row, M, cp.cfg[0], -1, tree.depth);      // every position's draw, with the key of the token its DEPTH produces
+  launch_verify_accept_tree(c, row, M, sampled ? c->vs_draws : nullptr);
+  launch_kv_tree_compact(c, row, M, past);
+  HIP_OK(c, hipMemcpyAsync(&cp.rec[0], c->vf_rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  if (int rc = finish_pass(c)) return rc;
+  if (int rc = follow_step_rows(c, cp, 0, 1, fn, out_ids, out_n, out_finish)) return rc;
+  c->vf_pass_rows = M; c->vf_pass_joint = false;
+  refresh_have_probs(c);
+  refresh_longest(c);
+  c->have_logits = true;
+  HIP_OK(c, hipGetLastError());
+  return TGX_OK;
 }
 
 // ---- the joint pass of tgx_verify_rows and tgx_advance_rows: the pass's sequences in ONE ragged causal pass — tgx_forward_rows' with each sequence's real length as

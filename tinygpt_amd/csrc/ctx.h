@@ -352,6 +352,10 @@ struct tgx_ctx {
   // lm_head stage them here, four to a pass over the weights), logits and argmax partials, and the record the accept launch leaves for the host.  Sized at first use
   enum { VERIFY_ROWS = TGX_MAX_DRAFT + 1 };
   float *vf_x = nullptr, *vf_logits = nullptr, *vf_part_val = nullptr; int *vf_part_idx = nullptr, *vf_rec = nullptr;
+  // tgx_verify_tree: the device tables of the pass's token tree, VT_* ints each slot of 16 (depth, parent position, the accepted path; the ancestor masks as 16-bit
+  // words in the fourth).  Allocated by the first non-chain tree call
+  enum { VT_DEPTH = 0, VT_PAR = 16, VT_PATH = 32, VT_ANC = 48, VT_INTS = 64 };
+  int* vt_tab = nullptr;
   int vf_pass_rows = 0;      // the positions of the verify pass whose logits vf_logits holds (tgx_read_pass_logits); 0: none, or another call has used the workspace since
   // ... and tgx_verify_row_sampled on a sampled row: the staged sampler's scratch and compacted lists for the VERIFY_ROWS positions (the pass's, not the row's) and
   // their draws.  Allocated by the first such call (vs_alloc): a context that never makes one holds none of it
@@ -475,6 +479,8 @@ int dev_grow(tgx_ctx* c, T** p, size_t* bytes, size_t need) {
 }
 
 namespace tgx { struct AttnArgs; struct FinalizeArgs; struct AttnPrefillArgs; struct RopeKvArgs; }
+// the device tables of a token tree's pass (tgx_verify_tree; csrc/verify_tree_plan.h): per pass position its depth and its ancestor-or-self mask
+struct TreePass { const int* depth; const unsigned short* anc; };
 
 // ---- abi.hip
 void drop_step_graphs(tgx_ctx* c);
@@ -503,6 +509,10 @@ void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws = nullptr
 // tgx_verify_rows, the joint pass: sequence i = row rows[i], M_i = n_draft[i] + 1 positions at slice first[i] of the vj_* workspace and of the pass's ids
 void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows, const int* first);          // ids[first[i]] <- row rows[i]'s current token, one launch
 void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled);   // one workgroup per row -> vj_rec[i]
+// tgx_verify_tree: the walk over a token tree (draws as above; vt_tab holds the tree's tables) -> vf_rec and the accepted path; then the accepted branch's K / V rows
+// of every layer from slot past + path[j] to slot past + j (kernels/kv_tree.h), stream-ordered behind the walk: path and count are read on the device
+void launch_verify_accept_tree(tgx_ctx* c, int row, int M, const int* draws);
+void launch_kv_tree_compact(tgx_ctx* c, int row, int M, int past);
 size_t verify_args_bytes();                                // one entry of the accept launch's table (vj_args)
 // ---- attn.hip (kernels/attn_decode.h, attn_decode_mfma.h)
 bool attn_batch_on_mfma(const tgx_ctx* c, int R);
@@ -516,7 +526,7 @@ int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);
 int vs_alloc(tgx_ctx* c);                                                    // tgx_verify_row_sampled: the positions' sampler workspace, at first use
 int vs_rezero(tgx_ctx* c);                                                   // ... its scratch back to the zero state the chain expects (tgx_reset_cache; stream-ordered; a no-op without the workspace)
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first = -1);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes); joint_first >= 0: over the row's slice of the vj_* workspace -> its slice of vj_draws
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first = -1, const int* depth = nullptr);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes); joint_first >= 0: over the row's slice of the vj_* workspace -> its slice of vj_draws
 int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
 bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)
@@ -562,8 +572,8 @@ int extend_attn_splits(const tgx_ctx* c, int S, int past);   // key splits of a 
 int ensure_extend_ws(tgx_ctx* c, int S, int past);           // ... and their partials' workspace, before the pass is issued
 // tgx_verify_rows: the key splits of a ragged continuation pass (p.n sequences, p.past set) by option extend.attn_splits -> p.ext_ns, and the partials' workspace
 int ensure_extend_rg_ws(tgx_ctx* c, RaggedPass& p);
-void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean);
-void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S);
+void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean, const unsigned short* anc = nullptr);   // anc: a token tree's device masks (TreePass)
+void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S, const int* depth = nullptr);                           // depth: a token tree's device depths (TreePass)
 void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, int nsplit, bool third = false);
 void launch_silu_slab_reduce(tgx_ctx* c, int M, int I, int nsplit);
 void launch_embed_rows(tgx_ctx* c, const long long* ids, float* X, int M, int S);
@@ -574,6 +584,6 @@ void launch_prefill_f32(tgx_ctx* c, int row0, int NB, int S, int past);   // pas
 bool decode_mfma_ok(const tgx_ctx* c);
 int ensure_skinny_ws(tgx_ctx* c, int rows);
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg);
-void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB)
+void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr, const TreePass* tree = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB); tree (NB == 1, no rg): the S positions are a token tree's
 void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x = nullptr);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
 int skinny_set_attrs(tgx_ctx* c);

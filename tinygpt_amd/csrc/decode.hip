@@ -8,6 +8,7 @@
 #include "kernels/gemv_packed.h"
 #include "kernels/oproj_sliced.h"
 #include "kernels/verify.h"
+#include "kernels/kv_tree.h"
 
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc) { return tgx::gemv_grid_plan(units, 4 / ks, c->num_cus * bpc).grid; }
 
@@ -408,6 +409,36 @@ void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws) {
   a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
   a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vf_rec);
   TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_kernel<DT>, dim3(1), dim3(256), 0, c->stream, a))
+}
+// ---- tgx_verify_tree: the walk over the token tree whose tables vt_tab holds (parent positions in, the accepted path out) ...
+void launch_verify_accept_tree(tgx_ctx* c, int row, int M, const int* draws) {
+  if (!c->vt_tab || !c->vf_rec || M > tgx::VERIFY_MAX_POS) { c->launch_fault = "tree verification requested before its buffers exist"; return; }
+  RowState& r = c->rows[(size_t)row];
+  tgx::VerifyTreeArgs t{};
+  tgx::VerifyArgs& a = t.v;
+  a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
+  a.logits = c->vf_logits; a.draft = r.prompt + 1; a.draws = draws;
+  a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
+  a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
+  a.embed = c->embed; a.wpe = nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
+  a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vf_rec);
+  t.par = c->vt_tab + tgx_ctx::VT_PAR; t.path = c->vt_tab + tgx_ctx::VT_PATH;
+  TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_tree_kernel<DT>, dim3(1), dim3(256), 0, c->stream, t))
+}
+// ... and behind it the accepted branch's K / V rows into place (kernels/kv_tree.h): one workgroup per (layer, kv head, K | V)
+void launch_kv_tree_compact(tgx_ctx* c, int row, int M, int past) {
+  const tgx_model_desc& d = c->d;
+  if (!c->vt_tab || !c->vf_rec || M > tgx::VERIFY_MAX_POS || d.head_dim % 8 != 0 || (tgx::VERIFY_MAX_POS - 1) * (d.head_dim / 8) > 256 || past + M > d.max_ctx) {
+    c->launch_fault = "kv_tree_compact: the pass does not fit the launch (at most 16 positions, head_dim <= 128)"; return;
+  }
+  RowState& r = c->rows[(size_t)row];
+  tgx::KvTreeArgs a{};
+  a.k = reinterpret_cast<bf16_t*>(r.kcache); a.v = reinterpret_cast<bf16_t*>(r.vcache);
+  a.layer_stride = (long long)(c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK : (size_t)d.kv_heads * d.max_ctx) * d.head_dim;
+  a.tbl = c->kv_paged ? r.tbl : nullptr;
+  a.path = c->vt_tab + tgx_ctx::VT_PATH; a.rec = reinterpret_cast<const tgx::VerifyRecord*>(c->vf_rec);
+  a.kv_heads = d.kv_heads; a.hd = d.head_dim; a.max_ctx = d.max_ctx; a.past = past; a.M = M;
+  hipLaunchKernelGGL(tgx::kv_tree_compact_kernel, dim3(d.layers * d.kv_heads, 2), dim3(256), 0, c->stream, a);
 }
 // ---- tgx_verify_rows: both launches for the n rows of a joint pass (ids: the pass's ids on the device, row i's M_i = n_draft[i] + 1 inputs from first[i])
 void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows, const int* first) {

@@ -35,6 +35,19 @@ __global__ __launch_bounds__(256, HD == 64 ? 1 : 2) void attn_extend_kernel(cons
   attn_prefill_wg<DT, HD, LA, 1, PAGED, true>(e.a, h, 0, t0, t1, part);
 }
 
+// ... of a token tree (tgx_verify_tree): the same splits under the tree mask (prefill.h TREE); attn_extend_merge_kernel merges them as they are
+struct AttnExtendTreeArgs { AttnExtendArgs e; const unsigned short* anc; };
+template <int DT, int HD, bool PAGED>
+__global__ __launch_bounds__(256, HD == 64 ? 1 : 2) void attn_extend_tree_kernel(const AttnExtendTreeArgs t) {
+  constexpr int LA = HD == 64 ? 2 : 1;
+  const AttnExtendArgs& e = t.e;
+  const int h = blockIdx.x, s = blockIdx.y;
+  const int base = e.n_tiles / e.ns, rem = e.n_tiles - base * e.ns;
+  const int t0 = s * base + min(s, rem), t1 = t0 + base + (s < rem ? 1 : 0);
+  float* const part = e.part + ((size_t)s * e.a.heads + h) * (size_t)(attn_extend_part_vals<HD>() * 256);
+  attn_prefill_wg<DT, HD, LA, 1, PAGED, true, true>(e.a, h, 0, t0, t1, part, t.anc);
+}
+
 template <int DT, int HD>
 __global__ __launch_bounds__(256) void attn_extend_merge_kernel(const AttnExtendArgs e) {
   constexpr int NB = HD / 32, NV = attn_extend_part_vals<HD>();

@@ -183,8 +183,10 @@ struct RopeKvArgs {
   const int* blk_tbl;      // paged KV (common.h kv_paged_off): this sequence's block table, k_cache / v_cache = the layer's pools — or nullptr
 };
 // workspace row s (position pos of its sequence) into that sequence's cache k_cache / v_cache (blk_tbl: its block table, paged KV)
+// pos = the cache SLOT the row's K / V land in; ang = the sequence position q and k are ROTATED for (the RoPE table's row).  A causal pass gives both the same value;
+// a token tree (tgx_verify_tree) writes node p to slot past + p and rotates it for past + depth(p)
 template <int DT>
-__device__ __forceinline__ void rope_kv_split_row(const RopeKvArgs& a, const int s, const int pos, bf16_t* const k_cache, bf16_t* const v_cache, const int* const blk_tbl) {
+__device__ __forceinline__ void rope_kv_split_row(const RopeKvArgs& a, const int s, const int pos, const int ang, bf16_t* const k_cache, bf16_t* const v_cache, const int* const blk_tbl) {
   // one workgroup per position; a thread owns FOUR adjacent RoPE pairs (p..p+3, p+half..p+half+3) of one head: 16-byte loads, 8-byte stores
   const int half = a.hd >> 1, q4 = half >> 2;
   const int qd = a.heads * a.hd, kvd = a.kv_heads * a.hd;
@@ -244,7 +246,7 @@ __device__ __forceinline__ void rope_kv_split_row(const RopeKvArgs& a, const int
       }
     }
     if (hh < a.heads + a.kv_heads) {
-      const f32x4 cs = *reinterpret_cast<const f32x4*>(a.rope_cos + (size_t)pos * half + p), sn = *reinterpret_cast<const f32x4*>(a.rope_sin + (size_t)pos * half + p);
+      const f32x4 cs = *reinterpret_cast<const f32x4*>(a.rope_cos + (size_t)ang * half + p), sn = *reinterpret_cast<const f32x4*>(a.rope_sin + (size_t)ang * half + p);
 #pragma unroll
       for (int t = 0; t < 4; t++) {
         float r0 = x0[t], r1 = x1[t];
@@ -273,7 +275,13 @@ __device__ __forceinline__ void rope_kv_split_row(const RopeKvArgs& a, const int
 }
 template <int DT>
 __global__ __launch_bounds__(256) void rope_kv_split_kernel(const RopeKvArgs a) {
-  rope_kv_split_row<DT>(a, blockIdx.x, a.past + (int)blockIdx.x, a.k_cache, a.v_cache, a.blk_tbl);
+  rope_kv_split_row<DT>(a, blockIdx.x, a.past + (int)blockIdx.x, a.past + (int)blockIdx.x, a.k_cache, a.v_cache, a.blk_tbl);
+}
+// ... of a token tree (tgx_verify_tree): pass position p into slot past + p, rotated for past + depth[p] (a device table of the pass's positions)
+struct RopeTreeArgs { RopeKvArgs a; const int* depth; };
+template <int DT>
+__global__ __launch_bounds__(256) void rope_kv_split_tree_kernel(const RopeTreeArgs r) {
+  rope_kv_split_row<DT>(r.a, blockIdx.x, r.a.past + (int)blockIdx.x, r.a.past + r.depth[blockIdx.x], r.a.k_cache, r.a.v_cache, r.a.blk_tbl);
 }
 
 // ---- ragged passes (tgx_forward_rows, tgx_verify_rows): sequences of different lengths stacked in one workspace, each into its own row's cache -------------
@@ -294,7 +302,7 @@ template <int DT>
 __global__ __launch_bounds__(256) void rope_kv_split_rg_kernel(const RopeRgArgs r) {
   const int s = blockIdx.x;
   const RgSeq q = r.seq[r.tok_seq[s]];
-  rope_kv_split_row<DT>(r.a, s, q.past + s - q.row0, q.k + r.layer_off, q.v + r.layer_off, q.tbl);
+  rope_kv_split_row<DT>(r.a, s, q.past + s - q.row0, q.past + s - q.row0, q.k + r.layer_off, q.v + r.layer_off, q.tbl);
 }
 
 // ---- C[M][N] (+)= (Ahi + Alo)[M][K] · B[N][K]ᵀ on v_mfma_f32_32x32x16_bf16 ------------------------------------------
@@ -604,9 +612,15 @@ constexpr int attn_extend_part_vals() { return HD / 32 * 16 + 2; }      // a SPL
 // one workgroup: query block qblk of head h (attn_prefill_kernel: from the grid; attn_prefill_rg_kernel: from its work item)
 // SPLIT (kernels/attn_extend.h): the workgroup walks the 64-key tiles [t0, t1) only and leaves its unnormalised (O, m, l) per query in `part` (the (split, head)
 // record, attn_extend_part_vals<HD>() values of 256 lanes each) instead of output rows.  Every difference is compile-time: the other instantiations are what they were.
-template <int DT, int HD, int LA, int KP, bool PAGED, bool SPLIT = false>
-__device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const int h, const int qblk, const int t0 = 0, const int t1 = 0, float* const part = nullptr) {
+// TREE (tgx_verify_tree): the S <= 16 queries are the positions of a token tree in topological order, key past + p' = pass position p'.  Query q attends the history
+// [0, past) and, among the new keys, its ancestors and itself: anc[q] bit p' (csrc/verify_tree_plan.h).  A parent stands before its child, so the tree mask is a subset
+// of the causal mask and is applied where that one is: in the tiles `diag` selects (every tile that holds a key beyond `past`; key `past` itself, the root, is bit 0 of
+// every mask).  Compile-time as well: with TREE off nothing below changes.
+template <int DT, int HD, int LA, int KP, bool PAGED, bool SPLIT = false, bool TREE = false>
+__device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const int h, const int qblk, const int t0 = 0, const int t1 = 0, float* const part = nullptr,
+                                                const unsigned short* const anc = nullptr) {
   static_assert(!SPLIT || KP == 1, "a key range per workgroup has no key split inside it");
+  static_assert(!TREE || KP == 1, "a token tree is one query block of at most 16 positions");
   constexpr int DIS = TGX_ATTN_DIS;
   constexpr int LQ = HD + 8;                  // 16-bit row stride of the K tile (144 / 272 B: conflict-free 16-byte fragment reads)
   constexpr int LV = HD + 32;                 // 16-bit row stride of the V tile ([key][d], 64 B more than a row: the four key rows of a transposing read fall on four bank quarters)
@@ -627,6 +641,8 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
   const int qi = q0 + ql;                              // this lane's query
   const bool qvalid = qi < a.S;
   const int qpos = a.past + qi;
+  unsigned int my_anc = 0;                             // TREE: this lane's query's ancestor-or-self mask over the pass's positions
+  if constexpr (TREE) my_anc = (qvalid && qi < 16) ? anc[qi] : 0u;
 
   bf16x8 qh[KS], qlo[KS];
 #pragma unroll
@@ -721,6 +737,14 @@ __device__ __forceinline__ void attn_prefill_wg(const AttnPrefillArgs& a, const 
 #pragma unroll
         for (int r = 0; r < 16; r++) {
           const int key = kb + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          if constexpr (TREE) {
+            // one select per score, as the causal form: a key of the history (rel < 0: the sign bit) or an ancestor-or-self (bit rel of this query's word).  rel & 15
+            // keeps the shift defined for every key of the tile — the history (negative) and the keys behind the pass (rel >= 16, refused by key <= qpos anyway)
+            const int rel = key - a.past;                             // negative: the history
+            const unsigned int seen = ((unsigned int)rel >> 31) | ((my_anc >> (rel & 15)) & 1u);
+            const bool vis = (int)qvalid & (int)(key <= qpos) & (int)seen;
+            sacc[sub][r] = vis ? sacc[sub][r] : -INFINITY;
+          } else
           if (!(qvalid && key <= qpos)) sacc[sub][r] = -INFINITY;     // isCausal (Attention.h:108) with the cache offset
         }
       }
@@ -876,6 +900,12 @@ __global__ __launch_bounds__(256 * KP, KP == 2 ? 2 : (LA == 1 ? (HD == 64 ? 3 : 
   const int qblk = a.heavy_first ? (int)gridDim.y - 1 - (int)blockIdx.y
                                  : ((a.qblk_mirror && h >= a.heads / 2) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x);
   attn_prefill_wg<DT, HD, LA, KP, PAGED>(a, h, qblk);
+}
+// ... of a token tree (tgx_verify_tree): the one query block of its M <= 16 positions, one workgroup per head, in the default form of the head dimension
+struct AttnTreeArgs { AttnPrefillArgs a; const unsigned short* anc; };      // anc: [S] device words, bit p' of anc[q] = query q attends new key past + p'
+template <int DT, int HD, bool PAGED>
+__global__ __launch_bounds__(256, HD == 64 ? 1 : 2) void attn_prefill_tree_kernel(const AttnTreeArgs t) {
+  attn_prefill_wg<DT, HD, (HD == 64 ? 2 : 1), 1, PAGED, false, true>(t.a, blockIdx.x, 0, 0, 0, nullptr, t.anc);
 }
 
 // ---- the prompt attention of a ragged pass (tgx_forward_rows): ONE launch for every prompt, one workgroup per work item (prompt, query block, head) of a device list

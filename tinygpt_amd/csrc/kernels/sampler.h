@@ -406,6 +406,8 @@ struct SampPickArgs {
   int* draws;                       // positions mode (POS instantiations; tgx_verify_row_sampled): blockIdx.y = position i of ONE row's verify pass, `s` the pass's
                                     // workspace and `fin` that row's own words (nothing is offset by i).  The launch draws with the row's seed for the token
                                     // index *fin.pos + 1 + i (common.h draw_key) into draws[i] and publishes nothing; nullptr otherwise
+  const int* depth;                 // positions mode of a token tree (tgx_verify_tree): position i stands at depth[i] of its branch and draws for the token index
+                                    // *fin.pos + 1 + depth[i]; nullptr: a chain, depth i
 };
 
 // row r's view of the launch's finalize arguments
@@ -435,11 +437,12 @@ __device__ __forceinline__ SampDrawWords samp_draw_words(const unsigned long lon
   return w;
 }
 // positions mode: position i of the row's verify pass draws what the row's step would draw for the token at index past + i + 1 (the pass has not moved *fin.pos)
-__device__ __forceinline__ SampDrawWords samp_position_words(const FinalizeArgs& fin, int i) {
+// (depth: a token tree's depth table — position i is the depth[i]-th input of its branch; nullptr: a chain)
+__device__ __forceinline__ SampDrawWords samp_position_words(const FinalizeArgs& fin, int i, const int* depth = nullptr) {
   SampDrawWords w{};
   w.seed = fin.req->seed;
   w.pos = *fin.pos;
-  w.index = w.pos + 1 + i;
+  w.index = w.pos + 1 + (depth ? depth[i] : i);
   return w;
 }
 
@@ -599,7 +602,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_tail_kernel(const SampPickArgs p
   double aw[4] = {0.0, 0.0, 0.0, 0.0};    // the compaction pass's bulk sums of this thread's four tiles (in flight beside the list)
   unsigned long long thr_k_prev = 0ull;
   if (pick) {
-    dw = POS ? samp_position_words(fin, row) : samp_draw_words<ROWS>(pa.seed, fin);
+    dw = POS ? samp_position_words(fin, row, pa.depth) : samp_draw_words<ROWS>(pa.seed, fin);
 #pragma unroll
     for (int j = 0; j < 4; j++) { const int w = tid * 4 + j; const double t = sc->wg_above[min(w, nwg - 1)]; aw[j] = w < nwg ? t : 0.0; }
     if (MODE == 1 && a.top_k > 0) thr_k_prev = sc->thr_k;
@@ -778,7 +781,7 @@ __global__ __launch_bounds__(SAMP_WG) void samp_pick_kernel(const SampPickArgs p
   double pw[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) { const int w = tid * 4 + j; pw[j] = sc->wg_z2[min(w, nwg - 1)]; }
-  const SampDrawWords dw = POS ? samp_position_words(fin, row) : samp_draw_words<ROWS>(pa.seed, fin);
+  const SampDrawWords dw = POS ? samp_position_words(fin, row, pa.depth) : samp_draw_words<ROWS>(pa.seed, fin);
   const unsigned long long thr_k = a.top_k > 0 ? sc->thr_k : 0ull, thr_p = a.top_p < 1.f ? sc->thr_p : 0ull;
   const float mx = samp_row_max(a, row, shf);
   const float z0 = a.min_p > 0.f ? samp_ordered_sum(sc->wg_z, nwg, shd) : 0.f;

@@ -35,8 +35,11 @@ static __global__ void verify_first_id_kernel(long long* ids, const int* tok) { 
 // (unsigned)idx < V guard of finalize_row), or the sampler's draw a.draws[i].
 // The row produces g[0], then g[1] if g[0] == draft[0], ... : draft[0 .. a - 1] followed by g[a]; a produced token that finishes the row (stop id, max_new)
 // ends the walk.  The position that produced the last token hands the row its logits row and partials; the next embedding is gathered at the advanced position.
-template <int DT>
-__device__ __forceinline__ void verify_accept_body(const VerifyArgs& a) {
+// TREE (tgx_verify_tree): the M positions are a token tree's (position 0 the row's current token; par[q] = the parent POSITION of position q, below q).  The walk
+// starts at position 0; the position it stands on produces g, and it moves to THE child that carries g as its input (siblings carry distinct tokens: at most one)
+// or ends.  path[j] = the position that produced token j: the cache slots past + path[j] hold the accepted inputs (kernels/kv_tree.h moves them into place).
+template <int DT, bool TREE = false>
+__device__ __forceinline__ void verify_accept_body(const VerifyArgs& a, const int* const par = nullptr, int* const path = nullptr) {
   __shared__ int s_g[VERIFY_MAX_POS];
   __shared__ int s_win, s_tok, s_pos;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -63,6 +66,20 @@ __device__ __forceinline__ void verify_accept_body(const VerifyArgs& a) {
   if (threadIdx.x == 0) {
     RowStopWords w = row_stop_words(a.req, a.tok);
     int n = 0, win = 0;
+    if constexpr (TREE) {
+      for (int cur = 0; n < a.M;) {                 // (a parent stands below its child: the walk ends within M positions whatever the tables hold)
+        const int t = s_g[cur];
+        row_count_and_stop(a.req, w, t);
+        w.produced++;
+        path[n] = cur; a.rec->ids[n++] = t; win = cur;
+        if (a.req->finished) break;
+        int nxt = -1;
+        for (int q = cur + 1; q < a.M; q++)
+          if (par[q] == cur && a.draft[q - 1] == (long long)t) { nxt = q; break; }
+        if (nxt < 0) break;
+        cur = nxt;
+      }
+    } else
     for (int i = 0; i < a.M; i++) {
       const int t = s_g[i];
       row_count_and_stop(a.req, w, t);
@@ -93,6 +110,9 @@ __device__ __forceinline__ void verify_accept_body(const VerifyArgs& a) {
 }
 template <int DT>
 __global__ __launch_bounds__(256) void verify_accept_kernel(const VerifyArgs a) { verify_accept_body<DT>(a); }
+struct VerifyTreeArgs { VerifyArgs v; const int* par; int* path; };      // device tables of VERIFY_MAX_POS ints each
+template <int DT>
+__global__ __launch_bounds__(256) void verify_accept_tree_kernel(const VerifyTreeArgs t) { verify_accept_body<DT, true>(t.v, t.par, t.path); }
 
 // ---- tgx_verify_rows: the same two launches for the n rows of a joint pass.  tab[i] = row i's arguments over ITS slice of the pass's workspace (logits, partials,
 // draws or nullptr, the draft ids behind its first input) and its own record; one workgroup per row runs the walk above, so a row ends as its own one-row call leaves it

@@ -299,13 +299,25 @@ int ensure_extend_ws(tgx_ctx* c, int S, int past) {
   if (!ns) return TGX_OK;
   return dev_grow(c, &c->ext_part, &c->ext_part_bytes, extend_part_bytes(c, ns));
 }
-static void launch_attn_extend(tgx_ctx* c, const tgx::AttnPrefillArgs& a, int ns) {
+static void launch_attn_extend(tgx_ctx* c, const tgx::AttnPrefillArgs& a, int ns, const unsigned short* anc = nullptr) {      // anc: a token tree's masks (tgx_verify_tree)
   const int hd = c->d.head_dim;
   tgx::AttnExtendArgs e{};
   e.a = a; e.part = c->ext_part; e.ns = ns; e.n_tiles = (a.past + a.S - 1) / tgx::ATTN_KTILE + 1;
   if (!c->ext_part || extend_part_bytes(c, ns) > c->ext_part_bytes) { c->launch_fault = "attn_extend: the partials' workspace was not sized for this pass"; return; }
   const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
   const dim3 grid(a.heads, ns), blk(256);
+  if (anc) {
+    tgx::AttnExtendTreeArgs t{};
+    t.e = e; t.anc = anc;
+    auto go_tree = [&](auto paged) {
+      constexpr bool P = decltype(paged)::value;
+      TGX_DT16_SWITCH(c->dt,
+        if (hd == 64) { hipLaunchKernelGGL((tgx::attn_extend_tree_kernel<DT, 64, P>), grid, blk, lds1, c->stream, t); hipLaunchKernelGGL((tgx::attn_extend_merge_kernel<DT, 64>), dim3(a.heads), blk, 0, c->stream, e); }
+        else { hipLaunchKernelGGL((tgx::attn_extend_tree_kernel<DT, 128, P>), grid, blk, lds1, c->stream, t); hipLaunchKernelGGL((tgx::attn_extend_merge_kernel<DT, 128>), dim3(a.heads), blk, 0, c->stream, e); })
+    };
+    if (a.blk_tbl) go_tree(std::true_type{}); else go_tree(std::false_type{});
+    return;
+  }
   auto go = [&](auto paged) {
     constexpr bool P = decltype(paged)::value;
     TGX_DT16_SWITCH(c->dt,
@@ -396,10 +408,27 @@ static void launch_attn_mixed(tgx_ctx* c, const tgx::AttnRgArgs& r, const Ragged
 }
 
 // causal GQA flash attention of S prompt positions of one batch row (grid = ceil(S / 128) query blocks x heads)
-void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_lean) {
+// anc (tgx_verify_tree): the S <= 16 positions are a token tree's, masked by its ancestor words — the key-split form by the same rule as a chain of S positions, else
+// one workgroup per head of the one query block
+void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a_, bool allow_lean, const unsigned short* anc) {
   tgx::AttnPrefillArgs a = a_;
   const int hd = c->d.head_dim;
-  if (const int ns = extend_attn_splits(c, a.S, a.past)) { launch_attn_extend(c, a, ns); return; }
+  if (const int ns = extend_attn_splits(c, a.S, a.past)) { launch_attn_extend(c, a, ns, anc); return; }
+  if (anc) {
+    if (a.S > 16 || (hd != 64 && hd != 128)) { c->launch_fault = "attn_prefill_tree: a token tree has at most 16 positions, head_dim 64 or 128"; return; }
+    tgx::AttnTreeArgs t{};
+    t.a = a; t.anc = anc;
+    const size_t lds = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;
+    const dim3 grid(a.heads), blk(256);
+    auto go_tree = [&](auto paged) {
+      constexpr bool P = decltype(paged)::value;
+      TGX_DT16_SWITCH(c->dt,
+        if (hd == 64) hipLaunchKernelGGL((tgx::attn_prefill_tree_kernel<DT, 64, P>), grid, blk, lds, c->stream, t);
+        else hipLaunchKernelGGL((tgx::attn_prefill_tree_kernel<DT, 128, P>), grid, blk, lds, c->stream, t))
+    };
+    if (a.blk_tbl) go_tree(std::true_type{}); else go_tree(std::false_type{});
+    return;
+  }
   const int nqb = (a.S + tgx::ATTN_QBLK - 1) / tgx::ATTN_QBLK, nwg = nqb * a.heads;
   const size_t lds1 = (size_t)tgx::ATTN_KTILE * ((hd + 8) + (hd + 32)) * 2;      // one K tile | V tile pair (kernels/prefill.h)
   // head_dim 64, three or more workgroups per CU (prompts from ~3k tokens at 32 heads): K / V tiles by LDS-DMA, the next tile's scores under the current tile's
@@ -524,7 +553,14 @@ size_t advance_tables(const tgx_ctx* c, RaggedPass& p, unsigned char* host, cons
   return bytes;
 }
 // RoPE + cache append + q split of S prompt rows of one batch row
-void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S) {
+// (depth: a token tree's device depth table, tgx_verify_tree — row s into slot past + s, rotated for past + depth[s])
+void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S, const int* depth) {
+  if (depth) {
+    tgx::RopeTreeArgs r{};
+    r.a = a; r.depth = depth;
+    TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::rope_kv_split_tree_kernel<DT>, dim3(S), dim3(256), 0, c->stream, r))
+    return;
+  }
   TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::rope_kv_split_kernel<DT>, dim3(S), dim3(256), 0, c->stream, a))
 }
 // ... of every row of a ragged pass, each into its own prompt's row: ONE launch

@@ -118,7 +118,7 @@ int vs_rezero(tgx_ctx* c) {
   return TGX_OK;
 }
 
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first) {
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first, const int* depth) {
   const bool joint = joint_first >= 0;      // tgx_verify_rows: the row's slice of the joint pass's workspace; the scratch and lists are the one-row call's (chains are stream-ordered)
   if (!c->vs_draws || !(joint ? c->vj_draws : c->vf_rec) || M > (int)tgx_ctx::VERIFY_ROWS) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
   const int V = c->d.vocab;
@@ -134,6 +134,7 @@ void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& 
   tgx::SampPickArgs pa{};
   pa.fin.pos = c->rows[(size_t)row].pos; pa.fin.req = c->row_req + row; pa.fin.row = row;      // the key's words: read, never written
   pa.draws = joint ? c->vj_draws + joint_first : c->vs_draws;
+  pa.depth = depth;      // (tgx_verify_tree: the device depth table of the pass's positions)
   launch_chain(c, a, cfg, M, pa, /*positions=*/true);
 }
 

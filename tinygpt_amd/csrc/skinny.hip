@@ -336,7 +336,8 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
 // Prompts of a few tokens (NB * S <= 32 workspace rows): the batched prefill with every product as a skinny MFMA GEMM (kernels/skinny.h) —
 // the 128-row tiles of gemm_x2_kernel would stream the weights for 4-25 % useful rows through a two-barrier K loop; here the weight stream
 // is the decode step's, RMSNorm rides in the activation staging and narrow products finish through the row-wise slab reducers.
-void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg) {
+// tree (tgx_verify_tree; one row): position p goes to cache slot past + p but is rotated for past + depth[p], and attends its own branch alone (TreePass)
+void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg, const TreePass* tree) {
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, I = d.inter, hd = d.head_dim, qd = d.heads * hd, kvd = d.kv_heads * hd;
   const size_t kv_layer = c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK * hd : (size_t)d.kv_heads * d.max_ctx * hd;      // elements (paged KV: a layer's pool)
@@ -384,7 +385,7 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
       a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
       a.heads = d.heads; a.kv_heads = d.kv_heads; a.hd = hd; a.max_ctx = d.max_ctx; a.past = past; a.blk_tbl = r.tbl;
       a.q_norm_w = d.qk_norm ? (const bf16_t*)w.q_norm : nullptr; a.k_norm_w = d.qk_norm ? (const bf16_t*)w.k_norm : nullptr; a.eps = d.norm_eps;
-      launch_rope_kv_split(c, a, S);
+      launch_rope_kv_split(c, a, S, tree ? tree->depth : nullptr);
     }
     for (int b = 0; b < NB && !rg; b++) {
       RowState& r = c->rows[(size_t)(row0 + b)];
@@ -394,7 +395,7 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
       a.k_cache = reinterpret_cast<bf16_t*>(r.kcache) + (size_t)l * kv_layer; a.v_cache = reinterpret_cast<bf16_t*>(r.vcache) + (size_t)l * kv_layer;
       a.o_hi = c->ws_ah + ro * qd; a.o_lo = c->ws_al + ro * qd; a.S = S; a.heads = d.heads; a.kv_heads = d.kv_heads; a.max_ctx = d.max_ctx; a.past = past;
       a.scale = 1.0f / sqrtf((float)hd); a.qblk_mirror = 1; a.blk_tbl = r.tbl;
-      launch_attn_prefill(c, a, /*allow_lean=*/false);
+      launch_attn_prefill(c, a, /*allow_lean=*/false, tree ? tree->anc : nullptr);
     }
     SkinnyCall o;
     o.epi = tgx::GEMM_RESIDUAL; o.W = w.wo; o.C = c->ws_x; o.ldc = H; o.M = M; o.N = H; o.K = qd; o.nt = 2; o.asrc = 0; o.a_hi = c->ws_ah; o.a_lo = c->ws_al;

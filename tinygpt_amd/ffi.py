@@ -110,6 +110,7 @@ ABI = {
     "restore_row": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "verify_row": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "verify_row_sampled": (c_int, [c_void_p, c_int, POINTER(c_int64), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "verify_tree": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int32), c_int, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "read_pass_logits": (c_int, [c_void_p, POINTER(c_float), c_int, POINTER(c_int32)]),
     "verify_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
     "advance_rows": (c_int, [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
@@ -437,6 +438,21 @@ class Model:
         n, fin = c_int32(0), c_int32(0)
         ptr = draft.ctypes.data_as(POINTER(c_int64)) if len(draft) else (c_int64 * 1)()
         self._check(self.be.verify_row_sampled(self._ctx, row, ptr, len(draft), out.ctypes.data_as(POINTER(c_int64)), ctypes.byref(n), ctypes.byref(fin)))
+        return out[:n.value].copy(), fin.value
+
+    def verify_tree(self, row: int, tokens, parent):
+        """verify a token TREE of 1 .. 15 guesses on the live row `row` in one pass (include/tgx.h tgx_verify_tree): tokens[i] is node i's token, parent[i] its parent
+        node (-1: a child of the row's current token, else an index < i).  Every node attends its own branch alone; the row takes the branch its own settings
+        produce (greedy, or its sampler's draws) and stands as after that many decode steps -> (produced ids, finish).  A chain (parent[i] == i - 1) is
+        verify_row_sampled itself"""
+        tokens = np.ascontiguousarray(np.asarray(tokens, dtype=np.int64).reshape(-1))
+        parent = np.ascontiguousarray(np.asarray(parent, dtype=np.int32).reshape(-1))
+        assert len(tokens) == len(parent), (len(tokens), len(parent))
+        out = np.empty(len(tokens) + 1, dtype=np.int64)
+        n, fin = c_int32(0), c_int32(0)
+        tptr = tokens.ctypes.data_as(POINTER(c_int64)) if len(tokens) else (c_int64 * 1)()
+        pptr = parent.ctypes.data_as(POINTER(c_int32)) if len(parent) else (c_int32 * 1)()
+        self._check(self.be.verify_tree(self._ctx, row, tptr, pptr, len(tokens), out.ctypes.data_as(POINTER(c_int64)), ctypes.byref(n), ctypes.byref(fin)))
         return out[:n.value].copy(), fin.value
 
     def pass_logits(self) -> np.ndarray:

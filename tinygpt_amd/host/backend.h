@@ -51,6 +51,8 @@ struct Backend {
   // ... under sampling (optional: GPTConfig::speculateSampled needs verify_row_sampled, set_row_sampler and sample_row besides; read_pass_logits is the tests' view of a pass)
   int (*verify_row_sampled)(tgx_ctx*, int, const int64_t*, int, int64_t*, int32_t*, int32_t*) = nullptr;
   int (*read_pass_logits)(tgx_ctx*, float*, int, int32_t*) = nullptr;
+  // ... of a token tree (optional: GPTConfig::speculateTree needs it; without it the drafts stay chains)
+  int (*verify_tree)(tgx_ctx*, int, const int64_t*, const int32_t*, int, int64_t*, int32_t*, int32_t*) = nullptr;
   // ... of a batch of several sequences (optional: all rows' drafts in one joint pass; without it a batch keeps the plain loop)
   int (*verify_rows)(tgx_ctx*, int, const int32_t*, const int64_t*, const int32_t*, int64_t*, int32_t*, int32_t*) = nullptr;
   // chunked prefill (optional; bound for a batch engine to come — nothing in this host engine calls it yet): prompt chunks and live rows' steps in one ragged pass
@@ -100,7 +102,7 @@ struct Backend {
     TGXH_BIND(reset_row, false); TGXH_BIND(forward_row, false); TGXH_BIND(sample_row, false); TGXH_BIND(past_length_row, false);
     TGXH_BIND(extend_row, false); TGXH_BIND(truncate_row, false); TGXH_BIND(splice_row, false);
     TGXH_BIND(verify_row, false); TGXH_BIND(set_row_stop, false); TGXH_BIND(decode_rows, false);
-    TGXH_BIND(verify_row_sampled, false); TGXH_BIND(read_pass_logits, false); TGXH_BIND(verify_rows, false);
+    TGXH_BIND(verify_row_sampled, false); TGXH_BIND(read_pass_logits, false); TGXH_BIND(verify_rows, false); TGXH_BIND(verify_tree, false);
     TGXH_BIND(advance_rows, false);
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
     TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);

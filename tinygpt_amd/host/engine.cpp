@@ -307,10 +307,28 @@ bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool&
   const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
   // a pass over n draft tokens produces up to n + 1 tokens and fills positions past .. past + n
   const int64_t cap = !speculateActive(1) ? 0 : std::min<int64_t>({(int64_t)config_.speculate, (int64_t)TGX_MAX_DRAFT, room - 1, contextSize() - past - 1});      // (GPTConfig::logprobs alone feeds the consumer one step at a time)
-  const std::vector<int32_t> draft = cap >= 1 ? ngram_draft(seq, (int)cap) : std::vector<int32_t>();
   int32_t n = 0, fin = 0;
   int64_t ids[TGX_MAX_DRAFT + 1] = {0};
-  if (!draft.empty()) {
+  // GPTConfig::speculateTree: the same positions as branches where the tail has continued in different ways before; a refusal as unsupported leaves the row as it
+  // was (ALL OR NOTHING), and the chain below takes this iteration and the rest of the call
+  bool treeDone = false;
+  if (cap >= 2 && config_.speculateTree >= 2 && be_.verify_tree && !treeRefused_) {
+    const tgxh::DraftTree tree = tgxh::ngram_tree(seq, (int)cap, config_.speculateTree);
+    if (tree.branches >= 2) {
+      int64_t t64[TGX_MAX_TREE_NODES];
+      for (size_t i = 0; i < tree.tokens.size(); i++) t64[i] = tree.tokens[i];
+      const int rc = be_.verify_tree(model_.ctx, 0, t64, tree.parent.data(), (int)tree.tokens.size(), ids, &n, &fin);
+      if (rc == TGX_ERR_UNSUPPORTED) treeRefused_ = true;
+      else if (rc != TGX_OK) return fail(std::string("verify_tree: ") + be_.last_error(model_.ctx));
+      else {
+        treeDone = true;
+        spec_.verifyCalls++; spec_.treePasses++; spec_.draftTokens += (int64_t)tree.tokens.size(); spec_.acceptedDrafts += n - 1; spec_.producedHist[n]++;
+      }
+    }
+  }
+  const std::vector<int32_t> draft = cap >= 1 && !treeDone ? ngram_draft(seq, (int)cap) : std::vector<int32_t>();
+  if (treeDone) {
+  } else if (!draft.empty()) {
     int64_t d64[TGX_MAX_DRAFT];
     for (size_t i = 0; i < draft.size(); i++) d64[i] = draft[i];
     const auto verify = speculateSampledActive(1) ? be_.verify_row_sampled : be_.verify_row;      // (the row's sampler is the call's: rowsBegin)
@@ -633,6 +651,7 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
     seq.push_back((int32_t)first[0]);
     if (be_.set_row_stop(model_.ctx, 0, (int32_t)(n_new - 1), nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
     bool finished = false;
+    treeRefused_ = false;      // (GPTConfig::speculateTree: a refusal holds for one call)
     while ((int64_t)seq.size() < S + n_new && !finished) {
       const size_t before = seq.size();
       if (!speculateMore(seq, S + n_new, finished)) return out;
@@ -826,6 +845,7 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
     std::vector<int32_t> seq = tokens;
     const int64_t maxNew = config_.maxNewTokens;
     bool finished = false;
+    treeRefused_ = false;      // (GPTConfig::speculateTree: a refusal holds for one call)
     if (be_.set_row_stop(model_.ctx, 0, (int32_t)(maxNew - 1), eosTokenIds_.empty() ? nullptr : eosTokenIds_.data(), (int)eosTokenIds_.size()) != TGX_OK) {
       fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); broke = true;
     }

@@ -84,6 +84,13 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // tgx_decode_rows.  A sampled token is a pure function of its logits and the draw key (seed, token index, row), so the ids are those of the plain loop up to
   // the summation order between kernel paths.  A backend without the call keeps the old loop.
   bool speculateSampled = false;
+  // ... with a token TREE of guesses (default 0 = off: every existing run is unchanged; 1 is the same as 0 — one branch is a chain).  B >= 2 (needs speculate > 0;
+  // ONE sequence): where the sequence's tail has
+  // occurred before with different continuations, up to B of them share the pass's `speculate` positions as branches below the current token (spec_draft.h
+  // ngram_tree) and the device follows whichever the row produces (include/tgx.h tgx_verify_tree); the first branch is the chain `speculate` alone would draft,
+  // cut to its share.  One candidate is a chain and goes the chain's way.  Where the device refuses a tree with TGX_ERR_UNSUPPORTED (fp32 storage, GPT-2, log-
+  // probability records, ..) the engine falls back to chain drafts for the rest of the call.  The ids are those of speculate = 0, as for the chain.
+  int speculateTree = 0;
   // Not in the reference's engine (its server speaks the completions protocol's `logprobs`): -1 = off, the loops below exactly as they were.  N in
   // [0, TGX_MAX_LOGPROBS]: every produced token comes with its log-probability under the model's distribution and the N most likely alternatives
   // (include/tgx.h tgx_set_row_logprobs).  The engine then steps through tgx_sample_row / tgx_decode_rows (tgx_verify_row under `speculate`) and drains the rows'
@@ -136,6 +143,7 @@ struct GPTOutput {       // src/engine/GPTEngine.h:34-40
 struct SpecStats {
   int64_t verifyCalls = 0, draftTokens = 0, acceptedDrafts = 0, plainSteps = 0;
   int64_t producedHist[TGX_MAX_DRAFT + 2] = {};
+  int64_t treePasses = 0;      // of verifyCalls: passes over a tree of two or more branches (GPTConfig::speculateTree)
 };
 
 // GPTEngine::score: the log-probability of tokenIds[i + 1] under the model's distribution after tokenIds[0 .. i], for i in [0, n - 1) — n - 1 values, one per
@@ -228,6 +236,7 @@ class GPTEngine {
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
   void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
   void setSpeculateSampled(bool on) { config_.speculateSampled = on; }
+  void setSpeculateTree(int branches) { config_.speculateTree = branches; }
   void setLogprobs(int topN) { config_.logprobs = topN; }
   const SamplerConfig& samplerConfig() const { return config_.samplerConfig; }
   void setProcessors(float repetition, float presence, float frequency, std::map<int32_t, float> bias) {      // kept by the C view across tgxe_reconfigure
@@ -295,6 +304,7 @@ class GPTEngine {
   std::vector<int32_t> cached_;      // reusePrefix: the token ids row 0's cache holds, position by position (empty: unknown / nothing)
   int64_t lastReused_ = 0, lastShifts_ = 0;
   SpecStats spec_;
+  bool treeRefused_ = false;                                  // GPTConfig::speculateTree: the device refused a tree as unsupported — chain drafts for the rest of the call
   std::string constraintPattern_;            // the pattern and stop ids of the table the device holds (constraintId_ >= 0)
   std::vector<int32_t> constraintStops_;
   int32_t constraintId_ = -1;

@@ -72,6 +72,9 @@ TGXE_API int64_t tgxe_last_shifts(tgxe_engine* h) { return h ? h->e->lastShifts(
 TGXE_API void tgxe_set_speculate(tgxe_engine* h, int max_draft) { if (h) h->e->setSpeculate(max_draft); }
 // ... under a sampling configuration as well (GPTConfig::speculateSampled; 0 = off, the default)
 TGXE_API void tgxe_set_speculate_sampled(tgxe_engine* h, int on) { if (h) h->e->setSpeculateSampled(on != 0); }
+// ... with token trees (GPTConfig::speculateTree: branches, 0 = off, the default); tgxe_spec_tree_passes = how many of the verify passes ran a tree of two or more branches
+TGXE_API void tgxe_set_speculate_tree(tgxe_engine* h, int branches) { if (h) h->e->setSpeculateTree(branches); }
+TGXE_API int64_t tgxe_spec_tree_passes(tgxe_engine* h) { return h ? h->e->specStats().treePasses : 0; }
 // the engine's device context (GPTEngine::ctx): for the diagnostic calls of include/tgx.h (tgx_read_pass_logits, tgx_read_kv) on what the engine just ran
 TGXE_API void* tgxe_ctx(tgxe_engine* h) { return h ? (void*)h->e->ctx() : nullptr; }
 TGXE_API int tgxe_spec_stats(tgxe_engine* h, int64_t* out, int cap) {
@@ -86,6 +89,13 @@ TGXE_API int tgxh_ngram_draft(const int32_t* ids, int n, int max_draft, int32_t*
   const std::vector<int32_t> d = tgxh::ngram_draft(std::vector<int32_t>(ids, ids + (ids && n > 0 ? n : 0)), max_draft);
   for (size_t i = 0; i < d.size(); i++) out[i] = d[i];
   return (int)d.size();
+}
+// ... and the tree drafter (spec_draft.h ngram_tree): tokens / parents of at most max_nodes nodes into the two arrays; returns the node count, *out_branches the chains
+TGXE_API int tgxh_ngram_tree(const int32_t* ids, int n, int max_nodes, int max_branches, int32_t* out_tokens, int32_t* out_parent, int32_t* out_branches) {
+  const tgxh::DraftTree t = tgxh::ngram_tree(std::vector<int32_t>(ids, ids + (ids && n > 0 ? n : 0)), max_nodes, max_branches);
+  for (size_t i = 0; i < t.tokens.size(); i++) { out_tokens[i] = t.tokens[i]; out_parent[i] = t.parent[i]; }
+  if (out_branches) *out_branches = t.branches;
+  return (int)t.tokens.size();
 }
 // per-token log-probabilities (GPTConfig::logprobs): top_n = -1 off, 0 .. TGX_MAX_LOGPROBS.  tgxe_last_logprobs copies what the last generate call recorded —
 // out_lp [batch * new tokens], out_top_ids / out_top_lp [batch * new tokens * top_n] (either may be NULL), up to cap tokens — and returns the number of tokens

@@ -63,6 +63,8 @@ static void usage(const char* prog) {
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (--temperature 0 --top-p 1; several prompts: every row's\n"
           "                            draft in one joint pass; default: 0 = off)\n"
           "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n"
+          "  --speculate-tree <b>      with --speculate, one prompt: where the text's tail has continued in different ways before, up to b of them share the pass's\n"
+          "                            positions as branches of a token tree, and the device follows the one the model produces (b >= 2; default: 0 = off, 1 is the same: one branch is a chain)\n"
           "  --context-shift           generate past the context: a full row keeps its first --keep positions, drops half of the rest and slides the tail down, its keys\n"
           "                            re-rotated (no drafts are proposed while it is on; default: off, the run ends at the context)\n"
           "  --keep <n>                with --context-shift: positions kept at the front of a shifted row (default: 0)\n",
@@ -75,6 +77,7 @@ static void print_spec(const tgxh::GPTConfig& cfg, const tgxh::GPTEngine& engine
   const tgxh::SpecStats& s = engine.specStats();
   printf("speculate: %lld verify passes, %lld of %lld draft tokens accepted, %lld ordinary steps\n", (long long)s.verifyCalls, (long long)s.acceptedDrafts, (long long)s.draftTokens,
          (long long)s.plainSteps);
+  if (cfg.speculateTree >= 2) printf("speculate-tree: %lld of the verify passes ran a tree of two or more branches\n", (long long)s.treePasses);
 }
 
 // --num-beams: one line per returned hypothesis, best first (nothing is printed without the flag)
@@ -161,6 +164,7 @@ int main(int argc, char** argv) {
     else if (a == "--num-return") cfg.numReturn = atoi(next());
     else if (a == "--speculate") cfg.speculate = atoi(next());
     else if (a == "--speculate-sampled") cfg.speculateSampled = true;
+    else if (a == "--speculate-tree") cfg.speculateTree = atoi(next());
     else if (a == "--context-shift") cfg.contextShift = true;
     else if (a == "--keep") cfg.shiftKeep = std::max(0, atoi(next()));
     else if (a == "--session-load") session_load = next();

@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from tinygpt_amd import known_desc, synth
 from tinygpt_amd.desc import desc_from_hf_config
-from tinygpt_amd.ffi import ADV_FEED, ADV_FEED_MORE, ADV_STEP, GREEDY, Backend, Model, SamplerCfg, TgxError, product_backend
+from tinygpt_amd.ffi import ABI, ADV_FEED, ADV_FEED_MORE, ADV_STEP, GREEDY, Backend, Model, SamplerCfg, TgxError, product_backend
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--parent-lib", default="", help="a libtgx_mi355x.so of the parent commit, run beside this build's")
@@ -133,7 +133,7 @@ def run(be, make, budget):
 
 lines, bad = [], 0
 mine = product_backend()
-parent = Backend(args.parent_lib, "tgx_") if args.parent_lib else None
+parent = Backend(args.parent_lib, "tgx_", required=[n for n in ABI if n != "verify_tree"]) if args.parent_lib else None      # (the parent commit has no tgx_verify_tree)
 for name, make, budget in (("Llama-3.2-1B bf16, slabs", llama, 0), ("Llama-3.2-1B bf16, kv.budget_tokens 4096, extend.attn_splits 4", llama, 4096), ("gpt2_hd64 geometry fp32", gpt2_fp32, 1), ("gpt2_hd64 geometry fp32, prefill.mfma 0", gpt2_fp32, 0)):
     a = run(mine, make, budget)
     h = hashlib.sha256()

@@ -21,7 +21,14 @@ usage: python tools/spec_bench.py --sampler 0.8,0,0.9,0 [--parent-lib PATH] [--r
 --rows B[,B..] (profiles/verify_rows.txt): tgx_verify_rows over B rows at context 2048 — 4 and 8 positions per row, greedy and T 0.8 / top-p 0.9, extend.attn_splits
 0, -1, the split count min(32, 2 * 256 CUs / (B * heads)) of the automatic rule and 2 / 4 / 8 — against B sequential tgx_verify_row_sampled calls and one B-row tgx_decode_rows step
 of the parent commit's library (--parent-lib; without it, of this build), and the accepted drafts per row from which the joint call beats plain stepping.
-usage: python tools/spec_bench.py --rows 2,4,8 [--parent-lib PATH] [--reps 9] [--out profiles/verify_rows.txt]"""
+usage: python tools/spec_bench.py --rows 2,4,8 [--parent-lib PATH] [--reps 9] [--out profiles/verify_rows.txt]
+
+--tree (profiles/verify_tree.txt): tgx_verify_tree at context 2048, greedy and T 0.8 / top-p 0.9.  COST: ms per tree pass at 4 / 8 / 16 positions (two branches
+interleaved in index order, the second one right: the accepted path is non-contiguous and the compaction moves every accepted row) against tgx_verify_row_sampled
+of the same number of positions on the parent commit's library (--parent-lib; without it, on this build) — the median of --reps calls, and beside it the spread of
+the parent's own figure over three repeated medians.  ACCEPTANCE: the host engine free-running with speculate 7, speculateTree 0 against 3, on a text the tool
+generates — a few phrases that share a stem and go on differently, in random order — tokens produced per verify pass, tree passes, ids against speculate 0.
+usage: python tools/spec_bench.py --tree [--parent-lib PATH] [--reps 10] [--out profiles/verify_tree.txt]"""
 import argparse
 import ctypes
 import os
@@ -318,14 +325,123 @@ def measure_rows(B_list, reps, lines, parent_lib):
         old.close()
 
 
+def measure_tree(reps, lines, parent_lib):
+    from tinygpt_amd.ffi import ABI, Backend, SamplerCfg
+    d = known_desc("llama-3.2-1b", "bf16")
+    d.max_batch = 1
+    seed = 7
+    m = Model(d).load_synthetic(1234, 0.02).finalize()
+    old = Model(d, backend=Backend(parent_lib, "tgx_", required=[n for n in ABI if n != "verify_tree"])).load_synthetic(1234, 0.02).finalize() if parent_lib else m
+    V = d.vocab
+    prompt = synth.synth_prompt(V, S, 1234)
+
+    def fresh_row(mm, c):
+        mm.reset_cache()
+        mm.forward_row(0, prompt)
+        mm.set_row_sampler(0, c, seed)
+        return int(mm.sample_row(0, c, seed))
+
+    lines.append("COST.  chain baseline from: %s; ms per call, synchronised; median (min .. max) of %d calls, the cases interleaved; the parent's figure three times over" % (
+        "the parent commit's library" if parent_lib else "this build (no --parent-lib)", reps))
+    lines.append("  sampler | positions | tree pass (this build) | chain pass tgx_verify_row_sampled (parent): three medians | spread of the parent's medians | tree - parent's middle median | tokens the tree pass produced")
+    for sname, c in (("greedy", GREEDY), ("T 0.8 / top-p 0.9", SamplerCfg(0.8, 0, 0.9, 0.0))):
+        fresh_row(m, c)
+        ref = [int(t) for t in m.decode_rows(16)[0][:, 0]]     # the row's own run
+        for P in (4, 8, 16):
+            n = P - 1
+            parent = [-1, -1] + list(range(n - 2))             # two branches interleaved in index order
+            depth = [1, 1] + [0] * (n - 2)
+            for i in range(2, n):
+                depth[i] = depth[parent[i]] + 1
+            # the second branch (odd nodes) carries the row's own continuation, the first one tokens it will not produce
+            tokens = [ref[depth[i] - 1] if i % 2 == 1 else (ref[depth[i] - 1] + 1) % V for i in range(n)]
+            tt, tp, got = [], [[], [], []], []
+            for rep in range(reps + 2):                        # two warm-up rounds, discarded
+                keep = rep >= 2
+                fresh_row(m, c)
+                ms, r = timed(lambda: m.verify_tree(0, tokens, parent))
+                if keep:
+                    tt.append(ms); got.append(len(r[0]))
+                for k in range(3):
+                    fresh_row(old, c)
+                    ms, _ = timed(lambda: old.verify_row_sampled(0, ref[:n]))
+                    if keep:
+                        tp[k].append(ms)
+            meds = sorted(statistics.median(x) for x in tp)
+            lines.append("  %s | %d | %s | %.3f  %.3f  %.3f | %.3f | %+.3f | %d of at most %d" % (
+                sname, P, med(tt), meds[0], meds[1], meds[2], meds[2] - meds[0], statistics.median(tt) - meds[1], statistics.median(got), n // 2 + 1))
+    m.close()
+    if old is not m:
+        old.close()
+
+
+def free_running_tree(lines):
+    from ctypes import POINTER, c_int, c_int64, c_void_p
+    from host_util import HostEngine, host_lib
+    lib = host_lib()
+    lib.tgxe_set_speculate.argtypes = [c_void_p, c_int]
+    lib.tgxe_set_speculate_sampled.argtypes = [c_void_p, c_int]
+    lib.tgxe_set_speculate_tree.argtypes = [c_void_p, c_int]
+    lib.tgxe_spec_tree_passes.restype = c_int64
+    lib.tgxe_spec_tree_passes.argtypes = [c_void_p]
+    lib.tgxe_spec_stats.restype = c_int
+    lib.tgxe_spec_stats.argtypes = [c_void_p, POINTER(c_int64), c_int]
+    # the text: four phrases of 16 tokens that share a 4-token stem and go on differently, 128 of them in random order — the tail of the text has been continued
+    # in several ways before, which is where a tree can hold what a chain cannot
+    rng = np.random.default_rng(99)
+    stem = synth.synth_prompt(128256, 4, 98).astype(np.int32)
+    phrases = [np.concatenate([stem, synth.synth_prompt(128256, 12, 100 + k).astype(np.int32)]) for k in range(4)]
+    prompt = np.concatenate([phrases[int(k)] for k in rng.integers(0, 4, S // 16)])
+    n_new = 256
+    lines.append("ACCEPTANCE.  free-running generateSync, speculate 7, %d new tokens after a %d-token prompt (four 16-token phrases sharing a 4-token stem, in random order), unpaged" % (n_new, len(prompt)))
+    for sname, sampler in (("greedy", {}), ("T 0.8 / top-p 0.9", dict(temperature=0.8, top_p=0.9))):
+        res = {}
+        for branches in (None, 0, 3):                          # None: speculate 0, the ids to compare against
+            e = HostEngine(lib, synthetic="llama-3.2-1b", device="mi355x", dtype=1, max_batch=1)      # a fresh engine per variant: its statistics count from zero
+            assert e.prepare(), e.error()
+            lib.tgxe_set_speculate(e.h, 0 if branches is None else 7)
+            lib.tgxe_set_speculate_sampled(e.h, 1 if sampler else 0)
+            lib.tgxe_set_speculate_tree(e.h, branches or 0)
+            times = []
+            for rep in range(3):
+                e.reconfigure(max_new=n_new, **sampler)
+                t = time.perf_counter()
+                ids, new, fin = e.generate_sync([prompt])
+                times.append((time.perf_counter() - t) * 1e3)
+            buf = (c_int64 * 32)()
+            lib.tgxe_spec_stats(e.h, buf, 32)
+            res[branches] = (times, ids[0, len(prompt):].tolist(), list(buf[:21]), int(lib.tgxe_spec_tree_passes(e.h)))
+            e.close()
+        for branches in (0, 3):
+            times, ids, st, trees = res[branches]
+            first_diff = next((i for i, (a, b) in enumerate(zip(res[None][1], ids)) if a != b), None)
+            lines.append("  %s | %s | whole call incl. prefill ms %s (speculate 0: %s) | over 3 runs: %d verify passes (%d of them trees), %d of %d draft tokens accepted, %d ordinary steps | %.3f tokens produced per verify pass | produced per pass 1..16: %s | ids equal to speculate 0: %s" % (
+                sname, "tree, 3 branches" if branches else "chain", med(times), med(res[None][0]), st[0], trees, st[2], st[1], st[3], (st[2] + st[0]) / max(st[0], 1), st[5:21],
+                "yes" if first_diff is None else "up to new token %d" % first_diff))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default="")
     ap.add_argument("--rows", default="", help="B[,B..]: measure tgx_verify_rows over B rows instead (profiles/verify_rows.txt), e.g. --rows 2,4,8")
     ap.add_argument("--sampler", default="", help="T,K,P,M: measure tgx_verify_row_sampled under this sampler instead")
+    ap.add_argument("--tree", action="store_true", help="measure tgx_verify_tree instead (profiles/verify_tree.txt)")
     ap.add_argument("--parent-lib", default="", help="with --sampler / --rows: a libtgx_mi355x.so of the parent commit, for the A/B baselines")
     a = ap.parse_args()
+    if a.tree:
+        import torch
+        lines = ["tools/spec_bench.py --tree --reps %d%s   device: %s   Llama-3.2-1B bf16 synthetic, prompt %d tokens, unpaged" % (
+            a.reps, " --parent-lib <parent build>" if a.parent_lib else "", torch.cuda.get_device_name(0), S)]
+        measure_tree(a.reps, lines, a.parent_lib)
+        free_running_tree(lines)
+        text = "\n".join(lines) + "\n"
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     if a.rows:
         import torch
         lines = ["tools/spec_bench.py --rows %s --reps %d%s   device: %s   Llama-3.2-1B bf16 synthetic, %d-token prompts, unpaged" % (
