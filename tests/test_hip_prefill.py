@@ -225,3 +225,27 @@ def test_down_on_wide_tiles_matches_the_square_tiles(name, S, dtype):
     np.testing.assert_array_equal(outs[1][0], outs[2][0])
 
 
+
+
+# the experiment knobs retired with their experiments (INTEGRATION.md "Which keys exist"): each is an unknown key now
+RETIRED_KEYS = ["prefill.gemm_dma", "prefill.defer_min_rows", "prefill.terms_rows", "prefill.wide_8k_max", "prefill.skinny_hidden_max_wide",
+                "attn.batch_la", "attn.batch_nw8", "attn.direct_g", "attn.fused_max", "attn.fused_nw4",
+                "skinny.cfg", "skinny.cfg_mid", "skinny.wgs", "skinny.dma_nbw", "skinny.dma_rows", "skinny.dma_qkv", "skinny.terms_above", "skinny.gu_split"]
+
+
+@pytest.fixture(scope="module")
+def llama_tiny():
+    cfg, g = load_golden("llama_tiny")
+    return Model(desc_from_hf_config(cfg, "bf16"), product_backend()).load_synthetic(int(g["seed"]), float(g["std"])).finalize()
+
+
+@pytest.mark.parametrize("key", RETIRED_KEYS)
+def test_retired_option_is_an_unknown_key(llama_tiny, key):
+    """tgx_set_option refuses a retired key like any unknown one (TGX_ERR_INVALID, "unknown option"), and tgx_get_option does not read it."""
+    from tinygpt_amd.ffi import TgxError
+    with pytest.raises(TgxError) as e:
+        llama_tiny.set_option(key, 0)
+    assert e.value.status == 1 and "unknown option" in str(e.value)      # TGX_ERR_INVALID
+    with pytest.raises(TgxError) as e:
+        llama_tiny.get_option(key)
+    assert e.value.status == 1

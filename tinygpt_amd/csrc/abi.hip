@@ -585,12 +585,15 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
 //   SKINNY  16-bit storage, a few rows: the weight stream of a decode step (skinny.hip; limits measured in ctx.h at prefill_skinny_rows)
 //   TILED   16-bit storage through the split-term GEMMs (prefill.hip; every family incl. GPT-2)
 enum PrefillRoute { ROUTE_STEPS, ROUTE_F32, ROUTE_SKINNY, ROUTE_TILED };
+// 65-128 rows take the skinny route (eight blocks, LDS-DMA ring kernel only) up to this hidden size.  Measured ms per prompt, skinny / tiled: Llama-3.2-1B S = 65
+// 1.65 / 1.89, 96 1.71 / 1.96, 128 1.82 / 2.05; Mistral-7B S = 96 8.01 / 7.56
+constexpr int SKINNY_HIDDEN_MAX_WIDE = 2048;
 static PrefillRoute prefill_route(const tgx_ctx* c, int len, int rows) {
   if (!c->prefill_mfma) return ROUTE_STEPS;
   if (c->dt == tgx::DT_F32) return len >= c->prefill_f32_min_rows ? ROUTE_F32 : ROUTE_STEPS;
   if (len < std::max(4, c->prefill_min_rows) || !prefill_shapes_ok(c->d)) return ROUTE_STEPS;
   const bool skinny = !c->gpt2 && c->prefill_skinny && c->d.vocab >= 128 &&
-                      (rows <= 32 ? c->prefill_skinny_rows >= rows : (rows <= c->prefill_skinny_rows && c->d.hidden <= c->prefill_skinny_hidden_max && (rows <= 64 || (c->skinny_dma && c->d.hidden <= c->prefill_skinny_hidden_max_wide))));
+                      (rows <= 32 ? c->prefill_skinny_rows >= rows : (rows <= c->prefill_skinny_rows && c->d.hidden <= c->prefill_skinny_hidden_max && (rows <= 64 || (c->skinny_dma && c->d.hidden <= SKINNY_HIDDEN_MAX_WIDE))));
   return skinny ? ROUTE_SKINNY : ROUTE_TILED;
 }
 
@@ -3003,52 +3006,34 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   }
   if (!strcmp(key, "attn.direct_max")) { c->attn_direct_max = c->attn_fused_max = value; return TGX_OK; }      // (both forms of the limit: an explicit value forces the form)
   if (!strcmp(key, "attn.direct_nw4")) { drop_step_graphs(c); c->attn_direct_nw4 = c->attn_fused_nw4 = value; return TGX_OK; }
-  if (!strcmp(key, "attn.fused_max")) { c->attn_fused_max = value; return TGX_OK; }
-  if (!strcmp(key, "attn.fused_nw4")) { drop_step_graphs(c); c->attn_fused_nw4 = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.terms_above")) { drop_step_graphs(c); c->skinny_terms_above = value; return TGX_OK; }
   if (!strcmp(key, "prefill.qkv_nosplit")) { c->qkv_nosplit = value; return TGX_OK; }
-  if (!strcmp(key, "prefill.terms_rows")) { c->prefill_terms_rows = value; return TGX_OK; }
   if (!strcmp(key, "prefill.splitk_8k")) { c->splitk_8k = value; return TGX_OK; }
   if (!strcmp(key, "act.round16")) { drop_step_graphs(c); c->act16 = value != 0; return TGX_OK; }
   if (!strcmp(key, "act.one_term_kernels")) { c->act16_kernels = value != 0; return TGX_OK; }      // 0: the two-term kernels on the all-zero second term (bit-identical; tests)      // (the all-zero term buffer is allocated with the next workspace check)
   if (!strcmp(key, "oproj.fused")) { drop_step_graphs(c); c->oproj_fused = value != 0; return TGX_OK; }
   if (!strcmp(key, "attn.raw_fuse")) { drop_step_graphs(c); c->attn_raw_fuse = value; return TGX_OK; }
-  if (!strcmp(key, "attn.batch_nw8")) { drop_step_graphs(c); c->attn_batch_nw8 = value; return TGX_OK; }
-  if (!strcmp(key, "attn.batch_la")) { if (value < -1 || value > 1) return set_err(c, TGX_ERR_INVALID, "attn.batch_la is -1, 0 or 1"); drop_step_graphs(c); c->attn_batch_la = value; return TGX_OK; }
   if (!strcmp(key, "attn.batch_mfma")) { if (value < 0) return set_err(c, TGX_ERR_INVALID, "attn.batch_mfma is a row count (0 = off)"); drop_step_graphs(c); c->attn_batch_mfma = value; return TGX_OK; }
-  if (!strcmp(key, "attn.direct_g")) { if (value != 0 && value != 1 && value != -1 && value != -2 && value != -4) return set_err(c, TGX_ERR_INVALID, "attn.direct_g is 0, 1 or -1 / -2 / -4"); drop_step_graphs(c); c->attn_direct_g = value; return TGX_OK; }
   if (!strcmp(key, "attn.mfma_min")) { c->attn_mfma_min = value; return TGX_OK; }
-  if (!strcmp(key, "prefill.defer_min_rows")) { c->defer_min_rows = value; return TGX_OK; }
   if (!strcmp(key, "prefill.defer_reduce")) { c->defer_reduce = value != 0; return TGX_OK; }
   if (!strcmp(key, "skinny.dma")) { drop_step_graphs(c); c->skinny_dma = value != 0; return TGX_OK; }
   if (!strcmp(key, "skinny.dma_oproj")) { drop_step_graphs(c); c->skinny_dma_oproj = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.dma_qkv")) { drop_step_graphs(c); c->skinny_dma_qkv = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.dma_nbw")) { if (value < 0 || value > 2) return set_err(c, TGX_ERR_INVALID, "skinny.dma_nbw is 0, 1 or 2"); drop_step_graphs(c); c->skinny_dma_nbw = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.dma_rows")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "skinny.dma_rows is a row count"); drop_step_graphs(c); c->skinny_dma_rows = value; return TGX_OK; }
   if (!strcmp(key, "skinny.terms")) { drop_step_graphs(c); c->skinny_terms = value; return TGX_OK; }     // 2: the QKV and lm_head products of 17-32-row batches as well (experiment)
   if (!strcmp(key, "skinny.ksplit")) { if (value < 0 || value > 2) return set_err(c, TGX_ERR_INVALID, "skinny.ksplit must be 0, 1 (<= 16 rows) or 2 (<= 32 rows)"); c->skinny_ksplit = value; return TGX_OK; }
   if (!strcmp(key, "prefill.gemm_tm")) { c->gemm_tm = value; return TGX_OK; }
-  if (!strcmp(key, "prefill.gemm_dma")) { c->gemm_dma = value; return TGX_OK; }
   if (!strcmp(key, "debug.gemv")) { c->debug_gemv = value; return TGX_OK; }
   if (!strcmp(key, "prefill.mfma")) { c->prefill_mfma = value != 0; return TGX_OK; }
   if (!strcmp(key, "prefill.min_rows")) { c->prefill_min_rows = value; return TGX_OK; }
   if (!strcmp(key, "prefill.f32_min_rows")) { c->prefill_f32_min_rows = value; return TGX_OK; }
   if (!strcmp(key, "prefill.splitk")) { c->gemm_splitk = value; return TGX_OK; }
   if (!strcmp(key, "decode.step_rows")) { if (value != 32 && value != 64 && value != 128) return set_err(c, TGX_ERR_INVALID, "decode.step_rows is 32, 64 or 128"); drop_step_graphs(c); c->decode_step_rows = value; return TGX_OK; }
-  if (!strcmp(key, "prefill.skinny_hidden_max_wide")) { c->prefill_skinny_hidden_max_wide = value; return TGX_OK; }
   if (!strcmp(key, "prefill.skinny_hidden_max")) { c->prefill_skinny_hidden_max = value; return TGX_OK; }
   if (!strcmp(key, "prefill.skinny_rows")) { if (value < 0 || value > 128) return set_err(c, TGX_ERR_INVALID, "prefill.skinny_rows is 0..128"); c->prefill_skinny_rows = value; return TGX_OK; }
   if (!strcmp(key, "prefill.wide_8k_eff")) { c->wide_8k_eff = value; return TGX_OK; }
-  if (!strcmp(key, "prefill.wide_8k_max")) { c->wide_8k_max = value; return TGX_OK; }
   if (!strcmp(key, "prefill.wide_n_min")) { c->wide_n_min = value; return TGX_OK; }
   if (!strcmp(key, "prefill.attn_dma")) { c->attn_dma = value; return TGX_OK; }
   if (!strcmp(key, "prefill.attn_ksplit")) { c->attn_ksplit = value; return TGX_OK; }
   if (!strcmp(key, "attn.qk_fuse")) { c->qk_fuse = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.wgs")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "skinny.wgs must be >= 1"); c->skinny_wgs = value; return TGX_OK; }
   if (!strcmp(key, "prefill.skinny")) { c->prefill_skinny = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.gu_split")) { c->skinny_gu_split = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.cfg_mid")) { if (value < 0 || value > 2) return set_err(c, TGX_ERR_INVALID, "skinny.cfg_mid is 0..2"); c->skinny_cfg_mid = value; return TGX_OK; }
-  if (!strcmp(key, "skinny.cfg")) { if (value < -1 || value > 2) return set_err(c, TGX_ERR_INVALID, "skinny.cfg is -1..2"); c->skinny_cfg_force = value; return TGX_OK; }
   if (!strcmp(key, "decode.mfma_min_batch")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "decode.mfma_min_batch must be >= 1"); c->decode_mfma_min = value; return TGX_OK; }
   if (!strcmp(key, "debug.profile_same_layer")) { c->prof_same_layer = value; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { if (value < -1) return set_err(c, TGX_ERR_INVALID, "extend.attn_splits is -1 (automatic), 0 (never) or a split count"); c->extend_attn_splits = value; return TGX_OK; }

@@ -33,8 +33,8 @@ static void launch_attn_g(tgx_ctx* c, tgx::AttnArgs a, int R, bool combine) {
   if (a.direct) {   // short context: one 16-wave workgroup per query head, no combine launch.  Measured (tok/s, direct vs split at context
     // ~120 / ~300 / ~430): see DESIGN.md §5; 1 head per workgroup beats 2 and 4 here (the K/V block is L2-resident, the softmax chain is not)
     // Batches (round 3): with R rows the K/V working set (R x kv_heads x T rows) no longer fits the L2s, and one workgroup per QUERY head reads each kv
-    // head gfull times — Llama-3.2-1B B = 32 at context ~600: 24 us per layer, a quarter of the step.  From `attn.direct_rows` rows on, a workgroup takes
-    // two query heads of a kv head (option attn.direct_g: 1, 2 or 4 heads).
+    // head gfull times — Llama-3.2-1B B = 32 at context ~600: 24 us per layer, a quarter of the step.  From 12 rows on, a workgroup takes
+    // two query heads of a kv head (1, 2 or 4 heads by batch rows: the dg line below).
     // measured ms/step by heads per workgroup (1 / 2 / 4): Llama-3.2-1B context 600 B = 16 1.105 / 1.058 / 1.132, B = 32 1.551 / 1.421 / 1.382; context 2k
     // B = 16 1.354 / 1.208 / 1.384, B = 32 2.458 / 1.906 / 1.680; Mistral-7B context 600 B = 16 4.11 / 3.94 / 4.35, B = 32 6.08 / 5.47 / 5.53
     // Batches on the matrix cores (round 3, option attn.batch_mfma = rows from which): the VALU form's arithmetic grows with the heads per workgroup
@@ -65,25 +65,19 @@ static void launch_attn_g(tgx_ctx* c, tgx::AttnArgs a, int R, bool combine) {
         if (!(c->debug_skip & 1)) {
           constexpr size_t lds4 = tgx::attn_mfma_lds_bytes<HD, 4>(), ldsr = tgx::attn_mfma_raw_lds_bytes<HD, 4>();
           // head_dim 64: the form without the second K / V register set — 208 instead of 309 registers, two workgroups per CU.  Measured ms/step with /
-          // without (Llama-3.2-1B, context 600): B = 32 1.317 / 1.314, B = 48 1.814 / 1.713, B = 64 1.902 / 1.796 — never behind: the default
-          // (option attn.batch_la: 1 = look-ahead, -1 = only while the workgroups number at most one per CU)
-          const bool la = HD != 64 || (c->attn_batch_la >= 0 ? c->attn_batch_la != 0 : (int)(gm.x * gm.y) <= c->num_cus);
-          // eight waves per workgroup (head_dim 64, option attn.batch_nw8: 1 = while the workgroups number at most one per CU, 2 = always): the blocks of 64 keys and the
-          // QKV finish's slab sums spread over twice the waves
+          // without (Llama-3.2-1B, context 600): B = 32 1.317 / 1.314, B = 48 1.814 / 1.713, B = 64 1.902 / 1.796 — never behind, so a property of the head dimension
+          constexpr bool la = HD != 64;
+          // eight waves per workgroup (head_dim 64) while the workgroups number at most one per CU: the blocks of 64 keys and the QKV finish's slab sums spread over
+          // twice the waves (Llama-3.2-1B B = 17 1.052 -> 1.030 ms/step, 32 1.189 -> 1.171; context 2k B = 17 1.239 -> 1.183; always: B = 64 1.518 -> 1.582)
           if constexpr (HD == 64) {
-            if ((a.raw_part || a.raw_qkv) && (c->attn_batch_nw8 >= 2 || (c->attn_batch_nw8 == 1 && (int)(gm.x * gm.y) <= c->num_cus))) {
+            if ((a.raw_part || a.raw_qkv) && (int)(gm.x * gm.y) <= c->num_cus) {
               constexpr size_t lds8 = tgx::attn_mfma_raw_lds_bytes<HD, 8>();
               hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 8, true, false, P>), gm, dim3(512), lds8, c->stream, a);
               return;
             }
           }
-          if (a.raw_part || a.raw_qkv) {     // + the QKV product's finish
-            if (la) hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 4, true, true, P>), gm, dim3(256), ldsr, c->stream, a);
-            else hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 4, true, false, P>), gm, dim3(256), ldsr, c->stream, a);
-          } else {
-            if (la) hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 4, false, true, P>), gm, dim3(256), lds4, c->stream, a);
-            else hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 4, false, false, P>), gm, dim3(256), lds4, c->stream, a);
-          }
+          if (a.raw_part || a.raw_qkv) hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 4, true, la, P>), gm, dim3(256), ldsr, c->stream, a);     // + the QKV product's finish
+          else hipLaunchKernelGGL((tgx::attn_decode_mfma_kernel<DT, HD, 4, false, la, P>), gm, dim3(256), lds4, c->stream, a);
         }
         return;
       }
@@ -91,8 +85,7 @@ static void launch_attn_g(tgx_ctx* c, tgx::AttnArgs a, int R, bool combine) {
     int dg = 1;
     // (two heads per workgroup as soon as one workgroup per query head would exceed one round of CUs: Llama-3.2-1B B = 9 0.937 -> 0.905 ms/step, B = 10 at context 2k
     //  1.194 -> 1.100; at 8 rows and fewer one head per workgroup stays ahead: B = 8 0.870 vs 0.895)
-    if (!QKN && c->attn_direct_g > 0) dg = R >= 24 ? (HD == 64 ? 4 : 2) : ((R >= 12 || R * a.heads > c->num_cus) ? 2 : 1);
-    if (!QKN && c->attn_direct_g < 0) dg = -c->attn_direct_g;          // experiments: force
+    if (!QKN) dg = R >= 24 ? (HD == 64 ? 4 : 2) : ((R >= 12 || R * a.heads > c->num_cus) ? 2 : 1);
     dg = std::min(dg, gfull);
     const bool raw = a.raw_part || a.raw_qkv;       // + the QKV product's finish in the prologue (batched step)
     if (dg >= 2 && gfull % dg == 0) {

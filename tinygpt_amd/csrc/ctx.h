@@ -255,25 +255,13 @@ struct tgx_ctx {
   // Measured ms per prompt, four-block skinny / tiled split-K: Llama-3.2-1B S = 33 1.48 / 1.51, 48 1.51 / 1.58, 64 1.57 / 1.70; Qwen2.5-0.5B S = 48 1.46 / 1.81;
   // Llama-3.2-3B S = 48 3.54 / 3.33, Mistral-7B 6.76 / 5.52 — four blocks put 8 MFMAs + 9 LDS fragment reads behind every 32 k of a weight row: at
   // hidden > 2048 the tiled path's weight stream is faster (option prefill.skinny_hidden_max)
-  // 65-128 rows (eight blocks, LDS-DMA ring kernel only), skinny / tiled: Llama-3.2-1B S = 65 1.65 / 1.89, 96 1.71 / 1.96, 128 1.82 / 2.05; Mistral-7B S = 96 8.01 / 7.56 -> hidden <= 2048
-  // (option prefill.skinny_hidden_max_wide)
-  int prefill_skinny_hidden_max_wide = 2048;
+  // 65-128 rows: hidden <= 2048 only (abi.hip SKINNY_HIDDEN_MAX_WIDE)
   int prefill_skinny_rows = 128;
   int prefill_skinny_hidden_max = 8192;   // (the 2048 limit of the panel-kernel form is gone with the LDS-DMA ring kernel: Llama-3.2-3B S = 48 3.12 -> 2.98 ms, Mistral-7B 5.36 / 5.38)
-  int skinny_dma = 1;          // option skinny.dma: products on stored 16-bit terms (two terms) run on the LDS-DMA ring kernel (kernels/skinny_dma.h) from skinny.dma_rows rows
-  int skinny_dma_rows = 1;
+  int skinny_dma = 1;          // option skinny.dma: products on stored 16-bit terms (two terms) run on the LDS-DMA ring kernel (kernels/skinny_dma.h)
   int skinny_dma_oproj = 2;    // option skinny.dma_oproj: the matrix-core attention of a batched step writes 16-bit terms, the o_proj product takes that kernel
-  // option skinny.dma_qkv: batches of up to 32 rows prepare the QKV / lm_head activations as stored terms as well (the 33-64-row form), so that the QKV product takes
-  // that kernel: 1 = from 17 rows, 2 = from 5.  Llama-3.2-1B ms/step 1 / 2: B = 5 0.898 / 0.867, 8 0.905 / 0.880, 12 0.962 / 0.939, 16 1.022 / 1.001; context 2k B = 8
-  // 1.071 / 1.050; Mistral-7B B = 8 3.587 / 3.556, B = 16 3.876 / 3.909
-  int skinny_dma_qkv = 2;
-  int skinny_dma_nbw = 0;      // option skinny.dma_nbw: weight blocks per wave of that kernel (0: as the panel kernel's geometry, 1 = 64-row, 2 = 128-row workgroups)
   int decode_step_rows = 128;   // option decode.step_rows: rows of a batch that share one pass over the weights in the matrix-core step (32: round 2; 128: eight blocks on the LDS-DMA ring kernel — Llama-3.2-1B B = 128 2.99 -> 2.32 ms/step, Mistral-7B 13.25 -> 10.47)
   int prefill_skinny = 1;    // option prefill.skinny: 0 sends prompts of <= 32 rows through the tiled GEMMs as well
-  int skinny_wgs = 256;      // option skinny.wgs: workgroups a skinny product aims for by splitting K
-  int skinny_gu_split = 0;   // option skinny.gu_split: 0 keeps the gate_up product unsplit (siluMul in its epilogue, one launch less)
-  int skinny_cfg_mid = 0;    // option skinny.cfg_mid: tile geometry (kernels/skinny.h SkinnyCfg) of the products that do not oversubscribe the chip
-  int skinny_cfg_force = -1; // option skinny.cfg: force one geometry for every product (experiments)
   // decode batches of at least this many rows run their Linears as skinny MFMA GEMMs (option decode.mfma_min_batch).  Measured ms/step,
   // GEMV row groups vs matrix cores: Llama-3.2-1B B = 2 0.794 / 0.991, B = 3 ~1.45 / 1.003, B = 4 1.042 / 1.007; Mistral-7B B = 4 5.04 / 4.01
   int decode_mfma_min = 3;
@@ -281,29 +269,18 @@ struct tgx_ctx {
   int prefill_min_rows = 4;  // prompts shorter than this go through the decode kernels, 4 positions per pass (set in tgx_create)
   int prefill_f32_min_rows = 16;   // fp32 storage: prompts from this length on take the f32-input MFMA GEMMs (64-row tiles; option prefill.f32_min_rows)
   int gemm_tm = 0;           // experiment: force the GEMM row tile (64 / 128); 0 = by the number of tiles
-  // option prefill.gemm_dma: bit 0 / 1 = unsplit prefill GEMMs take their tiles by LDS-DMA (kernels/gemm_dma.h), bit 2 = the wide product (gate_up / c_fc)
-  // on the 8-wave 256 x 256 three-stage kernel; bits 4-7 / 8-11 = ring geometry of the 128-row / 64-row tiles (k per stage, stages).  0 = the register-staged
-  // gemm_x2_kernel everywhere (round 1).  Default 7 | k32x2 << 4 | k64x2 << 8: Llama-3.2-1B 2048 tokens 11.4-11.7 -> 10.0-10.3 ms (tools/dma_sweep.py)
-  // bit 3 = the N = hidden products (o_proj, down) on the 8-wave 128 x 128 kernel with the K step split between wave pairs when their tiles number ~one per CU
-  int gemm_dma = 15 | (1 << 4) | (2 << 8);
-  int wide_8k_max = 8;       // option prefill.wide_8k_max: ... while its tiles number at most this many half-chips (8 = 4 tiles per CU: everything below the 256 x 256 kernel's range;
-                             // 3 / 8: Llama-3.2-1B S = 512 3.62 / 3.44 ms, 768 5.06 / 4.94; Mistral-7B S = 256 11.16 / 10.81, 512 22.5 / 21.4)
   int debug_attn = 0;        // experiment: AttnArgs.dbg
   int attn_gmax = 0;         // experiment: query heads per attention workgroup (default 2)
   int attn_direct_nw4 = 0;   // option attn.direct_nw4: contexts up to this many keys run the direct attention form with four waves per head (set in tgx_create)
   bool attn_nw4 = false;     // mode of the launches being issued / captured
   int attn_raw_fuse = 2;     // option attn.raw_fuse: that form also finishes the QKV product (slab sums, bias, q / k norm, RoPE, cache append) in its prologue
-  int attn_batch_nw8 = 1;    // option attn.batch_nw8: eight waves per workgroup of that form while its workgroups number at most one per CU (Llama-3.2-1B B = 17 1.052 -> 1.030 ms/step, 32 1.189 -> 1.171; context 2k B = 17 1.239 -> 1.183; 2 = always: B = 64 1.518 -> 1.582)
-  int attn_batch_la = 0;     // option attn.batch_la: K / V look-ahead registers of that form at head_dim 64 (-1: only while its workgroups number at most one per CU)
   int attn_batch_mfma = 17;  // option attn.batch_mfma: batches of this many rows and more run their direct-form attention on the matrix cores (0 = never)
-  int attn_direct_g = 1;     // option attn.direct_g: 1 = heads per workgroup of the direct attention form by batch rows (2 from 12 rows, 4 from 24 at head_dim 64), 0 = always one, -g = force g
   int attn_direct_max = 384; // contexts up to this many keys take the one-workgroup-per-head attention (no split, no combine launch); set in tgx_create
   bool attn_direct = false;  // mode of the launches being issued / captured
   // contexts from attn_mfma_min keys on take the MFMA decode attention (kernels/attn_decode_mfma.h); like the direct form it is a mode of the
   // captured step: the graphs are re-captured when a decode call crosses the limit.  Not for Qwen3's fused q/k norm, not for fp32 storage.
   int skinny_terms = 1;            // option skinny.terms: batches of 17-32 rows take gate_up's activations as terms prepared once per layer (round 3)
   int skinny_ksplit = 1;           // wide products (gate_up, lm_head) of the batched step on the barrier-free K-split kernel (option skinny.ksplit)
-  int defer_min_rows = 129;        // option prefill.defer_min_rows (192 until the row-wise norm launch loaded its slabs eight at a time: Llama-3.2-1B S = 160 2.51 -> 2.41 ms, 191 2.54 -> 2.46; Mistral-7B S = 160 9.90 -> 9.65)
   int defer_reduce = 1;            // split-K slabs of the prefill's N = hidden / QKV products are summed by the next row-wise kernel (option prefill.defer_reduce)
   int attn_mfma_min = -1;          // -1: the measured crossover of the geometry (attn_mfma_threshold); option attn.mfma_min overrides
   bool attn_mfma = false;
@@ -317,9 +294,7 @@ struct tgx_ctx {
   // (ModelLlama.h:62) that has a price: the matrix-core products then take ONE 16-bit term per activation.  ws_zero: the "lo term"
   // every stored-term product reads in this mode
   int act16 = 0, act16_kernels = 1;
-  int prefill_terms_rows = 16;   // option prefill.terms_rows: skinny prompts with more rows than this take their norm-fused products on stored 16-bit terms (round 4: from 17 rows instead of 33 — Mistral-7B S = 20 / 32 4.47 / 4.67 -> 3.94 / 4.30 ms, Llama-3.2-1B within noise)
   int wide_8k_eff = 76;      // (Llama-3.2-1B S = 1152 7.28 -> 6.78 ms, 1280 7.52 -> 6.95, 1400 8.45 -> 8.14; at 87 % fill the 256 x 256 tiles win again) option prefill.wide_8k_eff (per cent): gate_up on 128 x 128 tiles when the 256 x 256 tiling's rounds are filled less than this
-  int skinny_terms_above = 2;  // (round 4: 2 instead of 4 — Llama-3.2-1B B = 3 / 4 0.822 / 0.823 -> 0.794 / 0.798 ms per step) option skinny.terms_above: batched steps with more rows than this prepare stored terms for the norm-fused products (with skinny.dma_qkv 2)
   int qkv_nosplit = 1;       // option prefill.qkv_nosplit: the balanced QKV launch instead of K slabs when it alone covers 3/4 of the chip
   int splitk_8k = 1;         // option prefill.splitk_8k: N = hidden products of 129-1500-row prompts as 2-4 K slabs on the eight-wave LDS-DMA kernel
   bf16_t* ws_zero = nullptr;
@@ -575,7 +550,6 @@ int ensure_extend_rg_ws(tgx_ctx* c, RaggedPass& p);
 void launch_attn_prefill(tgx_ctx* c, const tgx::AttnPrefillArgs& a, bool allow_lean, const unsigned short* anc = nullptr);   // anc: a token tree's device masks (TreePass)
 void launch_rope_kv_split(tgx_ctx* c, const tgx::RopeKvArgs& a, int S, const int* depth = nullptr);                           // depth: a token tree's device depths (TreePass)
 void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, int nsplit, bool third = false);
-void launch_silu_slab_reduce(tgx_ctx* c, int M, int I, int nsplit);
 void launch_embed_rows(tgx_ctx* c, const long long* ids, float* X, int M, int S);
 // ---- prefill_f32.hip (kernels/gemm_f32.h)
 int ensure_f32_part(tgx_ctx* c, int rows);

@@ -53,18 +53,26 @@ int ensure_ws_part(tgx_ctx* c, size_t need) {
 // The gate_up product on full 128-byte lines (kernels/gemm_dma.h gemm_dma8i_kernel): taken where the 256 x 256 kernel would be, on the
 // default contract; the producing norm launch then writes the two terms interleaved per k32 block (rmsnorm_split_kernel `inter`) into ws_out, which is idle
 // between the RoPE / cache-append launch and the next layer's QKV product.
+// split-K slabs wait for their row-wise consumer from this many rows on (192 until the row-wise norm launch loaded its slabs eight at a time: Llama-3.2-1B
+// S = 160 2.51 -> 2.41 ms, 191 2.54 -> 2.46; Mistral-7B S = 160 9.90 -> 9.65)
+constexpr int DEFER_MIN_ROWS = 129;
+// the eight-wave 128 x 128 gate_up kernel while its tiles number at most this many half-chips (8 = 4 tiles per CU: everything below the 256 x 256 kernel's range;
+// 3 / 8: Llama-3.2-1B S = 512 3.62 / 3.44 ms, 768 5.06 / 4.94; Mistral-7B S = 256 11.16 / 10.81, 512 22.5 / 21.4)
+constexpr int WIDE_8K_MAX = 8;
 static bool gemm_full_lines(const tgx_ctx* c, int epi, int M, int N, int K) {
-  if (epi != tgx::GEMM_SILU || c->gpt2 || (c->act16 && c->ws_zero) || !(c->gemm_dma & 4) || K % 64 != 0 || N % 256 != 0) return false;
+  if (epi != tgx::GEMM_SILU || c->gpt2 || (c->act16 && c->ws_zero) || K % 64 != 0 || N % 256 != 0) return false;
   const tgx_model_desc& d = c->d;
   if ((size_t)d.heads * d.head_dim + 2 * (size_t)d.kv_heads * d.head_dim < (size_t)K) return false;      // ws_out holds [M][2 K] 16-bit terms
   const int t256 = ((N + 255) / 256) * ((M + 255) / 256), r256 = (t256 + c->num_cus - 1) / c->num_cus;
-  const bool ragged256 = c->wide_8k_eff > 0 && (c->gemm_dma & 8) && t256 >= c->num_cus && 100 * t256 < c->wide_8k_eff * r256 * c->num_cus;
+  const bool ragged256 = c->wide_8k_eff > 0 && t256 >= c->num_cus && 100 * t256 < c->wide_8k_eff * r256 * c->num_cus;
   return t256 >= c->num_cus && !ragged256;
 }
 
 static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_, float* C, int M, int N, int K, int ldc, bool three_terms = false,
                  const bf16_t* a_hi = nullptr, const bf16_t* a_lo = nullptr, int three_from = 0, int* defer = nullptr, bool a_inter = false) {
   if (defer) *defer = 1;
+  // every kernel below steps K by 64 (tgx::GBK); prefill_shapes_ok admits only models whose hidden, heads * head_dim and inter — the K of every caller — are such
+  if (K % 64 != 0) { c->launch_fault = "internal: launch_gemm with K not a multiple of 64"; return; }
   if (a_inter) {       // A arrives interleaved in a_hi (the caller asked gemm_full_lines first)
     tgx::GemmArgs g{};
     g.A_hi = a_hi; g.A_lo = nullptr; g.A_lo2 = nullptr; g.inter = N / 2; g.out_hi = c->ws_hh; g.out_lo = c->ws_hl;
@@ -95,14 +103,14 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
   const int ntiles = (int)(grid.x * grid.y), ktiles = K / tgx::GBK;
   int nsplit = 1;
   // (the balanced QKV launch below fills the chip by itself from 1024 rows on at hidden 2048: 128 + 128 workgroups of equal work; Llama-3.2-1B S = 1024 5.16 -> 5.06 ms — no slabs then; option prefill.qkv_nosplit)
-  const bool qkv_bal = (c->gemm_dma & 3) && three_terms && epi == tgx::GEMM_STORE && three_from > 0 && three_from % tgx::GBN == 0 && N > three_from && K % 64 == 0 && M >= 128;
+  const bool qkv_bal = three_terms && epi == tgx::GEMM_STORE && three_from > 0 && three_from % tgx::GBN == 0 && N > three_from && M >= 128;
   const int qkv_wgs = qkv_bal ? (three_from / tgx::GBN) * ((M + 127) / 128) + ((N - three_from + tgx::GBN - 1) / tgx::GBN) * ((M + 63) / 64) : 0;
   const bool qkv_nosplit = qkv_bal && c->qkv_nosplit && qkv_wgs >= c->num_cus;
-  if (c->gemm_splitk && ntiles < c->num_cus && K % tgx::GBK == 0 && !qkv_nosplit) nsplit = std::min(std::min(16, ktiles), (2 * c->num_cus + ntiles - 1) / ntiles);
+  if (c->gemm_splitk && ntiles < c->num_cus && !qkv_nosplit) nsplit = std::min(std::min(16, ktiles), (2 * c->num_cus + ntiles - 1) / ntiles);
   // N = hidden products of a 129-1500-row prompt (round 4, option prefill.splitk_8k): their 128 x 128 tiles number less than a chip (Llama-3.2-1B S = 1024: 128 tiles on 256
   // CUs, 84 us per product against 104 at twice the rows) — the eight-wave LDS-DMA kernel over 2-4 K slabs instead of 64-row register-staged slabs or a half-empty chip
   bool part_8k = false;
-  if (c->gemm_splitk && c->splitk_8k && (c->gemm_dma & 8) && K % 64 == 0 && !three_terms && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE) && M > 128) {
+  if (c->gemm_splitk && c->splitk_8k && !three_terms && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE) && M > 128) {
     const int t128 = ((N + 127) / 128) * ((M + 127) / 128);
     // slabs z = 2..4 that shorten the critical path: rounds of workgroups x 1 / z of the K loop against one round of whole tiles (160 tiles on 256 CUs: z = 3 -> 2 rounds of a
     // third = 0.67; 128 tiles: z = 2 -> 0.5); taken from 0.8 down (the slabs cost a pass over z x M x N floats)
@@ -116,7 +124,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
   // K >> N (`down`) on 128 x 256 tiles x 2 K slabs: a third fewer operand lines per output than the 128 x 128 kernel, which waits for them (kernels/gemm_dma.h
   // gemm_dma8n_kernel).  Needs a consumer that sums pending slabs (`defer`) and two rounds of workgroups (prefill.wide_n_min, in chips): at one
   // round (Llama-3.2-1B S = 2048: 256 workgroups) it ties with the one-slab 128 x 128 launch (141 vs 140-146 us) and costs a second slab; Mistral-7B S = 2048 56.1 -> 54.1 ms
-  if (nsplit == 1 && defer && c->defer_reduce && epi == tgx::GEMM_RESIDUAL && (c->gemm_dma & 8) && !three_terms && !one && K >= 2 * N && K % 128 == 0 && N % 256 == 0 &&
+  if (nsplit == 1 && defer && c->defer_reduce && epi == tgx::GEMM_RESIDUAL && !three_terms && !one && K >= 2 * N && K % 128 == 0 && N % 256 == 0 &&
       2 * (N / 256) * ((M + 127) / 128) >= c->wide_n_min * c->num_cus) {
     if (!ensure_ws_part(c, (size_t)2 * M * N * 4)) {      // (no slabs: the paths below)
       g.part = c->ws_part; g.nsplit = 2; g.interleave = 0; g.k_per = K / 2;
@@ -128,9 +136,9 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
   }
   // one tile per CU on the eight-wave 128 x 128 kernel, a consumer that can take a pending slab: store the product, let the consumer add it (see `defer` above)
   const int t128u = ((N + 127) / 128) * ((M + 127) / 128);
-  const bool store_slab = nsplit == 1 && defer && c->defer_reduce && epi == tgx::GEMM_RESIDUAL && (c->gemm_dma & 8) && K % 64 == 0 && !three_terms &&
+  const bool store_slab = nsplit == 1 && defer && c->defer_reduce && epi == tgx::GEMM_RESIDUAL && !three_terms &&
                           2 * t128u >= c->num_cus && 2 * t128u <= 3 * c->num_cus &&
-                          !((c->gemm_dma & 4) && ((N + 255) / 256) * ((M + 255) / 256) >= c->num_cus);
+                          ((N + 255) / 256) * ((M + 255) / 256) < c->num_cus;
   if ((nsplit > 1 || store_slab) && ensure_ws_part(c, (size_t)nsplit * M * N * 4)) nsplit = 1;
   if (store_slab && c->ws_part_bytes >= (size_t)M * N * 4) {
     g.part = c->ws_part; g.nsplit = 1; g.interleave = 0; g.k_per = K;
@@ -155,7 +163,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
       const size_t lds8 = (size_t)3 * 3 * 128 * 64 * 2;
       TGX_DT16_SWITCH(c->dt, if (one_k) hipLaunchKernelGGL((tgx::gemm_dma8k_kernel<DT, tgx::GEMM_PARTIAL, false>), g8, b8, lds8, c->stream, g); else hipLaunchKernelGGL((tgx::gemm_dma8k_kernel<DT, tgx::GEMM_PARTIAL>), g8, b8, lds8, c->stream, g);)
     }
-    const bool dma_part = !part_8k && M <= 64 && (c->gemm_dma & 3) && g.k_per % 64 == 0 && K % 64 == 0;
+    const bool dma_part = !part_8k && M <= 64 && g.k_per % 64 == 0;
     if (dma_part) {
       const int mi = (small || M <= 64) ? 1 : 2;
       const int dbk = (mi == 2 && three_terms) ? 32 : 64;
@@ -170,7 +178,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
       if (dma_part || part_8k) {}
       else if (small) hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_PARTIAL, 1>), gz, blk, dyn, c->stream, g);
       else hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_PARTIAL, 2>), gz, blk, dyn, c->stream, g);
-      if (defer && c->defer_reduce && M >= c->defer_min_rows && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE)) { *defer = nsplit; }   // with few rows the row-wise consumers are too few workgroups to sum 16 slabs quickly (round 2, S = 64: 1.82 -> 1.87 ms; S = 256: 2.80 -> 2.70)
+      if (defer && c->defer_reduce && M >= DEFER_MIN_ROWS && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE)) { *defer = nsplit; }   // with few rows the row-wise consumers are too few workgroups to sum 16 slabs quickly (round 2, S = 64: 1.82 -> 1.87 ms; S = 256: 2.80 -> 2.70)
       else if (epi == tgx::GEMM_SILU) hipLaunchKernelGGL((tgx::gemm_splitk_reduce_kernel<DT, tgx::GEMM_SILU>), rg, blk, 0, c->stream, g);
       else if (epi == tgx::GEMM_GELU) hipLaunchKernelGGL((tgx::gemm_splitk_reduce_kernel<DT, tgx::GEMM_GELU>), rg, blk, 0, c->stream, g);
       else if (epi == tgx::GEMM_RESIDUAL) hipLaunchKernelGGL((tgx::gemm_splitk_reduce_kernel<DT, tgx::GEMM_RESIDUAL>), rg, blk, 0, c->stream, g);
@@ -180,8 +188,8 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
   // (a prompt whose 256 x 256 tiles leave the last round of workgroups mostly empty — 1152 rows at intermediate 8192: 320 tiles = 1.25 rounds, the time of 2048 rows — takes the
   //  128 x 128 kernel below instead: 1152 tiles = 4.5 rounds; option prefill.wide_8k_eff = per cent of the last round's fill below which that happens)
   const int t256 = ((N + 255) / 256) * ((M + 255) / 256), r256 = (t256 + c->num_cus - 1) / c->num_cus;
-  const bool ragged256 = c->wide_8k_eff > 0 && epi == tgx::GEMM_SILU && (c->gemm_dma & 8) && t256 >= c->num_cus && 100 * t256 < c->wide_8k_eff * r256 * c->num_cus;
-  if ((c->gemm_dma & 4) && K % 64 == 0 && !three_terms && (epi == tgx::GEMM_SILU || epi == tgx::GEMM_GELU) && t256 >= c->num_cus && !ragged256) {
+  const bool ragged256 = c->wide_8k_eff > 0 && epi == tgx::GEMM_SILU && t256 >= c->num_cus && 100 * t256 < c->wide_8k_eff * r256 * c->num_cus;
+  if (!three_terms && (epi == tgx::GEMM_SILU || epi == tgx::GEMM_GELU) && t256 >= c->num_cus && !ragged256) {
     // the wide product (gate_up / c_fc) with enough 256 x 256 tiles to fill the chip: 8 waves, three-stage LDS-DMA ring
     const dim3 g8((N + 255) / 256, (M + 255) / 256), b8(512);
     const size_t lds8 = (size_t)3 * 3 * 256 * 32 * 2;
@@ -190,7 +198,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
       else hipLaunchKernelGGL((tgx::gemm_dma8_kernel<DT, tgx::GEMM_GELU>), g8, b8, lds8, c->stream, g);)
     return;
   }
-  if ((c->gemm_dma & 4) && K % 64 == 0 && !three_terms && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE) &&
+  if (!three_terms && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE) &&
       ((N + 255) / 256) * ((M + 255) / 256) >= c->num_cus) {
     // the N = hidden products of a prompt long enough to give every CU a 256 x 256 tile (Llama-3.2-1B from 8192 rows, Mistral-7B from 4096): the wide
     // product's kernel with the plain fp32 epilogue 
@@ -201,18 +209,18 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
       else { if (one_k) hipLaunchKernelGGL((tgx::gemm_dma8_kernel<DT, tgx::GEMM_STORE, false>), g8, b8, lds8, c->stream, g); else hipLaunchKernelGGL((tgx::gemm_dma8_kernel<DT, tgx::GEMM_STORE>), g8, b8, lds8, c->stream, g); })
     return;
   }
-  if ((c->gemm_dma & 8) && K % 64 == 0 && !three_terms && epi == tgx::GEMM_SILU) {
+  if (!three_terms && epi == tgx::GEMM_SILU) {
     // the wide product of a prompt too short for 256 x 256 tiles (129-384 rows: 128-384 tiles of 128 x 128): the eight-wave kernel with the K step split between
     // wave pairs instead of the four-wave one (option prefill.wide_8k: Llama-3.2-1B S = 256 gate_up 61 us per layer)
     const int t128 = ((N + 127) / 128) * ((M + 127) / 128);
-    if (2 * t128 >= c->num_cus && (2 * t128 <= c->wide_8k_max * c->num_cus || ragged256)) {
+    if (2 * t128 >= c->num_cus && (2 * t128 <= WIDE_8K_MAX * c->num_cus || ragged256)) {
       const dim3 g8((N + 127) / 128, (M + 127) / 128), b8(512);
       const size_t lds8 = (size_t)3 * 3 * 128 * 64 * 2;
       TGX_DT16_SWITCH(c->dt, if (one_k) hipLaunchKernelGGL((tgx::gemm_dma8k_kernel<DT, tgx::GEMM_SILU, false>), g8, b8, lds8, c->stream, g); else hipLaunchKernelGGL((tgx::gemm_dma8k_kernel<DT, tgx::GEMM_SILU>), g8, b8, lds8, c->stream, g);)
       return;
     }
   }
-  if ((c->gemm_dma & 8) && K % 64 == 0 && !three_terms && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE)) {
+  if (!three_terms && (epi == tgx::GEMM_RESIDUAL || epi == tgx::GEMM_STORE)) {
     // N = hidden products whose 128 x 128 tiles number between half a chip and a chip and a half: eight waves per tile, K step split between wave pairs
     const int t128 = ((N + 127) / 128) * ((M + 127) / 128);
     if (2 * t128 >= c->num_cus && 2 * t128 <= 3 * c->num_cus) {
@@ -224,7 +232,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
       return;
     }
   }
-  if ((c->gemm_dma & 3) && three_terms && epi == tgx::GEMM_STORE && three_from > 0 && three_from % tgx::GBN == 0 && N > three_from && K % 64 == 0 &&
+  if (three_terms && epi == tgx::GEMM_STORE && three_from > 0 && three_from % tgx::GBN == 0 && N > three_from &&
       (N - three_from) % 64 == 0 && three_from / tgx::GBN == (N - three_from) / 64 && 2 * (three_from / tgx::GBN) * ((M + 127) / 128) >= c->num_cus) {
     // ... with as many 128-column Q tiles as 64-column K | V tiles (q_dim = 4 kv_dim) and at least half a chip of workgroups: eight waves per workgroup, the Q tile and the
     // K | V tile of a row block on ONE staging of the activation lines (kernels/gemm_dma.h gemm_dma_qkv8_kernel)
@@ -240,7 +248,7 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
     TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL((tgx::gemm_dma_qkv8_kernel<DT>), dim3(nwg), dim3(512), (size_t)2 * (3 * 128 + 128 + 64) * 64 * 2, c->stream, g))
     return;
   }
-  if ((c->gemm_dma & 3) && three_terms && epi == tgx::GEMM_STORE && three_from > 0 && three_from % tgx::GBN == 0 && N > three_from && K % 64 == 0 && M >= 128) {
+  if (three_terms && epi == tgx::GEMM_STORE && three_from > 0 && three_from % tgx::GBN == 0 && N > three_from && M >= 128) {
     // the QKV product of a bf16 prompt: Q columns as two-term 128-row tiles, K / V columns as three-term 64-row tiles, ONE launch with
     // equal work per workgroup pair (kernels/gemm_dma.h gemm_dma_qkv_kernel)
     const int nq = (three_from / tgx::GBN) * ((M + 127) / 128), nkv = ((N - three_from + tgx::GBN - 1) / tgx::GBN) * ((M + 63) / 64);
@@ -248,32 +256,20 @@ static void launch_gemm(tgx_ctx* c, int epi, const ebyte* B_, const ebyte* bias_
     TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL((tgx::gemm_dma_qkv_kernel<DT, 32, 2>), dim3(nq + nkv), blk, ldsq, c->stream, g))
     return;
   }
-  if ((c->gemm_dma & 3) && K % 64 == 0) {     // operand tiles by LDS-DMA into a two-stage ring (kernels/gemm_dma.h): one barrier per K step
-    // geometry per tile height: 128-row tiles k = 32, 64-row tiles k = 64 (round 2's sweep, profiles/r02_prefill_dma_sweep.txt: deeper rings lose 4-20 % to occupancy
-    // here — the eight-wave kernels are where they pay; the other geometries went with the option bits that selected them in round 6)
-    const size_t lds = small ? tgx::gemm_dma_lds_bytes(1, three_terms, 64, 2) : tgx::gemm_dma_lds_bytes(2, three_terms, 32, 2);
+  // every other product: operand tiles by LDS-DMA into a two-stage ring (kernels/gemm_dma.h), one barrier per K step
+  // geometry per tile height: 128-row tiles k = 32, 64-row tiles k = 64 (round 2's sweep, profiles/r02_prefill_dma_sweep.txt: deeper rings lose 4-20 % to occupancy
+  // here — the eight-wave kernels are where they pay; the other geometries went with the option bits that selected them in round 6, the unsplit register-staged
+  // gemm_x2_kernel of round 1 with the family mask itself: Llama-3.2-1B 2048 tokens 11.4-11.7 -> 10.0-10.3 ms)
+  static_assert(tgx::gemm_dma_lds_bytes(1, true, 64, 2) <= 160 * 1024 && tgx::gemm_dma_lds_bytes(2, true, 32, 2) <= 160 * 1024, "the two-stage rings fit the LDS of a CU");
+  const size_t lds = small ? tgx::gemm_dma_lds_bytes(1, three_terms, 64, 2) : tgx::gemm_dma_lds_bytes(2, three_terms, 32, 2);
 #define TGX_DMA(EPI_, MI_) do { if ((MI_) == 1) hipLaunchKernelGGL((tgx::gemm_dma_kernel<DT, EPI_, 1, 64, 2>), grid, blk, lds, c->stream, g); \
                                 else hipLaunchKernelGGL((tgx::gemm_dma_kernel<DT, EPI_, 2, 32, 2>), grid, blk, lds, c->stream, g); } while (0)
-    if (lds <= 160 * 1024) {
-      TGX_DT16_SWITCH(c->dt,
-        if (epi == tgx::GEMM_SILU) TGX_DMA(tgx::GEMM_SILU, 2);
-        else if (epi == tgx::GEMM_GELU) TGX_DMA(tgx::GEMM_GELU, 2);
-        else if (epi == tgx::GEMM_RESIDUAL) { if (small) TGX_DMA(tgx::GEMM_RESIDUAL, 1); else TGX_DMA(tgx::GEMM_RESIDUAL, 2); }
-        else { if (small) TGX_DMA(tgx::GEMM_STORE, 1); else TGX_DMA(tgx::GEMM_STORE, 2); })
-      return;
-    }
-#undef TGX_DMA
-  }
   TGX_DT16_SWITCH(c->dt,
-    if (epi == tgx::GEMM_SILU) hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_SILU, 2>), grid, blk, dyn, c->stream, g);
-    else if (epi == tgx::GEMM_GELU) hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_GELU, 2>), grid, blk, dyn, c->stream, g);
-    else if (small) {
-      if (epi == tgx::GEMM_RESIDUAL) hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_RESIDUAL, 1>), grid, blk, dyn, c->stream, g);
-      else hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_STORE, 1>), grid, blk, dyn, c->stream, g);
-    } else {
-      if (epi == tgx::GEMM_RESIDUAL) hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_RESIDUAL, 2>), grid, blk, dyn, c->stream, g);
-      else hipLaunchKernelGGL((tgx::gemm_x2_kernel<DT, tgx::GEMM_STORE, 2>), grid, blk, dyn, c->stream, g);
-    })
+    if (epi == tgx::GEMM_SILU) TGX_DMA(tgx::GEMM_SILU, 2);
+    else if (epi == tgx::GEMM_GELU) TGX_DMA(tgx::GEMM_GELU, 2);
+    else if (epi == tgx::GEMM_RESIDUAL) { if (small) TGX_DMA(tgx::GEMM_RESIDUAL, 1); else TGX_DMA(tgx::GEMM_RESIDUAL, 2); }
+    else { if (small) TGX_DMA(tgx::GEMM_STORE, 1); else TGX_DMA(tgx::GEMM_STORE, 2); })
+#undef TGX_DMA
 }
 
 // ---- the key-split attention of a continuation (kernels/attn_extend.h; option extend.attn_splits).  Splits of a pass of S positions from `past`: 0 = the per-row
@@ -585,13 +581,6 @@ void launch_norm_terms(tgx_ctx* c, float* x, const ebyte* norm_w, int M, int H, 
   TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::rmsnorm_split_kernel<DT>, dim3(M), dim3(256), 0, c->stream, x, reinterpret_cast<const bf16_t*>(norm_w), c->d.norm_eps, H,
                                           c->ws_ah, c->ws_al, third ? c->ws_al2 : (bf16_t*)nullptr, (const float*)(nsplit > 1 ? c->ws_part : nullptr), nsplit, (long long)M * H, (const bf16_t*)nullptr))
 }
-// split-K slabs of a gate_up product -> siluMul -> 16-bit terms (ws_hh / ws_hl), z-ordered sums
-void launch_silu_slab_reduce(tgx_ctx* c, int M, int I, int nsplit) {
-  tgx::GemmArgs g{};
-  g.part = c->ws_part; g.nsplit = nsplit; g.M = M; g.N = 2 * I; g.inter = I; g.out_hi = c->ws_hh; g.out_lo = c->ws_hl;
-  const dim3 rg((unsigned)(((size_t)M * I + 255) / 256));
-  TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL((tgx::gemm_splitk_reduce_kernel<DT, tgx::GEMM_SILU>), rg, dim3(256), 0, c->stream, g))
-}
 void launch_embed_rows(tgx_ctx* c, const long long* ids, float* X, int M, int S) {
   TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::embed_rows_kernel<DT>, dim3(M), dim3(256), 0, c->stream, ids, (const bf16_t*)c->embed, X, c->d.hidden, S, (long long)c->d.max_ctx))
 }
@@ -771,10 +760,6 @@ void launch_score_tiled(tgx_ctx* c, const ScoreCall& sc) {
 
 // dynamic LDS sizes of the tiled GEMMs
 int prefill_set_attrs(tgx_ctx* c) {
-  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_x2_kernel<tgx::DT_BF16, tgx::GEMM_STORE, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, tgx::GBM * tgx::GLD * 2));
-  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_x2_kernel<tgx::DT_BF16, tgx::GEMM_RESIDUAL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, tgx::GBM * tgx::GLD * 2));
-  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_x2_kernel<tgx::DT_F16, tgx::GEMM_STORE, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, tgx::GBM * tgx::GLD * 2));
-  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_x2_kernel<tgx::DT_F16, tgx::GEMM_RESIDUAL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, tgx::GBM * tgx::GLD * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_x2_kernel<tgx::DT_BF16, tgx::GEMM_PARTIAL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, tgx::GBM * tgx::GLD * 2));
   HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_x2_kernel<tgx::DT_F16, tgx::GEMM_PARTIAL, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, tgx::GBM * tgx::GLD * 2));
 #define TGX_DMA_ATTR1(DT_, EPI_, MI_, BK_, NS_) HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::gemm_dma_kernel<DT_, EPI_, MI_, BK_, NS_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min<size_t>(160 * 1024, tgx::gemm_dma_lds_bytes(MI_, true, BK_, NS_))));

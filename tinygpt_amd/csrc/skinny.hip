@@ -9,7 +9,7 @@
 #include "kernels/skinny_dma.h"
 
 // ---- batched decode on the matrix cores (kernels/skinny.h) ---------------------------------------------------------------------------
-// the (epilogue, terms, activation source) combinations the batched step uses; every one exists for 2 dtypes x MB 1,2 x NBW 1,2
+// the (epilogue, terms, activation source) combinations the batched step uses; every one exists for 2 dtypes x MB 1,2 x geometries 0,2 (MB 4: skinny_set_attr_dt)
 #define TGX_SKINNY_COMBOS(X)                                                                                                   \
   X(tgx::GEMM_PARTIAL, 3, 2) X(tgx::GEMM_STORE, 3, 2) X(tgx::GEMM_PARTIAL, 2, 2) X(tgx::GEMM_STORE, 2, 2) X(tgx::GEMM_SILU, 2, 2) \
   X(tgx::GEMM_PARTIAL, 2, 1) X(tgx::GEMM_RESIDUAL, 2, 1) X(tgx::GEMM_PARTIAL, 2, 0) X(tgx::GEMM_RESIDUAL, 2, 0) X(tgx::GEMM_SILU, 2, 0) X(tgx::GEMM_STORE, 2, 0) \
@@ -18,7 +18,7 @@
 template <int DT, int EPI, int NT, int ASRC>
 static int skinny_set_attr_dt(tgx_ctx* c) {
 #define TGX_SK_A(MB_, CFG_) HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::skinny_gemm_kernel<DT, EPI, MB_, NT, CFG_, ASRC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tgx::skinny_lds_bytes(MB_, NT, CFG_)));
-  TGX_SK_A(1, 0) TGX_SK_A(1, 1) TGX_SK_A(1, 2) TGX_SK_A(2, 0) TGX_SK_A(2, 1) TGX_SK_A(2, 2)
+  TGX_SK_A(1, 0) TGX_SK_A(1, 2) TGX_SK_A(2, 0) TGX_SK_A(2, 2)
   if constexpr (ASRC == 0) { TGX_SK_A(4, 0) TGX_SK_A(4, 1) TGX_SK_A(4, 2) }
   if constexpr (ASRC == 1) { TGX_SK_A(4, 1) }
 #undef TGX_SK_A
@@ -44,8 +44,9 @@ static void skinny_dispatch(tgx_ctx* c, dim3 grid, int mb, int cfg, const tgx::G
       else if constexpr (ASRC == 1) TGX_SK_L(4, 1);             // fp32 rows split on the way (the o_proj product of a decode step): 128-k panels only
       else c->launch_fault = "internal: 33-64-row skinny GEMM takes stored 16-bit terms or plain fp32 rows";
     }
-    else if (mb == 2) { if (cfg == 2) TGX_SK_L(2, 2); else if (cfg == 1) TGX_SK_L(2, 1); else TGX_SK_L(2, 0); }
-    else { if (cfg == 2) TGX_SK_L(1, 2); else if (cfg == 1) TGX_SK_L(1, 1); else TGX_SK_L(1, 0); })
+    else if (cfg == 1) c->launch_fault = "internal: the 128-k panel geometry serves four activation blocks only";
+    else if (mb == 2) { if (cfg == 2) TGX_SK_L(2, 2); else TGX_SK_L(2, 0); }
+    else { if (cfg == 2) TGX_SK_L(1, 2); else TGX_SK_L(1, 0); })
 #undef TGX_SK_L
 }
 
@@ -94,6 +95,7 @@ struct SkinnyCall {
   bool allow_split = true;
 };
 }  // namespace
+constexpr int SKINNY_WGS = 256;      // workgroups a skinny product aims for by splitting K (two per CU: the bytes in flight per CU are what the stream rate follows)
 static int launch_skinny(tgx_ctx* c, const SkinnyCall& k) {
   tgx::GemmArgs g{};
   g.A_hi = k.a_hi; g.A_lo = k.a_lo; g.A_lo2 = k.a_lo2; g.A_f32 = k.a_f32; g.lda = k.lda;
@@ -107,17 +109,16 @@ static int launch_skinny(tgx_ctx* c, const SkinnyCall& k) {
   g.inter = k.N / 2; g.out_hi = c->ws_hh; g.out_lo = c->ws_hl;
   g.B = reinterpret_cast<const bf16_t*>(k.W); g.bias = reinterpret_cast<const bf16_t*>(k.bias); g.C = k.C; g.M = k.M; g.N = k.N; g.K = k.K; g.ldc = k.ldc;
   const int mb = k.M > 64 ? 8 : (k.M > 32 ? 4 : (k.M > 16 ? 2 : 1));       // eight blocks (65-128 rows): the LDS-DMA ring kernel only
-  // 128-row groups when they alone oversubscribe the chip (the lm_head), else 64-row groups: twice the workgroups for the same bytes
-  int cfg = (k.N + 127) / 128 >= 2 * c->num_cus ? 2 : c->skinny_cfg_mid;
-  if (c->skinny_cfg_force >= 0) cfg = c->skinny_cfg_force;
+  // 128-row groups when they alone oversubscribe the chip (the lm_head), else 64-row groups on 256-k panels: twice the workgroups for the same bytes
+  int cfg = (k.N + 127) / 128 >= 2 * c->num_cus ? 2 : 0;
   if (mb == 4 && k.asrc == 1) cfg = 1;
   if (mb == 4 && k.nt == 3 && cfg == 0) cfg = 1;     // three terms x four blocks: the 256-k panel's register image spills (80 us for the QKV product); 128-k panels
   const int kp = tgx::skinny_kp(cfg);
   const int panels = (k.K + kp - 1) / kp;
   const int gx = (k.N + tgx::skinny_rows(cfg) - 1) / tgx::skinny_rows(cfg);
-  // split K until ~skinny_wgs workgroups exist (default two per CU: the bytes in flight per CU are what the stream rate follows)
+  // split K until ~SKINNY_WGS workgroups exist
   int nsplit = 1;
-  if (k.allow_split && c->gemm_splitk && gx < c->skinny_wgs) nsplit = std::max(1, std::min(std::min(16, panels), (c->skinny_wgs + gx / 2) / gx));
+  if (k.allow_split && c->gemm_splitk && gx < SKINNY_WGS) nsplit = std::max(1, std::min(std::min(16, panels), (SKINNY_WGS + gx / 2) / gx));
   if (nsplit > 1 && (size_t)nsplit * k.M * k.N * 4 > c->ws_part_bytes) nsplit = 1;      // the slab buffer is sized before capture (ensure_skinny_ws)
   int epi = k.epi;
   if (nsplit > 1) {
@@ -128,9 +129,9 @@ static int launch_skinny(tgx_ctx* c, const SkinnyCall& k) {
     epi = tgx::GEMM_PARTIAL;
   }
   const dim3 grid(gx, nsplit);
-  if (c->skinny_dma && k.asrc == 0 && k.nt == 3 && k.a_lo2 && c->dt == tgx::DT_BF16 && k.M >= c->skinny_dma_rows && k.K % 64 == 0 && (nsplit == 1 || g.k_per % 64 == 0) &&
+  if (c->skinny_dma && k.asrc == 0 && k.nt == 3 && k.a_lo2 && c->dt == tgx::DT_BF16 && k.K % 64 == 0 && (nsplit == 1 || g.k_per % 64 == 0) &&
       (epi == tgx::GEMM_PARTIAL || epi == tgx::GEMM_STORE)) {
-    const int nbw = mb == 8 ? 1 : (c->skinny_dma_nbw ? c->skinny_dma_nbw : tgx::skinny_nbw(cfg));
+    const int nbw = mb == 8 ? 1 : tgx::skinny_nbw(cfg);      // weight blocks per wave: as the panel kernel's geometry
     const dim3 grid((k.N + 64 * nbw - 1) / (64 * nbw), nsplit);
     const dim3 blk(256);
     const size_t lds = tgx::skd_lds_bytes(mb, nbw, 3);
@@ -149,8 +150,8 @@ static int launch_skinny(tgx_ctx* c, const SkinnyCall& k) {
 #undef TGX_SKD3
     return nsplit;
   }
-  if (c->skinny_dma && k.asrc == 0 && k.nt == 2 && k.M >= c->skinny_dma_rows && k.K % 64 == 0 && (nsplit == 1 || g.k_per % 64 == 0)) {
-    const int nbw = mb == 8 ? 1 : (c->skinny_dma_nbw ? c->skinny_dma_nbw : tgx::skinny_nbw(cfg));
+  if (c->skinny_dma && k.asrc == 0 && k.nt == 2 && k.K % 64 == 0 && (nsplit == 1 || g.k_per % 64 == 0)) {
+    const int nbw = mb == 8 ? 1 : tgx::skinny_nbw(cfg);      // weight blocks per wave: as the panel kernel's geometry
     const dim3 grid((k.N + 64 * nbw - 1) / (64 * nbw), nsplit);
     switch (epi) {
       case tgx::GEMM_PARTIAL: skinny_dma_dispatch<tgx::GEMM_PARTIAL>(c, grid, mb, nbw, g); return nsplit;
@@ -232,7 +233,10 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
   const bool lm_ks = ksplit_ok(c, M, V, H);
   // 33-64 rows (round 3): four activation blocks; every RMSNorm-fused product takes its activations as 16-bit terms prepared once per product by the
   // row-wise launch that also adds the pending split-K residual (the RMSNorm-on-the-way staging runs out of registers at four blocks)
-  const bool terms = M > 32 || c->act16 || ((c->skinny_terms >= 2 || (c->skinny_dma && c->skinny_dma_qkv && M >= c->skinny_dma_rows && H % 64 == 0)) && M > (c->skinny_dma_qkv >= 2 ? c->skinny_terms_above : 16));      // (act.round16: the row-wise launch's first term IS the rounded input)
+  // Batches of 3-32 rows prepare the QKV / lm_head activations as stored terms as well, so that the QKV product takes the LDS-DMA ring kernel.  From 5 rows instead
+  // of 17, Llama-3.2-1B ms/step: B = 5 0.898 / 0.867, 8 0.905 / 0.880, 12 0.962 / 0.939, 16 1.022 / 1.001; context 2k B = 8 1.071 / 1.050; Mistral-7B B = 8 3.587 /
+  // 3.556, B = 16 3.876 / 3.909.  From 3 instead of 5 (round 4): Llama-3.2-1B B = 3 / 4 0.822 / 0.823 -> 0.794 / 0.798
+  const bool terms = M > 32 || c->act16 || ((c->skinny_terms >= 2 || (c->skinny_dma && H % 64 == 0)) && M > 2);      // (act.round16: the row-wise launch's first term IS the rounded input)
   int pend = 0;            // terms form: slabs of the previous layer's down product not yet added to the rows
   // the rows start as embedding rows (the finalize of the previous step gathered them): their sums of squares for the first RMSNorm
   if (!terms) hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)r.x, (long long)H, H, ssq);
@@ -251,8 +255,7 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
     const bool raw_fuse = c->attn_raw_fuse && c->attn_direct && !(c->debug_skip & 1) && !(d.qk_norm && hd != 128) &&
                           (attn_batch_on_mfma(c, M) ? d.heads / d.kv_heads <= tgx::ATTN_RAW_GMAX : c->attn_raw_fuse >= 2);      // 2: the VALU direct forms as well
     // the direct-form attention of the step leaves its rows as 16-bit terms for the o_proj product (option skinny.dma_oproj: 1 = the matrix-core form only, 2 = every direct form)
-    const bool attn_terms = c->skinny_dma && c->skinny_dma_oproj && c->attn_direct && (c->skinny_dma_oproj >= 2 || attn_batch_on_mfma(c, M)) && !(c->debug_skip & 1) &&
-                            M >= c->skinny_dma_rows && qd % 64 == 0;
+    const bool attn_terms = c->skinny_dma && c->skinny_dma_oproj && c->attn_direct && (c->skinny_dma_oproj >= 2 || attn_batch_on_mfma(c, M)) && !(c->debug_skip & 1) && qd % 64 == 0;
     if (!raw_fuse) {
       tgx::RopeRowsArgs a{};
       if (qs > 1) { a.part = c->ws_part; a.nsplit = qs; a.bias = w.bqkv; } else a.QKV = c->ws_out;
@@ -282,9 +285,8 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
     o.epi = tgx::GEMM_RESIDUAL; o.W = w.wo; o.C = r.x; o.ldc = H; o.M = M; o.N = H; o.K = qd; o.nt = 2; o.asrc = 1; o.a_f32 = r.attn; o.lda = qd;
     if (attn_terms) { o.asrc = 0; o.a_hi = c->ws_ah; o.a_lo = c->ws_al; o.a_f32 = nullptr; }
     const int os = launch_skinny(c, o);
-    const bool gu_dma = c->skinny_dma && M >= c->skinny_dma_rows && M > 16 && H % 64 == 0;     // 17+ rows: the LDS-DMA ring kernel on stored terms (16.8 vs 19.5 us at 32 rows)
+    const bool gu_dma = c->skinny_dma && M > 16 && H % 64 == 0;     // 17+ rows: the LDS-DMA ring kernel on stored terms (16.8 vs 19.5 us at 32 rows)
     const bool gu_ks = !gu_dma && ksplit_ok(c, M, 2 * I, H);
-    int gs = 1;
     if (gu_ks) {     // {sum slabs, residual, RMSNorm, 16-bit terms} in one row-wise launch, then the barrier-free wide product
       launch_norm_terms(c, r.x, w.post_norm, M, H, os);
       launch_ksplit(c, tgx::GEMM_SILU, w.wgu, nullptr, 2 * I, M, 2 * I, H);
@@ -294,17 +296,16 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
       launch_norm_terms(c, r.x, w.post_norm, M, H, os);
       SkinnyCall gu;
       gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 0; gu.a_hi = c->ws_ah; gu.a_lo = c->ws_al;
-      gu.allow_split = c->skinny_gu_split != 0;
-      gs = launch_skinny(c, gu);
+      gu.allow_split = false;      // gate_up stays unsplit: siluMul in its epilogue, one launch less
+      launch_skinny(c, gu);
     } else {
     if (os > 1) launch_reduce_rows(c, tgx::GEMM_RESIDUAL, os, nullptr, r.x, H, M, H, ssq);
     else hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)r.x, (long long)H, H, ssq);
     SkinnyCall gu;
     gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 2; gu.a_f32 = r.x; gu.lda = H;
-    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = c->skinny_gu_split != 0;
-    gs = launch_skinny(c, gu);                                             // -> ws_hh / ws_hl: the down product's activation terms
+    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = false;
+    launch_skinny(c, gu);                                                  // -> ws_hh / ws_hl: the down product's activation terms
     }
-    if (gs > 1) launch_silu_slab_reduce(c, M, I, gs);                       // slabs -> siluMul -> terms (z-ordered sums)
     SkinnyCall dn;
     dn.epi = tgx::GEMM_RESIDUAL; dn.W = w.wdown; dn.C = r.x; dn.ldc = H; dn.M = M; dn.N = H; dn.K = I; dn.nt = 2; dn.asrc = 0; dn.a_hi = c->ws_hh; dn.a_lo = c->ws_hl;
     const int ds = launch_skinny(c, dn);
@@ -348,7 +349,8 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
   else launch_embed_rows(c, (const long long*)c->rows[(size_t)row0].prompt, c->ws_x, M, S);
   // 33-64 rows (four activation blocks): RMSNorm + the 16-bit terms once per product in a row-wise launch (which also takes the pending split-K
   // residual), the panel kernel stages stored terms — its RMSNorm-on-the-way form runs out of registers at four blocks
-  const bool terms = M > c->prefill_terms_rows || c->act16;      // (option prefill.terms_rows)
+  // (from 17 rows instead of 33, round 4: Mistral-7B S = 20 / 32 4.47 / 4.67 -> 3.94 / 4.30 ms, Llama-3.2-1B within noise)
+  const bool terms = M > 16 || c->act16;
   int pend = 0;             // slabs of the previous layer's down product not yet added to ws_x (terms form)
   if (!terms) hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)c->ws_x, (long long)H, H, ssq);
   for (int l = 0; l < d.layers; l++) {
@@ -400,7 +402,6 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
     SkinnyCall o;
     o.epi = tgx::GEMM_RESIDUAL; o.W = w.wo; o.C = c->ws_x; o.ldc = H; o.M = M; o.N = H; o.K = qd; o.nt = 2; o.asrc = 0; o.a_hi = c->ws_ah; o.a_lo = c->ws_al;
     const int os = launch_skinny(c, o);
-    int gs = 1;
     if (ksplit_ok(c, M, 2 * I, H)) {       // prompts of <= 16 rows: as the batched decode step (the o_proj product has consumed ws_ah / ws_al by now)
       launch_norm_terms(c, c->ws_x, w.post_norm, M, H, os);
       launch_ksplit(c, tgx::GEMM_SILU, w.wgu, nullptr, 2 * I, M, 2 * I, H);
@@ -408,17 +409,16 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
       launch_norm_terms(c, c->ws_x, w.post_norm, M, H, os);
       SkinnyCall gu;
       gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 0; gu.a_hi = c->ws_ah; gu.a_lo = c->ws_al;
-      gu.allow_split = c->skinny_gu_split != 0;
-      gs = launch_skinny(c, gu);
+      gu.allow_split = false;      // gate_up stays unsplit: siluMul in its epilogue, one launch less
+      launch_skinny(c, gu);
     } else {
     if (os > 1) launch_reduce_rows(c, tgx::GEMM_RESIDUAL, os, nullptr, c->ws_x, H, M, H, ssq);
     else hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)c->ws_x, (long long)H, H, ssq);
     SkinnyCall gu;
     gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 2; gu.a_f32 = c->ws_x; gu.lda = H;
-    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = c->skinny_gu_split != 0;
-    gs = launch_skinny(c, gu);
+    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = false;
+    launch_skinny(c, gu);
     }
-    if (gs > 1) launch_silu_slab_reduce(c, M, I, gs);
     SkinnyCall dn;
     dn.epi = tgx::GEMM_RESIDUAL; dn.W = w.wdown; dn.C = c->ws_x; dn.ldc = H; dn.M = M; dn.N = H; dn.K = I; dn.nt = 2; dn.asrc = 0; dn.a_hi = c->ws_hh; dn.a_lo = c->ws_hl;
     const int ds = launch_skinny(c, dn);
