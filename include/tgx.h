@@ -525,7 +525,7 @@ TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_dr
  *                     tgx_sample_row with the row's cfg and seed right after the call returns the last produced id again (same logits, same key).
  *   Everything else   the refusals and their order, ALL OR NOTHING, the stop-condition walk (on the device, token by token), the paged-KV block accounting, "other
  *                     rows keep their state bit for bit", steps and tickets: as for tgx_verify_row, word for word.  A logit processor on: TGX_ERR_UNSUPPORTED
- *                     (penalty counting is sequential).  tgx_verify_row itself still refuses a sampled row.
+ *                     unless option verify.processors is 1 (below).  tgx_verify_row itself still refuses a sampled row.
  *   Log-probabilities recorded as by tgx_verify_row, one record per produced token: the MODEL's distribution, which the sampler does not touch.
  *   tgx_read_probs    the row has no vector until its next sampled step (the rule of tgx_fork_row): the pass's scratch is not the row's.
  *   Memory            the first call on a sampled row allocates the positions' sampler workspace: 16 x vocab x 12 bytes of compacted lists and 16 scratch
@@ -536,6 +536,40 @@ TGX_API int tgx_verify_row(tgx_ctx* ctx, int row, const int64_t* draft, int n_dr
  *                     1.313 / 1.250 / 1.312 at 4 / 8 / 16 positions against 1.297 / 1.239 / 1.303 for the greedy verify of the same build: +0.010 .. +0.016,
  *                     less than the +0.037 one row's chain adds to a decode step (0.788 against 0.750). */
 TGX_API int tgx_verify_row_sampled(tgx_ctx* ctx, int row, const int64_t* draft, int n_draft, int64_t* out_ids /* [n_draft + 1] */, int32_t* out_n, int32_t* out_finish);
+
+/* ---- verifying processed rows: speculative decoding for rows with penalties, a logit bias or an automaton (additive to ABI 3) ------------------------------
+ * tgx_set_option(ctx, "verify.processors", 1) — default 0, read back by tgx_get_option, set any time after tgx_finalize, read at each call.  At 0 every call
+ * returns, launches and allocates what it did before the option existed.  At 1 the CHAIN calls — tgx_verify_row, tgx_verify_row_sampled, tgx_verify_rows, a
+ * TGX_ADV_STEP row of tgx_advance_rows, a chain-shaped tgx_verify_tree — accept a row with a logit processor on (penalties, bias list, automaton; below), and a
+ * call on rows with no processor on still runs exactly the launches and bits of option 0.  Nothing in the processors needs one launch per token:
+ *
+ *   Positions         the pass's inputs are in[0] = t0 (the row's current token), in[1 ..] = the draft.  Position i of the row's M positions sees
+ *                       history  w_i[e] = the row's word for e with its count raised by #{ j <= i : in[j] == e } (saturating, the prompt bit kept): what i + 1
+ *                                counting steps would have left;
+ *                       state    s_i = the row's state word moved by in[0 .. i] under the step's rule (an entry that is NONE leaves the state where it is);
+ *                       vector   the four-stage formula below on the pass's raw logits v_i with w_i, the row's bias list and s_i — the same code and roundings
+ *                                as a step's processor launch.
+ *   Choice            g[i] = the lowest-index argmax of position i's processed vector (a greedy row), or the draw of the row's chain over it with the key
+ *                     (seed, past + i + 1, row) — a pure function of the processed fp32 vector, the settings and the key, as in tgx_decode_rows.  The accept
+ *                     walk, the stop-set / max_new counting, out_ids / out_n / out_finish and the paged-block trim are unchanged.
+ *   Afterwards        with n = out_n: the row's history words are raised by in[0 .. n - 1] and by nothing else (the tokens the n equivalent steps consume; the
+ *                     rejected tail and the last produced token are not counted); its state word is s_{n-1}.  Both are committed on the device behind the walk.
+ *                     The logits slot and argmax partials are the RAW ones of the producing position: tgx_read_logits and the logprobs ring stay the model's.
+ *                     tgx_sample_row with the row's settings right after the call returns the last produced id again (the history and state as they stand are
+ *                     what position n - 1 was processed with).  No tgx_read_probs vector until the row's next sampled step.  A refused call changes neither
+ *                     the history nor the state.
+ *   Still refused     a processed row on a tree that is no chain (tgx_verify_tree "Not built"); every other refusal, in the same order.
+ *   Memory            the first one-row call on a processed row allocates a processed slab of 16 x vocab floats with its per-tile partials and 16 state
+ *                     words; the first joint call with a processed row the same for 64 positions.  A context that never makes such a call holds none of it.
+ *   Cost              per call with a processed row: one one-workgroup launch that walks the automaton states (only with an automaton on) and one launch of
+ *                     ceil(vocab / 1024) x positions workgroups that reads the positions' raw logits and the row's words and writes the slab; the commit
+ *                     rides in the accept launch.  Positions of unprocessed rows get no workgroup.  Measured (profiles/verify_processed.txt, tools/spec_bench.py
+ *                     --processors; Llama-3.2-1B bf16, context 2048, a bias list, penalties and an automaton on the row, ms per tgx_verify_row, median of 3
+ *                     rounds x 9 calls): 1.290 / 1.223 / 1.279 at 4 / 8 / 16 positions against 1.289 / 1.233 / 1.303 for the same build's call with no
+ *                     processor on: +0.000 / -0.011 / -0.024, at or inside the spread of the rounds' medians (0.001 .. 0.026) — the two launches do not show
+ *                     in the call (the accept launch merges 126 per-tile partials per position instead of the lm_head's); 1.66 .. 1.75 times one
+ *                     tgx_decode_rows step of the processed row on the parent commit's library (0.739).  On a text a regular expression forces (tgx_cli,
+ *                     GPT-2 geometry, greedy): 5.58 tokens per verify pass and 5310 decode-only tokens/s against 3556 for the regex alone on the parent. */
 
 /* ---- tree speculative decoding: verifying a token TREE in one pass (additive to ABI 3) -------------------------------------------------------------------
  * A chain of guesses stops paying at its first wrong token.  A token tree spends the same <= 16 positions of one pass on alternatives: several candidates for the
@@ -567,7 +601,9 @@ TGX_API int tgx_verify_row_sampled(tgx_ctx* ctx, int row, const int64_t* draft, 
  *                     matrix-core route (fp32 storage, GPT-2, option prefill.mfma or prefill.skinny at 0, shapes the skinny kernels do not cover, a head_dim
  *                     other than 64 / 128) or when a paged cache has more than 1024 blocks per row.  Last the paged cache's room: TGX_ERR_CONTEXT.
  *                     Option prefill.min_rows is a speed threshold for chains and does not bind a tree: every M in [3, 16] runs the skinny route.
- *   Not built         trees in tgx_verify_rows / tgx_advance_rows; log-probability records, logit processors and automata on a tree that is no chain.
+ *   Not built         trees in tgx_verify_rows / tgx_advance_rows; log-probability records on a tree that is no chain; a row with a logit processor or an
+ *                     automaton on a tree that is no chain, whatever option verify.processors says (a position's history and state would depend on its
+ *                     branch): TGX_ERR_UNSUPPORTED.
  *   Cost              tgx_verify_row_sampled's for the same number of positions, plus ONE compaction launch of layers x kv_heads x 2 workgroups
  *                     (profiles/verify_tree.txt; Llama-3.2-1B bf16, context 2048, greedy, ms per call: 1.263 / 1.281 / 1.354 at 4 / 8 / 16 positions against
  *                     1.296 / 1.231 / 1.309 for the parent build's chain pass, whose repeated medians spread by 0.011). */
@@ -798,7 +834,7 @@ TGX_API int tgx_embed_rows(tgx_ctx* ctx, int n, const int32_t* rows, const int64
  *                     Temperature and the filters follow unchanged.
  *   Where             tgx_decode_rows; tgx_sample_row (the row's settings, no counting step: the row has no current token then).  tgx_decode, tgx_sample and
  *                     tgx_step_async ignore the processors, as they ignore every row setting.  tgx_verify_row on a row with a processor on is TGX_ERR_UNSUPPORTED
- *                     (its accept rule compares raw argmaxes).
+ *                     unless option verify.processors is 1 (the verify calls then process every position of the pass: "verifying processed rows" above).
  *   Settings          per row, kept across calls until changed, stream-ordered; the caller's arrays may be freed on return.  tgx_reset_row / tgx_reset_cache restore
  *                     the neutral settings (repetition 1, presence 0, frequency 0), empty the bias list and clear the row's history.
  *   Refusals          TGX_ERR_INVALID, nothing changes: a null cfg, a row outside [0, max_batch), repetition <= 0 or non-finite, a non-finite presence or frequency,
@@ -846,8 +882,8 @@ TGX_API int tgx_set_row_history(tgx_ctx* ctx, int row, const int64_t* prompt_ids
  *   Refusals          tgx_set_row_automaton, TGX_ERR_INVALID and nothing changes: a row outside [0, max_batch), an unknown id, a state outside [-1, n_states).
  *                     Before tgx_finalize: TGX_ERR_STATE.
  *   A processor       the automaton is a logit processor: every rule about "a processor on" applies unchanged.  tgx_verify_row, tgx_verify_row_sampled,
- *                     tgx_verify_rows and a STEP row of tgx_advance_rows refuse such a row with TGX_ERR_UNSUPPORTED; tgx_decode, tgx_sample and tgx_step_async
- *                     ignore it, as they ignore every row setting.
+ *                     tgx_verify_rows and a STEP row of tgx_advance_rows refuse such a row with TGX_ERR_UNSUPPORTED unless option verify.processors is 1;
+ *                     tgx_decode, tgx_sample and tgx_step_async ignore it, as they ignore every row setting.
  *   Cost              a context that never creates an automaton allocates nothing new and runs exactly the launches it ran before; so does a context that has
  *                     tables but no row using one.  The first row that names one allocates the processors' buffers (above).  While some row of the batch has one
  *                     on: the processor launch (2 * vocab more bytes read per constrained row) and, ahead of it, one one-workgroup launch that moves the state

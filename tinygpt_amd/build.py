@@ -158,6 +158,11 @@ def build_spec_mode_check(force: bool = False, verbose: bool = False):
     return _build_cpu_check("spec_mode_check", os.path.join(HOST, "spec_mode.h"), force, verbose)
 
 
+def build_spec_mode_processed_check(force: bool = False, verbose: bool = False):
+    """tests/spec_mode_processed_check.cpp, the CPU audit of SpecInputs::verifyProcessed in host/spec_mode.h."""
+    return _build_cpu_check("spec_mode_processed_check", os.path.join(HOST, "spec_mode.h"), force, verbose)
+
+
 def build_spec_rows_check(force: bool = False, verbose: bool = False):
     """tests/spec_rows_check.cpp, the CPU audit of SpecInputs::verifyRows in host/spec_mode.h."""
     return _build_cpu_check("spec_rows_check", os.path.join(HOST, "spec_mode.h"), force, verbose)

@@ -1826,6 +1826,8 @@ struct ContPass {
   std::vector<int> rows, idx, kind, first, lens, past, nd;
   std::vector<const int64_t*> ids;                          // its ids in the caller's array (a STEP: the draft)
   std::vector<char> holds, smp;                             // the row holds a sequence (0: an admission); a STEP row that does not sample greedily
+  std::vector<char> prc;                                    // a STEP row with a logit processor on (option verify.processors let it through)
+  bool any_processed = false;
   std::vector<tgx_sampler_cfg> cfg;                         // a STEP row's sampler settings
   std::vector<tgx::VerifyRecord> rec;                       // the STEP rows' records, read back behind the pass
   std::vector<int> adm;                                     // the admissions' rows
@@ -1837,6 +1839,7 @@ struct ContPass {
     past.push_back(held ? (int)c->row_host[(size_t)row].past : 0); holds.push_back(held);
     cfg.push_back(step ? row_cfg(c, row) : tgx_sampler_cfg{}); smp.push_back(step && !is_greedy(&cfg.back()));
     any_sampled = any_sampled || smp.back();
+    prc.push_back(step && row_processed(c, row)); any_processed = any_processed || prc.back();
     if (!held) adm.push_back(row);
     n++; M += sl;
     if (step) { ns++; Ms += sl; rec.emplace_back(); }
@@ -1909,6 +1912,7 @@ static int follow_step_rows(tgx_ctx* c, const ContPass& cp, int j0, int j1, cons
     r.fin = (char)rec.finish;
     if (row_records(c, row)) r.lp_count += rec.n;
     kv_trim_row(c, row, r.past);
+    if (cp.prc[(size_t)j] && c->row_host[(size_t)row].auto_id >= 0) c->row_req_host[(size_t)row].auto_state = rec.state;      // the mirror follows the commit
     if (!cp.smp[(size_t)j]) note_sampled(c, row, 1, cp.cfg[(size_t)j]);
     else r.probs_ok = false;
     for (int k = 0; k < rec.n; k++) out_ids[(size_t)i * (TGX_MAX_DRAFT + 1) + k] = rec.ids[k];
@@ -2002,7 +2006,7 @@ static int verify_row_check(tgx_ctx* c, int row, const int64_t* draft, int n_dra
   if (!rh.tok) return set_err(c, TGX_ERR_STATE, "row %d has no current token: tgx_sample_row it first", row);
   const tgx_sampler_cfg cfg = row_cfg(c, row);
   if (!is_greedy(&cfg) && !sampled_entry) return set_err(c, TGX_ERR_UNSUPPORTED, "tgx_verify_row: row %d does not sample greedily (verification under sampling is not built)", row);
-  if (row_processed(c, row)) return set_err(c, TGX_ERR_UNSUPPORTED, "%s: row %d has a logit processor on (the accept rule compares raw argmaxes)", fn, row);
+  if (row_processed(c, row) && !c->verify_processors) return set_err(c, TGX_ERR_UNSUPPORTED, "%s: row %d has a logit processor on (the accept rule compares raw argmaxes)", fn, row);
   if (rh.past + n_draft + 1 > d.max_ctx) return set_err(c, TGX_ERR_CONTEXT, "context size exceeded: row %d holds %lld positions, + %d > %d", row, (long long)rh.past, n_draft + 1, d.max_ctx);
   return TGX_OK;
 }
@@ -2015,6 +2019,8 @@ static int verify_row_run(tgx_ctx* c, ContPass& cp, int j, const char* fn, int64
   HIP_OK(c, hipSetDevice(c->device));
   if (int rc = ensure_verify_ws(c)) return rc;
   if (sampled) if (int rc = vs_alloc(c)) return rc;      // the positions' sampler workspace: only a sampled row's call ever holds it
+  const bool processed = cp.prc[(size_t)j];
+  if (processed) if (int rc = ensure_verify_proc_ws(c, /*joint=*/false)) return rc;      // ... and the processed slab: only a processed row's call
   if (int rc = ensure_extend_ws(c, M, past)) return rc;
   c->vf_pass_rows = 0;                             // the workspace changes hands
   (void)kv_ensure_blocks(c, row, (long long)past + M);      // the whole pass up front; cannot fail: counted above
@@ -2023,8 +2029,12 @@ static int verify_row_run(tgx_ctx* c, ContPass& cp, int j, const char* fn, int64
   HIP_OK(c, hipMemcpyAsync(c->rows[(size_t)row].prompt, ids, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
   launch_verify_first_id(c, row);
   if (int rc = issue_pass(c, row, 1, M, past, /*verify=*/true)) return rc;
-  if (sampled) launch_sample_positions(c, row, M, cp.cfg[(size_t)j]);      // every position's draw under the row's settings, with the key its step would use
-  launch_verify_accept(c, row, M, sampled ? c->vs_draws : nullptr);
+  if (processed) {      // every position as its step would have processed it (kernels/logit_proc.h): the automaton walk, then the positions launch
+    const int first = 0; const char on = 1; const long long* const in = c->rows[(size_t)row].prompt;
+    launch_logit_proc_positions(c, 1, &row, &first, &M, &in, &on, /*joint=*/false);
+  }
+  if (sampled) launch_sample_positions(c, row, M, cp.cfg[(size_t)j], -1, nullptr, processed);      // every position's draw under the row's settings, with the key its step would use
+  launch_verify_accept(c, row, M, sampled ? c->vs_draws : nullptr, processed);      // (a processed row: the commit of its history and state rides behind the walk)
   if (row_records(c, row)) launch_logprobs_verify(c, row, M);      // one record per produced token, each from the logits of the position that produced it
   HIP_OK(c, hipMemcpyAsync(&cp.rec[(size_t)j], c->vf_rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
   if (int rc = finish_pass(c)) return rc;
@@ -2082,6 +2092,8 @@ int tgx_verify_tree(tgx_ctx* c, int row, const int64_t* tokens, const int32_t* p
     case verify_tree_plan::DUP_SIBLING: return set_err(c, TGX_ERR_INVALID, "node %d carries the token of an earlier child of the same parent", tp.bad);
     case verify_tree_plan::BAD_COUNT: return set_err(c, TGX_ERR_INVALID, "n_nodes %d out of range [1,%d]", n_nodes, TGX_MAX_TREE_NODES);      // (the planner's own check: refused above already)
   }
+  if (!tp.chain && row_processed(c, row))
+    return set_err(c, TGX_ERR_UNSUPPORTED, "%s: row %d has a logit processor on (not built for a tree that is no chain: a position's history and state depend on its branch)", fn, row);
   ContPass cp;
   cp.add(c, row, 0, TGX_ADV_STEP, tokens, n_nodes);
   if (tp.chain) {      // tgx_verify_row_sampled's pass, launches and bits
@@ -2170,9 +2182,14 @@ static int call_buffer(tgx_ctx* c, const ContPass& cp, const RaggedPass& p, cons
 // produced token of a recording row; the records' read-back, queued
 static int step_tail(tgx_ctx* c, ContPass& cp, PrefillRoute lm_rt, const long long* d_ids) {
   launch_lm_head_all(c, lm_rt, cp.Ms, nullptr, /*joint=*/true);
+  if (cp.any_processed) {      // the processed rows' positions (option verify.processors): the automaton walk, then the positions launch; the other rows get no workgroup
+    std::vector<const long long*> in((size_t)cp.ns);
+    for (int j = 0; j < cp.ns; j++) in[(size_t)j] = d_ids + cp.first[(size_t)j];
+    launch_logit_proc_positions(c, cp.ns, cp.rows.data(), cp.first.data(), cp.lens.data(), in.data(), cp.prc.data(), /*joint=*/true);
+  }
   for (int j = 0; j < cp.ns; j++)
-    if (cp.smp[(size_t)j]) launch_sample_positions(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.cfg[(size_t)j], cp.first[(size_t)j]);
-  launch_verify_accept_rows(c, d_ids, cp.ns, cp.rows.data(), cp.first.data(), cp.nd.data(), cp.smp.data());
+    if (cp.smp[(size_t)j]) launch_sample_positions(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.cfg[(size_t)j], cp.first[(size_t)j], nullptr, cp.prc[(size_t)j]);
+  launch_verify_accept_rows(c, d_ids, cp.ns, cp.rows.data(), cp.first.data(), cp.nd.data(), cp.smp.data(), cp.prc.data());
   for (int j = 0; j < cp.ns; j++)
     if (row_records(c, cp.rows[(size_t)j])) launch_logprobs_verify(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.first[(size_t)j], j);
   HIP_OK(c, hipMemcpyAsync(cp.rec.data(), c->vj_rec, (size_t)cp.ns * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
@@ -2190,6 +2207,7 @@ static int joint_pass(tgx_ctx* c, ContPass& cp, ContAttn attn, PrefillRoute rt, 
   const int n = p.n, ns = cp.ns;
   if (ns) if (int rc = ensure_verify_rows_ws(c)) return rc;
   if (cp.any_sampled) if (int rc = vs_alloc(c)) return rc;
+  if (cp.any_processed) if (int rc = ensure_verify_proc_ws(c, /*joint=*/true)) return rc;
   // the STEP positions' lm_head: on the tiled route the GEMV form would stream the lm_head weights once per FOUR positions (32 step rows: eight passes, measured
   // +0.8 ms on Llama-3.2-1B, profiles/advance_rows.txt); where the skinny route would take Ms rows by themselves, its one-pass form serves them from ws_x
   // (a pass of STEP sequences alone: rt is that route already)
@@ -2975,6 +2993,7 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "score.vocab_chunk")) { *out_value = c->score_vocab_chunk; return TGX_OK; }
   if (!strcmp(key, "snapshot.stage_kib")) { *out_value = c->snapshot_stage_kib; return TGX_OK; }
   if (!strcmp(key, "verify.last_splits")) { *out_value = c->verify_last_splits; return TGX_OK; }  // read-only: the key splits of the last tgx_verify_rows joint pass's attention (0: unsplit)
+  if (!strcmp(key, "verify.processors")) { *out_value = c->verify_processors; return TGX_OK; }
   if (!strcmp(key, "verify.last_form")) { *out_value = c->verify_last_form; return TGX_OK; }      // read-only: the form of the last tgx_verify_rows (0 none yet, 1 the joint pass, 2 row by row)
   if (!strcmp(key, "advance.attn_tiles")) { *out_value = c->advance_attn_tiles; return TGX_OK; }
   if (!strcmp(key, "advance.last_form")) { *out_value = c->advance_last_form; return TGX_OK; }    // read-only: the form of the last tgx_advance_rows (0 none yet, 1 the joint pass, 2 piecewise)
@@ -3041,6 +3060,10 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "score.rows")) { if (value < 64 || value % 64) return set_err(c, TGX_ERR_INVALID, "score.rows is a positive multiple of 64"); c->score_rows = value; return TGX_OK; }
   if (!strcmp(key, "score.vocab_chunk")) { if (value < 1024 || value % 1024) return set_err(c, TGX_ERR_INVALID, "score.vocab_chunk is a positive multiple of 1024"); c->score_vocab_chunk = value; return TGX_OK; }
   if (!strcmp(key, "snapshot.stage_kib")) { if (value < 1) return set_err(c, TGX_ERR_INVALID, "snapshot.stage_kib is a size in KiB (one layer of a row is always staged)"); c->snapshot_stage_kib = value; return TGX_OK; }
+  if (!strcmp(key, "verify.processors")) {      // 1: the chain verify calls take rows with a logit processor on (include/tgx.h); read on the host at each call
+    if (value != 0 && value != 1) return set_err(c, TGX_ERR_INVALID, "verify.processors is 0 or 1");
+    c->verify_processors = value; return TGX_OK;
+  }
   if (!strcmp(key, "oproj.sliced")) { drop_step_graphs(c); c->oproj_sliced = value != 0; return TGX_OK; }
   if (!strcmp(key, "weights.packed") || !strcmp(key, "weights.packed_classes")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the packed copies are made there)", key);

@@ -346,6 +346,12 @@ struct tgx_ctx {
   unsigned char* vj_args = nullptr;              // [max_batch] tgx::VerifyArgs
   std::vector<unsigned char> vj_args_host;       // ... and the host copy the upload reads
   bool vf_pass_joint = false;                    // vf_pass_rows counts positions of vj_logits (a tgx_verify_rows joint pass), not of vf_logits
+  // ---- option verify.processors (include/tgx.h; kernels/logit_proc.h logit_proc_pos_kernel): 1 lets the chain verify calls take rows with a logit processor on.
+  // The processed slab of the pass's positions with its per-tile partials and the positions' automaton states — VERIFY_ROWS slots for the one-row calls (vp_*),
+  // VERIFY_POSITIONS for the joint ones (vpj_*) — each allocated by the first call that verifies a processed row (ensure_verify_proc_ws)
+  int verify_processors = 0;
+  float *vp_logits = nullptr, *vp_part_val = nullptr; int *vp_part_idx = nullptr, *vp_states = nullptr;
+  float *vpj_logits = nullptr, *vpj_part_val = nullptr; int *vpj_part_idx = nullptr, *vpj_states = nullptr;
   int verify_last_form = 0, verify_last_splits = 0;      // ... and `verify.last_splits` (read-only): the key splits of the last joint pass's attention (0: unsplit)
   // ---- tgx_advance_rows (include/tgx.h): prompt chunks and live rows' steps in one ragged pass.  Option advance.attn_tiles: the tile target of the mixed attention
   // (kernels/attn_mixed.h; csrc/attn_worklist.h): 0 never split (the work-list form alone), N >= 1 query blocks of more than N key tiles are cut into ranges of <= N
@@ -480,10 +486,10 @@ void launch_embed_chunk(tgx_ctx* c, const long long* ids, int R, int pos0);
 void launch_add_pos(tgx_ctx* c, int* pos, int n);
 void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_val, int* part_idx);
 void launch_verify_first_id(tgx_ctx* c, int row);         // tgx_verify_row: prompt[0] of the row <- its current token
-void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws = nullptr);    // ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h); draws: the positions' sampled ids
+void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws = nullptr, bool processed = false);    // (processed: g[i] from the vp_* partials, the history and state committed) ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h); draws: the positions' sampled ids
 // tgx_verify_rows, the joint pass: sequence i = row rows[i], M_i = n_draft[i] + 1 positions at slice first[i] of the vj_* workspace and of the pass's ids
 void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows, const int* first);          // ids[first[i]] <- row rows[i]'s current token, one launch
-void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled);   // one workgroup per row -> vj_rec[i]
+void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled, const char* processed = nullptr);   // one workgroup per row -> vj_rec[i]; processed[i]: row i chooses from the vpj_* slab and commits its history and state
 // tgx_verify_tree: the walk over a token tree (draws as above; vt_tab holds the tree's tables) -> vf_rec and the accepted path; then the accepted branch's K / V rows
 // of every layer from slot past + path[j] to slot past + j (kernels/kv_tree.h), stream-ordered behind the walk: path and count are read on the device
 void launch_verify_accept_tree(tgx_ctx* c, int row, int M, const int* draws);
@@ -501,9 +507,13 @@ int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);
 int vs_alloc(tgx_ctx* c);                                                    // tgx_verify_row_sampled: the positions' sampler workspace, at first use
 int vs_rezero(tgx_ctx* c);                                                   // ... its scratch back to the zero state the chain expects (tgx_reset_cache; stream-ordered; a no-op without the workspace)
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first = -1, const int* depth = nullptr);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes); joint_first >= 0: over the row's slice of the vj_* workspace -> its slice of vj_draws
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first = -1, const int* depth = nullptr, bool processed = false);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes); joint_first >= 0: over the row's slice of the vj_* workspace -> its slice of vj_draws
 int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
 bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
+int ensure_verify_proc_ws(tgx_ctx* c, bool joint);                          // the vp_* (one-row calls) or vpj_* (joint calls) workspace, at first use
+// the processors over a verify pass's positions (option verify.processors): the automaton walk, then the positions launch, for the n STEP rows with processed[j]
+// set — row rows[j]'s lens[j] positions from workspace row first[j], its inputs at ids[j] on the device; joint: the vj_* / vpj_* workspace, else vf_* / vp_*
+void launch_logit_proc_positions(tgx_ctx* c, int n, const int* rows, const int* first, const int* lens, const long long* const* ids, const char* processed, bool joint);
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)
 // beam search (kernels/beam.h): the three launches of tgx_beam_select over rows[0 .. n) and the read-back of its record (the caller checked every argument); the
 // publish launch of tgx_beam_advance: row rows[j] takes tokens[j] as its current token and the next embedding at its position

@@ -399,10 +399,23 @@ void launch_verify_first_id(tgx_ctx* c, int row) {
 }
 // ... and behind the pass and the M positions' lm_head, ONE launch accepts the draft's matching prefix and leaves the row as that many decode steps would
 // (draws: the positions' sampled ids, launch_sample_positions; nullptr: greedy)
-void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws) {
+// what g[i] is chosen from, and the commit: the raw pair again and nothing; a processed row (option verify.processors): the processed slab's per-tile partials
+// from workspace row `first`, the row's history words and — with an automaton on — its slice of the positions' states
+static void verify_select(tgx_ctx* c, tgx::VerifyArgs& a, int row, bool processed, bool joint, size_t first) {
+  a.sel_part_val = a.part_val; a.sel_part_idx = a.part_idx; a.sel_part_stride = a.part_stride; a.sel_n_part = a.n_part;
+  if (!processed) return;
+  const size_t T = (size_t)((c->d.vocab + 1023) / 1024);
+  a.sel_part_val = (joint ? c->vpj_part_val : c->vp_part_val) + first * T; a.sel_part_idx = (joint ? c->vpj_part_idx : c->vp_part_idx) + first * T;
+  a.sel_part_stride = (long long)T; a.sel_n_part = (int)T;
+  a.hist = c->proc_hist + (size_t)row * c->d.vocab;
+  a.states = (c->row_req_host[(size_t)row].proc & tgx::PROC_AUTOMATON) ? (joint ? c->vpj_states : c->vp_states) + first : nullptr;
+}
+void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws, bool processed) {
+  if (processed && (!c->vp_states || !c->proc_hist)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
   RowState& r = c->rows[(size_t)row];
   tgx::VerifyArgs a{};
   a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
+  verify_select(c, a, row, processed, /*joint=*/false, 0);
   a.logits = c->vf_logits; a.draft = r.prompt + 1; a.draws = draws;
   a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
   a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
@@ -417,6 +430,7 @@ void launch_verify_accept_tree(tgx_ctx* c, int row, int M, const int* draws) {
   tgx::VerifyTreeArgs t{};
   tgx::VerifyArgs& a = t.v;
   a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
+  verify_select(c, a, row, /*processed=*/false, /*joint=*/false, 0);
   a.logits = c->vf_logits; a.draft = r.prompt + 1; a.draws = draws;
   a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
   a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
@@ -446,7 +460,7 @@ void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows,
   for (int i = 0; i < n; i++) { f.tok[i] = c->rows[(size_t)rows[i]].tok; f.first[i] = first[i]; }
   hipLaunchKernelGGL(tgx::verify_first_ids_kernel, dim3(1), dim3(tgx::VERIFY_MAX_ROWS), 0, c->stream, ids, f, n);
 }
-void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled) {
+void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled, const char* processed) {
   static_assert(sizeof(tgx::VerifyArgs) % 8 == 0, "the table's entries hold pointers");
   if (!c->vj_args || !c->vj_rec || n > tgx::VERIFY_MAX_ROWS) { c->launch_fault = "joint verification requested before its buffers exist"; return; }
   const size_t V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
@@ -457,6 +471,9 @@ void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const in
     const size_t f = (size_t)first[i];
     tgx::VerifyArgs a{};
     a.part_val = c->vj_part_val + f * P; a.part_idx = c->vj_part_idx + f * P; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = n_draft[i] + 1;
+    const bool proc = processed && processed[i];
+    if (proc && (!c->vpj_states || !c->proc_hist)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
+    verify_select(c, a, rows[i], proc, /*joint=*/true, f);
     a.logits = c->vj_logits + f * V; a.draft = ids + f + 1; a.draws = sampled[i] ? c->vj_draws + f : nullptr;
     a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + rows[i];
     a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;

@@ -217,7 +217,7 @@ __device__ __forceinline__ unsigned long long draw_key(unsigned long long seed, 
 
 // tgx_verify_row (kernels/verify.h): what the accept launch leaves for the host — the tokens the row produced in the call and its finish reason
 constexpr int VERIFY_MAX_POS = 16;      // TGX_MAX_DRAFT + 1 positions of one pass
-struct VerifyRecord { int n, finish; int ids[VERIFY_MAX_POS]; };
+struct VerifyRecord { int n, finish; int ids[VERIFY_MAX_POS]; int state; };      // state: a processed row's automaton state behind the commit (kernels/verify.h), else not written
 constexpr int VERIFY_MAX_ROWS = 64;     // tgx_verify_rows: TGX_MAX_VERIFY_POSITIONS positions of one joint pass, so at most that many rows of one position each
 
 // per-token log-probabilities (kernels/logprobs.h; include/tgx.h tgx_set_row_logprobs): a row's ring of records and its device-side counters

@@ -80,17 +80,10 @@ __global__ __launch_bounds__(WAVE) void automaton_advance_kernel(const AutoAdvan
   }
 }
 
-__global__ __launch_bounds__(PROC_WG) void logit_proc_kernel(const LogitProcArgs a) {
-  __shared__ __attribute__((aligned(16))) float tile[PROC_TILE];
-  __shared__ float sv[PROC_WG / WAVE];
-  __shared__ int si[PROC_WG / WAVE];
-  const int y = blockIdx.y, t0 = blockIdx.x * PROC_TILE, tid = threadIdx.x, base = t0 + tid * PROC_EPT, V = a.V;
-  const RowReq& q = a.req[y];
-  const int proc = q.proc;
-  const bool on = proc != 0 && !(a.step && q.finished);      // (workgroup-uniform)
-  const bool vec = (V & 3) == 0;                              // then base < V covers the thread's four entries
-  const float* lg = a.logits + (size_t)y * a.logits_stride;
-  float v[PROC_EPT];
+// ---- the pieces logit_proc_kernel and logit_proc_pos_kernel share: a thread's four entries of its workgroup's tile, in registers
+// the thread's raw logits: one 16-byte load when V % 4 == 0 (then base < V covers all four), entry by entry otherwise
+__device__ __forceinline__ void proc_load_raw(const float* lg, int base, int V, float (&v)[PROC_EPT]) {
+  const bool vec = (V & 3) == 0;
   if (vec && base < V) {
     const f32x4 r = *reinterpret_cast<const f32x4*>(lg + base);
 #pragma unroll
@@ -99,66 +92,70 @@ __global__ __launch_bounds__(PROC_WG) void logit_proc_kernel(const LogitProcArgs
 #pragma unroll
     for (int j = 0; j < PROC_EPT; j++) v[j] = !vec && base + j < V ? lg[base + j] : 0.f;
   }
-  if (on) {
-    unsigned int* hw = a.hist + (size_t)y * V;
-    unsigned int w[PROC_EPT];
-    if (vec && base < V) {
-      const u32x4 r = *reinterpret_cast<const u32x4*>(hw + base);
+}
+// ... and its history words
+__device__ __forceinline__ void proc_load_words(const unsigned int* hw, int base, int V, unsigned int (&w)[PROC_EPT]) {
+  const bool vec = (V & 3) == 0;
+  if (vec && base < V) {
+    const u32x4 r = *reinterpret_cast<const u32x4*>(hw + base);
 #pragma unroll
-      for (int j = 0; j < PROC_EPT; j++) w[j] = r[j];
-    } else {
+    for (int j = 0; j < PROC_EPT; j++) w[j] = r[j];
+  } else {
 #pragma unroll
-      for (int j = 0; j < PROC_EPT; j++) w[j] = !vec && base + j < V ? hw[base + j] : 0u;
-    }
-    const bool pen = (proc & PROC_PENALTY) != 0;
-    const float rep = pen ? q.repetition : 1.f, pres = pen ? q.presence : 0.f, freq = pen ? q.frequency : 0.f;
-    const int tok = a.step ? a.tok[y] : -1;
-#pragma unroll
-    for (int j = 0; j < PROC_EPT; j++) {
-      if (base + j == tok && base + j < V) {      // the counting step: this thread owns the current token's word
-        const unsigned int n = w[j] & PROC_COUNT_MASK;
-        w[j] = (w[j] & PROC_PROMPT_BIT) | (n < PROC_COUNT_MASK ? n + 1u : n);
-        hw[base + j] = w[j];
-      }
-      v[j] = proc_penalise(v[j], w[j], rep, pres, freq);
-    }
-    const int n_bias = (proc & PROC_BIAS) ? min(q.n_bias, PROC_MAX_BIAS) : 0;
-    if (n_bias > 0) {
-      *reinterpret_cast<f32x4*>(tile + tid * PROC_EPT) = f32x4{v[0], v[1], v[2], v[3]};
-      __syncthreads();
-      const int* ids = a.bias_ids + (size_t)y * PROC_MAX_BIAS;
-      const float* bv = a.bias_val + (size_t)y * PROC_MAX_BIAS;
-      for (int k = tid; k < n_bias; k += PROC_WG) {
-        const int e = ids[k] - t0;
-        if (e >= 0 && e < PROC_TILE) tile[e] = proc_add(tile[e], bv[k]);
-      }
-      __syncthreads();
-      const f32x4 r = *reinterpret_cast<const f32x4*>(tile + tid * PROC_EPT);
-#pragma unroll
-      for (int j = 0; j < PROC_EPT; j++) v[j] = r[j];
-    }
-    if (proc & PROC_AUTOMATON) {      // stage 4: the entries the row's state does not allow
-      const unsigned short* nx = q.auto_next + (size_t)q.auto_state * V;
-      unsigned int e[PROC_EPT];
-      if (vec && base < V) {
-        const u32x2 r = *reinterpret_cast<const u32x2*>(nx + base);
-        e[0] = r[0] & 0xffffu; e[1] = r[0] >> 16; e[2] = r[1] & 0xffffu; e[3] = r[1] >> 16;
-      } else {
-#pragma unroll
-        for (int j = 0; j < PROC_EPT; j++) e[j] = !vec && base + j < V ? nx[base + j] : 0u;
-      }
-#pragma unroll
-      for (int j = 0; j < PROC_EPT; j++) if (e[j] == AUTO_NONE) v[j] = -INFINITY;
-    }
+    for (int j = 0; j < PROC_EPT; j++) w[j] = !vec && base + j < V ? hw[base + j] : 0u;
   }
-  float* out = a.out + (size_t)y * V;
-  if (vec) {
+}
+// one more occurrence of the word's token: the count saturates, the prompt bit stays
+__device__ __forceinline__ unsigned int proc_count(unsigned int w) {
+  const unsigned int n = w & PROC_COUNT_MASK;
+  return (w & PROC_PROMPT_BIT) | (n < PROC_COUNT_MASK ? n + 1u : n);
+}
+// stages 1-3 of the pinned formula on the thread's entries, with the words w as the position sees them: the penalties, then the row's bias entries that fall into
+// the tile, through LDS (`tile`: the workgroup's PROC_TILE floats).  Every thread of the workgroup calls it (q and proc are workgroup-uniform)
+__device__ __forceinline__ void proc_stages_1_3(float (&v)[PROC_EPT], const unsigned int (&w)[PROC_EPT], const RowReq& q, int proc, const int* bias_ids, const float* bias_val,
+                                                float* tile, int t0, int tid) {
+  const bool pen = (proc & PROC_PENALTY) != 0;
+  const float rep = pen ? q.repetition : 1.f, pres = pen ? q.presence : 0.f, freq = pen ? q.frequency : 0.f;
+#pragma unroll
+  for (int j = 0; j < PROC_EPT; j++) v[j] = proc_penalise(v[j], w[j], rep, pres, freq);
+  const int n_bias = (proc & PROC_BIAS) ? min(q.n_bias, PROC_MAX_BIAS) : 0;
+  if (n_bias > 0) {
+    *reinterpret_cast<f32x4*>(tile + tid * PROC_EPT) = f32x4{v[0], v[1], v[2], v[3]};
+    __syncthreads();
+    for (int k = tid; k < n_bias; k += PROC_WG) {
+      const int e = bias_ids[k] - t0;
+      if (e >= 0 && e < PROC_TILE) tile[e] = proc_add(tile[e], bias_val[k]);
+    }
+    __syncthreads();
+    const f32x4 r = *reinterpret_cast<const f32x4*>(tile + tid * PROC_EPT);
+#pragma unroll
+    for (int j = 0; j < PROC_EPT; j++) v[j] = r[j];
+  }
+}
+// stage 4: the entries that row `nx` of the automaton's table (the state's) does not allow
+__device__ __forceinline__ void proc_mask(float (&v)[PROC_EPT], const unsigned short* nx, int base, int V) {
+  const bool vec = (V & 3) == 0;
+  unsigned int e[PROC_EPT];
+  if (vec && base < V) {
+    const u32x2 r = *reinterpret_cast<const u32x2*>(nx + base);
+    e[0] = r[0] & 0xffffu; e[1] = r[0] >> 16; e[2] = r[1] & 0xffffu; e[3] = r[1] >> 16;
+  } else {
+#pragma unroll
+    for (int j = 0; j < PROC_EPT; j++) e[j] = !vec && base + j < V ? nx[base + j] : 0u;
+  }
+#pragma unroll
+  for (int j = 0; j < PROC_EPT; j++) if (e[j] == AUTO_NONE) v[j] = -INFINITY;
+}
+// the thread's entries into `out` [V], and the tile's (max, lowest index) into *pv / *pi: per thread in index order, across the wave by butterfly, across the four
+// waves through LDS (sv, si: PROC_WG / WAVE words each) — ties -> the lowest index
+__device__ __forceinline__ void proc_store(const float (&v)[PROC_EPT], float* out, int base, int V, float* sv, int* si, float* pv, int* pi) {
+  const int tid = threadIdx.x;
+  if ((V & 3) == 0) {
     if (base < V) *reinterpret_cast<f32x4*>(out + base) = f32x4{v[0], v[1], v[2], v[3]};
   } else {
 #pragma unroll
     for (int j = 0; j < PROC_EPT; j++) if (base + j < V) out[base + j] = v[j];
   }
-  // the tile's (max, lowest index): per thread in index order, across the wave by butterfly, across the four waves through LDS — ties -> the lowest index
   float best = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
   for (int j = 0; j < PROC_EPT; j++)
@@ -173,9 +170,111 @@ __global__ __launch_bounds__(PROC_WG) void logit_proc_kernel(const LogitProcArgs
   if (tid == 0) {
     for (int k = 1; k < PROC_WG / WAVE; k++)
       if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-    a.part_val[(size_t)y * a.n_tile + blockIdx.x] = best;
-    a.part_idx[(size_t)y * a.n_tile + blockIdx.x] = bi;
+    *pv = best; *pi = bi;
   }
+}
+
+__global__ __launch_bounds__(PROC_WG) void logit_proc_kernel(const LogitProcArgs a) {
+  __shared__ __attribute__((aligned(16))) float tile[PROC_TILE];
+  __shared__ float sv[PROC_WG / WAVE];
+  __shared__ int si[PROC_WG / WAVE];
+  const int y = blockIdx.y, t0 = blockIdx.x * PROC_TILE, tid = threadIdx.x, base = t0 + tid * PROC_EPT, V = a.V;
+  const RowReq& q = a.req[y];
+  const int proc = q.proc;
+  const bool on = proc != 0 && !(a.step && q.finished);      // (workgroup-uniform)
+  float v[PROC_EPT];
+  proc_load_raw(a.logits + (size_t)y * a.logits_stride, base, V, v);
+  if (on) {
+    unsigned int* hw = a.hist + (size_t)y * V;
+    unsigned int w[PROC_EPT];
+    proc_load_words(hw, base, V, w);
+    const int tok = a.step ? a.tok[y] : -1;
+#pragma unroll
+    for (int j = 0; j < PROC_EPT; j++)
+      if (base + j == tok && base + j < V) {      // the counting step: this thread owns the current token's word
+        w[j] = proc_count(w[j]);
+        hw[base + j] = w[j];
+      }
+    proc_stages_1_3(v, w, q, proc, a.bias_ids + (size_t)y * PROC_MAX_BIAS, a.bias_val + (size_t)y * PROC_MAX_BIAS, tile, t0, tid);
+    if (proc & PROC_AUTOMATON) proc_mask(v, q.auto_next + (size_t)q.auto_state * V, base, V);      // stage 4
+  }
+  proc_store(v, a.out + (size_t)y * V, base, V, sv, si, a.part_val + (size_t)y * a.n_tile + blockIdx.x, a.part_idx + (size_t)y * a.n_tile + blockIdx.x);
+}
+
+// ---- the processors over the positions of a verify pass (include/tgx.h option verify.processors; csrc/abi.hip verify_row_run / step_tail).  Position i of a
+// row's pass is processed as the row's step i would have been, without running the steps one after another:
+//   the words    w_i[e] = the row's word for e, counted once more per pass input 0 .. i that equals e (at most 16 comparisons per word; proc_count per hit)
+//   the state    s_i = the row's state moved by inputs 0 .. i under automaton_advance_kernel's rule — automaton_walk_kernel, a launch ahead of this one, leaves
+//                every position's state in states[]: one thread per row walks its <= 16 inputs
+//   the vector   stages 1-3 by proc_stages_1_3 (the code logit_proc_kernel runs), stage 4 with s_i
+// Grid (ceil(V / 1024), positions), 256 threads: logit_proc_kernel's tile ownership and 16-byte paths (the pass's slabs come from the device allocator and a
+// position starts at a multiple of V floats: 16-byte aligned when V % 4 == 0).  Only the positions of processed rows are listed: the consumers of an unprocessed
+// row's positions keep the raw pointers.  Nothing of the row is written here — neither its words nor its state: the pass's raw logits in, the processed slab and
+// its per-tile (max, lowest index) partials out.
+// THE COMMIT is the accept workgroup's (kernels/verify.h verify_accept_body, thread 0 behind the walk) and not a launch of its own: the count n stands in that
+// thread's registers, the work is at most 16 read-modify-writes and one state word by ONE thread (an id that occurs twice among the inputs is counted twice, in
+// order, without atomics), and a launch more would cost the call several microseconds for it.  Every reader of the words and the state in this call stands ahead
+// of the accept launch in stream order.
+struct ProcPos { int row, i, slot, pad; const long long* ids; };      // batch row; index within its pass; workspace row; the row's pass inputs on the device [i + 1 read]
+constexpr int PROC_MAX_POS = 64;                                       // == TGX_MAX_VERIFY_POSITIONS
+struct LogitProcPosArgs {
+  const float* logits;           // the pass's raw logits [slots][V]
+  const RowReq* req;             // [max_batch]
+  const unsigned int* hist;      // [max_batch][V]   (read only)
+  const int* bias_ids;           // [max_batch][PROC_MAX_BIAS]
+  const float* bias_val;
+  const int* states;             // [slots] (automaton_walk_kernel)
+  float* out;                    // processed [slots][V]
+  float* part_val; int* part_idx;   // [slots][n_tile]
+  int V, n_tile;
+  ProcPos pos[PROC_MAX_POS];
+};
+struct AutoWalkRow { const RowReq* req; const long long* ids; int first, M; };
+struct AutoWalkArgs { int* states; int n, V; AutoWalkRow r[PROC_MAX_POS]; };
+// states[first_j + i] for the positions of the call's processed rows (rows without an automaton: nothing).  One workgroup, one thread per row; no row state is written
+__global__ __launch_bounds__(PROC_MAX_POS) void automaton_walk_kernel(const AutoWalkArgs a) {
+  const int j = threadIdx.x;
+  if (j >= a.n) return;
+  const AutoWalkRow& r = a.r[j];
+  if (!(r.req->proc & PROC_AUTOMATON)) return;
+  int s = r.req->auto_state;
+  const unsigned short* next = r.req->auto_next;
+  for (int i = 0; i < r.M; i++) {
+    const long long t = r.ids[i];
+    if (t >= 0 && t < a.V) {
+      const unsigned short n = next[(size_t)s * a.V + (size_t)t];
+      if (n != AUTO_NONE) s = n;
+    }
+    a.states[r.first + i] = s;
+  }
+}
+
+__global__ __launch_bounds__(PROC_WG) void logit_proc_pos_kernel(const LogitProcPosArgs a) {
+  __shared__ __attribute__((aligned(16))) float tile[PROC_TILE];
+  __shared__ float sv[PROC_WG / WAVE];
+  __shared__ int si[PROC_WG / WAVE];
+  __shared__ int s_in[VERIFY_MAX_POS];
+  const ProcPos& p = a.pos[blockIdx.y];
+  const int t0 = blockIdx.x * PROC_TILE, tid = threadIdx.x, base = t0 + tid * PROC_EPT, V = a.V;
+  const int n_in = min(p.i + 1, VERIFY_MAX_POS);
+  if (tid < n_in) s_in[tid] = (int)p.ids[tid];      // the inputs 0 .. i, once per workgroup
+  __syncthreads();
+  const RowReq& q = a.req[p.row];
+  const int proc = q.proc;
+  float v[PROC_EPT];
+  proc_load_raw(a.logits + (size_t)p.slot * V, base, V, v);
+  unsigned int w[PROC_EPT];
+  proc_load_words(a.hist + (size_t)p.row * V, base, V, w);
+  for (int k = 0; k < n_in; k++) {
+    const unsigned int d = (unsigned int)(s_in[k] - base);      // (an input outside the thread's four entries: d >= PROC_EPT)
+    if (d < (unsigned int)PROC_EPT) {
+#pragma unroll
+      for (int j = 0; j < PROC_EPT; j++) if (d == (unsigned int)j) w[j] = proc_count(w[j]);
+    }
+  }
+  proc_stages_1_3(v, w, q, proc, a.bias_ids + (size_t)p.row * PROC_MAX_BIAS, a.bias_val + (size_t)p.row * PROC_MAX_BIAS, tile, t0, tid);
+  if (proc & PROC_AUTOMATON) proc_mask(v, q.auto_next + (size_t)a.states[p.slot] * V, base, V);
+  proc_store(v, a.out + (size_t)p.slot * V, base, V, sv, si, a.part_val + (size_t)p.slot * a.n_tile + blockIdx.x, a.part_idx + (size_t)p.slot * a.n_tile + blockIdx.x);
 }
 
 }  // namespace tgx

@@ -26,6 +26,16 @@ struct VerifyArgs {
   const void* wpe;           // GPT-2 learned positions or nullptr
   int H, V, n_pos;
   VerifyRecord* rec;
+  // a row with a logit processor on (option verify.processors; kernels/logit_proc.h logit_proc_pos_kernel): g[i] is chosen from the PROCESSED partials of the
+  // positions, while `logits` / `part_val` / `part_idx` above stay the raw ones — they are what the row's slots receive.  Every other row: the raw pair again
+  const float* sel_part_val;
+  const int* sel_part_idx;
+  long long sel_part_stride;
+  int sel_n_part, pad0;
+  // ... and the commit behind the walk, by thread 0: the row's history words [V] counted by the inputs that produced a token, its state word set to that of the
+  // last producing position (states: the row's slice of automaton_walk_kernel's, or nullptr without an automaton).  hist nullptr: nothing to commit
+  unsigned int* hist;
+  const int* states;
 };
 
 // the pass's first input is the row's device-resident current token: the host need not know it
@@ -48,10 +58,10 @@ __device__ __forceinline__ void verify_accept_body(const VerifyArgs& a, const in
       if (lane == 0) { const int t = a.draws[i]; s_g[i] = (unsigned)t < (unsigned)a.V ? t : 0; }
       continue;
     }
-    const float* pv = a.part_val + (size_t)i * a.part_stride;
-    const int* pi = a.part_idx + (size_t)i * a.part_stride;
+    const float* pv = a.sel_part_val + (size_t)i * a.sel_part_stride;
+    const int* pi = a.sel_part_idx + (size_t)i * a.sel_part_stride;
     float bv = -INFINITY; int bi = 0x7fffffff;
-    for (int p = lane; p < a.n_part; p += 64) {
+    for (int p = lane; p < a.sel_n_part; p += 64) {
       const float v = pv[p]; const int ix = pi[p];
       if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
     }
@@ -65,6 +75,7 @@ __device__ __forceinline__ void verify_accept_body(const VerifyArgs& a, const in
   __syncthreads();
   if (threadIdx.x == 0) {
     RowStopWords w = row_stop_words(a.req, a.tok);
+    const int in0 = *a.tok;      // the pass's input 0
     int n = 0, win = 0;
     if constexpr (TREE) {
       for (int cur = 0; n < a.M;) {                 // (a parent stands below its child: the walk ends within M positions whatever the tables hold)
@@ -88,6 +99,17 @@ __device__ __forceinline__ void verify_accept_body(const VerifyArgs& a, const in
       if (a.req->finished || i + 1 == a.M || a.draft[i] != (long long)t) break;
     }
     a.rec->n = n; a.rec->finish = a.req->finished;
+    if constexpr (!TREE)
+      if (a.hist) {      // a processed row: inputs 0 .. n - 1 are the tokens its n steps consumed — one thread, one after another (an id may occur twice)
+        for (int j = 0; j < n; j++) {
+          const int t = j ? (int)a.draft[j - 1] : in0;
+          if ((unsigned)t >= (unsigned)a.V) continue;
+          const unsigned int h = a.hist[t], c = h & PROC_COUNT_MASK;
+          a.hist[t] = (h & PROC_PROMPT_BIT) | (c < PROC_COUNT_MASK ? c + 1u : c);
+        }
+        if (a.states) a.req->auto_state = a.states[n - 1];
+        a.rec->state = a.req->auto_state;
+      }
     const int np = *a.pos + n;      // the n inputs that produced tokens are in the cache; the rows behind them are dead
     *a.pos = np; *a.tok = s_g[win];
     s_win = win; s_tok = s_g[win]; s_pos = np < a.n_pos ? np : a.n_pos - 1;

@@ -118,13 +118,19 @@ int vs_rezero(tgx_ctx* c) {
   return TGX_OK;
 }
 
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first, const int* depth) {
+void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first, const int* depth, bool processed) {
   const bool joint = joint_first >= 0;      // tgx_verify_rows: the row's slice of the joint pass's workspace; the scratch and lists are the one-row call's (chains are stream-ordered)
   if (!c->vs_draws || !(joint ? c->vj_draws : c->vf_rec) || M > (int)tgx_ctx::VERIFY_ROWS) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
   const int V = c->d.vocab;
   tgx::SampArgs a{};
   a.logits = joint ? c->vj_logits + (size_t)joint_first * V : c->vf_logits; a.logits_stride = V;
   a.part_val = joint ? c->vj_part_val + (size_t)joint_first * c->lm_grid : c->vf_part_val; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
+  if (processed) {      // option verify.processors: the row's positions in the processed slab (launch_logit_proc_positions ran ahead) and its per-tile maxima
+    if (!(joint ? c->vpj_states : c->vp_states)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
+    const int T = proc_tiles(c);
+    a.logits = joint ? c->vpj_logits + (size_t)joint_first * V : c->vp_logits;
+    a.part_val = joint ? c->vpj_part_val + (size_t)joint_first * T : c->vp_part_val; a.part_stride = T; a.n_part = T;
+  }
   a.sc = c->vs_scratch;
   a.V = V; a.idx_bits = 1;
   while ((1 << a.idx_bits) < V) a.idx_bits++;
@@ -236,6 +242,44 @@ int proc_alloc(tgx_ctx* c) {
   }
   HIP_OK(c, hipMemsetAsync(c->proc_hist, 0, B * V * sizeof(unsigned int), c->stream));
   return TGX_OK;
+}
+
+// ---- the processors over a verify pass's positions (kernels/logit_proc.h logit_proc_pos_kernel; option verify.processors)
+static_assert(tgx::PROC_MAX_POS == TGX_MAX_VERIFY_POSITIONS && (int)tgx_ctx::VERIFY_ROWS <= tgx::PROC_MAX_POS, "kernels/logit_proc.h");
+int ensure_verify_proc_ws(tgx_ctx* c, bool joint) {
+  float*& lg = joint ? c->vpj_logits : c->vp_logits; float*& pv = joint ? c->vpj_part_val : c->vp_part_val;
+  int*& pi = joint ? c->vpj_part_idx : c->vp_part_idx; int*& st = joint ? c->vpj_states : c->vp_states;
+  if (st) return TGX_OK;                     // the last of the four: set only when all of them exist
+  const size_t R = joint ? (size_t)tgx_ctx::VERIFY_POSITIONS : (size_t)tgx_ctx::VERIFY_ROWS, V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
+  int rc;
+  if ((rc = dev_alloc(c, &lg, R * V)) || (rc = dev_alloc(c, &pv, R * T)) || (rc = dev_alloc(c, &pi, R * T)) || (rc = dev_alloc(c, &st, R))) {
+    dev_free(c, &lg); dev_free(c, &pv); dev_free(c, &pi); dev_free(c, &st);      // all or nothing, as proc_alloc
+    return rc;
+  }
+  return TGX_OK;
+}
+void launch_logit_proc_positions(tgx_ctx* c, int n, const int* rows, const int* first, const int* lens, const long long* const* ids, const char* processed, bool joint) {
+  if (!c->proc_part_idx || !(joint ? c->vpj_states : c->vp_states) || !(joint ? c->vj_logits : c->vf_logits)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
+  const int slots = joint ? (int)tgx_ctx::VERIFY_POSITIONS : (int)tgx_ctx::VERIFY_ROWS;
+  tgx::AutoWalkArgs w{};
+  tgx::LogitProcPosArgs a{};
+  int np = 0;
+  bool any_auto = false;
+  for (int j = 0; j < n; j++) {
+    if (!processed[j]) continue;
+    if (first[j] < 0 || lens[j] < 1 || lens[j] > (int)tgx_ctx::VERIFY_ROWS || first[j] + lens[j] > slots || np + lens[j] > tgx::PROC_MAX_POS) { c->launch_fault = "processed verification: a row's positions do not fit the workspace"; return; }
+    any_auto = any_auto || (c->row_req_host[(size_t)rows[j]].proc & tgx::PROC_AUTOMATON);
+    w.r[w.n++] = tgx::AutoWalkRow{c->row_req + rows[j], ids[j], first[j], lens[j]};
+    for (int i = 0; i < lens[j]; i++) a.pos[np++] = tgx::ProcPos{rows[j], i, first[j] + i, 0, ids[j]};
+  }
+  if (!np) return;
+  w.states = joint ? c->vpj_states : c->vp_states; w.V = c->d.vocab;
+  if (any_auto) hipLaunchKernelGGL(tgx::automaton_walk_kernel, dim3(1), dim3(tgx::PROC_MAX_POS), 0, c->stream, w);
+  a.logits = joint ? c->vj_logits : c->vf_logits;
+  a.req = c->row_req; a.hist = c->proc_hist; a.bias_ids = c->proc_bias_ids; a.bias_val = c->proc_bias_val; a.states = w.states;
+  a.out = joint ? c->vpj_logits : c->vp_logits; a.part_val = joint ? c->vpj_part_val : c->vp_part_val; a.part_idx = joint ? c->vpj_part_idx : c->vp_part_idx;
+  a.V = c->d.vocab; a.n_tile = proc_tiles(c);
+  hipLaunchKernelGGL(tgx::logit_proc_pos_kernel, dim3((unsigned)a.n_tile, (unsigned)np), dim3(tgx::PROC_WG), 0, c->stream, a);
 }
 
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step) {

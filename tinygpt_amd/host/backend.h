@@ -70,6 +70,9 @@ struct Backend {
   int (*automaton_destroy)(tgx_ctx*, int32_t) = nullptr;
   int (*set_row_automaton)(tgx_ctx*, int, int32_t, int32_t) = nullptr;
   int (*read_row_automaton)(tgx_ctx*, int, int32_t*, int32_t*) = nullptr;
+  // run-time options (optional: GPTConfig::speculateProcessed sets "verify.processors" for the length of a generate call and needs both)
+  int (*set_option)(tgx_ctx*, const char*, int) = nullptr;
+  int (*get_option)(const tgx_ctx*, const char*, int*) = nullptr;
   // scoring a supplied sequence (optional: GPTEngine::score needs it)
   int (*score_row)(tgx_ctx*, int, const int64_t*, int, int, float*, int32_t*, float*) = nullptr;
   // embeddings (optional: GPTEngine::embed needs it)
@@ -107,6 +110,7 @@ struct Backend {
     TGXH_BIND(set_row_sampler, false); TGXH_BIND(set_row_logprobs, false); TGXH_BIND(read_row_logprobs, false);
     TGXH_BIND(set_row_penalties, false); TGXH_BIND(set_row_logit_bias, false); TGXH_BIND(set_row_history, false);
     TGXH_BIND(automaton_create, false); TGXH_BIND(automaton_destroy, false); TGXH_BIND(set_row_automaton, false); TGXH_BIND(read_row_automaton, false);
+    TGXH_BIND(set_option, false); TGXH_BIND(get_option, false);
     TGXH_BIND(score_row, false); TGXH_BIND(embed_rows, false);
     TGXH_BIND(beam_select, false); TGXH_BIND(beam_advance, false);
     TGXH_BIND(row_snapshot_bytes, false); TGXH_BIND(save_row, false); TGXH_BIND(restore_row, false);

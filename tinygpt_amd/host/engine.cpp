@@ -287,12 +287,12 @@ EmbedOutput GPTEngine::embed(const std::vector<std::string>& texts, const EmbedC
 
 // ---- GPTConfig::speculate: prompt-lookup drafts verified in one pass (spec_draft.h, include/tgx.h tgx_verify_row)
 // (which of the two, or neither: spec_mode.h)
-static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int batch, bool processors, size_t stopIds) {
+static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int batch, bool processors, size_t stopIds, bool verifyProcessed) {
   const SamplerConfig& s = cfg.samplerConfig;
   tgxh::SpecInputs in;
   in.speculate = cfg.speculate; in.speculateSampled = cfg.speculateSampled; in.batch = batch;
   in.greedy = !(s.temperature > 0.f || s.topK > 0 || s.topP < 1.f || s.minP > 0.f);      // Sampler.cpp:15-21
-  in.processors = processors; in.stopIds = stopIds; in.maxStopIds = (size_t)TGX_MAX_STOP_IDS;
+  in.processors = processors; in.verifyProcessed = verifyProcessed; in.stopIds = stopIds; in.maxStopIds = (size_t)TGX_MAX_STOP_IDS;
   in.rowStopCalls = be.set_row_stop && be.decode_rows;
   in.verifyRow = be.verify_row != nullptr;
   in.verifyRowSampled = be.verify_row_sampled && be.set_row_sampler && be.sample_row;
@@ -300,8 +300,22 @@ static tgxh::SpecMode spec_mode_of(const GPTConfig& cfg, const Backend& be, int 
   return tgxh::spec_mode(in);
 }
 // (GPTConfig::contextShift: the shifting loops take plain steps — a draft's positions are counted from the sequence, which a shifted row no longer holds in full)
-bool GPTEngine::speculateActive(int batch) const { return !shiftActive() && spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) != tgxh::SpecMode::Off; }
-bool GPTEngine::speculateSampledActive(int batch) const { return !shiftActive() && spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size()) == tgxh::SpecMode::Sampled; }
+bool GPTEngine::speculateActive(int batch) const { return !shiftActive() && spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size(), verifyProcessedOn_) != tgxh::SpecMode::Off; }
+bool GPTEngine::speculateSampledActive(int batch) const { return !shiftActive() && spec_mode_of(config_, be_, batch, processorsOn(), eosTokenIds_.size(), verifyProcessedOn_) == tgxh::SpecMode::Sampled; }
+// GPTConfig::speculateProcessed: the device's verify calls take processed rows only under option verify.processors (include/tgx.h), which the engine holds at 1
+// for the length of a generate call that drafts with processors on.  A backend without the option (or the option calls) keeps the plain steps
+bool GPTEngine::verifyProcessedBegin() {
+  verifyProcessedOn_ = false;
+  if (!config_.speculateProcessed || config_.speculate <= 0 || !processorsOn() || !be_.set_option || !be_.get_option) return false;
+  int was = 0;
+  if (be_.get_option(model_.ctx, "verify.processors", &was) != TGX_OK || be_.set_option(model_.ctx, "verify.processors", 1) != TGX_OK) return false;
+  verifyProcessedWas_ = was; verifyProcessedOn_ = true;
+  return true;
+}
+void GPTEngine::verifyProcessedEnd() {
+  if (verifyProcessedOn_) be_.set_option(model_.ctx, "verify.processors", verifyProcessedWas_);
+  verifyProcessedOn_ = false;
+}
 
 bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
   const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
@@ -593,6 +607,8 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   if (!prepared_ || prompts.empty()) { fail("generateSync: engine not prepared or empty batch"); return out; }
   if (config_.numBeams > 1) return beamsRefused(prompts.size()) ? out : generateBeams(prompts[0], padToken);
   if (logprobsRefused(false) || processorsRefused(false)) return out;
+  verifyProcessedBegin();
+  const auto verifyProcessedOff = at_exit([&] { verifyProcessedEnd(); });
   const int B = (int)prompts.size();
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts(prompts, padToken, S);
@@ -628,37 +644,45 @@ GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& promp
   const auto t1 = std::chrono::steady_clock::now();
   // decode: maxNewTokens-1 iterations, no EOS check (:165-172)
   if (n_new > 1 && B > 1 && speculateActive(B)) {      // a batch: every unfinished row advances through tgx_verify_rows, with its own draft or none
+    // (SamplerConfig::regex under speculateProcessed: the rows end on the device at an EOS id as in the per-row branch below, the pad token behind the stop)
+    const bool constrained = constraintOn();
     std::vector<std::vector<int32_t>> seqs((size_t)B);
+    std::vector<char> finished((size_t)B, 0);
     for (int b = 0; b < B; b++) {
       for (int64_t i = 0; i < S; i++) seqs[(size_t)b].push_back((int32_t)ids[(size_t)(b * S + i)]);
       seqs[(size_t)b].push_back((int32_t)first[(size_t)b]);
-      if (be_.set_row_stop(model_.ctx, b, (int32_t)(n_new - 1), nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+      if (be_.set_row_stop(model_.ctx, b, (int32_t)(n_new - 1), constrained && !eosTokenIds_.empty() ? eosTokenIds_.data() : nullptr, constrained ? (int)eosTokenIds_.size() : 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+      if (constrained && isEosToken((int32_t)first[(size_t)b])) finished[(size_t)b] = 1;
     }
-    std::vector<char> finished((size_t)B, 0);
     std::vector<int64_t> produced;
     auto open = [&] { for (int b = 0; b < B; b++) if (!finished[(size_t)b] && (int64_t)seqs[(size_t)b].size() < S + n_new) return true; return false; };
     while (open()) {
       if (!speculateMoreRows(seqs, S + n_new, finished, produced)) return out;
       for (int b = 0; lpOn && b < B; b++) if (!logprobsDrain(b, produced[(size_t)b], lpRows[(size_t)b])) return out;
     }
+    allStopped = constrained;
     for (int b = 0; b < B; b++) {
-      if ((int64_t)seqs[(size_t)b].size() != S + n_new) { fail("speculate: a row finished before maxNewTokens"); return out; }
-      for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)(i * B + b)] = seqs[(size_t)b][(size_t)(S + 1 + i)];
+      const std::vector<int32_t>& seq = seqs[(size_t)b];
+      if (!constrained && (int64_t)seq.size() != S + n_new) { fail("speculate: a row finished before maxNewTokens"); return out; }
+      for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)(i * B + b)] = S + 1 + i < (int64_t)seq.size() ? seq[(size_t)(S + 1 + i)] : padTokenId();
+      allStopped = allStopped && isEosToken(seq.back());
     }
   } else if (n_new > 1 && speculateActive(B)) {      // ... of which a verified draft covers several at once: no stop ids (no EOS check here), the length on the device
     std::vector<int32_t> seq;
     for (int64_t i = 0; i < S; i++) seq.push_back((int32_t)ids[(size_t)i]);
     seq.push_back((int32_t)first[0]);
-    if (be_.set_row_stop(model_.ctx, 0, (int32_t)(n_new - 1), nullptr, 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
-    bool finished = false;
+    const bool constrained = constraintOn();      // (SamplerConfig::regex under speculateProcessed: as in the batch branch above)
+    if (be_.set_row_stop(model_.ctx, 0, (int32_t)(n_new - 1), constrained && !eosTokenIds_.empty() ? eosTokenIds_.data() : nullptr, constrained ? (int)eosTokenIds_.size() : 0) != TGX_OK) { fail(std::string("set_row_stop: ") + be_.last_error(model_.ctx)); return out; }
+    bool finished = constrained && isEosToken((int32_t)first[0]);
     treeRefused_ = false;      // (GPTConfig::speculateTree: a refusal holds for one call)
     while ((int64_t)seq.size() < S + n_new && !finished) {
       const size_t before = seq.size();
       if (!speculateMore(seq, S + n_new, finished)) return out;
       if (lpOn && !logprobsDrain(0, (int64_t)(seq.size() - before), lpRows[0])) return out;
     }
-    if ((int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
-    for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = seq[(size_t)(S + 1 + i)];
+    if (!constrained && (int64_t)seq.size() != S + n_new) { fail("speculate: the row finished before maxNewTokens"); return out; }
+    for (int64_t i = 0; i + 1 < n_new; i++) rest[(size_t)i] = S + 1 + i < (int64_t)seq.size() ? seq[(size_t)(S + 1 + i)] : padTokenId();
+    allStopped = constrained && isEosToken(seq.back());
   } else if (shift && n_new > 1) {      // GPTConfig::contextShift: the rows may pass the context (decodeRowsShifting)
     const bool constrained = constraintOn();
     std::vector<std::vector<int64_t>> got((size_t)B);
@@ -804,6 +828,8 @@ GPTOutput GPTEngine::generateAsync(const std::vector<int32_t>& prompt, const Gen
   if (!prepared_) { fail("generateAsync: engine not prepared"); return out; }
   if (config_.numBeams > 1) { fail("beam search: generateAsync streams one sequence; use generateSync (numBeams " + std::to_string(config_.numBeams) + ")"); return out; }
   if (logprobsRefused(true) || processorsRefused(true)) return out;
+  verifyProcessedBegin();
+  const auto verifyProcessedOff = at_exit([&] { verifyProcessedEnd(); });
   int64_t S = 0;
   std::vector<int64_t> ids = alignPrompts({prompt}, 0, S);
   if (S == 0) { fail("generateAsync: the prompt is empty (nothing to prefill)"); return out; }

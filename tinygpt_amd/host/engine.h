@@ -84,6 +84,11 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // tgx_decode_rows.  A sampled token is a pure function of its logits and the draw key (seed, token index, row), so the ids are those of the plain loop up to
   // the summation order between kernel paths.  A backend without the call keeps the old loop.
   bool speculateSampled = false;
+  // ... and with logit processors on (default false: every existing run is unchanged — `speculate` falls back to plain steps while a penalty, a logit bias or a
+  // regex is on).  With it set and a backend that takes option "verify.processors" (include/tgx.h), the engine sets that option for the length of the generate
+  // call and keeps drafting: the verify calls process every position of a pass as the row's step would have, so the ids are those of speculate = 0.  Under a
+  // sampling configuration speculateSampled is needed as well; speculateTree falls back to chains (the device refuses a processed row on a tree that is no chain).
+  bool speculateProcessed = false;
   // ... with a token TREE of guesses (default 0 = off: every existing run is unchanged; 1 is the same as 0 — one branch is a chain).  B >= 2 (needs speculate > 0;
   // ONE sequence): where the sequence's tail has
   // occurred before with different continuations, up to B of them share the pass's `speculate` positions as branches below the current token (spec_draft.h
@@ -236,6 +241,7 @@ class GPTEngine {
   int64_t lastReused() const { return lastReused_; }      // prompt tokens the last generate call served from the cache
   void setSpeculate(int maxDraft) { config_.speculate = maxDraft; }
   void setSpeculateSampled(bool on) { config_.speculateSampled = on; }
+  void setSpeculateProcessed(bool on) { config_.speculateProcessed = on; }
   void setSpeculateTree(int branches) { config_.speculateTree = branches; }
   void setLogprobs(int topN) { config_.logprobs = topN; }
   const SamplerConfig& samplerConfig() const { return config_.samplerConfig; }
@@ -304,6 +310,10 @@ class GPTEngine {
   std::vector<int32_t> cached_;      // reusePrefix: the token ids row 0's cache holds, position by position (empty: unknown / nothing)
   int64_t lastReused_ = 0, lastShifts_ = 0;
   SpecStats spec_;
+  bool verifyProcessedBegin();                                // GPTConfig::speculateProcessed: option verify.processors on for this call (false: the backend refused it)
+  void verifyProcessedEnd();                                  // ... and back to what it was
+  bool verifyProcessedOn_ = false;                            // between the two: the verify calls take processed rows (spec_mode.h SpecInputs::verifyProcessed)
+  int verifyProcessedWas_ = 0;
   bool treeRefused_ = false;                                  // GPTConfig::speculateTree: the device refused a tree as unsupported — chain drafts for the rest of the call
   std::string constraintPattern_;            // the pattern and stop ids of the table the device holds (constraintId_ >= 0)
   std::vector<int32_t> constraintStops_;

@@ -72,6 +72,8 @@ TGXE_API int64_t tgxe_last_shifts(tgxe_engine* h) { return h ? h->e->lastShifts(
 TGXE_API void tgxe_set_speculate(tgxe_engine* h, int max_draft) { if (h) h->e->setSpeculate(max_draft); }
 // ... under a sampling configuration as well (GPTConfig::speculateSampled; 0 = off, the default)
 TGXE_API void tgxe_set_speculate_sampled(tgxe_engine* h, int on) { if (h) h->e->setSpeculateSampled(on != 0); }
+// ... with penalties, a logit bias or a regex on (GPTConfig::speculateProcessed; 0 = off, the default)
+TGXE_API void tgxe_set_speculate_processed(tgxe_engine* h, int on) { if (h) h->e->setSpeculateProcessed(on != 0); }
 // ... with token trees (GPTConfig::speculateTree: branches, 0 = off, the default); tgxe_spec_tree_passes = how many of the verify passes ran a tree of two or more branches
 TGXE_API void tgxe_set_speculate_tree(tgxe_engine* h, int branches) { if (h) h->e->setSpeculateTree(branches); }
 TGXE_API int64_t tgxe_spec_tree_passes(tgxe_engine* h) { return h ? h->e->specStats().treePasses : 0; }

@@ -63,6 +63,8 @@ static void usage(const char* prog) {
           "  --speculate <n>           greedy speculative decoding: up to n prompt-lookup draft tokens verified per pass (--temperature 0 --top-p 1; several prompts: every row's\n"
           "                            draft in one joint pass; default: 0 = off)\n"
           "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n"
+          "  --speculate-processed     with --speculate: keep drafting while --regex, a penalty or --logit-bias is on — every position of a verify pass is processed as its\n"
+          "                            step would have been (the ids of the run without --speculate; with a sampling configuration --speculate-sampled as well)\n"
           "  --speculate-tree <b>      with --speculate, one prompt: where the text's tail has continued in different ways before, up to b of them share the pass's\n"
           "                            positions as branches of a token tree, and the device follows the one the model produces (b >= 2; default: 0 = off, 1 is the same: one branch is a chain)\n"
           "  --context-shift           generate past the context: a full row keeps its first --keep positions, drops half of the rest and slides the tail down, its keys\n"
@@ -164,6 +166,7 @@ int main(int argc, char** argv) {
     else if (a == "--num-return") cfg.numReturn = atoi(next());
     else if (a == "--speculate") cfg.speculate = atoi(next());
     else if (a == "--speculate-sampled") cfg.speculateSampled = true;
+    else if (a == "--speculate-processed") cfg.speculateProcessed = true;
     else if (a == "--speculate-tree") cfg.speculateTree = atoi(next());
     else if (a == "--context-shift") cfg.contextShift = true;
     else if (a == "--keep") cfg.shiftKeep = std::max(0, atoi(next()));

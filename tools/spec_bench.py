@@ -28,7 +28,15 @@ interleaved in index order, the second one right: the accepted path is non-conti
 of the same number of positions on the parent commit's library (--parent-lib; without it, on this build) — the median of --reps calls, and beside it the spread of
 the parent's own figure over three repeated medians.  ACCEPTANCE: the host engine free-running with speculate 7, speculateTree 0 against 3, on a text the tool
 generates — a few phrases that share a stem and go on differently, in random order — tokens produced per verify pass, tree passes, ids against speculate 0.
-usage: python tools/spec_bench.py --tree [--parent-lib PATH] [--reps 10] [--out profiles/verify_tree.txt]"""
+usage: python tools/spec_bench.py --tree [--parent-lib PATH] [--reps 10] [--out profiles/verify_tree.txt]
+
+--processors (profiles/verify_processed.txt): the verify calls on a row with logit processors on (option verify.processors), at context 2048.  COST: ms per
+tgx_verify_row at 4 / 8 / 16 positions with a bias list, penalties and an automaton on the row, against the same build's call with no processor on and against one
+tgx_decode_rows step of the processed row on the parent commit's library (--parent-lib; without it, on this build).  Three rounds of --reps interleaved calls:
+the median over all of them, and beside it the spread of the three rounds' medians.  ACCEPTANCE: tgx_cli on a text a regular expression forces (the GPT-2
+geometry with the GPT-2 tokenizer fixture, the one full tokenizer in the tree), --regex --speculate 8 --speculate-processed against --regex alone on the parent
+commit's tgx_cli (--parent-cli; without it, this build's): tokens per verify pass and decode-only tokens per second.
+usage: python tools/spec_bench.py --processors [--parent-lib PATH] [--parent-cli PATH] [--reps 9] [--out profiles/verify_processed.txt]"""
 import argparse
 import ctypes
 import os
@@ -420,6 +428,123 @@ def free_running_tree(lines):
                 "yes" if first_diff is None else "up to new token %d" % first_diff))
 
 
+def measure_processed(reps, lines, parent_lib):
+    from tinygpt_amd.ffi import ABI, Backend
+    d = known_desc("llama-3.2-1b", "bf16")
+    d.max_batch = 1
+    m = Model(d).load_synthetic(1234, 0.02).finalize()
+    m.set_option("verify.processors", 1)
+    old = Model(d, backend=Backend(parent_lib, "tgx_", required=list(ABI))).load_synthetic(1234, 0.02).finalize() if parent_lib else None
+    V = d.vocab
+    prompt = synth.synth_prompt(V, S, 1234)
+    rng = np.random.default_rng(5)
+    bias = {int(t): float(v) for t, v in zip(rng.choice(V, size=64, replace=False), rng.uniform(-2, 2, size=64))}
+    table = np.full((4, V), 0xFFFF, np.uint16)      # four states, each allowing two thirds of the vocabulary
+    for s_ in range(4):
+        ok = (np.arange(V) + s_) % 3 != 0
+        table[s_, ok] = (s_ + 1) % 4
+    aid = {id(mm): mm.automaton_create(table, start=0) for mm in (m, old) if mm is not None}
+
+    def fresh_row(mm, processed):
+        mm.reset_cache()
+        mm.forward_row(0, prompt)
+        if processed:
+            mm.set_row_penalties(0, 1.1, 0.1, 0.1).set_row_logit_bias(0, bias).set_row_history(0, prompt_ids=prompt)
+            mm.set_row_automaton(0, aid[id(mm)], 0)
+        mm.set_row_sampler(0, GREEDY, 0)
+        return int(mm.sample_row(0, GREEDY, 0))
+
+    fresh_row(m, True)
+    ref_p = [int(t) for t in m.decode_rows(16)[0][:, 0]]       # the processed row's own run: the all-right draft
+    fresh_row(m, False)
+    ref_u = [int(t) for t in m.decode_rows(16)[0][:, 0]]
+    ND, ROUNDS = [3, 7, 15], 3
+    lines.append("the row: a bias list of 64 ids, penalties (repetition 1.1, presence 0.1, frequency 0.1) over a history seeded from the prompt, an automaton of 4 states that each "
+                 "allow two thirds of the vocabulary; greedy; unpaged")
+    lines.append("ms per call, synchronised: median over %d rounds x %d interleaved repeats (min .. max) [the rounds' medians: min .. max]" % (ROUNDS, reps))
+    keys = [(n, k) for n in ND for k in ("processed", "plain")] + ["step processed", "parent step processed", "step plain"]
+    t = {k: [[] for _ in range(ROUNDS)] for k in keys}
+    acc = {n: [] for n in ND}
+    for rnd in range(ROUNDS):
+        for rep_ in range(reps + (2 if rnd == 0 else 0)):          # two warm-up repeats, discarded
+            keep = rnd > 0 or rep_ >= 2
+            for n in ND:
+                fresh_row(m, True)
+                ms, r = timed(lambda: m.verify_row(0, ref_p[:n]))
+                if keep:
+                    t[(n, "processed")][rnd].append(ms); acc[n].append(len(r[0]))
+                fresh_row(m, False)
+                ms, _ = timed(lambda: m.verify_row(0, ref_u[:n]))
+                if keep:
+                    t[(n, "plain")][rnd].append(ms)
+            for k, mm, processed in (("step processed", m, True), ("parent step processed", old, True), ("step plain", m, False)):
+                if mm is None:
+                    continue
+                fresh_row(mm, processed)
+                ms, _ = timed(lambda: mm.decode_rows(1))
+                if keep:
+                    t[k][rnd].append(ms)
+
+    def fig(k):
+        flat = [x for r in t[k] for x in r]
+        meds = [statistics.median(r) for r in t[k]]
+        return "%s [%.3f .. %.3f]" % (med(flat), min(meds), max(meds))
+
+    def mid(k):
+        return statistics.median([x for r in t[k] for x in r])
+    for k in ("step plain", "step processed", "parent step processed"):
+        if t[k][0]:
+            lines.append("  one tgx_decode_rows step, %-22s %s" % (k + ":", fig(k)))
+    base_k = "parent step processed" if old is not None else "step processed"
+    lines.append("  positions | verify, processors on | verify, no processor (this build) | surcharge | processed verify / %s | break-even accepted drafts | tokens produced by the all-right draft (median)" % base_k)
+    for n in ND:
+        a_, g_ = mid((n, "processed")), mid((n, "plain"))
+        lines.append("  %9d | %s | %s | %+.3f | %.2f | %.2f | %d of %d" % (n + 1, fig((n, "processed")), fig((n, "plain")), a_ - g_, a_ / mid(base_k), a_ / mid(base_k) - 1,
+                                                                    statistics.median(acc[n]), n + 1))
+    m.close()
+    if old is not None:
+        old.close()
+
+
+def free_running_processed(lines, parent_cli):
+    import re
+    from tinygpt_amd import build
+    from constraint_util import GPT2_DIR
+    _, cli = build.build_host()
+    pattern = r'(\{"answer": "(yes|no)", "sure": (true|false)\}, )+'
+    prompt = 'Answers: {"answer": "yes", "sure": true}, {"answer": "no", "sure": false}, '
+    n_new = 192
+    base = ["--synthetic", "gpt2", "--tokenizer", GPT2_DIR, "--prompt", prompt, "--regex", pattern, "--stop-ids", "50256", "--max-tokens", str(n_new), "--temperature", "0", "--top-p", "1"]
+    runs = {"regex alone (%s)" % ("the parent commit's tgx_cli" if parent_cli else "this build's tgx_cli"): [parent_cli or cli] + base,
+            "regex, speculate 8 (no flag)": [cli] + base + ["--speculate", "8"],
+            "regex, speculate 8, speculate-processed": [cli] + base + ["--speculate", "8", "--speculate-processed"]}
+    lines.append("free-running tgx_cli, GPT-2 geometry (synthetic weights) with the GPT-2 tokenizer, greedy, %d new tokens, pattern %s" % (n_new, pattern))
+    outs = {}
+    for name, cmd in runs.items():
+        rates, stat, text = [], "", ""
+        for _ in range(3):
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                lines.append("  %s: FAILED: %s" % (name, r.stderr.strip()[-200:]))
+                break
+            rates.append(float(re.search(r"decode-only rate: ([0-9.]+) token/s", r.stdout).group(1)))
+            sp = [l for l in r.stdout.splitlines() if l.startswith("speculate:")]
+            stat = sp[0] if sp else ""
+            text = next((l for l in r.stdout.splitlines() if l.startswith("Output:")), "")
+        if not rates:
+            continue
+        outs[name] = text
+        line = "  %-45s decode-only tokens/s over 3 runs: %s" % (name + ":", med(rates))
+        mt = re.search(r"speculate: (\d+) verify passes, (\d+) of (\d+) draft tokens accepted, (\d+) ordinary steps", stat)
+        if mt:
+            p_, a_, dt, st = (int(x) for x in mt.groups())
+            line += " | %d verify passes, %d of %d draft tokens accepted, %d ordinary steps" % (p_, a_, dt, st)
+            if p_:
+                line += ", %.2f tokens per pass" % ((a_ + p_) / p_)
+        lines.append(line)
+    lines.append("  the three outputs are the same text: %s" % ("yes" if len(set(outs.values())) == 1 and len(outs) == 3 else "NO"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -428,7 +553,22 @@ def main():
     ap.add_argument("--sampler", default="", help="T,K,P,M: measure tgx_verify_row_sampled under this sampler instead")
     ap.add_argument("--tree", action="store_true", help="measure tgx_verify_tree instead (profiles/verify_tree.txt)")
     ap.add_argument("--parent-lib", default="", help="with --sampler / --rows: a libtgx_mi355x.so of the parent commit, for the A/B baselines")
+    ap.add_argument("--processors", action="store_true", help="measure the verify calls on a processed row instead (profiles/verify_processed.txt)")
+    ap.add_argument("--parent-cli", default="", help="with --processors: the parent commit's tgx_cli (beside its libraries), for the regex-alone baseline")
     a = ap.parse_args()
+    if a.processors:
+        import torch
+        lines = ["tools/spec_bench.py --processors --reps %d%s%s   device: %s   Llama-3.2-1B bf16 synthetic, prompt %d tokens" % (
+            a.reps, " --parent-lib <parent build>" if a.parent_lib else "", " --parent-cli <parent build>" if a.parent_cli else "", torch.cuda.get_device_name(0), S)]
+        measure_processed(a.reps, lines, a.parent_lib)
+        free_running_processed(lines, a.parent_cli)
+        text = "\n".join(lines) + "\n"
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     if a.tree:
         import torch
         lines = ["tools/spec_bench.py --tree --reps %d%s   device: %s   Llama-3.2-1B bf16 synthetic, prompt %d tokens, unpaged" % (
