@@ -976,6 +976,27 @@ TGX_API int tgx_set_logits(tgx_ctx* ctx, const float* logits, int batch);
  *   "advance.attn_tiles"  (default 16) the attention of a tgx_advance_rows joint pass: a query block whose causal key range exceeds this many 64-key tiles is cut into
  *                  ranges of at most that many (kernels/attn_mixed.h); 0 = never split, -1 = the largest target that gives the launches two workgroups per CU.
  *                  tgx_get_option reads it back, and the read-only "advance.last_form" / "advance.last_tiles" (tgx_advance_rows above)
+ *   "weights.fp8" 0/1  (default 0; set BEFORE tgx_finalize, TGX_ERR_STATE afterwards; bf16 storage, not GPT-2 — anything else makes tgx_finalize return
+ *                  TGX_ERR_UNSUPPORTED) FP8 WEIGHTS, opt-in and LOSSY: tgx_finalize quantizes every matrix of the classes in "weights.fp8_classes" — gate_up
+ *                  (the merged gate | up matrix), down, and lm_head (embed_tokens when tied) — to OCP E4M3 codes with one power-of-two scale per output row and
+ *                  OVERWRITES the bf16 master in place with the dequantized values, so prefill, batched steps, verify / advance passes, score, embed and beam
+ *                  select all compute the same model as the batch-1 step, which streams the codes (kernels/gemv_fp8.h: half the bytes of these matrices per
+ *                  token).  Rule per output row r (the gate and up rows are rows of the merged matrix):
+ *                    1. amax is the largest |w| of the row.  Write amax = m * 2^x with m in [0.5, 1) (frexp).
+ *                    2. e_r = x - 9 if m <= 0.875, else x - 8.  This is the smallest e with amax <= 448 * 2^e.
+ *                    3. Clamp e_r to >= -117, so the smallest non-zero dequantized value stays a normal bf16.
+ *                    4. An all-zero row takes e_r = 0.
+ *                    5. code = round-to-nearest, ties-to-even, of the exact quotient w / 2^e_r onto the OCP e4m3fn grid.  Subnormals of step 2^-9 are
+ *                       included and the sign is kept, so -0 stays -0.  The codes 0x7f and 0xff (NaN) are never produced.
+ *                    6. dq = code * 2^e_r.  It is always exactly representable in bf16.
+ *                    7. A selected matrix that holds a non-finite weight or a |w| >= 2^100 makes tgx_finalize return TGX_ERR_UNSUPPORTED and name the tensor.
+ *                  A context with the option on therefore equals, bit for bit, an ordinary context that was uploaded dq (tests/fp8_ref.py is the rule in numpy).
+ *                  A matrix whose shape the 8-bit stream does not cover (more than 8 chunks of 8 weights per lane: K > 16384) is quantized all the same and
+ *                  served by the plain kernel on the dequantized master.  A class quantized this way gets no exponent-packed copy ("weights.packed").
+ *                  MEMORY: the bf16 masters stay (every multi-row path reads them), so the option COSTS one byte per weight of the selected classes, about
+ *                  1.07 GB on Llama-3.2-1B.  Out of scope: qkv / o_proj, multi-row steps and prefill reading the codes, dropping the masters, pre-quantized
+ *                  checkpoints with other scales, per-group scales, an FP8 KV cache
+ *   "weights.fp8_classes"  (default 7; before tgx_finalize) which classes "weights.fp8" quantizes: bit 0 gate_up, bit 1 down, bit 2 lm_head
  *   "debug.*"      experiment switches (tools/gemv_dissect.py, tools/attn_dissect.py; live only in a -DTGX_DISSECT=1 build) */
 TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
 
@@ -985,14 +1006,17 @@ TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
  *                        o_proj product in the same launch), beyond it the split form
  *   "attn.nw4_limit"     ... and up to this many keys its four-wave variant (0 = never)
  *   "graph.steps"        decode steps per captured multi-step graph
- * Read-only figures: "weights.packed_matrices" / "weights.packed_fallbacks" / "weights.packed_max_row_esc" (after tgx_finalize), "kv.free_tokens" (above), and
+ * Read-only figures: "weights.packed_matrices" / "weights.packed_fallbacks" / "weights.packed_max_row_esc" (after tgx_finalize), "kv.free_tokens" (above),
+ *   "weights.fp8_matrices"   matrices that "weights.fp8" gave an 8-bit stream (after tgx_finalize) ...
+ *   "weights.fp8_fallbacks"  ... and matrices it quantized that the plain kernel serves on the dequantized master, and
  *   "mem.live_allocs"    device buffers the context holds now: weights, caches, and the workspaces that were sized at first use or grown since ...
  *   "mem.live_kib"       ... and their bytes, rounded up to KiB.  A workspace that grows replaces its buffer: a context's figures depend on the largest shapes it has
  *                        served (and on "act.round16" at the last growth), not on the way there — what a test can hold memory to on a device that others use */
 TGX_API int tgx_get_option(const tgx_ctx* ctx, const char* key, int* out_value);
 
 /* Algorithmic HBM bytes one decoded token streams at context length T (SURVEY.md §8d formula).  Matrices stored exponent-packed (option "weights.packed",
- * bf16 storage) count with the bytes the batch-1 step really streams: their packed planes and escape records instead of 2 bytes per weight. */
+ * bf16 storage) count with the bytes the batch-1 step really streams: their packed planes and escape records instead of 2 bytes per weight; matrices with an
+ * 8-bit stream (option "weights.fp8") likewise: their code planes as laid out plus one 4-byte scale per row. */
 TGX_API int64_t tgx_bytes_per_token(const tgx_ctx* ctx, int64_t T);
 
 TGX_API int tgx_abi_version(void);

@@ -912,6 +912,9 @@ int tgx_finalize(tgx_ctx* c) {
     if (d.qk_norm && (!w.q_norm_ok || !w.k_norm_ok)) return set_err(c, TGX_ERR_STATE, "Missing key: model.layers.%d.self_attn.{q,k}_norm.weight", l);
   }
   if (c->finalized) return TGX_OK;
+  // a lossy option that silently does nothing would mislead: the 8-bit form exists for bf16 storage and the RMSNorm families only
+  if (c->weights_fp8 && (c->dt != tgx::DT_BF16 || c->gpt2))
+    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp8 needs bf16 storage and a gated-MLP family (this context: %s%s)", c->dt == tgx::DT_BF16 ? "bf16" : (c->dt == tgx::DT_F16 ? "fp16" : "fp32"), c->gpt2 ? ", GPT-2" : "");
 
   std::vector<float> cs, sn;
   if (c->gpt2) {      // no rotary embedding: the qkv epilogue's rotation becomes the identity
@@ -926,7 +929,8 @@ int tgx_finalize(tgx_ctx* c) {
 
   // one grid for every lm_head launch (it sizes the argmax partials): the packed launch's workgroups per CU where the options ask for a packed lm_head
   // (pack_weights runs below; a lm_head that then falls back, and the batched steps, run their plain kernels on this grid too)
-  const bool lm_packed = c->weights_packed && (c->packed_classes & 4) && c->dt == tgx::DT_BF16 && !c->gpt2;
+  // (an lm_head quantized by weights.fp8 starts at the same value: gemv_fp8.h's launch takes the class's packed_bpc)
+  const bool lm_packed = ((c->weights_packed && (c->packed_classes & 4)) || (c->weights_fp8 && (c->fp8_classes & 4))) && c->dt == tgx::DT_BF16 && !c->gpt2;
   c->lm_grid = gemv_grid(c, (V + 1) / 2, 1, lm_packed ? c->tune[TGX_KERNEL_LMHEAD].packed_bpc : c->tune[TGX_KERNEL_LMHEAD].bpc);
   int ns = c->num_cus / d.kv_heads;
   c->attn_nsplit = ns < 1 ? 1 : (ns > 32 ? 32 : ns);
@@ -1008,7 +1012,7 @@ int tgx_finalize(tgx_ctx* c) {
   c->row_req_host.assign(B, row_req_default());
   if ((rc = dev_alloc(c, &c->row_req, B))) return rc;
   HIP_OK(c, hipMemcpy(c->row_req, c->row_req_host.data(), B * sizeof(tgx::RowReq), hipMemcpyHostToDevice));
-  if ((rc = pack_weights(c))) return rc;
+  if ((rc = quantize_weights(c)) || (rc = pack_weights(c))) return rc;
   c->past = 0;
   c->row_host.assign(B, RowHost{});
   c->finalized = true;
@@ -3005,6 +3009,10 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "weights.packed_matrices")) { *out_value = c->packed_matrices; return TGX_OK; }        // read-only, after tgx_finalize: matrices stored packed ...
   if (!strcmp(key, "weights.packed_fallbacks")) { *out_value = c->packed_fallbacks; return TGX_OK; }      // ... matrices that stayed plain because a row's escape record overflowed ...
   if (!strcmp(key, "weights.packed_max_row_esc")) { *out_value = c->packed_max_row_esc; return TGX_OK; }  // ... and the most escapes seen in one row
+  if (!strcmp(key, "weights.fp8")) { *out_value = c->weights_fp8; return TGX_OK; }
+  if (!strcmp(key, "weights.fp8_classes")) { *out_value = c->fp8_classes; return TGX_OK; }
+  if (!strcmp(key, "weights.fp8_matrices")) { *out_value = c->fp8_matrices; return TGX_OK; }            // read-only, after tgx_finalize: matrices with an 8-bit stream ...
+  if (!strcmp(key, "weights.fp8_fallbacks")) { *out_value = c->fp8_fallbacks; return TGX_OK; }          // ... matrices quantized but served by the plain kernel on the dequantized master
   if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv.free_blocks() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
   if (!strcmp(key, "mem.live_allocs")) { *out_value = (int)c->mem.live(); return TGX_OK; }                     // read-only: device buffers the context holds now ...
   if (!strcmp(key, "mem.live_kib")) { *out_value = (int)((c->mem.live_bytes() + 1023) / 1024); return TGX_OK; }  // ... and their bytes, rounded up to KiB
@@ -3071,6 +3079,12 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
     else c->weights_packed = value != 0;
     return TGX_OK;
   }
+  if (!strcmp(key, "weights.fp8") || !strcmp(key, "weights.fp8_classes")) {
+    if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the weights are quantized there)", key);
+    if (key[11] == '_') { if (value < 0 || value > 7) return set_err(c, TGX_ERR_INVALID, "weights.fp8_classes is a mask of gate_up (1), down (2), lm_head (4)"); c->fp8_classes = value; }
+    else { if (value != 0 && value != 1) return set_err(c, TGX_ERR_INVALID, "weights.fp8 is 0 or 1"); c->weights_fp8 = value; }
+    return TGX_OK;
+  }
   if (!strcmp(key, "kv.budget_tokens")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "kv.budget_tokens is set before tgx_finalize (it sizes the caches)");
     if (value < 0) return set_err(c, TGX_ERR_INVALID, "kv.budget_tokens >= 0 (0 = one max_ctx slab per row)");
@@ -3121,6 +3135,10 @@ int64_t tgx_bytes_per_token(const tgx_ctx* c, int64_t T) {
   auto packed_saving = [&](const PackedMat& m, int64_t rows, int64_t cols) { if (m.P) saved += b * rows * cols - rows * (m.row_bytes + 16 * m.ks); };      // (one 16-byte record per row and K-part)
   for (const LayerW& w : c->L) { packed_saving(w.pgu, 2 * I, H); packed_saving(w.pdown, H, I); }
   packed_saving(c->plm, V, H);
+  // matrices quantized by option weights.fp8 stream their code planes and one 4-byte scale per row
+  auto fp8_saving = [&](const Fp8Mat& m, int64_t rows, int64_t cols) { if (m.Q) saved += b * rows * cols - rows * (m.row_bytes + 4); };
+  for (const LayerW& w : c->L) { fp8_saving(w.qgu, 2 * I, H); fp8_saving(w.qdown, H, I); }
+  fp8_saving(c->qlm, V, H);
   return b * (L * per_layer + H + V * H) + b * 2 * L * kv * T - saved;
 }
 

@@ -49,10 +49,21 @@ struct PackedMat {
   long long n_esc = 0;            // escapes of the matrix
 };
 
+// the 8-bit stream of a matrix quantized by option weights.fp8 (kernels/gemv_fp8.h): E4M3 codes in the batch-1 launch's layout and one power-of-two scale per
+// row, made in tgx_finalize; the bf16 master beside it holds the dequantized values.  Q == nullptr: no stream (option off, class not selected, or a shape the
+// layout does not cover — the plain kernel then reads the dequantized master)
+struct Fp8Mat {
+  unsigned char* Q = nullptr;     // code planes, N * row_bytes
+  float* scale = nullptr;         // [N] 2^e_r
+  long long row_bytes = 0;
+  int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
+};
+
 struct LayerW {
   ebyte *in_norm = nullptr, *post_norm = nullptr;
   ebyte *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
   PackedMat pgu, pdown;         // wgu / wdown exponent-packed
+  Fp8Mat qgu, qdown;            // wgu / wdown as 8-bit streams (option weights.fp8)
   ebyte *q_norm = nullptr, *k_norm = nullptr;   // Qwen3 [head_dim]
   bool q_norm_ok = false, k_norm_ok = false;
   // one bit per checkpoint tensor that lands in a merged weight: q, k, v, gate, up (bits 0-4) and the q/k/v biases (bits 5-7) — a tensor
@@ -177,6 +188,12 @@ struct tgx_ctx {
   // packed_matrices / packed_fallbacks: matrices packed / fallen back to plain
   int weights_packed = 1, packed_classes = 5, packed_matrices = 0, packed_fallbacks = 0, packed_max_row_esc = 0;
   PackedMat plm;                // the lm_head matrix (embed when tied) exponent-packed
+  // option weights.fp8 (read at tgx_finalize; default 0, lossy): the matrices of the classes in weights.fp8_classes (bit 0 gate_up, 1 down, 2 lm_head) are
+  // quantized to E4M3 codes with a power-of-two scale per row (the rule: include/tgx.h); the bf16 masters are overwritten with the dequantized values, so every
+  // path computes the same model, and the batch-1 launches read the 8-bit streams.  A class quantized this way gets no exponent-packed copy.
+  // fp8_matrices / fp8_fallbacks: matrices with a stream / quantized but served by the plain kernel
+  int weights_fp8 = 0, fp8_classes = 7, fp8_matrices = 0, fp8_fallbacks = 0;
+  Fp8Mat qlm;                   // the lm_head matrix (embed when tied) as an 8-bit stream
   float *rope_cos = nullptr, *rope_sin = nullptr;
   std::vector<RowState> rows;   // views into the per-row slabs below (constant row stride: batched GEMV walks them)
   float *slab_x = nullptr, *slab_q = nullptr, *slab_kraw = nullptr, *slab_attn = nullptr, *slab_h = nullptr, *slab_logits = nullptr;
@@ -470,6 +487,7 @@ bool is_greedy(const tgx_sampler_cfg* s);   // Sampler.cpp:15-21
 bool row_records(const tgx_ctx* c, int row);   // the row records log-probabilities in the steps (tgx_set_row_logprobs; not while it is retired)
 // ---- decode.hip (kernels/gemv.h, kernels/oproj_sliced.h)
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc);
+int quantize_weights(tgx_ctx* c); // tgx_finalize, ahead of pack_weights: option weights.fp8 (dequantized masters in place, the 8-bit streams and row scales)
 int pack_weights(tgx_ctx* c);     // tgx_finalize: the exponent-packed copies of the bf16 gate_up / down / lm_head matrices (option weights.packed)
 bool oproj_sliced_ok(const tgx_ctx* c, int R, long long kv_stride);
 bool oproj_fused_capable(const tgx_ctx* c);                               // static conditions (geometry, dtype, option)

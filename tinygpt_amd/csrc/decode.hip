@@ -6,6 +6,7 @@
 #include "kernels/attn_decode.h"
 #include "kernels/gemv.h"
 #include "kernels/gemv_packed.h"
+#include "kernels/gemv_fp8.h"
 #include "kernels/oproj_sliced.h"
 #include "kernels/verify.h"
 #include "kernels/kv_tree.h"
@@ -113,20 +114,106 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
 int pack_weights(tgx_ctx* c) {
   const tgx_model_desc& d = c->d;
   if (!c->weights_packed || c->dt != tgx::DT_BF16 || c->gpt2) return TGX_OK;      // (GPT-2's LayerNorm / GELU launches have no packed form)
+  const int classes = c->packed_classes & ~(c->weights_fp8 ? c->fp8_classes : 0);      // a class quantized by weights.fp8 streams its codes: a packed copy would never be read
   int* stat_dev = nullptr;
   int rc = dev_alloc(c, &stat_dev, 4);
   for (size_t l = 0; l < c->L.size() && !rc; l++) {
     LayerW& w = c->L[l];
-    if (c->packed_classes & 1) rc = pack_matrix(c, w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, stat_dev, &w.pgu);
-    if (!rc && (c->packed_classes & 2) && d.inter <= 16384) rc = pack_matrix(c, w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, stat_dev, &w.pdown);
+    if (classes & 1) rc = pack_matrix(c, w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, stat_dev, &w.pgu);
+    if (!rc && (classes & 2) && d.inter <= 16384) rc = pack_matrix(c, w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, stat_dev, &w.pdown);
   }
-  if (!rc && (c->packed_classes & 4)) rc = pack_matrix(c, d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, stat_dev, &c->plm);
+  if (!rc && (classes & 4)) rc = pack_matrix(c, d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, stat_dev, &c->plm);
   dev_free(c, &stat_dev);
   return rc;
 }
 
+// ---- FP8 weights (kernels/gemv_fp8.h; option weights.fp8) ----
+template <int PRO, int EPI, int NX>
+static void launch_gemv_fp8_nx(tgx_ctx* c, const tgx::GemvFp8Args& p, int grid) {
+  const dim3 g(grid), b(256);
+  if constexpr (EPI != tgx::EPI_LOGITS) {      // the fixed-point residual stream behind the K-sliced o_proj (launch_gemv_nx)
+    if (p.g.x_acc || p.g.res_acc) { hipLaunchKernelGGL((tgx::gemv_fp8_kernel<PRO, EPI, NX, true>), g, b, p.g.x_acc ? (size_t)p.g.K * 4 : 0, c->stream, p); return; }
+  }
+  hipLaunchKernelGGL((tgx::gemv_fp8_kernel<PRO, EPI, NX, false>), g, b, 0, c->stream, p);
+}
+
 template <int PRO, int EPI>
-static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const PackedMat* pk = nullptr) {
+static void launch_gemv_fp8(tgx_ctx* c, const tgx::GemvArgs& a, const Fp8Mat& q, int grid, int nx) {
+  tgx::GemvFp8Args p{};
+  p.g = a; p.Q = q.Q; p.scale = q.scale; p.row_bytes = q.row_bytes;
+  switch (nx) {
+    case 1: launch_gemv_fp8_nx<PRO, EPI, 1>(c, p, grid); break;
+    case 2: launch_gemv_fp8_nx<PRO, EPI, 2>(c, p, grid); break;
+    case 3: launch_gemv_fp8_nx<PRO, EPI, 3>(c, p, grid); break;
+    case 4: launch_gemv_fp8_nx<PRO, EPI, 4>(c, p, grid); break;
+    case 5: launch_gemv_fp8_nx<PRO, EPI, 5>(c, p, grid); break;
+    case 6: launch_gemv_fp8_nx<PRO, EPI, 6>(c, p, grid); break;
+    case 7: launch_gemv_fp8_nx<PRO, EPI, 7>(c, p, grid); break;
+    default: launch_gemv_fp8_nx<PRO, EPI, 8>(c, p, grid); break;
+  }
+}
+
+// The matrices of the classes in weights.fp8_classes, quantized where they lie (the rule: include/tgx.h).  Two launches per matrix: the row scales and the
+// check for weights the rule refuses — all matrices first, so that nothing is overwritten when one is refused — then the dequantized master, the codes in the
+// layout of the class's batch-1 launch and nothing else.  A matrix whose shape the layout does not cover is quantized all the same and keeps no stream.
+int quantize_weights(tgx_ctx* c) {
+  const tgx_model_desc& d = c->d;
+  if (!c->weights_fp8) return TGX_OK;
+  struct Job { ebyte* W; int N, K, cls, layer; Fp8Mat* out; };
+  std::vector<Job> jobs;
+  for (size_t l = 0; l < c->L.size(); l++) {
+    LayerW& w = c->L[l];
+    if (c->fp8_classes & 1) jobs.push_back({w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, (int)l, &w.qgu});
+    if (c->fp8_classes & 2) jobs.push_back({w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, (int)l, &w.qdown});
+  }
+  if (c->fp8_classes & 4) jobs.push_back({d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, -1, &c->qlm});
+  if (jobs.empty()) return TGX_OK;
+  int* stat_dev = nullptr;
+  int rc = dev_alloc(c, &stat_dev, jobs.size());
+  if (rc) return rc;
+  std::vector<float*> scale(jobs.size(), nullptr);
+  std::vector<int> stat(jobs.size(), INT_MAX);
+  auto drop = [&]() { for (float*& s : scale) if (s) dev_free(c, &s); dev_free(c, &stat_dev); };
+  if (hipMemcpyAsync(stat_dev, stat.data(), stat.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) { drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: the status upload failed"); }
+  for (size_t i = 0; i < jobs.size(); i++) {
+    if ((rc = dev_alloc(c, &scale[i], (size_t)jobs[i].N))) { drop(); return rc; }
+    hipLaunchKernelGGL(tgx::fp8_row_scale_kernel, dim3(jobs[i].N), dim3(64), 0, c->stream, reinterpret_cast<const bf16_t*>(jobs[i].W), jobs[i].K, scale[i], stat_dev + i);
+  }
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(stat.data(), stat_dev, stat.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) { drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: the scan of the weights failed"); }
+  for (size_t i = 0; i < jobs.size(); i++) {
+    if (stat[i] >= jobs[i].N) continue;
+    const Job& j = jobs[i];
+    char name[96];
+    if (j.cls == TGX_KERNEL_LMHEAD) snprintf(name, sizeof name, "%s", d.tied ? "model.embed_tokens.weight" : "lm_head.weight");
+    else snprintf(name, sizeof name, "model.layers.%d.mlp.%s_proj.weight", j.layer, j.cls == TGX_KERNEL_DOWN ? "down" : (stat[i] < d.inter ? "gate" : "up"));
+    drop();
+    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp8: %s holds a non-finite weight or one of magnitude 2^100 or more (row %d)", name, stat[i]);
+  }
+  for (size_t i = 0; i < jobs.size(); i++) {
+    const Job& j = jobs[i];
+    const int ks = gemv_auto_ks(j.K, c->tune[j.cls].ks), nx = gemv_nx(j.K, ks);
+    const bool stream = j.K % 8 == 0 && nx <= 8;
+    Fp8Mat m;
+    tgx::Fp8QuantArgs a{};
+    a.W = reinterpret_cast<bf16_t*>(j.W); a.K = j.K; a.ks = ks; a.nx = nx; a.scale = scale[i];
+    if (stream) {
+      m.ks = ks; m.row_bytes = (long long)ks * ((nx + 1) / 2) * 1024; m.scale = scale[i];
+      if ((rc = dev_alloc(c, &m.Q, (size_t)j.N * (size_t)m.row_bytes))) { drop(); return rc; }
+      if (hipMemsetAsync(m.Q, 0, (size_t)j.N * (size_t)m.row_bytes, c->stream) != hipSuccess) { dev_free(c, &m.Q); drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: clearing the code planes failed"); }
+      a.Q = m.Q; a.row_bytes = m.row_bytes;
+    }
+    hipLaunchKernelGGL(tgx::fp8_quant_rows_kernel, dim3(j.N), dim3(64), 0, c->stream, a);
+    if (stream) { *j.out = m; scale[i] = nullptr; c->fp8_matrices++; }      // (the stream keeps its scales)
+    else c->fp8_fallbacks++;
+  }
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+  drop();
+  return ok ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "weights.fp8: quantizing the weights failed");
+}
+
+template <int PRO, int EPI>
+static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const PackedMat* pk = nullptr, const Fp8Mat* q8 = nullptr) {
   const Tune& tn = c->tune[cls];
   a.dbg = ((c->debug_gemv >> (8 + cls)) & 1) ? (c->debug_gemv & 15) : 0;
   if (!a.ldw) a.ldw = a.K;
@@ -138,6 +225,12 @@ static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const Packe
   const int grid = (EPI == tgx::EPI_LOGITS) ? c->lm_grid : gemv_grid(c, a.units, a.ks, tn.bpc);
   const int nx = gemv_nx(a.K, a.ks);
   if constexpr ((PRO == tgx::PRO_RMSNORM && (EPI == tgx::EPI_SILU_MUL || EPI == tgx::EPI_LOGITS)) || (PRO == tgx::PRO_PLAIN && EPI == tgx::EPI_RESIDUAL)) {
+    // batch 1 over a matrix quantized by option weights.fp8 with a stream laid out for this K split: half the bytes, bit-identical to the plain kernel over the
+    // dequantized master (workgroups per CU: the class's packed_bpc — no other value has been measured yet, profiles/weights_fp8.txt)
+    if (q8 && q8->Q && R == 1 && q8->ks == a.ks && a.ldw == a.K && !a.dbg) {
+      launch_gemv_fp8<PRO, EPI>(c, a, *q8, (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc), nx);
+      return;
+    }
     // batch 1 over an exponent-packed matrix laid out for this K split: 25 % fewer bytes, bit-identical results
     // (its own workgroups per CU, Tune::packed_bpc; the lm_head's grid is lm_grid in both forms: it sizes the argmax partials)
     if (pk && pk->P && R == 1 && pk->ks == a.ks && a.ldw == a.K && !a.dbg) {
@@ -296,7 +389,7 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
       }
       a.N = 2 * I; a.K = H; a.units = I; a.out = r.h; a.out_stride = I; a.hd = 2;
       if (resid_fixed(c, R, kv_stride)) a.x_acc = c->slab_acc + (size_t)(&r - c->rows.data()) * H;     // x' = fp32(acc)
-      launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_SILU_MUL>(c, a, TGX_KERNEL_GATEUP, R, &w.pgu);
+      launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_SILU_MUL>(c, a, TGX_KERNEL_GATEUP, R, &w.pgu, &w.qgu);
       break;
     }
     case TGX_KERNEL_DOWN: {  // down_proj + residual                                  (GatedMLP.h:40, DecoderLayer.h:41)
@@ -315,7 +408,7 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
         break;
       }
       if (resid_fixed(c, R, kv_stride)) a.res_acc = c->slab_acc + (size_t)(&r - c->rows.data()) * H;   // x = fp32(acc) + down(h); acc <- 0
-      launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, a, TGX_KERNEL_DOWN, R, &w.pdown);
+      launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, a, TGX_KERNEL_DOWN, R, &w.pdown, &w.qdown);
       break;
     }
     default: return 0;
@@ -349,7 +442,7 @@ void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_va
     launch_gemv<tgx::PRO_LAYERNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R);
     return;
   }
-  launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R, &c->plm);
+  launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R, &c->plm, &c->qlm);
 }
 
 tgx::FinalizeArgs make_finalize_args(tgx_ctx* c, int row, bool advance_pos, bool log_step) {

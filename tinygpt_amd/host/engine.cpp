@@ -54,11 +54,13 @@ bool GPTEngine::prepare() {
     return fail("device '" + config_.device + "' is not provided by this engine (only --device mi355x); the reference's cpu path lives in TinyTorch");
   if (!be_.open(lib, prefix)) return fail("cannot bind device shim " + lib + ": " + be_.error);
 
+  LoadOptions loadOpts;
+  loadOpts.weightsFp8 = config_.weightsFp8;
   if (!config_.synthetic.empty()) {
     if (!known_config(config_.synthetic, config_.dtype, config_.maxBatch, model_.config)) return fail("unknown synthetic config: " + config_.synthetic);
-    if (!load_synthetic(be_, model_.config, config_.deviceOrdinal, 1234, 0.02, &model_.ctx, err_)) return fail("Prepare failed: " + err_);
+    if (!load_synthetic(be_, model_.config, config_.deviceOrdinal, 1234, 0.02, &model_.ctx, err_, loadOpts)) return fail("Prepare failed: " + err_);
   } else {
-    if (!load_model_dir(be_, config_.modelDir, config_.deviceOrdinal, config_.dtype, config_.maxBatch, model_, err_)) return fail("Prepare failed: " + err_);
+    if (!load_model_dir(be_, config_.modelDir, config_.deviceOrdinal, config_.dtype, config_.maxBatch, model_, err_, loadOpts)) return fail("Prepare failed: " + err_);
   }
   // tokenizer: optional for the id entry points, required for the text ones (ModelLoader.cpp:60-69 always loads it)
   const std::string tdir = !config_.tokenizerDir.empty() ? config_.tokenizerDir : config_.modelDir;
@@ -1130,9 +1132,11 @@ bool known_config(const std::string& key, int compute_dtype, int max_batch, Mode
   return false;
 }
 
-bool load_synthetic(const Backend& be, const ModelConfig& cfg, int device_ordinal, uint64_t seed, double std_dev, tgx_ctx** ctx, std::string& err) {
+bool load_synthetic(const Backend& be, const ModelConfig& cfg, int device_ordinal, uint64_t seed, double std_dev, tgx_ctx** ctx, std::string& err,
+                    const LoadOptions& opts) {
   const tgx_model_desc& d = cfg.desc;
   if (be.create(&d, device_ordinal, ctx) != TGX_OK) { err = std::string("create failed: ") + be.last_error(*ctx); if (*ctx) be.destroy(*ctx); *ctx = nullptr; return false; }
+  if (!apply_load_options(be, *ctx, opts, err)) { be.destroy(*ctx); *ctx = nullptr; return false; }
   const int64_t H = d.hidden, I = d.inter, V = d.vocab, qd = (int64_t)d.heads * d.head_dim, kvd = (int64_t)d.kv_heads * d.head_dim;
   std::vector<uint16_t> buf;
   auto put = [&](const std::string& name, int64_t r, int64_t c) -> bool {

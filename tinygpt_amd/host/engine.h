@@ -116,6 +116,12 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   float lengthPenalty = 1.f;
   bool earlyStopping = false;
   int numReturn = 1;
+  // Not in the reference: FP8 weights (include/tgx.h option "weights.fp8"; default false: every run as it was).  Opt-in and LOSSY: the loader sets the option
+  // between tgx_create and tgx_finalize, which quantizes the gate_up, down and lm_head matrices to E4M3 codes with a power-of-two scale per row — every path then
+  // computes the quantized model, and the batch-1 step streams half the bytes of those matrices.  It costs one more byte per quantized weight of device memory.
+  // prepare() FAILS with a message that names the option when the backend has no tgx_set_option or refuses the key, and when tgx_finalize refuses the model
+  // (a storage dtype other than bf16, GPT-2, a non-finite weight): it never continues unquantized.
+  bool weightsFp8 = false;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -323,6 +329,7 @@ class GPTEngine {
 // Deterministic synthetic checkpoint — bit-identical to tinygpt_amd/synth.py (same integer hash).
 void synth_tensor_bf16(uint64_t seed, const std::string& name, size_t n, double std_dev, uint16_t* out);
 bool known_config(const std::string& key, int compute_dtype, int max_batch, ModelConfig& out);
-bool load_synthetic(const Backend& be, const ModelConfig& cfg, int device_ordinal, uint64_t seed, double std_dev, tgx_ctx** ctx, std::string& err);
+bool load_synthetic(const Backend& be, const ModelConfig& cfg, int device_ordinal, uint64_t seed, double std_dev, tgx_ctx** ctx, std::string& err,
+                    const LoadOptions& opts = LoadOptions());
 
 }  // namespace tgxh

@@ -24,12 +24,19 @@ static void keep_logprobs(tgxe_engine* h, tgxh::GPTOutput& r) {
 
 TGXE_API tgxe_engine* tgxe_create2(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
                                    const char* prefix, int device_ordinal, int dtype, int max_batch, const char* tokenizer_dir);
+TGXE_API tgxe_engine* tgxe_create3(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
+                                   const char* prefix, int device_ordinal, int dtype, int max_batch, const char* tokenizer_dir, int weights_fp8);
 TGXE_API tgxe_engine* tgxe_create(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
                                   const char* prefix, int device_ordinal, int dtype, int max_batch) {
   return tgxe_create2(model_dir, synthetic, device, backend_lib, prefix, device_ordinal, dtype, max_batch, nullptr);
 }
 TGXE_API tgxe_engine* tgxe_create2(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
                                    const char* prefix, int device_ordinal, int dtype, int max_batch, const char* tokenizer_dir) {
+  return tgxe_create3(model_dir, synthetic, device, backend_lib, prefix, device_ordinal, dtype, max_batch, tokenizer_dir, 0);
+}
+// ... and GPTConfig::weightsFp8 (FP8 weights, include/tgx.h option "weights.fp8"): fixed at creation like the dtype — tgxe_prepare quantizes or fails
+TGXE_API tgxe_engine* tgxe_create3(const char* model_dir, const char* synthetic, const char* device, const char* backend_lib,
+                                   const char* prefix, int device_ordinal, int dtype, int max_batch, const char* tokenizer_dir, int weights_fp8) {
   tgxh::GPTConfig c;
   c.modelDir = model_dir ? model_dir : "";
   c.synthetic = synthetic ? synthetic : "";
@@ -43,6 +50,7 @@ TGXE_API tgxe_engine* tgxe_create2(const char* model_dir, const char* synthetic,
 #endif
   c.deviceOrdinal = device_ordinal;
   c.dtype = dtype;
+  c.weightsFp8 = weights_fp8 != 0;
   c.maxBatch = max_batch;
   if (tokenizer_dir) c.tokenizerDir = tokenizer_dir;
   auto* h = new tgxe_engine();

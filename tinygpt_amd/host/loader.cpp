@@ -217,12 +217,24 @@ bool load_safetensors(const Backend& be, tgx_ctx* ctx, const std::string& path, 
   return true;
 }
 
+bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts, std::string& err) {
+  if (!opts.weightsFp8) return true;
+  if (!be.set_option) { err = "weightsFp8: the device shim exports no tgx_set_option, so option weights.fp8 cannot be set"; return false; }
+  if (be.set_option(ctx, "weights.fp8", 1) != TGX_OK) {
+    const char* why = be.last_error(ctx);
+    err = std::string("weightsFp8: the device shim refused option weights.fp8") + (why && *why ? std::string(": ") + why : std::string());
+    return false;
+  }
+  return true;
+}
+
 bool load_model_dir(const Backend& be, const std::string& dir, int device_ordinal, int compute_dtype, int max_batch,
-                    LoadedModel& out, std::string& err) {
+                    LoadedModel& out, std::string& err, const LoadOptions& opts) {
   if (!load_model_config(join_path(dir, "config.json"), compute_dtype, max_batch, out.config, err)) return false;
   if (!load_generation_config(join_path(dir, "generation_config.json"), out.generation, err)) return false;   // required (ModelLoader.cpp:34-38)
   int rc = be.create(&out.config.desc, device_ordinal, &out.ctx);
   if (rc != TGX_OK) { err = std::string("create failed: ") + be.last_error(out.ctx); if (out.ctx) be.destroy(out.ctx); out.ctx = nullptr; return false; }
+  if (!apply_load_options(be, out.ctx, opts, err)) { be.destroy(out.ctx); out.ctx = nullptr; return false; }
   std::string mp = join_path(dir, "model.safetensors");
   if (!file_exists(mp)) mp = join_path(dir, "model.safetensors.index.json");          // ModelLoader.cpp:72-75
   int loaded = 0;

@@ -45,7 +45,15 @@ struct LoadedModel {
   GenerationConfig generation;
   tgx_ctx* ctx = nullptr;
 };
+// What a load sets on the context between tgx_create and tgx_finalize (the options that are read there).  weightsFp8: option "weights.fp8" = 1
+// (include/tgx.h) — a backend without tgx_set_option, or one that refuses the key, FAILS the load with a message that names it: a lossy option is never
+// dropped silently.
+struct LoadOptions {
+  bool weightsFp8 = false;
+};
+bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts, std::string& err);
+
 bool load_model_dir(const Backend& be, const std::string& dir, int device_ordinal, int compute_dtype, int max_batch,
-                    LoadedModel& out, std::string& err);
+                    LoadedModel& out, std::string& err, const LoadOptions& opts = LoadOptions());
 
 }  // namespace tgxh

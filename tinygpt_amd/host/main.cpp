@@ -25,6 +25,8 @@ static void usage(const char* prog) {
           "  --synthetic <name>        instead of --model: llama-3.2-1b | llama-3.2-3b | qwen2.5-0.5b | mistral-7b-v0.3 (deterministic weights)\n"
           "  --device <mi355x>         device type (default: mi355x)\n"
           "  --dtype <bf16>            data type (default: bf16)\n"
+          "  --weights-fp8             FP8 weights (opt-in, lossy): gate_up, down and lm_head are quantized to E4M3 codes with a power-of-two scale per row when\n"
+          "                            the model is loaded (bf16 only); the run fails if the device library cannot do it (default: off)\n"
           "  --max-tokens <n>          max new tokens (default: 32)\n"
           "  --temperature <f>         sampling temperature (default: 0.8)\n"
           "  --top-p <f>               top-p sampling (default: 0.9)\n"
@@ -132,6 +134,7 @@ int main(int argc, char** argv) {
     else if (a == "--synthetic") cfg.synthetic = next();
     else if (a == "--device") cfg.device = next();
     else if (a == "--dtype") dtype = next();
+    else if (a == "--weights-fp8") cfg.weightsFp8 = true;
     else if (a == "--max-tokens") cfg.maxNewTokens = atoi(next());
     else if (a == "--temperature") cfg.samplerConfig.temperature = strtof(next(), nullptr);
     else if (a == "--top-p") cfg.samplerConfig.topP = strtof(next(), nullptr);
