@@ -1007,6 +1007,16 @@ TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
  *   "attn.nw4_limit"     ... and up to this many keys its four-wave variant (0 = never)
  *   "graph.steps"        decode steps per captured multi-step graph
  * Read-only figures: "weights.packed_matrices" / "weights.packed_fallbacks" / "weights.packed_max_row_esc" (after tgx_finalize), "kv.free_tokens" (above),
+ *   "weights.fp8_rows"  (default 0 = off; 0 or 3..64, anything else TGX_ERR_INVALID; any time, before or after tgx_finalize; drops the step graphs; no effect without
+ *                  "weights.fp8") the largest number of activation rows whose gate_up / down / lm_head products STREAM THE CODES on the matrix cores
+ *                  (kernels/skinny_fp8.h) instead of the dequantized bf16 master: tgx_decode / tgx_decode_rows steps of 3..64 rows, and the verify, extend and
+ *                  short-prompt passes of up to 64 workspace rows.  Same bits: the kernel keeps the panel / ring kernels' accumulation order, so ids and logits
+ *                  are those of the option at 0 with "skinny.ksplit" 0 (the K-split kernel, which a streamed product bypasses, sums in another order).
+ *                  A product the kernel does not cover (K or a split's K range no multiple of 512, activations not stored two-term bf16, 65..128 rows) is
+ *                  served from the master and counted.  Measured on Llama-3.2-1B at context 2048 (profiles/weights_fp8_rows.txt): pays at 16 and 32 rows
+ *                  (-1.0 %, -3.8 % per step), LOSES at 4, 8 and 64 rows (+2.7 %, +1.7 %, +4.8 %) — set it for batches of 16..32 rows on this shape.
+ *   "weights.fp8_row_products"   (read-only) product launches issued on the code stream (a launch recorded into a graph counts once, at capture) ...
+ *   "weights.fp8_row_fallbacks"  ... and products of a quantized matrix inside the row limit that were served from the master
  *   "weights.fp8_matrices"   matrices that "weights.fp8" gave an 8-bit stream (after tgx_finalize) ...
  *   "weights.fp8_fallbacks"  ... and matrices it quantized that the plain kernel serves on the dequantized master, and
  *   "mem.live_allocs"    device buffers the context holds now: weights, caches, and the workspaces that were sized at first use or grown since ...

@@ -22,7 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvi
          ] + (["-mllvm", "-amdgpu-mfma-vgpr-form"] if os.environ.get("TGX_VGPR_FORM", "1") == "1" else [])
 
 
-TUS = ["abi", "decode", "attn", "sampler", "prefill", "prefill_f32", "skinny"]     # csrc/<name>.hip, compiled in parallel (csrc/ctx.h lists what each holds)
+TUS = ["abi", "decode", "attn", "sampler", "prefill", "prefill_f32", "skinny", "skinny_fp8"]     # csrc/<name>.hip, compiled in parallel (csrc/ctx.h lists what each holds)
+# per-unit flags.  skinny_fp8: no packed fp32 arithmetic — the decode's eight multiplies per chunk stay scalar v_mul_f32
+TU_FLAGS = {"skinny_fp8": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 
@@ -50,7 +52,7 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags=()):
         src, obj = os.path.join(CSRC, tu + ".hip"), os.path.join(OBJDIR, tu + ".o")
         fresh = same_flags and os.path.exists(obj) and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in deps + [src])
         if force or not fresh:
-            cmd = [HIPCC] + cflags + ["-c", src, "-o", obj]
+            cmd = [HIPCC] + cflags + TU_FLAGS.get(tu, []) + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             jobs.append((tu, subprocess.Popen(cmd)))

@@ -3013,6 +3013,9 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "weights.fp8_classes")) { *out_value = c->fp8_classes; return TGX_OK; }
   if (!strcmp(key, "weights.fp8_matrices")) { *out_value = c->fp8_matrices; return TGX_OK; }            // read-only, after tgx_finalize: matrices with an 8-bit stream ...
   if (!strcmp(key, "weights.fp8_fallbacks")) { *out_value = c->fp8_fallbacks; return TGX_OK; }          // ... matrices quantized but served by the plain kernel on the dequantized master
+  if (!strcmp(key, "weights.fp8_rows")) { *out_value = c->fp8_rows; return TGX_OK; }
+  if (!strcmp(key, "weights.fp8_row_products")) { *out_value = c->fp8_row_products; return TGX_OK; }    // read-only: skinny product launches issued on the code stream (a graph's count once, at capture) ...
+  if (!strcmp(key, "weights.fp8_row_fallbacks")) { *out_value = c->fp8_row_fallbacks; return TGX_OK; }  // ... products of a quantized matrix inside the row limit but served from the master
   if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv.free_blocks() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
   if (!strcmp(key, "mem.live_allocs")) { *out_value = (int)c->mem.live(); return TGX_OK; }                     // read-only: device buffers the context holds now ...
   if (!strcmp(key, "mem.live_kib")) { *out_value = (int)((c->mem.live_bytes() + 1023) / 1024); return TGX_OK; }  // ... and their bytes, rounded up to KiB
@@ -3084,6 +3087,10 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
     if (key[11] == '_') { if (value < 0 || value > 7) return set_err(c, TGX_ERR_INVALID, "weights.fp8_classes is a mask of gate_up (1), down (2), lm_head (4)"); c->fp8_classes = value; }
     else { if (value != 0 && value != 1) return set_err(c, TGX_ERR_INVALID, "weights.fp8 is 0 or 1"); c->weights_fp8 = value; }
     return TGX_OK;
+  }
+  if (!strcmp(key, "weights.fp8_rows")) {      // any time; without weights.fp8 it has no effect (the step graphs were dropped above)
+    if (value != 0 && (value < 3 || value > 64)) return set_err(c, TGX_ERR_INVALID, "weights.fp8_rows is 0 (off) or a row count 3..64");
+    c->fp8_rows = value; return TGX_OK;
   }
   if (!strcmp(key, "kv.budget_tokens")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "kv.budget_tokens is set before tgx_finalize (it sizes the caches)");

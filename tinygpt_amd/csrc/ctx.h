@@ -194,6 +194,10 @@ struct tgx_ctx {
   // fp8_matrices / fp8_fallbacks: matrices with a stream / quantized but served by the plain kernel
   int weights_fp8 = 0, fp8_classes = 7, fp8_matrices = 0, fp8_fallbacks = 0;
   Fp8Mat qlm;                   // the lm_head matrix (embed when tied) as an 8-bit stream
+  // option weights.fp8_rows (any time; default 0 = off, else 3..64): skinny products of up to that many activation rows over a quantized matrix stream its codes
+  // (kernels/skinny_fp8.h).  fp8_row_products / fp8_row_fallbacks: product launches issued on the code stream / inside the limit but served from the master
+  // (a launch recorded into a graph counts once, at capture)
+  int fp8_rows = 0, fp8_row_products = 0, fp8_row_fallbacks = 0;
   float *rope_cos = nullptr, *rope_sin = nullptr;
   std::vector<RowState> rows;   // views into the per-row slabs below (constant row stride: batched GEMV walks them)
   float *slab_x = nullptr, *slab_q = nullptr, *slab_kraw = nullptr, *slab_attn = nullptr, *slab_h = nullptr, *slab_logits = nullptr;
@@ -589,3 +593,8 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
 void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr, const TreePass* tree = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB); tree (NB == 1, no rg): the S positions are a token tree's
 void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x = nullptr);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
 int skinny_set_attrs(tgx_ctx* c);
+// ---- skinny_fp8.hip (kernels/skinny_fp8.h)
+namespace tgx { struct GemmArgs; }
+bool skinny_fp8_covers(const tgx_ctx* c, const Fp8Mat& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)
+void launch_skinny_fp8(tgx_ctx* c, const tgx::GemmArgs& g, const Fp8Mat& q, int epi, int mb, int nsplit);
+int skinny_fp8_set_attrs(tgx_ctx* c);

@@ -56,6 +56,7 @@ bool GPTEngine::prepare() {
 
   LoadOptions loadOpts;
   loadOpts.weightsFp8 = config_.weightsFp8;
+  loadOpts.weightsFp8Rows = config_.weightsFp8Rows;
   if (!config_.synthetic.empty()) {
     if (!known_config(config_.synthetic, config_.dtype, config_.maxBatch, model_.config)) return fail("unknown synthetic config: " + config_.synthetic);
     if (!load_synthetic(be_, model_.config, config_.deviceOrdinal, 1234, 0.02, &model_.ctx, err_, loadOpts)) return fail("Prepare failed: " + err_);

@@ -122,6 +122,9 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // prepare() FAILS with a message that names the option when the backend has no tgx_set_option or refuses the key, and when tgx_finalize refuses the model
   // (a storage dtype other than bf16, GPT-2, a non-finite weight): it never continues unquantized.
   bool weightsFp8 = false;
+  // ... and the batched steps, verify / extend passes and short prompts of up to this many rows stream the codes as well (option "weights.fp8_rows": 0 = off, the
+  // default, or 3..64; read with weightsFp8 only).  Same bits as without it.  A value the backend refuses fails prepare() with a message that names the option.
+  int weightsFp8Rows = 0;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -249,6 +252,12 @@ class GPTEngine {
   void setSpeculateSampled(bool on) { config_.speculateSampled = on; }
   void setSpeculateProcessed(bool on) { config_.speculateProcessed = on; }
   void setSpeculateTree(int branches) { config_.speculateTree = branches; }
+  // GPTConfig::weightsFp8Rows; after prepare() the option is set on the live context (false: the backend refused the value)
+  bool setWeightsFp8Rows(int rows) {
+    if (model_.ctx && config_.weightsFp8 && (!be_.set_option || be_.set_option(model_.ctx, "weights.fp8_rows", rows) != TGX_OK)) return false;
+    config_.weightsFp8Rows = rows;
+    return true;
+  }
   void setLogprobs(int topN) { config_.logprobs = topN; }
   const SamplerConfig& samplerConfig() const { return config_.samplerConfig; }
   void setProcessors(float repetition, float presence, float frequency, std::map<int32_t, float> bias) {      // kept by the C view across tgxe_reconfigure

@@ -225,6 +225,11 @@ bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts
     err = std::string("weightsFp8: the device shim refused option weights.fp8") + (why && *why ? std::string(": ") + why : std::string());
     return false;
   }
+  if (opts.weightsFp8Rows && be.set_option(ctx, "weights.fp8_rows", opts.weightsFp8Rows) != TGX_OK) {
+    const char* why = be.last_error(ctx);
+    err = std::string("weightsFp8Rows: the device shim refused option weights.fp8_rows") + (why && *why ? std::string(": ") + why : std::string());
+    return false;
+  }
   return true;
 }
 

@@ -48,8 +48,10 @@ struct LoadedModel {
 // What a load sets on the context between tgx_create and tgx_finalize (the options that are read there).  weightsFp8: option "weights.fp8" = 1
 // (include/tgx.h) — a backend without tgx_set_option, or one that refuses the key, FAILS the load with a message that names it: a lossy option is never
 // dropped silently.
+// weightsFp8Rows: option "weights.fp8_rows" (0 = not set; only read with weightsFp8) — refused values fail the load the same way.
 struct LoadOptions {
   bool weightsFp8 = false;
+  int weightsFp8Rows = 0;
 };
 bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts, std::string& err);
 

@@ -27,6 +27,7 @@ static void usage(const char* prog) {
           "  --dtype <bf16>            data type (default: bf16)\n"
           "  --weights-fp8             FP8 weights (opt-in, lossy): gate_up, down and lm_head are quantized to E4M3 codes with a power-of-two scale per row when\n"
           "                            the model is loaded (bf16 only); the run fails if the device library cannot do it (default: off)\n"
+          "  --weights-fp8-rows <n>    with --weights-fp8: batched steps and passes of up to n rows (3..64) stream the codes too; same output (default: 0 = off)\n"
           "  --max-tokens <n>          max new tokens (default: 32)\n"
           "  --temperature <f>         sampling temperature (default: 0.8)\n"
           "  --top-p <f>               top-p sampling (default: 0.9)\n"
@@ -135,6 +136,7 @@ int main(int argc, char** argv) {
     else if (a == "--device") cfg.device = next();
     else if (a == "--dtype") dtype = next();
     else if (a == "--weights-fp8") cfg.weightsFp8 = true;
+    else if (a == "--weights-fp8-rows") cfg.weightsFp8Rows = atoi(next());
     else if (a == "--max-tokens") cfg.maxNewTokens = atoi(next());
     else if (a == "--temperature") cfg.samplerConfig.temperature = strtof(next(), nullptr);
     else if (a == "--top-p") cfg.samplerConfig.topP = strtof(next(), nullptr);

@@ -14,7 +14,7 @@ from tinygpt_amd import build as B
 
 def spills(tu):
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [B.HIPCC] + [f for f in B.FLAGS if f != "-shared"] + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(B.CSRC, tu + ".hip"), "-o", os.path.join(tmp, "x.o")]
+        cmd = [B.HIPCC] + [f for f in B.FLAGS if f != "-shared"] + B.TU_FLAGS.get(tu, []) + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(B.CSRC, tu + ".hip"), "-o", os.path.join(tmp, "x.o")]
         err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     out, cur = [], None
     for line in err.splitlines():

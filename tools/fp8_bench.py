@@ -10,7 +10,13 @@ Per model (the bench.py point: a 2048-token prefill, 16 warm-up steps, 256 timed
   * the per-class kernel times of tgx_profile_decode for both and the effective TB/s of the gate_up / down / lm_head launches (bytes the launch streams / time);
   * what the option does to the model: the largest and the RMS difference of the unrounded last-position logits against the base context over the timed
     steps (both contexts fed the BASE context's greedy ids, so every step compares the same position), and where the free-running greedy ids first differ.
-The figures are reported, not asserted: synthetic weights say little about a trained model's quality."""
+The figures are reported, not asserted: synthetic weights say little about a trained model's quality.
+
+    python tools/fp8_bench.py --rows [--parent-lib PATH]       # option weights.fp8_rows: writes profiles/weights_fp8_rows.txt
+
+--rows: ms per tgx_decode_rows step at 4, 8, 16, 32 and 64 rows and ms per 16-position tgx_verify_row pass, Llama-3.2-1B bf16, every row at context --prompt;
+base = weights.fp8 = 1 with weights.fp8_rows = 0 (the parent's launches; with --parent-lib the parent commit's library with weights.fp8 = 1 is timed beside it),
+against weights.fp8_rows = 64 on the SAME context, the two settings alternating, median of the rounds' medians with the spread.  Same bits either way."""
 import argparse
 import os
 import statistics
@@ -32,8 +38,10 @@ ap.add_argument("--warmup", type=int, default=16)
 ap.add_argument("--steps", type=int, default=256)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--reps", type=int, default=3, help="timed regions per context and round (the round's figure is their median)")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "weights_fp8.txt"))
+ap.add_argument("--out", default=None)
+ap.add_argument("--rows", action="store_true", help="measure option weights.fp8_rows instead (profiles/weights_fp8_rows.txt)")
 args = ap.parse_args()
+args.out = args.out or os.path.join(ROOT, "profiles", "weights_fp8_rows.txt" if args.rows else "weights_fp8.txt")
 
 lines = []
 
@@ -81,6 +89,81 @@ def class_table(m, d, fp8):
 
 
 parent = Backend(args.parent_lib, "tgx_", required=list(ABI)) if args.parent_lib else None
+
+
+def rows_bench():
+    """option weights.fp8_rows on the batched step and a verify pass"""
+    steps, ROWS = min(args.steps, 64), (4, 8, 16, 32, 64)
+    d = known_desc("llama-3.2-1b", "bf16")
+    d.max_ctx, d.max_batch = args.prompt + 256, max(ROWS)
+    ctxs = {"this": Model(d, product_backend())}
+    if parent:
+        ctxs["parent"] = Model(d, parent)
+    for m in ctxs.values():
+        m.set_option("weights.fp8", 1)
+        for tname, bits in synth.synth_checkpoint(d, 1234, 0.02):
+            m.upload(tname, bits)
+        m.finalize()
+    prompt = synth.synth_prompt(d.vocab, args.prompt, 1234)
+
+    def step_ms(m, rows, fp8_rows):
+        if fp8_rows is not None:
+            m.set_option("weights.fp8_rows", fp8_rows)
+        m.reset_cache()
+        for r in range(rows):
+            m.forward_row(r, prompt)
+            m.sample_row(r, GREEDY)
+        m.decode_rows(args.warmup)
+        m.synchronize()
+        t0 = time.perf_counter()
+        m.decode_rows(steps)
+        m.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / steps
+
+    def verify_ms(m, rows, fp8_rows):
+        """one 16-position pass (15 draft tokens; all rejected or not, the pass is the same work), timed over `steps` passes on a row kept at the prompt"""
+        if fp8_rows is not None:
+            m.set_option("weights.fp8_rows", fp8_rows)
+        ts = []
+        for _ in range(8):
+            m.reset_cache()
+            m.forward_row(0, prompt)
+            first = m.sample_row(0, GREEDY)
+            m.synchronize()
+            t0 = time.perf_counter()
+            m.verify_row(0, [first] * 15)
+            m.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts[1:])
+
+    say("# option weights.fp8_rows: batched steps and verify passes stream the FP8 codes on the matrix cores (kernels/skinny_fp8.h) — tools/fp8_bench.py --rows")
+    say(f"# Llama-3.2-1B bf16, every row at context {args.prompt}; {args.warmup} warm-up + {steps} timed tgx_decode_rows steps; {args.rounds} rounds, settings alternating; ms (spread of the rounds)")
+    say("# base = weights.fp8 1, weights.fp8_rows 0 (the parent's launches); rows64 = weights.fp8_rows 64; parent = the parent commit's library with weights.fp8 1")
+    settings = [("base", "this", 0), ("rows64", "this", 64)] + ([("parent", "parent", None)] if parent else [])
+    for what, fn, points in (("tgx_decode_rows step", step_ms, ROWS), ("16-position tgx_verify_row pass (host call included)", verify_ms, (1,))):
+        for rows in points:
+            for label, key, v in settings:
+                fn(ctxs[key], rows, v)                          # untimed: workspaces, graphs
+            got = {label: [] for label, _, _ in settings}
+            for _ in range(args.rounds):
+                for label, key, v in settings:
+                    got[label].append(fn(ctxs[key], rows, v))
+            med = {k: statistics.median(v) for k, v in got.items()}
+            spread = max(max(v) - min(v) for v in got.values())
+            verdict = "faster" if med["base"] - med["rows64"] > spread else ("SLOWER" if med["rows64"] - med["base"] > spread else "within the spread")
+            say(f"{what}, {rows} rows: " + "   ".join(f"{k} {med[k]:.4f} ({max(got[k]) - min(got[k]):.4f})" for k in got) +
+                f"   rows64 - base {med['rows64'] - med['base']:+.4f} ms = {100 * (med['rows64'] - med['base']) / med['base']:+.1f} %: {verdict}")
+    m = ctxs["this"]
+    say(f"code-stream products issued {m.get_option('weights.fp8_row_products')}, fallbacks {m.get_option('weights.fp8_row_fallbacks')}")
+    say("per-launch us of gate_up / down / lm_head and their effective TB/s at 1 B/weight: NOT MEASURED (tgx_profile_decode times the batch-1 step only)")
+
+
+if args.rows:
+    rows_bench()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 say("# option weights.fp8: FP8 (E4M3, one power-of-two scale per row) gate_up / down / lm_head streams at batch 1 — tools/fp8_bench.py")
 say(f"# base context: {'the parent commit library at its defaults' if parent else 'this library with weights.fp8 = 0 (the parent launches and bits)'}")
 say(f"# point: {args.prompt}-token prefill, {args.warmup} warm-up steps, {args.steps} timed greedy steps; {args.rounds} rounds x {args.reps} regions per context, contexts alternating")
