@@ -997,6 +997,34 @@ TGX_API int tgx_set_logits(tgx_ctx* ctx, const float* logits, int batch);
  *                  1.07 GB on Llama-3.2-1B.  Out of scope: qkv / o_proj, multi-row steps and prefill reading the codes, dropping the masters, pre-quantized
  *                  checkpoints with other scales, per-group scales, an FP8 KV cache
  *   "weights.fp8_classes"  (default 7; before tgx_finalize) which classes "weights.fp8" quantizes: bit 0 gate_up, bit 1 down, bit 2 lm_head
+ *   "weights.fp4" 0/1  (default 0; set BEFORE tgx_finalize, TGX_ERR_STATE afterwards; bf16 storage, not GPT-2 — anything else makes tgx_finalize return
+ *                  TGX_ERR_UNSUPPORTED) MXFP4 WEIGHTS, opt-in and LOSSY: as "weights.fp8", but every matrix of the classes in "weights.fp4_classes" is
+ *                  quantized to OCP E2M1 codes with one E8M0 scale byte per block of 32 — 4.25 bits per weight in the batch-1 step's stream
+ *                  (kernels/gemv_fp4.h) — and its bf16 master is OVERWRITTEN in place with the dequantized values, so every path computes the same model.
+ *                  Rule, on the bf16 patterns, per output row (the gate and up rows are rows of the merged matrix) and per block b of 32 consecutive k
+ *                  (the last block of a row may be shorter):
+ *                    1. amax is the largest |w| of the block.  If amax == 0 then e = 0.  Otherwise write amax = m * 2^x with m in [1, 2): e = x - 2 if
+ *                       m <= 1.5, else e = x - 1, so the scaled amax lies in (3, 6] and nothing ever saturates.  Clamp e >= -125, so the smallest non-zero
+ *                       dequantized value 0.5 * 2^e is a normal bf16; a block of bf16 subnormals takes the clamp.
+ *                    2. code = the sign bit plus the E2M1 magnitude nearest to the exact quotient |w| / 2^e on the grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  Ties go
+ *                       to the code whose low bit is 0: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4.  -0 keeps its sign (code 8).
+ *                    3. The scale byte is e + 127 (E8M0; 255 is never written).
+ *                    4. dq = code * 2^e.  It is always exactly a bf16; the master is overwritten with it.
+ *                    5. A selected matrix that holds a non-finite weight or a |w| >= 2^100 makes tgx_finalize return TGX_ERR_UNSUPPORTED and name the tensor.
+ *                  No rounding mode, denormal mode or convert instruction decides a code: the quantizer is integer arithmetic.  A context with the option on
+ *                  therefore equals, bit for bit, an ordinary context that was uploaded dq (tests/fp4_ref.py is the rule in numpy).  A matrix whose shape the
+ *                  4-bit stream does not cover (K % 32 != 0, or more than 8 chunks of 8 weights per lane) is quantized all the same and served by
+ *                  the plain kernel on the dequantized master; a down matrix beyond 16384 columns (the 70B geometry) streams as the K ranges of its launches.
+ *                  The stream holds 4.25 bits per weight wherever K is a multiple of 512 times the launch's K split (the 1B / 3B / 7B / 70B shapes), else
+ *                  whole lanes of padding on top.  "weights.fp8" may be on as well when the two class masks are disjoint (an FP4 MLP under an
+ *                  FP8 head: "weights.fp4_classes" 3, "weights.fp8_classes" 4); a class selected by both makes tgx_finalize return TGX_ERR_INVALID.  A class
+ *                  quantized by either gets no exponent-packed copy; "weights.fp8_rows" reaches only matrices with an 8-bit stream.
+ *                  MEMORY: the bf16 masters stay (every multi-row path reads them), so the option COSTS about 0.53 bytes per weight of the selected classes.
+ *                  MEASURED (profiles/weights_fp4.txt): the step beats the "weights.fp8" step by more than the rounds' spread on both models — Llama-3.2-1B
+ *                  0.5147 -> 0.4619 ms per step (0.6144 at the defaults), Mistral-7B geometry 2.2617 -> 1.8762 ms (2.7944) — and no class lost: gate_up, down and
+ *                  lm_head are each faster than their 8-bit launches.  It stays off by default because it changes the model.
+ *                  Out of scope: qkv / o_proj, multi-row paths reading the codes, dropping the masters, pre-quantized MXFP4 checkpoints, FP4 activations
+ *   "weights.fp4_classes"  (default 7; before tgx_finalize) which classes "weights.fp4" quantizes: bit 0 gate_up, bit 1 down, bit 2 lm_head
  *   "debug.*"      experiment switches (tools/gemv_dissect.py, tools/attn_dissect.py; live only in a -DTGX_DISSECT=1 build) */
 TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
 
@@ -1018,7 +1046,8 @@ TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
  *   "weights.fp8_row_products"   (read-only) product launches issued on the code stream (a launch recorded into a graph counts once, at capture) ...
  *   "weights.fp8_row_fallbacks"  ... and products of a quantized matrix inside the row limit that were served from the master
  *   "weights.fp8_matrices"   matrices that "weights.fp8" gave an 8-bit stream (after tgx_finalize) ...
- *   "weights.fp8_fallbacks"  ... and matrices it quantized that the plain kernel serves on the dequantized master, and
+ *   "weights.fp8_fallbacks"  ... and matrices it quantized that the plain kernel serves on the dequantized master,
+ *   "weights.fp4_matrices" / "weights.fp4_fallbacks"  the same two figures of "weights.fp4", and
  *   "mem.live_allocs"    device buffers the context holds now: weights, caches, and the workspaces that were sized at first use or grown since ...
  *   "mem.live_kib"       ... and their bytes, rounded up to KiB.  A workspace that grows replaces its buffer: a context's figures depend on the largest shapes it has
  *                        served (and on "act.round16" at the last growth), not on the way there — what a test can hold memory to on a device that others use */
@@ -1026,7 +1055,8 @@ TGX_API int tgx_get_option(const tgx_ctx* ctx, const char* key, int* out_value);
 
 /* Algorithmic HBM bytes one decoded token streams at context length T (SURVEY.md §8d formula).  Matrices stored exponent-packed (option "weights.packed",
  * bf16 storage) count with the bytes the batch-1 step really streams: their packed planes and escape records instead of 2 bytes per weight; matrices with an
- * 8-bit stream (option "weights.fp8") likewise: their code planes as laid out plus one 4-byte scale per row. */
+ * 8-bit stream (option "weights.fp8") likewise: their code planes as laid out plus one 4-byte scale per row; matrices with a
+ * 4-bit stream (option "weights.fp4"): their planes as laid out, codes and block scale bytes. */
 TGX_API int64_t tgx_bytes_per_token(const tgx_ctx* ctx, int64_t T);
 
 TGX_API int tgx_abi_version(void);

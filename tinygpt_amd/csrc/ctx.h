@@ -59,11 +59,21 @@ struct Fp8Mat {
   int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
 };
 
+// the 4-bit stream of a matrix quantized by option weights.fp4 (kernels/gemv_fp4.h): planes of E2M1 codes and E8M0 block scales in the batch-1 launch's layout,
+// made in tgx_finalize; the bf16 master beside it holds the dequantized values.  Q == nullptr: no stream, as for Fp8Mat
+struct Fp4Mat {
+  unsigned char* Q = nullptr;     // codes and block scales: `parts` K ranges one after the other, each N * row_bytes
+  long long row_bytes = 0;
+  int ks = 0;                     // the K split a range is laid out for: a launch with another split takes the plain kernel
+  int K = 0, parts = 1;           // the K range of one launch (the whole K unless the class's launch is split: down beyond 16384) and their number
+};
+
 struct LayerW {
   ebyte *in_norm = nullptr, *post_norm = nullptr;
   ebyte *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
   PackedMat pgu, pdown;         // wgu / wdown exponent-packed
   Fp8Mat qgu, qdown;            // wgu / wdown as 8-bit streams (option weights.fp8)
+  Fp4Mat fgu, fdown;            // wgu / wdown as 4-bit streams (option weights.fp4)
   ebyte *q_norm = nullptr, *k_norm = nullptr;   // Qwen3 [head_dim]
   bool q_norm_ok = false, k_norm_ok = false;
   // one bit per checkpoint tensor that lands in a merged weight: q, k, v, gate, up (bits 0-4) and the q/k/v biases (bits 5-7) — a tensor
@@ -194,6 +204,11 @@ struct tgx_ctx {
   // fp8_matrices / fp8_fallbacks: matrices with a stream / quantized but served by the plain kernel
   int weights_fp8 = 0, fp8_classes = 7, fp8_matrices = 0, fp8_fallbacks = 0;
   Fp8Mat qlm;                   // the lm_head matrix (embed when tied) as an 8-bit stream
+  // option weights.fp4 (read at tgx_finalize; default 0, lossy): the same for MXFP4 — E2M1 codes with an E8M0 scale per block of 32 k of a row (the rule:
+  // include/tgx.h).  A class may be selected by weights.fp8 or by weights.fp4, not by both (tgx_finalize: TGX_ERR_INVALID).
+  // fp4_matrices / fp4_fallbacks: matrices with a stream / quantized but served by the plain kernel
+  int weights_fp4 = 0, fp4_classes = 7, fp4_matrices = 0, fp4_fallbacks = 0;
+  Fp4Mat flm;                   // the lm_head matrix (embed when tied) as a 4-bit stream
   // option weights.fp8_rows (any time; default 0 = off, else 3..64): skinny products of up to that many activation rows over a quantized matrix stream its codes
   // (kernels/skinny_fp8.h).  fp8_row_products / fp8_row_fallbacks: product launches issued on the code stream / inside the limit but served from the master
   // (a launch recorded into a graph counts once, at capture)
@@ -492,6 +507,7 @@ bool row_records(const tgx_ctx* c, int row);   // the row records log-probabilit
 // ---- decode.hip (kernels/gemv.h, kernels/oproj_sliced.h)
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc);
 int quantize_weights(tgx_ctx* c); // tgx_finalize, ahead of pack_weights: option weights.fp8 (dequantized masters in place, the 8-bit streams and row scales)
+int quantize_weights_fp4(tgx_ctx* c); // ... and option weights.fp4 (dequantized masters in place, the 4-bit streams with their block scales)
 int pack_weights(tgx_ctx* c);     // tgx_finalize: the exponent-packed copies of the bf16 gate_up / down / lm_head matrices (option weights.packed)
 bool oproj_sliced_ok(const tgx_ctx* c, int R, long long kv_stride);
 bool oproj_fused_capable(const tgx_ctx* c);                               // static conditions (geometry, dtype, option)
@@ -593,6 +609,12 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
 void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr, const TreePass* tree = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB); tree (NB == 1, no rg): the S positions are a token tree's
 void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x = nullptr);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
 int skinny_set_attrs(tgx_ctx* c);
+// ---- decode_fp4.hip (kernels/gemv_fp4.h)
+namespace tgx { struct GemvArgs; }
+void launch_gemv_fp4(tgx_ctx* c, int cls, const tgx::GemvArgs& a, const Fp4Mat& q, int grid, int nx);      // cls: TGX_KERNEL_GATEUP / DOWN / LMHEAD picks the form
+void fp4_scan_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int* stat_dev);                             // *stat_dev = min(*stat_dev, the lowest row the rule refuses)
+long long fp4_row_bytes(int ks, int nx);
+void fp4_quant_matrix(tgx_ctx* c, ebyte* W, int N, int K, int ldw, int ks, int nx, unsigned char* Q, long long row_bytes);      // K columns of rows ldw apart; Q == nullptr: the master only
 // ---- skinny_fp8.hip (kernels/skinny_fp8.h)
 namespace tgx { struct GemmArgs; }
 bool skinny_fp8_covers(const tgx_ctx* c, const Fp8Mat& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)

@@ -114,7 +114,7 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
 int pack_weights(tgx_ctx* c) {
   const tgx_model_desc& d = c->d;
   if (!c->weights_packed || c->dt != tgx::DT_BF16 || c->gpt2) return TGX_OK;      // (GPT-2's LayerNorm / GELU launches have no packed form)
-  const int classes = c->packed_classes & ~(c->weights_fp8 ? c->fp8_classes : 0);      // a class quantized by weights.fp8 streams its codes: a packed copy would never be read
+  const int classes = c->packed_classes & ~(c->weights_fp8 ? c->fp8_classes : 0) & ~(c->weights_fp4 ? c->fp4_classes : 0);      // a class quantized by weights.fp8 / weights.fp4 streams its codes: a packed copy would never be read
   int* stat_dev = nullptr;
   int rc = dev_alloc(c, &stat_dev, 4);
   for (size_t l = 0; l < c->L.size() && !rc; l++) {
@@ -212,8 +212,65 @@ int quantize_weights(tgx_ctx* c) {
   return ok ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "weights.fp8: quantizing the weights failed");
 }
 
+// ---- FP4 weights (kernels/gemv_fp4.h, decode_fp4.hip; option weights.fp4) ----
+// The matrices of the classes in weights.fp4_classes, quantized where they lie (the rule: include/tgx.h), in quantize_weights' order: the scan for weights
+// the rule refuses over all matrices first, so that nothing is overwritten when one is refused, then one launch per matrix that writes the dequantized
+// master and every byte of the stream.  A matrix whose shape the layout does not cover is quantized all the same and keeps no stream.  A down matrix beyond
+// 16384 columns is laid out as the K ranges of its launches (launch_layer_kernel), each with the split and chunk count of that launch.  (A device allocation
+// that fails on the way leaves earlier matrices quantized: tgx_finalize has failed and the context is not usable.)
+// the K ranges of the down launch at intermediate sizes beyond 16384 (launch_layer_kernel): their number and the width of each but the last
+static int down_parts(int cls, int K) { return cls == TGX_KERNEL_DOWN && K > 16384 ? (K + 16383) / 16384 : 1; }
+static int down_part_k(int K, int parts) { return ((K / 8 + parts - 1) / parts) * 8; }
+
+int quantize_weights_fp4(tgx_ctx* c) {
+  const tgx_model_desc& d = c->d;
+  if (!c->weights_fp4) return TGX_OK;
+  struct Job { ebyte* W; int N, K, cls, layer; Fp4Mat* out; };
+  std::vector<Job> jobs;
+  for (size_t l = 0; l < c->L.size(); l++) {
+    LayerW& w = c->L[l];
+    if (c->fp4_classes & 1) jobs.push_back({w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, (int)l, &w.fgu});
+    if (c->fp4_classes & 2) jobs.push_back({w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, (int)l, &w.fdown});
+  }
+  if (c->fp4_classes & 4) jobs.push_back({d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, -1, &c->flm});
+  if (jobs.empty()) return TGX_OK;
+  int* stat_dev = nullptr;
+  int rc = dev_alloc(c, &stat_dev, jobs.size());
+  if (rc) return rc;
+  std::vector<int> stat(jobs.size(), INT_MAX);
+  if (hipMemcpyAsync(stat_dev, stat.data(), stat.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) { dev_free(c, &stat_dev); return set_err(c, TGX_ERR_DEVICE, "weights.fp4: the status upload failed"); }
+  for (size_t i = 0; i < jobs.size(); i++) fp4_scan_matrix(c, jobs[i].W, jobs[i].N, jobs[i].K, stat_dev + i);
+  const bool scanned = hipGetLastError() == hipSuccess && hipMemcpyAsync(stat.data(), stat_dev, stat.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+                       hipStreamSynchronize(c->stream) == hipSuccess;
+  dev_free(c, &stat_dev);
+  if (!scanned) return set_err(c, TGX_ERR_DEVICE, "weights.fp4: the scan of the weights failed");
+  for (size_t i = 0; i < jobs.size(); i++) {
+    if (stat[i] >= jobs[i].N) continue;
+    const Job& j = jobs[i];
+    char name[96];
+    if (j.cls == TGX_KERNEL_LMHEAD) snprintf(name, sizeof name, "%s", d.tied ? "model.embed_tokens.weight" : "lm_head.weight");
+    else snprintf(name, sizeof name, "model.layers.%d.mlp.%s_proj.weight", j.layer, j.cls == TGX_KERNEL_DOWN ? "down" : (stat[i] < d.inter ? "gate" : "up"));
+    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp4: %s holds a non-finite weight or one of magnitude 2^100 or more (row %d)", name, stat[i]);
+  }
+  for (size_t i = 0; i < jobs.size(); i++) {
+    const Job& j = jobs[i];
+    const int parts = down_parts(j.cls, j.K), Kp = down_part_k(j.K, parts);
+    const int ks = gemv_auto_ks(Kp, c->tune[j.cls].ks), nx = gemv_nx(Kp, ks);
+    Fp4Mat m;
+    if (Kp % 32 == 0 && Kp * parts == j.K && nx <= 8) {      // whole blocks of 32 k in equal ranges, at most 8 chunks per lane
+      m.ks = ks; m.K = Kp; m.parts = parts; m.row_bytes = fp4_row_bytes(ks, nx);
+      if ((rc = dev_alloc(c, &m.Q, (size_t)parts * j.N * (size_t)m.row_bytes))) return rc;
+    }
+    for (int s = 0; s < (m.Q ? parts : 1); s++)
+      fp4_quant_matrix(c, j.W + (size_t)s * Kp * c->esz, j.N, m.Q ? Kp : j.K, j.K, ks, nx, m.Q ? m.Q + (size_t)s * j.N * m.row_bytes : nullptr, m.row_bytes);
+    if (m.Q) { *j.out = m; c->fp4_matrices++; }
+    else c->fp4_fallbacks++;
+  }
+  return hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "weights.fp4: quantizing the weights failed");
+}
+
 template <int PRO, int EPI>
-static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const PackedMat* pk = nullptr, const Fp8Mat* q8 = nullptr) {
+static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const PackedMat* pk = nullptr, const Fp8Mat* q8 = nullptr, const Fp4Mat* q4 = nullptr) {
   const Tune& tn = c->tune[cls];
   a.dbg = ((c->debug_gemv >> (8 + cls)) & 1) ? (c->debug_gemv & 15) : 0;
   if (!a.ldw) a.ldw = a.K;
@@ -225,6 +282,12 @@ static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const Packe
   const int grid = (EPI == tgx::EPI_LOGITS) ? c->lm_grid : gemv_grid(c, a.units, a.ks, tn.bpc);
   const int nx = gemv_nx(a.K, a.ks);
   if constexpr ((PRO == tgx::PRO_RMSNORM && (EPI == tgx::EPI_SILU_MUL || EPI == tgx::EPI_LOGITS)) || (PRO == tgx::PRO_PLAIN && EPI == tgx::EPI_RESIDUAL)) {
+    // batch 1 over a matrix quantized by option weights.fp4 with a stream laid out for this K split: 4.25 bits per weight, bit-identical to the plain kernel
+    // over the dequantized master (workgroups per CU: the class's packed_bpc, profiles/weights_fp4.txt)
+    if (q4 && q4->Q && R == 1 && q4->ks == a.ks && q4->K == a.K && !a.dbg) {      // (a K range of wider rows has a stream of its own: ldw is the master's)
+      launch_gemv_fp4(c, cls, a, *q4, (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc), nx);
+      return;
+    }
     // batch 1 over a matrix quantized by option weights.fp8 with a stream laid out for this K split: half the bytes, bit-identical to the plain kernel over the
     // dequantized master (workgroups per CU: the class's packed_bpc — no other value has been measured yet, profiles/weights_fp8.txt)
     if (q8 && q8->Q && R == 1 && q8->ks == a.ks && a.ldw == a.K && !a.dbg) {
@@ -389,7 +452,7 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
       }
       a.N = 2 * I; a.K = H; a.units = I; a.out = r.h; a.out_stride = I; a.hd = 2;
       if (resid_fixed(c, R, kv_stride)) a.x_acc = c->slab_acc + (size_t)(&r - c->rows.data()) * H;     // x' = fp32(acc)
-      launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_SILU_MUL>(c, a, TGX_KERNEL_GATEUP, R, &w.pgu, &w.qgu);
+      launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_SILU_MUL>(c, a, TGX_KERNEL_GATEUP, R, &w.pgu, &w.qgu, &w.fgu);
       break;
     }
     case TGX_KERNEL_DOWN: {  // down_proj + residual                                  (GatedMLP.h:40, DecoderLayer.h:41)
@@ -403,12 +466,14 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
           tgx::GemvArgs p = a;
           p.W = w.wdown + (size_t)k0 * c->esz; p.x = r.h + k0; p.K = std::min(per, I - k0); p.ldw = I;
           if (k0) p.bias = nullptr;
-          launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, p, TGX_KERNEL_DOWN, R);
+          Fp4Mat f4 = w.fdown;      // option weights.fp4: this K range's stream
+          if (f4.Q) f4.Q += (size_t)(k0 / per) * H * (size_t)f4.row_bytes;
+          launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, p, TGX_KERNEL_DOWN, R, nullptr, nullptr, &f4);
         }
         break;
       }
       if (resid_fixed(c, R, kv_stride)) a.res_acc = c->slab_acc + (size_t)(&r - c->rows.data()) * H;   // x = fp32(acc) + down(h); acc <- 0
-      launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, a, TGX_KERNEL_DOWN, R, &w.pdown, &w.qdown);
+      launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, a, TGX_KERNEL_DOWN, R, &w.pdown, &w.qdown, &w.fdown);
       break;
     }
     default: return 0;
@@ -442,7 +507,7 @@ void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_va
     launch_gemv<tgx::PRO_LAYERNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R);
     return;
   }
-  launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R, &c->plm, &c->qlm);
+  launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R, &c->plm, &c->qlm, &c->flm);
 }
 
 tgx::FinalizeArgs make_finalize_args(tgx_ctx* c, int row, bool advance_pos, bool log_step) {

@@ -57,6 +57,8 @@ bool GPTEngine::prepare() {
   LoadOptions loadOpts;
   loadOpts.weightsFp8 = config_.weightsFp8;
   loadOpts.weightsFp8Rows = config_.weightsFp8Rows;
+  loadOpts.weightsFp4 = config_.weightsFp4;
+  loadOpts.weightsFp4Classes = config_.weightsFp4Classes;
   if (!config_.synthetic.empty()) {
     if (!known_config(config_.synthetic, config_.dtype, config_.maxBatch, model_.config)) return fail("unknown synthetic config: " + config_.synthetic);
     if (!load_synthetic(be_, model_.config, config_.deviceOrdinal, 1234, 0.02, &model_.ctx, err_, loadOpts)) return fail("Prepare failed: " + err_);

@@ -125,6 +125,12 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // ... and the batched steps, verify / extend passes and short prompts of up to this many rows stream the codes as well (option "weights.fp8_rows": 0 = off, the
   // default, or 3..64; read with weightsFp8 only).  Same bits as without it.  A value the backend refuses fails prepare() with a message that names the option.
   int weightsFp8Rows = 0;
+  // Not in the reference: MXFP4 weights (include/tgx.h option "weights.fp4"; default false).  Opt-in and LOSSY like weightsFp8, at 4.25 bits per weight: E2M1
+  // codes with an E8M0 scale per block of 32.  weightsFp4Classes (-1 = the library's default, 7) is option "weights.fp4_classes": bit 0 gate_up, 1 down,
+  // 2 lm_head.  With weightsFp8 as well the device library quantizes each class by one of them and refuses a class both select: prepare() then FAILS with
+  // its message, as it does for every other refusal (dtype, GPT-2, a non-finite weight, a backend without the key).
+  bool weightsFp4 = false;
+  int weightsFp4Classes = -1;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -256,6 +262,12 @@ class GPTEngine {
   bool setWeightsFp8Rows(int rows) {
     if (model_.ctx && config_.weightsFp8 && (!be_.set_option || be_.set_option(model_.ctx, "weights.fp8_rows", rows) != TGX_OK)) return false;
     config_.weightsFp8Rows = rows;
+    return true;
+  }
+  // GPTConfig::weightsFp4 / weightsFp4Classes: read by prepare() (false: the model is loaded already — the weights were quantized or not at tgx_finalize)
+  bool setWeightsFp4(bool on, int classes) {
+    if (model_.ctx) return false;
+    config_.weightsFp4 = on; config_.weightsFp4Classes = classes;
     return true;
   }
   void setLogprobs(int topN) { config_.logprobs = topN; }

@@ -218,6 +218,14 @@ bool load_safetensors(const Backend& be, tgx_ctx* ctx, const std::string& path, 
 }
 
 bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts, std::string& err) {
+  if (opts.weightsFp4) {      // option "weights.fp4" (+ "weights.fp4_classes"): refused the same way as weights.fp8 below
+    if (!be.set_option) { err = "weightsFp4: the device shim exports no tgx_set_option, so option weights.fp4 cannot be set"; return false; }
+    if (be.set_option(ctx, "weights.fp4", 1) != TGX_OK || (opts.weightsFp4Classes >= 0 && be.set_option(ctx, "weights.fp4_classes", opts.weightsFp4Classes) != TGX_OK)) {
+      const char* why = be.last_error(ctx);
+      err = std::string("weightsFp4: the device shim refused option weights.fp4") + (why && *why ? std::string(": ") + why : std::string());
+      return false;
+    }
+  }
   if (!opts.weightsFp8) return true;
   if (!be.set_option) { err = "weightsFp8: the device shim exports no tgx_set_option, so option weights.fp8 cannot be set"; return false; }
   if (be.set_option(ctx, "weights.fp8", 1) != TGX_OK) {

@@ -52,6 +52,8 @@ struct LoadedModel {
 struct LoadOptions {
   bool weightsFp8 = false;
   int weightsFp8Rows = 0;
+  bool weightsFp4 = false;        // option "weights.fp4" = 1 ...
+  int weightsFp4Classes = -1;     // ... and "weights.fp4_classes" (-1 = not set: the library's default, all three classes)
 };
 bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts, std::string& err);
 

@@ -27,6 +27,9 @@ static void usage(const char* prog) {
           "  --dtype <bf16>            data type (default: bf16)\n"
           "  --weights-fp8             FP8 weights (opt-in, lossy): gate_up, down and lm_head are quantized to E4M3 codes with a power-of-two scale per row when\n"
           "                            the model is loaded (bf16 only); the run fails if the device library cannot do it (default: off)\n"
+          "  --weights-fp4             MXFP4 weights (opt-in, lossy): gate_up, down and lm_head are quantized to E2M1 codes with an E8M0 scale per block of 32 when\n"
+          "                            the model is loaded (bf16 only); the run fails if the device library cannot do it (default: off)\n"
+          "  --weights-fp4-classes <m> with --weights-fp4: which classes, a mask of gate_up (1), down (2), lm_head (4) (default: 7)\n"
           "  --weights-fp8-rows <n>    with --weights-fp8: batched steps and passes of up to n rows (3..64) stream the codes too; same output (default: 0 = off)\n"
           "  --max-tokens <n>          max new tokens (default: 32)\n"
           "  --temperature <f>         sampling temperature (default: 0.8)\n"
@@ -137,6 +140,8 @@ int main(int argc, char** argv) {
     else if (a == "--dtype") dtype = next();
     else if (a == "--weights-fp8") cfg.weightsFp8 = true;
     else if (a == "--weights-fp8-rows") cfg.weightsFp8Rows = atoi(next());
+    else if (a == "--weights-fp4") cfg.weightsFp4 = true;
+    else if (a == "--weights-fp4-classes") cfg.weightsFp4Classes = atoi(next());
     else if (a == "--max-tokens") cfg.maxNewTokens = atoi(next());
     else if (a == "--temperature") cfg.samplerConfig.temperature = strtof(next(), nullptr);
     else if (a == "--top-p") cfg.samplerConfig.topP = strtof(next(), nullptr);

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""What option weights.fp8 buys and what it costs, measured on one box: writes profiles/weights_fp8.txt.
+"""What a quantized-weights option (weights.fp8, weights.fp4) buys and what it costs, measured on one box: writes profiles/<option>.txt.
 
-    python tools/fp8_bench.py [--parent-lib PATH] [--models llama-3.2-1b,mistral-7b-v0.3] [--rounds 3] [--out profiles/weights_fp8.txt]
+    python tools/fp8_bench.py [--option weights.fp8] [--base-opts KEY=V,...] [--parent-lib PATH] [--models llama-3.2-1b,mistral-7b-v0.3] [--rounds 3] [--out FILE]
+
+--option is the option under test (set to 1 on this library; the labels below say fp8 for it).  --base-opts adds a second base context with those options set
+(on the parent library when --parent-lib names it), e.g. --option weights.fp4 --base-opts weights.fp8=1: the FP4 step against the parent's FP8 step and
+against its defaults, all contexts side by side and alternating.  --bpc 2,6,8 adds, per model, the step of the option under test at those workgroups per CU
+of its three launches (options <class>.packed_bpc) beside the defaults, contexts alternating.
 
 Per model (the bench.py point: a 2048-token prefill, 16 warm-up steps, 256 timed greedy steps; Mistral-7B is BASELINE.json config 3's geometry):
-  * ms per step with weights.fp8 = 1 against the BASE context — the parent commit's library at its defaults when --parent-lib names it, else this library with
+  * ms per step with the option under test (weights.fp8 in what follows) = 1 against the BASE context — the parent commit's library at its defaults when --parent-lib names it, else this library with
     the option off (the same launches and bits: a default context is unchanged) — as the median of the rounds' medians, with the spread of the rounds;
     the two contexts live side by side and take turns within every round, so clock drift hits both;
   * the per-class kernel times of tgx_profile_decode for both and the effective TB/s of the gate_up / down / lm_head launches (bytes the launch streams / time);
@@ -28,9 +33,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tinygpt_amd import known_desc, synth  # noqa: E402
-from tinygpt_amd.ffi import ABI, GREEDY, Backend, Model, product_backend  # noqa: E402
+from tinygpt_amd.ffi import ABI, GREEDY, Backend, Model, TgxError, product_backend  # noqa: E402
 
 ap = argparse.ArgumentParser()
+ap.add_argument("--option", default="weights.fp8", help="the option under test: weights.fp8 or weights.fp4")
+ap.add_argument("--base-opts", default="", help="KEY=V,...: a second base context with these options")
+ap.add_argument("--bpc", default="", help="N,...: also time the option under test at these workgroups per CU of gate_up / down / lm_head")
 ap.add_argument("--parent-lib", default=None, help="the parent commit's libtgx_mi355x.so (default: this library with weights.fp8 = 0)")
 ap.add_argument("--models", default="llama-3.2-1b,mistral-7b-v0.3")
 ap.add_argument("--prompt", type=int, default=2048)
@@ -41,7 +49,9 @@ ap.add_argument("--reps", type=int, default=3, help="timed regions per context a
 ap.add_argument("--out", default=None)
 ap.add_argument("--rows", action="store_true", help="measure option weights.fp8_rows instead (profiles/weights_fp8_rows.txt)")
 args = ap.parse_args()
-args.out = args.out or os.path.join(ROOT, "profiles", "weights_fp8_rows.txt" if args.rows else "weights_fp8.txt")
+args.out = args.out or os.path.join(ROOT, "profiles", "weights_fp8_rows.txt" if args.rows else args.option.replace(".", "_") + ".txt")
+TAG = args.option.split(".")[-1]                                                            # fp8 / fp4: the label of the context under test
+BASE_OPTS = [(kv.split("=")[0], int(kv.split("=")[1])) for kv in args.base_opts.split(",") if kv]
 
 lines = []
 
@@ -72,16 +82,25 @@ def greedy_ids(m, prompt):
     return np.concatenate([first, rest])
 
 
-def class_table(m, d, fp8):
+def get_or_0(m, key):
+    try:
+        return m.get_option(key)
+    except TgxError:       # (a parent library that does not know the key)
+        return 0
+
+
+def class_table(m, d):
     """per-class kernel us per launch, and the stream bytes of the three weight launches of ONE layer / the head"""
     prof = m.profile_decode(8)
     H, I, V = d.hidden, d.inter, d.vocab
     packed = m.get_option("weights.packed_classes") if m.get_option("weights.packed") else 0
-    q8 = m.get_option("weights.fp8_classes") if fp8 else 0
+    q8 = m.get_option("weights.fp8_classes") if get_or_0(m, "weights.fp8") else 0
+    q4 = m.get_option("weights.fp4_classes") if get_or_0(m, "weights.fp4") else 0
     weights = {"gateup": 2 * I * H, "down": H * I, "lmhead": V * H}
     out = {}
     for bit, cls in enumerate(("gateup", "down", "lmhead")):
-        per_weight = 1.0 if q8 >> bit & 1 else (1.5 if packed >> bit & 1 else 2.0)      # (nominal: scales, escape records and padding left out)
+        # (nominal: scales, escape records and padding left out — but 0.53125 is what an FP4 stream holds, scales included, wherever K % (512 ks) == 0)
+        per_weight = 0.53125 if q4 >> bit & 1 else 1.0 if q8 >> bit & 1 else (1.5 if packed >> bit & 1 else 2.0)      # (nominal: scales, escape records and padding left out)
         n, ms = prof[cls]
         us = ms / n * 1e3 if n else float("nan")
         out[cls] = (us, weights[cls] * per_weight / (us * 1e-6) / 1e12 if n else float("nan"), per_weight)
@@ -164,42 +183,54 @@ if args.rows:
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     sys.exit(0)
-say("# option weights.fp8: FP8 (E4M3, one power-of-two scale per row) gate_up / down / lm_head streams at batch 1 — tools/fp8_bench.py")
-say(f"# base context: {'the parent commit library at its defaults' if parent else 'this library with weights.fp8 = 0 (the parent launches and bits)'}")
+say(f"# option {args.option}: quantized gate_up / down / lm_head streams at batch 1 — tools/fp8_bench.py --option {args.option}" + (f" --base-opts {args.base_opts}" if BASE_OPTS else ""))
+say(f"# base contexts: {'the parent commit library' if parent else 'this library'} at its defaults" + (f", and the same with {args.base_opts}" if BASE_OPTS else ""))
 say(f"# point: {args.prompt}-token prefill, {args.warmup} warm-up steps, {args.steps} timed greedy steps; {args.rounds} rounds x {args.reps} regions per context, contexts alternating")
 for name in args.models.split(","):
     d = known_desc(name, "bf16")
     d.max_ctx = min(d.max_ctx, 4096)
-    base, q = Model(d, parent or product_backend()), Model(d, product_backend())
-    q.set_option("weights.fp8", 1)
+    ctx = {"base": Model(d, parent or product_backend())}
+    if BASE_OPTS:
+        ctx["base+" + args.base_opts] = Model(d, parent or product_backend())
+        for k, v in BASE_OPTS:
+            ctx["base+" + args.base_opts].set_option(k, v)
+    ctx[TAG] = Model(d, product_backend())
+    ctx[TAG].set_option(args.option, 1)
+    base, q = ctx["base"], ctx[TAG]
     t0 = time.time()
     for tname, bits in synth.synth_checkpoint(d, 1234, 0.02):
-        base.upload(tname, bits); q.upload(tname, bits)
-    base.finalize(); q.finalize()
+        for m in ctx.values():
+            m.upload(tname, bits)
+    for m in ctx.values():
+        m.finalize()
     say()
     say(f"## {name} bf16 ({d.param_count() / 1e9:.2f} B parameters; load + quantize {time.time() - t0:.0f} s)")
-    say(f"fp8 streams {q.get_option('weights.fp8_matrices')}, fallbacks {q.get_option('weights.fp8_fallbacks')}; "
-        f"bytes per token at context {args.prompt + args.warmup + args.steps // 2}: base {base.bytes_per_token(args.prompt + args.warmup + args.steps // 2) / 1e6:.1f} MB, "
-        f"fp8 {q.bytes_per_token(args.prompt + args.warmup + args.steps // 2) / 1e6:.1f} MB")
+    T = args.prompt + args.warmup + args.steps // 2
+    say(f"{TAG} streams {q.get_option(args.option + '_matrices')}, fallbacks {q.get_option(args.option + '_fallbacks')}; bytes per token at context {T}: " +
+        ", ".join(f"{k} {m.bytes_per_token(T) / 1e6:.1f} MB" for k, m in ctx.items()))
     prompt = synth.synth_prompt(d.vocab, args.prompt, 1234)[None, :]
-    for m in (base, q):
+    for m in ctx.values():
         timed(m, prompt)                                    # untimed: workspaces, code objects, graphs
-    rounds = {"base": [], "fp8": []}
+    rounds = {k: [] for k in ctx}
     for r in range(args.rounds):
-        got = {"base": [], "fp8": []}
+        got = {k: [] for k in ctx}
         for _ in range(args.reps):
-            got["base"].append(timed(base, prompt)); got["fp8"].append(timed(q, prompt))
+            for k, m in ctx.items():
+                got[k].append(timed(m, prompt))
         for k in got:
             rounds[k].append(statistics.median(got[k]))
-        say(f"round {r}: base {rounds['base'][-1]:.4f} ms/step   fp8 {rounds['fp8'][-1]:.4f} ms/step")
-    mb, mq = statistics.median(rounds["base"]), statistics.median(rounds["fp8"])
-    sb, sq = max(rounds["base"]) - min(rounds["base"]), max(rounds["fp8"]) - min(rounds["fp8"])
-    say(f"ms per step, median of the rounds' medians (spread of the rounds): base {mb:.4f} ({sb:.4f})   fp8 {mq:.4f} ({sq:.4f})   "
-        f"difference {mb - mq:+.4f} ms = {100 * (mb - mq) / mb:+.1f} %   tok/s {1e3 / mb:.0f} -> {1e3 / mq:.0f}")
-    say("faster than the base by more than the spread" if mb - mq > max(sb, sq) else "NOT faster than the base by more than the spread")
-    for label, m, fp8 in (("base", base, 0), ("fp8", q, 1)):
+        say(f"round {r}: " + "   ".join(f"{k} {rounds[k][-1]:.4f} ms/step" for k in ctx))
+    med = {k: statistics.median(v) for k, v in rounds.items()}
+    spread = {k: max(v) - min(v) for k, v in rounds.items()}
+    say("ms per step, median of the rounds' medians (spread of the rounds): " + "   ".join(f"{k} {med[k]:.4f} ({spread[k]:.4f})" for k in ctx))
+    for k in ctx:
+        if k != TAG:
+            mb, mq = med[k], med[TAG]
+            say(f"{TAG} against {k}: difference {mb - mq:+.4f} ms = {100 * (mb - mq) / mb:+.1f} %   tok/s {1e3 / mb:.0f} -> {1e3 / mq:.0f}: " +
+                ("faster by more than the spread" if mb - mq > max(spread[k], spread[TAG]) else "NOT faster by more than the spread"))
+    for label, m in ctx.items():
         m.reset_cache(); m.forward(prompt); m.sample(GREEDY); m.decode(args.warmup, GREEDY, fetch=False)
-        prof, cls = class_table(m, d, fp8)
+        prof, cls = class_table(m, d)
         say(f"{label}: kernel us per launch  " + "  ".join(f"{k} {ms / n * 1e3:.2f}" for k, (n, ms) in prof.items() if n) +
             f"   sum per token {sum(ms for n, ms in prof.values()) / 8 * 1e3:.1f} us")
         say(f"{label}: effective TB/s  " + "  ".join(f"{k} {tb:.2f} (at {pw} B/weight)" for k, (us, tb, pw) in cls.items()))
@@ -221,7 +252,29 @@ for name in args.models.split(","):
         f"(largest |logit| {ref_max:.4g})")
     say(f"free-running greedy ids ({args.warmup + args.steps} tokens): " +
         ("all agree" if differ.size == 0 else f"first differ at token {int(differ[0])}, {int(differ.size)} of {ids_b.size} differ"))
-    base.close(); q.close()
+    for m in ctx.values():
+        m.close()
+    if args.bpc:      # the option under test at other workgroups per CU of its three launches
+        ctx = {"defaults": None, **{v: int(v) for v in args.bpc.split(",")}}
+        for k, bpc in list(ctx.items()):
+            ctx[k] = m = Model(d, product_backend())
+            m.set_option(args.option, 1)
+            for cls in ("gateup", "down", "lmhead"):
+                if bpc:
+                    m.set_option(cls + ".packed_bpc", bpc)
+        for tname, bits in synth.synth_checkpoint(d, 1234, 0.02):
+            for m in ctx.values():
+                m.upload(tname, bits)
+        rounds = {k: [] for k in ctx}
+        for m in ctx.values():
+            m.finalize(); timed(m, prompt)
+        for r in range(args.rounds):
+            for k, m in ctx.items():
+                rounds[k].append(statistics.median(timed(m, prompt) for _ in range(args.reps)))
+        say(f"{TAG} by workgroups per CU of gate_up / down / lm_head, ms per step, median of the rounds (spread): " +
+            "   ".join(f"{k}: {statistics.median(v):.4f} ({max(v) - min(v):.4f})" for k, v in rounds.items()))
+        for m in ctx.values():
+            m.close()
 
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 with open(args.out, "w") as f:
