@@ -359,7 +359,8 @@ TGX_API int tgx_extend_row(tgx_ctx* ctx, int row, const int64_t* ids, int seq);
  * row holds (truncate to min(common prefix, new prompt length - 1), then tgx_extend_row the rest).  Cache rows [0, new_len) are untouched; the position word and the
  * host length move; a finished state is cleared.  The logits of position new_len - 1 no longer exist, so the row then has NO LOGITS AND NO CURRENT TOKEN:
  * tgx_sample_row on it, tgx_fork_row from it, and tgx_decode / tgx_decode_rows / tgx_step_async / tgx_sample while it is in that state return TGX_ERR_STATE until
- * tgx_extend_row has run on it (tgx_reset_row ends the state as well).  new_len == past on a row whose logits are in place is a no-op that returns TGX_OK.
+ * tgx_extend_row has run on it (tgx_reset_row ends the state as well).  new_len == past on a row whose logits are in place is a no-op that returns TGX_OK —
+ * except on a FINISHED row, where it is a truncation like any other: the finished state is cleared and the row ends with no logits and no current token.
  * new_len < 1 (that is tgx_reset_row) and new_len > past: TGX_ERR_INVALID.  A retired or empty row: TGX_ERR_STATE.
  * Paged KV: the blocks beyond ceil(new_len / 128) lose this row's reference.  If new_len % 128 != 0 and the block that now holds the tail is shared with forked
  * siblings, the next append would write into a shared block: the row takes one fresh block, rows [0, new_len % 128) of every layer and both caches are copied into
@@ -387,9 +388,12 @@ TGX_API int tgx_truncate_row(tgx_ctx* ctx, int row, int64_t new_len);
  *                     [0, past): TGX_ERR_INVALID.  A retired or empty row, row >= batch, a poisoned context, a call before tgx_finalize: TGX_ERR_STATE.  GPT-2:
  *                     TGX_ERR_UNSUPPORTED (its positions are learned and added to the hidden state: there is nothing to re-rotate).  A cache row of head_dim *
  *                     element size bytes that is no multiple of 4 (or whose half is none): TGX_ERR_UNSUPPORTED, as for tgx_fork_row.
+ *                     In this order: the row and n_keep ranges; the row's state (a retired or empty row holds no positions, so it is refused for its state,
+ *                     whatever its ranges are); GPT-2; then the ranges against the row's length.
  *   ALL OR NOTHING    a refused call changes no row, moves no KV block, leaves kv.free_tokens as it was and does not poison the context.
  *   No-op             one range [0, past) on a row whose logits are in place returns TGX_OK and changes nothing; one range [0, L), L < past, IS
- *                     tgx_truncate_row(row, L): the same bits, the same block accounting.
+ *                     tgx_truncate_row(row, L): the same bits, the same block accounting.  (Ranges that touch count as one.)  On a FINISHED row [0, past) is
+ *                     tgx_truncate_row(row, past), no no-op: the finished state is cleared and the row ends in the state below.
  *   Afterwards        the row holds new_len positions and is in tgx_truncate_row's state "no logits, no current token": tgx_sample_row, the decode calls and
  *                     tgx_fork_row return TGX_ERR_STATE until tgx_extend_row has run on it.  The current token is NOT in the cache and is discarded, as
  *                     tgx_extend_row discards it: a caller that goes on generating passes it as ids[0] of the next tgx_extend_row (which starts the

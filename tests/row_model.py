@@ -10,6 +10,12 @@ call sequences against both (tests/test_row_model.py on a CPU, tests/test_hip_ro
                 conditions testable without a GPU.  What a reader sees of a row (cache rows, logits, records) is held here, so copies are copies bit for bit.
   Mirror        the reference of the numeric checks: per row an oracle and its reordered twin, fed the row's token list.
   run_sequence  draws operations, predicts each with the model, runs it on the device and checks what include/tgx.h promises after every one.
+
+The arms whose name ends in _x draw the later row calls as well (tgx_splice_row, tgx_verify_rows, tgx_advance_rows, tgx_beam_select, tgx_beam_advance).  After a
+splice a row's cache is no function of its token list any more: the oracles of such a row have their cache spliced (tests/splice_ref.py, rounded once to the storage
+dtype), cut (set_past) and copied (read_kv / write_kv) instead of being forwarded again, until the row is admitted afresh (Row.spliced).
+A negative
+lens[i] of tgx_advance_rows cannot be passed through tinygpt_amd.ffi: the driver makes that one call on the C entry point (raw_advance_rows).
 """
 from __future__ import annotations
 
@@ -18,6 +24,8 @@ import time
 
 import numpy as np
 
+import beam_ref
+import splice_ref
 from conftest import load_golden, rel_err
 from tinygpt_amd.desc import desc_from_hf_config
 from tinygpt_amd.ffi import GREEDY, SamplerCfg, TgxError
@@ -25,11 +33,13 @@ from tinygpt_amd.ffi import GREEDY, SamplerCfg, TgxError
 OK, INVALID, UNSUPPORTED, STATE, CONTEXT = 0, 1, 2, 4, 8
 BLK = 128
 MAX_STOP, MAX_DRAFT, MAX_LOGPROBS, LOGPROB_RING = 8, 15, 20, 256
+MAX_SPLICE_RANGES, MAX_VERIFY_POSITIONS, MAX_ADVANCE_POSITIONS, MAX_BEAMS, MAX_BEAM_CAND = 16, 64, 8192, 8, 32
+STEP, FEED, FEED_MORE = 0, 1, 2
 EMPTY, RETIRED, LIVE, FINISHED = "empty", "retired", "live", "finished"
 GREEDY_T = (0.0, 0, 1.0, 0.0)
 LENS = [1, 2, 17, 33, 100, 126, 127, 128, 129, 200, 255, 256, 257]
 FAMS = ["llama_tiny", "qwen2_tiny", "mistral_tiny", "qwen3_tiny", "gpt2_hd64"]
-ARMS = ["f32_slab", "h16_slab", "h16_paged"]
+ARMS = ["f32_slab", "h16_slab", "h16_paged", "f32_slab_x", "h16_slab_x", "h16_paged_x"]      # _x: the same dtype and layout, the kind table extended (Driver.WEIGHTS_X)
 MAX_CTX = 384
 
 
@@ -45,6 +55,7 @@ class Snap:
     """what a snapshot holds of a row, as far as the contract goes"""
     def __init__(self, row):
         self.tokens = list(row.tokens); self.has_logits = row.has_logits; self.has_token = row.has_logits and row.has_token
+        self.spliced = row.spliced
         self.tok = row.tok if self.has_token else None
 
 
@@ -60,6 +71,8 @@ class Row:
 
     def drop_sequence(self):
         self.tokens = []; self.tok = None; self.has_logits = False; self.has_token = False
+        self.fed_more = False     # the row's last feed was a TGX_ADV_FEED_MORE: the rest of its prompt is still to come
+        self.spliced = False      # tgx_splice_row has moved cache rows: the cache is no longer a function of the token list (until the row is admitted afresh)
 
     @property
     def holds(self):
@@ -97,8 +110,8 @@ class Pool:
 
 
 class RowModel:
-    def __init__(self, max_batch, max_ctx, vocab, budget_tokens=0):
-        self.max_batch, self.max_ctx, self.vocab = max_batch, max_ctx, vocab
+    def __init__(self, max_batch, max_ctx, vocab, budget_tokens=0, gpt2=False):
+        self.max_batch, self.max_ctx, self.vocab, self.gpt2 = max_batch, max_ctx, vocab, gpt2
         self.batch = 0
         self.rows = [Row() for _ in range(max_batch)]
         self.pool = Pool(budget_tokens) if budget_tokens else None
@@ -289,8 +302,7 @@ class RowModel:
             rs.append((STATE, "truncate_retired")); return
         if new_len < 1 or new_len > x.length:
             rs.append((INVALID, "new_len")); return
-        assert not (new_len == x.length and x.state == FINISHED), "the header does not say what new_len == past does to a finished row"
-        if new_len == x.length and x.has_logits:
+        if new_len == x.length and x.has_logits and x.state != FINISHED:      # (on a finished row new_len == past is a truncation like any other)
             return
         if self._cow(row, new_len) and not self.pool.free:
             rs.append((CONTEXT, "pool"))
@@ -324,6 +336,255 @@ class RowModel:
         if not rs and self.pool:
             self._short(blocks_for(len(snap.tokens)), len(self.pool.free) + self._given_back([row]), rs)
 
+    # ---- the later row calls: tgx_splice_row, tgx_verify_rows, tgx_advance_rows, tgx_beam_select, tgx_beam_advance
+    @staticmethod
+    def splice_src(ranges):
+        """the source position of every kept position"""
+        return [p for s, n in ranges for p in range(s, s + n)]
+
+    def _splice_plan(self, row, ranges):
+        """(new_len, f, no-op, the indices of the written blocks that forked siblings map as well) of a legal splice"""
+        x = self.rows[row]
+        src = self.splice_src(ranges)
+        new_len = len(src)
+        f = next((i for i, p in enumerate(src) if p != i), new_len)      # the end of the leading delta == 0 range; new_len for a truncation
+        noop = new_len == x.length and f == new_len and x.has_logits and x.state != FINISHED      # (on a finished row it is a truncation: the state is cleared)
+        swap = [i for i in range(f // BLK, blocks_for(new_len)) if self.pool.shared(x.blocks[i])] if self.pool and not noop else []
+        return new_len, f, noop, swap
+
+    def _why_splice_row(self, rs, row, ranges):
+        if not self._in(row):
+            rs.append((INVALID, "row_range")); return
+        # the header's order: the row and n_keep; the row's state; GPT-2; then the ranges against the row's length
+        if not 1 <= len(ranges) <= MAX_SPLICE_RANGES:
+            rs.append((INVALID, "n_keep")); return
+        x = self.rows[row]
+        if not x.holds:                                             # a retired or empty row holds no positions: refused for its state whatever its ranges are
+            rs.append((STATE, "splice_retired")); return
+        if self.gpt2:                                               # learned positions: nothing to re-rotate
+            rs.append((UNSUPPORTED, "gpt2")); return
+        end = 0
+        for s, n in ranges:                                          # empty, unsorted, overlapping, outside [0, past)
+            if n < 1 or s < end or s + n > x.length:
+                rs.append((INVALID, "bad_range")); return
+            end = s + n
+        new_len, f, noop, swap = self._splice_plan(row, ranges)
+        if len(swap) > (len(self.pool.free) if self.pool else 0):   # against the free list ALONE: what the row gives back is not counted
+            rs.append((CONTEXT, "pool"))
+
+    def _do_splice_row(self, row, ranges, out_len):
+        x = self.rows[row]
+        new_len, f, noop, swap = self._splice_plan(row, ranges)
+        assert int(out_len) == new_len, f"out_len {out_len}, the kept ranges hold {new_len}"
+        if noop:
+            return
+        if self.pool:
+            if swap:
+                self.note("splice_cow_block" if f < new_len else "cow_truncation")
+            for i in swap:
+                old = x.blocks[i]; x.blocks[i] = self.pool.take(); self.pool.drop(old)
+            self._trim(row, new_len)
+            if f < new_len and any(self.pool.shared(b) for b in x.blocks[:f // BLK]):
+                self.note("splice_shared_prefix_kept")
+        src = self.splice_src(ranges)
+        x.spliced = x.spliced or f < new_len
+        x.state = LIVE; x.tokens = [x.tokens[p] for p in src]; x.has_logits = x.has_token = False; x.tok = None
+
+    def _why_step_row(self, rs, r, n_draft, what):
+        """tgx_verify_rows' per-row checks, in the one-row call's order"""
+        if not self._in(r):
+            rs.append((INVALID, "row_range")); return False
+        if not 0 <= n_draft <= MAX_DRAFT:
+            rs.append((INVALID, "n_draft"))
+        if not self._source(r, rs, what):
+            return False
+        x = self.rows[r]
+        if not x.has_logits:
+            rs.append((STATE, "step_no_logits" if what == "step" else "truncated"))
+        elif not x.has_token:
+            rs.append((STATE, "step_no_token" if what == "step" else "no_token"))
+        if x.length + n_draft + 1 > self.max_ctx:
+            rs.append((CONTEXT, "max_ctx"))
+        return True
+
+    def _why_verify_rows(self, rs, rows, drafts):
+        if not 1 <= len(rows) <= self.max_batch:
+            rs.append((INVALID, "n")); return
+        if any(not self._in(r) for r in rows):
+            rs.append((INVALID, "row_range")); return
+        if len(set(rows)) != len(rows):
+            rs.append((INVALID, "row_twice"))
+        for r, d in zip(rows, drafts):
+            self._why_step_row(rs, r, len(d), "verify")
+        if sum(len(d) + 1 for d in drafts) > MAX_VERIFY_POSITIONS:
+            rs.append((INVALID, "positions"))
+        if not rs and self.pool:                                    # the blocks of ALL named rows together
+            self._short(sum(self._more(r, self.rows[r].length + len(d) + 1) for r, d in zip(rows, drafts)), len(self.pool.free), rs)
+
+    def _do_verify_rows(self, rows, drafts, out):
+        assert len(out) == len(rows), f"{len(out)} results for {len(rows)} rows"
+        if all(len(d) == 0 for d in drafts):
+            self.note("verify_rows_all_zero_drafts")
+        for r, d, o in zip(rows, drafts, out):
+            given = blocks_for(self.rows[r].length + len(d) + 1)
+            self._do_verify_row(r, d, o)
+            if self.pool and given > blocks_for(self.rows[r].length):
+                self.note("verify_rows_rejects_tail_block")
+
+    def _why_advance_rows(self, rs, rows, kinds, ids, lens=None):
+        """lens: the call's lens[] where it is not the lengths of `ids` (only a raw call can pass a negative one)"""
+        if not 1 <= len(rows) <= self.max_batch:
+            rs.append((INVALID, "n")); return
+        # first the call's own: kinds, lengths, the two position limits
+        if any(not STEP <= k <= FEED_MORE for k in kinds):
+            rs.append((INVALID, "kind")); return
+        if lens is not None:
+            assert any(n < 0 for n in lens) and all(n == len(d) for n, d in zip(lens, ids) if n >= 0), "explicit lens are for the negative-length refusal alone"
+            rs.append((INVALID, "neg_len")); return
+        if sum(len(d) + 1 for k, d in zip(kinds, ids) if k == STEP) > MAX_VERIFY_POSITIONS:
+            rs.append((INVALID, "step_positions")); return
+        if sum(len(d) + (k == STEP) for k, d in zip(kinds, ids)) > MAX_ADVANCE_POSITIONS:
+            rs.append((INVALID, "positions")); return
+        # then per row, each row's checks with the codes of its equivalent call
+        if any(not self._in(r) for r in rows):
+            rs.append((INVALID, "row_range")); return
+        if len(set(rows)) != len(rows):
+            rs.append((INVALID, "row_twice"))
+        for r, k, d in zip(rows, kinds, ids):
+            x = self.rows[r]
+            if k == STEP:
+                self._why_step_row(rs, r, len(d), "step")
+                continue
+            if len(d) < 1:
+                rs.append((INVALID, "len"))
+            if x.length + len(d) > self.max_ctx:                    # tgx_extend_row's past + seq, tgx_forward_row's seq
+                rs.append((CONTEXT, "max_ctx"))
+        new = sorted(r for r, k in zip(rows, kinds) if k != STEP and r >= self.batch)
+        if new != list(range(self.batch, self.batch + len(new))):
+            rs.append((INVALID, "gap"))
+        if not rs and self.pool:                                    # ALL named rows together, against the free list plus what admission targets give back
+            need = sum(self._more(r, self.rows[r].length + len(d) + (k == STEP)) for r, k, d in zip(rows, kinds, ids))
+            self._short(need, len(self.pool.free) + self._given_back([r for r, k in zip(rows, kinds) if k != STEP and not self.rows[r].holds]), rs)
+
+    def _do_advance_rows(self, rows, kinds, ids, out):
+        assert len(out) == len(rows), f"{len(out)} results for {len(rows)} rows"
+        has_step = STEP in kinds
+        for r, k, d, o in zip(rows, kinds, ids, out):
+            x = self.rows[r]
+            if k == STEP:
+                self._do_verify_row(r, d, o)
+                continue
+            assert len(o[0]) == 0 and o[1] == 0, f"a FEED row reports out_n {len(o[0])} / out_finish {o[1]}"
+            if x.holds:
+                if x.state == FINISHED and has_step:
+                    self.note("advance_over_finished_row")
+                if not x.has_logits and x.state == LIVE and x.fed_more and k == FEED:
+                    self.note("advance_feed_more_then_feed")
+                self._do_extend_row(r, d)
+            else:
+                if r >= self.batch:
+                    self.note("advance_admits_new_row")
+                self._do_forward_row(r, d)
+            x.fed_more = k == FEED_MORE
+            if k == FEED_MORE:                                      # "no logits and no current token"; an admission by FEED_MORE counts as an admission
+                x.has_logits = x.has_token = False; x.tok = None
+
+    def _why_beam_select(self, rs, rows, scores, k, end_ids):
+        if not 1 <= len(rows) <= MAX_BEAMS or not 1 <= k <= MAX_BEAMS or len(end_ids) > MAX_STOP:
+            rs.append((INVALID, "n_k_end")); return
+        if any(not np.isfinite(s) for s in scores):
+            rs.append((INVALID, "score"))
+        if any(not self._in(r) for r in rows):
+            rs.append((INVALID, "row_range")); return
+        if len(set(rows)) != len(rows):
+            rs.append((INVALID, "row_twice"))
+        for r in rows:
+            if self._source(r, rs, "beam") and not self.rows[r].has_logits:
+                rs.append((STATE, "no_logits"))
+
+    def _do_beam_select(self, rows, scores, k, end_ids):
+        pass
+
+    def beam_placement(self, rows, parent):
+        """the PINNED rule -> (out_rows, the childless sources)"""
+        n_next = len(parent)
+        out = [None] * n_next
+        sources = [i for i, r in enumerate(rows) if self.rows[r].state == LIVE]
+        pinned = {}
+        for j, p in enumerate(parent):
+            pinned.setdefault(p, j)
+        for p, j in pinned.items():
+            out[j] = rows[p]
+        childless = [i for i in sources if i not in pinned]
+        empty = sorted(childless + [i for i in range(len(rows)) if i not in sources])      # empty once the childless sources are retired, in array order
+        for j in range(n_next):
+            if out[j] is None:
+                out[j] = rows[empty.pop(0)]
+        return out, [rows[i] for i in childless]
+
+    def _why_beam_advance(self, rs, rows, parent, tokens):
+        if not 1 <= len(rows) <= MAX_BEAMS or not 1 <= len(parent) <= len(rows):
+            rs.append((INVALID, "n")); return
+        if any(not self._in(r) for r in rows):
+            rs.append((INVALID, "row_range")); return
+        if len(set(rows)) != len(rows):
+            rs.append((INVALID, "row_twice")); return
+        if any(not 0 <= p < len(rows) for p in parent):
+            rs.append((INVALID, "parent_range")); return
+        if any(not 0 <= t < self.vocab for t in tokens):
+            rs.append((INVALID, "token"))
+        for r in rows:
+            x = self.rows[r]
+            if x.state == FINISHED:
+                rs.append((STATE, "finished_source"))
+            elif x.state == LIVE and not x.has_logits:
+                rs.append((STATE, "no_logits"))
+        if any(self.rows[rows[p]].state not in (LIVE, FINISHED) for p in parent):
+            rs.append((STATE, "parent_is_spare"))
+        if any(c == STATE for c, _ in rs):
+            return
+        out, childless = self.beam_placement(rows, parent)
+        new = sorted(r for r in out if r >= self.batch)             # the new rows that RECEIVE a hypothesis
+        if new != list(range(self.batch, self.batch + len(new))):
+            rs.append((INVALID, "gap"))
+        if not rs and self.pool:                                    # the fresh tail blocks against the free list plus what the childless sources give back
+            pinned = set()
+            tails = 0
+            for j, p in enumerate(parent):
+                if p in pinned:
+                    tails += self.rows[rows[p]].length % BLK != 0
+                pinned.add(p)
+            self._short(tails, len(self.pool.free) + self._given_back(childless), rs)
+
+    def _do_beam_advance(self, rows, parent, tokens, out_rows):
+        want, childless = self.beam_placement(rows, parent)
+        assert [int(r) for r in out_rows] == want, f"out_rows {[int(r) for r in out_rows]}, the pinned placement gives {want}"
+        if self.pool and any(self.pool.shared(b) for r in rows for b in self.rows[r].blocks):
+            self.note("beam_on_already_forked_rows")
+        src = {rows[p]: Snap(self.rows[rows[p]]) for p in parent}
+        for r in childless:                                         # retired first, as by tgx_reset_row
+            self.note("beam_childless_source_retired")
+            self._do_reset_row(r)
+        seen = set()
+        for j, p in enumerate(parent):
+            r, d, s = rows[p], want[j], src[rows[p]]
+            if p not in seen:                                       # its lowest-j child stays in place
+                seen.add(p)
+                self.rows[r].has_token, self.rows[r].tok = True, int(tokens[j])
+                continue
+            if d >= self.batch:
+                self.note("beam_new_row_spare")
+            if self.pool:                                           # tgx_fork_row's destination, word for word
+                pb = self.rows[r].blocks
+                self._release(d)
+                for b in pb[:len(s.tokens) // BLK]:
+                    self.pool.ref[b] += 1; self.rows[d].blocks.append(b)
+                if len(s.tokens) % BLK:
+                    self.note("beam_copied_child_tail_block")
+                    self.rows[d].blocks.append(self.pool.take())
+            self._admit(d, s.tokens, True, True, int(tokens[j])); self.rows[d].spliced = s.spliced
+        return want, childless
+
     # ---- apply: the state after a call that returned TGX_OK.  `out` is what the device produced (ids); the counts it reported are checked against the stop rules
     def apply(self, kind, *a, out=None):
         return getattr(self, "_do_" + kind)(*a) if out is None else getattr(self, "_do_" + kind)(*a, out)
@@ -331,7 +592,7 @@ class RowModel:
     def _admit(self, r, tokens, has_logits=True, has_token=False, tok=None):
         x = self.rows[r]
         x.state = LIVE; x.tokens = list(tokens); x.has_logits = has_logits; x.has_token = has_token; x.tok = tok
-        x.produced = 0; x.lp_count = 0
+        x.produced = 0; x.lp_count = 0; x.fed_more = False
         self.batch = max(self.batch, r + 1)
 
     def _do_forward_rows(self, rows, prompts):
@@ -341,7 +602,7 @@ class RowModel:
             for r, p in zip(rows, prompts):
                 self._grow(r, len(p))
         for r, p in zip(rows, prompts):
-            self._admit(r, p)
+            self._admit(r, p); self.rows[r].spliced = False
 
     def _do_forward_row(self, row, ids):
         self._do_forward_rows([row], [ids])
@@ -425,7 +686,7 @@ class RowModel:
                 if s.length % BLK:
                     self.rows[d].blocks.append(self.pool.take())
         for d in dsts:
-            self._admit(d, s.tokens, True, s.has_token, s.tok)
+            self._admit(d, s.tokens, True, s.has_token, s.tok); self.rows[d].spliced = s.spliced
 
     def _do_extend_row(self, row, ids):
         x = self.rows[row]
@@ -442,7 +703,7 @@ class RowModel:
 
     def _do_truncate_row(self, row, new_len):
         x = self.rows[row]
-        if new_len == x.length and x.has_logits:
+        if new_len == x.length and x.has_logits and x.state != FINISHED:
             return
         if self._cow(row, new_len):
             self.note("cow_truncation")
@@ -483,23 +744,58 @@ class RowModel:
     def _do_restore_row(self, row, snap):
         if self.pool:
             self._release(row); self._grow(row, len(snap.tokens))
-        self._admit(row, snap.tokens, snap.has_logits, snap.has_token, snap.tok)
+        self._admit(row, snap.tokens, snap.has_logits, snap.has_token, snap.tok); self.rows[row].spliced = snap.spliced
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------------------------
 # the random stream behind a (seed, arm), where it is not the seed's own number: chosen in the CPU dry run (tests/test_row_model.py) so that the oracle stays far enough
 # from its reordered twin on every sequence
-STREAM = {(2, "f32_slab"): 402, (7, "f32_slab"): 407}      # mistral_tiny (hidden 512, head_dim 128) in fp32: 8.5e-6 and 7.0e-6 from the twin, under the 1e-5 the arm asks for
+# mistral_tiny (hidden 512, head_dim 128) in fp32: these streams stay under the 1e-5 the arm asks for, where the seed's own number did not (the dry run prints each floor)
+STREAM = {(2, "f32_slab"): 402, (7, "f32_slab"): 407, (2, "f32_slab_x"): 402}
+BUDGET_X = 1.0      # blocks per row of the paged _x arm: forked and beam rows share their full blocks, so the pool lasts longer per row than in the old arm
+
+
+def base_arm(arm):
+    return arm[:-2] if arm.endswith("_x") else arm
 
 
 def case(seed, arm):
     """the fixture, dtype and geometry of one (seed, arm)"""
     fam = FAMS[seed % len(FAMS)]
-    dtype = "fp32" if arm == "f32_slab" else ("fp16" if seed % 4 == 2 else "bf16")
-    rng = np.random.default_rng(90000 + 17 * STREAM.get((seed, arm), seed) + ARMS.index(arm))
-    max_batch = int(rng.integers(4, 7))
-    budget = blocks_for(int(1.5 * max_batch * BLK)) * BLK if arm == "h16_paged" else 0
-    return dict(seed=seed, arm=arm, fam=fam, dtype=dtype, max_batch=max_batch, max_ctx=MAX_CTX, budget=budget, rng=rng)
+    x, base = arm.endswith("_x"), base_arm(arm)
+    dtype = "fp32" if base == "f32_slab" else ("fp16" if seed % 4 == 2 else "bf16")
+    rng = np.random.default_rng(90000 + 17 * STREAM.get((seed, arm), seed) + ARMS.index(arm))      # (an _x arm's index is its own: a stream of its own)
+    max_batch = int(rng.integers(6, 9)) if x else int(rng.integers(4, 7))      # _x: a beam group of up to 4 + 2 spares next to bystanders
+    budget = blocks_for(int(BUDGET_X * max_batch * BLK)) * BLK if x else blocks_for(int(1.5 * max_batch * BLK)) * BLK
+    return dict(seed=seed, arm=arm, fam=fam, dtype=dtype, max_batch=max_batch, max_ctx=MAX_CTX, budget=budget if base == "h16_paged" else 0, rng=rng, extended=x)
+
+
+def angle_table(fam, dtype):
+    """the RoPE angles [MAX_CTX][hd / 2] tests/splice_ref.py rotates by: its own float32 table where the frequencies are unscaled; for Llama-3's scaled ones the
+    angles of the oracle's cos / sin tables (only differences of two angles are used, so the branch of atan2 does not matter)"""
+    if (fam, dtype) not in _angles:
+        d, _, _ = make_desc(fam, dtype, 1)
+        if d.rope_factor > 0:
+            cos, sin = new_oracle(fam, dtype).rope_tables(MAX_CTX)
+            _angles[(fam, dtype)] = np.arctan2(sin.astype(np.float64), cos.astype(np.float64))
+        else:
+            _angles[(fam, dtype)] = splice_ref.angles(d, MAX_CTX)
+    return _angles[(fam, dtype)]
+
+
+_angles = {}
+
+
+def round_storage(x, dtype):
+    """fp64 -> the storage dtype (round to nearest even), as float32"""
+    x = np.asarray(x, np.float64).astype(np.float32)
+    if dtype == "fp32":
+        return x
+    if dtype == "fp16":
+        return x.astype(np.float16).astype(np.float32)
+    u = x.view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32).reshape(x.shape)
 
 
 def make_desc(fam, dtype, max_batch, max_ctx=MAX_CTX):
@@ -548,6 +844,27 @@ class OracleSeq:
     def clear(self):
         self.o.reset_cache(); self.toks = []
 
+    # ---- a cache that is no function of the token list (tgx_splice_row): set from cache rows, never re-forwarded
+    def plant(self, kv, toks):
+        """the cache becomes kv ([layer] -> (K rows, V rows), rounded once to the storage dtype by write_kv) and holds len(toks) positions"""
+        self.o.reset_cache()
+        for l, (k, v) in enumerate(kv):
+            self.o.write_kv(0, l, k[:len(toks)], v[:len(toks)])
+        self.o.set_past(len(toks)); self.toks = [int(t) for t in toks]
+
+    def export(self, layers):
+        return [tuple(a.copy() for a in self.o.read_kv(0, l)) for l in range(layers)]
+
+    def splice(self, ranges, ang, layers):
+        kv = []
+        for l in range(layers):
+            k, v = self.o.read_kv(0, l)
+            kv.append(splice_ref.splice(k, v, ranges, ang))
+        self.plant(kv, [self.toks[p] for p in RowModel.splice_src(ranges)])
+
+    def cut(self, n):
+        self.o.set_past(n); self.toks = self.toks[:n]
+
     def logits(self):
         return self.o.logits(rounded=False)[0].copy()
 
@@ -570,6 +887,20 @@ def draw_token(lg, sampler, seed, pos, row):
     return int(np.random.default_rng([seed, pos, row]).choice(l.size, p=pr))
 
 
+def raw_advance_rows(dev, rows, kinds, ids, lens):
+    """tgx_advance_rows with a lens[] of the caller's own (tinygpt_amd.ffi.Model.advance_rows derives it from the arrays, so it cannot pass a negative one)"""
+    if isinstance(dev, OracleDevice):
+        return dev.advance_rows(rows, kinds, ids, lens=lens)
+    from ctypes import POINTER, c_int32, c_int64
+    a = lambda v, t: np.ascontiguousarray(np.asarray(v, dtype=t).reshape(-1))
+    r, k, n = a(rows, np.int32), a(kinds, np.int32), a(lens, np.int32)
+    flat = a([t for d in ids for t in d] + [0], np.int64)
+    out, out_n, fin = np.zeros((len(r), MAX_DRAFT + 1), np.int64), np.zeros(len(r), np.int32), np.zeros(len(r), np.int32)
+    p32, p64 = (lambda x: x.ctypes.data_as(POINTER(c_int32))), (lambda x: x.ctypes.data_as(POINTER(c_int64)))
+    dev._check(dev.be.advance_rows(dev._ctx, len(r), p32(r), p32(k), p64(flat), p32(n), p64(out), p32(out_n), p32(fin)))
+    return [(out[i, :out_n[i]].copy(), int(fin[i])) for i in range(len(r))]
+
+
 class OracleDevice:
     """the row calls of tinygpt_amd.ffi.Model answered by a RowModel and one batch-1 CPU oracle per row"""
     blob_is_private = True      # its snapshots are no tgx snapshots: two contexts need not write the same bytes
@@ -577,7 +908,7 @@ class OracleDevice:
     def __init__(self, fam, dtype, max_batch, max_ctx=MAX_CTX, budget=0):
         self.desc, _, _ = make_desc(fam, dtype, max_batch, max_ctx)
         self.fam, self.dtype = fam, dtype
-        self.m = RowModel(max_batch, max_ctx, self.desc.vocab, budget)
+        self.m = RowModel(max_batch, max_ctx, self.desc.vocab, budget, gpt2=self.desc.family == "gpt2")
         self.seq = [None] * max_batch
         self.kv = [None] * max_batch           # per row: [layer] -> [K rows, V rows], what read_kv returns
         self.lg = [None] * max_batch
@@ -606,7 +937,9 @@ class OracleDevice:
         """the row's oracle over base + new; the cache rows of `new` and the last logits become the row's"""
         o = self._oracle(r)
         base, new = list(base), [int(t) for t in new]
-        if base:
+        if base and self.m.rows[r].spliced:                         # the cache rows are the row's own: no token list gives them
+            o.plant(self.kv[r], base); o.sync(base + new)
+        elif base:
             o.sync(base); o.sync(base + new)
         else:
             o.clear(); o.sync(new)
@@ -655,7 +988,7 @@ class OracleDevice:
     def truncate_row(self, row, n):
         self._gate("truncate_row", row, int(n))
         x = self.m.rows[row]
-        if not (n == x.length and x.has_logits):
+        if not (n == x.length and x.has_logits and x.state != FINISHED):
             self.kv[row] = [[k[:n].copy(), v[:n].copy()] for k, v in self.kv[row]]
             self.lens[row] = int(n)
         self.m.apply("truncate_row", row, int(n))
@@ -746,6 +1079,76 @@ class OracleDevice:
     def _verified(self, row):
         pass
 
+    # ---- the later row calls
+    def splice_row(self, row, ranges):
+        ranges = [(int(s), int(n)) for s, n in np.asarray(ranges, np.int64).reshape(-1, 2)]
+        self._gate("splice_row", row, ranges)
+        new_len, f, noop, _ = self.m._splice_plan(row, ranges)
+        if not noop:
+            ang = angle_table(self.fam, self.dtype)
+            self.kv[row] = [[round_storage(a, self.dtype) for a in splice_ref.splice(k[:self.lens[row]], v[:self.lens[row]], ranges, ang)] for k, v in self.kv[row]]
+            self.lens[row] = new_len
+        self.m.apply("splice_row", row, ranges, out=new_len)
+        return new_len
+
+    def _verify_one(self, row, draft):
+        """tgx_verify_row_sampled's walk on one row -> (ids, finish); the model is not moved"""
+        x = self.m.rows[row]
+        toks, cur, shadow, out, fin = list(x.tokens), x.tok, Row(), [], 0
+        shadow.max_new, shadow.stop_ids, shadow.produced = x.max_new, x.stop_ids, x.produced
+        for i in range(len(draft) + 1):
+            self._step(row, toks, cur); toks.append(cur)
+            cur = draw_token(self.lg[row], x.sampler, x.seed, len(toks), row); out.append(cur); self._record(row, cur)
+            fin = shadow.note_produced(cur)
+            if fin or i == len(draft) or cur != draft[i]:
+                break
+        self._verified(row)
+        return np.array(out, np.int64), fin
+
+    def verify_rows(self, rows, drafts):
+        rows = [int(r) for r in rows]; drafts = [[int(t) for t in d] for d in drafts]
+        self._gate("verify_rows", rows, drafts)
+        out = [self._verify_one(r, d) for r, d in zip(rows, drafts)]
+        self.m.apply("verify_rows", rows, drafts, out=out)
+        return out
+
+    def advance_rows(self, rows, kinds, ids, lens=None):
+        rows = [int(r) for r in rows]; kinds = [int(k) for k in kinds]; ids = [[int(t) for t in d] for d in ids]
+        self._gate("advance_rows", rows, kinds, ids, *([] if lens is None else [list(lens)]))
+        out = []
+        for r, k, d in zip(rows, kinds, ids):
+            if k == STEP:
+                out.append(self._verify_one(r, d)); continue
+            x = self.m.rows[r]
+            if x.holds:
+                self._run(r, x.tokens, d)
+            else:
+                self.rec[r] = []; self._run(r, [], d)
+            out.append((np.zeros(0, np.int64), 0))
+        self.m.apply("advance_rows", rows, kinds, ids, out=out)
+        return out
+
+    def beam_select(self, rows, scores, k, end_ids=()):
+        rows = [int(r) for r in rows]; scores = [float(x) for x in scores]; end_ids = [int(e) for e in end_ids]
+        self._gate("beam_select", rows, scores, int(k), end_ids)
+        prefix, _ = beam_ref.select([self.lg[r] for r in rows], scores, int(k), end_ids)
+        return (np.array([c[1] for c in prefix], np.int32), np.array([c[3] for c in prefix], np.int32), np.array([c[0] for c in prefix], np.float32),
+                np.array([c[4] for c in prefix], np.float32))
+
+    def beam_advance(self, rows, parent, tokens):
+        rows = [int(r) for r in rows]; parent = [int(p) for p in parent]; tokens = [int(t) for t in tokens]
+        self._gate("beam_advance", rows, parent, tokens)
+        out, childless = self.m.beam_placement(rows, parent)
+        held = {rows[p]: (self._copy_rows(self.kv[rows[p]], self.lens[rows[p]]), self.lg[rows[p]].copy(), self.lens[rows[p]]) for p in parent}
+        for r in childless:
+            self.rec[r] = []; self.lens[r] = 0
+        for j, p in enumerate(parent):
+            if out[j] != rows[p]:
+                kv, lg, n = held[rows[p]]
+                self.kv[out[j]] = self._copy_rows(kv, n); self.lg[out[j]] = lg.copy(); self.lens[out[j]] = n; self.rec[out[j]] = []
+        self.m.apply("beam_advance", rows, parent, tokens, out=out)
+        return np.array(out, np.int32)
+
     # ---- copies
     def _copy_rows(self, src_kv, n):
         return [[k[:n].copy(), v[:n].copy()] for k, v in src_kv]
@@ -793,6 +1196,8 @@ class OracleDevice:
         return self.m.past_length()
 
     def get_option(self, key):
+        if key in ("verify.last_form", "advance.last_form"):
+            return 0                                                # no device pass is ever made here
         assert key == "kv.free_tokens"
         return self.m.free_tokens()
 
@@ -817,6 +1222,28 @@ class Mirror:
         if self.a[r] is not None:
             self.a[r].clear(); self.b[r].clear()
         self.lg[r] = None
+
+    # ---- rows whose cache tgx_splice_row has moved: the oracle's cache is spliced, cut and copied; it is never rebuilt from the token list
+    def splice(self, r, ranges, layers):
+        ang = angle_table(self.fam, self.dtype)
+        for o in self._pair(r):
+            o.splice(ranges, ang, layers)
+        self.lg[r] = None
+
+    def cut(self, r, n):
+        for o in self._pair(r):
+            o.cut(n)
+        self.lg[r] = None
+
+    def export(self, r, layers):
+        """what a copy of row r starts from: both oracles' cache rows, the token list, the logits"""
+        a, b = self._pair(r)
+        return dict(a=a.export(layers), b=b.export(layers), toks=list(a.toks), lg=None if self.lg[r] is None else self.lg[r].copy())
+
+    def plant(self, r, e, has_logits=True):
+        a, b = self._pair(r)
+        a.plant(e["a"], e["toks"]); b.plant(e["b"], e["toks"])
+        self.lg[r] = e["lg"].copy() if has_logits and e["lg"] is not None else None
 
     def _seen(self, r, la, lb):
         self.floor[r] = max(self.floor[r], rel_err(lb[None, :], la[None, :]))
@@ -856,6 +1283,7 @@ class Stats:
     def __init__(self):
         self.max_err = 0.0; self.floor = 0.0; self.greedy = 0; self.compared = 0
         self.accepted = {}; self.refused = {}; self.classes = {}; self.cov = {}; self.wall = 0.0
+        self.forms = {}            # (call, verify.last_form / advance.last_form) -> accepted calls
 
     def line(self):
         share = self.compared / max(self.greedy, 1)
@@ -881,8 +1309,17 @@ class Driver:
     WEIGHTS = dict(forward_row=2.0, forward_rows=1.2, reset_row=1.0, sample_row=1.5, set_row_sampler=0.6, set_row_stop=1.4, decode_rows=4.0, decode=0.8, fork_row=3.0,
                    extend_row=1.5, truncate_row=1.6, verify_row=2.0, snapshot=1.3, score_row=0.8, set_row_logprobs=1.0, finish_short_of_block=1.0)
 
-    def __init__(self, main, aux, rng, bound, gap, lp_tol, tag):
-        self.c, self.aux, self.rng = main, aux, rng
+    # the _x arms: the 16 kinds above plus the later row calls, which carry about half of the weight (beam = tgx_beam_select, then tgx_beam_advance on its candidates)
+    KINDS_X = ["splice_row", "verify_rows", "advance_rows", "beam_select", "beam_advance"]
+    WEIGHTS_X = dict(splice_row=6.0, verify_rows=5.0, advance_rows=7.0, beam=7.0)
+    LENS_X = [1, 2, 5, 17, 33, 100, 127, 128, 129]      # FEED lengths: every token goes through a per-row CPU oracle one by one behind a prefix
+    # the matrix-core routes' minimum (prefill_min_rows, set in tgx_create, tinygpt_amd/csrc/abi.hip: 5 at hidden <= 2048, 4 above): calls of fewer positions run row
+    # by row.  Every fixture of FAMS has hidden <= 512; a larger fixture needs its own value.  tgx_verify_rows' generator aims at it; tgx_advance_rows' FEED lengths
+    # (LENS_X) pass it on their own
+    MIN_JOINT = 5
+
+    def __init__(self, main, aux, rng, bound, gap, lp_tol, tag, extended=False):
+        self.c, self.aux, self.rng, self.extended = main, aux, rng, extended
         self.bound, self.gap, self.lp_tol, self.tag = bound, gap, lp_tol, tag
         self.log, self.stats, self.drawn = [], Stats(), {}
         self.pending, self.fixup = [], False
@@ -946,7 +1383,8 @@ class Driver:
             ret = m.apply(kind, *args, out=out_to_model(out)) if out_to_model else m.apply(kind, *args)
         except AssertionError as e:
             self.fail(f"the device's outputs contradict the header: {e}")
-        if kind in ("forward_row", "forward_rows", "extend_row", "score_row", "restore_row", "fork_row", "decode", "decode_rows", "verify_row"):
+        if kind in ("forward_row", "forward_rows", "extend_row", "score_row", "restore_row", "fork_row", "decode", "decode_rows", "verify_row", "verify_rows",
+                    "advance_rows", "beam_advance"):
             c.logits_exist = c.logits_exist or any(x.has_logits for x in m.rows)
         if named is None:
             named = ret
@@ -1081,7 +1519,9 @@ class Driver:
         res = self.op(c, "truncate_row", (row, n), lambda d: d.truncate_row(row, n), [row], illegal=illegal)
         if res:
             self.same_row(res["before"], res["after"], row, row, "truncate_row: rows [0, new_len)", upto=n, logits=False)
-            if not c.m.rows[row].has_logits:
+            if not c.m.rows[row].has_logits and c.m.rows[row].spliced:
+                c.mir.cut(row, n); self.mark("truncate_spliced_row")
+            elif not c.m.rows[row].has_logits:
                 c.mir.follow(row, c.m.rows[row].tokens); c.mir.lg[row] = None
         return res
 
@@ -1119,7 +1559,9 @@ class Driver:
         if res:
             for d in dsts:
                 self.same_row(res["after"], res["after"], src, d, f"fork {src} -> {d}")
-                c.mir.clear(d); c.mir.follow(d, c.m.rows[d].tokens)
+                self.copy_mirror(c, src, d)
+            if c.m.rows[src].spliced:
+                self.mark("splice_then_fork")
             self.check_logits(c, res["after"])
         return res
 
@@ -1143,6 +1585,8 @@ class Driver:
         if res:
             self.same_row(res["before"], res["after"], row, row, "a save changes nothing", logits=c.m.rows[row].has_logits)
             shot = dict(kv={0: res["after"]["kv"][row]}, lg=[res["after"]["lg"][row].copy()] if c.m.rows[row].has_logits else None)
+            if c.m.rows[row].spliced:                               # no token list gives this cache: the reference's own travels with the snapshot
+                res["ret"].planted = c.mir.export(row, c.layers)
             return res["out"], res["ret"], shot
         return None
 
@@ -1152,11 +1596,447 @@ class Driver:
         if res:
             self.need(res["after"]["lens"][row] == len(snap.tokens), "restored length")
             self.same_row(shot, res["after"], 0, row, f"restore into row {row}", logits=snap.has_logits)
-            c.mir.clear(row); c.mir.follow(row, snap.tokens)
+            if snap.spliced:
+                c.mir.plant(row, snap.planted, snap.has_logits)
+            else:
+                c.mir.clear(row); c.mir.follow(row, snap.tokens)
             if not snap.has_logits:
                 c.mir.lg[row] = None
             self.check_logits(c, res["after"])
         return res
+
+    # ---- the later row calls
+    def mark(self, what):
+        self.stats.cov[what] = self.stats.cov.get(what, 0) + 1
+
+    def copy_mirror(self, c, src, dst):
+        """the reference of a copy: a forward of the token list, or — behind a splice — the source oracle's cache rows"""
+        if c.m.rows[dst].spliced:
+            c.mir.plant(dst, c.mir.export(src, c.layers))
+        else:
+            c.mir.clear(dst); c.mir.follow(dst, c.m.rows[dst].tokens)
+
+    def tally_form(self, c, call):
+        if c is self.c:
+            f = int(c.dev.get_option(call + ".last_form"))
+            self.stats.forms[(call, f)] = self.stats.forms.get((call, f), 0) + 1
+
+    def do_splice(self, c, row, ranges, illegal=None):
+        from test_hip_splice_row import rotated_k_bound
+        m = c.m
+        ranges = [(int(s), int(n)) for s, n in ranges]
+        legal = not m.reasons("splice_row", row, ranges)
+        if legal:
+            x = m.rows[row]
+            plan, pre, was_spliced, was = m._splice_plan(row, ranges), list(x.tokens), x.spliced, (x.state, x.has_logits, x.has_token)
+        elif c is self.c and m._in(row) and not m.rows[row].holds and 1 <= len(ranges) <= MAX_SPLICE_RANGES:
+            self.mark("splice_refused_retired_row" if row < m.batch else "splice_refused_row_beyond_batch")
+        res = self.op(c, "splice_row", (row, ranges), lambda d: d.splice_row(row, np.array(ranges, np.int64).reshape(-1, 2)), [row], out_to_model=lambda n: n, illegal=illegal)
+        if not res:
+            return res
+        res["was"] = was
+        new_len, f, noop, _ = plan
+        if c is self.c:
+            was = res["was"]
+            self.mark("splice_on_finished_row" if was[0] == FINISHED else "splice_on_no_logits_row" if not was[1] else "splice_on_token_row" if was[2] else "splice_on_logits_only_row")
+            if noop:
+                self.mark("splice_noop")
+            elif f == new_len:
+                self.mark("splice_truncation_form")
+            elif ranges[0][0] == 0:
+                self.mark("splice_lead_on_block_edge" if f % BLK == 0 else "splice_lead_inside_block")
+            if any(a[0] + a[1] == b[0] for a, b in zip(ranges, ranges[1:])):
+                self.mark("splice_ranges_touch")
+        if noop:
+            self.same_row(res["before"], res["after"], row, row, "splice_row: the no-op")
+            return res
+        src = np.array(RowModel.splice_src(ranges)); moved = src != np.arange(new_len)
+        ang = angle_table(c.mir.fam, c.mir.dtype)
+        for l in range(c.layers):
+            (k0, v0), (k1, v1) = res["before"]["kv"][row][l], res["after"]["kv"][row][l]
+            self.need(v1.shape == v0[src].shape and np.array_equal(v1.view(np.uint32), v0[src].view(np.uint32)), f"splice_row: V rows of layer {l} are not the kept source rows")
+            self.need(np.array_equal(k1[~moved].view(np.uint32), k0[src][~moved].view(np.uint32)), f"splice_row: K rows of layer {l} with delta 0 changed")
+            if moved.any():
+                ref, _ = splice_ref.splice(k0, v0, ranges, ang)
+                err, bound = np.abs(k1 - ref)[moved], rotated_k_bound(ref, c.mir.dtype)[moved]
+                self.need((err <= bound).all(), f"splice_row: rotated K rows of layer {l} are {float((err / bound).max()):.2f} of the bound from tests/splice_ref.py")
+        if f < new_len:
+            if not was_spliced and (c.mir.a[row] is None or c.mir.a[row].toks != pre):
+                c.mir.follow(row, pre)
+            c.mir.splice(row, ranges, c.layers)
+        elif was_spliced:
+            c.mir.cut(row, new_len); self.mark("truncate_spliced_row")
+        else:
+            c.mir.follow(row, m.rows[row].tokens); c.mir.lg[row] = None
+        return res
+
+    def _stepped(self, c, r, base, tok, greedy, o, what, before, after):
+        """what the driver checks of a row that tgx_verify_row stepped, for every STEP row of the joint calls"""
+        out = [int(t) for t in o[0]]
+        self.same_row(before, after, r, r, what + ": the prefix", upto=len(base), logits=False)
+        self.follow_steps(c, r, base, [tok] + out[:-1], out, greedy, what)
+        if c.m.rows[r].state == FINISHED:
+            c.mir.lg[r] = None
+        else:
+            self.check_lp(c, r, after, out[-1])
+
+    def do_verify_rows(self, c, rows, drafts, illegal=None):
+        m = c.m
+        pre = {r: (list(m.rows[r].tokens), m.rows[r].tok, is_greedy(m.rows[r].sampler)) for r in rows if m._in(r)}
+        res = self.op(c, "verify_rows", (rows, drafts), lambda d: d.verify_rows(rows, drafts), rows, out_to_model=lambda o: o, illegal=illegal)
+        if res:
+            for r, o in zip(rows, res["out"]):
+                self._stepped(c, r, *pre[r], o, "verify_rows", res["before"], res["after"])
+            self.check_logits(c, res["after"])
+            self.tally_form(c, "verify")
+        return res
+
+    def do_advance_rows(self, c, rows, kinds, ids, lens=None, illegal=None):
+        m = c.m
+        pre = {r: (list(m.rows[r].tokens), m.rows[r].tok, is_greedy(m.rows[r].sampler), m.rows[r].holds) for r in rows if m._in(r)}
+        if lens is not None:                                        # a lens[] of its own: the raw call, refused by the header whatever else it names
+            return self.op(c, "advance_rows", (rows, kinds, ids, lens), lambda d: raw_advance_rows(d, rows, kinds, ids, lens), rows, out_to_model=lambda o: o, illegal=illegal)
+        res = self.op(c, "advance_rows", (rows, kinds, ids), lambda d: d.advance_rows(rows, kinds, ids), rows, out_to_model=lambda o: o, illegal=illegal)
+        if res:
+            for r, k, d, o in zip(rows, kinds, ids, res["out"]):
+                base, tok, greedy, held = pre[r]
+                if k == STEP:
+                    self._stepped(c, r, base, tok, greedy, o, "advance_rows", res["before"], res["after"])
+                    continue
+                if held:
+                    self.same_row(res["before"], res["after"], r, r, "advance_rows: the prefix", upto=len(base), logits=False)
+                    self.follow_steps(c, r, base, d, [], False, "advance_rows")
+                else:
+                    c.mir.clear(r); c.mir.follow(r, d)
+                if k == FEED_MORE:
+                    c.mir.lg[r] = None
+            self.check_logits(c, res["after"])
+            self.tally_form(c, "advance")
+        return res
+
+    def do_beam_select(self, c, rows, scores, k, ends, illegal=None):
+        res = self.op(c, "beam_select", (rows, scores, k, ends), lambda d: d.beam_select(rows, scores, k, ends), [], illegal=illegal)
+        if res:
+            beam, token, score, lp = res["out"]
+            vecs = [res["after"]["lg"][r] for r in rows]
+            prefix, rest = beam_ref.select(vecs, scores, k, ends)
+            self.need(len(beam) == len(prefix), f"beam_select returned {len(beam)} candidates, the reference on the device's own logits {len(prefix)}")
+            seq = prefix + rest[:1]
+            for j, (key, i, _, t, l) in enumerate(prefix):
+                tied = (j > 0 and seq[j - 1][0] == key) or (j + 1 < len(seq) and seq[j + 1][0] == key)
+                if not tied:                                        # (which of two equal keys comes first is the order's business; their score is the same number)
+                    self.need((int(beam[j]), int(token[j])) == (i, t), f"beam_select: candidate {j} is {(int(beam[j]), int(token[j]))}, the reference's {(i, t)}")
+                    self.need(abs(float(lp[j]) - l) <= self.lp_tol, f"beam_select: candidate {j} lp {float(lp[j]):.7f}, the reference's {l:.7f}")
+                else:                                               # the device's own choice among the tied: its lp against that row's reference
+                    self.need(0 <= int(beam[j]) < len(rows) and 0 <= int(token[j]) < c.m.vocab, f"beam_select: candidate {j} is {(int(beam[j]), int(token[j]))}")
+                    own = float(beam_ref.log_softmax64(vecs[int(beam[j])])[int(token[j])])
+                    self.need(abs(float(lp[j]) - own) <= self.lp_tol, f"beam_select: candidate {j} lp {float(lp[j]):.7f}, the fp64 log-softmax of its row gives {own:.7f}")
+                # lp_tol plus the fp32 rounding of the key: tests/test_hip_beam.py's bound on a score
+                self.need(abs(float(score[j]) - key) <= self.lp_tol + 2.0 ** -23 * abs(key), f"beam_select: candidate {j} score {float(score[j]):.7f}, the reference's {key:.7f}")
+        return res
+
+    def do_beam_advance(self, c, rows, parent, tokens, illegal=None):
+        m = c.m
+        lens = {r: m.rows[r].length for r in rows if m._in(r)}
+        res = self.op(c, "beam_advance", (rows, parent, tokens), lambda d: d.beam_advance(rows, parent, tokens), rows, out_to_model=lambda o: [int(r) for r in o], illegal=illegal)
+        if res:
+            want, childless = res["ret"]
+            for r in childless:
+                self.need(r in want or res["after"]["lens"][r] == 0, f"beam_advance: the childless source {r} is not retired")
+                c.mir.clear(r)
+            for j, p in enumerate(parent):
+                r, d = rows[p], want[j]
+                self.need(res["after"]["lens"][d] == lens[r], f"beam_advance: hypothesis {j} in row {d} holds {res['after']['lens'][d]} positions, its parent held {lens[r]}")
+                self.same_row(res["before"], res["after"], r, d, f"beam_advance: hypothesis {j} (row {r} -> {d})", upto=lens[r])
+                if d != r:
+                    self.copy_mirror(c, r, d)
+            self.check_logits(c, res["after"])
+        return res
+
+    def drafts_for(self, c, r, nd):
+        """as verify_row's generator: the oracle's greedy continuation, half of the time with one id replaced — accept lengths vary"""
+        x = c.m.rows[r]
+        if nd == 0:
+            return []
+        if not is_greedy(x.sampler) or x.spliced:
+            return self.ids(nd)
+        draft = c.mir.greedy_continuation(x.tokens, x.tok, nd)
+        if self.rng.random() < 0.5:
+            i = int(self.rng.integers(0, nd)); draft[i] = (draft[i] + 1 + int(self.rng.integers(0, c.m.vocab - 1))) % c.m.vocab
+        return draft
+
+    def splice_ranges(self, L):
+        """1 .. 4 kept ranges of a row of L >= 2 positions, in one of the forms the header singles out"""
+        rng = self.rng
+        form = str(self.pick(["noop", "trunc", "lead_in_block", "lead_on_edge", "touch", "no_lead", "multi", "multi"]))
+        cut = lambda lo, hi: int(rng.integers(lo, hi)) if hi > lo else lo
+        if form == "noop":
+            return [(0, L)]
+        if form == "trunc":
+            return [(0, cut(1, L))]
+        if form == "no_lead":
+            s = cut(1, L); return [(s, L - s)]
+        if form == "lead_on_edge" and L > BLK + 1:
+            a = BLK * cut(1, (L - 2) // BLK + 1); b = cut(a + 1, L)
+            return [(0, a), (b, L - b)]
+        if form == "touch" and L >= 4:
+            a = cut(1, L - 2); b = cut(a + 1, L - 1); e = cut(b + 1, L + 1)
+            return [(0, a), (a, b - a)] + ([(e, L - e)] if e < L else [])      # (without a third range: a truncation in two touching pieces)
+        if form in ("lead_in_block", "lead_on_edge", "touch"):
+            a = cut(1, L); a += a % BLK == 0 and a + 1 < L
+            b = cut(min(a + 1, L - 1), L)
+            return [(0, a), (b, L - b)] if b > a else [(0, a)]
+        n = int(rng.integers(2, 5))
+        pts = sorted(set(int(x) for x in rng.integers(0, L + 1, 2 * n)))
+        out = [(pts[i], pts[i + 1] - pts[i]) for i in range(0, len(pts) - 1, 2)]
+        return out or [(0, L)]
+
+    def draw_legal_x(self, kind):
+        """one of the later row calls, legal up to the pool (a shortfall is a refusal the model predicts)"""
+        c, m, rng = self.c, self.c.m, self.rng
+        live = self.rows_where(c, lambda r, x: x.state == LIVE)
+        ready = [r for r in live if m.rows[r].has_logits and m.rows[r].has_token and m.rows[r].length + 1 <= m.max_ctx]
+        if kind == "splice_row":
+            cand = self.rows_where(c, lambda r, x: x.holds and x.length >= 2)
+            if not cand:
+                return None
+            shared = [r for r in cand if m.pool and any(m.pool.shared(b) for b in m.rows[r].blocks)]
+            r = int(self.pick(shared)) if shared and rng.random() < 0.6 else int(self.pick(cand))
+            fin = [q for q in cand if m.rows[q].state == FINISHED]
+            if fin and rng.random() < 0.7:
+                r = int(self.pick(fin))
+            x = m.rows[r]
+            ranges = self.splice_ranges(x.length)
+            if r in shared and x.length > BLK + 2 and rng.random() < 0.9:      # the identity prefix covers whole blocks the siblings map as well: they stay shared
+                a = int(rng.integers(BLK, x.length - 1)); b = int(rng.integers(a + 1, x.length))
+                ranges = [(0, a), (b, x.length - b)]
+            if r in shared and not m.pool.free and rng.random() < 0.8:      # no free block: a splice that writes into a shared block is refused whatever the row gives back
+                ranges = [(1, x.length - 1)]
+            res = self.do_splice(c, r, ranges)
+            if res and not m.gpt2 and not m.rows[r].has_logits:    # next: what the spliced row goes through — fed again and forked, saved and restored, rolled back
+                nxt = str(self.pick(["fork", "fork", "snapshot", "snapshot", "truncate", "none"]))
+                if nxt == "fork":
+                    def feed_and_fork():
+                        if m.rows[r].holds and m.rows[r].spliced and m.rows[r].length + 3 <= m.max_ctx and self.do_extend(c, r, self.ids(int(rng.integers(1, 4)))):
+                            t = self.free_targets(c, int(rng.integers(1, 3)))
+                            if t:
+                                self.pending.append(lambda: self.do_fork(c, r, t) if m.rows[r].state == LIVE and m.rows[r].has_logits and not any(m.rows[d].holds for d in t) else None)
+                    self.pending.append(feed_and_fork)
+                elif nxt == "snapshot":
+                    self.pending.append(lambda: self.do_snapshot(r) if m.rows[r].state == LIVE else None)
+                elif nxt == "truncate" and m.rows[r].length >= 2:
+                    n = int(rng.integers(1, m.rows[r].length))
+                    self.pending.append(lambda: self.do_truncate(c, r, n) if m.rows[r].holds and m.rows[r].length >= n else None)
+            return res
+        if kind == "verify_rows":
+            if not ready:
+                return None
+            rng.shuffle(ready)
+            edge = [r for r in ready if m.rows[r].length % BLK >= BLK - MAX_DRAFT and m.rows[r].length + MAX_DRAFT + 1 <= m.max_ctx]
+            if not edge and m.pool and rng.random() < 0.35 and self.free_targets(c, 1):      # no such row: one is admitted, and verified next with a draft of noise
+                t = self.free_targets(c, 1)
+                res = self.do_admit(c, t, [self.ids(int(self.pick([120, 125, 127])))], "forward_row")
+                if res:
+                    self.pending.append(lambda: self.do_sample(c, t[0]) if m.rows[t[0]].state == LIVE and m.rows[t[0]].has_logits else None)
+                    self.pending.append(lambda: self.do_verify_rows(c, t, [self.ids(MAX_DRAFT)]) if m.rows[t[0]].state == LIVE and m.rows[t[0]].has_logits and m.rows[t[0]].has_token else None)
+                return res
+            if edge and rng.random() < 0.7:                        # a row whose draft reaches into the next block comes first
+                ready = edge[:1] + [r for r in ready if r != edge[0]]
+            rows = [int(r) for r in ready[:int(rng.integers(1, len(ready) + 1))]]
+            zero, left, drafts = rng.random() < 0.2, MAX_VERIFY_POSITIONS, []
+            for i, r in enumerate(rows):
+                room = min(MAX_DRAFT, m.max_ctx - m.rows[r].length - 1, left - (len(rows) - i))
+                nd = 0 if zero or room < 1 else int(rng.integers(0, room + 1))
+                if i == 0 and not zero and rng.random() < 0.5:                 # at or above the joint pass's minimum whatever the other rows draw
+                    nd = max(nd, min(room, self.MIN_JOINT - 1))
+                if i == 0 and r in edge and not zero and rng.random() < 0.7:   # ... and is all noise: the block it was given for the draft goes back
+                    drafts.append(self.ids(room)); left -= room + 1
+                    continue
+                drafts.append(self.drafts_for(c, r, nd)); left -= nd + 1
+            return self.do_verify_rows(c, rows, drafts)
+        if kind == "advance_rows":
+            fin_now = any(x.state == FINISHED for x in m.rows)
+            mode = "mixed" if fin_now else str(self.pick(["mixed", "mixed", "mixed", "mixed", "no_step", "no_feed"]))
+            rows, kinds, ids, left, nb = [], [], [], MAX_VERIFY_POSITIONS, m.batch
+            feed = lambda room: (FEED_MORE if rng.random() < 0.3 else FEED, self.ids(int(self.pick([n for n in self.LENS_X if n <= room]))))
+            for r in rng.permutation(m.max_batch):
+                r, x = int(r), m.rows[int(r)]
+                if r >= m.batch:
+                    continue
+                if x.state == LIVE and x.has_logits and x.has_token and mode != "no_step" and rng.random() < (0.9 if fin_now else 0.6) and x.length + 1 <= m.max_ctx and left >= 1:
+                    nd = int(rng.integers(0, min(MAX_DRAFT, m.max_ctx - x.length - 1, left - 1) + 1))
+                    rows.append(r); kinds.append(STEP); ids.append(self.drafts_for(c, r, nd)); left -= nd + 1
+                elif mode != "no_feed" and x.length < m.max_ctx and rng.random() < (0.8 if x.state == FINISHED or x.fed_more or x.state == RETIRED else 0.3):
+                    k, d = feed(m.max_ctx - x.length)
+                    rows.append(r); kinds.append(k); ids.append(d)
+            while mode != "no_feed" and nb < m.max_batch and rng.random() < 0.4:      # new rows: exactly batch .. batch + k - 1
+                k, d = feed(m.max_ctx)
+                rows.append(nb); kinds.append(k); ids.append(d); nb += 1
+            if not rows:
+                return None
+            return self.do_advance_rows(c, rows, kinds, ids)
+        if kind == "beam":
+            srcs = [r for r in live if m.rows[r].has_logits]
+            if len(srcs) < 2:
+                return None
+            rng.shuffle(srcs)
+            srcs = [int(r) for r in srcs[:int(rng.integers(2, min(4, len(srcs)) + 1))]]
+            scores = [float(x) for x in -np.round(rng.uniform(0, 6, len(srcs)) * 64) / 64]
+            k = int(rng.integers(1, len(srcs) + 3))
+            ends = self.ids(int(rng.integers(1, 4))) if rng.random() < 0.3 else []
+            sel = self.do_beam_select(c, srcs, scores, min(k, MAX_BEAMS), ends)
+            retired = self.rows_where(c, lambda r, x: r < m.batch and x.state == RETIRED)
+            spares = [int(r) for r in retired[:int(rng.integers(0, 3))]]
+            nb = m.batch
+            while len(spares) < 2 and nb < m.max_batch and rng.random() < 0.5:
+                spares.append(nb); nb += 1
+            rows = srcs + spares
+            n_next = int(rng.integers(1, len(rows) + 1))
+            parent = [int(p) for p in rng.integers(0, len(srcs), n_next)]
+            tailed = [i for i, r in enumerate(srcs) if m.rows[r].length % BLK]
+            if m.pool and len(m.pool.free) <= 2 and tailed and rng.random() < 0.9:      # a nearly empty pool: every row of the group a child of one parent, a fresh tail block each
+                parent = [int(self.pick(tailed))] * len(rows)
+            cand = {}
+            if sel:
+                for b, t in zip(sel["out"][0], sel["out"][1]):
+                    cand.setdefault(int(b), []).append(int(t))
+            tokens = [cand[p].pop(0) if cand.get(p) and rng.random() < 0.7 else int(rng.integers(0, m.vocab)) for p in parent]
+
+            def advance():
+                if all(m.rows[r].state == LIVE and m.rows[r].has_logits for r in srcs) and not any(m.rows[r].holds for r in spares) and [r for r in spares if r >= m.batch] == list(range(m.batch, m.batch + len([r for r in spares if r >= m.batch]))):
+                    if self.do_beam_advance(c, rows, parent, tokens):
+                        self.pending.append(lambda: self.ready_and_decode(c, 1))      # next: the step that makes the children differ
+            self.pending.append(advance)
+            return sel
+        return None
+
+    # the classes tests/test_row_model.py asks the seed set for: drawn first while a run has not drawn them (most need a state few operations leave a row in)
+    REACH_X = ("splice_gpt2", "splice_empty", "splice_retired", "verify_rows_twice", "verify_rows_notok", "verify_rows_positions", "advance_gap", "advance_step_nolog",
+               "advance_neg_len", "beam_parent_is_spare", "beam_finished", "beam_select_twice")
+
+    def draw_illegal_x(self, force=None):
+        """one of the later row calls that the header refuses in the current state for exactly one reason (None: no class is open)"""
+        c, m, rng = self.c, self.c.m, self.rng
+        live = self.rows_where(c, lambda r, x: x.state == LIVE)
+        holds = self.rows_where(c, lambda r, x: x.holds and x.length >= 3)
+        ready = [r for r in live if m.rows[r].has_logits and m.rows[r].has_token and m.rows[r].length + 2 <= m.max_ctx]
+        nolog = [r for r in live if not m.rows[r].has_logits]
+        notok = [r for r in live if m.rows[r].has_logits and not m.rows[r].has_token]
+        fin = self.rows_where(c, lambda r, x: x.state == FINISHED)
+        retired = self.rows_where(c, lambda r, x: r < m.batch and x.state == RETIRED)
+        full = [r for r in ready if m.rows[r].length + MAX_DRAFT + 1 > m.max_ctx]
+        srcs = [r for r in live if m.rows[r].has_logits]
+        gap = m.batch + 1 < m.max_batch
+        wide = [r for r in live if m.rows[r].has_logits and m.rows[r].length + MAX_DRAFT + 1 <= m.max_ctx]      # five of them exceed TGX_MAX_VERIFY_POSITIONS
+        opts = []
+        if m.gpt2:
+            opts += ["splice_gpt2"] if holds else []
+        else:
+            opts += ["splice_empty", "splice_unsorted", "splice_overlap", "splice_beyond", "splice_n_keep"] if holds else []
+            opts += ["splice_retired"] if retired or m.batch < m.max_batch else []
+            opts += ["splice_row_range"]
+        if ready:
+            opts += ["verify_rows_twice"] + (["verify_rows_max_ctx"] if full else [])
+            opts += ["verify_rows_notok"] if notok else []
+            opts += ["verify_rows_nolog"] if nolog else []
+            opts += ["verify_rows_finished"] if fin else []
+            opts += ["verify_rows_positions", "advance_step_positions"] if len(wide) >= 5 else []
+            opts += ["advance_kind", "advance_twice"]
+            opts += ["advance_step_nolog"] if nolog else []
+            opts += ["advance_step_notok"] if notok else []
+        opts += ["advance_gap"] if gap else []
+        opts += ["advance_positions", "advance_len0", "advance_neg_len"] if live else []
+        if len(srcs) >= 2:
+            opts += ["beam_twice", "beam_token", "beam_select_twice"]
+            opts += ["beam_parent_is_spare"] if retired or m.batch < m.max_batch else []
+            opts += ["beam_finished"] if fin else []
+            opts += ["beam_gap"] if gap else []
+            opts += ["beam_select_nolog"] if nolog else []
+        if not opts:
+            return None
+        if force is not None:
+            opts = [o for o in opts if o == force]
+            if not opts:
+                return None
+        rare = [o for o in opts if o in self.REACH_X and not self.drawn.get(o)]
+        if rare and rng.random() < 0.7:                             # classes that need a state few operations leave a row in
+            opts = rare
+        least = min(self.drawn.get(o, 0) for o in opts)
+        what = str(self.pick(sorted({o for o in opts if self.drawn.get(o, 0) == least})))
+        self.drawn[what] = self.drawn.get(what, 0) + 1
+        if what in ("verify_rows_positions", "advance_step_positions"):
+            ready = [int(r) for r in wide[:5]]
+            for r in ready:
+                if not m.rows[r].has_token:
+                    self.do_sample(c, r)
+        kind, args = self.illegal_call_x(what, live, holds, ready, nolog, notok, fin, retired, full, srcs)
+        if len({code for code, _ in m.reasons(kind, *args)}) != 1:      # only calls the header refuses for one code (a pool already short adds a second)
+            return None
+        do = dict(splice_row=self.do_splice, verify_rows=self.do_verify_rows, advance_rows=self.do_advance_rows, beam_select=self.do_beam_select, beam_advance=self.do_beam_advance)[kind]
+        return do(c, *args, illegal=what)
+
+    def illegal_call_x(self, what, live, holds, ready, nolog, notok, fin, retired, full, srcs):
+        c, m, rng = self.c, self.c.m, self.rng
+        if what.startswith("splice"):
+            r = int(self.pick(holds)) if holds else 0
+            L = m.rows[r].length
+            if what == "splice_gpt2":
+                return "splice_row", (r, [(0, 1), (2, L - 2)])
+            if what == "splice_retired":                                           # a retired row of the batch, or the first row beyond it
+                return "splice_row", (int(self.pick(retired)) if retired and (m.batch >= m.max_batch or rng.random() < 0.5) else m.batch, [(0, 1)])
+            if what == "splice_row_range":
+                return "splice_row", (m.max_batch, [(0, 1)])
+            ranges = dict(splice_empty=[(0, 1), (2, 0)], splice_unsorted=[(2, 1), (0, 1)], splice_overlap=[(0, 2), (1, 2)], splice_beyond=[(0, 1), (L - 1, 2)],
+                          splice_n_keep=[(i, 1) for i in range(0, 2 * MAX_SPLICE_RANGES + 2, 2)])[what]
+            return "splice_row", (r, ranges)
+        if what.startswith("verify_rows"):
+            good = [int(r) for r in ready[:2]]
+            if what == "verify_rows_twice":
+                return "verify_rows", (good + [good[0]], [self.ids(2) for _ in range(len(good) + 1)])
+            if what == "verify_rows_positions":
+                rows = [int(r) for r in ready[:5]]
+                return "verify_rows", (rows, [self.ids(MAX_DRAFT) for r in rows])
+            bad = dict(verify_rows_max_ctx=full, verify_rows_notok=notok, verify_rows_nolog=nolog, verify_rows_finished=fin)[what]
+            b = int(self.pick(bad))
+            rows = [r for r in good if r != b] + [b]
+            return "verify_rows", (rows, [self.ids(1) for _ in rows[:-1]] + [self.ids(MAX_DRAFT if what == "verify_rows_max_ctx" else 1)])
+        if what.startswith("advance"):
+            good = [int(r) for r in ready[:2]]
+            if what == "advance_kind":
+                return "advance_rows", (good, [3] + [STEP] * (len(good) - 1), [self.ids(1) for _ in good])
+            if what == "advance_twice":
+                return "advance_rows", (good + [good[0]], [STEP] * len(good) + [FEED], [[] for _ in good] + [self.ids(2)])
+            if what == "advance_step_positions":
+                rows = [int(r) for r in ready[:5]]
+                return "advance_rows", (rows, [STEP] * 5, [self.ids(MAX_DRAFT) for r in rows])
+            if what in ("advance_step_nolog", "advance_step_notok"):
+                b = int(self.pick(nolog if what == "advance_step_nolog" else notok))
+                return "advance_rows", (good + [b], [STEP] * (len(good) + 1), [[] for _ in good] + [[]])
+            if what == "advance_gap":
+                return "advance_rows", ([m.batch + 1], [FEED], [self.ids(3)])
+            if what == "advance_len0":
+                return "advance_rows", ([int(self.pick(live))], [FEED], [[]])
+            if what == "advance_neg_len":                                         # behind rows that are legal: nothing may change for them
+                rows = good + [int(self.pick([r for r in live if r not in good] or live))]
+                rows = rows if len(set(rows)) == len(rows) else rows[-1:]
+                return "advance_rows", (rows, [STEP] * (len(rows) - 1) + [FEED], [[] for _ in rows], [0] * (len(rows) - 1) + [-1])
+            n = m.max_batch                                                       # more than TGX_MAX_ADVANCE_POSITIONS ids in all: refused ahead of every row's own check
+            return "advance_rows", (list(range(n)), [FEED] * n, [[0] * (MAX_ADVANCE_POSITIONS // n + 1) for _ in range(n)])
+        two = [int(r) for r in srcs[:2]]
+        spare = int(retired[0]) if retired else m.batch
+        if what == "beam_select_twice":
+            return "beam_select", (two + [two[0]], [0.0, -1.0, -2.0], 2, [])
+        if what == "beam_select_nolog":
+            return "beam_select", (two + [int(nolog[0])], [0.0, -1.0, -2.0], 2, [])
+        if what == "beam_twice":
+            return "beam_advance", (two + [two[0]], [0, 1], [1, 2])
+        if what == "beam_token":
+            return "beam_advance", (two, [0, 1], [1, m.vocab])
+        if what == "beam_parent_is_spare":
+            return "beam_advance", (two + [spare], [0, 2], [1, 2])
+        if what == "beam_finished":
+            return "beam_advance", (two + [int(fin[0])], [0, 1], [1, 2])
+        return "beam_advance", ([two[0], m.batch + 1], [0, 0], [1, 2])          # beam_gap: the copied child would land in a new row that is not batch
 
     # ---- drawing
     def rows_where(self, c, pred):
@@ -1374,6 +2254,8 @@ class Driver:
             if res:
                 key = "restore_cross_layout" if bool(a.m.pool) != bool(c.m.pool) else "restore_cross_context"
                 self.stats.cov[key] = self.stats.cov.get(key, 0) + 1
+                if saved[1].spliced and key == "restore_cross_layout":
+                    self.mark("splice_then_restore_cross_layout")
                 again = self.do_save(a, t[0])
                 self.need(again is not None, "the restored row cannot be saved")
                 if isinstance(saved[0], bytes) and not getattr(c.dev, "blob_is_private", False):
@@ -1510,6 +2392,25 @@ class Driver:
             # need one are drawn while it does
             if self.pending:
                 self.pending.pop(0)(); was_illegal = False
+            elif self.extended and self.rng.random() < 0.5:        # _x arms: half of the draws are the later row calls, three in ten of those illegal on purpose
+                n_log = len(self.log)
+                if i >= 1 and not self.drawn.get("beam_finished") and any(x.state == FINISHED for x in c.m.rows) and self.rng.random() < 0.6:
+                    self.draw_illegal_x(force="beam_finished"); was_illegal = True      # (a finished row lives for an operation or two)
+                elif i >= 1 and self.rng.random() < 0.3:
+                    self.draw_illegal_x(); was_illegal = True
+                else:
+                    kinds = list(self.WEIGHTS_X); w = np.array([self.WEIGHTS_X[k] for k in kinds])
+                    if self.stats.greedy < 2 * len(self.log):      # few tokens so far: towards the calls that produce them
+                        w[kinds.index("verify_rows")] *= 3; w[kinds.index("advance_rows")] *= 2
+                    if any(x.state == FINISHED for x in c.m.rows):  # a finished row lives for an operation or two: an admission over it next to a STEP of another row,
+                        w[kinds.index("advance_rows")] *= 4; w[kinds.index("splice_row")] *= 3      # or a splice that clears its state
+                    if c.m.pool and not c.m.pool.free and any(c.m.pool.shared(b) for x in c.m.rows for b in x.blocks):
+                        w[kinds.index("splice_row")] *= 4           # an empty free list next to shared blocks: the copy on write that cannot be had
+                    if c.m.pool and len(c.m.pool.free) <= 2:
+                        w[kinds.index("beam")] *= 3                 # ... and the fresh tail blocks of a beam group's copies
+                    self.draw_legal_x(kinds[int(self.rng.choice(len(kinds), p=w / w.sum()))]); was_illegal = False
+                if len(self.log) == n_log:                          # the state offered that call nothing: one of the 16 instead
+                    self.draw_legal(); was_illegal = False
             elif i >= 1 and self.rng.random() < (0.3 if not was_illegal and self.draw_illegal(probe=True) else 1.0 / 8.0):
                 self.draw_illegal(); was_illegal = True
             else:
@@ -1529,8 +2430,8 @@ class Driver:
         return self.stats
 
 
-def run_sequence(device, model, rng, n_ops, *, fam, dtype, bound, gap=4e-3, lp_tol=2e-5, aux=None, tag=""):
+def run_sequence(device, model, rng, n_ops, *, fam, dtype, bound, gap=4e-3, lp_tol=2e-5, aux=None, tag="", extended=False):
     """n_ops random operations on `device`, each predicted by `model` and checked; aux = (device, model) of the second context snapshots travel through"""
     main = Ctx(device, model, Mirror(fam, dtype, model.max_batch), "main")
     second = Ctx(aux[0], aux[1], Mirror(fam, dtype, aux[1].max_batch), "aux") if aux else None
-    return Driver(main, second, rng, bound, gap, lp_tol, tag).run(n_ops)
+    return Driver(main, second, rng, bound, gap, lp_tol, tag, extended).run(n_ops)

@@ -75,6 +75,11 @@ def storage_ulp(x, dtype):
     return 2.0 ** (e - 7)
 
 
+def rotated_k_bound(ref, dtype):
+    """check 1's bound on a rotated K entry: one unit in the last place of the storage dtype at the entry's magnitude plus 2^-20 of its pair's norm"""
+    return storage_ulp(ref, dtype) + 2.0 ** -20 * splice_ref.pair_norm(ref)
+
+
 def force(m, toks):
     V = m.desc.vocab
     onehot = np.full((len(toks), V), -1.0, np.float32); onehot[np.arange(len(toks)), toks] = 1.0
@@ -131,7 +136,7 @@ def test_the_move_layer0_and_paged_equals_unpaged(name, dtype):
                 if table_ref:
                     ref, _ = splice_ref.splice(k0, v0, ranges, ang)
                     err = np.abs(k1 - ref)
-                    bound = storage_ulp(ref, dtype) + 2.0 ** -20 * splice_ref.pair_norm(ref)
+                    bound = rotated_k_bound(ref, dtype)
                     print(what, "max err / bound", float((err / bound).max()))
                     assert (err <= bound).all(), (what, float((err / bound).max()))
             # layer 0 against a fresh prefill of the spliced tokens, in row 1
