@@ -1022,7 +1022,8 @@ TGX_API int tgx_set_logits(tgx_ctx* ctx, const float* logits, int batch);
  *                  The stream holds 4.25 bits per weight wherever K is a multiple of 512 times the launch's K split (the 1B / 3B / 7B / 70B shapes), else
  *                  whole lanes of padding on top.  "weights.fp8" may be on as well when the two class masks are disjoint (an FP4 MLP under an
  *                  FP8 head: "weights.fp4_classes" 3, "weights.fp8_classes" 4); a class selected by both makes tgx_finalize return TGX_ERR_INVALID.  A class
- *                  quantized by either gets no exponent-packed copy; "weights.fp8_rows" reaches only matrices with an 8-bit stream.
+ *                  quantized by either gets no exponent-packed copy; "weights.fp8_rows" reaches only matrices with an 8-bit stream, "weights.fp4_rows" (below) only
+ *                  matrices with a 4-bit stream: with both on, each class takes its own code stream.
  *                  MEMORY: the bf16 masters stay (every multi-row path reads them), so the option COSTS about 0.53 bytes per weight of the selected classes.
  *                  MEASURED (profiles/weights_fp4.txt): the step beats the "weights.fp8" step by more than the rounds' spread on both models — Llama-3.2-1B
  *                  0.5147 -> 0.4619 ms per step (0.6144 at the defaults), Mistral-7B geometry 2.2617 -> 1.8762 ms (2.7944) — and no class lost: gate_up, down and
@@ -1049,6 +1050,14 @@ TGX_API int tgx_set_option(tgx_ctx* ctx, const char* key, int value);
  *                  (-1.0 %, -3.8 % per step), LOSES at 4, 8 and 64 rows (+2.7 %, +1.7 %, +4.8 %) — set it for batches of 16..32 rows on this shape.
  *   "weights.fp8_row_products"   (read-only) product launches issued on the code stream (a launch recorded into a graph counts once, at capture) ...
  *   "weights.fp8_row_fallbacks"  ... and products of a quantized matrix inside the row limit that were served from the master
+ *   "weights.fp4_rows"  (default 0 = off; 0 or 3..64, anything else TGX_ERR_INVALID; any time; drops the step graphs; no effect without "weights.fp4") the same
+ *                  for matrices with a 4-bit stream (kernels/skinny_fp4.h): their gate_up / down / lm_head products of up to that many rows read the E2M1 codes
+ *                  and E8M0 block scales as they lie, decoded by v_cvt_scalef32_pk_bf16_fp4 straight into the matrix cores' bf16 fragments.  Same bits as the
+ *                  option at 0 with "skinny.ksplit" 0.  Covered: K a multiple of 512, split K ranges in multiples of 64, stored two-term bf16 activations, a
+ *                  single-range stream (a down matrix beyond 16384 columns falls back); everything else is served from the master and counted.
+ *                  Measured on Llama-3.2-1B at context 2048 (profiles/weights_fp4_rows.txt), against the option at 0: pays at 32 rows (-1.4 % per step), within
+ *                  the spread at 16 (-0.1 %), LOSES at 4, 8 and 64 rows (+4.0 %, +2.9 %, +1.9 %); slower than "weights.fp8_rows" on an FP8 context at 4..32 rows.
+ *   "weights.fp4_row_products" / "weights.fp4_row_fallbacks"  (read-only) counted as the FP8 pair above
  *   "weights.fp8_matrices"   matrices that "weights.fp8" gave an 8-bit stream (after tgx_finalize) ...
  *   "weights.fp8_fallbacks"  ... and matrices it quantized that the plain kernel serves on the dequantized master,
  *   "weights.fp4_matrices" / "weights.fp4_fallbacks"  the same two figures of "weights.fp4", and

@@ -22,11 +22,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvi
          ] + (["-mllvm", "-amdgpu-mfma-vgpr-form"] if os.environ.get("TGX_VGPR_FORM", "1") == "1" else [])
 
 
-TUS = ["abi", "decode", "attn", "sampler", "prefill", "prefill_f32", "skinny", "skinny_fp8", "decode_fp4"]     # csrc/<name>.hip, compiled in parallel (csrc/ctx.h lists what each holds)
+TUS = ["abi", "decode", "attn", "sampler", "prefill", "prefill_f32", "skinny", "skinny_fp8", "decode_fp4", "skinny_fp4"]   # csrc/<name>.hip, compiled in parallel (csrc/ctx.h lists what each holds)
 # per-unit flags.  skinny_fp8: no packed fp32 arithmetic — the decode's eight multiplies per chunk stay scalar v_mul_f32; decode_fp4: likewise, its FMA
-# chains are gemv_kernel's scalar v_fma_f32
+# chains are gemv_kernel's scalar v_fma_f32; skinny_fp4: built like skinny_fp8 (its decode is converts only)
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-TU_FLAGS = {"skinny_fp8": NO_PK_F32, "decode_fp4": NO_PK_F32}
+TU_FLAGS = {"skinny_fp8": NO_PK_F32, "decode_fp4": NO_PK_F32, "skinny_fp4": NO_PK_F32}
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 

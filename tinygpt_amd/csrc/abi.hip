@@ -3020,6 +3020,9 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "weights.fp8_rows")) { *out_value = c->fp8_rows; return TGX_OK; }
   if (!strcmp(key, "weights.fp8_row_products")) { *out_value = c->fp8_row_products; return TGX_OK; }    // read-only: skinny product launches issued on the code stream (a graph's count once, at capture) ...
   if (!strcmp(key, "weights.fp8_row_fallbacks")) { *out_value = c->fp8_row_fallbacks; return TGX_OK; }  // ... products of a quantized matrix inside the row limit but served from the master
+  if (!strcmp(key, "weights.fp4_rows")) { *out_value = c->fp4_rows; return TGX_OK; }
+  if (!strcmp(key, "weights.fp4_row_products")) { *out_value = c->fp4_row_products; return TGX_OK; }    // read-only, counted as the FP8 pair above: launches on the 4-bit stream ...
+  if (!strcmp(key, "weights.fp4_row_fallbacks")) { *out_value = c->fp4_row_fallbacks; return TGX_OK; }  // ... and products inside the row limit served from the master
   if (!strcmp(key, "weights.fp4")) { *out_value = c->weights_fp4; return TGX_OK; }
   if (!strcmp(key, "weights.fp4_classes")) { *out_value = c->fp4_classes; return TGX_OK; }
   if (!strcmp(key, "weights.fp4_matrices")) { *out_value = c->fp4_matrices; return TGX_OK; }            // read-only, after tgx_finalize: matrices with a 4-bit stream ...
@@ -3099,6 +3102,10 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "weights.fp8_rows")) {      // any time; without weights.fp8 it has no effect (the step graphs were dropped above)
     if (value != 0 && (value < 3 || value > 64)) return set_err(c, TGX_ERR_INVALID, "weights.fp8_rows is 0 (off) or a row count 3..64");
     c->fp8_rows = value; return TGX_OK;
+  }
+  if (!strcmp(key, "weights.fp4_rows")) {      // any time; without weights.fp4 it has no effect (the step graphs were dropped above)
+    if (value != 0 && (value < 3 || value > 64)) return set_err(c, TGX_ERR_INVALID, "weights.fp4_rows is 0 (off) or a row count 3..64");
+    c->fp4_rows = value; return TGX_OK;
   }
   if (!strcmp(key, "weights.fp4") || !strcmp(key, "weights.fp4_classes")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the weights are quantized there)", key);

@@ -213,6 +213,8 @@ struct tgx_ctx {
   // (kernels/skinny_fp8.h).  fp8_row_products / fp8_row_fallbacks: product launches issued on the code stream / inside the limit but served from the master
   // (a launch recorded into a graph counts once, at capture)
   int fp8_rows = 0, fp8_row_products = 0, fp8_row_fallbacks = 0;
+  // option weights.fp4_rows: the same for matrices with a 4-bit stream (option weights.fp4; kernels/skinny_fp4.h), counted the same way
+  int fp4_rows = 0, fp4_row_products = 0, fp4_row_fallbacks = 0;
   float *rope_cos = nullptr, *rope_sin = nullptr;
   std::vector<RowState> rows;   // views into the per-row slabs below (constant row stride: batched GEMV walks them)
   float *slab_x = nullptr, *slab_q = nullptr, *slab_kraw = nullptr, *slab_attn = nullptr, *slab_h = nullptr, *slab_logits = nullptr;
@@ -620,3 +622,7 @@ namespace tgx { struct GemmArgs; }
 bool skinny_fp8_covers(const tgx_ctx* c, const Fp8Mat& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)
 void launch_skinny_fp8(tgx_ctx* c, const tgx::GemmArgs& g, const Fp8Mat& q, int epi, int mb, int nsplit);
 int skinny_fp8_set_attrs(tgx_ctx* c);
+// ---- skinny_fp4.hip (kernels/skinny_fp4.h)
+bool skinny_fp4_covers(const tgx_ctx* c, const Fp4Mat& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)
+void launch_skinny_fp4(tgx_ctx* c, const tgx::GemmArgs& g, const Fp4Mat& q, int epi, int mb, int nsplit);
+int skinny_fp4_set_attrs(tgx_ctx* c);

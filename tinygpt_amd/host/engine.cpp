@@ -59,6 +59,7 @@ bool GPTEngine::prepare() {
   loadOpts.weightsFp8Rows = config_.weightsFp8Rows;
   loadOpts.weightsFp4 = config_.weightsFp4;
   loadOpts.weightsFp4Classes = config_.weightsFp4Classes;
+  loadOpts.weightsFp4Rows = config_.weightsFp4Rows;
   if (!config_.synthetic.empty()) {
     if (!known_config(config_.synthetic, config_.dtype, config_.maxBatch, model_.config)) return fail("unknown synthetic config: " + config_.synthetic);
     if (!load_synthetic(be_, model_.config, config_.deviceOrdinal, 1234, 0.02, &model_.ctx, err_, loadOpts)) return fail("Prepare failed: " + err_);

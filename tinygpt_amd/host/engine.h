@@ -131,6 +131,9 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // its message, as it does for every other refusal (dtype, GPT-2, a non-finite weight, a backend without the key).
   bool weightsFp4 = false;
   int weightsFp4Classes = -1;
+  // ... and the batched steps, passes and short prompts of up to this many rows stream the 4-bit codes as well (option "weights.fp4_rows": 0 = off, the default,
+  // or 3..64; read with weightsFp4 only).  Same bits as without it; a value the backend refuses fails prepare() with a message that names the option.
+  int weightsFp4Rows = 0;
 #ifdef TGXH_TEST_HOOKS
   // Only in the test build (tests/_build/libtgx_host_test.so, tgx_cli_test: -DTGXH_TEST_HOOKS): bind another library that exports the tgx ABI
   // (the CPU oracle) to check host logic without a GPU.  The shipped library and CLI do not contain these fields or the code that reads them:
@@ -262,6 +265,12 @@ class GPTEngine {
   bool setWeightsFp8Rows(int rows) {
     if (model_.ctx && config_.weightsFp8 && (!be_.set_option || be_.set_option(model_.ctx, "weights.fp8_rows", rows) != TGX_OK)) return false;
     config_.weightsFp8Rows = rows;
+    return true;
+  }
+  // GPTConfig::weightsFp4Rows, as setWeightsFp8Rows
+  bool setWeightsFp4Rows(int rows) {
+    if (model_.ctx && config_.weightsFp4 && (!be_.set_option || be_.set_option(model_.ctx, "weights.fp4_rows", rows) != TGX_OK)) return false;
+    config_.weightsFp4Rows = rows;
     return true;
   }
   // GPTConfig::weightsFp4 / weightsFp4Classes: read by prepare() (false: the model is loaded already — the weights were quantized or not at tgx_finalize)

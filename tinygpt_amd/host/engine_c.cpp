@@ -61,6 +61,8 @@ TGXE_API tgxe_engine* tgxe_create3(const char* model_dir, const char* synthetic,
 TGXE_API int tgxe_set_weights_fp8_rows(tgxe_engine* h, int rows) { return h && h->e->setWeightsFp8Rows(rows) ? 0 : 1; }
 // GPTConfig::weightsFp4 / weightsFp4Classes (options "weights.fp4", "weights.fp4_classes"; classes < 0: the library's default), BEFORE tgxe_prepare; 0 = accepted
 TGXE_API int tgxe_set_weights_fp4(tgxe_engine* h, int on, int classes) { return h && h->e->setWeightsFp4(on != 0, classes) ? 0 : 1; }
+// GPTConfig::weightsFp4Rows (option "weights.fp4_rows"), before or after tgxe_prepare; 0 = accepted
+TGXE_API int tgxe_set_weights_fp4_rows(tgxe_engine* h, int rows) { return h && h->e->setWeightsFp4Rows(rows) ? 0 : 1; }
 TGXE_API void tgxe_destroy(tgxe_engine* h) { if (h) { delete h->e; delete h; } }
 TGXE_API int tgxe_prepare(tgxe_engine* h) { return h && h->e->prepare() ? 0 : 1; }
 TGXE_API const char* tgxe_last_error(tgxe_engine* h) { return h ? h->e->lastError().c_str() : "null engine"; }

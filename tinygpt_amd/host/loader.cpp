@@ -225,6 +225,11 @@ bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts
       err = std::string("weightsFp4: the device shim refused option weights.fp4") + (why && *why ? std::string(": ") + why : std::string());
       return false;
     }
+    if (opts.weightsFp4Rows && be.set_option(ctx, "weights.fp4_rows", opts.weightsFp4Rows) != TGX_OK) {
+      const char* why = be.last_error(ctx);
+      err = std::string("weightsFp4Rows: the device shim refused option weights.fp4_rows") + (why && *why ? std::string(": ") + why : std::string());
+      return false;
+    }
   }
   if (!opts.weightsFp8) return true;
   if (!be.set_option) { err = "weightsFp8: the device shim exports no tgx_set_option, so option weights.fp8 cannot be set"; return false; }

@@ -54,6 +54,7 @@ struct LoadOptions {
   int weightsFp8Rows = 0;
   bool weightsFp4 = false;        // option "weights.fp4" = 1 ...
   int weightsFp4Classes = -1;     // ... and "weights.fp4_classes" (-1 = not set: the library's default, all three classes)
+  int weightsFp4Rows = 0;         // option "weights.fp4_rows" (0 = not set; only read with weightsFp4) — a refused value fails the load
 };
 bool apply_load_options(const Backend& be, tgx_ctx* ctx, const LoadOptions& opts, std::string& err);
 

@@ -31,6 +31,7 @@ static void usage(const char* prog) {
           "                            the model is loaded (bf16 only); the run fails if the device library cannot do it (default: off)\n"
           "  --weights-fp4-classes <m> with --weights-fp4: which classes, a mask of gate_up (1), down (2), lm_head (4) (default: 7)\n"
           "  --weights-fp8-rows <n>    with --weights-fp8: batched steps and passes of up to n rows (3..64) stream the codes too; same output (default: 0 = off)\n"
+          "  --weights-fp4-rows <n>    with --weights-fp4: the same for the 4-bit codes (3..64; default: 0 = off)\n"
           "  --max-tokens <n>          max new tokens (default: 32)\n"
           "  --temperature <f>         sampling temperature (default: 0.8)\n"
           "  --top-p <f>               top-p sampling (default: 0.9)\n"
@@ -142,6 +143,7 @@ int main(int argc, char** argv) {
     else if (a == "--weights-fp8-rows") cfg.weightsFp8Rows = atoi(next());
     else if (a == "--weights-fp4") cfg.weightsFp4 = true;
     else if (a == "--weights-fp4-classes") cfg.weightsFp4Classes = atoi(next());
+    else if (a == "--weights-fp4-rows") cfg.weightsFp4Rows = atoi(next());
     else if (a == "--max-tokens") cfg.maxNewTokens = atoi(next());
     else if (a == "--temperature") cfg.samplerConfig.temperature = strtof(next(), nullptr);
     else if (a == "--top-p") cfg.samplerConfig.topP = strtof(next(), nullptr);

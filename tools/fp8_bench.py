@@ -18,10 +18,13 @@ Per model (the bench.py point: a 2048-token prefill, 16 warm-up steps, 256 timed
 The figures are reported, not asserted: synthetic weights say little about a trained model's quality.
 
     python tools/fp8_bench.py --rows [--parent-lib PATH]       # option weights.fp8_rows: writes profiles/weights_fp8_rows.txt
+    python tools/fp8_bench.py --rows --option weights.fp4      # option weights.fp4_rows: writes profiles/weights_fp4_rows.txt
 
 --rows: ms per tgx_decode_rows step at 4, 8, 16, 32 and 64 rows and ms per 16-position tgx_verify_row pass, Llama-3.2-1B bf16, every row at context --prompt;
 base = weights.fp8 = 1 with weights.fp8_rows = 0 (the parent's launches; with --parent-lib the parent commit's library with weights.fp8 = 1 is timed beside it),
-against weights.fp8_rows = 64 on the SAME context, the two settings alternating, median of the rounds' medians with the spread.  Same bits either way."""
+against weights.fp8_rows = 64 on the SAME context, the two settings alternating, median of the rounds' medians with the spread.  Same bits either way.
+With --option weights.fp4 the context under test is weights.fp4 = 1 with weights.fp4_rows 0 / 64, and a third context, weights.fp8 = 1 with weights.fp8_rows 64,
+takes its turn in every round."""
 import argparse
 import os
 import statistics
@@ -49,7 +52,7 @@ ap.add_argument("--reps", type=int, default=3, help="timed regions per context a
 ap.add_argument("--out", default=None)
 ap.add_argument("--rows", action="store_true", help="measure option weights.fp8_rows instead (profiles/weights_fp8_rows.txt)")
 args = ap.parse_args()
-args.out = args.out or os.path.join(ROOT, "profiles", "weights_fp8_rows.txt" if args.rows else args.option.replace(".", "_") + ".txt")
+args.out = args.out or os.path.join(ROOT, "profiles", args.option.replace(".", "_") + "_rows.txt" if args.rows else args.option.replace(".", "_") + ".txt")
 TAG = args.option.split(".")[-1]                                                            # fp8 / fp4: the label of the context under test
 BASE_OPTS = [(kv.split("=")[0], int(kv.split("=")[1])) for kv in args.base_opts.split(",") if kv]
 
@@ -111,15 +114,18 @@ parent = Backend(args.parent_lib, "tgx_", required=list(ABI)) if args.parent_lib
 
 
 def rows_bench():
-    """option weights.fp8_rows on the batched step and a verify pass"""
+    """option weights.fp8_rows / weights.fp4_rows (args.option + "_rows") on the batched step and a verify pass"""
+    rows_key, other = args.option + "_rows", args.option == "weights.fp4"
     steps, ROWS = min(args.steps, 64), (4, 8, 16, 32, 64)
     d = known_desc("llama-3.2-1b", "bf16")
     d.max_ctx, d.max_batch = args.prompt + 256, max(ROWS)
     ctxs = {"this": Model(d, product_backend())}
     if parent:
         ctxs["parent"] = Model(d, parent)
-    for m in ctxs.values():
-        m.set_option("weights.fp8", 1)
+    if other:
+        ctxs["fp8"] = Model(d, product_backend())
+    for key, m in ctxs.items():
+        m.set_option("weights.fp8" if key == "fp8" else args.option, 1)
         for tname, bits in synth.synth_checkpoint(d, 1234, 0.02):
             m.upload(tname, bits)
         m.finalize()
@@ -127,7 +133,7 @@ def rows_bench():
 
     def step_ms(m, rows, fp8_rows):
         if fp8_rows is not None:
-            m.set_option("weights.fp8_rows", fp8_rows)
+            m.set_option(rows_key, fp8_rows)
         m.reset_cache()
         for r in range(rows):
             m.forward_row(r, prompt)
@@ -142,7 +148,7 @@ def rows_bench():
     def verify_ms(m, rows, fp8_rows):
         """one 16-position pass (15 draft tokens; all rejected or not, the pass is the same work), timed over `steps` passes on a row kept at the prompt"""
         if fp8_rows is not None:
-            m.set_option("weights.fp8_rows", fp8_rows)
+            m.set_option(rows_key, fp8_rows)
         ts = []
         for _ in range(8):
             m.reset_cache()
@@ -155,10 +161,12 @@ def rows_bench():
             ts.append((time.perf_counter() - t0) * 1e3)
         return statistics.median(ts[1:])
 
-    say("# option weights.fp8_rows: batched steps and verify passes stream the FP8 codes on the matrix cores (kernels/skinny_fp8.h) — tools/fp8_bench.py --rows")
+    say(f"# option {rows_key}: batched steps and verify passes stream the {TAG.upper()} codes on the matrix cores (kernels/skinny_{TAG}.h) — tools/fp8_bench.py --rows" + (" --option weights.fp4" if other else ""))
     say(f"# Llama-3.2-1B bf16, every row at context {args.prompt}; {args.warmup} warm-up + {steps} timed tgx_decode_rows steps; {args.rounds} rounds, settings alternating; ms (spread of the rounds)")
-    say("# base = weights.fp8 1, weights.fp8_rows 0 (the parent's launches); rows64 = weights.fp8_rows 64; parent = the parent commit's library with weights.fp8 1")
-    settings = [("base", "this", 0), ("rows64", "this", 64)] + ([("parent", "parent", None)] if parent else [])
+    say(f"# base = {args.option} 1, {rows_key} 0 (the parent's launches); rows64 = {rows_key} 64; parent = the parent commit's library with {args.option} 1" + ("; fp8rows64 = weights.fp8 1, weights.fp8_rows 64" if other else ""))
+    settings = [("base", "this", 0), ("rows64", "this", 64)] + ([("parent", "parent", None)] if parent else []) + ([("fp8rows64", "fp8", None)] if other else [])
+    if other:
+        ctxs["fp8"].set_option("weights.fp8_rows", 64)
     for what, fn, points in (("tgx_decode_rows step", step_ms, ROWS), ("16-position tgx_verify_row pass (host call included)", verify_ms, (1,))):
         for rows in points:
             for label, key, v in settings:
@@ -173,8 +181,8 @@ def rows_bench():
             say(f"{what}, {rows} rows: " + "   ".join(f"{k} {med[k]:.4f} ({max(got[k]) - min(got[k]):.4f})" for k in got) +
                 f"   rows64 - base {med['rows64'] - med['base']:+.4f} ms = {100 * (med['rows64'] - med['base']) / med['base']:+.1f} %: {verdict}")
     m = ctxs["this"]
-    say(f"code-stream products issued {m.get_option('weights.fp8_row_products')}, fallbacks {m.get_option('weights.fp8_row_fallbacks')}")
-    say("per-launch us of gate_up / down / lm_head and their effective TB/s at 1 B/weight: NOT MEASURED (tgx_profile_decode times the batch-1 step only)")
+    say(f"code-stream products issued {m.get_option(rows_key[:-1] + '_products')}, fallbacks {m.get_option(rows_key[:-1] + '_fallbacks')}")
+    say("per-launch us of gate_up / down / lm_head: not from this tool (tgx_profile_decode times the batch-1 step only); a kernel trace of its own")
 
 
 if args.rows:
