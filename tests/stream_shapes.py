@@ -4,8 +4,8 @@ and lm_head meet every layout the kernels index, and the host rules that decide 
 tests/test_stream_shapes.py holds the table to the reach list below; tests/test_hip_stream_shapes.py runs every case bit for bit against the master path and
 holds the counters to predict_step().
 
-The rules are transcriptions: gemv_nx / gemv_auto_ks / launch_gemv's R = 2 rules (csrc/decode.hip), the quantizers' layout choice (quantize_weights,
-quantize_weights_fp4), launch_skinny's split rule, skinny_fp8_covers / skinny_fp4_covers, and the branches of launch_decode_step_mfma that hand a product to
+The rules are transcriptions: stream_nx (csrc/ctx.h) / gemv_auto_ks / launch_gemv's R = 2 rules (csrc/decode.hip), the quantizer's layout choice per form
+(quantize_weights), launch_skinny's split rule, skinny_fp8_covers / skinny_fp4_covers, and the branches of launch_decode_step_mfma that hand a product to
 launch_skinny (csrc/skinny.hip).  A change to one of those shows here as a counter mismatch on the GPU, with both geometries printed.
 
 Shapes: only the dimension under test is large.  K = hidden cases take intermediate 512 and a vocabulary of a few hundred; K = intermediate cases take hidden
@@ -122,7 +122,7 @@ def gemv_launch_ks(K, want, R, cls):
 
 @dataclass(frozen=True)
 class Layout:
-    """the stream quantize_weights / quantize_weights_fp4 lays out for one matrix"""
+    """the stream quantize_weights lays out for one matrix"""
     form: str
     N: int
     K: int

@@ -154,6 +154,8 @@ def test_tiny_families_are_bit_identical(fam, inter, hip):
 
 
 BOTH = FP4 + (("weights.fp8", 1), ("weights.fp8_classes", 6), ("weights.fp4_classes", 3))      # down selected twice
+# gate_up by FP8, down by FP4: the scan of both forms' matrices runs before either overwrites a master, so the FP4 refusal below leaves the FP8 class untouched too
+MIXED = FP4 + (("weights.fp8", 1), ("weights.fp8_classes", 1), ("weights.fp4_classes", 2))
 
 
 @pytest.mark.parametrize("fam,dtype,opts,bad,status,names", [
@@ -161,7 +163,8 @@ BOTH = FP4 + (("weights.fp8", 1), ("weights.fp8_classes", 6), ("weights.fp4_clas
     ("llama_tiny", "fp32", FP4, None, ERR_UNSUPPORTED, ["weights.fp4"]), ("llama_tiny", "bf16", BOTH, None, ERR_INVALID, ["weights.fp8", "weights.fp4"]),
     ("llama_tiny", "bf16", FP4, ("model.layers.1.mlp.up_proj.weight", 7, 0x7F80), ERR_UNSUPPORTED, ["model.layers.1.mlp.up_proj.weight"]),          # inf
     ("llama_tiny", "bf16", FP4, ("model.layers.0.mlp.down_proj.weight", 0, 0xFFC0), ERR_UNSUPPORTED, ["model.layers.0.mlp.down_proj.weight"]),      # NaN
-    ("llama_tiny", "bf16", FP4, ("model.embed_tokens.weight", 255, 0x7180), ERR_UNSUPPORTED, ["model.embed_tokens.weight"])])                       # 2^100
+    ("llama_tiny", "bf16", FP4, ("model.embed_tokens.weight", 255, 0x7180), ERR_UNSUPPORTED, ["model.embed_tokens.weight"]),                        # 2^100
+    ("llama_tiny", "bf16", MIXED, ("model.layers.1.mlp.down_proj.weight", 3, 0x7F80), ERR_UNSUPPORTED, ["weights.fp4:", "model.layers.1.mlp.down_proj.weight"])])      # inf
 def test_refusals(fam, dtype, opts, bad, status, names, hip):
     def plant(name, bits):
         if bad and name == bad[0]:

@@ -32,7 +32,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "verify_tree_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h")]
+            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "verify_tree_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h"), os.path.join(CSRC, "stream_launch.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 

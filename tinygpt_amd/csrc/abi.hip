@@ -913,12 +913,12 @@ int tgx_finalize(tgx_ctx* c) {
   }
   if (c->finalized) return TGX_OK;
   // a lossy option that silently does nothing would mislead: the 8-bit form exists for bf16 storage and the RMSNorm families only
-  if (c->weights_fp8 && (c->dt != tgx::DT_BF16 || c->gpt2))
-    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp8 needs bf16 storage and a gated-MLP family (this context: %s%s)", c->dt == tgx::DT_BF16 ? "bf16" : (c->dt == tgx::DT_F16 ? "fp16" : "fp32"), c->gpt2 ? ", GPT-2" : "");
-  if (c->weights_fp4 && (c->dt != tgx::DT_BF16 || c->gpt2))
-    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp4 needs bf16 storage and a gated-MLP family (this context: %s%s)", c->dt == tgx::DT_BF16 ? "bf16" : (c->dt == tgx::DT_F16 ? "fp16" : "fp32"), c->gpt2 ? ", GPT-2" : "");
-  if (c->weights_fp8 && c->weights_fp4 && (c->fp8_classes & c->fp4_classes))      // a matrix has one quantized form
-    return set_err(c, TGX_ERR_INVALID, "weights.fp8 and weights.fp4 select the same class (weights.fp8_classes %d, weights.fp4_classes %d): a class is quantized by one of them", c->fp8_classes, c->fp4_classes);
+  for (int kind : {WS_FP8, WS_FP4})
+    if (c->quant_of(kind).on && (c->dt != tgx::DT_BF16 || c->gpt2))
+      return set_err(c, TGX_ERR_UNSUPPORTED, "%s needs bf16 storage and a gated-MLP family (this context: %s%s)", kind == WS_FP8 ? "weights.fp8" : "weights.fp4", c->dt == tgx::DT_BF16 ? "bf16" : (c->dt == tgx::DT_F16 ? "fp16" : "fp32"), c->gpt2 ? ", GPT-2" : "");
+  const QuantForm &q8 = c->quant_of(WS_FP8), &q4 = c->quant_of(WS_FP4);
+  if (q8.on && q4.on && (q8.classes & q4.classes))      // a matrix has one quantized form
+    return set_err(c, TGX_ERR_INVALID, "weights.fp8 and weights.fp4 select the same class (weights.fp8_classes %d, weights.fp4_classes %d): a class is quantized by one of them", q8.classes, q4.classes);
 
   std::vector<float> cs, sn;
   if (c->gpt2) {      // no rotary embedding: the qkv epilogue's rotation becomes the identity
@@ -933,8 +933,8 @@ int tgx_finalize(tgx_ctx* c) {
 
   // one grid for every lm_head launch (it sizes the argmax partials): the packed launch's workgroups per CU where the options ask for a packed lm_head
   // (pack_weights runs below; a lm_head that then falls back, and the batched steps, run their plain kernels on this grid too)
-  // (an lm_head quantized by weights.fp8 starts at the same value: gemv_fp8.h's launch takes the class's packed_bpc)
-  const bool lm_packed = ((c->weights_packed && (c->packed_classes & 4)) || (c->weights_fp8 && (c->fp8_classes & 4)) || (c->weights_fp4 && (c->fp4_classes & 4))) && c->dt == tgx::DT_BF16 && !c->gpt2;
+  // (an lm_head quantized by weights.fp8 / weights.fp4 starts at the same value: every stream form's launch takes the class's packed_bpc)
+  const bool lm_packed = stream_form(c, 4) != WS_NONE;
   c->lm_grid = gemv_grid(c, (V + 1) / 2, 1, lm_packed ? c->tune[TGX_KERNEL_LMHEAD].packed_bpc : c->tune[TGX_KERNEL_LMHEAD].bpc);
   int ns = c->num_cus / d.kv_heads;
   c->attn_nsplit = ns < 1 ? 1 : (ns > 32 ? 32 : ns);
@@ -1016,7 +1016,7 @@ int tgx_finalize(tgx_ctx* c) {
   c->row_req_host.assign(B, row_req_default());
   if ((rc = dev_alloc(c, &c->row_req, B))) return rc;
   HIP_OK(c, hipMemcpy(c->row_req, c->row_req_host.data(), B * sizeof(tgx::RowReq), hipMemcpyHostToDevice));
-  if ((rc = quantize_weights(c)) || (rc = quantize_weights_fp4(c)) || (rc = pack_weights(c))) return rc;
+  if ((rc = quantize_weights(c)) || (rc = pack_weights(c))) return rc;
   c->past = 0;
   c->row_host.assign(B, RowHost{});
   c->finalized = true;
@@ -2989,6 +2989,12 @@ int tgx_set_logits(tgx_ctx* c, const float* logits, int batch) {
   return TGX_OK;
 }
 
+// the quantized form whose option family `key` belongs to ("weights.fp8..." / "weights.fp4...": the suffix starts at key[11]), or nullptr
+static const QuantForm* quant_key(const tgx_ctx* c, const char* key) {
+  if (!strncmp(key, "weights.fp8", 11)) return &c->quant_of(WS_FP8);
+  return !strncmp(key, "weights.fp4", 11) ? &c->quant_of(WS_FP4) : nullptr;
+}
+
 int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!c || !key || !out_value) return TGX_ERR_INVALID;
   if (!strcmp(key, "attn.direct_limit")) { *out_value = (int)std::min<long long>(direct_limit(c, c->batch, true), INT_MAX); return TGX_OK; }
@@ -3013,20 +3019,16 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "weights.packed_matrices")) { *out_value = c->packed_matrices; return TGX_OK; }        // read-only, after tgx_finalize: matrices stored packed ...
   if (!strcmp(key, "weights.packed_fallbacks")) { *out_value = c->packed_fallbacks; return TGX_OK; }      // ... matrices that stayed plain because a row's escape record overflowed ...
   if (!strcmp(key, "weights.packed_max_row_esc")) { *out_value = c->packed_max_row_esc; return TGX_OK; }  // ... and the most escapes seen in one row
-  if (!strcmp(key, "weights.fp8")) { *out_value = c->weights_fp8; return TGX_OK; }
-  if (!strcmp(key, "weights.fp8_classes")) { *out_value = c->fp8_classes; return TGX_OK; }
-  if (!strcmp(key, "weights.fp8_matrices")) { *out_value = c->fp8_matrices; return TGX_OK; }            // read-only, after tgx_finalize: matrices with an 8-bit stream ...
-  if (!strcmp(key, "weights.fp8_fallbacks")) { *out_value = c->fp8_fallbacks; return TGX_OK; }          // ... matrices quantized but served by the plain kernel on the dequantized master
-  if (!strcmp(key, "weights.fp8_rows")) { *out_value = c->fp8_rows; return TGX_OK; }
-  if (!strcmp(key, "weights.fp8_row_products")) { *out_value = c->fp8_row_products; return TGX_OK; }    // read-only: skinny product launches issued on the code stream (a graph's count once, at capture) ...
-  if (!strcmp(key, "weights.fp8_row_fallbacks")) { *out_value = c->fp8_row_fallbacks; return TGX_OK; }  // ... products of a quantized matrix inside the row limit but served from the master
-  if (!strcmp(key, "weights.fp4_rows")) { *out_value = c->fp4_rows; return TGX_OK; }
-  if (!strcmp(key, "weights.fp4_row_products")) { *out_value = c->fp4_row_products; return TGX_OK; }    // read-only, counted as the FP8 pair above: launches on the 4-bit stream ...
-  if (!strcmp(key, "weights.fp4_row_fallbacks")) { *out_value = c->fp4_row_fallbacks; return TGX_OK; }  // ... and products inside the row limit served from the master
-  if (!strcmp(key, "weights.fp4")) { *out_value = c->weights_fp4; return TGX_OK; }
-  if (!strcmp(key, "weights.fp4_classes")) { *out_value = c->fp4_classes; return TGX_OK; }
-  if (!strcmp(key, "weights.fp4_matrices")) { *out_value = c->fp4_matrices; return TGX_OK; }            // read-only, after tgx_finalize: matrices with a 4-bit stream ...
-  if (!strcmp(key, "weights.fp4_fallbacks")) { *out_value = c->fp4_fallbacks; return TGX_OK; }          // ... matrices quantized but served by the plain kernel on the dequantized master
+  if (const QuantForm* qf = quant_key(c, key)) {      // weights.fp8* / weights.fp4*
+    const char* f = key + 11;
+    if (!*f) { *out_value = qf->on; return TGX_OK; }
+    if (!strcmp(f, "_classes")) { *out_value = qf->classes; return TGX_OK; }
+    if (!strcmp(f, "_matrices")) { *out_value = qf->matrices; return TGX_OK; }              // read-only, after tgx_finalize: matrices with a code stream ...
+    if (!strcmp(f, "_fallbacks")) { *out_value = qf->fallbacks; return TGX_OK; }            // ... matrices quantized but served by the plain kernel on the dequantized master
+    if (!strcmp(f, "_rows")) { *out_value = qf->rows; return TGX_OK; }
+    if (!strcmp(f, "_row_products")) { *out_value = qf->row_products; return TGX_OK; }      // read-only: skinny product launches issued on the code stream (a graph's count once, at capture) ...
+    if (!strcmp(f, "_row_fallbacks")) { *out_value = qf->row_fallbacks; return TGX_OK; }    // ... products of a quantized matrix inside the row limit but served from the master
+  }
   if (!strcmp(key, "kv.free_tokens")) { *out_value = c->kv_paged ? (int)c->kv.free_blocks() * tgx::KV_BLOCK : -1; return TGX_OK; }      // paged KV: tokens' worth of unassigned blocks
   if (!strcmp(key, "mem.live_allocs")) { *out_value = (int)c->mem.live(); return TGX_OK; }                     // read-only: device buffers the context holds now ...
   if (!strcmp(key, "mem.live_kib")) { *out_value = (int)((c->mem.live_bytes() + 1023) / 1024); return TGX_OK; }  // ... and their bytes, rounded up to KiB
@@ -3093,25 +3095,18 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
     else c->weights_packed = value != 0;
     return TGX_OK;
   }
-  if (!strcmp(key, "weights.fp8") || !strcmp(key, "weights.fp8_classes")) {
-    if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the weights are quantized there)", key);
-    if (key[11] == '_') { if (value < 0 || value > 7) return set_err(c, TGX_ERR_INVALID, "weights.fp8_classes is a mask of gate_up (1), down (2), lm_head (4)"); c->fp8_classes = value; }
-    else { if (value != 0 && value != 1) return set_err(c, TGX_ERR_INVALID, "weights.fp8 is 0 or 1"); c->weights_fp8 = value; }
-    return TGX_OK;
-  }
-  if (!strcmp(key, "weights.fp8_rows")) {      // any time; without weights.fp8 it has no effect (the step graphs were dropped above)
-    if (value != 0 && (value < 3 || value > 64)) return set_err(c, TGX_ERR_INVALID, "weights.fp8_rows is 0 (off) or a row count 3..64");
-    c->fp8_rows = value; return TGX_OK;
-  }
-  if (!strcmp(key, "weights.fp4_rows")) {      // any time; without weights.fp4 it has no effect (the step graphs were dropped above)
-    if (value != 0 && (value < 3 || value > 64)) return set_err(c, TGX_ERR_INVALID, "weights.fp4_rows is 0 (off) or a row count 3..64");
-    c->fp4_rows = value; return TGX_OK;
-  }
-  if (!strcmp(key, "weights.fp4") || !strcmp(key, "weights.fp4_classes")) {
-    if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the weights are quantized there)", key);
-    if (key[11] == '_') { if (value < 0 || value > 7) return set_err(c, TGX_ERR_INVALID, "weights.fp4_classes is a mask of gate_up (1), down (2), lm_head (4)"); c->fp4_classes = value; }
-    else { if (value != 0 && value != 1) return set_err(c, TGX_ERR_INVALID, "weights.fp4 is 0 or 1"); c->weights_fp4 = value; }
-    return TGX_OK;
+  if (QuantForm* qf = const_cast<QuantForm*>(quant_key(c, key))) {      // weights.fp8* / weights.fp4*
+    const char* f = key + 11;
+    if (!*f || !strcmp(f, "_classes")) {
+      if (c->finalized) return set_err(c, TGX_ERR_STATE, "%s is set before tgx_finalize (the weights are quantized there)", key);
+      if (*f) { if (value < 0 || value > 7) return set_err(c, TGX_ERR_INVALID, "%s is a mask of gate_up (1), down (2), lm_head (4)", key); qf->classes = value; }
+      else { if (value != 0 && value != 1) return set_err(c, TGX_ERR_INVALID, "%s is 0 or 1", key); qf->on = value; }
+      return TGX_OK;
+    }
+    if (!strcmp(f, "_rows")) {      // any time; without the form's own option it has no effect (the step graphs were dropped above)
+      if (value != 0 && (value < 3 || value > 64)) return set_err(c, TGX_ERR_INVALID, "%s is 0 (off) or a row count 3..64", key);
+      qf->rows = value; return TGX_OK;
+    }
   }
   if (!strcmp(key, "kv.budget_tokens")) {
     if (c->finalized) return set_err(c, TGX_ERR_STATE, "kv.budget_tokens is set before tgx_finalize (it sizes the caches)");
@@ -3158,19 +3153,16 @@ int64_t tgx_bytes_per_token(const tgx_ctx* c, int64_t T) {
     return b * (L * per_layer + 2 * H + H + V * H) + b * 2 * L * kv * T;
   }
   const int64_t per_layer = (q + 2 * kv) * H + (d.qkv_bias ? (q + 2 * kv) : 0) + H * q + 2 * I * H + H * I + 2 * H;
-  // exponent-packed matrices (option weights.packed) stream their planes and escape records instead of 2 bytes per weight
+  // a matrix that owns a stream streams that instead of 2 bytes per weight: packed planes and one 16-byte escape record per row and K-part; FP8 code planes
+  // and one 4-byte scale per row; FP4 planes (codes and block scales as laid out) for every K range
   int64_t saved = 0;
-  auto packed_saving = [&](const PackedMat& m, int64_t rows, int64_t cols) { if (m.P) saved += b * rows * cols - rows * (m.row_bytes + 16 * m.ks); };      // (one 16-byte record per row and K-part)
-  for (const LayerW& w : c->L) { packed_saving(w.pgu, 2 * I, H); packed_saving(w.pdown, H, I); }
-  packed_saving(c->plm, V, H);
-  // matrices quantized by option weights.fp8 stream their code planes and one 4-byte scale per row
-  auto fp8_saving = [&](const Fp8Mat& m, int64_t rows, int64_t cols) { if (m.Q) saved += b * rows * cols - rows * (m.row_bytes + 4); };
-  for (const LayerW& w : c->L) { fp8_saving(w.qgu, 2 * I, H); fp8_saving(w.qdown, H, I); }
-  fp8_saving(c->qlm, V, H);
-  // ... and matrices quantized by option weights.fp4 their planes: codes and block scales as laid out
-  auto fp4_saving = [&](const Fp4Mat& m, int64_t rows, int64_t cols) { if (m.Q) saved += b * rows * cols - rows * m.row_bytes * m.parts; };
-  for (const LayerW& w : c->L) { fp4_saving(w.fgu, 2 * I, H); fp4_saving(w.fdown, H, I); }
-  fp4_saving(c->flm, V, H);
+  auto saving = [&](const WeightStream& m, int64_t rows, int64_t cols) {
+    if (!m.planes) return;
+    const int64_t row = m.kind == WS_PACKED ? m.row_bytes + 16 * m.ks : (m.kind == WS_FP8 ? m.row_bytes + 4 : m.row_bytes * m.parts);
+    saved += b * rows * cols - rows * row;
+  };
+  for (const LayerW& w : c->L) { saving(w.sgu, 2 * I, H); saving(w.sdown, H, I); }
+  saving(c->slm, V, H);
   return b * (L * per_layer + H + V * H) + b * 2 * L * kv * T - saved;
 }
 

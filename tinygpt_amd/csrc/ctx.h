@@ -11,6 +11,10 @@
 //                    and tgx_embed_rows (kernels/embed_pool.h) behind a pass
 //   prefill_f32.hip  batched prefill, fp32 storage (kernels/gemm_f32.h)
 //   skinny.hip       batched decode step / short prompts on the skinny MFMA GEMMs (kernels/skinny*.h)
+//   decode_fp4.hip   the MXFP4 batch-1 GEMV instantiations and quantizer launches (kernels/gemv_fp4.h); decode.hip holds the packed and FP8 ones
+//   skinny_fp8.hip, skinny_fp4.hip   the skinny products on the FP8 / MXFP4 code streams (kernels/skinny_fp8.h, skinny_fp4.h)
+//   stream_launch.h  the launch templates those units share: the NX / fixed-point switch of a batch-1 stream kernel family, the skinny (epilogue, blocks) table
+// A gate_up / down / lm_head matrix has at most one stream form, recorded in its WeightStream below; every launcher selects on its `kind`.
 // One context = one GPU = one HIP stream; every call comes from one host thread.  There is NO CPU path in this library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,43 +41,44 @@ namespace tgx { struct SampScratch; struct LpRecord; struct LpRow; }
 constexpr int MAX_TICKET_EVENTS = 64;
 constexpr int HOST_RING = 256;
 
-// a bf16 matrix in the lossless 12-bit exponent-packed form (kernels/gemv_packed.h; option weights.packed): made once in tgx_finalize beside the bf16 original,
-// read by the batch-1 decode launches of its class.  P == nullptr: not packed (option off, class not adopted, other dtype / shape, or a row's escapes overflowed)
-struct PackedMat {
-  unsigned char* P = nullptr;     // planes, N * row_bytes
-  tgx::u32x4* rec = nullptr;      // [N][ks] escape records, one per (row, K-part)
+// the form in which the batch-1 and batched launches may stream a gate_up / down / lm_head matrix instead of reading its bf16 master.  A matrix has at most
+// one: its class is given the form at tgx_finalize (stream_form below), quantize_weights / pack_weights make the planes and set `kind`.
+//   WS_PACKED  the lossless 12-bit exponent-packed copy (kernels/gemv_packed.h; option weights.packed).  Only a matrix that owns planes has this kind: one
+//              outside the format, or with a row whose escapes overflowed its record, stays WS_NONE
+//   WS_FP8     E4M3 codes and one power-of-two scale per row (kernels/gemv_fp8.h; option weights.fp8); the master holds the dequantized values
+//   WS_FP4     E2M1 codes and E8M0 block scales (kernels/gemv_fp4.h; option weights.fp4); the master holds the dequantized values
+// A quantized matrix whose shape the layout does not cover keeps its kind with planes == nullptr: the plain kernels read the dequantized master
+enum { WS_NONE = 0, WS_PACKED = 1, WS_FP8 = 2, WS_FP4 = 3 };
+struct WeightStream {
+  int kind = WS_NONE;
+  unsigned char* planes = nullptr;   // N * row_bytes (FP4: `parts` K ranges one after the other, each N * row_bytes)
   long long row_bytes = 0;
-  unsigned int e0h4 = 0;          // E0h * 0x01010101: the window's base in every byte
-  int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
-  int max_row_esc = 0;            // most escapes in one row
-  long long n_esc = 0;            // escapes of the matrix
+  int ks = 0;                        // the K split the planes are laid out for: a launch with another split takes the plain kernel
+  float* scale = nullptr;            // FP8: [N] 2^e_r
+  int K = 0, parts = 1;              // FP4: the K range of one launch (the whole K unless the class's launch is split: down beyond 16384) and their number
+  tgx::u32x4* rec = nullptr;         // packed: [N][ks] escape records, one per (row, K-part)
+  unsigned int e0h4 = 0;             // packed: E0h * 0x01010101, the window's base in every byte
+  int max_row_esc = 0;               // packed: most escapes in one row
+  long long n_esc = 0;               // packed: escapes of the matrix
+  // the stream of K range `part` of a matrix whose launch is split (FP4; the other forms have no per-range planes: their launches test ldw)
+  WeightStream range(int part, int N) const { WeightStream v = *this; if (v.planes && kind == WS_FP4) v.planes += (size_t)part * N * (size_t)row_bytes; return v; }
 };
+// 16-byte slices per lane per row for a K range split over ks waves: the NX template parameter of the GEMV kernels, the chunk slots (runs of 512 k) per
+// K-part of the layout a stream was made for
+inline int stream_nx(int K, int ks) { return ((K / 8) + ks * 64 - 1) / (ks * 64); }
 
-// the 8-bit stream of a matrix quantized by option weights.fp8 (kernels/gemv_fp8.h): E4M3 codes in the batch-1 launch's layout and one power-of-two scale per
-// row, made in tgx_finalize; the bf16 master beside it holds the dequantized values.  Q == nullptr: no stream (option off, class not selected, or a shape the
-// layout does not cover — the plain kernel then reads the dequantized master)
-struct Fp8Mat {
-  unsigned char* Q = nullptr;     // code planes, N * row_bytes
-  float* scale = nullptr;         // [N] 2^e_r
-  long long row_bytes = 0;
-  int ks = 0;                     // the K split the planes are laid out for: a launch with another split takes the plain kernel
-};
-
-// the 4-bit stream of a matrix quantized by option weights.fp4 (kernels/gemv_fp4.h): planes of E2M1 codes and E8M0 block scales in the batch-1 launch's layout,
-// made in tgx_finalize; the bf16 master beside it holds the dequantized values.  Q == nullptr: no stream, as for Fp8Mat
-struct Fp4Mat {
-  unsigned char* Q = nullptr;     // codes and block scales: `parts` K ranges one after the other, each N * row_bytes
-  long long row_bytes = 0;
-  int ks = 0;                     // the K split a range is laid out for: a launch with another split takes the plain kernel
-  int K = 0, parts = 1;           // the K range of one launch (the whole K unless the class's launch is split: down beyond 16384) and their number
+// the options and counters of one quantized form (tgx_ctx::quant; keys weights.fp8* / weights.fp4*)
+struct QuantForm {
+  int on = 0, classes = 7;              // read at tgx_finalize: the form is on, for these classes (bit 0 gate_up, 1 down, 2 lm_head)
+  int matrices = 0, fallbacks = 0;      // matrices with a stream / quantized but served by the plain kernel
+  int rows = 0;                         // any time; 0 = off, else 3..64: skinny products of up to that many activation rows stream the codes
+  int row_products = 0, row_fallbacks = 0;   // product launches issued on the code stream / inside the limit but served from the master (a graph's count once, at capture)
 };
 
 struct LayerW {
   ebyte *in_norm = nullptr, *post_norm = nullptr;
   ebyte *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
-  PackedMat pgu, pdown;         // wgu / wdown exponent-packed
-  Fp8Mat qgu, qdown;            // wgu / wdown as 8-bit streams (option weights.fp8)
-  Fp4Mat fgu, fdown;            // wgu / wdown as 4-bit streams (option weights.fp4)
+  WeightStream sgu, sdown;      // the stream form of wgu / wdown, if any
   ebyte *q_norm = nullptr, *k_norm = nullptr;   // Qwen3 [head_dim]
   bool q_norm_ok = false, k_norm_ok = false;
   // one bit per checkpoint tensor that lands in a merged weight: q, k, v, gate, up (bits 0-4) and the q/k/v biases (bits 5-7) — a tensor
@@ -197,24 +202,15 @@ struct tgx_ctx {
   // measures the same as without it (0.6286 against 0.6288 ms, inside the run-to-run spread; profiles/packed_kpart_geometry.txt, profiles/packed_weights_hl.txt).
   // packed_matrices / packed_fallbacks: matrices packed / fallen back to plain
   int weights_packed = 1, packed_classes = 5, packed_matrices = 0, packed_fallbacks = 0, packed_max_row_esc = 0;
-  PackedMat plm;                // the lm_head matrix (embed when tied) exponent-packed
-  // option weights.fp8 (read at tgx_finalize; default 0, lossy): the matrices of the classes in weights.fp8_classes (bit 0 gate_up, 1 down, 2 lm_head) are
-  // quantized to E4M3 codes with a power-of-two scale per row (the rule: include/tgx.h); the bf16 masters are overwritten with the dequantized values, so every
-  // path computes the same model, and the batch-1 launches read the 8-bit streams.  A class quantized this way gets no exponent-packed copy.
-  // fp8_matrices / fp8_fallbacks: matrices with a stream / quantized but served by the plain kernel
-  int weights_fp8 = 0, fp8_classes = 7, fp8_matrices = 0, fp8_fallbacks = 0;
-  Fp8Mat qlm;                   // the lm_head matrix (embed when tied) as an 8-bit stream
-  // option weights.fp4 (read at tgx_finalize; default 0, lossy): the same for MXFP4 — E2M1 codes with an E8M0 scale per block of 32 k of a row (the rule:
-  // include/tgx.h).  A class may be selected by weights.fp8 or by weights.fp4, not by both (tgx_finalize: TGX_ERR_INVALID).
-  // fp4_matrices / fp4_fallbacks: matrices with a stream / quantized but served by the plain kernel
-  int weights_fp4 = 0, fp4_classes = 7, fp4_matrices = 0, fp4_fallbacks = 0;
-  Fp4Mat flm;                   // the lm_head matrix (embed when tied) as a 4-bit stream
-  // option weights.fp8_rows (any time; default 0 = off, else 3..64): skinny products of up to that many activation rows over a quantized matrix stream its codes
-  // (kernels/skinny_fp8.h).  fp8_row_products / fp8_row_fallbacks: product launches issued on the code stream / inside the limit but served from the master
-  // (a launch recorded into a graph counts once, at capture)
-  int fp8_rows = 0, fp8_row_products = 0, fp8_row_fallbacks = 0;
-  // option weights.fp4_rows: the same for matrices with a 4-bit stream (option weights.fp4; kernels/skinny_fp4.h), counted the same way
-  int fp4_rows = 0, fp4_row_products = 0, fp4_row_fallbacks = 0;
+  WeightStream slm;             // the stream form of the lm_head matrix (embed when tied), if any
+  // options weights.fp8 / weights.fp4 (read at tgx_finalize; default 0, lossy): the matrices of the classes in weights.fp8_classes are quantized to E4M3 codes
+  // with a power-of-two scale per row, those in weights.fp4_classes to MXFP4 — E2M1 codes with an E8M0 scale per block of 32 k of a row (the rules:
+  // include/tgx.h); the bf16 masters are overwritten with the dequantized values, so every path computes the same model, and the batch-1 launches read the
+  // streams.  A class may be selected by one of the two, not by both (tgx_finalize: TGX_ERR_INVALID), and then gets no exponent-packed copy.
+  // options weights.fp8_rows / weights.fp4_rows: skinny products over a quantized matrix stream its codes (kernels/skinny_fp8.h, skinny_fp4.h)
+  QuantForm quant[2];           // [kind - WS_FP8]
+  QuantForm& quant_of(int kind) { return quant[kind - WS_FP8]; }
+  const QuantForm& quant_of(int kind) const { return quant[kind - WS_FP8]; }
   float *rope_cos = nullptr, *rope_sin = nullptr;
   std::vector<RowState> rows;   // views into the per-row slabs below (constant row stride: batched GEMV walks them)
   float *slab_x = nullptr, *slab_q = nullptr, *slab_kraw = nullptr, *slab_attn = nullptr, *slab_h = nullptr, *slab_logits = nullptr;
@@ -508,8 +504,8 @@ bool is_greedy(const tgx_sampler_cfg* s);   // Sampler.cpp:15-21
 bool row_records(const tgx_ctx* c, int row);   // the row records log-probabilities in the steps (tgx_set_row_logprobs; not while it is retired)
 // ---- decode.hip (kernels/gemv.h, kernels/oproj_sliced.h)
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc);
-int quantize_weights(tgx_ctx* c); // tgx_finalize, ahead of pack_weights: option weights.fp8 (dequantized masters in place, the 8-bit streams and row scales)
-int quantize_weights_fp4(tgx_ctx* c); // ... and option weights.fp4 (dequantized masters in place, the 4-bit streams with their block scales)
+int stream_form(const tgx_ctx* c, int bit);   // the WS_* form tgx_finalize gives the matrices of a class (bit: 1 gate_up, 2 down, 4 lm_head): one per class
+int quantize_weights(tgx_ctx* c); // tgx_finalize, ahead of pack_weights: options weights.fp8 / weights.fp4 (dequantized masters in place, the code streams)
 int pack_weights(tgx_ctx* c);     // tgx_finalize: the exponent-packed copies of the bf16 gate_up / down / lm_head matrices (option weights.packed)
 bool oproj_sliced_ok(const tgx_ctx* c, int R, long long kv_stride);
 bool oproj_fused_capable(const tgx_ctx* c);                               // static conditions (geometry, dtype, option)
@@ -613,16 +609,15 @@ void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, in
 int skinny_set_attrs(tgx_ctx* c);
 // ---- decode_fp4.hip (kernels/gemv_fp4.h)
 namespace tgx { struct GemvArgs; }
-void launch_gemv_fp4(tgx_ctx* c, int cls, const tgx::GemvArgs& a, const Fp4Mat& q, int grid, int nx);      // cls: TGX_KERNEL_GATEUP / DOWN / LMHEAD picks the form
+void launch_gemv_fp4(tgx_ctx* c, int cls, const tgx::GemvArgs& a, const WeightStream& q, int grid, int nx);      // cls: TGX_KERNEL_GATEUP / DOWN / LMHEAD picks the form
 void fp4_scan_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int* stat_dev);                             // *stat_dev = min(*stat_dev, the lowest row the rule refuses)
 long long fp4_row_bytes(int ks, int nx);
 void fp4_quant_matrix(tgx_ctx* c, ebyte* W, int N, int K, int ldw, int ks, int nx, unsigned char* Q, long long row_bytes);      // K columns of rows ldw apart; Q == nullptr: the master only
-// ---- skinny_fp8.hip (kernels/skinny_fp8.h)
+// ---- skinny_fp8.hip (kernels/skinny_fp8.h), skinny_fp4.hip (kernels/skinny_fp4.h): the two share stream_launch.h
 namespace tgx { struct GemmArgs; }
-bool skinny_fp8_covers(const tgx_ctx* c, const Fp8Mat& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)
-void launch_skinny_fp8(tgx_ctx* c, const tgx::GemmArgs& g, const Fp8Mat& q, int epi, int mb, int nsplit);
+bool skinny_fp8_covers(const tgx_ctx* c, const WeightStream& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)
+bool skinny_fp4_covers(const tgx_ctx* c, const WeightStream& q, int M, int K, int k_per);
+void launch_skinny_fp8(tgx_ctx* c, const tgx::GemmArgs& g, const WeightStream& q, int epi, int mb, int nsplit);
+void launch_skinny_fp4(tgx_ctx* c, const tgx::GemmArgs& g, const WeightStream& q, int epi, int mb, int nsplit);
 int skinny_fp8_set_attrs(tgx_ctx* c);
-// ---- skinny_fp4.hip (kernels/skinny_fp4.h)
-bool skinny_fp4_covers(const tgx_ctx* c, const Fp4Mat& q, int M, int K, int k_per);      // k_per: the K range of one split (0: unsplit)
-void launch_skinny_fp4(tgx_ctx* c, const tgx::GemmArgs& g, const Fp4Mat& q, int epi, int mb, int nsplit);
 int skinny_fp4_set_attrs(tgx_ctx* c);

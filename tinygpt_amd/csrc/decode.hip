@@ -1,7 +1,7 @@
 // decode.hip — the batch-1..4 decode step of the MI355X shim: one launch per kernel class and layer (kernels/gemv.h), the K-sliced o_proj behind
 // split-form attention (kernels/oproj_sliced.h), lm_head + per-workgroup argmax, the greedy finalize.
 // == for (auto& layer : layers_) x = layer->forward(x); norm; lm_head  (GPTModel.h:51-58, DecoderLayer.h:38-43, Attention.h:71-91, GatedMLP.h:37-41)
-#include "ctx.h"
+#include "stream_launch.h"
 #include "gemv_grid.h"
 #include "kernels/attn_decode.h"
 #include "kernels/gemv.h"
@@ -13,13 +13,10 @@
 
 int gemv_grid(const tgx_ctx* c, int units, int ks, int bpc) { return tgx::gemv_grid_plan(units, 4 / ks, c->num_cus * bpc).grid; }
 
-// 16-byte slices per lane per row for a K range split over ks waves (the kernel's NX template parameter)
-static int gemv_nx(int K, int ks) { return ((K / 8) + ks * 64 - 1) / (ks * 64); }
-
 // smallest K split that keeps a wave's slice within 8 x 512 elements; norm-fused launches must use 1
 static int gemv_auto_ks(int K, int want) {
   int ks = want;
-  while (ks < 4 && gemv_nx(K, ks) > 8) ks *= 2;
+  while (ks < 4 && stream_nx(K, ks) > 8) ks *= 2;
   return ks;
 }
 
@@ -53,46 +50,36 @@ static void launch_gemv_nx(tgx_ctx* c, const tgx::GemvArgs& a, int grid, int R) 
   for (int r = 0; r < R; r++) hipLaunchKernelGGL((tgx::gemv_kernel<DT, PRO, EPI, NX, 1>), g, b, 0, c->stream, gemv_row(c, a, r));
 }
 
-// ---- exponent-packed weights (kernels/gemv_packed.h; option weights.packed) ----
-template <int PRO, int EPI, int NX>
-static void launch_gemv_packed_nx(tgx_ctx* c, const tgx::GemvPackedArgs& p, int grid) {
-  const dim3 g(grid), b(256);
-  if constexpr (EPI != tgx::EPI_LOGITS) {      // the fixed-point residual stream behind the K-sliced o_proj (launch_gemv_nx)
-    if (p.g.x_acc || p.g.res_acc) { hipLaunchKernelGGL((tgx::gemv_packed_kernel<PRO, EPI, NX, true>), g, b, p.g.x_acc ? (size_t)p.g.K * 4 : 0, c->stream, p); return; }
-  }
-  hipLaunchKernelGGL((tgx::gemv_packed_kernel<PRO, EPI, NX, false>), g, b, 0, c->stream, p);
+// ---- the batch-1 launches over a weight stream (ctx.h WeightStream; the NX / fixed-point switch: stream_launch.h).  FP4's lives in decode_fp4.hip ----
+template <int PRO, int EPI>
+static void launch_gemv_packed(tgx_ctx* c, const tgx::GemvArgs& a, const WeightStream& pk, int grid, int nx) {
+  tgx::GemvPackedArgs p{};
+  p.g = a; p.P = pk.planes; p.rec = pk.rec; p.row_bytes = pk.row_bytes; p.e0h4 = pk.e0h4;
+  launch_gemv_stream<EPI != tgx::EPI_LOGITS>(c, p, grid, nx, [](auto NX, auto XA) { return &tgx::gemv_packed_kernel<PRO, EPI, decltype(NX)::value, decltype(XA)::value>; });
 }
 
 template <int PRO, int EPI>
-static void launch_gemv_packed(tgx_ctx* c, const tgx::GemvArgs& a, const PackedMat& pk, int grid, int nx) {
-  tgx::GemvPackedArgs p{};
-  p.g = a; p.P = pk.P; p.rec = pk.rec; p.row_bytes = pk.row_bytes; p.e0h4 = pk.e0h4;
-  switch (nx) {
-    case 1: launch_gemv_packed_nx<PRO, EPI, 1>(c, p, grid); break;
-    case 2: launch_gemv_packed_nx<PRO, EPI, 2>(c, p, grid); break;
-    case 3: launch_gemv_packed_nx<PRO, EPI, 3>(c, p, grid); break;
-    case 4: launch_gemv_packed_nx<PRO, EPI, 4>(c, p, grid); break;
-    case 5: launch_gemv_packed_nx<PRO, EPI, 5>(c, p, grid); break;
-    case 6: launch_gemv_packed_nx<PRO, EPI, 6>(c, p, grid); break;
-    case 7: launch_gemv_packed_nx<PRO, EPI, 7>(c, p, grid); break;
-    default: launch_gemv_packed_nx<PRO, EPI, 8>(c, p, grid); break;
-  }
+static void launch_gemv_fp8(tgx_ctx* c, const tgx::GemvArgs& a, const WeightStream& q, int grid, int nx) {
+  tgx::GemvFp8Args p{};
+  p.g = a; p.Q = q.planes; p.scale = q.scale; p.row_bytes = q.row_bytes;
+  launch_gemv_stream<EPI != tgx::EPI_LOGITS>(c, p, grid, nx, [](auto NX, auto XA) { return &tgx::gemv_fp8_kernel<PRO, EPI, decltype(NX)::value, decltype(XA)::value>; });
 }
 
+// ---- exponent-packed weights (kernels/gemv_packed.h; option weights.packed) ----
 // One matrix of class `cls` into the packed form, laid out for the K split its batch-1 launch uses now.  Leaves `out` empty (the plain kernel serves the
 // matrix) when the shape is outside the format or a row has more escapes than its record holds.
-static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* stat_dev, PackedMat* out) {
-  const int ks = gemv_auto_ks(K, c->tune[cls].ks), nx = gemv_nx(K, ks);
+static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* stat_dev, WeightStream* out) {
+  const int ks = gemv_auto_ks(K, c->tune[cls].ks), nx = stream_nx(K, ks);
   if (K % 8 || K > tgx::PACKED_K_MAX || nx > 8) return TGX_OK;
-  PackedMat m;
-  m.ks = ks; m.row_bytes = (long long)ks * ((nx + 3) / 4) * 3072;
+  WeightStream m;
+  m.kind = WS_PACKED; m.ks = ks; m.row_bytes = (long long)ks * ((nx + 3) / 4) * 3072;
   int rc;
-  if ((rc = dev_alloc(c, &m.P, (size_t)N * (size_t)m.row_bytes)) || (rc = dev_alloc(c, &m.rec, (size_t)N * (size_t)ks))) { dev_free(c, &m.P); return rc; }
+  if ((rc = dev_alloc(c, &m.planes, (size_t)N * (size_t)m.row_bytes)) || (rc = dev_alloc(c, &m.rec, (size_t)N * (size_t)ks))) { dev_free(c, &m.planes); return rc; }
   HIP_OK(c, hipMemsetAsync(stat_dev, 0, 4 * sizeof(int), c->stream));
   const size_t n8 = (size_t)N * K / 8;
   hipLaunchKernelGGL(tgx::packed_maxexp_kernel, dim3((unsigned)std::min<size_t>((n8 + 255) / 256, 4096)), dim3(256), 0, c->stream, reinterpret_cast<const bf16_t*>(W), n8, stat_dev);
   tgx::PackRowsArgs a{};
-  a.W = reinterpret_cast<const bf16_t*>(W); a.N = N; a.K = K; a.ks = ks; a.nx = nx; a.P = m.P; a.rec = m.rec; a.row_bytes = m.row_bytes; a.stat = stat_dev;
+  a.W = reinterpret_cast<const bf16_t*>(W); a.N = N; a.K = K; a.ks = ks; a.nx = nx; a.P = m.planes; a.rec = m.rec; a.row_bytes = m.row_bytes; a.stat = stat_dev;
   hipLaunchKernelGGL(tgx::pack_rows_kernel, dim3(N), dim3(64), 0, c->stream, a);
   int stat[4] = {0, 0, 0, 0};
   HIP_OK(c, hipGetLastError());
@@ -100,7 +87,7 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
   HIP_OK(c, hipStreamSynchronize(c->stream));
   c->packed_max_row_esc = std::max(c->packed_max_row_esc, stat[3]);
   if (stat[1] > 0) {       // a (row, K-part)'s escapes do not fit its record: this matrix stays plain
-    dev_free(c, &m.P); dev_free(c, &m.rec);
+    dev_free(c, &m.planes); dev_free(c, &m.rec);
     c->packed_fallbacks++;
     return TGX_OK;
   }
@@ -111,76 +98,74 @@ static int pack_matrix(tgx_ctx* c, const ebyte* W, int N, int K, int cls, int* s
   return TGX_OK;
 }
 
+// One form per class, decided here and nowhere else: a class selected by weights.fp8 or weights.fp4 (tgx_finalize refuses a class selected by both) streams
+// its codes, so a packed copy of it would never be read; the stream forms exist for bf16 storage and the gated-MLP families (GPT-2's LayerNorm / GELU
+// launches have none; tgx_finalize refuses the quantized options there).
+int stream_form(const tgx_ctx* c, int bit) {
+  if (c->dt != tgx::DT_BF16 || c->gpt2) return WS_NONE;
+  for (int kind : {WS_FP8, WS_FP4})
+    if (c->quant_of(kind).on && (c->quant_of(kind).classes & bit)) return kind;
+  return c->weights_packed && (c->packed_classes & bit) ? WS_PACKED : WS_NONE;
+}
+
 int pack_weights(tgx_ctx* c) {
   const tgx_model_desc& d = c->d;
-  if (!c->weights_packed || c->dt != tgx::DT_BF16 || c->gpt2) return TGX_OK;      // (GPT-2's LayerNorm / GELU launches have no packed form)
-  const int classes = c->packed_classes & ~(c->weights_fp8 ? c->fp8_classes : 0) & ~(c->weights_fp4 ? c->fp4_classes : 0);      // a class quantized by weights.fp8 / weights.fp4 streams its codes: a packed copy would never be read
+  const bool gu = stream_form(c, 1) == WS_PACKED, dn = stream_form(c, 2) == WS_PACKED && d.inter <= 16384, lm = stream_form(c, 4) == WS_PACKED;
+  if (!gu && !dn && !lm) return TGX_OK;
   int* stat_dev = nullptr;
   int rc = dev_alloc(c, &stat_dev, 4);
   for (size_t l = 0; l < c->L.size() && !rc; l++) {
     LayerW& w = c->L[l];
-    if (classes & 1) rc = pack_matrix(c, w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, stat_dev, &w.pgu);
-    if (!rc && (classes & 2) && d.inter <= 16384) rc = pack_matrix(c, w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, stat_dev, &w.pdown);
+    if (gu) rc = pack_matrix(c, w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, stat_dev, &w.sgu);
+    if (!rc && dn) rc = pack_matrix(c, w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, stat_dev, &w.sdown);
   }
-  if (!rc && (classes & 4)) rc = pack_matrix(c, d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, stat_dev, &c->plm);
+  if (!rc && lm) rc = pack_matrix(c, d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, stat_dev, &c->slm);
   dev_free(c, &stat_dev);
   return rc;
 }
 
-// ---- FP8 weights (kernels/gemv_fp8.h; option weights.fp8) ----
-template <int PRO, int EPI, int NX>
-static void launch_gemv_fp8_nx(tgx_ctx* c, const tgx::GemvFp8Args& p, int grid) {
-  const dim3 g(grid), b(256);
-  if constexpr (EPI != tgx::EPI_LOGITS) {      // the fixed-point residual stream behind the K-sliced o_proj (launch_gemv_nx)
-    if (p.g.x_acc || p.g.res_acc) { hipLaunchKernelGGL((tgx::gemv_fp8_kernel<PRO, EPI, NX, true>), g, b, p.g.x_acc ? (size_t)p.g.K * 4 : 0, c->stream, p); return; }
-  }
-  hipLaunchKernelGGL((tgx::gemv_fp8_kernel<PRO, EPI, NX, false>), g, b, 0, c->stream, p);
-}
+// ---- quantized weights (kernels/gemv_fp8.h; kernels/gemv_fp4.h through decode_fp4.hip; options weights.fp8 / weights.fp4) ----
+// the K ranges of the down launch at intermediate sizes beyond 16384 (launch_layer_kernel): their number and the width of each but the last
+static int down_parts(int cls, int K) { return cls == TGX_KERNEL_DOWN && K > 16384 ? (K + 16383) / 16384 : 1; }
+static int down_part_k(int K, int parts) { return ((K / 8 + parts - 1) / parts) * 8; }
 
-template <int PRO, int EPI>
-static void launch_gemv_fp8(tgx_ctx* c, const tgx::GemvArgs& a, const Fp8Mat& q, int grid, int nx) {
-  tgx::GemvFp8Args p{};
-  p.g = a; p.Q = q.Q; p.scale = q.scale; p.row_bytes = q.row_bytes;
-  switch (nx) {
-    case 1: launch_gemv_fp8_nx<PRO, EPI, 1>(c, p, grid); break;
-    case 2: launch_gemv_fp8_nx<PRO, EPI, 2>(c, p, grid); break;
-    case 3: launch_gemv_fp8_nx<PRO, EPI, 3>(c, p, grid); break;
-    case 4: launch_gemv_fp8_nx<PRO, EPI, 4>(c, p, grid); break;
-    case 5: launch_gemv_fp8_nx<PRO, EPI, 5>(c, p, grid); break;
-    case 6: launch_gemv_fp8_nx<PRO, EPI, 6>(c, p, grid); break;
-    case 7: launch_gemv_fp8_nx<PRO, EPI, 7>(c, p, grid); break;
-    default: launch_gemv_fp8_nx<PRO, EPI, 8>(c, p, grid); break;
-  }
-}
-
-// The matrices of the classes in weights.fp8_classes, quantized where they lie (the rule: include/tgx.h).  Two launches per matrix: the row scales and the
-// check for weights the rule refuses — all matrices first, so that nothing is overwritten when one is refused — then the dequantized master, the codes in the
-// layout of the class's batch-1 launch and nothing else.  A matrix whose shape the layout does not cover is quantized all the same and keeps no stream.
+// The matrices of the classes given a quantized form (stream_form), quantized where they lie (the rules: include/tgx.h).  First the scan for weights the rule
+// refuses over ALL matrices of BOTH forms (FP8's scan also leaves the row scales), so that no master is overwritten when one is refused; then per matrix the
+// form's launch: the dequantized master and the codes in the layout of the class's batch-1 launch.  A matrix whose shape the layout does not cover is
+// quantized all the same and keeps its kind without planes.
+//   FP8: K % 8 == 0 and at most 8 chunks per lane; the planes are zeroed first (the kernel does not write their padding)
+//   FP4: whole blocks of 32 k in equal ranges, at most 8 chunks per lane; the kernel writes every byte.  A down matrix beyond 16384 columns is laid out as the
+//        K ranges of its launches (launch_layer_kernel), each with the split and chunk count of that launch
+// Every error path frees what the call still owns (streams already handed to their matrix belong to the context: tgx_finalize has failed, tgx_destroy frees them).
 int quantize_weights(tgx_ctx* c) {
   const tgx_model_desc& d = c->d;
-  if (!c->weights_fp8) return TGX_OK;
-  struct Job { ebyte* W; int N, K, cls, layer; Fp8Mat* out; };
+  struct Job { int kind; ebyte* W; int N, K, cls, layer; WeightStream* out; float* scale; };
   std::vector<Job> jobs;
-  for (size_t l = 0; l < c->L.size(); l++) {
-    LayerW& w = c->L[l];
-    if (c->fp8_classes & 1) jobs.push_back({w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, (int)l, &w.qgu});
-    if (c->fp8_classes & 2) jobs.push_back({w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, (int)l, &w.qdown});
+  for (int kind : {WS_FP8, WS_FP4}) {      // (FP8's matrices first: the order the two forms were quantized in when each had a driver of its own)
+    for (size_t l = 0; l < c->L.size(); l++) {
+      LayerW& w = c->L[l];
+      if (stream_form(c, 1) == kind) jobs.push_back({kind, w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, (int)l, &w.sgu, nullptr});
+      if (stream_form(c, 2) == kind) jobs.push_back({kind, w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, (int)l, &w.sdown, nullptr});
+    }
+    if (stream_form(c, 4) == kind) jobs.push_back({kind, d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, -1, &c->slm, nullptr});
   }
-  if (c->fp8_classes & 4) jobs.push_back({d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, -1, &c->qlm});
   if (jobs.empty()) return TGX_OK;
+  auto opt = [](int kind) { return kind == WS_FP8 ? "weights.fp8" : "weights.fp4"; };
+  const char* first = opt(jobs[0].kind);      // names a failure of a step the forms share
   int* stat_dev = nullptr;
   int rc = dev_alloc(c, &stat_dev, jobs.size());
   if (rc) return rc;
-  std::vector<float*> scale(jobs.size(), nullptr);
   std::vector<int> stat(jobs.size(), INT_MAX);
-  auto drop = [&]() { for (float*& s : scale) if (s) dev_free(c, &s); dev_free(c, &stat_dev); };
-  if (hipMemcpyAsync(stat_dev, stat.data(), stat.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) { drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: the status upload failed"); }
-  for (size_t i = 0; i < jobs.size(); i++) {
-    if ((rc = dev_alloc(c, &scale[i], (size_t)jobs[i].N))) { drop(); return rc; }
-    hipLaunchKernelGGL(tgx::fp8_row_scale_kernel, dim3(jobs[i].N), dim3(64), 0, c->stream, reinterpret_cast<const bf16_t*>(jobs[i].W), jobs[i].K, scale[i], stat_dev + i);
+  auto drop = [&]() { for (Job& j : jobs) if (j.scale) dev_free(c, &j.scale); dev_free(c, &stat_dev); };
+  if (hipMemcpyAsync(stat_dev, stat.data(), stat.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) { drop(); return set_err(c, TGX_ERR_DEVICE, "%s: the status upload failed", first); }
+  for (size_t i = 0; i < jobs.size(); i++) {      // stat[i] = the lowest row the rule refuses
+    Job& j = jobs[i];
+    if (j.kind == WS_FP4) { fp4_scan_matrix(c, j.W, j.N, j.K, stat_dev + i); continue; }
+    if ((rc = dev_alloc(c, &j.scale, (size_t)j.N))) { drop(); return rc; }
+    hipLaunchKernelGGL(tgx::fp8_row_scale_kernel, dim3(j.N), dim3(64), 0, c->stream, reinterpret_cast<const bf16_t*>(j.W), j.K, j.scale, stat_dev + i);
   }
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(stat.data(), stat_dev, stat.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) { drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: the scan of the weights failed"); }
+      hipStreamSynchronize(c->stream) != hipSuccess) { drop(); return set_err(c, TGX_ERR_DEVICE, "%s: the scan of the weights failed", first); }
   for (size_t i = 0; i < jobs.size(); i++) {
     if (stat[i] >= jobs[i].N) continue;
     const Job& j = jobs[i];
@@ -188,117 +173,72 @@ int quantize_weights(tgx_ctx* c) {
     if (j.cls == TGX_KERNEL_LMHEAD) snprintf(name, sizeof name, "%s", d.tied ? "model.embed_tokens.weight" : "lm_head.weight");
     else snprintf(name, sizeof name, "model.layers.%d.mlp.%s_proj.weight", j.layer, j.cls == TGX_KERNEL_DOWN ? "down" : (stat[i] < d.inter ? "gate" : "up"));
     drop();
-    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp8: %s holds a non-finite weight or one of magnitude 2^100 or more (row %d)", name, stat[i]);
+    return set_err(c, TGX_ERR_UNSUPPORTED, "%s: %s holds a non-finite weight or one of magnitude 2^100 or more (row %d)", opt(j.kind), name, stat[i]);
   }
-  for (size_t i = 0; i < jobs.size(); i++) {
-    const Job& j = jobs[i];
-    const int ks = gemv_auto_ks(j.K, c->tune[j.cls].ks), nx = gemv_nx(j.K, ks);
-    const bool stream = j.K % 8 == 0 && nx <= 8;
-    Fp8Mat m;
-    tgx::Fp8QuantArgs a{};
-    a.W = reinterpret_cast<bf16_t*>(j.W); a.K = j.K; a.ks = ks; a.nx = nx; a.scale = scale[i];
-    if (stream) {
-      m.ks = ks; m.row_bytes = (long long)ks * ((nx + 1) / 2) * 1024; m.scale = scale[i];
-      if ((rc = dev_alloc(c, &m.Q, (size_t)j.N * (size_t)m.row_bytes))) { drop(); return rc; }
-      if (hipMemsetAsync(m.Q, 0, (size_t)j.N * (size_t)m.row_bytes, c->stream) != hipSuccess) { dev_free(c, &m.Q); drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: clearing the code planes failed"); }
-      a.Q = m.Q; a.row_bytes = m.row_bytes;
+  for (Job& j : jobs) {
+    const int parts = j.kind == WS_FP4 ? down_parts(j.cls, j.K) : 1, Kp = parts > 1 ? down_part_k(j.K, parts) : j.K;      // the K range of one launch
+    const int ks = gemv_auto_ks(Kp, c->tune[j.cls].ks), nx = stream_nx(Kp, ks);
+    WeightStream m;
+    m.kind = j.kind;
+    if (j.kind == WS_FP8) {
+      tgx::Fp8QuantArgs a{};
+      a.W = reinterpret_cast<bf16_t*>(j.W); a.K = j.K; a.ks = ks; a.nx = nx; a.scale = j.scale;
+      if (j.K % 8 == 0 && nx <= 8) {
+        m.ks = ks; m.row_bytes = (long long)ks * ((nx + 1) / 2) * 1024;
+        if ((rc = dev_alloc(c, &m.planes, (size_t)j.N * (size_t)m.row_bytes))) { drop(); return rc; }
+        if (hipMemsetAsync(m.planes, 0, (size_t)j.N * (size_t)m.row_bytes, c->stream) != hipSuccess) { dev_free(c, &m.planes); drop(); return set_err(c, TGX_ERR_DEVICE, "weights.fp8: clearing the code planes failed"); }
+        a.Q = m.planes; a.row_bytes = m.row_bytes;
+        m.scale = j.scale; j.scale = nullptr;      // (the stream keeps its scales)
+      }
+      hipLaunchKernelGGL(tgx::fp8_quant_rows_kernel, dim3(j.N), dim3(64), 0, c->stream, a);
+    } else {
+      if (Kp % 32 == 0 && Kp * parts == j.K && nx <= 8) {
+        m.ks = ks; m.K = Kp; m.parts = parts; m.row_bytes = fp4_row_bytes(ks, nx);
+        if ((rc = dev_alloc(c, &m.planes, (size_t)parts * j.N * (size_t)m.row_bytes))) { drop(); return rc; }
+      }
+      for (int s = 0; s < (m.planes ? parts : 1); s++)
+        fp4_quant_matrix(c, j.W + (size_t)s * Kp * c->esz, j.N, m.planes ? Kp : j.K, j.K, ks, nx, m.planes ? m.planes + (size_t)s * j.N * m.row_bytes : nullptr, m.row_bytes);
     }
-    hipLaunchKernelGGL(tgx::fp8_quant_rows_kernel, dim3(j.N), dim3(64), 0, c->stream, a);
-    if (stream) { *j.out = m; scale[i] = nullptr; c->fp8_matrices++; }      // (the stream keeps its scales)
-    else c->fp8_fallbacks++;
+    *j.out = m;
+    if (m.planes) c->quant_of(j.kind).matrices++;
+    else c->quant_of(j.kind).fallbacks++;
   }
   const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
+  const char* last = opt(jobs.back().kind);
   drop();
-  return ok ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "weights.fp8: quantizing the weights failed");
-}
-
-// ---- FP4 weights (kernels/gemv_fp4.h, decode_fp4.hip; option weights.fp4) ----
-// The matrices of the classes in weights.fp4_classes, quantized where they lie (the rule: include/tgx.h), in quantize_weights' order: the scan for weights
-// the rule refuses over all matrices first, so that nothing is overwritten when one is refused, then one launch per matrix that writes the dequantized
-// master and every byte of the stream.  A matrix whose shape the layout does not cover is quantized all the same and keeps no stream.  A down matrix beyond
-// 16384 columns is laid out as the K ranges of its launches (launch_layer_kernel), each with the split and chunk count of that launch.  (A device allocation
-// that fails on the way leaves earlier matrices quantized: tgx_finalize has failed and the context is not usable.)
-// the K ranges of the down launch at intermediate sizes beyond 16384 (launch_layer_kernel): their number and the width of each but the last
-static int down_parts(int cls, int K) { return cls == TGX_KERNEL_DOWN && K > 16384 ? (K + 16383) / 16384 : 1; }
-static int down_part_k(int K, int parts) { return ((K / 8 + parts - 1) / parts) * 8; }
-
-int quantize_weights_fp4(tgx_ctx* c) {
-  const tgx_model_desc& d = c->d;
-  if (!c->weights_fp4) return TGX_OK;
-  struct Job { ebyte* W; int N, K, cls, layer; Fp4Mat* out; };
-  std::vector<Job> jobs;
-  for (size_t l = 0; l < c->L.size(); l++) {
-    LayerW& w = c->L[l];
-    if (c->fp4_classes & 1) jobs.push_back({w.wgu, 2 * d.inter, d.hidden, TGX_KERNEL_GATEUP, (int)l, &w.fgu});
-    if (c->fp4_classes & 2) jobs.push_back({w.wdown, d.hidden, d.inter, TGX_KERNEL_DOWN, (int)l, &w.fdown});
-  }
-  if (c->fp4_classes & 4) jobs.push_back({d.tied ? c->embed : c->lm_head, d.vocab, d.hidden, TGX_KERNEL_LMHEAD, -1, &c->flm});
-  if (jobs.empty()) return TGX_OK;
-  int* stat_dev = nullptr;
-  int rc = dev_alloc(c, &stat_dev, jobs.size());
-  if (rc) return rc;
-  std::vector<int> stat(jobs.size(), INT_MAX);
-  if (hipMemcpyAsync(stat_dev, stat.data(), stat.size() * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) { dev_free(c, &stat_dev); return set_err(c, TGX_ERR_DEVICE, "weights.fp4: the status upload failed"); }
-  for (size_t i = 0; i < jobs.size(); i++) fp4_scan_matrix(c, jobs[i].W, jobs[i].N, jobs[i].K, stat_dev + i);
-  const bool scanned = hipGetLastError() == hipSuccess && hipMemcpyAsync(stat.data(), stat_dev, stat.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
-                       hipStreamSynchronize(c->stream) == hipSuccess;
-  dev_free(c, &stat_dev);
-  if (!scanned) return set_err(c, TGX_ERR_DEVICE, "weights.fp4: the scan of the weights failed");
-  for (size_t i = 0; i < jobs.size(); i++) {
-    if (stat[i] >= jobs[i].N) continue;
-    const Job& j = jobs[i];
-    char name[96];
-    if (j.cls == TGX_KERNEL_LMHEAD) snprintf(name, sizeof name, "%s", d.tied ? "model.embed_tokens.weight" : "lm_head.weight");
-    else snprintf(name, sizeof name, "model.layers.%d.mlp.%s_proj.weight", j.layer, j.cls == TGX_KERNEL_DOWN ? "down" : (stat[i] < d.inter ? "gate" : "up"));
-    return set_err(c, TGX_ERR_UNSUPPORTED, "weights.fp4: %s holds a non-finite weight or one of magnitude 2^100 or more (row %d)", name, stat[i]);
-  }
-  for (size_t i = 0; i < jobs.size(); i++) {
-    const Job& j = jobs[i];
-    const int parts = down_parts(j.cls, j.K), Kp = down_part_k(j.K, parts);
-    const int ks = gemv_auto_ks(Kp, c->tune[j.cls].ks), nx = gemv_nx(Kp, ks);
-    Fp4Mat m;
-    if (Kp % 32 == 0 && Kp * parts == j.K && nx <= 8) {      // whole blocks of 32 k in equal ranges, at most 8 chunks per lane
-      m.ks = ks; m.K = Kp; m.parts = parts; m.row_bytes = fp4_row_bytes(ks, nx);
-      if ((rc = dev_alloc(c, &m.Q, (size_t)parts * j.N * (size_t)m.row_bytes))) return rc;
-    }
-    for (int s = 0; s < (m.Q ? parts : 1); s++)
-      fp4_quant_matrix(c, j.W + (size_t)s * Kp * c->esz, j.N, m.Q ? Kp : j.K, j.K, ks, nx, m.Q ? m.Q + (size_t)s * j.N * m.row_bytes : nullptr, m.row_bytes);
-    if (m.Q) { *j.out = m; c->fp4_matrices++; }
-    else c->fp4_fallbacks++;
-  }
-  return hipGetLastError() == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "weights.fp4: quantizing the weights failed");
+  return ok ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "%s: quantizing the weights failed", last);
 }
 
 template <int PRO, int EPI>
-static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const PackedMat* pk = nullptr, const Fp8Mat* q8 = nullptr, const Fp4Mat* q4 = nullptr) {
+static void launch_gemv(tgx_ctx* c, tgx::GemvArgs a, int cls, int R, const WeightStream* ws = nullptr) {
   const Tune& tn = c->tune[cls];
   a.dbg = ((c->debug_gemv >> (8 + cls)) & 1) ? (c->debug_gemv & 15) : 0;
   if (!a.ldw) a.ldw = a.K;
   a.ks = gemv_auto_ks(a.K, tn.ks);   // norm-fused launches K-split too (their waves exchange the sums of squares through LDS)
-  while (R > 1 && a.ks < 4 && gemv_nx(a.K, a.ks) > 4) a.ks *= 2;   // batch rows: at most 4 slices per row and lane (measured: B = 2 and 4 on the 1B / 3B / 7B shapes)
+  while (R > 1 && a.ks < 4 && stream_nx(a.K, a.ks) > 4) a.ks *= 2;   // batch rows: at most 4 slices per row and lane (measured: B = 2 and 4 on the 1B / 3B / 7B shapes)
   // two rows on the gate_up launch: 2 slices per row and lane leave room for the double-buffered weight registers (R x NX <= 4):
   // Llama-3.2-1B B = 2: 2394 -> 2506 tok/s; the same split loses 2-6 % at B = 4 and on the other launches (tools/batch_bench.py --opts)
-  if (R == 2 && cls == TGX_KERNEL_GATEUP && a.ks == 1 && gemv_nx(a.K, 1) == 4) a.ks = 2;
+  if (R == 2 && cls == TGX_KERNEL_GATEUP && a.ks == 1 && stream_nx(a.K, 1) == 4) a.ks = 2;
   const int grid = (EPI == tgx::EPI_LOGITS) ? c->lm_grid : gemv_grid(c, a.units, a.ks, tn.bpc);
-  const int nx = gemv_nx(a.K, a.ks);
+  const int nx = stream_nx(a.K, a.ks);
   if constexpr ((PRO == tgx::PRO_RMSNORM && (EPI == tgx::EPI_SILU_MUL || EPI == tgx::EPI_LOGITS)) || (PRO == tgx::PRO_PLAIN && EPI == tgx::EPI_RESIDUAL)) {
-    // batch 1 over a matrix quantized by option weights.fp4 with a stream laid out for this K split: 4.25 bits per weight, bit-identical to the plain kernel
-    // over the dequantized master (workgroups per CU: the class's packed_bpc, profiles/weights_fp4.txt)
-    if (q4 && q4->Q && R == 1 && q4->ks == a.ks && q4->K == a.K && !a.dbg) {      // (a K range of wider rows has a stream of its own: ldw is the master's)
-      launch_gemv_fp4(c, cls, a, *q4, (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc), nx);
-      return;
-    }
-    // batch 1 over a matrix quantized by option weights.fp8 with a stream laid out for this K split: half the bytes, bit-identical to the plain kernel over the
-    // dequantized master (workgroups per CU: the class's packed_bpc — no other value has been measured yet, profiles/weights_fp8.txt)
-    if (q8 && q8->Q && R == 1 && q8->ks == a.ks && a.ldw == a.K && !a.dbg) {
-      launch_gemv_fp8<PRO, EPI>(c, a, *q8, (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc), nx);
-      return;
-    }
-    // batch 1 over an exponent-packed matrix laid out for this K split: 25 % fewer bytes, bit-identical results
-    // (its own workgroups per CU, Tune::packed_bpc; the lm_head's grid is lm_grid in both forms: it sizes the argmax partials)
-    if (pk && pk->P && R == 1 && pk->ks == a.ks && a.ldw == a.K && !a.dbg) {
-      launch_gemv_packed<PRO, EPI>(c, a, *pk, (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc), nx);
-      return;
+    // batch 1 over a matrix that owns a stream laid out for this K split: bit-identical to the plain kernel over the (dequantized) master.  Workgroups per CU:
+    // the class's packed_bpc for every form (Tune::packed_bpc; no other value has been measured for FP8, profiles/weights_fp8.txt; FP4: profiles/weights_fp4.txt);
+    // the lm_head's grid is lm_grid in all forms: it sizes the argmax partials
+    if (ws && ws->planes && R == 1 && ws->ks == a.ks && !a.dbg) {
+      const int sgrid = (EPI == tgx::EPI_LOGITS) ? grid : gemv_grid(c, a.units, a.ks, tn.packed_bpc);
+      switch (ws->kind) {
+        case WS_FP4:      // 4.25 bits per weight.  A K range of wider rows has a stream of its own (WeightStream::range): no ldw test, ldw is the master's
+          if (ws->K == a.K) { launch_gemv_fp4(c, cls, a, *ws, sgrid, nx); return; }
+          break;
+        case WS_FP8:      // half the bytes
+          if (a.ldw == a.K) { launch_gemv_fp8<PRO, EPI>(c, a, *ws, sgrid, nx); return; }
+          break;
+        case WS_PACKED:   // 25 % fewer bytes, lossless
+          if (a.ldw == a.K) { launch_gemv_packed<PRO, EPI>(c, a, *ws, sgrid, nx); return; }
+          break;
+        default: break;
+      }
     }
   }
   if constexpr (PRO == tgx::PRO_LAYERNORM || EPI == tgx::EPI_GELU) {   // GPT-2 (hidden <= 2048, checked in tgx_create): at most 4 slices per lane
@@ -452,7 +392,7 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
       }
       a.N = 2 * I; a.K = H; a.units = I; a.out = r.h; a.out_stride = I; a.hd = 2;
       if (resid_fixed(c, R, kv_stride)) a.x_acc = c->slab_acc + (size_t)(&r - c->rows.data()) * H;     // x' = fp32(acc)
-      launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_SILU_MUL>(c, a, TGX_KERNEL_GATEUP, R, &w.pgu, &w.qgu, &w.fgu);
+      launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_SILU_MUL>(c, a, TGX_KERNEL_GATEUP, R, &w.sgu);
       break;
     }
     case TGX_KERNEL_DOWN: {  // down_proj + residual                                  (GatedMLP.h:40, DecoderLayer.h:41)
@@ -466,14 +406,13 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
           tgx::GemvArgs p = a;
           p.W = w.wdown + (size_t)k0 * c->esz; p.x = r.h + k0; p.K = std::min(per, I - k0); p.ldw = I;
           if (k0) p.bias = nullptr;
-          Fp4Mat f4 = w.fdown;      // option weights.fp4: this K range's stream
-          if (f4.Q) f4.Q += (size_t)(k0 / per) * H * (size_t)f4.row_bytes;
-          launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, p, TGX_KERNEL_DOWN, R, nullptr, nullptr, &f4);
+          const WeightStream part = w.sdown.range(k0 / per, H);      // this K range's stream, if the form keeps one per range
+          launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, p, TGX_KERNEL_DOWN, R, &part);
         }
         break;
       }
       if (resid_fixed(c, R, kv_stride)) a.res_acc = c->slab_acc + (size_t)(&r - c->rows.data()) * H;   // x = fp32(acc) + down(h); acc <- 0
-      launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, a, TGX_KERNEL_DOWN, R, &w.pdown, &w.qdown, &w.fdown);
+      launch_gemv<tgx::PRO_PLAIN, tgx::EPI_RESIDUAL>(c, a, TGX_KERNEL_DOWN, R, &w.sdown);
       break;
     }
     default: return 0;
@@ -507,7 +446,7 @@ void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_va
     launch_gemv<tgx::PRO_LAYERNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R);
     return;
   }
-  launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R, &c->plm, &c->qlm, &c->flm);
+  launch_gemv<tgx::PRO_RMSNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R, &c->slm);
 }
 
 tgx::FinalizeArgs make_finalize_args(tgx_ctx* c, int row, bool advance_pos, bool log_step) {

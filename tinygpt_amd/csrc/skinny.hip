@@ -93,27 +93,23 @@ struct SkinnyCall {
   const float* a_f32 = nullptr; int lda = 0;
   const ebyte* norm_w = nullptr; const float* ssq_in = nullptr;
   bool allow_split = true;
-  const Fp8Mat* q8 = nullptr;      // the matrix is quantized (option weights.fp8) and this product is inside weights.fp8_rows: stream its codes where kernels/skinny_fp8.h covers it
-  const Fp4Mat* q4 = nullptr;      // the same for option weights.fp4 and weights.fp4_rows (kernels/skinny_fp4.h); a matrix is quantized by one of the two
+  const WeightStream* ws = nullptr;      // the matrix is quantized and this product is inside its form's row option (rows_stream): stream its codes where the form's kernel covers it
 };
 }  // namespace
-// the 8-bit stream of a quantized class (bit: 1 gate_up, 2 down, 4 lm_head) for a product of M activation rows, or nullptr: option weights.fp8_rows does not reach it
-static const Fp8Mat* fp8_rows_mat(const tgx_ctx* c, const Fp8Mat& q, int bit, int M) {
-  return (c->weights_fp8 && (c->fp8_classes & bit) && c->dt == tgx::DT_BF16 && c->fp8_rows && M <= c->fp8_rows) ? &q : nullptr;
+// the stream of a quantized class for a product of M activation rows, or nullptr: the form's row option (weights.fp8_rows / weights.fp4_rows) does not reach it.
+// An FP8 matrix that kept no planes is still returned — its products count as row fallbacks — an FP4 one is not
+static const WeightStream* rows_stream(const tgx_ctx* c, const WeightStream& ws, int M) {
+  if (ws.kind != WS_FP8 && ws.kind != WS_FP4) return nullptr;
+  const QuantForm& qf = c->quant_of(ws.kind);
+  return (qf.rows && M <= qf.rows && (ws.kind == WS_FP8 || ws.planes)) ? &ws : nullptr;
 }
-// the 4-bit stream of a class quantized by option weights.fp4, or nullptr: option weights.fp4_rows does not reach it (or the matrix owns no stream)
-static const Fp4Mat* fp4_rows_mat(const tgx_ctx* c, const Fp4Mat& q, int bit, int M) {
-  return (c->weights_fp4 && (c->fp4_classes & bit) && c->dt == tgx::DT_BF16 && c->fp4_rows && M <= c->fp4_rows && q.Q) ? &q : nullptr;
+static bool rows_covers(const tgx_ctx* c, const WeightStream& ws, int M, int K, int k_per) {
+  return ws.kind == WS_FP8 ? skinny_fp8_covers(c, ws, M, K, k_per) : skinny_fp4_covers(c, ws, M, K, k_per);
 }
-// does a product of M rows over K stream codes unsplit (either quantized form)?  Such a product bypasses the K-split kernel (another summation order)
-static bool rows_streams(const tgx_ctx* c, const Fp8Mat* q8, const Fp4Mat* q4, int M, int K) {
-  return (q8 && skinny_fp8_covers(c, *q8, M, K, 0)) || (q4 && skinny_fp4_covers(c, *q4, M, K, 0));
-}
+// does a product of M rows over K stream codes unsplit?  Such a product bypasses the K-split kernel (another summation order)
+static bool rows_streams(const tgx_ctx* c, const WeightStream* ws, int M, int K) { return ws && rows_covers(c, *ws, M, K, 0); }
 // a product of a quantized matrix inside its row limit is served from the master
-static void rows_fallback(tgx_ctx* c, const Fp8Mat* q8, const Fp4Mat* q4) {
-  if (q8) c->fp8_row_fallbacks++;
-  if (q4) c->fp4_row_fallbacks++;
-}
+static void rows_fallback(tgx_ctx* c, const WeightStream* ws) { if (ws) c->quant_of(ws->kind).row_fallbacks++; }
 constexpr int SKINNY_WGS = 256;     // workgroups a skinny product aims for by splitting K (two per CU: the bytes in flight per CU are what the stream rate follows)
 static int launch_skinny(tgx_ctx* c, const SkinnyCall& k) {
   tgx::GemmArgs g{};
@@ -148,13 +144,13 @@ static int launch_skinny(tgx_ctx* c, const SkinnyCall& k) {
     epi = tgx::GEMM_PARTIAL;
   }
   const dim3 grid(gx, nsplit);
-  if (k.q8) {      // same K ranges, slabs and epilogues; bit-identical to the kernels below over the dequantized master
-    if (k.asrc == 0 && k.nt == 2 && mb <= 4 && skinny_fp8_covers(c, *k.q8, k.M, k.K, nsplit > 1 ? g.k_per : 0)) { launch_skinny_fp8(c, g, *k.q8, epi, mb, nsplit); return nsplit; }
-    c->fp8_row_fallbacks++;
-  }
-  if (k.q4) {
-    if (k.asrc == 0 && k.nt == 2 && mb <= 4 && skinny_fp4_covers(c, *k.q4, k.M, k.K, nsplit > 1 ? g.k_per : 0)) { launch_skinny_fp4(c, g, *k.q4, epi, mb, nsplit); return nsplit; }
-    c->fp4_row_fallbacks++;
+  if (k.ws) {      // same K ranges, slabs and epilogues; bit-identical to the kernels below over the dequantized master
+    if (k.asrc == 0 && k.nt == 2 && mb <= 4 && rows_covers(c, *k.ws, k.M, k.K, nsplit > 1 ? g.k_per : 0)) {
+      if (k.ws->kind == WS_FP8) launch_skinny_fp8(c, g, *k.ws, epi, mb, nsplit);
+      else launch_skinny_fp4(c, g, *k.ws, epi, mb, nsplit);
+      return nsplit;
+    }
+    rows_fallback(c, k.ws);
   }
   if (c->skinny_dma && k.asrc == 0 && k.nt == 3 && k.a_lo2 && c->dt == tgx::DT_BF16 && k.K % 64 == 0 && (nsplit == 1 || g.k_per % 64 == 0) &&
       (epi == tgx::GEMM_PARTIAL || epi == tgx::GEMM_STORE)) {
@@ -258,9 +254,8 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
   const int nt_qkv = c->dt == tgx::DT_BF16 ? 3 : 2;
   float* ssq = c->ws_ssq;
   // options weights.fp8_rows / weights.fp4_rows: a product that streams the codes bypasses the K-split kernel (another summation order)
-  const Fp8Mat* qlm = fp8_rows_mat(c, c->qlm, 4, M);
-  const Fp4Mat* flm = fp4_rows_mat(c, c->flm, 4, M);
-  const bool lm_ks = !rows_streams(c, qlm, flm, M, H) && ksplit_ok(c, M, V, H);
+  const WeightStream* slm = rows_stream(c, c->slm, M);
+  const bool lm_ks = !rows_streams(c, slm, M, H) && ksplit_ok(c, M, V, H);
   // 33-64 rows (round 3): four activation blocks; every RMSNorm-fused product takes its activations as 16-bit terms prepared once per product by the
   // row-wise launch that also adds the pending split-K residual (the RMSNorm-on-the-way staging runs out of registers at four blocks)
   // Batches of 3-32 rows prepare the QKV / lm_head activations as stored terms as well, so that the QKV product takes the LDS-DMA ring kernel.  From 5 rows instead
@@ -316,14 +311,13 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
     if (attn_terms) { o.asrc = 0; o.a_hi = c->ws_ah; o.a_lo = c->ws_al; o.a_f32 = nullptr; }
     const int os = launch_skinny(c, o);
     const bool gu_dma = c->skinny_dma && M > 16 && H % 64 == 0;     // 17+ rows: the LDS-DMA ring kernel on stored terms (16.8 vs 19.5 us at 32 rows)
-    const Fp8Mat* qgu = fp8_rows_mat(c, w.qgu, 1, M);
-    const Fp4Mat* fgu = fp4_rows_mat(c, w.fgu, 1, M);
-    const bool gu_q8 = rows_streams(c, qgu, fgu, M, H);
+    const WeightStream* sgu = rows_stream(c, w.sgu, M);
+    const bool gu_q8 = rows_streams(c, sgu, M, H);
     const bool gu_ks = !gu_dma && !gu_q8 && ksplit_ok(c, M, 2 * I, H);
     if (gu_ks) {     // {sum slabs, residual, RMSNorm, 16-bit terms} in one row-wise launch, then the barrier-free wide product
       launch_norm_terms(c, r.x, w.post_norm, M, H, os);
       launch_ksplit(c, tgx::GEMM_SILU, w.wgu, nullptr, 2 * I, M, 2 * I, H);
-      rows_fallback(c, qgu, fgu);
+      rows_fallback(c, sgu);
     } else if (c->skinny_terms || terms || gu_dma || gu_q8) {
       // 17-32 rows (round 3): {sum slabs, residual, RMSNorm, 16-bit terms} ONCE per layer in the row-wise launch that replaces reduce_rows; the panel
       // kernel then stages stored terms instead of normalising and splitting every 256-k panel in each of its 256 workgroups
@@ -331,19 +325,19 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
       SkinnyCall gu;
       gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 0; gu.a_hi = c->ws_ah; gu.a_lo = c->ws_al;
       gu.allow_split = false;      // gate_up stays unsplit: siluMul in its epilogue, one launch less
-      gu.q8 = qgu; gu.q4 = fgu;
+      gu.ws = sgu;
       launch_skinny(c, gu);
     } else {
     if (os > 1) launch_reduce_rows(c, tgx::GEMM_RESIDUAL, os, nullptr, r.x, H, M, H, ssq);
     else hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)r.x, (long long)H, H, ssq);
     SkinnyCall gu;
     gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 2; gu.a_f32 = r.x; gu.lda = H;
-    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = false; gu.q8 = qgu; gu.q4 = fgu;
+    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = false; gu.ws = sgu;
     launch_skinny(c, gu);                                                  // -> ws_hh / ws_hl: the down product's activation terms
     }
     SkinnyCall dn;
     dn.epi = tgx::GEMM_RESIDUAL; dn.W = w.wdown; dn.C = r.x; dn.ldc = H; dn.M = M; dn.N = H; dn.K = I; dn.nt = 2; dn.asrc = 0; dn.a_hi = c->ws_hh; dn.a_lo = c->ws_hl;
-    dn.q8 = fp8_rows_mat(c, w.qdown, 2, M); dn.q4 = fp4_rows_mat(c, w.fdown, 2, M);
+    dn.ws = rows_stream(c, w.sdown, M);
     const int ds = launch_skinny(c, dn);
     if (l + 1 == d.layers && (lm_ks || terms)) launch_norm_terms(c, r.x, c->final_norm, M, H, ds);      // the last residual goes straight into model.norm's terms
     else if (terms) pend = ds;                                                                         // the next layer's norm launch adds the slabs
@@ -352,13 +346,13 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
   }
   if (lm_ks) {
     launch_ksplit(c, tgx::GEMM_STORE, d.tied ? c->embed : c->lm_head, r.logits, V, M, V, H);
-    rows_fallback(c, qlm, flm);
+    rows_fallback(c, slm);
   } else {
   SkinnyCall lm;
   lm.epi = tgx::GEMM_STORE; lm.W = d.tied ? c->embed : c->lm_head; lm.C = r.logits; lm.ldc = V; lm.M = M; lm.N = V; lm.K = H; lm.nt = 2; lm.asrc = 2;
   lm.a_f32 = r.x; lm.lda = H; lm.norm_w = c->final_norm; lm.ssq_in = ssq; lm.allow_split = false;
   if (terms) { lm.asrc = 0; lm.a_hi = c->ws_ah; lm.a_lo = c->ws_al; lm.a_f32 = nullptr; lm.norm_w = nullptr; lm.ssq_in = nullptr; }
-  lm.q8 = qlm; lm.q4 = flm;
+  lm.ws = slm;
   launch_skinny(c, lm);
   }
   hipLaunchKernelGGL(tgx::argmax_partials_rows_kernel, dim3(std::min(c->lm_grid, std::max(1, (V / 4 + 255) / 256)), M), dim3(256), 0, c->stream, (const float*)r.logits, (long long)V, V, r.part_val, r.part_idx,
@@ -440,31 +434,30 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
     SkinnyCall o;
     o.epi = tgx::GEMM_RESIDUAL; o.W = w.wo; o.C = c->ws_x; o.ldc = H; o.M = M; o.N = H; o.K = qd; o.nt = 2; o.asrc = 0; o.a_hi = c->ws_ah; o.a_lo = c->ws_al;
     const int os = launch_skinny(c, o);
-    const Fp8Mat* qgu = fp8_rows_mat(c, w.qgu, 1, M);
-    const Fp4Mat* fgu = fp4_rows_mat(c, w.fgu, 1, M);
-    const bool gu_q8 = rows_streams(c, qgu, fgu, M, H);
+    const WeightStream* sgu = rows_stream(c, w.sgu, M);
+    const bool gu_q8 = rows_streams(c, sgu, M, H);
     if (!gu_q8 && ksplit_ok(c, M, 2 * I, H)) {       // prompts of <= 16 rows: as the batched decode step (the o_proj product has consumed ws_ah / ws_al by now)
       launch_norm_terms(c, c->ws_x, w.post_norm, M, H, os);
       launch_ksplit(c, tgx::GEMM_SILU, w.wgu, nullptr, 2 * I, M, 2 * I, H);
-      rows_fallback(c, qgu, fgu);
+      rows_fallback(c, sgu);
     } else if (terms || gu_q8) {
       launch_norm_terms(c, c->ws_x, w.post_norm, M, H, os);
       SkinnyCall gu;
       gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 0; gu.a_hi = c->ws_ah; gu.a_lo = c->ws_al;
       gu.allow_split = false;      // gate_up stays unsplit: siluMul in its epilogue, one launch less
-      gu.q8 = qgu; gu.q4 = fgu;
+      gu.ws = sgu;
       launch_skinny(c, gu);
     } else {
     if (os > 1) launch_reduce_rows(c, tgx::GEMM_RESIDUAL, os, nullptr, c->ws_x, H, M, H, ssq);
     else hipLaunchKernelGGL(tgx::row_ssq_kernel, dim3(M, tgx::SK_NCB), dim3(256), 0, c->stream, (const float*)c->ws_x, (long long)H, H, ssq);
     SkinnyCall gu;
     gu.epi = tgx::GEMM_SILU; gu.W = w.wgu; gu.M = M; gu.N = 2 * I; gu.K = H; gu.ldc = 2 * I; gu.nt = 2; gu.asrc = 2; gu.a_f32 = c->ws_x; gu.lda = H;
-    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = false; gu.q8 = qgu; gu.q4 = fgu;
+    gu.norm_w = w.post_norm; gu.ssq_in = ssq; gu.allow_split = false; gu.ws = sgu;
     launch_skinny(c, gu);
     }
     SkinnyCall dn;
     dn.epi = tgx::GEMM_RESIDUAL; dn.W = w.wdown; dn.C = c->ws_x; dn.ldc = H; dn.M = M; dn.N = H; dn.K = I; dn.nt = 2; dn.asrc = 0; dn.a_hi = c->ws_hh; dn.a_lo = c->ws_hl;
-    dn.q8 = fp8_rows_mat(c, w.qdown, 2, M); dn.q4 = fp4_rows_mat(c, w.fdown, 2, M);
+    dn.ws = rows_stream(c, w.sdown, M);
     const int ds = launch_skinny(c, dn);
     if (terms && l + 1 < d.layers) pend = ds;        // the next layer's norm launch adds the slabs
     else if (ds > 1) launch_reduce_rows(c, tgx::GEMM_RESIDUAL, ds, nullptr, c->ws_x, H, M, H, ssq);
@@ -483,14 +476,13 @@ void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, in
   const int H = d.hidden, V = d.vocab;
   const ebyte* W = d.tied ? c->embed : c->lm_head;
   launch_norm_terms(c, x ? x : c->ws_x, c->final_norm, M, H, 0);
-  const Fp8Mat* qlm = fp8_rows_mat(c, c->qlm, 4, M);
-  const Fp4Mat* flm = fp4_rows_mat(c, c->flm, 4, M);
-  if (!rows_streams(c, qlm, flm, M, H) && ksplit_ok(c, M, V, H)) {
+  const WeightStream* slm = rows_stream(c, c->slm, M);
+  if (!rows_streams(c, slm, M, H) && ksplit_ok(c, M, V, H)) {
     launch_ksplit(c, tgx::GEMM_STORE, W, logits, V, M, V, H);
-    rows_fallback(c, qlm, flm);
+    rows_fallback(c, slm);
   } else {
     SkinnyCall lm;
-    lm.epi = tgx::GEMM_STORE; lm.W = W; lm.C = logits; lm.ldc = V; lm.M = M; lm.N = V; lm.K = H; lm.nt = 2; lm.asrc = 0; lm.a_hi = c->ws_ah; lm.a_lo = c->ws_al; lm.allow_split = false; lm.q8 = qlm; lm.q4 = flm;
+    lm.epi = tgx::GEMM_STORE; lm.W = W; lm.C = logits; lm.ldc = V; lm.M = M; lm.N = V; lm.K = H; lm.nt = 2; lm.asrc = 0; lm.a_hi = c->ws_ah; lm.a_lo = c->ws_al; lm.allow_split = false; lm.ws = slm;
     launch_skinny(c, lm);
   }
   hipLaunchKernelGGL(tgx::argmax_partials_rows_kernel, dim3(std::min(c->lm_grid, std::max(1, (V / 4 + 255) / 256)), M), dim3(256), 0, c->stream, (const float*)logits, (long long)V, V, part_val, part_idx,
