@@ -32,7 +32,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 
 def _deps():
     deps = [os.path.join(HERE, "..", "include", "tgx.h"), os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "kv_pool.h"), os.path.join(CSRC, "dev_mem.h"), os.path.join(CSRC, "row_snapshot.h"),
-            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "verify_tree_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h"), os.path.join(CSRC, "stream_launch.h")]
+            os.path.join(CSRC, "splice_plan.h"), os.path.join(CSRC, "beam_plan.h"), os.path.join(CSRC, "prefix_groups.h"), os.path.join(CSRC, "verify_tree_plan.h"), os.path.join(CSRC, "attn_worklist.h"), os.path.join(CSRC, "automaton.h"), os.path.join(CSRC, "gemv_grid.h"), os.path.join(CSRC, "stream_launch.h")]
     kd =os.path.join(CSRC, "kernels")
     return deps + [os.path.join(kd, f) for f in sorted(os.listdir(kd))]
 
@@ -115,6 +115,13 @@ def build_beam_plan_check(force: bool = False, verbose: bool = False):
     if _stale(os.path.join(TEST_BUILD, "beam_plan_check"), [os.path.join(CSRC, "kv_pool.h")]):
         force = True
     return _build_cpu_check("beam_plan_check", os.path.join(CSRC, "beam_plan.h"), force, verbose)
+
+
+def build_prefix_groups_check(force: bool = False, verbose: bool = False):
+    """tests/prefix_groups_check.cpp, the CPU audit of csrc/prefix_groups.h (beside a KvPool)."""
+    if _stale(os.path.join(TEST_BUILD, "prefix_groups_check"), [os.path.join(CSRC, "kv_pool.h")]):
+        force = True
+    return _build_cpu_check("prefix_groups_check", os.path.join(CSRC, "prefix_groups.h"), force, verbose)
 
 
 def build_verify_tree_plan_check(force: bool = False, verbose: bool = False):

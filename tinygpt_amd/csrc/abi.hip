@@ -223,7 +223,7 @@ static void launch_decode_step(tgx_ctx* c, const tgx_sampler_cfg& cfg) {
     // rows per weight pass (option decode.step_rows: 32 or 64): batches beyond 32 rows take four activation blocks per skinny product (one pass over
     // the weights for up to 64 rows) instead of two passes of two blocks
     // (128 rows = eight blocks exist on the LDS-DMA ring kernel only: every product must then take stored terms, i.e. the attention a direct form that writes them)
-    const bool wide_ok = c->skinny_dma && c->skinny_dma_oproj >= 2 && c->attn_direct && c->dt != tgx::DT_F32;
+    const bool wide_ok = c->skinny_dma && c->skinny_dma_oproj >= 2 && (c->attn_direct || c->attn_prefix) && c->dt != tgx::DT_F32;      // (the shared-prefix form writes terms as the direct forms do)
     const int per = c->decode_step_rows > 64 && !wide_ok ? 64 : c->decode_step_rows;
     for (int row0 = 0; row0 < c->batch; row0 += per) launch_decode_step_mfma(c, row0, std::min(per, c->batch - row0), cfg);
     return;
@@ -280,7 +280,7 @@ static int ensure_step_graph(tgx_ctx* c, const tgx_sampler_cfg& cfg, bool want_m
   for (int i = 0; i < 6; i++) {
     const tgx_ctx::GraphSet& g = c->graph_cache[i];
     if (g.step && g.batch == c->batch && g.rows == c->row_union && (c->row_union >= 0 || same_cfg(g.cfg, cfg)) && g.direct == c->attn_direct && g.mfma == c->attn_mfma &&
-        g.nw4 == c->attn_nw4) { hit = i; break; }
+        g.nw4 == c->attn_nw4 && g.prefix == c->attn_prefix) { hit = i; break; }
     if (!g.step) victim = i;
     else if (c->graph_cache[victim].step && g.used < c->graph_cache[victim].used) victim = i;
   }
@@ -295,7 +295,7 @@ static int ensure_step_graph(tgx_ctx* c, const tgx_sampler_cfg& cfg, bool want_m
     }
     int rc = capture_steps(c, cfg, 1, &g.step);
     if (rc) { g = tgx_ctx::GraphSet{}; return rc; }
-    g.batch = c->batch; g.cfg = cfg; g.rows = c->row_union; g.direct = c->attn_direct; g.mfma = c->attn_mfma; g.nw4 = c->attn_nw4;
+    g.batch = c->batch; g.cfg = cfg; g.rows = c->row_union; g.direct = c->attn_direct; g.mfma = c->attn_mfma; g.nw4 = c->attn_nw4; g.prefix = c->attn_prefix;
     g.used = ++c->graph_clock;
     hit = victim;
   }
@@ -512,6 +512,39 @@ static int read_tok_log(tgx_ctx* c, int64_t start, int n, int* dst) {
   return TGX_OK;
 }
 
+// option attn.shared_prefix: the groups of this decode call (prefix_groups.h), planned from the pool's mirror after the call's blocks were assigned.  The table goes
+// to the device stream-ordered — behind the replays that read the previous one — and only when it differs from what the device holds.  c->attn_prefix: some group
+// exists (a mode of the captured step).  The form serves the batched matrix-core step when ONE pass over the weights holds the whole batch (the plan names batch rows)
+static int plan_prefix_groups(tgx_ctx* c) {
+  c->attn_prefix = false; c->last_prefix_groups = 0;
+  if (!c->shared_prefix || !attn_prefix_capable(c) || !decode_mfma_ok(c) || (c->debug_skip & 1)) return TGX_OK;
+  if (c->batch > c->decode_step_rows || (c->batch > 64 && !(c->skinny_dma && c->skinny_dma_oproj >= 2))) return TGX_OK;
+  const tgx_model_desc& d = c->d;
+  std::vector<prefix_groups::Row> st((size_t)c->batch);
+  for (int b = 0; b < c->batch; b++) { st[(size_t)b].past = c->row_host[(size_t)b].past; st[(size_t)b].live = !c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin; }
+  const prefix_groups::Plan plan = prefix_groups::make(c->kv, st.data(), c->batch, d.heads / d.kv_heads, c->shared_prefix, d.kv_heads, c->num_cus);
+  if (plan.groups.empty()) return TGX_OK;
+  // the tail range [nb * 128, pos] of a member is never empty: pos = past >= nb * 128 (the merge launch relies on it)
+  for (const prefix_groups::Group& g : plan.groups)
+    for (int k = 0; k < g.n_rows; k++)
+      if ((long long)g.nb * tgx::KV_BLOCK > c->row_host[(size_t)g.rows[k]].past || g.nb > c->kv.row_blocks(g.rows[k]) || g.nsplit < 1 || g.nsplit > prefix_groups::MAX_SPLITS)
+        return set_err(c, TGX_ERR_STATE, "internal: shared-prefix group of %d blocks does not fit row %d (past %lld)", g.nb, g.rows[k], (long long)c->row_host[(size_t)g.rows[k]].past);
+  const std::vector<int> table = prefix_groups::table(plan, d.max_batch);
+  if (!c->pfx_plan) {      // the device table starts as the all-zero table (no group), and so does its mirror
+    if (int rc = dev_alloc(c, &c->pfx_plan, table.size())) return rc;
+    HIP_OK(c, hipMemsetAsync(c->pfx_plan, 0, table.size() * 4, c->stream));      // (outside any capture: the plan is made before the graphs are chosen)
+    c->pfx_plan_host.assign(table.size(), 0);
+  }
+  if (!c->pfx_rec) { if (int rc = dev_alloc(c, &c->pfx_rec, (size_t)d.max_batch * d.heads * prefix_groups::MAX_SPLITS * (d.head_dim + 4))) return rc; }
+  // the entries that differ from what the device holds travel BY VALUE in the block tables' push launches (kv_tbl_push): no host buffer has to outlive the call
+  KvPool::Changes ch;
+  for (size_t i = 0; i < table.size(); i++)
+    if (table[i] != c->pfx_plan_host[i]) ch.emplace_back((int)i, table[i]);
+  if (!ch.empty()) { kv_tbl_push(c, ch, c->pfx_plan); c->pfx_plan_host = table; }
+  c->attn_prefix = true; c->last_prefix_groups = (int)plan.groups.size();
+  return TGX_OK;
+}
+
 // rows mode (c->row_union >= 0, tgx_decode_rows): every row samples with its own settings, `cfg` and `seed` are unused, finished rows take no blocks and stay
 // where they are, and the caller updates the rows' `past` from the device afterwards (rows may finish on the device)
 static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t seed, int n) {
@@ -528,6 +561,7 @@ static int run_decode_steps(tgx_ctx* c, const tgx_sampler_cfg& cfg, uint64_t see
     for (int b = 0; b < c->batch; b++)
       if (!c->row_host[(size_t)b].idle && !c->row_host[(size_t)b].fin) { int rc = kv_ensure_blocks(c, b, c->row_host[(size_t)b].past + n); if (rc) return rc; }
   }
+  if (int rc = plan_prefix_groups(c)) return rc;
   if (rows) {
     for (int b = 0; b < c->batch; b++) { note_sampled(c, b, 1, row_cfg(c, b)); c->row_host[(size_t)b].probs_proc = (c->row_union & ROWU_PROC) != 0; }      // (a processed step passes every row through the processed slab)
   } else if (int rc = ensure_seed(c, cfg, seed)) return rc;
@@ -3000,6 +3034,8 @@ int tgx_get_option(const tgx_ctx* c, const char* key, int* out_value) {
   if (!strcmp(key, "attn.direct_limit")) { *out_value = (int)std::min<long long>(direct_limit(c, c->batch, true), INT_MAX); return TGX_OK; }
   if (!strcmp(key, "attn.nw4_limit")) { *out_value = (int)nw4_limit(c, c->batch, true); return TGX_OK; }
   if (!strcmp(key, "graph.steps")) { *out_value = c->graph_steps; return TGX_OK; }
+  if (!strcmp(key, "attn.shared_prefix")) { *out_value = c->shared_prefix; return TGX_OK; }
+  if (!strcmp(key, "attn.last_prefix_groups")) { *out_value = c->last_prefix_groups; return TGX_OK; }      // read-only: the groups the last decode call ran with (0: option off, unpaged, nothing qualified)
   if (!strcmp(key, "act.round16")) { *out_value = c->act16; return TGX_OK; }
   if (!strcmp(key, "kv.budget_tokens")) { *out_value = c->kv_budget_tokens; return TGX_OK; }
   if (!strcmp(key, "extend.attn_splits")) { *out_value = c->extend_attn_splits; return TGX_OK; }
@@ -3057,6 +3093,10 @@ int tgx_set_option(tgx_ctx* c, const char* key, int value) {
   if (!strcmp(key, "attn.raw_fuse")) { drop_step_graphs(c); c->attn_raw_fuse = value; return TGX_OK; }
   if (!strcmp(key, "attn.batch_mfma")) { if (value < 0) return set_err(c, TGX_ERR_INVALID, "attn.batch_mfma is a row count (0 = off)"); drop_step_graphs(c); c->attn_batch_mfma = value; return TGX_OK; }
   if (!strcmp(key, "attn.mfma_min")) { c->attn_mfma_min = value; return TGX_OK; }
+  if (!strcmp(key, "attn.shared_prefix")) {      // tokens of whole blocks rows must share to be grouped (prefix_groups.h; the step graphs were dropped above)
+    if (value != 0 && value < tgx::KV_BLOCK) return set_err(c, TGX_ERR_INVALID, "attn.shared_prefix is 0 (off) or a token count >= %d", tgx::KV_BLOCK);
+    c->shared_prefix = value; return TGX_OK;
+  }
   if (!strcmp(key, "prefill.defer_reduce")) { c->defer_reduce = value != 0; return TGX_OK; }
   if (!strcmp(key, "skinny.dma")) { drop_step_graphs(c); c->skinny_dma = value != 0; return TGX_OK; }
   if (!strcmp(key, "skinny.dma_oproj")) { drop_step_graphs(c); c->skinny_dma_oproj = value; return TGX_OK; }

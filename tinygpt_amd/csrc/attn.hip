@@ -1,9 +1,10 @@
-// attn.hip — the decode attention launches of the MI355X shim (kernels/attn_decode.h, attn_decode_mfma.h): the form is chosen per decode call from the
+// attn.hip — the decode attention launches of the MI355X shim (kernels/attn_decode.h, attn_decode_mfma.h, attn_prefix.h): the form is chosen per decode call from the
 // context (direct / split + combine / matrix cores, update_attn_modes in abi.hip) and per launch from the batch rows.
 // == flashAttention(q, Kall, Vall) over keys [0, pos[row]]  (Attention.h:103-112)
 #include "ctx.h"
 #include "kernels/attn_decode.h"
 #include "kernels/attn_decode_mfma.h"
+#include "kernels/attn_prefix.h"
 
 // the direct-form attention of a batched step runs on the matrix cores from attn.batch_mfma rows (17) when a kv head serves 3+ query heads (the VALU form's
 // cost grows with the heads per workgroup, the MFMA form's does not: Qwen3-1.7B, 2 heads per kv head, B = 32 2.29 (VALU) vs 2.39 ms/step)
@@ -154,6 +155,28 @@ void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine) {
   TGX_DT_SWITCH(c->dt, if (c->d.head_dim == 64) launch_attn_g<DT, 64>(c, a, R, combine); else launch_attn_g<DT, 128>(c, a, R, combine))
 }
 
+// ---- the shared-prefix form of a batched step (option attn.shared_prefix; kernels/attn_prefix.h, csrc/prefix_groups.h)
+static_assert(tgx::PFX_QCOLS == prefix_groups::QCOLS && tgx::PFX_SPLITS == prefix_groups::MAX_SPLITS && tgx::PFX_GROUP_INTS == prefix_groups::GROUP_INTS && tgx::PFX_ROW_INTS == prefix_groups::ROW_INTS,
+              "the kernels read the planner's table");
+bool attn_prefix_capable(const tgx_ctx* c) {
+  return c->kv_paged && c->dt != tgx::DT_F32 && (c->d.head_dim == 64 || c->d.head_dim == 128) && c->d.heads % c->d.kv_heads == 0 && c->d.heads / c->d.kv_heads <= prefix_groups::GMAX;
+}
+template <int DT, int HD>
+static void launch_attn_prefix_t(tgx_ctx* c, const tgx::PrefixArgs& p, int R) {
+  constexpr size_t lds = tgx::attn_mfma_lds_bytes<HD, 4>();
+  // the grid is sized for the most groups and splits a plan can hold: the plan is data, workgroups beyond it exit
+  hipLaunchKernelGGL((tgx::attn_prefix_mfma_kernel<DT, HD>), dim3(p.kv_heads, tgx::PFX_SPLITS, c->d.max_batch / 2), dim3(256), lds, c->stream, p);
+  hipLaunchKernelGGL((tgx::attn_tail_merge_kernel<DT, HD>), dim3(p.kv_heads, R), dim3(256), lds, c->stream, p);
+}
+void launch_attn_prefix(tgx_ctx* c, const tgx::AttnArgs& a, int R) {
+  if (!attn_prefix_capable(c) || !c->pfx_plan || !c->pfx_rec || !a.blk_tbl) { c->launch_fault = "internal: the shared-prefix attention needs a paged 16-bit context and its plan"; return; }
+  tgx::PrefixArgs p{};
+  p.q = a.q; p.q_stride = a.q_stride; p.k_cache = a.k_cache; p.v_cache = a.v_cache; p.blk_tbl = a.blk_tbl; p.tbl_stride = a.tbl_stride;
+  p.plan = c->pfx_plan; p.rows_max = c->d.max_batch; p.rec = c->pfx_rec; p.pos = a.pos; p.out = a.out; p.out_hi = a.out_hi; p.out_lo = a.out_lo;
+  p.heads = a.heads; p.kv_heads = a.kv_heads; p.gfull = a.heads / a.kv_heads; p.act16 = a.act16; p.scale = a.scale;
+  TGX_DT16_SWITCH(c->dt, if (c->d.head_dim == 64) launch_attn_prefix_t<DT, 64>(c, p, R); else launch_attn_prefix_t<DT, 128>(c, p, R);)
+}
+
 // dynamic LDS sizes of the matrix-core forms
 template <bool P>
 static int attn_set_attrs_p(tgx_ctx* c) {
@@ -167,5 +190,11 @@ static int attn_set_attrs_p(tgx_ctx* c) {
 }
 int attn_set_attrs(tgx_ctx* c) {
   int rc = attn_set_attrs_p<false>(c);
-  return rc ? rc : attn_set_attrs_p<true>(c);
+  if (!rc) rc = attn_set_attrs_p<true>(c);
+  if (rc) return rc;
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefix_mfma_kernel<tgx::DT_BF16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tgx::attn_mfma_lds_bytes<128>()));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_prefix_mfma_kernel<tgx::DT_F16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tgx::attn_mfma_lds_bytes<128>()));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_tail_merge_kernel<tgx::DT_BF16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tgx::attn_mfma_lds_bytes<128>()));
+  HIP_OK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&tgx::attn_tail_merge_kernel<tgx::DT_F16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tgx::attn_mfma_lds_bytes<128>()));
+  return TGX_OK;
 }

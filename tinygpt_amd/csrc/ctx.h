@@ -1,11 +1,12 @@
 // ctx.h — the context of the MI355X shim (include/tgx.h) and the host-side launch interface shared by its translation units:
 //   abi.hip          C ABI entry points, weight upload, step graphs, decode loop, prompt admission (route, pass issuer, tgx_forward_row / tgx_forward_rows),
 //                    the device side of paged-KV block assignment (table pushes) and tgx_fork_row with its copy launch (kernels/kv_fork.h)
+//   prefix_groups.h  the planner of the shared-prefix decode attention (option attn.shared_prefix): rows that map the same leading blocks — host-only, checked on a CPU
 //   kv_pool.h        KvPool: the paged cache's block bookkeeping (free list, per-block row counts, the table's host mirror) — host-only, checked on a CPU
 //   row_snapshot.h   the byte format of a row snapshot (tgx_save_row / tgx_restore_row): header, size formula, validation — host-only, checked on a CPU
 //   dev_mem.h        DevMem: the owner of every device allocation of the context (dev_alloc / dev_free / dev_grow below) — host-only, checked on a CPU
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
-//   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h)
+//   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h, attn_prefix.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
 //   prefill.hip      batched MFMA prefill, 16-bit storage (kernels/prefill.h, gemm_dma.h); the device tables of a ragged pass; the launches of tgx_score_row (kernels/score.h)
 //                    and tgx_embed_rows (kernels/embed_pool.h) behind a pass
@@ -32,6 +33,7 @@
 #include "kernels/common.h"
 #include "kv_pool.h"
 #include "dev_mem.h"
+#include "prefix_groups.h"
 
 using tgx::bf16_t;
 typedef unsigned char ebyte;   // parameter / KV-cache storage in the compute dtype: offsets are elements * ctx.esz
@@ -250,7 +252,7 @@ struct tgx_ctx {
   // captured step graphs by (batch, sampler config, attention form): a generation that crosses an attention-form limit, or an engine that alternates between
   // sampler configurations / batch sizes, re-uses what it captured before instead of re-capturing (round 3; round 2 dropped the graphs at every change)
   // (per-row steps are keyed on the union of the rows' chains, not on cfg values: the kernels read every row's settings from row_req)
-  struct GraphSet { hipGraphExec_t step = nullptr, multi = nullptr; int batch = 0; tgx_sampler_cfg cfg{}; int rows = -1; bool direct = false, mfma = false, nw4 = false; unsigned long long used = 0; };
+  struct GraphSet { hipGraphExec_t step = nullptr, multi = nullptr; int batch = 0; tgx_sampler_cfg cfg{}; int rows = -1; bool direct = false, mfma = false, nw4 = false, prefix = false; unsigned long long used = 0; };
   GraphSet graph_cache[6];
   unsigned long long graph_clock = 0;
   int graph_cur = -1;
@@ -318,6 +320,15 @@ struct tgx_ctx {
   int defer_reduce = 1;            // split-K slabs of the prefill's N = hidden / QKV products are summed by the next row-wise kernel (option prefill.defer_reduce)
   int attn_mfma_min = -1;          // -1: the measured crossover of the geometry (attn_mfma_threshold); option attn.mfma_min overrides
   bool attn_mfma = false;
+  // ---- option attn.shared_prefix (default 0 = off; N >= 128: live rows of a batched step that map the same leading blocks for at least N tokens are grouped;
+  // prefix_groups.h, kernels/attn_prefix.h).  The plan of a decode call is made on the host before its graphs are chosen (plan_prefix_groups, abi.hip) and goes
+  // to pfx_plan, stream-ordered and by value (the entries that differ from the device's), when it differs from the one the device holds; attn_prefix = "some group exists" is a mode of the captured step, like attn_direct.
+  // attn.last_prefix_groups (read-only): the groups of the last decode call.  The buffers are allocated by the first call that finds a group
+  int shared_prefix = 0, last_prefix_groups = 0;
+  bool attn_prefix = false;
+  int* pfx_plan = nullptr;                   // device: prefix_groups::table
+  std::vector<int> pfx_plan_host;            // ... and what it holds
+  float* pfx_rec = nullptr;                  // [max_batch][heads][16][head_dim + 4] prefix records
   int debug_gemv = 0;        // experiment: GemvArgs.dbg = value & 15 for the kernel classes selected by bits 8.. (1 << (8 + class))
   int debug_skip = 0;        // experiment: bit0 skip attn decode kernel, bit1 skip combine (results invalid)
   int prof_same_layer = 0;   // experiment: tgx_profile_decode replays ONE layer's weights (Infinity-Cache resident)
@@ -534,6 +545,8 @@ size_t verify_args_bytes();                                // one entry of the a
 // ---- attn.hip (kernels/attn_decode.h, attn_decode_mfma.h)
 bool attn_batch_on_mfma(const tgx_ctx* c, int R);
 void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true);   // combine = false: the caller's o_proj merges the split records
+bool attn_prefix_capable(const tgx_ctx* c);                        // the context can run the shared-prefix form at all (paged, 16-bit storage, head_dim 64 / 128, <= 8 heads per kv head)
+void launch_attn_prefix(tgx_ctx* c, const tgx::AttnArgs& a, int R);   // the shared-prefix form of a batched step's attention (rows 0 .. R - 1; q in memory): prefix launch + tail / merge launch
 int attn_set_attrs(tgx_ctx* c);
 // ---- sampler.hip (kernels/sampler.h)
 void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool advance_pos, bool log_step, bool processed = false);   // processed: from the processed logits (launch_logit_proc ran for these rows)

@@ -16,6 +16,9 @@
 // Qwen2.5-0.5B 18.1 -> 14.4): the shim switches at those contexts (attn_mfma_threshold; option attn.mfma_min overrides;
 // profiles/r02_attn_long.txt).  Logits within 3e-5 of the VALU kernel, ids equal (tools/attn_long.py, tests).
 //
+// The main loop below (block loads, S^T, online softmax, P split, PV) exists a second time, without the look-ahead, as pfx_walk in attn_prefix.h (the shared-prefix
+// form): term order, rescale rule and V-tile layout are kept the same there — a change to one loop belongs in the other.
+//
 // Roofline: HBM — 2 * kv_heads * (T+1) * hd * 2 bytes per launch.  MFMA work: 2 x (QK^T + PV) x 32 / G of the useful flops — negligible.
 #pragma once
 #include "attn_decode.h"

@@ -277,10 +277,12 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
     const int qs = launch_skinny(c, q);
     // the QKV product's finish (slab sums + bias, q / k norm, RoPE, cache append) inside the attention launch when that is the batched matrix-core form
     // (option attn.raw_fuse): one launch per layer less
-    const bool raw_fuse = c->attn_raw_fuse && c->attn_direct && !(c->debug_skip & 1) && !(d.qk_norm && hd != 128) &&
+    // (option attn.shared_prefix with groups in this call: q must be in memory before the prefix launch — the un-fused finish below, then kernels/attn_prefix.h)
+    const bool prefix = c->attn_prefix;
+    const bool raw_fuse = !prefix && c->attn_raw_fuse && c->attn_direct && !(c->debug_skip & 1) && !(d.qk_norm && hd != 128) &&
                           (attn_batch_on_mfma(c, M) ? d.heads / d.kv_heads <= tgx::ATTN_RAW_GMAX : c->attn_raw_fuse >= 2);      // 2: the VALU direct forms as well
     // the direct-form attention of the step leaves its rows as 16-bit terms for the o_proj product (option skinny.dma_oproj: 1 = the matrix-core form only, 2 = every direct form)
-    const bool attn_terms = c->skinny_dma && c->skinny_dma_oproj && c->attn_direct && (c->skinny_dma_oproj >= 2 || attn_batch_on_mfma(c, M)) && !(c->debug_skip & 1) && qd % 64 == 0;
+    const bool attn_terms = c->skinny_dma && c->skinny_dma_oproj && (prefix || (c->attn_direct && (c->skinny_dma_oproj >= 2 || attn_batch_on_mfma(c, M)))) && !(c->debug_skip & 1) && qd % 64 == 0;
     if (!raw_fuse) {
       tgx::RopeRowsArgs a{};
       if (qs > 1) { a.part = c->ws_part; a.nsplit = qs; a.bias = w.bqkv; } else a.QKV = c->ws_out;
@@ -304,7 +306,8 @@ void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg&
         a.q_norm_w = d.qk_norm ? w.q_norm : nullptr; a.k_norm_w = d.qk_norm ? w.k_norm : nullptr;
       }
       if (attn_terms) { a.out_hi = c->ws_ah; a.out_lo = c->ws_al; }
-      launch_attn(c, a, M);
+      if (prefix) launch_attn_prefix(c, a, M);
+      else launch_attn(c, a, M);
     }
     SkinnyCall o;
     o.epi = tgx::GEMM_RESIDUAL; o.W = w.wo; o.C = r.x; o.ldc = H; o.M = M; o.N = H; o.K = qd; o.nt = 2; o.asrc = 1; o.a_f32 = r.attn; o.lda = qd;

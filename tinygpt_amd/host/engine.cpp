@@ -322,6 +322,25 @@ void GPTEngine::verifyProcessedEnd() {
   if (verifyProcessedOn_) be_.set_option(model_.ctx, "verify.processors", verifyProcessedWas_);
   verifyProcessedOn_ = false;
 }
+// GPTConfig::sharedPrefix: option attn.shared_prefix (include/tgx.h) held at the configured value for the length of a beam search, as verify.processors above.
+// false: the call fails with a message that names the key — a backend without the option calls, or one that refuses the value (1..127), is never passed over silently
+bool GPTEngine::sharedPrefixBegin() {
+  sharedPrefixOn_ = false;
+  if (config_.sharedPrefix == 0) return true;
+  int was = 0;
+  if (!be_.set_option || !be_.get_option) { fail("sharedPrefix: the device shim exports no tgx_set_option / tgx_get_option, so option attn.shared_prefix cannot be set"); return false; }
+  if (be_.get_option(model_.ctx, "attn.shared_prefix", &was) != TGX_OK || be_.set_option(model_.ctx, "attn.shared_prefix", config_.sharedPrefix) != TGX_OK) {
+    const char* why = be_.last_error(model_.ctx);
+    fail("sharedPrefix: the device shim refused option attn.shared_prefix = " + std::to_string(config_.sharedPrefix) + (why && *why ? std::string(": ") + why : std::string()));
+    return false;
+  }
+  sharedPrefixWas_ = was; sharedPrefixOn_ = true;
+  return true;
+}
+void GPTEngine::sharedPrefixEnd() {
+  if (sharedPrefixOn_) be_.set_option(model_.ctx, "attn.shared_prefix", sharedPrefixWas_);
+  sharedPrefixOn_ = false;
+}
 
 bool GPTEngine::speculateMore(std::vector<int32_t>& seq, int64_t maxTotal, bool& finished) {
   const int64_t past = (int64_t)seq.size() - 1, room = maxTotal - (int64_t)seq.size();      // room: tokens the call may still produce
@@ -611,7 +630,11 @@ std::vector<int64_t> GPTEngine::alignPrompts(const std::vector<std::vector<int32
 GPTOutput GPTEngine::generateSync(const std::vector<std::vector<int32_t>>& prompts, int32_t padToken) {
   GPTOutput out;
   if (!prepared_ || prompts.empty()) { fail("generateSync: engine not prepared or empty batch"); return out; }
-  if (config_.numBeams > 1) return beamsRefused(prompts.size()) ? out : generateBeams(prompts[0], padToken);
+  if (config_.numBeams > 1) {      // (the only loop of the engine whose rows are forked from one prompt: option attn.shared_prefix around it alone)
+    if (beamsRefused(prompts.size()) || !sharedPrefixBegin()) return out;
+    const auto sharedPrefixOff = at_exit([&] { sharedPrefixEnd(); });
+    return generateBeams(prompts[0], padToken);
+  }
   if (logprobsRefused(false) || processorsRefused(false)) return out;
   verifyProcessedBegin();
   const auto verifyProcessedOff = at_exit([&] { verifyProcessedEnd(); });

@@ -89,6 +89,11 @@ struct GPTConfig {       // src/engine/GPTEngine.h:25-32 (+ where to find the de
   // call and keeps drafting: the verify calls process every position of a pass as the row's step would have, so the ids are those of speculate = 0.  Under a
   // sampling configuration speculateSampled is needed as well; speculateTree falls back to chains (the device refuses a processed row on a tree that is no chain).
   bool speculateProcessed = false;
+  // shared-prefix decode attention (default 0 = off: every existing run is unchanged).  N >= 128 tokens: the engine sets option "attn.shared_prefix"
+  // (include/tgx.h) to N for the length of a beam search (numBeams > 1: the one loop whose rows are forked from one prompt) and restores what it was; a backend
+  // that lacks the option calls or refuses the value fails the generate call with a message.  INERT TODAY: the option groups rows of a PAGED cache only, and
+  // this engine creates unpaged contexts (nothing here sets "kv.budget_tokens"), so no group ever forms; the field is the hook for a paged host engine.
+  int sharedPrefix = 0;
   // ... with a token TREE of guesses (default 0 = off: every existing run is unchanged; 1 is the same as 0 — one branch is a chain).  B >= 2 (needs speculate > 0;
   // ONE sequence): where the sequence's tail has
   // occurred before with different continuations, up to B of them share the pass's `speculate` positions as branches below the current token (spec_draft.h
@@ -348,6 +353,9 @@ class GPTEngine {
   SpecStats spec_;
   bool verifyProcessedBegin();                                // GPTConfig::speculateProcessed: option verify.processors on for this call (false: the backend refused it)
   void verifyProcessedEnd();                                  // ... and back to what it was
+  bool sharedPrefixBegin();                                   // GPTConfig::sharedPrefix: option attn.shared_prefix set for a beam search (false: the backend refused it, the call has failed)
+  void sharedPrefixEnd();                                     // ... and back to what it was
+  bool sharedPrefixOn_ = false; int sharedPrefixWas_ = 0;
   bool verifyProcessedOn_ = false;                            // between the two: the verify calls take processed rows (spec_mode.h SpecInputs::verifyProcessed)
   int verifyProcessedWas_ = 0;
   bool treeRefused_ = false;                                  // GPTConfig::speculateTree: the device refused a tree as unsupported — chain drafts for the rest of the call

@@ -72,6 +72,8 @@ static void usage(const char* prog) {
           "  --speculate-sampled       with --speculate: verify drafts under a sampling configuration as well, with the row's own sampler (the ids of the plain loop)\n"
           "  --speculate-processed     with --speculate: keep drafting while --regex, a penalty or --logit-bias is on — every position of a verify pass is processed as its\n"
           "                            step would have been (the ids of the run without --speculate; with a sampling configuration --speculate-sampled as well)\n"
+          "  --shared-prefix <n>       with --num-beams: option attn.shared_prefix = n (n >= 128) around the beam search — blocks the beams share are attended once per\n"
+          "                            group.  INERT today: it needs a paged cache and this engine creates unpaged contexts (default: 0 = off)\n"
           "  --speculate-tree <b>      with --speculate, one prompt: where the text's tail has continued in different ways before, up to b of them share the pass's\n"
           "                            positions as branches of a token tree, and the device follows the one the model produces (b >= 2; default: 0 = off, 1 is the same: one branch is a chain)\n"
           "  --context-shift           generate past the context: a full row keeps its first --keep positions, drops half of the rest and slides the tail down, its keys\n"
@@ -179,6 +181,10 @@ int main(int argc, char** argv) {
     else if (a == "--speculate") cfg.speculate = atoi(next());
     else if (a == "--speculate-sampled") cfg.speculateSampled = true;
     else if (a == "--speculate-processed") cfg.speculateProcessed = true;
+    else if (a == "--shared-prefix") {
+      cfg.sharedPrefix = atoi(next());
+      if (cfg.sharedPrefix != 0 && cfg.sharedPrefix < 128) { fprintf(stderr, "Error: --shared-prefix is 0 (off) or a token count >= 128\n"); return 1; }
+    }
     else if (a == "--speculate-tree") cfg.speculateTree = atoi(next());
     else if (a == "--context-shift") cfg.contextShift = true;
     else if (a == "--keep") cfg.shiftKeep = std::max(0, atoi(next()));
