@@ -1,7 +1,8 @@
 // dev_mem_check.cpp — the CPU audit of tinygpt_amd/csrc/dev_mem.h (built and run by tests/test_dev_mem.py under the address and undefined-behaviour sanitizers).
-// DevMem is bound to a counting malloc / free pair that logs every call and can be told to fail; after every operation the harness compares live() / live_bytes()
+// DevMem is bound to a counting malloc / free pair that logs every call and can be told to refuse the k-th request from now; after every operation the harness compares live() / live_bytes()
 // and the allocator's outstanding count with a naive model (a map pointer -> bytes).  Two parts: a scripted case for each rule (grow's three, release(nullptr),
-// release_all), and a random run of alloc / release / grow over a few slots with injected failures.  Every buffer handed out is written over its whole length and
+// release_all, alloc_group served and refused at its first, a middle and its last member), and a random run of alloc / release / grow / alloc_group over a few
+// slots with injected failures.  Every buffer handed out is written over its whole length and
 // every buffer still live at the end is freed by release_all alone: a record that kept a dead pointer is a double free for AddressSanitizer, one that lost a live
 // pointer a leak for LeakSanitizer at exit.
 #include "../tinygpt_amd/csrc/dev_mem.h"
@@ -12,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <vector>
 
 #define REQUIRE(cond)                                                                              \
   do {                                                                                             \
@@ -20,14 +22,16 @@
 
 // ---- the bound allocator
 static long outstanding;        // mallocs not yet freed
-static bool fail_next;          // the next request fails (and clears the flag)
+static int fail_in;             // k > 0: the k-th request from now is refused (and the count is 0 again); 0: none
 static std::string calls;       // 'A' a request served, 'X' a request refused, 'F' a free — in order
+static std::vector<void*> ptrs; // ... and the pointer of each call (nullptr for an 'X')
 static void* counting_alloc(size_t bytes) {
-  if (fail_next) { fail_next = false; calls += 'X'; return nullptr; }
+  if (fail_in > 0 && --fail_in == 0) { calls += 'X'; ptrs.push_back(nullptr); return nullptr; }
   calls += 'A'; outstanding++;
-  return malloc(bytes);
+  ptrs.push_back(malloc(bytes));
+  return ptrs.back();
 }
-static void counting_free(void* p) { calls += 'F'; outstanding--; free(p); }
+static void counting_free(void* p) { calls += 'F'; ptrs.push_back(p); outstanding--; free(p); }
 
 struct Harness {
   DevMem m{counting_alloc, counting_free};
@@ -39,9 +43,9 @@ struct Harness {
   }
   // every operation: the rule's own postcondition, the model's update, the audit.  `fail`: the allocator refuses the request this operation makes, if it makes one
   void* alloc(size_t bytes, bool fail = false) {
-    fail_next = fail;
+    fail_in = fail ? 1 : 0;
     void* p = m.alloc(bytes);
-    fail_next = false;
+    fail_in = 0;
     REQUIRE((p == nullptr) == fail);
     if (p) { REQUIRE(!model.count(p)); memset(p, 0xA5, bytes); model[p] = bytes; }
     audit();
@@ -54,9 +58,9 @@ struct Harness {
   }
   bool grow(void** p, size_t* have, size_t need, bool fail = false) {
     void* const old = *p; const size_t had = *have, mark = calls.size();
-    fail_next = fail;
+    fail_in = fail ? 1 : 0;
     const bool ok = m.grow(p, have, need);
-    fail_next = false;
+    fail_in = 0;
     const std::string did = calls.substr(mark);
     if (need <= had) { REQUIRE(ok && *p == old && *have == had && did.empty()); audit(); return ok; }      // rule 1: nothing happens
     REQUIRE(did == (old ? (fail ? "FX" : "FA") : (fail ? "X" : "A")));      // rule 2: the old buffer goes BEFORE the new one is requested
@@ -64,6 +68,30 @@ struct Harness {
     REQUIRE(ok == !fail);
     if (ok) { REQUIRE(*p && *have == need && !model.count(*p)); memset(*p, 0x5A, need); model[*p] = need; }
     else REQUIRE(*p == nullptr && *have == 0);      // rule 3: the failure leaves nothing, and (the audit) the record does not hold the dead pointer
+    audit();
+    return ok;
+  }
+  // a group of n <= MAX_GROUP buffers into ps[0 .. n), all null on entry; refuse: the member (1 .. n) whose request the allocator refuses, 0: none
+  static constexpr int MAX_GROUP = 7;
+  bool group(void** ps, const size_t* bytes, int n, int refuse = 0) {
+    DevMem::Want g[MAX_GROUP];
+    for (int i = 0; i < n; i++) { REQUIRE(!ps[i]); g[i] = DevMem::Want{&ps[i], bytes[i]}; }
+    const size_t mark = calls.size(), live = m.live(), live_bytes = m.live_bytes();
+    fail_in = refuse;
+    const bool ok = m.alloc_group(g, (size_t)n);
+    fail_in = 0;
+    const std::string did = calls.substr(mark);
+    REQUIRE(ok == !refuse);
+    if (ok) {      // one request per member, in order, and nothing else
+      REQUIRE(did == std::string((size_t)n, 'A'));
+      for (int i = 0; i < n; i++) { REQUIRE(ps[i] == ptrs[mark + (size_t)i] && !model.count(ps[i])); memset(ps[i], 0xC3, bytes[i]); model[ps[i]] = bytes[i]; }
+    } else {       // members 1 .. k - 1 served, member k refused, then the k - 1 released newest first; nothing is left of the call
+      const size_t k = (size_t)refuse;
+      REQUIRE(did == std::string(k - 1, 'A') + "X" + std::string(k - 1, 'F'));
+      for (size_t j = 0; j + 1 < k; j++) REQUIRE(ptrs[mark + k + j] == ptrs[mark + k - 2 - j]);
+      for (int i = 0; i < n; i++) REQUIRE(ps[i] == nullptr);
+      REQUIRE(m.live() == live && m.live_bytes() == live_bytes);
+    }
     audit();
     return ok;
   }
@@ -97,6 +125,22 @@ static void scripted() {
   void* again = h.alloc(5);                            // the owner goes on working
   h.release(again);
   REQUIRE(outstanding == 0);
+  // alloc_group over groups of 1, 4 and 7 members, beside two older records: served; refused at the first, a middle and the last member, each time with a
+  // retry that is served
+  void* const old0 = h.alloc(11); void* const old1 = h.alloc(13);
+  const size_t bytes[Harness::MAX_GROUP] = {64, 1, 4096, 17, 300, 8, 1000};
+  for (int n : {1, 4, 7}) {
+    void* ps[Harness::MAX_GROUP] = {nullptr};
+    REQUIRE(h.group(ps, bytes, n) && h.m.live() == 2 + (size_t)n);
+    for (int i = 0; i < n; i++) { h.release(ps[i]); ps[i] = nullptr; }
+    for (int k : {1, (n + 1) / 2, n}) {
+      REQUIRE(!h.group(ps, bytes, n, k) && h.m.live() == 2 && h.m.live_bytes() == 24);
+      REQUIRE(h.group(ps, bytes, n));                  // the retry starts over: nothing was left to allocate over
+      for (int i = n - 1; i >= 0; i--) { h.release(ps[i]); ps[i] = nullptr; }
+    }
+  }
+  h.release(old0); h.release(old1);
+  REQUIRE(outstanding == 0);
 }
 
 // ---- the random run
@@ -104,8 +148,8 @@ static uint64_t rng_state;
 static uint32_t rnd() { rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(rng_state >> 33); }
 static int rnd_in(int lo, int hi) { return lo + (int)(rnd() % (uint32_t)(hi - lo + 1)); }      // [lo, hi]
 
-enum Kind { ALLOC, ALLOC_FAIL, RELEASE, RELEASE_NULL, GROW_NOOP, GROW, GROW_FAIL, RELEASE_ALL, N_KINDS };
-static const char* kind_name[N_KINDS] = {"alloc", "alloc refused", "release", "release(nullptr)", "grow, need <= have", "grow", "grow refused", "release_all"};
+enum Kind { ALLOC, ALLOC_FAIL, RELEASE, RELEASE_NULL, GROW_NOOP, GROW, GROW_FAIL, GROUP, GROUP_FAIL, RELEASE_ALL, N_KINDS };
+static const char* kind_name[N_KINDS] = {"alloc", "alloc refused", "release", "release(nullptr)", "grow, need <= have", "grow", "grow refused", "group", "group refused", "release_all"};
 static long done[N_KINDS];
 
 static void random_run(uint64_t seed, int n_ops) {
@@ -113,6 +157,8 @@ static void random_run(uint64_t seed, int n_ops) {
   rng_state = seed;
   Harness h;
   struct Slot { void* p = nullptr; size_t have = 0; } slot[SLOTS];
+  const int GROUPS = 4;
+  struct Group { void* p[Harness::MAX_GROUP] = {nullptr}; int n = 0; } group[GROUPS];      // n > 0: live
   for (int op = 0; op < n_ops; op++) {
     Slot& s = slot[rnd_in(0, SLOTS - 1)];
     const int dice = rnd_in(0, 99);
@@ -127,6 +173,18 @@ static void random_run(uint64_t seed, int n_ops) {
       done[s.p ? RELEASE : RELEASE_NULL]++;
       h.release(s.p);
       s = Slot{};
+    } else if (dice < 67) {      // ---- a first-use group of 1 .. 7 buffers (dev_alloc_group), a quarter of them refused at a random member; a live one is freed member by member
+      Group& g = group[rnd_in(0, GROUPS - 1)];
+      if (g.n) {
+        for (int i = 0; i < g.n; i++) { done[RELEASE]++; h.release(g.p[i]); }
+        g = Group{};
+        continue;
+      }
+      size_t bytes[Harness::MAX_GROUP];
+      const int n = rnd_in(1, Harness::MAX_GROUP), refuse = rnd_in(0, 3) == 0 ? rnd_in(1, n) : 0;
+      for (int i = 0; i < n; i++) bytes[i] = (size_t)rnd_in(1, 5000);
+      if (h.group(g.p, bytes, n, refuse)) g.n = n;
+      done[refuse ? GROUP_FAIL : GROUP]++;
     } else if (dice < 99) {      // ---- a workspace that grows on demand; a third of the requests fit what it has
       const size_t need = rnd_in(0, 2) == 0 ? (size_t)rnd_in(0, (int)s.have) : s.have + (size_t)rnd_in(1, 3000);
       const bool noop = need <= s.have, ok = h.grow(&s.p, &s.have, need, fail);
@@ -135,6 +193,7 @@ static void random_run(uint64_t seed, int n_ops) {
       done[RELEASE_ALL]++;
       h.release_all();
       for (Slot& t : slot) t = Slot{};
+      for (Group& g : group) g = Group{};
     }
   }
   h.release_all();

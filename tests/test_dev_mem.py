@@ -1,6 +1,6 @@
 """The owner of a context's device allocations (tinygpt_amd/csrc/dev_mem.h) without a GPU: tests/dev_mem_check.cpp, a stand-alone program, binds it to a counting
-malloc / free pair under the address and undefined-behaviour sanitizers — a scripted case for each rule of grow, release(nullptr), release_all, and a random run
-of alloc / release / grow with injected allocation failures against a naive model.  LeakSanitizer at exit is part of the verdict."""
+malloc / free pair under the address and undefined-behaviour sanitizers — a scripted case for each rule of grow, release(nullptr), release_all and alloc_group (served, and refused
+at its first, a middle and its last member), and a random run of alloc / release / grow / alloc_group with injected allocation failures against a naive model.  LeakSanitizer at exit is part of the verdict."""
 import subprocess
 
 from tinygpt_amd import build

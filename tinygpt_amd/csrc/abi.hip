@@ -643,38 +643,34 @@ static int launch_route(tgx_ctx* c, PrefillRoute rt, int M, int row0, int NB, in
   return TGX_OK;
 }
 
-// tgx_verify_row: the logits and argmax partials of ALL M positions of a one-row pass into the vf_* workspace.  The skinny route's final residual rows (ws_x) go
-// through the batched step's one-pass lm_head; every other route stages its hidden rows in vf_x (the matrix-core routes' ws_x here, prefill by steps chunk by chunk)
-// and runs the GEMV lm_head four rows per pass over the weights (a group of three rides as four: vf_x holds VERIFY_ROWS rows, the fourth's results are not read)
+// The logits and argmax partials of ALL M positions of a pass into workspace w (default: a one-row pass into the one-row workspace; tgx_verify_rows' joint pass: the
+// M <= VERIFY_POSITIONS positions of all its rows into the joint one).  The skinny route's final residual rows (ws_x) go through the batched step's one-pass
+// lm_head; every other route stages its hidden rows in w.raw.x (the matrix-core routes' ws_x here, prefill by steps chunk by chunk) and runs the GEMV lm_head four
+// rows per pass over the weights (a group of three rides as four: the slab holds a multiple of four rows, the fourth's results are not read)
 // (src: the M hidden rows of a matrix-core route, default the first M of ws_x — a scoring pass feeds it one group of positions at a time)
-// (joint: tgx_verify_rows' joint pass — the M <= VERIFY_POSITIONS positions of all its rows into the vj_* workspace, the same two forms)
-static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M, float* src = nullptr, bool joint = false) {
-  const size_t H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
-  float* const x = joint ? c->vj_x : c->vf_x;
-  float* const logits = joint ? c->vj_logits : c->vf_logits;
-  float* const part_val = joint ? c->vj_part_val : c->vf_part_val;
-  int* const part_idx = joint ? c->vj_part_idx : c->vf_part_idx;
-  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, logits, part_val, part_idx, src); return; }
-  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(x, src ? src : c->ws_x, (size_t)M * H * 4, hipMemcpyDeviceToDevice, c->stream);
+static void launch_lm_head_all(tgx_ctx* c, PrefillRoute rt, int M, float* src = nullptr, const VerifyWs* w = nullptr) {
+  const PosSlab& raw = (w ? w : &c->verify_ws[VWS_ROW])->raw;
+  if (rt == ROUTE_SKINNY) { launch_lm_head_skinny(c, M, raw, src); return; }
+  if (rt != ROUTE_STEPS) (void)hipMemcpyAsync(raw.x, src ? src : c->ws_x, (size_t)M * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
   for (int m0 = 0; m0 < M;) {
     const int rem = M - m0, R = rem >= 3 ? 4 : rem;
-    launch_lm_head_at(c, x + m0 * H, logits + m0 * V, part_val + m0 * P, part_idx + m0 * P, R);
+    launch_lm_head_at(c, raw, (size_t)m0, R);
     m0 += R;
   }
 }
 
-// tgx_score_row on the routes without the matrix-core form: the R <= VERIFY_ROWS positions from g0 through the verify form's lm_head into the vf_* workspace
-// (hidden: their rows of ws_x; nullptr: staged in vf_x already, prefill by steps), then the tile and record launches of kernels/score.h over it
+// tgx_score_row on the routes without the matrix-core form: the R <= VERIFY_ROWS positions from g0 through the verify form's lm_head into the one-row workspace
+// (hidden: their rows of ws_x; nullptr: staged in its raw.x already, prefill by steps), then the tile and record launches of kernels/score.h over it
 static void launch_score_group(tgx_ctx* c, PrefillRoute rt, const ScoreCall& sc, int g0, int R, float* hidden) {
-  c->vf_pass_rows = 0;                     // the workspace no longer holds a verify pass (tgx_read_pass_logits)
+  c->pass = {};                            // the workspace no longer holds a verify pass (tgx_read_pass_logits)
   launch_lm_head_all(c, rt, R, hidden);
-  launch_score_tiles(c, sc, c->vf_logits, c->d.vocab, 0, c->d.vocab, R, g0);
+  launch_score_tiles(c, sc, c->verify_ws[VWS_ROW].raw.logits, c->d.vocab, 0, c->d.vocab, R, g0);
   launch_score_record(c, sc, R, g0);
 }
 
 // One pass of nb rows [row0, row0 + nb) over positions past .. past + seq - 1 of each (their ids are in rows[].prompt, their blocks assigned); leaves every row's
 // logits and advances its position word.  `past` is an argument: tgx_forward passes the batch's pastLength, an admission 0 whatever the other rows hold.
-// verify (tgx_verify_row, nb == 1): the same pass, but the logits of EVERY position land in the vf_* workspace (launch_lm_head_all) and neither the row's logits
+// verify (tgx_verify_row, nb == 1): the same pass, but the logits of EVERY position land in the one-row workspace (launch_lm_head_all) and neither the row's logits
 // slot nor its position word moves — the accept launch behind the pass writes both
 // sc (tgx_score_row, nb == 1): the plain pass, and behind it every position's score — the matrix-core form over ws_x on ROUTE_TILED (prefill.hip
 // launch_score_tiled), groups of VERIFY_ROWS positions on every other route (prefill by steps scores each group as its chunks complete)
@@ -714,13 +710,13 @@ static int issue_pass(tgx_ctx* c, int row0, int nb, int seq, int past, bool veri
       launch_layers(c, c->chunk, R, 0);
       s0 += R;
       if (verify) {                                      // every position's hidden state feeds lm_head
-        (void)hipMemcpyAsync(c->vf_x + (size_t)(s0 - R) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(c->verify_ws[VWS_ROW].raw.x + (size_t)(s0 - R) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
         if (s0 == seq) launch_lm_head_all(c, rt, seq);
         continue;
       }
       if (sc) {                                          // the chunk's hidden rows into their group's slots; a complete group (chunks of four: its boundary is a chunk's) is scored at once
         const int g0 = (s0 - R) / SG * SG;
-        (void)hipMemcpyAsync(c->vf_x + (size_t)(s0 - R - g0) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(c->verify_ws[VWS_ROW].raw.x + (size_t)(s0 - R - g0) * c->d.hidden, c->ch_x, (size_t)R * c->d.hidden * 4, hipMemcpyDeviceToDevice, c->stream);
         if ((s0 % SG == 0 || s0 == seq) && g0 < sc->n_score) launch_score_group(c, rt, *sc, g0, std::min(s0, sc->n_score) - g0, nullptr);
       }
       if (em) {                                          // the chunk's pooled positions into the staging slice; a slice that is complete, or the text's last, is summed
@@ -1198,7 +1194,7 @@ int tgx_reset_cache(tgx_ctx* c) {
   if (c->proc_hist) HIP_OK(c, hipMemsetAsync(c->proc_hist, 0, (size_t)c->d.max_batch * c->d.vocab * sizeof(unsigned int), c->stream));
   if (int rc = vs_rezero(c)) return rc;      // (a sampled verify pass that failed half-way may have left its histograms)
   HIP_OK(c, hipStreamSynchronize(c->stream));
-  c->vf_pass_rows = 0;
+  c->pass = {};
   c->past = 0;
   for (RowHost& r : c->row_host) { r.restart(0, /*idle=*/false, /*fin=*/0); r.lp_count = 0; r.auto_id = -1; }
   c->have_logits = c->have_token = false;
@@ -1291,20 +1287,23 @@ static int check_target_rows(tgx_ctx* c, int n, const int32_t* rows, const int32
 // may_join (tgx_forward_rows): consecutive whole prompts share ONE ragged prefill pass per group of <= max(8192, longest) workspace rows where a matrix-core route
 // takes the group's rows; every other prompt, and every prompt of tgx_forward_row, runs issue_pass's one-row pass.  Only a call with a ragged pass uploads tables
 // (one buffer, ONE upload: per group the tables of ragged_tables, then the call's ids) and holds the four lm_head staging rows.
-// the vf_* workspace: every position's logits of a one-row verify pass (tgx_verify_row), at first use; the group form of tgx_score_row holds it as well
-static int ensure_verify_ws(tgx_ctx* c) {
-  if (c->vf_rec) return TGX_OK;
-  const size_t R = tgx_ctx::VERIFY_ROWS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
-  int rc;
-  if ((rc = dev_alloc(c, &c->vf_x, R * H)) || (rc = dev_alloc(c, &c->vf_logits, R * V)) || (rc = dev_alloc(c, &c->vf_part_val, R * P)) || (rc = dev_alloc(c, &c->vf_part_idx, R * P))) return rc;
-  HIP_OK(c, hipMemset(c->vf_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
-  return dev_alloc(c, &c->vf_rec, sizeof(tgx::VerifyRecord) / 4);
+// a verify workspace (ctx.h VerifyWs) without its processed slab, at first use: the one-row one by the first one-row verify call or group-form tgx_score_row, the
+// joint one — with the sampled rows' draws and the accept launch's argument table — by the first joint call that has a STEP
+static int ensure_verify_ws(tgx_ctx* c, VerifyWs& w) {
+  if (w.ready()) return TGX_OK;
+  const size_t R = (size_t)w.slots, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid, B = (size_t)c->d.max_batch;
+  const DevMem::Want x = dev_buf(&w.raw.x, R * H), lg = dev_buf(&w.raw.logits, R * V), pv = dev_buf(&w.raw.part_val, R * P), pi = dev_buf(&w.raw.part_idx, R * P);
+  const bool joint = &w == &c->verify_ws[VWS_JOINT];
+  if (int rc = joint ? dev_alloc_group(c, {x, lg, pv, pi, dev_buf(&w.draws, R), dev_buf(&w.rec, B * (sizeof(tgx::VerifyRecord) / 4)), dev_buf(&w.args, B * verify_args_bytes())})
+                     : dev_alloc_group(c, {x, lg, pv, pi, dev_buf(&w.rec, sizeof(tgx::VerifyRecord) / 4)})) return rc;
+  HIP_OK(c, hipMemset(w.raw.x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
+  return TGX_OK;
 }
 // tgx_score_row: the workspace of a scoring pass of seq positions on route rt, before the pass is issued; the read-back of its scores, behind it
 static int score_prepare(tgx_ctx* c, ScoreCall* sc, PrefillRoute rt, int row) {
   sc->ids = c->rows[(size_t)row].prompt;
   if (sc->n_score < 1) return TGX_OK;
-  if (rt != ROUTE_TILED) if (int rc = ensure_verify_ws(c)) return rc;
+  if (rt != ROUTE_TILED) if (int rc = ensure_verify_ws(c, c->verify_ws[VWS_ROW])) return rc;
   return ensure_score_ws(c, sc->n_score + 1, rt == ROUTE_TILED);
 }
 static int score_read_back(tgx_ctx* c, const ScoreCall* sc) {
@@ -1315,11 +1314,10 @@ static int score_read_back(tgx_ctx* c, const ScoreCall* sc) {
 
 // the four lm_head staging rows of a ragged pass, at first use
 static int ensure_rg_lm_ws(tgx_ctx* c) {
-  if (c->rg_x) return TGX_OK;
+  PosSlab& s = c->rg_lm;
+  if (s.ready()) return TGX_OK;
   const size_t V = (size_t)c->d.vocab, H = (size_t)c->d.hidden, P = (size_t)c->lm_grid;
-  int rc;
-  if ((rc = dev_alloc(c, &c->rg_x, 4 * H)) || (rc = dev_alloc(c, &c->rg_logits, 4 * V)) || (rc = dev_alloc(c, &c->rg_part_val, 4 * P)) || (rc = dev_alloc(c, &c->rg_part_idx, 4 * P))) return rc;
-  return TGX_OK;
+  return dev_alloc_group(c, {dev_buf(&s.x, 4 * H), dev_buf(&s.logits, 4 * V), dev_buf(&s.part_val, 4 * P), dev_buf(&s.part_idx, 4 * P)});
 }
 // lm_head of the batch rows rws[] whose hidden rows a ragged pass left (tgx_forward_rows, tgx_advance_rows' FEED rows): four at a time (tgx_forward's grouping where
 // they are consecutive rows; else gathered into staging rows and scattered back)
@@ -1334,13 +1332,13 @@ static void launch_lm_head_rows(tgx_ctx* c, const std::vector<int>& rws) {
       launch_lm_head(c, rws[k], R);
     } else {
       for (int j = 0; j < R; j++)
-        (void)hipMemcpyAsync(c->rg_x + j * H, c->rows[(size_t)rws[k + std::min<size_t>(j, real - 1)]].x, H * 4, hipMemcpyDeviceToDevice, c->stream);
-      launch_lm_head_at(c, c->rg_x, c->rg_logits, c->rg_part_val, c->rg_part_idx, R);
+        (void)hipMemcpyAsync(c->rg_lm.x + j * H, c->rows[(size_t)rws[k + std::min<size_t>(j, real - 1)]].x, H * 4, hipMemcpyDeviceToDevice, c->stream);
+      launch_lm_head_at(c, c->rg_lm, 0, R);
       for (size_t j = 0; j < real; j++) {
         RowState& r = c->rows[(size_t)rws[k + j]];
-        (void)hipMemcpyAsync(r.logits, c->rg_logits + j * V, V * 4, hipMemcpyDeviceToDevice, c->stream);
-        (void)hipMemcpyAsync(r.part_val, c->rg_part_val + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
-        (void)hipMemcpyAsync(r.part_idx, c->rg_part_idx + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.logits, c->rg_lm.logits + j * V, V * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.part_val, c->rg_lm.part_val + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
+        (void)hipMemcpyAsync(r.part_idx, c->rg_lm.part_idx + j * P, P * 4, hipMemcpyDeviceToDevice, c->stream);
       }
     }
     k += real;
@@ -2059,12 +2057,14 @@ static int verify_row_run(tgx_ctx* c, ContPass& cp, int j, const char* fn, int64
   const bool sampled = cp.smp[(size_t)j];
   static_assert((int)tgx_ctx::VERIFY_ROWS == tgx::VERIFY_MAX_POS, "kernels/verify.h VerifyRecord");
   HIP_OK(c, hipSetDevice(c->device));
-  if (int rc = ensure_verify_ws(c)) return rc;
+  VerifyWs& w = c->verify_ws[VWS_ROW];
+  const VerifySlice sl{&w, 0, 0};
+  if (int rc = ensure_verify_ws(c, w)) return rc;
   if (sampled) if (int rc = vs_alloc(c)) return rc;      // the positions' sampler workspace: only a sampled row's call ever holds it
   const bool processed = cp.prc[(size_t)j];
-  if (processed) if (int rc = ensure_verify_proc_ws(c, /*joint=*/false)) return rc;      // ... and the processed slab: only a processed row's call
+  if (processed) if (int rc = ensure_verify_proc_ws(c, w)) return rc;      // ... and the processed slab: only a processed row's call
   if (int rc = ensure_extend_ws(c, M, past)) return rc;
-  c->vf_pass_rows = 0;                             // the workspace changes hands
+  c->pass = {};                                    // the workspace changes hands
   (void)kv_ensure_blocks(c, row, (long long)past + M);      // the whole pass up front; cannot fail: counted above
   long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the draft; input 0 is written on the device from the row's token word
   for (int i = 0; i + 1 < M; i++) ids[i + 1] = cp.ids[(size_t)j][i];
@@ -2073,15 +2073,15 @@ static int verify_row_run(tgx_ctx* c, ContPass& cp, int j, const char* fn, int64
   if (int rc = issue_pass(c, row, 1, M, past, /*verify=*/true)) return rc;
   if (processed) {      // every position as its step would have processed it (kernels/logit_proc.h): the automaton walk, then the positions launch
     const int first = 0; const char on = 1; const long long* const in = c->rows[(size_t)row].prompt;
-    launch_logit_proc_positions(c, 1, &row, &first, &M, &in, &on, /*joint=*/false);
+    launch_logit_proc_positions(c, w, 1, &row, &first, &M, &in, &on);
   }
-  if (sampled) launch_sample_positions(c, row, M, cp.cfg[(size_t)j], -1, nullptr, processed);      // every position's draw under the row's settings, with the key its step would use
-  launch_verify_accept(c, row, M, sampled ? c->vs_draws : nullptr, processed);      // (a processed row: the commit of its history and state rides behind the walk)
-  if (row_records(c, row)) launch_logprobs_verify(c, row, M);      // one record per produced token, each from the logits of the position that produced it
-  HIP_OK(c, hipMemcpyAsync(&cp.rec[(size_t)j], c->vf_rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  if (sampled) launch_sample_positions(c, sl, row, M, cp.cfg[(size_t)j], nullptr, processed);      // every position's draw under the row's settings, with the key its step would use
+  launch_verify_accept(c, row, M, sampled, processed);      // (a processed row: the commit of its history and state rides behind the walk)
+  if (row_records(c, row)) launch_logprobs_verify(c, sl, row, M);      // one record per produced token, each from the logits of the position that produced it
+  HIP_OK(c, hipMemcpyAsync(&cp.rec[(size_t)j], w.rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
   if (int rc = finish_pass(c)) return rc;
   if (int rc = follow_step_rows(c, cp, j, j + 1, fn, out_ids, out_n, out_finish)) return rc;
-  c->vf_pass_rows = M; c->vf_pass_joint = false;
+  c->pass = {&w, M};
   refresh_have_probs(c);
   refresh_longest(c);
   c->have_logits = true;
@@ -2153,12 +2153,13 @@ int tgx_verify_tree(tgx_ctx* c, int row, const int64_t* tokens, const int32_t* p
   // ---- the pass
   const bool sampled = cp.smp[0];
   HIP_OK(c, hipSetDevice(c->device));
-  if (int rc = ensure_verify_ws(c)) return rc;
+  VerifyWs& w = c->verify_ws[VWS_ROW];
+  if (int rc = ensure_verify_ws(c, w)) return rc;
   if (!c->vt_tab) if (int rc = dev_alloc(c, &c->vt_tab, (size_t)tgx_ctx::VT_INTS)) return rc;
   if (sampled) if (int rc = vs_alloc(c)) return rc;
   if (int rc = ensure_extend_ws(c, M, past)) return rc;
   if (int rc = ensure_skinny_ws(c, M)) return rc;
-  c->vf_pass_rows = 0;                             // the workspace changes hands
+  c->pass = {};                                    // the workspace changes hands
   (void)kv_ensure_blocks(c, row, (long long)past + M);      // the whole pass up front; cannot fail: counted above
   long long ids[tgx_ctx::VERIFY_ROWS] = {0};       // inputs 1 .. M - 1 = the nodes; input 0 is written on the device from the row's token word
   int tab[tgx_ctx::VT_INTS] = {0};                 // (both live until finish_pass has synchronised)
@@ -2174,13 +2175,13 @@ int tgx_verify_tree(tgx_ctx* c, int row, const int64_t* tokens, const int32_t* p
   TreePass tree{c->vt_tab + tgx_ctx::VT_DEPTH, reinterpret_cast<const unsigned short*>(c->vt_tab + tgx_ctx::VT_ANC)};
   launch_prefill_skinny(c, row, 1, M, past, nullptr, &tree);
   launch_lm_head_all(c, ROUTE_SKINNY, M);
-  if (sampled) launch_sample_positions(c, row, M, cp.cfg[0], -1, tree.depth);      // every position's draw, with the key of the token its DEPTH produces
-  launch_verify_accept_tree(c, row, M, sampled ? c->vs_draws : nullptr);
+  if (sampled) launch_sample_positions(c, {&w, 0, 0}, row, M, cp.cfg[0], tree.depth);      // every position's draw, with the key of the token its DEPTH produces
+  launch_verify_accept_tree(c, row, M, sampled);
   launch_kv_tree_compact(c, row, M, past);
-  HIP_OK(c, hipMemcpyAsync(&cp.rec[0], c->vf_rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(c, hipMemcpyAsync(&cp.rec[0], w.rec, sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
   if (int rc = finish_pass(c)) return rc;
   if (int rc = follow_step_rows(c, cp, 0, 1, fn, out_ids, out_n, out_finish)) return rc;
-  c->vf_pass_rows = M; c->vf_pass_joint = false;
+  c->pass = {&w, M};
   refresh_have_probs(c);
   refresh_longest(c);
   c->have_logits = true;
@@ -2192,17 +2193,7 @@ int tgx_verify_tree(tgx_ctx* c, int row, const int64_t* tokens, const int32_t* p
 // its `past` (RaggedPass.past) — on the skinny or tiled route rt.  Sequence j's ids stand at workspace rows [first_j, first_j + lens_j) and go into its row's cache
 // from past_j; a STEP sequence's row 0 is the row's current token, written on the device.  Behind the pass: the STEP sequences' tail (step_tail), tgx_forward_rows'
 // lm_head for the FEED rows' last positions (launch_lm_head_rows; FEED_MORE rows: none), ONE read-back of the records.
-// The vj_* workspace of the STEP positions: hidden rows, logits and argmax partials per position, the sampled rows' draws, one record per row and the accept
-// launch's argument table; sized by the first call that has a STEP
-static int ensure_verify_rows_ws(tgx_ctx* c) {
-  if (c->vj_args) return TGX_OK;      // the last of them
-  const size_t R = tgx_ctx::VERIFY_POSITIONS, H = (size_t)c->d.hidden, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid, B = (size_t)c->d.max_batch;
-  int rc;
-  if ((rc = dev_alloc(c, &c->vj_x, R * H)) || (rc = dev_alloc(c, &c->vj_logits, R * V)) || (rc = dev_alloc(c, &c->vj_part_val, R * P)) || (rc = dev_alloc(c, &c->vj_part_idx, R * P)) ||
-      (rc = dev_alloc(c, &c->vj_draws, R)) || (rc = dev_alloc(c, &c->vj_rec, B * (sizeof(tgx::VerifyRecord) / 4)))) return rc;
-  HIP_OK(c, hipMemset(c->vj_x, 0, R * H * 4));      // (a group of three positions rides as four through lm_head: the fourth row is read)
-  return dev_alloc(c, &c->vj_args, B * verify_args_bytes());
-}
+// The STEP positions live in the joint workspace (ensure_verify_ws), sized by the first call that has a STEP.
 // The call's buffer: the pass's tables, then its ids — ONE upload.  tables(host, dev): ragged_tables, or advance_tables with its target; (nullptr, nullptr) sizes
 // them.  Grows rg_buf, fills `host` (it lives until finish_pass has synchronised) and scatters the caller's ids behind each sequence's first slot (input 0 of a STEP
 // sequence is written on the device from the row's token word); *o_ids: where the ids stand in the buffer
@@ -2219,22 +2210,23 @@ static int call_buffer(tgx_ctx* c, const ContPass& cp, const RaggedPass& p, cons
   }
   return TGX_OK;
 }
-// The STEP tail behind a joint pass: lm_head of the Ms STEP positions into the vj_* workspace; a sampled row's positions under its own settings, each with the key its
+// The STEP tail behind a joint pass: lm_head of the Ms STEP positions into the joint workspace; a sampled row's positions under its own settings, each with the key its
 // step would use (the chains share one scratch: stream order); the accept launch with one workgroup per row (kernels/verify.h); one log-probability record per
 // produced token of a recording row; the records' read-back, queued
 static int step_tail(tgx_ctx* c, ContPass& cp, PrefillRoute lm_rt, const long long* d_ids) {
-  launch_lm_head_all(c, lm_rt, cp.Ms, nullptr, /*joint=*/true);
+  VerifyWs& w = c->verify_ws[VWS_JOINT];
+  launch_lm_head_all(c, lm_rt, cp.Ms, nullptr, &w);
   if (cp.any_processed) {      // the processed rows' positions (option verify.processors): the automaton walk, then the positions launch; the other rows get no workgroup
     std::vector<const long long*> in((size_t)cp.ns);
     for (int j = 0; j < cp.ns; j++) in[(size_t)j] = d_ids + cp.first[(size_t)j];
-    launch_logit_proc_positions(c, cp.ns, cp.rows.data(), cp.first.data(), cp.lens.data(), in.data(), cp.prc.data(), /*joint=*/true);
+    launch_logit_proc_positions(c, w, cp.ns, cp.rows.data(), cp.first.data(), cp.lens.data(), in.data(), cp.prc.data());
   }
   for (int j = 0; j < cp.ns; j++)
-    if (cp.smp[(size_t)j]) launch_sample_positions(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.cfg[(size_t)j], cp.first[(size_t)j], nullptr, cp.prc[(size_t)j]);
+    if (cp.smp[(size_t)j]) launch_sample_positions(c, {&w, cp.first[(size_t)j], j}, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.cfg[(size_t)j], nullptr, cp.prc[(size_t)j]);
   launch_verify_accept_rows(c, d_ids, cp.ns, cp.rows.data(), cp.first.data(), cp.nd.data(), cp.smp.data(), cp.prc.data());
   for (int j = 0; j < cp.ns; j++)
-    if (row_records(c, cp.rows[(size_t)j])) launch_logprobs_verify(c, cp.rows[(size_t)j], cp.lens[(size_t)j], cp.first[(size_t)j], j);
-  HIP_OK(c, hipMemcpyAsync(cp.rec.data(), c->vj_rec, (size_t)cp.ns * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
+    if (row_records(c, cp.rows[(size_t)j])) launch_logprobs_verify(c, {&w, cp.first[(size_t)j], j}, cp.rows[(size_t)j], cp.lens[(size_t)j]);
+  HIP_OK(c, hipMemcpyAsync(cp.rec.data(), w.rec, (size_t)cp.ns * sizeof(tgx::VerifyRecord), hipMemcpyDeviceToHost, c->stream));
   return TGX_OK;
 }
 // The attention form is the routine's one switch.  ATTN_KEY_SPLIT (tgx_verify_rows): the STEP sequences alone — the pass's first ns — with the key-split attention
@@ -2247,9 +2239,10 @@ static int joint_pass(tgx_ctx* c, ContPass& cp, ContAttn attn, PrefillRoute rt, 
   const bool mixed = attn == ATTN_MIXED;
   RaggedPass p = cp.view(/*steps_only=*/!mixed);
   const int n = p.n, ns = cp.ns;
-  if (ns) if (int rc = ensure_verify_rows_ws(c)) return rc;
+  VerifyWs& w = c->verify_ws[VWS_JOINT];
+  if (ns) if (int rc = ensure_verify_ws(c, w)) return rc;
   if (cp.any_sampled) if (int rc = vs_alloc(c)) return rc;
-  if (cp.any_processed) if (int rc = ensure_verify_proc_ws(c, /*joint=*/true)) return rc;
+  if (cp.any_processed) if (int rc = ensure_verify_proc_ws(c, w)) return rc;
   // the STEP positions' lm_head: on the tiled route the GEMV form would stream the lm_head weights once per FOUR positions (32 step rows: eight passes, measured
   // +0.8 ms on Llama-3.2-1B, profiles/advance_rows.txt); where the skinny route would take Ms rows by themselves, its one-pass form serves them from ws_x
   // (a pass of STEP sequences alone: rt is that route already)
@@ -2270,7 +2263,7 @@ static int joint_pass(tgx_ctx* c, ContPass& cp, ContAttn attn, PrefillRoute rt, 
   if (mixed) if (int rc = ensure_mix_ws(c, p)) return rc;
   long long* const d_ids = reinterpret_cast<long long*>(c->rg_buf + o_ids);
   p.ids = d_ids;
-  c->vf_pass_rows = 0;                             // the workspace changes hands
+  c->pass = {};                                    // the workspace changes hands
   if (c->kv_paged)                                 // the admissions' rows give their blocks back first
     for (int j = ns; j < n; j++) if (!cp.holds[(size_t)j]) kv_release_row(c, cp.rows[(size_t)j]);
   for (int j = 0; j < n; j++) (void)kv_ensure_blocks(c, cp.rows[(size_t)j], (long long)cp.past[(size_t)j] + cp.lens[(size_t)j]);      // cannot fail: counted (check_paged_room)
@@ -2287,7 +2280,7 @@ static int joint_pass(tgx_ctx* c, ContPass& cp, ContAttn attn, PrefillRoute rt, 
   if (int rc = finish_pass(c)) return rc;
   // ---- the host follows the device: the STEP rows from their records, the FEED rows as an admission / tgx_extend_row does
   if (int rc = follow_step_rows(c, cp, 0, ns, fn, out_ids, out_n, out_finish)) return rc;
-  c->vf_pass_rows = cp.Ms; c->vf_pass_joint = true;
+  c->pass = {&w, cp.Ms};
   if (mixed) { c->advance_last_form = 1; c->advance_last_tiles = target; }
   else { c->verify_last_form = 1; c->verify_last_splits = p.ext_ns; }
   for (int j = ns; j < n; j++) {
@@ -2305,19 +2298,20 @@ static int joint_pass(tgx_ctx* c, ContPass& cp, ContAttn attn, PrefillRoute rt, 
 
 // The STEP sequences of a pass behind their checks — all of tgx_verify_rows, and the STEP part of tgx_advance_rows' piecewise form.  Where a matrix-core route
 // takes the Ms positions: the joint pass with the key-split attention.  Else (fp32 storage, prefill.mfma 0, shapes the tile does not cover, Ms below the routes'
-// minimum) row by row: each row's own pass -> draws -> accept, bit for bit the one-row call; its positions' logits then join the call's in vj_logits:
+// minimum) row by row: each row's own pass -> draws -> accept, bit for bit the one-row call; its positions' logits then join the call's in the joint workspace:
 // verify.last_form 2
 static int verify_steps(tgx_ctx* c, ContPass& cp, const char* fn, int64_t* out_ids, int32_t* out_n, int32_t* out_finish) {
   const PrefillRoute rt = prefill_route(c, cp.Ms, cp.Ms);
   if (rt == ROUTE_SKINNY || rt == ROUTE_TILED) return joint_pass(c, cp, ATTN_KEY_SPLIT, rt, fn, out_ids, out_n, out_finish);
-  if (int rc = ensure_verify_rows_ws(c)) return rc;
+  VerifyWs& w = c->verify_ws[VWS_JOINT];
+  if (int rc = ensure_verify_ws(c, w)) return rc;
   const size_t V = (size_t)c->d.vocab;
   for (int j = 0; j < cp.ns; j++) {
     if (int rc = verify_row_run(c, cp, j, fn, out_ids, out_n, out_finish)) return rc;
-    HIP_OK(c, hipMemcpyAsync(c->vj_logits + (size_t)cp.first[(size_t)j] * V, c->vf_logits, (size_t)cp.lens[(size_t)j] * V * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_OK(c, hipMemcpyAsync(w.raw.logits + (size_t)cp.first[(size_t)j] * V, c->verify_ws[VWS_ROW].raw.logits, (size_t)cp.lens[(size_t)j] * V * 4, hipMemcpyDeviceToDevice, c->stream));
   }
   if (int rc = finish_pass(c)) return rc;
-  c->vf_pass_rows = cp.Ms; c->vf_pass_joint = true;
+  c->pass = {&w, cp.Ms};
   c->verify_last_form = 2;
   return TGX_OK;
 }
@@ -2418,8 +2412,8 @@ int tgx_advance_rows(tgx_ctx* c, int n, const int32_t* rows, const int32_t* kind
 // test / diagnostic use: the fp32 logits [M][V] of the last verify pass, while the workspace still holds them
 int tgx_read_pass_logits(tgx_ctx* c, float* out, int cap_rows, int32_t* out_rows) {
   if (!c || !out || !out_rows) return c ? set_err(c, TGX_ERR_INVALID, "null argument") : TGX_ERR_INVALID;
-  const int M = c->vf_pass_rows;
-  const float* const src = c->vf_pass_joint ? c->vj_logits : c->vf_logits;      // (a tgx_verify_rows joint pass: all its positions in call order)
+  const int M = c->pass.rows;
+  const float* const src = c->pass.ws ? c->pass.ws->raw.logits : nullptr;      // (a tgx_verify_rows joint pass: all its positions in call order)
   if (M < 1 || !src) return set_err(c, TGX_ERR_STATE, "no verify pass to read: the workspace holds none (no call yet, or another call has used it since)");
   if (cap_rows < M) return set_err(c, TGX_ERR_INVALID, "cap_rows %d below the pass's %d positions", cap_rows, M);
   HIP_OK(c, hipSetDevice(c->device));

@@ -4,7 +4,7 @@
 //   prefix_groups.h  the planner of the shared-prefix decode attention (option attn.shared_prefix): rows that map the same leading blocks — host-only, checked on a CPU
 //   kv_pool.h        KvPool: the paged cache's block bookkeeping (free list, per-block row counts, the table's host mirror) — host-only, checked on a CPU
 //   row_snapshot.h   the byte format of a row snapshot (tgx_save_row / tgx_restore_row): header, size formula, validation — host-only, checked on a CPU
-//   dev_mem.h        DevMem: the owner of every device allocation of the context (dev_alloc / dev_free / dev_grow below) — host-only, checked on a CPU
+//   dev_mem.h        DevMem: the owner of every device allocation of the context (dev_alloc / dev_alloc_group / dev_free / dev_grow below) — host-only, checked on a CPU
 //   decode.hip       batch-1..4 decode step: GEMV launches (kernels/gemv.h, oproj_sliced.h), lm_head, greedy finalize
 //   attn.hip         decode attention launches (kernels/attn_decode.h, attn_decode_mfma.h, attn_prefix.h)
 //   sampler.hip      Sampler::sample (kernels/sampler.h)
@@ -15,6 +15,8 @@
 //   decode_fp4.hip   the MXFP4 batch-1 GEMV instantiations and quantizer launches (kernels/gemv_fp4.h); decode.hip holds the packed and FP8 ones
 //   skinny_fp8.hip, skinny_fp4.hip   the skinny products on the FP8 / MXFP4 code streams (kernels/skinny_fp8.h, skinny_fp4.h)
 //   stream_launch.h  the launch templates those units share: the NX / fixed-point switch of a batch-1 stream kernel family, the skinny (epilogue, blocks) table
+// The speculative-decoding calls read "the logits of every position of a pass" out of a VerifyWs below: one instance for the one-row calls, one for the joint
+// ones; a launcher is handed a VerifySlice of either.
 // A gate_up / down / lm_head matrix has at most one stream form, recorded in its WeightStream below; every launcher selects on its `kind`.
 // One context = one GPU = one HIP stream; every call comes from one host thread.  There is NO CPU path in this library.
 #pragma once
@@ -178,6 +180,42 @@ struct RaggedPass {
   const tgx::MixItem *mix_split = nullptr, *mix_merge = nullptr;
   int n_mix_split = 0, n_mix_merge = 0, mix_slots = 0;
 };
+
+// ---- the workspaces of the speculative-decoding calls.  Every record is a first-use group of dev_alloc_group below: its members exist together or not at all
+// the hidden rows, logits and argmax partials (stride lm_grid) of N positions
+struct PosSlab {
+  float *x = nullptr, *logits = nullptr, *part_val = nullptr; int* part_idx = nullptr;
+  bool ready() const { return x != nullptr; }
+};
+// option verify.processors (kernels/logit_proc.h logit_proc_pos_kernel): the processed logits of N positions, their per-tile partials and automaton states
+struct ProcSlab {
+  float *logits = nullptr, *part_val = nullptr; int *part_idx = nullptr, *states = nullptr;
+  bool ready() const { return logits != nullptr; }
+};
+// the staged sampler's scratch and compacted lists [VERIFY_ROWS][vocab] of a verify pass's positions (the pass's, not the row's): one row's positions at a time,
+// the chains stream-ordered.  Its group's fourth buffer is the one-row workspace's `draws`
+struct SampPosWs {
+  tgx::SampScratch* scratch = nullptr; unsigned long long* list_comp = nullptr; float* list_v = nullptr;
+  bool ready() const { return scratch != nullptr; }
+};
+// "the logits of every position of a pass", and what the accept launch (kernels/verify.h) reads and leaves.  The context holds two (tgx_ctx::verify_ws):
+//   VWS_ROW    slots = VERIFY_ROWS: one row's pass — tgx_verify_row, _sampled, _tree, the row-by-row form of tgx_verify_rows, the group form of tgx_score_row.
+//              One record; `draws` comes with the sampler's group (vs_alloc): only a sampled row's call ever holds it
+//   VWS_JOINT  slots = VERIFY_POSITIONS: the joint pass of tgx_verify_rows / tgx_advance_rows — one record per named row, and the accept launch's argument table
+// raw (with rec, and the joint one's draws and args): ensure_verify_ws, by the first call that verifies; proc: ensure_verify_proc_ws, by the first that
+// verifies a processed row.  A context that never makes such a call holds none of it
+struct VerifyWs {
+  int slots = 0;
+  PosSlab raw;                                // [slots]: a route without a one-pass lm_head stages the hidden rows in raw.x, four to a pass over the weights
+  ProcSlab proc;                              // [slots]
+  int *rec = nullptr, *draws = nullptr;       // tgx::VerifyRecord per row; the sampled positions' ids [slots]
+  unsigned char* args = nullptr;              // VWS_JOINT: [max_batch] tgx::VerifyArgs
+  std::vector<unsigned char> args_host;       // ... and the host copy the upload reads
+  bool ready() const { return raw.ready(); }
+};
+enum { VWS_ROW = 0, VWS_JOINT = 1 };
+// one row's positions in a workspace: `first` is its first slot, rec_i its record.  A one-row call passes {&verify_ws[VWS_ROW], 0, 0}
+struct VerifySlice { VerifyWs* ws; int first, rec_i; };
 
 inline void* hip_dev_alloc(size_t bytes) { void* p = nullptr; return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr; }      // the library's two uses of the
 inline void hip_dev_free(void* p) { (void)hipFree(p); }                                                                         // device allocator: tgx_ctx::mem
@@ -355,7 +393,7 @@ struct tgx_ctx {
   long long* slab_acc = nullptr;   // [max_batch][hidden], resting at zero between layers
   // tgx_forward_rows: the call's buffer (the RaggedPass device tables, then the ids; one upload per call) and four staging rows for the lm_head of scattered target rows
   unsigned char* rg_buf = nullptr; size_t rg_bytes = 0;
-  float *rg_x = nullptr, *rg_logits = nullptr, *rg_part_val = nullptr; int* rg_part_idx = nullptr;
+  PosSlab rg_lm;
   // ---- tgx_extend_row / tgx_truncate_row (include/tgx.h)
   // option extend.attn_splits: the key-split attention of a continuation pass of <= 128 positions (kernels/attn_extend.h): -1 automatic, 0 never (the per-row prompt
   // attention with `past`), N >= 1 N splits (clamped to the key tiles).  Automatic: min(32, CUs / heads) splits once past + S exceeds extend_attn_min{64,128} (head_dim)
@@ -368,35 +406,20 @@ struct tgx_ctx {
   int extend_attn_splits = -1;
   int extend_attn_min64 = 512, extend_attn_min128 = 1024;
   float* ext_part = nullptr; size_t ext_part_bytes = 0;      // the splits' partials [ns][heads][attn_extend_part_vals][256] (kernels/attn_extend.h)
-  // ---- tgx_verify_row (include/tgx.h; kernels/verify.h): the M <= VERIFY_ROWS positions of a verify pass — their hidden rows (the routes without a one-pass
-  // lm_head stage them here, four to a pass over the weights), logits and argmax partials, and the record the accept launch leaves for the host.  Sized at first use
-  enum { VERIFY_ROWS = TGX_MAX_DRAFT + 1 };
-  float *vf_x = nullptr, *vf_logits = nullptr, *vf_part_val = nullptr; int *vf_part_idx = nullptr, *vf_rec = nullptr;
+  // ---- tgx_verify_row, tgx_verify_rows and their kin (include/tgx.h; kernels/verify.h): a one-row pass verifies M <= VERIFY_ROWS positions, a joint pass
+  // M <= VERIFY_POSITIONS positions of several rows; verify_ws[VWS_ROW / VWS_JOINT] (VerifyWs above) hold them.  `pass`: the workspace whose logits are the last
+  // verify pass's, and how many positions (tgx_read_pass_logits); rows 0: none, or another call has used the workspace since.
+  // Option verify.last_form (read-only): 0 no tgx_verify_rows yet, 1 the joint pass, 2 row by row
+  enum { VERIFY_ROWS = TGX_MAX_DRAFT + 1, VERIFY_POSITIONS = TGX_MAX_VERIFY_POSITIONS };
+  VerifyWs verify_ws[2] = {{VERIFY_ROWS}, {VERIFY_POSITIONS}};
+  struct PassHeld { const VerifyWs* ws = nullptr; int rows = 0; } pass;
+  SampPosWs vs;              // tgx_verify_row_sampled and every sampled STEP row: allocated by the first such call (vs_alloc)
   // tgx_verify_tree: the device tables of the pass's token tree, VT_* ints each slot of 16 (depth, parent position, the accepted path; the ancestor masks as 16-bit
   // words in the fourth).  Allocated by the first non-chain tree call
   enum { VT_DEPTH = 0, VT_PAR = 16, VT_PATH = 32, VT_ANC = 48, VT_INTS = 64 };
   int* vt_tab = nullptr;
-  int vf_pass_rows = 0;      // the positions of the verify pass whose logits vf_logits holds (tgx_read_pass_logits); 0: none, or another call has used the workspace since
-  // ... and tgx_verify_row_sampled on a sampled row: the staged sampler's scratch and compacted lists for the VERIFY_ROWS positions (the pass's, not the row's) and
-  // their draws.  Allocated by the first such call (vs_alloc): a context that never makes one holds none of it
-  tgx::SampScratch* vs_scratch = nullptr;
-  unsigned long long* vs_list_comp = nullptr;    // [VERIFY_ROWS][vocab]
-  float* vs_list_v = nullptr;
-  int* vs_draws = nullptr;                       // [VERIFY_ROWS]
-  // ---- tgx_verify_rows (include/tgx.h): the joint pass over M <= VERIFY_POSITIONS positions of several rows — the hidden rows, logits and argmax partials of every
-  // position, one record per named row, the sampled rows' draws, and the accept launch's per-row argument table.  Sized by the first call (ensure_verify_rows_ws):
-  // a context that never makes it holds none of it.  Option verify.last_form (read-only): 0 no call yet, 1 the joint pass, 2 row by row
-  enum { VERIFY_POSITIONS = TGX_MAX_VERIFY_POSITIONS };
-  float *vj_x = nullptr, *vj_logits = nullptr, *vj_part_val = nullptr; int *vj_part_idx = nullptr, *vj_rec = nullptr, *vj_draws = nullptr;
-  unsigned char* vj_args = nullptr;              // [max_batch] tgx::VerifyArgs
-  std::vector<unsigned char> vj_args_host;       // ... and the host copy the upload reads
-  bool vf_pass_joint = false;                    // vf_pass_rows counts positions of vj_logits (a tgx_verify_rows joint pass), not of vf_logits
-  // ---- option verify.processors (include/tgx.h; kernels/logit_proc.h logit_proc_pos_kernel): 1 lets the chain verify calls take rows with a logit processor on.
-  // The processed slab of the pass's positions with its per-tile partials and the positions' automaton states — VERIFY_ROWS slots for the one-row calls (vp_*),
-  // VERIFY_POSITIONS for the joint ones (vpj_*) — each allocated by the first call that verifies a processed row (ensure_verify_proc_ws)
+  // ---- option verify.processors (include/tgx.h): 1 lets the chain verify calls take rows with a logit processor on (VerifyWs::proc)
   int verify_processors = 0;
-  float *vp_logits = nullptr, *vp_part_val = nullptr; int *vp_part_idx = nullptr, *vp_states = nullptr;
-  float *vpj_logits = nullptr, *vpj_part_val = nullptr; int *vpj_part_idx = nullptr, *vpj_states = nullptr;
   int verify_last_form = 0, verify_last_splits = 0;      // ... and `verify.last_splits` (read-only): the key splits of the last joint pass's attention (0: unsplit)
   // ---- tgx_advance_rows (include/tgx.h): prompt chunks and live rows' steps in one ragged pass.  Option advance.attn_tiles: the tile target of the mixed attention
   // (kernels/attn_mixed.h; csrc/attn_worklist.h): 0 never split (the work-list form alone), N >= 1 query blocks of more than N key tiles are cut into ranges of <= N
@@ -495,6 +518,12 @@ int dev_alloc(tgx_ctx* c, T** p, size_t n) {
   *p = static_cast<T*>(c->mem.alloc(n * sizeof(T)));
   return *p ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "dev_alloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(hipPeekAtLastError()));
 }
+// a first-use group: dev_alloc_group(c, {dev_buf(&a, n_a), dev_buf(&b, n_b), ...}) serves every member (n elements each) in order, or none of them — on failure
+// every pointer is nullptr and c->mem holds what it held (DevMem::alloc_group), so a later call starts over
+template <typename T> DevMem::Want dev_buf(T** p, size_t n) { return DevMem::Want{reinterpret_cast<void**>(p), n * sizeof(T)}; }
+inline int dev_alloc_group(tgx_ctx* c, std::initializer_list<DevMem::Want> g) {
+  return c->mem.alloc_group(g.begin(), g.size()) ? TGX_OK : set_err(c, TGX_ERR_DEVICE, "dev_alloc of a group of %zu buffers failed: %s", g.size(), hipGetErrorString(hipPeekAtLastError()));
+}
 template <typename T> void dev_free(tgx_ctx* c, T** p) { c->mem.release(*p); *p = nullptr; }
 template <typename T>
 int dev_grow(tgx_ctx* c, T** p, size_t* bytes, size_t need) {
@@ -525,7 +554,7 @@ int launch_layer_kernel(tgx_ctx* c, RowState* rv, int R, int l, int cls, float* 
 void launch_layers(tgx_ctx* c, RowState* rv, int R, long long kv_stride);
 void launch_layers(tgx_ctx* c, int row0, int R);
 void launch_lm_head(tgx_ctx* c, int row0, int R);
-void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_val, int* part_idx, int R);   // R rows at row strides from these pointers
+void launch_lm_head_at(tgx_ctx* c, const PosSlab& s, size_t pos0, int R);   // R positions of the slab from pos0, at row strides
 tgx::FinalizeArgs make_finalize_args(tgx_ctx* c, int row, bool advance_pos, bool log_step);
 void launch_finalize_greedy(tgx_ctx* c, int row0, int R, bool advance_pos, bool log_step);   // one finalize_greedy launch per row
 void launch_finalize_rows(tgx_ctx* c, int row0, int M);                                     // the batched step's greedy finalize (+ step counter)
@@ -533,15 +562,15 @@ void launch_embed_chunk(tgx_ctx* c, const long long* ids, int R, int pos0);
 void launch_add_pos(tgx_ctx* c, int* pos, int n);
 void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_val, int* part_idx);
 void launch_verify_first_id(tgx_ctx* c, int row);         // tgx_verify_row: prompt[0] of the row <- its current token
-void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws = nullptr, bool processed = false);    // (processed: g[i] from the vp_* partials, the history and state committed) ... and the accept launch over the M positions in the vf_* workspace (kernels/verify.h); draws: the positions' sampled ids
-// tgx_verify_rows, the joint pass: sequence i = row rows[i], M_i = n_draft[i] + 1 positions at slice first[i] of the vj_* workspace and of the pass's ids
+void launch_verify_accept(tgx_ctx* c, int row, int M, bool sampled, bool processed = false);    // ... and the accept launch over the M positions in the one-row workspace (kernels/verify.h); sampled: against the positions' draws; processed: g[i] from the processed slab's partials, the history and state committed
+// tgx_verify_rows, the joint pass: sequence i = row rows[i], M_i = n_draft[i] + 1 positions at slice first[i] of the joint workspace and of the pass's ids
 void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows, const int* first);          // ids[first[i]] <- row rows[i]'s current token, one launch
-void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled, const char* processed = nullptr);   // one workgroup per row -> vj_rec[i]; processed[i]: row i chooses from the vpj_* slab and commits its history and state
-// tgx_verify_tree: the walk over a token tree (draws as above; vt_tab holds the tree's tables) -> vf_rec and the accepted path; then the accepted branch's K / V rows
+void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled, const char* processed = nullptr);   // one workgroup per row -> record i; processed[i]: row i chooses from the processed slab and commits its history and state
+// tgx_verify_tree: the walk over a token tree (sampled as above; vt_tab holds the tree's tables) -> the one-row record and the accepted path; then the accepted branch's K / V rows
 // of every layer from slot past + path[j] to slot past + j (kernels/kv_tree.h), stream-ordered behind the walk: path and count are read on the device
-void launch_verify_accept_tree(tgx_ctx* c, int row, int M, const int* draws);
+void launch_verify_accept_tree(tgx_ctx* c, int row, int M, bool sampled);
 void launch_kv_tree_compact(tgx_ctx* c, int row, int M, int past);
-size_t verify_args_bytes();                                // one entry of the accept launch's table (vj_args)
+size_t verify_args_bytes();                                // one entry of the accept launch's table (VerifyWs::args)
 // ---- attn.hip (kernels/attn_decode.h, attn_decode_mfma.h)
 bool attn_batch_on_mfma(const tgx_ctx* c, int R);
 void launch_attn(tgx_ctx* c, const tgx::AttnArgs& a, int R, bool combine = true);   // combine = false: the caller's o_proj merges the split records
@@ -556,13 +585,13 @@ int row_union_of(const tgx_ctx* c);
 void launch_probs(tgx_ctx* c, int row, const tgx_sampler_cfg& cfg, bool processed = false);
 int vs_alloc(tgx_ctx* c);                                                    // tgx_verify_row_sampled: the positions' sampler workspace, at first use
 int vs_rezero(tgx_ctx* c);                                                   // ... its scratch back to the zero state the chain expects (tgx_reset_cache; stream-ordered; a no-op without the workspace)
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first = -1, const int* depth = nullptr, bool processed = false);   // the uniform chain of the row's cfg over the M positions in the vf_* workspace -> vs_draws (nothing of the row changes); joint_first >= 0: over the row's slice of the vj_* workspace -> its slice of vj_draws
+void launch_sample_positions(tgx_ctx* c, VerifySlice s, int row, int M, const tgx_sampler_cfg& cfg, const int* depth = nullptr, bool processed = false);   // the uniform chain of the row's cfg over the M positions of its slice -> the slice's draws (nothing of the row changes)
 int proc_alloc(tgx_ctx* c);                                                  // the logit processors' buffers, at first use
 bool row_processed(const tgx_ctx* c, int row);                               // the row has a logit processor on (not while it is retired)
-int ensure_verify_proc_ws(tgx_ctx* c, bool joint);                          // the vp_* (one-row calls) or vpj_* (joint calls) workspace, at first use
+int ensure_verify_proc_ws(tgx_ctx* c, VerifyWs& w);                         // the workspace's processed slab, at first use
 // the processors over a verify pass's positions (option verify.processors): the automaton walk, then the positions launch, for the n STEP rows with processed[j]
-// set — row rows[j]'s lens[j] positions from workspace row first[j], its inputs at ids[j] on the device; joint: the vj_* / vpj_* workspace, else vf_* / vp_*
-void launch_logit_proc_positions(tgx_ctx* c, int n, const int* rows, const int* first, const int* lens, const long long* const* ids, const char* processed, bool joint);
+// set — row rows[j]'s lens[j] positions from row first[j] of workspace w, its inputs at ids[j] on the device
+void launch_logit_proc_positions(tgx_ctx* c, VerifyWs& w, int n, const int* rows, const int* first, const int* lens, const long long* const* ids, const char* processed);
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step);            // raw logits of rows [row0, row0 + R) -> the processed slab and partials (step: count the current tokens)
 // beam search (kernels/beam.h): the three launches of tgx_beam_select over rows[0 .. n) and the read-back of its record (the caller checked every argument); the
 // publish launch of tgx_beam_advance: row rows[j] takes tokens[j] as its current token and the next embedding at its position
@@ -571,7 +600,7 @@ void launch_beam_publish(tgx_ctx* c, int n, const int* rows, const int32_t* toke
 int sampler_alloc(tgx_ctx* c);
 int logprobs_alloc(tgx_ctx* c);                                              // the rings, counters and tile partials, at first use
 void launch_logprobs(tgx_ctx* c, int row0, int R, bool force);             // behind a step's publish: the rows that record and produced a token (force: tgx_sample_row)
-void launch_logprobs_verify(tgx_ctx* c, int row, int M, int joint_first = -1, int joint_i = 0);   // behind tgx_verify_row's accept launch: one record per produced token (joint_first >= 0: the row's slice of the vj_* workspace, its record vj_rec[joint_i])
+void launch_logprobs_verify(tgx_ctx* c, VerifySlice s, int row, int M);   // behind the accept launch: one record per produced token, from the row's slice and its record
 // ---- prefill.hip (kernels/prefill.h, gemm_dma.h)
 bool prefill_shapes_ok(const tgx_model_desc& d);
 int ensure_prefill_ws(tgx_ctx* c, int S);
@@ -618,7 +647,7 @@ bool decode_mfma_ok(const tgx_ctx* c);
 int ensure_skinny_ws(tgx_ctx* c, int rows);
 void launch_decode_step_mfma(tgx_ctx* c, int row0, int M, const tgx_sampler_cfg& cfg);
 void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const RaggedPass* rg = nullptr, const TreePass* tree = nullptr);   // past: as launch_prefill; rg: a ragged pass of rg->M rows (from position 0) instead of rows [row0, row0 + NB); tree (NB == 1, no rg): the S positions are a token tree's
-void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x = nullptr);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
+void launch_lm_head_skinny(tgx_ctx* c, int M, const PosSlab& out, float* x = nullptr);   // model.norm -> lm_head of ALL M rows of ws_x behind launch_prefill_skinny as ONE pass over the weights (the batched step's form) + their argmax partials (stride lm_grid)
 int skinny_set_attrs(tgx_ctx* c);
 // ---- decode_fp4.hip (kernels/gemv_fp4.h)
 namespace tgx { struct GemvArgs; }

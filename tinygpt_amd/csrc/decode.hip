@@ -431,16 +431,16 @@ void launch_layers(tgx_ctx* c, int row0, int R) { launch_layers(c, &c->rows[(siz
 // model.norm -> lm_head on the current position + per-workgroup argmax partials   (GPTModel.h:56-57)
 void launch_lm_head(tgx_ctx* c, int row0, int R) {
   RowState& r = c->rows[(size_t)row0];
-  launch_lm_head_at(c, r.x, r.logits, r.part_val, r.part_idx, R);
+  launch_lm_head_at(c, PosSlab{r.x, r.logits, r.part_val, r.part_idx}, 0, R);
 }
 
-void launch_lm_head_at(tgx_ctx* c, const float* x, float* logits, float* part_val, int* part_idx, int R) {
+void launch_lm_head_at(tgx_ctx* c, const PosSlab& s, size_t pos0, int R) {
   const tgx_model_desc& d = c->d;
   tgx::GemvArgs a{};
   fill_strides(c, a);
-  a.W = d.tied ? c->embed : c->lm_head; a.x = x; a.x_stride = d.hidden; a.norm_w = c->final_norm; a.eps = d.norm_eps;
+  a.W = d.tied ? c->embed : c->lm_head; a.x = s.x + pos0 * d.hidden; a.x_stride = d.hidden; a.norm_w = c->final_norm; a.eps = d.norm_eps;
   a.N = d.vocab; a.K = d.hidden; a.units = (d.vocab + 1) / 2; a.hd = 2;
-  a.logits = logits; a.part_val = part_val; a.part_idx = part_idx;
+  a.logits = s.logits + pos0 * d.vocab; a.part_val = s.part_val + pos0 * c->lm_grid; a.part_idx = s.part_idx + pos0 * c->lm_grid;
   if (c->gpt2) {   // ln_f -> wte^T (tied head, ModelGPT2.h:170-176)
     a.norm_b = c->final_norm_b;
     launch_gemv<tgx::PRO_LAYERNORM, tgx::EPI_LOGITS>(c, a, TGX_KERNEL_LMHEAD, R);
@@ -494,52 +494,50 @@ void launch_argmax_partials(tgx_ctx* c, const float* logits, int V, float* part_
 void launch_verify_first_id(tgx_ctx* c, int row) {
   hipLaunchKernelGGL(tgx::verify_first_id_kernel, dim3(1), dim3(64), 0, c->stream, c->rows[(size_t)row].prompt, (const int*)c->rows[(size_t)row].tok);
 }
-// ... and behind the pass and the M positions' lm_head, ONE launch accepts the draft's matching prefix and leaves the row as that many decode steps would
-// (draws: the positions' sampled ids, launch_sample_positions; nullptr: greedy)
-// what g[i] is chosen from, and the commit: the raw pair again and nothing; a processed row (option verify.processors): the processed slab's per-tile partials
-// from workspace row `first`, the row's history words and — with an automaton on — its slice of the positions' states
-static void verify_select(tgx_ctx* c, tgx::VerifyArgs& a, int row, bool processed, bool joint, size_t first) {
-  a.sel_part_val = a.part_val; a.sel_part_idx = a.part_idx; a.sel_part_stride = a.part_stride; a.sel_n_part = a.n_part;
-  if (!processed) return;
-  const size_t T = (size_t)((c->d.vocab + 1023) / 1024);
-  a.sel_part_val = (joint ? c->vpj_part_val : c->vp_part_val) + first * T; a.sel_part_idx = (joint ? c->vpj_part_idx : c->vp_part_idx) + first * T;
-  a.sel_part_stride = (long long)T; a.sel_n_part = (int)T;
-  a.hist = c->proc_hist + (size_t)row * c->d.vocab;
-  a.states = (c->row_req_host[(size_t)row].proc & tgx::PROC_AUTOMATON) ? (joint ? c->vpj_states : c->vp_states) + first : nullptr;
-}
-void launch_verify_accept(tgx_ctx* c, int row, int M, const int* draws, bool processed) {
-  if (processed && (!c->vp_states || !c->proc_hist)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
+// ... and behind the pass and the M positions' lm_head, ONE launch accepts the draft's matching prefix and leaves the row as that many decode steps would.
+// The arguments of one row's walk over its slice s of a workspace (ids: the pass's ids on the device, the row's inputs from s.first; M positions):
+// sampled: against the positions' draws (launch_sample_positions), else greedy.  What g[i] is chosen from, and the commit: the raw partials again and nothing;
+// a processed row (option verify.processors): the processed slab's per-tile partials, the row's history words and — with an automaton on — its slice of the
+// positions' states.  false: a buffer is missing (launch_fault says which)
+static bool verify_args(tgx_ctx* c, tgx::VerifyArgs& a, VerifySlice s, int row, int M, const long long* ids, bool sampled, bool processed) {
+  const VerifyWs& w = *s.ws;
+  if (!w.ready() || (sampled && !w.draws)) { c->launch_fault = "verification requested before its buffers exist"; return false; }
+  if (processed && (!w.proc.ready() || !c->proc_hist)) { c->launch_fault = "processed verification requested before its buffers exist"; return false; }
   RowState& r = c->rows[(size_t)row];
-  tgx::VerifyArgs a{};
-  a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
-  verify_select(c, a, row, processed, /*joint=*/false, 0);
-  a.logits = c->vf_logits; a.draft = r.prompt + 1; a.draws = draws;
+  const size_t f = (size_t)s.first, V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
+  a.part_val = w.raw.part_val + f * P; a.part_idx = w.raw.part_idx + f * P; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
+  a.sel_part_val = a.part_val; a.sel_part_idx = a.part_idx; a.sel_part_stride = a.part_stride; a.sel_n_part = a.n_part;
+  if (processed) {
+    const size_t T = (size_t)((c->d.vocab + 1023) / 1024);
+    a.sel_part_val = w.proc.part_val + f * T; a.sel_part_idx = w.proc.part_idx + f * T; a.sel_part_stride = (long long)T; a.sel_n_part = (int)T;
+    a.hist = c->proc_hist + (size_t)row * V;
+    a.states = (c->row_req_host[(size_t)row].proc & tgx::PROC_AUTOMATON) ? w.proc.states + f : nullptr;
+  }
+  a.logits = w.raw.logits + f * V; a.draft = ids + f + 1; a.draws = sampled ? w.draws + f : nullptr;
   a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
   a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
   a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
-  a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vf_rec);
+  a.rec = reinterpret_cast<tgx::VerifyRecord*>(w.rec) + s.rec_i;
+  return true;
+}
+void launch_verify_accept(tgx_ctx* c, int row, int M, bool sampled, bool processed) {
+  tgx::VerifyArgs a{};
+  if (!verify_args(c, a, {&c->verify_ws[VWS_ROW], 0, 0}, row, M, c->rows[(size_t)row].prompt, sampled, processed)) return;
   TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_kernel<DT>, dim3(1), dim3(256), 0, c->stream, a))
 }
 // ---- tgx_verify_tree: the walk over the token tree whose tables vt_tab holds (parent positions in, the accepted path out) ...
-void launch_verify_accept_tree(tgx_ctx* c, int row, int M, const int* draws) {
-  if (!c->vt_tab || !c->vf_rec || M > tgx::VERIFY_MAX_POS) { c->launch_fault = "tree verification requested before its buffers exist"; return; }
-  RowState& r = c->rows[(size_t)row];
+void launch_verify_accept_tree(tgx_ctx* c, int row, int M, bool sampled) {
+  if (!c->vt_tab || M > tgx::VERIFY_MAX_POS) { c->launch_fault = "tree verification requested before its buffers exist"; return; }
   tgx::VerifyTreeArgs t{};
-  tgx::VerifyArgs& a = t.v;
-  a.part_val = c->vf_part_val; a.part_idx = c->vf_part_idx; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = M;
-  verify_select(c, a, row, /*processed=*/false, /*joint=*/false, 0);
-  a.logits = c->vf_logits; a.draft = r.prompt + 1; a.draws = draws;
-  a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + row;
-  a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
-  a.embed = c->embed; a.wpe = nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
-  a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vf_rec);
+  if (!verify_args(c, t.v, {&c->verify_ws[VWS_ROW], 0, 0}, row, M, c->rows[(size_t)row].prompt, sampled, /*processed=*/false)) return;
+  t.v.wpe = nullptr;      // (no GPT-2 on the tree's route)
   t.par = c->vt_tab + tgx_ctx::VT_PAR; t.path = c->vt_tab + tgx_ctx::VT_PATH;
   TGX_DT16_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_tree_kernel<DT>, dim3(1), dim3(256), 0, c->stream, t))
 }
 // ... and behind it the accepted branch's K / V rows into place (kernels/kv_tree.h): one workgroup per (layer, kv head, K | V)
 void launch_kv_tree_compact(tgx_ctx* c, int row, int M, int past) {
   const tgx_model_desc& d = c->d;
-  if (!c->vt_tab || !c->vf_rec || M > tgx::VERIFY_MAX_POS || d.head_dim % 8 != 0 || (tgx::VERIFY_MAX_POS - 1) * (d.head_dim / 8) > 256 || past + M > d.max_ctx) {
+  if (!c->vt_tab || !c->verify_ws[VWS_ROW].ready() || M > tgx::VERIFY_MAX_POS || d.head_dim % 8 != 0 || (tgx::VERIFY_MAX_POS - 1) * (d.head_dim / 8) > 256 || past + M > d.max_ctx) {
     c->launch_fault = "kv_tree_compact: the pass does not fit the launch (at most 16 positions, head_dim <= 128)"; return;
   }
   RowState& r = c->rows[(size_t)row];
@@ -547,7 +545,7 @@ void launch_kv_tree_compact(tgx_ctx* c, int row, int M, int past) {
   a.k = reinterpret_cast<bf16_t*>(r.kcache); a.v = reinterpret_cast<bf16_t*>(r.vcache);
   a.layer_stride = (long long)(c->kv_paged ? (size_t)c->kv.n_blocks() * d.kv_heads * tgx::KV_BLOCK : (size_t)d.kv_heads * d.max_ctx) * d.head_dim;
   a.tbl = c->kv_paged ? r.tbl : nullptr;
-  a.path = c->vt_tab + tgx_ctx::VT_PATH; a.rec = reinterpret_cast<const tgx::VerifyRecord*>(c->vf_rec);
+  a.path = c->vt_tab + tgx_ctx::VT_PATH; a.rec = reinterpret_cast<const tgx::VerifyRecord*>(c->verify_ws[VWS_ROW].rec);
   a.kv_heads = d.kv_heads; a.hd = d.head_dim; a.max_ctx = d.max_ctx; a.past = past; a.M = M;
   hipLaunchKernelGGL(tgx::kv_tree_compact_kernel, dim3(d.layers * d.kv_heads, 2), dim3(256), 0, c->stream, a);
 }
@@ -559,27 +557,17 @@ void launch_verify_first_ids(tgx_ctx* c, long long* ids, int n, const int* rows,
 }
 void launch_verify_accept_rows(tgx_ctx* c, const long long* ids, int n, const int* rows, const int* first, const int* n_draft, const char* sampled, const char* processed) {
   static_assert(sizeof(tgx::VerifyArgs) % 8 == 0, "the table's entries hold pointers");
-  if (!c->vj_args || !c->vj_rec || n > tgx::VERIFY_MAX_ROWS) { c->launch_fault = "joint verification requested before its buffers exist"; return; }
-  const size_t V = (size_t)c->d.vocab, P = (size_t)c->lm_grid;
-  c->vj_args_host.resize((size_t)n * sizeof(tgx::VerifyArgs));      // (the context's: it outlives the upload)
-  tgx::VerifyArgs* tab = reinterpret_cast<tgx::VerifyArgs*>(c->vj_args_host.data());
+  VerifyWs& w = c->verify_ws[VWS_JOINT];
+  if (!w.ready() || n > tgx::VERIFY_MAX_ROWS) { c->launch_fault = "joint verification requested before its buffers exist"; return; }
+  w.args_host.resize((size_t)n * sizeof(tgx::VerifyArgs));      // (the context's: it outlives the upload)
+  tgx::VerifyArgs* tab = reinterpret_cast<tgx::VerifyArgs*>(w.args_host.data());
   for (int i = 0; i < n; i++) {
-    RowState& r = c->rows[(size_t)rows[i]];
-    const size_t f = (size_t)first[i];
     tgx::VerifyArgs a{};
-    a.part_val = c->vj_part_val + f * P; a.part_idx = c->vj_part_idx + f * P; a.part_stride = c->lm_grid; a.n_part = c->lm_grid; a.M = n_draft[i] + 1;
-    const bool proc = processed && processed[i];
-    if (proc && (!c->vpj_states || !c->proc_hist)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
-    verify_select(c, a, rows[i], proc, /*joint=*/true, f);
-    a.logits = c->vj_logits + f * V; a.draft = ids + f + 1; a.draws = sampled[i] ? c->vj_draws + f : nullptr;
-    a.tok = r.tok; a.pos = r.pos; a.req = c->row_req + rows[i];
-    a.row_logits = r.logits; a.row_part_val = r.part_val; a.row_part_idx = r.part_idx; a.x = r.x;
-    a.embed = c->embed; a.wpe = c->gpt2 ? c->wpe : nullptr; a.H = c->d.hidden; a.V = c->d.vocab; a.n_pos = c->d.n_positions > 0 ? c->d.n_positions : 1;
-    a.rec = reinterpret_cast<tgx::VerifyRecord*>(c->vj_rec) + i;
+    if (!verify_args(c, a, {&w, first[i], i}, rows[i], n_draft[i] + 1, ids, sampled[i], processed && processed[i])) return;
     tab[i] = a;
   }
-  if (hipMemcpyAsync(c->vj_args, tab, (size_t)n * sizeof(tgx::VerifyArgs), hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->launch_fault = "joint verification: the argument table's upload failed"; return; }
-  TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_rows_kernel<DT>, dim3(n), dim3(256), 0, c->stream, reinterpret_cast<const tgx::VerifyArgs*>(c->vj_args)))
+  if (hipMemcpyAsync(w.args, tab, (size_t)n * sizeof(tgx::VerifyArgs), hipMemcpyHostToDevice, c->stream) != hipSuccess) { c->launch_fault = "joint verification: the argument table's upload failed"; return; }
+  TGX_DT_SWITCH(c->dt, hipLaunchKernelGGL(tgx::verify_accept_rows_kernel<DT>, dim3(n), dim3(256), 0, c->stream, reinterpret_cast<const tgx::VerifyArgs*>(w.args)))
 }
-// the size of one entry of the accept launch's table, for the workspace (abi.hip ensure_verify_rows_ws)
+// the size of one entry of the accept launch's table, for the workspace (abi.hip ensure_verify_ws)
 size_t verify_args_bytes() { return sizeof(tgx::VerifyArgs); }

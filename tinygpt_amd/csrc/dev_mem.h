@@ -1,4 +1,4 @@
-// dev_mem.h — the owner of a context's device allocations: every buffer is handed out by alloc / grow and recorded (pointer, bytes), so that destroying the context
+// dev_mem.h — the owner of a context's device allocations: every buffer is handed out by alloc / alloc_group / grow and recorded (pointer, bytes), so that destroying the context
 // needs no list of names (release_all) and "grow a workspace" is written once.  Host-only — the standard library alone, no HIP: ctx.h binds it to hipMalloc /
 // hipFree, tests/dev_mem_check.cpp drives it on a CPU with malloc / free.  No sub-allocation, no pooling: one alloc is one call of the bound allocator.
 #pragma once
@@ -34,6 +34,18 @@ class DevMem {
     *p = alloc(need);
     *have = *p ? need : 0;
     return *p != nullptr;
+  }
+  // a group of n buffers that exist together or not at all: g[i] is served into *g[i].p by one request of g[i].bytes, in order.  false: a request was refused —
+  // what this call was given is released, newest first, every *g[i].p is nullptr and the record is what it was before the call.  (Every *g[i].p is nullptr
+  // on entry: a group is allocated once, by the caller that found it missing)
+  struct Want { void** p; size_t bytes; };
+  bool alloc_group(const Want* g, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+      if ((*g[i].p = alloc(g[i].bytes))) continue;
+      while (i > 0) { i--; release(*g[i].p); *g[i].p = nullptr; }
+      return false;
+    }
+    return true;
   }
   void release_all() {      // newest first
     for (size_t i = recs.size(); i > 0; i--) free_fn(recs[i - 1].p);

@@ -100,46 +100,43 @@ void launch_sample(tgx_ctx* c, int row0, int R, const tgx_sampler_cfg& cfg, bool
   launch_chain(c, samp_args(c, row0, cfg, processed), cfg, R, pa, /*positions=*/false);
 }
 
-// tgx_verify_row_sampled: the M positions of row `row`'s verify pass ride on blockIdx.y of the uniform chain of the row's cfg, over the pass's logits and argmax
-// partials (vf_*) with a scratch and lists of their own (vs_*).  The end of the chain draws every position with the row's seed and the key of the token that
-// position produces (kernels/common.h draw_key) into vs_draws and publishes nothing: the accept launch decides what the row takes
+// tgx_verify_row_sampled: the M positions of row `row`'s verify pass ride on blockIdx.y of the uniform chain of the row's cfg, over the logits and argmax
+// partials of its slice of a verify workspace, with a scratch and lists of their own (c->vs).  The end of the chain draws every position with the row's seed and
+// the key of the token that position produces (kernels/common.h draw_key) into the slice's draws and publishes nothing: the accept launch decides what the row takes
 int vs_alloc(tgx_ctx* c) {
-  if (c->vs_draws) return TGX_OK;            // the last of the four: set only when all of them exist
+  if (c->vs.ready()) return TGX_OK;
   const size_t R = tgx_ctx::VERIFY_ROWS, V = (size_t)c->d.vocab;
-  int rc;
-  if ((rc = dev_alloc(c, &c->vs_scratch, R)) || (rc = dev_alloc(c, &c->vs_list_comp, R * V)) || (rc = dev_alloc(c, &c->vs_list_v, R * V)) || (rc = dev_alloc(c, &c->vs_draws, R))) {
-    dev_free(c, &c->vs_scratch); dev_free(c, &c->vs_list_comp); dev_free(c, &c->vs_list_v); dev_free(c, &c->vs_draws);      // all or nothing, as proc_alloc
-    return rc;
-  }
+  if (int rc = dev_alloc_group(c, {dev_buf(&c->vs.scratch, R), dev_buf(&c->vs.list_comp, R * V), dev_buf(&c->vs.list_v, R * V), dev_buf(&c->verify_ws[VWS_ROW].draws, R)})) return rc;
   return vs_rezero(c);      // (the chain's launches leave it zero again)
 }
 int vs_rezero(tgx_ctx* c) {
-  if (c->vs_scratch) HIP_OK(c, hipMemsetAsync(c->vs_scratch, 0, sizeof(tgx::SampScratch) * (size_t)tgx_ctx::VERIFY_ROWS, c->stream));
+  if (c->vs.ready()) HIP_OK(c, hipMemsetAsync(c->vs.scratch, 0, sizeof(tgx::SampScratch) * (size_t)tgx_ctx::VERIFY_ROWS, c->stream));
   return TGX_OK;
 }
 
-void launch_sample_positions(tgx_ctx* c, int row, int M, const tgx_sampler_cfg& cfg, int joint_first, const int* depth, bool processed) {
-  const bool joint = joint_first >= 0;      // tgx_verify_rows: the row's slice of the joint pass's workspace; the scratch and lists are the one-row call's (chains are stream-ordered)
-  if (!c->vs_draws || !(joint ? c->vj_draws : c->vf_rec) || M > (int)tgx_ctx::VERIFY_ROWS) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
+void launch_sample_positions(tgx_ctx* c, VerifySlice s, int row, int M, const tgx_sampler_cfg& cfg, const int* depth, bool processed) {
+  const VerifyWs& w = *s.ws;      // (a joint pass's rows share the one scratch and lists: their chains are stream-ordered)
+  if (!c->vs.ready() || !w.ready() || !w.draws || M > (int)tgx_ctx::VERIFY_ROWS) { c->launch_fault = "sampled verification requested before its buffers exist"; return; }
   const int V = c->d.vocab;
+  const size_t f = (size_t)s.first;
   tgx::SampArgs a{};
-  a.logits = joint ? c->vj_logits + (size_t)joint_first * V : c->vf_logits; a.logits_stride = V;
-  a.part_val = joint ? c->vj_part_val + (size_t)joint_first * c->lm_grid : c->vf_part_val; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
+  a.logits = w.raw.logits + f * V; a.logits_stride = V;
+  a.part_val = w.raw.part_val + f * c->lm_grid; a.part_stride = c->lm_grid; a.n_part = c->lm_grid;
   if (processed) {      // option verify.processors: the row's positions in the processed slab (launch_logit_proc_positions ran ahead) and its per-tile maxima
-    if (!(joint ? c->vpj_states : c->vp_states)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
+    if (!w.proc.ready()) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
     const int T = proc_tiles(c);
-    a.logits = joint ? c->vpj_logits + (size_t)joint_first * V : c->vp_logits;
-    a.part_val = joint ? c->vpj_part_val + (size_t)joint_first * T : c->vp_part_val; a.part_stride = T; a.n_part = T;
+    a.logits = w.proc.logits + f * V;
+    a.part_val = w.proc.part_val + f * T; a.part_stride = T; a.n_part = T;
   }
-  a.sc = c->vs_scratch;
+  a.sc = c->vs.scratch;
   a.V = V; a.idx_bits = 1;
   while ((1 << a.idx_bits) < V) a.idx_bits++;
   a.temperature = cfg.temperature; a.top_k = cfg.top_k; a.top_p = cfg.top_p; a.min_p = cfg.min_p;
-  a.list_comp = c->vs_list_comp; a.list_v = c->vs_list_v;
+  a.list_comp = c->vs.list_comp; a.list_v = c->vs.list_v;
   a.z_from_tail = ((cfg.top_k > 0 || cfg.top_p < 1.f) && !(cfg.min_p > 0.f)) ? 1 : 0;
   tgx::SampPickArgs pa{};
   pa.fin.pos = c->rows[(size_t)row].pos; pa.fin.req = c->row_req + row; pa.fin.row = row;      // the key's words: read, never written
-  pa.draws = joint ? c->vj_draws + joint_first : c->vs_draws;
+  pa.draws = w.draws + f;
   pa.depth = depth;      // (tgx_verify_tree: the device depth table of the pass's positions)
   launch_chain(c, a, cfg, M, pa, /*positions=*/true);
 }
@@ -231,59 +228,47 @@ static_assert(tgx::PROC_MAX_BIAS == TGX_MAX_LOGIT_BIAS && tgx::PROC_TILE == tgx:
 bool row_processed(const tgx_ctx* c, int row) { return c->row_req_host[(size_t)row].proc != 0 && !c->row_host[(size_t)row].idle; }
 
 int proc_alloc(tgx_ctx* c) {
-  if (c->proc_part_idx) return TGX_OK;       // the last of the six: set only when all of them exist
+  if (c->proc_hist) return TGX_OK;
   const size_t B = (size_t)c->d.max_batch, V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
-  int rc;
-  if ((rc = dev_alloc(c, &c->proc_hist, B * V)) || (rc = dev_alloc(c, &c->proc_bias_ids, B * tgx::PROC_MAX_BIAS)) || (rc = dev_alloc(c, &c->proc_bias_val, B * tgx::PROC_MAX_BIAS)) ||
-      (rc = dev_alloc(c, &c->proc_logits, B * V)) || (rc = dev_alloc(c, &c->proc_part_val, B * T)) || (rc = dev_alloc(c, &c->proc_part_idx, B * T))) {
-    // all or nothing: a later attempt starts over instead of allocating over live pointers (dev_free of a null pointer is a no-op)
-    dev_free(c, &c->proc_hist); dev_free(c, &c->proc_bias_ids); dev_free(c, &c->proc_bias_val); dev_free(c, &c->proc_logits); dev_free(c, &c->proc_part_val); dev_free(c, &c->proc_part_idx);
-    return rc;
-  }
+  if (int rc = dev_alloc_group(c, {dev_buf(&c->proc_hist, B * V), dev_buf(&c->proc_bias_ids, B * tgx::PROC_MAX_BIAS), dev_buf(&c->proc_bias_val, B * tgx::PROC_MAX_BIAS),
+                                   dev_buf(&c->proc_logits, B * V), dev_buf(&c->proc_part_val, B * T), dev_buf(&c->proc_part_idx, B * T)})) return rc;
   HIP_OK(c, hipMemsetAsync(c->proc_hist, 0, B * V * sizeof(unsigned int), c->stream));
   return TGX_OK;
 }
 
 // ---- the processors over a verify pass's positions (kernels/logit_proc.h logit_proc_pos_kernel; option verify.processors)
 static_assert(tgx::PROC_MAX_POS == TGX_MAX_VERIFY_POSITIONS && (int)tgx_ctx::VERIFY_ROWS <= tgx::PROC_MAX_POS, "kernels/logit_proc.h");
-int ensure_verify_proc_ws(tgx_ctx* c, bool joint) {
-  float*& lg = joint ? c->vpj_logits : c->vp_logits; float*& pv = joint ? c->vpj_part_val : c->vp_part_val;
-  int*& pi = joint ? c->vpj_part_idx : c->vp_part_idx; int*& st = joint ? c->vpj_states : c->vp_states;
-  if (st) return TGX_OK;                     // the last of the four: set only when all of them exist
-  const size_t R = joint ? (size_t)tgx_ctx::VERIFY_POSITIONS : (size_t)tgx_ctx::VERIFY_ROWS, V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
-  int rc;
-  if ((rc = dev_alloc(c, &lg, R * V)) || (rc = dev_alloc(c, &pv, R * T)) || (rc = dev_alloc(c, &pi, R * T)) || (rc = dev_alloc(c, &st, R))) {
-    dev_free(c, &lg); dev_free(c, &pv); dev_free(c, &pi); dev_free(c, &st);      // all or nothing, as proc_alloc
-    return rc;
-  }
-  return TGX_OK;
+int ensure_verify_proc_ws(tgx_ctx* c, VerifyWs& w) {
+  ProcSlab& p = w.proc;
+  if (p.ready()) return TGX_OK;
+  const size_t R = (size_t)w.slots, V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
+  return dev_alloc_group(c, {dev_buf(&p.logits, R * V), dev_buf(&p.part_val, R * T), dev_buf(&p.part_idx, R * T), dev_buf(&p.states, R)});
 }
-void launch_logit_proc_positions(tgx_ctx* c, int n, const int* rows, const int* first, const int* lens, const long long* const* ids, const char* processed, bool joint) {
-  if (!c->proc_part_idx || !(joint ? c->vpj_states : c->vp_states) || !(joint ? c->vj_logits : c->vf_logits)) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
-  const int slots = joint ? (int)tgx_ctx::VERIFY_POSITIONS : (int)tgx_ctx::VERIFY_ROWS;
+void launch_logit_proc_positions(tgx_ctx* c, VerifyWs& ws, int n, const int* rows, const int* first, const int* lens, const long long* const* ids, const char* processed) {
+  if (!c->proc_hist || !ws.proc.ready() || !ws.ready()) { c->launch_fault = "processed verification requested before its buffers exist"; return; }
   tgx::AutoWalkArgs w{};
   tgx::LogitProcPosArgs a{};
   int np = 0;
   bool any_auto = false;
   for (int j = 0; j < n; j++) {
     if (!processed[j]) continue;
-    if (first[j] < 0 || lens[j] < 1 || lens[j] > (int)tgx_ctx::VERIFY_ROWS || first[j] + lens[j] > slots || np + lens[j] > tgx::PROC_MAX_POS) { c->launch_fault = "processed verification: a row's positions do not fit the workspace"; return; }
+    if (first[j] < 0 || lens[j] < 1 || lens[j] > (int)tgx_ctx::VERIFY_ROWS || first[j] + lens[j] > ws.slots || np + lens[j] > tgx::PROC_MAX_POS) { c->launch_fault = "processed verification: a row's positions do not fit the workspace"; return; }
     any_auto = any_auto || (c->row_req_host[(size_t)rows[j]].proc & tgx::PROC_AUTOMATON);
     w.r[w.n++] = tgx::AutoWalkRow{c->row_req + rows[j], ids[j], first[j], lens[j]};
     for (int i = 0; i < lens[j]; i++) a.pos[np++] = tgx::ProcPos{rows[j], i, first[j] + i, 0, ids[j]};
   }
   if (!np) return;
-  w.states = joint ? c->vpj_states : c->vp_states; w.V = c->d.vocab;
+  w.states = ws.proc.states; w.V = c->d.vocab;
   if (any_auto) hipLaunchKernelGGL(tgx::automaton_walk_kernel, dim3(1), dim3(tgx::PROC_MAX_POS), 0, c->stream, w);
-  a.logits = joint ? c->vj_logits : c->vf_logits;
+  a.logits = ws.raw.logits;
   a.req = c->row_req; a.hist = c->proc_hist; a.bias_ids = c->proc_bias_ids; a.bias_val = c->proc_bias_val; a.states = w.states;
-  a.out = joint ? c->vpj_logits : c->vp_logits; a.part_val = joint ? c->vpj_part_val : c->vp_part_val; a.part_idx = joint ? c->vpj_part_idx : c->vp_part_idx;
+  a.out = ws.proc.logits; a.part_val = ws.proc.part_val; a.part_idx = ws.proc.part_idx;
   a.V = c->d.vocab; a.n_tile = proc_tiles(c);
   hipLaunchKernelGGL(tgx::logit_proc_pos_kernel, dim3((unsigned)a.n_tile, (unsigned)np), dim3(tgx::PROC_WG), 0, c->stream, a);
 }
 
 void launch_logit_proc(tgx_ctx* c, int row0, int R, bool step) {
-  if (!c->proc_part_idx) { c->launch_fault = "logit processors requested before their buffers exist"; return; }
+  if (!c->proc_hist) { c->launch_fault = "logit processors requested before their buffers exist"; return; }
   const size_t V = (size_t)c->d.vocab, T = (size_t)proc_tiles(c);
   tgx::LogitProcArgs a{};
   a.logits = c->rows[(size_t)row0].logits; a.logits_stride = (long long)V;
@@ -302,9 +287,8 @@ static int lp_tiles(const tgx_ctx* c) { return (c->d.vocab + tgx::SAMP_TILE - 1)
 int logprobs_alloc(tgx_ctx* c) {
   if (c->lp_rows) return TGX_OK;
   const size_t B = (size_t)c->d.max_batch, rows = std::max<size_t>(B, tgx_ctx::VERIFY_ROWS), T = (size_t)lp_tiles(c);
-  int rc;
-  if ((rc = dev_alloc(c, &c->lp_ring, B * tgx::LP_RING)) || (rc = dev_alloc(c, &c->lp_tile_max, rows * T)) || (rc = dev_alloc(c, &c->lp_tile_sum, rows * T)) ||
-      (rc = dev_alloc(c, &c->lp_tile_keys, rows * T * tgx::LP_MAX)) || (rc = dev_alloc(c, &c->lp_rows, B))) return rc;
+  if (int rc = dev_alloc_group(c, {dev_buf(&c->lp_ring, B * tgx::LP_RING), dev_buf(&c->lp_tile_max, rows * T), dev_buf(&c->lp_tile_sum, rows * T),
+                                   dev_buf(&c->lp_tile_keys, rows * T * tgx::LP_MAX), dev_buf(&c->lp_rows, B)})) return rc;
   HIP_OK(c, hipMemsetAsync(c->lp_rows, 0, B * sizeof(tgx::LpRow), c->stream));
   return TGX_OK;
 }
@@ -331,13 +315,12 @@ void launch_logprobs(tgx_ctx* c, int row0, int R, bool force) {
   lp_launch(c, a, R);
 }
 
-void launch_logprobs_verify(tgx_ctx* c, int row, int M, int joint_first, int joint_i) {
-  if (!c->lp_rows) { c->launch_fault = "log-probabilities requested before their buffers exist"; return; }
-  const bool joint = joint_first >= 0;
+void launch_logprobs_verify(tgx_ctx* c, VerifySlice s, int row, int M) {
+  if (!c->lp_rows || !s.ws->ready()) { c->launch_fault = "log-probabilities requested before their buffers exist"; return; }
   tgx::LpArgs a = lp_args(c);
-  a.logits = joint ? c->vj_logits + (size_t)joint_first * c->d.vocab : c->vf_logits;
+  a.logits = s.ws->raw.logits + (size_t)s.first * c->d.vocab;
   a.req = c->row_req + row; a.st = c->lp_rows + row;
-  a.rec = joint ? reinterpret_cast<const tgx::VerifyRecord*>(c->vj_rec) + joint_i : reinterpret_cast<const tgx::VerifyRecord*>(c->vf_rec);
+  a.rec = reinterpret_cast<const tgx::VerifyRecord*>(s.ws->rec) + s.rec_i;
   a.tile_max = c->lp_tile_max; a.tile_sum = c->lp_tile_sum; a.tile_keys = c->lp_tile_keys;
   a.ring = c->lp_ring + (size_t)row * tgx::LP_RING;
   lp_launch(c, a, M);

@@ -474,21 +474,21 @@ void launch_prefill_skinny(tgx_ctx* c, int row0, int NB, int S, int past, const 
 
 // tgx_verify_row: the logits of every position of a skinny pass.  ws_x holds the M final residual rows; model.norm's 16-bit terms come from the row-wise launch and
 // the product is the batched decode step's lm_head (terms form), ONE pass over the weights for all M rows, then the rows' argmax partials
-void launch_lm_head_skinny(tgx_ctx* c, int M, float* logits, float* part_val, int* part_idx, float* x) {      // x: the M hidden rows (default: the first M of ws_x)
+void launch_lm_head_skinny(tgx_ctx* c, int M, const PosSlab& out, float* x) {      // x: the M hidden rows (default: the first M of ws_x); out: where their logits and partials go (out.x is not used)
   const tgx_model_desc& d = c->d;
   const int H = d.hidden, V = d.vocab;
   const ebyte* W = d.tied ? c->embed : c->lm_head;
   launch_norm_terms(c, x ? x : c->ws_x, c->final_norm, M, H, 0);
   const WeightStream* slm = rows_stream(c, c->slm, M);
   if (!rows_streams(c, slm, M, H) && ksplit_ok(c, M, V, H)) {
-    launch_ksplit(c, tgx::GEMM_STORE, W, logits, V, M, V, H);
+    launch_ksplit(c, tgx::GEMM_STORE, W, out.logits, V, M, V, H);
     rows_fallback(c, slm);
   } else {
     SkinnyCall lm;
-    lm.epi = tgx::GEMM_STORE; lm.W = W; lm.C = logits; lm.ldc = V; lm.M = M; lm.N = V; lm.K = H; lm.nt = 2; lm.asrc = 0; lm.a_hi = c->ws_ah; lm.a_lo = c->ws_al; lm.allow_split = false; lm.ws = slm;
+    lm.epi = tgx::GEMM_STORE; lm.W = W; lm.C = out.logits; lm.ldc = V; lm.M = M; lm.N = V; lm.K = H; lm.nt = 2; lm.asrc = 0; lm.a_hi = c->ws_ah; lm.a_lo = c->ws_al; lm.allow_split = false; lm.ws = slm;
     launch_skinny(c, lm);
   }
-  hipLaunchKernelGGL(tgx::argmax_partials_rows_kernel, dim3(std::min(c->lm_grid, std::max(1, (V / 4 + 255) / 256)), M), dim3(256), 0, c->stream, (const float*)logits, (long long)V, V, part_val, part_idx,
+  hipLaunchKernelGGL(tgx::argmax_partials_rows_kernel, dim3(std::min(c->lm_grid, std::max(1, (V / 4 + 255) / 256)), M), dim3(256), 0, c->stream, (const float*)out.logits, (long long)V, V, out.part_val, out.part_idx,
                      (long long)c->lm_grid, c->lm_grid);
 }
 

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Bit identity of the continuation calls (include/tgx.h: tgx_extend_row, tgx_score_row on a held row, tgx_verify_row, tgx_verify_row_sampled, tgx_verify_rows,
-tgx_advance_rows) between this build and another library of the same ABI — the parent commit's, when the calls' host side is refactored.
+"""Bit identity of the continuation calls (include/tgx.h: tgx_extend_row, tgx_score_row on a held row, tgx_verify_row, tgx_verify_row_sampled, tgx_verify_tree,
+tgx_verify_rows, tgx_advance_rows) between this build and another library of the same ABI — the parent commit's, when the calls' host side is refactored.
 
 One seeded script per configuration: Llama-3.2-1B bf16 with synthetic weights, on slabs and with kv.budget_tokens and extend.attn_splits set (the skinny and tiled routes, the key-split and
 the mixed attention), and the gpt2_hd64 fixture's geometry in fp32, as it is and with prefill.mfma 0 (the fp32 and by-steps routes; the row-by-row and piecewise forms: *.last_form 2).  The script runs twice, each
 time on a fresh context — the first pass finds the token row 3 produces in the tgx_verify_rows call, the second sets it as that row's stop id — and calls: extend_row of 3, 8 and a
 long run of ids; score_row on a held row, short and long; verify_row; verify_row_sampled; verify_rows with greedy and sampled rows, a row without a draft, a row recording
 log-probabilities and the row with the stop id; a decode step with that row retired; advance_rows with two STEPs, a FEED, a FEED_MORE into a new row and a FEED into
-the retired row; the closing FEED; four decode_rows steps.  After every call it dumps the returned ids and finish flags, the pass logits, every row's logits, the
+the retired row; the closing FEED; four decode_rows steps; verify_tree on a greedy and on a sampled row (a tree with two branches, and a chain-shaped one; where no skinny pass
+takes a tree the refusal's status is what is dumped); then, with verify.processors 1 and a penalty, a logit bias and an automaton on rows 0 and 1, verify_row, verify_row_sampled,
+verify_rows and advance_rows over them.  After every call it dumps the returned ids and finish flags, the pass logits, every row's logits, the
 lengths, kv.free_tokens, the log-probability ring of the recording row and the *.last_* options.
 
     python tools/continuation_identity.py [--parent-lib PATH] [--out FILE]
@@ -21,7 +23,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from tinygpt_amd import known_desc, synth
 from tinygpt_amd.desc import desc_from_hf_config
-from tinygpt_amd.ffi import ABI, ADV_FEED, ADV_FEED_MORE, ADV_STEP, GREEDY, Backend, Model, SamplerCfg, TgxError, product_backend
+from tinygpt_amd.ffi import ADV_FEED, ADV_FEED_MORE, ADV_STEP, GREEDY, Backend, Model, SamplerCfg, TgxError, product_backend
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--parent-lib", default="", help="a libtgx_mi355x.so of the parent commit, run beside this build's")
@@ -53,6 +55,15 @@ def gpt2_fp32(be, mfma):
     m = Model(d, be).load_synthetic(1234, 0.02).finalize()
     m.set_option("prefill.mfma", mfma)
     return m, dict(prompts=(20, 21, 33, 40), long=40, feed=9, more=17, admit=30)
+
+
+def auto_table(V):
+    """three states, each allowing all but every eleventh token: a mask that moves with the state"""
+    t = np.empty((3, V), np.uint16)
+    for s in range(3):
+        t[s] = (s + 1) % 3
+        t[s, (11 - s) % 11::11] = 0xFFFF
+    return t
 
 
 def script(m, sz, stop_tok, dump):
@@ -119,6 +130,32 @@ def script(m, sz, stop_tok, dump):
     for k, a in enumerate(out):
         dump(f"decode_rows [{k}]", a)
     snap("decode_rows")
+    # ---- tgx_verify_tree on row 4 (no processor, no log-probabilities), greedy and then sampled: two branches under the root, the first child the token the row's
+    # own logits choose, so that a greedy walk takes at least one node off the first slot; and a chain-shaped tree, which is verify_row_sampled's pass
+    for what, cfg in (("greedy", None), ("sampled", SAMPLED)):
+        if cfg:
+            m.set_row_sampler(4, cfg, 555)
+        best = int(np.argmax(m.logits(rounded=False)[4]))
+        other = ids(5, 90)
+        for shape, tokens, parent in (("tree", [(best + 1) % V, best] + other[:4], [-1, -1, 0, 0, 1, 1]), ("chain", other[:4], [-1, 0, 1, 2])):
+            try:
+                snap(f"verify_tree {what} {shape}", [m.verify_tree(4, tokens, parent)])
+            except TgxError as e:
+                dump(f"verify_tree {what} {shape} refused", np.asarray([e.status], np.int32))
+    # ---- rows with a logit processor on (option verify.processors): a penalty, a logit bias and an automaton on rows 0 (greedy) and 1 (sampled), through the one-row
+    # and the joint calls; row 2 (recording) rides in the joint ones unprocessed
+    m.set_option("verify.processors", 1)
+    aid = m.automaton_create(auto_table(V))
+    for r in (0, 1):
+        m.set_row_penalties(r, 1.3, 0.2, 0.1).set_row_logit_bias(r, {5: 2.0, 9: float("-inf"), V - 1: -1.5})
+        m.set_row_history(r, prompt_ids=ids(30, 60 + r), produced_ids=ids(6, 70 + r)).set_row_automaton(r, aid)
+    snap("processed verify_row", [m.verify_row(0, ids(5, 81))])
+    snap("processed verify_row_sampled", [m.verify_row_sampled(1, ids(7, 82))])
+    got = m.verify_rows([1, 2, 0], [ids(4, 83), ids(3, 84), ids(6, 85)])
+    recorded[0] += len(got[1][0])
+    snap("processed verify_rows", got)
+    snap("processed advance_rows", m.advance_rows([0, 4, 1], [ADV_STEP, ADV_FEED, ADV_STEP], [ids(3, 86), ids(sz["feed"], 87), ids(2, 88)]))
+    dump("automaton states", np.asarray([m.read_row_automaton(r)[1] for r in (0, 1)], np.int32))
     return tok3
 
 
@@ -133,7 +170,7 @@ def run(be, make, budget):
 
 lines, bad = [], 0
 mine = product_backend()
-parent = Backend(args.parent_lib, "tgx_", required=[n for n in ABI if n != "verify_tree"]) if args.parent_lib else None      # (the parent commit has no tgx_verify_tree)
+parent = Backend(args.parent_lib, "tgx_") if args.parent_lib else None
 for name, make, budget in (("Llama-3.2-1B bf16, slabs", llama, 0), ("Llama-3.2-1B bf16, kv.budget_tokens 4096, extend.attn_splits 4", llama, 4096), ("gpt2_hd64 geometry fp32", gpt2_fp32, 1), ("gpt2_hd64 geometry fp32, prefill.mfma 0", gpt2_fp32, 0)):
     a = run(mine, make, budget)
     h = hashlib.sha256()

@@ -163,7 +163,7 @@ def free_running(lines):
     same = res[0][0][1] == res[7][0][1]
     first_diff = next((i for i, (a, b) in enumerate(zip(res[0][0][1], res[7][0][1])) if a != b), None)
     lines.append("free-running generateSync, %d new tokens after a %d-token prompt (a 64-token span repeated), unpaged, whole call incl. prefill, ms: speculate 0 %s | speculate 7 %s" % (
-        n_new, med([r[0] for r in res[0]]), med([r[0] for r in res[7]])))
+        n_new, len(prompt), med([r[0] for r in res[0]]), med([r[0] for r in res[7]])))
     lines.append("  ids equal: %s%s" % ("yes" if same else "no", "" if same else " (first difference at new token %d: a step whose top-2 gap is inside the band between the kernel paths)" % first_diff))
     lines.append("  over the 3 speculate-7 runs: %d verify passes, %d of %d draft tokens accepted, %d ordinary steps; tokens produced per verify pass 1..16: %s" % (st[0], st[2], st[1], st[3], st[5:21]))
     e.close()
